@@ -5,9 +5,15 @@ One "step" = one batch of FRESH synthetic reads through the whole C-ABI boundary
 band, split, traceback schedule, on the device when the batch allows it -- and upload), sa_batch_run (forward,
 backward/posterior, fold, finalisation, result copy to the host), results read, sa_batch_destroy.  The next batch is created
 while the current one is on the GPU (sa_batch_start / sa_batch_wait), as a pipeline that sees every read once would do it;
-consecutive steps take different read sets.  The kernels-only rate on a planned, HBM-resident batch (what round 1
-reported as its headline) is measured first and reported beside it (config.kernels_only_resident_inputs); the roofline
-figures come from that phase's HIP-event times.
+consecutive steps take different read sets.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, the K
+timed steps, the result line.  `--full` adds everything measured beside it: the kernels-only rate on a planned, HBM-resident
+batch (what round 1 reported as its headline; config.kernels_only_resident_inputs) with the roofline figures from that
+phase's HIP-event times, serial cycles, the long steady-state run, the CPU baseline, the secondary legs (every other
+BASELINE config) and the scaling job, and writes the complete record beside the line (--full-record).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed seeded sample
+of the reads in full plus per-read summaries of all of them), so that two builds can be compared output for output.
 
 Workload at every N: BASELINE.json configs[1] per GPU -- R9.4 6-mer template Gaussian HMM, 2000 synthetic 5k-event reads,
 band (diagonal expansion) 50, threshold 0.01, traceBackDiagonals 100 -- i.e. weak scaling: reads are independent, each rank
@@ -35,6 +41,79 @@ MODEL = os.path.join(ROOT, "tests", "golden", "models", "testModelR9.4_450bps.nu
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 ALGO_BYTES_PER_CELL = 24.0     # 3 fp64 states of every band cell, written once, read once
 ISSUE_PEAK_VALU_PER_S = 1024 / 1.83e-9   # 256 CUs x 4 SIMDs, one fp64 VALU wave-instruction per 1.83 ns each (probes/issue_probe.hip)
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together at most this
+DUMP_SAMPLE_READS = 32         # reads whose results are written in full
+DUMP_SAMPLE_SEED = 0x5A11D0    # their choice: fixed, the same for every run with the same number of reads
+
+
+def dump_sample(n_jobs):
+    """The reads --dump-outputs writes in full: a fixed, seeded choice of DUMP_SAMPLE_READS job indices, in order."""
+    rng = np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED))
+    return np.sort(rng.choice(n_jobs, size=min(n_jobs, DUMP_SAMPLE_READS), replace=False))
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy (float32 or float64 only, DUMP_BUDGET_BYTES in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the budget of %d" % (total, DUMP_BUDGET_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def ragged_sample(n_jobs, parts):
+    """--dump-outputs of a per-job ragged output: parts(j) -> dict of 1-D/2-D arrays of job j.  Returns the sampled jobs'
+    arrays concatenated (float64) and their lengths."""
+    pick = dump_sample(n_jobs)
+    out = {"sample_reads": pick.astype(np.float64)}
+    rows = [parts(int(j)) for j in pick]
+    for name in (rows[0] if rows else {}):
+        out["sample_" + name] = np.concatenate([np.asarray(r[name], dtype=np.float64) for r in rows])
+    out["sample_rows_per_read"] = np.array([len(next(iter(r.values()))) for r in rows], dtype=np.float64)
+    return out
+
+
+def unpack_records(recs):
+    """The batch's packed result records (results_view: uint64 [n, 2] sa_pair16_t, or [n, 1] sa_pair8_t with --pairs8) as
+    the fields of sa_pair_t -- numpy restatement of sa_pair16_unpack / the sa_pair8_t layout in include/signalalign_hip.h."""
+    if recs.shape[1] == 1:
+        r = recs[:, 0]
+        return {"x": r & np.uint64(0xfffff), "y": (r >> np.uint64(20)) & np.uint64(0xfffff), "prob_e7": r >> np.uint64(40)}
+    a, b = recs[:, 0], recs[:, 1]
+    return {"x": a & np.uint64(0xfffffff), "y": (a >> np.uint64(28)) & np.uint64(0xfffffff),
+            "path": ((a >> np.uint64(56)) & np.uint64(0xff)) | (((b >> np.uint64(56)) & np.uint64(0xff)) << np.uint64(8)),
+            "kmer_id": b & np.uint64(0xffffffff), "prob_e7": (b >> np.uint64(32)) & np.uint64(0xffffff)}
+
+
+def batch_outputs(batch, n_jobs, first_buf):
+    """--dump-outputs of a finished pair-HMM batch (what sa_batch_pairs16_all hands its caller): per read the number of pairs
+    and the sum of their posteriors (every read), and every pair of the sampled reads (x, y, path, k-mer id as float32 --
+    exact below 2^24 --, posterior as float64), at most DUMP_BUDGET_BYTES / 2 of them."""
+    recs, first = batch.results_view(first_buf)
+    first = np.array(first[:n_jobs + 1], dtype=np.int64)
+    out = {"pairs_per_read": np.diff(first).astype(np.float64)}
+    # exact per-read sums of prob_e7 from a running integer sum over all records, in chunks
+    at = np.zeros(n_jobs + 1, dtype=np.int64)        # running sum at first[j]
+    base, chunk, total = 0, 1 << 24, int(first[-1])
+    for c0 in range(0, max(total, 1), chunk):
+        c1 = min(total, c0 + chunk)
+        cs = np.concatenate([[0], np.cumsum(unpack_records(recs[c0:c1])["prob_e7"].astype(np.int64))]) if c1 > c0 else np.zeros(1, np.int64)
+        sel = (first >= c0) & (first <= c1)
+        at[sel] = base + cs[first[sel] - c0]
+        base += int(cs[-1])
+    out["posterior_sum_per_read"] = np.diff(at).astype(np.float64) / 1e7
+    pick = dump_sample(n_jobs)
+    cap = (DUMP_BUDGET_BYTES // 2) // (4 * 4 + 8) // max(len(pick), 1)   # rows per sampled read at most
+    parts = [unpack_records(np.array(recs[first[j]:min(first[j + 1], first[j] + cap)])) for j in pick]
+    out["sample_reads"] = pick.astype(np.float64)
+    out["sample_rows_per_read"] = np.array([len(p["x"]) for p in parts], dtype=np.float64)
+    for name in ("x", "y", "path", "kmer_id"):
+        if name in parts[0]:
+            out["sample_" + name] = np.concatenate([p[name] for p in parts]).astype(np.float32)
+    out["sample_posterior"] = np.concatenate([p["prob_e7"] for p in parts]).astype(np.float64) / 1e7
+    return out
 
 
 def host_cpu_info():
@@ -150,7 +229,12 @@ def bench_event_align(args):
                                   "bandwidth 100" % (args.reads, args.events),
                       "kernel_ms": kms / K, "c_call_ms": cms / K, "kernel_cell_updates_per_s": cells / (kms / K * 1e-3),
                       "reads_aligned": int(sum(1 for o in out if o[2] == 0)), "cells_per_read": cells / max(len(jobs), 1)}}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:   # per read (k-mer index, event index) of the last step's alignment
+        d = {"status": np.array([o[2] for o in out], dtype=np.float64),
+             "path_length": np.array([len(o[0]) for o in out], dtype=np.float64)}
+        d.update(ragged_sample(len(out), lambda j: {"kmer_idx": out[j][0], "event_idx": out[j][1]}))
+        write_outputs(args.dump_outputs, d)
+    if args.full and not args.no_cpu_baseline:
         from oracle import sa_oracle_py as oracle          # the CPU restatement: timed here as the baseline, nothing else
         from concurrent.futures import ThreadPoolExecutor
         om = oracle.Model(alpha, k, t10, tab)
@@ -188,15 +272,17 @@ def bench_mea(args):
         pr = b.pairs(j)
         ev, rf, po, sh = sa.mea_params(pr["x"], pr["y"], np.round(pr["prob_e7"] / 1e7, 6))
         jobs.append(dict(event_idx=ev, ref_idx=rf, posterior=po, shortest=sh))
-    # the chained form: matrices built on the device from the pairs the batch left in HBM (sa_batch_mea)
-    cst = {}
-    for _ in range(max(args.warmup, 1)):
-        b.mea(stats=cst)
-    ckms = ccms = 0.0
-    for _ in range(args.steps):
-        chained = b.mea(stats=cst)
-        ckms += cst["kernel_ms"]
-        ccms += cst["call_ms"]
+    # --full: the chained form beside it, matrices built on the device from the pairs the batch left in HBM (sa_batch_mea)
+    chained, ckms, ccms = None, None, None
+    if args.full:
+        cst = {}
+        for _ in range(max(args.warmup, 1)):
+            b.mea(stats=cst)
+        ckms = ccms = 0.0
+        for _ in range(args.steps):
+            chained = b.mea(stats=cst)
+            ckms += cst["kernel_ms"]
+            ccms += cst["call_ms"]
     b.close()
     entries = float(sum(len(j["posterior"]) for j in jobs))
     stats = {}
@@ -216,12 +302,18 @@ def bench_mea(args):
            "config": {"workload": "maximum expected accuracy path (src/signalalign/mea_algorithm.py:25-264) over the posteriors "
                                   "of %d synthetic %d-event reads" % (args.reads, args.events),
                       "kernel_ms": kms / K, "c_call_ms": cms / K, "kernel_entries_per_s": entries / (kms / K * 1e-3),
-                      "chained_kernel_ms": ckms / K, "chained_c_call_ms": ccms / K,
-                      "chained_paths_found": int(sum(1 for o in chained if o[2] == 0)),
+                      "chained_kernel_ms": None if chained is None else ckms / K, "chained_c_call_ms": None if chained is None else ccms / K,
+                      "chained_paths_found": None if chained is None else int(sum(1 for o in chained if o[2] == 0)),
                       "entries_per_read": entries / max(len(jobs), 1),
                       "paths_found": int(sum(1 for o in out if o[2] == 0)),
                       "mean_path_length": float(np.mean([len(o[0]) for o in out]))}}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:   # per read the last step's path (ref, event), best sum, status and final forward edges
+        d = {"best_sum": np.array([o[1] for o in out], dtype=np.float64), "status": np.array([o[2] for o in out], dtype=np.float64),
+             "final_edges": np.array([o[3] for o in out], dtype=np.float64),
+             "path_length": np.array([len(o[0]) for o in out], dtype=np.float64)}
+        d.update(ragged_sample(len(out), lambda j: {"path": np.asarray(out[j][0]).reshape(-1, 2)}))
+        write_outputs(args.dump_outputs, d)
+    if args.full and not args.no_cpu_baseline:
         from oracle import sa_oracle_py as oracle          # the CPU restatement: timed here as the baseline, nothing else
         from concurrent.futures import ThreadPoolExecutor
         cores = min(os.cpu_count() or 1, 16)
@@ -269,8 +361,11 @@ def bench_expectations(args, compact=False):
     for _ in range(args.steps):
         trans, lik, _ = sa.expect_batch(pm, params, jobs, ambig=ambig)
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs and not compact:   # the last step's transition expectations and log-likelihoods, per read
+        write_outputs(args.dump_outputs, {"transition_expectations": np.asarray(trans, dtype=np.float64),
+                                          "log_likelihood": np.asarray(lik, dtype=np.float64)})
     dtg = float("nan")
-    if not compact:   # (the memory-resident checker kernels beside it)
+    if args.full and not compact:   # (--full: the memory-resident checker kernels beside it)
         tg0 = time.perf_counter()
         for _ in range(max(1, args.steps // 4)):
             sa.expect_batch(pm, params, jobs, ambig=ambig, flags=sa.FLAG_FORCE_GENERIC)
@@ -290,7 +385,7 @@ def bench_expectations(args, compact=False):
            "roofline": {"bound": "issue", "bound_of_the_formula": "hbm", "kernel": "k_bwd_ring<EXPECT>" if cpg else "k_bwd_fast_expect", "achieved": None,
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
                         "note": "whole-call rate; the per-kernel split is in profiles/ (rocprofv3 --kernel-trace --stats)"}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import sa_oracle_py as oracle          # the CPU restatement: timed here as the baseline, nothing else
         from concurrent.futures import ThreadPoolExecutor
         info = host_cpu_info()
@@ -540,29 +635,38 @@ def measure(args, ctx, compact=False):
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- phase 1 (not the headline): the kernels alone, on a batch whose plan and inputs are resident in HBM ----
+    # ---- phase 1 (not the headline; --full or --kernels-only): the kernels alone, on a batch whose plan and inputs are resident
+    # in HBM.  A plain run creates and runs that batch once only: the pipeline of phase 2 is sized from its storage and pairs ----
+    phase1 = args.full or args.kernels_only
+    dump_s = [0.0]     # --dump-outputs: host time spent collecting the last timed step's results (taken out of the timed region)
+    outputs = {}
     t_create = time.perf_counter()
     batch = sa.Batch(pm, params, arrays[0], ambig=ambig, device=device, flags=xflags)
     t_create = time.perf_counter() - t_create
     st0 = batch.stats()
     cells = st0.cells_forward + st0.cells_backward
-    KR = max(3, min(args.steps, 10))
-    for _ in range(max(1, min(args.warmup, 3))):
+    # (--kernels-only: the K steps asked for are the timed ones)
+    KR = max(1, args.steps) if args.kernels_only else max(3, min(args.steps, 10))
+    for _ in range(max(1, min(args.warmup, 3)) if phase1 else 1):
         batch.run()
-    t0 = time.perf_counter()
-    ms_f = ms_b = ms_fold = 0.0
-    for _ in range(KR):
-        batch.run()
-        s_ = batch.stats()
-        ms_f += s_.ms_forward
-        ms_b += s_.ms_backward
-        ms_fold += s_.ms_fold
-    dt_resident = (time.perf_counter() - t0) / KR
-    ms_f, ms_b, ms_fold = ms_f / KR, ms_b / KR, ms_fold / KR
+    ms_f = ms_b = ms_fold = dt_resident = None
+    if phase1:
+        t0 = time.perf_counter()
+        ms_f = ms_b = ms_fold = 0.0
+        for _ in range(KR):
+            batch.run()
+            s_ = batch.stats()
+            ms_f += s_.ms_forward
+            ms_b += s_.ms_backward
+            ms_fold += s_.ms_fold
+        dt_resident = (time.perf_counter() - t0) / KR
+        ms_f, ms_b, ms_fold = ms_f / KR, ms_b / KR, ms_fold / KR
     n_pairs = int(batch.results_view()[1][-1])
+    if args.kernels_only and args.dump_outputs and rank == 0:
+        outputs = batch_outputs(batch, len(jobs), np.zeros(len(jobs) + 1, dtype=np.int64))
     # what a caller pays who wants sa_pair_t rows instead of the packed records the step ends at: sa_batch_pairs_all (host threads)
     unpack_ms = None
-    if not compact and 0 < n_pairs < 5e7:
+    if phase1 and not compact and 0 < n_pairs < 5e7:
         from signalalign_amd._capi import PAIR_DTYPE
         rows_buf = np.empty(n_pairs, dtype=PAIR_DTYPE)
         t_u = []
@@ -579,7 +683,7 @@ def measure(args, ctx, compact=False):
     # SA_GROUPS=1 (profiles/r04_W_kernel_stats.csv) shows the same average duration.  (The eight result groups of the phase
     # above overlap pairwise on two streams; their stage time also holds fold / finalisation kernels of earlier groups.)
     single = None
-    if int(st0.n_groups) > int(st0.n_chunks) and not os.environ.get("SA_GROUPS"):
+    if phase1 and int(st0.n_groups) > int(st0.n_chunks) and not os.environ.get("SA_GROUPS"):
         os.environ["SA_GROUPS"] = "1"
         try:
             b1 = sa.Batch(pm, params, arrays[0], ambig=ambig, device=device, flags=xflags)
@@ -597,12 +701,12 @@ def measure(args, ctx, compact=False):
         single = {"ms_forward": f1 / K1, "ms_backward": bk1 / K1, "launches_per_pass": int(s1.n_groups) // max(int(s1.n_chunks), 1),
                   "passes": int(s1.n_chunks)}
         b1.close()
-    elif int(st0.n_groups) == int(st0.n_chunks):
+    elif phase1 and int(st0.n_groups) == int(st0.n_chunks):
         single = {"ms_forward": ms_f, "ms_backward": ms_b, "launches_per_pass": 1, "passes": int(st0.n_chunks)}
 
-    # serial cycles (median of five, outside the timed region): what a caller without overlap pays per batch in steady state
-    cycle = {"create": 0.0, "run": dt_resident * 1e3, "destroy": 0.0}
-    if not args.kernels_only:
+    # serial cycles (--full; median of five, outside the timed region): what a caller without overlap pays per batch in steady state
+    cycle = {"create": 0.0, "run": dt_resident * 1e3, "destroy": 0.0} if phase1 else None
+    if phase1 and not args.kernels_only:
         samples = []
         for q in range(1 if args.workload == "scaling" or compact else 5):
             tc0 = time.perf_counter()
@@ -658,7 +762,13 @@ def measure(args, ctx, compact=False):
                 "median_create_ms": round(med_c, 3), "median_wait_ms": round(med_w, 3),
                 "slowest": [{"ms": round(x[0], 2), "create_ms": round(x[1], 2), "wait_ms": round(x[2], 2)} for x in slow]}
 
-    def stream(n_steps, first, leave_next=False):
+    def collect(b_):
+        """--dump-outputs: the results of the last timed step, read before its batch is destroyed (host time not timed)"""
+        t_x = time.perf_counter()
+        outputs.update(batch_outputs(b_, len(jobs), np.zeros(len(jobs) + 1, dtype=np.int64)))
+        dump_s[0] += time.perf_counter() - t_x
+
+    def stream(n_steps, first, leave_next=False, on_last=None):
         flying = []
         if depth == 1:
             # one batch at a time on the device (its forward storage takes most of the card): the next batch's reads are
@@ -688,6 +798,8 @@ def measure(args, ctx, compact=False):
                 groups_seen[0] = int(stc.n_groups)
                 pairs_seen[0] += int(cur.results_view(first_buf)[1][-1])
                 done_at.append(time.perf_counter())
+                if on_last is not None and s == n_steps - 1:
+                    on_last(cur)
                 cur.close()
                 if dbg:
                     print("[bench] step %d: next batch's first half %.1f ms, then waited %.1f ms, collect %.1f ms; device %.1f ms"
@@ -698,6 +810,7 @@ def measure(args, ctx, compact=False):
             return
         dbg = os.environ.get("SA_BENCH_DEBUG")
         defer = bool(os.environ.get("SA_BENCH_DEFER"))   # (experiment hook)
+        last = []   # the batch of the call's last step
 
         def retire(old):
             t_w = time.perf_counter()
@@ -711,6 +824,8 @@ def measure(args, ctx, compact=False):
             # pinned block (sa_batch_pairs16_all: one call, nothing copied)
             pairs_seen[0] += int(old.results_view(first_buf)[1][-1])
             done_at.append(time.perf_counter())
+            if on_last is not None and last and old is last[0]:
+                on_last(old)
             old.close()
 
         for s in range(n_steps):
@@ -725,6 +840,8 @@ def measure(args, ctx, compact=False):
             t_b = time.perf_counter()
             cur.start()
             flying.append(cur)
+            if s == n_steps - 1:
+                last.append(cur)
             wait_ms[0] = 0.0
             if len(flying) >= depth:
                 retire(flying.pop(0))
@@ -756,9 +873,10 @@ def measure(args, ctx, compact=False):
         del done_at[:]
         del step_log[:]
         t0 = time.perf_counter()
-        stream(args.steps, priming + args.warmup, leave_next=args.warmup > 0)
+        stream(args.steps, priming + args.warmup, leave_next=args.warmup > 0,
+               on_last=collect if args.dump_outputs and rank == 0 and not compact else None)
         sync()
-        dt = time.perf_counter() - t0
+        dt = time.perf_counter() - t0 - dump_s[0]
         steps_timed = step_stats(step_log)
         if carry.get("nxt") is not None:
             carry.pop("nxt").close()
@@ -772,7 +890,7 @@ def measure(args, ctx, compact=False):
         gaps = sorted(b_ - a_ for a_, b_ in zip(done_at[:args.steps - 1], done_at[1:args.steps]))
         median_step_ms = gaps[len(gaps) // 2] * 1e3
     long_run = None
-    if (not compact and not args.kernels_only and world == 1 and args.workload == "gaussian" and not args.no_secondary
+    if (args.full and not compact and not args.kernels_only and world == 1 and args.workload == "gaussian" and not args.no_secondary
             and args.long_steps > args.steps):
         # K = 20 steps are 0.2 s: a longer sample of the same loop beside it (NOT `value`: the contract times exactly K steps)
         cells_done[0] = 0.0
@@ -797,74 +915,77 @@ def measure(args, ctx, compact=False):
 
     if rank == 0:
         K = args.steps
-        # dominant kernel of rank 0, timed with HIP events on the library's own streams.  k_bwd_fast runs as
-        # n_groups launches per step that overlap pairwise on two streams: its duration here is
-        # the wall time of the whole traceback stage (end of forward -> end of the last k_bwd_fast), which also
-        # contains the fold/finalisation kernels of the earlier groups, and the bytes are those of all launches.
-        fam = "fast" if st0.n_fast_regions == st0.n_regions else ("ring" if st0.n_ring_regions > 0 else "generic")
-        if fam == "ring" and 2 * st0.n_strip_regions > st0.n_ring_regions:
-            fam = "strip"
-        sfx = "_hdp" if (args.workload.startswith("hdp") and fam == "fast") else ""
-        rf_f, rf_b = (single["ms_forward"], single["ms_backward"]) if single else (ms_f, ms_b)
-        if ms_b >= ms_f:
-            dom, dom_ms, dom_cells = "k_bwd_" + fam + sfx, rf_b, st0.cells_backward
-            if fam == "strip" and os.environ.get("SA_STRIP_PASSES") != "2":
-                dom = "k_bwd_strip1"   # the one-pass sweep (round 4; SA_STRIP_PASSES=2: k_bwd_strip)
-            dom_parts = [dom]
-        else:
-            dom, dom_ms, dom_cells = "k_fwd_" + fam + sfx, rf_f, st0.cells_forward
-            dom_parts = [dom]
-            if sfx:   # the HDP forward stage is two kernels: the emission plane (k_emit_hdp), then the sweep that reads it
-                dom_parts = ["k_emit_hdp", dom]
-                dom = "k_emit_hdp + " + dom
-        achieved = ALGO_BYTES_PER_CELL * dom_cells / (dom_ms * 1e-3) / 1e9
-        # HBM bytes per step of the dominant kernel from the rocprofv3 --pmc passes (profiles/traffic.json, written by
-        # probes/profile_r02.sh + probes/traffic_from_pmc.py: FETCH_SIZE and WRITE_SIZE in separate passes, fetch doubled as
-        # MI355X_MICROARCH.md prescribes for gfx950); collected at the default size of each workload only
-        traffic = None
-        profiles_meta = None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        default_size = (args.reads == {"scaling": 12500, "hdp": 5000, "hdp_dense": 5000, "cpg": 10000}.get(args.workload, 2000) and   # (sizes of the counter passes)
-                        args.events == (10000 if args.workload == "scaling" else 5000))
-        if os.path.exists(tp) and default_size:
-            try:
-                tj = json.load(open(tp))
-                tparts = [tj.get(args.workload, {}).get(q, {}).get("bytes_per_step") for q in dom_parts]
-                traffic = sum(tparts) if all(tparts) else None
-                profiles_meta = tj.get("_meta", {}).get(args.workload)   # commit and date of the counter passes (not this run)
-            except Exception:
-                traffic = None
-        # instruction issue of the dominant kernel: wave-instructions per step from the rocprofv3 --pmc passes
-        # (profiles/instr_mix.json, probes/profile_final.sh + probes/instr_from_pmc.py) over the stage time measured here.
-        # Peak: one fp64 VALU instruction per SIMD every 1.83 ns (probes/issue_probe.hip on this part) x 1024 SIMDs.
-        issue = None
-        ip = os.path.join(ROOT, "profiles", "instr_mix.json")
-        if os.path.exists(ip) and default_size:
-            try:
-                recs = [json.load(open(ip)).get(args.workload, {}).get(q) for q in dom_parts]
-                rec = None
-                if all(recs):
-                    rec = dict(recs[-1])
-                    for kk in ("valu_per_step", "instructions_per_step"):
-                        rec[kk] = sum(r_.get(kk) or 0.0 for r_ in recs)
-            except Exception:
-                rec = None
-            if rec and rec.get("valu_per_step"):
-                valu_rate = rec["valu_per_step"] / (dom_ms * 1e-3)
-                issue = {"kernel": dom, "valu_per_step": rec["valu_per_step"],
-                         "instructions_per_step": rec.get("instructions_per_step"),
-                         "achieved": valu_rate, "peak": ISSUE_PEAK_VALU_PER_S, "unit": "fp64 VALU wave-instructions/s",
-                         "frac": valu_rate / ISSUE_PEAK_VALU_PER_S,
-                         "all_instructions_per_s": (rec.get("instructions_per_step") or 0.0) / (dom_ms * 1e-3),
-                         "wave_wait_frac": rec.get("SQ_WAIT_ANY_frac_of_wave_cycles"),
-                         "source": "profiles/instr_mix.json (SQ_INSTS_* per kernel, rocprofv3 --pmc over bench.py --kernels-only)"}
-        lane_use = None
-        if ambig is not None and st0.n_ring_regions > st0.n_strip_regions:
-            try:
-                amb_opts = {"X": 2}
-                lane_use = lane_use_of_ring_regions(sa, pm, params, jobs[:8], ambig, k, lambda c: amb_opts.get(c, 1))
-            except Exception as ex:   # (never the line's problem)
-                lane_use = {"failed": "%s: %s" % (type(ex).__name__, ex)}
+        # --full / --kernels-only: the roofline of phase 1's dominant kernel
+        dom = issue = lane_use = None
+        if phase1:
+            # dominant kernel of rank 0, timed with HIP events on the library's own streams.  k_bwd_fast runs as
+            # n_groups launches per step that overlap pairwise on two streams: its duration here is
+            # the wall time of the whole traceback stage (end of forward -> end of the last k_bwd_fast), which also
+            # contains the fold/finalisation kernels of the earlier groups, and the bytes are those of all launches.
+            fam = "fast" if st0.n_fast_regions == st0.n_regions else ("ring" if st0.n_ring_regions > 0 else "generic")
+            if fam == "ring" and 2 * st0.n_strip_regions > st0.n_ring_regions:
+                fam = "strip"
+            sfx = "_hdp" if (args.workload.startswith("hdp") and fam == "fast") else ""
+            rf_f, rf_b = (single["ms_forward"], single["ms_backward"]) if single else (ms_f, ms_b)
+            if ms_b >= ms_f:
+                dom, dom_ms, dom_cells = "k_bwd_" + fam + sfx, rf_b, st0.cells_backward
+                if fam == "strip" and os.environ.get("SA_STRIP_PASSES") != "2":
+                    dom = "k_bwd_strip1"   # the one-pass sweep (round 4; SA_STRIP_PASSES=2: k_bwd_strip)
+                dom_parts = [dom]
+            else:
+                dom, dom_ms, dom_cells = "k_fwd_" + fam + sfx, rf_f, st0.cells_forward
+                dom_parts = [dom]
+                if sfx:   # the HDP forward stage is two kernels: the emission plane (k_emit_hdp), then the sweep that reads it
+                    dom_parts = ["k_emit_hdp", dom]
+                    dom = "k_emit_hdp + " + dom
+            achieved = ALGO_BYTES_PER_CELL * dom_cells / (dom_ms * 1e-3) / 1e9
+            # HBM bytes per step of the dominant kernel from the rocprofv3 --pmc passes (profiles/traffic.json, written by
+            # probes/profile_r02.sh + probes/traffic_from_pmc.py: FETCH_SIZE and WRITE_SIZE in separate passes, fetch doubled as
+            # MI355X_MICROARCH.md prescribes for gfx950); collected at the default size of each workload only
+            traffic = None
+            profiles_meta = None
+            tp = os.path.join(ROOT, "profiles", "traffic.json")
+            default_size = (args.reads == {"scaling": 12500, "hdp": 5000, "hdp_dense": 5000, "cpg": 10000}.get(args.workload, 2000) and   # (sizes of the counter passes)
+                            args.events == (10000 if args.workload == "scaling" else 5000))
+            if os.path.exists(tp) and default_size:
+                try:
+                    tj = json.load(open(tp))
+                    tparts = [tj.get(args.workload, {}).get(q, {}).get("bytes_per_step") for q in dom_parts]
+                    traffic = sum(tparts) if all(tparts) else None
+                    profiles_meta = tj.get("_meta", {}).get(args.workload)   # commit and date of the counter passes (not this run)
+                except Exception:
+                    traffic = None
+            # instruction issue of the dominant kernel: wave-instructions per step from the rocprofv3 --pmc passes
+            # (profiles/instr_mix.json, probes/profile_final.sh + probes/instr_from_pmc.py) over the stage time measured here.
+            # Peak: one fp64 VALU instruction per SIMD every 1.83 ns (probes/issue_probe.hip on this part) x 1024 SIMDs.
+            issue = None
+            ip = os.path.join(ROOT, "profiles", "instr_mix.json")
+            if os.path.exists(ip) and default_size:
+                try:
+                    recs = [json.load(open(ip)).get(args.workload, {}).get(q) for q in dom_parts]
+                    rec = None
+                    if all(recs):
+                        rec = dict(recs[-1])
+                        for kk in ("valu_per_step", "instructions_per_step"):
+                            rec[kk] = sum(r_.get(kk) or 0.0 for r_ in recs)
+                except Exception:
+                    rec = None
+                if rec and rec.get("valu_per_step"):
+                    valu_rate = rec["valu_per_step"] / (dom_ms * 1e-3)
+                    issue = {"kernel": dom, "valu_per_step": rec["valu_per_step"],
+                             "instructions_per_step": rec.get("instructions_per_step"),
+                             "achieved": valu_rate, "peak": ISSUE_PEAK_VALU_PER_S, "unit": "fp64 VALU wave-instructions/s",
+                             "frac": valu_rate / ISSUE_PEAK_VALU_PER_S,
+                             "all_instructions_per_s": (rec.get("instructions_per_step") or 0.0) / (dom_ms * 1e-3),
+                             "wave_wait_frac": rec.get("SQ_WAIT_ANY_frac_of_wave_cycles"),
+                             "source": "profiles/instr_mix.json (SQ_INSTS_* per kernel, rocprofv3 --pmc over bench.py --kernels-only)"}
+            lane_use = None
+            if ambig is not None and st0.n_ring_regions > st0.n_strip_regions:
+                try:
+                    amb_opts = {"X": 2}
+                    lane_use = lane_use_of_ring_regions(sa, pm, params, jobs[:8], ambig, k, lambda c: amb_opts.get(c, 1))
+                except Exception as ex:   # (never the line's problem)
+                    lane_use = {"failed": "%s: %s" % (type(ex).__name__, ex)}
         out = {
             "metric": "dp_cell_updates_per_s",
             "value": cells_all / dt,
@@ -907,6 +1028,10 @@ def measure(args, ctx, compact=False):
                 "read_sets_cycled": n_sets, "batches_in_flight": depth, "long_run": long_run, "step_ms": steps_timed,
                 "allocator_priming_batches_before_warmup": (depth + 2 if depth > 1 else 0) if not args.kernels_only else 0,
                 "first_batch_create_s": t_create,
+            },
+        }
+        if phase1:
+            out["config"].update({
                 "serial_cycle_ms": cycle,
                 "value_serial_cycle": cells / (sum(cycle.values()) * 1e-3),
                 "kernels_only_resident_inputs": {"value": cells / dt_resident, "ms_per_step": dt_resident * 1e3,
@@ -915,33 +1040,34 @@ def measure(args, ctx, compact=False):
                 "kernel_ms": {"forward": ms_f, "backward_posterior": ms_b, "fold_and_finalize": ms_fold},
                 "kernel_cell_updates_per_s": {"forward": st0.cells_forward / (ms_f * 1e-3),
                                               "backward_posterior": st0.cells_backward / (ms_b * 1e-3)},
-            },
+            })
             # `frac` follows SURVEY section 8(d): algorithmic bytes (24 B per cell update) over the stage time against HBM peak;
             # `frac_by_counters` are the bytes the counters saw.  `bound` names what the evidence says limits the kernel: the
             # sweeps issue instructions during most of their cycles while HBM idles ("issue"; HBM figures kept beside it)
-            "roofline": {"bound": "issue" if issue and issue["frac"] > (traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if traffic else 0.0)
-                         else "hbm", "bound_of_the_formula": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_over_algorithmic": (traffic / (ALGO_BYTES_PER_CELL * dom_cells)) if traffic else None,
-                         "frac_by_counters": (traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                         "limiter": "instruction issue (VALU + SALU of the serial per-diagonal chain), not HBM: see "
-                                    "profiles/ and DESIGN.md section 4",
-                         "counters_collected_at": profiles_meta,
-                         "kernel_passes_phase1": (max(1, min(args.warmup, 3)) + KR),
-                         "algorithmic_bytes_per_step": ALGO_BYTES_PER_CELL * dom_cells,
-                         "stage_ms": dom_ms,
-                         "stage_ms_is": ("the dominant kernel's launches of one step, each alone on its stream (resident batch planned "
-                                         "with SA_GROUPS=1), HIP events on that stream: launches_per_step launches, one per "
-                                         "forward-storage pass" if single else "stage wall of the grouped launches"),
-                         "stage_ms_of_the_grouped_launches": ms_b if dom.startswith("k_bwd") else ms_f,
-                         "launches_per_step": (single["passes"] * single["launches_per_pass"] if single else
-                                               (int(st0.n_groups) if dom.startswith("k_bwd") else int(st0.n_chunks))),
-                         "avg_launch_ms": dom_ms / max(1, (single["passes"] * single["launches_per_pass"]) if single else
-                                                       (int(st0.n_groups) if dom.startswith("k_bwd") else int(st0.n_chunks)))},
-        }
+            out["roofline"] = {"bound": "issue" if issue and issue["frac"] > (traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if traffic else 0.0)
+                               else "hbm", "bound_of_the_formula": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "traffic_over_algorithmic": (traffic / (ALGO_BYTES_PER_CELL * dom_cells)) if traffic else None,
+                               "frac_by_counters": (traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                               "limiter": "instruction issue (VALU + SALU of the serial per-diagonal chain), not HBM: see "
+                                          "profiles/ and DESIGN.md section 4",
+                               "counters_collected_at": profiles_meta,
+                               "kernel_passes_phase1": (max(1, min(args.warmup, 3)) + KR),
+                               "algorithmic_bytes_per_step": ALGO_BYTES_PER_CELL * dom_cells,
+                               "stage_ms": dom_ms,
+                               "stage_ms_is": ("the dominant kernel's launches of one step, each alone on its stream (resident batch planned "
+                                               "with SA_GROUPS=1), HIP events on that stream: launches_per_step launches, one per "
+                                               "forward-storage pass" if single else "stage wall of the grouped launches"),
+                               "stage_ms_of_the_grouped_launches": ms_b if dom.startswith("k_bwd") else ms_f,
+                               "launches_per_step": (single["passes"] * single["launches_per_pass"] if single else
+                                                     (int(st0.n_groups) if dom.startswith("k_bwd") else int(st0.n_chunks))),
+                               "avg_launch_ms": dom_ms / max(1, (single["passes"] * single["launches_per_pass"]) if single else
+                                                             (int(st0.n_groups) if dom.startswith("k_bwd") else int(st0.n_chunks)))}
         if issue:
             out["issue_roofline"] = issue
-        if not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only)
+        if args.dump_outputs and not compact:
+            write_outputs(args.dump_outputs, outputs)
+        if args.full and not args.no_cpu_baseline and world == 1:   # (--full, rank 0 at N = 1 only)
             # the CPU restatement on a bounded sample of THIS workload: same generator, model (HDP loaded where the workload has
             # one), ambiguity table, threshold and anchors
             from oracle import sa_oracle_py as oracle          # timed here as the baseline, nothing else
@@ -1308,8 +1434,16 @@ def main():
     ap.add_argument("--job-events", type=int, default=10000)
     ap.add_argument("--job-slice", type=int, default=2000, help="reads per batch of the scaling job")
     ap.add_argument("--job-sets", type=int, default=2, help="distinct slice-sized read sets a rank generates and cycles")
-    ap.add_argument("--full-record", default=os.path.join(ROOT, "gpurun_out", "bench_full_record.json"),
-                    help="where the complete record goes (the printed line is its short form); '' = nowhere")
+    ap.add_argument("--full", action="store_true",
+                    help="everything measured beside the headline: the kernels-only phase and its roofline, serial cycles, "
+                         "the long run, the CPU baseline, the secondary legs and the scaling job (off: set-up, warm-up, the "
+                         "timed steps and the line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: per-read summaries of every read, the full results of a fixed seeded sample of reads)")
+    ap.add_argument("--full-record", default=None,
+                    help="where the complete record goes (the printed line is its short form; default with --full: "
+                         "bench_out/bench_full_record.json); '' = nowhere")
     ap.add_argument("--no-scaling-job", action="store_true", help="skip config.scaling_job")
     ap.add_argument("--job-reps", type=int, default=5, help="repetitions of the scaling job inside one launch (median, min, max reported)")
     ap.add_argument("--pairs8", action="store_true", help="SA_FLAG_PAIRS8: the batches hold 8-byte result records (x, y, probability) "
@@ -1327,6 +1461,12 @@ def main():
         args.events = 10000 if args.workload == "scaling" else 5000
     if args.threshold is None:
         args.threshold = 0.1 if args.workload.startswith("hdp") else 0.01
+    if args.full_record is None:
+        args.full_record = os.path.join(ROOT, "bench_out", "bench_full_record.json") if args.full else ""
+    if args.dump_outputs and args.workload == "scaling_job":
+        ap.error("--dump-outputs: the scaling job keeps no results of its slices")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: become one (nothing in this process has touched or will touch the GPU)
         sys.exit(self_launch(args.gpus))
@@ -1383,7 +1523,7 @@ def main():
             dist.destroy_process_group()
         return
     out = measure(args, ctx)
-    if world > 1 and args.workload == "gaussian" and not args.kernels_only and not args.no_scaling_job:
+    if args.full and world > 1 and args.workload == "gaussian" and not args.kernels_only and not args.no_scaling_job:
         # BASELINE configs[4] on the multi-GPU line: the 100 000-read job, strong scaling, beside the weak-scaling headline
         sa.lib().sa_pool_release()
         try:
@@ -1392,7 +1532,7 @@ def main():
             job = {"failed": "%s: %s" % (type(ex).__name__, ex)}
         if out is not None:
             out["config"]["scaling_job"] = job
-    if out is not None and world == 1 and args.workload == "gaussian" and not args.kernels_only and not args.no_secondary:
+    if args.full and out is not None and world == 1 and args.workload == "gaussian" and not args.kernels_only and not args.no_secondary:
         # Every other BASELINE config and the two workloads beside them, compactly, on the same line: configs[2] (cpg) at its
         # 10 000 reads, configs[3] (hdp) at its 5000 reads and the reference's threshold 0.1 with the 0.01 figure beside it, one
         # GPU's slice of configs[4] (scaling), reads with the anchors of a real guide alignment (realistic) and the expectation

@@ -10,6 +10,6 @@ d=json.loads(open("gpurun_out/%s.json"%n).read().strip().splitlines()[-1]); c=d[
 print(n, "%.4g"%d["value"], "%.1f ms"%d["ms_per_step"], "passes", c["forward_storage_passes"], "in flight", c["batches_in_flight"], "ko %.4g"%c["kernels_only_value"])
 PY
 }
-run cpg10k_one python bench.py --workload cpg --steps 6 --warmup 2 --no-cpu-baseline
-SA_F_BUDGET_CELLPATHS=2900000000 run cpg10k_two python bench.py --workload cpg --steps 6 --warmup 2 --no-cpu-baseline --in-flight 2
-SA_F_BUDGET_CELLPATHS=1900000000 run cpg10k_three python bench.py --workload cpg --steps 6 --warmup 2 --no-cpu-baseline --in-flight 3
+run cpg10k_one python bench.py --full --workload cpg --steps 6 --warmup 2 --no-cpu-baseline
+SA_F_BUDGET_CELLPATHS=2900000000 run cpg10k_two python bench.py --full --workload cpg --steps 6 --warmup 2 --no-cpu-baseline --in-flight 2
+SA_F_BUDGET_CELLPATHS=1900000000 run cpg10k_three python bench.py --full --workload cpg --steps 6 --warmup 2 --no-cpu-baseline --in-flight 3

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export SA_SYNTH_CACHE=/tmp/sa_reads
 O=gpurun_out/pipeline_busy; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --secondary-budget-s 0 --no-cpu-baseline --steps 20 --warmup 5 --long-steps 200 "$@" > $O/bench.json 2> $O/log
+rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --full --secondary-budget-s 0 --no-cpu-baseline --steps 20 --warmup 5 --long-steps 200 "$@" > $O/bench.json 2> $O/log
 f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

@@ -12,7 +12,7 @@ cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof_${T}_$W
 rm -rf $O && mkdir -p $O
 P=3   # kernel passes per counter run: --warmup 1 + --steps ... -> bench phase 1 runs min(warmup,3) + max(3,min(steps,10)) passes
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --workload $W --no-cpu-baseline $EXTRA > $O/bench_under_profiler.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --workload $W --no-cpu-baseline $EXTRA > $O/bench_under_profiler.json 2> $O/stats.log
 find $O/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python3 bench.py --workload $W --kernels-only --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null 2> $O/pmc_$c.log

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof_r02_$W
 mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --workload $W $X --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_profiler.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --workload $W $X --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_under_profiler.json 2> $O/stats.log
 find $O/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --workload $W $X --kernels-only --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_fetch.json 2> $O/pmc_fetch.log
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 bench.py --workload $W $X --kernels-only --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_write.json 2> $O/pmc_write.log
@@ -19,5 +19,5 @@ rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE
 python3 probes/pmc_summary.py $O/pmc_mix1 > $O/pmc_mix1.json
 python3 probes/pmc_summary.py $O/pmc_mix2 > $O/pmc_mix2.json
 rm -rf $O/stats $O/pmc_fetch $O/pmc_write $O/pmc_mix1 $O/pmc_mix2
-python3 bench.py --workload $W $X $( [ "$W" = gaussian ] || echo --no-cpu-baseline ) > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --workload $W $X $( [ "$W" = gaussian ] || echo --no-cpu-baseline ) > $O/bench.json 2> $O/bench.err
 echo "profile of $W done"
