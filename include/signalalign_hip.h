@@ -403,6 +403,10 @@ int sa_fasta_subsequence(const char *fasta_path, const char *name, int64_t start
  * in.  `out` needs 32 bytes for |v| < 9e15 (larger values, inf and nan go through snprintf: up to 320); a terminator is
  * written; returns the length. */
 int sa_format_f6(char *out, double v);
+/* How pandas' to_csv prints np.round(v, 6) -- Python's repr of that double ("0.5", "1.0", "0.123457", "5e-05"): the value
+ * columns of AggregateOverReadsFull.write_data (src/signalalign/variantCaller.py:393-410).  For 0 <= v <= 1; `out` needs 32
+ * bytes; returns the length. */
+int sa_format_py_round6(char *out, double v);
 
 /* Batches take their device and pinned-host storage from a caching allocator: what a destroyed batch held is kept and
  * handed to the next one (a pipeline that sees every read once creates and destroys a batch per few thousand reads;
@@ -475,6 +479,37 @@ int sa_mea_printed_posterior_device(int64_t first, int64_t n, double *out, int d
 int64_t sa_mea_params(const int64_t *reference_index, const int64_t *event_index, const double *posterior, int64_t n,
                       int32_t *event_idx_out, int32_t *ref_idx_out, double *posterior_out, int32_t *shortest_out,
                       int64_t *n_events_out);
+
+/* ---- per-site variant / methylation calls over a read's posteriors ----------------------------------
+ * Replaces MarginalizeFullVariants.get_data (src/signalalign/variantCaller.py:92-187) over the full TSV
+ * (writePosteriorProbsFull), chained onto a finished batch like sa_batch_mea: the pairs are read where they lie in HBM and
+ * only the calls cross PCIe.
+ *   site      a k-mer index x whose LAST letter, ref[x + k - 1], is an ambiguity letter of the batch's map (the reference tests
+ *             aligned_kmer[k - 1], :152-154)
+ *   letters   the distinct options of that letter, sorted (sorted(variants)); a pair's letter is its path k-mer's last letter,
+ *             the last digit of kmer_id
+ *   units     per letter, the sum over the site's pairs of the posterior the TSV prints ("%f" of prob_e7 / 1e7) in integers of
+ *             1e-6: exact and independent of the order of summation
+ *   prob      units[l] / sum of units (:157-172), the same double on the device and on the host
+ * A site is reported when its pairs print a non-zero total (the reference asserts on a zero one).  x is the pair's k-mer index;
+ * the TSV's reference_index of it is the CLI's business (signalMachine --site-calls).
+ * SA_FLAG_SITE_CALLS at sa_batch_create / _deferred: the batch records its sites (one host pass over each reference) and keeps
+ * them until it is destroyed -- nothing of this without the flag.  With SA_FLAG_VC_ROWS: SA_EINVAL (that flag drops the rows
+ * this step reads); an ambiguity letter at a site with more than SA_SITE_MAX_LETTERS distinct options, or a site in a
+ * SA_FLAG_PAIRS8 batch: SA_EUNSUPPORTED. */
+#define SA_FLAG_SITE_CALLS 128u
+#define SA_SITE_MAX_LETTERS 8
+typedef struct sa_site_call {
+    int32_t x, n_letters;                  /* k-mer index of the site, number of its letters              */
+    char letters[SA_SITE_MAX_LETTERS];     /* sorted; not terminated when there are 8                     */
+    int64_t units[SA_SITE_MAX_LETTERS];    /* printed posterior summed per letter, in 1e-6               */
+    double prob[SA_SITE_MAX_LETTERS];      /* units[l] / sum(units)                                       */
+} sa_site_call_t;
+/* After sa_batch_run (also after sa_batch_release_device, SA_FLAG_EXACT, on every kernel family and with HDP models):
+ * calls_out[j] (malloc'd, sa_free) holds job j's n_out[j] calls in ascending x; one entry per job of the batch.
+ * kernel_ms_out (may be NULL): HIP-event time of the kernels.  SA_ESTATE: created without SA_FLAG_SITE_CALLS, or not run.
+ * Deterministic: the sums are integer atomics. */
+int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out);
 
 /* Plans a whole batch on the host (no GPU needed) with `threads` planner threads (0 = as sa_batch_create would) and
  * returns aggregate geometry plus a 64-bit FNV-1a digest over every array that would be uploaded.  The digest must

@@ -15,6 +15,8 @@ FLAG_DEVICE_TO_ITSELF = 8
 FLAG_INPUTS_IN_HOST_BLOCK = 16
 FLAG_VC_ROWS = 32
 FLAG_PAIRS8 = 64
+FLAG_SITE_CALLS = 128
+SITE_MAX_LETTERS = 8
 
 
 class SaError(RuntimeError):
@@ -43,6 +45,12 @@ class Job(C.Structure):
 
 
 JOB_LEFT_END_NOT_RAGGED, JOB_RIGHT_END_NOT_RAGGED = 1, 2   # sa_job_t.ends (alignmentHasRaggedLeftEnd / RightEnd, inverted)
+
+
+class SiteCall(C.Structure):
+    """sa_site_call_t (include/signalalign_hip.h)"""
+    _fields_ = [("x", C.c_int32), ("n_letters", C.c_int32), ("letters", C.c_char * SITE_MAX_LETTERS),
+                ("units", C.c_int64 * SITE_MAX_LETTERS), ("prob", C.c_double * SITE_MAX_LETTERS)]
 
 
 class Pair(C.Structure):
@@ -80,13 +88,15 @@ class PlanInfo(C.Structure):
 
 
 PAIR_DTYPE = np.dtype([("prob_e7", "<i8"), ("x", "<i4"), ("y", "<i4"), ("path", "<i4"), ("kmer_id", "<i4")])
+SITE_CALL_DTYPE = np.dtype([("x", "<i4"), ("n_letters", "<i4"), ("letters", "S1", (SITE_MAX_LETTERS,)),
+                            ("units", "<i8", (SITE_MAX_LETTERS,)), ("prob", "<f8", (SITE_MAX_LETTERS,))])
 
 EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alphabet", "sa_model_table5",
            "sa_model_set_to_hdp_expected_values", "sa_model_set_emission", "sa_model_clone_with_table", "sa_kmer_id", "sa_default_ambig", "sa_load_ambig",
            "sa_batch_create", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
            "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
            "sa_plan_check_path_records", "sa_dplan_compare",
-           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
+           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
@@ -221,6 +231,8 @@ def lib():
     i32p = C.POINTER(C.c_int32)
     L.sa_mea_batch.argtypes = [C.POINTER(MeaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, i32p, dp]
     L.sa_batch_mea.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, dp]
+    L.sa_batch_site_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(SiteCall)), ip, dp]
+    L.sa_format_py_round6.argtypes = [C.c_char_p, C.c_double]
     L.sa_mea_printed_posterior_device.argtypes = [C.c_int64, C.c_int64, dp, C.c_int]
     L.sa_mea_printed_posterior.restype = C.c_double
     L.sa_mea_printed_posterior.argtypes = [C.c_int64]
@@ -570,6 +582,30 @@ class Batch:
                 C.memmove(a.ctypes.data, ptrs[i], 8 * int(cnt[i]))
             lib().sa_free(ptrs[i])
             out.append((a, float(sums[i]), int(st[i])))
+        return out
+
+    def site_calls(self, stats=None):
+        """sa_batch_site_calls (a batch created with FLAG_SITE_CALLS, after run()): per job a dict of numpy arrays -- x [n] (k-mer
+        index of each reported site), letters [n] (its sorted letters as a str), units [n, 8] (printed posterior summed per
+        letter, in 1e-6) and prob [n, 8] (units / their sum); columns past a site's letter count are 0."""
+        n = self.n_jobs
+        ptrs = (C.POINTER(SiteCall) * max(n, 1))()
+        cnt = np.zeros(max(n, 1), dtype=np.int64)
+        kms = C.c_double()
+        t0 = time.perf_counter()
+        _chk(lib().sa_batch_site_calls(self._h, 0, ptrs, _ip(cnt), C.byref(kms)), "sa_batch_site_calls")
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+            stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+        out = []
+        for i in range(n):
+            m = int(cnt[i])
+            rec = np.zeros(m, dtype=SITE_CALL_DTYPE)
+            if m:
+                C.memmove(rec.ctypes.data, ptrs[i], C.sizeof(SiteCall) * m)
+            lib().sa_free(ptrs[i])
+            letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
+            out.append({"x": rec["x"].copy(), "letters": letters, "units": rec["units"].copy(), "prob": rec["prob"].copy()})
         return out
 
     def stats(self):

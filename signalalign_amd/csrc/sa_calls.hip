@@ -1,0 +1,389 @@
+// Per-site variant / methylation calls on gfx950 -- MarginalizeFullVariants.get_data (src/signalalign/variantCaller.py:92-187),
+// chained onto a finished batch as sa_batch_mea is: the pairs are read where sa_batch_run left them in HBM and only the calls
+// come back.
+//
+// A site is a k-mer index x whose last letter is an ambiguity letter; its call sums, per letter l of that ambiguity letter, the
+// printed posterior of the pairs at x whose path k-mer ends in l, and normalises over the letters.  The sums are integers of
+// 1e-6 (sa_printed_units): exact, so the result does not depend on the order in which the pairs arrive.
+//
+// Tables (built on the host at sa_batch_create, uploaded on the first call): one bit per k-mer index of every job, set at a
+// site, and per 64-bit word the index of its first site -- a pair finds its site slot with one word, one prefix and a popcount.
+// Per site its x and its kind (which ambiguity letter), per kind and alphabet digit the letter's index (-1: not a letter of it).
+//
+// Kernels:
+//   k_site_accum    one thread per 16-byte record, blocks over chunks of a job's records: unpack x, kmer_id, prob_e7; bit test;
+//                   one 64-bit integer atomic add into units[site * stride + letter].  Reads 16 B per record, writes nothing else.
+//   k_site_final    one wave per job: totals, probabilities (in place beside the units), kept sites counted by ballot
+//   k_site_scan     one block of 1024 threads: exclusive scan of the per-job counts
+//   k_site_compact  one wave per job: the kept sites written, in x order, to the job's place in the compact output
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#include <algorithm>
+#include <atomic>
+#include <string>
+#include <vector>
+
+#include "sa_internal.h"
+#include "sa_scratch.h"
+
+#define SITE_CHUNK 4096   // records per block of k_site_accum
+
+struct SaSites {
+    int n_alpha = 0, k = 0, stride = 0;                // stride: most letters of any kind in the batch
+    long long n_sites = 0;
+    std::vector<long long> site_off;                   // n_jobs + 1: job j's sites are [site_off[j], site_off[j + 1])
+    std::vector<long long> word_off;                   // n_jobs + 1: job j's bitmap words
+    std::vector<unsigned long long> bits;              // bit x of job j: x is a site
+    std::vector<int> pre;                              // per word: global index of the first site at or after its first bit
+    std::vector<int> x;                                // per site
+    std::vector<unsigned char> kind;                   // per site
+    std::vector<std::string> letters;                  // per kind: distinct options, sorted
+    std::vector<signed char> slot;                     // kind * n_alpha + digit: index into letters[kind], -1 none
+    // device copy of the tables, one block from the caching allocator: [bits | pre | word_off | site_off | kind | nl | slot]
+    char *d = nullptr;
+    int device = -1;
+    size_t o_pre = 0, o_woff = 0, o_soff = 0, o_kind = 0, o_nl = 0, o_slot = 0;
+};
+
+int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaSites **out) {
+    *out = nullptr;
+    SaSites *S = new (std::nothrow) SaSites();
+    if (!S) return SA_ENOMEM;
+    S->n_alpha = m->n_alpha;
+    S->k = m->k;
+    int kind_of[256];
+    for (int c = 0; c < 256; c++) kind_of[c] = -1;
+    S->site_off.assign((size_t) n_jobs + 1, 0);
+    S->word_off.assign((size_t) n_jobs + 1, 0);
+    for (int64_t j = 0; j < n_jobs; j++) {
+        const long long lx = jobs[j].ref_len - S->k + 1;
+        S->word_off[(size_t) j + 1] = S->word_off[(size_t) j] + (lx > 0 ? (lx + 63) / 64 : 0);
+    }
+    S->bits.assign((size_t) S->word_off[(size_t) n_jobs], 0ull);
+    S->pre.assign(S->bits.size(), 0);
+    int rc = SA_OK;
+    for (int64_t j = 0; j < n_jobs && rc == SA_OK; j++) {
+        const char *ref = jobs[j].ref;
+        const long long lx = jobs[j].ref_len - S->k + 1;
+        const long long w0 = S->word_off[(size_t) j];
+        for (long long x = 0; x < lx; x++) {
+            if ((x & 63) == 0) S->pre[(size_t) (w0 + (x >> 6))] = (int) S->x.size();
+            const unsigned char c = (unsigned char) ref[x + S->k - 1];
+            const char *opts = ambig ? ambig[c] : nullptr;
+            if (!opts) continue;
+            if (kind_of[c] < 0) {
+                std::string l(opts);
+                std::sort(l.begin(), l.end());
+                l.erase(std::unique(l.begin(), l.end()), l.end());
+                if (l.size() > SA_SITE_MAX_LETTERS || S->letters.size() >= 256) { rc = SA_EUNSUPPORTED; break; }
+                kind_of[c] = (int) S->letters.size();
+                S->letters.push_back(l);
+                S->stride = std::max(S->stride, (int) l.size());
+            }
+            S->bits[(size_t) (w0 + (x >> 6))] |= 1ull << (x & 63);
+            S->x.push_back((int) x);
+            S->kind.push_back((unsigned char) kind_of[c]);
+            if (S->x.size() >= (size_t) INT32_MAX) { rc = SA_EUNSUPPORTED; break; }
+        }
+        S->site_off[(size_t) j + 1] = (long long) S->x.size();
+    }
+    if (rc != SA_OK) { delete S; return rc; }
+    S->n_sites = (long long) S->x.size();
+    S->slot.assign(S->letters.size() * (size_t) S->n_alpha, (signed char) -1);
+    for (size_t kd = 0; kd < S->letters.size(); kd++)
+        for (size_t i = 0; i < S->letters[kd].size(); i++)
+            for (int a = 0; a < S->n_alpha; a++)
+                if (m->alphabet[a] == S->letters[kd][i]) S->slot[kd * (size_t) S->n_alpha + (size_t) a] = (signed char) i;
+    *out = S;
+    return SA_OK;
+}
+
+long long sa_sites_count(const SaSites *s) { return s ? s->n_sites : 0; }
+void sa_sites_release_device(SaSites *s) {
+    if (!s || !s->d) return;
+    g_sa_pool.put(SaPool::DEVICE, s->d);
+    s->d = nullptr;
+    s->device = -1;
+}
+void sa_sites_free(SaSites *s) {
+    sa_sites_release_device(s);
+    delete s;
+}
+
+struct SiteTabs {
+    const unsigned long long *bits;
+    const int *pre;
+    const long long *word_off, *site_off;
+    const unsigned char *kind;
+    const int *nl;            // per kind: number of letters
+    const signed char *slot;
+    int n_alpha, stride;
+};
+static SiteTabs sites_tabs(const SaSites *S) {
+    SiteTabs T;
+    T.bits = (const unsigned long long *) S->d;
+    T.pre = (const int *) (S->d + S->o_pre);
+    T.word_off = (const long long *) (S->d + S->o_woff);
+    T.site_off = (const long long *) (S->d + S->o_soff);
+    T.kind = (const unsigned char *) (S->d + S->o_kind);
+    T.nl = (const int *) (S->d + S->o_nl);
+    T.slot = (const signed char *) (S->d + S->o_slot);
+    T.n_alpha = S->n_alpha;
+    T.stride = S->stride;
+    return T;
+}
+
+static int sites_upload(SaSites *S, int device) {
+    if (S->d && S->device == device) return SA_OK;
+    sa_sites_release_device(S);
+    const size_t nw = S->bits.size(), nj1 = S->word_off.size(), ns = (size_t) S->n_sites, nk = S->letters.size();
+    std::vector<int> nl(nk);
+    for (size_t kd = 0; kd < nk; kd++) nl[kd] = (int) S->letters[kd].size();
+    S->o_pre = sa_up256(8 * nw);
+    S->o_woff = sa_up256(S->o_pre + 4 * nw);
+    S->o_soff = sa_up256(S->o_woff + 8 * nj1);
+    S->o_kind = sa_up256(S->o_soff + 8 * nj1);
+    S->o_nl = sa_up256(S->o_kind + ns);
+    S->o_slot = sa_up256(S->o_nl + 4 * nk);
+    const size_t bytes = S->o_slot + S->slot.size() + 1;
+    if (g_sa_pool.get(SaPool::DEVICE, (void **) &S->d, bytes, device) != hipSuccess) { S->d = nullptr; return SA_ENOMEM; }
+    S->device = device;
+    const struct { size_t off; const void *src; size_t n; } up[] = {
+        {0, S->bits.data(), 8 * nw}, {S->o_pre, S->pre.data(), 4 * nw}, {S->o_woff, S->word_off.data(), 8 * nj1},
+        {S->o_soff, S->site_off.data(), 8 * nj1}, {S->o_kind, S->kind.data(), ns}, {S->o_nl, nl.data(), 4 * nk},
+        {S->o_slot, S->slot.data(), S->slot.size()}};
+    for (const auto &u : up)
+        if (u.n && hipMemcpy(S->d + u.off, u.src, u.n, hipMemcpyHostToDevice) != hipSuccess) {
+            sa_sites_release_device(S);
+            return SA_ENODEVICE;
+        }
+    return SA_OK;
+}
+
+struct SiteChunk {
+    long long first;   // first record of the chunk in the batch's device results
+    int n, job;
+};
+
+// units[site * stride + letter] += printed units of every record of the chunk that sits at a site
+__global__ __launch_bounds__(256) void k_site_accum(const sa_pair16_t *__restrict__ pairs, const SiteChunk *__restrict__ chunks,
+                                                    SiteTabs T, unsigned long long *__restrict__ units) {
+    const SiteChunk C = chunks[blockIdx.x];
+    const long long w0 = T.word_off[C.job], w1 = T.word_off[C.job + 1];
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        const sa_pair16_t r = pairs[C.first + i];
+        const long long x = (long long) (r.a & 0xfffffffull);
+        const long long w = w0 + (x >> 6);
+        if (w >= w1) continue;   // (x beyond the job's k-mers: not a record of this job's matrix; cannot happen)
+        const unsigned long long word = T.bits[w];
+        if (!((word >> (x & 63)) & 1ull)) continue;
+        const int site = T.pre[w] + __popcll(word & ((1ull << (x & 63)) - 1ull));
+        const unsigned kmer_id = (unsigned) (r.b & 0xffffffffull);
+        const int l = T.slot[(int) T.kind[site] * T.n_alpha + (int) (kmer_id % (unsigned) T.n_alpha)];
+        if (l < 0) continue;
+        const long long u = sa_printed_units((long long) ((r.b >> 32) & 0xffffffull));
+        if (u) atomicAdd(&units[(size_t) site * (size_t) T.stride + (size_t) l], (unsigned long long) u);
+    }
+}
+
+// job blockIdx.x: every site's total and probabilities; count[j] = its sites with a non-zero total
+__global__ __launch_bounds__(64) void k_site_final(SiteTabs T, const unsigned long long *__restrict__ units, double *__restrict__ prob,
+                                                   int *__restrict__ count) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const long long s0 = T.site_off[j], s1 = T.site_off[j + 1];
+    int kept = 0;
+    for (long long base = s0; base < s1; base += 64) {
+        const long long s = base + lane;
+        bool keep = false;
+        if (s < s1) {
+            const int nl = T.nl[T.kind[s]];
+            const unsigned long long *u = units + (size_t) s * (size_t) T.stride;
+            unsigned long long tot = 0;
+            for (int l = 0; l < nl; l++) tot += u[l];
+            keep = tot != 0;
+            double *p = prob + (size_t) s * (size_t) T.stride;
+            for (int l = 0; l < nl; l++) p[l] = keep ? (double) u[l] / (double) tot : 0.0;
+        }
+        kept += __popcll(__ballot(keep));
+    }
+    if (lane == 0) count[j] = kept;
+}
+
+// exclusive scan of count[0 .. n) into off[0 .. n], one block of 1024 threads: each thread sums a contiguous run of
+// ceil(n / 1024) counts, the run sums are scanned across the block (wave scans, then the waves' totals through LDS), and each
+// thread writes its run's offsets
+#define SITE_SCAN_THREADS 1024
+__global__ __launch_bounds__(SITE_SCAN_THREADS) void k_site_scan(const int *__restrict__ count, long long *__restrict__ off, int n) {
+    __shared__ long long wave_tot[SITE_SCAN_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int per = (n + SITE_SCAN_THREADS - 1) / SITE_SCAN_THREADS;
+    const int a = min(n, t * per), e = min(n, a + per);
+    long long mine = 0;
+    for (int i = a; i < e; i++) mine += count[i];
+    long long incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    long long before = 0;
+    for (int q = 0; q < wv; q++) before += wave_tot[q];
+    long long run = before + incl - mine;
+    for (int i = a; i < e; i++) { off[i] = run; run += count[i]; }
+    if (t == SITE_SCAN_THREADS - 1) off[n] = before + incl;   // (the last thread's inclusive sum is the total)
+}
+
+// job blockIdx.x: its kept sites, in x order, from off[j] on -- site index, units and probabilities (stride per site)
+__global__ __launch_bounds__(64) void k_site_compact(SiteTabs T, const unsigned long long *__restrict__ units, const double *__restrict__ prob,
+                                                     const long long *__restrict__ off, int *__restrict__ o_site,
+                                                     unsigned long long *__restrict__ o_units, double *__restrict__ o_prob) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const long long s0 = T.site_off[j], s1 = T.site_off[j + 1];
+    const size_t st = (size_t) T.stride;
+    long long w = off[j];
+    for (long long base = s0; base < s1; base += 64) {
+        const long long s = base + lane;
+        bool keep = false;
+        int nl = 0;
+        if (s < s1) {
+            nl = T.nl[T.kind[s]];
+            for (int l = 0; l < nl; l++) keep = keep || units[(size_t) s * st + (size_t) l] != 0;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            const size_t dst = (size_t) (w + __popcll(mask & ((1ull << lane) - 1ull)));
+            o_site[dst] = (int) s;
+            for (int l = 0; l < nl; l++) {
+                o_units[dst * st + (size_t) l] = units[(size_t) s * st + (size_t) l];
+                o_prob[dst * st + (size_t) l] = prob[(size_t) s * st + (size_t) l];
+            }
+        }
+        w += __popcll(mask);
+    }
+}
+
+// the timing events and the lock around them; the call's device and pinned storage comes from the caching allocator and goes
+// back to it at the end of the call (sa_pool_release / the pool's bounds reach it)
+static SaScratch g_site_ws;
+
+#define SITECHK(call)                                                                                       \
+    do {                                                                                                    \
+        hipError_t e_ = (call);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
+            goto done;                                                                                      \
+        }                                                                                                   \
+    } while (0)
+
+extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
+    (void) flags;
+    if (!b || !calls_out || !n_out) return SA_EINVAL;
+    SaSites *S = nullptr;
+    int64_t nj64 = 0;
+    int rc = sa_batch_sites(b, &S, &nj64);
+    if (rc) return rc;
+    const size_t nj = (size_t) nj64;
+    for (size_t j = 0; j < nj; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    const size_t stride = (size_t) S->stride, ns = (size_t) S->n_sites;
+    std::vector<long long> h_off(nj + 1, 0);
+    const int *h_site = nullptr;
+    const unsigned long long *h_units = nullptr;
+    const double *h_prob = nullptr;
+    char *d = nullptr, *h = nullptr;   // this call's device and pinned blocks (g_sa_pool)
+    SaScratch &W = g_site_ws;
+    std::unique_lock<std::mutex> guard(W.mu, std::defer_lock);
+    if (ns > 0) {   // (a batch without sites -- a SA_FLAG_PAIRS8 one among them -- has nothing to read on the device)
+        const sa_pair16_t *d_pairs = nullptr;
+        std::vector<long long> first, count, n_events;
+        int device = 0;
+        if ((rc = sa_batch_device_view(b, &d_pairs, &first, &count, &n_events, &device)) != SA_OK) return rc;
+        std::vector<SiteChunk> chunks;
+        for (size_t j = 0; j < nj; j++)
+            for (long long c = 0; c < count[j]; c += SITE_CHUNK)
+                chunks.push_back(SiteChunk{first[j] + c, (int) std::min<long long>(SITE_CHUNK, count[j] - c), (int) j});
+        const size_t nc = chunks.size();
+        // device: [units | prob | chunks | count | off | out site | out units | out prob]
+        const size_t o_units = 0, o_prob = sa_up256(8 * ns * stride), o_chunks = sa_up256(o_prob + 8 * ns * stride),
+                     o_count = sa_up256(o_chunks + sizeof(SiteChunk) * (nc ? nc : 1)), o_off = sa_up256(o_count + 4 * nj),
+                     o_osite = sa_up256(o_off + 8 * (nj + 1)), o_ounits = sa_up256(o_osite + 4 * ns),
+                     o_oprob = o_ounits + 8 * ns * stride, dev_bytes = o_oprob + 8 * ns * stride;
+        guard.lock();
+        if ((rc = W.rebind(device)) != SA_OK || (rc = W.events()) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
+        if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
+        const SiteTabs T = sites_tabs(S);
+        float kms = 0;
+        size_t n_kept = 0, o_hunits = 0, o_hprob = 0;
+        if (nc) SITECHK(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SiteChunk) * nc, hipMemcpyHostToDevice, 0));
+        SITECHK(hipMemsetAsync(d + o_units, 0, 8 * ns * stride, 0));
+        SITECHK(hipEventRecord(W.e0, 0));
+        if (nc) hipLaunchKernelGGL(k_site_accum, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SiteChunk *) (d + o_chunks), T,
+                                   (unsigned long long *) (d + o_units));
+        hipLaunchKernelGGL(k_site_final, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
+                           (double *) (d + o_prob), (int *) (d + o_count));
+        hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SITE_SCAN_THREADS), 0, 0, (const int *) (d + o_count), (long long *) (d + o_off), (int) nj);
+        hipLaunchKernelGGL(k_site_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
+                           (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_osite),
+                           (unsigned long long *) (d + o_ounits), (double *) (d + o_oprob));
+        SITECHK(hipEventRecord(W.e1, 0));
+        SITECHK(hipGetLastError());
+        SITECHK(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
+        SITECHK(hipEventElapsedTime(&kms, W.e0, W.e1));
+        if (kernel_ms_out) *kernel_ms_out = (double) kms;
+        // only the kept calls cross PCIe
+        n_kept = (size_t) h_off[nj];
+        o_hunits = sa_up256(4 * n_kept);
+        o_hprob = o_hunits + 8 * n_kept * stride;
+        if (g_sa_pool.get(SaPool::PINNED, (void **) &h, o_hprob + 8 * n_kept * stride + 256, device) != hipSuccess) {
+            h = nullptr;
+            rc = SA_ENOMEM;
+            goto done;
+        }
+        if (n_kept) {
+            SITECHK(hipMemcpyAsync(h, d + o_osite, 4 * n_kept, hipMemcpyDeviceToHost, 0));
+            SITECHK(hipMemcpyAsync(h + o_hunits, d + o_ounits, 8 * n_kept * stride, hipMemcpyDeviceToHost, 0));
+            SITECHK(hipMemcpyAsync(h + o_hprob, d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost, 0));
+            SITECHK(hipStreamSynchronize(0));
+        }
+        h_site = (const int *) h;
+        h_units = (const unsigned long long *) (h + o_hunits);
+        h_prob = (const double *) (h + o_hprob);
+    }
+    {
+        std::atomic<bool> oom(false);
+        sa_parallel_for(nj, [&](size_t j) {
+            const long long a = h_off[j], n = h_off[j + 1] - h_off[j];
+            n_out[j] = n;
+            calls_out[j] = (sa_site_call_t *) calloc((size_t) (n > 0 ? n : 1), sizeof(sa_site_call_t));
+            if (!calls_out[j]) { oom = true; return; }
+            for (long long i = 0; i < n; i++) {
+                sa_site_call_t &c = calls_out[j][i];
+                const size_t s = (size_t) h_site[a + i], r = (size_t) (a + i) * stride;
+                const std::string &l = S->letters[S->kind[s]];
+                c.x = S->x[s];
+                c.n_letters = (int32_t) l.size();
+                memcpy(c.letters, l.data(), l.size());
+                for (size_t q = 0; q < l.size(); q++) {
+                    c.units[q] = (int64_t) h_units[r + q];
+                    c.prob[q] = h_prob[r + q];
+                }
+            }
+        });
+        if (oom) rc = SA_ENOMEM;
+    }
+done:
+    if (rc != SA_OK && d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
+    if (d) g_sa_pool.put(SaPool::DEVICE, d);   // (every kernel and copy of the call has completed: synchronous copies above)
+    if (h) g_sa_pool.put(SaPool::PINNED, h);
+    if (rc != SA_OK)
+        for (size_t j = 0; j < nj; j++) { free(calls_out[j]); calls_out[j] = nullptr; n_out[j] = 0; }
+    return rc;
+}

@@ -1262,6 +1262,7 @@ struct sa_batch {
     long long *d_vc_off = nullptr, *d_seg_all = nullptr;
     std::vector<unsigned long long> h_vc_bits;  // (the same on the host, for SA_FLAG_EXACT's host finalisation)
     std::vector<long long> h_vc_off, job_all_n, job_all_sum;
+    SaSites *sites = nullptr;                   // SA_FLAG_SITE_CALLS: the batch's sites (sa_calls.hip)
     bool plan_hdp = false;                      // the batch's model holds an HDP
     unsigned hdp_hot = 0xffffffffu;             // DevModel.hdp_hot
     char *d_seam;            // their seam storage: per wave two arrays of seam_cap records of 16 bytes
@@ -1721,6 +1722,7 @@ void sa_batch_destroy(sa_batch_t *b) {
     g_sa_pool.put(SaPool::DEVICE, b->d_pairs_up);
     g_sa_pool.put(SaPool::PINNED, b->h_seg_off);
     g_sa_pool.put(SaPool::PINNED, b->h_overflow);
+    sa_sites_free(b->sites);
     const double td2 = now_ms_d();
     sa_plan_free(b->plan);
     delete b;
@@ -1779,6 +1781,8 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     // reference-ordered kernels.  (SA_TWO_DIST_FAST_OFF=1: always the reference-ordered kernels, as up to round 5.)
     if (m->emission != 0 && ((flags & (SA_FLAG_EXPECT_INTERNAL | SA_FLAG_FORCE_GENERIC)) || getenv("SA_TWO_DIST_FAST_OFF")))
         flags |= SA_FLAG_EXACT;
+    if (flags & SA_FLAG_EXPECT_INTERNAL) flags &= ~SA_FLAG_SITE_CALLS;
+    if ((flags & SA_FLAG_SITE_CALLS) && (flags & SA_FLAG_VC_ROWS)) return SA_EINVAL;   // (that flag drops the rows the calls are made of)
     const bool trace_c = getenv("SA_TRACE") != nullptr;
     auto now_ms_c = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = now_ms_c();
@@ -1833,6 +1837,14 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     b->d_pairs_up = nullptr; b->d_pairs_up_cap = 0;
     memset(&b->stats, 0, sizeof(b->stats));
     for (int i = 0; i < 8; i++) b->ev[i] = nullptr;
+    if (flags & SA_FLAG_SITE_CALLS) {   // the sites of every job: one pass over its reference (sa_calls.hip)
+        const int rcs = n_jobs > 0 && !jobs ? SA_EINVAL : sa_sites_build(m, jobs, n_jobs, ambig, &b->sites);
+        // (an 8-byte record names no k-mer: such a batch may hold no site)
+        if (rcs || ((flags & SA_FLAG_PAIRS8) && sa_sites_count(b->sites) > 0)) {
+            sa_batch_destroy(b);
+            return rcs ? rcs : SA_EUNSUPPORTED;
+        }
+    }
 #define TRY(x) do { int rc_ = (x); if (rc_) { sa_batch_destroy(b); return rc_; } } while (0)
     if (g_handles.stream(&b->cstream[0], device, 0) != hipSuccess || g_handles.stream(&b->cstream[1], device, 0) != hipSuccess) {
         sa_batch_destroy(b);
@@ -3093,6 +3105,14 @@ int sa_batch_device_view(sa_batch_t *b, const sa_pair16_t **pairs, std::vector<l
     return SA_OK;
 }
 
+int sa_batch_sites(sa_batch_t *b, SaSites **sites, int64_t *n_jobs) {
+    if (!b || !sites || !n_jobs) return SA_EINVAL;
+    if (!b->sites || !b->ran) return SA_ESTATE;
+    *sites = b->sites;
+    *n_jobs = b->c_n;
+    return SA_OK;
+}
+
 // sa_batch_run on a thread of the library's own, so that the caller can plan the next batch (sa_batch_create is host
 // work) while this one is on the GPU; sa_batch_wait joins it and returns sa_batch_run's code.
 int sa_batch_prepare(sa_batch_t *b) {
@@ -3132,6 +3152,7 @@ int sa_batch_release_device(sa_batch_t *b) {
     for (void **pp : ptrs)
         if (*pp) { g_sa_pool.put(SaPool::DEVICE, *pp); *pp = nullptr; }
     if (b->held_stage) { g_sa_pool.put(SaPool::PINNED, b->held_stage); b->held_stage = nullptr; }
+    sa_sites_release_device(b->sites);
     b->released = true;
     return SA_OK;
 }

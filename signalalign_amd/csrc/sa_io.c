@@ -67,6 +67,28 @@ int sa_format_f6(char *out, double v) {
     return (int) (p - out);
 }
 
+/* repr(float(np.round(v, 6))) for 0 <= v <= 1.  numpy rounds as rint(v * 1e6) / 1e6, which is the double nearest n / 1e6 for
+ * the integer n = rint(v * 1e6); the shortest decimal that reads back as that double is n * 1e-6 itself (at most seven significant
+ * digits), which repr writes in fixed notation down to 1e-4 and as "<digits>e-0X" below. */
+int sa_format_py_round6(char *out, double v) {
+    const double r = rint(v * 1e6);
+    if (!(r >= 0.0 && r <= 1e6)) return sprintf(out, "%.17g", rint(v * 1e6) / 1e6);
+    const long n = (long) r;
+    if (n == 0) return sprintf(out, "0.0");
+    if (n == 1000000) return sprintf(out, "1.0");
+    char d[8];
+    sprintf(d, "%06ld", n);
+    int len = 6;
+    while (d[len - 1] == '0') len--;
+    d[len] = 0;
+    if (n >= 100) return sprintf(out, "0.%s", d);
+    /* below 1e-4: scientific, one digit before the point */
+    const int lead = n >= 10 ? 4 : 5;   /* index of the first non-zero digit in d */
+    const int exp10 = -(lead + 1);
+    if (len - lead == 1) return sprintf(out, "%ce-%02d", d[lead], -exp10);
+    return sprintf(out, "%c.%se-%02d", d[lead], d + lead + 1, -exp10);
+}
+
 static double sa_atod(const char *p) {
     static const double p10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16,
                                    1e17, 1e18, 1e19, 1e20, 1e21, 1e22};

@@ -829,21 +829,10 @@ extern "C" int64_t sa_mea_params(const int64_t *reference_index, const int64_t *
 // pairs into the COO matrix and shortest_ref_per_event in place (k_mea_from_pairs) and the MEA kernels follow, so
 // nothing but the final paths crosses PCIe.
 //
-// The event table's posterior_probability is what the TSV prints, "%f" of prob_e7 / 1e7, six decimals: a decimal
-// rounding of a binary double.  Only a last digit of 5 can tie; then the sign of q * 1e7 - prob_e7 (one fma, exact in
-// sign) says on which side of the tie the double q = prob_e7 / 1e7 lies, and an exact tie goes to even as glibc's
-// printf does.  tests/test_host_mea.py checks every value of prob_e7 against Python's "%f".
+// The event table's posterior_probability is what the TSV prints, "%f" of prob_e7 / 1e7, six decimals (sa_printed_units,
+// sa_scratch.h).
 __host__ __device__ static inline double mea_printed_posterior(long long prob_e7) {
-    long long k = prob_e7 / 10;
-    const long long rem = prob_e7 % 10;
-    if (rem > 5) {
-        k++;
-    } else if (rem == 5) {
-        const double q = (double) prob_e7 / 1e7;
-        const double side = fma(q, 1e7, -(double) prob_e7);
-        if (side > 0 || (side == 0 && (k & 1))) k++;
-    }
-    return (double) k / 1e6;
+    return (double) sa_printed_units(prob_e7) / 1e6;
 }
 extern "C" double sa_mea_printed_posterior(int64_t prob_e7) { return mea_printed_posterior((long long) prob_e7); }
 

@@ -66,7 +66,11 @@ static void usage(void) {
     fprintf(stderr, "--emission <meanOnly|twoDist>: match emission of a Gaussian model (default meanOnly, what the reference's\n"
                     "                  signalMachine installs; twoDist adds the inverse Gaussian on the event noise; single read only)\n");
     fprintf(stderr, "--device <n>: GPU to use\n");
-    fprintf(stderr, "--mea: also write <posteriors file>.mea, the rows of the full output on the maximum expected accuracy path\n\n");
+    fprintf(stderr, "--mea: also write <posteriors file>.mea, the rows of the full output on the maximum expected accuracy path\n");
+    fprintf(stderr, "--site-calls: also write <posteriors file>.calls, per read and ambiguous site the normalised probability of\n"
+                    "                  each of its letters (variantCaller.py MarginalizeFullVariants)\n");
+    fprintf(stderr, "--site-calls-aggregate <file>: write the per-site calls averaged over all reads of the run to <file>\n"
+                    "                  (AggregateOverReadsFull); a manifest's posteriors file may then be '-' (no TSV for that read)\n\n");
 }
 
 static double descale(double e, double level, double scale, double shift, double var) {
@@ -322,6 +326,8 @@ static int load_strand_model(strand_model_t *sm, const char *model_path, const c
 typedef struct {
     int hdp, two_d, rna, expect_mode;
     int mea; /* --mea: also write the maximum-expected-accuracy path of every read (not in the reference binary) */
+    int site_calls;         /* --site-calls: also write <posteriors>.calls (not in the reference binary) */
+    const char *agg_path;   /* --site-calls-aggregate: the over-reads table, written at the end of the run */
     int two_dist; /* --emission twoDist: the two-distribution emission (not an option of the reference binary: it is what its
                    * state machine carried when the reference's shipped output files were written); one read per process */
     int64_t out_fmt, constraint_trim;
@@ -675,6 +681,9 @@ typedef struct {
     int64_t *const *all_n;      /* [strand][job], -s 1 only (SA_FLAG_VC_ROWS): number and prob_e7 sum of ALL pairs of the job -- the */
     int64_t *const *all_sum;    /* rows the variant-caller output does not print were dropped on the device                        */
     const int *p8;              /* [strand]: the batch holds 8-byte records (SA_FLAG_PAIRS8): path 0, the reference's k-mer at x          */
+    sa_site_call_t ***calls;    /* [strand][job], --site-calls / --site-calls-aggregate only */
+    int64_t **n_calls;
+    unsigned char *tmpl_amb;    /* [job], the same with --twoD: the template strand has a row on an ambiguous k-mer (order_calls) */
 } out_job_t;
 
 /* kmer_id of the k letters at s (sorted alphabet, first letter most significant), -1 for a letter outside it */
@@ -716,6 +725,200 @@ static void write_mea(const char *post_path, const out_ctx_t *o, const sa_mea_pa
     m.n_pairs = n;
     write_full(out_path, &m);
     free(rows); free(x_of); free(best); free(out_path);
+}
+
+/* ---- --site-calls / --site-calls-aggregate: MarginalizeFullVariants.get_data and AggregateOverReadsFull
+ * (src/signalalign/variantCaller.py:92-187, :393-410) over the calls sa_batch_site_calls made on the device ---- */
+typedef struct { int64_t pos, i; } call_pos_t;
+/* does any of the strand's pairs sit on a reference k-mer that holds an ambiguity letter (a variant_data row of get_data, :112)? */
+static int has_ambiguous_rows(const char *const *ambig, const char *target, int k, const sa_pair_t *pairs, int64_t n) {
+    const int64_t len = (int64_t) strlen(target);
+    int64_t *last = malloc(sizeof(int64_t) * (size_t) (len + 1));   /* last[i]: the last ambiguous position below i, -1 none */
+    int64_t prev = -1;
+    for (int64_t i = 0; i <= len; i++) {
+        last[i] = prev;
+        if (i < len && ambig[(unsigned char) target[i]]) prev = i;
+    }
+    int found = 0;
+    for (int64_t i = 0; i < n && !found; i++) {
+        const int64_t end = (int64_t) pairs[i].x + k;
+        found = end <= len && last[end] >= pairs[i].x;
+    }
+    free(last);
+    return found;
+}
+static int cmp_call_pos(const void *a, const void *b) {
+    const int64_t x = ((const call_pos_t *) a)->pos, y = ((const call_pos_t *) b)->pos;
+    return x < y ? -1 : x > y;
+}
+/* The calls of one strand of a read in the order get_data walks them (:141-144): by the reference_index the TSV prints for the
+ * site's k-mer (adjust_ref), ascending, reversed when the strand's mapping strand is '-'.  The mapping strand (:128-131, :179):
+ * mapping_strands[mapping_index], where the index starts at 0 and moves on after every read strand that has variant_data rows --
+ * rows whose reference k-mer holds an ambiguity letter (:112), whether or not one of them is a site.  So the complement gets
+ * mapping_strands[1] exactly when the template has such a row (`tmpl_amb`, template_has_ambiguous_rows). */
+static call_pos_t *order_calls(const read_t *rd, int s, int tmpl_amb, const sa_site_call_t *calls, int64_t n, int k, char *mapped) {
+    const int idx = (s == 1 && tmpl_amb) ? 1 : 0;
+    *mapped = (idx == 0) == (rd->forward != 0) ? '+' : '-';
+    const char *target = s == 0 ? rd->template_target : rd->complement_target;
+    const int64_t ref_len = (int64_t) strlen(target), ref_len_kmers = ref_len - k, off = s == 0 ? rd->r_shift_t : rd->r_shift_c;
+    call_pos_t *v = malloc(sizeof(call_pos_t) * (size_t) (n > 0 ? n : 1));
+    for (int64_t i = 0; i < n; i++) {
+        v[i].pos = adjust_ref(calls[i].x, off, ref_len_kmers, ref_len, s == 0, rd->forward);
+        v[i].i = i;
+    }
+    qsort(v, (size_t) n, sizeof(call_pos_t), cmp_call_pos);
+    if (*mapped == '-')
+        for (int64_t a = 0, b = n - 1; a < b; a++, b--) { call_pos_t t = v[a]; v[a] = v[b]; v[b] = t; }
+    return v;
+}
+/* <posteriors>.calls: label contig position strand forward_mapped letters p_1 .. p_n (one row per reported site) */
+static void write_calls(const char *post_path, const read_t *rd, int s, int tmpl_amb, const sa_site_call_t *calls, int64_t n, int k) {
+    char *out_path = malloc(strlen(post_path) + 8);
+    sprintf(out_path, "%s.calls", post_path);
+    FILE *fh = open_rows(out_path);
+    char mapped;
+    call_pos_t *v = order_calls(rd, s, tmpl_amb, calls, n, k, &mapped);
+    char *line = malloc(strlen(rd->label) + strlen(rd->pA->contig1) + 512);
+    for (int64_t q = 0; q < n; q++) {
+        const sa_site_call_t *c = &calls[v[q].i];
+        char *w = line;
+        w = put_s(w, rd->label); *w++ = '\t';
+        w = put_s(w, rd->pA->contig1); *w++ = '\t';
+        w = put_i64(w, v[q].pos); *w++ = '\t';
+        *w++ = s == 0 ? 't' : 'c'; *w++ = '\t';
+        *w++ = mapped; *w++ = '\t';
+        for (int l = 0; l < c->n_letters; l++) *w++ = c->letters[l];
+        for (int l = 0; l < c->n_letters; l++) { *w++ = '\t'; w = put_f(w, c->prob[l]); }
+        *w++ = '\n';
+        fwrite(line, 1, (size_t) (w - line), fh);
+    }
+    free(line); free(v); free(out_path);
+    fclose(fh);
+}
+
+/* The over-reads table (_normalize_all_data :393-407): per (contig, position, strand, forward_mapped) and letter the per-read
+ * probabilities summed in read order; written at the end of the run. */
+#define AGG_MAX_LETTERS 16
+typedef struct {
+    int64_t pos;
+    int contig, n;
+    char strand, mapped, used;
+    char letter[AGG_MAX_LETTERS];
+    double sum[AGG_MAX_LETTERS];
+} agg_entry_t;
+static struct {
+    agg_entry_t *tab;
+    size_t cap, n;
+    char **contigs;
+    int n_contigs;
+} g_agg;
+static uint64_t agg_hash(int contig, int64_t pos, char strand, char mapped) {
+    uint64_t h = (uint64_t) pos * 0x9E3779B97F4A7C15ull ^ ((uint64_t) (unsigned) contig << 17) ^ ((uint64_t) (unsigned char) strand << 8) ^
+                 (uint64_t) (unsigned char) mapped;
+    h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32;
+    return h;
+}
+static agg_entry_t *agg_slot(int contig, int64_t pos, char strand, char mapped) {
+    if (2 * (g_agg.n + 1) > g_agg.cap) {   /* grow: rehash into twice the room */
+        const size_t ncap = g_agg.cap ? 2 * g_agg.cap : 1 << 16;
+        agg_entry_t *nt = calloc(ncap, sizeof(agg_entry_t));
+        if (!nt) die("signalMachine: out of memory%s", "");
+        for (size_t i = 0; i < g_agg.cap; i++) {
+            const agg_entry_t *e = &g_agg.tab[i];
+            if (!e->used) continue;
+            size_t h = (size_t) agg_hash(e->contig, e->pos, e->strand, e->mapped) & (ncap - 1);
+            while (nt[h].used) h = (h + 1) & (ncap - 1);
+            nt[h] = *e;
+        }
+        free(g_agg.tab);
+        g_agg.tab = nt;
+        g_agg.cap = ncap;
+    }
+    size_t h = (size_t) agg_hash(contig, pos, strand, mapped) & (g_agg.cap - 1);
+    for (;; h = (h + 1) & (g_agg.cap - 1)) {
+        agg_entry_t *e = &g_agg.tab[h];
+        if (!e->used) {
+            e->used = 1; e->contig = contig; e->pos = pos; e->strand = strand; e->mapped = mapped;
+            g_agg.n++;
+            return e;
+        }
+        if (e->contig == contig && e->pos == pos && e->strand == strand && e->mapped == mapped) return e;
+    }
+}
+static void agg_add_read(const read_t *rd, int s, int tmpl_amb, const sa_site_call_t *calls, int64_t n, int k) {
+    if (n <= 0) return;
+    int ci = 0;
+    while (ci < g_agg.n_contigs && strcmp(g_agg.contigs[ci], rd->pA->contig1) != 0) ci++;
+    if (ci == g_agg.n_contigs) {
+        g_agg.contigs = realloc(g_agg.contigs, sizeof(char *) * (size_t) (g_agg.n_contigs + 1));
+        g_agg.contigs[g_agg.n_contigs++] = strdup(rd->pA->contig1);
+    }
+    char mapped;
+    call_pos_t *v = order_calls(rd, s, tmpl_amb, calls, n, k, &mapped);
+    for (int64_t q = 0; q < n; q++) {
+        const sa_site_call_t *c = &calls[v[q].i];
+        agg_entry_t *e = agg_slot(ci, v[q].pos, s == 0 ? 't' : 'c', mapped);
+        for (int l = 0; l < c->n_letters; l++) {
+            int t = 0;
+            while (t < e->n && e->letter[t] != c->letters[l]) t++;
+            if (t == e->n) {
+                if (e->n == AGG_MAX_LETTERS) die("signalMachine: --site-calls-aggregate: more than 16 letters at one site%s", "");
+                e->letter[e->n] = c->letters[l]; e->sum[e->n] = 0.0; e->n++;
+            }
+            e->sum[t] += c->prob[l];
+        }
+    }
+    free(v);
+}
+static int cmp_agg(const void *a, const void *b) {
+    const agg_entry_t *x = *(const agg_entry_t *const *) a, *y = *(const agg_entry_t *const *) b;
+    const int c = strcmp(g_agg.contigs[x->contig], g_agg.contigs[y->contig]);
+    if (c) return c;
+    if (x->strand != y->strand) return x->strand < y->strand ? -1 : 1;
+    if (x->mapped != y->mapped) return x->mapped < y->mapped ? -1 : 1;
+    return x->pos < y->pos ? -1 : x->pos > y->pos;
+}
+/* write_data (:409-411): header, then the rows as pandas prints them -- np.round(sum / total, 6) through repr.  Columns: the sorted
+ * union of the letters; a letter a site does not have counts 0. */
+static void write_aggregate(const char *path) {
+    int have[256] = {0};
+    agg_entry_t **rows = malloc(sizeof(agg_entry_t *) * (g_agg.n ? g_agg.n : 1));
+    size_t n = 0;
+    for (size_t i = 0; i < g_agg.cap; i++)
+        if (g_agg.tab[i].used) {
+            rows[n++] = &g_agg.tab[i];
+            for (int t = 0; t < g_agg.tab[i].n; t++) have[(unsigned char) g_agg.tab[i].letter[t]] = 1;
+        }
+    qsort(rows, n, sizeof(agg_entry_t *), cmp_agg);
+    FILE *fh = fopen(path, "w");
+    if (!fh) die("signalMachine: cannot open output %s", path);
+    setvbuf(fh, NULL, _IOFBF, 1 << 20);
+    char cols[256];
+    int nc = 0;
+    for (int ch = 0; ch < 256; ch++)
+        if (have[ch]) cols[nc++] = (char) ch;
+    fprintf(fh, "contig\tposition\tstrand\tforward_mapped");
+    for (int c = 0; c < nc; c++) fprintf(fh, "\t%c", cols[c]);
+    fputc('\n', fh);
+    char num[40];
+    for (size_t r = 0; r < n; r++) {
+        const agg_entry_t *e = rows[r];
+        double total = 0.0;   /* sum over the letters in column order, as the reference's generator adds them */
+        for (int c = 0; c < nc; c++)
+            for (int t = 0; t < e->n; t++)
+                if (e->letter[t] == cols[c]) total += e->sum[t];
+        fprintf(fh, "%s\t%" PRId64 "\t%c\t%c", g_agg.contigs[e->contig], e->pos, e->strand, e->mapped);
+        for (int c = 0; c < nc; c++) {
+            double v = 0.0;
+            for (int t = 0; t < e->n; t++)
+                if (e->letter[t] == cols[c]) v = e->sum[t];
+            sa_format_py_round6(num, v / total);
+            fprintf(fh, "\t%s", num);
+        }
+        fputc('\n', fh);
+    }
+    fclose(fh);
+    free(rows);
 }
 
 static void output_one(int64_t j, void *ctx) {
@@ -790,6 +993,8 @@ static void output_one(int64_t j, void *ctx) {
         }
         c->score[j][s] = 100.0 * tot / ((double) n_all * PROB_1); /* scoreByPosteriorProbabilityIgnoringGaps :407-412 */
     }
+    const int tmpl_amb = c->tmpl_amb && has_ambiguous_rows(R->ambig, rd->template_target, R->smt.k, pp[0], c->n_pairs[0][j]);
+    if (c->tmpl_amb) c->tmpl_amb[j] = (unsigned char) tmpl_amb;
     if (rd->post_path != NULL) {
         out_ctx_t o;
         o.label = rd->label; o.contig = rd->pA->contig1; o.sm = &R->smt; o.npp = rd->np->template_params;
@@ -798,12 +1003,14 @@ static void output_one(int64_t j, void *ctx) {
         o.n_pairs = c->n_pairs[0][j]; o.score = c->score[j][0];
         output_alignment(R->out_fmt, rd->post_path, rd->post_path2, &o);
         if (R->mea) write_mea(rd->post_path, &o, c->mea[0][j], c->n_mea[0][j]);
+        if (R->site_calls) write_calls(rd->post_path, rd, 0, tmpl_amb, c->calls[0][j], c->n_calls[0][j], R->smt.k);
         if (R->two_d) {
             o.sm = &R->smc; o.npp = rd->np->complement_params; o.events = rd->np->complement_events;
             o.target = rd->complement_target; o.is_template = 0; o.event_offset = rd->c_lo; o.ref_offset = rd->r_shift_c;
             o.pairs = pp[1]; o.n_pairs = c->n_pairs[1][j]; o.score = c->score[j][1];
             output_alignment(R->out_fmt, rd->post_path, rd->post_path2, &o);
             if (R->mea) write_mea(rd->post_path, &o, c->mea[1][j], c->n_mea[1][j]);
+            if (R->site_calls) write_calls(rd->post_path, rd, 1, tmpl_amb, c->calls[1][j], c->n_calls[1][j], R->smc.k);
         }
     }
     free(mine[0]); free(mine[1]);
@@ -855,6 +1062,8 @@ typedef struct {
     sa_batch_t *batch[2];  /* alive until the slice is rendered (their packed records are what the rendering reads) */
     int64_t *all_n_s[2], *all_sum_s[2];   /* -s 1: see out_job_t */
     int p8_s[2];          /* see out_job_t */
+    sa_site_call_t **calls_s[2];   /* see out_job_t */
+    int64_t *n_calls_s[2];
     int64_t n_failed;     /* out */
 } render_job_t;
 static void *render_slice(void *arg);
@@ -928,11 +1137,17 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
     int64_t *all_n[2] = {NULL, NULL}, *all_sum[2] = {NULL, NULL};
     /* -s 1 prints only the rows whose reference k-mer holds an X: the others stay on the device (SA_FLAG_VC_ROWS), the run's pair
      * count and score come from the totals the device kept */
-    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !getenv("SA_CLI_EXPAND_EARLY") && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
+    /* --site-calls / --site-calls-aggregate: every batch records its sites (SA_FLAG_SITE_CALLS) and keeps every row (the calls are
+     * made of the rows SA_FLAG_VC_ROWS would drop; -s 1 then filters on the host, write_vc) */
+    const int want_calls = R.site_calls || R.agg_path != NULL;
+    const unsigned calls_flag = want_calls ? SA_FLAG_SITE_CALLS : 0u;
+    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !want_calls && !getenv("SA_CLI_EXPAND_EARLY") && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
+    sa_site_call_t **calls_s[2] = {NULL, NULL};
+    int64_t *n_calls_s[2] = {NULL, NULL};
     /* -s 0 / -s 2 without --mea: 8-byte result records where the batch allows them (one path per cell: no ambiguity letter in any
      * read's reference; fewer than 2^20 positions and events per read) -- the planner says SA_EUNSUPPORTED otherwise and the strand's
      * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker). */
-    const unsigned p8_want = ((R.out_fmt == 0 || R.out_fmt == 2) && !R.mea && !getenv("SA_CLI_EXPAND_EARLY") && !getenv("SA_CLI_PAIRS16")) ? SA_FLAG_PAIRS8 : 0u;
+    const unsigned p8_want = ((R.out_fmt == 0 || R.out_fmt == 2) && !R.mea && !want_calls && !getenv("SA_CLI_EXPAND_EARLY") && !getenv("SA_CLI_PAIRS16")) ? SA_FLAG_PAIRS8 : 0u;
     int p8_used[2] = {0, 0};
     for (int s = 0; s < n_strands; s++) {
         pairs[s] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(sa_pair_t *));
@@ -940,17 +1155,23 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
         if (n_ok == 0) continue;
         fprintf(stderr, s == 0 ? "signalAlign - starting template alignment\n" : "signalAlign - starting complement alignment\n");
         for (int64_t j = 0; j < n_ok; j++) bj[j] = reads[who[j]].jobs[s];
+        if (want_calls) {
+            calls_s[s] = calloc((size_t) n_ok, sizeof(sa_site_call_t *));
+            n_calls_s[s] = calloc((size_t) n_ok, sizeof(int64_t));
+        }
         int rc;
-        if (!R.mea && getenv("SA_CLI_EXPAND_EARLY")) {   /* (A/B hook: the one-shot call of rounds 1-3) */
+        if (!R.mea && !want_calls && getenv("SA_CLI_EXPAND_EARLY")) {   /* (A/B hook: the one-shot call of rounds 1-3) */
             rc = sa_align_batch(R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, 0, pairs[s],
                                 n_pairs[s]);
         } else if (!R.mea) {   /* the batch stays alive for the rendering, which expands its packed records job by job */
             sa_batch_t *b = NULL;
-            rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, vc_flag | p8_want);
+            rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device,
+                                 vc_flag | p8_want | calls_flag);
             p8_used[s] = rc == SA_OK && p8_want != 0;
             if (rc == SA_EUNSUPPORTED && p8_want)
                 rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, vc_flag);
             if (rc == SA_OK) rc = sa_batch_run(b);
+            if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
             for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) rc = sa_batch_n_pairs(b, j, &n_pairs[s][j]);
             if (vc_flag && rc == SA_OK) {
                 free(all_n[s]); free(all_sum[s]);
@@ -967,8 +1188,9 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
             sa_batch_t *b = NULL;
             mea[s] = calloc((size_t) n_ok, sizeof(sa_mea_pair_t *));
             n_mea[s] = calloc((size_t) n_ok, sizeof(int64_t));
-            rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, 0);
+            rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, calls_flag);
             if (rc == SA_OK) rc = sa_batch_run(b);
+            if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
             for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) {
                 sa_batch_n_pairs(b, j, &n_pairs[s][j]);
                 pairs[s][j] = malloc(sizeof(sa_pair_t) * (size_t) (n_pairs[s][j] > 0 ? n_pairs[s][j] : 1));
@@ -995,6 +1217,10 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
                     for (int64_t j = 0; j < n_ok; j++) { sa_free(pairs[q][j]); if (R.mea && mea[q]) sa_free(mea[q][j]); }
                     free(pairs[q]); free(n_pairs[q]);
                     if (R.mea) { free(mea[q]); free(n_mea[q]); mea[q] = NULL; n_mea[q] = NULL; }
+                    if (calls_s[q]) {
+                        for (int64_t j = 0; j < n_ok; j++) sa_free(calls_s[q][j]);
+                        free(calls_s[q]); free(n_calls_s[q]); calls_s[q] = NULL; n_calls_s[q] = NULL;
+                    }
                     pairs[q] = NULL; n_pairs[q] = NULL;
                 }
                 n_ok = k2;
@@ -1012,7 +1238,8 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
     g_t_gpu += now_s() - ts1;
     render_job_t *job = calloc(1, sizeof(*job));
     job->Rp = Rp; job->reads = reads; job->n_reads = n_reads; job->n_ok = n_ok; job->who = who; job->bj = bj;
-    for (int s = 0; s < 2; s++) { job->pairs_s[s] = pairs[s]; job->n_pairs_s[s] = n_pairs[s]; job->mea_s[s] = mea[s]; job->n_mea_s[s] = n_mea[s]; job->batch[s] = batches[s]; job->all_n_s[s] = all_n[s]; job->all_sum_s[s] = all_sum[s]; job->p8_s[s] = p8_used[s]; }
+    for (int s = 0; s < 2; s++) { job->pairs_s[s] = pairs[s]; job->n_pairs_s[s] = n_pairs[s]; job->mea_s[s] = mea[s]; job->n_mea_s[s] = n_mea[s]; job->batch[s] = batches[s]; job->all_n_s[s] = all_n[s]; job->all_sum_s[s] = all_sum[s]; job->p8_s[s] = p8_used[s];
+                              job->calls_s[s] = calls_s[s]; job->n_calls_s[s] = n_calls_s[s]; }
     return job;
 #undef R
 }
@@ -1033,12 +1260,19 @@ static void *render_slice(void *arg) {
     const int n_strands = R.two_d ? 2 : 1;
     const double ts2 = now_s();
     double (*score)[2] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(*score));
+    unsigned char *tmpl_amb = (R.two_d && job->calls_s[1]) ? calloc((size_t) (n_ok > 0 ? n_ok : 1), 1) : NULL;
     {
-        out_job_t oc = {&R, reads, who, pairs, n_pairs, score, mea, n_mea, job->batch, job->all_n_s, job->all_sum_s, job->p8_s};
+        out_job_t oc = {&R, reads, who, pairs, n_pairs, score, mea, n_mea, job->batch, job->all_n_s, job->all_sum_s, job->p8_s,
+                        job->calls_s, job->n_calls_s, tmpl_amb};
         if (outputs_distinct(reads, who, n_ok)) parallel_for(n_ok, output_one, &oc);
         else for (int64_t j = 0; j < n_ok; j++) output_one(j, &oc);
     }
     for (int s = 0; s < 2; s++) { sa_batch_destroy(job->batch[s]); job->batch[s] = NULL; }
+    if (R.agg_path)   /* (in read order: the sums over reads do not depend on the rendering threads) */
+        for (int64_t j = 0; j < n_ok; j++)
+            for (int s = 0; s < n_strands && !reads[who[j]].failed; s++)
+                agg_add_read(&reads[who[j]], s, tmpl_amb && tmpl_amb[j], job->calls_s[s][j], job->n_calls_s[s][j],
+                             s == 0 ? R.smt.k : R.smc.k);
     for (int64_t j = 0; j < n_ok; j++) {
         read_t *rd = &reads[who[j]];
         if (rd->failed) continue;
@@ -1051,6 +1285,12 @@ static void *render_slice(void *arg) {
             if (R.mea) sa_free(mea[s][j]);
         }
     }
+    free(tmpl_amb);
+    for (int s = 0; s < n_strands; s++)
+        if (job->calls_s[s]) {
+            for (int64_t j = 0; j < n_ok; j++) sa_free(job->calls_s[s][j]);
+            free(job->calls_s[s]); free(job->n_calls_s[s]);
+        }
     t_add(&g_t_render, now_s() - ts2);
     int64_t n_failed = 0;
     for (int64_t i = 0; i < n_reads; i++) n_failed += reads[i].failed ? 1 : 0;
@@ -1111,6 +1351,8 @@ int main(int argc, char **argv) {
                                            {"mea", no_argument, 0, 1002},
                                            {"batch-reads", required_argument, 0, 1003},
                                            {"emission", required_argument, 0, 1004},
+                                           {"site-calls", no_argument, 0, 1005},
+                                           {"site-calls-aggregate", required_argument, 0, 1006},
                                            {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -1144,6 +1386,8 @@ int main(int argc, char **argv) {
             case 1000: manifest = strdup(optarg); break;
             case 1001: device = atoi(optarg); break;
             case 1002: R.mea = 1; break;
+            case 1005: R.site_calls = 1; break;
+            case 1006: R.agg_path = strdup(optarg); break;
             case 1003: batch_reads = atoll(optarg) > 0 ? atoll(optarg) : batch_reads; break;
             case 1004:
                 if (!strcmp(optarg, "twoDist")) R.two_dist = 1;
@@ -1192,6 +1436,8 @@ int main(int argc, char **argv) {
             die("[signalMachine] ERROR: need -f <fasta> and -n <sequence name>", NULL);
         }
     }
+
+    if (R.expect_mode && (R.site_calls || R.agg_path)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate need the alignment mode, not -t/-c%s", ""); }
 
     R.p.threshold = threshold;
     R.p.diagonal_expansion = diag_expansion % 2 == 0 ? diag_expansion : diag_expansion + 1;
@@ -1277,6 +1523,7 @@ int main(int argc, char **argv) {
         n_failed += render_prev->n_failed;
         free(render_prev);
     }
+    if (R.agg_path) write_aggregate(R.agg_path);
     if (batch_mode)
         fprintf(stderr, "[signalMachine] batch: %" PRId64 " of %" PRId64 " reads aligned\n", n_reads - n_failed, n_reads);
     if (getenv("SA_CLI_TIMING"))
