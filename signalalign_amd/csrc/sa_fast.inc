@@ -96,8 +96,8 @@ __device__ __forceinline__ void la_tab_init(double *tab, int tid) {
 // Per-site tables.  logAdd(a + k1, b + k2) = k1 + logAdd(a, b + (k2 - k1)) and the constant k1 can sit in the table's constant
 // term (row 15, the cut-off, then holds k1 instead of 0): a cell's four logAdds need three operand additions instead
 // of seven.  The forward sweeps keep four such tables (sites 0..3, see la_sites_fwd); the backward sweeps stay on the plain
-// table: there the extra constants cost registers (k_bwd_fast: twelve spilled at its 96-register budget; k_bwd_strip: 141 ->
-// 151) and the sweeps came out 2-4 % slower.
+// table: there the extra constants cost registers (k_bwd_fast: twelve spilled at its 96-register budget) and the sweeps came
+// out 2-4 % slower.
 #define LA_SITES 4
 __device__ __forceinline__ void la_tab_init_site(double *tab, int tid, double k) {
     la_tab_init(tab, tid);

@@ -862,9 +862,9 @@ __global__ __launch_bounds__(256) void k_check_events(const double *__restrict__
     if (__ballot(bad) && (threadIdx.x & 63) == 0) flag[2] = 1;
 }
 
-// spec (one-pass strip sweep, sa_strip.inc): per segment the speculative total its candidate bound was derived from, NaN for every
-// other segment.  The bound is only valid while no exact total of the segment lies below spec - slack: checked here, raised in
-// P.overflow[1] (the pass is then repeated with the two-pass sweep).
+// spec (register, ring and strip kernels, sa_strip.inc): per segment the speculative total its candidate bound was derived from, NaN
+// for every other segment.  The bound is only valid while no exact total of the segment lies below spec - slack: checked here,
+// raised in P.overflow[1] (the pass is then repeated with a larger slack).
 // vc_bits (SA_FLAG_VC_ROWS): one bit per reference position of every job (job j's from bit vc_off[j] on): set where the k-mer that
 // starts there holds the ambiguity letter 'X' -- the rows writePosteriorProbsVC prints (impl/signalMachine.c:161-232).  Pairs
 // elsewhere are counted and summed into seg_all (their number and the sum of their floor(p 1e7), what
@@ -987,10 +987,6 @@ __global__ __launch_bounds__(1024) void k_scan(const int *in, long long *out, lo
 // gather survivors of a segment in REVERSE candidate order (=> ascending diagonals, x descending, path descending:
 // the order of stList_pop + stable sort by x+y, impl/pairwiseAligner.c:2043-2050, impl/signalMachine.c:872)
 // seg_off: exclusive scan over the n_segs segments starting at seg0 (indexed from 0); out: first slot of that range
-// strip segment: a one-path ring-kernel region that the strip kernels sweep (the host's strip_region(), sa_hip.hip)
-__device__ __forceinline__ bool seg_is_strip(const sa_region_t *R, int strip_on) {
-    return strip_on && R->kind == SA_KIND_RING && R->max_p == 1 && R->lX < 64ll * STRIP_NS_MAX && R->N >= 1;
-}
 // spec: per segment its speculative total where the ring / strip kernels produced the candidates (NaN elsewhere), or nullptr.
 //   * a strip segment's candidates arrive strip by strip: k_gather_sorted writes it;
 //   * a ring segment's candidates arrive diagonal by diagonal (the workgroup's barrier separates diagonals) but, inside a
@@ -1020,7 +1016,7 @@ __global__ __launch_bounds__(64) void k_gather(DevPlan P, int seg0, int n_segs, 
     if (spec) {
         const double sp = spec[seg];
         if (sp == sp) {
-            if (seg_is_strip(R, strip_on)) return;
+            if (strip_region(R, strip_on)) return;
             unordered = R->kind == SA_KIND_RING;   // (a register-kernel segment is one wave: its candidates are in order)
         }
     }
@@ -1058,7 +1054,7 @@ __global__ __launch_bounds__(64) void k_gather(DevPlan P, int seg0, int n_segs, 
 }
 
 
-// The same for the segments of the ring kernels and of the one-pass strip sweep (sa_ring.inc, sa_strip.inc), whose candidates are
+// The same for the segments of the ring kernels and of the strip kernels (sa_ring.inc, sa_strip.inc), whose candidates are
 // appended in the order the waves / strips get to them instead of in candidate order (diagonals downwards, columns upwards, a
 // cell's paths upwards): the survivors are put in candidate order first -- a counting sort by diagonal (histogram of the
 // segment's diagonals in LDS, GATHER_H at a time), then every diagonal's few survivors by (column, path) -- and written as k_gather
@@ -1075,7 +1071,7 @@ __global__ __launch_bounds__(64) void k_gather_sorted(DevPlan P, int seg0, int n
     { const double sp = spec[seg]; if (!(sp == sp)) return; }   // not a segment of these kernels: k_gather wrote it
     const sa_seg_t *S = &P.segs[seg];
     const sa_region_t *R = &P.regions[S->region];
-    if (!seg_is_strip(R, 1)) return;                            // a ring segment: k_gather wrote it
+    if (!strip_region(R, 1)) return;                             // a ring segment: k_gather wrote it
     const int *poff = P.poff + R->poff_off;
     const int *pid = P.pid + R->pid_off;
     const int n = P.cand_count[seg];
@@ -1250,8 +1246,6 @@ struct sa_batch {
     int wide_cap;            // cells per row of the register kernels' LDS ring for wide diagonals (0: every diagonal fits)
     int gen_threads;         // 64, or 128 when a diagonal of a memory-resident region holds more than 64 cell-paths
     bool strip_on;           // one-path ring-kernel regions run on the strip kernels (default; SA_STRIP=0: ring kernels)
-    double *d_ckxy;          // ... and the (two-pass) backward kernel's side buffer (2 x n_vbuf doubles)
-    bool strip_one_pass;     // strip segments run the one-pass backward sweep (k_bwd_strip1; SA_STRIP_PASSES=2: the two-pass one)
     double *d_spec;          // ring / strip kernels: speculative totals, one per segment (NaN: a segment of another kernel family)
     double spec_slack;       // candidates: forward + backward >= spec - slack + log(threshold); grows when a pass has to be repeated
     int spec_repeats;        // passes repeated because of it (the second repeat drops the bound altogether)
@@ -1704,7 +1698,7 @@ void sa_batch_destroy(sa_batch_t *b) {
     void *ptrs[] = {b->d_regions, b->d_rows, b->d_pk, b->d_poff, b->d_pid, b->d_px, b->d_xc, b->d_prec, b->d_ev, b->d_segs, b->d_cks, b->d_F, b->d_E,
                     b->d_vbuf, b->d_cands, b->d_cand_count, b->d_overflow, b->d_totals, b->d_bscratch, b->d_tab6, b->d_noise3, b->d_evn, b->d_two,
                     b->d_hdp_slot, b->d_hdp_y, b->d_hdp_slope, b->d_hdp_grid, b->d_hdp_tab, b->d_hdp_coef, b->d_prob, b->d_seg_pass, b->d_seg_off,
-                    b->d_out, b->d_ids, b->d_gsum, b->d_gmc, b->d_seam, b->d_ckxy, b->d_blk, b->d_spec, b->d_sortkey, b->d_sortidx,
+                    b->d_out, b->d_ids, b->d_gsum, b->d_gmc, b->d_seam, b->d_blk, b->d_spec, b->d_sortkey, b->d_sortidx,
                     b->d_vc_bits, b->d_vc_off, b->d_seg_all};
     for (void *p : ptrs)
         if (p) g_sa_pool.put(SaPool::DEVICE, p);
@@ -1817,9 +1811,9 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     b->d_prec = nullptr; b->d_blk = nullptr;
     b->d_ev = nullptr; b->d_segs = nullptr; b->d_cks = nullptr; b->d_F = nullptr; b->d_E = nullptr; b->d_vbuf = nullptr;
     b->d_cands = nullptr; b->d_cand_count = nullptr; b->d_overflow = nullptr; b->d_totals = nullptr;
-    b->d_seam = nullptr; b->d_ckxy = nullptr; b->seam_cap = 0; b->seam_cap_bwd = 0; b->seam_bwd_off = 0; b->strip_on = false;
+    b->d_seam = nullptr; b->seam_cap = 0; b->seam_cap_bwd = 0; b->seam_bwd_off = 0; b->strip_on = false;
     b->prepared = false; b->prepare_rc = SA_OK; b->lw_strip_max_n = b->lw_strip_max_seg = b->lw_strip_fwd_slots = b->lw_strip_bwd_slots = 0;
-    b->strip_one_pass = false; b->d_spec = nullptr; b->d_sortkey = nullptr; b->d_sortidx = nullptr;
+    b->d_spec = nullptr; b->d_sortkey = nullptr; b->d_sortidx = nullptr;
     // the exact totals of a traceback drift away from its speculative total diagonal by diagonal (1.6e-4 per diagonal with the flat
     // HDP fixture: sa_strip.inc), so the slack is sized for the traceback's length -- the default 0.5 at the default 1100 diagonals --
     // and starts from what earlier batches of this model on this device had to grow to
@@ -1923,9 +1917,6 @@ static int batch_build_lists(sa_batch *b) {
     // One-path ring-kernel regions go to the strip kernels (sa_strip.inc): Gaussian emissions, default arithmetic,
     // device-side finalisation, reference windows of fewer than 64 * STRIP_NS_MAX positions.  SA_STRIP=0: ring kernels.
     b->strip_on = !host_finalize && !(getenv("SA_STRIP") && atoi(getenv("SA_STRIP")) == 0);   // (HDP regions too: they read the emission plane)
-    auto strip_region = [&](const sa_region_t &Rq) {
-        return b->strip_on && Rq.kind == SA_KIND_RING && Rq.max_p == 1 && Rq.lX < 64ll * STRIP_NS_MAX && Rq.N >= 1;
-    };
     long long strip_max_n = 0, strip_max_seg = 0, strip_fwd_slots = 0, strip_bwd_slots = 0;
     long long r = 0;
     for (int c = 0; c < pl->n_chunks; c++) {
@@ -1942,7 +1933,7 @@ static int batch_build_lists(sa_batch *b) {
         };
         for (long long q = ra; q < rb; q++) {
             const sa_region_t &Rq = pl->regions[q];
-            if (strip_region(Rq)) { sr_.push_back((int) q); strip_max_n = Rq.N > strip_max_n ? Rq.N : strip_max_n; }
+            if (strip_region(&Rq, b->strip_on)) { sr_.push_back((int) q); strip_max_n = Rq.N > strip_max_n ? Rq.N : strip_max_n; }
             else if (Rq.kind == SA_KIND_RING) rr[ring_class(Rq)].push_back((int) q);
             else if (Rq.kind != SA_KIND_FAST) gr.push_back((int) q);
             else fr.push_back((int) q);
@@ -2000,7 +1991,7 @@ static int batch_build_lists(sa_batch *b) {
             for (long long t = qa; t < q; t++) {
                 const sa_region_t *R = &pl->regions[t];
                 for (long long sg = R->seg_off; sg < R->seg_off + R->n_seg; sg++) {
-                    if (strip_region(*R)) {
+                    if (strip_region(R, b->strip_on)) {
                         ss.push_back((int) sg);
                         const long long span = pl->segs[sg].start - pl->segs[sg].to;
                         strip_max_seg = span > strip_max_seg ? span : strip_max_seg;
@@ -2391,17 +2382,13 @@ static int batch_finish_body(sa_batch *b) {
                 b->seam_cap_bwd = (unsigned) (strip_max_seg + 16);
                 b->seam_bwd_off = strip_fwd_slots * 32ll * (long long) b->seam_cap;
                 TRY(dalloc((void **) &b->d_seam, b->seam_bwd_off + strip_bwd_slots * 32ll * (long long) b->seam_cap_bwd));
-                // side buffer of the (two-pass) backward strip kernel: the two backward gap sums of every checkpoint cell, laid out like vbuf
-                TRY(dalloc((void **) &b->d_ckxy, 16ll * (pl->n_vbuf > 0 ? pl->n_vbuf : 1)));
-                // the one-pass sweep (default; SA_STRIP_PASSES=2: the two-pass sweep of round 2): speculative totals per segment, sort keys
-                // per candidate slot.  Its 64-bit sort key holds 24 bits of diagonals below a traceback's start (de << 40).
-                b->strip_one_pass = !(getenv("SA_STRIP_PASSES") && atoi(getenv("SA_STRIP_PASSES")) == 2);
             }
             if ((pl->n_ring_regions + pl->n_fast_regions > 0 && !host_finalize) || (b->expect && pl->n_ring_regions > 0)) {
-                // register, ring and (one-pass) strip kernels: candidates against the traceback's speculative total (one per segment)
+                // register, ring and strip kernels: candidates against the traceback's speculative total (one per segment)
                 TRY(dalloc((void **) &b->d_spec, 8ll * (pl->n_segs > 0 ? pl->n_segs : 1)));
             }
-            if (b->strip_one_pass && strip_fwd_slots > 0 && !host_finalize) {   // k_gather_sorted: sort keys per candidate slot
+            // k_gather_sorted: sort keys per candidate slot.  A 64-bit key holds 24 bits of diagonals below a traceback's start (de << 40).
+            if (strip_fwd_slots > 0 && !host_finalize) {
                 TRY(dalloc((void **) &b->d_sortkey, 8ll * (pl->n_cand > 0 ? pl->n_cand : 1)));
                 TRY(dalloc((void **) &b->d_sortidx, 4ll * (pl->n_cand > 0 ? pl->n_cand : 1)));
             }
@@ -2427,7 +2414,7 @@ static int batch_finish_body(sa_batch *b) {
         void **ptrs[] = {(void **) &b->d_F, (void **) &b->d_E, (void **) &b->d_vbuf, (void **) &b->d_cands, (void **) &b->d_prob,
                          (void **) &b->d_cand_count, (void **) &b->d_seg_pass, (void **) &b->d_seg_off, (void **) &b->d_overflow,
                          (void **) &b->d_totals, (void **) &b->d_bscratch, (void **) &b->d_gsum, (void **) &b->d_gmc, (void **) &b->d_seam,
-                         (void **) &b->d_ckxy, (void **) &b->d_spec, (void **) &b->d_sortkey, (void **) &b->d_sortidx,
+                         (void **) &b->d_spec, (void **) &b->d_sortkey, (void **) &b->d_sortidx,
                          (void **) &b->d_out};
         for (void **q : ptrs)
             if (*q) { g_sa_pool.put(SaPool::DEVICE, *q); *q = nullptr; }
@@ -2436,7 +2423,7 @@ static int batch_finish_body(sa_batch *b) {
         for (hipEvent_t e : b->gev) if (e) g_handles.park(e, device);
         for (hipEvent_t e : b->cev) if (e) g_handles.park(e, device);
         b->gev.clear(); b->cev.clear();
-        b->seam_cap = 0; b->seam_cap_bwd = 0; b->seam_bwd_off = 0; b->strip_one_pass = false;
+        b->seam_cap = 0; b->seam_cap_bwd = 0; b->seam_bwd_off = 0;
     };
     // A batch whose RESULTS take longer to cross PCIe than its kernels take to run (broad HDP densities at a low threshold: hundreds of
     // millions of pairs) ends when its last copy ends, and its first copy cannot start before the forward sweep of its first pass has
@@ -2557,7 +2544,7 @@ int sa_dplan_compare(const sa_model_t *m, const sa_params_t *p, const sa_job_t *
     b->d_cands = nullptr; b->d_cand_count = nullptr; b->d_overflow = nullptr; b->d_totals = nullptr; b->d_bscratch = nullptr;
     b->d_tab6 = nullptr; b->d_hdp_slot = nullptr; b->d_hdp_y = nullptr; b->d_hdp_slope = nullptr; b->d_hdp_grid = nullptr;
     b->d_hdp_tab = nullptr; b->d_hdp_coef = nullptr; b->d_prob = nullptr; b->d_seg_pass = nullptr; b->d_seg_off = nullptr; b->d_out = nullptr;
-    b->d_ids = nullptr; b->d_gsum = nullptr; b->d_gmc = nullptr; b->d_seam = nullptr; b->d_ckxy = nullptr;
+    b->d_ids = nullptr; b->d_gsum = nullptr; b->d_gmc = nullptr; b->d_seam = nullptr;
     b->d_spec = nullptr; b->d_sortkey = nullptr; b->d_sortidx = nullptr;
     int rcd;
     {
@@ -2638,11 +2625,9 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
     if (G.nss) {
         StripT ST;
         ST.ev_total = pl->n_ev + 8; ST.seam_cap = b->seam_cap_bwd; ST.seam_stride = 32ull * b->seam_cap_bwd; ST.seam_first = G.seam_first;
-        ST.ck_half = pl->n_vbuf;
-        ST.spec = b->strip_one_pass ? b->d_spec : nullptr;
+        ST.spec = b->d_spec;
         ST.slack = b->spec_slack;
-        if (b->strip_one_pass) launch_bwd_strip1(P, b->d_ids + G.ids_ss, G.nss, st, b->d_seam + b->seam_bwd_off, ST);
-        else launch_bwd_strip(P, b->d_ids + G.ids_ss, G.nss, st, b->d_seam + b->seam_bwd_off, b->d_ckxy, ST);
+        launch_bwd_strip1(P, b->d_ids + G.ids_ss, G.nss, st, b->d_seam + b->seam_bwd_off, ST);
     }
     for (int cl = 15; cl >= 0; cl--)   // widest (longest-running) classes first
         if (G.nrs[cl]) launch_bwd_ring(P, b->d_ids + G.ids_rs[cl], G.nrs[cl], st, 64 * ((cl & 7) + 1), cl >= 8, b->expect);
@@ -2655,14 +2640,14 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
         long long *soff = b->d_seg_off + G.seg0 + g;
         bool any_ring = G.nfs > 0;
         for (int cl = 0; cl < 16; cl++) any_ring = any_ring || G.nrs[cl] > 0;
-        // (groups without register / ring / one-pass strip segments: no look at the speculative totals)
-        const double *spec = (b->d_spec && (any_ring || (b->strip_one_pass && G.nss > 0))) ? b->d_spec : nullptr;
+        // (groups without register / ring / strip segments: no look at the speculative totals)
+        const double *spec = (b->d_spec && (any_ring || G.nss > 0)) ? b->d_spec : nullptr;
         hipLaunchKernelGGL(k_finalize, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, b->d_seg_pass, spec,
                            b->spec_slack, (const unsigned long long *) b->d_vc_bits, (const long long *) b->d_vc_off, b->d_seg_all);
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, b->d_seg_pass + G.seg0, soff, b->h_seg_off + G.seg0 + g, n);
         sa_pair16_t *const gout = b->out_at(pl->segs[G.seg0].cand_off);
         hipLaunchKernelGGL(k_gather, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, soff,
-                           gout, spec, (b->strip_on && b->strip_one_pass && b->d_sortkey) ? 1 : 0, b->p8 ? 1 : 0);
+                           gout, spec, (b->strip_on && b->d_sortkey) ? 1 : 0, b->p8 ? 1 : 0);
         if (spec && G.nss > 0 && b->d_sortkey)
             hipLaunchKernelGGL(k_gather_sorted, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, soff,
                                gout, spec, b->d_sortkey, b->d_sortidx, b->p8 ? 1 : 0);
@@ -2723,7 +2708,7 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
             if (C.nst) {
                 StripT ST;
                 ST.ev_total = pl->n_ev + 8; ST.seam_cap = b->seam_cap; ST.seam_stride = 32ull * b->seam_cap; ST.seam_first = 0;
-                ST.spec = b->strip_one_pass ? b->d_spec : nullptr;
+                ST.spec = b->d_spec;
                 ST.slack = b->spec_slack;
                 launch_fwd_strip(P, b->d_ids + C.ids_st, C.nst, lanes[0], b->d_seam, ST);
                 which = n_lanes > 1 ? 1 : 0;
@@ -3146,7 +3131,7 @@ int sa_batch_release_device(sa_batch_t *b) {
                      (void **) &b->d_totals, (void **) &b->d_bscratch, (void **) &b->d_tab6, (void **) &b->d_noise3, (void **) &b->d_evn, (void **) &b->d_two,
                      (void **) &b->d_hdp_slot, (void **) &b->d_hdp_y, (void **) &b->d_hdp_slope, (void **) &b->d_hdp_grid, (void **) &b->d_hdp_tab, (void **) &b->d_hdp_coef,
                      (void **) &b->d_prob, (void **) &b->d_seg_pass, (void **) &b->d_seg_off, (void **) &b->d_out, (void **) &b->d_ids,
-                     (void **) &b->d_gsum, (void **) &b->d_gmc, (void **) &b->d_seam, (void **) &b->d_ckxy, (void **) &b->d_blk, (void **) &b->d_spec,
+                     (void **) &b->d_gsum, (void **) &b->d_gmc, (void **) &b->d_seam, (void **) &b->d_blk, (void **) &b->d_spec,
                      (void **) &b->d_sortkey, (void **) &b->d_sortidx, (void **) &b->d_vc_bits, (void **) &b->d_vc_off,
                      (void **) &b->d_seg_all};
     for (void **pp : ptrs)

@@ -25,21 +25,24 @@
 // Arithmetic and order of operations per cell are those of the ring kernels' one-path flavour (messages oM, oX, oY with the
 // transitions folded in, la_fast, folded Gaussian constants): results are bit-identical to theirs.
 //
-// Backward: a traceback segment's total-probability checkpoints need the maximum term of a whole diagonal before a
-// candidate can be told from a non-candidate, and a strip only sees its own 64 columns of it.  So the sweep (pass 1) only
-// leaves what the posterior side needs: forward.match + backward.match of every posterior cell in the cell's own slot of the
-// gapX plane (a cell is posterior for exactly one segment; the gap planes of a diagonal that is not a checkpoint hold
-// nothing), and on checkpoint diagonals -- whose gap planes do hold the forward gap states -- that sum in the checkpoint's
-// slot of vbuf and the two backward gap sums in a side buffer.  A second pass of the same wave then walks the diagonals in
-// output order, 64 cells per load: on a checkpoint diagonal (and the one above it) it computes the checkpoint's per-cell
-// terms from five coalesced loads and their maximum, on every diagonal it appends the candidates exactly as the other
-// kernels do -- the fold and finalisation kernels are unchanged.  (The first version computed the checkpoint terms inside
-// the sweep: two more prefetched loads per diagonal, and 4.7 of the sweep's 21.4 ms.)
+// Backward: a traceback segment's candidate bound depends on its total, which sums whole diagonals, and a strip only sees its
+// own 64 columns of one.  So the bound comes from the segment's speculative total (below), known before the sweep starts: one
+// wave sweeps the segment's strips once, appends every posterior cell that passes the bound to the segment's candidates as it
+// meets it, and writes each checkpoint's per-cell terms (and the match-through terms of the diagonal above it) to vbuf in cell
+// order.  The fold and finalisation kernels are those of every other kernel; k_finalize applies the exact test with the exact
+// totals.
 //
 // Forward storage: the planes of SA_KIND_RING regions (match | gapX | gapY, gap planes on checkpoint diagonals only).
 
 #define STRIP_WAVES 4
 #define STRIP_NS_MAX 256      // strips per region: reference windows below 16384 k-mers (longer ones stay on the ring kernels)
+
+// The regions these kernels sweep: one-path SA_KIND_RING regions with fewer than 64 * STRIP_NS_MAX reference positions, in a
+// batch that runs them (strip_on).  The host's launch lists and k_gather / k_gather_sorted (which of the two writes a
+// segment's pairs) both decide by this one test.
+__host__ __device__ __forceinline__ bool strip_region(const sa_region_t *R, int strip_on) {
+    return strip_on && R->kind == SA_KIND_RING && R->max_p == 1 && R->lX < 64ll * STRIP_NS_MAX && R->N >= 1;
+}
 
 struct StripT {
     FastT f;
@@ -47,12 +50,11 @@ struct StripT {
     unsigned long long seam_stride;  // bytes of seam storage per wave: two arrays of seam_cap records
     unsigned seam_cap;               // records (16 bytes) per seam array
     unsigned seam_first;             // this launch's first wave slot in the seam storage
-    long long ck_half;               // backward: doubles between the two halves of the checkpoint side buffer (= vbuf's size)
-    double *spec;                    // one-pass backward sweep: per traceback segment its speculative total (below)
+    double *spec;                    // backward: per traceback segment its speculative total (below)
     double slack;                    // ... and how far below it the candidate bound is put (STRIP_SPEC_SLACK unless a pass is repeated)
 };
 
-// ---- the speculative total of a traceback (one-pass backward sweep, k_bwd_strip1; the ring kernels use it too) ----
+// ---- the speculative total of a traceback (k_bwd_strip1; the ring kernels use it too) ----
 // A traceback's posteriors are exp(f + b - total) with the total refreshed at every tenth diagonal (impl/pairwiseAligner.c:1538);
 // all those totals estimate the same quantity, the probability of the data given the band, and differ only by what the
 // reference's approximate logAdd and the band's clipping leave between them (~1e-3).  One of them can be bounded BEFORE the
@@ -355,7 +357,7 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
 }
 
 // ---------------------------------------------------------------------------------------------------
-// backward + checkpoint terms (pass 1), candidates in output order (pass 2)
+// backward: one sweep per segment, candidates and checkpoint terms written as the sweep meets them
 // ---------------------------------------------------------------------------------------------------
 struct StripInB {
     double e;
@@ -364,440 +366,14 @@ struct StripInB {
                      // does not survive the loop's back edge without a copy, and the copy waits for the load)
 };
 
-// maximum over each row of 16 lanes, in every lane of the row (four DPP row rotates); v_max_f64 has no DPP form
-__device__ __forceinline__ double row16_max(double v) {
-#define STRIP_ROR(ctrl)                                                                                                    \
-    {                                                                                                                      \
-        const int lo_ = __builtin_amdgcn_mov_dpp(__double2loint(v), ctrl, 0xF, 0xF, false);   /* every lane has a source */ \
-        const int hi_ = __builtin_amdgcn_mov_dpp(__double2hiint(v), ctrl, 0xF, 0xF, false);                                \
-        v = vmax(v, __hiloint2double(hi_, lo_));                                                                           \
-    }
-    STRIP_ROR(0x121) STRIP_ROR(0x122) STRIP_ROR(0x124) STRIP_ROR(0x128)
-#undef STRIP_ROR
-    return v;
-}
-
 #define STRIP_BWD_OCC 4
-template <bool HDP>
-__global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_eu(STRIP_BWD_OCC, STRIP_BWD_OCC))) void k_bwd_strip(
-    const sa_region_t *__restrict__ regions, const sa_seg_t *__restrict__ segs, const sa_row_t *__restrict__ rows_all,
-    const sa_ck_t *__restrict__ cks, const double4 *__restrict__ xc_all, const double *__restrict__ ev_all, double *__restrict__ F_all,
-    double *__restrict__ vbuf, double *__restrict__ ckxy, sa_cand_t *__restrict__ cands, int *__restrict__ cand_count,
-    int *__restrict__ overflow, char *__restrict__ seam_all, StripT ST, const int *__restrict__ seg_ids, int n,
-    const double *__restrict__ E_all) {
-    __shared__ __attribute__((aligned(32))) double LT[LA_TAB_DOUBLES];
-    __shared__ int s_lo[STRIP_WAVES][STRIP_NS_MAX], s_hi[STRIP_WAVES][STRIP_NS_MAX];
-    __shared__ double s_b0[STRIP_WAVES];   // maximum of the first checkpoint's match-through terms (gathered by the sweep)
-    const FastT &T = ST.f;
-    la_tab_init(LT, threadIdx.x);
-    __syncthreads();
-    const int wv = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    if (wv >= n) return;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int seg = __builtin_amdgcn_readfirstlane(seg_ids[wv]);
-    const sa_seg_t *S = &segs[seg];
-    const sa_region_t *R = &regions[S->region];
-    const int4 *rows4 = reinterpret_cast<const int4 *>(rows_all + R->row_off);
-    const int lX = (int) R->lX;
-    const long long C = R->f_cellpaths;
-    double *F = F_all + 3 * R->f_base;
-    const int start = (int) S->start, from = (int) S->from, to = (int) S->to;
-    const long long ck_base = S->ck_base;
-    const int n_ck = S->n_ck;
-    const int4 *cks4 = reinterpret_cast<const int4 *>(cks + ck_base);   // {voff lo, voff hi, nA, nB}
-    const int ns = (lX >> 6) + 1;
-    int *lo = s_lo[wid], *hi = s_hi[wid];
-    int smin, smax;
-    strip_ranges(rows4, to + 1, start, lane, ns, lo, hi, smin, smax);
-
-    const rsrc_t rs_xc = make_rsrc(xc_all + R->pid_off), rs_F = make_rsrc(F);
-    const long long ev_left = (ST.ev_total - R->ev_off) * 8;
-    const rsrc_t rs_ev = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(ev_all + R->ev_off), 0,
-                                                           (int) (ev_left < 0x7fffffffll ? (ev_left > 0 ? ev_left : 0) : 0x7fffffffll),
-                                                           0x00020000);
-    char *seam = seam_all + (unsigned long long) (ST.seam_first + (unsigned) wv) * ST.seam_stride;
-    const rsrc_t rs_seam = __builtin_amdgcn_make_buffer_rsrc(seam, 0, (int) ST.seam_stride, 0x00020000);
-    const unsigned C8 = (unsigned) C * 8u;
-    const unsigned OOB = 0xfffffff0u;
-    const unsigned sentinel8 = C8 - 8u;   // cell C-1 of the match plane holds -inf (and of the emission plane)
-    const rsrc_t rs_E = make_rsrc(HDP ? (const void *) (E_all + R->f_base) : (const void *) ev_all);
-    const unsigned seam_vo = lane == 0 ? 0u : OOB;           // lane 0 publishes
-    const unsigned sh = ST.seam_cap * 8u;   // bytes between a record's two values
-    unsigned sw = 0u, sr = ST.seam_cap * 16u;
-    if (lane == 0) {
-        seam_store(rs_seam, 0u, sw, sh, NEG_INF, NEG_INF);
-        seam_store(rs_seam, 0u, sw + 8u, sh, NEG_INF, NEG_INF);
-        seam_store(rs_seam, 0u, sr, sh, NEG_INF, NEG_INF);
-        seam_store(rs_seam, 0u, sr + 8u, sh, NEG_INF, NEG_INF);
-    }
-    if (lane == 0) s_b0[wid] = NEG_INF;
-    wave_fence();
-    double end_m, end_x, end_y;  // endStateProb / raggedEndStateProb (impl/stateMachine.c:1145-1173)
-    if (S->at_end && R->ragged_r) {
-        end_m = (T.t_mx + T.t_my) / 2.0; end_x = T.t_xx; end_y = T.t_yy;
-    } else {
-        end_m = T.t_mm; end_x = T.t_xm; end_y = T.t_ym;
-    }
-    int e0_r = 0, n_r = 0;   // seam array being read: record i <-> diagonal e0_r - (i - 1), i = 1 .. n_r
-
-    // ---- pass 1: strips from the highest columns down ----
-    for (int s = smax; s >= smin; s--) {
-        const int dlo = __builtin_amdgcn_readfirstlane(lo[s]), dhi = __builtin_amdgcn_readfirstlane(hi[s]);
-        if (dhi < dlo) {   // (a gap inside the band cannot happen; kept for safety)
-            if (lane == 0) seam_store(rs_seam, 0u, sw + 8u, sh, NEG_INF, NEG_INF);
-            wave_fence();
-            e0_r = 0; n_r = 0;
-            { const unsigned t_ = sw; sw = sr; sr = t_; }
-            continue;
-        }
-        // lead-in of two idle diagonals (seam values of dhi+1, dhi+2), rounded up to 3 (mod 4): the loop runs in groups of
-        // four diagonals (four prefetch stages: the forward values stream from HBM) and has a single exit, so the last group
-        // may end up to three (idle) diagonals below dlo
-        const int e0 = (dhi + 2) | 3;
-        const int e_stop = (dlo & ~3) - 1;
-        const int nst = e0 - e_stop;
-        if (lane == 0) seam_store(rs_seam, 0u, sw + (unsigned) (nst + 1) * 8u, sh, NEG_INF, NEG_INF);
-        const int x = 64 * s + lane;
-        const unsigned x8 = (unsigned) x * 8u;
-        double4 c = {0.0, 0.0, 0.0, 0.0};
-        if (!HDP) c = buf_load_f64x4(rs_xc, (x <= lX ? (unsigned) x : 0u) * 32u);
-        double mY1 = NEG_INF, sX = NEG_INF, sMe = NEG_INF, sMo = NEG_INF;
-        int e = e0;
-        // 64 row records covering diagonals [base, base + 63], base = (e & ~31) - 32: e .. e-4 are entries >= 28
-        // diagonals outside [dlo, dhi] (the lead-in, anything beyond the segment) get width 0: every lane idles there
-        auto tile_at = [&](int base) -> int4 {
-            const int i = base + lane;
-            int4 r = rows4[i < 0 ? 0 : i];
-            r.y = (i >= dlo && i <= dhi) ? r.y : 0;
-            return r;
-        };
-        // what the posterior side does on a diagonal, worked out for 64 diagonals at a time (one per lane) instead of by
-        // scalar counters every diagonal.  q = from - i: posterior diagonals have q >= 0, checkpoints sit at q = 0, 10, ...
-        //   bit 0: posterior diagonal that is not a checkpoint (forward + backward goes to the gapX plane)
-        //   bit 1: total-probability checkpoint (forward + backward and the backward gap sums go to vbuf / the side buffer)
-        //   bit 2: the diagonal above the posterior range: the match-through terms of the first checkpoint (the second pass
-        //          never comes here)                                 bits 8..: the checkpoint (bits 1, 2)
-        auto flags_at = [&](int base) -> int {
-            const int i = base + lane;
-            const int qi = from - i;
-            const bool post = qi >= 0 && i > to;
-            const int qq = qi >= 0 ? qi : 0;
-            const int ck_i = qq / SA_CKPT_EVERY, ph_i = qq - ck_i * SA_CKPT_EVERY;
-            const bool isck = post && ph_i == 0;
-            const bool above = qi == -1 && i - 1 > to;
-            return (post && !isck ? 1 : 0) | (isck ? 2 : 0) | (above ? 4 : 0) | ((isck ? ck_i : 0) << 8);
-        };
-        int4 tile = tile_at((e & ~31) - 32), tile_n = tile_at((e & ~31) - 64);
-        int ft = flags_at((e & ~31) - 32), ft_n = flags_at((e & ~31) - 64);
-        // records of 64 consecutive checkpoints, one per lane, from the first one this strip meets
-        int ckt_base = from - e >= 0 ? (from - e) / SA_CKPT_EVERY : 0;
-        auto ck_tile_at = [&](int base) -> int4 { const int i = base + lane; return cks4[i < n_ck ? i : (n_ck > 0 ? n_ck - 1 : 0)]; };
-        int4 ckt = ck_tile_at(ckt_base);
-        double pend_a = NEG_INF, pend_b = NEG_INF;
-        unsigned pend_svo = OOB, pend_sso = sw;   // (advanced by 8 bytes per diagonal)
-        // running values of the diagonal being requested (requests are issued for consecutive diagonals downwards)
-        unsigned evo_r = (unsigned) ((e - 1) * 8);   // byte offset of the event of column 0
-        int si_r = e0_r - e + 1;                     // its record in the seam array being read
-        const int n1_r = n_r + 1;
-
-        // li: entry of the requested diagonal in the tiles.  The forward match value is read on every diagonal (the lead-in
-        // of a traceback, a tenth of its diagonals, does not use it).
-        auto request = [&](StripInB &in, int li) {
-            if (!HDP) in.e = buf_load_f64(rs_ev, evo_r - x8, 0);
-            int si = si_r < 0 ? 0 : si_r;
-            si = si > n1_r ? n1_r : si;
-            const unsigned so = sr + (unsigned) si * 8u;
-            in.sa = buf_load_f64_l2(rs_seam, 0u, so);
-            in.sb = buf_load_f64_l2(rs_seam, 0u, so + sh);
-            const int xL = __builtin_amdgcn_readlane(tile.w, li), w = __builtin_amdgcn_readlane(tile.y, li);
-            const unsigned fo8 = (unsigned) __builtin_amdgcn_readlane(tile.z, li) * 8u;
-            const int t = x - xL;
-            const bool act = (unsigned) t < (unsigned) w;
-            in.fm = buf_load_f64_stream(rs_F, act ? (unsigned) t * 8u + fo8 : sentinel8, 0);
-            if (HDP) in.e = buf_load_f64(rs_E, act ? (unsigned) t * 8u + fo8 : sentinel8, 0);
-            evo_r -= 8u;
-            si_r++;
-        };
-        // one diagonal; the stage was requested four diagonals earlier and is refilled at the end; sMp holds mM of
-        // (x+1, y+1) (written two diagonals ago) and is overwritten
-        auto half = [&](auto head, StripInB &cur, double &sMp) {
-            const int li = (e & 31) + 32;
-            seam_store(rs_seam, pend_svo, pend_sso, sh, pend_a, pend_b);
-            const int xL = __builtin_amdgcn_readlane(tile.w, li), w = __builtin_amdgcn_readlane(tile.y, li);
-            const unsigned fo8 = (unsigned) __builtin_amdgcn_readlane(tile.z, li) * 8u;
-            const int fl = __builtin_amdgcn_readlane(ft, li);
-            const int t = x - xL;
-            const bool act = (unsigned) t < (unsigned) w;
-            double lM, lY_;
-            if (HDP) {
-                lM = cur.e; lY_ = cur.e;
-            } else {
-                const double pmask = __hiloint2double(act ? 0 : 0x7ff00000, 0);
-                const double a = (cur.e - c.x) * c.y;
-                emit_gauss_q(c, fma(a, a, pmask), lM, lY_);
-            }
-            // (plain table: the per-site tables of the forward sweep cost the backward one more than they save -- measured)
-            LaP pm, px, py;
-            la_prep(pm, sMp + T.t_mm, mY1 + T.t_my);
-            la_prep(px, sMp + T.t_xm, sX + T.t_xx);
-            la_prep(py, sMp + T.t_ym, mY1 + T.t_yy);
-            la_fetch(pm, LT);
-            la_fetch(px, LT);
-            la_fetch(py, LT);
-            __builtin_amdgcn_sched_barrier(0);
-            const double tm1 = la_finish(pm);
-            double tx = la_finish(px);
-            double ty = la_finish(py);
-            double tm = la_fast(LT, tm1, sX + T.t_mx);
-            if (decltype(head)::value) {
-                // the diagonal the traceback starts on (one of a strip's first six): every message above it is -inf, so are
-                // tm, tx, ty -- the end state enters as a maximum
-                const bool is_start = e == start;
-                tm = vmax(tm, is_start ? end_m : NEG_INF);
-                tx = vmax(tx, is_start ? end_x : NEG_INF);
-                ty = vmax(ty, is_start ? end_y : NEG_INF);
-            }
-            const double mM = tm + lM;               // -inf outside the band
-            mY1 = ty + lY_;
-            const double mX = act ? tx + SA_LOG_GAPX : NEG_INF;
-            sX = strip_from_above(mX, cur.sb);
-            sMp = strip_from_above(mM, cur.sa);
-            pend_a = mM; pend_b = mX; pend_svo = seam_vo; pend_sso += 8u;
-            // posterior side (all conditions wave-uniform; no load and no wait inside the branches)
-            const double fb = cur.fm + tm;   // -inf for lanes without a cell
-            const unsigned vo = act ? (unsigned) t * 8u : OOB;
-            if (fl & 1) buf_store_f64(rs_F, vo, fo8 + C8, fb);   // the cell's slot of the gapX plane: read back by pass 2
-            if (fl & 6) {
-                const int cl = (fl >> 8) - ckt_base;                      // (the tile is moved on between the 32-diagonal blocks)
-                const long long voff = ((long long) __builtin_amdgcn_readlane(ckt.y, cl) << 32) |
-                                       (unsigned) __builtin_amdgcn_readlane(ckt.x, cl);
-                if (fl & 2) {   // a checkpoint: what pass 2 needs for the cell's term
-                    buf_store_f64(make_rsrc(vbuf + voff), vo, 0u, fb);
-                    buf_store_f64(make_rsrc(ckxy + voff), vo, 0u, tx);
-                    buf_store_f64(make_rsrc(ckxy + ST.ck_half + voff), vo, 0u, ty);
-                } else {        // the diagonal above the first checkpoint: its match-through terms
-                    const int nA = __builtin_amdgcn_readlane(ckt.z, cl), nB = __builtin_amdgcn_readlane(ckt.w, cl);
-                    if (nB > 0) {
-                        buf_store_f64(make_rsrc(vbuf + voff + nA), vo, 0u, fb);
-                        __hip_atomic_fetch_max(&s_b0[wid], fb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            request(cur, li - 4);   // the stage is free again
-            e--;
-        };
-        auto next_tile = [&]() {   // e just crossed a multiple of 32 downwards: (e & 31) == 31
-            tile = tile_n; ft = ft_n;
-            tile_n = tile_at((e & ~31) - 64);
-            ft_n = flags_at((e & ~31) - 64);
-            const int cki = from - e >= 0 ? (from - e) / SA_CKPT_EVERY : 0;
-            if (cki + 8 - ckt_base >= 64) {   // the next 32 diagonals meet at most four more checkpoints
-                ckt_base = cki;
-                ckt = ck_tile_at(ckt_base);
-            }
-        };
-        StripInB S0, S1, S2, S3;
-        request(S0, (e & 31) + 32);
-        request(S1, (e & 31) + 31);
-        request(S2, (e & 31) + 30);
-        request(S3, (e & 31) + 29);
-        const std::integral_constant<bool, false> BODY;
-        const std::integral_constant<bool, true> HEAD;
-        // the first two groups hold the lead-in and, when the strip reaches it, the diagonal the traceback starts on
-        half(HEAD, S0, sMo);
-        half(HEAD, S1, sMe);
-        half(HEAD, S2, sMo);
-        half(HEAD, S3, sMe);
-        if ((e & 31) == 31) next_tile();
-        half(HEAD, S0, sMo);
-        half(HEAD, S1, sMe);
-        half(HEAD, S2, sMo);
-        half(HEAD, S3, sMe);
-        while (e > e_stop) {
-            if ((e & 31) == 31) next_tile();
-            do {
-                half(BODY, S0, sMo);
-                half(BODY, S1, sMe);
-                half(BODY, S2, sMo);
-                half(BODY, S3, sMe);
-            } while (e > e_stop && (e & 31) != 31);
-        }
-        seam_store(rs_seam, pend_svo, pend_sso, sh, pend_a, pend_b);
-        wave_fence();
-        e0_r = e0; n_r = nst;
-        { const unsigned t_ = sw; sw = sr; sr = t_; }
-    }
-
-    // ---- pass 2: checkpoint terms and candidates, diagonals downwards (output order), cells upwards.  A diagonal's first 128
-    // cells travel through two registers requested four diagonals ahead; wider diagonals read the rest on the spot.  Border
-    // cells and lanes without a cell hold -inf (the forward value of a border cell is -inf), so the candidate test is one
-    // compare.  A checkpoint's bound is the maximum of its per-cell terms (computed here, on its diagonal) and of the
-    // match-through terms of the diagonal above it (forward + backward of that diagonal's cells: the diagonal before). ----
-    sa_cand_t *my_cands = cands + S->cand_off;
-    const int cand_cap = S->cand_cap;
-    int count = 0;
-    if (from > to) {
-        auto emit = [&](bool pass, int x, int e_, double fb) {
-            const unsigned long long mask = __ballot(pass);
-            if (mask) {
-                const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-                if (pass) {
-                    const int pos = count + rank;
-                    if (pos < cand_cap) {
-                        sa_cand_t cd;
-                        cd.x = x - 1; cd.y = e_ - x - 1; cd.path = 0; cd.pad = 0; cd.fb = fb;
-                        my_cands[pos] = cd;
-                    } else {
-                        overflow[0] = 1;
-                    }
-                }
-                count += __popcll(mask);
-            }
-        };
-        const unsigned lane8 = (unsigned) lane * 8u;   // byte offset of the lane's cell inside a chunk of a diagonal
-        double lim = __builtin_inf();
-        double maxB = s_b0[wid];   // match-through maximum of the checkpoint ahead (the first one's: from the sweep)
-        int ckt_base = 0;
-        int4 ckt = cks4[lane < n_ck ? lane : (n_ck > 0 ? n_ck - 1 : 0)];   // records of 64 consecutive checkpoints
-        auto ck_record = [&](int ci, long long &voff, int &nA, int &nB) {
-            if (ci - ckt_base >= 64) {
-                ckt_base = ci;
-                ckt = cks4[ci + lane < n_ck ? ci + lane : (n_ck > 0 ? n_ck - 1 : 0)];
-            }
-            const int cl = ci - ckt_base;
-            voff = ((long long) __builtin_amdgcn_readlane(ckt.y, cl) << 32) | (unsigned) __builtin_amdgcn_readlane(ckt.x, cl);
-            nA = __builtin_amdgcn_readlane(ckt.z, cl); nB = __builtin_amdgcn_readlane(ckt.w, cl);
-        };
-        int e = from;
-        while (e > to) {
-            // the diagonals [eb, e] of one 64-aligned block of row records; groups of four (a single loop exit), diagonals
-            // below eb count as empty
-            const int tb = e & ~63;
-            const int eb = tb > to + 1 ? tb : to + 1;
-            const int4 tile = rows4[tb + lane];
-            int ph = (from - e) % SA_CKPT_EVERY, cki = (from - e) / SA_CKPT_EVERY;
-            double fa0, fb0, fa1, fb1, fa2, fb2, fa3, fb3;
-            auto fetch = [&](double &fa, double &fb_, int e_) {
-                const int li = (e_ - tb) & 63;
-                int w = __builtin_amdgcn_readlane(tile.y, li);
-                const unsigned fo8 = (unsigned) __builtin_amdgcn_readlane(tile.z, li) * 8u + C8;
-                w = e_ >= eb ? w : 0;
-                fa = buf_load_f64_l2(rs_F, lane < w ? lane8 + fo8 : sentinel8, 0);
-                fb_ = buf_load_f64_l2(rs_F, lane + 64 < w ? lane8 + 512u + fo8 : sentinel8, 0);
-            };
-            auto step = [&](double &fa, double &fb_) {
-                const int li = (e - tb) & 63;
-                const int w = e >= eb ? __builtin_amdgcn_readlane(tile.y, li) : 0;
-                if (ph == 0 && e >= eb) {
-                    // ---- a checkpoint diagonal: per-cell terms logAdd(logAdd(f.m + b.m, f.x + b.x), f.y + b.y), their maximum,
-                    // and this diagonal's candidates (its forward + backward sits in vbuf, not in the gapX plane) ----
-                    const int xL = __builtin_amdgcn_readlane(tile.w, li);
-                    const unsigned fo8 = (unsigned) __builtin_amdgcn_readlane(tile.z, li) * 8u;
-                    long long voff; int nA, nB;
-                    ck_record(cki, voff, nA, nB);
-                    const rsrc_t rs_v = make_rsrc(vbuf + voff), rs_tx = make_rsrc(ckxy + voff), rs_ty = make_rsrc(ckxy + ST.ck_half + voff);
-                    // one chunk: the five loads, the term, its store; returns forward + backward of the lane's cell
-                    auto term = [&](int t, double &v) -> double {
-                        const unsigned vo = t < w ? (unsigned) t * 8u : OOB;
-                        const double fbv = buf_load_f64_l2(rs_v, vo, 0u);
-                        const double fx = buf_load_f64(rs_F, vo, fo8 + C8), fy = buf_load_f64(rs_F, vo, fo8 + 2u * C8);
-                        const double tx = buf_load_f64_l2(rs_tx, vo, 0u), ty = buf_load_f64_l2(rs_ty, vo, 0u);
-                        v = la_fast(LT, la_fast(LT, fbv, fx + tx), fy + ty);
-                        v = t < w ? v : NEG_INF;
-                        buf_store_f64(rs_v, vo, 0u, v);
-                        return t < w ? fbv : NEG_INF;
-                    };
-                    // the first 128 cells stay in registers for the candidate sweep; wider diagonals park the rest
-                    double v0, v1 = NEG_INF, q1 = NEG_INF;
-                    const double q0 = term(lane, v0);
-                    if (w > 64) q1 = term(lane + 64, v1);
-                    double mA = vmax(v0, v1);
-                    for (int ch = 2; ch * 64 < w; ch++) {
-                        const int t = ch * 64 + lane;
-                        double v;
-                        const double fbv = term(t, v);
-                        buf_store_f64(rs_tx, t < w ? (unsigned) t * 8u : OOB, 0u, fbv);   // parked (its tx has been read)
-                        mA = vmax(mA, v);
-                    }
-                    mA = wave_max(mA);
-                    // (flat posteriors: the terms of the diagonal's first 128 cells within t of the maximum bound the total from
-                    // below by max + log n - t, sa_fast.inc tight_bound_gain -- a count over some of the terms is still a bound)
-                    if (HDP) mA += tight_bound_gain2(mA - v0, mA - v1);
-                    const double Mc = (nB > 0 && maxB > mA) ? maxB : mA;
-                    lim = (Mc > NEG_INF) ? Mc + T.thr_off : __builtin_inf();
-                    emit(q0 >= lim, xL + lane, e, q0);   // (a border cell's value is -inf)
-                    if (w > 64) emit(q1 >= lim, xL + lane + 64, e, q1);
-                    if (w > 128) {
-                        wave_fence();
-                        for (int ch = 2; ch * 64 < w; ch++) {
-                            const int t = ch * 64 + lane;
-                            const double fbv = buf_load_f64_l2(rs_tx, t < w ? (unsigned) t * 8u : OOB, 0u);
-                            emit(t < w && fbv >= lim, xL + t, e, fbv);
-                        }
-                    }
-                } else {
-                    if (__ballot(fa >= lim) | __ballot(fb_ >= lim)) {   // (rare: about one diagonal in two holds a pair)
-                        const int xL = __builtin_amdgcn_readlane(tile.w, li);
-                        emit(fa >= lim, xL + lane, e, fa);
-                        emit(fb_ >= lim, xL + lane + 64, e, fb_);
-                    }
-                    const bool above = ph == SA_CKPT_EVERY - 1 && e - 1 > to && e >= eb;   // the next diagonal is a checkpoint
-                    if (w > 128 || above) {
-                        const int xL = __builtin_amdgcn_readlane(tile.w, li);
-                        const unsigned fo8 = (unsigned) __builtin_amdgcn_readlane(tile.z, li) * 8u;
-                        long long voff = 0; int nA = 0, nB = 0;
-                        if (above) ck_record(cki + 1, voff, nA, nB);
-                        const bool terms = above && nB > 0;     // this diagonal's cells are that checkpoint's match-through terms
-                        const rsrc_t rs_b = make_rsrc(vbuf + voff + nA);
-                        double mB = NEG_INF;
-                        if (terms) {
-                            buf_store_f64(rs_b, lane < w ? lane8 : OOB, 0u, fa);
-                            buf_store_f64(rs_b, lane + 64 < w ? lane8 + 512u : OOB, 0u, fb_);
-                            mB = vmax(fa, fb_);
-                        }
-                        for (int ch = 2; ch * 64 < w; ch++) {   // wider than 128 cells: the rest, read on the spot
-                            const int t = ch * 64 + lane;
-                            const double fbv = buf_load_f64_l2(rs_F, t < w ? (unsigned) t * 8u + fo8 + C8 : sentinel8, 0);
-                            emit(fbv >= lim, xL + t, e, fbv);
-                            if (terms) {
-                                buf_store_f64(rs_b, t < w ? (unsigned) t * 8u : OOB, 0u, fbv);
-                                mB = vmax(mB, fbv);
-                            }
-                        }
-                        if (above) maxB = wave_max(mB);
-                    }
-                }
-                fetch(fa, fb_, e - 4);
-                if (++ph == SA_CKPT_EVERY) { ph = 0; cki++; }
-                e--;
-            };
-            fetch(fa0, fb0, e); fetch(fa1, fb1, e - 1); fetch(fa2, fb2, e - 2); fetch(fa3, fb3, e - 3);
-            do {
-                step(fa0, fb0);
-                step(fa1, fb1);
-                step(fa2, fb2);
-                step(fa3, fb3);
-            } while (e >= eb);
-            e = eb - 1;
-        }
-    }
-    if (lane == 0) cand_count[seg] = count < cand_cap ? count : cand_cap;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// backward in ONE pass (round 4).  The sweep of k_bwd_strip with the posterior side folded in: the candidate bound is known
-// before the sweep starts (the traceback's speculative total, above), so
-//   * a posterior cell is tested and, when it passes, appended to the segment's candidates right away -- nothing is parked
-//     in the gapX plane (8 B per posterior cell written and read again by the second pass of k_bwd_strip) and no second pass
-//     walks the diagonals;
+// The candidate bound is known before the sweep starts (the traceback's speculative total, above), so
+//   * a posterior cell is tested and, when it passes, appended to the segment's candidates right away;
 //   * a checkpoint's per-cell terms logAdd(logAdd(f.m + b.m, f.x + b.x), f.y + b.y) and the match-through terms of the diagonal
 //     above it go straight to vbuf, in cell order, where k_fold reads them (the forward gap states of a checkpoint diagonal are
-//     loaded inside that diagonal's branch: one diagonal in ten; no side buffer);
+//     loaded inside that diagonal's branch: one diagonal in ten);
 //   * candidates arrive strip by strip (high columns first), not in output order: k_finalize tests them against the exact
-//     totals as before and k_gather sorts a segment's survivors by (diagonal, column) before it writes them (sa_hip.hip).
-// The arithmetic of every value that reaches the results is that of k_bwd_strip: pairs are bit-identical (tested).
-// ---------------------------------------------------------------------------------------------------
+//     totals as for every other kernel and k_gather_sorted writes a segment's survivors in (diagonal, column) order (sa_hip.hip).
 template <bool HDP>
 __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_eu(STRIP_BWD_OCC, STRIP_BWD_OCC))) void k_bwd_strip1(
     const sa_region_t *__restrict__ regions, const sa_seg_t *__restrict__ segs, const sa_row_t *__restrict__ rows_all,
@@ -1065,7 +641,6 @@ static void launch_fwd_strip(const DevPlan &P, const int *ids, int n, hipStream_
         hipLaunchKernelGGL(k_fwd_strip<false>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.rows,
                            P.pk, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, seam, ST, ids, n, (const double *) nullptr, P.segs);
 }
-// the one-pass sweep (ST.spec set)
 static void launch_bwd_strip1(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, StripT ST) {
     ST.f = make_fast_t(P);
     if (P.m.hdp)
@@ -1076,15 +651,4 @@ static void launch_bwd_strip1(const DevPlan &P, const int *ids, int n, hipStream
         hipLaunchKernelGGL(k_bwd_strip1<false>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs,
                            P.rows, P.cks, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, P.cands, P.cand_count, P.overflow,
                            seam, ST, ids, n, (const double *) nullptr);
-}
-static void launch_bwd_strip(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, double *ckxy, StripT ST) {
-    ST.f = make_fast_t(P);
-    if (P.m.hdp)
-        hipLaunchKernelGGL(k_bwd_strip<true>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs,
-                           P.rows, P.cks, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, ckxy, P.cands, P.cand_count,
-                           P.overflow, seam, ST, ids, n, (const double *) P.E);
-    else
-        hipLaunchKernelGGL(k_bwd_strip<false>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs,
-                           P.rows, P.cks, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, ckxy, P.cands, P.cand_count,
-                           P.overflow, seam, ST, ids, n, (const double *) nullptr);
 }

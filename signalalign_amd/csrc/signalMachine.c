@@ -931,10 +931,9 @@ static void output_one(int64_t j, void *ctx) {
         rd->failed = 1;
         return;
     }
-    /* Round 4: the GPU stage no longer expands every job's pairs into freshly allocated sa_pair_t arrays on the main thread (523 MB
-     * per slice of 2048 long reads); the rows are expanded here, job by job on the rendering threads, from the packed 16-byte
-     * records the batch holds in page-locked memory.  (Measured: no difference in wall time -- 2.42-2.55 s against 2.49 s per 6144
-     * long reads, SA_CLI_EXPAND_EARLY=1 -- the front door is bound by the CPU time of parsing and rendering, not by this.) */
+    /* The rows are expanded here, job by job on the rendering threads, from the packed records the batch holds in page-locked
+     * memory: the GPU stage does not expand every job's pairs into freshly allocated sa_pair_t arrays on the main thread (523 MB
+     * per slice of 2048 long reads). */
     sa_pair_t *mine[2] = {NULL, NULL};
     const sa_pair_t *pp[2] = {NULL, NULL};
     for (int s = 0; s < n_strands; s++) {
@@ -1046,8 +1045,7 @@ static void *slice_prepare(void *arg) {
     return NULL;
 }
 
-/* What the GPU stage of a slice leaves for its rendering: the outputs of slice k are written (on a thread of their own) while
- * the GPU stage of slice k + 1 runs -- 30 000 long reads: GPU stage 3.8 s, rendering 3.9 s, one after the other before. */
+/* What the GPU stage of a slice leaves for its rendering */
 static void release_read(read_t *rd);
 typedef struct {
     run_t *Rp;
@@ -1064,9 +1062,8 @@ typedef struct {
     int p8_s[2];          /* see out_job_t */
     sa_site_call_t **calls_s[2];   /* see out_job_t */
     int64_t *n_calls_s[2];
-    int64_t n_failed;     /* out */
 } render_job_t;
-static void *render_slice(void *arg);
+static int64_t render_slice(render_job_t *job);
 
 /* GPU stage of a slice; returns the rendering job (NULL: nothing left to render -- the expectations mode writes its files
  * here -- with the number of failed reads in *n_failed_now) */
@@ -1141,13 +1138,13 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
      * made of the rows SA_FLAG_VC_ROWS would drop; -s 1 then filters on the host, write_vc) */
     const int want_calls = R.site_calls || R.agg_path != NULL;
     const unsigned calls_flag = want_calls ? SA_FLAG_SITE_CALLS : 0u;
-    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !want_calls && !getenv("SA_CLI_EXPAND_EARLY") && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
+    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !want_calls && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
     sa_site_call_t **calls_s[2] = {NULL, NULL};
     int64_t *n_calls_s[2] = {NULL, NULL};
     /* -s 0 / -s 2 without --mea: 8-byte result records where the batch allows them (one path per cell: no ambiguity letter in any
      * read's reference; fewer than 2^20 positions and events per read) -- the planner says SA_EUNSUPPORTED otherwise and the strand's
      * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker). */
-    const unsigned p8_want = ((R.out_fmt == 0 || R.out_fmt == 2) && !R.mea && !want_calls && !getenv("SA_CLI_EXPAND_EARLY") && !getenv("SA_CLI_PAIRS16")) ? SA_FLAG_PAIRS8 : 0u;
+    const unsigned p8_want = ((R.out_fmt == 0 || R.out_fmt == 2) && !R.mea && !want_calls && !getenv("SA_CLI_PAIRS16")) ? SA_FLAG_PAIRS8 : 0u;
     int p8_used[2] = {0, 0};
     for (int s = 0; s < n_strands; s++) {
         pairs[s] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(sa_pair_t *));
@@ -1160,10 +1157,7 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
             n_calls_s[s] = calloc((size_t) n_ok, sizeof(int64_t));
         }
         int rc;
-        if (!R.mea && !want_calls && getenv("SA_CLI_EXPAND_EARLY")) {   /* (A/B hook: the one-shot call of rounds 1-3) */
-            rc = sa_align_batch(R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, 0, pairs[s],
-                                n_pairs[s]);
-        } else if (!R.mea) {   /* the batch stays alive for the rendering, which expands its packed records job by job */
+        if (!R.mea) {   /* the batch stays alive for the rendering, which expands its packed records job by job */
             sa_batch_t *b = NULL;
             rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device,
                                  vc_flag | p8_want | calls_flag);
@@ -1180,7 +1174,7 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
                 for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) rc = sa_batch_all_pairs_summary(b, j, &all_n[s][j], &all_sum[s][j]);
             }
             /* only the packed pairs (pinned host memory) are read from here on: the batch's HBM goes back now, so that the
-             * complement strand's batch -- and, with a render thread, the next slice's -- plans into the whole card */
+             * complement strand's batch plans into the whole card */
             if (rc == SA_OK) rc = sa_batch_release_device(b);
             if (rc == SA_OK) batches[s] = b;
             else sa_batch_destroy(b);
@@ -1244,9 +1238,9 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
 #undef R
 }
 
-/* rendering of a slice (one file per read, in parallel), summary lines in read order, then the reads' memory goes back */
-static void *render_slice(void *arg) {
-    render_job_t *job = arg;
+/* rendering of a slice (one file per read, in parallel), summary lines in read order, then the reads' memory goes back;
+ * returns the number of the slice's reads that failed */
+static int64_t render_slice(render_job_t *job) {
     run_t *Rp = job->Rp;
 #define R (*Rp)
     read_t *reads = job->reads;
@@ -1297,8 +1291,7 @@ static void *render_slice(void *arg) {
     for (int s = 0; s < n_strands; s++) { free(pairs[s]); free(n_pairs[s]); free(job->all_n_s[s]); free(job->all_sum_s[s]); if (R.mea) { free(mea[s]); free(n_mea[s]); } }
     free(score); free(bj); free(who);
     for (int64_t i = 0; i < n_reads; i++) release_read(&reads[i]);
-    job->n_failed = n_failed;
-    return NULL;
+    return n_failed;
 #undef R
 }
 
@@ -1475,12 +1468,10 @@ int main(int argc, char **argv) {
     }
     /* the reads go through in slices of --batch-reads (default 2048): bounded host and device memory for any manifest */
     /* Two slices are in the air: while the GPU stage and the rendering of slice k run here, a second thread does the host side
-     * of slice k+1 (10 000 short reads: host stage 0.39 s, GPU 0.28 s, rendering 0.25 s, one after the other before).  A third
-     * stage -- rendering on a thread of its own -- exists behind SA_CLI_RENDER_THREAD=1 and does not pay (see below). */
+     * of slice k+1 (10 000 short reads: host stage 0.39 s, GPU 0.28 s, rendering 0.25 s, one after the other before).  Rendering
+     * stays on this thread, slice after slice, so the summary lines stay in read order: the front door is bound by host CPU
+     * time -- text parsing and TSV rendering -- not by the order of its stages. */
     int64_t n_failed = 0;
-    pthread_t render_th;
-    render_job_t *render_prev = NULL;
-    int rendering = 0;
     slice_prep_t cur = {&R, reads, n_reads < batch_reads ? n_reads : batch_reads, batch_mode}, nxt;
     slice_prepare(&cur);
     for (int64_t off = 0; off < n_reads; off += batch_reads) {
@@ -1496,32 +1487,8 @@ int main(int argc, char **argv) {
         int64_t failed_now = 0;
         render_job_t *job = run_slice(&R, reads + off, n, batch_mode, device, &failed_now);
         n_failed += failed_now;
-        /* the previous slice's rendering has had this slice's GPU stage to finish in; slices are rendered one after the other,
-         * so the summary lines stay in read order */
-        if (rendering) {
-            pthread_join(render_th, NULL);
-            n_failed += render_prev->n_failed;
-            free(render_prev);
-            rendering = 0;
-        }
-        if (job) {
-            /* SA_CLI_RENDER_THREAD=1: the slice is rendered on a thread of its own while the next slice's GPU stage runs.
-             * Measured on the 16-CPU quota of a GPU box and found SLOWER (30 000 long reads: 9.9 against 8.5 s; 100 000 short
-             * reads: no difference): the front door is bound by host CPU time -- text parsing and TSV rendering, 110
-             * thread-seconds per 30 000 long reads on 16 CPUs -- not by the order of its stages. */
-            const char *ert = getenv("SA_CLI_RENDER_THREAD");
-            if (ert && atoi(ert) == 1) {
-                render_prev = job;
-                rendering = pthread_create(&render_th, NULL, render_slice, job) == 0;
-            }
-            if (!rendering) { render_slice(job); n_failed += job->n_failed; free(job); }
-        }
+        if (job) { n_failed += render_slice(job); free(job); }
         if (started) pthread_join(th, NULL);
-    }
-    if (rendering) {
-        pthread_join(render_th, NULL);
-        n_failed += render_prev->n_failed;
-        free(render_prev);
     }
     if (R.agg_path) write_aggregate(R.agg_path);
     if (batch_mode)

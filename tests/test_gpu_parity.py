@@ -356,7 +356,7 @@ def test_ring_kernels_wide_bands_every_read_against_the_oracle(oracle, monkeypat
 
 def test_strip_kernels_wide_bands_bit_identical_to_the_ring_kernels(oracle, monkeypatch):
     """One-path regions with wide bands run on the strip kernels (sa_strip.inc: a lane is a reference column, strips of 64
-    columns, seams through HBM, candidates by a second pass over forward + backward).  Per cell they do the ring kernels'
+    columns, seams through HBM, candidates tested against the traceback's speculative total during the backward sweep).  Per cell they do the ring kernels'
     arithmetic in the ring kernels' order, so every pair -- rows, order, prob_e7 -- must equal the ring kernels' (SA_STRIP=0),
     and both are within the tolerance of the CPU restatement.  Cases: anchors of a real guide alignment, no anchors at all
     (bands of several hundred cells, one strip holds whole diagonals), reads shorter than one strip, several traceback
@@ -396,18 +396,18 @@ def test_strip_kernels_wide_bands_bit_identical_to_the_ring_kernels(oracle, monk
     again, _ = _run(pm, p, jobs)                                      # same bytes on a second batch (seams, atomics, planes)
     for j in range(len(jobs)):
         assert np.array_equal(again[j], got[j]), j
-    # round 4: `got` came from the one-pass backward sweep (candidates against the traceback's speculative total, survivors put in
-    # order by k_gather_strip); the two-pass sweep of round 2 (SA_STRIP_PASSES=2) gives the same bytes -- at several thresholds
-    # (a low one multiplies the candidates per diagonal, threshold 0.5 leaves diagonals without any) and with short tracebacks
+    # the strip kernels' candidates are tested against the traceback's speculative total and put in order by k_gather_sorted:
+    # the same bytes as the ring kernels' at several thresholds (a low one multiplies the candidates per diagonal, threshold 0.5
+    # leaves diagonals without any) and with short tracebacks
     for kw in (dict(), dict(threshold=0.0005), dict(threshold=0.5), dict(expansion=20, trace_back=30, min_diags=150)):
         q = sa.default_params(**kw)
-        one, st1 = _run(pm, q, jobs)
-        monkeypatch.setenv("SA_STRIP_PASSES", "2")
-        two, st2p = _run(pm, q, jobs)
-        monkeypatch.delenv("SA_STRIP_PASSES")
-        assert st1.n_strip_regions == st2p.n_strip_regions and st1.n_strip_regions >= 12
+        strip, st1 = _run(pm, q, jobs)
+        monkeypatch.setenv("SA_STRIP", "0")
+        ring, st2r = _run(pm, q, jobs)
+        monkeypatch.delenv("SA_STRIP")
+        assert st1.n_strip_regions >= 12 and st2r.n_strip_regions == 0
         for j in range(len(jobs)):
-            assert np.array_equal(one[j], two[j]), (kw, j, len(one[j]), len(two[j]))
+            assert np.array_equal(strip[j], ring[j]), (kw, j, len(strip[j]), len(ring[j]))
 
 
 def test_ring_kernels_ambiguous_positions_every_read_against_the_oracle(oracle, monkeypatch):
