@@ -685,10 +685,7 @@ static void dplan_release(sa_batch *b, DPlanPending *P, bool arrays_too) {
     if (P->back) g_sa_pool.put(SaPool::PINNED, P->back);
     for (void *q : P->temps) g_sa_pool.put(SaPool::DEVICE, q);
     if (arrays_too) {
-        void *mine[] = {b->d_regions, b->d_rows, b->d_pk, b->d_poff, b->d_pid, b->d_ev, b->d_segs, b->d_cks, b->d_prec};
-        for (void *q : mine) g_sa_pool.put(SaPool::DEVICE, q);
-        b->d_regions = nullptr; b->d_rows = nullptr; b->d_pk = nullptr; b->d_poff = nullptr; b->d_pid = nullptr; b->d_prec = nullptr;
-        b->d_ev = nullptr; b->d_segs = nullptr; b->d_cks = nullptr;
+        b->put_blocks(sa_batch::BLK_PLAN, sa_batch::BLK_REST);
         free(P->pl); free(P->h_regions); free(P->h_jobs); free(P->h_segs);
     }
     delete P;
@@ -706,7 +703,6 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
         p->min_diags_between_trace_back < 2 || p->trace_back_diagonals + 1 >= p->min_diags_between_trace_back)
         return 1;   // (sa_plan_build reports it)
     const bool trace = getenv("SA_TRACE") != nullptr;
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double t0 = now_ms();
     DPlanArgs A;
     memset(&A, 0, sizeof(A));
@@ -1090,7 +1086,6 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
 // not take (everything released: the host planner takes over and names errors), or < 0
 static int dplan_back(sa_batch *b, DPlanPending *P) {
     const bool trace = getenv("SA_TRACE") != nullptr;
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const hipError_t e = hipEventSynchronize(P->done);   // (a blocking-sync event: the waiting thread sleeps)
     g_handles.park(P->done, b->device);
     P->done = nullptr;

@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <mutex>
 #include <new>
@@ -1203,55 +1204,78 @@ __global__ __launch_bounds__(256) void k_fill_xc(const sa_region_t *__restrict__
         }                                                                                      \
     } while (0)
 
+// Launch classes: every chunk (forward pass over regions) and every group (traceback segments) has one id list per class, laid out
+// in d_ids in this order.  launch_class() says which class a region -- and so each of its segments -- belongs to.
+enum {
+    LC_GENERIC = 0,            // memory-resident kernels
+    LC_FAST = 1,               // register kernels
+    LC_RING = 2,               // ring kernels: LC_RING + multi * 8 + cap class, cap = 64 * (class + 1)
+    LC_STRIP = LC_RING + 16,   // one-path ring-kernel regions taken by the strip kernels (sa_strip.inc)
+    LC_N
+};
+struct sa_ids {
+    long long off;   // into d_ids
+    int n;
+};
+// how many of the classes [c0, c1) have a non-empty list
+static int n_nonempty(const sa_ids *ids, int c0, int c1) {
+    int n = 0;
+    for (int c = c0; c < c1; c++) n += ids[c].n > 0;
+    return n;
+}
+static int launch_class(const sa_region_t &R, bool strip_on) {
+    if (strip_region(&R, strip_on)) return LC_STRIP;
+    if (R.kind == SA_KIND_RING) {
+        const int cl = R.max_rowpaths <= 64 ? 0 : (int) ((R.max_rowpaths - 1) / 64);   // <= 7 (SA_RING_MAX_ROWPATHS)
+        return LC_RING + (R.max_p > 1 ? 8 : 0) + (cl > 7 ? 7 : cl);
+    }
+    return R.kind == SA_KIND_FAST ? LC_FAST : LC_GENERIC;
+}
 struct sa_launch_chunk {
-    long long ids_gr, ids_fr;  // offsets into d_ids: memory-resident / register-kernel regions
-    int ngr, nfr;
-    long long ids_rr[16];      // ring-kernel regions by class: [multi * 8 + cap class], cap = 64 * (class + 1)
-    int nrr[16];
-    long long ids_st;          // one-path ring-kernel regions taken by the strip kernels (sa_strip.inc)
-    int nst;
+    sa_ids ids[LC_N];          // regions
     int g0, g1;                // groups [g0, g1)
 };
 struct sa_launch_group {
     long long seg0, seg1, ck0, ck1;
-    long long ids_gs, ids_fs;           // segments of memory-resident / register-kernel regions
-    int ngs, nfs;
-    long long ids_rs[16];               // segments of ring-kernel regions, by the class of their region
-    int nrs[16];
-    long long ids_ss;                   // segments of strip-kernel regions
-    int nss;
-    unsigned seam_first;                // their first wave slot in the seam storage
+    sa_ids ids[LC_N];          // segments, by the class of their region
+    unsigned seam_first;       // their first wave slot in the seam storage
 };
 
+static double now_ms() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
 struct sa_batch {
-    sa_plan_t *plan;
-    int device;
-    unsigned flags;
-    hipStream_t stream;            // == cstream[0]
-    hipStream_t cstream[2];        // compute streams; groups alternate between them
-    hipStream_t xstream[2];        // two more, for the forward launches of the ring-kernel classes
-    // device buffers
-    sa_region_t *d_regions; sa_row_t *d_rows; int *d_pk; int *d_poff; int *d_pid; int *d_px; double *d_xc; double *d_ev;
-    sa_prec_t *d_prec;
-    size_t d_blk_bytes;
-    char *d_blk;           // SA_FLAG_INPUTS_IN_HOST_BLOCK: the image of the caller's block (its event records are gathered on this
-                           // batch's own stream, possibly after sa_batch_create has returned: kept until the batch goes)
-    sa_seg_t *d_segs; sa_ck_t *d_cks;
-    double *d_F; double *d_E; double *d_vbuf; sa_cand_t *d_cands; int *d_cand_count; int *d_overflow; double *d_totals;
-    double *d_bscratch;
-    double *d_gsum, *d_gmc;  // expectation mode only
-    bool expect;
-    bool relax;              // memory-resident kernels in their RELAX flavour
-    int ring_cap;            // cell-paths per diagonal of their LDS ring (0: rows stay in global memory)
-    int wide_cap;            // cells per row of the register kernels' LDS ring for wide diagonals (0: every diagonal fits)
-    int gen_threads;         // 64, or 128 when a diagonal of a memory-resident region holds more than 64 cell-paths
-    bool strip_on;           // one-path ring-kernel regions run on the strip kernels (default; SA_STRIP=0: ring kernels)
-    double *d_spec;          // ring / strip kernels: speculative totals, one per segment (NaN: a segment of another kernel family)
-    double spec_slack;       // candidates: forward + backward >= spec - slack + log(threshold); grows when a pass has to be repeated
-    int spec_repeats;        // passes repeated because of it (the second repeat drops the bound altogether)
-    bool released;           // sa_batch_release_device: the working storage went back to the pool, the results stay
-    unsigned long long *d_sortkey;   // k_gather_sorted's scratch: 8 + 4 bytes per candidate slot
-    unsigned *d_sortidx;
+    sa_plan_t *plan = nullptr;
+    int device = -1;
+    unsigned flags = 0;
+    hipStream_t stream = nullptr;             // == cstream[0]
+    hipStream_t cstream[2] = {};              // compute streams; groups alternate between them
+    hipStream_t xstream[2] = {};              // two more, for the forward launches of the ring-kernel classes
+    // device buffers (blocks() lists them)
+    sa_region_t *d_regions = nullptr; sa_row_t *d_rows = nullptr; int *d_pk = nullptr; int *d_poff = nullptr; int *d_pid = nullptr;
+    int *d_px = nullptr; double *d_xc = nullptr; double *d_ev = nullptr; sa_prec_t *d_prec = nullptr;
+    size_t d_blk_bytes = 0;
+    char *d_blk = nullptr;   // SA_FLAG_INPUTS_IN_HOST_BLOCK: the image of the caller's block (its event records are gathered on this
+                             // batch's own stream, possibly after sa_batch_create has returned: kept until the batch goes)
+    sa_seg_t *d_segs = nullptr; sa_ck_t *d_cks = nullptr;
+    double *d_F = nullptr; double *d_E = nullptr; double *d_vbuf = nullptr; sa_cand_t *d_cands = nullptr; int *d_cand_count = nullptr;
+    int *d_overflow = nullptr; double *d_totals = nullptr; double *d_bscratch = nullptr;
+    double *d_gsum = nullptr, *d_gmc = nullptr;   // expectation mode only
+    bool expect = false;
+    bool relax = false;        // memory-resident kernels in their RELAX flavour
+    int ring_cap = 0;          // cell-paths per diagonal of their LDS ring (0: rows stay in global memory)
+    int wide_cap = 0;          // cells per row of the register kernels' LDS ring for wide diagonals (0: every diagonal fits)
+    int gen_threads = 64;      // 64, or 128 when a diagonal of a memory-resident region holds more than 64 cell-paths
+    bool strip_on = false;     // one-path ring-kernel regions run on the strip kernels (default; SA_STRIP=0: ring kernels)
+    double *d_spec = nullptr;  // ring / strip kernels: speculative totals, one per segment (NaN: a segment of another kernel family)
+    double spec_slack = 0;     // candidates: forward + backward >= spec - slack + log(threshold); grows when a pass has to be repeated
+    int spec_repeats = 0;      // passes repeated because of it (the second repeat drops the bound altogether)
+    bool released = false;     // sa_batch_release_device: the working storage went back to the pool, the results stay
+    unsigned long long *d_sortkey = nullptr;   // k_gather_sorted's scratch: 8 + 4 bytes per candidate slot
+    unsigned *d_sortidx = nullptr;
     unsigned long long *d_vc_bits = nullptr;   // SA_FLAG_VC_ROWS: see k_finalize
     long long *d_vc_off = nullptr, *d_seg_all = nullptr;
     std::vector<unsigned long long> h_vc_bits;  // (the same on the host, for SA_FLAG_EXACT's host finalisation)
@@ -1259,64 +1283,93 @@ struct sa_batch {
     SaSites *sites = nullptr;                   // SA_FLAG_SITE_CALLS: the batch's sites (sa_calls.hip)
     bool plan_hdp = false;                      // the batch's model holds an HDP
     unsigned hdp_hot = 0xffffffffu;             // DevModel.hdp_hot
-    char *d_seam;            // their seam storage: per wave two arrays of seam_cap records of 16 bytes
-    unsigned seam_cap;
-    unsigned seam_cap_bwd;   // records per seam array of the backward launches (a traceback segment is shorter than a region)
-    long long seam_bwd_off;  // bytes: the forward launch's slots come first, then those of a pass's backward launches
+    char *d_seam = nullptr;      // their seam storage: per wave two arrays of seam_cap records of 16 bytes
+    unsigned seam_cap = 0;
+    unsigned seam_cap_bwd = 0;   // records per seam array of the backward launches (a traceback segment is shorter than a region)
+    long long seam_bwd_off = 0;  // bytes: the forward launch's slots come first, then those of a pass's backward launches
     double *d_two = nullptr; long long two_xn_off = 0;   // two-distribution emission on the register kernels (DevPlan.two)
-    double *d_tab6; double *d_noise3; double *d_evn; int *d_hdp_slot; double *d_hdp_y, *d_hdp_slope, *d_hdp_grid, *d_hdp_tab, *d_hdp_coef;
-    long long *d_prob; int *d_seg_pass; long long *d_seg_off; sa_pair16_t *d_out;
-    int *d_ids;  // region / segment id lists per launch
-    long long cand_alloc;
-    long long out_alloc;
-    int cand_factor;               // candidate capacity relative to the planner's 2 per posterior diagonal (overflow re-runs)
+    double *d_tab6 = nullptr; double *d_noise3 = nullptr; double *d_evn = nullptr; int *d_hdp_slot = nullptr;
+    double *d_hdp_y = nullptr, *d_hdp_slope = nullptr, *d_hdp_grid = nullptr, *d_hdp_tab = nullptr, *d_hdp_coef = nullptr;
+    long long *d_prob = nullptr; int *d_seg_pass = nullptr; long long *d_seg_off = nullptr; sa_pair16_t *d_out = nullptr;
+    int *d_ids = nullptr;  // region / segment id lists per launch
+    long long cand_alloc = 0;
+    long long out_alloc = 0;
+    int cand_factor = 1;           // candidate capacity relative to the planner's 2 per posterior diagonal (overflow re-runs)
     // launch lists (host): a chunk is one forward-storage pass; its traceback segments are cut into groups of
     // consecutive reads so that the result copy of one group overlaps the backward kernels of the next
     std::vector<sa_launch_chunk> chunks;
     std::vector<sa_launch_group> groups;
     std::vector<int> ids_flat;
-    hipStream_t pair_stream;       // the pairs themselves
+    hipStream_t pair_stream = nullptr;   // the pairs themselves
     std::vector<hipEvent_t> gev;   // per group: backward start, backward end, results ready, (unused)
     std::vector<hipEvent_t> cev;   // per chunk: forward start, forward end
-    long long *h_seg_off;          // pinned: per group n+1 exclusive offsets
-    int *h_overflow;               // pinned
+    long long *h_seg_off = nullptr;      // pinned: per group n+1 exclusive offsets
+    int *h_overflow = nullptr;           // pinned
     // results
-    sa_pair16_t *h_pairs;    // pinned host copy of all pairs (packed, sa_internal.h), job after job
+    sa_pair16_t *h_pairs = nullptr;   // pinned host copy of all pairs (packed, sa_internal.h), job after job
     bool p8 = false;         // SA_FLAG_PAIRS8: the records are 8 bytes (sa_pair8_t), in h_pairs and in d_out alike
     size_t rec() const { return p8 ? sizeof(sa_pair8_t) : sizeof(sa_pair16_t); }
     sa_pair16_t *out_at(long long slot) const { return reinterpret_cast<sa_pair16_t *>(reinterpret_cast<char *>(d_out) + rec() * (size_t) slot); }
     sa_pair16_t *host_at(long long slot) const { return reinterpret_cast<sa_pair16_t *>(reinterpret_cast<char *>(h_pairs) + rec() * (size_t) slot); }
-    long long h_pairs_cap, n_pairs_total;
+    long long h_pairs_cap = 0, n_pairs_total = 0;
     std::vector<long long> job_off;
     std::vector<long long> job_dev_off;   // where a job's pairs start in d_out (device finalisation only)
-    sa_pair16_t *d_pairs_up;              // host-finalised pairs uploaded for a downstream device step (sa_batch_mea)
-    long long d_pairs_up_cap;
-    bool ran;
-    bool quiet;            // the last run returned SA_OK: it waited for everything it had queued, the batch's streams are idle
-    bool dev_planned;      // the plan was built on the device (sa_dplan.inc): its big arrays exist in HBM only
-    std::thread *runner;   // sa_batch_start .. sa_batch_wait
-    int runner_rc;
-    sa_batch_stats_t stats;
-    hipEvent_t ev[8];
+    sa_pair16_t *d_pairs_up = nullptr;    // host-finalised pairs uploaded for a downstream device step (sa_batch_mea)
+    long long d_pairs_up_cap = 0;
+    bool ran = false;
+    bool quiet = false;          // the last run returned SA_OK: it waited for everything it had queued, the batch's streams are idle
+    bool dev_planned = false;    // the plan was built on the device (sa_dplan.inc): its big arrays exist in HBM only
+    std::thread *runner = nullptr;   // sa_batch_start .. sa_batch_wait
+    int runner_rc = SA_OK;
+    sa_batch_stats_t stats{};
+    hipEvent_t ev[8] = {};
     // Creation in two halves (sa_batch_create_deferred): what the second half needs.  `pending` is the device plan whose kernels
     // are queued; the caller's arrays (c_jobs, c_ambig) are only touched again if that plan turns a read down and the host
     // planner takes over -- which is why a deferred batch asks the caller to keep them until its first run has returned.
-    struct DPlanPending *pending;
-    const sa_model_t *c_m;
-    sa_params_t c_p;
-    const sa_job_t *c_jobs;
-    int64_t c_n;
-    const char *const *c_ambig;
-    long long c_budget;
-    double c_t0;
-    bool c_deferred;
-    char *held_stage;      // (deferred batches: see dplan_back)
-    bool finished;
-    int prepare_rc;
-    bool prepared;           // plan collected and launch lists built (sa_batch_prepare, or the first step of finishing)
-    long long lw_strip_max_n, lw_strip_max_seg, lw_strip_fwd_slots, lw_strip_bwd_slots;   // from the launch lists: seam storage
-    int finish_rc;
+    struct DPlanPending *pending = nullptr;
+    const sa_model_t *c_m = nullptr;
+    sa_params_t c_p{};
+    const sa_job_t *c_jobs = nullptr;
+    int64_t c_n = 0;
+    const char *const *c_ambig = nullptr;
+    long long c_budget = 0;
+    double c_t0 = 0;
+    bool c_deferred = false;
+    char *held_stage = nullptr;   // (deferred batches: see dplan_back)
+    bool finished = false;
+    int prepare_rc = SA_OK;
+    bool prepared = false;        // plan collected and launch lists built (sa_batch_prepare, or the first step of finishing)
+    long long lw_strip_max_n = 0, lw_strip_max_seg = 0, lw_strip_fwd_slots = 0, lw_strip_bwd_slots = 0;   // from the launch lists: seam storage
+    int finish_rc = SA_OK;
     std::mutex fin_mu;
+
+    // Every device block above that the batch takes from the caching allocator, by lifetime:
+    //   [0, BLK_PLAN)         working storage: what build_working (batch_finish_body) allocates, released by release_working
+    //   [BLK_PLAN, BLK_REST)  the planner's arrays: sa_dplan.inc's dplan_release gives them back when the device plan is dropped
+    //   [BLK_REST, BLK_END)   everything else, kept until sa_batch_release_device or sa_batch_destroy
+    // d_pairs_up is not listed: it survives sa_batch_release_device.
+    enum { BLK_PLAN = 18, BLK_REST = 27, BLK_END = 44 };
+    std::array<void **, BLK_END> blocks() {
+        const std::array all{
+            (void **) &d_F, (void **) &d_E, (void **) &d_vbuf, (void **) &d_cands, (void **) &d_prob, (void **) &d_cand_count,
+            (void **) &d_seg_pass, (void **) &d_seg_off, (void **) &d_overflow, (void **) &d_totals, (void **) &d_bscratch,
+            (void **) &d_gsum, (void **) &d_gmc, (void **) &d_seam, (void **) &d_spec, (void **) &d_sortkey, (void **) &d_sortidx,
+            (void **) &d_out,
+            (void **) &d_regions, (void **) &d_rows, (void **) &d_pk, (void **) &d_poff, (void **) &d_pid, (void **) &d_ev,
+            (void **) &d_segs, (void **) &d_cks, (void **) &d_prec,
+            (void **) &d_px, (void **) &d_xc, (void **) &d_blk, (void **) &d_tab6, (void **) &d_noise3, (void **) &d_evn,
+            (void **) &d_hdp_slot, (void **) &d_hdp_y, (void **) &d_hdp_slope, (void **) &d_hdp_grid, (void **) &d_hdp_tab,
+            (void **) &d_hdp_coef, (void **) &d_two, (void **) &d_vc_bits, (void **) &d_vc_off, (void **) &d_seg_all,
+            (void **) &d_ids};
+        static_assert(all.size() == BLK_END, "sa_batch::blocks: the list and BLK_END disagree");
+        return all;
+    }
+    // gives the blocks [lo, hi) back to the caching allocator
+    void put_blocks(int lo, int hi) {
+        const auto slot = blocks();
+        for (int i = lo; i < hi; i++)
+            if (*slot[i]) { g_sa_pool.put(SaPool::DEVICE, *slot[i]); *slot[i] = nullptr; }
+    }
 };
 static int batch_finish(sa_batch *b);
 
@@ -1684,8 +1737,7 @@ void sa_batch_destroy(sa_batch_t *b) {
     // the storage goes back to the caching allocators without the implicit synchronisation of hipFree: nothing of this
     // batch may still be in flight (only possible after an error inside a run)
     const bool trace_d = getenv("SA_TRACE") != nullptr;
-    auto now_ms_d = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double td0 = now_ms_d();
+    const double td0 = now_ms();
     if (!b->quiet) {   // (a failed or interrupted run, or a batch that never ran: 0.6-0.9 ms of API calls otherwise, per batch,
                        // on the thread that is about to plan the next one)
         for (int i = 0; i < 2; i++)
@@ -1694,14 +1746,8 @@ void sa_batch_destroy(sa_batch_t *b) {
             if (b->xstream[i]) (void) hipStreamSynchronize(b->xstream[i]);
         if (b->pair_stream) (void) hipStreamSynchronize(b->pair_stream);
     }
-    const double td1 = now_ms_d();
-    void *ptrs[] = {b->d_regions, b->d_rows, b->d_pk, b->d_poff, b->d_pid, b->d_px, b->d_xc, b->d_prec, b->d_ev, b->d_segs, b->d_cks, b->d_F, b->d_E,
-                    b->d_vbuf, b->d_cands, b->d_cand_count, b->d_overflow, b->d_totals, b->d_bscratch, b->d_tab6, b->d_noise3, b->d_evn, b->d_two,
-                    b->d_hdp_slot, b->d_hdp_y, b->d_hdp_slope, b->d_hdp_grid, b->d_hdp_tab, b->d_hdp_coef, b->d_prob, b->d_seg_pass, b->d_seg_off,
-                    b->d_out, b->d_ids, b->d_gsum, b->d_gmc, b->d_seam, b->d_blk, b->d_spec, b->d_sortkey, b->d_sortidx,
-                    b->d_vc_bits, b->d_vc_off, b->d_seg_all};
-    for (void *p : ptrs)
-        if (p) g_sa_pool.put(SaPool::DEVICE, p);
+    const double td1 = now_ms();
+    b->put_blocks(0, sa_batch::BLK_END);
     for (int i = 0; i < 8; i++)
         g_handles.park(b->ev[i], b->device);
     for (hipEvent_t e : b->gev) g_handles.park(e, b->device);
@@ -1717,10 +1763,10 @@ void sa_batch_destroy(sa_batch_t *b) {
     g_sa_pool.put(SaPool::PINNED, b->h_seg_off);
     g_sa_pool.put(SaPool::PINNED, b->h_overflow);
     sa_sites_free(b->sites);
-    const double td2 = now_ms_d();
+    const double td2 = now_ms();
     sa_plan_free(b->plan);
     delete b;
-    if (trace_d) fprintf(stderr, "[trace] destroy: streams idle after %.2f ms, blocks parked after %.2f ms, done after %.2f ms\n", td1 - td0, td2 - td0, now_ms_d() - td0);
+    if (trace_d) fprintf(stderr, "[trace] destroy: streams idle after %.2f ms, blocks parked after %.2f ms, done after %.2f ms\n", td1 - td0, td2 - td0, now_ms() - td0);
 }
 
 #include "sa_dplan.inc"
@@ -1778,12 +1824,11 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     if (flags & SA_FLAG_EXPECT_INTERNAL) flags &= ~SA_FLAG_SITE_CALLS;
     if ((flags & SA_FLAG_SITE_CALLS) && (flags & SA_FLAG_VC_ROWS)) return SA_EINVAL;   // (that flag drops the rows the calls are made of)
     const bool trace_c = getenv("SA_TRACE") != nullptr;
-    auto now_ms_c = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double tc0 = now_ms_c();
+    const double tc0 = now_ms();
     HIPCHK(hipSetDevice(device));
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (trace_c) fprintf(stderr, "[trace] create: memory queried at %.1f ms\n", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: memory queried at %.1f ms\n", now_ms() - tc0);
     free_b += g_sa_pool.idle_bytes(SaPool::DEVICE, device);   // what destroyed batches left parked is available to this one
     if (deferred && (flags & SA_FLAG_DEVICE_TO_ITSELF)) free_b += g_sa_pool.live_bytes(SaPool::DEVICE, device);   // ... and what the running ones hold
     // forward storage gets at most 60% of what is free; 24 B per cell-path (HDP models: 8 B more, the emission plane)
@@ -1792,28 +1837,9 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     if (envb && atoll(envb) > 0) budget = atoll(envb);
 
     sa_batch *b = new sa_batch();
-    b->plan = nullptr;
-    b->pending = nullptr; b->finished = false; b->finish_rc = SA_OK; b->c_deferred = false; b->held_stage = nullptr;
     b->c_m = m; b->c_p = *p; b->c_jobs = jobs; b->c_n = n_jobs; b->c_ambig = ambig; b->c_budget = budget; b->c_t0 = tc0;
-    b->dev_planned = false;
     b->device = device;
     b->flags = flags;
-    b->stream = nullptr;
-    b->cstream[0] = b->cstream[1] = nullptr;
-    b->xstream[0] = b->xstream[1] = nullptr;
-    b->pair_stream = nullptr;
-    b->h_seg_off = nullptr;
-    b->h_overflow = nullptr;
-    b->ran = false; b->released = false;
-    b->quiet = false;
-    b->runner = nullptr; b->runner_rc = SA_OK;
-    b->d_regions = nullptr; b->d_rows = nullptr; b->d_pk = nullptr; b->d_poff = nullptr; b->d_pid = nullptr; b->d_px = nullptr; b->d_xc = nullptr;
-    b->d_prec = nullptr; b->d_blk = nullptr;
-    b->d_ev = nullptr; b->d_segs = nullptr; b->d_cks = nullptr; b->d_F = nullptr; b->d_E = nullptr; b->d_vbuf = nullptr;
-    b->d_cands = nullptr; b->d_cand_count = nullptr; b->d_overflow = nullptr; b->d_totals = nullptr;
-    b->d_seam = nullptr; b->seam_cap = 0; b->seam_cap_bwd = 0; b->seam_bwd_off = 0; b->strip_on = false;
-    b->prepared = false; b->prepare_rc = SA_OK; b->lw_strip_max_n = b->lw_strip_max_seg = b->lw_strip_fwd_slots = b->lw_strip_bwd_slots = 0;
-    b->d_spec = nullptr; b->d_sortkey = nullptr; b->d_sortidx = nullptr;
     // the exact totals of a traceback drift away from its speculative total diagonal by diagonal (1.6e-4 per diagonal with the flat
     // HDP fixture: sa_strip.inc), so the slack is sized for the traceback's length -- the default 0.5 at the default 1100 diagonals --
     // and starts from what earlier batches of this model on this device had to grow to
@@ -1823,14 +1849,6 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
         const double v_ = atof(ets);
         if (v_ > 0.0) b->spec_slack = v_;
     }
-    b->d_bscratch = nullptr; b->d_tab6 = nullptr; b->d_noise3 = nullptr; b->d_evn = nullptr; b->d_two = nullptr; b->two_xn_off = 0; b->d_hdp_slot = nullptr; b->d_hdp_y = nullptr;
-    b->d_hdp_slope = nullptr; b->d_hdp_grid = nullptr; b->d_hdp_tab = nullptr; b->d_hdp_coef = nullptr; b->d_prob = nullptr; b->d_seg_pass = nullptr;
-    b->d_seg_off = nullptr; b->d_out = nullptr; b->d_ids = nullptr; b->d_gsum = nullptr; b->d_gmc = nullptr;
-    b->cand_alloc = 0; b->out_alloc = 0; b->cand_factor = 1; b->spec_repeats = 0;
-    b->h_pairs = nullptr; b->h_pairs_cap = 0; b->n_pairs_total = 0;
-    b->d_pairs_up = nullptr; b->d_pairs_up_cap = 0;
-    memset(&b->stats, 0, sizeof(b->stats));
-    for (int i = 0; i < 8; i++) b->ev[i] = nullptr;
     if (flags & SA_FLAG_SITE_CALLS) {   // the sites of every job: one pass over its reference (sa_calls.hip)
         const int rcs = n_jobs > 0 && !jobs ? SA_EINVAL : sa_sites_build(m, jobs, n_jobs, ambig, &b->sites);
         // (an 8-byte record names no k-mer: such a batch may hold no site)
@@ -1918,44 +1936,31 @@ static int batch_build_lists(sa_batch *b) {
     // device-side finalisation, reference windows of fewer than 64 * STRIP_NS_MAX positions.  SA_STRIP=0: ring kernels.
     b->strip_on = !host_finalize && !(getenv("SA_STRIP") && atoi(getenv("SA_STRIP")) == 0);   // (HDP regions too: they read the emission plane)
     long long strip_max_n = 0, strip_max_seg = 0, strip_fwd_slots = 0, strip_bwd_slots = 0;
+    // one list per launch class, longest first (the tail of a launch is then made of short waves), appended to ids_flat in class order
+    auto append = [&](std::vector<int> (&lists)[LC_N], sa_ids *out, auto longer) {
+        for (int c = 0; c < LC_N; c++) {
+            std::stable_sort(lists[c].begin(), lists[c].end(), longer);
+            out[c] = sa_ids{(long long) b->ids_flat.size(), (int) lists[c].size()};
+            b->ids_flat.insert(b->ids_flat.end(), lists[c].begin(), lists[c].end());
+        }
+    };
     long long r = 0;
     for (int c = 0; c < pl->n_chunks; c++) {
         long long ra = r;
         while (r < pl->n_regions && pl->regions[r].chunk == c) r++;
         long long rb = r;
         sa_launch_chunk C;
-        std::vector<int> gr, fr, sr_;
+        std::vector<int> ids[LC_N];
         double work = 0;
-        std::vector<int> rr[16];
-        auto ring_class = [](const sa_region_t &Rq) {
-            const int cl = Rq.max_rowpaths <= 64 ? 0 : (int) ((Rq.max_rowpaths - 1) / 64);   // <= 7 (SA_RING_MAX_ROWPATHS)
-            return (Rq.max_p > 1 ? 8 : 0) + (cl > 7 ? 7 : cl);
-        };
         for (long long q = ra; q < rb; q++) {
             const sa_region_t &Rq = pl->regions[q];
-            if (strip_region(&Rq, b->strip_on)) { sr_.push_back((int) q); strip_max_n = Rq.N > strip_max_n ? Rq.N : strip_max_n; }
-            else if (Rq.kind == SA_KIND_RING) rr[ring_class(Rq)].push_back((int) q);
-            else if (Rq.kind != SA_KIND_FAST) gr.push_back((int) q);
-            else fr.push_back((int) q);
+            const int lc = launch_class(Rq, b->strip_on);
+            ids[lc].push_back((int) q);
+            if (lc == LC_STRIP) strip_max_n = Rq.N > strip_max_n ? Rq.N : strip_max_n;
             work += (double) Rq.N;
         }
-        auto by_len_r = [&](int a, int d) { return pl->regions[a].N > pl->regions[d].N; };
-        // longest first inside each launch: the tail of a launch is then made of short waves
-        std::stable_sort(gr.begin(), gr.end(), by_len_r);
-        std::stable_sort(fr.begin(), fr.end(), by_len_r);
-        C.ids_gr = (long long) b->ids_flat.size(); C.ngr = (int) gr.size();
-        b->ids_flat.insert(b->ids_flat.end(), gr.begin(), gr.end());
-        C.ids_fr = (long long) b->ids_flat.size(); C.nfr = (int) fr.size();
-        b->ids_flat.insert(b->ids_flat.end(), fr.begin(), fr.end());
-        for (int cl = 0; cl < 16; cl++) {
-            std::stable_sort(rr[cl].begin(), rr[cl].end(), by_len_r);
-            C.ids_rr[cl] = (long long) b->ids_flat.size(); C.nrr[cl] = (int) rr[cl].size();
-            b->ids_flat.insert(b->ids_flat.end(), rr[cl].begin(), rr[cl].end());
-        }
-        std::stable_sort(sr_.begin(), sr_.end(), by_len_r);
-        C.ids_st = (long long) b->ids_flat.size(); C.nst = (int) sr_.size();
-        b->ids_flat.insert(b->ids_flat.end(), sr_.begin(), sr_.end());
-        strip_fwd_slots = (long long) sr_.size() > strip_fwd_slots ? (long long) sr_.size() : strip_fwd_slots;
+        append(ids, C.ids, [&](int a, int d) { return pl->regions[a].N > pl->regions[d].N; });
+        strip_fwd_slots = std::max(strip_fwd_slots, (long long) C.ids[LC_STRIP].n);
         long long chunk_bwd_slots = 0;
         C.g0 = (int) b->groups.size();
         // a group should still be a sizeable launch: at least 2048 segments each (measured optimum 6-8 groups
@@ -1986,44 +1991,24 @@ static int batch_build_lists(sa_batch *b) {
             while (q < rb && pl->regions[q].job == pl->regions[q - 1].job) { acc += (double) pl->regions[q].N; q++; }
             sa_launch_group G;
             G.seg0 = G.seg1 = G.ck0 = G.ck1 = 0;
-            std::vector<int> gs, fs, rs[16], ss;
+            std::vector<int> sids[LC_N];
             bool any = false;
             for (long long t = qa; t < q; t++) {
                 const sa_region_t *R = &pl->regions[t];
+                const int lc = launch_class(*R, b->strip_on);
                 for (long long sg = R->seg_off; sg < R->seg_off + R->n_seg; sg++) {
-                    if (strip_region(R, b->strip_on)) {
-                        ss.push_back((int) sg);
-                        const long long span = pl->segs[sg].start - pl->segs[sg].to;
-                        strip_max_seg = span > strip_max_seg ? span : strip_max_seg;
-                    }
-                    else if (R->kind == SA_KIND_RING) rs[ring_class(*R)].push_back((int) sg);
-                    else (R->kind != SA_KIND_FAST ? gs : fs).push_back((int) sg);
+                    sids[lc].push_back((int) sg);
                     const sa_seg_t *S = &pl->segs[sg];
+                    if (lc == LC_STRIP) strip_max_seg = std::max(strip_max_seg, (long long) (S->start - S->to));
                     if (!any) { G.seg0 = sg; G.ck0 = S->ck_base; any = true; }
                     G.seg1 = sg + 1;
                     G.ck1 = S->ck_base + S->n_ck;
                 }
             }
             if (!any) continue;
-            auto by_len_s = [&](int a, int d) {
-                return pl->segs[a].start - pl->segs[a].to > pl->segs[d].start - pl->segs[d].to;
-            };
-            std::stable_sort(gs.begin(), gs.end(), by_len_s);
-            std::stable_sort(fs.begin(), fs.end(), by_len_s);
-            G.ids_gs = (long long) b->ids_flat.size(); G.ngs = (int) gs.size();
-            b->ids_flat.insert(b->ids_flat.end(), gs.begin(), gs.end());
-            G.ids_fs = (long long) b->ids_flat.size(); G.nfs = (int) fs.size();
-            b->ids_flat.insert(b->ids_flat.end(), fs.begin(), fs.end());
-            for (int cl = 0; cl < 16; cl++) {
-                std::stable_sort(rs[cl].begin(), rs[cl].end(), by_len_s);
-                G.ids_rs[cl] = (long long) b->ids_flat.size(); G.nrs[cl] = (int) rs[cl].size();
-                b->ids_flat.insert(b->ids_flat.end(), rs[cl].begin(), rs[cl].end());
-            }
-            std::stable_sort(ss.begin(), ss.end(), by_len_s);
-            G.ids_ss = (long long) b->ids_flat.size(); G.nss = (int) ss.size();
-            b->ids_flat.insert(b->ids_flat.end(), ss.begin(), ss.end());
+            append(sids, G.ids, [&](int a, int d) { return pl->segs[a].start - pl->segs[a].to > pl->segs[d].start - pl->segs[d].to; });
             G.seam_first = (unsigned) chunk_bwd_slots;   // (rebased behind the forward slots below)
-            chunk_bwd_slots += (long long) ss.size();
+            chunk_bwd_slots += G.ids[LC_STRIP].n;
             b->groups.push_back(G);
         }
         strip_bwd_slots = chunk_bwd_slots > strip_bwd_slots ? chunk_bwd_slots : strip_bwd_slots;
@@ -2047,7 +2032,6 @@ static int batch_prepare_body(sa_batch *b) {
     const long long budget = b->c_budget;
     const int device = b->device;
     const bool trace_c = getenv("SA_TRACE") != nullptr;
-    auto now_ms_c = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = b->c_t0;
     HIPCHK(hipSetDevice(device));
     // (only a deferred batch: with several batches in flight and creation in one piece the second upload stream measured
@@ -2079,10 +2063,10 @@ static int batch_prepare_body(sa_batch *b) {
         }
         sa_plan_use_allocator(nullptr, nullptr);
         if (rc) return rc;
-        if (trace_c) fprintf(stderr, "[trace] create: planned at %.1f ms\n", now_ms_c() - tc0);
+        if (trace_c) fprintf(stderr, "[trace] create: planned at %.1f ms\n", now_ms() - tc0);
         b->plan = pl;
     }
-    if (trace_c) fprintf(stderr, "[trace] create: planned (%s) at %.1f ms\n", b->dev_planned ? "device" : "host", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: planned (%s) at %.1f ms\n", b->dev_planned ? "device" : "host", now_ms() - tc0);
 
     b->expect = (flags & SA_FLAG_EXPECT_INTERNAL) != 0;
     b->plan_hdp = m->hdp != nullptr;
@@ -2124,7 +2108,7 @@ static int batch_prepare_body(sa_batch *b) {
     // sa_batch_prepare that is while the batch before this one still runs; nothing of it needs the working storage)
     std::unique_lock<std::mutex> up_lock((*UPT).mu);
     TRY((*UPT).bind(device));
-    if (trace_c) fprintf(stderr, "[trace] create: upload ring ready at %.1f ms\n", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: upload ring ready at %.1f ms\n", now_ms() - tc0);
     {   // candidate capacity an earlier batch of this stream had to grow to
         const int f = pl->params.threshold > 0.0 ? cand_memo_factor(m, pl->params.threshold, device) : 1;
         if (f > 1) {
@@ -2308,9 +2292,9 @@ static int batch_prepare_body(sa_batch *b) {
     }
     TRY((*UPT).drain());
     up_lock.unlock();
-    if (trace_c) fprintf(stderr, "[trace] create: inputs uploaded at %.1f ms\n", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: inputs uploaded at %.1f ms\n", now_ms() - tc0);
     TRY(batch_build_lists(b));
-    if (trace_c) fprintf(stderr, "[trace] create: launch lists at %.1f ms\n", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: launch lists at %.1f ms\n", now_ms() - tc0);
     return SA_OK;
 #undef TRY
 }
@@ -2321,7 +2305,6 @@ static int batch_finish_body(sa_batch *b) {
     const unsigned flags = b->flags;
     const int device = b->device;
     const bool trace_c = getenv("SA_TRACE") != nullptr;
-    auto now_ms_c = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = b->c_t0;
     (void) p;
     HIPCHK(hipSetDevice(device));
@@ -2411,13 +2394,7 @@ static int batch_finish_body(sa_batch *b) {
         return SA_OK;
     };
     auto release_working = [&]() {
-        void **ptrs[] = {(void **) &b->d_F, (void **) &b->d_E, (void **) &b->d_vbuf, (void **) &b->d_cands, (void **) &b->d_prob,
-                         (void **) &b->d_cand_count, (void **) &b->d_seg_pass, (void **) &b->d_seg_off, (void **) &b->d_overflow,
-                         (void **) &b->d_totals, (void **) &b->d_bscratch, (void **) &b->d_gsum, (void **) &b->d_gmc, (void **) &b->d_seam,
-                         (void **) &b->d_spec, (void **) &b->d_sortkey, (void **) &b->d_sortidx,
-                         (void **) &b->d_out};
-        for (void **q : ptrs)
-            if (*q) { g_sa_pool.put(SaPool::DEVICE, *q); *q = nullptr; }
+        b->put_blocks(0, sa_batch::BLK_PLAN);
         if (b->h_seg_off) { g_sa_pool.put(SaPool::PINNED, b->h_seg_off); b->h_seg_off = nullptr; }
         if (b->h_overflow) { g_sa_pool.put(SaPool::PINNED, b->h_overflow); b->h_overflow = nullptr; }
         for (hipEvent_t e : b->gev) if (e) g_handles.park(e, device);
@@ -2484,7 +2461,7 @@ static int batch_finish_body(sa_batch *b) {
         TRY(upload(&b->d_ids, b->ids_flat.data(), (long long) b->ids_flat.size()));
         TRY((*UPT).drain());
     }
-    if (trace_c) fprintf(stderr, "[trace] create: buffers allocated at %.1f ms\n", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: buffers allocated at %.1f ms\n", now_ms() - tc0);
     b->stats.cells_forward = pl->cells_fwd;
     b->stats.cells_backward = pl->cells_bwd;
     b->stats.n_regions = pl->n_regions;
@@ -2493,7 +2470,7 @@ static int batch_finish_body(sa_batch *b) {
     b->stats.n_fast_regions = pl->n_fast_regions;
     b->stats.n_ring_regions = pl->n_ring_regions;
     b->stats.n_strip_regions = 0;
-    for (const auto &C_ : b->chunks) b->stats.n_strip_regions += C_.nst;
+    for (const auto &C_ : b->chunks) b->stats.n_strip_regions += C_.ids[LC_STRIP].n;
     b->stats.n_chunks = pl->n_chunks;
     b->stats.n_groups = (int64_t) b->groups.size();
     double fb = 0;
@@ -2513,7 +2490,7 @@ static int batch_finish_body(sa_batch *b) {
         if (g_sa_pool.get(SaPool::PINNED, (void **) &b->h_pairs, b->rec() * (size_t) cap, device) == hipSuccess) b->h_pairs_cap = cap;
         else { (void) hipGetLastError(); b->h_pairs = nullptr; }   // (the run asks again)
     }
-    if (trace_c) fprintf(stderr, "[trace] create: done at %.1f ms\n", now_ms_c() - tc0);
+    if (trace_c) fprintf(stderr, "[trace] create: done at %.1f ms\n", now_ms() - tc0);
     return SA_OK;
 }
 
@@ -2533,19 +2510,6 @@ int sa_dplan_compare(const sa_model_t *m, const sa_params_t *p, const sa_job_t *
     if (envb && atoll(envb) > 0) budget = atoll(envb);
     sa_batch *b = new sa_batch();
     b->device = device;
-    b->plan = nullptr;
-    b->dev_planned = false;
-    b->runner = nullptr;
-    b->cstream[0] = b->cstream[1] = nullptr; b->xstream[0] = b->xstream[1] = nullptr; b->pair_stream = nullptr; b->stream = nullptr;
-    b->h_pairs = nullptr; b->d_pairs_up = nullptr; b->h_seg_off = nullptr; b->h_overflow = nullptr;
-    for (int i = 0; i < 8; i++) b->ev[i] = nullptr;
-    b->d_regions = nullptr; b->d_rows = nullptr; b->d_pk = nullptr; b->d_poff = nullptr; b->d_pid = nullptr; b->d_px = nullptr; b->d_xc = nullptr;
-    b->d_prec = nullptr; b->d_blk = nullptr; b->d_ev = nullptr; b->d_segs = nullptr; b->d_cks = nullptr; b->d_F = nullptr; b->d_E = nullptr; b->d_vbuf = nullptr;
-    b->d_cands = nullptr; b->d_cand_count = nullptr; b->d_overflow = nullptr; b->d_totals = nullptr; b->d_bscratch = nullptr;
-    b->d_tab6 = nullptr; b->d_hdp_slot = nullptr; b->d_hdp_y = nullptr; b->d_hdp_slope = nullptr; b->d_hdp_grid = nullptr;
-    b->d_hdp_tab = nullptr; b->d_hdp_coef = nullptr; b->d_prob = nullptr; b->d_seg_pass = nullptr; b->d_seg_off = nullptr; b->d_out = nullptr;
-    b->d_ids = nullptr; b->d_gsum = nullptr; b->d_gmc = nullptr; b->d_seam = nullptr;
-    b->d_spec = nullptr; b->d_sortkey = nullptr; b->d_sortidx = nullptr;
     int rcd;
     {
         std::unique_lock<std::mutex> lk(g_uploader.mu);
@@ -2615,40 +2579,41 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
     hipStream_t st = b->cstream[which_stream];
     HIPCHK(hipEventRecord(b->gev[4 * g], st));
     const size_t relax_lds = sizeof(double) * (size_t) (LA_TAB_DOUBLES + 9 * b->ring_cap);
-    if (G.ngs && b->expect)
-        hipLaunchKernelGGL((k_bwd_generic<true, false>), dim3(G.ngs), dim3(b->gen_threads), 0, st, P, b->d_ids + G.ids_gs, G.ngs, 0);
-    else if (G.ngs && b->relax)
-        hipLaunchKernelGGL((k_bwd_generic<false, true>), dim3(G.ngs), dim3(b->gen_threads), relax_lds, st, P, b->d_ids + G.ids_gs, G.ngs,
+    const sa_ids &Lg = G.ids[LC_GENERIC], &Ls = G.ids[LC_STRIP], &Lf = G.ids[LC_FAST];
+    if (Lg.n && b->expect)
+        hipLaunchKernelGGL((k_bwd_generic<true, false>), dim3(Lg.n), dim3(b->gen_threads), 0, st, P, b->d_ids + Lg.off, Lg.n, 0);
+    else if (Lg.n && b->relax)
+        hipLaunchKernelGGL((k_bwd_generic<false, true>), dim3(Lg.n), dim3(b->gen_threads), relax_lds, st, P, b->d_ids + Lg.off, Lg.n,
                            b->ring_cap);
-    else if (G.ngs)
-        hipLaunchKernelGGL((k_bwd_generic<false, false>), dim3(G.ngs), dim3(b->gen_threads), 0, st, P, b->d_ids + G.ids_gs, G.ngs, 0);
-    if (G.nss) {
+    else if (Lg.n)
+        hipLaunchKernelGGL((k_bwd_generic<false, false>), dim3(Lg.n), dim3(b->gen_threads), 0, st, P, b->d_ids + Lg.off, Lg.n, 0);
+    if (Ls.n) {
         StripT ST;
         ST.ev_total = pl->n_ev + 8; ST.seam_cap = b->seam_cap_bwd; ST.seam_stride = 32ull * b->seam_cap_bwd; ST.seam_first = G.seam_first;
         ST.spec = b->d_spec;
         ST.slack = b->spec_slack;
-        launch_bwd_strip1(P, b->d_ids + G.ids_ss, G.nss, st, b->d_seam + b->seam_bwd_off, ST);
+        launch_bwd_strip1(P, b->d_ids + Ls.off, Ls.n, st, b->d_seam + b->seam_bwd_off, ST);
     }
-    for (int cl = 15; cl >= 0; cl--)   // widest (longest-running) classes first
-        if (G.nrs[cl]) launch_bwd_ring(P, b->d_ids + G.ids_rs[cl], G.nrs[cl], st, 64 * ((cl & 7) + 1), cl >= 8, b->expect);
-    if (G.nfs) { const int rcl = launch_bwd_fast(P, b->d_ids + G.ids_fs, G.nfs, st, b->expect); if (rcl) return rcl; }
+    for (int cl = 15; cl >= 0; cl--) {   // widest (longest-running) classes first
+        const sa_ids &L = G.ids[LC_RING + cl];
+        if (L.n) launch_bwd_ring(P, b->d_ids + L.off, L.n, st, 64 * ((cl & 7) + 1), cl >= 8, b->expect);
+    }
+    if (Lf.n) { const int rcl = launch_bwd_fast(P, b->d_ids + Lf.off, Lf.n, st, b->expect); if (rcl) return rcl; }
     HIPCHK(hipEventRecord(b->gev[4 * g + 1], st));
     if (G.ck1 > G.ck0)
         hipLaunchKernelGGL(k_fold, dim3((unsigned) ((G.ck1 - G.ck0 + 63) / 64)), dim3(64), 0, st, P, G.ck0, G.ck1);
     if (finalize) {
         const int n = (int) (G.seg1 - G.seg0);
         long long *soff = b->d_seg_off + G.seg0 + g;
-        bool any_ring = G.nfs > 0;
-        for (int cl = 0; cl < 16; cl++) any_ring = any_ring || G.nrs[cl] > 0;
         // (groups without register / ring / strip segments: no look at the speculative totals)
-        const double *spec = (b->d_spec && (any_ring || G.nss > 0)) ? b->d_spec : nullptr;
+        const double *spec = (b->d_spec && n_nonempty(G.ids, LC_FAST, LC_N) > 0) ? b->d_spec : nullptr;
         hipLaunchKernelGGL(k_finalize, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, b->d_seg_pass, spec,
                            b->spec_slack, (const unsigned long long *) b->d_vc_bits, (const long long *) b->d_vc_off, b->d_seg_all);
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, b->d_seg_pass + G.seg0, soff, b->h_seg_off + G.seg0 + g, n);
         sa_pair16_t *const gout = b->out_at(pl->segs[G.seg0].cand_off);
         hipLaunchKernelGGL(k_gather, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, soff,
                            gout, spec, (b->strip_on && b->d_sortkey) ? 1 : 0, b->p8 ? 1 : 0);
-        if (spec && G.nss > 0 && b->d_sortkey)
+        if (spec && Ls.n > 0 && b->d_sortkey)
             hipLaunchKernelGGL(k_gather_sorted, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, soff,
                                gout, spec, b->d_sortkey, b->d_sortidx, b->p8 ? 1 : 0);
         HIPCHK(hipEventRecord(b->gev[4 * g + 2], st));
@@ -2675,17 +2640,17 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
     HIPCHK(hipEventRecord(b->ev[0], s0));
     for (size_t c = 0; c < b->chunks.size(); c++) {
         const sa_launch_chunk &C = b->chunks[c];
+        const sa_ids &Lg = C.ids[LC_GENERIC], &Ls = C.ids[LC_STRIP], &Lf = C.ids[LC_FAST];
         HIPCHK(hipEventRecord(b->cev[2 * c], s0));
-        if (C.ngr && b->relax)
-            hipLaunchKernelGGL(k_fwd_generic<true>, dim3(C.ngr), dim3(b->gen_threads), sizeof(double) * (size_t) (LA_TAB_DOUBLES + 9 * b->ring_cap),
-                               s0, P, b->d_ids + C.ids_gr, C.ngr, b->ring_cap);
-        else if (C.ngr)
-            hipLaunchKernelGGL(k_fwd_generic<false>, dim3(C.ngr), dim3(b->gen_threads), 0, s0, P, b->d_ids + C.ids_gr, C.ngr, 0);
+        if (Lg.n && b->relax)
+            hipLaunchKernelGGL(k_fwd_generic<true>, dim3(Lg.n), dim3(b->gen_threads), sizeof(double) * (size_t) (LA_TAB_DOUBLES + 9 * b->ring_cap),
+                               s0, P, b->d_ids + Lg.off, Lg.n, b->ring_cap);
+        else if (Lg.n)
+            hipLaunchKernelGGL(k_fwd_generic<false>, dim3(Lg.n), dim3(b->gen_threads), 0, s0, P, b->d_ids + Lg.off, Lg.n, 0);
         {   // ring-kernel regions, one launch per class of row capacity.  A forward launch holds one workgroup per read and
             // lasts as long as its longest read's serial chain, so launches that follow each other on one stream leave the chip
             // mostly empty three times over: the classes alternate between the two compute streams and run side by side
-            int n_cl = C.nst > 0;
-            for (int cl = 0; cl < 16; cl++) n_cl += C.nrr[cl] > 0;
+            const int n_cl = n_nonempty(C.ids, LC_RING, LC_N);   // (the strip kernels' list among them)
             hipStream_t lanes[4] = {s0, s1, b->xstream[0], b->xstream[1]};
             int n_lanes = n_cl < 4 ? n_cl : 4;
             for (int q = 2; q < n_lanes; q++)   // the two extra streams are made on first need
@@ -2695,29 +2660,32 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
                 }
             if (P.m.hdp) {   // the emission plane of this pass's ring / strip regions, ahead of the sweeps that read it (on s0: the
                              // other lanes wait for the event recorded below)
-                if (C.nst) launch_emit_hdp_ring(P, b->d_ids + C.ids_st, C.nst, pl->regions[b->ids_flat[(size_t) C.ids_st]].N, s0, false);
-                for (int cl = 0; cl < 16; cl++)
-                    if (C.nrr[cl])
-                        launch_emit_hdp_ring(P, b->d_ids + C.ids_rr[cl], C.nrr[cl], pl->regions[b->ids_flat[(size_t) C.ids_rr[cl]]].N, s0, cl >= 8);
+                if (Ls.n) launch_emit_hdp_ring(P, b->d_ids + Ls.off, Ls.n, pl->regions[b->ids_flat[(size_t) Ls.off]].N, s0, false);
+                for (int cl = 0; cl < 16; cl++) {
+                    const sa_ids &L = C.ids[LC_RING + cl];
+                    if (L.n) launch_emit_hdp_ring(P, b->d_ids + L.off, L.n, pl->regions[b->ids_flat[(size_t) L.off]].N, s0, cl >= 8);
+                }
             }
             if (n_lanes > 1) {
                 HIPCHK(hipEventRecord(b->ev[1], s0));
                 for (int q = 1; q < n_lanes; q++) HIPCHK(hipStreamWaitEvent(lanes[q], b->ev[1], 0));
             }
             int which = 0;
-            if (C.nst) {
+            if (Ls.n) {
                 StripT ST;
                 ST.ev_total = pl->n_ev + 8; ST.seam_cap = b->seam_cap; ST.seam_stride = 32ull * b->seam_cap; ST.seam_first = 0;
                 ST.spec = b->d_spec;
                 ST.slack = b->spec_slack;
-                launch_fwd_strip(P, b->d_ids + C.ids_st, C.nst, lanes[0], b->d_seam, ST);
+                launch_fwd_strip(P, b->d_ids + Ls.off, Ls.n, lanes[0], b->d_seam, ST);
                 which = n_lanes > 1 ? 1 : 0;
             }
-            for (int cl = 15; cl >= 0; cl--)
-                if (C.nrr[cl]) {
-                    launch_fwd_ring(P, b->d_ids + C.ids_rr[cl], C.nrr[cl], lanes[n_lanes > 1 ? which : 0], 64 * ((cl & 7) + 1), cl >= 8);
+            for (int cl = 15; cl >= 0; cl--) {
+                const sa_ids &L = C.ids[LC_RING + cl];
+                if (L.n) {
+                    launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], 64 * ((cl & 7) + 1), cl >= 8);
                     which = (which + 1) % (n_lanes > 1 ? n_lanes : 1);
                 }
+            }
             for (int q = 1; q < n_lanes; q++) {
                 HIPCHK(hipEventRecord(b->ev[1 + q], lanes[q]));
                 HIPCHK(hipStreamWaitEvent(s0, b->ev[1 + q], 0));
@@ -2727,13 +2695,11 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
         // forward sweep of slice k runs beside the emission kernel of slice k + 1 -- neither keeps the chip busy alone --: forward
         // stage 15.8 -> 18.6 / 17.1 / 20.0 ms per 5000 reads.  A forward launch of fewer reads lasts as long as its longest chain and
         // the emission kernel slows down beside it by more than the overlap gives.)
-        if (C.nfr && P.m.hdp) launch_emit_hdp(P, b->d_ids + C.ids_fr, C.nfr, pl->regions[b->ids_flat[(size_t) C.ids_fr]].N, s0);
-        if (C.nfr) launch_fwd_fast(P, b->d_ids + C.ids_fr, C.nfr, s0, b->wide_cap);
-        if (b->d_spec && C.g1 > C.g0) {   // the candidate bounds of this pass's ring / strip tracebacks (k_spec_match)
-            bool any = C.nst > 0 || C.nfr > 0;
-            for (int cl = 0; cl < 16; cl++) any = any || C.nrr[cl] > 0;
+        if (Lf.n && P.m.hdp) launch_emit_hdp(P, b->d_ids + Lf.off, Lf.n, pl->regions[b->ids_flat[(size_t) Lf.off]].N, s0);
+        if (Lf.n) launch_fwd_fast(P, b->d_ids + Lf.off, Lf.n, s0, b->wide_cap);
+        if (b->d_spec && C.g1 > C.g0) {   // the candidate bounds of this pass's register / ring / strip tracebacks (k_spec_match)
             const long long sa_ = b->groups[(size_t) C.g0].seg0, sb_ = b->groups[(size_t) C.g1 - 1].seg1;
-            if (any && sb_ > sa_)
+            if (n_nonempty(C.ids, LC_FAST, LC_N) > 0 && sb_ > sa_)
                 hipLaunchKernelGGL(k_spec_match, dim3((unsigned) (sb_ - sa_)), dim3(64), 0, s0, P, (int) sa_, (int) (sb_ - sa_), b->d_spec);
         }
         HIPCHK(hipEventRecord(b->cev[2 * c + 1], s0));
@@ -2788,26 +2754,18 @@ static int grow_after_overflow(sa_batch *b) {
     sa_plan_grow_candidates(pl, 4);
     b->cand_factor = (b->cand_factor > 0 ? b->cand_factor : 1) * 4;
     cand_memo_note(pl->model, pl->params.threshold, b->device, b->cand_factor);
-    g_sa_pool.put(SaPool::DEVICE, b->d_cands);
-    g_sa_pool.put(SaPool::DEVICE, b->d_prob);
-    b->d_cands = nullptr;
-    b->d_prob = nullptr;
-    HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_cands, sizeof(sa_cand_t) * (size_t) pl->n_cand, b->device));
-    HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_prob, 8 * (size_t) pl->n_cand, b->device));
+    // the blocks sized by candidate slots (those of them the batch has), at their bytes per slot
+    const struct { void **slot; size_t bytes; } per_cand[] = {
+        {(void **) &b->d_cands, sizeof(sa_cand_t)}, {(void **) &b->d_prob, 8}, {(void **) &b->d_out, sizeof(sa_pair16_t)},
+        {(void **) &b->d_sortkey, 8}, {(void **) &b->d_sortidx, 4}};
+    for (const auto &k : per_cand) {
+        if (!*k.slot) continue;
+        g_sa_pool.put(SaPool::DEVICE, *k.slot);
+        *k.slot = nullptr;
+        HIPCHK(g_sa_pool.get(SaPool::DEVICE, k.slot, k.bytes * (size_t) pl->n_cand, b->device));
+    }
     b->cand_alloc = pl->n_cand;
-    if (b->d_out) {
-        g_sa_pool.put(SaPool::DEVICE, b->d_out);
-        b->d_out = nullptr;
-        HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_out, sizeof(sa_pair16_t) * (size_t) pl->n_cand, b->device));
-        b->out_alloc = pl->n_cand;
-    }
-    if (b->d_sortkey) {
-        g_sa_pool.put(SaPool::DEVICE, b->d_sortkey);
-        g_sa_pool.put(SaPool::DEVICE, b->d_sortidx);
-        b->d_sortkey = nullptr; b->d_sortidx = nullptr;
-        HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_sortkey, 8 * (size_t) pl->n_cand, b->device));
-        HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_sortidx, 4 * (size_t) pl->n_cand, b->device));
-    }
+    if (b->d_out) b->out_alloc = pl->n_cand;
     HIPCHK(hipMemcpy(b->d_segs, pl->segs, sizeof(sa_seg_t) * (size_t) pl->n_segs, hipMemcpyHostToDevice));
     return SA_OK;
 }
@@ -2922,7 +2880,6 @@ static int batch_run_body(sa_batch_t *b) {
     std::vector<long long> gbase(ng + 1, 0);
     bool done = false;
     const bool trace = getenv("SA_TRACE") != nullptr;
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     for (int attempt = 0; attempt < 6 && !done; attempt++) {
         double t0 = now_ms();
         bool piped = true;
@@ -3125,17 +3082,7 @@ int sa_batch_release_device(sa_batch_t *b) {
         if (b->xstream[i]) HIPCHK(sa_sync_stream(b->xstream[i], b->device));
     }
     if (b->pair_stream) HIPCHK(sa_sync_stream(b->pair_stream, b->device));
-    void **ptrs[] = {(void **) &b->d_regions, (void **) &b->d_rows, (void **) &b->d_pk, (void **) &b->d_poff, (void **) &b->d_pid, (void **) &b->d_px,
-                     (void **) &b->d_xc, (void **) &b->d_prec, (void **) &b->d_ev, (void **) &b->d_segs, (void **) &b->d_cks, (void **) &b->d_F,
-                     (void **) &b->d_E, (void **) &b->d_vbuf, (void **) &b->d_cands, (void **) &b->d_cand_count, (void **) &b->d_overflow,
-                     (void **) &b->d_totals, (void **) &b->d_bscratch, (void **) &b->d_tab6, (void **) &b->d_noise3, (void **) &b->d_evn, (void **) &b->d_two,
-                     (void **) &b->d_hdp_slot, (void **) &b->d_hdp_y, (void **) &b->d_hdp_slope, (void **) &b->d_hdp_grid, (void **) &b->d_hdp_tab, (void **) &b->d_hdp_coef,
-                     (void **) &b->d_prob, (void **) &b->d_seg_pass, (void **) &b->d_seg_off, (void **) &b->d_out, (void **) &b->d_ids,
-                     (void **) &b->d_gsum, (void **) &b->d_gmc, (void **) &b->d_seam, (void **) &b->d_blk, (void **) &b->d_spec,
-                     (void **) &b->d_sortkey, (void **) &b->d_sortidx, (void **) &b->d_vc_bits, (void **) &b->d_vc_off,
-                     (void **) &b->d_seg_all};
-    for (void **pp : ptrs)
-        if (*pp) { g_sa_pool.put(SaPool::DEVICE, *pp); *pp = nullptr; }
+    b->put_blocks(0, sa_batch::BLK_END);
     if (b->held_stage) { g_sa_pool.put(SaPool::PINNED, b->held_stage); b->held_stage = nullptr; }
     sa_sites_release_device(b->sites);
     b->released = true;
