@@ -13,9 +13,9 @@ import sys
 p = sys.argv[1]
 s = open(p).read()
 s = s.replace('#include "sa_ring.inc"\n', '#include "sa_ring.inc"\n#include "sa_ringp.inc"\n', 1)
-old = "                    launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], 64 * ((cl & 7) + 1), cl >= 8);"
+old = "                    launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], ring_class(cl).cap, ring_class(cl).multi);"
 new = ("                    if ((cl == 8 || cl == 9) && ring_packed_on())\n"
-       "                        launch_fwd_ringp(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], 64 * ((cl & 7) + 1));\n"
+       "                        launch_fwd_ringp(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], ring_class(cl).cap);\n"
        "                    else\n    " + old)
 assert old in s
 open(p, 'w').write(s.replace(old, new))

@@ -1665,13 +1665,14 @@ __global__ __launch_bounds__(64 * FAST_WAVES) __attribute__((amdgpu_waves_per_eu
                              bscratch, E_all, T, seg_ids, n, gsum, gmc);
 }
 
-static FastT make_fast_t(const DevPlan &P) {
+// wide_cap: cells per row of k_fwd_fast*'s LDS ring for wide diagonals (0 for every other kernel)
+static FastT make_fast_t(const DevPlan &P, int wide_cap = 0) {
     FastT T;
     memset(&T, 0, sizeof(T));
     T.t_mm = P.m.t_mm; T.t_xm = P.m.t_xm; T.t_ym = P.m.t_ym; T.t_my = P.m.t_my; T.t_yy = P.m.t_yy;
     T.t_mx = P.m.t_mx; T.t_xx = P.m.t_xx;
     T.thr_off = P.log_thr - SA_CAND_EPS;
-    T.wide_cap = 0;
+    T.wide_cap = wide_cap;
     T.spec = P.spec;
     T.slack = P.spec_slack;
     T.two_xn_off = P.two_xn_off;
@@ -1684,83 +1685,61 @@ static FastT make_fast_t(const DevPlan &P) {
     return T;
 }
 
-static int fast_waves_per_block() {
-    static int w = 0;
-    if (w == 0) {
-        const char *e = getenv("SA_FAST_WAVES");  // tuning hook: waves per workgroup (1..FAST_WAVES)
-        w = e ? atoi(e) : FAST_WAVES;
-        if (w < 1 || w > FAST_WAVES) w = FAST_WAVES;
-    }
-    return w;
-}
-
+// The register kernels: one wave per region (forward) / segment (backward), FAST_WAVES to a workgroup.  The emission flavour
+// (HDP plane, two distributions, Gaussian) and the expectation pass pick the instance; the HDP and two-distribution kernels
+// take their extra table through the same parameter.
 static void launch_fwd_fast(const DevPlan &P, const int *ids, int n, hipStream_t st, int wide_cap) {
-    const int W = fast_waves_per_block();
-    int blocks = (n + W - 1) / W;
-    FastT T = make_fast_t(P);
-    T.wide_cap = wide_cap;
-    const size_t lds = sizeof(double) * 9 * (size_t) wide_cap * (size_t) W;   // 3 rows x 3 planes per wave
-    if (P.m.hdp)
-        hipLaunchKernelGGL(k_fwd_fast_hdp, dim3(blocks), dim3(64 * W), lds, st, P.regions, P.rows, P.pk,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, (const double *) P.E, T, ids, n, P.segs);
-    else if (P.two)
-        hipLaunchKernelGGL(k_fwd_fast_two, dim3(blocks), dim3(64 * W), lds, st, P.regions, P.rows, P.pk,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, (const double *) P.two, T, ids, n, P.segs);
-    else
-        hipLaunchKernelGGL(k_fwd_fast, dim3(blocks), dim3(64 * W), lds, st, P.regions, P.rows, P.pk,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, T, ids, n, P.segs);
-}
-// the emission plane of the register-kernel regions of one forward-storage pass (HDP models only); max_n: diagonals of the
-// longest region of the list
-static void launch_emit_hdp(const DevPlan &P, const int *ids, int n, long long max_n, hipStream_t st) {
-    const unsigned tiles = (unsigned) ((max_n + 1 + EMIT_TILE - 1) / EMIT_TILE);
-    for (int a = 0; a < n; a += 32768) {   // (grid.y is a 16-bit quantity)
-        const int m = n - a < 32768 ? n - a : 32768;
-        hipLaunchKernelGGL(k_emit_hdp, dim3(tiles, (unsigned) m), dim3(256), 0, st, P.regions, P.rows,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, P.m.hdp_tab, P.m.hdp_coef, P.E, make_fast_t(P), ids + a);
-    }
-}
-// ... and of the ring / strip regions of one launch list (multi: several paths per cell, per-path records)
-static void launch_emit_hdp_ring(const DevPlan &P, const int *ids, int n, long long max_n, hipStream_t st, bool multi) {
-    const unsigned tiles = (unsigned) ((max_n + 1 + EMIT_TILE - 1) / EMIT_TILE);
-    for (int a = 0; a < n; a += 32768) {
-        const int m = n - a < 32768 ? n - a : 32768;
-        if (multi)
-            hipLaunchKernelGGL(k_emit_hdp_ring<true>, dim3(tiles, (unsigned) m), dim3(256), 0, st, P.regions, P.rows, P.prec,
-                               reinterpret_cast<const double4 *>(P.xc), P.ev, P.m.hdp_tab, P.m.hdp_coef, P.E, make_fast_t(P), ids + a);
-        else
-            hipLaunchKernelGGL(k_emit_hdp_ring<false>, dim3(tiles, (unsigned) m), dim3(256), 0, st, P.regions, P.rows, P.prec,
-                               reinterpret_cast<const double4 *>(P.xc), P.ev, P.m.hdp_tab, P.m.hdp_coef, P.E, make_fast_t(P), ids + a);
+    const dim3 grid((n + FAST_WAVES - 1) / FAST_WAVES), block(64 * FAST_WAVES);
+    const size_t lds = sizeof(double) * 9 * (size_t) wide_cap * FAST_WAVES;   // 3 rows x 3 planes per wave
+    const FastT T = make_fast_t(P, wide_cap);
+    const double4 *xc = reinterpret_cast<const double4 *>(P.xc);
+    if (P.m.hdp || P.two) {
+        auto k = P.m.hdp ? k_fwd_fast_hdp : k_fwd_fast_two;
+        hipLaunchKernelGGL(k, grid, block, lds, st, P.regions, P.rows, P.pk, xc, P.ev, P.F, P.m.hdp ? (const double *) P.E : P.two,
+                           T, ids, n, P.segs);
+    } else {
+        hipLaunchKernelGGL(k_fwd_fast, grid, block, lds, st, P.regions, P.rows, P.pk, xc, P.ev, P.F, T, ids, n, P.segs);
     }
 }
 // returns SA_OK, or SA_ESTATE when the batch's state does not allow the launch (the caller's pass fails with that code: a library does
 // not abort its process)
-static int launch_bwd_fast(const DevPlan &P, const int *ids, int n, hipStream_t st, bool expect = false) {
-    const int W = fast_waves_per_block();
-    int blocks = (n + W - 1) / W;
-    if (!expect && P.spec == nullptr) {   // (cannot happen: a batch with register-kernel regions allocates d_spec, batch_finish_body)
+static int launch_bwd_fast(const DevPlan &P, const int *ids, int n, hipStream_t st) {
+    if (!P.expect && P.spec == nullptr) {   // (cannot happen: a batch with register-kernel regions allocates d_spec, batch_finish_body)
         fprintf(stderr, "[signalalign_hip] internal error: backward register kernels launched without speculative totals\n");
         return SA_ESTATE;
     }
-    if (expect && P.m.hdp)
-        hipLaunchKernelGGL(k_bwd_fast_expect<true>, dim3(blocks), dim3(64 * W), 0, st, P.regions, P.segs, P.rows, P.pk, P.cks,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
-                           P.cand_count, P.overflow, P.bscratch, (const double *) P.E, make_fast_t(P), ids, n, P.gsum, P.gmc);
-    else if (expect)
-        hipLaunchKernelGGL(k_bwd_fast_expect<false>, dim3(blocks), dim3(64 * W), 0, st, P.regions, P.segs, P.rows, P.pk, P.cks,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
-                           P.cand_count, P.overflow, P.bscratch, (const double *) nullptr, make_fast_t(P), ids, n, P.gsum, P.gmc);
-    else if (P.m.hdp)
-        hipLaunchKernelGGL(k_bwd_fast_hdp, dim3(blocks), dim3(64 * W), 0, st, P.regions, P.segs, P.rows, P.pk, P.cks,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
-                           P.cand_count, P.overflow, P.bscratch, (const double *) P.E, make_fast_t(P), ids, n);
-    else if (P.two)
-        hipLaunchKernelGGL(k_bwd_fast_two, dim3(blocks), dim3(64 * W), 0, st, P.regions, P.segs, P.rows, P.pk, P.cks,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
-                           P.cand_count, P.overflow, P.bscratch, (const double *) P.two, make_fast_t(P), ids, n);
-    else
-        hipLaunchKernelGGL(k_bwd_fast, dim3(blocks), dim3(64 * W), 0, st, P.regions, P.segs, P.rows, P.pk, P.cks,
-                           reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
-                           P.cand_count, P.overflow, P.bscratch, make_fast_t(P), ids, n);
+    const dim3 grid((n + FAST_WAVES - 1) / FAST_WAVES), block(64 * FAST_WAVES);
+    const FastT T = make_fast_t(P);
+    const double4 *xc = reinterpret_cast<const double4 *>(P.xc);
+    const double *F = P.F;
+    if (P.expect) {
+        auto k = P.m.hdp ? k_bwd_fast_expect<true> : k_bwd_fast_expect<false>;
+        hipLaunchKernelGGL(k, grid, block, 0, st, P.regions, P.segs, P.rows, P.pk, P.cks, xc, P.ev, F, P.vbuf, P.cands, P.cand_count,
+                           P.overflow, P.bscratch, P.m.hdp ? (const double *) P.E : nullptr, T, ids, n, P.gsum, P.gmc);
+    } else if (P.m.hdp || P.two) {
+        auto k = P.m.hdp ? k_bwd_fast_hdp : k_bwd_fast_two;
+        hipLaunchKernelGGL(k, grid, block, 0, st, P.regions, P.segs, P.rows, P.pk, P.cks, xc, P.ev, F, P.vbuf, P.cands, P.cand_count,
+                           P.overflow, P.bscratch, P.m.hdp ? (const double *) P.E : P.two, T, ids, n);
+    } else {
+        hipLaunchKernelGGL(k_bwd_fast, grid, block, 0, st, P.regions, P.segs, P.rows, P.pk, P.cks, xc, P.ev, F, P.vbuf, P.cands,
+                           P.cand_count, P.overflow, P.bscratch, T, ids, n);
+    }
     return SA_OK;
+}
+// The emission plane (HDP models only) of one launch list, one 256-thread workgroup per EMIT_TILE diagonals of each region: the
+// register-kernel regions of a forward-storage pass (ring == false), or the ring / strip regions of one launch list (ring == true;
+// multi: several paths per cell, per-path records).  max_n: diagonals of the longest region of the list.
+static void launch_emit_hdp(const DevPlan &P, const int *ids, int n, long long max_n, hipStream_t st, bool ring, bool multi) {
+    const unsigned tiles = (unsigned) ((max_n + 1 + EMIT_TILE - 1) / EMIT_TILE);
+    const FastT T = make_fast_t(P);
+    const double4 *xc = reinterpret_cast<const double4 *>(P.xc);
+    for (int a = 0; a < n; a += 32768) {   // (grid.y is a 16-bit quantity)
+        const dim3 grid(tiles, (unsigned) (n - a < 32768 ? n - a : 32768));
+        if (ring) {
+            auto k = multi ? k_emit_hdp_ring<true> : k_emit_hdp_ring<false>;
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, st, P.regions, P.rows, P.prec, xc, P.ev, P.m.hdp_tab, P.m.hdp_coef, P.E, T, ids + a);
+        } else {
+            hipLaunchKernelGGL(k_emit_hdp, grid, dim3(256), 0, st, P.regions, P.rows, xc, P.ev, P.m.hdp_tab, P.m.hdp_coef, P.E, T, ids + a);
+        }
+    }
 }

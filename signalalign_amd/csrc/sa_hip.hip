@@ -31,6 +31,7 @@
 #include <new>
 #include <thread>
 #include <time.h>
+#include <type_traits>
 #include <vector>
 
 #include "sa_internal.h"
@@ -736,6 +737,20 @@ __global__ __launch_bounds__(128) void k_bwd_generic(DevPlan P, const int *seg_i
     if (tid == 0) P.cand_count[seg] = count < S->cand_cap ? count : S->cand_cap;
 }
 
+// One workgroup of `threads` (64 / 128) per region (forward) / segment (backward).  relax: the RELAX flavour, its LDS ring
+// `ring_cap` cell-paths per row; otherwise EXACT (the expectation pass among them: a batch in that pass is never relaxed).
+static size_t generic_lds(bool relax, int ring_cap) {
+    return relax ? sizeof(double) * (size_t) (LA_TAB_DOUBLES + 9 * ring_cap) : 0;
+}
+static void launch_fwd_generic(const DevPlan &P, const int *ids, int n, hipStream_t st, int threads, bool relax, int ring_cap) {
+    auto k = relax ? k_fwd_generic<true> : k_fwd_generic<false>;
+    hipLaunchKernelGGL(k, dim3(n), dim3(threads), generic_lds(relax, ring_cap), st, P, ids, n, relax ? ring_cap : 0);
+}
+static void launch_bwd_generic(const DevPlan &P, const int *ids, int n, hipStream_t st, int threads, bool relax, int ring_cap) {
+    auto k = P.expect ? k_bwd_generic<true, false> : (relax ? k_bwd_generic<false, true> : k_bwd_generic<false, false>);
+    hipLaunchKernelGGL(k, dim3(n), dim3(threads), generic_lds(relax, ring_cap), st, P, ids, n, relax ? ring_cap : 0);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // fold: totalProbability of every checkpoint, folded exactly as dpDiagonal_dotProduct does
 // (impl/pairwiseAligner.c:1167-1180): a left fold over the cells in ascending x-y.
@@ -1231,6 +1246,12 @@ static int launch_class(const sa_region_t &R, bool strip_on) {
     }
     return R.kind == SA_KIND_FAST ? LC_FAST : LC_GENERIC;
 }
+// the ring class cl (launch class LC_RING + cl): rows of up to `cap` cell-paths, several paths per cell when `multi`
+struct ring_class_shape {
+    int cap;
+    bool multi;
+};
+static ring_class_shape ring_class(int cl) { return {64 * ((cl & 7) + 1), cl >= 8}; }
 struct sa_launch_chunk {
     sa_ids ids[LC_N];          // regions
     int g0, g1;                // groups [g0, g1)
@@ -2088,21 +2109,15 @@ static int batch_prepare_body(sa_batch *b) {
             if (pl->regions[r].kind == SA_KIND_FAST && pl->regions[r].slots > 1 && pl->regions[r].max_rowpaths > widest)
                 widest = pl->regions[r].max_rowpaths;
         if (widest > 0) b->wide_cap = (int) (widest < 256 ? (widest + 31) / 32 * 32 : 256);
-        if (const char *envw = getenv("SA_WIDE_CAP")) b->wide_cap = atoi(envw) < 0 ? 0 : atoi(envw);  // tuning / test hook
     }
     for (long long r = 0; r < pl->n_regions; r++)
         if (pl->regions[r].kind == SA_KIND_GENERIC && pl->regions[r].max_rowpaths > 64) b->gen_threads = 128;
-    if (const char *envt = getenv("SA_GENERIC_THREADS")) b->gen_threads = atoi(envt) == 128 ? 128 : 64;  // test hook
     if (b->relax) {
         long long cap = 0;
         for (long long r = 0; r < pl->n_regions; r++)
             if (pl->regions[r].kind == SA_KIND_GENERIC && pl->regions[r].max_rowpaths > cap) cap = pl->regions[r].max_rowpaths;
         // diagonals wider than the ring go through global memory one by one; a small ring keeps many waves per CU
-        long long lim = 128;
-        const char *envr = getenv("SA_RING_CAP");  // tuning hook
-        if (envr && atoll(envr) > 0) lim = atoll(envr);
-        if (lim > 900) lim = 900;                   // 64 KB of dynamic LDS
-        b->ring_cap = (int) (cap < lim ? cap : lim);
+        b->ring_cap = (int) (cap < 128 ? cap : 128);
     }
     // (round 4: the model tables, the plan arrays of a host-built plan and the emission constants go up here too -- with
     // sa_batch_prepare that is while the batch before this one still runs; nothing of it needs the working storage)
@@ -2578,27 +2593,16 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
     const sa_launch_group &G = b->groups[g];
     hipStream_t st = b->cstream[which_stream];
     HIPCHK(hipEventRecord(b->gev[4 * g], st));
-    const size_t relax_lds = sizeof(double) * (size_t) (LA_TAB_DOUBLES + 9 * b->ring_cap);
     const sa_ids &Lg = G.ids[LC_GENERIC], &Ls = G.ids[LC_STRIP], &Lf = G.ids[LC_FAST];
-    if (Lg.n && b->expect)
-        hipLaunchKernelGGL((k_bwd_generic<true, false>), dim3(Lg.n), dim3(b->gen_threads), 0, st, P, b->d_ids + Lg.off, Lg.n, 0);
-    else if (Lg.n && b->relax)
-        hipLaunchKernelGGL((k_bwd_generic<false, true>), dim3(Lg.n), dim3(b->gen_threads), relax_lds, st, P, b->d_ids + Lg.off, Lg.n,
-                           b->ring_cap);
-    else if (Lg.n)
-        hipLaunchKernelGGL((k_bwd_generic<false, false>), dim3(Lg.n), dim3(b->gen_threads), 0, st, P, b->d_ids + Lg.off, Lg.n, 0);
-    if (Ls.n) {
-        StripT ST;
-        ST.ev_total = pl->n_ev + 8; ST.seam_cap = b->seam_cap_bwd; ST.seam_stride = 32ull * b->seam_cap_bwd; ST.seam_first = G.seam_first;
-        ST.spec = b->d_spec;
-        ST.slack = b->spec_slack;
-        launch_bwd_strip1(P, b->d_ids + Ls.off, Ls.n, st, b->d_seam + b->seam_bwd_off, ST);
-    }
+    if (Lg.n) launch_bwd_generic(P, b->d_ids + Lg.off, Lg.n, st, b->gen_threads, b->relax, b->ring_cap);
+    if (Ls.n)
+        launch_bwd_strip(P, b->d_ids + Ls.off, Ls.n, st, b->d_seam + b->seam_bwd_off,
+                         make_strip_t(P, pl->n_ev + 8, b->seam_cap_bwd, G.seam_first));
     for (int cl = 15; cl >= 0; cl--) {   // widest (longest-running) classes first
         const sa_ids &L = G.ids[LC_RING + cl];
-        if (L.n) launch_bwd_ring(P, b->d_ids + L.off, L.n, st, 64 * ((cl & 7) + 1), cl >= 8, b->expect);
+        if (L.n) launch_bwd_ring(P, b->d_ids + L.off, L.n, st, ring_class(cl).cap, ring_class(cl).multi);
     }
-    if (Lf.n) { const int rcl = launch_bwd_fast(P, b->d_ids + Lf.off, Lf.n, st, b->expect); if (rcl) return rcl; }
+    if (Lf.n) { const int rcl = launch_bwd_fast(P, b->d_ids + Lf.off, Lf.n, st); if (rcl) return rcl; }
     HIPCHK(hipEventRecord(b->gev[4 * g + 1], st));
     if (G.ck1 > G.ck0)
         hipLaunchKernelGGL(k_fold, dim3((unsigned) ((G.ck1 - G.ck0 + 63) / 64)), dim3(64), 0, st, P, G.ck0, G.ck1);
@@ -2642,11 +2646,7 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
         const sa_launch_chunk &C = b->chunks[c];
         const sa_ids &Lg = C.ids[LC_GENERIC], &Ls = C.ids[LC_STRIP], &Lf = C.ids[LC_FAST];
         HIPCHK(hipEventRecord(b->cev[2 * c], s0));
-        if (Lg.n && b->relax)
-            hipLaunchKernelGGL(k_fwd_generic<true>, dim3(Lg.n), dim3(b->gen_threads), sizeof(double) * (size_t) (LA_TAB_DOUBLES + 9 * b->ring_cap),
-                               s0, P, b->d_ids + Lg.off, Lg.n, b->ring_cap);
-        else if (Lg.n)
-            hipLaunchKernelGGL(k_fwd_generic<false>, dim3(Lg.n), dim3(b->gen_threads), 0, s0, P, b->d_ids + Lg.off, Lg.n, 0);
+        if (Lg.n) launch_fwd_generic(P, b->d_ids + Lg.off, Lg.n, s0, b->gen_threads, b->relax, b->ring_cap);
         {   // ring-kernel regions, one launch per class of row capacity.  A forward launch holds one workgroup per read and
             // lasts as long as its longest read's serial chain, so launches that follow each other on one stream leave the chip
             // mostly empty three times over: the classes alternate between the two compute streams and run side by side
@@ -2660,10 +2660,11 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
                 }
             if (P.m.hdp) {   // the emission plane of this pass's ring / strip regions, ahead of the sweeps that read it (on s0: the
                              // other lanes wait for the event recorded below)
-                if (Ls.n) launch_emit_hdp_ring(P, b->d_ids + Ls.off, Ls.n, pl->regions[b->ids_flat[(size_t) Ls.off]].N, s0, false);
+                if (Ls.n) launch_emit_hdp(P, b->d_ids + Ls.off, Ls.n, pl->regions[b->ids_flat[(size_t) Ls.off]].N, s0, true, false);
                 for (int cl = 0; cl < 16; cl++) {
                     const sa_ids &L = C.ids[LC_RING + cl];
-                    if (L.n) launch_emit_hdp_ring(P, b->d_ids + L.off, L.n, pl->regions[b->ids_flat[(size_t) L.off]].N, s0, cl >= 8);
+                    if (L.n)
+                        launch_emit_hdp(P, b->d_ids + L.off, L.n, pl->regions[b->ids_flat[(size_t) L.off]].N, s0, true, ring_class(cl).multi);
                 }
             }
             if (n_lanes > 1) {
@@ -2672,17 +2673,13 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
             }
             int which = 0;
             if (Ls.n) {
-                StripT ST;
-                ST.ev_total = pl->n_ev + 8; ST.seam_cap = b->seam_cap; ST.seam_stride = 32ull * b->seam_cap; ST.seam_first = 0;
-                ST.spec = b->d_spec;
-                ST.slack = b->spec_slack;
-                launch_fwd_strip(P, b->d_ids + Ls.off, Ls.n, lanes[0], b->d_seam, ST);
+                launch_fwd_strip(P, b->d_ids + Ls.off, Ls.n, lanes[0], b->d_seam, make_strip_t(P, pl->n_ev + 8, b->seam_cap, 0));
                 which = n_lanes > 1 ? 1 : 0;
             }
             for (int cl = 15; cl >= 0; cl--) {
                 const sa_ids &L = C.ids[LC_RING + cl];
                 if (L.n) {
-                    launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], 64 * ((cl & 7) + 1), cl >= 8);
+                    launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], ring_class(cl).cap, ring_class(cl).multi);
                     which = (which + 1) % (n_lanes > 1 ? n_lanes : 1);
                 }
             }
@@ -2695,7 +2692,7 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
         // forward sweep of slice k runs beside the emission kernel of slice k + 1 -- neither keeps the chip busy alone --: forward
         // stage 15.8 -> 18.6 / 17.1 / 20.0 ms per 5000 reads.  A forward launch of fewer reads lasts as long as its longest chain and
         // the emission kernel slows down beside it by more than the overlap gives.)
-        if (Lf.n && P.m.hdp) launch_emit_hdp(P, b->d_ids + Lf.off, Lf.n, pl->regions[b->ids_flat[(size_t) Lf.off]].N, s0);
+        if (Lf.n && P.m.hdp) launch_emit_hdp(P, b->d_ids + Lf.off, Lf.n, pl->regions[b->ids_flat[(size_t) Lf.off]].N, s0, false, false);
         if (Lf.n) launch_fwd_fast(P, b->d_ids + Lf.off, Lf.n, s0, b->wide_cap);
         if (b->d_spec && C.g1 > C.g0) {   // the candidate bounds of this pass's register / ring / strip tracebacks (k_spec_match)
             const long long sa_ = b->groups[(size_t) C.g0].seg0, sb_ = b->groups[(size_t) C.g1 - 1].seg1;

@@ -809,105 +809,68 @@ static size_t ring_lds_fwd(int cap) { return sizeof(double) * (size_t) (LA_TAB_D
 static size_t ring_lds_bwd(int cap, bool multi) {
     return sizeof(double) * (size_t) (LA_TAB_DOUBLES + RING_XTRA + (multi ? 15 : 9) * cap);
 }
-
-template <bool MULTI>
-static void launch_fwd_ring_t(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, int waves) {
+static RingT make_ring_t(const DevPlan &P, int cap, bool all_planes) {
     RingT RT;
     RT.f = make_fast_t(P);
     RT.cap = cap;
     RT.spec = P.spec;
     RT.slack = P.spec_slack;
-    RT.all_planes = P.expect;
-    const int K = (cap + 64 * waves - 1) / (64 * waves);
-#define RING_FWD(KK)                                                                                                           \
-    do {                                                                                                                       \
-        if (P.m.hdp)                                                                                                           \
-            hipLaunchKernelGGL((k_fwd_ring<MULTI, KK, true>), dim3(n), dim3(64 * waves), ring_lds_fwd(cap), st, P.regions, P.rows, \
-                               P.pk, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, RT, ids, n, P.poff,            \
-                               (const double *) P.E, P.segs);                                                                  \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_fwd_ring<MULTI, KK, false>), dim3(n), dim3(64 * waves), ring_lds_fwd(cap), st, P.regions, P.rows, \
-                               P.pk, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, RT, ids, n, P.poff,            \
-                               (const double *) nullptr, P.segs);                                                              \
-        if (MULTI && P.m.hdp)   /* the sparse instance over the same list (DENSE above k_fwd_ring) */                           \
-            hipLaunchKernelGGL((k_fwd_ring<MULTI, KK, true, false>), dim3(n), dim3(64 * waves), ring_lds_fwd(cap), st, P.regions, P.rows, \
-                               P.pk, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, RT, ids, n, P.poff,            \
-                               (const double *) P.E, P.segs);                                                                  \
-        else if (MULTI)                                                                                                        \
-            hipLaunchKernelGGL((k_fwd_ring<MULTI, KK, false, false>), dim3(n), dim3(64 * waves), ring_lds_fwd(cap), st, P.regions, P.rows, \
-                               P.pk, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, RT, ids, n, P.poff,            \
-                               (const double *) nullptr, P.segs);                                                              \
-    } while (0)
-    if (K <= 1) RING_FWD(1);
-    else if (K == 2) RING_FWD(2);
-    else if (K <= 4) RING_FWD(4);
-    else RING_FWD(8);
-#undef RING_FWD
+    RT.all_planes = all_planes;
+    return RT;
 }
-// cap: cell-paths per ring row, a multiple of 64 up to 512
+// calls f(std::integral_constant<int, K>()) with the instance K -- cell-paths per thread and diagonal, 1, 2, 4 or 8 -- that
+// covers a ring of `cap` entries per row on `waves` waves
+template <typename Fn>
+static void with_ring_k(int cap, int waves, Fn f) {
+    const int K = (cap + 64 * waves - 1) / (64 * waves);
+    if (K <= 1) f(std::integral_constant<int, 1>());
+    else if (K == 2) f(std::integral_constant<int, 2>());
+    else if (K <= 4) f(std::integral_constant<int, 4>());
+    else f(std::integral_constant<int, 8>());
+}
+
+// One workgroup per region (forward) / segment (backward).  cap: cell-paths per ring row, a multiple of 64 up to 512; multi:
+// several paths per cell, where the dense and then the sparse instance run over the same list (DENSE above k_fwd_ring).
 static void launch_fwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi) {
-    if (multi) launch_fwd_ring_t<true>(P, ids, n, st, cap, ring_waves(cap));
-    else launch_fwd_ring_t<false>(P, ids, n, st, cap, ring_waves(cap));
-}
-
-template <bool MULTI>
-static void launch_bwd_ring_t(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, int waves) {
-    RingT RT;
-    RT.f = make_fast_t(P);
-    RT.cap = cap;
-    RT.spec = P.spec;
-    RT.slack = P.spec_slack;
-    RT.all_planes = 0;
-    const int K = (cap + 64 * waves - 1) / (64 * waves);
-#define RING_BWD(KK)                                                                                                              \
-    do {                                                                                                                          \
-        if (P.m.hdp)                                                                                                              \
-            hipLaunchKernelGGL((k_bwd_ring<MULTI, KK, true>), dim3(n), dim3(64 * waves), ring_lds_bwd(cap, MULTI), st, P.regions, \
-                               P.segs, P.rows, P.poff, P.cks, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev,              \
-                               (const double *) P.F, P.vbuf, P.cands, P.cand_count, P.overflow, RT, ids, n, (const double *) P.E); \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((k_bwd_ring<MULTI, KK, false>), dim3(n), dim3(64 * waves), ring_lds_bwd(cap, MULTI), st, P.regions, \
-                               P.segs, P.rows, P.poff, P.cks, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev,              \
-                               (const double *) P.F, P.vbuf, P.cands, P.cand_count, P.overflow, RT, ids, n,                       \
-                               (const double *) nullptr);                                                                         \
-        if (MULTI && P.m.hdp)   /* the sparse instance over the same list */                                                      \
-            hipLaunchKernelGGL((k_bwd_ring<MULTI, KK, true, false, false>), dim3(n), dim3(64 * waves), ring_lds_bwd(cap, MULTI), st, P.regions, \
-                               P.segs, P.rows, P.poff, P.cks, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev,              \
-                               (const double *) P.F, P.vbuf, P.cands, P.cand_count, P.overflow, RT, ids, n, (const double *) P.E); \
-        else if (MULTI)                                                                                                           \
-            hipLaunchKernelGGL((k_bwd_ring<MULTI, KK, false, false, false>), dim3(n), dim3(64 * waves), ring_lds_bwd(cap, MULTI), st, P.regions, \
-                               P.segs, P.rows, P.poff, P.cks, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev,              \
-                               (const double *) P.F, P.vbuf, P.cands, P.cand_count, P.overflow, RT, ids, n,                       \
-                               (const double *) nullptr);                                                                         \
-    } while (0)
-    if (K <= 1) RING_BWD(1);
-    else if (K == 2) RING_BWD(2);
-    else if (K <= 4) RING_BWD(4);
-    else RING_BWD(8);
-#undef RING_BWD
-}
-// the expectation pass: several paths per cell, Gaussian emissions
-static void launch_bwd_ring_expect(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap) {
     const int waves = ring_waves(cap);
-    RingT RT;
-    RT.f = make_fast_t(P);
-    RT.cap = cap;
-    RT.spec = P.spec;
-    RT.slack = P.spec_slack;
-    RT.all_planes = 1;
-    const int K = (cap + 64 * waves - 1) / (64 * waves);
-#define RING_BWDX(KK)                                                                                                             \
-    hipLaunchKernelGGL((k_bwd_ring<true, KK, false, true>), dim3(n), dim3(64 * waves), ring_lds_bwd(cap, true), st, P.regions, P.segs, \
-                       P.rows, P.poff, P.cks, P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, \
-                       P.cands, P.cand_count, P.overflow, RT, ids, n, (const double *) nullptr, P.gsum, P.gmc)
-    if (K <= 1) RING_BWDX(1);
-    else if (K == 2) RING_BWDX(2);
-    else if (K <= 4) RING_BWDX(4);
-    else RING_BWDX(8);
-#undef RING_BWDX
+    const RingT RT = make_ring_t(P, cap, P.expect);
+    const bool hdp = P.m.hdp;
+    with_ring_k(cap, waves, [&](auto KK) {
+        constexpr int K = decltype(KK)::value;
+        auto launch = [&](auto k) {
+            hipLaunchKernelGGL(k, dim3(n), dim3(64 * waves), ring_lds_fwd(cap), st, P.regions, P.rows, P.pk, P.prec,
+                               reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, RT, ids, n, P.poff,
+                               hdp ? (const double *) P.E : nullptr, P.segs);
+        };
+        if (multi) {
+            launch(hdp ? k_fwd_ring<true, K, true> : k_fwd_ring<true, K, false>);
+            launch(hdp ? k_fwd_ring<true, K, true, false> : k_fwd_ring<true, K, false, false>);
+        } else {
+            launch(hdp ? k_fwd_ring<false, K, true> : k_fwd_ring<false, K, false>);
+        }
+    });
 }
-static void launch_bwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi, bool expect = false) {
-    if (expect && multi) { launch_bwd_ring_expect(P, ids, n, st, cap); return; }
-    if (multi) launch_bwd_ring_t<true>(P, ids, n, st, cap, ring_waves(cap));
-    else launch_bwd_ring_t<false>(P, ids, n, st, cap, ring_waves(cap));
+// the expectation pass (P.expect) takes the EXPECT instance for several paths per cell (Gaussian emissions)
+static void launch_bwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi) {
+    const int waves = ring_waves(cap);
+    const bool expect = P.expect && multi;
+    const RingT RT = make_ring_t(P, cap, expect);
+    const bool hdp = P.m.hdp && !expect;
+    with_ring_k(cap, waves, [&](auto KK) {
+        constexpr int K = decltype(KK)::value;
+        auto launch = [&](auto k) {
+            hipLaunchKernelGGL(k, dim3(n), dim3(64 * waves), ring_lds_bwd(cap, multi), st, P.regions, P.segs, P.rows, P.poff, P.cks,
+                               P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
+                               P.cand_count, P.overflow, RT, ids, n, hdp ? (const double *) P.E : nullptr,
+                               expect ? P.gsum : nullptr, expect ? P.gmc : nullptr);
+        };
+        if (expect) {
+            launch(k_bwd_ring<true, K, false, true>);
+        } else if (multi) {
+            launch(hdp ? k_bwd_ring<true, K, true> : k_bwd_ring<true, K, false>);
+            launch(hdp ? k_bwd_ring<true, K, true, false, false> : k_bwd_ring<true, K, false, false, false>);
+        } else {
+            launch(hdp ? k_bwd_ring<false, K, true> : k_bwd_ring<false, K, false>);
+        }
+    });
 }

@@ -632,23 +632,26 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
     if (lane == 0) cand_count[seg] = count < cand_cap ? count : cand_cap;
 }
 
-static void launch_fwd_strip(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, StripT ST) {
+// seam: the launch's seam storage, seam_cap records per seam array and its first wave slot seam_first; ev_total: doubles in the
+// batch's event array
+static StripT make_strip_t(const DevPlan &P, long long ev_total, unsigned seam_cap, unsigned seam_first) {
+    StripT ST;
     ST.f = make_fast_t(P);
-    if (P.m.hdp)
-        hipLaunchKernelGGL(k_fwd_strip<true>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.rows,
-                           P.pk, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, seam, ST, ids, n, (const double *) P.E, P.segs);
-    else
-        hipLaunchKernelGGL(k_fwd_strip<false>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.rows,
-                           P.pk, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, seam, ST, ids, n, (const double *) nullptr, P.segs);
+    ST.ev_total = ev_total; ST.seam_cap = seam_cap; ST.seam_stride = 32ull * seam_cap; ST.seam_first = seam_first;
+    ST.spec = P.spec;
+    ST.slack = P.spec_slack;
+    return ST;
 }
-static void launch_bwd_strip1(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, StripT ST) {
-    ST.f = make_fast_t(P);
-    if (P.m.hdp)
-        hipLaunchKernelGGL(k_bwd_strip1<true>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs,
-                           P.rows, P.cks, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, P.cands, P.cand_count, P.overflow,
-                           seam, ST, ids, n, (const double *) P.E);
-    else
-        hipLaunchKernelGGL(k_bwd_strip1<false>, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs,
-                           P.rows, P.cks, reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, P.cands, P.cand_count, P.overflow,
-                           seam, ST, ids, n, (const double *) nullptr);
+// one wave per region (forward) / segment (backward), STRIP_WAVES to a workgroup
+static void launch_fwd_strip(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, const StripT &ST) {
+    auto k = P.m.hdp ? k_fwd_strip<true> : k_fwd_strip<false>;
+    hipLaunchKernelGGL(k, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.rows, P.pk,
+                       reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, seam, ST, ids, n, P.m.hdp ? (const double *) P.E : nullptr,
+                       P.segs);
+}
+static void launch_bwd_strip(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, const StripT &ST) {
+    auto k = P.m.hdp ? k_bwd_strip1<true> : k_bwd_strip1<false>;
+    hipLaunchKernelGGL(k, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs, P.rows, P.cks,
+                       reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, P.cands, P.cand_count, P.overflow, seam, ST, ids, n,
+                       P.m.hdp ? (const double *) P.E : nullptr);
 }
