@@ -370,7 +370,7 @@ int sa_dplan_compare(const sa_model_t *m, const sa_params_t *p, const sa_job_t *
  * struct AlignedPair list {ref_pos = k-mer index, read_pos = event index} in ascending order; it is empty and
  * status_out[j] != 0 when the reference would have rejected the alignment (bit 0: average log emission < -5.2, bit 1:
  * first/last k-mer not reached, bit 2: more than 50 skipped k-mers in a row, bit 3: more than 5 events per k-mer).
- * Parity of this entry point is pinned by the CPU restatement only (the reference's tests of it need fast5 files). */
+ * Bit-identical to the CPU restatement; the reference's own literals are pinned through sa_raw_event_align_batch below. */
 typedef struct sa_ea_job {
     const char *sequence;      /* nucleotides; a k-mer at every position (build_kmer_list, impl/eventAligner.c:755-782) */
     int64_t seq_len;
@@ -392,6 +392,62 @@ int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs, int64_t n
 /* sa_event_align_batch keeps its device and pinned-host scratch between calls (grow only, one workspace per process,
  * calls serialise on it); this returns the memory.  Safe to call at any time, also when nothing is held. */
 void sa_event_align_release(void);
+
+/* ---- event detection from raw current, chained into event alignment ------------------------------------------------
+ * detect_events (impl/event_detection.c:268-330, Scrappie's t-statistic detector) for many reads in one call, and
+ * load_from_raw2 (impl/eventAligner.c:1242-1300) up to the table fast5_set_basecall_event_table writes.  Events are
+ * bit-identical to the reference's arithmetic: raw to pA in float, sum / sum of squares as sequential double folds (the
+ * square a float product), compute_tstat's mix of double sums and float means, the short/long peak detector's integer
+ * semantics, create_event's float mean and stdv.  Callers read the fast5 themselves: int16 samples plus the channel_id
+ * attributes and the read's start_time, as floats (the reference reads them through H5T_NATIVE_FLOAT).
+ * Departures from the reference's undefined behaviour: a read whose detector emits no peak is ONE event [0, n) and its
+ * status has SA_RAW_NO_PEAK (the reference indexes peaks[-1]); n_samples == 0 is SA_EINVAL (the reference asserts).
+ * No trimming: every caller of trim_and_segment_raw in the reference discards its result, so detection runs over all
+ * n_samples. */
+typedef struct sa_raw_job {
+    const int16_t *raw;        /* Raw/Reads/Read_* /Signal, ADC counts                                              */
+    int64_t n_samples;         /* 1 .. 2^31 - 1                                                                      */
+    float digitisation, offset, range, sample_rate;  /* UniqueGlobalKey/channel_id (sample_rate: "sampling_rate")   */
+    float start_time;          /* Raw/Reads/Read_* start_time                                                        */
+} sa_raw_job_t;
+typedef struct sa_detector_params {
+    int32_t window_length1, window_length2;   /* >= 1 */
+    float threshold1, threshold2, peak_height;
+} sa_detector_params_t;
+/* inc/event_detection.h: event_detection_defaults and event_detection_rna */
+#define SA_DETECTOR_DNA {3, 6, 1.4f, 9.0f, 0.2f}
+#define SA_DETECTOR_RNA {7, 14, 2.5f, 9.0f, 1.0f}
+/* one row of the basecalled event table (basecalled_event, inc/eventAligner.h:16-26; event_table_to_basecalled_table,
+ * impl/eventAligner.c:744-768): the detector's float values widened to double, start / length in seconds */
+typedef struct sa_raw_event {
+    int64_t raw_start, raw_length;
+    double mean, stdv;
+    double start, length;
+    int32_t kmer_idx;          /* model_state as the k-mer position in the sequence (build_kmer_list order); -1: none */
+    int32_t move;
+    double p_model_state;      /* exp of the MeanOnly log emission of model_state under the MoM scalings; 0 unmapped */
+} sa_raw_event_t;
+#define SA_RAW_NO_PEAK 16      /* status bit: the detector emitted no peak (one event spans the read) */
+/* params NULL: SA_DETECTOR_DNA, or SA_DETECTOR_RNA with SA_FLAG_RNA.  events_out[j] (malloc'd, sa_free) holds job j's
+ * n_events_out[j] events in time order, kmer_idx -1.  status_out (may be NULL): 0 or SA_RAW_NO_PEAK per job;
+ * kernel_ms_out (may be NULL): HIP-event time of the detection kernels. */
+int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, const sa_detector_params_t *params, int device,
+                           unsigned flags, sa_raw_event_t **events_out, int64_t *n_events_out, int32_t *status_out,
+                           double *kernel_ms_out);
+/* load_from_raw2 for a batch: detection as above; with SA_FLAG_RNA the events reversed (reverse_events); MoM scalings
+ * (sa_scalings_mom on the events' means); sa_event_align_batch with var = 1; the base-to-event map on the host
+ * (alignment_to_base_event_map, with its skip of a second pair on one event while the previous k-mer is 0, or for RNA
+ * rna_alignment_to_base_event_map walked from the last pair, the table then reversed back to time order).
+ * events_out[j] is in time order with kmer_idx / move / p_model_state filled for mapped events (the rows the reference
+ * writes); pairs_out (may be NULL) receives sa_event_align_batch's pairs, event indices in the aligned order (reversed
+ * for RNA); status_out: sa_event_align_batch's bits | SA_RAW_NO_PEAK (a non-zero EA status leaves every event unmapped);
+ * shift_out / scale_out (may be NULL): the MoM scalings; kernel_ms_out (may be NULL): detection + alignment kernels. */
+int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t *jobs, const char *const *sequences, int64_t n_jobs,
+                             const sa_detector_params_t *params, int device, unsigned flags, sa_raw_event_t **events_out,
+                             int64_t *n_events_out, sa_ea_pair_t **pairs_out, int64_t *n_pairs_out, int32_t *status_out,
+                             double *shift_out, double *scale_out, double *kernel_ms_out);
+/* the detector's device and pinned-host scratch, kept between calls (grow only), returned */
+void sa_detect_release(void);
 
 /* fastaHandler_getSubSequence (impl/fasta_handler.c:15-44, htslib faidx underneath): bases [start, end) of the record
  * `name` (the header's first word) of a FASTA file; strand == 0 asks htslib for [end, start - 1] as the reference does.

@@ -72,6 +72,25 @@ class EaJob(C.Structure):
                 ("n_events", C.c_int64), ("scale", C.c_double), ("shift", C.c_double), ("var", C.c_double)]
 
 
+class RawJob(C.Structure):
+    _fields_ = [("raw", C.POINTER(C.c_int16)), ("n_samples", C.c_int64), ("digitisation", C.c_float), ("offset", C.c_float),
+                ("range", C.c_float), ("sample_rate", C.c_float), ("start_time", C.c_float)]
+
+
+class DetectorParams(C.Structure):
+    _fields_ = [("window_length1", C.c_int32), ("window_length2", C.c_int32), ("threshold1", C.c_float),
+                ("threshold2", C.c_float), ("peak_height", C.c_float)]
+
+
+# inc/event_detection.h: event_detection_defaults / event_detection_rna (window_length1, window_length2, threshold1,
+# threshold2, peak_height)
+DETECTOR_DNA = (3, 6, 1.4, 9.0, 0.2)
+DETECTOR_RNA = (7, 14, 2.5, 9.0, 1.0)
+RAW_NO_PEAK = 16
+RAW_EVENT_DTYPE = np.dtype([("raw_start", "<i8"), ("raw_length", "<i8"), ("mean", "<f8"), ("stdv", "<f8"), ("start", "<f8"),
+                            ("length", "<f8"), ("kmer_idx", "<i4"), ("move", "<i4"), ("p_model_state", "<f8")])
+
+
 class MeaJob(C.Structure):
     _fields_ = [("event_idx", C.POINTER(C.c_int32)), ("ref_idx", C.POINTER(C.c_int32)), ("posterior", C.POINTER(C.c_double)),
                 ("n", C.c_int64), ("shortest_ref_per_event", C.POINTER(C.c_int32)), ("n_events", C.c_int64)]
@@ -96,7 +115,7 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_batch_create", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
            "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
            "sa_plan_check_path_records", "sa_dplan_compare",
-           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
+           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
@@ -229,6 +248,12 @@ def lib():
     L.sa_event_align_batch.argtypes = [C.c_void_p, C.POINTER(EaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip,
                                        C.POINTER(C.c_int32), dp, dp]
     i32p = C.POINTER(C.c_int32)
+    L.sa_detect_events_batch.argtypes = [C.POINTER(RawJob), C.c_int64, C.POINTER(DetectorParams), C.c_int, C.c_uint,
+                                         C.POINTER(C.c_void_p), ip, i32p, dp]
+    L.sa_raw_event_align_batch.argtypes = [C.c_void_p, C.POINTER(RawJob), C.POINTER(C.c_char_p), C.c_int64,
+                                           C.POINTER(DetectorParams), C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip,
+                                           C.POINTER(C.c_void_p), ip, i32p, dp, dp, dp]
+    L.sa_detect_release.restype = None
     L.sa_mea_batch.argtypes = [C.POINTER(MeaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, i32p, dp]
     L.sa_batch_mea.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, dp]
     L.sa_batch_site_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(SiteCall)), ip, dp]
@@ -726,6 +751,89 @@ def event_align_batch(model, jobs, device=0, flags=0, stats=None):
 
 def _i32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _raw_jobs(jobs):
+    """jobs: dicts(raw int16 array, digitisation, offset, range, sample_rate, start_time)"""
+    n = len(jobs)
+    arr = (RawJob * max(n, 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        raw = np.ascontiguousarray(j["raw"], dtype=np.int16)
+        keep.append(raw)
+        arr[i] = RawJob(raw.ctypes.data_as(C.POINTER(C.c_int16)), len(raw), j["digitisation"], j["offset"], j["range"],
+                        j["sample_rate"], j["start_time"])
+    return arr, keep
+
+
+def _detector_params(params):
+    return None if params is None else C.byref(DetectorParams(*params))
+
+
+def _raw_events(ptrs, cnt, i):
+    a = np.zeros(int(cnt[i]), dtype=RAW_EVENT_DTYPE)
+    if cnt[i]:
+        C.memmove(a.ctypes.data, ptrs[i], RAW_EVENT_DTYPE.itemsize * int(cnt[i]))
+    lib().sa_free(ptrs[i])
+    return a
+
+
+def detect_events_batch(jobs, params=None, rna=False, device=0, stats=None):
+    """sa_detect_events_batch: one RAW_EVENT_DTYPE array per read (time order).  params: (window_length1, window_length2,
+    threshold1, threshold2, peak_height), default DETECTOR_DNA / DETECTOR_RNA; stats (a dict, optional) receives the
+    per-read status words (RAW_NO_PEAK) and the kernel time."""
+    n = len(jobs)
+    arr, keep = _raw_jobs(jobs)
+    ptrs = (C.c_void_p * max(n, 1))()
+    cnt = np.zeros(max(n, 1), dtype=np.int64)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    kms = C.c_double()
+    _chk(lib().sa_detect_events_batch(arr, n, _detector_params(params), device, FLAG_RNA if rna else 0, ptrs, _ip(cnt), _i32p(st),
+                                      C.byref(kms)), "sa_detect_events_batch")
+    del keep
+    if stats is not None:
+        stats["status"] = st[:n].copy()
+        stats["kernel_ms"] = kms.value
+    return [_raw_events(ptrs, cnt, i) for i in range(n)]
+
+
+def raw_event_align_batch(model, jobs, sequences, rna=False, params=None, device=0, stats=None):
+    """sa_raw_event_align_batch (load_from_raw2 for a batch).  Returns per read a dict: events (RAW_EVENT_DTYPE, time
+    order), model_state (k-mer string per event, "" unmapped), kmer_idx / event_idx (the event aligner's pairs, event
+    indices in the aligned order: reversed for RNA), status, shift, scale."""
+    n = len(jobs)
+    arr, keep = _raw_jobs(jobs)
+    seqs = [s.encode() for s in sequences]
+    sp = (C.c_char_p * max(n, 1))(*seqs)
+    ev_p, pr_p = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    ev_n, pr_n = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    sh, sc = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    kms = C.c_double()
+    _chk(lib().sa_raw_event_align_batch(model._h, arr, sp, n, _detector_params(params), device, FLAG_RNA if rna else 0, ev_p,
+                                        _ip(ev_n), pr_p, _ip(pr_n), _i32p(st), _dp(sh), _dp(sc), C.byref(kms)),
+         "sa_raw_event_align_batch")
+    del keep
+    if stats is not None:
+        stats["kernel_ms"] = kms.value
+    k = model.alphabet()[1]
+    out = []
+    for i in range(n):
+        ev = _raw_events(ev_p, ev_n, i)
+        a = np.zeros((int(pr_n[i]), 2), dtype=np.int32)
+        if pr_n[i]:
+            C.memmove(a.ctypes.data, pr_p[i], 8 * int(pr_n[i]))
+        lib().sa_free(pr_p[i])
+        seq = sequences[i].replace("U", "T") if rna else sequences[i]
+        kmers = [seq[p:p + k][::-1] if rna else seq[p:p + k] for p in range(len(seq) - k + 1)]
+        ms = [kmers[x] if x >= 0 else "" for x in ev["kmer_idx"].tolist()]
+        out.append(dict(events=ev, model_state=ms, kmer_idx=a[:, 0].copy(), event_idx=a[:, 1].copy(), status=int(st[i]),
+                        shift=float(sh[i]), scale=float(sc[i])))
+    return out
+
+
+def detect_release():
+    lib().sa_detect_release()
 
 
 def mea_batch(jobs, device=0, flags=0, stats=None):

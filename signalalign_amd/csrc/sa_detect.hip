@@ -1,0 +1,500 @@
+// sa_detect.hip -- event detection from raw current on the GPU, and the raw-to-event-map chain (load_from_raw2).
+//
+// What it replaces: detect_events (impl/event_detection.c:268-330, Scrappie's t-statistic detector) as load_from_raw2
+// (impl/eventAligner.c:1242-1300) calls it, then reverse_events, estimate_scalings_using_mom, the adaptive banded
+// event aligner and the base-to-event map.  The last three are the existing sa_scalings_mom / sa_event_align_batch
+// (sa_ea.hip): one event-alignment code path.
+//
+// Bit parity.  Every stage follows the reference's operations and casts (the file is compiled with -ffp-contract=off,
+// correctly rounded f32 division and square root, f32 denormals on):
+//   raw to pA       float: unit = range / digitisation, pA = (raw + offset) * unit
+//   prefix sums     double, sum[i+1] = sum[i] + x[i], sumsq[i+1] = sumsq[i] + (double)(x[i] * x[i]) with a FLOAT square.
+//                   A left-to-right fold: sumsq reaches ~2^38 with float-spaced terms, past 53 bits, so a parallel scan
+//                   (another association) is not bit-identical.  One lane per read runs the fold.
+//   t-statistics    compute_tstat (:58-115): double window sums, float sum2 / sumsq2, float means, combined_var built in
+//                   double and stored as float, clamped to FLT_MIN; fabs and sqrt in DOUBLE as the C library's are (the
+//                   HIP float overloads would round differently).  Parallel over samples.
+//   peak detector   short_long_peak_detector (:122-205): serial state machine, one lane per read; masked_to starts at 0
+//                   and compares as size_t (sample 0 is never examined), window halving is integer.
+//   events          create_events / create_event (:207-266): float length, mean = (float) dsum / length, var in float,
+//                   stdv = sqrtf(fmaxf(var, 0)).  Per-read offsets from a device scan of the peak counts.
+// Departures from undefined behaviour: a read with no peak is one event [0, n) (the reference reads peaks[-1]); an
+// empty read is SA_EINVAL.  No trimming: trim_and_segment_raw's result is discarded by every caller in the reference.
+//
+// Mapping: k_det_prefix and k_det_peaks run one lane per read (64 reads per wave), each lane streaming its own read
+// with 16-byte loads; k_det_tstat is one thread per sample (both windows), k_det_events one block per read.
+#include <hip/hip_runtime.h>
+
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "sa_internal.h"
+#include "sa_scratch.h"
+
+struct DetJob {
+    long long raw_off;   // samples (int16) into the raw image, a multiple of 8; also the offset of t1 / t2 / peaks
+    long long ps_off;    // into sum / sumsq (n + 1 entries per read)
+    int n;
+    float digitisation, offset, range;
+};
+
+struct DetEvent {        // event_t's fields the table needs
+    int start;
+    float length, mean, stdv;
+};
+
+#define DET_LANES 64
+
+// sum / sumsq of the pA values, one lane per read: 8 samples per 16-byte load, the next load in flight meanwhile
+__global__ __launch_bounds__(DET_LANES) void k_det_prefix(const DetJob *__restrict__ jobs, int n_jobs, const int16_t *__restrict__ raw,
+                                                          double *__restrict__ S, double *__restrict__ Q) {
+    const int r = blockIdx.x * DET_LANES + threadIdx.x;
+    if (r >= n_jobs) return;
+    const DetJob J = jobs[r];
+    const uint4 *src = (const uint4 *) (raw + J.raw_off);
+    double *s = S + J.ps_off, *q = Q + J.ps_off;
+    const float unit = J.range / J.digitisation, off = J.offset;
+    double a = 0.0, b = 0.0;
+    s[0] = 0.0;
+    q[0] = 0.0;
+    const int n = J.n, n_chunks = (n + 7) / 8;
+    uint4 nxt = src[0];
+    for (int c = 0; c < n_chunks; c++) {
+        const uint4 cur = nxt;
+        if (c + 1 < n_chunks) nxt = src[c + 1];
+        const unsigned w[4] = {cur.x, cur.y, cur.z, cur.w};
+        const int base = 8 * c;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (base + k < n) {
+                const int16_t v = (int16_t) ((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+                const float x = ((float) v + off) * unit;
+                a = a + (double) x;
+                b = b + (double) (x * x);
+                s[base + k + 1] = a;
+                q[base + k + 1] = b;
+            }
+        }
+    }
+}
+
+// compute_tstat for one window at sample i (d_length n, w_length w)
+__device__ __forceinline__ float det_tstat(const double *s, const double *q, int n, int w, int i) {
+    if (n < 2 * w || w < 2) return 0.0f;
+    if (i < w || i > n - w) return 0.0f;
+    double sum1 = s[i], sumsq1 = q[i];
+    if (i > w) {
+        sum1 -= s[i - w];
+        sumsq1 -= q[i - w];
+    }
+    const float sum2 = (float) (s[i + w] - s[i]);
+    const float sumsq2 = (float) (q[i + w] - q[i]);
+    const float wf = (float) w;
+    const float mean1 = (float) (sum1 / (double) wf);
+    const float mean2 = sum2 / wf;
+    float cv = (float) (sumsq1 / (double) wf - (double) (mean1 * mean1) + (double) (sumsq2 / wf) - (double) (mean2 * mean2));
+    cv = fmaxf(cv, FLT_MIN);
+    const float dm = mean2 - mean1;
+    return (float) (fabs((double) dm) / sqrt((double) (cv / wf)));
+}
+
+// both t-statistic arrays, one thread per sample; blk[b] = (read, first sample) of block b
+__global__ __launch_bounds__(256) void k_det_tstat(const DetJob *__restrict__ jobs, const int2 *__restrict__ blk, const double *__restrict__ S,
+                                                   const double *__restrict__ Q, float *__restrict__ T1, float *__restrict__ T2, int w1, int w2) {
+    const int2 bi = blk[blockIdx.x];
+    const DetJob J = jobs[bi.x];
+    const int i = bi.y + (int) threadIdx.x;
+    if (i >= J.n) return;
+    const double *s = S + J.ps_off, *q = Q + J.ps_off;
+    T1[J.raw_off + i] = det_tstat(s, q, J.n, w1, i);
+    T2[J.raw_off + i] = det_tstat(s, q, J.n, w2, i);
+}
+
+struct DetState {
+    long long masked_to;
+    int peak_pos;
+    float peak_value;
+    bool valid;
+};
+
+// short_long_peak_detector, one lane per read: peaks in emission order, their number in cnt[r]
+__global__ __launch_bounds__(DET_LANES) void k_det_peaks(const DetJob *__restrict__ jobs, int n_jobs, const float *__restrict__ T1,
+                                                         const float *__restrict__ T2, int *__restrict__ peaks, int *__restrict__ cnt,
+                                                         int w1, int w2, float thr1, float thr2, float ph) {
+    const int r = blockIdx.x * DET_LANES + threadIdx.x;
+    if (r >= n_jobs) return;
+    const DetJob J = jobs[r];
+    const float4 *t1 = (const float4 *) (T1 + J.raw_off), *t2 = (const float4 *) (T2 + J.raw_off);
+    int *pk = peaks + J.raw_off;
+    const int n = J.n, n_chunks = (n + 3) / 4;
+    DetState sd = {0, -1, FLT_MAX, false}, ld = {0, -1, FLT_MAX, false};
+    const long long half1 = w1 / 2, half2 = w2 / 2;
+    int np = 0;
+    float4 n1 = t1[0], n2 = t2[0];
+    for (int c = 0; c < n_chunks; c++) {
+        const float4 c1 = n1, c2 = n2;
+        if (c + 1 < n_chunks) { n1 = t1[c + 1]; n2 = t2[c + 1]; }
+        const float v1[4] = {c1.x, c1.y, c1.z, c1.w}, v2[4] = {c2.x, c2.y, c2.z, c2.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i = 4 * c + k;
+            if (i >= n) break;
+            // the short detector
+            if (sd.masked_to < i) {
+                const float v = v1[k];
+                if (sd.peak_pos == -1) {
+                    if (v < sd.peak_value) sd.peak_value = v;
+                    else if (v - sd.peak_value > ph) { sd.peak_value = v; sd.peak_pos = i; }
+                } else {
+                    if (v > sd.peak_value) { sd.peak_value = v; sd.peak_pos = i; }
+                    if (sd.peak_value > thr1) {   // dominate the long detector
+                        ld.masked_to = (long long) sd.peak_pos + w1;
+                        ld.peak_pos = -1;
+                        ld.peak_value = FLT_MAX;
+                        ld.valid = false;
+                    }
+                    if (sd.peak_value - v > ph && sd.peak_value > thr1) sd.valid = true;
+                    if (sd.valid && (long long) (i - sd.peak_pos) > half1) {
+                        if (np < n) pk[np] = sd.peak_pos;   // peaks rise strictly: np < n always; the test keeps a fault impossible
+                        np++;
+                        sd.peak_pos = -1;
+                        sd.peak_value = v;
+                        sd.valid = false;
+                    }
+                }
+            }
+            // the long detector
+            if (ld.masked_to < i) {
+                const float v = v2[k];
+                if (ld.peak_pos == -1) {
+                    if (v < ld.peak_value) ld.peak_value = v;
+                    else if (v - ld.peak_value > ph) { ld.peak_value = v; ld.peak_pos = i; }
+                } else {
+                    if (v > ld.peak_value) { ld.peak_value = v; ld.peak_pos = i; }
+                    if (ld.peak_value - v > ph && ld.peak_value > thr2) ld.valid = true;
+                    if (ld.valid && (long long) (i - ld.peak_pos) > half2) {
+                        if (np < n) pk[np] = ld.peak_pos;
+                        np++;
+                        ld.peak_pos = -1;
+                        ld.peak_value = v;
+                        ld.valid = false;
+                    }
+                }
+            }
+        }
+    }
+    cnt[r] = np < n ? np : n - 1;
+}
+
+// events per read (peaks + 1: a read without a peak is one event) -> exclusive offsets, one block; off[n_jobs] = total
+__global__ __launch_bounds__(1024) void k_det_scan(const int *__restrict__ cnt, int n_jobs, long long *__restrict__ off) {
+    __shared__ long long part[1024];
+    const int t = threadIdx.x, per = (n_jobs + 1023) / 1024, a = t * per, b = min(a + per, n_jobs);
+    long long sum = 0;
+    for (int j = a; j < b; j++) sum += cnt[j] + 1;
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const long long v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    long long run = part[t] - sum;
+    for (int j = a; j < b; j++) { off[j] = run; run += cnt[j] + 1; }
+    if (t == 1023) off[n_jobs] = part[t];
+}
+
+// create_events: event e of read r spans [peaks[e - 1], peaks[e]) with peaks[-1] = 0 and peaks[np] = n
+__global__ __launch_bounds__(256) void k_det_events(const DetJob *__restrict__ jobs, const int *__restrict__ peaks, const int *__restrict__ cnt,
+                                                    const long long *__restrict__ off, const double *__restrict__ S,
+                                                    const double *__restrict__ Q, DetEvent *__restrict__ out) {
+    const int r = blockIdx.x;
+    const DetJob J = jobs[r];
+    const int np = cnt[r];
+    const int *pk = peaks + J.raw_off;
+    const double *s = S + J.ps_off, *q = Q + J.ps_off;
+    DetEvent *o = out + off[r];
+    for (int e = threadIdx.x; e <= np; e += blockDim.x) {
+        const int st = e == 0 ? 0 : pk[e - 1];
+        const int en = e == np ? J.n : pk[e];
+        DetEvent ev;
+        ev.start = st;
+        ev.length = (float) (unsigned long long) ((long long) en - (long long) st);   // size_t difference, as the reference's
+        ev.mean = (float) (s[en] - s[st]) / ev.length;
+        const float deltasqr = (float) (q[en] - q[st]);
+        const float var = deltasqr / ev.length - ev.mean * ev.mean;
+        ev.stdv = sqrtf(fmaxf(var, 0.0f));
+        o[e] = ev;
+    }
+}
+
+#define DETCHK(call)                                                                                        \
+    do {                                                                                                    \
+        hipError_t e_ = (call);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
+            goto done;                                                                                      \
+        }                                                                                                   \
+    } while (0)
+
+// Device and pinned-host scratch of sa_detect_events_batch, kept between calls (sa_scratch.h).
+struct DetWorkspace : SaScratch {
+    void *d_ws = nullptr, *d_ev = nullptr, *h_raw = nullptr, *h_ev = nullptr;
+    size_t d_ws_cap = 0, d_ev_cap = 0, h_raw_cap = 0, h_ev_cap = 0;
+};
+static DetWorkspace g_det_ws;
+
+extern "C" void sa_detect_release(void) {
+    std::lock_guard<std::mutex> guard(g_det_ws.mu);
+    g_det_ws.release();
+}
+
+static const sa_detector_params_t k_det_dna = SA_DETECTOR_DNA, k_det_rna = SA_DETECTOR_RNA;
+
+extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, const sa_detector_params_t *params, int device,
+                                      unsigned flags, sa_raw_event_t **events_out, int64_t *n_events_out, int32_t *status_out,
+                                      double *kernel_ms_out) {
+    if ((!jobs && n_jobs > 0) || n_jobs < 0 || n_jobs > (1 << 30) || !events_out || !n_events_out) return SA_EINVAL;
+    const sa_detector_params_t P = params ? *params : ((flags & SA_FLAG_RNA) ? k_det_rna : k_det_dna);
+    if (P.window_length1 < 1 || P.window_length2 < 1) return SA_EINVAL;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        events_out[j] = nullptr;
+        n_events_out[j] = 0;
+        if (status_out) status_out[j] = 0;
+    }
+    for (int64_t j = 0; j < n_jobs; j++)
+        if (!jobs[j].raw || jobs[j].n_samples < 1 || jobs[j].n_samples > 0x7fffffffLL - 8) return SA_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
+        return SA_ENODEVICE;
+    }
+    if (device < 0 || device >= ndev) return SA_EINVAL;
+    if (n_jobs == 0) return SA_OK;
+    const size_t nj = (size_t) n_jobs;
+    std::vector<DetJob> hj(nj);
+    std::vector<int2> blk;
+    long long raw_tot = 0, ps_tot = 0;
+    for (size_t j = 0; j < nj; j++) {
+        DetJob &J = hj[j];
+        J.n = (int) jobs[j].n_samples;
+        J.raw_off = raw_tot;
+        J.ps_off = ps_tot;
+        J.digitisation = jobs[j].digitisation;
+        J.offset = jobs[j].offset;
+        J.range = jobs[j].range;
+        raw_tot += ((long long) J.n + 7) / 8 * 8;     // zero padding to the 16-byte chunk the lanes load
+        ps_tot += (long long) J.n + 1;
+        for (int b = 0; b < J.n; b += 256) blk.push_back(make_int2((int) j, b));
+    }
+    DetWorkspace &W = g_det_ws;
+    std::lock_guard<std::mutex> guard(W.mu);
+    int rc = SA_OK;
+    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
+    // device workspace: [jobs | blocks | raw | sum | sumsq | t1 | t2 | peaks | counts | offsets]; events in their own block
+    const size_t o_jobs = 0, o_blk = sa_up256(sizeof(DetJob) * nj), o_raw = sa_up256(o_blk + sizeof(int2) * blk.size()),
+                 o_s = sa_up256(o_raw + sizeof(int16_t) * (size_t) raw_tot), o_q = sa_up256(o_s + sizeof(double) * (size_t) ps_tot),
+                 o_t1 = sa_up256(o_q + sizeof(double) * (size_t) ps_tot), o_t2 = sa_up256(o_t1 + sizeof(float) * (size_t) raw_tot),
+                 o_pk = sa_up256(o_t2 + sizeof(float) * (size_t) raw_tot), o_cnt = sa_up256(o_pk + sizeof(int) * (size_t) raw_tot),
+                 o_off = sa_up256(o_cnt + sizeof(int) * nj), dev_bytes = o_off + sizeof(long long) * (nj + 1);
+    const size_t res_bytes = dev_bytes - o_cnt;   // counts | offsets, one copy back
+    const size_t raw_bytes = sizeof(int16_t) * (size_t) raw_tot;
+    float kms = 0;
+    long long n_ev_tot = 0;
+    const int *h_cnt;
+    const long long *h_off;
+    const DetEvent *h_ev;
+    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, dev_bytes, device)) != SA_OK) return rc;
+    // events: at most one per peak plus one per read, and peaks are fewer than samples
+    if ((rc = W.dev(&W.d_ev, &W.d_ev_cap, sizeof(DetEvent) * (size_t) (raw_tot + (long long) nj), device)) != SA_OK) return rc;
+    if ((rc = W.pin(&W.h_raw, &W.h_raw_cap, raw_bytes > res_bytes ? raw_bytes : res_bytes, device)) != SA_OK) return rc;
+    if ((rc = W.events()) != SA_OK) return rc;
+    {
+        int16_t *hr = (int16_t *) W.h_raw;
+        sa_parallel_for(nj, [&](size_t j) {
+            const DetJob &J = hj[j];
+            memcpy(hr + J.raw_off, jobs[j].raw, sizeof(int16_t) * (size_t) J.n);
+            for (int k = J.n; k % 8; k++) hr[J.raw_off + k] = 0;
+        });
+    }
+    {
+        char *d = (char *) W.d_ws;
+        const DetJob *d_jobs = (const DetJob *) (d + o_jobs);
+        double *d_s = (double *) (d + o_s), *d_q = (double *) (d + o_q);
+        float *d_t1 = (float *) (d + o_t1), *d_t2 = (float *) (d + o_t2);
+        int *d_pk = (int *) (d + o_pk), *d_cnt = (int *) (d + o_cnt);
+        long long *d_off = (long long *) (d + o_off);
+        DETCHK(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(DetJob) * nj, hipMemcpyHostToDevice, 0));
+        DETCHK(hipMemcpyAsync(d + o_blk, blk.data(), sizeof(int2) * blk.size(), hipMemcpyHostToDevice, 0));
+        DETCHK(hipMemcpyAsync(d + o_raw, W.h_raw, raw_bytes, hipMemcpyHostToDevice, 0));
+        DETCHK(hipEventRecord(W.e0, 0));
+        const unsigned lane_blocks = (unsigned) ((nj + DET_LANES - 1) / DET_LANES);
+        hipLaunchKernelGGL(k_det_prefix, dim3(lane_blocks), dim3(DET_LANES), 0, 0, d_jobs, (int) nj, (const int16_t *) (d + o_raw), d_s, d_q);
+        hipLaunchKernelGGL(k_det_tstat, dim3((unsigned) blk.size()), dim3(256), 0, 0, d_jobs, (const int2 *) (d + o_blk), d_s, d_q, d_t1,
+                           d_t2, P.window_length1, P.window_length2);
+        hipLaunchKernelGGL(k_det_peaks, dim3(lane_blocks), dim3(DET_LANES), 0, 0, d_jobs, (int) nj, d_t1, d_t2, d_pk, d_cnt,
+                           P.window_length1, P.window_length2, P.threshold1, P.threshold2, P.peak_height);
+        hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, 0, d_cnt, (int) nj, d_off);
+        hipLaunchKernelGGL(k_det_events, dim3((unsigned) nj), dim3(256), 0, 0, d_jobs, (const int *) d_pk, (const int *) d_cnt,
+                           (const long long *) d_off, (const double *) d_s, (const double *) d_q, (DetEvent *) W.d_ev);
+        DETCHK(hipEventRecord(W.e1, 0));
+        DETCHK(hipGetLastError());
+        DETCHK(hipMemcpyAsync(W.h_raw, d + o_cnt, res_bytes, hipMemcpyDeviceToHost, 0));   // the raw image is uploaded by now
+        DETCHK(hipStreamSynchronize(0));
+        DETCHK(hipEventElapsedTime(&kms, W.e0, W.e1));
+        h_cnt = (const int *) W.h_raw;
+        h_off = (const long long *) ((const char *) W.h_raw + (o_off - o_cnt));
+        n_ev_tot = h_off[nj];
+        if ((rc = W.pin(&W.h_ev, &W.h_ev_cap, sizeof(DetEvent) * (size_t) n_ev_tot, device)) != SA_OK) goto done;
+        DETCHK(hipMemcpyAsync(W.h_ev, W.d_ev, sizeof(DetEvent) * (size_t) n_ev_tot, hipMemcpyDeviceToHost, 0));
+        DETCHK(hipStreamSynchronize(0));
+    }
+    if (kernel_ms_out) *kernel_ms_out = (double) kms;
+    h_ev = (const DetEvent *) W.h_ev;
+    {
+        std::atomic<bool> oom(false);
+        sa_parallel_for(nj, [&](size_t j) {
+            const long long a = h_off[j], n = h_off[j + 1] - a;
+            sa_raw_event_t *o = (sa_raw_event_t *) malloc(sizeof(sa_raw_event_t) * (size_t) n);
+            if (!o) { oom = true; return; }
+            const float sr = jobs[j].sample_rate, st = jobs[j].start_time;
+            const double st_sr = (double) (st / sr);
+            for (long long e = 0; e < n; e++) {   // event_table_to_basecalled_table (impl/eventAligner.c:753-766)
+                const DetEvent &v = h_ev[a + e];
+                sa_raw_event_t &r = o[e];
+                r.raw_start = v.start;
+                r.raw_length = (int64_t) (uint64_t) v.length;
+                r.mean = v.mean;
+                r.stdv = v.stdv;
+                r.start = ((double) (uint64_t) v.start) / sr + st_sr;
+                r.length = v.length / sr;
+                r.kmer_idx = -1;
+                r.move = 0;
+                r.p_model_state = 0.0;
+            }
+            events_out[j] = o;
+            n_events_out[j] = n;
+            if (status_out) status_out[j] = h_cnt[j] == 0 ? SA_RAW_NO_PEAK : 0;
+        });
+        if (oom) rc = SA_ENOMEM;
+    }
+done:
+    if (rc != SA_OK)
+        for (size_t j = 0; j < nj; j++) { free(events_out[j]); events_out[j] = nullptr; n_events_out[j] = 0; }
+    return rc;
+}
+
+extern "C" int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t *jobs, const char *const *sequences, int64_t n_jobs,
+                                        const sa_detector_params_t *params, int device, unsigned flags, sa_raw_event_t **events_out,
+                                        int64_t *n_events_out, sa_ea_pair_t **pairs_out, int64_t *n_pairs_out, int32_t *status_out,
+                                        double *shift_out, double *scale_out, double *kernel_ms_out) {
+    if (!m || (!sequences && n_jobs > 0) || n_jobs < 0 || !events_out || !n_events_out || !status_out) return SA_EINVAL;
+    if (pairs_out && !n_pairs_out) return SA_EINVAL;
+    if (m->hdp) return SA_EUNSUPPORTED;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (!sequences[j]) return SA_EINVAL;
+        if (pairs_out) { pairs_out[j] = nullptr; n_pairs_out[j] = 0; }
+    }
+    const bool rna = (flags & SA_FLAG_RNA) != 0;
+    const size_t nj = (size_t) n_jobs;
+    double det_ms = 0, ea_ms = 0;
+    int rc = sa_detect_events_batch(jobs, n_jobs, params, device, flags, events_out, n_events_out, status_out, &det_ms);
+    if (rc != SA_OK || n_jobs == 0) return rc;
+    // the aligned event order (reverse_events for RNA) and the MoM scalings of it
+    std::vector<std::vector<double>> means(nj);
+    std::vector<sa_ea_job_t> ej(nj);
+    std::vector<double> shift(nj), scale(nj);
+    std::vector<sa_ea_pair_t *> pairs(nj, nullptr);
+    std::vector<int64_t> n_pairs(nj, 0);
+    std::vector<int32_t> ea_st(nj, 0);
+    for (size_t j = 0; j < nj && rc == SA_OK; j++) {
+        const int64_t n = n_events_out[j];
+        means[j].resize((size_t) n);
+        for (int64_t e = 0; e < n; e++) means[j][(size_t) e] = events_out[j][rna ? n - 1 - e : e].mean;
+        const int64_t len = (int64_t) strlen(sequences[j]);
+        rc = sa_scalings_mom(m, sequences[j], len, means[j].data(), n, flags, &shift[j], &scale[j]);
+        ej[j] = sa_ea_job_t{sequences[j], len, means[j].data(), n, scale[j], shift[j], 1.0};
+    }
+    if (rc == SA_OK)
+        rc = sa_event_align_batch(m, ej.data(), n_jobs, device, flags & SA_FLAG_RNA, pairs.data(), n_pairs.data(), ea_st.data(),
+                                  nullptr, &ea_ms);
+    if (rc == SA_OK) {
+        std::atomic<int> bad(SA_OK);
+        sa_parallel_for(nj, [&](size_t j) {
+            status_out[j] |= ea_st[j];
+            if (shift_out) shift_out[j] = shift[j];
+            if (scale_out) scale_out[j] = scale[j];
+            const int64_t np = n_pairs[j], n_ev = n_events_out[j], n_kmers = ej[j].seq_len - (m->k - 1);
+            if (np == 0) return;
+            std::vector<int32_t> ids((size_t) n_kmers);
+            const int rck = sa_ea_kmer_ids(m, sequences[j], n_kmers, rna, ids.data());
+            if (rck) { bad = rck; return; }
+            sa_raw_event_t *ev = events_out[j];
+            const double sc = scale[j], sh = shift[j];
+            // event index of the aligned table -> row of the time-ordered output
+            auto row = [&](int64_t e) -> sa_raw_event_t & { return ev[rna ? n_ev - 1 - e : e]; };
+            auto map = [&](int64_t k, int64_t e) {
+                sa_raw_event_t &r = row(e);
+                const int64_t id = ids[(size_t) k];
+                const double mu = m->table5[5 * id], sd = m->table5[5 * id + 1];
+                // emissions_signal_strawManGetKmerEventMatchProbWithDescaling_MeanOnly with var = 1 (sa_ea.hip: ea_emit)
+                const double c = sd == 0.0 ? -INFINITY : (-0.91893853320467267 - log(sd));
+                const double en = (r.mean + 1.0 * mu - sc * mu - sh) / 1.0;
+                const double a = (en - mu) / (sd == 0.0 ? 1.0 : sd);
+                r.p_model_state = exp(log(1 / 1.0) + (c + (-0.5 * a * a)));
+                r.kmer_idx = (int32_t) k;
+            };
+            const sa_ea_pair_t *p = pairs[j];
+            int64_t prev_e = -1;
+            if (!rna) {   // alignment_to_base_event_map (impl/eventAligner.c:1310-1360)
+                int64_t prev_k = 0;
+                for (int64_t i = 0; i < np; i++) {
+                    const int64_t k = p[i].kmer_idx, e = p[i].event_idx;
+                    if (e == prev_e) {
+                        if (k == prev_k || prev_k == 0) continue;   // the reference reports the first, skips the second
+                        map(k, e);
+                        row(e).move += (int32_t) (k - prev_k);
+                    } else {
+                        map(k, e);
+                        row(e).move = (int32_t) (k - prev_k);
+                    }
+                    prev_k = k;
+                    prev_e = e;
+                }
+            } else {      // rna_alignment_to_base_event_map (:1362-1414), walked from the last pair
+                int64_t prev_k = n_kmers - 1;
+                for (int64_t i = np - 1; i >= 0; i--) {
+                    const int64_t k = p[i].kmer_idx, e = p[i].event_idx;
+                    if (e == prev_e) {
+                        if (k == prev_k) continue;
+                        map(k, e);
+                        row(e).move += (int32_t) (prev_k - k);
+                    } else {
+                        map(k, e);
+                        row(e).move = (int32_t) (prev_k - k);
+                    }
+                    prev_k = k;
+                    prev_e = e;
+                }
+            }
+        });
+        rc = bad;
+    }
+    if (kernel_ms_out) *kernel_ms_out = det_ms + ea_ms;
+    for (size_t j = 0; j < nj; j++) {
+        if (pairs_out && rc == SA_OK) { pairs_out[j] = pairs[j]; n_pairs_out[j] = n_pairs[j]; }
+        else free(pairs[j]);
+    }
+    if (rc != SA_OK)
+        for (size_t j = 0; j < nj; j++) { free(events_out[j]); events_out[j] = nullptr; n_events_out[j] = 0; }
+    return rc;
+}

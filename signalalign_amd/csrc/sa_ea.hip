@@ -13,8 +13,8 @@
 // blocks staged in LDS.
 // Arithmetic follows the reference's order of operations and float casts (the file is compiled with
 // -ffp-contract=off), with the emission of the memory-resident EXACT kernels: results are bit-identical to the CPU
-// restatement in oracle/sa_oracle.c.  PARITY UNPINNED against the reference itself: its tests of this function need
-// fast5 files (tests/eventAlignerTests.c:223-320, :404-430).
+// restatement in oracle/sa_oracle.c.  Pinned to the reference's own literals through the raw-current chain (sa_detect.hip:
+// tests/test_gpu_event_detect.py asserts tests/eventAlignerTests.c:404-433's last pair on this kernel's output).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -383,6 +383,11 @@ static int ea_kmer_ids(const sa_model_t *m, const char *seq, int64_t n_kmers, bo
         }
     }
     return SA_OK;
+}
+
+// the same ids for sa_detect.hip's base-to-event map (one k-mer list for both steps)
+int sa_ea_kmer_ids(const sa_model_t *m, const char *seq, int64_t n_kmers, bool rna, int32_t *out) {
+    return ea_kmer_ids(m, seq, n_kmers, rna, out);
 }
 
 #define EACHK(call)                                                                                         \

@@ -54,6 +54,10 @@ struct sa_model {
                               * model per read): what the library keys per-model memory on (candidate capacity, sa_hip.hip) */
 };
 uint64_t sa_model_next_uid(void);
+#ifdef __cplusplus
+/* sa_ea.hip: k-mer id of every position as build_kmer_list lists them (SA_EALPHABET for a foreign letter) */
+int sa_ea_kmer_ids(const sa_model_t *m, const char *seq, int64_t n_kmers, bool rna, int32_t *out);
+#endif
 
 /* ---- plan (host arrays, uploaded as they are) -------------------------------------------------- */
 typedef struct sa_row {

@@ -309,3 +309,23 @@ def make_reads_parallel(spec, indices, workers=None):
     except Exception:   # (no processes to be had: process limits, a broken pool) -- the serial loop gives the same reads
         return keep(_reads_chunk((spec, indices)))
     return keep([r for part in parts for r in part])
+
+
+def make_raw(seed, n_events, mean_dwell=9.0, noise_pa=1.5, level_range=(60.0, 130.0), n_samples=None):
+    """Synthetic raw current with known event boundaries: piecewise-constant levels (pA) with Gaussian noise, digitised to
+    int16 ADC counts with R9.4-like channel attributes.  Dwells are geometric with mean `mean_dwell` samples (at least
+    1).  n_samples: cut or pad (the last level held) to exactly this many samples.  Returns a dict in the shape
+    detect_events_batch takes (raw, digitisation, offset, range, sample_rate, start_time) plus `boundaries`, the first
+    sample of every level after the first."""
+    rng = np.random.default_rng(seed)
+    dwell = rng.geometric(1.0 / mean_dwell, size=max(n_events, 1))
+    levels = rng.uniform(level_range[0], level_range[1], size=len(dwell))
+    pa = np.repeat(levels, dwell)
+    if n_samples is not None:
+        pa = pa[:n_samples] if len(pa) >= n_samples else np.concatenate([pa, np.full(n_samples - len(pa), pa[-1])])
+    pa = pa + rng.normal(0.0, noise_pa, size=len(pa))
+    digitisation, offset, rng_pa = 8192.0, 10.0, 1452.26
+    raw = np.clip(np.round(pa * digitisation / rng_pa - offset), -32768, 32767).astype(np.int16)
+    b = np.cumsum(dwell)[:-1]
+    return dict(raw=raw, digitisation=digitisation, offset=offset, range=rng_pa, sample_rate=4000.0,
+                start_time=float(rng.integers(0, 10 ** 7)), boundaries=b[b < len(raw)])
