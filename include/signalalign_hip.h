@@ -567,6 +567,64 @@ typedef struct sa_site_call {
  * Deterministic: the sums are integer atomics. */
 int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out);
 
+/* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
+ * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
+ * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output
+ * (build_alignments.py:76-275) over the assignments rows (kmer, strand, descaled, prob) -- in HBM across batches.
+ *   printed   both values as the -s 2 file prints them, "%f": integers of 1e-6 (descaled: the CLI's descale() of the event mean
+ *             and the path k-mer's level mean in the table of the model the table was created with, no fused multiply-add)
+ *   ties      the row earlier in run order wins: batches and add_rows calls in call order, jobs in order, a job's rows in
+ *             sa_batch_pairs order (the reference's order comes from a directory listing: the one deliberate difference)
+ * sa_kmer_table_add_batch reads a finished batch's records where the run left them in HBM (16- or 8-byte ones); after
+ * sa_batch_release_device, and with SA_FLAG_EXACT (host-finalised pairs), the records are first copied up again, all of them; `jobs` / `n_jobs` are the batch's own (event means, scalings and, for
+ * 8-byte records, the references).  SA_FLAG_VC_ROWS batch: SA_EINVAL; not run: SA_ESTATE; a descaled value outside
+ * +-2^31 or not finite: SA_EUNSUPPORTED.  max_per_kmer < 1 or min_prob outside [0, 1]: SA_EINVAL. */
+typedef struct sa_kmer_table sa_kmer_table_t;
+typedef struct sa_kmer_row {
+    int64_t descaled_units;   /* "%f" of the descaled mean in 1e-6                                        */
+    int64_t run;              /* run ordinal of the row                                                    */
+    int32_t kmer_id, prob_units;
+    int32_t neg_zero;         /* 1: the descaled value printed as "-0.000000"                             */
+    int32_t pad;
+} sa_kmer_row_t;
+typedef struct sa_kmer_stat {
+    int64_t n;                /* rows of the k-mer in the table (0: the k-mer is not trained)              */
+    double m, s;              /* mean and population sd, or (use_median) median and MAD / ndtri(0.75)     */
+} sa_kmer_stat_t;
+int sa_kmer_table_create(sa_kmer_table_t **out, const sa_model_t *m, int64_t max_per_kmer, double min_prob, int device);
+void sa_kmer_table_destroy(sa_kmer_table_t *t);
+int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand, double *kernel_ms_out);
+/* rows read back from assignments files (parsed "%f" values; strand as above) */
+int sa_kmer_table_add_rows(sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, const double *descaled, const double *prob, int64_t n);
+/* the table's rows of a strand, k-mer ascending, posterior descending, then run order; *rows_out malloc'd (sa_free) */
+int sa_kmer_table_rows(const sa_kmer_table_t *t, int strand, sa_kmer_row_t **rows_out, int64_t *n_out);
+/* the rows as the table file prints them, "kmer\tstrand\tdescaled\tprob\n": strand 0 or 1, or -1 for both (t, then c); append
+ * != 0 adds them to the end of an existing file */
+int sa_kmer_table_write(const sa_kmer_table_t *t, int strand, const char *path, int append);
+/* The table as it is now becomes the state sa_kmer_table_rollback returns to (rows and run ordinals): for a caller that may
+ * have to add a slice of reads again (signalMachine --batch drops reads a batch's planner refuses and runs the rest again).
+ * The arrays a strand had at the checkpoint are kept until the next checkpoint or destroy, not copied.  Rollback without a
+ * checkpoint: SA_ESTATE. */
+int sa_kmer_table_checkpoint(sa_kmer_table_t *t);
+int sa_kmer_table_rollback(sa_kmer_table_t *t);
+/* per k-mer (out: one entry per kmer_id) statistics over the table's rows, computed exactly on the device: mean = the double
+ * nearest S / (n 1e6), sd = sqrt of the double nearest (n Q - S^2) / (n^2 1e12); median and MAD exact in half / quarter units,
+ * MAD converted and divided by 0.6744897501960817 (scipy's scale='normal') */
+int sa_kmer_table_stats(const sa_kmer_table_t *t, int strand, int use_median, sa_kmer_stat_t *out, double *kernel_ms_out);
+/* The M-step and HmmModel.write (hiddenMarkovModel.py:304-336), host only: the prior model file as written, and for every k-mer
+ * with stats[id].n > 0 (and, with mod_only, a letter outside ACGT; with kmer_mask, mask[id] != 0)
+ *   mean = (m n + mean0 w) / (n + w), sd = max((s n + sd0 w) / (n + w), min_sd), noise_lambda = mean^3 / sd^2
+ * (set_kmer_event_mean_params, :900-909: the lambda is overwritten, a reference quirk kept on purpose).  Every number is
+ * printed as Python's str(float). */
+int sa_model_write_trained(const char *prior_model_path, const sa_kmer_stat_t *stats, double weight, double min_sd, int mod_only,
+                           const uint8_t *kmer_mask, const char *out_path);
+/* Python's repr of a double (shortest round-trip digits); `out` needs 32 bytes; returns the length (test hook and writer) */
+int sa_format_py_repr(char *out, double v);
+/* the device's "%f" rounding of v[0 .. n) into units of 1e-6 and the negative-zero flag (test hook: must equal the host's,
+ * sa_f6_units); returns SA_EUNSUPPORTED in rc_out[i] for a value outside +-2^31 */
+int sa_f6_units_device(const double *v, int64_t n, int64_t *units_out, int32_t *neg_zero_out, int32_t *rc_out, int device);
+int sa_f6_units(double v, int64_t *units_out, int32_t *neg_zero_out);
+
 /* Plans a whole batch on the host (no GPU needed) with `threads` planner threads (0 = as sa_batch_create would) and
  * returns aggregate geometry plus a 64-bit FNV-1a digest over every array that would be uploaded.  The digest must
  * not depend on the number of threads: the CPU test-suite checks exactly that. */

@@ -120,6 +120,8 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
            "sa_hmm_load_into_model", "sa_model_transitions10",
+           "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
+           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
            "sa_version", "sa_free"]
 
 
@@ -258,6 +260,20 @@ def lib():
     L.sa_batch_mea.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, dp]
     L.sa_batch_site_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(SiteCall)), ip, dp]
     L.sa_format_py_round6.argtypes = [C.c_char_p, C.c_double]
+    L.sa_kmer_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_double, C.c_int]
+    L.sa_kmer_table_destroy.argtypes = [C.c_void_p]
+    L.sa_kmer_table_destroy.restype = None
+    L.sa_kmer_table_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int64, C.c_int, dp]
+    L.sa_kmer_table_add_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), dp, dp, C.c_int64]
+    L.sa_kmer_table_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), ip]
+    L.sa_kmer_table_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+    L.sa_kmer_table_checkpoint.argtypes = [C.c_void_p]
+    L.sa_kmer_table_rollback.argtypes = [C.c_void_p]
+    L.sa_kmer_table_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, dp]
+    L.sa_model_write_trained.argtypes = [C.c_char_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_char_p]
+    L.sa_format_py_repr.argtypes = [C.c_char_p, C.c_double]
+    L.sa_f6_units_device.argtypes = [dp, C.c_int64, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
+    L.sa_f6_units.argtypes = [C.c_double, ip, C.POINTER(C.c_int32)]
     L.sa_mea_printed_posterior_device.argtypes = [C.c_int64, C.c_int64, dp, C.c_int]
     L.sa_mea_printed_posterior.restype = C.c_double
     L.sa_mea_printed_posterior.argtypes = [C.c_int64]
@@ -486,6 +502,7 @@ class Batch:
         else:
             self.n_jobs = len(jobs)
             arr, self._keep = _make_jobs(jobs)
+        self._arr = arr   # (KmerTable.add_batch hands the jobs over again)
         amb = ambig if ambig is not None else default_ambig()
         self._amb, self._model = amb, model
         self._flags = int(flags)
@@ -1234,3 +1251,110 @@ def hdp_finalize_distributions(grid, collectors, samples, device=0):
     _chk(lib().sa_hdp_finalize_distributions(_dp(grid), len(grid), _dp(s), s.shape[0], int(samples), device, _dp(y), _dp(k)),
          "sa_hdp_finalize_distributions")
     return y, k
+
+
+# ---- Gaussian k-mer emission training (sa_kmer_table_*, sa_model_write_trained) ----------------------------------------
+KMER_ROW_DTYPE = np.dtype([("descaled_units", "<i8"), ("run", "<i8"), ("kmer_id", "<i4"), ("prob_units", "<i4"),
+                           ("neg_zero", "<i4"), ("pad", "<i4")])
+KMER_STAT_DTYPE = np.dtype([("n", "<i8"), ("m", "<f8"), ("s", "<f8")])
+
+
+class KmerTable:
+    """sa_kmer_table_t: per strand (0 't', 1 'c') and path k-mer the max_per_kmer rows of largest printed posterior
+    (>= min_prob), kept in HBM across add_batch / add_rows calls."""
+
+    def __init__(self, model, max_per_kmer=10, min_prob=0.8, device=0):
+        self._h = C.c_void_p()
+        self._model = model
+        _chk(lib().sa_kmer_table_create(C.byref(self._h), model._h, int(max_per_kmer), float(min_prob), int(device)),
+             "sa_kmer_table_create")
+
+    def add_batch(self, batch, strand=0, stats=None):
+        """the rows of a finished Batch (its own job array supplies event means, scalings and references)"""
+        kms = C.c_double()
+        _chk(lib().sa_kmer_table_add_batch(self._h, batch._h, batch._arr, batch.n_jobs, int(strand), C.byref(kms)),
+             "sa_kmer_table_add_batch")
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+
+    def add_rows(self, kmer_ids, descaled, prob, strand=0):
+        k = np.ascontiguousarray(kmer_ids, dtype=np.int32)
+        d = np.ascontiguousarray(descaled, dtype=np.float64)
+        p = np.ascontiguousarray(prob, dtype=np.float64)
+        assert len(k) == len(d) == len(p)
+        _chk(lib().sa_kmer_table_add_rows(self._h, int(strand), k.ctypes.data_as(C.POINTER(C.c_int32)), _dp(d), _dp(p), len(k)),
+             "sa_kmer_table_add_rows")
+
+    def rows(self, strand=0):
+        """structured array (KMER_ROW_DTYPE): k-mer ascending, posterior descending, then run order"""
+        ptr = C.c_void_p()
+        n = np.zeros(1, dtype=np.int64)
+        _chk(lib().sa_kmer_table_rows(self._h, int(strand), C.byref(ptr), _ip(n)), "sa_kmer_table_rows")
+        out = np.zeros(int(n[0]), dtype=KMER_ROW_DTYPE)
+        if n[0]:
+            C.memmove(out.ctypes.data, ptr, out.nbytes)
+        lib().sa_free(ptr)
+        return out
+
+    def write(self, path, strand=-1, append=False):
+        _chk(lib().sa_kmer_table_write(self._h, int(strand), os.fsencode(path), int(bool(append))), "sa_kmer_table_write")
+
+    def checkpoint(self):
+        _chk(lib().sa_kmer_table_checkpoint(self._h), "sa_kmer_table_checkpoint")
+
+    def rollback(self):
+        _chk(lib().sa_kmer_table_rollback(self._h), "sa_kmer_table_rollback")
+
+    def stats(self, strand=0, use_median=False, info=None):
+        """structured array (KMER_STAT_DTYPE), one entry per kmer_id"""
+        alpha, k = self._model.alphabet()
+        nk = len(alpha) ** k
+        out = np.zeros(nk, dtype=KMER_STAT_DTYPE)
+        kms = C.c_double()
+        _chk(lib().sa_kmer_table_stats(self._h, int(strand), int(bool(use_median)), out.ctypes.data, C.byref(kms)),
+             "sa_kmer_table_stats")
+        if info is not None:
+            info["kernel_ms"] = kms.value
+        return out
+
+    def close(self):
+        if self._h:
+            lib().sa_kmer_table_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def model_write_trained(prior_path, stats, out_path, weight=100.0, min_sd=0.0, mod_only=False, kmer_mask=None):
+    st = np.ascontiguousarray(stats, dtype=KMER_STAT_DTYPE)
+    mask = None if kmer_mask is None else np.ascontiguousarray(kmer_mask, dtype=np.uint8)
+    _chk(lib().sa_model_write_trained(os.fsencode(prior_path), st.ctypes.data, float(weight), float(min_sd), int(bool(mod_only)),
+                                      None if mask is None else mask.ctypes.data, os.fsencode(out_path)), "sa_model_write_trained")
+
+
+def format_py_repr(v):
+    buf = C.create_string_buffer(40)
+    n = lib().sa_format_py_repr(buf, float(v))
+    return buf.raw[:n].decode()
+
+
+def f6_units(v):
+    """host "%f" rounding of v: (units of 1e-6, negative-zero flag, rc)"""
+    u = np.zeros(1, dtype=np.int64)
+    z = C.c_int32()
+    rc = lib().sa_f6_units(float(v), _ip(u), C.byref(z))
+    return int(u[0]), int(z.value), rc
+
+
+def f6_units_device(values, device=0):
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    u = np.zeros(len(v), dtype=np.int64)
+    z = np.zeros(len(v), dtype=np.int32)
+    r = np.zeros(len(v), dtype=np.int32)
+    _chk(lib().sa_f6_units_device(_dp(v), len(v), _ip(u), z.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  r.ctypes.data_as(C.POINTER(C.c_int32)), int(device)), "sa_f6_units_device")
+    return u, z, r

@@ -3044,6 +3044,39 @@ int sa_batch_device_view(sa_batch_t *b, const sa_pair16_t **pairs, std::vector<l
     return SA_OK;
 }
 
+// The same for a step that reads either record size (sa_train.hip): *p8 says which.  Per job the first record in *recs (in
+// records of that size) and the number of records; a SA_FLAG_VC_ROWS batch is SA_EINVAL (it dropped rows), one that has not
+// run SA_ESTATE.
+int sa_batch_device_records(sa_batch_t *b, const void **recs, bool *p8, std::vector<long long> *first, std::vector<long long> *count,
+                            int *device) {
+    if (!b || !recs || !p8 || !first || !count || !device) return SA_EINVAL;
+    if (b->flags & SA_FLAG_VC_ROWS) return SA_EINVAL;
+    if (!b->ran || b->expect) return SA_ESTATE;
+    const size_t nj = (size_t) b->c_n;
+    first->assign(nj, 0); count->assign(nj, 0);
+    for (size_t j = 0; j < nj; j++) (*count)[j] = b->job_off[j + 1] - b->job_off[j];
+    *p8 = b->p8;
+    *device = b->device;
+    HIPCHK(hipSetDevice(b->device));
+    if (b->job_dev_off.size() == nj && !b->released) {
+        *recs = b->d_out;
+        for (size_t j = 0; j < nj; j++) (*first)[j] = b->job_dev_off[j];
+        return SA_OK;
+    }
+    // host-finalised or released: the records go up again, into a block counted in 16-byte records
+    const long long bytes = (long long) b->rec() * b->n_pairs_total, need16 = (bytes + 15) / 16;
+    if (need16 > b->d_pairs_up_cap) {
+        g_sa_pool.put(SaPool::DEVICE, b->d_pairs_up);
+        b->d_pairs_up = nullptr; b->d_pairs_up_cap = 0;
+        HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_pairs_up, sizeof(sa_pair16_t) * (size_t) need16, b->device));
+        b->d_pairs_up_cap = need16;
+    }
+    if (bytes) HIPCHK(hipMemcpy(b->d_pairs_up, b->h_pairs, (size_t) bytes, hipMemcpyHostToDevice));
+    *recs = b->d_pairs_up;
+    for (size_t j = 0; j < nj; j++) (*first)[j] = b->job_off[j];
+    return SA_OK;
+}
+
 int sa_batch_sites(sa_batch_t *b, SaSites **sites, int64_t *n_jobs) {
     if (!b || !sites || !n_jobs) return SA_EINVAL;
     if (!b->sites || !b->ran) return SA_ESTATE;

@@ -253,6 +253,9 @@ extern SaPool g_sa_pool;
 // of pairs, number of events)
 int sa_batch_device_view(sa_batch_t *b, const sa_pair16_t **pairs, std::vector<long long> *first, std::vector<long long> *count,
                          std::vector<long long> *n_events, int *device);
+// the same for a step that reads 16- and 8-byte records alike (*p8: which); SA_EINVAL for a SA_FLAG_VC_ROWS batch
+int sa_batch_device_records(sa_batch_t *b, const void **recs, bool *p8, std::vector<long long> *first, std::vector<long long> *count,
+                            int *device);
 
 // sa_calls.hip: the sites a SA_FLAG_SITE_CALLS batch records at creation (sa_sites_build), the device copy of their tables going
 // back with the batch's working storage (sa_sites_release_device) and everything with the batch (sa_sites_free)

@@ -1,0 +1,1081 @@
+// Gaussian k-mer emission training on gfx950 -- trainModels.train_normal_emmissions (src/signalalign/train/trainModels.py:735-828)
+// without the assignments files: generate_top_n_kmers_from_sa_output (build_alignments.py:76-275) keeps, per strand and path
+// k-mer, the N rows of largest printed posterior among those >= min_prob; the model's event means and SDs are then blended
+// with the statistics of those rows.  The rows are read where a finished batch left them in HBM; the kept ones stay in HBM
+// across batches (sa_kmer_table_t), and only per-k-mer statistics -- or the rows, when the table file is asked for -- come back.
+//
+// Selection key of a row: printed posterior (20 bits) << 40 | (2^40 - 1 - run ordinal).  Keys are unique, so "the N largest
+// keys of a k-mer" is the reference's top N with ties broken by run order, whatever order the rows arrive in.  It is found by
+// radix selection, 10 bits per level from the top: a level histograms the candidates of every k-mer that is not settled yet
+// and whose key matches the k-mer's prefix so far, and a cut picks the digit holding the N-th largest key.  Most k-mers settle
+// after one or two levels (the posterior alone); only k-mers with more rows tied at the cutoff posterior than they still need
+// go on to the run-order levels, which read a copy of those tied rows only.  Candidates are the table's rows (earlier batches)
+// and the new batch's records.  The histograms are global (n_kmers x 1024 counters): a block's records spread over all k-mers.
+//
+// Kernels:
+//   k_kt_hist_rows / k_kt_hist_rec<P8>   one thread per row / record: filter, key, one 32-bit integer atomic into
+//                                        hist[kmer * 1024 + digit] (16- or 8-byte records; the k-mer of an 8-byte record is the
+//                                        job's reference k-mer at x)
+//   k_kt_cut                             one wave per k-mer: suffix sums of its 1024 bins, the digit of the N-th largest key
+//   k_kt_tie_rows / k_kt_tie_rec<P8>     after the two posterior levels, only if some k-mer is still open: its rows at the cutoff
+//                                        posterior into one buffer, which the run-order levels then read instead of all candidates
+//   k_kt_scan                            one block of 1024 threads: exclusive scan of the kept counts into the new table's offsets
+//   k_kt_compact_rows / _rec<P8>         the rows at or above the k-mer's threshold into the k-mer's segment of the new table;
+//                                        for records the descaled mean is computed and rounded as "%f" prints it
+//   k_kt_stats                           one block per k-mer: exact integer sums (S, and Q in two words), radix selection (8 bits
+//                                        per pass) of the median and of the median absolute deviation
+// Within a k-mer's segment rows lie in arrival order; the keys are unique, so sa_kmer_table_rows sorts them on the host and
+// every statistic is independent of the order.  Scratch comes from the library's caching allocator.
+#include <hip/hip_runtime.h>
+
+#include <ctype.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "sa_internal.h"
+#include "sa_scratch.h"
+
+#define KT_CHUNK 4096                    // records per block of the record kernels
+#define KT_BINS 1024                     // 10 bits per selection level
+#define KT_RUN_BITS 40
+#define KT_RUN_MASK ((1ull << KT_RUN_BITS) - 1ull)
+#define KT_UNITS_LIMIT 2147483648.0      // descaled values beyond +-2^31 are refused (their "%f" is not computed here)
+#define KT_ERR_RANGE 1                   // err word bits
+#define KT_ERR_BOUNDS 2
+
+// "%f" of v as glibc prints it: the exact binary value rounded to six decimals, ties to even.  floor(v * 1e6) is found exactly
+// with the sign of one fma against an integer (exact in sign), the rounding with the sign against the half point.
+__host__ __device__ static inline int kt_f6_units(double v, long long *units, int *neg_zero) {
+    if (!(fabs(v) < KT_UNITS_LIMIT)) return SA_EUNSUPPORTED;
+    double f = floor(v * 1e6);
+    if (fma(v, 1e6, -f) < 0) f -= 1.0;
+    else if (fma(v, 1e6, -(f + 1.0)) >= 0) f += 1.0;
+    const double d = fma(v, 1e6, -(f + 0.5));
+    double r = f;
+    if (d > 0) r = f + 1.0;
+    else if (d == 0) r = fmod(f, 2.0) == 0 ? f : f + 1.0;
+    *units = (long long) r;
+    *neg_zero = (signbit(v) && *units == 0) ? 1 : 0;
+    return SA_OK;
+}
+
+struct KtRow {                  // a kept row in HBM (24 bytes)
+    unsigned long long key;
+    long long desc;             // descaled units
+    int kmer, neg_zero;
+};
+struct KtState {                // per k-mer selection state
+    unsigned long long prefix, thr;
+    long long need, keep;
+    int done, pad;
+};
+struct KtJob {                  // per job of a batch
+    long long ev_off, n_ev, x_off, n_x;
+    double scale, shift, var;
+};
+struct KtChunk {
+    long long first;            // first record of the chunk in the batch's device results
+    long long run0;             // run ordinal of that record
+    int n, job;
+};
+struct KtRecs {
+    const void *recs;
+    const KtChunk *chunks;
+    const KtJob *jobs;
+    const double *ev;           // event means of every job, dense
+    const int *xk;              // 8-byte records: k-mer id of every reference position of every job
+    const double *level;        // level mean per k-mer
+    long long min_units, n_kmers;
+};
+
+__device__ static inline bool kt_rec(const KtRecs &R, bool p8, const KtChunk &C, int i, int *kmer, unsigned long long *key, long long *y,
+                                     unsigned *err) {
+    long long pe7;
+    int x;
+    if (p8) {
+        const sa_pair8_t r = ((const sa_pair8_t *) R.recs)[C.first + i];
+        x = (int) (r & 0xfffffull);
+        *y = (long long) ((r >> 20) & 0xfffffull);
+        pe7 = (long long) (r >> 40);
+        const KtJob J = R.jobs[C.job];
+        if (x >= J.n_x) { atomicOr(err, KT_ERR_BOUNDS); return false; }
+        *kmer = R.xk[J.x_off + x];
+    } else {
+        const sa_pair16_t r = ((const sa_pair16_t *) R.recs)[C.first + i];
+        *y = (long long) ((r.a >> 28) & 0xfffffffull);
+        *kmer = (int) (unsigned) (r.b & 0xffffffffull);
+        pe7 = (long long) ((r.b >> 32) & 0xffffffull);
+    }
+    if (*kmer < 0 || *kmer >= R.n_kmers) { atomicOr(err, KT_ERR_BOUNDS); return false; }
+    const long long u = sa_printed_units(pe7);
+    if (u < R.min_units) return false;
+    *key = ((unsigned long long) u << KT_RUN_BITS) | (KT_RUN_MASK - (unsigned long long) (C.run0 + i));
+    return true;
+}
+
+__device__ static inline void kt_count(const KtState *st, unsigned *hist, int kmer, unsigned long long key, int shift) {
+    const KtState &s = st[kmer];
+    if (s.done) return;
+    if (shift < 50 && (key >> (shift + 10)) != s.prefix) return;
+    atomicAdd(&hist[(size_t) kmer * KT_BINS + ((key >> shift) & (KT_BINS - 1))], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_kt_hist_rows(const KtRow *__restrict__ rows, long long n, const KtState *__restrict__ st,
+                                                      unsigned *__restrict__ hist, int shift) {
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const KtRow r = rows[i];
+    kt_count(st, hist, r.kmer, r.key, shift);
+}
+
+template <bool P8>
+__global__ __launch_bounds__(256) void k_kt_hist_rec(KtRecs R, const KtState *__restrict__ st, unsigned *__restrict__ hist, int shift,
+                                                     unsigned *__restrict__ err) {
+    const KtChunk C = R.chunks[blockIdx.x];
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        int kmer;
+        unsigned long long key;
+        long long y;
+        if (kt_rec(R, P8, C, i, &kmer, &key, &y, err)) kt_count(st, hist, kmer, key, shift);
+    }
+}
+
+// k-mer blockIdx.x (one wave): lane l holds bins [16 l, 16 l + 16); suffix sums from the top bin down find the digit of the
+// need-th largest key.  Level 0 (shift 50) also settles every k-mer with at most N candidates (all of them are kept).
+__global__ __launch_bounds__(64) void k_kt_cut(KtState *__restrict__ st, const unsigned *__restrict__ hist, int shift,
+                                               unsigned *__restrict__ active, unsigned long long *__restrict__ tied) {
+    const long long km = blockIdx.x;
+    const int lane = threadIdx.x;
+    KtState s = st[km];
+    if (s.done) return;
+    const unsigned *h = hist + (size_t) km * KT_BINS + (size_t) lane * 16;
+    long long mine = 0;
+    for (int q = 0; q < 16; q++) mine += h[q];
+    long long incl = mine;   // sum over lanes >= lane
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_down(incl, o);
+        if (lane + o < 64) incl += u;
+    }
+    const long long total = __shfl(incl, 0);
+    if (shift == 50 && total <= s.need) {   // (s.need is N at level 0)
+        if (lane == 0) { s.done = 1; s.thr = 0; s.keep = total; st[km] = s; }
+        return;
+    }
+    if (shift == 50) s.keep = s.need;
+    const long long above = incl - mine;   // keys in bins of higher lanes
+    const bool mine_holds = above < s.need && incl >= s.need;
+    const unsigned long long owner = __ballot(mine_holds);
+    const int ol = owner ? (int) __ffsll((long long) owner) - 1 : -1;
+    if (lane != ol) {
+        if (lane == 0 && ol < 0) atomicAdd(active, 0x10000u);   // (cannot happen: the counts hold at least `need` keys)
+        return;
+    }
+    long long acc = above;
+    int digit = lane * 16 + 15;
+    for (; digit >= lane * 16; digit--) {
+        const long long c = h[digit - lane * 16];
+        if (acc + c >= s.need) break;
+        acc += c;
+    }
+    const long long c = h[digit - lane * 16];
+    s.need -= acc;
+    s.prefix = (s.prefix << 10) | (unsigned long long) digit;
+    if (c == s.need || shift == 0) {
+        s.done = 1;
+        s.thr = s.prefix << shift;
+    } else {
+        atomicAdd(active, 1u);
+        if (shift == 40) atomicAdd(tied, (unsigned long long) c);   // (the rows at the cutoff posterior: the run-order levels' input)
+    }
+    st[km] = s;
+}
+
+// The run-order levels read only the rows tied at the cutoff posterior of a k-mer still open after the two posterior levels:
+// these copy them (key and k-mer) into one buffer, in any order (the keys are unique).
+__device__ static inline void kt_tie(const KtState *st, int kmer, unsigned long long key, KtRow *tie, unsigned long long *n_tie,
+                                     unsigned long long cap, unsigned *err) {
+    const KtState &s = st[kmer];
+    if (s.done || (key >> 40) != s.prefix) return;
+    const unsigned long long slot = atomicAdd(n_tie, 1ull);
+    if (slot >= cap) { atomicOr(err, KT_ERR_BOUNDS); return; }
+    KtRow r;
+    r.key = key; r.desc = 0; r.kmer = kmer; r.neg_zero = 0;
+    tie[slot] = r;
+}
+__global__ __launch_bounds__(256) void k_kt_tie_rows(const KtRow *__restrict__ rows, long long n, const KtState *__restrict__ st,
+                                                     KtRow *__restrict__ tie, unsigned long long *__restrict__ n_tie, unsigned long long cap,
+                                                     unsigned *__restrict__ err) {
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) kt_tie(st, rows[i].kmer, rows[i].key, tie, n_tie, cap, err);
+}
+template <bool P8>
+__global__ __launch_bounds__(256) void k_kt_tie_rec(KtRecs R, const KtState *__restrict__ st, KtRow *__restrict__ tie,
+                                                    unsigned long long *__restrict__ n_tie, unsigned long long cap, unsigned *__restrict__ err) {
+    const KtChunk C = R.chunks[blockIdx.x];
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        int kmer;
+        unsigned long long key;
+        long long y;
+        if (kt_rec(R, P8, C, i, &kmer, &key, &y, err)) kt_tie(st, kmer, key, tie, n_tie, cap, err);
+    }
+}
+
+// exclusive scan of keep[0 .. n) into off[0 .. n] (k_site_scan's scheme: per-thread runs, wave scans, wave totals through LDS)
+#define KT_SCAN_THREADS 1024
+__global__ __launch_bounds__(KT_SCAN_THREADS) void k_kt_scan(const KtState *__restrict__ st, long long *__restrict__ off, long long n) {
+    __shared__ long long wave_tot[KT_SCAN_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const long long per = (n + KT_SCAN_THREADS - 1) / KT_SCAN_THREADS;
+    const long long a = min(n, (long long) t * per), e = min(n, a + per);
+    long long mine = 0;
+    for (long long i = a; i < e; i++) mine += st[i].keep;
+    long long incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) wave_tot[wv] = incl;
+    __syncthreads();
+    long long before = 0;
+    for (int q = 0; q < wv; q++) before += wave_tot[q];
+    long long run = before + incl - mine;
+    for (long long i = a; i < e; i++) { off[i] = run; run += st[i].keep; }
+    if (t == KT_SCAN_THREADS - 1) off[n] = before + incl;
+}
+
+__device__ static inline void kt_put(const KtState *st, const long long *off, unsigned long long *fill, KtRow *out, const KtRow &r,
+                                     unsigned *err) {
+    const KtState &s = st[r.kmer];
+    if (r.key < s.thr) return;
+    const long long slot = off[r.kmer] + (long long) atomicAdd(&fill[r.kmer], 1ull);
+    if (slot >= off[r.kmer + 1]) { atomicOr(err, KT_ERR_BOUNDS); return; }
+    out[slot] = r;
+}
+
+__global__ __launch_bounds__(256) void k_kt_compact_rows(const KtRow *__restrict__ rows, long long n, const KtState *__restrict__ st,
+                                                         const long long *__restrict__ off, unsigned long long *__restrict__ fill,
+                                                         KtRow *__restrict__ out, unsigned *__restrict__ err) {
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) kt_put(st, off, fill, out, rows[i], err);
+}
+
+template <bool P8>
+__global__ __launch_bounds__(256) void k_kt_compact_rec(KtRecs R, const KtState *__restrict__ st, const long long *__restrict__ off,
+                                                        unsigned long long *__restrict__ fill, KtRow *__restrict__ out,
+                                                        unsigned *__restrict__ err) {
+    const KtChunk C = R.chunks[blockIdx.x];
+    const KtJob J = R.jobs[C.job];
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        KtRow r;
+        long long y;
+        if (!kt_rec(R, P8, C, i, &r.kmer, &r.key, &y, err)) continue;
+        if (r.key < st[r.kmer].thr) continue;
+        if (y >= J.n_ev) { atomicOr(err, KT_ERR_BOUNDS); continue; }
+        const double e = R.ev[J.ev_off + y], level = R.level[r.kmer];
+        const double desc = (e + J.var * level - J.scale * level - J.shift) / J.var;   // signalMachine.c descale(); no contraction
+        if (kt_f6_units(desc, &r.desc, &r.neg_zero) != SA_OK) { atomicOr(err, KT_ERR_RANGE); continue; }
+        kt_put(st, off, fill, out, r, err);
+    }
+}
+
+struct KtRaw {                  // per k-mer result of k_kt_stats
+    long long n, S;
+    unsigned long long q_lo, q_hi;
+    long long med2;             // median in half units (sum of the two middle values)
+    unsigned long long mad4;    // MAD in quarter units (sum of the two middle |2 x - med2|)
+};
+
+// value of rank r (ascending) among f(0 .. n), unsigned 64-bit, 8 bits per pass; every thread of the block gets it
+template <class F>
+__device__ static unsigned long long kt_select(F f, long long n, long long r, unsigned *hist, unsigned long long *sh) {
+    unsigned long long prefix = 0;
+    for (int s = 56; s >= 0; s -= 8) {
+        for (int t = threadIdx.x; t < 256; t += blockDim.x) hist[t] = 0;
+        __syncthreads();
+        for (long long i = threadIdx.x; i < n; i += blockDim.x) {
+            const unsigned long long v = f(i);
+            if (s == 56 || (v >> (s + 8)) == prefix) atomicAdd(&hist[(v >> s) & 255], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            long long c = 0;
+            int d = 0;
+            for (; d < 255; d++) {
+                if (r < c + (long long) hist[d]) break;
+                c += hist[d];
+            }
+            sh[0] = (prefix << 8) | (unsigned long long) d;
+            sh[1] = (unsigned long long) (r - c);
+        }
+        __syncthreads();
+        prefix = sh[0];
+        r = (long long) sh[1];
+        __syncthreads();
+    }
+    return prefix;
+}
+
+#define KT_STATS_THREADS 256
+__global__ __launch_bounds__(KT_STATS_THREADS) void k_kt_stats(const KtRow *__restrict__ rows, const long long *__restrict__ off, int median,
+                                                               KtRaw *__restrict__ out) {
+    __shared__ long long s_S[KT_STATS_THREADS];
+    __shared__ unsigned long long s_lo[KT_STATS_THREADS], s_hi[KT_STATS_THREADS];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long sh[2];
+    const long long km = blockIdx.x, a = off[km], n = off[km + 1] - a;
+    const int t = threadIdx.x;
+    long long S = 0;
+    unsigned long long lo = 0, hi = 0;
+    for (long long i = t; i < n; i += KT_STATS_THREADS) {
+        const long long v = rows[a + i].desc;
+        S += v;
+        const unsigned long long u = (unsigned long long) (v < 0 ? -v : v), sq = u * u;   // |v| < 2^31: u^2 < 2^62
+        lo += sq;
+        hi += lo < sq ? 1ull : 0ull;
+    }
+    s_S[t] = S; s_lo[t] = lo; s_hi[t] = hi;
+    __syncthreads();
+    for (int w = KT_STATS_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            s_S[t] += s_S[t + w];
+            const unsigned long long l = s_lo[t] + s_lo[t + w];
+            s_hi[t] += s_hi[t + w] + (l < s_lo[t] ? 1ull : 0ull);
+            s_lo[t] = l;
+        }
+        __syncthreads();
+    }
+    KtRaw R;
+    R.n = n; R.S = s_S[0]; R.q_lo = s_lo[0]; R.q_hi = s_hi[0]; R.med2 = 0; R.mad4 = 0;
+    if (median && n > 0) {
+        const unsigned long long bias = 1ull << 63;
+        auto val = [&](long long i) { return (unsigned long long) rows[a + i].desc ^ bias; };
+        const long long lo_m = (long long) (kt_select(val, n, (n - 1) / 2, hist, sh) ^ bias);
+        const long long hi_m = (long long) (kt_select(val, n, n / 2, hist, sh) ^ bias);
+        const long long med2 = lo_m + hi_m;
+        auto dev = [&](long long i) {
+            const long long d = 2 * rows[a + i].desc - med2;
+            return (unsigned long long) (d < 0 ? -d : d);
+        };
+        R.med2 = med2;
+        R.mad4 = kt_select(dev, n, (n - 1) / 2, hist, sh) + kt_select(dev, n, n / 2, hist, sh);
+    }
+    if (t == 0) out[km] = R;
+}
+
+// ---- the table ---------------------------------------------------------------------------------------------------------------
+struct KtSide {
+    KtRow *d_rows = nullptr;          // n_rows rows, k-mer segments at off[]
+    long long n_rows = 0;
+    long long *d_off = nullptr;       // n_kmers + 1
+};
+struct sa_kmer_table {
+    int n_alpha = 0, k = 0, device = 0;
+    char alphabet[64] = {0};
+    long long n_kmers = 0, N = 0, min_units = 0;
+    unsigned long long run_next = 0;  // run ordinal of the next row
+    double *d_level = nullptr;
+    KtSide side[2];
+    // sa_kmer_table_checkpoint: the state to go back to; the arrays a side had then are kept (not returned to the pool) when the
+    // side first changes after the checkpoint
+    bool ck = false;
+    unsigned long long ck_run = 0;
+    KtSide ck_side[2];
+    bool ck_taken[2] = {false, false};
+    std::mutex mu;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+#define KTCHK(call)                                                                                         \
+    do {                                                                                                    \
+        hipError_t e_ = (call);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
+            goto done;                                                                                      \
+        }                                                                                                   \
+    } while (0)
+
+extern "C" int sa_kmer_table_create(sa_kmer_table_t **out, const sa_model_t *m, int64_t max_per_kmer, double min_prob, int device) {
+    if (!out || !m || max_per_kmer < 1 || !(min_prob >= 0.0 && min_prob <= 1.0)) return SA_EINVAL;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SA_ENODEVICE;
+    if (device < 0 || device >= ndev) return SA_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
+    sa_kmer_table *t = new (std::nothrow) sa_kmer_table();
+    if (!t) return SA_ENOMEM;
+    t->n_alpha = m->n_alpha; t->k = m->k; t->device = device;
+    memcpy(t->alphabet, m->alphabet, sizeof(t->alphabet));
+    t->n_kmers = m->n_kmers;
+    t->N = max_per_kmer;
+    // float(printed) >= min_prob: the smallest printed value that passes (the parse of "%f" is units / 1e6, correctly rounded)
+    long long u = 0;
+    while (u <= 1000000 && !((double) u / 1e6 >= min_prob)) u++;
+    t->min_units = u;
+    std::vector<double> level((size_t) t->n_kmers);
+    for (long long i = 0; i < t->n_kmers; i++) level[(size_t) i] = m->table5[5 * i];
+    int rc = SA_OK;
+    std::vector<long long> zero((size_t) t->n_kmers + 1, 0);
+    KTCHK(hipEventCreate(&t->e0));
+    KTCHK(hipEventCreate(&t->e1));
+    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_level, sizeof(double) * (size_t) t->n_kmers, device));
+    KTCHK(hipMemcpy(t->d_level, level.data(), sizeof(double) * (size_t) t->n_kmers, hipMemcpyHostToDevice));
+    for (int s = 0; s < 2; s++) {
+        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &t->side[s].d_off, sizeof(long long) * zero.size(), device));
+        KTCHK(hipMemcpy(t->side[s].d_off, zero.data(), sizeof(long long) * zero.size(), hipMemcpyHostToDevice));
+    }
+done:
+    if (rc != SA_OK) { sa_kmer_table_destroy(t); return rc; }
+    *out = t;
+    return SA_OK;
+}
+
+extern "C" void sa_kmer_table_destroy(sa_kmer_table_t *t) {
+    if (!t) return;
+    (void) hipSetDevice(t->device);
+    for (int s = 0; s < 2; s++) {
+        g_sa_pool.put(SaPool::DEVICE, t->side[s].d_rows);
+        g_sa_pool.put(SaPool::DEVICE, t->side[s].d_off);
+        if (t->ck_taken[s]) {
+            g_sa_pool.put(SaPool::DEVICE, t->ck_side[s].d_rows);
+            g_sa_pool.put(SaPool::DEVICE, t->ck_side[s].d_off);
+        }
+    }
+    g_sa_pool.put(SaPool::DEVICE, t->d_level);
+    if (t->e0) (void) hipEventDestroy(t->e0);
+    if (t->e1) (void) hipEventDestroy(t->e1);
+    delete t;
+}
+
+// The selection over the table's rows of `side` and a set of new candidates, and the new table.  `rec` (records of a batch,
+// nc chunks) or `rows` (n_new rows already in table form) are the new candidates.  Levels 1-2 (the posterior) histogram every
+// candidate; if a k-mer is still open then, its rows at the cutoff posterior are copied out once (k_kt_tie_*) and levels 3-6
+// (the run ordinal) histogram only that copy.  *kms_out: HIP-event time of the device work, summed over the stretches between
+// the host's reads of the level counters (the waits for those reads are not in it).
+static int kt_merge(sa_kmer_table *t, int side, const KtRecs *rec, bool p8, long long nc, const KtRow *new_rows, long long n_new,
+                    double *kms_out) {
+    KtSide &S = t->side[side];
+    const long long nk = t->n_kmers;
+    const int dev = t->device;
+    int rc = SA_OK;
+    char *d = nullptr;
+    KtRow *d_new = nullptr, *d_tie = nullptr;
+    long long *d_off_new = nullptr;
+    long long total = 0;
+    unsigned h_err = 0, h_active = 0;
+    unsigned long long h_tied = 0;
+    double kms = 0;
+    float seg = 0;
+    // scratch: [state | hist | off | fill | err, active | tied, n_tie]
+    const size_t o_st = 0, o_hist = sa_up256(sizeof(KtState) * (size_t) nk), o_off = sa_up256(o_hist + 4 * (size_t) nk * KT_BINS),
+                 o_fill = sa_up256(o_off + 8 * (size_t) (nk + 1)), o_err = sa_up256(o_fill + 8 * (size_t) nk), o_tied = o_err + 8,
+                 bytes = o_tied + 16;
+    std::vector<KtState> st0((size_t) nk);
+    for (KtState &q : st0) { q.prefix = 0; q.thr = 0; q.need = t->N; q.keep = 0; q.done = 0; q.pad = 0; }
+    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, dev));
+    {
+        KtState *st = (KtState *) (d + o_st);
+        unsigned *hist = (unsigned *) (d + o_hist), *err = (unsigned *) (d + o_err), *active = err + 1;
+        unsigned long long *tied = (unsigned long long *) (d + o_tied), *n_tie = tied + 1;
+        long long *off = (long long *) (d + o_off);
+        unsigned long long *fill = (unsigned long long *) (d + o_fill);
+        KTCHK(hipMemcpyAsync(st, st0.data(), sizeof(KtState) * (size_t) nk, hipMemcpyHostToDevice, 0));
+        KTCHK(hipMemsetAsync(err, 0, 8, 0));
+        KTCHK(hipMemsetAsync(tied, 0, 16, 0));
+        for (int shift = 50; shift >= 0; shift -= 10) {
+            KTCHK(hipEventRecord(t->e0, 0));
+            KTCHK(hipMemsetAsync(hist, 0, 4 * (size_t) nk * KT_BINS, 0));
+            KTCHK(hipMemsetAsync(active, 0, 4, 0));
+            if (shift >= 40) {   // the posterior levels: every candidate
+                if (S.n_rows)
+                    hipLaunchKernelGGL(k_kt_hist_rows, dim3((unsigned) ((S.n_rows + 255) / 256)), dim3(256), 0, 0, S.d_rows, S.n_rows, st, hist, shift);
+                if (n_new)
+                    hipLaunchKernelGGL(k_kt_hist_rows, dim3((unsigned) ((n_new + 255) / 256)), dim3(256), 0, 0, new_rows, n_new, st, hist, shift);
+                if (nc) {
+                    if (p8) hipLaunchKernelGGL(k_kt_hist_rec<true>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, hist, shift, err);
+                    else hipLaunchKernelGGL(k_kt_hist_rec<false>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, hist, shift, err);
+                }
+            } else if (h_tied) {   // the run-order levels: the tied rows only
+                hipLaunchKernelGGL(k_kt_hist_rows, dim3((unsigned) ((h_tied + 255) / 256)), dim3(256), 0, 0, d_tie, (long long) h_tied, st, hist, shift);
+            }
+            hipLaunchKernelGGL(k_kt_cut, dim3((unsigned) nk), dim3(64), 0, 0, st, hist, shift, active, tied);
+            KTCHK(hipEventRecord(t->e1, 0));
+            KTCHK(hipGetLastError());
+            KTCHK(hipMemcpy(&h_active, active, 4, hipMemcpyDeviceToHost));
+            KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+            kms += seg;
+            if (h_active >= 0x10000u) { rc = SA_ENODEVICE; goto done; }   // (a cut found fewer keys than it counted before)
+            if (h_active == 0) break;
+            if (shift == 40) {   // k-mers still open: copy their rows at the cutoff posterior out once
+                KTCHK(hipMemcpy(&h_tied, tied, 8, hipMemcpyDeviceToHost));
+                KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d_tie, sizeof(KtRow) * (size_t) (h_tied ? h_tied : 1), dev));
+                KTCHK(hipEventRecord(t->e0, 0));
+                if (S.n_rows)
+                    hipLaunchKernelGGL(k_kt_tie_rows, dim3((unsigned) ((S.n_rows + 255) / 256)), dim3(256), 0, 0, S.d_rows, S.n_rows, st, d_tie, n_tie, h_tied, err);
+                if (n_new)
+                    hipLaunchKernelGGL(k_kt_tie_rows, dim3((unsigned) ((n_new + 255) / 256)), dim3(256), 0, 0, new_rows, n_new, st, d_tie, n_tie, h_tied, err);
+                if (nc) {
+                    if (p8) hipLaunchKernelGGL(k_kt_tie_rec<true>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, d_tie, n_tie, h_tied, err);
+                    else hipLaunchKernelGGL(k_kt_tie_rec<false>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, d_tie, n_tie, h_tied, err);
+                }
+                KTCHK(hipEventRecord(t->e1, 0));
+                KTCHK(hipGetLastError());
+                KTCHK(hipEventSynchronize(t->e1));
+                KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+                kms += seg;
+            }
+        }
+        KTCHK(hipEventRecord(t->e0, 0));
+        hipLaunchKernelGGL(k_kt_scan, dim3(1), dim3(KT_SCAN_THREADS), 0, 0, st, off, nk);
+        KTCHK(hipEventRecord(t->e1, 0));
+        KTCHK(hipMemcpy(&total, off + nk, 8, hipMemcpyDeviceToHost));
+        KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+        kms += seg;
+        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d_new, sizeof(KtRow) * (size_t) (total > 0 ? total : 1), dev));
+        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d_off_new, 8 * (size_t) (nk + 1), dev));
+        KTCHK(hipEventRecord(t->e0, 0));
+        KTCHK(hipMemsetAsync(fill, 0, 8 * (size_t) nk, 0));
+        if (S.n_rows)
+            hipLaunchKernelGGL(k_kt_compact_rows, dim3((unsigned) ((S.n_rows + 255) / 256)), dim3(256), 0, 0, S.d_rows, S.n_rows, st, off, fill, d_new, err);
+        if (n_new)
+            hipLaunchKernelGGL(k_kt_compact_rows, dim3((unsigned) ((n_new + 255) / 256)), dim3(256), 0, 0, new_rows, n_new, st, off, fill, d_new, err);
+        if (nc) {
+            if (p8) hipLaunchKernelGGL(k_kt_compact_rec<true>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, off, fill, d_new, err);
+            else hipLaunchKernelGGL(k_kt_compact_rec<false>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, off, fill, d_new, err);
+        }
+        KTCHK(hipMemcpyAsync(d_off_new, off, 8 * (size_t) (nk + 1), hipMemcpyDeviceToDevice, 0));
+        KTCHK(hipEventRecord(t->e1, 0));
+        KTCHK(hipGetLastError());
+        KTCHK(hipMemcpy(&h_err, err, 4, hipMemcpyDeviceToHost));
+        KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+        kms += seg;
+        if (h_err & KT_ERR_BOUNDS) { rc = SA_EINVAL; goto done; }
+        if (h_err & KT_ERR_RANGE) { rc = SA_EUNSUPPORTED; goto done; }
+        if (t->ck && !t->ck_taken[side]) {   // the first change since the checkpoint: keep what the side had
+            t->ck_side[side] = S;
+            t->ck_taken[side] = true;
+        } else {
+            g_sa_pool.put(SaPool::DEVICE, S.d_rows);
+            g_sa_pool.put(SaPool::DEVICE, S.d_off);
+        }
+        S.d_rows = d_new;
+        S.d_off = d_off_new;
+        S.n_rows = total;
+        d_new = nullptr;
+        d_off_new = nullptr;
+        if (kms_out) *kms_out = kms;
+    }
+done:
+    if (rc != SA_OK) (void) hipDeviceSynchronize();
+    g_sa_pool.put(SaPool::DEVICE, d_new);
+    g_sa_pool.put(SaPool::DEVICE, d_off_new);
+    g_sa_pool.put(SaPool::DEVICE, d_tie);
+    g_sa_pool.put(SaPool::DEVICE, d);
+    return rc;
+}
+
+extern "C" int sa_kmer_table_checkpoint(sa_kmer_table_t *t) {
+    if (!t) return SA_EINVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    (void) hipSetDevice(t->device);
+    for (int s = 0; s < 2; s++)
+        if (t->ck_taken[s]) {
+            g_sa_pool.put(SaPool::DEVICE, t->ck_side[s].d_rows);
+            g_sa_pool.put(SaPool::DEVICE, t->ck_side[s].d_off);
+            t->ck_side[s] = KtSide();
+            t->ck_taken[s] = false;
+        }
+    t->ck = true;
+    t->ck_run = t->run_next;
+    return SA_OK;
+}
+
+extern "C" int sa_kmer_table_rollback(sa_kmer_table_t *t) {
+    if (!t) return SA_EINVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    if (!t->ck) return SA_ESTATE;
+    (void) hipSetDevice(t->device);
+    for (int s = 0; s < 2; s++)
+        if (t->ck_taken[s]) {
+            g_sa_pool.put(SaPool::DEVICE, t->side[s].d_rows);
+            g_sa_pool.put(SaPool::DEVICE, t->side[s].d_off);
+            t->side[s] = t->ck_side[s];
+            t->ck_side[s] = KtSide();
+            t->ck_taken[s] = false;
+        }
+    t->run_next = t->ck_run;
+    return SA_OK;
+}
+
+static int kt_kmer_ids(const sa_kmer_table *t, const char *ref, long long n_x, int *out) {
+    int digit[256];
+    for (int c = 0; c < 256; c++) digit[c] = -1;
+    for (int a = 0; a < t->n_alpha; a++) digit[(unsigned char) t->alphabet[a]] = a;
+    for (long long x = 0; x < n_x; x++) {
+        long long id = 0;
+        for (int i = 0; i < t->k; i++) {
+            const int dg = digit[(unsigned char) ref[x + i]];
+            if (dg < 0) return SA_EALPHABET;
+            id = id * t->n_alpha + dg;
+        }
+        out[x] = (int) id;
+    }
+    return SA_OK;
+}
+
+extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand,
+                                       double *kernel_ms_out) {
+    if (!t || !b || (n_jobs > 0 && !jobs) || n_jobs < 0 || (strand != 0 && strand != 1)) return SA_EINVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    const void *recs = nullptr;
+    bool p8 = false;
+    std::vector<long long> first, count;
+    int device = 0;
+    int rc = sa_batch_device_records(b, &recs, &p8, &first, &count, &device);
+    if (rc) return rc;
+    if ((int64_t) first.size() != n_jobs || device != t->device) return SA_EINVAL;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    const size_t nj = (size_t) n_jobs;
+    long long n_total = 0;
+    for (size_t j = 0; j < nj; j++) n_total += count[j];
+    if (t->run_next + (unsigned long long) n_total > KT_RUN_MASK) return SA_EUNSUPPORTED;
+    // per job: events (dense means) and, for 8-byte records, the k-mer id of every reference position
+    std::vector<KtJob> kj(nj);
+    long long n_ev = 0, n_x = 0;
+    for (size_t j = 0; j < nj; j++) {
+        const sa_job_t &J = jobs[j];
+        if (J.n_events < 0 || (J.n_events > 0 && (!J.events || J.event_stride < 1)) || !(J.var != 0)) return SA_EINVAL;
+        kj[j].ev_off = n_ev; kj[j].n_ev = J.n_events;
+        kj[j].scale = J.scale; kj[j].shift = J.shift; kj[j].var = J.var;
+        n_ev += J.n_events;
+        const long long lx = p8 ? std::max<long long>(0, J.ref_len - t->k + 1) : 0;
+        if (p8 && lx > 0 && !J.ref) return SA_EINVAL;
+        kj[j].x_off = n_x; kj[j].n_x = lx;
+        n_x += lx;
+    }
+    std::vector<KtChunk> chunks;
+    long long run = (long long) t->run_next;
+    for (size_t j = 0; j < nj; j++) {
+        for (long long c = 0; c < count[j]; c += KT_CHUNK)
+            chunks.push_back(KtChunk{first[j] + c, run + c, (int) std::min<long long>(KT_CHUNK, count[j] - c), (int) j});
+        run += count[j];
+    }
+    const long long nc = (long long) chunks.size();
+    // one pinned staging block and one device block: [jobs | chunks | events | k-mer ids]
+    const size_t o_jobs = 0, o_ch = sa_up256(sizeof(KtJob) * (nj ? nj : 1)), o_ev = sa_up256(o_ch + sizeof(KtChunk) * (size_t) (nc ? nc : 1)),
+                 o_xk = sa_up256(o_ev + 8 * (size_t) n_ev), bytes = o_xk + 4 * (size_t) n_x + 4;
+    char *h = nullptr, *d = nullptr;
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    if (g_sa_pool.get(SaPool::PINNED, (void **) &h, bytes, t->device) != hipSuccess) return SA_ENOMEM;
+    {
+        memcpy(h + o_jobs, kj.data(), sizeof(KtJob) * nj);
+        if (nc) memcpy(h + o_ch, chunks.data(), sizeof(KtChunk) * (size_t) nc);
+        double *ev = (double *) (h + o_ev);
+        int *xk = (int *) (h + o_xk);
+        std::vector<int> bad(nj, SA_OK);
+        sa_parallel_for(nj, [&](size_t j) {
+            const sa_job_t &J = jobs[j];
+            double *e = ev + kj[j].ev_off;
+            for (long long y = 0; y < J.n_events; y++) e[y] = J.events[y * J.event_stride];
+            if (p8) bad[j] = kt_kmer_ids(t, J.ref, kj[j].n_x, xk + kj[j].x_off);
+        });
+        for (size_t j = 0; j < nj; j++)
+            if (bad[j] != SA_OK) { rc = bad[j]; goto done; }
+        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, t->device));
+        KTCHK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+        KtRecs R;
+        R.recs = recs;
+        R.chunks = (const KtChunk *) (d + o_ch);
+        R.jobs = (const KtJob *) (d + o_jobs);
+        R.ev = (const double *) (d + o_ev);
+        R.xk = (const int *) (d + o_xk);
+        R.level = t->d_level;
+        R.min_units = t->min_units;
+        R.n_kmers = t->n_kmers;
+        rc = kt_merge(t, strand, &R, p8, nc, nullptr, 0, kernel_ms_out);
+        if (rc == SA_OK) t->run_next += (unsigned long long) n_total;
+    }
+done:
+    g_sa_pool.put(SaPool::DEVICE, d);
+    g_sa_pool.put(SaPool::PINNED, h);
+    return rc;
+}
+
+extern "C" int sa_kmer_table_add_rows(sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, const double *descaled, const double *prob,
+                                      int64_t n) {
+    if (!t || n < 0 || (n > 0 && (!kmer_ids || !descaled || !prob)) || (strand != 0 && strand != 1)) return SA_EINVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->run_next + (unsigned long long) n > KT_RUN_MASK) return SA_EUNSUPPORTED;
+    std::vector<KtRow> rows;
+    rows.reserve((size_t) n);
+    for (int64_t i = 0; i < n; i++) {
+        if (kmer_ids[i] < 0 || kmer_ids[i] >= t->n_kmers || !(prob[i] >= 0.0 && prob[i] <= 1.0)) return SA_EINVAL;
+        long long pu;
+        int nz;
+        if (kt_f6_units(prob[i], &pu, &nz) != SA_OK) return SA_EINVAL;
+        if (pu < t->min_units) continue;
+        KtRow r;
+        r.kmer = kmer_ids[i];
+        r.key = ((unsigned long long) pu << KT_RUN_BITS) | (KT_RUN_MASK - (t->run_next + (unsigned long long) i));
+        if (kt_f6_units(descaled[i], &r.desc, &r.neg_zero) != SA_OK) return SA_EUNSUPPORTED;
+        rows.push_back(r);
+    }
+    int rc = SA_OK;
+    KtRow *d = nullptr;
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, sizeof(KtRow) * (rows.size() ? rows.size() : 1), t->device));
+    if (!rows.empty()) KTCHK(hipMemcpy(d, rows.data(), sizeof(KtRow) * rows.size(), hipMemcpyHostToDevice));
+    rc = kt_merge(t, strand, nullptr, false, 0, d, (long long) rows.size(), nullptr);
+    if (rc == SA_OK) t->run_next += (unsigned long long) n;
+done:
+    g_sa_pool.put(SaPool::DEVICE, d);
+    return rc;
+}
+
+// the rows of a strand and their k-mer offsets, on the host, each k-mer's rows sorted by key (posterior, then run order)
+static int kt_fetch(const sa_kmer_table *t, int strand, std::vector<KtRow> *rows, std::vector<long long> *off) {
+    const KtSide &S = t->side[strand];
+    rows->resize((size_t) S.n_rows);
+    off->resize((size_t) t->n_kmers + 1);
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    if (S.n_rows && hipMemcpy(rows->data(), S.d_rows, sizeof(KtRow) * (size_t) S.n_rows, hipMemcpyDeviceToHost) != hipSuccess) return SA_ENODEVICE;
+    if (hipMemcpy(off->data(), S.d_off, 8 * off->size(), hipMemcpyDeviceToHost) != hipSuccess) return SA_ENODEVICE;
+    for (long long km = 0; km < t->n_kmers; km++)
+        std::sort(rows->begin() + (*off)[(size_t) km], rows->begin() + (*off)[(size_t) km + 1],
+                  [](const KtRow &a, const KtRow &b) { return a.key > b.key; });
+    return SA_OK;
+}
+
+extern "C" int sa_kmer_table_rows(const sa_kmer_table_t *t, int strand, sa_kmer_row_t **rows_out, int64_t *n_out) {
+    if (!t || !rows_out || !n_out || (strand != 0 && strand != 1)) return SA_EINVAL;
+    *rows_out = nullptr;
+    *n_out = 0;
+    std::lock_guard<std::mutex> g(const_cast<sa_kmer_table *>(t)->mu);
+    std::vector<KtRow> rows;
+    std::vector<long long> off;
+    int rc = kt_fetch(t, strand, &rows, &off);
+    if (rc) return rc;
+    sa_kmer_row_t *o = (sa_kmer_row_t *) calloc(rows.size() ? rows.size() : 1, sizeof(sa_kmer_row_t));
+    if (!o) return SA_ENOMEM;
+    for (size_t i = 0; i < rows.size(); i++) {
+        o[i].descaled_units = rows[i].desc;
+        o[i].run = (int64_t) (KT_RUN_MASK - (rows[i].key & KT_RUN_MASK));
+        o[i].kmer_id = rows[i].kmer;
+        o[i].prob_units = (int32_t) (rows[i].key >> KT_RUN_BITS);
+        o[i].neg_zero = rows[i].neg_zero;
+    }
+    *rows_out = o;
+    *n_out = (int64_t) rows.size();
+    return SA_OK;
+}
+
+static char *kt_put_units(char *w, long long u, int neg_zero) {   // "%f" of u / 1e6 as printf prints the double it came from
+    if (u < 0 || neg_zero) *w++ = '-';
+    unsigned long long a = (unsigned long long) (u < 0 ? -u : u);
+    char tmp[24];
+    int n = 0;
+    unsigned long long ip = a / 1000000ull;
+    do { tmp[n++] = (char) ('0' + ip % 10); ip /= 10; } while (ip);
+    while (n) *w++ = tmp[--n];
+    *w++ = '.';
+    unsigned long long fp = a % 1000000ull;
+    for (int q = 5; q >= 0; q--) { w[q] = (char) ('0' + fp % 10); fp /= 10; }
+    return w + 6;
+}
+
+extern "C" int sa_kmer_table_write(const sa_kmer_table_t *t, int strand, const char *path, int append) {
+    if (!t || !path || strand < -1 || strand > 1) return SA_EINVAL;
+    FILE *f = fopen(path, append ? "a" : "w");
+    if (!f) return SA_EIO;
+    std::lock_guard<std::mutex> g(const_cast<sa_kmer_table *>(t)->mu);
+    int rc = SA_OK;
+    std::vector<char> buf(128);
+    for (int s = 0; s < 2 && rc == SA_OK; s++) {
+        if (strand >= 0 && s != strand) continue;
+        std::vector<KtRow> rows;
+        std::vector<long long> off;
+        if ((rc = kt_fetch(t, s, &rows, &off)) != SA_OK) break;
+        for (const KtRow &r : rows) {
+            char *w = buf.data();
+            long long id = r.kmer;
+            for (int i = t->k - 1; i >= 0; i--) { w[i] = t->alphabet[id % t->n_alpha]; id /= t->n_alpha; }
+            w += t->k;
+            *w++ = '\t';
+            *w++ = s ? 'c' : 't';
+            *w++ = '\t';
+            w = kt_put_units(w, r.desc, r.neg_zero);
+            *w++ = '\t';
+            w = kt_put_units(w, (long long) (r.key >> KT_RUN_BITS), 0);
+            *w++ = '\n';
+            if (fwrite(buf.data(), 1, (size_t) (w - buf.data()), f) != (size_t) (w - buf.data())) { rc = SA_EIO; break; }
+        }
+    }
+    if (fclose(f) != 0 && rc == SA_OK) rc = SA_EIO;
+    return rc;
+}
+
+// the double nearest num / den (den > 0), by long division: 64 significant bits and a sticky bit, rounded to 53 bits, ties to even
+static double kt_ratio(unsigned __int128 num, unsigned __int128 den) {
+    if (num == 0) return 0.0;
+    unsigned __int128 q = num / den, r = num % den;
+    int e = 0;   // value = q * 2^-e + r / den * 2^-e
+    while (q < ((unsigned __int128) 1 << 64)) {   // (at least 65 significant bits in q)
+        q <<= 1;
+        r <<= 1;
+        if (r >= den) { q |= 1; r -= den; }
+        e++;
+    }
+    int nb = 0;
+    for (unsigned __int128 z = q; z; z >>= 1) nb++;
+    const int drop = nb - 53;
+    unsigned __int128 mant = q >> drop;
+    const unsigned __int128 rest = q & (((unsigned __int128) 1 << drop) - 1), half = (unsigned __int128) 1 << (drop - 1);
+    const bool sticky = r != 0;
+    if (rest > half || (rest == half && (sticky || (mant & 1)))) mant++;
+    return ldexp((double) (unsigned long long) mant, drop - e);
+}
+
+extern "C" int sa_kmer_table_stats(const sa_kmer_table_t *t, int strand, int use_median, sa_kmer_stat_t *out, double *kernel_ms_out) {
+    if (!t || !out || (strand != 0 && strand != 1)) return SA_EINVAL;
+    sa_kmer_table *T = const_cast<sa_kmer_table *>(t);
+    std::lock_guard<std::mutex> g(T->mu);
+    const long long nk = t->n_kmers;
+    std::vector<KtRaw> raw((size_t) nk);
+    int rc = SA_OK;
+    KtRaw *d = nullptr;
+    float kms = 0;
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, sizeof(KtRaw) * (size_t) nk, t->device));
+    KTCHK(hipEventRecord(T->e0, 0));
+    hipLaunchKernelGGL(k_kt_stats, dim3((unsigned) nk), dim3(KT_STATS_THREADS), 0, 0, t->side[strand].d_rows, t->side[strand].d_off,
+                       use_median ? 1 : 0, d);
+    KTCHK(hipEventRecord(T->e1, 0));
+    KTCHK(hipGetLastError());
+    KTCHK(hipMemcpy(raw.data(), d, sizeof(KtRaw) * (size_t) nk, hipMemcpyDeviceToHost));
+    KTCHK(hipEventElapsedTime(&kms, T->e0, T->e1));
+    if (kernel_ms_out) *kernel_ms_out = (double) kms;
+    for (long long km = 0; km < nk; km++) {
+        const KtRaw &R = raw[(size_t) km];
+        sa_kmer_stat_t &o = out[km];
+        o.n = R.n;
+        o.m = o.s = 0.0;
+        if (R.n == 0) continue;
+        if (use_median) {
+            o.m = (double) R.med2 / 2e6;
+            o.s = ((double) R.mad4 / 4e6) / 0.6744897501960817;
+        } else {
+            o.m = (double) R.S / ((double) R.n * 1e6);
+            const unsigned __int128 Q = ((unsigned __int128) R.q_hi << 64) | R.q_lo;
+            const unsigned __int128 aS = (unsigned __int128) (R.S < 0 ? -(__int128) R.S : (__int128) R.S);
+            const unsigned __int128 V = (unsigned __int128) R.n * Q - aS * aS;   // >= 0 (Cauchy-Schwarz)
+            const unsigned __int128 D = (unsigned __int128) R.n * (unsigned __int128) R.n * (unsigned __int128) 1000000000000ull;
+            o.s = sqrt(kt_ratio(V, D));
+        }
+    }
+done:
+    g_sa_pool.put(SaPool::DEVICE, d);
+    return rc;
+}
+
+// ---- host: Python's repr, the "%f" units, the model writer ----------------------------------------------------------------------
+extern "C" int sa_format_py_repr(char *out, double v) {
+    if (isnan(v)) return sprintf(out, "nan");
+    if (isinf(v)) return sprintf(out, v < 0 ? "-inf" : "inf");
+    if (v == 0) return sprintf(out, signbit(v) ? "-0.0" : "0.0");
+    // shortest digit string that reads back as v: the correctly rounded one of each length, or its neighbour in the last digit
+    // (near a power of two the round-trip interval is lopsided, and the nearest string of a length may miss it while the next
+    // one up or down does not)
+    char buf[64];
+    unsigned long long M = 0;
+    int E = 0, P = 0;
+    bool found = false;
+    for (int p = 0; p <= 16 && !found; p++) {
+        snprintf(buf, sizeof buf, "%.*e", p, fabs(v));
+        char *ep = strchr(buf, 'e');
+        const int ex = atoi(ep + 1);
+        unsigned long long m = 0;
+        for (char *c = buf; c < ep; c++)
+            if (*c >= '0' && *c <= '9') m = m * 10 + (unsigned long long) (*c - '0');
+        const unsigned long long cand[3] = {m, m - 1, m + 1};
+        for (int q = 0; q < 3 && !found; q++) {
+            if (cand[q] == 0) continue;
+            snprintf(buf, sizeof buf, "%llue%d", cand[q], ex - p);
+            if (strtod(buf, nullptr) == fabs(v)) { M = cand[q]; E = ex - p; P = p; found = true; }
+        }
+    }
+    if (!found) {   // (17 significant digits always read back)
+        snprintf(buf, sizeof buf, "%.16e", fabs(v));
+        char *ep = strchr(buf, 'e');
+        M = 0;
+        for (char *c = buf; c < ep; c++)
+            if (*c >= '0' && *c <= '9') M = M * 10 + (unsigned long long) (*c - '0');
+        E = atoi(ep + 1) - 16;
+    }
+    (void) P;
+    while (M % 10 == 0) { M /= 10; E++; }
+    char dg[24];
+    const int nd = snprintf(dg, sizeof dg, "%llu", M);
+    const int decpt = nd + E;   // value = 0.d1d2... * 10^decpt
+    char *w = out;
+    if (v < 0) *w++ = '-';
+    if (decpt > -4 && decpt <= 16) {   // float_repr_style 'short', format code 'r'
+        if (decpt <= 0) {
+            *w++ = '0'; *w++ = '.';
+            for (int i = 0; i < -decpt; i++) *w++ = '0';
+            memcpy(w, dg, (size_t) nd); w += nd;
+        } else if (decpt >= nd) {
+            memcpy(w, dg, (size_t) nd); w += nd;
+            for (int i = nd; i < decpt; i++) *w++ = '0';
+            *w++ = '.'; *w++ = '0';
+        } else {
+            memcpy(w, dg, (size_t) decpt); w += decpt;
+            *w++ = '.';
+            memcpy(w, dg + decpt, (size_t) (nd - decpt)); w += nd - decpt;
+        }
+    } else {
+        *w++ = dg[0];
+        if (nd > 1) { *w++ = '.'; memcpy(w, dg + 1, (size_t) (nd - 1)); w += nd - 1; }
+        const int x = decpt - 1;
+        w += sprintf(w, "e%c%02d", x < 0 ? '-' : '+', x < 0 ? -x : x);
+    }
+    *w = 0;
+    return (int) (w - out);
+}
+
+extern "C" int sa_f6_units(double v, int64_t *units_out, int32_t *neg_zero_out) {
+    long long u = 0;
+    int nz = 0;
+    const int rc = kt_f6_units(v, &u, &nz);
+    if (units_out) *units_out = u;
+    if (neg_zero_out) *neg_zero_out = nz;
+    return rc;
+}
+
+__global__ void k_kt_f6(const double *v, long long n, long long *u, int *nz, int *rc) {
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long a = 0;
+    int z = 0;
+    rc[i] = kt_f6_units(v[i], &a, &z);
+    u[i] = a;
+    nz[i] = z;
+}
+extern "C" int sa_f6_units_device(const double *v, int64_t n, int64_t *units_out, int32_t *neg_zero_out, int32_t *rc_out, int device) {
+    if (n < 0 || (n > 0 && (!v || !units_out || !neg_zero_out || !rc_out)) || n > (1ll << 31)) return SA_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SA_ENODEVICE;
+    if (device < 0 || device >= ndev) return SA_EINVAL;
+    if (n == 0) return SA_OK;
+    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
+    char *d = nullptr;
+    const size_t o_u = sa_up256(8 * (size_t) n), o_z = sa_up256(o_u + 8 * (size_t) n), o_r = sa_up256(o_z + 4 * (size_t) n);
+    if (hipMalloc((void **) &d, o_r + 4 * (size_t) n) != hipSuccess) return SA_ENOMEM;
+    int rc = SA_OK;
+    KTCHK(hipMemcpy(d, v, 8 * (size_t) n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_kt_f6, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, (const double *) d, (long long) n, (long long *) (d + o_u),
+                       (int *) (d + o_z), (int *) (d + o_r));
+    KTCHK(hipGetLastError());
+    KTCHK(hipMemcpy(units_out, d + o_u, 8 * (size_t) n, hipMemcpyDeviceToHost));
+    KTCHK(hipMemcpy(neg_zero_out, d + o_z, 4 * (size_t) n, hipMemcpyDeviceToHost));
+    KTCHK(hipMemcpy(rc_out, d + o_r, 4 * (size_t) n, hipMemcpyDeviceToHost));
+done:
+    (void) hipFree(d);
+    return rc;
+}
+
+static bool kt_read_line_tokens(FILE *f, std::vector<std::string> *tok) {
+    tok->clear();
+    std::string line;
+    int c;
+    while ((c = fgetc(f)) != EOF && c != '\n') line.push_back((char) c);
+    if (c == EOF && line.empty()) return false;
+    size_t i = 0;
+    while (i < line.size()) {
+        while (i < line.size() && isspace((unsigned char) line[i])) i++;
+        size_t j = i;
+        while (j < line.size() && !isspace((unsigned char) line[j])) j++;
+        if (j > i) tok->push_back(line.substr(i, j - i));
+        i = j;
+    }
+    return true;
+}
+
+static bool kt_parse(const std::string &s, double *v) {
+    char *end = nullptr;
+    *v = strtod(s.c_str(), &end);
+    return end && *end == 0 && !s.empty();
+}
+
+extern "C" int sa_model_write_trained(const char *prior_model_path, const sa_kmer_stat_t *stats, double weight, double min_sd, int mod_only,
+                                      const uint8_t *kmer_mask, const char *out_path) {
+    if (!prior_model_path || !stats || !out_path) return SA_EINVAL;
+    FILE *f = fopen(prior_model_path, "r");
+    if (!f) return SA_EIO;
+    std::vector<std::string> head, trans, params;
+    const bool ok = kt_read_line_tokens(f, &head) && kt_read_line_tokens(f, &trans) && kt_read_line_tokens(f, &params);
+    fclose(f);
+    if (!ok || head.size() != 4 || trans.size() != 10) return SA_EIO;
+    const int n_alpha = atoi(head[1].c_str()), k = atoi(head[3].c_str());
+    std::string alphabet = head[2];
+    if (n_alpha < 1 || k < 1 || (int) alphabet.size() != n_alpha) return SA_EIO;
+    long long nk = 1;
+    for (int i = 0; i < k; i++) nk *= n_alpha;
+    if ((long long) params.size() != 5 * nk) return SA_EIO;
+    std::vector<double> tv(10), pv((size_t) (5 * nk));
+    for (int i = 0; i < 10; i++)
+        if (!kt_parse(trans[(size_t) i], &tv[(size_t) i])) return SA_EIO;
+    for (size_t i = 0; i < pv.size(); i++)
+        if (!kt_parse(params[i], &pv[i])) return SA_EIO;
+    std::string sorted = alphabet;
+    std::sort(sorted.begin(), sorted.end());
+    for (long long km = 0; km < nk; km++) {
+        const sa_kmer_stat_t &S = stats[km];
+        if (S.n <= 0) continue;
+        if (kmer_mask && !kmer_mask[km]) continue;
+        if (mod_only) {   // k-mers made only of A, C, G, T keep their prior
+            bool canonical = true;
+            long long id = km;
+            for (int i = 0; i < k; i++) {
+                const char c = sorted[(size_t) (id % n_alpha)];
+                id /= n_alpha;
+                canonical = canonical && (c == 'A' || c == 'C' || c == 'G' || c == 'T');
+            }
+            if (canonical) continue;
+        }
+        const double n = (double) S.n;
+        const double mean0 = pv[(size_t) (5 * km)] * weight, sd0 = pv[(size_t) (5 * km + 1)] * weight;
+        const double mu = (S.m * n + mean0) / (n + weight);
+        const double sd = std::max((S.s * n + sd0) / (n + weight), min_sd);   // (np.max([a, min_sd]): a NaN would win; none occurs)
+        pv[(size_t) (5 * km)] = mu;
+        pv[(size_t) (5 * km + 1)] = sd;
+        // gaussian_param_to_inv_gaussian_param (hiddenMarkovModel.py:1149-1155): Python's ** is libm's pow, which the compiler would
+        // otherwise turn into sd * sd (pow is not correctly rounded: they differ in the last bit now and then)
+        volatile double three = 3.0, two = 2.0;
+        pv[(size_t) (5 * km + 4)] = pow(mu, (double) three) / pow(sd, (double) two);
+    }
+    FILE *o = fopen(out_path, "w");
+    if (!o) return SA_EIO;
+    char num[40];
+    fprintf(o, "3\t%d\t%s\t%d\n", n_alpha, alphabet.c_str(), k);
+    for (int i = 0; i < 9; i++) {
+        sa_format_py_repr(num, tv[(size_t) i]);
+        fprintf(o, "%s\t", num);
+    }
+    sa_format_py_repr(num, tv[9]);
+    fprintf(o, "%s\n", num);
+    for (size_t i = 0; i < pv.size(); i++) {
+        sa_format_py_repr(num, pv[i]);
+        fputs(num, o);
+        fputc('\t', o);
+    }
+    fputc('\n', o);
+    return fclose(o) == 0 ? SA_OK : SA_EIO;
+}

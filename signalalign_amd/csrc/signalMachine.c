@@ -70,7 +70,14 @@ static void usage(void) {
     fprintf(stderr, "--site-calls: also write <posteriors file>.calls, per read and ambiguous site the normalised probability of\n"
                     "                  each of its letters (variantCaller.py MarginalizeFullVariants)\n");
     fprintf(stderr, "--site-calls-aggregate <file>: write the per-site calls averaged over all reads of the run to <file>\n"
-                    "                  (AggregateOverReadsFull); a manifest's posteriors file may then be '-' (no TSV for that read)\n\n");
+                    "                  (AggregateOverReadsFull); a manifest's posteriors file may then be '-' (no TSV for that read)\n");
+    fprintf(stderr, "--train-assignments <file>: write the top-N assignments table of the run (buildAlignment: kmer, strand, descaled\n"
+                    "                  mean, posterior; what buildHdpUtil -l reads), selected on the GPU\n"
+                    "--train-template-model <file> / --train-complement-model <file>: write the -T / -C model with its Gaussian event\n"
+                    "                  means and SDs retrained on that table (trainModels.py train_normal_emmissions)\n"
+                    "--train-min-prob <p> (0.8), --train-max-assignments <n> (10), --train-weight <w> (100), --train-min-sd <s> (0),\n"
+                    "--train-median, --train-mod-only, --train-kmers <file> (one k-mer per line: only those are trained)\n"
+                    "                  with any --train-* output, a manifest's posteriors file may be '-' as well\n\n");
 }
 
 static double descale(double e, double level, double scale, double shift, double var) {
@@ -328,6 +335,12 @@ typedef struct {
     int mea; /* --mea: also write the maximum-expected-accuracy path of every read (not in the reference binary) */
     int site_calls;         /* --site-calls: also write <posteriors>.calls (not in the reference binary) */
     const char *agg_path;   /* --site-calls-aggregate: the over-reads table, written at the end of the run */
+    /* --train-*: the top-N assignments of the whole run in k-mer tables on the GPU (one per strand), written at the end */
+    const char *train_assign, *train_model[2], *train_kmers;
+    double train_min_prob, train_weight, train_min_sd;
+    int64_t train_n;
+    int train_median, train_mod_only;
+    sa_kmer_table_t *train_tab[2];
     int two_dist; /* --emission twoDist: the two-distribution emission (not an option of the reference binary: it is what its
                    * state machine carried when the reference's shipped output files were written); one read per process */
     int64_t out_fmt, constraint_trim;
@@ -1067,6 +1080,49 @@ static int64_t render_slice(render_job_t *job);
 
 /* GPU stage of a slice; returns the rendering job (NULL: nothing left to render -- the expectations mode writes its files
  * here -- with the number of failed reads in *n_failed_now) */
+/* --train-*: the assignments table (generate_top_n_kmers_from_sa_output) and the retrained models (train_normal_emmissions:
+ * the prior is the -T / -C file as written on disk) */
+static void write_training(run_t *R, const char *t_model, const char *c_model, int device) {
+    const int n_strands = R->two_d ? 2 : 1;
+    if (!(R->train_assign || R->train_model[0] || R->train_model[1])) return;
+    for (int s = 0; s < n_strands; s++)   /* (a run without a read that aligned: empty tables) */
+        if (!R->train_tab[s] && sa_kmer_table_create(&R->train_tab[s], (s ? &R->smc : &R->smt)->model, R->train_n, R->train_min_prob, device) != SA_OK)
+            die("signalMachine: --train-*: no k-mer table%s", "");
+    if (R->train_assign) {   /* the template table's 't' rows, then the complement table's 'c' rows */
+        for (int s = 0; s < n_strands; s++)
+            if (sa_kmer_table_write(R->train_tab[s], s, R->train_assign, s > 0) != SA_OK) die("signalMachine: cannot write %s", R->train_assign);
+    }
+    for (int s = 0; s < n_strands; s++) {
+        if (!R->train_model[s]) continue;
+        const strand_model_t *sm = s ? &R->smc : &R->smt;
+        int64_t nk = 1;
+        for (int i = 0; i < sm->k; i++) nk *= sm->n_alpha;
+        sa_kmer_stat_t *st = calloc((size_t) nk, sizeof(sa_kmer_stat_t));
+        uint8_t *mask = NULL;
+        if (R->train_kmers) {   /* load_training_kmers (trainModels.py:704-719): a duplicate line is an error */
+            FILE *f = fopen(R->train_kmers, "r");
+            if (!f) die("signalMachine: cannot read %s", R->train_kmers);
+            mask = calloc((size_t) nk, 1);
+            char line[256];
+            while (fgets(line, sizeof line, f)) {
+                line[strcspn(line, "\r\n")] = 0;
+                const int64_t id = (int64_t) strlen(line) == sm->k ? sa_kmer_id(sm->model, line) : -1;
+                if (id < 0 || id >= nk) continue;   /* (a k-mer outside the model never matches, as in the reference) */
+                if (mask[id]) die("signalMachine: --train-kmers: duplicate k-mer %s", line);
+                mask[id] = 1;
+            }
+            fclose(f);
+        }
+        if (!st || sa_kmer_table_stats(R->train_tab[s], s, R->train_median, st, NULL) != SA_OK)
+            die("signalMachine: --train-*: statistics failed%s", "");
+        if (sa_model_write_trained(s ? c_model : t_model, st, R->train_weight, R->train_min_sd, R->train_mod_only, mask, R->train_model[s]) != SA_OK)
+            die("signalMachine: cannot write %s", R->train_model[s]);
+        free(st);
+        free(mask);
+    }
+    for (int s = 0; s < 2; s++) { sa_kmer_table_destroy(R->train_tab[s]); R->train_tab[s] = NULL; }
+}
+
 static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int batch_mode, int device, int64_t *n_failed_now) {
 #define R (*Rp)
     *n_failed_now = 0;
@@ -1138,7 +1194,8 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
      * made of the rows SA_FLAG_VC_ROWS would drop; -s 1 then filters on the host, write_vc) */
     const int want_calls = R.site_calls || R.agg_path != NULL;
     const unsigned calls_flag = want_calls ? SA_FLAG_SITE_CALLS : 0u;
-    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !want_calls && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
+    const int want_train = R.train_assign || R.train_model[0] || R.train_model[1];
+    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !want_calls && !want_train && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
     sa_site_call_t **calls_s[2] = {NULL, NULL};
     int64_t *n_calls_s[2] = {NULL, NULL};
     /* -s 0 / -s 2 without --mea: 8-byte result records where the batch allows them (one path per cell: no ambiguity letter in any
@@ -1146,6 +1203,16 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
      * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker). */
     const unsigned p8_want = ((R.out_fmt == 0 || R.out_fmt == 2) && !R.mea && !want_calls && !getenv("SA_CLI_PAIRS16")) ? SA_FLAG_PAIRS8 : 0u;
     int p8_used[2] = {0, 0};
+    /* --train-*: each strand's rows go into the run's k-mer table right after its batch ran, while the records are still in HBM;
+     * the tables are checkpointed here, so that the retry below (a read the planner refuses) can take the slice's rows back */
+    for (int s = 0; s < n_strands && want_train; s++) {
+        int rc = R.train_tab[s] ? SA_OK : sa_kmer_table_create(&R.train_tab[s], sms[s]->model, R.train_n, R.train_min_prob, device);
+        if (rc == SA_OK) rc = sa_kmer_table_checkpoint(R.train_tab[s]);
+        if (rc != SA_OK) {
+            fprintf(stderr, "signalMachine: --train-*: %s\n", sa_strerror(rc));
+            exit(1);
+        }
+    }
     for (int s = 0; s < n_strands; s++) {
         pairs[s] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(sa_pair_t *));
         n_pairs[s] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(int64_t));
@@ -1166,6 +1233,13 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
                 rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, vc_flag);
             if (rc == SA_OK) rc = sa_batch_run(b);
             if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
+            if (rc == SA_OK && want_train) {
+                rc = sa_kmer_table_add_batch(R.train_tab[s], b, bj, n_ok, s, NULL);
+                if (rc != SA_OK) {   /* (a batch that ran: nothing a retry without some reads would change) */
+                    fprintf(stderr, "signalMachine: --train-*: %s\n", sa_strerror(rc));
+                    exit(1);
+                }
+            }
             for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) rc = sa_batch_n_pairs(b, j, &n_pairs[s][j]);
             if (vc_flag && rc == SA_OK) {
                 free(all_n[s]); free(all_sum[s]);
@@ -1205,6 +1279,8 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
             for (int64_t j = 0; j < n_ok; j++)
                 if (!reads[who[j]].failed) who[k2++] = who[j];
             if (k2 < n_ok) {
+                for (int q = 0; q < n_strands && want_train; q++)
+                    if (sa_kmer_table_rollback(R.train_tab[q]) != SA_OK) die("signalMachine: --train-*: rollback failed%s", "");
                 for (int q = 0; q <= s; q++) {
                     sa_batch_destroy(batches[q]);
                     batches[q] = NULL;
@@ -1308,6 +1384,9 @@ static void release_read(read_t *rd) {
 int main(int argc, char **argv) {
     run_t R;
     memset(&R, 0, sizeof(R));
+    R.train_min_prob = 0.8;   /* probability_threshold, number_of_kmer_assignments, og_model_weight (trainModels.py) */
+    R.train_n = 10;
+    R.train_weight = 100.0;
     int64_t diag_expansion = 50, trace_back = 50, batch_reads = 2048;
     double threshold = 0.01;
     int device = 0; /* --device: which GPU of the node (one process per GPU; reads shard across processes) */
@@ -1346,6 +1425,16 @@ int main(int argc, char **argv) {
                                            {"emission", required_argument, 0, 1004},
                                            {"site-calls", no_argument, 0, 1005},
                                            {"site-calls-aggregate", required_argument, 0, 1006},
+                                           {"train-assignments", required_argument, 0, 1010},
+                                           {"train-template-model", required_argument, 0, 1011},
+                                           {"train-complement-model", required_argument, 0, 1012},
+                                           {"train-min-prob", required_argument, 0, 1013},
+                                           {"train-max-assignments", required_argument, 0, 1014},
+                                           {"train-weight", required_argument, 0, 1015},
+                                           {"train-min-sd", required_argument, 0, 1016},
+                                           {"train-median", no_argument, 0, 1017},
+                                           {"train-mod-only", no_argument, 0, 1018},
+                                           {"train-kmers", required_argument, 0, 1019},
                                            {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -1381,6 +1470,16 @@ int main(int argc, char **argv) {
             case 1002: R.mea = 1; break;
             case 1005: R.site_calls = 1; break;
             case 1006: R.agg_path = strdup(optarg); break;
+            case 1010: R.train_assign = strdup(optarg); break;
+            case 1011: R.train_model[0] = strdup(optarg); break;
+            case 1012: R.train_model[1] = strdup(optarg); break;
+            case 1013: R.train_min_prob = atof(optarg); break;
+            case 1014: R.train_n = atoll(optarg); break;
+            case 1015: R.train_weight = atof(optarg); break;
+            case 1016: R.train_min_sd = atof(optarg); break;
+            case 1017: R.train_median = 1; break;
+            case 1018: R.train_mod_only = 1; break;
+            case 1019: R.train_kmers = strdup(optarg); break;
             case 1003: batch_reads = atoll(optarg) > 0 ? atoll(optarg) : batch_reads; break;
             case 1004:
                 if (!strcmp(optarg, "twoDist")) R.two_dist = 1;
@@ -1430,6 +1529,11 @@ int main(int argc, char **argv) {
         }
     }
 
+    if (R.train_assign || R.train_model[0] || R.train_model[1]) {
+        if (R.expect_mode || R.mea) die("signalMachine: --train-* needs the alignment mode without --mea%s", "");
+        if (R.train_model[1] && !R.two_d) die("signalMachine: --train-complement-model needs a 2-D run%s", "");
+        if (R.train_n < 1 || !(R.train_min_prob >= 0 && R.train_min_prob <= 1)) die("signalMachine: bad --train-max-assignments / --train-min-prob%s", "");
+    }
     if (R.expect_mode && (R.site_calls || R.agg_path)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate need the alignment mode, not -t/-c%s", ""); }
 
     R.p.threshold = threshold;
@@ -1491,6 +1595,7 @@ int main(int argc, char **argv) {
         if (started) pthread_join(th, NULL);
     }
     if (R.agg_path) write_aggregate(R.agg_path);
+    write_training(&R, t_model, c_model, device);
     if (batch_mode)
         fprintf(stderr, "[signalMachine] batch: %" PRId64 " of %" PRId64 " reads aligned\n", n_reads - n_failed, n_reads);
     if (getenv("SA_CLI_TIMING"))
