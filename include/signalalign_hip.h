@@ -567,6 +567,53 @@ typedef struct sa_site_call {
  * Deterministic: the sums are integer atomics. */
 int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out);
 
+/* ---- Per-position marginals: single-nucleotide probabilities ------------------------------------------------------------
+ * Replaces CallMethylation.call_methyls (src/signalalign/scripts/alignmentAnalysisLib.py:159-247) over one full TSV per job, in
+ * target coordinates, chained onto a finished batch like sa_batch_site_calls.
+ *   position  an index p of the job's `ref` that holds an ambiguity letter of the batch's map
+ *   rows      every record with x <= p <= x + k - 1; its letter is digit p - x of its path k-mer (kmer_id, first letter most
+ *             significant: the path k-mer as the TSV prints it)
+ *   sum       per letter, the printed posterior of those rows ("%f" of prob_e7 / 1e7 read back as a double, i.e. units / 1e6)
+ *             added serially in row order (sa_batch_pairs order, the TSV's), starting from 0
+ *   prob      sum[l] / total, total = ((0 + sum[0]) + sum[1]) + ... over the sorted letters -- the reference's bits
+ * One record per (job, position with at least one row), in ascending p.  x_min_out / x_max_out (n_jobs entries each, may be
+ * NULL): the smallest and largest x of the job's records, -1 for a job without records.
+ * SA_FLAG_POSITION_CALLS at sa_batch_create / _deferred: the batch records its ambiguous positions (one host pass over each
+ * reference).  With SA_FLAG_VC_ROWS: SA_EINVAL; with SA_FLAG_PAIRS8, or an ambiguity letter with more than SA_SITE_MAX_LETTERS
+ * distinct options: SA_EUNSUPPORTED (both at creation).  The call: SA_ESTATE when created without the flag or not run.  Works
+ * after sa_batch_release_device and with SA_FLAG_EXACT (the records go up again).  Deterministic: counts and bucket slots are
+ * integer atomics, every bucket is put in row order before it is folded. */
+#define SA_FLAG_POSITION_CALLS 256u
+typedef struct sa_position_call {
+    int32_t p, n_rows, n_letters, pad;     /* position in the job's ref, covering rows, number of letters             */
+    char letters[SA_SITE_MAX_LETTERS];     /* sorted; not terminated when there are 8                                  */
+    double sum[SA_SITE_MAX_LETTERS];       /* printed posterior summed per letter, in row order                       */
+    double prob[SA_SITE_MAX_LETTERS];      /* sum[l] / total                                                          */
+} sa_position_call_t;
+int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out, int32_t *x_min_out,
+                            int32_t *x_max_out, double *kernel_ms_out);
+
+/* ---- host helpers of signalMachine --snp-step (singleNucleotideProbabilities.py:551-723) -------------------------------
+ * sa_snp_substitute: the window of replace_periodic_sequence_positions (utils/sequenceTools.py:207-254).  ref[i] lies at contig
+ * coordinate c0 + i, or c0 - i when `reversed`; out[i] = `letter` where that coordinate is = phase (mod step), else ref[i] in
+ * upper case.  `out` needs len + 1 bytes (terminated).  step < 1 or phase outside [0, step): SA_EINVAL. */
+int sa_snp_substitute(const char *ref, int64_t len, int64_t contig_pos_of_ref0, int reversed, int64_t step, int64_t phase,
+                      char letter, char *out);
+/* the sites of call_methyls with a step offset: [*lo_out, *hi_out) with lo = (min_ref_index - step) floored to a multiple of
+ * step and hi = (max_ref_index + step) raised to one; the sites of phase s are lo + s, lo + s + step, ... below hi */
+int sa_snp_site_window(int64_t min_ref_index, int64_t max_ref_index, int64_t step, int64_t *lo_out, int64_t *hi_out);
+/* one line of a marginals file: position (the TSV's reference_index), strand 0 't' / 1 'c', the probabilities of A, C, G, T */
+typedef struct sa_snp_site {
+    int64_t pos;
+    int32_t strand, pad;
+    double p[4];
+} sa_snp_site_t;
+/* <read_id>.tsv as discover_single_nucleotide_probabilities writes it (singleNucleotideProbabilities.py:655-718): the header
+ * (contig empty when n == 0; strand "complement" when `backward`), then the lines sorted stably by position, the probabilities
+ * as Python's str(float), in T G C A order when `backward`.  `sites` holds the step files' lines one file after the other. */
+int sa_snp_write_read(const char *path, const char *fast5_input, const char *read_id, const char *contig, int backward,
+                      const sa_snp_site_t *sites, int64_t n);
+
 /* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
  * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
  * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output

@@ -16,6 +16,7 @@ FLAG_INPUTS_IN_HOST_BLOCK = 16
 FLAG_VC_ROWS = 32
 FLAG_PAIRS8 = 64
 FLAG_SITE_CALLS = 128
+FLAG_POSITION_CALLS = 256
 SITE_MAX_LETTERS = 8
 
 
@@ -51,6 +52,18 @@ class SiteCall(C.Structure):
     """sa_site_call_t (include/signalalign_hip.h)"""
     _fields_ = [("x", C.c_int32), ("n_letters", C.c_int32), ("letters", C.c_char * SITE_MAX_LETTERS),
                 ("units", C.c_int64 * SITE_MAX_LETTERS), ("prob", C.c_double * SITE_MAX_LETTERS)]
+
+
+class PositionCall(C.Structure):
+    """sa_position_call_t (include/signalalign_hip.h)"""
+    _fields_ = [("p", C.c_int32), ("n_rows", C.c_int32), ("n_letters", C.c_int32), ("pad", C.c_int32),
+                ("letters", C.c_char * SITE_MAX_LETTERS), ("sum", C.c_double * SITE_MAX_LETTERS),
+                ("prob", C.c_double * SITE_MAX_LETTERS)]
+
+
+class SnpSite(C.Structure):
+    """sa_snp_site_t (include/signalalign_hip.h)"""
+    _fields_ = [("pos", C.c_int64), ("strand", C.c_int32), ("pad", C.c_int32), ("p", C.c_double * 4)]
 
 
 class Pair(C.Structure):
@@ -107,6 +120,9 @@ class PlanInfo(C.Structure):
 
 
 PAIR_DTYPE = np.dtype([("prob_e7", "<i8"), ("x", "<i4"), ("y", "<i4"), ("path", "<i4"), ("kmer_id", "<i4")])
+POSITION_CALL_DTYPE = np.dtype([("p", "<i4"), ("n_rows", "<i4"), ("n_letters", "<i4"), ("pad", "<i4"),
+                                ("letters", "S1", (SITE_MAX_LETTERS,)), ("sum", "<f8", (SITE_MAX_LETTERS,)),
+                                ("prob", "<f8", (SITE_MAX_LETTERS,))])
 SITE_CALL_DTYPE = np.dtype([("x", "<i4"), ("n_letters", "<i4"), ("letters", "S1", (SITE_MAX_LETTERS,)),
                             ("units", "<i8", (SITE_MAX_LETTERS,)), ("prob", "<f8", (SITE_MAX_LETTERS,))])
 
@@ -115,7 +131,7 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_batch_create", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
            "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
            "sa_plan_check_path_records", "sa_dplan_compare",
-           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
+           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
@@ -260,6 +276,10 @@ def lib():
     L.sa_batch_mea.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, dp]
     L.sa_batch_site_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(SiteCall)), ip, dp]
     L.sa_format_py_round6.argtypes = [C.c_char_p, C.c_double]
+    L.sa_batch_position_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(PositionCall)), ip, i32p, i32p, dp]
+    L.sa_snp_substitute.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_char, C.c_char_p]
+    L.sa_snp_site_window.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip]
+    L.sa_snp_write_read.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(SnpSite), C.c_int64]
     L.sa_kmer_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_double, C.c_int]
     L.sa_kmer_table_destroy.argtypes = [C.c_void_p]
     L.sa_kmer_table_destroy.restype = None
@@ -648,6 +668,36 @@ class Batch:
             lib().sa_free(ptrs[i])
             letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
             out.append({"x": rec["x"].copy(), "letters": letters, "units": rec["units"].copy(), "prob": rec["prob"].copy()})
+        return out
+
+    def position_calls(self, stats=None):
+        """sa_batch_position_calls (a batch created with FLAG_POSITION_CALLS, after run()): per job a dict -- p [n] (ambiguous
+        position in the job's ref), n_rows [n], letters [n] (sorted, as a str), sum [n, 8] (printed posterior summed per letter in
+        row order), prob [n, 8] (sum / total); columns past a position's letter count are 0 -- and x_min, x_max (the smallest and
+        largest x of the job's records, -1 without records)."""
+        n = self.n_jobs
+        ptrs = (C.POINTER(PositionCall) * max(n, 1))()
+        cnt = np.zeros(max(n, 1), dtype=np.int64)
+        xmin = np.zeros(max(n, 1), dtype=np.int32)
+        xmax = np.zeros(max(n, 1), dtype=np.int32)
+        kms = C.c_double()
+        i32 = C.POINTER(C.c_int32)
+        t0 = time.perf_counter()
+        _chk(lib().sa_batch_position_calls(self._h, 0, ptrs, _ip(cnt), xmin.ctypes.data_as(i32), xmax.ctypes.data_as(i32),
+                                           C.byref(kms)), "sa_batch_position_calls")
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+            stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+        out = []
+        for i in range(n):
+            m = int(cnt[i])
+            rec = np.zeros(m, dtype=POSITION_CALL_DTYPE)
+            if m:
+                C.memmove(rec.ctypes.data, ptrs[i], C.sizeof(PositionCall) * m)
+            lib().sa_free(ptrs[i])
+            letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
+            out.append({"p": rec["p"].copy(), "n_rows": rec["n_rows"].copy(), "letters": letters, "sum": rec["sum"].copy(),
+                        "prob": rec["prob"].copy(), "x_min": int(xmin[i]), "x_max": int(xmax[i])})
         return out
 
     def stats(self):
@@ -1334,6 +1384,34 @@ def model_write_trained(prior_path, stats, out_path, weight=100.0, min_sd=0.0, m
     mask = None if kmer_mask is None else np.ascontiguousarray(kmer_mask, dtype=np.uint8)
     _chk(lib().sa_model_write_trained(os.fsencode(prior_path), st.ctypes.data, float(weight), float(min_sd), int(bool(mod_only)),
                                       None if mask is None else mask.ctypes.data, os.fsencode(out_path)), "sa_model_write_trained")
+
+
+def snp_substitute(ref, contig_pos_of_ref0, reversed=False, step=10, phase=0, letter="X"):
+    """sa_snp_substitute: `letter` at the window's positions whose contig coordinate is = phase (mod step), the rest upper-cased"""
+    b = ref.encode() if isinstance(ref, str) else bytes(ref)
+    out = C.create_string_buffer(len(b) + 1)
+    _chk(lib().sa_snp_substitute(b, len(b), int(contig_pos_of_ref0), 1 if reversed else 0, int(step), int(phase),
+                                 letter.encode()[:1], out), "sa_snp_substitute")
+    return out.raw[:len(b)].decode()
+
+
+def snp_site_window(min_ref_index, max_ref_index, step):
+    """sa_snp_site_window: (lo, hi) of the sites call_methyls visits with a step offset"""
+    lo, hi = C.c_int64(), C.c_int64()
+    _chk(lib().sa_snp_site_window(int(min_ref_index), int(max_ref_index), int(step), C.byref(lo), C.byref(hi)), "sa_snp_site_window")
+    return int(lo.value), int(hi.value)
+
+
+def snp_write_read(path, fast5_input, read_id, contig, backward, sites):
+    """sa_snp_write_read: `sites` an iterable of (pos, strand 0/1, (pA, pC, pG, pT)), the step files' lines in file order"""
+    sites = list(sites)
+    arr = (SnpSite * max(len(sites), 1))()
+    for i, (pos, strand, p) in enumerate(sites):
+        arr[i].pos, arr[i].strand = int(pos), int(strand)
+        for q in range(4):
+            arr[i].p[q] = float(p[q])
+    _chk(lib().sa_snp_write_read(path.encode(), fast5_input.encode(), read_id.encode(), contig.encode(), 1 if backward else 0,
+                                 arr, len(sites)), "sa_snp_write_read")
 
 
 def format_py_repr(v):

@@ -18,6 +18,7 @@
 //   k_site_compact  one wave per job: the kept sites written, in x order, to the job's place in the compact output
 #include <hip/hip_runtime.h>
 
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,14 +35,16 @@
 
 #define SITE_CHUNK 4096   // records per block of k_site_accum
 
+// The table of a batch's ambiguity letters, shared by the site calls and the position calls.  Index i of job j names the letter
+// ref[i + tail]: tail k - 1 for the sites (k-mer indices, the k-mer's last letter), 0 for the positions (reference positions).
 struct SaSites {
     int n_alpha = 0, k = 0, stride = 0;                // stride: most letters of any kind in the batch
     long long n_sites = 0;
     std::vector<long long> site_off;                   // n_jobs + 1: job j's sites are [site_off[j], site_off[j + 1])
     std::vector<long long> word_off;                   // n_jobs + 1: job j's bitmap words
-    std::vector<unsigned long long> bits;              // bit x of job j: x is a site
+    std::vector<unsigned long long> bits;              // bit i of job j: i is a site
     std::vector<int> pre;                              // per word: global index of the first site at or after its first bit
-    std::vector<int> x;                                // per site
+    std::vector<int> x;                                // per site: its index i
     std::vector<unsigned char> kind;                   // per site
     std::vector<std::string> letters;                  // per kind: distinct options, sorted
     std::vector<signed char> slot;                     // kind * n_alpha + digit: index into letters[kind], -1 none
@@ -50,11 +53,9 @@ struct SaSites {
     int device = -1;
     size_t o_pre = 0, o_woff = 0, o_soff = 0, o_kind = 0, o_nl = 0, o_slot = 0;
 };
+struct SaPositions : SaSites {};
 
-int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaSites **out) {
-    *out = nullptr;
-    SaSites *S = new (std::nothrow) SaSites();
-    if (!S) return SA_ENOMEM;
+static int ambig_tab_build(SaSites *S, const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, int tail) {
     S->n_alpha = m->n_alpha;
     S->k = m->k;
     int kind_of[256];
@@ -62,26 +63,25 @@ int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, co
     S->site_off.assign((size_t) n_jobs + 1, 0);
     S->word_off.assign((size_t) n_jobs + 1, 0);
     for (int64_t j = 0; j < n_jobs; j++) {
-        const long long lx = jobs[j].ref_len - S->k + 1;
+        const long long lx = jobs[j].ref_len - tail;
         S->word_off[(size_t) j + 1] = S->word_off[(size_t) j] + (lx > 0 ? (lx + 63) / 64 : 0);
     }
     S->bits.assign((size_t) S->word_off[(size_t) n_jobs], 0ull);
     S->pre.assign(S->bits.size(), 0);
-    int rc = SA_OK;
-    for (int64_t j = 0; j < n_jobs && rc == SA_OK; j++) {
+    for (int64_t j = 0; j < n_jobs; j++) {
         const char *ref = jobs[j].ref;
-        const long long lx = jobs[j].ref_len - S->k + 1;
+        const long long lx = jobs[j].ref_len - tail;
         const long long w0 = S->word_off[(size_t) j];
         for (long long x = 0; x < lx; x++) {
             if ((x & 63) == 0) S->pre[(size_t) (w0 + (x >> 6))] = (int) S->x.size();
-            const unsigned char c = (unsigned char) ref[x + S->k - 1];
+            const unsigned char c = (unsigned char) ref[x + tail];
             const char *opts = ambig ? ambig[c] : nullptr;
             if (!opts) continue;
             if (kind_of[c] < 0) {
                 std::string l(opts);
                 std::sort(l.begin(), l.end());
                 l.erase(std::unique(l.begin(), l.end()), l.end());
-                if (l.size() > SA_SITE_MAX_LETTERS || S->letters.size() >= 256) { rc = SA_EUNSUPPORTED; break; }
+                if (l.size() > SA_SITE_MAX_LETTERS || S->letters.size() >= 256) return SA_EUNSUPPORTED;
                 kind_of[c] = (int) S->letters.size();
                 S->letters.push_back(l);
                 S->stride = std::max(S->stride, (int) l.size());
@@ -89,17 +89,25 @@ int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, co
             S->bits[(size_t) (w0 + (x >> 6))] |= 1ull << (x & 63);
             S->x.push_back((int) x);
             S->kind.push_back((unsigned char) kind_of[c]);
-            if (S->x.size() >= (size_t) INT32_MAX) { rc = SA_EUNSUPPORTED; break; }
+            if (S->x.size() >= (size_t) INT32_MAX) return SA_EUNSUPPORTED;
         }
         S->site_off[(size_t) j + 1] = (long long) S->x.size();
     }
-    if (rc != SA_OK) { delete S; return rc; }
     S->n_sites = (long long) S->x.size();
     S->slot.assign(S->letters.size() * (size_t) S->n_alpha, (signed char) -1);
     for (size_t kd = 0; kd < S->letters.size(); kd++)
         for (size_t i = 0; i < S->letters[kd].size(); i++)
             for (int a = 0; a < S->n_alpha; a++)
                 if (m->alphabet[a] == S->letters[kd][i]) S->slot[kd * (size_t) S->n_alpha + (size_t) a] = (signed char) i;
+    return SA_OK;
+}
+
+int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaSites **out) {
+    *out = nullptr;
+    SaSites *S = new (std::nothrow) SaSites();
+    if (!S) return SA_ENOMEM;
+    const int rc = ambig_tab_build(S, m, jobs, n_jobs, ambig, m->k - 1);
+    if (rc != SA_OK) { delete S; return rc; }
     *out = S;
     return SA_OK;
 }
@@ -123,7 +131,7 @@ struct SiteTabs {
     const unsigned char *kind;
     const int *nl;            // per kind: number of letters
     const signed char *slot;
-    int n_alpha, stride;
+    int n_alpha, k, stride;
 };
 static SiteTabs sites_tabs(const SaSites *S) {
     SiteTabs T;
@@ -135,6 +143,7 @@ static SiteTabs sites_tabs(const SaSites *S) {
     T.nl = (const int *) (S->d + S->o_nl);
     T.slot = (const signed char *) (S->d + S->o_slot);
     T.n_alpha = S->n_alpha;
+    T.k = S->k;
     T.stride = S->stride;
     return T;
 }
@@ -383,6 +392,343 @@ done:
     if (rc != SA_OK && d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
     if (d) g_sa_pool.put(SaPool::DEVICE, d);   // (every kernel and copy of the call has completed: synchronous copies above)
     if (h) g_sa_pool.put(SaPool::PINNED, h);
+    if (rc != SA_OK)
+        for (size_t j = 0; j < nj; j++) { free(calls_out[j]); calls_out[j] = nullptr; n_out[j] = 0; }
+    return rc;
+}
+
+// ---- Per-position marginals (sa_batch_position_calls): CallMethylation.call_methyls (alignmentAnalysisLib.py:159-247) ----
+// A position is an index p of a job's reference that holds an ambiguity letter; every record with x <= p <= x + k - 1 adds its
+// printed posterior to the letter that its path k-mer has at p.  The reference adds floating-point values serially in TSV row
+// order, so the sums are made in that order: the rows of each position are gathered into a bucket, the bucket is put in row
+// order and folded by one lane.
+//
+// Tables (built at sa_batch_create with SA_FLAG_POSITION_CALLS): the sites' tables (ambig_tab_build) with tail 0, i.e. one bit
+// per reference position of every job, set at an ambiguous one; a "site" of that table is a position, its slot below.
+//
+// Kernels:
+//   k_pos_count     one thread per record: x_min / x_max of the job (wave reduction, one integer atomic per wave); per covered
+//                   ambiguous position one integer atomic increment of the slot's row count
+//   k_pos_job_scan  one wave per job: exclusive scan of its slots' counts (bucket offsets inside the job), the job's total
+//   k_site_scan     the jobs' totals into the jobs' bucket bases
+//   k_pos_scatter   one thread per record: per covered ambiguous position one 8-byte entry (row ordinal << 24 | letter << 20 |
+//                   printed units) at the slot's next free place (integer atomic)
+//   k_pos_fold      one lane per slot: insertion sort of its bucket (the keys are unique: a record has one entry per slot), the
+//                   serial fold, total and probabilities; per job the number of non-empty slots
+//   k_site_scan     those counts into output offsets
+//   k_pos_compact   one wave per job: the non-empty slots in position order
+#define POS_MAX_K 32
+
+int sa_positions_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaPositions **out) {
+    *out = nullptr;
+    if (m->k > POS_MAX_K) return SA_EUNSUPPORTED;
+    SaPositions *P = new (std::nothrow) SaPositions();
+    if (!P) return SA_ENOMEM;
+    const int rc = ambig_tab_build(P, m, jobs, n_jobs, ambig, 0);
+    if (rc != SA_OK) { delete P; return rc; }
+    *out = P;
+    return SA_OK;
+}
+
+void sa_positions_release_device(SaPositions *s) { sa_sites_release_device(s); }
+void sa_positions_free(SaPositions *s) {
+    sa_sites_release_device(s);
+    delete s;
+}
+
+struct PosChunk {
+    long long first;   // first record of the chunk in the batch's device results
+    long long local;   // its ordinal inside the job
+    int n, job;
+};
+
+// the digits of kmer_id, first letter first
+__device__ static inline void pos_digits(unsigned id, int n_alpha, int k, unsigned char *dig) {
+    for (int i = k - 1; i >= 0; i--) {
+        dig[i] = (unsigned char) (id % (unsigned) n_alpha);
+        id /= (unsigned) n_alpha;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pos_count(const sa_pair16_t *__restrict__ pairs, const PosChunk *__restrict__ chunks, SiteTabs T,
+                                                   unsigned *__restrict__ cnt, int *__restrict__ xmin, int *__restrict__ xmax) {
+    const PosChunk C = chunks[blockIdx.x];
+    const long long w0 = T.word_off[C.job], w1 = T.word_off[C.job + 1];
+    int lo = INT_MAX, hi = -1;
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        const sa_pair16_t r = pairs[C.first + i];
+        const int x = (int) (r.a & 0xfffffffull);
+        lo = min(lo, x);
+        hi = max(hi, x);
+        unsigned char dig[POS_MAX_K];
+        bool have = false;
+        for (int d = 0; d < T.k; d++) {
+            const long long p = (long long) x + d, w = w0 + (p >> 6);
+            if (w >= w1) break;   // (past the job's reference: cannot happen for a record of its matrix)
+            const unsigned long long word = T.bits[w];
+            if (!((word >> (p & 63)) & 1ull)) continue;
+            if (!have) { pos_digits((unsigned) (r.b & 0xffffffffull), T.n_alpha, T.k, dig); have = true; }
+            const int slot = T.pre[w] + __popcll(word & ((1ull << (p & 63)) - 1ull));
+            if (T.slot[(int) T.kind[slot] * T.n_alpha + (int) dig[d]] < 0) continue;
+            atomicAdd(&cnt[slot], 1u);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o));
+        hi = max(hi, __shfl_xor(hi, o));
+    }
+    if ((threadIdx.x & 63) == 0 && hi >= 0) {
+        atomicMin(&xmin[C.job], lo);
+        atomicMax(&xmax[C.job], hi);
+    }
+}
+
+// job blockIdx.x (one wave): loc[s] = rows of the job's slots before s; tot[j] = the job's rows over all its slots
+__global__ __launch_bounds__(64) void k_pos_job_scan(SiteTabs T, const unsigned *__restrict__ cnt, unsigned *__restrict__ loc,
+                                                     int *__restrict__ tot) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const long long s0 = T.site_off[j], s1 = T.site_off[j + 1];
+    unsigned carry = 0;
+    for (long long base = s0; base < s1; base += 64) {
+        const long long s = base + lane;
+        const unsigned v = s < s1 ? cnt[s] : 0u;
+        unsigned incl = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned u = __shfl_up(incl, o);
+            if (lane >= o) incl += u;
+        }
+        if (s < s1) loc[s] = carry + incl - v;
+        carry += __shfl(incl, 63);
+    }
+    if (lane == 0) tot[j] = (int) carry;
+}
+
+__global__ __launch_bounds__(256) void k_pos_scatter(const sa_pair16_t *__restrict__ pairs, const PosChunk *__restrict__ chunks, SiteTabs T,
+                                                     const unsigned *__restrict__ loc, const long long *__restrict__ base,
+                                                     unsigned *__restrict__ fill, unsigned long long *__restrict__ ent) {
+    const PosChunk C = chunks[blockIdx.x];
+    const long long w0 = T.word_off[C.job], w1 = T.word_off[C.job + 1], b0 = base[C.job];
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        const sa_pair16_t r = pairs[C.first + i];
+        const int x = (int) (r.a & 0xfffffffull);
+        unsigned char dig[POS_MAX_K];
+        bool have = false;
+        for (int d = 0; d < T.k; d++) {
+            const long long p = (long long) x + d, w = w0 + (p >> 6);
+            if (w >= w1) break;
+            const unsigned long long word = T.bits[w];
+            if (!((word >> (p & 63)) & 1ull)) continue;
+            if (!have) { pos_digits((unsigned) (r.b & 0xffffffffull), T.n_alpha, T.k, dig); have = true; }
+            const int slot = T.pre[w] + __popcll(word & ((1ull << (p & 63)) - 1ull));
+            const int l = T.slot[(int) T.kind[slot] * T.n_alpha + (int) dig[d]];
+            if (l < 0) continue;
+            const unsigned long long units = (unsigned long long) sa_printed_units((long long) ((r.b >> 32) & 0xffffffull));
+            const unsigned q = atomicAdd(&fill[slot], 1u);
+            ent[b0 + (long long) loc[slot] + q] = ((unsigned long long) (C.local + i) << 24) | ((unsigned long long) l << 20) | units;
+        }
+    }
+}
+
+// job blockIdx.x: every slot's bucket in row order, folded; kept[j] = the job's slots with rows
+__global__ __launch_bounds__(256) void k_pos_fold(SiteTabs T, const unsigned *__restrict__ cnt, const unsigned *__restrict__ loc,
+                                                  const long long *__restrict__ base, unsigned long long *__restrict__ ent,
+                                                  double *__restrict__ sum, double *__restrict__ prob, int *__restrict__ kept) {
+    __shared__ int n_kept;
+    const int j = blockIdx.x;
+    if (threadIdx.x == 0) n_kept = 0;
+    __syncthreads();
+    const long long s0 = T.site_off[j], s1 = T.site_off[j + 1];
+    for (long long s = s0 + threadIdx.x; s < s1; s += blockDim.x) {
+        const unsigned n = cnt[s];
+        if (n == 0) continue;
+        unsigned long long *e = ent + base[j] + loc[s];
+        for (unsigned a = 1; a < n; a++) {   // insertion sort: buckets hold tens of entries
+            const unsigned long long v = e[a];
+            unsigned b = a;
+            while (b > 0 && e[b - 1] > v) { e[b] = e[b - 1]; b--; }
+            e[b] = v;
+        }
+        double acc[SA_SITE_MAX_LETTERS];
+        const int nl = T.nl[T.kind[s]];
+        for (int l = 0; l < SA_SITE_MAX_LETTERS; l++) acc[l] = 0.0;
+        for (unsigned a = 0; a < n; a++) {
+            const unsigned long long v = e[a];
+            const int l = (int) ((v >> 20) & 0xfull);
+            const double u = (double) (long long) (v & 0xfffffull) / 1e6;   // the double "%f" reads back as
+#pragma unroll
+            for (int q = 0; q < SA_SITE_MAX_LETTERS; q++)
+                if (q == l) acc[q] += u;
+        }
+        double total = 0.0;
+        for (int l = 0; l < nl; l++) total += acc[l];
+        double *ps = sum + (size_t) s * (size_t) T.stride, *pp = prob + (size_t) s * (size_t) T.stride;
+        for (int l = 0; l < nl; l++) {
+            ps[l] = acc[l];
+            pp[l] = acc[l] / total;
+        }
+        atomicAdd(&n_kept, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) kept[j] = n_kept;
+}
+
+// job blockIdx.x: its non-empty slots, in position order, from off[j] on -- slot index, row count, sums and probabilities
+__global__ __launch_bounds__(64) void k_pos_compact(SiteTabs T, const unsigned *__restrict__ cnt, const double *__restrict__ sum,
+                                                    const double *__restrict__ prob, const long long *__restrict__ off,
+                                                    int *__restrict__ o_slot, unsigned *__restrict__ o_n, double *__restrict__ o_sum,
+                                                    double *__restrict__ o_prob) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const long long s0 = T.site_off[j], s1 = T.site_off[j + 1];
+    const size_t st = (size_t) T.stride;
+    long long w = off[j];
+    for (long long b = s0; b < s1; b += 64) {
+        const long long s = b + lane;
+        const bool keep = s < s1 && cnt[s] != 0;
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            const size_t dst = (size_t) (w + __popcll(mask & ((1ull << lane) - 1ull)));
+            const int nl = T.nl[T.kind[s]];
+            o_slot[dst] = (int) s;
+            o_n[dst] = cnt[s];
+            for (int l = 0; l < nl; l++) {
+                o_sum[dst * st + (size_t) l] = sum[(size_t) s * st + (size_t) l];
+                o_prob[dst * st + (size_t) l] = prob[(size_t) s * st + (size_t) l];
+            }
+        }
+        w += __popcll(mask);
+    }
+}
+
+static SaScratch g_pos_ws;
+
+extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out,
+                                       int32_t *x_min_out, int32_t *x_max_out, double *kernel_ms_out) {
+    (void) flags;
+    if (!b || !calls_out || !n_out) return SA_EINVAL;
+    SaPositions *P = nullptr;
+    int64_t nj64 = 0;
+    int rc = sa_batch_positions(b, &P, &nj64);
+    if (rc) return rc;
+    const size_t nj = (size_t) nj64;
+    for (size_t j = 0; j < nj; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (nj == 0) return SA_OK;
+    const size_t stride = (size_t) (P->stride > 0 ? P->stride : 1), ns = (size_t) P->n_sites;
+    const sa_pair16_t *d_pairs = nullptr;
+    std::vector<long long> first, count, n_events;
+    int device = 0;
+    if ((rc = sa_batch_device_view(b, &d_pairs, &first, &count, &n_events, &device)) != SA_OK) return rc;
+    std::vector<PosChunk> chunks;
+    for (size_t j = 0; j < nj; j++)   // (a job's bucket entries, at most k per record, are counted in 32 bits)
+        if ((long long) P->k * count[j] >= (long long) INT32_MAX) return SA_EUNSUPPORTED;
+    for (size_t j = 0; j < nj; j++)
+        for (long long c = 0; c < count[j]; c += SITE_CHUNK)
+            chunks.push_back(PosChunk{first[j] + c, c, (int) std::min<long long>(SITE_CHUNK, count[j] - c), (int) j});
+    const size_t nc = chunks.size(), ns1 = ns ? ns : 1;
+    // device: [cnt | fill | loc | sum | prob | chunks | tot | base | kept | off | xmin | xmax | out slot | out n | out sum |
+    // out prob]; the entries in a block of their own, sized once the counts are known
+    const size_t o_cnt = 0, o_fill = sa_up256(4 * ns1), o_loc = sa_up256(o_fill + 4 * ns1), o_sum = sa_up256(o_loc + 4 * ns1),
+                 o_prob = sa_up256(o_sum + 8 * ns1 * stride), o_chunks = sa_up256(o_prob + 8 * ns1 * stride),
+                 o_tot = sa_up256(o_chunks + sizeof(PosChunk) * (nc ? nc : 1)), o_base = sa_up256(o_tot + 4 * nj),
+                 o_kept = sa_up256(o_base + 8 * (nj + 1)), o_off = sa_up256(o_kept + 4 * nj), o_xmin = sa_up256(o_off + 8 * (nj + 1)),
+                 o_xmax = sa_up256(o_xmin + 4 * nj), o_oslot = sa_up256(o_xmax + 4 * nj), o_on = sa_up256(o_oslot + 4 * ns1),
+                 o_osum = sa_up256(o_on + 4 * ns1), o_oprob = o_osum + 8 * ns1 * stride, dev_bytes = o_oprob + 8 * ns1 * stride;
+    std::vector<long long> h_base(nj + 1, 0), h_off(nj + 1, 0);
+    std::vector<int> h_xmin(nj), h_xmax(nj);
+    std::vector<int> h_slot;
+    std::vector<unsigned> h_cnt;
+    std::vector<double> h_sum, h_prob;
+    char *d = nullptr;
+    unsigned long long *d_ent = nullptr;
+    SaScratch &W = g_pos_ws;
+    std::unique_lock<std::mutex> guard(W.mu);
+    float kms0 = 0, kms1 = 0;
+    size_t n_kept = 0;
+    SiteTabs T;
+    if ((rc = W.rebind(device)) != SA_OK || (rc = W.events()) != SA_OK || (rc = sites_upload(P, device)) != SA_OK) return rc;
+    if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
+    T = sites_tabs(P);
+    if (nc) SITECHK(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(PosChunk) * nc, hipMemcpyHostToDevice, 0));
+    SITECHK(hipMemsetAsync(d + o_cnt, 0, o_loc, 0));   // (cnt and fill)
+    SITECHK(hipMemsetAsync(d + o_xmin, 0x7f, 4 * nj, 0));
+    SITECHK(hipMemsetAsync(d + o_xmax, 0xff, 4 * nj, 0));
+    SITECHK(hipEventRecord(W.e0, 0));
+    if (nc) hipLaunchKernelGGL(k_pos_count, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const PosChunk *) (d + o_chunks), T,
+                               (unsigned *) (d + o_cnt), (int *) (d + o_xmin), (int *) (d + o_xmax));
+    hipLaunchKernelGGL(k_pos_job_scan, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned *) (d + o_cnt), (unsigned *) (d + o_loc),
+                       (int *) (d + o_tot));
+    hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SITE_SCAN_THREADS), 0, 0, (const int *) (d + o_tot), (long long *) (d + o_base), (int) nj);
+    SITECHK(hipEventRecord(W.e1, 0));
+    SITECHK(hipGetLastError());
+    SITECHK(hipMemcpy(h_base.data(), d + o_base, 8 * (nj + 1), hipMemcpyDeviceToHost));
+    SITECHK(hipEventElapsedTime(&kms0, W.e0, W.e1));
+    {   // the buckets: 8 bytes per (record, covered ambiguous position)
+        const size_t n_ent = (size_t) h_base[nj];
+        if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_ent, 8 * (n_ent ? n_ent : 1), device) != hipSuccess) {
+            d_ent = nullptr;
+            rc = SA_ENOMEM;
+            goto done;
+        }
+    }
+    SITECHK(hipEventRecord(W.e0, 0));
+    if (nc) hipLaunchKernelGGL(k_pos_scatter, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const PosChunk *) (d + o_chunks), T,
+                               (const unsigned *) (d + o_loc), (const long long *) (d + o_base), (unsigned *) (d + o_fill), d_ent);
+    hipLaunchKernelGGL(k_pos_fold, dim3((unsigned) nj), dim3(256), 0, 0, T, (const unsigned *) (d + o_cnt), (const unsigned *) (d + o_loc),
+                       (const long long *) (d + o_base), d_ent, (double *) (d + o_sum), (double *) (d + o_prob), (int *) (d + o_kept));
+    hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SITE_SCAN_THREADS), 0, 0, (const int *) (d + o_kept), (long long *) (d + o_off), (int) nj);
+    hipLaunchKernelGGL(k_pos_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned *) (d + o_cnt), (const double *) (d + o_sum),
+                       (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_oslot), (unsigned *) (d + o_on),
+                       (double *) (d + o_osum), (double *) (d + o_oprob));
+    SITECHK(hipEventRecord(W.e1, 0));
+    SITECHK(hipGetLastError());
+    SITECHK(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
+    SITECHK(hipEventElapsedTime(&kms1, W.e0, W.e1));
+    if (kernel_ms_out) *kernel_ms_out = (double) kms0 + (double) kms1;
+    n_kept = (size_t) h_off[nj];
+    SITECHK(hipMemcpy(h_xmin.data(), d + o_xmin, 4 * nj, hipMemcpyDeviceToHost));
+    SITECHK(hipMemcpy(h_xmax.data(), d + o_xmax, 4 * nj, hipMemcpyDeviceToHost));
+    if (n_kept) {   // only the kept positions cross PCIe
+        h_slot.resize(n_kept);
+        h_cnt.resize(n_kept);
+        h_sum.resize(n_kept * stride);
+        h_prob.resize(n_kept * stride);
+        SITECHK(hipMemcpy(h_slot.data(), d + o_oslot, 4 * n_kept, hipMemcpyDeviceToHost));
+        SITECHK(hipMemcpy(h_cnt.data(), d + o_on, 4 * n_kept, hipMemcpyDeviceToHost));
+        SITECHK(hipMemcpy(h_sum.data(), d + o_osum, 8 * n_kept * stride, hipMemcpyDeviceToHost));
+        SITECHK(hipMemcpy(h_prob.data(), d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost));
+    }
+    for (size_t j = 0; j < nj; j++) {
+        const bool any = count[j] > 0;
+        if (x_min_out) x_min_out[j] = any ? (int32_t) h_xmin[j] : -1;
+        if (x_max_out) x_max_out[j] = any ? (int32_t) h_xmax[j] : -1;
+    }
+    {
+        std::atomic<bool> oom(false);
+        sa_parallel_for(nj, [&](size_t j) {
+            const long long a = h_off[j], n = h_off[j + 1] - h_off[j];
+            n_out[j] = n;
+            calls_out[j] = (sa_position_call_t *) calloc((size_t) (n > 0 ? n : 1), sizeof(sa_position_call_t));
+            if (!calls_out[j]) { oom = true; return; }
+            for (long long i = 0; i < n; i++) {
+                sa_position_call_t &c = calls_out[j][i];
+                const size_t r = (size_t) (a + i), s = (size_t) h_slot[r];
+                const std::string &l = P->letters[P->kind[s]];
+                c.p = P->x[s];
+                c.n_rows = (int32_t) h_cnt[r];
+                c.n_letters = (int32_t) l.size();
+                memcpy(c.letters, l.data(), l.size());
+                for (size_t q = 0; q < l.size(); q++) {
+                    c.sum[q] = h_sum[r * stride + q];
+                    c.prob[q] = h_prob[r * stride + q];
+                }
+            }
+        });
+        if (oom) rc = SA_ENOMEM;
+    }
+done:
+    if (rc != SA_OK && d) (void) hipStreamSynchronize(0);
+    if (d) g_sa_pool.put(SaPool::DEVICE, d);
+    if (d_ent) g_sa_pool.put(SaPool::DEVICE, d_ent);
     if (rc != SA_OK)
         for (size_t j = 0; j < nj; j++) { free(calls_out[j]); calls_out[j] = nullptr; n_out[j] = 0; }
     return rc;

@@ -1302,6 +1302,7 @@ struct sa_batch {
     std::vector<unsigned long long> h_vc_bits;  // (the same on the host, for SA_FLAG_EXACT's host finalisation)
     std::vector<long long> h_vc_off, job_all_n, job_all_sum;
     SaSites *sites = nullptr;                   // SA_FLAG_SITE_CALLS: the batch's sites (sa_calls.hip)
+    SaPositions *positions = nullptr;           // SA_FLAG_POSITION_CALLS: the batch's ambiguous positions (sa_calls.hip)
     bool plan_hdp = false;                      // the batch's model holds an HDP
     unsigned hdp_hot = 0xffffffffu;             // DevModel.hdp_hot
     char *d_seam = nullptr;      // their seam storage: per wave two arrays of seam_cap records of 16 bytes
@@ -1784,6 +1785,7 @@ void sa_batch_destroy(sa_batch_t *b) {
     g_sa_pool.put(SaPool::PINNED, b->h_seg_off);
     g_sa_pool.put(SaPool::PINNED, b->h_overflow);
     sa_sites_free(b->sites);
+    sa_positions_free(b->positions);
     const double td2 = now_ms();
     sa_plan_free(b->plan);
     delete b;
@@ -1842,8 +1844,9 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     // reference-ordered kernels.  (SA_TWO_DIST_FAST_OFF=1: always the reference-ordered kernels, as up to round 5.)
     if (m->emission != 0 && ((flags & (SA_FLAG_EXPECT_INTERNAL | SA_FLAG_FORCE_GENERIC)) || getenv("SA_TWO_DIST_FAST_OFF")))
         flags |= SA_FLAG_EXACT;
-    if (flags & SA_FLAG_EXPECT_INTERNAL) flags &= ~SA_FLAG_SITE_CALLS;
-    if ((flags & SA_FLAG_SITE_CALLS) && (flags & SA_FLAG_VC_ROWS)) return SA_EINVAL;   // (that flag drops the rows the calls are made of)
+    if (flags & SA_FLAG_EXPECT_INTERNAL) flags &= ~(SA_FLAG_SITE_CALLS | SA_FLAG_POSITION_CALLS);
+    if ((flags & (SA_FLAG_SITE_CALLS | SA_FLAG_POSITION_CALLS)) && (flags & SA_FLAG_VC_ROWS)) return SA_EINVAL;   // (that flag drops the rows the calls are made of)
+    if ((flags & SA_FLAG_POSITION_CALLS) && (flags & SA_FLAG_PAIRS8)) return SA_EUNSUPPORTED;   // (an 8-byte record names no path k-mer)
     const bool trace_c = getenv("SA_TRACE") != nullptr;
     const double tc0 = now_ms();
     HIPCHK(hipSetDevice(device));
@@ -1876,6 +1879,13 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
         if (rcs || ((flags & SA_FLAG_PAIRS8) && sa_sites_count(b->sites) > 0)) {
             sa_batch_destroy(b);
             return rcs ? rcs : SA_EUNSUPPORTED;
+        }
+    }
+    if (flags & SA_FLAG_POSITION_CALLS) {   // every job's ambiguous positions: one pass over its reference (sa_calls.hip)
+        const int rcp = n_jobs > 0 && !jobs ? SA_EINVAL : sa_positions_build(m, jobs, n_jobs, ambig, &b->positions);
+        if (rcp) {
+            sa_batch_destroy(b);
+            return rcp;
         }
     }
 #define TRY(x) do { int rc_ = (x); if (rc_) { sa_batch_destroy(b); return rc_; } } while (0)
@@ -3085,6 +3095,14 @@ int sa_batch_sites(sa_batch_t *b, SaSites **sites, int64_t *n_jobs) {
     return SA_OK;
 }
 
+int sa_batch_positions(sa_batch_t *b, SaPositions **positions, int64_t *n_jobs) {
+    if (!b || !positions || !n_jobs) return SA_EINVAL;
+    if (!b->positions || !b->ran) return SA_ESTATE;
+    *positions = b->positions;
+    *n_jobs = b->c_n;
+    return SA_OK;
+}
+
 // sa_batch_run on a thread of the library's own, so that the caller can plan the next batch (sa_batch_create is host
 // work) while this one is on the GPU; sa_batch_wait joins it and returns sa_batch_run's code.
 int sa_batch_prepare(sa_batch_t *b) {
@@ -3115,6 +3133,7 @@ int sa_batch_release_device(sa_batch_t *b) {
     b->put_blocks(0, sa_batch::BLK_END);
     if (b->held_stage) { g_sa_pool.put(SaPool::PINNED, b->held_stage); b->held_stage = nullptr; }
     sa_sites_release_device(b->sites);
+    sa_positions_release_device(b->positions);
     b->released = true;
     return SA_OK;
 }

@@ -8,6 +8,7 @@
 #define _GNU_SOURCE
 #include "sa_io.h"
 
+#include <inttypes.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -657,4 +658,55 @@ char *sa_reverse_complement(const char *s) {
     char *o = sa_complement(s);
     sa_reverse_in_place(o);
     return o;
+}
+
+/* ---- signalMachine --snp-step: replace_periodic_sequence_positions on a window, the site window of call_methyls and the
+ * per-read file of discover_single_nucleotide_probabilities (include/signalalign_hip.h) ---- */
+int sa_snp_substitute(const char *ref, int64_t len, int64_t contig_pos_of_ref0, int reversed, int64_t step, int64_t phase,
+                      char letter, char *out) {
+    if (!ref || !out || len < 0 || step < 1 || phase < 0 || phase >= step) return SA_EINVAL;
+    for (int64_t i = 0; i < len; i++) {
+        const int64_t c = reversed ? contig_pos_of_ref0 - i : contig_pos_of_ref0 + i;
+        const int64_t r = ((c % step) + step) % step;
+        const char ch = ref[i];
+        out[i] = r == phase ? letter : (ch >= 'a' && ch <= 'z') ? (char) (ch - 'a' + 'A') : ch;
+    }
+    out[len] = 0;
+    return SA_OK;
+}
+
+static int64_t floor_mult(int64_t v, int64_t m) { return v - (((v % m) + m) % m); }
+int sa_snp_site_window(int64_t min_ref_index, int64_t max_ref_index, int64_t step, int64_t *lo_out, int64_t *hi_out) {
+    if (step < 1 || !lo_out || !hi_out) return SA_EINVAL;
+    *lo_out = floor_mult(min_ref_index - step, step);
+    const int64_t hi = max_ref_index + step;
+    *hi_out = floor_mult(hi, step) == hi ? hi : floor_mult(hi, step) + step;
+    return SA_OK;
+}
+
+static int cmp_snp_pos(const void *a, const void *b) {   /* by position, then by index: a stable sort */
+    const sa_snp_site_t *x = *(const sa_snp_site_t *const *) a, *y = *(const sa_snp_site_t *const *) b;
+    if (x->pos != y->pos) return x->pos < y->pos ? -1 : 1;
+    return x < y ? -1 : x > y;
+}
+int sa_format_py_repr(char *out, double v);
+int sa_snp_write_read(const char *path, const char *fast5_input, const char *read_id, const char *contig, int backward,
+                      const sa_snp_site_t *sites, int64_t n) {
+    if (!path || !fast5_input || !read_id || !contig || n < 0 || (n > 0 && !sites)) return SA_EINVAL;
+    const sa_snp_site_t **v = malloc(sizeof(*v) * (size_t) (n > 0 ? n : 1));
+    if (!v) return SA_ENOMEM;
+    for (int64_t i = 0; i < n; i++) v[i] = &sites[i];
+    qsort(v, (size_t) n, sizeof(*v), cmp_snp_pos);
+    FILE *fh = fopen(path, "w");
+    if (!fh) { free(v); return SA_EIO; }
+    setvbuf(fh, NULL, _IOFBF, 1 << 16);
+    fprintf(fh, "## fast5_input: %s\n## read_id: %s\n## contig: %s\n## strand: %s\n#CHROM\tPOS\tpA\tpC\tpG\tpT\n", fast5_input,
+            read_id, n > 0 ? contig : "", backward ? "complement" : "template");
+    char num[4][40];
+    for (int64_t i = 0; i < n; i++) {
+        for (int l = 0; l < 4; l++) sa_format_py_repr(num[l], v[i]->p[backward ? 3 - l : l]);
+        fprintf(fh, "%s\t%" PRId64 "\t%s\t%s\t%s\t%s\n", contig, v[i]->pos, num[0], num[1], num[2], num[3]);
+    }
+    free(v);
+    return fclose(fh) == 0 ? SA_OK : SA_EIO;
 }

@@ -266,6 +266,14 @@ void sa_sites_release_device(SaSites *s);
 void sa_sites_free(SaSites *s);                 // NULL: nothing
 // sa_hip.hip: a finished batch's sites (SA_ESTATE: created without SA_FLAG_SITE_CALLS, or not run)
 int sa_batch_sites(sa_batch_t *b, SaSites **sites, int64_t *n_jobs);
+// sa_calls.hip: the ambiguous positions a SA_FLAG_POSITION_CALLS batch records at creation (sa_positions_build); their device
+// tables go back with the batch's working storage, everything with the batch
+struct SaPositions;
+int sa_positions_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaPositions **out);
+void sa_positions_release_device(SaPositions *s);
+void sa_positions_free(SaPositions *s);                 // NULL: nothing
+// sa_hip.hip: a finished batch's positions (SA_ESTATE: created without SA_FLAG_POSITION_CALLS, or not run)
+int sa_batch_positions(sa_batch_t *b, SaPositions **positions, int64_t *n_jobs);
 
 // The posterior the TSV prints, "%f" of prob_e7 / 1e7, in integers of 1e-6: a decimal rounding of a binary double.  Only a
 // last digit of 5 can tie; then the sign of q * 1e7 - prob_e7 (one fma, exact in sign) says on which side of the tie the

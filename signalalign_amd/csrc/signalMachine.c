@@ -24,6 +24,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <errno.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "sa_io.h"
@@ -71,6 +73,9 @@ static void usage(void) {
                     "                  each of its letters (variantCaller.py MarginalizeFullVariants)\n");
     fprintf(stderr, "--site-calls-aggregate <file>: write the per-site calls averaged over all reads of the run to <file>\n"
                     "                  (AggregateOverReadsFull); a manifest's posteriors file may then be '-' (no TSV for that read)\n");
+    fprintf(stderr, "--snp-step <N> --snp-dir <dir>: single-nucleotide probabilities: every read is aligned N times, with X at the\n"
+                    "                  reference positions = s (mod N) in run s; <dir>/<label>.tsv gets pA pC pG pT per covered position\n"
+                    "                  (singleNucleotideProbabilities.py); no posteriors file: no -u, a manifest's posteriors column '-'\n");
     fprintf(stderr, "--train-assignments <file>: write the top-N assignments table of the run (buildAlignment: kmer, strand, descaled\n"
                     "                  mean, posterior; what buildHdpUtil -l reads), selected on the GPU\n"
                     "--train-template-model <file> / --train-complement-model <file>: write the -T / -C model with its Gaussian event\n"
@@ -344,6 +349,8 @@ typedef struct {
     int two_dist; /* --emission twoDist: the two-distribution emission (not an option of the reference binary: it is what its
                    * state machine carried when the reference's shipped output files were written); one read per process */
     int64_t out_fmt, constraint_trim;
+    int64_t snp_step;       /* --snp-step N: single-nucleotide probabilities, N substituted copies of every read's reference */
+    const char *snp_dir;    /* --snp-dir: where <label>.tsv goes */
     const char *fwd_ref, *bwd_ref;
     sa_params_t p;
     strand_model_t smt, smc;
@@ -358,6 +365,7 @@ typedef struct {
     char *forward_seq, *backward_seq;
     const char *template_target, *complement_target;
     int64_t t_lo, t_hi, c_lo, c_hi, r_shift_t, r_shift_c, n_guide;
+    int64_t win_lo;       /* contig coordinate of forward_seq[0] (backward_seq[i] lies at win_lo + len - 1 - i) */
     int forward;
     int64_t *ax[2], *ay[2];
     sa_job_t jobs[2];
@@ -451,6 +459,7 @@ static int prepare_read(const run_t *R, read_t *rd, int fatal) {
         return fail(rd, 0, "sequence name %s is not in the reference fasta", seq_name);
     }
     if (rd->forward_seq == NULL) return fail(rd, fatal, "[signalMachine] ERROR: Unable to fetch reference sequence.  ", NULL);
+    rd->win_lo = pA->strand1 ? pA->start1 : pA->end1;
     if (R->bwd_ref) {
         rd->backward_seq = pA->strand1 ? sa_fasta_fetch(R->bwd_ref, seq_name, pA->start1, pA->end1 - 1, &ferr)
                                        : sa_fasta_fetch(R->bwd_ref, seq_name, pA->end1, pA->start1 - 1, &ferr);
@@ -1381,6 +1390,231 @@ static void release_read(read_t *rd) {
     rd->pA = NULL; rd->np = NULL; rd->forward_seq = rd->backward_seq = NULL;
 }
 
+/* ---- --snp-step N --snp-dir DIR: single-nucleotide probabilities (singleNucleotideProbabilities.py:551-723) ----
+ * Every read strand becomes N jobs in one batch: job s aligns the read to its window with X at the contig positions = s (mod N)
+ * (replace_periodic_reference_positions; the default ambiguity table makes X the four bases).  sa_batch_position_calls folds
+ * the rows of every X position on the device (CallMethylation.call_methyls); the N step files of a read are merged into
+ * DIR/<label>.tsv (discover_single_nucleotide_probabilities).  fast5_input names the .npRead: the one deliberate difference. */
+typedef struct {
+    const run_t *run;
+    read_t *reads;
+    const int64_t *who;
+    int64_t N;
+    sa_position_call_t **calls[2];   /* [strand][read * N + step] */
+    int64_t *n_calls[2];
+    int32_t *x_min[2], *x_max[2];
+} snp_out_t;
+
+/* contig coordinate of index t of a strand's target (the TSV's reference_index of a k-mer at t covers t .. t + k - 1) */
+static int64_t snp_contig_pos(const read_t *rd, int s, int64_t t) {
+    const int64_t off = s == 0 ? rd->r_shift_t : rd->r_shift_c;
+    const int same = (s == 0 && rd->forward) || (s == 1 && !rd->forward);
+    return same ? off + t : off - 1 - t;
+}
+
+static void snp_output_one(int64_t j, void *ctx) {
+    snp_out_t *c = ctx;
+    const run_t *R = c->run;
+    read_t *rd = &c->reads[c->who[j]];
+    const int n_strands = R->two_d ? 2 : 1;
+    int64_t cap = 0;
+    for (int64_t s = 0; s < c->N; s++)
+        for (int q = 0; q < n_strands; q++) cap += c->n_calls[q][j * c->N + s];
+    sa_snp_site_t *sites = malloc(sizeof(sa_snp_site_t) * (size_t) (cap > 0 ? cap : 1));
+    if (!sites) die("signalMachine: out of memory%s", "");
+    int64_t n = 0;
+    for (int64_t s = 0; s < c->N; s++) {   /* one step file after the other */
+        const int64_t js = j * c->N + s;
+        /* the window of call_methyls (:160-169) over the reference_index of every row of the step's file, both strands */
+        int64_t lo_ref = INT64_MAX, hi_ref = INT64_MIN;
+        for (int q = 0; q < n_strands; q++) {
+            if (c->x_min[q][js] < 0) continue;
+            const int k = q == 0 ? R->smt.k : R->smc.k;
+            const char *target = q == 0 ? rd->template_target : rd->complement_target;
+            const int64_t len = (int64_t) strlen(target), off = q == 0 ? rd->r_shift_t : rd->r_shift_c;
+            const int64_t a = adjust_ref(c->x_min[q][js], off, len - k, len, q == 0, rd->forward);
+            const int64_t b = adjust_ref(c->x_max[q][js], off, len - k, len, q == 0, rd->forward);
+            lo_ref = a < lo_ref ? a : lo_ref; lo_ref = b < lo_ref ? b : lo_ref;
+            hi_ref = a > hi_ref ? a : hi_ref; hi_ref = b > hi_ref ? b : hi_ref;
+        }
+        if (lo_ref > hi_ref) continue;   /* no row at all: the reference's step file cannot be parsed and is missing */
+        int64_t w_lo = 0, w_hi = 0;
+        sa_snp_site_window(lo_ref, hi_ref, c->N, &w_lo, &w_hi);
+        for (int q = 0; q < n_strands; q++) {   /* template sites, then complement sites, each ascending */
+            const sa_position_call_t *pc = c->calls[q][js];
+            const int64_t m = c->n_calls[q][js];
+            const int same = (q == 0 && rd->forward) || (q == 1 && !rd->forward);
+            for (int64_t i0 = 0; i0 < m; i0++) {
+                const sa_position_call_t *p = &pc[same ? i0 : m - 1 - i0];
+                const int64_t pos = snp_contig_pos(rd, q, p->p);
+                if (pos < w_lo || pos >= w_hi) continue;
+                sa_snp_site_t *o = &sites[n++];
+                o->pos = pos;
+                o->strand = q;
+                o->pad = 0;
+                for (int l = 0; l < 4; l++) {
+                    o->p[l] = 0.0;
+                    for (int e = 0; e < p->n_letters; e++)
+                        if (p->letters[e] == "ACGT"[l]) o->p[l] = p->prob[e];
+                }
+            }
+        }
+    }
+    const char *np_name = strrchr(rd->npread_path, '/') ? strrchr(rd->npread_path, '/') + 1 : rd->npread_path;
+    char *path = malloc(strlen(R->snp_dir) + strlen(rd->label) + 8);
+    sprintf(path, "%s/%s.tsv", R->snp_dir, rd->label);
+    if (sa_snp_write_read(path, np_name, rd->label, rd->pA->contig1, !rd->forward, sites, n) != SA_OK)
+        die("signalMachine: cannot write %s", path);
+    free(path);
+    free(sites);
+}
+
+/* plans every substituted job of a read alone on the host (validate_read for the N copies) */
+typedef struct { const run_t *R; read_t *reads; const int64_t *who; sa_job_t *const *jobs; int64_t N; } snp_validate_t;
+static void snp_validate_one(int64_t j, void *ctx) {
+    snp_validate_t *v = ctx;
+    read_t *rd = &v->reads[v->who[j]];
+    for (int q = 0; q < (v->R->two_d ? 2 : 1) && !rd->failed; q++)
+        for (int64_t s = 0; s < v->N && !rd->failed; s++) {
+            const int rc = sa_plan_describe(q == 0 ? v->R->smt.model : v->R->smc.model, &v->R->p, &v->jobs[q][j * v->N + s], v->R->ambig,
+                                            0, NULL, NULL, 0, NULL, 0, NULL, 0);
+            if (rc != SA_OK) fail(rd, 0, "alignment job rejected: %s", sa_strerror(rc));
+        }
+    if (rd->failed) fprintf(stderr, "[signalMachine] ERROR: read %s skipped: %s\n", rd->label, rd->err);
+}
+
+/* GPU stage and outputs of a slice in --snp-step mode; returns the number of the slice's reads that failed */
+static int64_t run_slice_snp(run_t *Rp, read_t *reads, int64_t n_reads, int batch_mode, int device) {
+#define R (*Rp)
+    const int n_strands = R.two_d ? 2 : 1;
+    const int64_t N = R.snp_step;
+    const strand_model_t *sms[2] = {&R.smt, &R.smc};
+    const double ts1 = now_s();
+    int64_t *who = malloc(sizeof(int64_t) * (size_t) (n_reads > 0 ? n_reads : 1));
+    int64_t n_ok = 0;
+    for (int64_t i = 0; i < n_reads; i++)
+        if (!reads[i].failed) who[n_ok++] = i;
+    /* the substituted targets: read j, step s, strand q at tgt[q][j * N + s] */
+    char **tgt[2] = {NULL, NULL};
+    sa_job_t *jobs[2] = {NULL, NULL};
+    const size_t nj_all = (size_t) (n_ok > 0 ? n_ok : 1) * (size_t) N;
+    for (int q = 0; q < n_strands; q++) {
+        tgt[q] = calloc(nj_all, sizeof(char *));
+        jobs[q] = calloc(nj_all, sizeof(sa_job_t));
+        if (!tgt[q] || !jobs[q]) die("signalMachine: out of memory%s", "");
+    }
+    for (int64_t j = 0; j < n_ok; j++) {
+        read_t *rd = &reads[who[j]];
+        const int64_t hi = rd->win_lo + (int64_t) strlen(rd->forward_seq) - 1;
+        for (int q = 0; q < n_strands; q++) {
+            const char *t = q == 0 ? rd->template_target : rd->complement_target;
+            const int from_fwd = t == rd->forward_seq;   /* forward_seq[i] at win_lo + i, backward_seq[i] at hi - i */
+            const int64_t len = (int64_t) strlen(t);
+            for (int64_t s = 0; s < N; s++) {
+                char *o = malloc((size_t) len + 1);
+                if (!o) die("signalMachine: out of memory%s", "");
+                sa_snp_substitute(t, len, from_fwd ? rd->win_lo : hi, !from_fwd, N, s, 'X', o);
+                tgt[q][j * N + s] = o;
+                jobs[q][j * N + s] = rd->jobs[q];
+                jobs[q][j * N + s].ref = o;
+            }
+        }
+    }
+    snp_out_t oc;
+    memset(&oc, 0, sizeof(oc));
+    oc.run = Rp; oc.reads = reads; oc.who = who; oc.N = N;
+    int64_t *n_pairs[2] = {NULL, NULL}, *sum_e7[2] = {NULL, NULL};
+    int validated = !batch_mode;
+    for (int q = 0; q < n_strands; q++) {
+        const int64_t nj = n_ok * N;
+        oc.calls[q] = calloc(nj_all, sizeof(sa_position_call_t *));
+        oc.n_calls[q] = calloc(nj_all, sizeof(int64_t));
+        oc.x_min[q] = calloc(nj_all, sizeof(int32_t));
+        oc.x_max[q] = calloc(nj_all, sizeof(int32_t));
+        n_pairs[q] = calloc(nj_all, sizeof(int64_t));
+        sum_e7[q] = calloc(nj_all, sizeof(int64_t));
+        if (nj == 0) continue;
+        fprintf(stderr, q == 0 ? "signalAlign - starting template alignment\n" : "signalAlign - starting complement alignment\n");
+        sa_batch_t *b = NULL;
+        int rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[q] : sms[q]->model, &R.p, jobs[q], nj, R.ambig, device,
+                                 SA_FLAG_POSITION_CALLS);
+        if (rc == SA_OK) rc = sa_batch_run(b);
+        if (rc == SA_OK) rc = sa_batch_position_calls(b, 0, oc.calls[q], oc.n_calls[q], oc.x_min[q], oc.x_max[q], NULL);
+        for (int64_t i = 0; i < nj && rc == SA_OK; i++) rc = sa_batch_all_pairs_summary(b, i, &n_pairs[q][i], &sum_e7[q][i]);
+        sa_batch_destroy(b);
+        if (!validated && rc != SA_OK && rc != SA_ENODEVICE && rc != SA_ENOMEM) {
+            /* the planner turned the batch down: the reads whose substituted jobs it rejects fail alone, the rest start over */
+            validated = 1;
+            snp_validate_t vc = {&R, reads, who, jobs, N};
+            parallel_for(n_ok, snp_validate_one, &vc);
+            /* the slice closes up: a refused read's targets are freed, a kept read's move down to its new place and leave
+             * their old slots empty, so that every target is owned by exactly one slot of tgt */
+            int64_t k2 = 0;
+            for (int64_t j = 0; j < n_ok; j++) {
+                const int refused = reads[who[j]].failed;
+                for (int q2 = 0; q2 < n_strands; q2++)
+                    for (int64_t s = 0; s < N; s++) {
+                        char **src = &tgt[q2][j * N + s];
+                        if (refused) {
+                            free(*src);
+                            *src = NULL;
+                        } else if (k2 != j) {
+                            tgt[q2][k2 * N + s] = *src;
+                            jobs[q2][k2 * N + s] = jobs[q2][j * N + s];
+                            *src = NULL;
+                        }
+                    }
+                if (!refused) who[k2++] = who[j];
+            }
+            if (k2 < n_ok) {
+                for (int q2 = 0; q2 <= q; q2++) {
+                    for (size_t i = 0; i < nj_all; i++) sa_free(oc.calls[q2][i]);
+                    free(oc.calls[q2]); free(oc.n_calls[q2]); free(oc.x_min[q2]); free(oc.x_max[q2]);
+                    free(n_pairs[q2]); free(sum_e7[q2]);
+                    oc.calls[q2] = NULL; oc.n_calls[q2] = NULL; oc.x_min[q2] = oc.x_max[q2] = NULL;
+                    n_pairs[q2] = sum_e7[q2] = NULL;
+                }
+                n_ok = k2;
+                q = -1;   /* both strands again, without the offenders */
+                continue;
+            }
+        }
+        if (rc != SA_OK) {
+            fprintf(stderr, "signalMachine: alignment failed: %s\n", sa_strerror(rc));
+            exit(1);
+        }
+    }
+    g_t_gpu += now_s() - ts1;
+    const double ts2 = now_s();
+    parallel_for(n_ok, snp_output_one, &oc);
+    /* the summary lines of the N -s 0 runs of every read, step after step */
+    for (int64_t j = 0; j < n_ok; j++) {
+        read_t *rd = &reads[who[j]];
+        for (int64_t s = 0; s < N; s++) {
+            const int64_t js = j * N + s;
+            double score[2];
+            for (int q = 0; q < n_strands; q++)
+                score[q] = 100.0 * (double) sum_e7[q][js] / ((double) n_pairs[q][js] * PROB_1);
+            fprintf(stdout, "%s %" PRId64 "\t%" PRId64 "(%f)\t", rd->label, rd->n_guide, n_pairs[0][js], score[0]);
+            if (R.two_d) fprintf(stdout, "%" PRId64 "(%f)\n", n_pairs[1][js], score[1]);
+            else fprintf(stdout, "\n");
+            fprintf(stderr, "signalAlign - SUCCESS: finished alignment of query %s, exiting\n", rd->label);
+        }
+    }
+    t_add(&g_t_render, now_s() - ts2);
+    for (int q = 0; q < n_strands; q++) {
+        for (size_t i = 0; i < nj_all; i++) { sa_free(oc.calls[q] ? oc.calls[q][i] : NULL); free(tgt[q][i]); }
+        free(oc.calls[q]); free(oc.n_calls[q]); free(oc.x_min[q]); free(oc.x_max[q]);
+        free(n_pairs[q]); free(sum_e7[q]); free(tgt[q]); free(jobs[q]);
+    }
+    free(who);
+    int64_t n_failed = 0;
+    for (int64_t i = 0; i < n_reads; i++) n_failed += reads[i].failed ? 1 : 0;
+    for (int64_t i = 0; i < n_reads; i++) release_read(&reads[i]);
+    return n_failed;
+#undef R
+}
+
 int main(int argc, char **argv) {
     run_t R;
     memset(&R, 0, sizeof(R));
@@ -1390,6 +1624,7 @@ int main(int argc, char **argv) {
     int64_t diag_expansion = 50, trace_back = 50, batch_reads = 2048;
     double threshold = 0.01;
     int device = 0; /* --device: which GPU of the node (one process per GPU; reads shard across processes) */
+    int snp_set = 0;
     R.constraint_trim = 14;
     char *t_model = NULL, *c_model = NULL, *label = NULL, *npread_path = NULL, *cigar_path = NULL, *post_path = NULL;
     char *t_expect = NULL, *c_expect = NULL, *t_hdp = NULL, *c_hdp = NULL, *fwd_ref = NULL, *bwd_ref = NULL,
@@ -1435,6 +1670,8 @@ int main(int argc, char **argv) {
                                            {"train-median", no_argument, 0, 1017},
                                            {"train-mod-only", no_argument, 0, 1018},
                                            {"train-kmers", required_argument, 0, 1019},
+                                           {"snp-step", required_argument, 0, 1020},
+                                           {"snp-dir", required_argument, 0, 1021},
                                            {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -1480,6 +1717,11 @@ int main(int argc, char **argv) {
             case 1017: R.train_median = 1; break;
             case 1018: R.train_mod_only = 1; break;
             case 1019: R.train_kmers = strdup(optarg); break;
+            case 1020:
+                snp_set = 1;
+                if (sscanf(optarg, "%" SCNd64, &R.snp_step) != 1) R.snp_step = 0;
+                break;
+            case 1021: R.snp_dir = strdup(optarg); break;
             case 1003: batch_reads = atoll(optarg) > 0 ? atoll(optarg) : batch_reads; break;
             case 1004:
                 if (!strcmp(optarg, "twoDist")) R.two_dist = 1;
@@ -1535,6 +1777,20 @@ int main(int argc, char **argv) {
         if (R.train_n < 1 || !(R.train_min_prob >= 0 && R.train_min_prob <= 1)) die("signalMachine: bad --train-max-assignments / --train-min-prob%s", "");
     }
     if (R.expect_mode && (R.site_calls || R.agg_path)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate need the alignment mode, not -t/-c%s", ""); }
+    if (snp_set || R.snp_dir) {   /* --snp-step: its own outputs only */
+        if (!snp_set || R.snp_step < 1) { usage(); die("signalMachine: --snp-step takes a step N >= 1%s", ""); }
+        if (!R.snp_dir) { usage(); die("signalMachine: --snp-step needs --snp-dir <directory>%s", ""); }
+        if (R.expect_mode) { usage(); die("signalMachine: --snp-step cannot be combined with -t/-c%s", ""); }
+        if (R.mea) { usage(); die("signalMachine: --snp-step cannot be combined with --mea%s", ""); }
+        if (R.site_calls || R.agg_path) { usage(); die("signalMachine: --snp-step cannot be combined with --site-calls / --site-calls-aggregate%s", ""); }
+        if (R.train_assign || R.train_model[0] || R.train_model[1]) { usage(); die("signalMachine: --snp-step cannot be combined with --train-*%s", ""); }
+        for (int64_t i = 0; i < n_reads; i++)
+            if (reads[i].post_path || reads[i].post_path2) {
+                usage();
+                die(batch_mode ? "signalMachine: --snp-step writes no posteriors file: the manifest's posteriors column of %s must be '-'"
+                               : "signalMachine: --snp-step writes no posteriors file: -u / -i not allowed%s", batch_mode ? reads[i].label : "");
+            }
+    }
 
     R.p.threshold = threshold;
     R.p.diagonal_expansion = diag_expansion % 2 == 0 ? diag_expansion : diag_expansion + 1;
@@ -1576,6 +1832,10 @@ int main(int argc, char **argv) {
      * stays on this thread, slice after slice, so the summary lines stay in read order: the front door is bound by host CPU
      * time -- text parsing and TSV rendering -- not by the order of its stages. */
     int64_t n_failed = 0;
+    if (R.snp_step > 0) {   /* a slice holds at most --batch-reads jobs: N per read and strand */
+        batch_reads = batch_reads / R.snp_step > 0 ? batch_reads / R.snp_step : 1;
+        if (mkdir(R.snp_dir, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.snp_dir);
+    }
     slice_prep_t cur = {&R, reads, n_reads < batch_reads ? n_reads : batch_reads, batch_mode}, nxt;
     slice_prepare(&cur);
     for (int64_t off = 0; off < n_reads; off += batch_reads) {
@@ -1589,6 +1849,11 @@ int main(int argc, char **argv) {
             if (!started) slice_prepare(&nxt);
         }
         int64_t failed_now = 0;
+        if (R.snp_step > 0) {
+            n_failed += run_slice_snp(&R, reads + off, n, batch_mode, device);
+            if (started) pthread_join(th, NULL);
+            continue;
+        }
         render_job_t *job = run_slice(&R, reads + off, n, batch_mode, device, &failed_now);
         n_failed += failed_now;
         if (job) { n_failed += render_slice(job); free(job); }
