@@ -31,13 +31,10 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_scratch.h"
+#include "sa_chain.h"
 
-#define SITE_CHUNK 4096   // records per block of k_site_accum
-
-// The table of a batch's ambiguity letters, shared by the site calls and the position calls.  Index i of job j names the letter
-// ref[i + tail]: tail k - 1 for the sites (k-mer indices, the k-mer's last letter), 0 for the positions (reference positions).
-struct SaSites {
+// The table of a batch's ambiguity letters, shared by the site calls and the position calls (sa_chain.h)
+struct SaAmbigTab {
     int n_alpha = 0, k = 0, stride = 0;                // stride: most letters of any kind in the batch
     long long n_sites = 0;
     std::vector<long long> site_off;                   // n_jobs + 1: job j's sites are [site_off[j], site_off[j + 1])
@@ -53,9 +50,8 @@ struct SaSites {
     int device = -1;
     size_t o_pre = 0, o_woff = 0, o_soff = 0, o_kind = 0, o_nl = 0, o_slot = 0;
 };
-struct SaPositions : SaSites {};
 
-static int ambig_tab_build(SaSites *S, const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, int tail) {
+static int ambig_tab_build(SaAmbigTab *S, const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, int tail) {
     S->n_alpha = m->n_alpha;
     S->k = m->k;
     int kind_of[256];
@@ -102,25 +98,25 @@ static int ambig_tab_build(SaSites *S, const sa_model_t *m, const sa_job_t *jobs
     return SA_OK;
 }
 
-int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaSites **out) {
+int sa_ambig_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, int tail, SaAmbigTab **out) {
     *out = nullptr;
-    SaSites *S = new (std::nothrow) SaSites();
+    SaAmbigTab *S = new (std::nothrow) SaAmbigTab();
     if (!S) return SA_ENOMEM;
-    const int rc = ambig_tab_build(S, m, jobs, n_jobs, ambig, m->k - 1);
+    const int rc = ambig_tab_build(S, m, jobs, n_jobs, ambig, tail);
     if (rc != SA_OK) { delete S; return rc; }
     *out = S;
     return SA_OK;
 }
 
-long long sa_sites_count(const SaSites *s) { return s ? s->n_sites : 0; }
-void sa_sites_release_device(SaSites *s) {
+long long sa_ambig_count(const SaAmbigTab *s) { return s ? s->n_sites : 0; }
+void sa_ambig_release_device(SaAmbigTab *s) {
     if (!s || !s->d) return;
     g_sa_pool.put(SaPool::DEVICE, s->d);
     s->d = nullptr;
     s->device = -1;
 }
-void sa_sites_free(SaSites *s) {
-    sa_sites_release_device(s);
+void sa_ambig_free(SaAmbigTab *s) {
+    sa_ambig_release_device(s);
     delete s;
 }
 
@@ -133,7 +129,7 @@ struct SiteTabs {
     const signed char *slot;
     int n_alpha, k, stride;
 };
-static SiteTabs sites_tabs(const SaSites *S) {
+static SiteTabs sites_tabs(const SaAmbigTab *S) {
     SiteTabs T;
     T.bits = (const unsigned long long *) S->d;
     T.pre = (const int *) (S->d + S->o_pre);
@@ -148,19 +144,21 @@ static SiteTabs sites_tabs(const SaSites *S) {
     return T;
 }
 
-static int sites_upload(SaSites *S, int device) {
+static int sites_upload(SaAmbigTab *S, int device) {
     if (S->d && S->device == device) return SA_OK;
-    sa_sites_release_device(S);
+    sa_ambig_release_device(S);
     const size_t nw = S->bits.size(), nj1 = S->word_off.size(), ns = (size_t) S->n_sites, nk = S->letters.size();
     std::vector<int> nl(nk);
     for (size_t kd = 0; kd < nk; kd++) nl[kd] = (int) S->letters[kd].size();
-    S->o_pre = sa_up256(8 * nw);
-    S->o_woff = sa_up256(S->o_pre + 4 * nw);
-    S->o_soff = sa_up256(S->o_woff + 8 * nj1);
-    S->o_kind = sa_up256(S->o_soff + 8 * nj1);
-    S->o_nl = sa_up256(S->o_kind + ns);
-    S->o_slot = sa_up256(S->o_nl + 4 * nk);
-    const size_t bytes = S->o_slot + S->slot.size() + 1;
+    SaLayout L;
+    L.add(8 * nw);   // (the bitmap, at 0)
+    S->o_pre = L.add(4 * nw);
+    S->o_woff = L.add(8 * nj1);
+    S->o_soff = L.add(8 * nj1);
+    S->o_kind = L.add(ns);
+    S->o_nl = L.add(4 * nk);
+    S->o_slot = L.add(S->slot.size() + 1);
+    const size_t bytes = L.end;
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &S->d, bytes, device) != hipSuccess) { S->d = nullptr; return SA_ENOMEM; }
     S->device = device;
     const struct { size_t off; const void *src; size_t n; } up[] = {
@@ -169,21 +167,16 @@ static int sites_upload(SaSites *S, int device) {
         {S->o_slot, S->slot.data(), S->slot.size()}};
     for (const auto &u : up)
         if (u.n && hipMemcpy(S->d + u.off, u.src, u.n, hipMemcpyHostToDevice) != hipSuccess) {
-            sa_sites_release_device(S);
+            sa_ambig_release_device(S);
             return SA_ENODEVICE;
         }
     return SA_OK;
 }
 
-struct SiteChunk {
-    long long first;   // first record of the chunk in the batch's device results
-    int n, job;
-};
-
 // units[site * stride + letter] += printed units of every record of the chunk that sits at a site
-__global__ __launch_bounds__(256) void k_site_accum(const sa_pair16_t *__restrict__ pairs, const SiteChunk *__restrict__ chunks,
+__global__ __launch_bounds__(256) void k_site_accum(const sa_pair16_t *__restrict__ pairs, const SaRecChunk *__restrict__ chunks,
                                                     SiteTabs T, unsigned long long *__restrict__ units) {
-    const SiteChunk C = chunks[blockIdx.x];
+    const SaRecChunk C = chunks[blockIdx.x];
     const long long w0 = T.word_off[C.job], w1 = T.word_off[C.job + 1];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
         const sa_pair16_t r = pairs[C.first + i];
@@ -224,29 +217,9 @@ __global__ __launch_bounds__(64) void k_site_final(SiteTabs T, const unsigned lo
     if (lane == 0) count[j] = kept;
 }
 
-// exclusive scan of count[0 .. n) into off[0 .. n], one block of 1024 threads: each thread sums a contiguous run of
-// ceil(n / 1024) counts, the run sums are scanned across the block (wave scans, then the waves' totals through LDS), and each
-// thread writes its run's offsets
-#define SITE_SCAN_THREADS 1024
-__global__ __launch_bounds__(SITE_SCAN_THREADS) void k_site_scan(const int *__restrict__ count, long long *__restrict__ off, int n) {
-    __shared__ long long wave_tot[SITE_SCAN_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int per = (n + SITE_SCAN_THREADS - 1) / SITE_SCAN_THREADS;
-    const int a = min(n, t * per), e = min(n, a + per);
-    long long mine = 0;
-    for (int i = a; i < e; i++) mine += count[i];
-    long long incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    long long before = 0;
-    for (int q = 0; q < wv; q++) before += wave_tot[q];
-    long long run = before + incl - mine;
-    for (int i = a; i < e; i++) { off[i] = run; run += count[i]; }
-    if (t == SITE_SCAN_THREADS - 1) off[n] = before + incl;   // (the last thread's inclusive sum is the total)
+// exclusive scan of count[0 .. n) into off[0 .. n], one block
+__global__ __launch_bounds__(SA_SCAN_THREADS) void k_site_scan(const int *__restrict__ count, long long *__restrict__ off, int n) {
+    sa_block_excl_scan([count](int i) { return (long long) count[i]; }, off, n);
 }
 
 // job blockIdx.x: its kept sites, in x order, from off[j] on -- site index, units and probabilities (stride per site)
@@ -282,22 +255,12 @@ __global__ __launch_bounds__(64) void k_site_compact(SiteTabs T, const unsigned 
 // back to it at the end of the call (sa_pool_release / the pool's bounds reach it)
 static SaScratch g_site_ws;
 
-#define SITECHK(call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
-            goto done;                                                                                      \
-        }                                                                                                   \
-    } while (0)
-
 extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
     (void) flags;
     if (!b || !calls_out || !n_out) return SA_EINVAL;
-    SaSites *S = nullptr;
+    SaAmbigTab *S = nullptr;
     int64_t nj64 = 0;
-    int rc = sa_batch_sites(b, &S, &nj64);
+    int rc = sa_batch_ambig(b, SA_TAB_SITES, &S, &nj64);
     if (rc) return rc;
     const size_t nj = (size_t) nj64;
     for (size_t j = 0; j < nj; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
@@ -311,41 +274,38 @@ extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t
     SaScratch &W = g_site_ws;
     std::unique_lock<std::mutex> guard(W.mu, std::defer_lock);
     if (ns > 0) {   // (a batch without sites -- a SA_FLAG_PAIRS8 one among them -- has nothing to read on the device)
-        const sa_pair16_t *d_pairs = nullptr;
-        std::vector<long long> first, count, n_events;
-        int device = 0;
-        if ((rc = sa_batch_device_view(b, &d_pairs, &first, &count, &n_events, &device)) != SA_OK) return rc;
-        std::vector<SiteChunk> chunks;
-        for (size_t j = 0; j < nj; j++)
-            for (long long c = 0; c < count[j]; c += SITE_CHUNK)
-                chunks.push_back(SiteChunk{first[j] + c, (int) std::min<long long>(SITE_CHUNK, count[j] - c), (int) j});
+        SaBatchView V;
+        if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
+        if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+        const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
+        const int device = V.device;
+        const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, SA_ORDINAL_PER_JOB);   // (ordinals unused)
         const size_t nc = chunks.size();
-        // device: [units | prob | chunks | count | off | out site | out units | out prob]
-        const size_t o_units = 0, o_prob = sa_up256(8 * ns * stride), o_chunks = sa_up256(o_prob + 8 * ns * stride),
-                     o_count = sa_up256(o_chunks + sizeof(SiteChunk) * (nc ? nc : 1)), o_off = sa_up256(o_count + 4 * nj),
-                     o_osite = sa_up256(o_off + 8 * (nj + 1)), o_ounits = sa_up256(o_osite + 4 * ns),
-                     o_oprob = o_ounits + 8 * ns * stride, dev_bytes = o_oprob + 8 * ns * stride;
+        SaLayout L;   // device: [units | prob | chunks | count | off | out site | out units | out prob]
+        const size_t o_units = L.add(8 * ns * stride), o_prob = L.add(8 * ns * stride), o_chunks = L.add(sizeof(SaRecChunk) * nc),
+                     o_count = L.add(4 * nj), o_off = L.add(8 * (nj + 1)), o_osite = L.add(4 * ns), o_ounits = L.add(8 * ns * stride),
+                     o_oprob = L.add(8 * ns * stride), dev_bytes = L.end;
         guard.lock();
         if ((rc = W.rebind(device)) != SA_OK || (rc = W.events()) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
         if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
         const SiteTabs T = sites_tabs(S);
         float kms = 0;
         size_t n_kept = 0, o_hunits = 0, o_hprob = 0;
-        if (nc) SITECHK(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SiteChunk) * nc, hipMemcpyHostToDevice, 0));
-        SITECHK(hipMemsetAsync(d + o_units, 0, 8 * ns * stride, 0));
-        SITECHK(hipEventRecord(W.e0, 0));
-        if (nc) hipLaunchKernelGGL(k_site_accum, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SiteChunk *) (d + o_chunks), T,
+        if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_units, 0, 8 * ns * stride, 0));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        if (nc) hipLaunchKernelGGL(k_site_accum, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
                                    (unsigned long long *) (d + o_units));
         hipLaunchKernelGGL(k_site_final, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
                            (double *) (d + o_prob), (int *) (d + o_count));
-        hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SITE_SCAN_THREADS), 0, 0, (const int *) (d + o_count), (long long *) (d + o_off), (int) nj);
+        hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const int *) (d + o_count), (long long *) (d + o_off), (int) nj);
         hipLaunchKernelGGL(k_site_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
                            (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_osite),
                            (unsigned long long *) (d + o_ounits), (double *) (d + o_oprob));
-        SITECHK(hipEventRecord(W.e1, 0));
-        SITECHK(hipGetLastError());
-        SITECHK(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
-        SITECHK(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
         if (kernel_ms_out) *kernel_ms_out = (double) kms;
         // only the kept calls cross PCIe
         n_kept = (size_t) h_off[nj];
@@ -357,10 +317,10 @@ extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t
             goto done;
         }
         if (n_kept) {
-            SITECHK(hipMemcpyAsync(h, d + o_osite, 4 * n_kept, hipMemcpyDeviceToHost, 0));
-            SITECHK(hipMemcpyAsync(h + o_hunits, d + o_ounits, 8 * n_kept * stride, hipMemcpyDeviceToHost, 0));
-            SITECHK(hipMemcpyAsync(h + o_hprob, d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost, 0));
-            SITECHK(hipStreamSynchronize(0));
+            SA_HIP_GOTO_DONE(hipMemcpyAsync(h, d + o_osite, 4 * n_kept, hipMemcpyDeviceToHost, 0));
+            SA_HIP_GOTO_DONE(hipMemcpyAsync(h + o_hunits, d + o_ounits, 8 * n_kept * stride, hipMemcpyDeviceToHost, 0));
+            SA_HIP_GOTO_DONE(hipMemcpyAsync(h + o_hprob, d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost, 0));
+            SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
         }
         h_site = (const int *) h;
         h_units = (const unsigned long long *) (h + o_hunits);
@@ -417,31 +377,6 @@ done:
 //                   serial fold, total and probabilities; per job the number of non-empty slots
 //   k_site_scan     those counts into output offsets
 //   k_pos_compact   one wave per job: the non-empty slots in position order
-#define POS_MAX_K 32
-
-int sa_positions_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaPositions **out) {
-    *out = nullptr;
-    if (m->k > POS_MAX_K) return SA_EUNSUPPORTED;
-    SaPositions *P = new (std::nothrow) SaPositions();
-    if (!P) return SA_ENOMEM;
-    const int rc = ambig_tab_build(P, m, jobs, n_jobs, ambig, 0);
-    if (rc != SA_OK) { delete P; return rc; }
-    *out = P;
-    return SA_OK;
-}
-
-void sa_positions_release_device(SaPositions *s) { sa_sites_release_device(s); }
-void sa_positions_free(SaPositions *s) {
-    sa_sites_release_device(s);
-    delete s;
-}
-
-struct PosChunk {
-    long long first;   // first record of the chunk in the batch's device results
-    long long local;   // its ordinal inside the job
-    int n, job;
-};
-
 // the digits of kmer_id, first letter first
 __device__ static inline void pos_digits(unsigned id, int n_alpha, int k, unsigned char *dig) {
     for (int i = k - 1; i >= 0; i--) {
@@ -450,9 +385,29 @@ __device__ static inline void pos_digits(unsigned id, int n_alpha, int k, unsign
     }
 }
 
-__global__ __launch_bounds__(256) void k_pos_count(const sa_pair16_t *__restrict__ pairs, const PosChunk *__restrict__ chunks, SiteTabs T,
+// fn(slot, l) for every ambiguous position p = x + d (d ascending) that record r of a job with bitmap words [w0, w1) covers and
+// whose letter in r's path k-mer is letter l of the position's kind; the k-mer's digits are made at the first such position
+template <class F>
+__device__ __forceinline__ void pos_for_each_covered(const SiteTabs &T, long long w0, long long w1, const sa_pair16_t &r, F fn) {
+    const int x = (int) (r.a & 0xfffffffull);
+    unsigned char dig[SA_POS_MAX_K];
+    bool have = false;
+    for (int d = 0; d < T.k; d++) {
+        const long long p = (long long) x + d, w = w0 + (p >> 6);
+        if (w >= w1) break;   // (past the job's reference: cannot happen for a record of its matrix)
+        const unsigned long long word = T.bits[w];
+        if (!((word >> (p & 63)) & 1ull)) continue;
+        if (!have) { pos_digits((unsigned) (r.b & 0xffffffffull), T.n_alpha, T.k, dig); have = true; }
+        const int slot = T.pre[w] + __popcll(word & ((1ull << (p & 63)) - 1ull));
+        const int l = T.slot[(int) T.kind[slot] * T.n_alpha + (int) dig[d]];
+        if (l < 0) continue;
+        fn(slot, l);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pos_count(const sa_pair16_t *__restrict__ pairs, const SaRecChunk *__restrict__ chunks, SiteTabs T,
                                                    unsigned *__restrict__ cnt, int *__restrict__ xmin, int *__restrict__ xmax) {
-    const PosChunk C = chunks[blockIdx.x];
+    const SaRecChunk C = chunks[blockIdx.x];
     const long long w0 = T.word_off[C.job], w1 = T.word_off[C.job + 1];
     int lo = INT_MAX, hi = -1;
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
@@ -460,18 +415,7 @@ __global__ __launch_bounds__(256) void k_pos_count(const sa_pair16_t *__restrict
         const int x = (int) (r.a & 0xfffffffull);
         lo = min(lo, x);
         hi = max(hi, x);
-        unsigned char dig[POS_MAX_K];
-        bool have = false;
-        for (int d = 0; d < T.k; d++) {
-            const long long p = (long long) x + d, w = w0 + (p >> 6);
-            if (w >= w1) break;   // (past the job's reference: cannot happen for a record of its matrix)
-            const unsigned long long word = T.bits[w];
-            if (!((word >> (p & 63)) & 1ull)) continue;
-            if (!have) { pos_digits((unsigned) (r.b & 0xffffffffull), T.n_alpha, T.k, dig); have = true; }
-            const int slot = T.pre[w] + __popcll(word & ((1ull << (p & 63)) - 1ull));
-            if (T.slot[(int) T.kind[slot] * T.n_alpha + (int) dig[d]] < 0) continue;
-            atomicAdd(&cnt[slot], 1u);
-        }
+        pos_for_each_covered(T, w0, w1, r, [&](int slot, int) { atomicAdd(&cnt[slot], 1u); });
     }
     for (int o = 32; o > 0; o >>= 1) {
         lo = min(lo, __shfl_xor(lo, o));
@@ -492,40 +436,25 @@ __global__ __launch_bounds__(64) void k_pos_job_scan(SiteTabs T, const unsigned 
     for (long long base = s0; base < s1; base += 64) {
         const long long s = base + lane;
         const unsigned v = s < s1 ? cnt[s] : 0u;
-        unsigned incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
+        const unsigned incl = sa_wave_incl_scan(v, lane);
         if (s < s1) loc[s] = carry + incl - v;
         carry += __shfl(incl, 63);
     }
     if (lane == 0) tot[j] = (int) carry;
 }
 
-__global__ __launch_bounds__(256) void k_pos_scatter(const sa_pair16_t *__restrict__ pairs, const PosChunk *__restrict__ chunks, SiteTabs T,
+__global__ __launch_bounds__(256) void k_pos_scatter(const sa_pair16_t *__restrict__ pairs, const SaRecChunk *__restrict__ chunks, SiteTabs T,
                                                      const unsigned *__restrict__ loc, const long long *__restrict__ base,
                                                      unsigned *__restrict__ fill, unsigned long long *__restrict__ ent) {
-    const PosChunk C = chunks[blockIdx.x];
+    const SaRecChunk C = chunks[blockIdx.x];
     const long long w0 = T.word_off[C.job], w1 = T.word_off[C.job + 1], b0 = base[C.job];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
         const sa_pair16_t r = pairs[C.first + i];
-        const int x = (int) (r.a & 0xfffffffull);
-        unsigned char dig[POS_MAX_K];
-        bool have = false;
-        for (int d = 0; d < T.k; d++) {
-            const long long p = (long long) x + d, w = w0 + (p >> 6);
-            if (w >= w1) break;
-            const unsigned long long word = T.bits[w];
-            if (!((word >> (p & 63)) & 1ull)) continue;
-            if (!have) { pos_digits((unsigned) (r.b & 0xffffffffull), T.n_alpha, T.k, dig); have = true; }
-            const int slot = T.pre[w] + __popcll(word & ((1ull << (p & 63)) - 1ull));
-            const int l = T.slot[(int) T.kind[slot] * T.n_alpha + (int) dig[d]];
-            if (l < 0) continue;
+        pos_for_each_covered(T, w0, w1, r, [&](int slot, int l) {
             const unsigned long long units = (unsigned long long) sa_printed_units((long long) ((r.b >> 32) & 0xffffffull));
             const unsigned q = atomicAdd(&fill[slot], 1u);
             ent[b0 + (long long) loc[slot] + q] = ((unsigned long long) (C.local + i) << 24) | ((unsigned long long) l << 20) | units;
-        }
+        });
     }
 }
 
@@ -605,34 +534,34 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
                                        int32_t *x_min_out, int32_t *x_max_out, double *kernel_ms_out) {
     (void) flags;
     if (!b || !calls_out || !n_out) return SA_EINVAL;
-    SaPositions *P = nullptr;
+    SaAmbigTab *P = nullptr;
     int64_t nj64 = 0;
-    int rc = sa_batch_positions(b, &P, &nj64);
+    int rc = sa_batch_ambig(b, SA_TAB_POSITIONS, &P, &nj64);
     if (rc) return rc;
     const size_t nj = (size_t) nj64;
     for (size_t j = 0; j < nj; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
     if (kernel_ms_out) *kernel_ms_out = 0.0;
     if (nj == 0) return SA_OK;
     const size_t stride = (size_t) (P->stride > 0 ? P->stride : 1), ns = (size_t) P->n_sites;
-    const sa_pair16_t *d_pairs = nullptr;
-    std::vector<long long> first, count, n_events;
-    int device = 0;
-    if ((rc = sa_batch_device_view(b, &d_pairs, &first, &count, &n_events, &device)) != SA_OK) return rc;
-    std::vector<PosChunk> chunks;
+    SaBatchView V;
+    if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
+    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+    const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
+    const int device = V.device;
+    const std::vector<long long> &count = V.count;
     for (size_t j = 0; j < nj; j++)   // (a job's bucket entries, at most k per record, are counted in 32 bits)
         if ((long long) P->k * count[j] >= (long long) INT32_MAX) return SA_EUNSUPPORTED;
-    for (size_t j = 0; j < nj; j++)
-        for (long long c = 0; c < count[j]; c += SITE_CHUNK)
-            chunks.push_back(PosChunk{first[j] + c, c, (int) std::min<long long>(SITE_CHUNK, count[j] - c), (int) j});
+    const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, SA_ORDINAL_PER_JOB);
     const size_t nc = chunks.size(), ns1 = ns ? ns : 1;
-    // device: [cnt | fill | loc | sum | prob | chunks | tot | base | kept | off | xmin | xmax | out slot | out n | out sum |
-    // out prob]; the entries in a block of their own, sized once the counts are known
-    const size_t o_cnt = 0, o_fill = sa_up256(4 * ns1), o_loc = sa_up256(o_fill + 4 * ns1), o_sum = sa_up256(o_loc + 4 * ns1),
-                 o_prob = sa_up256(o_sum + 8 * ns1 * stride), o_chunks = sa_up256(o_prob + 8 * ns1 * stride),
-                 o_tot = sa_up256(o_chunks + sizeof(PosChunk) * (nc ? nc : 1)), o_base = sa_up256(o_tot + 4 * nj),
-                 o_kept = sa_up256(o_base + 8 * (nj + 1)), o_off = sa_up256(o_kept + 4 * nj), o_xmin = sa_up256(o_off + 8 * (nj + 1)),
-                 o_xmax = sa_up256(o_xmin + 4 * nj), o_oslot = sa_up256(o_xmax + 4 * nj), o_on = sa_up256(o_oslot + 4 * ns1),
-                 o_osum = sa_up256(o_on + 4 * ns1), o_oprob = o_osum + 8 * ns1 * stride, dev_bytes = o_oprob + 8 * ns1 * stride;
+    // device: [cnt, fill | loc | sum | prob | chunks | tot | base | kept | off | xmin | xmax | out slot | out n | out sum |
+    // out prob]; cnt and fill are one entry (one memset clears both); the entries in a block of their own, sized once the
+    // counts are known
+    SaLayout L;
+    const size_t o_cnt = L.add(2 * 4 * ns1), o_fill = o_cnt + 4 * ns1, o_loc = L.add(4 * ns1), o_sum = L.add(8 * ns1 * stride),
+                 o_prob = L.add(8 * ns1 * stride), o_chunks = L.add(sizeof(SaRecChunk) * nc), o_tot = L.add(4 * nj),
+                 o_base = L.add(8 * (nj + 1)), o_kept = L.add(4 * nj), o_off = L.add(8 * (nj + 1)), o_xmin = L.add(4 * nj),
+                 o_xmax = L.add(4 * nj), o_oslot = L.add(4 * ns1), o_on = L.add(4 * ns1), o_osum = L.add(8 * ns1 * stride),
+                 o_oprob = L.add(8 * ns1 * stride), dev_bytes = L.end;
     std::vector<long long> h_base(nj + 1, 0), h_off(nj + 1, 0);
     std::vector<int> h_xmin(nj), h_xmax(nj);
     std::vector<int> h_slot;
@@ -648,20 +577,20 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
     if ((rc = W.rebind(device)) != SA_OK || (rc = W.events()) != SA_OK || (rc = sites_upload(P, device)) != SA_OK) return rc;
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
     T = sites_tabs(P);
-    if (nc) SITECHK(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(PosChunk) * nc, hipMemcpyHostToDevice, 0));
-    SITECHK(hipMemsetAsync(d + o_cnt, 0, o_loc, 0));   // (cnt and fill)
-    SITECHK(hipMemsetAsync(d + o_xmin, 0x7f, 4 * nj, 0));
-    SITECHK(hipMemsetAsync(d + o_xmax, 0xff, 4 * nj, 0));
-    SITECHK(hipEventRecord(W.e0, 0));
-    if (nc) hipLaunchKernelGGL(k_pos_count, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const PosChunk *) (d + o_chunks), T,
+    if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
+    SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_cnt, 0, 2 * 4 * ns1, 0));   // (cnt and fill)
+    SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_xmin, 0x7f, 4 * nj, 0));
+    SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_xmax, 0xff, 4 * nj, 0));
+    SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+    if (nc) hipLaunchKernelGGL(k_pos_count, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
                                (unsigned *) (d + o_cnt), (int *) (d + o_xmin), (int *) (d + o_xmax));
     hipLaunchKernelGGL(k_pos_job_scan, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned *) (d + o_cnt), (unsigned *) (d + o_loc),
                        (int *) (d + o_tot));
-    hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SITE_SCAN_THREADS), 0, 0, (const int *) (d + o_tot), (long long *) (d + o_base), (int) nj);
-    SITECHK(hipEventRecord(W.e1, 0));
-    SITECHK(hipGetLastError());
-    SITECHK(hipMemcpy(h_base.data(), d + o_base, 8 * (nj + 1), hipMemcpyDeviceToHost));
-    SITECHK(hipEventElapsedTime(&kms0, W.e0, W.e1));
+    hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const int *) (d + o_tot), (long long *) (d + o_base), (int) nj);
+    SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+    SA_HIP_GOTO_DONE(hipGetLastError());
+    SA_HIP_GOTO_DONE(hipMemcpy(h_base.data(), d + o_base, 8 * (nj + 1), hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms0, W.e0, W.e1));
     {   // the buckets: 8 bytes per (record, covered ambiguous position)
         const size_t n_ent = (size_t) h_base[nj];
         if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_ent, 8 * (n_ent ? n_ent : 1), device) != hipSuccess) {
@@ -670,32 +599,32 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
             goto done;
         }
     }
-    SITECHK(hipEventRecord(W.e0, 0));
-    if (nc) hipLaunchKernelGGL(k_pos_scatter, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const PosChunk *) (d + o_chunks), T,
+    SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+    if (nc) hipLaunchKernelGGL(k_pos_scatter, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
                                (const unsigned *) (d + o_loc), (const long long *) (d + o_base), (unsigned *) (d + o_fill), d_ent);
     hipLaunchKernelGGL(k_pos_fold, dim3((unsigned) nj), dim3(256), 0, 0, T, (const unsigned *) (d + o_cnt), (const unsigned *) (d + o_loc),
                        (const long long *) (d + o_base), d_ent, (double *) (d + o_sum), (double *) (d + o_prob), (int *) (d + o_kept));
-    hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SITE_SCAN_THREADS), 0, 0, (const int *) (d + o_kept), (long long *) (d + o_off), (int) nj);
+    hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const int *) (d + o_kept), (long long *) (d + o_off), (int) nj);
     hipLaunchKernelGGL(k_pos_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned *) (d + o_cnt), (const double *) (d + o_sum),
                        (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_oslot), (unsigned *) (d + o_on),
                        (double *) (d + o_osum), (double *) (d + o_oprob));
-    SITECHK(hipEventRecord(W.e1, 0));
-    SITECHK(hipGetLastError());
-    SITECHK(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
-    SITECHK(hipEventElapsedTime(&kms1, W.e0, W.e1));
+    SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+    SA_HIP_GOTO_DONE(hipGetLastError());
+    SA_HIP_GOTO_DONE(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms1, W.e0, W.e1));
     if (kernel_ms_out) *kernel_ms_out = (double) kms0 + (double) kms1;
     n_kept = (size_t) h_off[nj];
-    SITECHK(hipMemcpy(h_xmin.data(), d + o_xmin, 4 * nj, hipMemcpyDeviceToHost));
-    SITECHK(hipMemcpy(h_xmax.data(), d + o_xmax, 4 * nj, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipMemcpy(h_xmin.data(), d + o_xmin, 4 * nj, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipMemcpy(h_xmax.data(), d + o_xmax, 4 * nj, hipMemcpyDeviceToHost));
     if (n_kept) {   // only the kept positions cross PCIe
         h_slot.resize(n_kept);
         h_cnt.resize(n_kept);
         h_sum.resize(n_kept * stride);
         h_prob.resize(n_kept * stride);
-        SITECHK(hipMemcpy(h_slot.data(), d + o_oslot, 4 * n_kept, hipMemcpyDeviceToHost));
-        SITECHK(hipMemcpy(h_cnt.data(), d + o_on, 4 * n_kept, hipMemcpyDeviceToHost));
-        SITECHK(hipMemcpy(h_sum.data(), d + o_osum, 8 * n_kept * stride, hipMemcpyDeviceToHost));
-        SITECHK(hipMemcpy(h_prob.data(), d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_slot.data(), d + o_oslot, 4 * n_kept, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_cnt.data(), d + o_on, 4 * n_kept, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_sum.data(), d + o_osum, 8 * n_kept * stride, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_prob.data(), d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost));
     }
     for (size_t j = 0; j < nj; j++) {
         const bool any = count[j] > 0;

@@ -36,7 +36,7 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_scratch.h"
+#include "sa_chain.h"
 
 struct DetJob {
     long long raw_off;   // samples (int16) into the raw image, a multiple of 8; also the offset of t1 / t2 / peaks
@@ -236,16 +236,6 @@ __global__ __launch_bounds__(256) void k_det_events(const DetJob *__restrict__ j
     }
 }
 
-#define DETCHK(call)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
-            goto done;                                                                                      \
-        }                                                                                                   \
-    } while (0)
-
 // Device and pinned-host scratch of sa_detect_events_batch, kept between calls (sa_scratch.h).
 struct DetWorkspace : SaScratch {
     void *d_ws = nullptr, *d_ev = nullptr, *h_raw = nullptr, *h_ev = nullptr;
@@ -333,10 +323,10 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         float *d_t1 = (float *) (d + o_t1), *d_t2 = (float *) (d + o_t2);
         int *d_pk = (int *) (d + o_pk), *d_cnt = (int *) (d + o_cnt);
         long long *d_off = (long long *) (d + o_off);
-        DETCHK(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(DetJob) * nj, hipMemcpyHostToDevice, 0));
-        DETCHK(hipMemcpyAsync(d + o_blk, blk.data(), sizeof(int2) * blk.size(), hipMemcpyHostToDevice, 0));
-        DETCHK(hipMemcpyAsync(d + o_raw, W.h_raw, raw_bytes, hipMemcpyHostToDevice, 0));
-        DETCHK(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(DetJob) * nj, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_blk, blk.data(), sizeof(int2) * blk.size(), hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_raw, W.h_raw, raw_bytes, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
         const unsigned lane_blocks = (unsigned) ((nj + DET_LANES - 1) / DET_LANES);
         hipLaunchKernelGGL(k_det_prefix, dim3(lane_blocks), dim3(DET_LANES), 0, 0, d_jobs, (int) nj, (const int16_t *) (d + o_raw), d_s, d_q);
         hipLaunchKernelGGL(k_det_tstat, dim3((unsigned) blk.size()), dim3(256), 0, 0, d_jobs, (const int2 *) (d + o_blk), d_s, d_q, d_t1,
@@ -346,17 +336,17 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, 0, d_cnt, (int) nj, d_off);
         hipLaunchKernelGGL(k_det_events, dim3((unsigned) nj), dim3(256), 0, 0, d_jobs, (const int *) d_pk, (const int *) d_cnt,
                            (const long long *) d_off, (const double *) d_s, (const double *) d_q, (DetEvent *) W.d_ev);
-        DETCHK(hipEventRecord(W.e1, 0));
-        DETCHK(hipGetLastError());
-        DETCHK(hipMemcpyAsync(W.h_raw, d + o_cnt, res_bytes, hipMemcpyDeviceToHost, 0));   // the raw image is uploaded by now
-        DETCHK(hipStreamSynchronize(0));
-        DETCHK(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_raw, d + o_cnt, res_bytes, hipMemcpyDeviceToHost, 0));   // the raw image is uploaded by now
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
         h_cnt = (const int *) W.h_raw;
         h_off = (const long long *) ((const char *) W.h_raw + (o_off - o_cnt));
         n_ev_tot = h_off[nj];
         if ((rc = W.pin(&W.h_ev, &W.h_ev_cap, sizeof(DetEvent) * (size_t) n_ev_tot, device)) != SA_OK) goto done;
-        DETCHK(hipMemcpyAsync(W.h_ev, W.d_ev, sizeof(DetEvent) * (size_t) n_ev_tot, hipMemcpyDeviceToHost, 0));
-        DETCHK(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_ev, W.d_ev, sizeof(DetEvent) * (size_t) n_ev_tot, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
     h_ev = (const DetEvent *) W.h_ev;

@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_scratch.h"
+#include "sa_chain.h"
 
 #define EA_BW 100
 #define EA_HALF 50
@@ -390,16 +390,6 @@ int sa_ea_kmer_ids(const sa_model_t *m, const char *seq, int64_t n_kmers, bool r
     return ea_kmer_ids(m, seq, n_kmers, rna, out);
 }
 
-#define EACHK(call)                                                                                         \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
-            goto done;                                                                                      \
-        }                                                                                                   \
-    } while (0)
-
 extern "C" int sa_scalings_mom(const sa_model_t *m, const char *sequence, int64_t seq_len, const double *event_mean,
                                int64_t n_events, unsigned flags, double *shift_out, double *scale_out) {
     if (!m || !sequence || !event_mean || !shift_out || !scale_out) return SA_EINVAL;
@@ -547,12 +537,12 @@ extern "C" int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs
     if ((rc = W.events()) != SA_OK) goto done;
     {
         char *d = (char *) W.d_ws;
-        EACHK(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(EaJob) * nj, hipMemcpyHostToDevice, 0));
-        EACHK(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(EaJob) * nj, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
         P.jobs = (EaJob *) (d + o_jobs); P.ev = (double *) (d + o_in); P.kc = (double *) (d + o_kc);
         P.trace = (unsigned char *) W.d_trace; P.ll = (int *) (d + o_ll); P.col = (double *) (d + o_col);
         P.out = (int *) (d + o_out); P.n_out = (int *) (d + o_res); P.status = P.n_out + nj; P.fills = P.status + nj;
-        EACHK(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
         {
             const long long n_pos = (long long) (kc_tot / 3);
             const double *d_kt = P.ev + ev_tot;
@@ -563,11 +553,11 @@ extern "C" int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs
             hipLaunchKernelGGL(k_event_align<true>, dim3((unsigned) n_jobs), dim3(EA_THREADS), 0, 0, P, (int) n_jobs);
         else
             hipLaunchKernelGGL(k_event_align<false>, dim3((unsigned) n_jobs), dim3(EA_THREADS), 0, 0, P, (int) n_jobs);
-        EACHK(hipEventRecord(W.e1, 0));
-        EACHK(hipGetLastError());
-        EACHK(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
-        EACHK(hipStreamSynchronize(0));
-        EACHK(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
     h_out = (const int *) W.h_res;

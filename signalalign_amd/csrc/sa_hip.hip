@@ -35,7 +35,7 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_scratch.h"
+#include "sa_chain.h"
 
 #define NEG_INF (-__builtin_inf())
 
@@ -1301,8 +1301,7 @@ struct sa_batch {
     long long *d_vc_off = nullptr, *d_seg_all = nullptr;
     std::vector<unsigned long long> h_vc_bits;  // (the same on the host, for SA_FLAG_EXACT's host finalisation)
     std::vector<long long> h_vc_off, job_all_n, job_all_sum;
-    SaSites *sites = nullptr;                   // SA_FLAG_SITE_CALLS: the batch's sites (sa_calls.hip)
-    SaPositions *positions = nullptr;           // SA_FLAG_POSITION_CALLS: the batch's ambiguous positions (sa_calls.hip)
+    SaAmbigTab *ambig_tab[SA_TAB_N] = {};       // SA_FLAG_SITE_CALLS / SA_FLAG_POSITION_CALLS: the batch's sites / ambiguous positions
     bool plan_hdp = false;                      // the batch's model holds an HDP
     unsigned hdp_hot = 0xffffffffu;             // DevModel.hdp_hot
     char *d_seam = nullptr;      // their seam storage: per wave two arrays of seam_cap records of 16 bytes
@@ -1336,8 +1335,8 @@ struct sa_batch {
     long long h_pairs_cap = 0, n_pairs_total = 0;
     std::vector<long long> job_off;
     std::vector<long long> job_dev_off;   // where a job's pairs start in d_out (device finalisation only)
-    sa_pair16_t *d_pairs_up = nullptr;    // host-finalised pairs uploaded for a downstream device step (sa_batch_mea)
-    long long d_pairs_up_cap = 0;
+    void *d_pairs_up = nullptr;           // host-finalised records uploaded for a downstream device step (sa_batch_view)
+    size_t d_pairs_up_cap = 0;            // bytes
     bool ran = false;
     bool quiet = false;          // the last run returned SA_OK: it waited for everything it had queued, the batch's streams are idle
     bool dev_planned = false;    // the plan was built on the device (sa_dplan.inc): its big arrays exist in HBM only
@@ -1784,8 +1783,7 @@ void sa_batch_destroy(sa_batch_t *b) {
     g_sa_pool.put(SaPool::DEVICE, b->d_pairs_up);
     g_sa_pool.put(SaPool::PINNED, b->h_seg_off);
     g_sa_pool.put(SaPool::PINNED, b->h_overflow);
-    sa_sites_free(b->sites);
-    sa_positions_free(b->positions);
+    for (SaAmbigTab *tab : b->ambig_tab) sa_ambig_free(tab);
     const double td2 = now_ms();
     sa_plan_free(b->plan);
     delete b;
@@ -1873,19 +1871,18 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
         const double v_ = atof(ets);
         if (v_ > 0.0) b->spec_slack = v_;
     }
-    if (flags & SA_FLAG_SITE_CALLS) {   // the sites of every job: one pass over its reference (sa_calls.hip)
-        const int rcs = n_jobs > 0 && !jobs ? SA_EINVAL : sa_sites_build(m, jobs, n_jobs, ambig, &b->sites);
-        // (an 8-byte record names no k-mer: such a batch may hold no site)
-        if (rcs || ((flags & SA_FLAG_PAIRS8) && sa_sites_count(b->sites) > 0)) {
-            sa_batch_destroy(b);
-            return rcs ? rcs : SA_EUNSUPPORTED;
+    if (flags & (SA_FLAG_SITE_CALLS | SA_FLAG_POSITION_CALLS)) {   // every job's sites / ambiguous positions: one pass over its reference each
+        int rct = n_jobs > 0 && !jobs ? SA_EINVAL : SA_OK;
+        if (!rct && (flags & SA_FLAG_SITE_CALLS)) {
+            rct = sa_ambig_build(m, jobs, n_jobs, ambig, m->k - 1, &b->ambig_tab[SA_TAB_SITES]);
+            // (an 8-byte record names no k-mer: such a batch may hold no site)
+            if (!rct && (flags & SA_FLAG_PAIRS8) && sa_ambig_count(b->ambig_tab[SA_TAB_SITES]) > 0) rct = SA_EUNSUPPORTED;
         }
-    }
-    if (flags & SA_FLAG_POSITION_CALLS) {   // every job's ambiguous positions: one pass over its reference (sa_calls.hip)
-        const int rcp = n_jobs > 0 && !jobs ? SA_EINVAL : sa_positions_build(m, jobs, n_jobs, ambig, &b->positions);
-        if (rcp) {
+        if (!rct && (flags & SA_FLAG_POSITION_CALLS))
+            rct = m->k > SA_POS_MAX_K ? SA_EUNSUPPORTED : sa_ambig_build(m, jobs, n_jobs, ambig, 0, &b->ambig_tab[SA_TAB_POSITIONS]);
+        if (rct) {
             sa_batch_destroy(b);
-            return rcp;
+            return rct;
         }
     }
 #define TRY(x) do { int rc_ = (x); if (rc_) { sa_batch_destroy(b); return rc_; } } while (0)
@@ -3019,86 +3016,41 @@ static int batch_run_body(sa_batch_t *b) {
     return SA_OK;
 }
 
-// Device-side view of the results for a downstream device step (sa_mea.hip): per job the first pair in *pairs and the
-// number of pairs and of events.  After host finalisation (SA_FLAG_EXACT) the pairs are uploaded once.
-int sa_batch_device_view(sa_batch_t *b, const sa_pair16_t **pairs, std::vector<long long> *first, std::vector<long long> *count,
-                         std::vector<long long> *n_events, int *device) {
-    if (!b || !pairs || !first || !count || !n_events || !device) return SA_EINVAL;
-    // (8-byte records name neither path nor k-mer, and a batch filtered for the variant-caller output holds only the rows of X positions:
-    // nothing a downstream device step -- the MEA path over ALL posteriors -- may read)
-    if (!b->ran || b->p8 || (b->flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;
+// The records of a finished batch for a step chained onto it (sa_chain.h): where the run left them in d_out, or -- after host
+// finalisation (SA_FLAG_EXACT) or sa_batch_release_device -- uploaded again from h_pairs into d_pairs_up.
+int sa_batch_view(sa_batch_t *b, SaBatchView *v) {
+    if (!b || !v) return SA_EINVAL;
+    v->p8 = b->p8;
+    v->batch_flags = b->flags;
+    v->device = b->device;
+    if (!b->ran) return SA_ESTATE;
     const sa_plan_t *pl = b->plan;
     const size_t nj = (size_t) pl->n_jobs;
-    first->assign(nj, 0); count->assign(nj, 0); n_events->assign(nj, 0);
+    const bool resident = b->job_dev_off.size() == nj && !b->released;
+    v->first.assign(nj, 0); v->count.assign(nj, 0); v->n_events.assign(nj, 0);
     for (size_t j = 0; j < nj; j++) {
-        (*count)[j] = b->job_off[j + 1] - b->job_off[j];
-        (*n_events)[j] = pl->jobs[j].n_events;
+        v->first[j] = resident ? b->job_dev_off[j] : b->job_off[j];
+        v->count[j] = b->job_off[j + 1] - b->job_off[j];
+        v->n_events[j] = pl->jobs[j].n_events;
     }
-    *device = b->device;
     HIPCHK(hipSetDevice(b->device));
-    if (b->job_dev_off.size() == nj && !b->released) {
-        *pairs = b->d_out;
-        for (size_t j = 0; j < nj; j++) (*first)[j] = b->job_dev_off[j];
-        return SA_OK;
-    }
-    if (b->n_pairs_total > b->d_pairs_up_cap) {
+    if (resident) { v->recs = b->d_out; return SA_OK; }
+    const size_t bytes = b->rec() * (size_t) b->n_pairs_total;
+    if (bytes > b->d_pairs_up_cap) {
         g_sa_pool.put(SaPool::DEVICE, b->d_pairs_up);
         b->d_pairs_up = nullptr; b->d_pairs_up_cap = 0;
-        HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_pairs_up, sizeof(sa_pair16_t) * (size_t) b->n_pairs_total, b->device));
-        b->d_pairs_up_cap = b->n_pairs_total;
+        HIPCHK(g_sa_pool.get(SaPool::DEVICE, &b->d_pairs_up, bytes, b->device));
+        b->d_pairs_up_cap = bytes;
     }
-    if (b->n_pairs_total)
-        HIPCHK(hipMemcpy(b->d_pairs_up, b->h_pairs, sizeof(sa_pair16_t) * (size_t) b->n_pairs_total, hipMemcpyHostToDevice));
-    *pairs = b->d_pairs_up;
-    for (size_t j = 0; j < nj; j++) (*first)[j] = b->job_off[j];
+    if (bytes) HIPCHK(hipMemcpy(b->d_pairs_up, b->h_pairs, bytes, hipMemcpyHostToDevice));
+    v->recs = b->d_pairs_up;
     return SA_OK;
 }
 
-// The same for a step that reads either record size (sa_train.hip): *p8 says which.  Per job the first record in *recs (in
-// records of that size) and the number of records; a SA_FLAG_VC_ROWS batch is SA_EINVAL (it dropped rows), one that has not
-// run SA_ESTATE.
-int sa_batch_device_records(sa_batch_t *b, const void **recs, bool *p8, std::vector<long long> *first, std::vector<long long> *count,
-                            int *device) {
-    if (!b || !recs || !p8 || !first || !count || !device) return SA_EINVAL;
-    if (b->flags & SA_FLAG_VC_ROWS) return SA_EINVAL;
-    if (!b->ran || b->expect) return SA_ESTATE;
-    const size_t nj = (size_t) b->c_n;
-    first->assign(nj, 0); count->assign(nj, 0);
-    for (size_t j = 0; j < nj; j++) (*count)[j] = b->job_off[j + 1] - b->job_off[j];
-    *p8 = b->p8;
-    *device = b->device;
-    HIPCHK(hipSetDevice(b->device));
-    if (b->job_dev_off.size() == nj && !b->released) {
-        *recs = b->d_out;
-        for (size_t j = 0; j < nj; j++) (*first)[j] = b->job_dev_off[j];
-        return SA_OK;
-    }
-    // host-finalised or released: the records go up again, into a block counted in 16-byte records
-    const long long bytes = (long long) b->rec() * b->n_pairs_total, need16 = (bytes + 15) / 16;
-    if (need16 > b->d_pairs_up_cap) {
-        g_sa_pool.put(SaPool::DEVICE, b->d_pairs_up);
-        b->d_pairs_up = nullptr; b->d_pairs_up_cap = 0;
-        HIPCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &b->d_pairs_up, sizeof(sa_pair16_t) * (size_t) need16, b->device));
-        b->d_pairs_up_cap = need16;
-    }
-    if (bytes) HIPCHK(hipMemcpy(b->d_pairs_up, b->h_pairs, (size_t) bytes, hipMemcpyHostToDevice));
-    *recs = b->d_pairs_up;
-    for (size_t j = 0; j < nj; j++) (*first)[j] = b->job_off[j];
-    return SA_OK;
-}
-
-int sa_batch_sites(sa_batch_t *b, SaSites **sites, int64_t *n_jobs) {
-    if (!b || !sites || !n_jobs) return SA_EINVAL;
-    if (!b->sites || !b->ran) return SA_ESTATE;
-    *sites = b->sites;
-    *n_jobs = b->c_n;
-    return SA_OK;
-}
-
-int sa_batch_positions(sa_batch_t *b, SaPositions **positions, int64_t *n_jobs) {
-    if (!b || !positions || !n_jobs) return SA_EINVAL;
-    if (!b->positions || !b->ran) return SA_ESTATE;
-    *positions = b->positions;
+int sa_batch_ambig(sa_batch_t *b, int which, SaAmbigTab **tab, int64_t *n_jobs) {
+    if (!b || !tab || !n_jobs || which < 0 || which >= SA_TAB_N) return SA_EINVAL;
+    if (!b->ambig_tab[which] || !b->ran) return SA_ESTATE;
+    *tab = b->ambig_tab[which];
     *n_jobs = b->c_n;
     return SA_OK;
 }
@@ -3132,8 +3084,7 @@ int sa_batch_release_device(sa_batch_t *b) {
     if (b->pair_stream) HIPCHK(sa_sync_stream(b->pair_stream, b->device));
     b->put_blocks(0, sa_batch::BLK_END);
     if (b->held_stage) { g_sa_pool.put(SaPool::PINNED, b->held_stage); b->held_stage = nullptr; }
-    sa_sites_release_device(b->sites);
-    sa_positions_release_device(b->positions);
+    for (SaAmbigTab *tab : b->ambig_tab) sa_ambig_release_device(tab);
     b->released = true;
     return SA_OK;
 }

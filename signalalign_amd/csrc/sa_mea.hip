@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_scratch.h"
+#include "sa_chain.h"
 
 #define MEA_FRONT_CAP 256     // entries per LDS front (2 fronts x 16 bytes x 256 = 8 KB per wave)
 #define MEA_ST_OVERFLOW 100   // internal: front outgrew LDS, the read is re-run with global fronts
@@ -582,16 +582,6 @@ extern "C" void sa_mea_release(void) {
     mea_chain_release();
 }
 
-#define MEACHK(call)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
-            goto done;                                                                                      \
-        }                                                                                                   \
-    } while (0)
-
 // Three tiers of the same algorithm: fronts in registers (64 edges), in LDS (256), in global memory (any length); a read
 // whose front outgrows a tier is handed to the next one.  SA_MEA_TIER=1|2 starts lower (tests).  h_status: pinned, one
 // word per read.
@@ -617,10 +607,10 @@ static int mea_run_tiers(MeaWorkspace &W, MeaPlan &P, std::vector<MeaJob> &hj, c
             }
             if ((rc = W.dev(&W.d_gf, &W.d_gf_cap, sizeof(MeaEdge) * gf_tot, device)) != SA_OK) goto done;
             P.gf = (MeaEdge *) W.d_gf;
-            MEACHK(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
+            SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
         }
-        if (!all) MEACHK(hipMemcpyAsync(d + o_ids, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, 0));
-        MEACHK(hipEventRecord(W.e0, 0));
+        if (!all) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_ids, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
         if (tier == 0) {
             if (!all) { rc = SA_EINVAL; goto done; }   // the register tier is only ever the first
             hipLaunchKernelGGL(k_mea_wave, dim3(grid), dim3(64), 0, 0, P, (int) nj);
@@ -629,11 +619,11 @@ static int mea_run_tiers(MeaWorkspace &W, MeaPlan &P, std::vector<MeaJob> &hj, c
         } else {
             hipLaunchKernelGGL(k_mea<true>, dim3(grid), dim3(64), 0, 0, P, d_ids, (int) grid);
         }
-        MEACHK(hipEventRecord(W.e1, 0));
-        MEACHK(hipGetLastError());
-        MEACHK(hipMemcpyAsync(h_status, P.status, 4 * nj, hipMemcpyDeviceToHost, 0));
-        MEACHK(hipStreamSynchronize(0));
-        MEACHK(hipEventElapsedTime(&kms2, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(h_status, P.status, 4 * nj, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms2, W.e0, W.e1));
         *kms_out += kms2;
         redo.clear();
         for (size_t j = 0; j < nj; j++)
@@ -712,8 +702,8 @@ extern "C" int sa_mea_batch(const sa_mea_job_t *jobs, int64_t n_jobs, int device
     if ((rc = W.events()) != SA_OK) goto done;
     {
         char *d = (char *) W.d_ws;
-        MEACHK(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
-        if (in_bytes) MEACHK(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
+        if (in_bytes) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
         P.jobs = (const MeaJob *) (d + o_jobs);
         P.data = (const double *) (d + o_in);
         P.rows = (const int *) (d + o_in + o_h_rows);
@@ -724,8 +714,8 @@ extern "C" int sa_mea_batch(const sa_mea_job_t *jobs, int64_t n_jobs, int device
         P.sum = (double *) (d + o_sum);
         P.n_out = (int *) (d + o_res); P.n_edges = P.n_out + nj; P.status = P.n_edges + nj;
         if ((rc = mea_run_tiers(W, P, hj, d, o_jobs, o_ids, (int *) ((char *) W.h_res + (o_res - o_out)) + 2 * nj, device, &kms)) != SA_OK) goto done;
-        MEACHK(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
-        MEACHK(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
     {
@@ -830,7 +820,7 @@ extern "C" int64_t sa_mea_params(const int64_t *reference_index, const int64_t *
 // nothing but the final paths crosses PCIe.
 //
 // The event table's posterior_probability is what the TSV prints, "%f" of prob_e7 / 1e7, six decimals (sa_printed_units,
-// sa_scratch.h).
+// sa_chain.h).
 __host__ __device__ static inline double mea_printed_posterior(long long prob_e7) {
     return (double) sa_printed_units(prob_e7) / 1e6;
 }
@@ -844,13 +834,6 @@ struct MeaChain {
 __device__ __forceinline__ int wave_max_i(int v) {
     for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o));
     return uni(v);
-}
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o);
-        if (lane >= o) v += t;
-    }
-    return v;
 }
 
 // next cell of an event's bucket [b0, b1) in reference order: the smallest reference position above `last`, and the
@@ -904,7 +887,7 @@ __global__ __launch_bounds__(64) void k_mea_from_pairs(const sa_pair16_t *__rest
     for (int base = 0; base < n_ev; base += 64) {
         const int e = base + lane;
         const int c = e < n_ev ? fl[e] : 0;
-        const int incl = wave_incl_scan(c, lane);
+        const int incl = sa_wave_incl_scan(c, lane);
         if (e < n_ev) fl[e] = carry + incl - c;
         carry += rl(incl, 63);
     }
@@ -927,7 +910,7 @@ __global__ __launch_bounds__(64) void k_mea_from_pairs(const sa_pair16_t *__rest
             last = ref;
             kept += mea_printed_posterior(prob) != 0.0;
         }
-        const int incl = wave_incl_scan(kept, lane);
+        const int incl = sa_wave_incl_scan(kept, lane);
         int w = n_out + incl - kept;
         last = -1;
         while (mea_next_cell(sr, sp, b0, b1, last, ref, prob)) {
@@ -977,11 +960,15 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
     const bool trace = getenv("SA_TRACE") != nullptr;
     auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double t0 = now_ms();
-    const sa_pair16_t *d_pairs = nullptr;
-    std::vector<long long> first, count, n_events;
-    int device = 0;
-    int rc = sa_batch_device_view(b, &d_pairs, &first, &count, &n_events, &device);
+    SaBatchView V;
+    int rc = sa_batch_view(b, &V);
     if (rc) return rc;
+    // (8-byte records name neither path nor k-mer, and a batch filtered for the variant-caller output holds only the rows of X
+    // positions: not what the MEA path over ALL posteriors reads)
+    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;
+    const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
+    const int device = V.device;
+    const std::vector<long long> &first = V.first, &count = V.count, &n_events = V.n_events;
     const size_t nj = first.size();
     for (size_t j = 0; j < nj; j++) {
         path_out[j] = nullptr; n_path_out[j] = 0;
@@ -1008,13 +995,15 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
     std::lock_guard<std::mutex> guard(W.mu);
     // device: [jobs | chain | data f64 | rows | cols | shortest | arena ref, ev, prev | out | sum | n_out, n_edges, status | mins | ids]
     // aux (dead after k_mea_from_pairs): [fill | sorted ref | sorted prob]
-    const size_t o_jobs = 0, o_chain = sa_up256(sizeof(MeaJob) * nj), o_data = sa_up256(o_chain + sizeof(MeaChain) * nj),
-                 o_rows = sa_up256(o_data + 8 * n_tot), o_cols = sa_up256(o_rows + 4 * n_tot), o_sh = sa_up256(o_cols + 4 * n_tot),
-                 o_arena = sa_up256(o_sh + 4 * sh_tot), o_out = sa_up256(o_arena + 12 * n_tot),
-                 o_sum = sa_up256(o_out + 8 * out_tot), o_res = o_sum + 8 * nj, o_mins = o_res + 12 * nj,
-                 o_ndev = o_mins + 8 * nj, o_ids = sa_up256(o_ndev + 4 * nj), dev_bytes = o_ids + 4 * nj;
+    // out and the per-job words [sum | n_out, n_edges, status | mins | n_dev] are consecutive entries, the words ONE entry: a
+    // single copy brings [o_out, o_ids) back
+    SaLayout L, A;
+    const size_t o_jobs = L.add(sizeof(MeaJob) * nj), o_chain = L.add(sizeof(MeaChain) * nj), o_data = L.add(8 * n_tot),
+                 o_rows = L.add(4 * n_tot), o_cols = L.add(4 * n_tot), o_sh = L.add(4 * sh_tot), o_arena = L.add(12 * n_tot),
+                 o_out = L.add(8 * out_tot), o_sum = L.add((8 + 12 + 8 + 4) * nj), o_res = o_sum + 8 * nj, o_mins = o_res + 12 * nj,
+                 o_ndev = o_mins + 8 * nj, o_ids = L.add(4 * nj), dev_bytes = L.end;
     const size_t res_bytes = o_ids - o_out;
-    const size_t a_fill = 0, a_sref = sa_up256(4 * sh_tot), a_sprob = sa_up256(a_sref + 4 * n_tot), aux_bytes = a_sprob + 4 * n_tot;
+    const size_t a_fill = A.add(4 * sh_tot), a_sref = A.add(4 * n_tot), a_sprob = A.add(4 * n_tot), aux_bytes = A.end;
     MeaPlan P;
     memset(&P, 0, sizeof(P));
     float kms = 0, kms0 = 0;
@@ -1024,8 +1013,8 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
     if ((rc = W.events()) != SA_OK) return rc;
     {
         char *d = (char *) W.d_ws, *a = (char *) W.d_aux;
-        MEACHK(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
-        MEACHK(hipMemcpyAsync(d + o_chain, hc.data(), sizeof(MeaChain) * nj, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chain, hc.data(), sizeof(MeaChain) * nj, hipMemcpyHostToDevice, 0));
         P.jobs = (const MeaJob *) (d + o_jobs);
         P.data = (const double *) (d + o_data);
         P.rows = (const int *) (d + o_rows);
@@ -1037,20 +1026,20 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
         P.n_out = (int *) (d + o_res); P.n_edges = P.n_out + nj; P.status = P.n_edges + nj;
         P.n_dev = (const int *) (d + o_ndev);
         P.mins = (const int *) (d + o_mins);
-        MEACHK(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
         hipLaunchKernelGGL(k_mea_from_pairs, dim3((unsigned) nj), dim3(64), 0, 0, d_pairs, (const MeaChain *) (d + o_chain), P,
                            (int *) (a + a_fill), (int *) (a + a_sref), (int *) (a + a_sprob), (int *) (d + o_ndev),
                            (int *) (d + o_mins), (int) nj);
-        MEACHK(hipEventRecord(W.e1, 0));
-        MEACHK(hipGetLastError());
-        MEACHK(hipStreamSynchronize(0));
-        MEACHK(hipEventElapsedTime(&kms0, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms0, W.e0, W.e1));
         if (trace) fprintf(stderr, "[trace] mea: matrices built at %.3f ms\n", now_ms() - t0);
         if ((rc = mea_run_tiers(W, P, hj, d, o_jobs, o_ids, (int *) ((char *) W.h_res + (o_res - o_out)) + 2 * nj, device, &kms)) != SA_OK)
             goto done;
         if (trace) fprintf(stderr, "[trace] mea: paths done at %.3f ms\n", now_ms() - t0);
-        MEACHK(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
-        MEACHK(hipStreamSynchronize(0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
         if (trace) fprintf(stderr, "[trace] mea: %zu bytes on the host at %.3f ms\n", res_bytes, now_ms() - t0);
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms + (double) kms0;

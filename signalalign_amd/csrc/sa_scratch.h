@@ -1,6 +1,9 @@
-// Grow-only device and pinned-host scratch kept between calls of a one-shot entry point (sa_event_align_batch,
-// sa_mea_batch), so that a caller feeding batches in a loop pays allocation once.  One instance per entry point and
-// process; calls serialise on `mu`; the matching sa_*_release() returns the memory.
+// Allocators and host fan-out shared by the library's HIP sources (what concerns a finished batch is in sa_chain.h):
+//   SaScratch   grow-only device and pinned-host scratch kept between calls of a one-shot entry point (sa_event_align_batch,
+//               sa_mea_batch), so that a caller feeding batches in a loop pays allocation once.  One instance per entry point
+//               and process; calls serialise on `mu`; the matching sa_*_release() returns the memory.
+//   SaPool      caching allocators for a batch's working storage
+//   SaWorkers, sa_parallel_for   host-side fan-out over reads
 #ifndef SA_SCRATCH_H
 #define SA_SCRATCH_H
 
@@ -248,49 +251,6 @@ struct SaPool {
     }
 };
 extern SaPool g_sa_pool;
-
-// sa_hip.hip: device-side view of a finished batch for a downstream device step (per job: first pair in *pairs, number
-// of pairs, number of events)
-int sa_batch_device_view(sa_batch_t *b, const sa_pair16_t **pairs, std::vector<long long> *first, std::vector<long long> *count,
-                         std::vector<long long> *n_events, int *device);
-// the same for a step that reads 16- and 8-byte records alike (*p8: which); SA_EINVAL for a SA_FLAG_VC_ROWS batch
-int sa_batch_device_records(sa_batch_t *b, const void **recs, bool *p8, std::vector<long long> *first, std::vector<long long> *count,
-                            int *device);
-
-// sa_calls.hip: the sites a SA_FLAG_SITE_CALLS batch records at creation (sa_sites_build), the device copy of their tables going
-// back with the batch's working storage (sa_sites_release_device) and everything with the batch (sa_sites_free)
-struct SaSites;
-int sa_sites_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaSites **out);
-long long sa_sites_count(const SaSites *s);   // 0 for NULL
-void sa_sites_release_device(SaSites *s);
-void sa_sites_free(SaSites *s);                 // NULL: nothing
-// sa_hip.hip: a finished batch's sites (SA_ESTATE: created without SA_FLAG_SITE_CALLS, or not run)
-int sa_batch_sites(sa_batch_t *b, SaSites **sites, int64_t *n_jobs);
-// sa_calls.hip: the ambiguous positions a SA_FLAG_POSITION_CALLS batch records at creation (sa_positions_build); their device
-// tables go back with the batch's working storage, everything with the batch
-struct SaPositions;
-int sa_positions_build(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, SaPositions **out);
-void sa_positions_release_device(SaPositions *s);
-void sa_positions_free(SaPositions *s);                 // NULL: nothing
-// sa_hip.hip: a finished batch's positions (SA_ESTATE: created without SA_FLAG_POSITION_CALLS, or not run)
-int sa_batch_positions(sa_batch_t *b, SaPositions **positions, int64_t *n_jobs);
-
-// The posterior the TSV prints, "%f" of prob_e7 / 1e7, in integers of 1e-6: a decimal rounding of a binary double.  Only a
-// last digit of 5 can tie; then the sign of q * 1e7 - prob_e7 (one fma, exact in sign) says on which side of the tie the
-// double q = prob_e7 / 1e7 lies, and an exact tie goes to even as glibc's printf does.  tests/test_host_mea.py checks every
-// value of prob_e7 against Python's "%f".
-__host__ __device__ static inline long long sa_printed_units(long long prob_e7) {
-    long long k = prob_e7 / 10;
-    const long long rem = prob_e7 % 10;
-    if (rem > 5) {
-        k++;
-    } else if (rem == 5) {
-        const double q = (double) prob_e7 / 1e7;
-        const double side = fma(q, 1e7, -(double) prob_e7);
-        if (side > 0 || (side == 0 && (k & 1))) k++;
-    }
-    return k;
-}
 
 // Worker threads of the host fan-out below, started on first use and parked between calls: a fresh std::thread per worker and
 // call cost 0.5-0.7 ms per fan-out at 13 workers, and sa_batch_create fans out five times (a third of its host time).  One

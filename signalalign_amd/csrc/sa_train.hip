@@ -41,9 +41,8 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_scratch.h"
+#include "sa_chain.h"
 
-#define KT_CHUNK 4096                    // records per block of the record kernels
 #define KT_BINS 1024                     // 10 bits per selection level
 #define KT_RUN_BITS 40
 #define KT_RUN_MASK ((1ull << KT_RUN_BITS) - 1ull)
@@ -81,14 +80,9 @@ struct KtJob {                  // per job of a batch
     long long ev_off, n_ev, x_off, n_x;
     double scale, shift, var;
 };
-struct KtChunk {
-    long long first;            // first record of the chunk in the batch's device results
-    long long run0;             // run ordinal of that record
-    int n, job;
-};
 struct KtRecs {
     const void *recs;
-    const KtChunk *chunks;
+    const SaRecChunk *chunks;
     const KtJob *jobs;
     const double *ev;           // event means of every job, dense
     const int *xk;              // 8-byte records: k-mer id of every reference position of every job
@@ -96,7 +90,7 @@ struct KtRecs {
     long long min_units, n_kmers;
 };
 
-__device__ static inline bool kt_rec(const KtRecs &R, bool p8, const KtChunk &C, int i, int *kmer, unsigned long long *key, long long *y,
+__device__ static inline bool kt_rec(const KtRecs &R, bool p8, const SaRecChunk &C, int i, int *kmer, unsigned long long *key, long long *y,
                                      unsigned *err) {
     long long pe7;
     int x;
@@ -117,7 +111,7 @@ __device__ static inline bool kt_rec(const KtRecs &R, bool p8, const KtChunk &C,
     if (*kmer < 0 || *kmer >= R.n_kmers) { atomicOr(err, KT_ERR_BOUNDS); return false; }
     const long long u = sa_printed_units(pe7);
     if (u < R.min_units) return false;
-    *key = ((unsigned long long) u << KT_RUN_BITS) | (KT_RUN_MASK - (unsigned long long) (C.run0 + i));
+    *key = ((unsigned long long) u << KT_RUN_BITS) | (KT_RUN_MASK - (unsigned long long) (C.local + i));
     return true;
 }
 
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(256) void k_kt_hist_rows(const KtRow *__restrict__ 
 template <bool P8>
 __global__ __launch_bounds__(256) void k_kt_hist_rec(KtRecs R, const KtState *__restrict__ st, unsigned *__restrict__ hist, int shift,
                                                      unsigned *__restrict__ err) {
-    const KtChunk C = R.chunks[blockIdx.x];
+    const SaRecChunk C = R.chunks[blockIdx.x];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
         int kmer;
         unsigned long long key;
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(256) void k_kt_tie_rows(const KtRow *__restrict__ r
 template <bool P8>
 __global__ __launch_bounds__(256) void k_kt_tie_rec(KtRecs R, const KtState *__restrict__ st, KtRow *__restrict__ tie,
                                                     unsigned long long *__restrict__ n_tie, unsigned long long cap, unsigned *__restrict__ err) {
-    const KtChunk C = R.chunks[blockIdx.x];
+    const SaRecChunk C = R.chunks[blockIdx.x];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
         int kmer;
         unsigned long long key;
@@ -228,27 +222,9 @@ __global__ __launch_bounds__(256) void k_kt_tie_rec(KtRecs R, const KtState *__r
     }
 }
 
-// exclusive scan of keep[0 .. n) into off[0 .. n] (k_site_scan's scheme: per-thread runs, wave scans, wave totals through LDS)
-#define KT_SCAN_THREADS 1024
-__global__ __launch_bounds__(KT_SCAN_THREADS) void k_kt_scan(const KtState *__restrict__ st, long long *__restrict__ off, long long n) {
-    __shared__ long long wave_tot[KT_SCAN_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const long long per = (n + KT_SCAN_THREADS - 1) / KT_SCAN_THREADS;
-    const long long a = min(n, (long long) t * per), e = min(n, a + per);
-    long long mine = 0;
-    for (long long i = a; i < e; i++) mine += st[i].keep;
-    long long incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    long long before = 0;
-    for (int q = 0; q < wv; q++) before += wave_tot[q];
-    long long run = before + incl - mine;
-    for (long long i = a; i < e; i++) { off[i] = run; run += st[i].keep; }
-    if (t == KT_SCAN_THREADS - 1) off[n] = before + incl;
+// exclusive scan of keep[0 .. n) into off[0 .. n], one block
+__global__ __launch_bounds__(SA_SCAN_THREADS) void k_kt_scan(const KtState *__restrict__ st, long long *__restrict__ off, long long n) {
+    sa_block_excl_scan([st](long long i) { return st[i].keep; }, off, n);
 }
 
 __device__ static inline void kt_put(const KtState *st, const long long *off, unsigned long long *fill, KtRow *out, const KtRow &r,
@@ -271,7 +247,7 @@ template <bool P8>
 __global__ __launch_bounds__(256) void k_kt_compact_rec(KtRecs R, const KtState *__restrict__ st, const long long *__restrict__ off,
                                                         unsigned long long *__restrict__ fill, KtRow *__restrict__ out,
                                                         unsigned *__restrict__ err) {
-    const KtChunk C = R.chunks[blockIdx.x];
+    const SaRecChunk C = R.chunks[blockIdx.x];
     const KtJob J = R.jobs[C.job];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
         KtRow r;
@@ -393,16 +369,6 @@ struct sa_kmer_table {
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
-#define KTCHK(call)                                                                                         \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
-            goto done;                                                                                      \
-        }                                                                                                   \
-    } while (0)
-
 extern "C" int sa_kmer_table_create(sa_kmer_table_t **out, const sa_model_t *m, int64_t max_per_kmer, double min_prob, int device) {
     if (!out || !m || max_per_kmer < 1 || !(min_prob >= 0.0 && min_prob <= 1.0)) return SA_EINVAL;
     *out = nullptr;
@@ -424,13 +390,13 @@ extern "C" int sa_kmer_table_create(sa_kmer_table_t **out, const sa_model_t *m, 
     for (long long i = 0; i < t->n_kmers; i++) level[(size_t) i] = m->table5[5 * i];
     int rc = SA_OK;
     std::vector<long long> zero((size_t) t->n_kmers + 1, 0);
-    KTCHK(hipEventCreate(&t->e0));
-    KTCHK(hipEventCreate(&t->e1));
-    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_level, sizeof(double) * (size_t) t->n_kmers, device));
-    KTCHK(hipMemcpy(t->d_level, level.data(), sizeof(double) * (size_t) t->n_kmers, hipMemcpyHostToDevice));
+    SA_HIP_GOTO_DONE(hipEventCreate(&t->e0));
+    SA_HIP_GOTO_DONE(hipEventCreate(&t->e1));
+    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_level, sizeof(double) * (size_t) t->n_kmers, device));
+    SA_HIP_GOTO_DONE(hipMemcpy(t->d_level, level.data(), sizeof(double) * (size_t) t->n_kmers, hipMemcpyHostToDevice));
     for (int s = 0; s < 2; s++) {
-        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &t->side[s].d_off, sizeof(long long) * zero.size(), device));
-        KTCHK(hipMemcpy(t->side[s].d_off, zero.data(), sizeof(long long) * zero.size(), hipMemcpyHostToDevice));
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->side[s].d_off, sizeof(long long) * zero.size(), device));
+        SA_HIP_GOTO_DONE(hipMemcpy(t->side[s].d_off, zero.data(), sizeof(long long) * zero.size(), hipMemcpyHostToDevice));
     }
 done:
     if (rc != SA_OK) { sa_kmer_table_destroy(t); return rc; }
@@ -474,26 +440,26 @@ static int kt_merge(sa_kmer_table *t, int side, const KtRecs *rec, bool p8, long
     unsigned long long h_tied = 0;
     double kms = 0;
     float seg = 0;
-    // scratch: [state | hist | off | fill | err, active | tied, n_tie]
-    const size_t o_st = 0, o_hist = sa_up256(sizeof(KtState) * (size_t) nk), o_off = sa_up256(o_hist + 4 * (size_t) nk * KT_BINS),
-                 o_fill = sa_up256(o_off + 8 * (size_t) (nk + 1)), o_err = sa_up256(o_fill + 8 * (size_t) nk), o_tied = o_err + 8,
-                 bytes = o_tied + 16;
+    // scratch: [state | hist | off | fill | err, active | tied, n_tie]; each pair of words is one entry (one memset clears both)
+    SaLayout L;
+    const size_t o_st = L.add(sizeof(KtState) * (size_t) nk), o_hist = L.add(4 * (size_t) nk * KT_BINS), o_off = L.add(8 * (size_t) (nk + 1)),
+                 o_fill = L.add(8 * (size_t) nk), o_err = L.add(2 * 4), o_tied = L.add(2 * 8), bytes = L.end;
     std::vector<KtState> st0((size_t) nk);
     for (KtState &q : st0) { q.prefix = 0; q.thr = 0; q.need = t->N; q.keep = 0; q.done = 0; q.pad = 0; }
-    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, dev));
+    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, dev));
     {
         KtState *st = (KtState *) (d + o_st);
         unsigned *hist = (unsigned *) (d + o_hist), *err = (unsigned *) (d + o_err), *active = err + 1;
         unsigned long long *tied = (unsigned long long *) (d + o_tied), *n_tie = tied + 1;
         long long *off = (long long *) (d + o_off);
         unsigned long long *fill = (unsigned long long *) (d + o_fill);
-        KTCHK(hipMemcpyAsync(st, st0.data(), sizeof(KtState) * (size_t) nk, hipMemcpyHostToDevice, 0));
-        KTCHK(hipMemsetAsync(err, 0, 8, 0));
-        KTCHK(hipMemsetAsync(tied, 0, 16, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(st, st0.data(), sizeof(KtState) * (size_t) nk, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemsetAsync(err, 0, 8, 0));
+        SA_HIP_GOTO_DONE(hipMemsetAsync(tied, 0, 16, 0));
         for (int shift = 50; shift >= 0; shift -= 10) {
-            KTCHK(hipEventRecord(t->e0, 0));
-            KTCHK(hipMemsetAsync(hist, 0, 4 * (size_t) nk * KT_BINS, 0));
-            KTCHK(hipMemsetAsync(active, 0, 4, 0));
+            SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
+            SA_HIP_GOTO_DONE(hipMemsetAsync(hist, 0, 4 * (size_t) nk * KT_BINS, 0));
+            SA_HIP_GOTO_DONE(hipMemsetAsync(active, 0, 4, 0));
             if (shift >= 40) {   // the posterior levels: every candidate
                 if (S.n_rows)
                     hipLaunchKernelGGL(k_kt_hist_rows, dim3((unsigned) ((S.n_rows + 255) / 256)), dim3(256), 0, 0, S.d_rows, S.n_rows, st, hist, shift);
@@ -507,17 +473,17 @@ static int kt_merge(sa_kmer_table *t, int side, const KtRecs *rec, bool p8, long
                 hipLaunchKernelGGL(k_kt_hist_rows, dim3((unsigned) ((h_tied + 255) / 256)), dim3(256), 0, 0, d_tie, (long long) h_tied, st, hist, shift);
             }
             hipLaunchKernelGGL(k_kt_cut, dim3((unsigned) nk), dim3(64), 0, 0, st, hist, shift, active, tied);
-            KTCHK(hipEventRecord(t->e1, 0));
-            KTCHK(hipGetLastError());
-            KTCHK(hipMemcpy(&h_active, active, 4, hipMemcpyDeviceToHost));
-            KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+            SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
+            SA_HIP_GOTO_DONE(hipGetLastError());
+            SA_HIP_GOTO_DONE(hipMemcpy(&h_active, active, 4, hipMemcpyDeviceToHost));
+            SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, t->e0, t->e1));
             kms += seg;
             if (h_active >= 0x10000u) { rc = SA_ENODEVICE; goto done; }   // (a cut found fewer keys than it counted before)
             if (h_active == 0) break;
             if (shift == 40) {   // k-mers still open: copy their rows at the cutoff posterior out once
-                KTCHK(hipMemcpy(&h_tied, tied, 8, hipMemcpyDeviceToHost));
-                KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d_tie, sizeof(KtRow) * (size_t) (h_tied ? h_tied : 1), dev));
-                KTCHK(hipEventRecord(t->e0, 0));
+                SA_HIP_GOTO_DONE(hipMemcpy(&h_tied, tied, 8, hipMemcpyDeviceToHost));
+                SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d_tie, sizeof(KtRow) * (size_t) (h_tied ? h_tied : 1), dev));
+                SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
                 if (S.n_rows)
                     hipLaunchKernelGGL(k_kt_tie_rows, dim3((unsigned) ((S.n_rows + 255) / 256)), dim3(256), 0, 0, S.d_rows, S.n_rows, st, d_tie, n_tie, h_tied, err);
                 if (n_new)
@@ -526,23 +492,23 @@ static int kt_merge(sa_kmer_table *t, int side, const KtRecs *rec, bool p8, long
                     if (p8) hipLaunchKernelGGL(k_kt_tie_rec<true>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, d_tie, n_tie, h_tied, err);
                     else hipLaunchKernelGGL(k_kt_tie_rec<false>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, d_tie, n_tie, h_tied, err);
                 }
-                KTCHK(hipEventRecord(t->e1, 0));
-                KTCHK(hipGetLastError());
-                KTCHK(hipEventSynchronize(t->e1));
-                KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+                SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
+                SA_HIP_GOTO_DONE(hipGetLastError());
+                SA_HIP_GOTO_DONE(hipEventSynchronize(t->e1));
+                SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, t->e0, t->e1));
                 kms += seg;
             }
         }
-        KTCHK(hipEventRecord(t->e0, 0));
-        hipLaunchKernelGGL(k_kt_scan, dim3(1), dim3(KT_SCAN_THREADS), 0, 0, st, off, nk);
-        KTCHK(hipEventRecord(t->e1, 0));
-        KTCHK(hipMemcpy(&total, off + nk, 8, hipMemcpyDeviceToHost));
-        KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+        SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
+        hipLaunchKernelGGL(k_kt_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, st, off, nk);
+        SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
+        SA_HIP_GOTO_DONE(hipMemcpy(&total, off + nk, 8, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, t->e0, t->e1));
         kms += seg;
-        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d_new, sizeof(KtRow) * (size_t) (total > 0 ? total : 1), dev));
-        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d_off_new, 8 * (size_t) (nk + 1), dev));
-        KTCHK(hipEventRecord(t->e0, 0));
-        KTCHK(hipMemsetAsync(fill, 0, 8 * (size_t) nk, 0));
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d_new, sizeof(KtRow) * (size_t) (total > 0 ? total : 1), dev));
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d_off_new, 8 * (size_t) (nk + 1), dev));
+        SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
+        SA_HIP_GOTO_DONE(hipMemsetAsync(fill, 0, 8 * (size_t) nk, 0));
         if (S.n_rows)
             hipLaunchKernelGGL(k_kt_compact_rows, dim3((unsigned) ((S.n_rows + 255) / 256)), dim3(256), 0, 0, S.d_rows, S.n_rows, st, off, fill, d_new, err);
         if (n_new)
@@ -551,11 +517,11 @@ static int kt_merge(sa_kmer_table *t, int side, const KtRecs *rec, bool p8, long
             if (p8) hipLaunchKernelGGL(k_kt_compact_rec<true>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, off, fill, d_new, err);
             else hipLaunchKernelGGL(k_kt_compact_rec<false>, dim3((unsigned) nc), dim3(256), 0, 0, *rec, st, off, fill, d_new, err);
         }
-        KTCHK(hipMemcpyAsync(d_off_new, off, 8 * (size_t) (nk + 1), hipMemcpyDeviceToDevice, 0));
-        KTCHK(hipEventRecord(t->e1, 0));
-        KTCHK(hipGetLastError());
-        KTCHK(hipMemcpy(&h_err, err, 4, hipMemcpyDeviceToHost));
-        KTCHK(hipEventElapsedTime(&seg, t->e0, t->e1));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d_off_new, off, 8 * (size_t) (nk + 1), hipMemcpyDeviceToDevice, 0));
+        SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(hipMemcpy(&h_err, err, 4, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, t->e0, t->e1));
         kms += seg;
         if (h_err & KT_ERR_BOUNDS) { rc = SA_EINVAL; goto done; }
         if (h_err & KT_ERR_RANGE) { rc = SA_EUNSUPPORTED; goto done; }
@@ -635,13 +601,14 @@ extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const 
                                        double *kernel_ms_out) {
     if (!t || !b || (n_jobs > 0 && !jobs) || n_jobs < 0 || (strand != 0 && strand != 1)) return SA_EINVAL;
     std::lock_guard<std::mutex> g(t->mu);
-    const void *recs = nullptr;
-    bool p8 = false;
-    std::vector<long long> first, count;
-    int device = 0;
-    int rc = sa_batch_device_records(b, &recs, &p8, &first, &count, &device);
+    SaBatchView V;
+    int rc = sa_batch_view(b, &V);
+    if (V.batch_flags & SA_FLAG_VC_ROWS) return SA_EINVAL;   // (it dropped rows; refused before the batch's state is looked at)
     if (rc) return rc;
-    if ((int64_t) first.size() != n_jobs || device != t->device) return SA_EINVAL;
+    if (V.batch_flags & SA_FLAG_EXPECT_INTERNAL) return SA_ESTATE;
+    if ((int64_t) V.count.size() != n_jobs || V.device != t->device) return SA_EINVAL;
+    const bool p8 = V.p8;   // (either record size is read)
+    const std::vector<long long> &count = V.count;
     if (kernel_ms_out) *kernel_ms_out = 0.0;
     const size_t nj = (size_t) n_jobs;
     long long n_total = 0;
@@ -661,23 +628,18 @@ extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const 
         kj[j].x_off = n_x; kj[j].n_x = lx;
         n_x += lx;
     }
-    std::vector<KtChunk> chunks;
-    long long run = (long long) t->run_next;
-    for (size_t j = 0; j < nj; j++) {
-        for (long long c = 0; c < count[j]; c += KT_CHUNK)
-            chunks.push_back(KtChunk{first[j] + c, run + c, (int) std::min<long long>(KT_CHUNK, count[j] - c), (int) j});
-        run += count[j];
-    }
+    const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, (long long) t->run_next);   // (run ordinals)
     const long long nc = (long long) chunks.size();
     // one pinned staging block and one device block: [jobs | chunks | events | k-mer ids]
-    const size_t o_jobs = 0, o_ch = sa_up256(sizeof(KtJob) * (nj ? nj : 1)), o_ev = sa_up256(o_ch + sizeof(KtChunk) * (size_t) (nc ? nc : 1)),
-                 o_xk = sa_up256(o_ev + 8 * (size_t) n_ev), bytes = o_xk + 4 * (size_t) n_x + 4;
+    SaLayout L;
+    const size_t o_jobs = L.add(sizeof(KtJob) * nj), o_ch = L.add(sizeof(SaRecChunk) * (size_t) nc), o_ev = L.add(8 * (size_t) n_ev),
+                 o_xk = L.add(4 * (size_t) n_x + 4), bytes = L.end;
     char *h = nullptr, *d = nullptr;
     if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
     if (g_sa_pool.get(SaPool::PINNED, (void **) &h, bytes, t->device) != hipSuccess) return SA_ENOMEM;
     {
         memcpy(h + o_jobs, kj.data(), sizeof(KtJob) * nj);
-        if (nc) memcpy(h + o_ch, chunks.data(), sizeof(KtChunk) * (size_t) nc);
+        if (nc) memcpy(h + o_ch, chunks.data(), sizeof(SaRecChunk) * (size_t) nc);
         double *ev = (double *) (h + o_ev);
         int *xk = (int *) (h + o_xk);
         std::vector<int> bad(nj, SA_OK);
@@ -689,11 +651,11 @@ extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const 
         });
         for (size_t j = 0; j < nj; j++)
             if (bad[j] != SA_OK) { rc = bad[j]; goto done; }
-        KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, t->device));
-        KTCHK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, t->device));
+        SA_HIP_GOTO_DONE(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
         KtRecs R;
-        R.recs = recs;
-        R.chunks = (const KtChunk *) (d + o_ch);
+        R.recs = V.recs;
+        R.chunks = (const SaRecChunk *) (d + o_ch);
         R.jobs = (const KtJob *) (d + o_jobs);
         R.ev = (const double *) (d + o_ev);
         R.xk = (const int *) (d + o_xk);
@@ -731,8 +693,8 @@ extern "C" int sa_kmer_table_add_rows(sa_kmer_table_t *t, int strand, const int3
     int rc = SA_OK;
     KtRow *d = nullptr;
     if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, sizeof(KtRow) * (rows.size() ? rows.size() : 1), t->device));
-    if (!rows.empty()) KTCHK(hipMemcpy(d, rows.data(), sizeof(KtRow) * rows.size(), hipMemcpyHostToDevice));
+    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, sizeof(KtRow) * (rows.size() ? rows.size() : 1), t->device));
+    if (!rows.empty()) SA_HIP_GOTO_DONE(hipMemcpy(d, rows.data(), sizeof(KtRow) * rows.size(), hipMemcpyHostToDevice));
     rc = kt_merge(t, strand, nullptr, false, 0, d, (long long) rows.size(), nullptr);
     if (rc == SA_OK) t->run_next += (unsigned long long) n;
 done:
@@ -853,14 +815,14 @@ extern "C" int sa_kmer_table_stats(const sa_kmer_table_t *t, int strand, int use
     KtRaw *d = nullptr;
     float kms = 0;
     if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    KTCHK(g_sa_pool.get(SaPool::DEVICE, (void **) &d, sizeof(KtRaw) * (size_t) nk, t->device));
-    KTCHK(hipEventRecord(T->e0, 0));
+    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, sizeof(KtRaw) * (size_t) nk, t->device));
+    SA_HIP_GOTO_DONE(hipEventRecord(T->e0, 0));
     hipLaunchKernelGGL(k_kt_stats, dim3((unsigned) nk), dim3(KT_STATS_THREADS), 0, 0, t->side[strand].d_rows, t->side[strand].d_off,
                        use_median ? 1 : 0, d);
-    KTCHK(hipEventRecord(T->e1, 0));
-    KTCHK(hipGetLastError());
-    KTCHK(hipMemcpy(raw.data(), d, sizeof(KtRaw) * (size_t) nk, hipMemcpyDeviceToHost));
-    KTCHK(hipEventElapsedTime(&kms, T->e0, T->e1));
+    SA_HIP_GOTO_DONE(hipEventRecord(T->e1, 0));
+    SA_HIP_GOTO_DONE(hipGetLastError());
+    SA_HIP_GOTO_DONE(hipMemcpy(raw.data(), d, sizeof(KtRaw) * (size_t) nk, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, T->e0, T->e1));
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
     for (long long km = 0; km < nk; km++) {
         const KtRaw &R = raw[(size_t) km];
@@ -979,13 +941,13 @@ extern "C" int sa_f6_units_device(const double *v, int64_t n, int64_t *units_out
     const size_t o_u = sa_up256(8 * (size_t) n), o_z = sa_up256(o_u + 8 * (size_t) n), o_r = sa_up256(o_z + 4 * (size_t) n);
     if (hipMalloc((void **) &d, o_r + 4 * (size_t) n) != hipSuccess) return SA_ENOMEM;
     int rc = SA_OK;
-    KTCHK(hipMemcpy(d, v, 8 * (size_t) n, hipMemcpyHostToDevice));
+    SA_HIP_GOTO_DONE(hipMemcpy(d, v, 8 * (size_t) n, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_kt_f6, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, (const double *) d, (long long) n, (long long *) (d + o_u),
                        (int *) (d + o_z), (int *) (d + o_r));
-    KTCHK(hipGetLastError());
-    KTCHK(hipMemcpy(units_out, d + o_u, 8 * (size_t) n, hipMemcpyDeviceToHost));
-    KTCHK(hipMemcpy(neg_zero_out, d + o_z, 4 * (size_t) n, hipMemcpyDeviceToHost));
-    KTCHK(hipMemcpy(rc_out, d + o_r, 4 * (size_t) n, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipGetLastError());
+    SA_HIP_GOTO_DONE(hipMemcpy(units_out, d + o_u, 8 * (size_t) n, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipMemcpy(neg_zero_out, d + o_z, 4 * (size_t) n, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipMemcpy(rc_out, d + o_r, 4 * (size_t) n, hipMemcpyDeviceToHost));
 done:
     (void) hipFree(d);
     return rc;

@@ -2,6 +2,7 @@
 (sa_mea_batch): the reference's known-answer matrix, bit-identical paths and sums against the CPU restatement on
 random matrices and on posteriors produced by the HIP aligner itself, the reference's exception cases as status words,
 and the global-front second pass."""
+import ctypes as C
 import json
 import os
 
@@ -160,6 +161,57 @@ def test_chained_onto_a_finished_batch(oracle, flags):
         # every pair of the path is one of the read's aligned pairs
         have = set(zip(pr["x"].tolist(), pr["y"].tolist()))
         assert all((int(x), int(y)) in have for x, y in path)
+    b.close()
+
+
+def test_chained_again_after_release_device():
+    """sa_batch_release_device keeps the results: sa_batch_mea then reads the pairs uploaded again from the host copy and
+    gives what it gave from the pairs the run left in HBM."""
+    pm = sa.Model.load(cases.MODEL_6MER)
+    reads = cases.synthetic_jobs(cases.MODEL_6MER, 8, 1200, 300)
+    b = sa.Batch(pm, sa.default_params(), reads)
+    b.run()
+    before = b.mea()
+    b.release_device()
+    after = b.mea()
+    b.close()
+    assert len(before) == len(after) == len(reads)
+    assert sum(len(path) for path, _, _ in before) > 0
+    for (path0, best0, st0), (path1, best1, st1) in zip(before, after):
+        assert np.array_equal(path0, path1)
+        assert best0 == best1
+        assert st0 == st1
+
+
+def _batch_mea_rc(b):
+    n = max(b.n_jobs, 1)
+    ptrs = (C.c_void_p * n)()
+    cnt = np.zeros(n, dtype=np.int64)
+    rc = sa.lib().sa_batch_mea(b._h, 0, ptrs, cnt.ctypes.data_as(C.POINTER(C.c_int64)), None, None, None)
+    for q in ptrs:
+        sa.lib().sa_free(q)
+    return rc
+
+
+def test_chained_error_contract():
+    """SA_ESTATE (-7) for a batch that has not run and for one whose records are not every row's 16 bytes"""
+    p = sa.default_params()
+    pm = sa.Model.load(cases.MODEL_6MER)
+    jobs = cases.synthetic_jobs(cases.MODEL_6MER, 2, 600, 500)
+    b = sa.Batch(pm, p, jobs)
+    assert _batch_mea_rc(b) == -7                                # not run yet
+    b.run()
+    assert _batch_mea_rc(b) == 0
+    b.close()
+    b = sa.Batch(pm, p, jobs, flags=sa.FLAG_PAIRS8)
+    b.run()
+    assert _batch_mea_rc(b) == -7
+    b.close()
+    pc = sa.Model.load(cases.MODEL_CPG)
+    jobs = cases.synthetic_jobs(cases.MODEL_CPG, 2, 600, 500, cpg_ambiguous=True)
+    b = sa.Batch(pc, p, jobs, ambig=sa.default_ambig({"X": "CE"}), flags=sa.FLAG_VC_ROWS)
+    b.run()
+    assert _batch_mea_rc(b) == -7
     b.close()
 
 
