@@ -856,6 +856,46 @@ int64_t sa_hdp_state_samples_taken(const sa_hdp_state_t *s);
 double sa_hdp_digamma(double x);    /* test hooks: the two special functions of the maximum-likelihood alpha (x > 0) */
 double sa_hdp_trigamma(double x);
 
+/* ---- HDP distribution distances ---------------------------------------------------------------
+ * How far apart are the distributions of two Dirichlet processes: DistributionMetricMemo (inc/hdp.h:82-106, impl/hdp.c:2614-2866)
+ * and its k-mer wrappers (inc/nanopore_hdp.h:77-97, impl/nanopore_hdp.c:431-483).  The reference fills its memo lazily, a pair at a
+ * time; here the whole triangle is one GPU pass (signalalign_amd/csrc/sa_hdpdist.hip), a thread per pair, the reference's
+ * expressions term for term in its summation order -- no clamping: a zero density is a NaN for KL and Shannon-Jensen, an integral
+ * above one a NaN for Hellinger, two bit-identical rows give exactly 0 for KL, Shannon-Jensen and L2.
+ * Argument checks come before any device use (SA_EINVAL: grid_length < 2, n_rows < 1, an unknown metric, a NULL array; n_rows == 1
+ * succeeds and writes nothing), then SA_ENODEVICE without a GPU.  The state-level calls: SA_ESTATE unless the splines are
+ * finalised, SA_EINVAL for an id outside [0, num_dps); an unobserved DP stands for its nearest observed ancestor (:2651-2658,
+ * :2600-2602).  kernel_ms_out (may be NULL): HIP-event time of the kernels alone. */
+#define SA_HDP_METRIC_KL 0              /* kl_divergence          impl/hdp.c:2666-2683 (symmetrised) */
+#define SA_HDP_METRIC_HELLINGER 1       /* hellinger_distance     :2693-2710 */
+#define SA_HDP_METRIC_L2 2              /* l2_distance            :2720-2738 */
+#define SA_HDP_METRIC_SHANNON_JENSEN 3  /* shannon_jensen_distance :2748-2767 */
+/* all pairs among n_rows distributions sampled on one grid: tri_out[(i - 1) * i / 2 + j] for i > j
+ * (the memo's index, impl/hdp.c:2629); n_rows * (n_rows - 1) / 2 doubles in ordinary host memory */
+int sa_hdp_distances(const double *grid, int64_t grid_length, const double *rows, int64_t n_rows, int metric,
+                     int device, double *tri_out, double *kernel_ms_out);
+/* returns the device and pinned scratch sa_hdp_distances keeps between calls */
+void sa_hdp_distances_release(void);
+/* n pairs: a[i * grid_length ..] against b[i * grid_length ..] */
+int sa_hdp_distances_paired(const double *grid, int64_t grid_length, const double *a, const double *b, int64_t n,
+                            int metric, int device, double *out, double *kernel_ms_out);
+/* dir_proc_density (:2588-2612) for n_dps DP ids x n_x query points, out[d * n_x + q]; on the device.  grid_spline_interp
+ * (impl/hdp_math_utils.c:471-495) operation for operation; its left knot index is kept within the arrays */
+int sa_hdp_state_densities(const sa_hdp_state_t *s, const int64_t *dp_ids, int64_t n_dps, const double *x, int64_t n_x,
+                           int device, double *out);
+/* the full memo over the state's observed DPs (rows as sa_hdp_state_info_t.row_of_dp) */
+int sa_hdp_state_distances(const sa_hdp_state_t *s, int metric, int device, double *tri_out, double *kernel_ms_out);
+/* get_dir_proc_distance (:2614-2636) for n pairs of DP ids: 0.0 for dp1[i] == dp2[i] without evaluating; two different ids that
+ * resolve to one row are evaluated */
+int sa_hdp_state_distance_pairs(const sa_hdp_state_t *s, int metric, const int64_t *dp1, const int64_t *dp2, int64_t n,
+                                int device, double *out);
+/* compare_hdp_distrs (:2809-2842): s1's grid is the master, s2's densities are interpolated on it (no shortcut for equal ids) */
+int sa_hdp_state_compare(const sa_hdp_state_t *s1, const int64_t *dp1, const sa_hdp_state_t *s2, const int64_t *dp2,
+                         int64_t n, int metric, int device, double *out);
+/* get_nanopore_hdp_alphabet (impl/nanopore_hdp.c): the model's alphabet, NUL-terminated, into at least 64 bytes; k-mer ids count
+ * in its order (sa_hdp_state_kmer_dp) */
+int sa_hdp_state_alphabet(const sa_hdp_state_t *s, char *alphabet_out);
+
 int sa_device_count(void);
 /* HBM of `device`: bytes free (what the library's caching allocator holds counts as free) and in total; a caller that keeps
  * several batches in flight sizes its pipeline with this (sa_batch_stats_t.f_bytes is the bulk of a batch) */

@@ -133,6 +133,7 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_plan_check_path_records", "sa_dplan_compare",
            "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
+           "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
            "sa_hmm_load_into_model", "sa_model_transitions10",
@@ -324,6 +325,14 @@ def lib():
     L.sa_hdp_digamma.restype = C.c_double
     L.sa_hdp_trigamma.argtypes = [C.c_double]
     L.sa_hdp_trigamma.restype = C.c_double
+    L.sa_hdp_distances.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, dp, dp]
+    L.sa_hdp_distances_release.restype = None
+    L.sa_hdp_distances_paired.argtypes = [dp, C.c_int64, dp, dp, C.c_int64, C.c_int, C.c_int, dp, dp]
+    L.sa_hdp_state_densities.argtypes = [C.c_void_p, ip, C.c_int64, dp, C.c_int64, C.c_int, dp]
+    L.sa_hdp_state_distances.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp]
+    L.sa_hdp_state_distance_pairs.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_int64, C.c_int, dp]
+    L.sa_hdp_state_compare.argtypes = [C.c_void_p, ip, C.c_void_p, ip, C.c_int64, C.c_int, C.c_int, dp]
+    L.sa_hdp_state_alphabet.argtypes = [C.c_void_p, C.c_char_p]
     _LIB = L
     return L
 
@@ -1275,6 +1284,48 @@ class HdpState:
             lib().sa_free(C.cast(q, C.c_void_p))
         return out
 
+    def alphabet(self):
+        buf = C.create_string_buffer(64)
+        _chk(lib().sa_hdp_state_alphabet(self._h, buf), "sa_hdp_state_alphabet")
+        return buf.value.decode()
+
+    def densities(self, dp_ids, x, device=0):
+        """sa_hdp_state_densities: dir_proc_density of every DP id at every query point, len(dp_ids) x len(x) (GPU)"""
+        ids = np.ascontiguousarray(dp_ids, dtype=np.int64).ravel()
+        q = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        out = np.empty((len(ids), len(q)), dtype=np.float64)
+        _chk(lib().sa_hdp_state_densities(self._h, _ip(ids), len(ids), _dp(q), len(q), device, _dp(out)), "sa_hdp_state_densities")
+        return out
+
+    def distances(self, metric, device=0, stats=None):
+        """sa_hdp_state_distances: the whole memo over the observed DPs, triangular over the rows of row_of_dp (GPU)"""
+        n = int(self.info.n_observed)
+        out = np.empty(max(n * (n - 1) // 2, 1), dtype=np.float64)
+        ms = C.c_double(0.0)
+        _chk(lib().sa_hdp_state_distances(self._h, int(metric), device, _dp(out), C.byref(ms)), "sa_hdp_state_distances")
+        if stats is not None:
+            stats["kernel_ms"] = ms.value
+        return out[:n * (n - 1) // 2]
+
+    def distance_pairs(self, metric, dp1, dp2, device=0):
+        """sa_hdp_state_distance_pairs: get_dir_proc_distance for pairs of DP ids (GPU)"""
+        a, b = np.ascontiguousarray(dp1, dtype=np.int64).ravel(), np.ascontiguousarray(dp2, dtype=np.int64).ravel()
+        if len(a) != len(b):
+            raise SaError(-1, "distance_pairs: as many first ids as second ids")
+        out = np.empty(max(len(a), 1), dtype=np.float64)
+        _chk(lib().sa_hdp_state_distance_pairs(self._h, int(metric), _ip(a), _ip(b), len(a), device, _dp(out)),
+             "sa_hdp_state_distance_pairs")
+        return out[:len(a)]
+
+    def compare(self, other, dp1, dp2, metric, device=0):
+        """sa_hdp_state_compare: compare_hdp_distrs, this state's grid is the master (GPU)"""
+        a, b = np.ascontiguousarray(dp1, dtype=np.int64).ravel(), np.ascontiguousarray(dp2, dtype=np.int64).ravel()
+        if len(a) != len(b):
+            raise SaError(-1, "compare: as many first ids as second ids")
+        out = np.empty(max(len(a), 1), dtype=np.float64)
+        _chk(lib().sa_hdp_state_compare(self._h, _ip(a), other._h, _ip(b), len(a), int(metric), device, _dp(out)), "sa_hdp_state_compare")
+        return out[:len(a)]
+
     def distr_sample(self, device=0):
         """sa_hdp_state_distr_sample: what one sample of this state adds to every observed DP's collector (GPU)"""
         out = np.zeros((int(self.info.n_observed), int(self.info.grid_length)), dtype=np.float64)
@@ -1283,6 +1334,42 @@ class HdpState:
 
 
 HDP_LAYOUT_FLAT, HDP_LAYOUT_MULTISET, HDP_LAYOUT_MIDDLE_NTS, HDP_LAYOUT_COMPOSITION, HDP_LAYOUT_GROUP_MULTISET = 0, 1, 2, 3, 4
+HDP_METRIC_KL, HDP_METRIC_HELLINGER, HDP_METRIC_L2, HDP_METRIC_SHANNON_JENSEN = 0, 1, 2, 3
+
+
+def hdp_distances(grid, rows, metric, device=0, stats=None):
+    """sa_hdp_distances: all pairs among the rows (n_rows x grid_length, one grid) -- the triangular vector, [(i - 1) * i / 2 + j]
+    for i > j (GPU).  stats (a dict): kernel_ms"""
+    g = np.ascontiguousarray(grid, dtype=np.float64)
+    r = np.ascontiguousarray(rows, dtype=np.float64)
+    if r.ndim != 2 or g.ndim != 1 or r.shape[1] != len(g):
+        raise SaError(-1, "hdp_distances: rows must be n_rows x len(grid)")
+    n = r.shape[0]
+    out = np.empty(max(n * (n - 1) // 2, 1), dtype=np.float64)
+    ms = C.c_double(0.0)
+    _chk(lib().sa_hdp_distances(_dp(g), len(g), _dp(r), n, int(metric), device, _dp(out), C.byref(ms)), "sa_hdp_distances")
+    if stats is not None:
+        stats["kernel_ms"] = ms.value
+    return out[:n * (n - 1) // 2]
+
+
+def hdp_distances_paired(grid, a, b, metric, device=0, stats=None):
+    """sa_hdp_distances_paired: row i of a against row i of b (GPU)"""
+    g = np.ascontiguousarray(grid, dtype=np.float64)
+    pa, pb = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    if pa.ndim != 2 or pa.shape != pb.shape or g.ndim != 1 or pa.shape[1] != len(g):
+        raise SaError(-1, "hdp_distances_paired: a and b must both be n x len(grid)")
+    out = np.empty(max(pa.shape[0], 1), dtype=np.float64)
+    ms = C.c_double(0.0)
+    _chk(lib().sa_hdp_distances_paired(_dp(g), len(g), _dp(pa), _dp(pb), pa.shape[0], int(metric), device, _dp(out), C.byref(ms)),
+         "sa_hdp_distances_paired")
+    if stats is not None:
+        stats["kernel_ms"] = ms.value
+    return out[:pa.shape[0]]
+
+
+def hdp_distances_release():
+    lib().sa_hdp_distances_release()
 
 
 def hdp_nig_params_from_table(table5):

@@ -851,6 +851,13 @@ int sa_hdp_state_kmer_dp(const sa_hdp_state_t *s, const char *kmer) {   /* kmer_
     return (int) id;
 }
 
+int sa_hdp_state_alphabet(const sa_hdp_state_t *s, char *alphabet_out) {
+    if (!s || !alphabet_out || s->alphabet_size < 0 || s->alphabet_size > 63) return SA_EINVAL;
+    memcpy(alphabet_out, s->alphabet, (size_t) s->alphabet_size);
+    alphabet_out[s->alphabet_size] = 0;
+    return SA_OK;
+}
+
 int sa_hdp_state_pass_assignments(sa_hdp_state_t *s, const char *kmers, const double *events, int64_t n) {
     if (!s || !kmers || !events || n < 1) return SA_EINVAL;
     int64_t *ids = malloc(sizeof(int64_t) * (size_t) n);

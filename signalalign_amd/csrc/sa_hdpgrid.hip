@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "signalalign_hip.h"
+#include "sa_hdpdev.h"
 #include "sa_hdpstate.h"
 
 namespace {
@@ -95,26 +96,6 @@ __global__ __launch_bounds__(64) void k_hdp_finalize(const double *__restrict__ 
         const double right = 1.0 / (x[idx + 1] - x[idx]);
         k[idx] = (k[idx] - right * k[idx + 1]) / cc[idx];
     }
-}
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void) hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes > 0 ? bytes : 8) == hipSuccess ? SA_OK : SA_ENOMEM; }
-    int put(const void *src, size_t bytes) {
-        if (alloc(bytes)) return SA_ENOMEM;
-        return (bytes == 0 || hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess) ? SA_OK : SA_ENODEVICE;
-    }
-};
-
-int use_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        (void) hipGetLastError();
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    return hipSetDevice(device) == hipSuccess ? SA_OK : SA_ENODEVICE;
 }
 
 }  // namespace
