@@ -82,6 +82,16 @@ extern "C" {
                                      batch's arrays should be contiguous in the block.  A batch whose covering ranges hold more
                                      than twice the bytes its jobs name (one arena shared by several batches, gaps) is packed
                                      by host threads instead, as without the flag: same results, none of the saving */
+#define SA_FLAG_TWO_DIST_ALL_KERNELS 512u /* a Gaussian model with an SA_EMISSION_TWO_DIST* emission (sa_model_set_emission): every region
+                                     goes to the kernel family it would get with SA_EMISSION_MEAN_ONLY -- register, ring or strip
+                                     kernels -- and that family runs its two-distribution instance, instead of the whole batch
+                                     falling back to the reference-ordered kernels as soon as one region holds an ambiguity
+                                     letter or a band wider than a wave.  Opt-in: without the flag the routing (and so the
+                                     arithmetic) of such a batch is what it was.  Ignored for SA_EMISSION_MEAN_ONLY models, with
+                                     SA_FLAG_EXACT or SA_FLAG_FORCE_GENERIC and by the expectation pass (sa_expect_batch); a batch
+                                     with a region that even a MeanOnly model would send to the memory-resident kernels falls
+                                     back as without the flag.  SA_EUNSUPPORTED with an HDP model.  Required by
+                                     sa_batch_create_noise_scaled. */
 
 typedef struct sa_model sa_model_t; /* replaces StateMachine3 / StateMachine3_HDP (inc/stateMachine.h:150-190) */
 typedef struct sa_batch sa_batch_t;
@@ -233,9 +243,13 @@ int64_t sa_kmer_id(const sa_model_t *m, const char *kmer); /* impl/nanopore_hdp.
  *                          every region of the batch holds one path per cell (sa_align_batch / sa_batch_*; not the expectation
  *                          pass); otherwise, and with SA_FLAG_EXACT, the reference-ordered memory-resident kernels (the batch then
  *                          behaves as with SA_FLAG_EXACT); jobs must hand over event records (event_stride >= 2: the
- *                          noise is a record's second value); the noise columns are the MODEL's, so the reads of a batch share
- *                          one noise scaling (the reference rescales them per read, emissions_signal_scaleNoise: create the
- *                          model from the rescaled table sa_estimate_params leaves). */
+ *                          noise is a record's second value).  With SA_FLAG_TWO_DIST_ALL_KERNELS the ring and strip kernels run
+ *                          two-distribution instances too (k_*_ring<..., TWO>, k_*_strip<..., TWO>) and no region sends the
+ *                          batch to the reference-ordered kernels for its ambiguity letters or its band.  The noise columns
+ *                          are the MODEL's, so the reads of a batch created with sa_batch_create share one noise scaling; the
+ *                          reference rescales them per read (emissions_signal_scaleNoise): hand every job its two factors
+ *                          with sa_batch_create_noise_scaled, or create a model per read from the rescaled table
+ *                          sa_estimate_params leaves (sa_model_clone_with_table). */
 #define SA_EMISSION_MEAN_ONLY 0
 #define SA_EMISSION_TWO_DIST 1
 /*   SA_EMISSION_TWO_DIST_SCALED_MODEL  emissions_signal_strawManGetKmerEventMatchProb (:659-700): the same two distributions on the
@@ -263,6 +277,19 @@ int sa_load_ambig(const char *path, const char **map256);
  * pairs:  rows in the order signalMachine writes them (stable sort by x+y of the reference's list). */
 int sa_batch_create(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs,
                     int64_t n_jobs, const char *const *ambig256, int device, unsigned flags);
+/* sa_batch_create with the noise columns of the model rescaled PER JOB: job j is aligned as if its model were
+ * sa_model_clone_with_table(m, T_j), T_j = emissions_signal_scaleNoise (impl/stateMachine.c:721-741) of m's table with noise[j] --
+ * noise_mean * scale_sd and noise_lambda * var_sd, each product rounded to a double before anything is derived from it.  The two
+ * factors are out7[4] and out7[5] of sa_estimate_params.  What signalMachine --batch --emission twoDist needs: one batch, one
+ * model, every read its own noise scaling.  Requires SA_FLAG_TWO_DIST_ALL_KERNELS, an SA_EMISSION_TWO_DIST* model and event
+ * records (event_stride >= 2); every factor finite and > 0: SA_EINVAL otherwise.  The scaling exists in the register, ring and
+ * strip kernels' two-distribution instances only: a batch with a region none of them takes (SA_FLAG_EXACT, SA_FLAG_FORCE_GENERIC,
+ * threshold 0, a matrix whose storage does not fit, the ring kernels switched off) returns SA_EUNSUPPORTED -- it is never aligned
+ * with the model's own noise without a word.  `noise` is copied. */
+typedef struct sa_noise_scale { double scale_sd, var_sd; } sa_noise_scale_t;   /* out7[4], out7[5] of sa_estimate_params */
+int sa_batch_create_noise_scaled(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs,
+                                 const sa_noise_scale_t *noise /* n_jobs */, int64_t n_jobs,
+                                 const char *const *ambig256, int device, unsigned flags);
 int sa_batch_run(sa_batch_t *b);
 /* sa_batch_create in two halves, for a caller that streams batches (sa_batch_start / sa_batch_wait below).  The first half --
  * input checks, packing and upload of the reads, the planning kernels queued -- runs here; the second -- waiting for the plan,

@@ -17,6 +17,7 @@ FLAG_VC_ROWS = 32
 FLAG_PAIRS8 = 64
 FLAG_SITE_CALLS = 128
 FLAG_POSITION_CALLS = 256
+FLAG_TWO_DIST_ALL_KERNELS = 512
 SITE_MAX_LETTERS = 8
 
 
@@ -128,7 +129,7 @@ SITE_CALL_DTYPE = np.dtype([("x", "<i4"), ("n_letters", "<i4"), ("letters", "S1"
 
 EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alphabet", "sa_model_table5",
            "sa_model_set_to_hdp_expected_values", "sa_model_set_emission", "sa_model_clone_with_table", "sa_kmer_id", "sa_default_ambig", "sa_load_ambig",
-           "sa_batch_create", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
+           "sa_batch_create", "sa_batch_create_noise_scaled", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
            "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
            "sa_plan_check_path_records", "sa_dplan_compare",
            "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
@@ -223,6 +224,9 @@ def lib():
     L.sa_load_ambig.argtypes = [C.c_char_p, C.POINTER(C.c_char_p)]
     L.sa_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64,
                                   C.POINTER(C.c_char_p), C.c_int, C.c_uint]
+    L.sa_batch_create_noise_scaled.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(Params), C.POINTER(Job), dp, C.c_int64,
+                                               C.POINTER(C.c_char_p), C.c_int, C.c_uint]
+    L.sa_model_clone_with_table.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, dp]
     L.sa_batch_create_deferred.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64,
                                   C.POINTER(C.c_char_p), C.c_int, C.c_uint]
     L.sa_batch_run.argtypes = [C.c_void_p]
@@ -415,6 +419,13 @@ class Model:
         """0: MeanOnly (signalMachine's), 1: the two-distribution emission (sa_model_set_emission)."""
         _chk(lib().sa_model_set_emission(self._h, int(emission)), "sa_model_set_emission")
 
+    def clone_with_table(self, table5):
+        """sa_model_clone_with_table: the same model with another emission table (a read's own noise scaling)."""
+        h = C.c_void_p()
+        tb = np.ascontiguousarray(table5, dtype=np.float64)
+        _chk(lib().sa_model_clone_with_table(C.byref(h), self._h, _dp(tb)), "sa_model_clone_with_table")
+        return Model(h)
+
     def set_to_hdp_expected_values(self):
         _chk(lib().sa_model_set_to_hdp_expected_values(self._h), "sa_model_set_to_hdp_expected_values")
 
@@ -522,9 +533,11 @@ class JobArray:
 class Batch:
     """sa_batch_t: plan + HBM-resident inputs; run() launches the kernels."""
 
-    def __init__(self, model, params, jobs, ambig=None, device=0, flags=0, deferred=False):
+    def __init__(self, model, params, jobs, ambig=None, device=0, flags=0, deferred=False, noise=None):
         """deferred=True: sa_batch_create_deferred (the plan is collected on the batch's first use; the job arrays and the
-        ambiguity table are kept alive by this object)."""
+        ambiguity table are kept alive by this object).
+        noise: one (scale_sd, var_sd) per job -- sa_batch_create_noise_scaled (needs FLAG_TWO_DIST_ALL_KERNELS and a
+        two-distribution model; not with deferred)."""
         self._h = C.c_void_p()
         if isinstance(jobs, JobArray):
             self.n_jobs, arr, self._keep = jobs.n, jobs.arr, jobs
@@ -535,6 +548,15 @@ class Batch:
         amb = ambig if ambig is not None else default_ambig()
         self._amb, self._model = amb, model
         self._flags = int(flags)
+        if noise is not None:
+            if deferred:
+                raise ValueError("Batch: noise= and deferred=True do not go together")
+            nz = np.ascontiguousarray(noise, dtype=np.float64).reshape(-1, 2)
+            if nz.shape[0] != self.n_jobs:
+                raise ValueError("Batch: noise= needs one (scale_sd, var_sd) per job")
+            _chk(lib().sa_batch_create_noise_scaled(C.byref(self._h), model._h, C.byref(params), arr, _dp(nz), self.n_jobs, amb, device,
+                                                    flags), "sa_batch_create_noise_scaled")
+            return
         fn, name = (lib().sa_batch_create_deferred, "sa_batch_create_deferred") if deferred else (lib().sa_batch_create, "sa_batch_create")
         _chk(fn(C.byref(self._h), model._h, C.byref(params), arr, self.n_jobs, amb, device, flags), name)
 

@@ -1226,6 +1226,7 @@ enum {
     LC_FAST = 1,               // register kernels
     LC_RING = 2,               // ring kernels: LC_RING + multi * 8 + cap class, cap = 64 * (class + 1)
     LC_STRIP = LC_RING + 16,   // one-path ring-kernel regions taken by the strip kernels (sa_strip.inc)
+    LC_RING_WIDE,              // ring kernels, several paths per cell, rows of SA_RING_WIDE_MAX_ROWPATHS (sa_internal.h)
     LC_N
 };
 struct sa_ids {
@@ -1241,6 +1242,7 @@ static int n_nonempty(const sa_ids *ids, int c0, int c1) {
 static int launch_class(const sa_region_t &R, bool strip_on) {
     if (strip_region(&R, strip_on)) return LC_STRIP;
     if (R.kind == SA_KIND_RING) {
+        if (R.max_rowpaths > SA_RING_MAX_ROWPATHS) return LC_RING_WIDE;
         const int cl = R.max_rowpaths <= 64 ? 0 : (int) ((R.max_rowpaths - 1) / 64);   // <= 7 (SA_RING_MAX_ROWPATHS)
         return LC_RING + (R.max_p > 1 ? 8 : 0) + (cl > 7 ? 7 : cl);
     }
@@ -1353,6 +1355,7 @@ struct sa_batch {
     const sa_job_t *c_jobs = nullptr;
     int64_t c_n = 0;
     const char *const *c_ambig = nullptr;
+    std::vector<sa_noise_scale_t> c_noise;   // sa_batch_create_noise_scaled: every job's two factors (a copy), else empty
     long long c_budget = 0;
     double c_t0 = 0;
     bool c_deferred = false;
@@ -1823,7 +1826,8 @@ struct SaPairsMemo {
 static SaPairsMemo g_pairs_memo;
 
 static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs, int64_t n_jobs,
-                             const char *const *ambig, int device, unsigned flags, bool deferred) {
+                             const char *const *ambig, int device, unsigned flags, bool deferred,
+                             const sa_noise_scale_t *noise = nullptr, bool noise_scaled = false) {
     if (!out || !m || !p) return SA_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -1842,6 +1846,17 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
     // reference-ordered kernels.  (SA_TWO_DIST_FAST_OFF=1: always the reference-ordered kernels, as up to round 5.)
     if (m->emission != 0 && ((flags & (SA_FLAG_EXPECT_INTERNAL | SA_FLAG_FORCE_GENERIC)) || getenv("SA_TWO_DIST_FAST_OFF")))
         flags |= SA_FLAG_EXACT;
+    // SA_FLAG_TWO_DIST_ALL_KERNELS: the ring and strip kernels' two-distribution instances (sa_plan.c plans such a batch's regions as a
+    // MeanOnly model's); nothing to do for a MeanOnly model, no such instance for an HDP model
+    if ((flags & SA_FLAG_TWO_DIST_ALL_KERNELS) && m->hdp) return SA_EUNSUPPORTED;
+    if (noise_scaled) {   // sa_batch_create_noise_scaled: per-job factors on the noise columns (batch_prepare_body applies them)
+        if (!(flags & SA_FLAG_TWO_DIST_ALL_KERNELS) || m->emission == 0 || n_jobs < 0 || (n_jobs > 0 && (!noise || !jobs))) return SA_EINVAL;
+        for (int64_t j = 0; j < n_jobs; j++) {
+            const double a_ = noise[j].scale_sd, b_ = noise[j].var_sd;
+            if (!(a_ > 0.0) || !(b_ > 0.0) || a_ == INFINITY || b_ == INFINITY || jobs[j].event_stride < 2) return SA_EINVAL;
+        }
+        if (flags & SA_FLAG_EXACT) return SA_EUNSUPPORTED;   // (the reference-ordered kernels read the model's own noise columns)
+    }
     if (flags & SA_FLAG_EXPECT_INTERNAL) flags &= ~(SA_FLAG_SITE_CALLS | SA_FLAG_POSITION_CALLS);
     if ((flags & (SA_FLAG_SITE_CALLS | SA_FLAG_POSITION_CALLS)) && (flags & SA_FLAG_VC_ROWS)) return SA_EINVAL;   // (that flag drops the rows the calls are made of)
     if ((flags & SA_FLAG_POSITION_CALLS) && (flags & SA_FLAG_PAIRS8)) return SA_EUNSUPPORTED;   // (an 8-byte record names no path k-mer)
@@ -1860,6 +1875,7 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
 
     sa_batch *b = new sa_batch();
     b->c_m = m; b->c_p = *p; b->c_jobs = jobs; b->c_n = n_jobs; b->c_ambig = ambig; b->c_budget = budget; b->c_t0 = tc0;
+    if (noise_scaled) b->c_noise.assign(noise, noise + n_jobs);
     b->device = device;
     b->flags = flags;
     // the exact totals of a traceback drift away from its speculative total diagonal by diagonal (1.6e-4 per diagonal with the flat
@@ -1919,6 +1935,10 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
 int sa_batch_create(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs, int64_t n_jobs,
                     const char *const *ambig, int device, unsigned flags) {
     return batch_create_impl(out, m, p, jobs, n_jobs, ambig, device, flags, false);
+}
+int sa_batch_create_noise_scaled(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs,
+                                 const sa_noise_scale_t *noise, int64_t n_jobs, const char *const *ambig, int device, unsigned flags) {
+    return batch_create_impl(out, m, p, jobs, n_jobs, ambig, device, flags, false, noise, true);
 }
 int sa_batch_create_deferred(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs, int64_t n_jobs,
                              const char *const *ambig, int device, unsigned flags) {
@@ -2081,8 +2101,17 @@ static int batch_prepare_body(sa_batch *b) {
         static std::atomic<int> batches_created(0);
         if (SaPool::enabled() && batches_created.fetch_add(1) >= 2) sa_plan_use_allocator(plan_pinned_alloc, plan_pinned_free);
         int rc = sa_plan_build(&pl, m, p, jobs, n_jobs, ambig, flags | SA_FLAG_DEVICE_XC_INTERNAL, budget);
-        if (rc == SA_OK && m->emission != 0 && !(flags & SA_FLAG_EXACT) && pl->n_fast_regions != pl->n_regions) {
-            // the two-distribution emission off the register kernels: the reference-ordered kernels for the whole batch
+        // (SA_FLAG_TWO_DIST_ALL_KERNELS: the ring and strip kernels have it too; what is left are the regions that a MeanOnly model
+        // would send to the memory-resident kernels as well)
+        const long long n_two_regions = pl ? pl->n_fast_regions + ((flags & SA_FLAG_TWO_DIST_ALL_KERNELS) ? pl->n_ring_regions : 0) : 0;
+        if (rc == SA_OK && m->emission != 0 && !(flags & SA_FLAG_EXACT) && n_two_regions != pl->n_regions) {
+            // the two-distribution emission off these kernels: the reference-ordered kernels for the whole batch -- which know
+            // nothing of a noise scaling per job
+            if (!b->c_noise.empty()) {
+                sa_plan_free(pl);
+                sa_plan_use_allocator(nullptr, nullptr);
+                return SA_EUNSUPPORTED;
+            }
             sa_plan_free(pl);
             pl = nullptr;
             b->flags |= SA_FLAG_EXACT;
@@ -2224,13 +2253,30 @@ static int batch_prepare_body(sa_batch *b) {
                     const double n = evn[(size_t) (2 * y)];
                     two[(size_t) (4 * y)] = n; two[(size_t) (4 * y + 1)] = 1.0 / n; two[(size_t) (4 * y + 2)] = 1.5 * evn[(size_t) (2 * y + 1)];
                 }
-                for (long long i = 0; i < pl->n_pid; i++) {
+                for (long long i = 0; i < pl->n_pid && b->c_noise.empty(); i++) {
                     const int id = pl->pid[i];
                     if (id < 0) continue;
                     double *q = &two[(size_t) (4 * (ne + i))];
                     q[0] = 0.5 * (nz[(size_t) (3 * id + 2)] - 1.8378770664093453);
                     q[1] = 1.0 / nz[(size_t) (3 * id)];
                     q[2] = 0.5 * nz[(size_t) (3 * id + 1)];
+                }
+                // sa_batch_create_noise_scaled: the same from the job's own table, emissions_signal_scaleNoise of the model's
+                // (impl/stateMachine.c:721-741: noise_mean * scale_sd, noise_lambda * var_sd, each product a double before anything is
+                // derived from it).  A region's path-space indices are its own (pid_off, poff), and a region knows its job.
+                for (long long r = 0; r < pl->n_regions && !b->c_noise.empty(); r++) {
+                    const sa_region_t *R = &pl->regions[r];
+                    const sa_noise_scale_t ns = b->c_noise[(size_t) R->job];
+                    const long long n_paths = pl->poff[R->poff_off + R->lX + 1];
+                    for (long long i = R->pid_off; i < R->pid_off + n_paths; i++) {
+                        const int id = pl->pid[i];
+                        if (id < 0) continue;
+                        const double mean = nz[(size_t) (3 * id)] * ns.scale_sd, lambda = nz[(size_t) (3 * id + 1)] * ns.var_sd;
+                        double *q = &two[(size_t) (4 * (ne + i))];
+                        q[0] = 0.5 * (log(lambda) - 1.8378770664093453);
+                        q[1] = 1.0 / mean;
+                        q[2] = 0.5 * lambda;
+                    }
                 }
                 b->two_xn_off = ne;
                 TRY(upload(&b->d_two, two.data(), (long long) two.size()));
@@ -2605,9 +2651,13 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
     if (Ls.n)
         launch_bwd_strip(P, b->d_ids + Ls.off, Ls.n, st, b->d_seam + b->seam_bwd_off,
                          make_strip_t(P, pl->n_ev + 8, b->seam_cap_bwd, G.seam_first));
+    if (G.ids[LC_RING_WIDE].n) {
+        const int rcl = launch_bwd_ring(P, b->d_ids + G.ids[LC_RING_WIDE].off, G.ids[LC_RING_WIDE].n, st, SA_RING_WIDE_MAX_ROWPATHS, true);
+        if (rcl) return rcl;
+    }
     for (int cl = 15; cl >= 0; cl--) {   // widest (longest-running) classes first
         const sa_ids &L = G.ids[LC_RING + cl];
-        if (L.n) launch_bwd_ring(P, b->d_ids + L.off, L.n, st, ring_class(cl).cap, ring_class(cl).multi);
+        if (L.n) { const int rcl = launch_bwd_ring(P, b->d_ids + L.off, L.n, st, ring_class(cl).cap, ring_class(cl).multi); if (rcl) return rcl; }
     }
     if (Lf.n) { const int rcl = launch_bwd_fast(P, b->d_ids + Lf.off, Lf.n, st); if (rcl) return rcl; }
     HIPCHK(hipEventRecord(b->gev[4 * g + 1], st));
@@ -2683,10 +2733,17 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
                 launch_fwd_strip(P, b->d_ids + Ls.off, Ls.n, lanes[0], b->d_seam, make_strip_t(P, pl->n_ev + 8, b->seam_cap, 0));
                 which = n_lanes > 1 ? 1 : 0;
             }
+            if (C.ids[LC_RING_WIDE].n) {
+                const int rcl = launch_fwd_ring(P, b->d_ids + C.ids[LC_RING_WIDE].off, C.ids[LC_RING_WIDE].n, lanes[n_lanes > 1 ? which : 0],
+                                                SA_RING_WIDE_MAX_ROWPATHS, true);
+                if (rcl) return rcl;
+                which = (which + 1) % (n_lanes > 1 ? n_lanes : 1);
+            }
             for (int cl = 15; cl >= 0; cl--) {
                 const sa_ids &L = C.ids[LC_RING + cl];
                 if (L.n) {
-                    launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], ring_class(cl).cap, ring_class(cl).multi);
+                    const int rcl = launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], ring_class(cl).cap, ring_class(cl).multi);
+                    if (rcl) return rcl;
                     which = (which + 1) % (n_lanes > 1 ? n_lanes : 1);
                 }
             }

@@ -72,7 +72,12 @@ typedef struct sa_row {
  * diagonal's record is one 16-byte scalar load), and rows[N + 1] is a sentinel whose offset closes the last diagonal. */
 enum { SA_KIND_GENERIC = 0, SA_KIND_FAST = 1, SA_KIND_RING = 2 };
 #define SA_RING_MAX_ROWPATHS 512      /* widest diagonal (cell-paths) the LDS ring takes: 3 rows x 3 messages x 8 B x 512 = 36 KB */
-#define SA_RING_WIDE_FRACTION 0.5     /* one-path regions go to the ring kernels when more than this share of their cells lies on
+/* ... and the widest one of a region with several paths per cell in a two-distribution batch under SA_FLAG_TWO_DIST_ALL_KERNELS (a
+ * three-way code at every C: up to 81 paths per cell, 2023 cell-paths on a diagonal of the reference's whole-read known answer): 144 KB
+ * of LDS ring; the backward sweep's checkpoint sums then live in the segment's global scratch (k_bwd_ring<WIDE>, sa_ring.inc).  One
+ * launch class of its own, rows of SA_RING_WIDE_MAX_ROWPATHS entries on four waves. */
+#define SA_RING_WIDE_MAX_ROWPATHS 2048
+#define SA_RING_WIDE_FRACTION 0.5    /* one-path regions go to the ring kernels when more than this share of their cells lies on
                                        * diagonals the register kernels cannot hold (SA_PK_FWD clear) */
 
 /* per cell-path record of SA_KIND_RING regions with several paths per cell (index: pid_off + poff[x] + path).

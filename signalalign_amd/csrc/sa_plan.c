@@ -721,10 +721,16 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
     const int expect_ = (pl->flags & SA_FLAG_EXPECT_INTERNAL) != 0;
     /* (the two-distribution emission exists in the register kernels and the reference-ordered ones: a one-path region with a wide
      * band stays a register-kernel region -- their in-kernel memory-resident path --, one with several paths per cell is not
-     * SA_KIND_FAST and sends the batch to the reference-ordered kernels, sa_hip.hip batch_prepare_body) */
-    int ring_ok = !(pl->flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC)) && hdp_plane_ok && m->emission == 0 &&
+     * SA_KIND_FAST and sends the batch to the reference-ordered kernels, sa_hip.hip batch_prepare_body -- unless the batch asks for
+     * the ring and strip kernels' two-distribution instances, SA_FLAG_TWO_DIST_ALL_KERNELS: the routing of a MeanOnly model then) */
+    /* (such a batch's regions with several paths per cell: rows of up to SA_RING_WIDE_MAX_ROWPATHS, sa_internal.h -- a MeanOnly
+     * model's routing is what it was) */
+    const int64_t ring_max_rowpaths = (m->emission != 0 && (pl->flags & SA_FLAG_TWO_DIST_ALL_KERNELS) && maxP > 1 && !expect_ &&
+                                       m->hdp == NULL) ? SA_RING_WIDE_MAX_ROWPATHS : SA_RING_MAX_ROWPATHS;
+    int ring_ok = !(pl->flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC)) && hdp_plane_ok &&
+                  (m->emission == 0 || (pl->flags & SA_FLAG_TWO_DIST_ALL_KERNELS)) &&
                   (!expect_ || (maxP > 1 && m->hdp == NULL)) &&
-                  max_rowpaths <= SA_RING_MAX_ROWPATHS && foff + 1 <= SA_FAST_MAX_CELLS && ring_env_on() &&
+                  max_rowpaths <= ring_max_rowpaths && foff + 1 <= SA_FAST_MAX_CELLS && ring_env_on() &&
                   (maxP == 1 || (maxP <= 255 && ambig_options_distinct(ambig)));
     int use_ring = 0;
     if (ring_ok && maxP > 1) use_ring = 1;
@@ -807,7 +813,9 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
         S->cand_off = pl->n_cand;
         pl->n_cand += cap;
         S->bscratch_off = pl->n_bscratch;
-        if (R->kind != SA_KIND_RING) pl->n_bscratch += 12 * (int64_t) max_rowpaths; /* the ring kernels keep backward rows in LDS */
+        /* the ring kernels keep backward rows in LDS (a wide ring's checkpoint sums: 6 rows of its capacity, k_bwd_ring<WIDE>) */
+        if (R->kind != SA_KIND_RING) pl->n_bscratch += 12 * (int64_t) max_rowpaths;
+        else if (max_rowpaths > SA_RING_MAX_ROWPATHS) pl->n_bscratch += 6 * (int64_t) SA_RING_WIDE_MAX_ROWPATHS;
         traced_to = S->from;
     }
     R->n_seg = (int32_t) (pl->n_segs - R->seg_off);

@@ -46,6 +46,7 @@ struct RingT {
                     // total on the traceback's first diagonal, taken between the forward and the backward sweep)
     double slack;   // candidates are the cell-paths with forward + backward >= spec - slack + log(threshold)
     int all_planes; // forward: keep all three planes of every diagonal (the expectation pass reads them)
+    double *wscr;   // backward, WIDE: the segments' global scratch (sa_seg_t.bscratch_off) -- the checkpoint sums that do not fit in LDS
 };
 
 #define RING_XTRA 2   // doubles behind the logAdd table: [0] holds -inf (neighbour outside its row), [1] is scrap
@@ -61,6 +62,18 @@ struct RingIn {
     int po;        // backward, several paths per cell: poff[x] (the path index of a candidate is g - poff[x])
     int p0, npd;   // backward expectation pass: first legal predecessor in column x - 1 and their number (stride as above)
 };
+
+// two-distribution emission (the TWO instances): the noise constants of the cell-path's k-mer and of the cell's event
+// (FastT.two_xn_off), requested with the other inputs.  Kept beside RingIn: the other instances never name them.
+struct RingTwo {
+    double4 cn, n3;
+};
+// The inverse-Gaussian term of the event's noise (emit_two, sa_fast.inc: the same operations in the same order); the strip
+// kernels add the same term, bit for bit.
+__device__ __forceinline__ double two_l2(const double4 &cn, const double4 &n3) {
+    const double a = fma(n3.x, cn.y, -1.0);
+    return cn.x - n3.z - cn.z * (a * a) * n3.y;
+}
 
 // The per-path record of a cell-path is requested TWO diagonals ahead and its other inputs one diagonal ahead: the event's
 // address depends on the record's column, and a dependent pair of loads inside one diagonal is a memory latency in the
@@ -80,9 +93,12 @@ typedef const __attribute__((address_space(1))) double *ring_gd_t;
 // HDP: the emission itself arrives instead of constants and event -- one 8-byte load from the region's emission plane
 // (k_emit_hdp_ring, sa_fast.inc: value j of the diagonal at its offset + j; pe8 = byte offset of the lane's value, or of the
 // plane's -inf sentinel for a lane without a cell-path)
-template <bool MULTI, bool BWD, bool HDP = false>
+// TWO: xn / en = the region's position and event halves of the noise constants, en_pad = the last entry of the events' padding (1.0
+// throughout).  A lane without a k-mer/event pair reads that entry and the region's NULL position (zeros): both finite.
+template <bool MULTI, bool BWD, bool HDP = false, bool TWO = false>
 __device__ __forceinline__ void ring_request(RingIn &in, const u32x4 rec, bool act, int g, int d, ring_xc_t rs_xc, ring_ev_t rs_ev,
-                                             rsrc_t rs_E, unsigned pe8) {
+                                             rsrc_t rs_E, unsigned pe8, RingTwo *tw = nullptr, ring_xc_t rs_xn = nullptr,
+                                             ring_ev_t rs_en = nullptr, ring_ev_t en_pad = nullptr) {
     in.x = g; in.a0 = BWD ? g + 1 : g - 1; in.na = 1; in.stride = 0; in.po = 0; in.p0 = g - 1; in.npd = 1;
     if (MULTI) {
         // all four words stay live up to here: the register of a word this direction does not use would otherwise be handed
@@ -107,6 +123,16 @@ __device__ __forceinline__ void ring_request(RingIn &in, const u32x4 rec, bool a
         in.c.z = __hiloint2double((int) b.y, (int) b.x); in.c.w = __hiloint2double((int) b.w, (int) b.z);
         in.e = *(ring_gd_t) (rs_ev + ((act && y >= 1) ? (unsigned) (y - 1) : 0u) * 8u);
     }
+    if (TWO) {
+        const bool ok = act && y >= 1;
+        const ring_gq_t pn = (ring_gq_t) (rs_xn + (ok ? (unsigned) g : 0u) * 32u);
+        const ring_gq_t pe = (ring_gq_t) (ok ? rs_en + (unsigned) (y - 1) * 32u : en_pad);
+        const u32x4 a = pn[0], b = pn[1], c_ = pe[0], d_ = pe[1];
+        tw->cn.x = __hiloint2double((int) a.y, (int) a.x); tw->cn.y = __hiloint2double((int) a.w, (int) a.z);
+        tw->cn.z = __hiloint2double((int) b.y, (int) b.x); tw->cn.w = 0.0;
+        tw->n3.x = __hiloint2double((int) c_.y, (int) c_.x); tw->n3.y = __hiloint2double((int) c_.w, (int) c_.z);
+        tw->n3.z = __hiloint2double((int) d_.y, (int) d_.x); tw->n3.w = 0.0;
+    }
 }
 
 // LDS byte address of entry idx of a row plane, or of the -inf cell when idx is outside [0, n)
@@ -130,7 +156,9 @@ __device__ __forceinline__ unsigned lds_base(const void *p) { return (unsigned) 
 // which leaves the sums unchanged exactly): every 8th / 40th CpG ambiguous, 2000 reads: forward 10.7 -> 9.0 / 10.2 -> 7.5 ms,
 // backward 12.8 -> 12.3 / 9.9 -> 8.9 ms.  One instance with the test inside cost the dense regions 1.5 % (the branch splits the
 // diagonal's code), both loops in one kernel twenty registers (88 -> 108: four waves per SIMD instead of five).
-template <bool MULTI, int K, bool HDP, bool DENSE = true>
+// TWO (Gaussian models only): the two-distribution emission -- E_all is then the buffer of noise constants (FastT.two_xn_off),
+// indexed in path space like the position constants: every path of a cell has its own k-mer, hence its own noise mean and lambda.
+template <bool MULTI, int K, bool HDP, bool DENSE = true, bool TWO = false>
 __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict__ regions, const sa_row_t *__restrict__ rows_all,
                                                   const int *__restrict__ pk_all, const sa_prec_t *__restrict__ prec_all,
                                                   const double4 *__restrict__ xc_all, const double *__restrict__ ev_all,
@@ -170,6 +198,9 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
     const unsigned OOB = 0xfffffff0u;
     const rsrc_t rs_E = make_rsrc(HDP ? (const void *) (E_all + R->f_base) : (const void *) ev_all);   // HDP: the region's emission plane
     const unsigned sentinel8 = C8 - 8u;
+    const ring_xc_t rs_xn = TWO ? (ring_xc_t) (reinterpret_cast<const double4 *>(E_all) + T.two_xn_off + R->pid_off) : rs_xc;
+    const ring_ev_t rs_en = TWO ? (ring_ev_t) (reinterpret_cast<const double4 *>(E_all) + R->ev_off) : rs_ev;
+    const ring_ev_t en_pad = TWO ? (ring_ev_t) (reinterpret_cast<const double4 *>(E_all) + T.two_xn_off - 1) : rs_ev;
     const double cx_m = SA_LOG_GAPX + T.t_mx, cx_x = SA_LOG_GAPX + T.t_xx;
     const unsigned ninf_a = lds_base(LT + LA_TAB_DOUBLES), scrap_a = ninf_a + 8u;
     // (round 4, forward sweep only -- in the backward sweep the same change measured 1-2 % slower) every plane of a ring row ends
@@ -232,6 +263,7 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
     const int n_seg = R->n_seg;
     int sg_k = 0, sg_next = n_seg > 0 ? (int) segs_r[0].start : 0x7fffffff;
     RingIn A[K], B[K];
+    RingTwo An[TWO ? K : 1], Bn[TWO ? K : 1];   // (the other instances: one unused entry)
     u32x4 rq[K];   // per-path records of diagonal d + 1 (behind the request below: d + 2)
     int pkc;
     {   // inputs of diagonal 1
@@ -240,8 +272,8 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
         for (int k = 0; k < K; k++) {
             const int j = tid + k * nthr;
             const bool act = j < np;
-            ring_request<MULTI, false, HDP>(A[k], ring_rec<MULTI>(rs_pr, g0 + j), act, g0 + (act ? j : 0), 1, rs_xc, rs_ev, rs_E,
-                                            act ? (unsigned) (r1.z + j) * 8u : sentinel8);
+            ring_request<MULTI, false, HDP, TWO>(A[k], ring_rec<MULTI>(rs_pr, g0 + j), act, g0 + (act ? j : 0), 1, rs_xc, rs_ev, rs_E,
+                                                 act ? (unsigned) (r1.z + j) * 8u : sentinel8, &An[TWO ? k : 0], rs_xn, rs_en, en_pad);
             rq[k] = ring_rec<MULTI>(rs_pr, r2.w + j);
         }
         pkc = __builtin_amdgcn_readlane(pkt, 1);
@@ -251,7 +283,7 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
     int d = 1;
     // one diagonal: `cur` was requested one diagonal earlier, `nxt` receives the request for d + 1 (harmless behind the
     // last diagonal: the sentinel row has no cell-path, every lane asks for entry 0)
-    auto half = [&](RingIn (&cur)[K], RingIn (&nxt)[K]) {
+    auto half = [&](RingIn (&cur)[K], RingIn (&nxt)[K], RingTwo (&curn)[TWO ? K : 1], RingTwo (&nxtn)[TWO ? K : 1]) {
         { const unsigned t = b2; b2 = b1; b1 = b0; b0 = t; }
         rd = r1; r1 = r2;
         const int idx = d + 2 <= N + 1 ? d + 2 : N + 1;
@@ -274,8 +306,8 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
             for (int k = 0; k < K; k++) {
                 const int j = tid + k * nthr;
                 const bool act = j < npn;
-                ring_request<MULTI, false, HDP>(nxt[k], rq[k], act, g0n + (act ? j : 0), d + 1, rs_xc, rs_ev, rs_E,
-                                                act ? (unsigned) (r1.z + j) * 8u : sentinel8);
+                ring_request<MULTI, false, HDP, TWO>(nxt[k], rq[k], act, g0n + (act ? j : 0), d + 1, rs_xc, rs_ev, rs_E,
+                                                     act ? (unsigned) (r1.z + j) * 8u : sentinel8, &nxtn[TWO ? k : 0], rs_xn, rs_en, en_pad);
                 rq[k] = ring_rec<MULTI>(rs_pr, r2.w + j);
             }
             pkc = pkn1;
@@ -291,6 +323,10 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
             const int g = g0 + (act ? j : 0);
             double lM, lY_;
             emit_fast<HDP>(in.c, in.e, lM, lY_);
+            if (TWO) {
+                const double l2 = two_l2(curn[k].cn, curn[k].n3);
+                lM += l2; lY_ += l2;
+            }
             int i2 = in.a0 - g0_2, i1 = in.a0 - g0_1;
             const int iu = g - g0_1;
             double m, xg, yg;
@@ -379,10 +415,10 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
         }
     };
     while (d <= N) {
-        half(A, B);
+        half(A, B, An, Bn);
         next_tile();
         if (d > N) break;
-        half(B, A);
+        half(B, A, Bn, An);
         next_tile();
     }
 }
@@ -400,7 +436,11 @@ __global__ __launch_bounds__(256) void k_fwd_ring(const sa_region_t *__restrict_
 // (the forward sweep of such a batch keeps all three on every diagonal), the legal predecessors from the per-path record.  Sums
 // are kept per lane, scaled by the traceback's speculative total (any scale near the totals will do: sa_expect_batch rescales
 // with the exact total of each checkpoint group, k_expect_reduce), and flushed per checkpoint group (gsum / gmc).
-template <bool MULTI, int K, bool HDP, bool EXPECT = false, bool DENSE = true>
+// TWO: as in k_fwd_ring (never with HDP or EXPECT).
+// WIDE (several paths per cell, TWO, K = 8 on four waves: rows of SA_RING_WIDE_MAX_ROWPATHS cell-paths): the ring alone is 144 KB of
+// LDS, so the two copies of a checkpoint diagonal's sums (scr) live in the segment's global scratch instead.  They are written in front
+// of a diagonal's barrier and read behind it by the same workgroup -- the barrier orders them --, on two diagonals in ten.
+template <bool MULTI, int K, bool HDP, bool EXPECT = false, bool DENSE = true, bool TWO = false, bool WIDE = false>
 __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict__ regions, const sa_seg_t *__restrict__ segs,
                                                   const sa_row_t *__restrict__ rows_all, const int *__restrict__ poff_all,
                                                   const sa_ck_t *__restrict__ cks, const sa_prec_t *__restrict__ prec_all,
@@ -426,6 +466,7 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
     const int seg = __builtin_amdgcn_readfirstlane(seg_ids[blockIdx.x]);
     const sa_seg_t *S = &segs[seg];
     const sa_region_t *R = &regions[S->region];
+    if (WIDE) scr = RT.wscr + S->bscratch_off;
     if (tid == 0) {   // endStateProb / raggedEndStateProb (impl/stateMachine.c:1145-1173)
         const bool ragged = S->at_end && R->ragged_r;
         s_end[0] = ragged ? (T.t_mx + T.t_my) / 2.0 : T.t_mm;
@@ -455,6 +496,9 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
     const rsrc_t rs_pr = MULTI ? make_rsrc_n(prec_all + R->pid_off, 16u * (unsigned) poff[R->lX + 1]) : make_rsrc(rows_all);
     const unsigned C8 = (unsigned) C * 8u;
     const rsrc_t rs_E = make_rsrc(HDP ? (const void *) (E_all + R->f_base) : (const void *) ev_all);   // HDP: the region's emission plane
+    const ring_xc_t rs_xn = TWO ? (ring_xc_t) (reinterpret_cast<const double4 *>(E_all) + T.two_xn_off + R->pid_off) : rs_xc;
+    const ring_ev_t rs_en = TWO ? (ring_ev_t) (reinterpret_cast<const double4 *>(E_all) + R->ev_off) : rs_ev;
+    const ring_ev_t en_pad = TWO ? (ring_ev_t) (reinterpret_cast<const double4 *>(E_all) + T.two_xn_off - 1) : rs_ev;
     const int start = (int) S->start, from = (int) S->from, to = (int) S->to;
     gu32x2_t *my_cands = (gu32x2_t *) (cands + S->cand_off);   // 24-byte records, written as a 16-byte and an 8-byte store
     if (K == 1) asm volatile("" : "+v"(my_cands));
@@ -508,6 +552,7 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
     int tck = start - from, cki = 0;   // (start >= from)
     int4 rup = rows4[start + 1], re = rows4[start], rdn = rows4[start - 1 >= 0 ? start - 1 : 0];   // rows e+1, e, e-1
     RingIn A[K], B[K];
+    RingTwo An[TWO ? K : 1], Bn[TWO ? K : 1];   // (the other instances: one unused entry)
     u32x4 rq[K];   // per-path records of diagonal e - 1 (behind the request of a diagonal: e - 2)
     int g0nn = rows4[start - 2 >= 0 ? start - 2 : 0].w;   // first path of the row two below
     {   // inputs of diagonal `start`
@@ -518,8 +563,8 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
         for (int k = 0; k < K; k++) {
             const int j = tid + k * nthr;
             const bool act = j < np;
-            ring_request<MULTI, true, HDP>(A[k], ring_rec<MULTI>(rs_pr, g0 + j), act, g0 + (act ? j : 0), start, rs_xc, rs_ev, rs_E,
-                                           act ? (unsigned) (re.z + j) * 8u : C8 - 8u);
+            ring_request<MULTI, true, HDP, TWO>(A[k], ring_rec<MULTI>(rs_pr, g0 + j), act, g0 + (act ? j : 0), start, rs_xc, rs_ev, rs_E,
+                                                act ? (unsigned) (re.z + j) * 8u : C8 - 8u, &An[TWO ? k : 0], rs_xn, rs_en, en_pad);
             if (MULTI) A[k].po = poff[act ? (unsigned) A[k].x : 0u];
             rq[k] = ring_rec<MULTI>(rs_pr, rdn.w + j);
             A[k].fm = buf_load_f64_stream(rs_F, (act && wf) ? (unsigned) j * 8u + (unsigned) re.z * 8u : C8 - 8u, 0);   // else: -inf sentinel
@@ -541,7 +586,7 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
     }
 
     int e = start;
-    auto half = [&](RingIn (&cur)[K], RingIn (&nxt)[K], const int2 &pcur, int2 &pnxt) {
+    auto half = [&](RingIn (&cur)[K], RingIn (&nxt)[K], const int2 &pcur, int2 &pnxt, RingTwo (&curn)[TWO ? K : 1], RingTwo (&nxtn)[TWO ? K : 1]) {
         { const unsigned t = b2; b2 = b1; b1 = b0; b0 = t; }
         const int g0 = re.w, np = rup.z - re.z;
         const unsigned fo8 = (unsigned) re.z * 8u;
@@ -566,8 +611,8 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
             for (int k = 0; k < K; k++) {
                 const int j = tid + k * nthr;
                 const bool act = j < npn;
-                ring_request<MULTI, true, HDP>(nxt[k], rq[k], act, g0n + (act ? j : 0), e - 1, rs_xc, rs_ev, rs_E,
-                                               act ? (unsigned) (rdn.z + j) * 8u : C8 - 8u);
+                ring_request<MULTI, true, HDP, TWO>(nxt[k], rq[k], act, g0n + (act ? j : 0), e - 1, rs_xc, rs_ev, rs_E,
+                                                    act ? (unsigned) (rdn.z + j) * 8u : C8 - 8u, &nxtn[TWO ? k : 0], rs_xn, rs_en, en_pad);
                 if (MULTI) nxt[k].po = poff[act ? (unsigned) nxt[k].x : 0u];   // with the request: no load behind the candidate test
                 rq[k] = ring_rec<MULTI>(rs_pr, g0nn + j);
                 nxt[k].fm = buf_load_f64_stream(rs_F, (act && wf) ? (unsigned) j * 8u + (unsigned) rdn.z * 8u : C8 - 8u, 0);
@@ -596,6 +641,10 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
             const int a0 = MULTI ? in.a0 : g + 1;
             double lM, lY_;
             emit_fast<HDP>(in.c, in.e, lM, lY_);
+            if (TWO) {
+                const double l2 = two_l2(curn[k].cn, curn[k].n3);
+                lM += l2; lY_ += l2;
+            }
             // EXPECT (round 6): the forward states the expectation terms of this cell-path need -- lower neighbour (x - 1, y) on e - 1 and
             // middle neighbour (x - 1, y - 1) on e - 2 for its first two legal predecessor paths, upper neighbour (x, y - 1) on e - 1 for its
             // own path -- are requested HERE, in front of the diagonal's arithmetic, with an address select instead of a branch (no
@@ -782,9 +831,9 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
         e--;
     };
     while (e > to) {
-        half(A, B, PA, PB);
+        half(A, B, PA, PB, An, Bn);
         if (e <= to) break;
-        half(B, A, PB, PA);
+        half(B, A, PB, PA, Bn, An);
     }
     __syncthreads();
     if (EXPECT) {
@@ -797,11 +846,8 @@ __global__ __launch_bounds__(256) void k_bwd_ring(const sa_region_t *__restrict_
 
 // waves per workgroup and cell-paths per thread for a ring of `cap` entries per row
 static int ring_waves(int cap) {
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("SA_RING_WAVES");   // tuning / test hook
-        forced = e ? atoi(e) : 0;
-    }
+    const char *e = getenv("SA_RING_WAVES");   // tuning / test hook, read at every launch like SA_RING / SA_STRIP
+    const int forced = e ? atoi(e) : 0;
     if (forced == 1 || forced == 2 || forced == 4) return forced;
     return cap <= 64 ? 1 : (cap <= 128 ? 2 : 4);
 }
@@ -816,6 +862,7 @@ static RingT make_ring_t(const DevPlan &P, int cap, bool all_planes) {
     RT.spec = P.spec;
     RT.slack = P.spec_slack;
     RT.all_planes = all_planes;
+    RT.wscr = P.bscratch;
     return RT;
 }
 // calls f(std::integral_constant<int, K>()) with the instance K -- cell-paths per thread and diagonal, 1, 2, 4 or 8 -- that
@@ -829,42 +876,90 @@ static void with_ring_k(int cap, int waves, Fn f) {
     else f(std::integral_constant<int, 8>());
 }
 
-// One workgroup per region (forward) / segment (backward).  cap: cell-paths per ring row, a multiple of 64 up to 512; multi:
-// several paths per cell, where the dense and then the sparse instance run over the same list (DENSE above k_fwd_ring).
-static void launch_fwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi) {
-    const int waves = ring_waves(cap);
+// a launch with more dynamic LDS than the default limit of a kernel: say so first
+template <typename Kern>
+static void ring_lds_limit(Kern k, size_t bytes) {
+    if (bytes > 64u * 1024u) (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+}
+// the wide class (SA_RING_WIDE_MAX_ROWPATHS, sa_internal.h) exists for the two-distribution instances with several paths per cell
+// only: the planner sends no other region there, and a launch without a kernel is an error (SA_EUNSUPPORTED from the launch)
+static int ring_wide(int cap, bool multi, bool two, bool *wide) {
+    *wide = cap > SA_RING_MAX_ROWPATHS;
+    if (*wide && (!multi || !two || cap != SA_RING_WIDE_MAX_ROWPATHS)) {
+        fprintf(stderr, "[signalalign_hip] no ring kernel for rows of %d cell-paths (multi %d, two-distribution %d)\n", cap, (int) multi, (int) two);
+        return SA_EUNSUPPORTED;
+    }
+    return SA_OK;
+}
+
+// One workgroup per region (forward) / segment (backward).  cap: cell-paths per ring row, a multiple of 64 up to 512 (or the wide
+// class's 2048); multi: several paths per cell, where the dense and then the sparse instance run over the same list (DENSE above
+// k_fwd_ring).
+static int launch_fwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi) {
+    bool wide_ = false;
+    const int rcw = ring_wide(cap, multi, P.two != nullptr && !P.m.hdp, &wide_);
+    if (rcw) return rcw;
+    const int waves = wide_ ? RING_MAX_WAVES : ring_waves(cap);   // (wide: K = 8 on four waves, whatever SA_RING_WAVES says)
     const RingT RT = make_ring_t(P, cap, P.expect);
     const bool hdp = P.m.hdp;
+    const bool two = P.two != nullptr;   // the two-distribution emission (never with an HDP model)
     with_ring_k(cap, waves, [&](auto KK) {
         constexpr int K = decltype(KK)::value;
         auto launch = [&](auto k) {
+            ring_lds_limit(k, ring_lds_fwd(cap));
             hipLaunchKernelGGL(k, dim3(n), dim3(64 * waves), ring_lds_fwd(cap), st, P.regions, P.rows, P.pk, P.prec,
                                reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, RT, ids, n, P.poff,
-                               hdp ? (const double *) P.E : nullptr, P.segs);
+                               hdp ? (const double *) P.E : P.two, P.segs);
         };
-        if (multi) {
+        if (two) {
+            if (multi) {
+                launch(k_fwd_ring<true, K, false, true, true>);
+                launch(k_fwd_ring<true, K, false, false, true>);
+            } else {
+                launch(k_fwd_ring<false, K, false, true, true>);
+            }
+        } else if (multi) {
             launch(hdp ? k_fwd_ring<true, K, true> : k_fwd_ring<true, K, false>);
             launch(hdp ? k_fwd_ring<true, K, true, false> : k_fwd_ring<true, K, false, false>);
         } else {
             launch(hdp ? k_fwd_ring<false, K, true> : k_fwd_ring<false, K, false>);
         }
     });
+    return SA_OK;
 }
 // the expectation pass (P.expect) takes the EXPECT instance for several paths per cell (Gaussian emissions)
-static void launch_bwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi) {
-    const int waves = ring_waves(cap);
+static int launch_bwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t st, int cap, bool multi) {
     const bool expect = P.expect && multi;
+    bool wide_ = false;
+    const int rcw = ring_wide(cap, multi, P.two != nullptr && !expect && !P.m.hdp, &wide_);
+    if (rcw) return rcw;
+    const int waves = wide_ ? RING_MAX_WAVES : ring_waves(cap);
+    const size_t lds = ring_lds_bwd(cap, multi && !wide_);
     const RingT RT = make_ring_t(P, cap, expect);
     const bool hdp = P.m.hdp && !expect;
+    const bool two = P.two != nullptr && !expect;   // (the expectation pass of such a model never gets here: reference-ordered kernels)
     with_ring_k(cap, waves, [&](auto KK) {
         constexpr int K = decltype(KK)::value;
         auto launch = [&](auto k) {
-            hipLaunchKernelGGL(k, dim3(n), dim3(64 * waves), ring_lds_bwd(cap, multi), st, P.regions, P.segs, P.rows, P.poff, P.cks,
+            ring_lds_limit(k, lds);
+            hipLaunchKernelGGL(k, dim3(n), dim3(64 * waves), lds, st, P.regions, P.segs, P.rows, P.poff, P.cks,
                                P.prec, reinterpret_cast<const double4 *>(P.xc), P.ev, (const double *) P.F, P.vbuf, P.cands,
-                               P.cand_count, P.overflow, RT, ids, n, hdp ? (const double *) P.E : nullptr,
+                               P.cand_count, P.overflow, RT, ids, n, hdp ? (const double *) P.E : P.two,
                                expect ? P.gsum : nullptr, expect ? P.gmc : nullptr);
         };
-        if (expect) {
+        if (wide_) {
+            if constexpr (K == 8) {
+                launch(k_bwd_ring<true, 8, false, false, true, true, true>);
+                launch(k_bwd_ring<true, 8, false, false, false, true, true>);
+            }
+        } else if (two) {
+            if (multi) {
+                launch(k_bwd_ring<true, K, false, false, true, true>);
+                launch(k_bwd_ring<true, K, false, false, false, true>);
+            } else {
+                launch(k_bwd_ring<false, K, false, false, true, true>);
+            }
+        } else if (expect) {
             launch(k_bwd_ring<true, K, false, true>);
         } else if (multi) {
             launch(hdp ? k_bwd_ring<true, K, true> : k_bwd_ring<true, K, false>);
@@ -873,4 +968,5 @@ static void launch_bwd_ring(const DevPlan &P, const int *ids, int n, hipStream_t
             launch(hdp ? k_bwd_ring<false, K, true> : k_bwd_ring<false, K, false>);
         }
     });
+    return SA_OK;
 }

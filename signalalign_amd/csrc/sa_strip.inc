@@ -96,6 +96,34 @@ struct StripIn {
     double e;        // event mean of the lane's cell (0 where the cell has no event: such a cell is a border or outside the band)
     double sa, sb;   // seam record of the diagonal, the same in every lane
 };
+// two-distribution emission (the TWO instances): the noise constants {n, 1 / n, 1.5 log n} of the cell's event, requested with the
+// event (zeros where the cell has no event, like the event itself).  Kept beside the stage: the other instances never name it.
+struct StripTwo {
+    double n, rn, l3;
+};
+__device__ __forceinline__ void strip_request_two(StripTwo &tw, rsrc_t rs_en, unsigned vo) {
+    const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rs_en, vo, 0, 0);
+    const u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(rs_en, vo, 16, 0);
+    tw.n = __hiloint2double((int) a.y, (int) a.x); tw.rn = __hiloint2double((int) a.w, (int) a.z);
+    tw.l3 = __hiloint2double((int) b.y, (int) b.x);
+}
+// the noise term of a cell (two_l2, sa_ring.inc: the same operations in the same order); a lane outside the band adds nothing --
+// its emission is -inf already, and what it read may belong to another read.  One place where the two families do NOT compute the same
+// term: a band cell without an event (row y = 0) reads zeros here (the descriptor's range check: l2 = cn.x) and the padding entry and
+// the NULL position in the ring kernels (l2 = 0).  Both are finite, and every predecessor sum of such a cell is -inf, so the term never
+// reaches a stored value: the byte equality of strip and one-path ring rests on that -- keep it in mind when the border handling changes.
+__device__ __forceinline__ double strip_two_l2(const double4 &cn, const StripTwo &tw, bool act) {
+    double4 n3;
+    n3.x = tw.n; n3.y = tw.rn; n3.z = tw.l3; n3.w = 0.0;
+    const double l2 = two_l2(cn, n3);
+    return act ? l2 : 0.0;
+}
+// the events' half of the noise constants as the region sees it: entry y - 1 of the region, the batch's padding included
+__device__ __forceinline__ rsrc_t strip_rsrc_en(const double *E_all, long long ev_off, long long two_xn_off) {
+    const long long left = (two_xn_off - ev_off) * 32;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double4 *>(reinterpret_cast<const double4 *>(E_all) + ev_off), 0,
+                                             (int) (left < 0x7fffffffll ? (left > 0 ? left : 0) : 0x7fffffffll), 0x00020000);
+}
 // A seam array holds its records' first values, then (half an array further on) their second values: two 8-byte loads the
 // compiler cannot merge into one 16-byte register tuple -- a tuple does not survive the loop's back edge without a copy, and
 // the copy waits for the load.  `so` = byte offset of the record's first value, `half_` = bytes between the two.
@@ -148,7 +176,9 @@ __device__ __forceinline__ void strip_ranges(const int4 *rows4, int da, int db, 
 // HDP: a lane's per-diagonal input is its cell's emission from the region's emission plane (k_emit_hdp_ring, sa_fast.inc: value t
 // of the diagonal at its offset + t, -inf sentinel in entry C - 1) instead of the event mean -- the request then needs the
 // requested diagonal's row record (two diagonals ahead: still inside the 64-entry tile), and no position constants are loaded.
-template <bool HDP>
+// TWO (Gaussian models only): the two-distribution emission -- E_all is then the buffer of noise constants (FastT.two_xn_off); a
+// lane's position constants are loaded once per strip like the Gaussian ones, the event's arrive with the event.
+template <bool HDP, bool TWO = false>
 __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_t *__restrict__ regions, const sa_row_t *__restrict__ rows_all,
                                                                 const int *__restrict__ pk_all, const double4 *__restrict__ xc_all,
                                                                 const double *__restrict__ ev_all, double *__restrict__ F_all,
@@ -188,6 +218,8 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
     const unsigned C8 = (unsigned) C * 8u;
     const unsigned OOB = 0xfffffff0u;
     const rsrc_t rs_E = make_rsrc(HDP ? (const void *) (E_all + R->f_base) : (const void *) ev_all);
+    const rsrc_t rs_en = TWO ? strip_rsrc_en(E_all, R->ev_off, T.two_xn_off) : rs_ev;
+    const rsrc_t rs_xn = TWO ? make_rsrc(reinterpret_cast<const double4 *>(E_all) + T.two_xn_off + R->pid_off) : rs_xc;
     const unsigned sentinel8 = C8 - 8u;
     const unsigned seam_vo = lane == 63 ? 0u : OOB;   // lane 63 publishes
     const unsigned sh = ST.seam_cap * 8u;             // bytes between a record's two values
@@ -227,6 +259,8 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
         const unsigned x8 = (unsigned) x * 8u;
         double4 c = {0.0, 0.0, 0.0, 0.0};
         if (!HDP) c = buf_load_f64x4(rs_xc, (x <= lX ? (unsigned) x : 0u) * 32u);
+        double4 cn = {0.0, 0.0, 0.0, 0.0};
+        if (TWO) cn = buf_load_f64x4(rs_xn, (x <= lX ? (unsigned) x : 0u) * 32u);
         double oY = NEG_INF, sX = NEG_INF, sMe = NEG_INF, sMo = NEG_INF;
         int d = d0;
         int sg_k = 0;   // the first traceback that starts at or above this strip's first diagonal (a scalar search: a dozen segments)
@@ -250,7 +284,8 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
         int si_r = d - d0_r + 1;                     // its record in the seam array being read
         const int n1_r = n_r + 1;
 
-        auto request = [&](StripIn &in, int li_r) {   // li_r: entry of the requested diagonal in the row tile (HDP only)
+        auto request = [&](StripIn &in, StripTwo &tw, int li_r) {   // li_r: entry of the requested diagonal in the row tile (HDP only)
+            if (TWO) strip_request_two(tw, rs_en, (evo_r - x8) * 4u);
             if (HDP) {
                 const int xL_r = __builtin_amdgcn_readlane(tile.w, li_r), w_r = __builtin_amdgcn_readlane(tile.y, li_r);
                 const unsigned fo8_r = (unsigned) __builtin_amdgcn_readlane(tile.z, li_r) * 8u;
@@ -269,7 +304,7 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
         };
         // one diagonal.  `cur` was requested two diagonals earlier and is refilled at the end of the step; sMp holds oM of
         // (x-1, y-1) (written two diagonals ago) and is overwritten with this diagonal's shifted oM.
-        auto half = [&](StripIn &cur, double &sMp) {
+        auto half = [&](StripIn &cur, StripTwo &curn, double &sMp) {
             const int li = d & 31;
             // the previous diagonal's stores, behind that diagonal's request (vmcnt retires in order: sa_fast.inc)
             buf_store_f64(rs_F, pend_vo, pend_so, pend_m);
@@ -287,6 +322,10 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
                 const double pmask = __hiloint2double(act ? 0 : 0x7ff00000, 0);
                 const double a = (cur.e - c.x) * c.y;
                 emit_gauss_q(c, fma(a, a, pmask), lM, lY_);
+            }
+            if (TWO) {
+                const double l2 = strip_two_l2(cn, curn, act);
+                lM += l2; lY_ += l2;
             }
             double m = sMp + lM;
             double xg = act ? sX : NEG_INF;
@@ -329,7 +368,7 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
             pend_m = m; pend_vo = vo; pend_so = fo8;
             pend_a = oM; pend_b = oX; pend_svo = seam_vo; pend_sso += 8u;
             __builtin_amdgcn_sched_barrier(0);
-            request(cur, li + 2);   // the stage is free again: it takes the inputs of the diagonal two steps on
+            request(cur, curn, li + 2);   // the stage is free again: it takes the inputs of the diagonal two steps on
             d++;
         };
         auto next_tile = [&]() {   // d is a multiple of 32
@@ -338,12 +377,13 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) void k_fwd_strip(const sa_region_
             pkn = pk[d + 32 + lane];
         };
         StripIn S0, S1;
-        request(S0, d & 31);
-        request(S1, (d & 31) + 1);
+        StripTwo N0, N1;
+        request(S0, N0, d & 31);
+        request(S1, N1, (d & 31) + 1);
         for (;;) {
             do {
-                half(S0, sMe);
-                half(S1, sMo);
+                half(S0, N0, sMe);
+                half(S1, N1, sMo);
             } while (d <= d_stop && (d & 31) != 0);
             if (d > d_stop) break;
             next_tile();
@@ -374,8 +414,11 @@ struct StripInB {
 //     loaded inside that diagonal's branch: one diagonal in ten);
 //   * candidates arrive strip by strip (high columns first), not in output order: k_finalize tests them against the exact
 //     totals as for every other kernel and k_gather_sorted writes a segment's survivors in (diagonal, column) order (sa_hip.hip).
-template <bool HDP>
-__global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_eu(STRIP_BWD_OCC, STRIP_BWD_OCC))) void k_bwd_strip1(
+// TWO: as in k_fwd_strip.  Its four stages hold twelve doubles more: at four waves per SIMD (128 registers) 43 of them spilled into
+// the loop, so this instance is built for three.
+template <bool HDP, bool TWO = false>
+__global__ __launch_bounds__(64 * STRIP_WAVES)
+__attribute__((amdgpu_waves_per_eu(TWO ? STRIP_BWD_OCC - 1 : STRIP_BWD_OCC, TWO ? STRIP_BWD_OCC - 1 : STRIP_BWD_OCC))) void k_bwd_strip1(
     const sa_region_t *__restrict__ regions, const sa_seg_t *__restrict__ segs, const sa_row_t *__restrict__ rows_all,
     const sa_ck_t *__restrict__ cks, const double4 *__restrict__ xc_all, const double *__restrict__ ev_all, double *__restrict__ F_all,
     double *__restrict__ vbuf, sa_cand_t *__restrict__ cands, int *__restrict__ cand_count, int *__restrict__ overflow,
@@ -415,6 +458,8 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
     const unsigned OOB = 0xfffffff0u;
     const unsigned sentinel8 = C8 - 8u;
     const rsrc_t rs_E = make_rsrc(HDP ? (const void *) (E_all + R->f_base) : (const void *) ev_all);
+    const rsrc_t rs_en = TWO ? strip_rsrc_en(E_all, R->ev_off, T.two_xn_off) : rs_ev;
+    const rsrc_t rs_xn = TWO ? make_rsrc(reinterpret_cast<const double4 *>(E_all) + T.two_xn_off + R->pid_off) : rs_xc;
     const unsigned seam_vo = lane == 0 ? 0u : OOB;
     const unsigned sh = ST.seam_cap * 8u;
     unsigned sw = 0u, sr = ST.seam_cap * 16u;
@@ -456,6 +501,8 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
         const unsigned x8 = (unsigned) x * 8u;
         double4 c = {0.0, 0.0, 0.0, 0.0};
         if (!HDP) c = buf_load_f64x4(rs_xc, (x <= lX ? (unsigned) x : 0u) * 32u);
+        double4 cn = {0.0, 0.0, 0.0, 0.0};
+        if (TWO) cn = buf_load_f64x4(rs_xn, (x <= lX ? (unsigned) x : 0u) * 32u);
         double mY1 = NEG_INF, sX = NEG_INF, sMe = NEG_INF, sMo = NEG_INF;
         int e = e0;
         auto tile_at = [&](int base) -> int4 {
@@ -489,8 +536,9 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
         int si_r = e0_r - e + 1;
         const int n1_r = n_r + 1;
 
-        auto request = [&](StripInB &in, int li) {
+        auto request = [&](StripInB &in, StripTwo &tw, int li) {
             if (!HDP) in.e = buf_load_f64(rs_ev, evo_r - x8, 0);
+            if (TWO) strip_request_two(tw, rs_en, (evo_r - x8) * 4u);
             int si = si_r < 0 ? 0 : si_r;
             si = si > n1_r ? n1_r : si;
             const unsigned so = sr + (unsigned) si * 8u;
@@ -505,7 +553,7 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
             evo_r -= 8u;
             si_r++;
         };
-        auto half = [&](auto head, StripInB &cur, double &sMp) {
+        auto half = [&](auto head, StripInB &cur, StripTwo &curn, double &sMp) {
             const int li = (e & 31) + 32;
             seam_store(rs_seam, pend_svo, pend_sso, sh, pend_a, pend_b);
             const int xL = __builtin_amdgcn_readlane(tile.w, li), w = __builtin_amdgcn_readlane(tile.y, li);
@@ -521,6 +569,10 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
                 const double pmask = __hiloint2double(act ? 0 : 0x7ff00000, 0);
                 const double a = (cur.e - c.x) * c.y;
                 emit_gauss_q(c, fma(a, a, pmask), lM, lY_);
+            }
+            if (TWO) {
+                const double l2 = strip_two_l2(cn, curn, act);
+                lM += l2; lY_ += l2;
             }
             LaP pm, px, py;
             la_prep(pm, sMp + T.t_mm, mY1 + T.t_my);
@@ -586,7 +638,7 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            request(cur, li - 4);
+            request(cur, curn, li - 4);
             e--;
         };
         auto next_tile = [&]() {
@@ -600,28 +652,29 @@ __global__ __launch_bounds__(64 * STRIP_WAVES) __attribute__((amdgpu_waves_per_e
             }
         };
         StripInB S0, S1, S2, S3;
-        request(S0, (e & 31) + 32);
-        request(S1, (e & 31) + 31);
-        request(S2, (e & 31) + 30);
-        request(S3, (e & 31) + 29);
+        StripTwo N0, N1, N2, N3;
+        request(S0, N0, (e & 31) + 32);
+        request(S1, N1, (e & 31) + 31);
+        request(S2, N2, (e & 31) + 30);
+        request(S3, N3, (e & 31) + 29);
         const std::integral_constant<bool, false> BODY;
         const std::integral_constant<bool, true> HEAD;
-        half(HEAD, S0, sMo);
-        half(HEAD, S1, sMe);
-        half(HEAD, S2, sMo);
-        half(HEAD, S3, sMe);
+        half(HEAD, S0, N0, sMo);
+        half(HEAD, S1, N1, sMe);
+        half(HEAD, S2, N2, sMo);
+        half(HEAD, S3, N3, sMe);
         if ((e & 31) == 31) next_tile();
-        half(HEAD, S0, sMo);
-        half(HEAD, S1, sMe);
-        half(HEAD, S2, sMo);
-        half(HEAD, S3, sMe);
+        half(HEAD, S0, N0, sMo);
+        half(HEAD, S1, N1, sMe);
+        half(HEAD, S2, N2, sMo);
+        half(HEAD, S3, N3, sMe);
         while (e > e_stop) {
             if ((e & 31) == 31) next_tile();
             do {
-                half(BODY, S0, sMo);
-                half(BODY, S1, sMe);
-                half(BODY, S2, sMo);
-                half(BODY, S3, sMe);
+                half(BODY, S0, N0, sMo);
+                half(BODY, S1, N1, sMe);
+                half(BODY, S2, N2, sMo);
+                half(BODY, S3, N3, sMe);
             } while (e > e_stop && (e & 31) != 31);
         }
         seam_store(rs_seam, pend_svo, pend_sso, sh, pend_a, pend_b);
@@ -644,14 +697,14 @@ static StripT make_strip_t(const DevPlan &P, long long ev_total, unsigned seam_c
 }
 // one wave per region (forward) / segment (backward), STRIP_WAVES to a workgroup
 static void launch_fwd_strip(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, const StripT &ST) {
-    auto k = P.m.hdp ? k_fwd_strip<true> : k_fwd_strip<false>;
+    auto k = P.m.hdp ? k_fwd_strip<true> : (P.two ? k_fwd_strip<false, true> : k_fwd_strip<false>);
     hipLaunchKernelGGL(k, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.rows, P.pk,
-                       reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, seam, ST, ids, n, P.m.hdp ? (const double *) P.E : nullptr,
+                       reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, seam, ST, ids, n, P.m.hdp ? (const double *) P.E : P.two,
                        P.segs);
 }
 static void launch_bwd_strip(const DevPlan &P, const int *ids, int n, hipStream_t st, char *seam, const StripT &ST) {
-    auto k = P.m.hdp ? k_bwd_strip1<true> : k_bwd_strip1<false>;
+    auto k = P.m.hdp ? k_bwd_strip1<true> : (P.two ? k_bwd_strip1<false, true> : k_bwd_strip1<false>);
     hipLaunchKernelGGL(k, dim3((n + STRIP_WAVES - 1) / STRIP_WAVES), dim3(64 * STRIP_WAVES), 0, st, P.regions, P.segs, P.rows, P.cks,
                        reinterpret_cast<const double4 *>(P.xc), P.ev, P.F, P.vbuf, P.cands, P.cand_count, P.overflow, seam, ST, ids, n,
-                       P.m.hdp ? (const double *) P.E : nullptr);
+                       P.m.hdp ? (const double *) P.E : P.two);
 }

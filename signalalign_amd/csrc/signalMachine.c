@@ -66,7 +66,8 @@ static void usage(void) {
     fprintf(stderr, "--batch <manifest>: align many reads in one process (one GPU batch per strand model)\n");
     fprintf(stderr, "--batch-reads <n>: reads per GPU batch of a manifest (default 2048)\n");
     fprintf(stderr, "--emission <meanOnly|twoDist>: match emission of a Gaussian model (default meanOnly, what the reference's\n"
-                    "                  signalMachine installs; twoDist adds the inverse Gaussian on the event noise; single read only)\n");
+                    "                  signalMachine installs; twoDist adds the inverse Gaussian on the event noise, every read with its own\n"
+                    "                  noise scaling -- with --batch too; Gaussian models, not with -t / -c)\n");
     fprintf(stderr, "--device <n>: GPU to use\n");
     fprintf(stderr, "--mea: also write <posteriors file>.mea, the rows of the full output on the maximum expected accuracy path\n");
     fprintf(stderr, "--site-calls: also write <posteriors file>.calls, per read and ambiguous site the normalised probability of\n"
@@ -93,6 +94,8 @@ typedef struct {
     sa_model_t *model;
     double *table;          /* EMISSION_MATCH_MATRIX as the DP uses it (HDP expected means once they are set)  */
     double *table_orig;     /* as loaded: what the per-read parameter estimation starts from                  */
+    sa_model_t *model_two;  /* --batch --emission twoDist: the same model with the two-distribution emission, the base of
+                             * sa_batch_create_noise_scaled (every read's noise scaling is applied inside the batch) */
     char alphabet[64];
     int n_alpha, k;
 } strand_model_t;
@@ -347,7 +350,10 @@ typedef struct {
     int train_median, train_mod_only;
     sa_kmer_table_t *train_tab[2];
     int two_dist; /* --emission twoDist: the two-distribution emission (not an option of the reference binary: it is what its
-                   * state machine carried when the reference's shipped output files were written); one read per process */
+                   * state machine carried when the reference's shipped output files were written).  A single read is aligned with
+                   * a model of its own (read_t.model); the reads of a manifest share one batch on the strand's model_two and
+                   * hand over their noise scalings (sa_batch_create_noise_scaled) */
+    int batch_mode;
     int64_t out_fmt, constraint_trim;
     int64_t snp_step;       /* --snp-step N: single-nucleotide probabilities, N substituted copies of every read's reference */
     const char *snp_dir;    /* --snp-dir: where <label>.tsv goes */
@@ -369,7 +375,7 @@ typedef struct {
     int forward;
     int64_t *ax[2], *ay[2];
     sa_job_t jobs[2];
-    sa_model_t *model[2]; /* --emission twoDist: the strand models with this read's noise scaling */
+    sa_model_t *model[2]; /* --emission twoDist, single read: the strand models with this read's noise scaling */
     int failed;
     char err[512];
 } read_t;
@@ -508,7 +514,7 @@ static int prepare_read(const run_t *R, read_t *rd, int fatal) {
     /* per-strand: estimate the read's parameters (signalUtils_estimateNanoporeParams), build the job */
     if (estimate_strand(&R->smt, np->template_strand_event_map, np->template_events, np->n_template_events,
                         np->template_read, np->template_read_length, &np->template_params,
-                        R->two_dist ? &rd->model[0] : NULL) != SA_OK) {
+                        R->two_dist && !R->batch_mode ? &rd->model[0] : NULL) != SA_OK) {
         free(gx); free(gy);
         return fail(rd, fatal, "Cannot get scale params with no assignments", NULL);
     }
@@ -527,7 +533,7 @@ static int prepare_read(const run_t *R, read_t *rd, int fatal) {
     if (R->two_d) {
         if (estimate_strand(&R->smc, np->complement_strand_event_map, np->complement_events, np->n_complement_events,
                             np->complement_read, np->complement_read_length, &np->complement_params,
-                            R->two_dist ? &rd->model[1] : NULL) != SA_OK) {
+                            R->two_dist && !R->batch_mode ? &rd->model[1] : NULL) != SA_OK) {
             free(gx); free(gy);
             return fail(rd, fatal, "Cannot get scale params with no assignments", NULL);
         }
@@ -1132,6 +1138,28 @@ static void write_training(run_t *R, const char *t_model, const char *c_model, i
     for (int s = 0; s < 2; s++) { sa_kmer_table_destroy(R->train_tab[s]); R->train_tab[s] = NULL; }
 }
 
+/* One strand's batch of a slice.  jobs[i] belongs to reads[who[i / per_read]] (per_read > 1: --snp-step's substituted copies).
+ * --emission twoDist: a single read brings its own model; the reads of a manifest share the strand's two-distribution model and
+ * each job gets the scale_sd / var_sd its read's parameter estimation left (emissions_signal_scaleNoise, applied inside the batch:
+ * SA_FLAG_TWO_DIST_ALL_KERNELS, whatever kernel family a read's regions take). */
+static int create_strand_batch(sa_batch_t **b, const run_t *R, const strand_model_t *sm, const read_t *reads, const int64_t *who,
+                               int strand, const sa_job_t *jobs, int64_t n_jobs, int64_t per_read, int device, unsigned flags) {
+    if (!R->two_dist) return sa_batch_create(b, sm->model, &R->p, jobs, n_jobs, R->ambig, device, flags);
+    if (!R->batch_mode) return sa_batch_create(b, reads[who[0]].model[strand], &R->p, jobs, n_jobs, R->ambig, device, flags);
+    sa_noise_scale_t *nz = malloc(sizeof(sa_noise_scale_t) * (size_t) (n_jobs > 0 ? n_jobs : 1));
+    if (!nz) return SA_ENOMEM;
+    for (int64_t i = 0; i < n_jobs; i++) {
+        const sa_npread_t *np = reads[who[i / per_read]].np;
+        const sa_strand_params_t *pp = strand == 0 ? &np->template_params : &np->complement_params;
+        nz[i].scale_sd = pp->scale_sd;
+        nz[i].var_sd = pp->var_sd;
+    }
+    const int rc = sa_batch_create_noise_scaled(b, sm->model_two, &R->p, jobs, nz, n_jobs, R->ambig, device,
+                                                flags | SA_FLAG_TWO_DIST_ALL_KERNELS);
+    free(nz);
+    return rc;
+}
+
 static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int batch_mode, int device, int64_t *n_failed_now) {
 #define R (*Rp)
     *n_failed_now = 0;
@@ -1235,11 +1263,10 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
         int rc;
         if (!R.mea) {   /* the batch stays alive for the rendering, which expands its packed records job by job */
             sa_batch_t *b = NULL;
-            rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device,
-                                 vc_flag | p8_want | calls_flag);
+            rc = create_strand_batch(&b, &R, sms[s], reads, who, s, bj, n_ok, 1, device, vc_flag | p8_want | calls_flag);
             p8_used[s] = rc == SA_OK && p8_want != 0;
             if (rc == SA_EUNSUPPORTED && p8_want)
-                rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, vc_flag);
+                rc = create_strand_batch(&b, &R, sms[s], reads, who, s, bj, n_ok, 1, device, vc_flag);
             if (rc == SA_OK) rc = sa_batch_run(b);
             if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
             if (rc == SA_OK && want_train) {
@@ -1265,7 +1292,7 @@ static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int ba
             sa_batch_t *b = NULL;
             mea[s] = calloc((size_t) n_ok, sizeof(sa_mea_pair_t *));
             n_mea[s] = calloc((size_t) n_ok, sizeof(int64_t));
-            rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[s] : sms[s]->model, &R.p, bj, n_ok, R.ambig, device, calls_flag);
+            rc = create_strand_batch(&b, &R, sms[s], reads, who, s, bj, n_ok, 1, device, calls_flag);
             if (rc == SA_OK) rc = sa_batch_run(b);
             if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
             for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) {
@@ -1536,8 +1563,7 @@ static int64_t run_slice_snp(run_t *Rp, read_t *reads, int64_t n_reads, int batc
         if (nj == 0) continue;
         fprintf(stderr, q == 0 ? "signalAlign - starting template alignment\n" : "signalAlign - starting complement alignment\n");
         sa_batch_t *b = NULL;
-        int rc = sa_batch_create(&b, R.two_dist ? reads[who[0]].model[q] : sms[q]->model, &R.p, jobs[q], nj, R.ambig, device,
-                                 SA_FLAG_POSITION_CALLS);
+        int rc = create_strand_batch(&b, &R, sms[q], reads, who, q, jobs[q], nj, N, device, SA_FLAG_POSITION_CALLS);
         if (rc == SA_OK) rc = sa_batch_run(b);
         if (rc == SA_OK) rc = sa_batch_position_calls(b, 0, oc.calls[q], oc.n_calls[q], oc.x_min[q], oc.x_max[q], NULL);
         for (int64_t i = 0; i < nj && rc == SA_OK; i++) rc = sa_batch_all_pairs_summary(b, i, &n_pairs[q][i], &sum_e7[q][i]);
@@ -1741,8 +1767,7 @@ int main(int argc, char **argv) {
     read_t *reads = NULL;
     int64_t n_reads = 0;
     const int batch_mode = manifest != NULL;
-    if (R.two_dist && (batch_mode || R.hdp || R.expect_mode))
-        die("signalMachine: --emission twoDist aligns one read per process with a Gaussian model%s", "");
+    R.batch_mode = batch_mode;
     if (batch_mode) {
         n_reads = load_manifest(manifest, &reads);
         if (n_reads < 0) die("[signalMachine]ERROR: cannot read the batch manifest %s", manifest);
@@ -1770,6 +1795,9 @@ int main(int argc, char **argv) {
             die("[signalMachine] ERROR: need -f <fasta> and -n <sequence name>", NULL);
         }
     }
+    /* (the expectation pass keeps the reference-ordered kernels and the model's own noise; an HDP model has no such emission) */
+    if (R.two_dist && (R.hdp || t_hdp != NULL || c_hdp != NULL || R.expect_mode || t_expect != NULL || c_expect != NULL))
+        die("signalMachine: --emission twoDist aligns reads with a Gaussian model: not with an .nhdp, not with -t / -c%s", "");
 
     if (R.train_assign || R.train_model[0] || R.train_model[1]) {
         if (R.expect_mode || R.mea) die("signalMachine: --train-* needs the alignment mode without --mea%s", "");
@@ -1813,6 +1841,12 @@ int main(int argc, char **argv) {
         die("signalAlign - ERROR: couldn't find model file here: %s", t_model);
     if (R.two_d && load_strand_model(&R.smc, c_model, R.hdp ? c_hdp : NULL) != SA_OK)
         die("signalAlign - ERROR: couldn't find model file here: %s", c_model);
+    for (int s = 0; s < (R.two_d ? 2 : 1) && R.two_dist && batch_mode; s++) {   /* the base of the slices' noise-scaled batches */
+        strand_model_t *sm = s == 0 ? &R.smt : &R.smc;
+        if (sa_model_clone_with_table(&sm->model_two, sm->model, sm->table_orig) != SA_OK ||
+            sa_model_set_emission(sm->model_two, SA_EMISSION_TWO_DIST) != SA_OK)
+            die("signalMachine: --emission twoDist: could not set up the two-distribution model%s", "");
+    }
     if (ambig_model) {
         if (sa_load_ambig(ambig_model, R.ambig) != SA_OK) {
             printf("Couldn't open %s for reading\n", ambig_model);
