@@ -241,7 +241,7 @@ def test_path_legal_transitions_and_substituted_kmers(oracle, golden):
     m = oracle.Model.from_file(os.path.join(golden, "models", "testModelR73_acegot_template.model"))
     A, k = m.n_alpha, m.k
 
-    def legal(a, b):  # the arithmetic the kernels use (sa_hip.hip:legal_step)
+    def legal(a, b):  # the arithmetic the kernels use (sa_generic.inc:legal_step)
         if a is None or b is None:
             return True
         return m.kmer_id(a) % A ** (k - 1) == m.kmer_id(b) // A
