@@ -39,6 +39,14 @@ static void die(const char *fmt, const char *a) { /* st_errAbort: message to std
     exit(1);
 }
 
+/* the one allocator of this file: n elements (a zero count becomes one), zeroed on request; never NULL */
+static void *xalloc(int64_t n, size_t size, int zeroed) {
+    const size_t count = (size_t) (n > 0 ? n : 1);
+    void *p = zeroed ? calloc(count, size) : malloc(count * size);
+    if (!p) die("signalMachine: out of memory%s", "");
+    return p;
+}
+
 static void usage(void) {
     fprintf(stderr, "\n\tsignalMachine - Align ONT ionic current to a reference sequence\n\n");
     fprintf(stderr, "--help: Display this super useful message and exit\n");
@@ -345,6 +353,7 @@ typedef struct {
     const char *agg_path;   /* --site-calls-aggregate: the over-reads table, written at the end of the run */
     /* --train-*: the top-N assignments of the whole run in k-mer tables on the GPU (one per strand), written at the end */
     const char *train_assign, *train_model[2], *train_kmers;
+    int want_train;         /* any of --train-assignments / --train-template-model / --train-complement-model */
     double train_min_prob, train_weight, train_min_sd;
     int64_t train_n;
     int train_median, train_mod_only;
@@ -359,18 +368,26 @@ typedef struct {
     const char *snp_dir;    /* --snp-dir: where <label>.tsv goes */
     const char *fwd_ref, *bwd_ref;
     sa_params_t p;
-    strand_model_t smt, smc;
+    strand_model_t sm[2];   /* [strand]: 0 template, 1 complement (--twoD only) */
     const char *ambig[256];
 } run_t;
 
+static int n_strands(const run_t *R) { return R->two_d ? 2 : 1; }
+static const char *strand_name(int s) { return s == 0 ? "template" : "complement"; }
+
 /* one read: its inputs, the two alignment jobs, where its outputs go */
 typedef struct {
-    char *label, *npread_path, *cigar_path, *post_path, *post_path2, *seq_name, *t_expect, *c_expect;
+    char *label, *npread_path, *cigar_path, *post_path, *post_path2, *seq_name;
+    char *expect[2];      /* [strand]: where -t / -c write the strand's expectations */
     sa_cigar_t *pA;
     sa_npread_t *np;
     char *forward_seq, *backward_seq;
-    const char *template_target, *complement_target;
-    int64_t t_lo, t_hi, c_lo, c_hi, r_shift_t, r_shift_c, n_guide;
+    struct {
+        const char *target;   /* the window the strand is aligned to: forward_seq or backward_seq */
+        int64_t lo, hi;       /* the strand's events inside the guide alignment */
+        int64_t r_shift;      /* reference coordinate shift of the strand's rows */
+    } st[2];
+    int64_t n_guide;
     int64_t win_lo;       /* contig coordinate of forward_seq[0] (backward_seq[i] lies at win_lo + len - 1 - i) */
     int forward;
     int64_t *ax[2], *ay[2];
@@ -379,6 +396,20 @@ typedef struct {
     int failed;
     char err[512];
 } read_t;
+
+/* sa_npread_t names its strands; everything here indexes them */
+static sa_strand_params_t *np_params(sa_npread_t *np, int s) { return s == 0 ? &np->template_params : &np->complement_params; }
+static double *np_events(sa_npread_t *np, int s) { return s == 0 ? np->template_events : np->complement_events; }
+static int64_t np_n_events(const sa_npread_t *np, int s) { return s == 0 ? np->n_template_events : np->n_complement_events; }
+static const char *np_read(const sa_npread_t *np, int s) { return s == 0 ? np->template_read : np->complement_read; }
+static int64_t np_read_length(const sa_npread_t *np, int s) { return s == 0 ? np->template_read_length : np->complement_read_length; }
+static const int64_t *np_strand_map(const sa_npread_t *np, int s) {
+    return s == 0 ? np->template_strand_event_map : np->complement_strand_event_map;
+}
+/* base of the aligned read -> event of the strand: per base of the 2D read with --twoD, of the template read without */
+static const int64_t *np_event_map(const sa_npread_t *np, int s, int two_d) {
+    return s == 0 ? (two_d ? np->template_event_map : np->template_strand_event_map) : np->complement_event_map;
+}
 
 /* single-read mode keeps the reference's abort-with-message behaviour; in batch mode a bad read is reported and skipped */
 static int fail(read_t *rd, int fatal, const char *fmt, const char *a) {
@@ -408,7 +439,6 @@ static int estimate_strand(const strand_model_t *sm, const int64_t *strand_map, 
     return SA_OK;
 }
 
-/* everything of impl/signalMachine.c:main between option parsing and performSignalAlignment, for one read */
 /* SA_CLI_TIMING=1: wall time of the three stages of every slice and the thread-seconds spent inside the host stage, printed
  * at the end of the run (probes/batch_cli_timing.sh; INTEGRATION.md quotes them) */
 static double g_t_prep, g_t_gpu, g_t_render;                 /* wall seconds, summed over slices */
@@ -425,7 +455,40 @@ static void t_add(double *acc, double dt) {
     pthread_mutex_unlock(&g_t_mu);
 }
 
-static int validate_read(const run_t *R, read_t *rd);
+/* plans `per_read` jobs per strand alone on the host (integer geometry only, no GPU); marks the read failed when the planner
+ * rejects one */
+static int validate_read(const run_t *R, read_t *rd, const sa_job_t *const jobs[2], int64_t per_read) {
+    for (int s = 0; s < n_strands(R); s++)
+        for (int64_t i = 0; i < per_read; i++) {
+            int rc = sa_plan_describe(R->sm[s].model, &R->p, &jobs[s][i], R->ambig, 0, NULL, NULL, 0, NULL, 0, NULL, 0);
+            if (rc != SA_OK) return fail(rd, 0, "alignment job rejected: %s", sa_strerror(rc));
+        }
+    return 0;
+}
+
+/* one strand of a read: estimate the read's parameters (signalUtils_estimateNanoporeParams), build the job from the guide
+ * alignment's anchors */
+static int build_strand_job(const run_t *R, read_t *rd, int s, const int64_t *gx, const int64_t *gy) {
+    sa_npread_t *np = rd->np;
+    sa_strand_params_t *pp = np_params(np, s);
+    if (estimate_strand(&R->sm[s], np_strand_map(np, s), np_events(np, s), np_n_events(np, s), np_read(np, s), np_read_length(np, s), pp,
+                        R->two_dist && !R->batch_mode ? &rd->model[s] : NULL) != SA_OK)
+        return -1;
+    sa_job_t *job = &rd->jobs[s];
+    rd->ax[s] = xalloc(rd->n_guide + 1, sizeof(int64_t), 0);
+    rd->ay[s] = xalloc(rd->n_guide + 1, sizeof(int64_t), 0);
+    job->n_anchors = sa_remap_anchors(gx, gy, rd->n_guide, np_event_map(np, s, R->two_d), rd->pA->start2, rd->ax[s], rd->ay[s]);
+    job->anchor_x = rd->ax[s]; job->anchor_y = rd->ay[s];
+    job->ref = rd->st[s].target;
+    job->ref_len = (int64_t) strlen(rd->st[s].target);
+    job->events = np_events(np, s) + 4 * rd->st[s].lo;
+    job->event_stride = 4;
+    job->n_events = rd->st[s].hi - rd->st[s].lo;
+    job->scale = pp->scale; job->shift = pp->shift; job->var = pp->var;
+    return 0;
+}
+
+/* everything of impl/signalMachine.c:main between option parsing and performSignalAlignment, for one read */
 static int prepare_read(const run_t *R, read_t *rd, int fatal) {
     const double tp0 = now_s();
     if (rd->cigar_path == NULL) return fail(rd, fatal, "[signalMachine]ERROR: Need to provide input guide alignments, exiting", NULL);
@@ -489,16 +552,17 @@ static int prepare_read(const run_t *R, read_t *rd, int fatal) {
         pA->strand1 = !pA->strand1;
         strand1 = pA->strand1;
     }
-    rd->template_target = strand1 ? rd->forward_seq : rd->backward_seq;
-    rd->complement_target = strand1 ? rd->backward_seq : rd->forward_seq;
+    rd->st[0].target = strand1 ? rd->forward_seq : rd->backward_seq;
+    rd->st[1].target = strand1 ? rd->backward_seq : rd->forward_seq;
 
     /* event slices and coordinate shifts (impl/signalMachine.c:726-750) */
-    const int64_t *t_map = R->two_d ? np->template_event_map : np->template_strand_event_map;
-    rd->t_lo = t_map[pA->start2];
-    rd->t_hi = t_map[pA->end2 - 1];
-    if (R->two_d) { rd->c_lo = np->complement_event_map[pA->start2]; rd->c_hi = np->complement_event_map[pA->end2 - 1]; }
-    rd->r_shift_t = pA->start1;
-    rd->r_shift_c = R->two_d ? pA->end1 : 0;
+    for (int s = 0; s < n_strands(R); s++) {
+        const int64_t *map = np_event_map(np, s, R->two_d);
+        rd->st[s].lo = map[pA->start2];
+        rd->st[s].hi = map[pA->end2 - 1];
+    }
+    rd->st[0].r_shift = pA->start1;
+    rd->st[1].r_shift = R->two_d ? pA->end1 : 0;
     rd->forward = pA->strand1;
 
     const double tp2 = now_s();
@@ -506,77 +570,27 @@ static int prepare_read(const run_t *R, read_t *rd, int fatal) {
     /* anchors from the guide alignment (pA is rebased inside, impl/signalMachineUtils.c:142-164) */
     int64_t cap = 0;
     for (int64_t i = 0; i < pA->n_ops; i++) cap += pA->op_len[i];
-    int64_t *gx = malloc(sizeof(int64_t) * (size_t) (cap + 1)), *gy = malloc(sizeof(int64_t) * (size_t) (cap + 1));
+    int64_t *gx = xalloc(cap + 1, sizeof(int64_t), 0), *gy = xalloc(cap + 1, sizeof(int64_t), 0);
     rd->n_guide = sa_guide_to_anchors(pA->start1, pA->end1, pA->strand1, pA->start2, pA->op_type, pA->op_len, pA->n_ops,
                                       R->constraint_trim, gx, gy, cap + 1);
-    if (rd->n_guide < 0) { free(gx); free(gy); return fail(rd, fatal, "signalMachine: could not convert the guide alignment", NULL); }
-
-    /* per-strand: estimate the read's parameters (signalUtils_estimateNanoporeParams), build the job */
-    if (estimate_strand(&R->smt, np->template_strand_event_map, np->template_events, np->n_template_events,
-                        np->template_read, np->template_read_length, &np->template_params,
-                        R->two_dist && !R->batch_mode ? &rd->model[0] : NULL) != SA_OK) {
-        free(gx); free(gy);
-        return fail(rd, fatal, "Cannot get scale params with no assignments", NULL);
-    }
+    int built = rd->n_guide < 0 ? -1 : 0;
     memset(rd->jobs, 0, sizeof(rd->jobs));
-    rd->ax[0] = malloc(sizeof(int64_t) * (size_t) (rd->n_guide + 1));
-    rd->ay[0] = malloc(sizeof(int64_t) * (size_t) (rd->n_guide + 1));
-    int64_t na0 = sa_remap_anchors(gx, gy, rd->n_guide, t_map, pA->start2, rd->ax[0], rd->ay[0]);
-    rd->jobs[0].ref = rd->template_target;
-    rd->jobs[0].ref_len = (int64_t) strlen(rd->template_target);
-    rd->jobs[0].events = np->template_events + 4 * rd->t_lo;
-    rd->jobs[0].event_stride = 4;
-    rd->jobs[0].n_events = rd->t_hi - rd->t_lo;
-    rd->jobs[0].anchor_x = rd->ax[0]; rd->jobs[0].anchor_y = rd->ay[0]; rd->jobs[0].n_anchors = na0;
-    rd->jobs[0].scale = np->template_params.scale; rd->jobs[0].shift = np->template_params.shift;
-    rd->jobs[0].var = np->template_params.var;
-    if (R->two_d) {
-        if (estimate_strand(&R->smc, np->complement_strand_event_map, np->complement_events, np->n_complement_events,
-                            np->complement_read, np->complement_read_length, &np->complement_params,
-                            R->two_dist && !R->batch_mode ? &rd->model[1] : NULL) != SA_OK) {
-            free(gx); free(gy);
-            return fail(rd, fatal, "Cannot get scale params with no assignments", NULL);
-        }
-        rd->ax[1] = malloc(sizeof(int64_t) * (size_t) (rd->n_guide + 1));
-        rd->ay[1] = malloc(sizeof(int64_t) * (size_t) (rd->n_guide + 1));
-        int64_t na1 = sa_remap_anchors(gx, gy, rd->n_guide, np->complement_event_map, pA->start2, rd->ax[1], rd->ay[1]);
-        rd->jobs[1].ref = rd->complement_target;
-        rd->jobs[1].ref_len = (int64_t) strlen(rd->complement_target);
-        rd->jobs[1].events = np->complement_events + 4 * rd->c_lo;
-        rd->jobs[1].event_stride = 4;
-        rd->jobs[1].n_events = rd->c_hi - rd->c_lo;
-        rd->jobs[1].anchor_x = rd->ax[1]; rd->jobs[1].anchor_y = rd->ay[1]; rd->jobs[1].n_anchors = na1;
-        rd->jobs[1].scale = np->complement_params.scale; rd->jobs[1].shift = np->complement_params.shift;
-        rd->jobs[1].var = np->complement_params.var;
-    }
+    for (int s = 0; s < n_strands(R) && built == 0; s++) built = build_strand_job(R, rd, s, gx, gy);
     free(gx);
     free(gy);
+    if (rd->n_guide < 0) return fail(rd, fatal, "signalMachine: could not convert the guide alignment", NULL);
+    if (built != 0) return fail(rd, fatal, "Cannot get scale params with no assignments", NULL);
     t_add(&g_ts_estimate, now_s() - tp2);
     /* batch mode: the reads of a slice share one GPU batch, and the planner rejects a whole batch for one bad job (a
      * reference window with a letter outside the alphabet, anchors that give an invalid diagonal).  The reference runs one
      * process per read, so only that read may fail.  Alignment runs find the offender when -- and only when -- a batch is
-     * turned down (validate_reads below); the expectation routine writes files strand by strand and cannot be re-run, so
-     * its jobs are planned alone on the host here (integer geometry only, no GPU). */
-    if (!fatal && R->expect_mode) return validate_read(R, rd);
-    return 0;
-}
-
-/* plans every job of the read alone on the host; marks the read failed when the planner rejects one */
-static int validate_read(const run_t *R, read_t *rd) {
-    for (int s = 0; s < (R->two_d ? 2 : 1); s++) {
-        int rc = sa_plan_describe(s == 0 ? R->smt.model : R->smc.model, &R->p, &rd->jobs[s], R->ambig, 0, NULL, NULL, 0, NULL, 0,
-                                  NULL, 0);
-        if (rc != SA_OK) return fail(rd, 0, "alignment job rejected: %s", sa_strerror(rc));
+     * turned down (drop_refused_reads below); the expectation routine writes files strand by strand and cannot be re-run, so
+     * its jobs are planned alone on the host here. */
+    if (!fatal && R->expect_mode) {
+        const sa_job_t *const own[2] = {&rd->jobs[0], &rd->jobs[1]};
+        return validate_read(R, rd, own, 1);
     }
     return 0;
-}
-
-typedef struct { const run_t *R; read_t *reads; const int64_t *who; } validate_ctx_t;
-static void validate_one(int64_t j, void *ctx) {
-    validate_ctx_t *v = ctx;
-    read_t *rd = &v->reads[v->who[j]];
-    if (validate_read(v->R, rd) != 0)
-        fprintf(stderr, "[signalMachine] ERROR: read %s skipped: %s\n", rd->label, rd->err);
 }
 
 static void set_hdp_expected(strand_model_t *sm) { /* stateMachine3_setModelToHdpExpectedValues, once per run */
@@ -622,8 +636,8 @@ static int64_t load_manifest(const char *path, read_t **out) {
         rd->post_path = dup_field(f[3]);
         rd->post_path2 = dup_field(f[4]);
         rd->seq_name = dup_field(f[5]);
-        rd->t_expect = dup_field(f[6]);
-        rd->c_expect = dup_field(f[7]);
+        rd->expect[0] = dup_field(f[6]);
+        rd->expect[1] = dup_field(f[7]);
     }
     free(line);
     fclose(fh);
@@ -683,36 +697,140 @@ static void parallel_for(int64_t n, void (*fn)(int64_t, void *), void *ctx) {
         if (started[k]) pthread_join(th[k], NULL);
 }
 
+/* One slice of the run's reads: host side of every read, one GPU batch per strand model, outputs.  (The whole manifest used to
+ * be one batch: fine for thousands of reads, not for a flow cell.) */
 typedef struct {
-    const run_t *R;
+    run_t *R;
     read_t *reads;
-    int fatal;
-} prep_ctx_t;
+    int64_t n_reads;
+    int device;
+    int64_t *who, n_ok;   /* the reads that are still in: reads[who[0 .. n_ok)] */
+    int validated;        /* the reads' jobs have been planned one by one (drop_refused_reads) */
+} slice_t;
 
 static void prep_one(int64_t i, void *ctx) {
-    prep_ctx_t *c = ctx;
-    if (prepare_read(c->R, &c->reads[i], c->fatal) != 0)
-        fprintf(stderr, "[signalMachine] ERROR: read %s skipped: %s\n", c->reads[i].label, c->reads[i].err);
+    const slice_t *sl = ctx;
+    read_t *rd = &sl->reads[i];
+    if (prepare_read(sl->R, rd, !sl->R->batch_mode) != 0)
+        fprintf(stderr, "[signalMachine] ERROR: read %s skipped: %s\n", rd->label, rd->err);
 }
 
+/* host side of every read of a slice (files, parameter estimation, anchors): all host threads */
+static void *slice_prepare(void *arg) {
+    slice_t *sl = arg;
+    const double ts0 = now_s();
+    parallel_for(sl->n_reads, prep_one, sl);
+    t_add(&g_t_prep, now_s() - ts0);
+    return NULL;
+}
+
+/* what a read holds once its outputs are written */
+static void release_read(read_t *rd) {
+    if (rd->pA) sa_cigar_free(rd->pA);
+    if (rd->np) sa_npread_free(rd->np);
+    free(rd->forward_seq); free(rd->backward_seq);
+    for (int s = 0; s < 2; s++) { free(rd->ax[s]); free(rd->ay[s]); rd->ax[s] = rd->ay[s] = NULL; }
+    for (int s = 0; s < 2; s++) { if (rd->model[s]) sa_model_destroy(rd->model[s]); rd->model[s] = NULL; }
+    rd->pA = NULL; rd->np = NULL; rd->forward_seq = rd->backward_seq = NULL;
+}
+
+/* the GPU stage of a slice starts here: who[0 .. n_ok) are the reads whose host side went through */
+static void slice_open(slice_t *sl, run_t *R, read_t *reads, int64_t n_reads, int device) {
+    memset(sl, 0, sizeof(*sl));
+    sl->R = R; sl->reads = reads; sl->n_reads = n_reads; sl->device = device;
+    sl->validated = !R->batch_mode;   /* a single-read run has nobody to isolate a bad job from */
+    sl->who = xalloc(n_reads, sizeof(int64_t), 0);
+    for (int64_t i = 0; i < n_reads; i++)
+        if (!reads[i].failed) sl->who[sl->n_ok++] = i;
+}
+
+/* ... and ends here: the reads' memory goes back; returns the number of the slice's reads that failed */
+static int64_t slice_close(slice_t *sl) {
+    int64_t n_failed = 0;
+    for (int64_t i = 0; i < sl->n_reads; i++) n_failed += sl->reads[i].failed ? 1 : 0;
+    for (int64_t i = 0; i < sl->n_reads; i++) release_read(&sl->reads[i]);
+    free(sl->who);
+    return n_failed;
+}
+
+/* the summary line on stdout (n == NULL: none, the expectations mode) and the SUCCESS line on stderr of one alignment of a read */
+static void report_read(const run_t *R, const read_t *rd, const int64_t *n, const double *score) {
+    if (n) {
+        fprintf(stdout, "%s %" PRId64 "\t%" PRId64 "(%f)\t", rd->label, rd->n_guide, n[0], score[0]);
+        if (R->two_d) fprintf(stdout, "%" PRId64 "(%f)\n", n[1], score[1]);
+        else fprintf(stdout, "\n");
+    }
+    fprintf(stderr, "signalAlign - SUCCESS: finished alignment of query %s, exiting\n", rd->label);
+}
+
+/* The planner turned a strand's batch down with `rc` (a letter outside the alphabet, anchors that give no band, a cell of more
+ * paths or a matrix larger than the result records can name -- SA_EUNSUPPORTED --, ...): find the reads whose jobs it rejects
+ * (each planned alone on the host, all host threads) and let them fail alone, as the reference's one-process-per-read runs
+ * would.  jobs[strand] holds per_read jobs for every read of who (NULL: the reads' own jobs).  Once per slice, never for a
+ * single read, nor when the device or its memory is what is missing.  Returns 1 when reads were dropped: who and n_ok are closed
+ * up (kept_from[k], if asked for, is the place the read now at k had before) and the caller starts both strands over; on 0 the
+ * caller ends the run when rc is an error, for no read is to blame. */
+typedef struct { const slice_t *sl; sa_job_t *const *jobs; int64_t per_read; } validate_ctx_t;
+static void validate_one(int64_t j, void *ctx) {
+    validate_ctx_t *v = ctx;
+    read_t *rd = &v->sl->reads[v->sl->who[j]];
+    const sa_job_t *jobs[2];
+    for (int s = 0; s < 2; s++) jobs[s] = !v->jobs ? &rd->jobs[s] : v->jobs[s] ? v->jobs[s] + j * v->per_read : NULL;
+    if (validate_read(v->sl->R, rd, jobs, v->per_read) != 0)
+        fprintf(stderr, "[signalMachine] ERROR: read %s skipped: %s\n", rd->label, rd->err);
+}
+static int drop_refused_reads(slice_t *sl, int rc, sa_job_t *const *jobs, int64_t per_read, int64_t *kept_from) {
+    if (sl->validated || rc == SA_OK || rc == SA_ENODEVICE || rc == SA_ENOMEM) return 0;
+    sl->validated = 1;
+    validate_ctx_t vc = {sl, jobs, per_read};
+    parallel_for(sl->n_ok, validate_one, &vc);
+    int64_t k = 0;
+    for (int64_t j = 0; j < sl->n_ok; j++)
+        if (!sl->reads[sl->who[j]].failed) {
+            if (kept_from) kept_from[k] = j;
+            sl->who[k++] = sl->who[j];
+        }
+    const int dropped = k < sl->n_ok;
+    sl->n_ok = k;
+    return dropped;
+}
+
+/* What one strand's batch of a slice leaves for the rendering, [job] each.  Without --mea the batch stays alive and pairs[job]
+ * is NULL: a job's rows are expanded from the batch's packed records by the thread that renders the job. */
 typedef struct {
-    const run_t *R;
-    read_t *reads;
-    const int64_t *who;
-    sa_pair_t ***pairs;   /* [strand][job] */
-    int64_t **n_pairs;
-    double (*score)[2];
-    sa_mea_pair_t ***mea; /* [strand][job], --mea only */
-    int64_t **n_mea;
-    sa_batch_t *const *batch;   /* [strand]: the batch is still alive and pairs[strand][job] is NULL -- a job's rows are expanded
-                                 * from the batch's packed records (sa_batch_pairs16) by the thread that renders the job */
-    int64_t *const *all_n;      /* [strand][job], -s 1 only (SA_FLAG_VC_ROWS): number and prob_e7 sum of ALL pairs of the job -- the */
-    int64_t *const *all_sum;    /* rows the variant-caller output does not print were dropped on the device                        */
-    const int *p8;              /* [strand]: the batch holds 8-byte records (SA_FLAG_PAIRS8): path 0, the reference's k-mer at x          */
-    sa_site_call_t ***calls;    /* [strand][job], --site-calls / --site-calls-aggregate only */
-    int64_t **n_calls;
-    unsigned char *tmpl_amb;    /* [job], the same with --twoD: the template strand has a row on an ambiguous k-mer (order_calls) */
-} out_job_t;
+    sa_pair_t **pairs;
+    int64_t *n_pairs;
+    sa_mea_pair_t **mea;        /* --mea only */
+    int64_t *n_mea;
+    sa_batch_t *batch;
+    int64_t *all_n, *all_sum;   /* -s 1 only (SA_FLAG_VC_ROWS): number and prob_e7 sum of ALL pairs of the job -- the rows the
+                                 * variant-caller output does not print were dropped on the device */
+    int p8;                     /* the batch holds 8-byte records (SA_FLAG_PAIRS8): path 0, the reference's k-mer at x */
+    sa_site_call_t **calls;     /* --site-calls / --site-calls-aggregate only */
+    int64_t *n_calls;
+} strand_result_t;
+
+/* a result of n_jobs jobs, filled as far as its batch got */
+static void strand_result_free(strand_result_t *sr, int64_t n_jobs) {
+    sa_batch_destroy(sr->batch);
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (sr->pairs) sa_free(sr->pairs[j]);
+        if (sr->mea) sa_free(sr->mea[j]);
+        if (sr->calls) sa_free(sr->calls[j]);
+    }
+    free(sr->pairs); free(sr->n_pairs); free(sr->mea); free(sr->n_mea); free(sr->all_n); free(sr->all_sum);
+    free(sr->calls); free(sr->n_calls);
+    memset(sr, 0, sizeof(*sr));
+}
+
+/* an alignment slice between its GPU stage and its rendering */
+typedef struct {
+    slice_t sl;
+    sa_job_t *bj;              /* [job]: the jobs of the strand whose batch is being made */
+    strand_result_t sr[2];
+    double (*score)[2];        /* [job][strand] */
+    unsigned char *tmpl_amb;   /* [job], --twoD with site calls: the template strand has a row on an ambiguous k-mer (order_calls) */
+} align_slice_t;
 
 /* kmer_id of the k letters at s (sorted alphabet, first letter most significant), -1 for a letter outside it */
 static int32_t kmer_id_of(const strand_model_t *sm, const char *s) {
@@ -742,7 +860,7 @@ static void write_mea(const char *post_path, const out_ctx_t *o, const sa_mea_pa
         if (p->y > y_max || x_of[p->y] != p->x) continue;
         if (best[p->y] < 0 || p->prob_e7 < o->pairs[best[p->y]].prob_e7) best[p->y] = i;
     }
-    sa_pair_t *rows = malloc(sizeof(sa_pair_t) * (size_t) (n_path > 0 ? n_path : 1));
+    sa_pair_t *rows = xalloc(n_path, sizeof(sa_pair_t), 0);
     int64_t n = 0;
     for (int64_t i = 0; i < o->n_pairs; i++) {   /* output order of the posteriors file */
         const sa_pair_t *p = &o->pairs[i];
@@ -787,9 +905,8 @@ static int cmp_call_pos(const void *a, const void *b) {
 static call_pos_t *order_calls(const read_t *rd, int s, int tmpl_amb, const sa_site_call_t *calls, int64_t n, int k, char *mapped) {
     const int idx = (s == 1 && tmpl_amb) ? 1 : 0;
     *mapped = (idx == 0) == (rd->forward != 0) ? '+' : '-';
-    const char *target = s == 0 ? rd->template_target : rd->complement_target;
-    const int64_t ref_len = (int64_t) strlen(target), ref_len_kmers = ref_len - k, off = s == 0 ? rd->r_shift_t : rd->r_shift_c;
-    call_pos_t *v = malloc(sizeof(call_pos_t) * (size_t) (n > 0 ? n : 1));
+    const int64_t ref_len = (int64_t) strlen(rd->st[s].target), ref_len_kmers = ref_len - k, off = rd->st[s].r_shift;
+    call_pos_t *v = xalloc(n, sizeof(call_pos_t), 0);
     for (int64_t i = 0; i < n; i++) {
         v[i].pos = adjust_ref(calls[i].x, off, ref_len_kmers, ref_len, s == 0, rd->forward);
         v[i].i = i;
@@ -910,7 +1027,7 @@ static int cmp_agg(const void *a, const void *b) {
  * union of the letters; a letter a site does not have counts 0. */
 static void write_aggregate(const char *path) {
     int have[256] = {0};
-    agg_entry_t **rows = malloc(sizeof(agg_entry_t *) * (g_agg.n ? g_agg.n : 1));
+    agg_entry_t **rows = xalloc((int64_t) g_agg.n, sizeof(agg_entry_t *), 0);
     size_t n = 0;
     for (size_t i = 0; i < g_agg.cap; i++)
         if (g_agg.tab[i].used) {
@@ -949,96 +1066,93 @@ static void write_aggregate(const char *path) {
     free(rows);
 }
 
+static out_ctx_t out_ctx_for(const run_t *R, const read_t *rd, int s, const sa_pair_t *pairs, int64_t n_pairs, double score) {
+    out_ctx_t o;
+    o.label = rd->label; o.contig = rd->pA->contig1; o.sm = &R->sm[s]; o.npp = *np_params(rd->np, s);
+    o.events = np_events(rd->np, s); o.target = rd->st[s].target; o.forward = rd->forward; o.is_template = s == 0;
+    o.rna = R->rna; o.event_offset = rd->st[s].lo; o.ref_offset = rd->st[s].r_shift; o.pairs = pairs;
+    o.n_pairs = n_pairs; o.score = score;
+    return o;
+}
+
+/* The rows of job j, expanded from the packed records the strand's batch holds in page-locked memory.  This runs job by job on
+ * the rendering threads: the GPU stage does not expand every job's pairs into freshly allocated sa_pair_t arrays on the main
+ * thread (523 MB per slice of 2048 long reads).  NULL, and the read marked failed, when the records cannot be had.
+ * 8-byte records (-s 0 / 2 on reads without ambiguity letters -- half the bytes over PCIe where the pairs outweigh the kernels,
+ * e.g. --sm3Hdp -D 0.01) hold x, y and the probability; the pair's k-mer is the reference's at x, its path 0. */
+static sa_pair_t *expand_job_pairs(const run_t *R, read_t *rd, int s, const strand_result_t *sr, int64_t j) {
+    const sa_pair8_t *pk8 = NULL;
+    const sa_pair16_t *pk16 = NULL;
+    int64_t n = 0;
+    const int rc = sr->p8 ? sa_batch_pairs8(sr->batch, j, &pk8, &n) : sa_batch_pairs16(sr->batch, j, &pk16, &n);
+    if (rc != SA_OK || n != sr->n_pairs[j]) {
+        fprintf(stderr, "[signalMachine] ERROR: read %s: results of the batch are not readable\n", rd->label);
+        rd->failed = 1;
+        return NULL;
+    }
+    sa_pair_t *rows = xalloc(n, sizeof(sa_pair_t), 0);
+    if (!sr->p8) {
+        for (int64_t i = 0; i < n; i++) rows[i] = sa_pair16_unpack(pk16[i]);
+        return rows;
+    }
+    int bad_kmer = 0;
+    for (int64_t i = 0; i < n; i++) {
+        sa_pair_t *q = &rows[i];
+        sa_pair8_unpack(pk8[i], &q->prob_e7, &q->x, &q->y);
+        q->path = 0;
+        q->kmer_id = kmer_id_of(&R->sm[s], rd->st[s].target + q->x);
+        bad_kmer |= q->kmer_id < 0;
+    }
+    if (bad_kmer) {   /* (cannot happen: the planner refuses a reference with a letter outside the model's alphabet) */
+        fprintf(stderr, "[signalMachine] ERROR: read %s: a pair names a k-mer outside the model's alphabet\n", rd->label);
+        rd->failed = 1;
+        free(rows);
+        return NULL;
+    }
+    return rows;
+}
+
 static void output_one(int64_t j, void *ctx) {
-    out_job_t *c = ctx;
-    const run_t *R = c->R;
-    read_t *rd = &c->reads[c->who[j]];
-    const int n_strands = R->two_d ? 2 : 1;
+    align_slice_t *c = ctx;
+    const run_t *R = c->sl.R;
+    read_t *rd = &c->sl.reads[c->sl.who[j]];
     if (R->out_fmt == 3 && rd->post_path2 == NULL) {
         fprintf(stderr, "[signalMachine] ERROR: read %s: 'both' output format needs a second output file\n", rd->label);
         rd->failed = 1;
         return;
     }
-    /* The rows are expanded here, job by job on the rendering threads, from the packed records the batch holds in page-locked
-     * memory: the GPU stage does not expand every job's pairs into freshly allocated sa_pair_t arrays on the main thread (523 MB
-     * per slice of 2048 long reads). */
     sa_pair_t *mine[2] = {NULL, NULL};
     const sa_pair_t *pp[2] = {NULL, NULL};
-    for (int s = 0; s < n_strands; s++) {
-        pp[s] = c->pairs[s][j];
-        if (pp[s] == NULL && c->batch && c->batch[s] && c->p8 && c->p8[s]) {
-            /* 8-byte records (round 6: -s 0 / 2 on reads without ambiguity letters -- half the bytes over PCIe where the pairs outweigh
-             * the kernels, e.g. --sm3Hdp -D 0.01): x, y, probability; the pair's k-mer is the reference's at x, its path 0 */
-            const sa_pair8_t *pk8 = NULL;
-            int64_t n = 0;
-            const strand_model_t *sm = s == 0 ? &R->smt : &R->smc;
-            const char *target = s == 0 ? rd->template_target : rd->complement_target;
-            if (sa_batch_pairs8(c->batch[s], j, &pk8, &n) != SA_OK || n != c->n_pairs[s][j]) {
-                fprintf(stderr, "[signalMachine] ERROR: read %s: results of the batch are not readable\n", rd->label);
-                rd->failed = 1;
-                free(mine[0]);
-                return;
-            }
-            mine[s] = malloc(sizeof(sa_pair_t) * (size_t) (n > 0 ? n : 1));
-            int bad_kmer = 0;
-            for (int64_t i = 0; i < n; i++) {
-                sa_pair_t *q = &mine[s][i];
-                sa_pair8_unpack(pk8[i], &q->prob_e7, &q->x, &q->y);
-                q->path = 0;
-                q->kmer_id = kmer_id_of(sm, target + q->x);
-                bad_kmer |= q->kmer_id < 0;
-            }
-            if (bad_kmer) {   /* (cannot happen: the planner refuses a reference with a letter outside the model's alphabet) */
-                fprintf(stderr, "[signalMachine] ERROR: read %s: a pair names a k-mer outside the model's alphabet\n", rd->label);
-                rd->failed = 1;
-                free(mine[0]); free(mine[1]);
-                return;
-            }
-            pp[s] = mine[s];
-        } else if (pp[s] == NULL && c->batch && c->batch[s]) {
-            const sa_pair16_t *pk = NULL;
-            int64_t n = 0;
-            if (sa_batch_pairs16(c->batch[s], j, &pk, &n) != SA_OK || n != c->n_pairs[s][j]) {
-                fprintf(stderr, "[signalMachine] ERROR: read %s: results of the batch are not readable\n", rd->label);
-                rd->failed = 1;
-                free(mine[0]);
-                return;
-            }
-            mine[s] = malloc(sizeof(sa_pair_t) * (size_t) (n > 0 ? n : 1));
-            for (int64_t i = 0; i < n; i++) mine[s][i] = sa_pair16_unpack(pk[i]);
-            pp[s] = mine[s];
+    for (int s = 0; s < n_strands(R); s++) {
+        const strand_result_t *sr = &c->sr[s];
+        pp[s] = sr->pairs[j];
+        if (pp[s] != NULL || sr->batch == NULL) continue;
+        pp[s] = mine[s] = expand_job_pairs(R, rd, s, sr, j);
+        if (mine[s] == NULL) {
+            free(mine[0]);
+            return;
         }
     }
-    for (int s = 0; s < n_strands; s++) {
+    for (int s = 0; s < n_strands(R); s++) {
+        const strand_result_t *sr = &c->sr[s];
         double tot = 0.0;
-        int64_t n_all = c->n_pairs[s][j];
-        if (c->all_n && c->all_n[s]) {   /* (prob_e7 sums are integers below 2^53: the same double as the loop below gives) */
-            n_all = c->all_n[s][j];
-            tot = (double) c->all_sum[s][j];
+        int64_t n_all = sr->n_pairs[j];
+        if (sr->all_n) {   /* (prob_e7 sums are integers below 2^53: the same double as the loop below gives) */
+            n_all = sr->all_n[j];
+            tot = (double) sr->all_sum[j];
         } else {
-            for (int64_t i = 0; i < c->n_pairs[s][j]; i++) tot += (double) pp[s][i].prob_e7;
+            for (int64_t i = 0; i < sr->n_pairs[j]; i++) tot += (double) pp[s][i].prob_e7;
         }
         c->score[j][s] = 100.0 * tot / ((double) n_all * PROB_1); /* scoreByPosteriorProbabilityIgnoringGaps :407-412 */
     }
-    const int tmpl_amb = c->tmpl_amb && has_ambiguous_rows(R->ambig, rd->template_target, R->smt.k, pp[0], c->n_pairs[0][j]);
+    const int tmpl_amb = c->tmpl_amb && has_ambiguous_rows(R->ambig, rd->st[0].target, R->sm[0].k, pp[0], c->sr[0].n_pairs[j]);
     if (c->tmpl_amb) c->tmpl_amb[j] = (unsigned char) tmpl_amb;
-    if (rd->post_path != NULL) {
-        out_ctx_t o;
-        o.label = rd->label; o.contig = rd->pA->contig1; o.sm = &R->smt; o.npp = rd->np->template_params;
-        o.events = rd->np->template_events; o.target = rd->template_target; o.forward = rd->forward; o.is_template = 1;
-        o.rna = R->rna; o.event_offset = rd->t_lo; o.ref_offset = rd->r_shift_t; o.pairs = pp[0];
-        o.n_pairs = c->n_pairs[0][j]; o.score = c->score[j][0];
+    for (int s = 0; s < n_strands(R) && rd->post_path != NULL; s++) {
+        const strand_result_t *sr = &c->sr[s];
+        const out_ctx_t o = out_ctx_for(R, rd, s, pp[s], sr->n_pairs[j], c->score[j][s]);
         output_alignment(R->out_fmt, rd->post_path, rd->post_path2, &o);
-        if (R->mea) write_mea(rd->post_path, &o, c->mea[0][j], c->n_mea[0][j]);
-        if (R->site_calls) write_calls(rd->post_path, rd, 0, tmpl_amb, c->calls[0][j], c->n_calls[0][j], R->smt.k);
-        if (R->two_d) {
-            o.sm = &R->smc; o.npp = rd->np->complement_params; o.events = rd->np->complement_events;
-            o.target = rd->complement_target; o.is_template = 0; o.event_offset = rd->c_lo; o.ref_offset = rd->r_shift_c;
-            o.pairs = pp[1]; o.n_pairs = c->n_pairs[1][j]; o.score = c->score[j][1];
-            output_alignment(R->out_fmt, rd->post_path, rd->post_path2, &o);
-            if (R->mea) write_mea(rd->post_path, &o, c->mea[1][j], c->n_mea[1][j]);
-            if (R->site_calls) write_calls(rd->post_path, rd, 1, tmpl_amb, c->calls[1][j], c->n_calls[1][j], R->smc.k);
-        }
+        if (R->mea) write_mea(rd->post_path, &o, sr->mea[j], sr->n_mea[j]);
+        if (R->site_calls) write_calls(rd->post_path, rd, s, tmpl_amb, sr->calls[j], sr->n_calls[j], R->sm[s].k);
     }
     free(mine[0]); free(mine[1]);
 }
@@ -1060,56 +1174,20 @@ static int outputs_distinct(const read_t *reads, const int64_t *who, int64_t n) 
     return ok;
 }
 
-/* One slice of the run's reads: host side of every read, one GPU batch per strand model, outputs.  Returns the number
- * of reads that failed.  (The whole manifest used to be one batch: fine for thousands of reads, not for a flow cell.) */
-/* host side of every read of a slice (files, parameter estimation, anchors): all host threads */
-typedef struct { const run_t *R; read_t *reads; int64_t n; int batch_mode; } slice_prep_t;
-static void *slice_prepare(void *arg) {
-    slice_prep_t *sp = arg;
-    const double ts0 = now_s();
-    prep_ctx_t pc = {sp->R, sp->reads, !sp->batch_mode};
-    parallel_for(sp->n, prep_one, &pc);
-    t_add(&g_t_prep, now_s() - ts0);
-    return NULL;
-}
-
-/* What the GPU stage of a slice leaves for its rendering */
-static void release_read(read_t *rd);
-typedef struct {
-    run_t *Rp;
-    read_t *reads;
-    int64_t n_reads, n_ok;
-    int64_t *who;
-    sa_job_t *bj;
-    sa_pair_t **pairs_s[2];
-    int64_t *n_pairs_s[2];
-    sa_mea_pair_t **mea_s[2];
-    int64_t *n_mea_s[2];
-    sa_batch_t *batch[2];  /* alive until the slice is rendered (their packed records are what the rendering reads) */
-    int64_t *all_n_s[2], *all_sum_s[2];   /* -s 1: see out_job_t */
-    int p8_s[2];          /* see out_job_t */
-    sa_site_call_t **calls_s[2];   /* see out_job_t */
-    int64_t *n_calls_s[2];
-} render_job_t;
-static int64_t render_slice(render_job_t *job);
-
-/* GPU stage of a slice; returns the rendering job (NULL: nothing left to render -- the expectations mode writes its files
- * here -- with the number of failed reads in *n_failed_now) */
 /* --train-*: the assignments table (generate_top_n_kmers_from_sa_output) and the retrained models (train_normal_emmissions:
  * the prior is the -T / -C file as written on disk) */
 static void write_training(run_t *R, const char *t_model, const char *c_model, int device) {
-    const int n_strands = R->two_d ? 2 : 1;
-    if (!(R->train_assign || R->train_model[0] || R->train_model[1])) return;
-    for (int s = 0; s < n_strands; s++)   /* (a run without a read that aligned: empty tables) */
-        if (!R->train_tab[s] && sa_kmer_table_create(&R->train_tab[s], (s ? &R->smc : &R->smt)->model, R->train_n, R->train_min_prob, device) != SA_OK)
+    if (!R->want_train) return;
+    for (int s = 0; s < n_strands(R); s++)   /* (a run without a read that aligned: empty tables) */
+        if (!R->train_tab[s] && sa_kmer_table_create(&R->train_tab[s], R->sm[s].model, R->train_n, R->train_min_prob, device) != SA_OK)
             die("signalMachine: --train-*: no k-mer table%s", "");
     if (R->train_assign) {   /* the template table's 't' rows, then the complement table's 'c' rows */
-        for (int s = 0; s < n_strands; s++)
+        for (int s = 0; s < n_strands(R); s++)
             if (sa_kmer_table_write(R->train_tab[s], s, R->train_assign, s > 0) != SA_OK) die("signalMachine: cannot write %s", R->train_assign);
     }
-    for (int s = 0; s < n_strands; s++) {
+    for (int s = 0; s < n_strands(R); s++) {
         if (!R->train_model[s]) continue;
-        const strand_model_t *sm = s ? &R->smc : &R->smt;
+        const strand_model_t *sm = &R->sm[s];
         int64_t nk = 1;
         for (int i = 0; i < sm->k; i++) nk *= sm->n_alpha;
         sa_kmer_stat_t *st = calloc((size_t) nk, sizeof(sa_kmer_stat_t));
@@ -1142,279 +1220,187 @@ static void write_training(run_t *R, const char *t_model, const char *c_model, i
  * --emission twoDist: a single read brings its own model; the reads of a manifest share the strand's two-distribution model and
  * each job gets the scale_sd / var_sd its read's parameter estimation left (emissions_signal_scaleNoise, applied inside the batch:
  * SA_FLAG_TWO_DIST_ALL_KERNELS, whatever kernel family a read's regions take). */
-static int create_strand_batch(sa_batch_t **b, const run_t *R, const strand_model_t *sm, const read_t *reads, const int64_t *who,
-                               int strand, const sa_job_t *jobs, int64_t n_jobs, int64_t per_read, int device, unsigned flags) {
-    if (!R->two_dist) return sa_batch_create(b, sm->model, &R->p, jobs, n_jobs, R->ambig, device, flags);
-    if (!R->batch_mode) return sa_batch_create(b, reads[who[0]].model[strand], &R->p, jobs, n_jobs, R->ambig, device, flags);
-    sa_noise_scale_t *nz = malloc(sizeof(sa_noise_scale_t) * (size_t) (n_jobs > 0 ? n_jobs : 1));
-    if (!nz) return SA_ENOMEM;
+static int create_strand_batch(sa_batch_t **b, const slice_t *sl, int strand, const sa_job_t *jobs, int64_t n_jobs, int64_t per_read,
+                               unsigned flags) {
+    const run_t *R = sl->R;
+    const strand_model_t *sm = &R->sm[strand];
+    if (!R->two_dist) return sa_batch_create(b, sm->model, &R->p, jobs, n_jobs, R->ambig, sl->device, flags);
+    if (!R->batch_mode) return sa_batch_create(b, sl->reads[sl->who[0]].model[strand], &R->p, jobs, n_jobs, R->ambig, sl->device, flags);
+    sa_noise_scale_t *nz = xalloc(n_jobs, sizeof(sa_noise_scale_t), 0);
     for (int64_t i = 0; i < n_jobs; i++) {
-        const sa_npread_t *np = reads[who[i / per_read]].np;
-        const sa_strand_params_t *pp = strand == 0 ? &np->template_params : &np->complement_params;
+        const sa_strand_params_t *pp = np_params(sl->reads[sl->who[i / per_read]].np, strand);
         nz[i].scale_sd = pp->scale_sd;
         nz[i].var_sd = pp->var_sd;
     }
-    const int rc = sa_batch_create_noise_scaled(b, sm->model_two, &R->p, jobs, nz, n_jobs, R->ambig, device,
+    const int rc = sa_batch_create_noise_scaled(b, sm->model_two, &R->p, jobs, nz, n_jobs, R->ambig, sl->device,
                                                 flags | SA_FLAG_TWO_DIST_ALL_KERNELS);
     free(nz);
     return rc;
 }
 
-static render_job_t *run_slice(run_t *Rp, read_t *reads, int64_t n_reads, int batch_mode, int device, int64_t *n_failed_now) {
-#define R (*Rp)
-    *n_failed_now = 0;
-    /* (the host side of the slice's reads has run: slice_prepare, a slice ahead of this function) */
-    int64_t n_ok = 0;
-    for (int64_t i = 0; i < n_reads; i++) n_ok += reads[i].failed ? 0 : 1;
-    const double ts1 = now_s();
-    const strand_model_t *sms[2] = {&R.smt, &R.smc};
-    const int n_strands = R.two_d ? 2 : 1;
-
-    /* ---- the pair-HMM on the GPU: one batch per strand model, all reads side by side ---- */
-    sa_job_t *bj = malloc(sizeof(sa_job_t) * (size_t) (n_ok > 0 ? n_ok : 1));
-    int64_t *who = malloc(sizeof(int64_t) * (size_t) (n_ok > 0 ? n_ok : 1));
-    int64_t k = 0;
-    for (int64_t i = 0; i < n_reads; i++)
-        if (!reads[i].failed) who[k++] = i;
-
-    if (R.expect_mode) { /* impl/signalMachine.c:772-848 */
-        if (n_ok > 0) fprintf(stderr, "Starting expectations routine\n");
-        for (int s = 0; s < n_strands && n_ok > 0; s++) {
-            fprintf(stderr, "signalAlign - getting expectations for %s\n", s == 0 ? "template" : "complement");
-            for (int64_t j = 0; j < n_ok; j++) bj[j] = reads[who[j]].jobs[s];
-            double *trans = malloc(sizeof(double) * 9 * (size_t) n_ok), *lik = calloc((size_t) n_ok, sizeof(double));
-            for (int64_t j = 0; j < 9 * n_ok; j++) trans[j] = 0.001; /* transitionsPseudocount, :785 */
-            sa_assignment_t **as = calloc((size_t) n_ok, sizeof(*as));
-            int64_t *n_as = calloc((size_t) n_ok, sizeof(int64_t));
-            int rc = sa_expect_batch(sms[s]->model, &R.p, bj, n_ok, R.ambig, device, 0, trans, lik, as, n_as);
-            if (rc != SA_OK) {
-                fprintf(stderr, "signalMachine: expectations failed: %s\n", sa_strerror(rc));
-                exit(1);
+/* Expectations mode (-t / -c, impl/signalMachine.c:772-848): sa_expect_batch per strand, the .expectations file of every read */
+static int64_t run_slice_expect(run_t *R, read_t *reads, int64_t n_reads, int device) {
+    slice_t sl;
+    slice_open(&sl, R, reads, n_reads, device);
+    const int64_t n_ok = sl.n_ok;
+    sa_job_t *bj = xalloc(n_ok, sizeof(sa_job_t), 0);
+    if (n_ok > 0) fprintf(stderr, "Starting expectations routine\n");
+    for (int s = 0; s < n_strands(R) && n_ok > 0; s++) {
+        fprintf(stderr, "signalAlign - getting expectations for %s\n", strand_name(s));
+        for (int64_t j = 0; j < n_ok; j++) bj[j] = reads[sl.who[j]].jobs[s];
+        double *trans = xalloc(9 * n_ok, sizeof(double), 0), *lik = xalloc(n_ok, sizeof(double), 1);
+        for (int64_t j = 0; j < 9 * n_ok; j++) trans[j] = 0.001; /* transitionsPseudocount, :785 */
+        sa_assignment_t **as = xalloc(n_ok, sizeof(*as), 1);
+        int64_t *n_as = xalloc(n_ok, sizeof(int64_t), 1);
+        int rc = sa_expect_batch(R->sm[s].model, &R->p, bj, n_ok, R->ambig, device, 0, trans, lik, as, n_as);
+        if (rc != SA_OK) die("signalMachine: expectations failed: %s", sa_strerror(rc));
+        for (int64_t j = 0; j < n_ok; j++) {
+            read_t *rd = &reads[sl.who[j]];
+            if (R->hdp)
+                fprintf(stderr, s == 0 ? "signalAlign - got %" PRId64 " template HDP assignments\n"
+                                       : "signalAlign - got %" PRId64 "complement HDP assignments\n", n_as[j]);
+            if (rd->expect[s] != NULL) {
+                fprintf(stderr, "signalAlign - writing expectations to file: %s\n", rd->expect[s]);
+                write_expectations(rd->expect[s], &R->sm[s], np_params(rd->np, s), R->hdp, R->p.threshold, trans + 9 * j, lik[j],
+                                   &rd->jobs[s], as[j], n_as[j]);
             }
-            for (int64_t j = 0; j < n_ok; j++) {
-                read_t *rd = &reads[who[j]];
-                const char *path = s == 0 ? rd->t_expect : rd->c_expect;
-                if (R.hdp)
-                    fprintf(stderr, s == 0 ? "signalAlign - got %" PRId64 " template HDP assignments\n"
-                                           : "signalAlign - got %" PRId64 "complement HDP assignments\n", n_as[j]);
-                if (path != NULL) {
-                    fprintf(stderr, "signalAlign - writing expectations to file: %s\n", path);
-                    write_expectations(path, sms[s], s == 0 ? &rd->np->template_params : &rd->np->complement_params, R.hdp,
-                                       R.p.threshold, trans + 9 * j, lik[j], &rd->jobs[s], as[j], n_as[j]);
-                }
-                sa_free(as[j]);
-            }
-            free(trans); free(lik); free(as); free(n_as);
+            sa_free(as[j]);
         }
-        for (int64_t j = 0; j < n_ok; j++)
-            fprintf(stderr, "signalAlign - SUCCESS: finished alignment of query %s, exiting\n", reads[who[j]].label);
-        free(bj); free(who);
-        *n_failed_now = n_reads - n_ok;
-        for (int64_t i = 0; i < n_reads; i++) release_read(&reads[i]);
-        return NULL;
+        free(trans); free(lik); free(as); free(n_as);
     }
-
-    sa_pair_t **pairs_s[2] = {NULL, NULL};
-    int64_t *n_pairs_s[2] = {NULL, NULL};
-    sa_pair_t ***pairs = pairs_s;
-    int64_t **n_pairs = n_pairs_s;
-    sa_mea_pair_t **mea_s[2] = {NULL, NULL};
-    int64_t *n_mea_s[2] = {NULL, NULL};
-    sa_mea_pair_t ***mea = mea_s;
-    int64_t **n_mea = n_mea_s;
-    int validated = !batch_mode;   /* a single-read run has nobody to isolate a bad job from */
-    sa_batch_t *batches[2] = {NULL, NULL};
-    int64_t *all_n[2] = {NULL, NULL}, *all_sum[2] = {NULL, NULL};
-    /* -s 1 prints only the rows whose reference k-mer holds an X: the others stay on the device (SA_FLAG_VC_ROWS), the run's pair
-     * count and score come from the totals the device kept */
-    /* --site-calls / --site-calls-aggregate: every batch records its sites (SA_FLAG_SITE_CALLS) and keeps every row (the calls are
-     * made of the rows SA_FLAG_VC_ROWS would drop; -s 1 then filters on the host, write_vc) */
-    const int want_calls = R.site_calls || R.agg_path != NULL;
-    const unsigned calls_flag = want_calls ? SA_FLAG_SITE_CALLS : 0u;
-    const int want_train = R.train_assign || R.train_model[0] || R.train_model[1];
-    const unsigned vc_flag = (R.out_fmt == 1 && !R.mea && !want_calls && !want_train && !getenv("SA_CLI_VC_ON_HOST")) ? SA_FLAG_VC_ROWS : 0u;
-    sa_site_call_t **calls_s[2] = {NULL, NULL};
-    int64_t *n_calls_s[2] = {NULL, NULL};
-    /* -s 0 / -s 2 without --mea: 8-byte result records where the batch allows them (one path per cell: no ambiguity letter in any
-     * read's reference; fewer than 2^20 positions and events per read) -- the planner says SA_EUNSUPPORTED otherwise and the strand's
-     * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker). */
-    const unsigned p8_want = ((R.out_fmt == 0 || R.out_fmt == 2) && !R.mea && !want_calls && !getenv("SA_CLI_PAIRS16")) ? SA_FLAG_PAIRS8 : 0u;
-    int p8_used[2] = {0, 0};
-    /* --train-*: each strand's rows go into the run's k-mer table right after its batch ran, while the records are still in HBM;
-     * the tables are checkpointed here, so that the retry below (a read the planner refuses) can take the slice's rows back */
-    for (int s = 0; s < n_strands && want_train; s++) {
-        int rc = R.train_tab[s] ? SA_OK : sa_kmer_table_create(&R.train_tab[s], sms[s]->model, R.train_n, R.train_min_prob, device);
-        if (rc == SA_OK) rc = sa_kmer_table_checkpoint(R.train_tab[s]);
-        if (rc != SA_OK) {
-            fprintf(stderr, "signalMachine: --train-*: %s\n", sa_strerror(rc));
-            exit(1);
-        }
-    }
-    for (int s = 0; s < n_strands; s++) {
-        pairs[s] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(sa_pair_t *));
-        n_pairs[s] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(int64_t));
-        if (n_ok == 0) continue;
-        fprintf(stderr, s == 0 ? "signalAlign - starting template alignment\n" : "signalAlign - starting complement alignment\n");
-        for (int64_t j = 0; j < n_ok; j++) bj[j] = reads[who[j]].jobs[s];
-        if (want_calls) {
-            calls_s[s] = calloc((size_t) n_ok, sizeof(sa_site_call_t *));
-            n_calls_s[s] = calloc((size_t) n_ok, sizeof(int64_t));
-        }
-        int rc;
-        if (!R.mea) {   /* the batch stays alive for the rendering, which expands its packed records job by job */
-            sa_batch_t *b = NULL;
-            rc = create_strand_batch(&b, &R, sms[s], reads, who, s, bj, n_ok, 1, device, vc_flag | p8_want | calls_flag);
-            p8_used[s] = rc == SA_OK && p8_want != 0;
-            if (rc == SA_EUNSUPPORTED && p8_want)
-                rc = create_strand_batch(&b, &R, sms[s], reads, who, s, bj, n_ok, 1, device, vc_flag);
-            if (rc == SA_OK) rc = sa_batch_run(b);
-            if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
-            if (rc == SA_OK && want_train) {
-                rc = sa_kmer_table_add_batch(R.train_tab[s], b, bj, n_ok, s, NULL);
-                if (rc != SA_OK) {   /* (a batch that ran: nothing a retry without some reads would change) */
-                    fprintf(stderr, "signalMachine: --train-*: %s\n", sa_strerror(rc));
-                    exit(1);
-                }
-            }
-            for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) rc = sa_batch_n_pairs(b, j, &n_pairs[s][j]);
-            if (vc_flag && rc == SA_OK) {
-                free(all_n[s]); free(all_sum[s]);
-                all_n[s] = calloc((size_t) n_ok, sizeof(int64_t));
-                all_sum[s] = calloc((size_t) n_ok, sizeof(int64_t));
-                for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) rc = sa_batch_all_pairs_summary(b, j, &all_n[s][j], &all_sum[s][j]);
-            }
-            /* only the packed pairs (pinned host memory) are read from here on: the batch's HBM goes back now, so that the
-             * complement strand's batch plans into the whole card */
-            if (rc == SA_OK) rc = sa_batch_release_device(b);
-            if (rc == SA_OK) batches[s] = b;
-            else sa_batch_destroy(b);
-        } else { /* the same batch, kept alive for the path step: its pairs are still on the device */
-            sa_batch_t *b = NULL;
-            mea[s] = calloc((size_t) n_ok, sizeof(sa_mea_pair_t *));
-            n_mea[s] = calloc((size_t) n_ok, sizeof(int64_t));
-            rc = create_strand_batch(&b, &R, sms[s], reads, who, s, bj, n_ok, 1, device, calls_flag);
-            if (rc == SA_OK) rc = sa_batch_run(b);
-            if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, calls_s[s], n_calls_s[s], NULL);
-            for (int64_t j = 0; j < n_ok && rc == SA_OK; j++) {
-                sa_batch_n_pairs(b, j, &n_pairs[s][j]);
-                pairs[s][j] = malloc(sizeof(sa_pair_t) * (size_t) (n_pairs[s][j] > 0 ? n_pairs[s][j] : 1));
-                rc = sa_batch_pairs(b, j, pairs[s][j], n_pairs[s][j]);
-            }
-            if (rc == SA_OK) rc = sa_batch_mea(b, 0, mea[s], n_mea[s], NULL, NULL, NULL);
-            sa_batch_destroy(b);
-        }
-        if (!validated && rc != SA_OK && rc != SA_ENODEVICE && rc != SA_ENOMEM) {
-            /* the planner turned the batch down (a letter outside the alphabet, anchors that give no band, a cell of more paths
-             * or a matrix larger than the result records can name -- SA_EUNSUPPORTED --, ...): find the reads whose jobs it
-             * rejects (each planned alone on the host, all host threads), let them fail alone as the reference's
-             * one-process-per-read runs would, and start over.  Only when no read is to blame does the run end below. */
-            validated = 1;
-            validate_ctx_t vc = {&R, reads, who};
-            parallel_for(n_ok, validate_one, &vc);
-            int64_t k2 = 0;
-            for (int64_t j = 0; j < n_ok; j++)
-                if (!reads[who[j]].failed) who[k2++] = who[j];
-            if (k2 < n_ok) {
-                for (int q = 0; q < n_strands && want_train; q++)
-                    if (sa_kmer_table_rollback(R.train_tab[q]) != SA_OK) die("signalMachine: --train-*: rollback failed%s", "");
-                for (int q = 0; q <= s; q++) {
-                    sa_batch_destroy(batches[q]);
-                    batches[q] = NULL;
-                    for (int64_t j = 0; j < n_ok; j++) { sa_free(pairs[q][j]); if (R.mea && mea[q]) sa_free(mea[q][j]); }
-                    free(pairs[q]); free(n_pairs[q]);
-                    if (R.mea) { free(mea[q]); free(n_mea[q]); mea[q] = NULL; n_mea[q] = NULL; }
-                    if (calls_s[q]) {
-                        for (int64_t j = 0; j < n_ok; j++) sa_free(calls_s[q][j]);
-                        free(calls_s[q]); free(n_calls_s[q]); calls_s[q] = NULL; n_calls_s[q] = NULL;
-                    }
-                    pairs[q] = NULL; n_pairs[q] = NULL;
-                }
-                n_ok = k2;
-                s = -1;   /* both strands again, without the offenders */
-                continue;
-            }
-        }
-        if (rc != SA_OK) {
-            fprintf(stderr, "signalMachine: alignment failed: %s\n", sa_strerror(rc));
-            exit(1);
-        }
-    }
-
-    /* ---- outputs: rendered in parallel (one file per read), summary lines in read order ---- */
-    g_t_gpu += now_s() - ts1;
-    render_job_t *job = calloc(1, sizeof(*job));
-    job->Rp = Rp; job->reads = reads; job->n_reads = n_reads; job->n_ok = n_ok; job->who = who; job->bj = bj;
-    for (int s = 0; s < 2; s++) { job->pairs_s[s] = pairs[s]; job->n_pairs_s[s] = n_pairs[s]; job->mea_s[s] = mea[s]; job->n_mea_s[s] = n_mea[s]; job->batch[s] = batches[s]; job->all_n_s[s] = all_n[s]; job->all_sum_s[s] = all_sum[s]; job->p8_s[s] = p8_used[s];
-                              job->calls_s[s] = calls_s[s]; job->n_calls_s[s] = n_calls_s[s]; }
-    return job;
-#undef R
+    for (int64_t j = 0; j < n_ok; j++) report_read(R, &reads[sl.who[j]], NULL, NULL);
+    free(bj);
+    return slice_close(&sl);
 }
 
-/* rendering of a slice (one file per read, in parallel), summary lines in read order, then the reads' memory goes back;
- * returns the number of the slice's reads that failed */
-static int64_t render_slice(render_job_t *job) {
-    run_t *Rp = job->Rp;
-#define R (*Rp)
-    read_t *reads = job->reads;
-    const int64_t n_reads = job->n_reads, n_ok = job->n_ok;
-    int64_t *who = job->who;
-    sa_job_t *bj = job->bj;
-    sa_pair_t ***pairs = job->pairs_s;
-    int64_t **n_pairs = job->n_pairs_s;
-    sa_mea_pair_t ***mea = job->mea_s;
-    int64_t **n_mea = job->n_mea_s;
-    const int n_strands = R.two_d ? 2 : 1;
+/* Creates, runs and harvests the batch of strand s of an alignment slice into c->sr[s]; whatever it returns, the result is one
+ * strand_result_free can take.
+ * -s 1 prints only the rows whose reference k-mer holds an X: the others stay on the device (SA_FLAG_VC_ROWS), the run's pair
+ * count and score come from the totals the device kept.
+ * --site-calls / --site-calls-aggregate: every batch records its sites (SA_FLAG_SITE_CALLS) and keeps every row (the calls are
+ * made of the rows SA_FLAG_VC_ROWS would drop; -s 1 then filters on the host, write_vc).
+ * -s 0 / -s 2 without --mea: 8-byte result records where the batch allows them (one path per cell: no ambiguity letter in any
+ * read's reference; fewer than 2^20 positions and events per read) -- the planner says SA_EUNSUPPORTED otherwise and the strand's
+ * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker).
+ * --train-*: the strand's rows go into the run's k-mer table right after its batch ran, while the records are still in HBM.
+ * --mea: the pairs are copied out while the batch still has them on the device for the path step; the batch ends here.
+ * Otherwise the batch stays alive for the rendering, which expands its packed records job by job. */
+static int run_strand_batch(align_slice_t *c, int s) {
+    const slice_t *sl = &c->sl;
+    run_t *R = sl->R;
+    strand_result_t *sr = &c->sr[s];
+    const int64_t n = sl->n_ok;
+    const int want_calls = R->site_calls || R->agg_path != NULL;
+    unsigned flags = want_calls ? SA_FLAG_SITE_CALLS : 0u, p8 = 0u;
+    if (!R->mea && !want_calls) {
+        if (R->out_fmt == 1 && !R->want_train && !getenv("SA_CLI_VC_ON_HOST")) flags |= SA_FLAG_VC_ROWS;
+        if ((R->out_fmt == 0 || R->out_fmt == 2) && !getenv("SA_CLI_PAIRS16")) p8 = SA_FLAG_PAIRS8;
+    }
+    for (int64_t j = 0; j < n; j++) c->bj[j] = sl->reads[sl->who[j]].jobs[s];
+    sr->pairs = xalloc(n, sizeof(sa_pair_t *), 1);
+    sr->n_pairs = xalloc(n, sizeof(int64_t), 1);
+    if (want_calls) {
+        sr->calls = xalloc(n, sizeof(sa_site_call_t *), 1);
+        sr->n_calls = xalloc(n, sizeof(int64_t), 1);
+    }
+    if (R->mea) {
+        sr->mea = xalloc(n, sizeof(sa_mea_pair_t *), 1);
+        sr->n_mea = xalloc(n, sizeof(int64_t), 1);
+    }
+    sa_batch_t *b = NULL;
+    int rc = create_strand_batch(&b, sl, s, c->bj, n, 1, flags | p8);
+    sr->p8 = rc == SA_OK && p8 != 0;
+    if (rc == SA_EUNSUPPORTED && p8) rc = create_strand_batch(&b, sl, s, c->bj, n, 1, flags);
+    if (rc == SA_OK) rc = sa_batch_run(b);
+    if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, sr->calls, sr->n_calls, NULL);
+    if (rc == SA_OK && R->want_train) {   /* (a batch that ran: nothing a retry without some reads would change) */
+        rc = sa_kmer_table_add_batch(R->train_tab[s], b, c->bj, n, s, NULL);
+        if (rc != SA_OK) die("signalMachine: --train-*: %s", sa_strerror(rc));
+    }
+    if (R->mea) {
+        for (int64_t j = 0; j < n && rc == SA_OK; j++) {
+            sa_batch_n_pairs(b, j, &sr->n_pairs[j]);
+            sr->pairs[j] = xalloc(sr->n_pairs[j], sizeof(sa_pair_t), 0);
+            rc = sa_batch_pairs(b, j, sr->pairs[j], sr->n_pairs[j]);
+        }
+        if (rc == SA_OK) rc = sa_batch_mea(b, 0, sr->mea, sr->n_mea, NULL, NULL, NULL);
+        sa_batch_destroy(b);
+        return rc;
+    }
+    for (int64_t j = 0; j < n && rc == SA_OK; j++) rc = sa_batch_n_pairs(b, j, &sr->n_pairs[j]);
+    if ((flags & SA_FLAG_VC_ROWS) && rc == SA_OK) {
+        sr->all_n = xalloc(n, sizeof(int64_t), 1);
+        sr->all_sum = xalloc(n, sizeof(int64_t), 1);
+        for (int64_t j = 0; j < n && rc == SA_OK; j++) rc = sa_batch_all_pairs_summary(b, j, &sr->all_n[j], &sr->all_sum[j]);
+    }
+    /* only the packed pairs (pinned host memory) are read from here on: the batch's HBM goes back now, so that the
+     * complement strand's batch plans into the whole card */
+    if (rc == SA_OK) rc = sa_batch_release_device(b);
+    if (rc == SA_OK) sr->batch = b;
+    else sa_batch_destroy(b);
+    return rc;
+}
+
+/* rendering of an alignment slice (one file per read, in parallel), summary lines in read order */
+static void render_slice(align_slice_t *c) {
+    const slice_t *sl = &c->sl;
+    const run_t *R = sl->R;
     const double ts2 = now_s();
-    double (*score)[2] = calloc((size_t) (n_ok > 0 ? n_ok : 1), sizeof(*score));
-    unsigned char *tmpl_amb = (R.two_d && job->calls_s[1]) ? calloc((size_t) (n_ok > 0 ? n_ok : 1), 1) : NULL;
-    {
-        out_job_t oc = {&R, reads, who, pairs, n_pairs, score, mea, n_mea, job->batch, job->all_n_s, job->all_sum_s, job->p8_s,
-                        job->calls_s, job->n_calls_s, tmpl_amb};
-        if (outputs_distinct(reads, who, n_ok)) parallel_for(n_ok, output_one, &oc);
-        else for (int64_t j = 0; j < n_ok; j++) output_one(j, &oc);
-    }
-    for (int s = 0; s < 2; s++) { sa_batch_destroy(job->batch[s]); job->batch[s] = NULL; }
-    if (R.agg_path)   /* (in read order: the sums over reads do not depend on the rendering threads) */
-        for (int64_t j = 0; j < n_ok; j++)
-            for (int s = 0; s < n_strands && !reads[who[j]].failed; s++)
-                agg_add_read(&reads[who[j]], s, tmpl_amb && tmpl_amb[j], job->calls_s[s][j], job->n_calls_s[s][j],
-                             s == 0 ? R.smt.k : R.smc.k);
-    for (int64_t j = 0; j < n_ok; j++) {
-        read_t *rd = &reads[who[j]];
+    c->score = xalloc(sl->n_ok, sizeof(*c->score), 1);
+    c->tmpl_amb = (R->two_d && c->sr[1].calls) ? xalloc(sl->n_ok, 1, 1) : NULL;
+    if (outputs_distinct(sl->reads, sl->who, sl->n_ok)) parallel_for(sl->n_ok, output_one, c);
+    else for (int64_t j = 0; j < sl->n_ok; j++) output_one(j, c);
+    for (int64_t j = 0; j < sl->n_ok; j++) {
+        const read_t *rd = &sl->reads[sl->who[j]];
         if (rd->failed) continue;
-        fprintf(stdout, "%s %" PRId64 "\t%" PRId64 "(%f)\t", rd->label, rd->n_guide, job->all_n_s[0] ? job->all_n_s[0][j] : n_pairs[0][j], score[j][0]);
-        if (R.two_d) fprintf(stdout, "%" PRId64 "(%f)\n", job->all_n_s[1] ? job->all_n_s[1][j] : n_pairs[1][j], score[j][1]);
-        else fprintf(stdout, "\n");
-        fprintf(stderr, "signalAlign - SUCCESS: finished alignment of query %s, exiting\n", rd->label);
-        for (int s = 0; s < n_strands; s++) {
-            sa_free(pairs[s][j]);
-            if (R.mea) sa_free(mea[s][j]);
+        int64_t n_all[2] = {0, 0};
+        for (int s = 0; s < n_strands(R); s++) {
+            const strand_result_t *sr = &c->sr[s];
+            n_all[s] = sr->all_n ? sr->all_n[j] : sr->n_pairs[j];
+            /* (the aggregate's sums over reads are taken here, in read order: they do not depend on the rendering threads) */
+            if (R->agg_path) agg_add_read(rd, s, c->tmpl_amb && c->tmpl_amb[j], sr->calls[j], sr->n_calls[j], R->sm[s].k);
         }
+        report_read(R, rd, n_all, c->score[j]);
     }
-    free(tmpl_amb);
-    for (int s = 0; s < n_strands; s++)
-        if (job->calls_s[s]) {
-            for (int64_t j = 0; j < n_ok; j++) sa_free(job->calls_s[s][j]);
-            free(job->calls_s[s]); free(job->n_calls_s[s]);
-        }
+    free(c->tmpl_amb);
+    free(c->score);
+    for (int s = 0; s < 2; s++) strand_result_free(&c->sr[s], sl->n_ok);
     t_add(&g_t_render, now_s() - ts2);
-    int64_t n_failed = 0;
-    for (int64_t i = 0; i < n_reads; i++) n_failed += reads[i].failed ? 1 : 0;
-    for (int s = 0; s < n_strands; s++) { free(pairs[s]); free(n_pairs[s]); free(job->all_n_s[s]); free(job->all_sum_s[s]); if (R.mea) { free(mea[s]); free(n_mea[s]); } }
-    free(score); free(bj); free(who);
-    for (int64_t i = 0; i < n_reads; i++) release_read(&reads[i]);
-    return n_failed;
-#undef R
 }
 
-/* what a read holds once its outputs are written */
-static void release_read(read_t *rd) {
-    if (rd->pA) sa_cigar_free(rd->pA);
-    if (rd->np) sa_npread_free(rd->np);
-    free(rd->forward_seq); free(rd->backward_seq);
-    for (int s = 0; s < 2; s++) { free(rd->ax[s]); free(rd->ay[s]); rd->ax[s] = rd->ay[s] = NULL; }
-    for (int s = 0; s < 2; s++) { if (rd->model[s]) sa_model_destroy(rd->model[s]); rd->model[s] = NULL; }
-    rd->pA = NULL; rd->np = NULL; rd->forward_seq = rd->backward_seq = NULL;
+/* Alignment mode: the pair-HMM on the GPU, one batch per strand model with all reads side by side, then the outputs */
+static int64_t run_slice_align(run_t *R, read_t *reads, int64_t n_reads, int device) {
+    align_slice_t c;
+    memset(&c, 0, sizeof(c));
+    slice_t *sl = &c.sl;
+    /* (the host side of the slice's reads has run: slice_prepare, a slice ahead of this function) */
+    slice_open(sl, R, reads, n_reads, device);
+    const double ts1 = now_s();
+    c.bj = xalloc(sl->n_ok, sizeof(sa_job_t), 0);
+    /* --train-*: the tables are checkpointed here, so that the retry below (a read the planner refuses) can take the slice's
+     * rows back */
+    for (int s = 0; s < n_strands(R) && R->want_train; s++) {
+        int rc = R->train_tab[s] ? SA_OK : sa_kmer_table_create(&R->train_tab[s], R->sm[s].model, R->train_n, R->train_min_prob, device);
+        if (rc == SA_OK) rc = sa_kmer_table_checkpoint(R->train_tab[s]);
+        if (rc != SA_OK) die("signalMachine: --train-*: %s", sa_strerror(rc));
+    }
+    for (int s = 0; s < n_strands(R) && sl->n_ok > 0; s++) {
+        fprintf(stderr, "signalAlign - starting %s alignment\n", strand_name(s));
+        const int64_t n_jobs = sl->n_ok;
+        const int rc = run_strand_batch(&c, s);
+        if (drop_refused_reads(sl, rc, NULL, 1, NULL)) {
+            for (int q = 0; q < n_strands(R) && R->want_train; q++)
+                if (sa_kmer_table_rollback(R->train_tab[q]) != SA_OK) die("signalMachine: --train-*: rollback failed%s", "");
+            for (int q = 0; q <= s; q++) strand_result_free(&c.sr[q], n_jobs);
+            s = -1;   /* both strands again, without the offenders */
+            continue;
+        }
+        if (rc != SA_OK) die("signalMachine: alignment failed: %s", sa_strerror(rc));
+    }
+    g_t_gpu += now_s() - ts1;
+    render_slice(&c);
+    free(c.bj);
+    return slice_close(sl);
 }
 
 /* ---- --snp-step N --snp-dir DIR: single-nucleotide probabilities (singleNucleotideProbabilities.py:551-723) ----
@@ -1422,54 +1408,62 @@ static void release_read(read_t *rd) {
  * (replace_periodic_reference_positions; the default ambiguity table makes X the four bases).  sa_batch_position_calls folds
  * the rows of every X position on the device (CallMethylation.call_methyls); the N step files of a read are merged into
  * DIR/<label>.tsv (discover_single_nucleotide_probabilities).  fast5_input names the .npRead: the one deliberate difference. */
+typedef struct {   /* what one strand's batch leaves, [read * N + step] each */
+    sa_position_call_t **calls;
+    int64_t *n_calls;
+    int32_t *x_min, *x_max;
+    int64_t *n_pairs, *sum_e7;
+} snp_result_t;
+
+static void snp_result_free(snp_result_t *r, int64_t n_jobs) {
+    for (int64_t i = 0; i < n_jobs && r->calls; i++) sa_free(r->calls[i]);
+    free(r->calls); free(r->n_calls); free(r->x_min); free(r->x_max); free(r->n_pairs); free(r->sum_e7);
+    memset(r, 0, sizeof(*r));
+}
+
 typedef struct {
-    const run_t *run;
-    read_t *reads;
-    const int64_t *who;
-    int64_t N;
-    sa_position_call_t **calls[2];   /* [strand][read * N + step] */
-    int64_t *n_calls[2];
-    int32_t *x_min[2], *x_max[2];
-} snp_out_t;
+    slice_t sl;
+    int64_t N, n_slots;   /* n_slots: the reads the slice started with, times N */
+    char **tgt[2];        /* the substituted targets: read j, step s, strand q at tgt[q][j * N + s] */
+    sa_job_t *jobs[2];
+    snp_result_t sr[2];
+} snp_slice_t;
 
 /* contig coordinate of index t of a strand's target (the TSV's reference_index of a k-mer at t covers t .. t + k - 1) */
 static int64_t snp_contig_pos(const read_t *rd, int s, int64_t t) {
-    const int64_t off = s == 0 ? rd->r_shift_t : rd->r_shift_c;
+    const int64_t off = rd->st[s].r_shift;
     const int same = (s == 0 && rd->forward) || (s == 1 && !rd->forward);
     return same ? off + t : off - 1 - t;
 }
 
 static void snp_output_one(int64_t j, void *ctx) {
-    snp_out_t *c = ctx;
-    const run_t *R = c->run;
-    read_t *rd = &c->reads[c->who[j]];
-    const int n_strands = R->two_d ? 2 : 1;
+    snp_slice_t *c = ctx;
+    const run_t *R = c->sl.R;
+    read_t *rd = &c->sl.reads[c->sl.who[j]];
     int64_t cap = 0;
     for (int64_t s = 0; s < c->N; s++)
-        for (int q = 0; q < n_strands; q++) cap += c->n_calls[q][j * c->N + s];
-    sa_snp_site_t *sites = malloc(sizeof(sa_snp_site_t) * (size_t) (cap > 0 ? cap : 1));
-    if (!sites) die("signalMachine: out of memory%s", "");
+        for (int q = 0; q < n_strands(R); q++) cap += c->sr[q].n_calls[j * c->N + s];
+    sa_snp_site_t *sites = xalloc(cap, sizeof(sa_snp_site_t), 0);
     int64_t n = 0;
     for (int64_t s = 0; s < c->N; s++) {   /* one step file after the other */
         const int64_t js = j * c->N + s;
         /* the window of call_methyls (:160-169) over the reference_index of every row of the step's file, both strands */
         int64_t lo_ref = INT64_MAX, hi_ref = INT64_MIN;
-        for (int q = 0; q < n_strands; q++) {
-            if (c->x_min[q][js] < 0) continue;
-            const int k = q == 0 ? R->smt.k : R->smc.k;
-            const char *target = q == 0 ? rd->template_target : rd->complement_target;
-            const int64_t len = (int64_t) strlen(target), off = q == 0 ? rd->r_shift_t : rd->r_shift_c;
-            const int64_t a = adjust_ref(c->x_min[q][js], off, len - k, len, q == 0, rd->forward);
-            const int64_t b = adjust_ref(c->x_max[q][js], off, len - k, len, q == 0, rd->forward);
+        for (int q = 0; q < n_strands(R); q++) {
+            if (c->sr[q].x_min[js] < 0) continue;
+            const int k = R->sm[q].k;
+            const int64_t len = (int64_t) strlen(rd->st[q].target), off = rd->st[q].r_shift;
+            const int64_t a = adjust_ref(c->sr[q].x_min[js], off, len - k, len, q == 0, rd->forward);
+            const int64_t b = adjust_ref(c->sr[q].x_max[js], off, len - k, len, q == 0, rd->forward);
             lo_ref = a < lo_ref ? a : lo_ref; lo_ref = b < lo_ref ? b : lo_ref;
             hi_ref = a > hi_ref ? a : hi_ref; hi_ref = b > hi_ref ? b : hi_ref;
         }
         if (lo_ref > hi_ref) continue;   /* no row at all: the reference's step file cannot be parsed and is missing */
         int64_t w_lo = 0, w_hi = 0;
         sa_snp_site_window(lo_ref, hi_ref, c->N, &w_lo, &w_hi);
-        for (int q = 0; q < n_strands; q++) {   /* template sites, then complement sites, each ascending */
-            const sa_position_call_t *pc = c->calls[q][js];
-            const int64_t m = c->n_calls[q][js];
+        for (int q = 0; q < n_strands(R); q++) {   /* template sites, then complement sites, each ascending */
+            const sa_position_call_t *pc = c->sr[q].calls[js];
+            const int64_t m = c->sr[q].n_calls[js];
             const int same = (q == 0 && rd->forward) || (q == 1 && !rd->forward);
             for (int64_t i0 = 0; i0 < m; i0++) {
                 const sa_position_call_t *p = &pc[same ? i0 : m - 1 - i0];
@@ -1496,149 +1490,119 @@ static void snp_output_one(int64_t j, void *ctx) {
     free(sites);
 }
 
-/* plans every substituted job of a read alone on the host (validate_read for the N copies) */
-typedef struct { const run_t *R; read_t *reads; const int64_t *who; sa_job_t *const *jobs; int64_t N; } snp_validate_t;
-static void snp_validate_one(int64_t j, void *ctx) {
-    snp_validate_t *v = ctx;
-    read_t *rd = &v->reads[v->who[j]];
-    for (int q = 0; q < (v->R->two_d ? 2 : 1) && !rd->failed; q++)
-        for (int64_t s = 0; s < v->N && !rd->failed; s++) {
-            const int rc = sa_plan_describe(q == 0 ? v->R->smt.model : v->R->smc.model, &v->R->p, &v->jobs[q][j * v->N + s], v->R->ambig,
-                                            0, NULL, NULL, 0, NULL, 0, NULL, 0);
-            if (rc != SA_OK) fail(rd, 0, "alignment job rejected: %s", sa_strerror(rc));
-        }
-    if (rd->failed) fprintf(stderr, "[signalMachine] ERROR: read %s skipped: %s\n", rd->label, rd->err);
-}
-
-/* GPU stage and outputs of a slice in --snp-step mode; returns the number of the slice's reads that failed */
-static int64_t run_slice_snp(run_t *Rp, read_t *reads, int64_t n_reads, int batch_mode, int device) {
-#define R (*Rp)
-    const int n_strands = R.two_d ? 2 : 1;
-    const int64_t N = R.snp_step;
-    const strand_model_t *sms[2] = {&R.smt, &R.smc};
-    const double ts1 = now_s();
-    int64_t *who = malloc(sizeof(int64_t) * (size_t) (n_reads > 0 ? n_reads : 1));
-    int64_t n_ok = 0;
-    for (int64_t i = 0; i < n_reads; i++)
-        if (!reads[i].failed) who[n_ok++] = i;
-    /* the substituted targets: read j, step s, strand q at tgt[q][j * N + s] */
-    char **tgt[2] = {NULL, NULL};
-    sa_job_t *jobs[2] = {NULL, NULL};
-    const size_t nj_all = (size_t) (n_ok > 0 ? n_ok : 1) * (size_t) N;
-    for (int q = 0; q < n_strands; q++) {
-        tgt[q] = calloc(nj_all, sizeof(char *));
-        jobs[q] = calloc(nj_all, sizeof(sa_job_t));
-        if (!tgt[q] || !jobs[q]) die("signalMachine: out of memory%s", "");
+/* the substituted copies of every read's jobs */
+static void snp_build_jobs(snp_slice_t *c) {
+    const slice_t *sl = &c->sl;
+    const int64_t N = c->N;
+    c->n_slots = sl->n_ok * N;
+    for (int q = 0; q < n_strands(sl->R); q++) {
+        c->tgt[q] = xalloc(c->n_slots, sizeof(char *), 1);
+        c->jobs[q] = xalloc(c->n_slots, sizeof(sa_job_t), 1);
     }
-    for (int64_t j = 0; j < n_ok; j++) {
-        read_t *rd = &reads[who[j]];
+    for (int64_t j = 0; j < sl->n_ok; j++) {
+        const read_t *rd = &sl->reads[sl->who[j]];
         const int64_t hi = rd->win_lo + (int64_t) strlen(rd->forward_seq) - 1;
-        for (int q = 0; q < n_strands; q++) {
-            const char *t = q == 0 ? rd->template_target : rd->complement_target;
+        for (int q = 0; q < n_strands(sl->R); q++) {
+            const char *t = rd->st[q].target;
             const int from_fwd = t == rd->forward_seq;   /* forward_seq[i] at win_lo + i, backward_seq[i] at hi - i */
             const int64_t len = (int64_t) strlen(t);
             for (int64_t s = 0; s < N; s++) {
-                char *o = malloc((size_t) len + 1);
-                if (!o) die("signalMachine: out of memory%s", "");
+                char *o = xalloc(len + 1, 1, 0);
                 sa_snp_substitute(t, len, from_fwd ? rd->win_lo : hi, !from_fwd, N, s, 'X', o);
-                tgt[q][j * N + s] = o;
-                jobs[q][j * N + s] = rd->jobs[q];
-                jobs[q][j * N + s].ref = o;
+                c->tgt[q][j * N + s] = o;
+                c->jobs[q][j * N + s] = rd->jobs[q];
+                c->jobs[q][j * N + s].ref = o;
             }
         }
     }
-    snp_out_t oc;
-    memset(&oc, 0, sizeof(oc));
-    oc.run = Rp; oc.reads = reads; oc.who = who; oc.N = N;
-    int64_t *n_pairs[2] = {NULL, NULL}, *sum_e7[2] = {NULL, NULL};
-    int validated = !batch_mode;
-    for (int q = 0; q < n_strands; q++) {
-        const int64_t nj = n_ok * N;
-        oc.calls[q] = calloc(nj_all, sizeof(sa_position_call_t *));
-        oc.n_calls[q] = calloc(nj_all, sizeof(int64_t));
-        oc.x_min[q] = calloc(nj_all, sizeof(int32_t));
-        oc.x_max[q] = calloc(nj_all, sizeof(int32_t));
-        n_pairs[q] = calloc(nj_all, sizeof(int64_t));
-        sum_e7[q] = calloc(nj_all, sizeof(int64_t));
-        if (nj == 0) continue;
-        fprintf(stderr, q == 0 ? "signalAlign - starting template alignment\n" : "signalAlign - starting complement alignment\n");
-        sa_batch_t *b = NULL;
-        int rc = create_strand_batch(&b, &R, sms[q], reads, who, q, jobs[q], nj, N, device, SA_FLAG_POSITION_CALLS);
-        if (rc == SA_OK) rc = sa_batch_run(b);
-        if (rc == SA_OK) rc = sa_batch_position_calls(b, 0, oc.calls[q], oc.n_calls[q], oc.x_min[q], oc.x_max[q], NULL);
-        for (int64_t i = 0; i < nj && rc == SA_OK; i++) rc = sa_batch_all_pairs_summary(b, i, &n_pairs[q][i], &sum_e7[q][i]);
-        sa_batch_destroy(b);
-        if (!validated && rc != SA_OK && rc != SA_ENODEVICE && rc != SA_ENOMEM) {
-            /* the planner turned the batch down: the reads whose substituted jobs it rejects fail alone, the rest start over */
-            validated = 1;
-            snp_validate_t vc = {&R, reads, who, jobs, N};
-            parallel_for(n_ok, snp_validate_one, &vc);
-            /* the slice closes up: a refused read's targets are freed, a kept read's move down to its new place and leave
-             * their old slots empty, so that every target is owned by exactly one slot of tgt */
-            int64_t k2 = 0;
-            for (int64_t j = 0; j < n_ok; j++) {
-                const int refused = reads[who[j]].failed;
-                for (int q2 = 0; q2 < n_strands; q2++)
-                    for (int64_t s = 0; s < N; s++) {
-                        char **src = &tgt[q2][j * N + s];
-                        if (refused) {
-                            free(*src);
-                            *src = NULL;
-                        } else if (k2 != j) {
-                            tgt[q2][k2 * N + s] = *src;
-                            jobs[q2][k2 * N + s] = jobs[q2][j * N + s];
-                            *src = NULL;
-                        }
-                    }
-                if (!refused) who[k2++] = who[j];
-            }
-            if (k2 < n_ok) {
-                for (int q2 = 0; q2 <= q; q2++) {
-                    for (size_t i = 0; i < nj_all; i++) sa_free(oc.calls[q2][i]);
-                    free(oc.calls[q2]); free(oc.n_calls[q2]); free(oc.x_min[q2]); free(oc.x_max[q2]);
-                    free(n_pairs[q2]); free(sum_e7[q2]);
-                    oc.calls[q2] = NULL; oc.n_calls[q2] = NULL; oc.x_min[q2] = oc.x_max[q2] = NULL;
-                    n_pairs[q2] = sum_e7[q2] = NULL;
+}
+
+/* The slice closes up after drop_refused_reads: the read now at k was at kept_from[k].  A refused read's targets are freed, a
+ * kept read's move down to its new place and leave their old slots empty, so that every target is owned by exactly one slot. */
+static void snp_close_up(snp_slice_t *c, int64_t n_before, const int64_t *kept_from) {
+    const int64_t N = c->N;
+    for (int64_t j = 0, k = 0; j < n_before; j++) {
+        const int kept = k < c->sl.n_ok && kept_from[k] == j;
+        for (int q = 0; q < n_strands(c->sl.R); q++)
+            for (int64_t s = 0; s < N; s++) {
+                char **src = &c->tgt[q][j * N + s];
+                if (!kept) {
+                    free(*src);
+                    *src = NULL;
+                } else if (k != j) {
+                    c->tgt[q][k * N + s] = *src;
+                    c->jobs[q][k * N + s] = c->jobs[q][j * N + s];
+                    *src = NULL;
                 }
-                n_ok = k2;
-                q = -1;   /* both strands again, without the offenders */
-                continue;
             }
-        }
-        if (rc != SA_OK) {
-            fprintf(stderr, "signalMachine: alignment failed: %s\n", sa_strerror(rc));
-            exit(1);
-        }
+        k += kept;
     }
+}
+
+/* creates, runs and harvests the batch of strand q of a --snp-step slice into c->sr[q] */
+static int snp_run_strand_batch(snp_slice_t *c, int q) {
+    snp_result_t *r = &c->sr[q];
+    const int64_t nj = c->sl.n_ok * c->N;
+    r->calls = xalloc(nj, sizeof(sa_position_call_t *), 1);
+    r->n_calls = xalloc(nj, sizeof(int64_t), 1);
+    r->x_min = xalloc(nj, sizeof(int32_t), 1);
+    r->x_max = xalloc(nj, sizeof(int32_t), 1);
+    r->n_pairs = xalloc(nj, sizeof(int64_t), 1);
+    r->sum_e7 = xalloc(nj, sizeof(int64_t), 1);
+    sa_batch_t *b = NULL;
+    int rc = create_strand_batch(&b, &c->sl, q, c->jobs[q], nj, c->N, SA_FLAG_POSITION_CALLS);
+    if (rc == SA_OK) rc = sa_batch_run(b);
+    if (rc == SA_OK) rc = sa_batch_position_calls(b, 0, r->calls, r->n_calls, r->x_min, r->x_max, NULL);
+    for (int64_t i = 0; i < nj && rc == SA_OK; i++) rc = sa_batch_all_pairs_summary(b, i, &r->n_pairs[i], &r->sum_e7[i]);
+    sa_batch_destroy(b);
+    return rc;
+}
+
+/* --snp-step mode: GPU stage and outputs of a slice */
+static int64_t run_slice_snp(run_t *R, read_t *reads, int64_t n_reads, int device) {
+    snp_slice_t c;
+    memset(&c, 0, sizeof(c));
+    slice_t *sl = &c.sl;
+    const int64_t N = c.N = R->snp_step;
+    const double ts1 = now_s();
+    slice_open(sl, R, reads, n_reads, device);
+    snp_build_jobs(&c);
+    int64_t *kept_from = xalloc(sl->n_ok, sizeof(int64_t), 0);
+    for (int q = 0; q < n_strands(R) && sl->n_ok > 0; q++) {
+        fprintf(stderr, "signalAlign - starting %s alignment\n", strand_name(q));
+        const int64_t n_before = sl->n_ok;
+        const int rc = snp_run_strand_batch(&c, q);
+        if (drop_refused_reads(sl, rc, c.jobs, N, kept_from)) {
+            snp_close_up(&c, n_before, kept_from);
+            for (int q2 = 0; q2 <= q; q2++) snp_result_free(&c.sr[q2], n_before * N);
+            q = -1;   /* both strands again, without the offenders */
+            continue;
+        }
+        if (rc != SA_OK) die("signalMachine: alignment failed: %s", sa_strerror(rc));
+    }
+    free(kept_from);
     g_t_gpu += now_s() - ts1;
     const double ts2 = now_s();
-    parallel_for(n_ok, snp_output_one, &oc);
+    parallel_for(sl->n_ok, snp_output_one, &c);
     /* the summary lines of the N -s 0 runs of every read, step after step */
-    for (int64_t j = 0; j < n_ok; j++) {
-        read_t *rd = &reads[who[j]];
+    for (int64_t j = 0; j < sl->n_ok; j++)
         for (int64_t s = 0; s < N; s++) {
             const int64_t js = j * N + s;
-            double score[2];
-            for (int q = 0; q < n_strands; q++)
-                score[q] = 100.0 * (double) sum_e7[q][js] / ((double) n_pairs[q][js] * PROB_1);
-            fprintf(stdout, "%s %" PRId64 "\t%" PRId64 "(%f)\t", rd->label, rd->n_guide, n_pairs[0][js], score[0]);
-            if (R.two_d) fprintf(stdout, "%" PRId64 "(%f)\n", n_pairs[1][js], score[1]);
-            else fprintf(stdout, "\n");
-            fprintf(stderr, "signalAlign - SUCCESS: finished alignment of query %s, exiting\n", rd->label);
+            int64_t n[2] = {0, 0};
+            double score[2] = {0.0, 0.0};
+            for (int q = 0; q < n_strands(R); q++) {
+                n[q] = c.sr[q].n_pairs[js];
+                score[q] = 100.0 * (double) c.sr[q].sum_e7[js] / ((double) n[q] * PROB_1);
+            }
+            report_read(R, &reads[sl->who[j]], n, score);
         }
-    }
     t_add(&g_t_render, now_s() - ts2);
-    for (int q = 0; q < n_strands; q++) {
-        for (size_t i = 0; i < nj_all; i++) { sa_free(oc.calls[q] ? oc.calls[q][i] : NULL); free(tgt[q][i]); }
-        free(oc.calls[q]); free(oc.n_calls[q]); free(oc.x_min[q]); free(oc.x_max[q]);
-        free(n_pairs[q]); free(sum_e7[q]); free(tgt[q]); free(jobs[q]);
+    for (int q = 0; q < n_strands(R); q++) {
+        snp_result_free(&c.sr[q], sl->n_ok * N);
+        for (int64_t i = 0; i < c.n_slots; i++) free(c.tgt[q][i]);
+        free(c.tgt[q]); free(c.jobs[q]);
     }
-    free(who);
-    int64_t n_failed = 0;
-    for (int64_t i = 0; i < n_reads; i++) n_failed += reads[i].failed ? 1 : 0;
-    for (int64_t i = 0; i < n_reads; i++) release_read(&reads[i]);
-    return n_failed;
-#undef R
+    return slice_close(sl);
 }
 
 int main(int argc, char **argv) {
@@ -1766,25 +1730,24 @@ int main(int argc, char **argv) {
     /* the reads of this run */
     read_t *reads = NULL;
     int64_t n_reads = 0;
-    const int batch_mode = manifest != NULL;
-    R.batch_mode = batch_mode;
-    if (batch_mode) {
+    R.batch_mode = manifest != NULL;
+    if (R.batch_mode) {
         n_reads = load_manifest(manifest, &reads);
         if (n_reads < 0) die("[signalMachine]ERROR: cannot read the batch manifest %s", manifest);
         for (int64_t i = 0; i < n_reads; i++) {
             if (reads[i].seq_name == NULL && seq_name != NULL) reads[i].seq_name = strdup(seq_name);
-            if (reads[i].t_expect != NULL || reads[i].c_expect != NULL) R.expect_mode = 1;
+            if (reads[i].expect[0] != NULL || reads[i].expect[1] != NULL) R.expect_mode = 1;
         }
         if (R.expect_mode)
             for (int64_t i = 0; i < n_reads; i++)
-                if (reads[i].t_expect == NULL && reads[i].c_expect == NULL)
+                if (reads[i].expect[0] == NULL && reads[i].expect[1] == NULL)
                     die("[signalMachine]ERROR: batch manifest mixes expectation and alignment reads (%s)", reads[i].label);
     } else {
         reads = calloc(1, sizeof(read_t));
         n_reads = 1;
         reads[0].label = label; reads[0].npread_path = npread_path; reads[0].cigar_path = cigar_path;
         reads[0].post_path = post_path; reads[0].post_path2 = post_path2; reads[0].seq_name = seq_name;
-        reads[0].t_expect = t_expect; reads[0].c_expect = c_expect;
+        reads[0].expect[0] = t_expect; reads[0].expect[1] = c_expect;
         R.expect_mode = t_expect != NULL || c_expect != NULL;
         if (fwd_ref == NULL || seq_name == NULL) {
             /* the reference needs -n; kept after the cigar check so that the error order matches (impl/signalMachine.c:642-663) */
@@ -1799,7 +1762,8 @@ int main(int argc, char **argv) {
     if (R.two_dist && (R.hdp || t_hdp != NULL || c_hdp != NULL || R.expect_mode || t_expect != NULL || c_expect != NULL))
         die("signalMachine: --emission twoDist aligns reads with a Gaussian model: not with an .nhdp, not with -t / -c%s", "");
 
-    if (R.train_assign || R.train_model[0] || R.train_model[1]) {
+    R.want_train = R.train_assign || R.train_model[0] || R.train_model[1];
+    if (R.want_train) {
         if (R.expect_mode || R.mea) die("signalMachine: --train-* needs the alignment mode without --mea%s", "");
         if (R.train_model[1] && !R.two_d) die("signalMachine: --train-complement-model needs a 2-D run%s", "");
         if (R.train_n < 1 || !(R.train_min_prob >= 0 && R.train_min_prob <= 1)) die("signalMachine: bad --train-max-assignments / --train-min-prob%s", "");
@@ -1811,12 +1775,12 @@ int main(int argc, char **argv) {
         if (R.expect_mode) { usage(); die("signalMachine: --snp-step cannot be combined with -t/-c%s", ""); }
         if (R.mea) { usage(); die("signalMachine: --snp-step cannot be combined with --mea%s", ""); }
         if (R.site_calls || R.agg_path) { usage(); die("signalMachine: --snp-step cannot be combined with --site-calls / --site-calls-aggregate%s", ""); }
-        if (R.train_assign || R.train_model[0] || R.train_model[1]) { usage(); die("signalMachine: --snp-step cannot be combined with --train-*%s", ""); }
+        if (R.want_train) { usage(); die("signalMachine: --snp-step cannot be combined with --train-*%s", ""); }
         for (int64_t i = 0; i < n_reads; i++)
             if (reads[i].post_path || reads[i].post_path2) {
                 usage();
-                die(batch_mode ? "signalMachine: --snp-step writes no posteriors file: the manifest's posteriors column of %s must be '-'"
-                               : "signalMachine: --snp-step writes no posteriors file: -u / -i not allowed%s", batch_mode ? reads[i].label : "");
+                die(R.batch_mode ? "signalMachine: --snp-step writes no posteriors file: the manifest's posteriors column of %s must be '-'"
+                                 : "signalMachine: --snp-step writes no posteriors file: -u / -i not allowed%s", R.batch_mode ? reads[i].label : "");
             }
     }
 
@@ -1837,12 +1801,12 @@ int main(int argc, char **argv) {
     }
     if (R.hdp && t_hdp == NULL) die("signalAlign - ERROR: --sm3Hdp needs -v <template .nhdp>", NULL);
 
-    if (load_strand_model(&R.smt, t_model, R.hdp ? t_hdp : NULL) != SA_OK)
+    if (load_strand_model(&R.sm[0], t_model, R.hdp ? t_hdp : NULL) != SA_OK)
         die("signalAlign - ERROR: couldn't find model file here: %s", t_model);
-    if (R.two_d && load_strand_model(&R.smc, c_model, R.hdp ? c_hdp : NULL) != SA_OK)
+    if (R.two_d && load_strand_model(&R.sm[1], c_model, R.hdp ? c_hdp : NULL) != SA_OK)
         die("signalAlign - ERROR: couldn't find model file here: %s", c_model);
-    for (int s = 0; s < (R.two_d ? 2 : 1) && R.two_dist && batch_mode; s++) {   /* the base of the slices' noise-scaled batches */
-        strand_model_t *sm = s == 0 ? &R.smt : &R.smc;
+    for (int s = 0; s < n_strands(&R) && R.two_dist && R.batch_mode; s++) {   /* the base of the slices' noise-scaled batches */
+        strand_model_t *sm = &R.sm[s];
         if (sa_model_clone_with_table(&sm->model_two, sm->model, sm->table_orig) != SA_OK ||
             sa_model_set_emission(sm->model_two, SA_EMISSION_TWO_DIST) != SA_OK)
             die("signalMachine: --emission twoDist: could not set up the two-distribution model%s", "");
@@ -1857,8 +1821,7 @@ int main(int argc, char **argv) {
     }
 
     if (R.hdp && !R.expect_mode) { /* the alignment branch sets the HDP expected values (impl/signalMachine.c:861-863), the expectation branch does not */
-        set_hdp_expected(&R.smt);
-        if (R.two_d) set_hdp_expected(&R.smc);
+        for (int s = 0; s < n_strands(&R); s++) set_hdp_expected(&R.sm[s]);
     }
     /* the reads go through in slices of --batch-reads (default 2048): bounded host and device memory for any manifest */
     /* Two slices are in the air: while the GPU stage and the rendering of slice k run here, a second thread does the host side
@@ -1867,10 +1830,12 @@ int main(int argc, char **argv) {
      * time -- text parsing and TSV rendering -- not by the order of its stages. */
     int64_t n_failed = 0;
     if (R.snp_step > 0) {   /* a slice holds at most --batch-reads jobs: N per read and strand */
-        batch_reads = batch_reads / R.snp_step > 0 ? batch_reads / R.snp_step : 1;
+        batch_reads /= R.snp_step;
+        if (batch_reads < 1) batch_reads = 1;
         if (mkdir(R.snp_dir, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.snp_dir);
     }
-    slice_prep_t cur = {&R, reads, n_reads < batch_reads ? n_reads : batch_reads, batch_mode}, nxt;
+    int64_t (*const run_slice)(run_t *, read_t *, int64_t, int) = R.expect_mode ? run_slice_expect : R.snp_step > 0 ? run_slice_snp : run_slice_align;
+    slice_t cur = {.R = &R, .reads = reads, .n_reads = n_reads < batch_reads ? n_reads : batch_reads}, nxt;
     slice_prepare(&cur);
     for (int64_t off = 0; off < n_reads; off += batch_reads) {
         const int64_t n = n_reads - off < batch_reads ? n_reads - off : batch_reads;
@@ -1878,24 +1843,16 @@ int main(int argc, char **argv) {
         int started = 0;
         if (off + n < n_reads) {
             const int64_t n2 = n_reads - off - n < batch_reads ? n_reads - off - n : batch_reads;
-            nxt = (slice_prep_t) {&R, reads + off + n, n2, batch_mode};
+            nxt = (slice_t) {.R = &R, .reads = reads + off + n, .n_reads = n2};
             started = pthread_create(&th, NULL, slice_prepare, &nxt) == 0;
             if (!started) slice_prepare(&nxt);
         }
-        int64_t failed_now = 0;
-        if (R.snp_step > 0) {
-            n_failed += run_slice_snp(&R, reads + off, n, batch_mode, device);
-            if (started) pthread_join(th, NULL);
-            continue;
-        }
-        render_job_t *job = run_slice(&R, reads + off, n, batch_mode, device, &failed_now);
-        n_failed += failed_now;
-        if (job) { n_failed += render_slice(job); free(job); }
+        n_failed += run_slice(&R, reads + off, n, device);
         if (started) pthread_join(th, NULL);
     }
     if (R.agg_path) write_aggregate(R.agg_path);
     write_training(&R, t_model, c_model, device);
-    if (batch_mode)
+    if (R.batch_mode)
         fprintf(stderr, "[signalMachine] batch: %" PRId64 " of %" PRId64 " reads aligned\n", n_reads - n_failed, n_reads);
     if (getenv("SA_CLI_TIMING"))
         fprintf(stderr, "[signalMachine] timing: host stage %.3f s wall (thread-seconds: npRead+cigar parse %.3f, reference fetch "

@@ -41,7 +41,8 @@ def _restate(tsv_paths, alphabet, k, n, min_prob):
     return ref.top_n(rows, n, min_prob)
 
 
-def test_batch_table_and_model(oracle, tmp_path):
+def _four_windows(oracle, tmp_path):
+    """Four 1200-base windows of r9p4_oneD.npRead on a contig made of the read itself: the manifest rows with and without TSVs"""
     npread = os.path.join(cases.GOLDEN, "npReads", "r9p4_oneD.npRead")
     read = oracle.parse_npread(npread)["template_read"]
     L = 1200
@@ -55,6 +56,11 @@ def test_batch_table_and_model(oracle, tmp_path):
         tsvs.append(str(tmp_path / ("r%d.tsv" % i)))
         lines.append("r%d\t%s\t%s\t%s\t-\tchrA\n" % (i, npread, cigar, tsvs[-1]))
         lines_dash.append("r%d\t%s\t%s\t-\t-\tchrA\n" % (i, npread, cigar))
+    return npread, read, fasta, lines, lines_dash, tsvs
+
+
+def test_batch_table_and_model(oracle, tmp_path):
+    _, _, fasta, lines, lines_dash, tsvs = _four_windows(oracle, tmp_path)
     man, man_dash = str(tmp_path / "m.tsv"), str(tmp_path / "m_dash.tsv")
     open(man, "w").writelines(lines)
     open(man_dash, "w").writelines(lines_dash)
@@ -99,6 +105,49 @@ def test_batch_table_and_model(oracle, tmp_path):
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert pr.returncode == 0, pr.stderr[-2000:]
     assert os.path.exists(out)
+
+
+def test_refused_read_rolls_the_tables_back(oracle, tmp_path):
+    """A read the planner refuses (an N in its reference window) shares the first slice with two good reads: the slice is
+    retried without it, and the rows its first attempt put into the run's k-mer table are taken back (checkpoint / rollback).
+    Everything the four good reads produce is byte for byte what the manifest without the refused read produces."""
+    npread, read, fasta, lines, _, tsvs = _four_windows(oracle, tmp_path)
+    L = 1200
+    base = [BIN, "-T", cases.MODEL_6MER, "-f", fasta, "-s", "2", "-g", "100", "--batch-reads", "3",
+            "--train-max-assignments", "3", "--train-min-prob", "0.5"]
+    man, man_bad = str(tmp_path / "m.tsv"), str(tmp_path / "m_bad.tsv")
+    open(man, "w").writelines(lines)
+    A, M, A2, M2 = (str(tmp_path / n) for n in ("a.tsv", "t.model", "a2.tsv", "t2.model"))
+    pr = subprocess.run(base + ["--batch", man, "--train-assignments", A, "--train-template-model", M],
+                        capture_output=True, text=True, timeout=600)
+    assert pr.returncode == 0, pr.stderr[-2000:]
+    want = [open(t, "rb").read() for t in tsvs]
+    assert all(want) and open(A, "rb").read()
+    for t in tsvs:
+        os.remove(t)
+    # the refused read, second in the manifest: the first slice is [r0, bad, r1], the second [r2, r3]
+    contig = read[:L + 400] + "ACGTACGTAC"
+    fasta_n = str(tmp_path / "refN.fa")
+    _write_fasta(fasta_n, "chrN", contig[:700] + "N" + contig[701:])
+    os.remove(fasta_n + ".fai")                  # two records in one file: let the loader scan it (no index)
+    with open(fasta, "a") as f:
+        f.write(open(fasta_n).read())
+    os.remove(fasta + ".fai")
+    cigar_n = str(tmp_path / "bad.cigar")
+    with open(cigar_n, "w") as f:
+        f.write("cigar: bad %d %d + chrN %d %d + 1 M %d\n" % (60, 60 + L, 60, 60 + L, L))
+    bad_tsv = str(tmp_path / "bad.tsv")
+    lines.insert(1, "bad\t%s\t%s\t%s\t-\tchrN\n" % (npread, cigar_n, bad_tsv))
+    open(man_bad, "w").writelines(lines)
+    pr = subprocess.run(base + ["--batch", man_bad, "--train-assignments", A2, "--train-template-model", M2],
+                        capture_output=True, text=True, timeout=600)
+    assert pr.returncode == 1, pr.stderr[-2000:]
+    assert "read bad skipped: alignment job rejected" in pr.stderr
+    assert "4 of 5 reads aligned" in pr.stderr
+    assert not os.path.exists(bad_tsv)
+    assert [open(t, "rb").read() for t in tsvs] == want
+    assert open(A2, "rb").read() == open(A, "rb").read()
+    assert open(M2, "rb").read() == open(M, "rb").read()
 
 
 def test_two_d_run_writes_both_strands(tmp_path):
