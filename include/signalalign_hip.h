@@ -692,6 +692,49 @@ int sa_kmer_table_stats(const sa_kmer_table_t *t, int strand, int use_median, sa
  * printed as Python's str(float). */
 int sa_model_write_trained(const char *prior_model_path, const sa_kmer_stat_t *stats, double weight, double min_sd, int mod_only,
                            const uint8_t *kmer_mask, const char *out_path);
+/* ---- Gaussian mixtures over a k-mer's rows (src/signalalign/mixture_model.py:42-186) ---------------------------------------
+ * fit_model_to_kmer_dist / get_nanopore_gauss_mixture: a K-component Gaussian mixture (scalar variances) fitted by EM to
+ * x_i = descaled_units_i / 1e6 over the rows of one (strand, k-mer), the rows in sa_kmer_table_rows order.  It is sklearn's
+ * GaussianMixture.fit with n_init = 1 (max_iter 100, tol 1e-3, reg_covar 1e-6 are its defaults) from a deterministic start
+ * instead of a random k-means draw:
+ *   start    labels min(K - 1, floor(K (x_i - lo) / (hi - lo))) (lo / hi the k-mer's smallest / largest x; all 0 when equal),
+ *            one M-step on the one-hot responsibilities; or, with `init`, the caller's weights, means and sds as they are
+ *   M-step   nk_c = sum_i r_ic + 10 DBL_EPSILON, mean_c = sum r_ic x_i / nk_c, var_c = sum r_ic (x_i - mean_c)^2 / nk_c + reg_covar,
+ *            weight_c = nk_c / sum_c nk_c
+ *   E-step   lp_ic = -(log 2 pi + ((x_i - mean_c) / sd_c)^2) / 2 - log sd_c + log weight_c, norm_i = logsumexp_c lp_ic,
+ *            r_ic = exp(lp_ic - norm_i), lower_bound = sum_i norm_i / n
+ *   loop     lb = -inf; for it = 1 .. max_iter: prev = lb, E-step, M-step, stop (converged) when |lb - prev| < tol
+ * The whole loop runs on the device, one work-group per job, in fp64.  A fit depends on the table's contents only, not on
+ * how the table was filled: equal tables give equal bits.  A job is a k-mer id; the same list may be fitted for several K in
+ * successive calls (AIC / BIC from lower_bound and n: 3K - 1 free parameters).
+ * n_components outside 1..4, max_iter < 1, tol < 0 or not finite, reg_covar < 0 or not finite, a k-mer id outside the model,
+ * an initial weight or sd that is not finite and positive, an initial mean that is not finite: SA_EINVAL. */
+typedef struct sa_mixture_params { int32_t n_components, max_iter; double tol, reg_covar; } sa_mixture_params_t;
+typedef struct sa_mixture_fit {
+    int64_t n;                /* rows of the k-mer                                                           */
+    int32_t kmer_id, n_iter, converged, status;   /* status 0 fitted, 1 fewer rows than components (the fields below are zero) */
+    double lower_bound;       /* mean log-likelihood per row at the last E-step                              */
+    double weight[4], mean[4], sd[4];             /* components in initialisation order                       */
+} sa_mixture_fit_t;
+/* kmer_ids NULL: every k-mer of the model (out: n_kmers entries).  init NULL, or n_jobs x 3K doubles (per job K weights, K means, K sds). */
+int sa_kmer_table_mixture(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs,
+                          const sa_mixture_params_t *p, const double *init, sa_mixture_fit_t *out, double *kernel_ms_out);
+/* the start the call above makes for itself when init is NULL, in init's layout (a job with fewer rows than components: zeros);
+ * handed back as init it gives the same fit, bit for bit */
+int sa_kmer_table_mixture_start(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs,
+                                const sa_mixture_params_t *p, double *init_out);
+/* closest_to_canonical (mixture_model.py:92-104) of a fitted two-component mixture: *match_out the component whose mean is
+ * nearest canonical_mean (strict < against an initial 1000, the first minimal index: component 0 and distance 1000 when
+ * neither is nearer than that), *other_out the other one.  A fit with status != 0: SA_EINVAL.  Host only. */
+int sa_mixture_assign(const sa_mixture_fit_t *fit, double canonical_mean, int32_t *match_out, int32_t *other_out, double *distance_out);
+/* get_motif_kmer_pairs (mixture_model.py:189-200) over get_motif_kmers (utils/sequenceTools.py:332-374): the (canonical,
+ * modified) k-mer pairs of every window of k letters over the motif's modified position, flanks from `alphabet` (NULL: "ATGC",
+ * the reference's default).  The canonical k-mer has the first occurrence of the new letter replaced.  *pairs_out (sa_free):
+ * *n_out pairs, sorted and without duplicates, each 2 (k + 1) bytes: the canonical k-mer, NUL, the modified k-mer, NUL.
+ * Motifs of unequal length or not differing in exactly one letter, a canonical motif with a letter outside ACGT, k outside
+ * 1..16: SA_EINVAL.  Host only. */
+int sa_motif_kmer_pairs(int k, const char *canonical_motif, const char *modified_motif, const char *alphabet, char **pairs_out,
+                        int64_t *n_out);
 /* Python's repr of a double (shortest round-trip digits); `out` needs 32 bytes; returns the length (test hook and writer) */
 int sa_format_py_repr(char *out, double v);
 /* the device's "%f" rounding of v[0 .. n) into units of 1e-6 and the negative-zero flag (test hook: must equal the host's,

@@ -139,8 +139,13 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
            "sa_hmm_load_into_model", "sa_model_transitions10",
            "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
-           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
+           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
            "sa_version", "sa_free"]
+
+
+class MixtureParams(C.Structure):
+    """sa_mixture_params_t (include/signalalign_hip.h)"""
+    _fields_ = [("n_components", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("reg_covar", C.c_double)]
 
 
 class HmmView(C.Structure):
@@ -295,6 +300,10 @@ def lib():
     L.sa_kmer_table_checkpoint.argtypes = [C.c_void_p]
     L.sa_kmer_table_rollback.argtypes = [C.c_void_p]
     L.sa_kmer_table_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, dp]
+    L.sa_kmer_table_mixture.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp, C.c_void_p, dp]
+    L.sa_kmer_table_mixture_start.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp]
+    L.sa_mixture_assign.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
+    L.sa_motif_kmer_pairs.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), ip]
     L.sa_model_write_trained.argtypes = [C.c_char_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_char_p]
     L.sa_format_py_repr.argtypes = [C.c_char_p, C.c_double]
     L.sa_f6_units_device.argtypes = [dp, C.c_int64, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
@@ -1416,6 +1425,8 @@ def hdp_finalize_distributions(grid, collectors, samples, device=0):
 KMER_ROW_DTYPE = np.dtype([("descaled_units", "<i8"), ("run", "<i8"), ("kmer_id", "<i4"), ("prob_units", "<i4"),
                            ("neg_zero", "<i4"), ("pad", "<i4")])
 KMER_STAT_DTYPE = np.dtype([("n", "<i8"), ("m", "<f8"), ("s", "<f8")])
+MIXTURE_FIT_DTYPE = np.dtype([("n", "<i8"), ("kmer_id", "<i4"), ("n_iter", "<i4"), ("converged", "<i4"), ("status", "<i4"),
+                              ("lower_bound", "<f8"), ("weight", "<f8", (4,)), ("mean", "<f8", (4,)), ("sd", "<f8", (4,))])
 
 
 class KmerTable:
@@ -1476,6 +1487,36 @@ class KmerTable:
             info["kernel_ms"] = kms.value
         return out
 
+    def _mixture_args(self, kmer_ids, n_components, max_iter, tol, reg_covar):
+        alpha, k = self._model.alphabet()
+        ids = None if kmer_ids is None else np.ascontiguousarray(kmer_ids, dtype=np.int32)
+        nj = len(alpha) ** k if ids is None else len(ids)
+        p = MixtureParams(int(n_components), int(max_iter), float(tol), float(reg_covar))
+        return ids, nj, p, (None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)))
+
+    def mixture(self, kmer_ids=None, n_components=2, strand=0, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, info=None):
+        """sa_kmer_table_mixture: structured array (MIXTURE_FIT_DTYPE), one entry per k-mer id of `kmer_ids` (None: every
+        k-mer of the model); init: None or an array n_jobs x 3 x K (weights, means, sds)"""
+        ids, nj, p, idp = self._mixture_args(kmer_ids, n_components, max_iter, tol, reg_covar)
+        out = np.zeros(nj, dtype=MIXTURE_FIT_DTYPE)
+        ini = None
+        if init is not None:
+            ini = np.ascontiguousarray(init, dtype=np.float64).reshape(-1)
+            assert len(ini) == nj * 3 * int(n_components)
+        kms = C.c_double()
+        _chk(lib().sa_kmer_table_mixture(self._h, int(strand), idp, nj, C.byref(p), None if ini is None else _dp(ini),
+                                         out.ctypes.data, C.byref(kms)), "sa_kmer_table_mixture")
+        if info is not None:
+            info["kernel_ms"] = kms.value
+        return out
+
+    def mixture_start(self, kmer_ids=None, n_components=2, strand=0, reg_covar=1e-6):
+        """sa_kmer_table_mixture_start: the default start of every job, n_jobs x 3 x K (weights, means, sds)"""
+        ids, nj, p, idp = self._mixture_args(kmer_ids, n_components, 1, 0.0, reg_covar)
+        out = np.zeros((nj, 3, int(n_components)), dtype=np.float64)
+        _chk(lib().sa_kmer_table_mixture_start(self._h, int(strand), idp, nj, C.byref(p), _dp(out)), "sa_kmer_table_mixture_start")
+        return out
+
     def close(self):
         if self._h:
             lib().sa_kmer_table_destroy(self._h)
@@ -1493,6 +1534,26 @@ def model_write_trained(prior_path, stats, out_path, weight=100.0, min_sd=0.0, m
     mask = None if kmer_mask is None else np.ascontiguousarray(kmer_mask, dtype=np.uint8)
     _chk(lib().sa_model_write_trained(os.fsencode(prior_path), st.ctypes.data, float(weight), float(min_sd), int(bool(mod_only)),
                                       None if mask is None else mask.ctypes.data, os.fsencode(out_path)), "sa_model_write_trained")
+
+
+def mixture_assign(fit, canonical_mean):
+    """sa_mixture_assign: (match, other, distance) of one fitted two-component entry of KmerTable.mixture"""
+    f = np.ascontiguousarray(fit, dtype=MIXTURE_FIT_DTYPE).reshape(1)
+    a, b, d = C.c_int32(), C.c_int32(), C.c_double()
+    _chk(lib().sa_mixture_assign(f.ctypes.data, float(canonical_mean), C.byref(a), C.byref(b), C.byref(d)), "sa_mixture_assign")
+    return int(a.value), int(b.value), float(d.value)
+
+
+def motif_kmer_pairs(k, canonical_motif, modified_motif, alphabet=None):
+    """sa_motif_kmer_pairs: sorted list of (canonical k-mer, modified k-mer)"""
+    ptr = C.c_void_p()
+    n = np.zeros(1, dtype=np.int64)
+    _chk(lib().sa_motif_kmer_pairs(int(k), canonical_motif.encode(), modified_motif.encode(),
+                                   None if alphabet is None else alphabet.encode(), C.byref(ptr), _ip(n)), "sa_motif_kmer_pairs")
+    raw = C.string_at(ptr, int(n[0]) * 2 * (int(k) + 1)) if n[0] else b""
+    lib().sa_free(ptr)
+    w = int(k) + 1
+    return [(raw[2 * i * w:2 * i * w + k].decode(), raw[(2 * i + 1) * w:(2 * i + 1) * w + k].decode()) for i in range(int(n[0]))]
 
 
 def snp_substitute(ref, contig_pos_of_ref0, reversed=False, step=10, phase=0, letter="X"):

@@ -24,6 +24,8 @@
 //                                        for records the descaled mean is computed and rounded as "%f" prints it
 //   k_kt_stats                           one block per k-mer: exact integer sums (S, and Q in two words), radix selection (8 bits
 //                                        per pass) of the median and of the median absolute deviation
+//   k_kt_mixture<K> / k_kt_mix_gather    one block per (k-mer, K): a K-component Gaussian mixture by EM over the k-mer's rows
+//                                        (mixture_model.py:42-186; see the section further down)
 // Within a k-mer's segment rows lie in arrival order; the keys are unique, so sa_kmer_table_rows sorts them on the host and
 // every statistic is independent of the order.  Scratch comes from the library's caching allocator.
 #include <hip/hip_runtime.h>
@@ -39,6 +41,8 @@
 #include <mutex>
 #include <string>
 #include <vector>
+
+#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "sa_internal.h"
 #include "sa_chain.h"
@@ -845,6 +849,474 @@ extern "C" int sa_kmer_table_stats(const sa_kmer_table_t *t, int strand, int use
 done:
     g_sa_pool.put(SaPool::DEVICE, d);
     return rc;
+}
+
+// ---- Gaussian mixtures over a k-mer's descaled event means (mixture_model.py:42-186) ---------------------------------------------
+// fit_model_to_kmer_dist / get_nanopore_gauss_mixture fit sklearn's GaussianMixture to the rows of one k-mer; here the same EM
+// (sklearn's fit with n_init = 1: E-step, M-step, |change of the mean log-likelihood| < tol) runs on the device from a
+// deterministic start, one work-group per job, the loop and its convergence test included.  x_i = units_i / 1e6.
+//   order      a fit must be a function of the table's contents only, but a segment lies in arrival order (atomics).  Every
+//              fitted segment is therefore put into key order first (keys are unique): a bitonic sort in LDS for a segment of
+//              at most KT_MIX_LDS_ROWS rows, rocPRIM's segmented radix sort into a copy in HBM for the others
+//   sums       thread t adds rows t, t + 256, ... in that order; a wave's 64 partial sums are added by a shuffle tree and the
+//              four waves' sums as (w0 + w1) + (w2 + w3): the same rows give the same bits
+//   centring   rows are held as (units - c) / 1e6 with c the midpoint of the k-mer's smallest and largest units (an integer).
+//              An iteration is one pass: the E-step's t = x - mean_c is also what the M-step sums (R = sum r, S1 = sum r t,
+//              S2 = sum r t^2), so the new mean is the old one plus d = (S1 - 10 eps mean) / nk and the new variance
+//              (S2 - 2 d S1 + d^2 R) / nk: sum r x / nk and sum r (x - mean)^2 / nk written out.  Shifting by the component's own
+//              mean, not by a constant of the k-mer, keeps the rounding of the variance relative to the variance: a
+//              component that has shrunk onto one row has var = reg_covar = 1e-6, and a constant shift leaves an error of
+//              eps (x - c)^2 ~ 1e-14 there, 1e-8 of it
+//   LDS        KT_MIX_LDS_ROWS = 2048 rows: 16 KiB of keys and 16 KiB of values per work-group, four work-groups of 256
+//              threads per CU (160 KiB); a larger segment is read from its sorted copy in HBM once per iteration
+//   start      hard labels min(K - 1, floor(K (x - lo) / (hi - lo))) and one M-step on them, or the caller's weights, means
+//              and sds; either way the loop starts from (weight, mean, sd) in the caller's units, so that the default start
+//              handed back in as an explicit one gives the same bits
+#define KT_MIX_THREADS 256
+#define KT_MIX_LDS_ROWS 2048
+#define KT_MIX_MAXK 4
+#define KT_MIX_EPS10 (10.0 * 2.220446049250313e-16)
+
+struct KtMixJob {
+    long long a, n;             // the k-mer's segment of the table
+    long long so;               // n > KT_MIX_LDS_ROWS: where its sorted units lie in the copy
+    int kmer, pad;
+};
+
+// sums of v[0 .. NV) over the block, in every thread (fixed tree; s_red: 4 x NV doubles)
+template <int NV>
+__device__ static inline void kt_mix_sum(double (&v)[NV], double *s_red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NV; q++) {
+        double x = v[q];
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
+        v[q] = x;
+    }
+    __syncthreads();   // (the readers of the previous sums are done)
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; q++) s_red[wave * NV + q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV; q++) v[q] = (s_red[q] + s_red[NV + q]) + (s_red[2 * NV + q] + s_red[3 * NV + q]);
+}
+
+// M-step from R_c = sum r, S1_c = sum r t, S2_c = sum r t^2 with t = x - m_c (the component's mean before the step, centred;
+// cd: the centre).  sum r x / nk moves the mean by d = (S1 - 10 eps (m + cd)) / nk, and sum r (x - mean)^2 = S2 - 2 d S1 + d^2 R.
+template <int K>
+__device__ static inline void kt_mix_mstep(const double *v, double reg, double cd, double *w, double *m, double *sd) {
+    double nk[K], tot = 0;
+#pragma unroll
+    for (int c = 0; c < K; c++) {
+        const double R = v[3 * c], S1 = v[3 * c + 1], S2 = v[3 * c + 2];
+        nk[c] = R + KT_MIX_EPS10;
+        const double d = (S1 - KT_MIX_EPS10 * (m[c] + cd)) / nk[c];
+        double var = (S2 - 2.0 * d * S1 + d * d * R) / nk[c];
+        if (var < 0) var = 0;   // (rounding, when every row of the component has one value)
+        m[c] += d;
+        sd[c] = sqrt(var + reg);
+        tot += nk[c];
+    }
+#pragma unroll
+    for (int c = 0; c < K; c++) w[c] = nk[c] / tot;
+}
+
+__global__ __launch_bounds__(KT_MIX_THREADS) void k_kt_mix_gather(const KtRow *__restrict__ rows, const KtMixJob *__restrict__ jobs,
+                                                                  const int *__restrict__ large, unsigned long long *__restrict__ keys,
+                                                                  long long *__restrict__ units) {
+    const KtMixJob J = jobs[large[blockIdx.x]];
+    for (long long i = threadIdx.x; i < J.n; i += KT_MIX_THREADS) {
+        const KtRow r = rows[J.a + i];
+        keys[J.so + i] = r.key;
+        units[J.so + i] = r.desc;
+    }
+}
+
+// job blockIdx.x.  init: n_jobs x 3K doubles (weights, means, sds) or null.  start_out (n_jobs x 3K, or null): the start is
+// written there and nothing is fitted.
+template <int K>
+__global__ __launch_bounds__(KT_MIX_THREADS) void k_kt_mixture(const KtRow *__restrict__ rows, const long long *__restrict__ sorted,
+                                                               const KtMixJob *__restrict__ jobs, sa_mixture_params_t P,
+                                                               const double *__restrict__ init, double *__restrict__ start_out,
+                                                               sa_mixture_fit_t *__restrict__ out) {
+    constexpr int NV = 3 * K + 1;
+    __shared__ unsigned long long s_key[KT_MIX_LDS_ROWS];
+    __shared__ long long s_val[KT_MIX_LDS_ROWS];   // units, then the bits of the centred doubles
+    __shared__ double s_red[4 * NV];
+    __shared__ long long s_mm[8];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const KtMixJob J = jobs[blockIdx.x];
+    const long long n = J.n;
+    sa_mixture_fit_t F;
+    memset(&F, 0, sizeof F);
+    F.n = n;
+    F.kmer_id = J.kmer;
+    if (n < K) {
+        F.status = 1;
+        if (t == 0) out[blockIdx.x] = F;
+        return;
+    }
+    const bool lds = n <= KT_MIX_LDS_ROWS;
+    const long long *src = sorted + (lds ? 0 : J.so);
+    if (lds) {   // key order: bitonic sort, descending, of (key + 1, units); the padding (key 0) ends up behind the rows
+        int p2 = 1;
+        while (p2 < n) p2 <<= 1;
+        for (int i = t; i < p2; i += KT_MIX_THREADS) {
+            if (i < n) {
+                const KtRow r = rows[J.a + i];
+                s_key[i] = r.key + 1ull;
+                s_val[i] = r.desc;
+            } else {
+                s_key[i] = 0;
+                s_val[i] = 0;
+            }
+        }
+        __syncthreads();
+        for (int k2 = 2; k2 <= p2; k2 <<= 1)
+            for (int j = k2 >> 1; j > 0; j >>= 1) {
+                for (int i = t; i < p2; i += KT_MIX_THREADS) {
+                    const int p = i ^ j;
+                    if (p <= i) continue;
+                    const unsigned long long ki = s_key[i], kp = s_key[p];
+                    if ((i & k2) == 0 ? ki < kp : ki > kp) {
+                        s_key[i] = kp; s_key[p] = ki;
+                        const long long u = s_val[i];
+                        s_val[i] = s_val[p]; s_val[p] = u;
+                    }
+                }
+                __syncthreads();
+            }
+    }
+    // smallest and largest units (integers: any order gives the same)
+    long long lo = 0x7fffffffffffffffll, hi = -0x7fffffffffffffffll - 1;
+    for (long long i = t; i < n; i += KT_MIX_THREADS) {
+        const long long u = lds ? s_val[i] : src[i];
+        lo = u < lo ? u : lo;
+        hi = u > hi ? u : hi;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long a = __shfl_down(lo, o), b = __shfl_down(hi, o);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    if (lane == 0) { s_mm[2 * wave] = lo; s_mm[2 * wave + 1] = hi; }
+    __syncthreads();
+    lo = s_mm[0]; hi = s_mm[1];
+    for (int q = 1; q < 4; q++) {
+        lo = s_mm[2 * q] < lo ? s_mm[2 * q] : lo;
+        hi = s_mm[2 * q + 1] > hi ? s_mm[2 * q + 1] : hi;
+    }
+    const long long cu = lo + (hi - lo) / 2;
+    const double cd = (double) cu / 1e6;
+    double w[K], m[K], sd[K], v[NV];
+    if (init) {
+#pragma unroll
+        for (int c = 0; c < K; c++) {
+            w[c] = init[(size_t) blockIdx.x * 3 * K + c];
+            m[c] = init[(size_t) blockIdx.x * 3 * K + K + c];
+            sd[c] = init[(size_t) blockIdx.x * 3 * K + 2 * K + c];
+        }
+    } else {
+        // the labels' M-step as it is written, in two passes: means first, then the squares about them
+        const double xlo = (double) lo / 1e6, xhi = (double) hi / 1e6;
+        auto label_of = [&](long long u) {
+            if (hi == lo) return 0;
+            const double f = floor((double) K * ((double) u / 1e6 - xlo) / (xhi - xlo));
+            return f < (double) (K - 1) ? (int) f : K - 1;
+        };
+#pragma unroll
+        for (int q = 0; q < NV; q++) v[q] = 0;
+        for (long long i = t; i < n; i += KT_MIX_THREADS) {
+            const long long u = lds ? s_val[i] : src[i];
+            const int label = label_of(u);
+            const double xc = (double) (u - cu) / 1e6;
+#pragma unroll
+            for (int c = 0; c < K; c++) {
+                const double r = label == c ? 1.0 : 0.0;
+                v[3 * c] += r;
+                v[3 * c + 1] += r * xc;
+            }
+        }
+        kt_mix_sum<NV>(v, s_red);
+        double nk[K], tot = 0;
+#pragma unroll
+        for (int c = 0; c < K; c++) {
+            nk[c] = v[3 * c] + KT_MIX_EPS10;
+            m[c] = (v[3 * c + 1] - KT_MIX_EPS10 * cd) / nk[c];
+            tot += nk[c];
+        }
+#pragma unroll
+        for (int q = 0; q < NV; q++) v[q] = 0;
+        for (long long i = t; i < n; i += KT_MIX_THREADS) {
+            const long long u = lds ? s_val[i] : src[i];
+            const int label = label_of(u);
+            const double xc = (double) (u - cu) / 1e6;
+#pragma unroll
+            for (int c = 0; c < K; c++) v[c] += label == c ? (xc - m[c]) * (xc - m[c]) : 0.0;
+        }
+        kt_mix_sum<NV>(v, s_red);
+#pragma unroll
+        for (int c = 0; c < K; c++) {
+            w[c] = nk[c] / tot;
+            sd[c] = sqrt(v[c] / nk[c] + P.reg_covar);
+            m[c] += cd;
+        }
+    }
+    if (start_out) {
+        if (t == 0)
+            for (int c = 0; c < K; c++) {
+                start_out[(size_t) blockIdx.x * 3 * K + c] = w[c];
+                start_out[(size_t) blockIdx.x * 3 * K + K + c] = m[c];
+                start_out[(size_t) blockIdx.x * 3 * K + 2 * K + c] = sd[c];
+            }
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < K; c++) m[c] -= cd;
+    if (lds) {   // the rows as centred doubles, once
+        __syncthreads();
+        for (int i = t; i < n; i += KT_MIX_THREADS) s_val[i] = __double_as_longlong((double) (s_val[i] - cu) / 1e6);
+        __syncthreads();
+    }
+    double lb = -INFINITY;
+    int it = 0, converged = 0;
+    while (it < P.max_iter) {
+        it++;
+        const double prev = lb;
+        double off[K];
+#pragma unroll
+        for (int c = 0; c < K; c++) off[c] = log(w[c]) - log(sd[c]);
+#pragma unroll
+        for (int q = 0; q < NV; q++) v[q] = 0;
+        for (long long i = t; i < n; i += KT_MIX_THREADS) {
+            const double x = lds ? __longlong_as_double(s_val[i]) : (double) (src[i] - cu) / 1e6;
+            double lp[K], tc[K], mx = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < K; c++) {
+                tc[c] = x - m[c];
+                const double z = tc[c] / sd[c];
+                lp[c] = -0.5 * (1.8378770664093453 + z * z) + off[c];
+                mx = lp[c] > mx ? lp[c] : mx;
+            }
+            double s = 0;
+#pragma unroll
+            for (int c = 0; c < K; c++) s += exp(lp[c] - mx);
+            const double norm = mx + log(s);
+#pragma unroll
+            for (int c = 0; c < K; c++) {
+                const double r = exp(lp[c] - norm);
+                v[3 * c] += r;
+                v[3 * c + 1] += r * tc[c];
+                v[3 * c + 2] += r * tc[c] * tc[c];
+            }
+            v[3 * K] += norm;
+        }
+        kt_mix_sum<NV>(v, s_red);
+        lb = v[3 * K] / (double) n;
+        kt_mix_mstep<K>(v, P.reg_covar, cd, w, m, sd);
+        if (fabs(lb - prev) < P.tol) { converged = 1; break; }
+    }
+    F.n_iter = it;
+    F.converged = converged;
+    F.lower_bound = lb;
+#pragma unroll
+    for (int c = 0; c < K; c++) { F.weight[c] = w[c]; F.mean[c] = m[c] + cd; F.sd[c] = sd[c]; }
+    if (t == 0) out[blockIdx.x] = F;
+}
+
+template <int K>
+static void kt_mix_launch(long long nj, const KtRow *rows, const long long *sorted, const KtMixJob *jobs, const sa_mixture_params_t &P,
+                          const double *init, double *start_out, sa_mixture_fit_t *out) {
+    hipLaunchKernelGGL(k_kt_mixture<K>, dim3((unsigned) nj), dim3(KT_MIX_THREADS), 0, 0, rows, sorted, jobs, P, init, start_out, out);
+}
+
+// the fits (out) or, with start_out, only the start of every job (n_jobs x 3K doubles; a job with fewer rows than components: zeros)
+static int kt_mixture(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs, const sa_mixture_params_t *p,
+                      const double *init, sa_mixture_fit_t *out, double *start_out, double *kernel_ms_out) {
+    if (!t || !p || (!out && !start_out) || (strand != 0 && strand != 1) || n_jobs < 0) return SA_EINVAL;
+    if (p->n_components < 1 || p->n_components > KT_MIX_MAXK || p->max_iter < 1 || !(p->tol >= 0) || !isfinite(p->tol) ||
+        !(p->reg_covar >= 0) || !isfinite(p->reg_covar))
+        return SA_EINVAL;
+    const int K = p->n_components;
+    const long long nj = kmer_ids ? (long long) n_jobs : t->n_kmers;
+    if (nj > 0x7fffffffll) return SA_EUNSUPPORTED;
+    for (long long j = 0; kmer_ids && j < nj; j++)
+        if (kmer_ids[j] < 0 || kmer_ids[j] >= t->n_kmers) return SA_EINVAL;
+    for (long long q = 0; init && q < nj * 3 * K; q++) {
+        const bool is_mean = (q % (3 * K)) / K == 1;
+        if (!isfinite(init[q]) || (!is_mean && !(init[q] > 0))) return SA_EINVAL;
+    }
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (nj == 0) return SA_OK;
+    sa_kmer_table *T = const_cast<sa_kmer_table *>(t);
+    std::lock_guard<std::mutex> g(T->mu);
+    const KtSide &S = t->side[strand];
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    std::vector<long long> off((size_t) t->n_kmers + 1);
+    if (hipMemcpy(off.data(), S.d_off, 8 * off.size(), hipMemcpyDeviceToHost) != hipSuccess) return SA_ENODEVICE;
+    // jobs; those above the LDS cap get a place in the sorted copy
+    std::vector<KtMixJob> jobs((size_t) nj);
+    std::vector<int> large;
+    std::vector<unsigned> seg_begin, seg_end;
+    long long n_large = 0;
+    for (long long j = 0; j < nj; j++) {
+        const long long km = kmer_ids ? kmer_ids[j] : j;
+        KtMixJob &J = jobs[(size_t) j];
+        J.a = off[(size_t) km]; J.n = off[(size_t) km + 1] - J.a; J.so = 0; J.kmer = (int) km; J.pad = 0;
+        if (J.n > KT_MIX_LDS_ROWS && J.n >= K) {
+            J.so = n_large;
+            large.push_back((int) j);
+            seg_begin.push_back((unsigned) n_large);
+            n_large += J.n;
+            if (n_large > 0xffffffffll) return SA_EUNSUPPORTED;   // (the segmented sort counts rows in 32 bits)
+            seg_end.push_back((unsigned) n_large);
+        }
+    }
+    const size_t nl = large.size(), n_init = init ? (size_t) nj * 3 * K : 0, n_start = start_out ? (size_t) nj * 3 * K : 0;
+    SaLayout L;
+    const size_t o_jobs = L.add(sizeof(KtMixJob) * (size_t) nj), o_large = L.add(4 * nl), o_beg = L.add(4 * nl), o_end = L.add(4 * nl),
+                 o_init = L.add(8 * n_init), o_up = L.end, o_out = L.add(sizeof(sa_mixture_fit_t) * (size_t) nj), o_start = L.add(8 * n_start),
+                 o_k0 = L.add(8 * (size_t) n_large), o_k1 = L.add(8 * (size_t) n_large), o_u0 = L.add(8 * (size_t) n_large),
+                 o_u1 = L.add(8 * (size_t) n_large), bytes = L.end;
+    int rc = SA_OK;
+    char *h = nullptr, *d = nullptr;
+    void *d_tmp = nullptr;
+    size_t tmp_bytes = 0;
+    float kms = 0;
+    if (g_sa_pool.get(SaPool::PINNED, (void **) &h, o_up, t->device) != hipSuccess) return SA_ENOMEM;
+    {
+        memcpy(h + o_jobs, jobs.data(), sizeof(KtMixJob) * (size_t) nj);
+        if (nl) {
+            memcpy(h + o_large, large.data(), 4 * nl);
+            memcpy(h + o_beg, seg_begin.data(), 4 * nl);
+            memcpy(h + o_end, seg_end.data(), 4 * nl);
+        }
+        if (n_init) memcpy(h + o_init, init, 8 * n_init);
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, t->device));
+        SA_HIP_GOTO_DONE(hipMemcpy(d, h, o_up, hipMemcpyHostToDevice));
+        const KtMixJob *dj = (const KtMixJob *) (d + o_jobs);
+        unsigned long long *k0 = (unsigned long long *) (d + o_k0), *k1 = (unsigned long long *) (d + o_k1);
+        long long *u0 = (long long *) (d + o_u0), *u1 = (long long *) (d + o_u1);
+        const unsigned *beg = (const unsigned *) (d + o_beg), *end = (const unsigned *) (d + o_end);
+        if (nl) {
+            SA_HIP_GOTO_DONE(rocprim::segmented_radix_sort_pairs_desc(nullptr, tmp_bytes, k0, k1, u0, u1, (unsigned) n_large, (unsigned) nl, beg,
+                                                                      end, 0, 64 - 4, (hipStream_t) 0));
+            SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, &d_tmp, tmp_bytes, t->device));
+        }
+        SA_HIP_GOTO_DONE(hipEventRecord(T->e0, 0));
+        if (nl) {
+            hipLaunchKernelGGL(k_kt_mix_gather, dim3((unsigned) nl), dim3(KT_MIX_THREADS), 0, 0, S.d_rows, dj, (const int *) (d + o_large), k0, u0);
+            SA_HIP_GOTO_DONE(rocprim::segmented_radix_sort_pairs_desc(d_tmp, tmp_bytes, k0, k1, u0, u1, (unsigned) n_large, (unsigned) nl, beg,
+                                                                      end, 0, 64 - 4, (hipStream_t) 0));
+        }
+        const double *d_init = n_init ? (const double *) (d + o_init) : nullptr;
+        double *d_start = n_start ? (double *) (d + o_start) : nullptr;
+        sa_mixture_fit_t *d_out = (sa_mixture_fit_t *) (d + o_out);
+        if (n_start) SA_HIP_GOTO_DONE(hipMemsetAsync(d_start, 0, 8 * n_start, 0));
+        switch (K) {
+            case 1: kt_mix_launch<1>(nj, S.d_rows, u1, dj, *p, d_init, d_start, d_out); break;
+            case 2: kt_mix_launch<2>(nj, S.d_rows, u1, dj, *p, d_init, d_start, d_out); break;
+            case 3: kt_mix_launch<3>(nj, S.d_rows, u1, dj, *p, d_init, d_start, d_out); break;
+            default: kt_mix_launch<4>(nj, S.d_rows, u1, dj, *p, d_init, d_start, d_out); break;
+        }
+        SA_HIP_GOTO_DONE(hipEventRecord(T->e1, 0));
+        SA_HIP_GOTO_DONE(hipGetLastError());
+        if (start_out) SA_HIP_GOTO_DONE(hipMemcpy(start_out, d_start, 8 * n_start, hipMemcpyDeviceToHost));
+        else SA_HIP_GOTO_DONE(hipMemcpy(out, d_out, sizeof(sa_mixture_fit_t) * (size_t) nj, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, T->e0, T->e1));
+        if (kernel_ms_out) *kernel_ms_out = (double) kms;
+    }
+done:
+    if (rc != SA_OK) (void) hipDeviceSynchronize();
+    g_sa_pool.put(SaPool::DEVICE, d_tmp);
+    g_sa_pool.put(SaPool::DEVICE, d);
+    g_sa_pool.put(SaPool::PINNED, h);
+    return rc;
+}
+
+extern "C" int sa_kmer_table_mixture(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs,
+                                     const sa_mixture_params_t *p, const double *init, sa_mixture_fit_t *out, double *kernel_ms_out) {
+    if (!out) return SA_EINVAL;
+    return kt_mixture(t, strand, kmer_ids, n_jobs, p, init, out, nullptr, kernel_ms_out);
+}
+
+extern "C" int sa_kmer_table_mixture_start(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs,
+                                           const sa_mixture_params_t *p, double *init_out) {
+    if (!init_out) return SA_EINVAL;
+    return kt_mixture(t, strand, kmer_ids, n_jobs, p, nullptr, nullptr, init_out, nullptr);
+}
+
+// closest_to_canonical (mixture_model.py:92-104) for two components: strict < against 1000, the first minimal index
+extern "C" int sa_mixture_assign(const sa_mixture_fit_t *fit, double canonical_mean, int32_t *match_out, int32_t *other_out,
+                                 double *distance_out) {
+    if (!fit || fit->status != 0) return SA_EINVAL;
+    int min_index = 0;
+    double min_distance = 1000;
+    for (int i = 0; i < 2; i++) {
+        const double distance = fabs(fit->mean[i] - canonical_mean);
+        if (distance < min_distance) { min_index = i; min_distance = distance; }
+    }
+    if (match_out) *match_out = min_index;
+    if (other_out) *other_out = 1 - min_index;
+    if (distance_out) *distance_out = min_distance;
+    return SA_OK;
+}
+
+// get_motif_kmer_pairs (mixture_model.py:189-200) over get_motif_kmers (utils/sequenceTools.py:332-374): every window of k
+// letters that covers the modified position of the motif, the positions outside the motif filled with every letter of
+// `alphabet`; the canonical k-mer has the FIRST occurrence of the new letter replaced (so a flank that holds the new letter
+// gives a pair whose canonical half still carries one: the reference's behaviour, kept)
+extern "C" int sa_motif_kmer_pairs(int k, const char *canonical_motif, const char *modified_motif, const char *alphabet, char **pairs_out,
+                                   int64_t *n_out) {
+    if (!canonical_motif || !modified_motif || !pairs_out || !n_out || k < 1 || k > 16) return SA_EINVAL;
+    *pairs_out = nullptr;
+    *n_out = 0;
+    std::string can(canonical_motif), mod(modified_motif), alpha(alphabet ? alphabet : "ATGC");
+    for (char &c : can) c = (char) toupper((unsigned char) c);
+    for (char &c : mod) c = (char) toupper((unsigned char) c);
+    if (can.size() != mod.size() || can.empty() || alpha.empty()) return SA_EINVAL;
+    const int len = (int) can.size();
+    int pos = -1, n_diff = 0;
+    for (int i = 0; i < len; i++) {
+        if (!strchr("ATGC", can[(size_t) i])) return SA_EINVAL;
+        if (can[(size_t) i] != mod[(size_t) i]) { pos = i; n_diff++; }
+    }
+    if (n_diff != 1) return SA_EINVAL;
+    const char old_c = can[(size_t) pos], new_c = mod[(size_t) pos];
+    std::vector<std::pair<std::string, std::string>> pairs;
+    for (int i = 0; i < k; i++) {
+        const int s = pos + i - k + 1, nf = s < 0 ? -s : 0, nb = s + k > len ? s + k - len : 0;
+        const std::string core = mod.substr((size_t) (s < 0 ? 0 : s), (size_t) (k - nf - nb));
+        double combos = 1;
+        for (int q = 0; q < nf + nb; q++) combos *= (double) alpha.size();
+        if (combos * k > 1e7) return SA_EUNSUPPORTED;
+        std::vector<int> digit((size_t) (nf + nb), 0);
+        for (;;) {
+            std::string km;
+            for (int q = 0; q < nf; q++) km.push_back(alpha[(size_t) digit[(size_t) q]]);
+            km += core;
+            for (int q = 0; q < nb; q++) km.push_back(alpha[(size_t) digit[(size_t) (nf + q)]]);
+            std::string old_km = km;
+            old_km[old_km.find(new_c)] = old_c;
+            pairs.emplace_back(old_km, km);
+            int q = nf + nb - 1;
+            while (q >= 0 && ++digit[(size_t) q] == (int) alpha.size()) digit[(size_t) q--] = 0;
+            if (q < 0) break;
+        }
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    char *o = (char *) calloc(pairs.size() * 2 * (size_t) (k + 1) + 1, 1);
+    if (!o) return SA_ENOMEM;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        memcpy(o + (2 * i) * (size_t) (k + 1), pairs[i].first.c_str(), (size_t) k);
+        memcpy(o + (2 * i + 1) * (size_t) (k + 1), pairs[i].second.c_str(), (size_t) k);
+    }
+    *pairs_out = o;
+    *n_out = (int64_t) pairs.size();
+    return SA_OK;
 }
 
 // ---- host: Python's repr, the "%f" units, the model writer ----------------------------------------------------------------------

@@ -16,6 +16,7 @@
  * files, stdout summary line and stderr SUCCESS line are produced as by one single-read invocation.
  */
 #define _GNU_SOURCE
+#include <ctype.h>
 #include <getopt.h>
 #include <inttypes.h>
 #include <math.h>
@@ -91,7 +92,13 @@ static void usage(void) {
                     "                  means and SDs retrained on that table (trainModels.py train_normal_emmissions)\n"
                     "--train-min-prob <p> (0.8), --train-max-assignments <n> (10), --train-weight <w> (100), --train-min-sd <s> (0),\n"
                     "--train-median, --train-mod-only, --train-kmers <file> (one k-mer per line: only those are trained)\n"
-                    "                  with any --train-* output, a manifest's posteriors file may be '-' as well\n\n");
+                    "                  with any --train-* output, a manifest's posteriors file may be '-' as well\n"
+                    "--train-mixture-motifs <canonical:modified,...> (e.g. CCAGG:CEAGG,CCTGG:CETGG) with --train-mixture-template-model\n"
+                    "                  <file> / --train-mixture-complement-model <file> / --train-mixture-distances <file>: every\n"
+                    "                  canonical k-mer over a motif's modified position gets a two-component Gaussian mixture fitted\n"
+                    "                  to its rows of that table on the GPU; the component farther from the -T / -C level mean\n"
+                    "                  becomes the modified k-mer's mean and SD in the model written (mixture_model.py), the\n"
+                    "                  distances file lists both components per k-mer\n\n");
 }
 
 static double descale(double e, double level, double scale, double shift, double var) {
@@ -353,10 +360,12 @@ typedef struct {
     const char *agg_path;   /* --site-calls-aggregate: the over-reads table, written at the end of the run */
     /* --train-*: the top-N assignments of the whole run in k-mer tables on the GPU (one per strand), written at the end */
     const char *train_assign, *train_model[2], *train_kmers;
-    int want_train;         /* any of --train-assignments / --train-template-model / --train-complement-model */
+    int want_train;         /* any of --train-assignments / --train-template-model / --train-complement-model / --train-mixture-* */
     double train_min_prob, train_weight, train_min_sd;
     int64_t train_n;
     int train_median, train_mod_only;
+    /* --train-mixture-*: the modified k-mers of motif pairs get the other component of a two-component mixture (mixture_model.py) */
+    const char *mix_motifs, *mix_model[2], *mix_dist;
     sa_kmer_table_t *train_tab[2];
     int two_dist; /* --emission twoDist: the two-distribution emission (not an option of the reference binary: it is what its
                    * state machine carried when the reference's shipped output files were written).  A single read is aligned with
@@ -1174,6 +1183,156 @@ static int outputs_distinct(const read_t *reads, const int64_t *who, int64_t n) 
     return ok;
 }
 
+/* --train-mixture-motifs: the (canonical, modified) k-mer ids of every motif pair of the list, for the model of strand s:
+ * get_motif_kmer_pairs with the reference's flanks (A, T, G, C), the pairs of all motifs as one sorted set (mixture_model.py
+ * main(): a set union).  A malformed list or a letter outside the model's alphabet ends the run with the usage text. */
+typedef struct {
+    int32_t canonical, modified;
+    char name[2][24];
+} mix_pair_t;
+
+static int cmp_mix_pair(const void *a, const void *b) {
+    const mix_pair_t *x = a, *y = b;
+    const int c = strcmp(x->name[0], y->name[0]);
+    return c ? c : strcmp(x->name[1], y->name[1]);
+}
+
+static int64_t mixture_pairs(const run_t *R, int s, mix_pair_t **out) {
+    const strand_model_t *sm = &R->sm[s];
+    char *list = strdup(R->mix_motifs), *save = NULL;
+    mix_pair_t *v = NULL;
+    int64_t n = 0;
+    if (R->mix_motifs[0] == 0 || R->mix_motifs[strlen(R->mix_motifs) - 1] == ',' || strstr(R->mix_motifs, ",,")) {
+        usage();
+        die("signalMachine: --train-mixture-motifs: malformed list %s", R->mix_motifs);
+    }
+    for (char *item = strtok_r(list, ",", &save); item; item = strtok_r(NULL, ",", &save)) {
+        char *colon = strchr(item, ':');
+        if (!colon || colon == item || colon[1] == 0 || strchr(colon + 1, ':')) {
+            usage();
+            die("signalMachine: --train-mixture-motifs: expected <canonical>:<modified>, got %s", item);
+        }
+        *colon = 0;
+        for (const char *m = item; m; m = m == item ? colon + 1 : NULL)
+            for (const char *c = m; *c; c++)
+                if (!memchr(sm->alphabet, toupper((unsigned char) *c), (size_t) sm->n_alpha)) {
+                    usage();
+                    die("signalMachine: --train-mixture-motifs: a letter of %s is not in the model's alphabet", m);
+                }
+        char *pairs = NULL;
+        int64_t np = 0;
+        if (sm->k >= (int) sizeof(v->name[0]) || sa_motif_kmer_pairs(sm->k, item, colon + 1, NULL, &pairs, &np) != SA_OK) {
+            usage();
+            die("signalMachine: --train-mixture-motifs: %s and its partner must differ in one letter, the first of them made of A, C, G, T", item);
+        }
+        v = realloc(v, (size_t) (n + np + 1) * sizeof(mix_pair_t));
+        if (!v) die("signalMachine: out of memory%s", "");
+        for (int64_t i = 0; i < np; i++) {
+            mix_pair_t *q = &v[n];
+            snprintf(q->name[0], sizeof q->name[0], "%s", pairs + (2 * i) * (sm->k + 1));
+            snprintf(q->name[1], sizeof q->name[1], "%s", pairs + (2 * i + 1) * (sm->k + 1));
+            q->canonical = (int32_t) sa_kmer_id(sm->model, q->name[0]);
+            q->modified = (int32_t) sa_kmer_id(sm->model, q->name[1]);
+            if (q->canonical >= 0 && q->modified >= 0) n++;
+        }
+        sa_free(pairs);
+    }
+    free(list);
+    if (n) qsort(v, (size_t) n, sizeof(mix_pair_t), cmp_mix_pair);
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; i++)
+        if (m == 0 || cmp_mix_pair(&v[m - 1], &v[i]) != 0) v[m++] = v[i];
+    *out = v;
+    return m;
+}
+
+typedef struct {
+    const char *kmer;
+    double v[7];            /* canonical model mean, sd; canonical mixture mean, sd; modified mixture mean, sd; distance */
+    int strand;
+} mix_row_t;
+
+static int cmp_mix_row(const void *a, const void *b) {   /* distance descending, then k-mer, then strand */
+    const mix_row_t *x = a, *y = b;
+    if (x->v[6] != y->v[6]) return x->v[6] > y->v[6] ? -1 : 1;
+    const int c = strcmp(x->kmer, y->kmer);
+    return c ? c : x->strand - y->strand;
+}
+
+/* generate_gaussian_mixture_model_for_motifs (mixture_model.py:122-186) per strand: K = 2 with sklearn's defaults on the rows of
+ * every pair's canonical k-mer, closest_to_canonical against the -T / -C file's level mean, the other component into the
+ * modified k-mer's row ({n = 1, m, s} at weight 0 gives m and s back exactly, and the mean^3 / sd^2 lambda of
+ * set_kmer_event_mean_params).  The distances of all strands go into one file. */
+static void write_mixture(run_t *R, const char *t_model, const char *c_model) {
+    if (!R->mix_motifs) return;
+    mix_row_t *rows = NULL;
+    mix_pair_t *pairs[2] = {NULL, NULL};
+    int64_t n_rows = 0;
+    for (int s = 0; s < n_strands(R); s++) {
+        if (!R->mix_model[s] && !R->mix_dist) continue;
+        const strand_model_t *sm = &R->sm[s];
+        int64_t nk = 1;
+        for (int i = 0; i < sm->k; i++) nk *= sm->n_alpha;
+        const int64_t np = mixture_pairs(R, s, &pairs[s]);
+        int32_t *ids = xalloc(np, sizeof(int32_t), 1);
+        sa_mixture_fit_t *fit = xalloc(np, sizeof(sa_mixture_fit_t), 1);
+        sa_kmer_stat_t *st = xalloc(nk, sizeof(sa_kmer_stat_t), 1);
+        uint8_t *mask = xalloc(nk, 1, 1);
+        for (int64_t i = 0; i < np; i++) ids[i] = pairs[s][i].canonical;
+        const sa_mixture_params_t mp = {2, 100, 1e-3, 1e-6};
+        if (np > 0 && sa_kmer_table_mixture(R->train_tab[s], s, ids, np, &mp, NULL, fit, NULL) != SA_OK)
+            die("signalMachine: --train-mixture-*: the fit failed%s", "");
+        rows = realloc(rows, (size_t) (n_rows + np + 1) * sizeof(mix_row_t));
+        if (!rows) die("signalMachine: out of memory%s", "");
+        for (int64_t i = 0; i < np; i++) {
+            const mix_pair_t *q = &pairs[s][i];
+            int32_t match = 0, other = 1;
+            double distance = 0;
+            if (fit[i].status != 0 || sa_mixture_assign(&fit[i], sm->table_orig[5 * q->canonical], &match, &other, &distance) != SA_OK) {
+                fprintf(stderr, "No alignments found for kmer: %s\n", q->name[0]);
+                continue;
+            }
+            st[q->modified].n = 1;
+            st[q->modified].m = fit[i].mean[other];
+            st[q->modified].s = fit[i].sd[other];
+            mask[q->modified] = 1;
+            mix_row_t *r = &rows[n_rows++];
+            r->kmer = q->name[0];
+            r->strand = s;
+            r->v[0] = sm->table_orig[5 * q->canonical]; r->v[1] = sm->table_orig[5 * q->canonical + 1];
+            r->v[2] = fit[i].mean[match]; r->v[3] = fit[i].sd[match];
+            r->v[4] = fit[i].mean[other]; r->v[5] = fit[i].sd[other];
+            r->v[6] = distance;
+        }
+        if (R->mix_model[s] && sa_model_write_trained(s ? c_model : t_model, st, 0.0, 0.0, 0, mask, R->mix_model[s]) != SA_OK)
+            die("signalMachine: cannot write %s", R->mix_model[s]);
+        free(ids);
+        free(fit);
+        free(st);
+        free(mask);
+    }
+    if (R->mix_dist) {
+        FILE *f = fopen(R->mix_dist, "w");
+        if (!f) die("signalMachine: cannot write %s", R->mix_dist);
+        if (n_rows) qsort(rows, (size_t) n_rows, sizeof(mix_row_t), cmp_mix_row);
+        fprintf(f, "kmer\tcanonical_model_mean\tcanonical_model_sd\tcanonical_mixture_mean\tcanonical_mixture_sd\tmodified_mixture_mean\t"
+                   "modified_mixture_sd\tdistance\tstrand\n");
+        for (int64_t i = 0; i < n_rows; i++) {
+            fputs(rows[i].kmer, f);
+            for (int q = 0; q < 7; q++) {
+                char num[40];
+                sa_format_py_repr(num, rows[i].v[q]);
+                fprintf(f, "\t%s", num);
+            }
+            fprintf(f, "\t%c\n", rows[i].strand ? 'c' : 't');
+        }
+        if (fclose(f) != 0) die("signalMachine: cannot write %s", R->mix_dist);
+    }
+    free(rows);
+    free(pairs[0]);
+    free(pairs[1]);
+}
+
 /* --train-*: the assignments table (generate_top_n_kmers_from_sa_output) and the retrained models (train_normal_emmissions:
  * the prior is the -T / -C file as written on disk) */
 static void write_training(run_t *R, const char *t_model, const char *c_model, int device) {
@@ -1213,6 +1372,7 @@ static void write_training(run_t *R, const char *t_model, const char *c_model, i
         free(st);
         free(mask);
     }
+    write_mixture(R, t_model, c_model);
     for (int s = 0; s < 2; s++) { sa_kmer_table_destroy(R->train_tab[s]); R->train_tab[s] = NULL; }
 }
 
@@ -1660,6 +1820,10 @@ int main(int argc, char **argv) {
                                            {"train-median", no_argument, 0, 1017},
                                            {"train-mod-only", no_argument, 0, 1018},
                                            {"train-kmers", required_argument, 0, 1019},
+                                           {"train-mixture-motifs", required_argument, 0, 1040},
+                                           {"train-mixture-template-model", required_argument, 0, 1041},
+                                           {"train-mixture-complement-model", required_argument, 0, 1042},
+                                           {"train-mixture-distances", required_argument, 0, 1043},
                                            {"snp-step", required_argument, 0, 1020},
                                            {"snp-dir", required_argument, 0, 1021},
                                            {0, 0, 0, 0}};
@@ -1707,6 +1871,10 @@ int main(int argc, char **argv) {
             case 1017: R.train_median = 1; break;
             case 1018: R.train_mod_only = 1; break;
             case 1019: R.train_kmers = strdup(optarg); break;
+            case 1040: R.mix_motifs = strdup(optarg); break;
+            case 1041: R.mix_model[0] = strdup(optarg); break;
+            case 1042: R.mix_model[1] = strdup(optarg); break;
+            case 1043: R.mix_dist = strdup(optarg); break;
             case 1020:
                 snp_set = 1;
                 if (sscanf(optarg, "%" SCNd64, &R.snp_step) != 1) R.snp_step = 0;
@@ -1762,10 +1930,15 @@ int main(int argc, char **argv) {
     if (R.two_dist && (R.hdp || t_hdp != NULL || c_hdp != NULL || R.expect_mode || t_expect != NULL || c_expect != NULL))
         die("signalMachine: --emission twoDist aligns reads with a Gaussian model: not with an .nhdp, not with -t / -c%s", "");
 
-    R.want_train = R.train_assign || R.train_model[0] || R.train_model[1];
+    const int mix_out = R.mix_model[0] || R.mix_model[1] || R.mix_dist;
+    if ((R.mix_motifs != NULL) != (mix_out != 0)) {
+        usage();
+        die("signalMachine: --train-mixture-motifs goes with --train-mixture-template-model / -complement-model / -distances%s", "");
+    }
+    R.want_train = R.train_assign || R.train_model[0] || R.train_model[1] || R.mix_motifs;
     if (R.want_train) {
         if (R.expect_mode || R.mea) die("signalMachine: --train-* needs the alignment mode without --mea%s", "");
-        if (R.train_model[1] && !R.two_d) die("signalMachine: --train-complement-model needs a 2-D run%s", "");
+        if ((R.train_model[1] || R.mix_model[1]) && !R.two_d) die("signalMachine: --train-complement-model needs a 2-D run%s", "");
         if (R.train_n < 1 || !(R.train_min_prob >= 0 && R.train_min_prob <= 1)) die("signalMachine: bad --train-max-assignments / --train-min-prob%s", "");
     }
     if (R.expect_mode && (R.site_calls || R.agg_path)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate need the alignment mode, not -t/-c%s", ""); }
@@ -1810,6 +1983,13 @@ int main(int argc, char **argv) {
         if (sa_model_clone_with_table(&sm->model_two, sm->model, sm->table_orig) != SA_OK ||
             sa_model_set_emission(sm->model_two, SA_EMISSION_TWO_DIST) != SA_OK)
             die("signalMachine: --emission twoDist: could not set up the two-distribution model%s", "");
+    }
+    if (R.mix_motifs) {   /* parsed once here, so that a bad list stops the run before it starts */
+        mix_pair_t *probe = NULL;
+        for (int s = 0; s < n_strands(&R); s++) {
+            mixture_pairs(&R, s, &probe);
+            free(probe);
+        }
     }
     if (ambig_model) {
         if (sa_load_ambig(ambig_model, R.ambig) != SA_OK) {
