@@ -15,6 +15,6 @@ F="-O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -I$T/include
 /opt/rocm/bin/hipcc $F -c $T/csrc/sa_hip.hip -o $T/sa_hip.o
 O=$(ls signalalign_amd/lib/*.o | grep -v "lib/sa_hip.o")
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o probes/_variants/lib_$n.so $O $T/sa_hip.o -lm -lpthread
-diff <(cd signalalign_amd/csrc && cat sa_hip.hip sa_*.inc) <(cd $T/csrc && cat sa_hip.hip sa_*.inc) | head -12
+diff <(cd signalalign_amd/csrc && cat sa_hip.hip sa_*.inc sa_plan_rules.h) <(cd $T/csrc && cat sa_hip.hip sa_*.inc sa_plan_rules.h) | head -12
 rm -rf $T
 echo built probes/_variants/lib_$n.so

@@ -1,15 +1,16 @@
 // sa_dplan.inc -- the planner on the device.  Included by sa_hip.hip.
 //
-// sa_plan.c builds, per read, the band table (band_construct impl/pairwiseAligner.c:195-246), the packed band words of the
-// register kernels, the traceback schedule and the total-probability checkpoints (getPosteriorProbsWithBanding :1450-1590,
-// the schedule only) on the host and uploads ~400 KB per read.  For the common batch -- canonical references (one path per
-// cell), no anchor gap large enough to split a matrix (getSplitPoints :1886-1937), Gaussian or HDP emissions through the
-// default kernels -- the same arrays are built here from what a read really consists of: its reference letters, event
-// means and anchors (~60 KB).  One workgroup per read; every step is the host planner's formula evaluated per diagonal
-// (box of a diagonal by binary search over the anchors instead of the host's running index), prefix sums by workgroup
-// scans.  The result is bit-identical to sa_plan.c's (tests/test_gpu_dplan.py compares every array), so which planner ran
-// is invisible downstream.  Whatever is not covered (ambiguous letters, split matrices, SA_FLAG_EXACT, expectations)
-// takes the host planner as before.
+// The host planner builds, per read, the band table (band_construct impl/pairwiseAligner.c:195-246), the packed band words of
+// the register kernels, the traceback schedule and the total-probability checkpoints (getPosteriorProbsWithBanding :1450-1590,
+// the schedule only) and uploads ~400 KB per read.  For the common batch -- no anchor gap large enough to split a matrix
+// (getSplitPoints :1886-1937), Gaussian or HDP emissions through the default kernels -- the same arrays are built here from
+// what a read really consists of: its reference letters, event means and anchors (~60 KB).  What is computed per diagonal,
+// segment, path and region is sa_plan_rules.h, the one statement both planners compile, and what a batch must be to be planned
+// at all are the predicates of sa_internal.h; this file is how the device walks a read: one workgroup per read, strided loops
+// over the diagonals (box of a diagonal by binary search over the anchors instead of the host's running index), prefix sums by
+// workgroup scans.  The result is bit-identical to the host planner's (tests/test_gpu_dplan.py compares every array), so which
+// planner ran is invisible downstream.  Whatever is not covered (split matrices, SA_FLAG_EXACT, the two-distribution
+// emissions, a region the rules route to SA_KIND_GENERIC) takes the host planner as before.
 //
 // Passes: k_dplan_region (one workgroup per read: k-mer ids, band rows, offsets, packed words, schedule into per-read
 // slabs) -> k_dplan_scan (one workgroup: running sums over the reads, forward-storage passes) -> k_dplan_compact (per
@@ -61,39 +62,14 @@ struct DPlanArgs {
     sa_ck_t *ck_slab;
     sa_dcount_t *counts;
     long long expansion, trace_back, min_diags;
-    long long pow_check;        // 1 << (31 - SA_PK_SHIFT)
-    int k, n_alpha, ring_on, ring_wide_on, fast_hdp_ok, cand_per_diag, expect;
+    int k, n_alpha;
+    sa_route_in_t route;        // the batch's part of the routing inputs (flags, model, environment); the kernel adds each region's
     sa_prec_t *prec;            // per-path neighbour records (batches with ambiguous letters only)
     unsigned char lut[256];     // letter -> digit of the sorted alphabet, 255: not in it
     unsigned char amb_n[256];   // options of an ambiguity letter, 1 for every other letter
     unsigned short amb_off[256];// where its options' digits start in amb_dig
     unsigned char amb_dig[512]; // digits of the options, letter after letter
 };
-
-// (integer type I: int when every coordinate sum of the read fits 30 bits -- N + 2 * expansion + 4 < 2^30, every read the result
-// records can name -- long long otherwise.  Same operations, same results; the band clip is most of this planner's instructions
-// and 64-bit integer arithmetic costs two to four instructions per operation: round 4.)
-template <typename I>
-__device__ __forceinline__ I dp_clampz(I z, I hi) { return z < 0 ? 0 : (z > hi ? hi : z); }
-
-// clip_row of sa_plan.c
-template <typename I>
-__device__ __forceinline__ bool dp_clip_row(I xay, I xL, I yL, I xU, I yU, I &lo, I &hi) {
-    I a = xL - yL, b = xU - yU;
-    if ((xay + a) % 2 != 0) a++;
-    if ((xay + b) % 2 != 0) b++;
-    I x = (xay + a) / 2;
-    if (x < xL) a += 2 * (xL - x);
-    I y = (xay - a) / 2;
-    if (yL < y) a += 2 * (y - yL);
-    x = (xay + b) / 2;
-    if (xU < x) b -= 2 * (x - xU);
-    y = (xay - b) / 2;
-    if (y < yU) b -= 2 * (yU - y);
-    lo = a;
-    hi = b;
-    return !((xay + a) % 2 != 0 || (xay + b) % 2 != 0 || a > b);
-}
 
 // exclusive workgroup scan of one value per thread; returns the workgroup total through `total`
 __device__ __forceinline__ long long dp_block_scan(long long v, long long *lds_wave /* >= 4 */, long long &total) {
@@ -114,20 +90,6 @@ __device__ __forceinline__ long long dp_block_scan(long long v, long long *lds_w
     }
     total = tot;
     return before + incl - v;
-}
-
-template <typename I>
-__device__ __forceinline__ int dp_span3(const sa_row_t *rows, I d, I K) {
-    const sa_row_t r = rows[d];
-    const I uL = ((I) r.xmyL + K) >> 1, uR = uL + r.width - 1;
-    I wl = uL - 1, wr = uR + 1;
-    for (I b = 1; b <= 2 && d - b >= 0; b++) {
-        const sa_row_t q = rows[d - b];
-        const I l2 = ((I) q.xmyL + K) >> 1, r2 = l2 + q.width - 1;
-        wl = l2 < wl ? l2 : wl;
-        wr = r2 > wr ? r2 : wr;
-    }
-    return (int) (wr - wl + 1);
 }
 
 // SA_FLAG_INPUTS_IN_HOST_BLOCK: the caller's block arrived in HBM with ONE DMA (pinned source); this kernel does on the device
@@ -210,8 +172,9 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
     }
     int status = 0;
 
-    // ---- per-position path tables (hdCell_construct2 impl/pairwiseAligner.c:723-801 as expand_kmer of sa_plan.c lists them:
-    // every substitution of the window's ambiguity letters, last position varying fastest); cell x = 0 is the NULL k-mer ----
+    // ---- per-position path tables (hdCell_construct2 impl/pairwiseAligner.c:723-801: every substitution of the window's
+    // ambiguity letters, last position varying fastest -- the host planner's expand_kmer lists them from the letters themselves,
+    // here from their digits); cell x = 0 is the NULL k-mer ----
     int maxP = 1;
     if (!(J.bits & 1)) {   // no ambiguity letter in this read: one path per cell
         for (long long x = t; x <= lX + 1; x += DPLAN_NT) poff[x] = (int) x;
@@ -275,13 +238,13 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
     if (sums_in_lds)
         for (int i = t; i < J.n_anchors; i += DPLAN_NT) s_sum[i] = ax[i] + ay[i] + 2;
     __syncthreads();
-    const bool small = N + 2 * e + 4 < (1ll << 30) && e >= 0;
+    const bool small = sa_band_fits32(N, e);   // (32-bit instance of the band rules: every read the result records can name)
     auto band_rows = [&](auto zero) {
         typedef decltype(zero) I;
         const I lXi = (I) lX, lYi = (I) lY, ei = (I) e, Ni = (I) N;
         for (I d = (I) t; d <= Ni; d += DPLAN_NT) {
             I lo = 0, hi = 0;
-            bool ok = true;
+            int rc = SA_OK;
             if (d >= 1) {
                 // the box of diagonal d: first anchor (in matrix coordinates, +1) whose x + y >= d; behind the last: (lX, lY)
                 int a = 0, b = J.n_anchors;
@@ -296,28 +259,29 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
                         if ((I) ax[m] + ay[m] + 2 >= d) b = m; else a = m + 1;
                     }
                 }
-                I x = lXi, y = lYi, p_sum = 0, p_dif = 0;
+                I x = lXi, y = lYi, p_sum = 0, p_dif = 0, c[4];
                 if (a < J.n_anchors) { x = (I) ax[a] + 1; y = (I) ay[a] + 1; }
                 if (a >= 1) {
                     const I px = (I) ax[a - 1] + 1, py = (I) ay[a - 1] + 1;
                     p_sum = px + py; p_dif = px - py;
                 }
-                const I n_sum = x + y, n_dif = x - y;
-                const I xL = dp_clampz<I>((p_sum + p_dif - ei) / 2, lXi);
-                const I yL = dp_clampz<I>((n_sum - n_dif + ei) / 2, lYi);
-                const I xU = dp_clampz<I>((n_sum + n_dif + ei) / 2, lXi);
-                const I yU = dp_clampz<I>((p_sum - p_dif - ei) / 2, lYi);
-                ok = dp_clip_row<I>(d, xL, yL, xU, yU, lo, hi);
+                if constexpr (sizeof(I) == 4) {   // the box's corners c, then the diagonal clipped to it: by the rules' instance for I
+                    sa_band_box_32(p_sum, p_dif, x + y, x - y, ei, lXi, lYi, c);
+                    rc = sa_clip_row_32(d, c[0], c[1], c[2], c[3], &lo, &hi);
+                } else {
+                    sa_band_box_64(p_sum, p_dif, x + y, x - y, ei, lXi, lYi, c);
+                    rc = sa_clip_row_64(d, c[0], c[1], c[2], c[3], &lo, &hi);
+                }
             }
-            if (!ok) status = SA_EBAND;
+            if (rc) status = rc;
             sa_row_t row;
             row.xmyL = (int) lo;
-            row.width = ok ? (int) ((hi - lo) / 2 + 1) : 1;
+            row.width = rc == SA_OK ? (int) ((hi - lo) / 2 + 1) : 1;
             row.foff = 0;
             rows[d] = row;
         }
     };
-    if (small) band_rows(0); else band_rows(0ll);
+    if (small) band_rows((int32_t) 0); else band_rows((int64_t) 0);
     __threadfence_block();
     __syncthreads();
 
@@ -343,25 +307,21 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
     __syncthreads();
 
     // ---- packed band words, widest window, share of cells on diagonals the register kernels cannot hold ----
-    const long long K = lY + (lY & 1) + 2;
+    const long long K = sa_band_K(lY);
     long long span = 0, wide_cells = 0;
     auto band_words = [&](auto zero) {
         typedef decltype(zero) I;
         const I Ki = (I) K, Ni = (I) N;
+        auto span3 = [&](I dd) { if constexpr (sizeof(I) == 4) return sa_span3_32(rows, dd, Ki); else return sa_span3_64(rows, dd, Ki); };
         for (I d = (I) t; d <= Ni; d += DPLAN_NT) {
             const sa_row_t rw = rows[d];
-            const int s3 = dp_span3<I>(rows, d, Ki);
-            const int s3b = dp_span3<I>(rows, d + 2 <= Ni ? d + 2 : Ni, Ki);
-            const I uL = ((I) rw.xmyL + Ki) >> 1;
-            int word = (int) ((rw.width > SA_PK_WIDTH_MASK ? SA_PK_WIDTH_MASK : rw.width) | ((unsigned) uL << SA_PK_SHIFT));
-            if (s3 <= 64) word |= SA_PK_FWD;
-            if (s3b <= 64) word |= SA_PK_BWD;
-            pk[d] = word;
+            const int s3 = span3(d), s3b = span3(d + 2 <= Ni ? d + 2 : Ni);
+            pk[d] = sa_pk_word(rw.width, (unsigned) (((I) rw.xmyL + Ki) >> 1), s3, s3b);
             span = s3 > span ? s3 : span;
             if (d >= 1 && s3 > 64) wide_cells += rw.width;
         }
     };
-    if (small) band_words(0); else band_words(0ll);
+    if (small) band_words((int32_t) 0); else band_words((int64_t) 0);
     {   // workgroup reductions: max width, max span, wide cells, status
         long long tot;
         (void) dp_block_scan(wide_cells, s_wave, tot);
@@ -386,14 +346,11 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
     const long long max_rowpaths = max_w;
     const double cf = (double) (total_cells - (rows[1].foff - rows[0].foff));
 
-    // ---- which kernels (add_region of sa_plan.c, one path per cell) ----
-    int fast_ok = A.fast_hdp_ok;
-    if (total_cells + 1 > SA_FAST_MAX_CELLS || ((lX + lY + K) >> 1) >= A.pow_check) fast_ok = 0;
-    if (maxP > 1) fast_ok = 0;
-    const int ring_ok = A.ring_on && max_rowpaths <= SA_RING_MAX_ROWPATHS && total_cells + 1 <= SA_FAST_MAX_CELLS;
-    // (the expectation pass: ring kernels for several paths per cell only; one-path regions keep the register kernels' variant)
-    const int use_ring = ring_ok && (maxP > 1 || (!A.expect && fast_ok && A.ring_wide_on && ((double) wide_cells > SA_RING_WIDE_FRACTION * cf)));
-    const int kind = use_ring ? SA_KIND_RING : (fast_ok ? SA_KIND_FAST : SA_KIND_GENERIC);
+    // ---- which kernels ----
+    sa_route_in_t route = A.route;
+    route.max_p = maxP; route.max_rowpaths = max_rowpaths; route.cellpaths = total_cells;
+    route.lX = lX; route.lY = lY; route.K = K; route.cf = cf; route.wide_cells = (double) wide_cells;
+    const int kind = sa_route_kind(&route);
     if (kind == SA_KIND_GENERIC && status == 0) status = SA_EUNSUPPORTED;   // not plannable here: the host planner takes the batch
 
     // ---- traceback schedule (getPosteriorProbsWithBanding, the schedule only) ----
@@ -417,9 +374,9 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
         }
         const long long d = found;
         const int at_end = d == N;
-        const long long from = d - (at_end ? 0 : A.trace_back + 1), to = traced_to;
+        const long long from = sa_seg_from(d, at_end, A.trace_back), to = traced_to;
         if (from <= to) { status = SA_EINVAL; break; }
-        const long long nck = (from - to + SA_CKPT_EVERY - 1) / SA_CKPT_EVERY;
+        const long long nck = sa_seg_n_ck(from, to), cap = sa_seg_cand_cap(A.route.hdp, from, to);
         // checkpoints: diagonals from, from - 10, ... > to; their per-cell terms are laid out one after the other
         long long vcarry = 0;
         for (long long base = 0; base < nck; base += DPLAN_NT) {
@@ -447,20 +404,14 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
             S.region = r; S.at_end = at_end;
             S.start = d; S.from = from; S.to = to;
             S.ck_base = n_ck; S.n_ck = (int) nck;
-            long long cap = (long long) A.cand_per_diag * (from - to + 32);
-            if (cap > 2147483647ll) cap = 2147483647ll;
             S.cand_cap = (int) cap;
             S.cand_off = n_cand;
             S.bscratch_off = n_bscr;
             segs[n_seg] = S;
-            pk[d] |= SA_PK_FULL;   // (as sa_plan.c: the diagonal a traceback starts on keeps all three forward planes)
+            pk[d] |= SA_PK_FULL;   // (the diagonal a traceback starts on keeps all three forward planes)
         }
-        {
-            long long cap = (long long) A.cand_per_diag * (from - to + 32);
-            if (cap > 2147483647ll) cap = 2147483647ll;
-            n_cand += cap;
-        }
-        if (kind != SA_KIND_RING) n_bscr += 12 * max_rowpaths;
+        n_cand += cap;
+        n_bscr += sa_seg_bscratch(kind, max_rowpaths);
         if (to + 2 <= d) cb += (double) (rows[d + 1].foff - rows[to + 2].foff);
         n_ck += nck;
         n_vbuf += vcarry;
@@ -471,46 +422,26 @@ __global__ __launch_bounds__(DPLAN_NT) void k_dplan_region(DPlanArgs A, int n_jo
     __threadfence_block();
     __syncthreads();
 
-    // ---- derived flags of the packed words (the words behind diagonal N are zero) ----
+    // ---- derived flags of the packed words (the words behind diagonal N, and the one in front of diagonal 0, are zero) ----
+    const int expect = (A.route.flags & SA_FLAG_EXPECT_INTERNAL) != 0;
     for (long long d = t; d <= N && status == 0; d += DPLAN_NT) {
-        int w = pk[d];
-        const int w1 = pk[d + 1], w2 = pk[d + 2];
-        int add = 0;
-        if ((w & SA_PK_CK) || !(w1 & SA_PK_FWD) || !(w2 & SA_PK_FWD) || d + 2 > N || A.expect) add |= SA_PK_FULL;
-        if (d < N && (w1 & SA_PK_FWD)) add |= SA_PK_FWD_MORE;
-        if (d >= 1 && (pk[d - 1] & SA_PK_BWD)) add |= SA_PK_BWD_MORE;
         // every thread writes only its own word, and the bits added here (FULL, FWD_MORE, BWD_MORE) are not among those a
         // neighbour tests (FWD, BWD, CK): a concurrent reader sees the same answer before and after
-        pk[d] = w | add;
+        const int w = pk[d];
+        pk[d] = w | sa_pk_derived(w, d >= 1 ? pk[d - 1] : 0, pk[d + 1], pk[d + 2], d, N, expect);
     }
     if (kind == SA_KIND_RING)
         for (long long d = t; d <= N; d += DPLAN_NT) rows[d].foff |= (long long) poff[(d + rows[d].xmyL) / 2] << 32;   // g0 = poff[first x]
     if (kind == SA_KIND_RING && maxP > 1 && status == 0) {
-        // per-path neighbour records (fill_prec of sa_plan.c)
+        // per-path neighbour records (their limits hold here: no window with more than 255 paths came this far)
         sa_prec_t *pr = A.prec + J.pid_off;
-        if (t == 0) {
-            sa_prec_t o;
-            o.x = 0; o.pred0 = -1; o.succ0 = lX >= 1 ? poff[1] : -1;
-            o.meta = (unsigned) (lX >= 1 ? poff[2] - poff[1] : 0);
-            pr[0] = o;
-        }
+        if (t == 0) (void) sa_prec_col0(poff, lX, &pr[0]);
         for (long long x = 1 + t; x <= lX; x += DPLAN_NT) {
             const unsigned char *w = ref + (x - 1);
-            const long long P = (long long) poff[x + 1] - poff[x];
-            const long long n_last = A.amb_n[w[A.k - 1]];
-            const long long shared = P / n_last;
-            long long npred = 1, stride = 0;
-            if (x >= 2) { npred = A.amb_n[w[-1]]; stride = shared; }
-            long long nsucc = 0, shared_n = 1, n_last_n = 1;
-            if (x < lX) { n_last_n = A.amb_n[w[A.k]]; shared_n = P / A.amb_n[w[0]]; nsucc = n_last_n; }
-            for (long long q = 0; q < P; q++) {
-                sa_prec_t o;
-                o.x = (int) x;
-                o.pred0 = (int) (x >= 2 ? poff[x - 1] + q / n_last : 0);
-                o.succ0 = x < lX ? (int) (poff[x + 1] + (q % shared_n) * n_last_n) : -1;
-                o.meta = (unsigned) (stride << 16) | (unsigned) (npred << 8) | (unsigned) nsucc;
-                pr[poff[x] + q] = o;
-            }
+            sa_prec_col_t col;
+            (void) sa_prec_column(&col, poff, x, lX, x >= 2 ? A.amb_n[w[-1]] : 1, A.amb_n[w[0]], A.amb_n[w[A.k - 1]], x < lX ? A.amb_n[w[A.k]] : 1);
+            const int p0 = poff[x], P = poff[x + 1] - p0;
+            for (int q = 0; q < P; q++) pr[p0 + q] = sa_prec_path(&col, poff, q);
         }
     }
 
@@ -698,10 +629,7 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     if (!dplan_enabled() || n_jobs <= 0 || n_jobs > 0x3fffffff) return 1;
     if (flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC)) return 1;
     if (m->emission != 0) return 1;   // the two-distribution emission: host planner (its constants are built from the host's pid array)
-    if (!(p->threshold > 0.0 && p->threshold <= 1.0)) return 1;
-    if (p->diagonal_expansion < 0 || p->diagonal_expansion % 2 != 0 || p->trace_back_diagonals < 1 ||
-        p->min_diags_between_trace_back < 2 || p->trace_back_diagonals + 1 >= p->min_diags_between_trace_back)
-        return 1;   // (sa_plan_build reports it)
+    if (!(p->threshold > 0.0) || !sa_params_plannable(p)) return 1;   // (threshold 0: capacities the host sizes; else sa_plan_build reports it)
     const bool trace = getenv("SA_TRACE") != nullptr;
     const double t0 = now_ms();
     DPlanArgs A;
@@ -709,7 +637,7 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     memset(A.lut, 255, sizeof(A.lut));
     for (int i = 0; i < m->n_alpha; i++) A.lut[(unsigned char) m->alphabet[i]] = (unsigned char) i;
     // ambiguity letters: options as digits; a letter whose options repeat, leave the alphabet or do not fit the tables sends the
-    // batch to the host planner (the index form of path legality needs distinct options: sa_plan.c)
+    // batch to the host planner (the index form of path legality needs distinct options)
     bool amb_any[256], amb_bad[256];
     int amb_used = 0;
     for (int c = 0; c < 256; c++) {
@@ -732,8 +660,7 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     }
     // (reads with ambiguity letters are planned here only for the ring kernels; without them -- SA_RING=0, the expectation pass, an
     // HDP table too large for the emission plane's 32-bit offsets -- such a read sends the batch to the host planner)
-    const bool ring_possible = !(getenv("SA_RING") && atoi(getenv("SA_RING")) == 0) &&
-                               !(m->hdp != nullptr && (m->hdp->grid_length < 2 || m->hdp->n_slots * m->hdp->grid_length * 16 >= SA_HDP_FAST_MAX_BYTES)) &&
+    const bool ring_possible = sa_ring_env_on() && sa_hdp_plane_fits(m) &&
                                !((flags & SA_FLAG_EXPECT_INTERNAL) && m->hdp != nullptr);   // (expectation pass: Gaussian models only)
     const int k = m->k;
     const long long limit = p->split_matrix_bigger_than_this;
@@ -805,13 +732,10 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     long long n_rows = 0, n_pk = 0, n_poff = 0, n_pid = 0, n_ev = 0, n_ref = 0, n_anc = 0, n_sslab = 0, n_cslab = 0;
     for (int64_t j = 0; j < n_jobs; j++) {
         const sa_job_t *jb = &jobs[j];
-        bool ok = jb->ref && jb->ref_len >= 0 && jb->n_events >= 0 && jb->n_anchors >= 0 && (!jb->n_events || jb->events) &&
-                  (!jb->n_anchors || (jb->anchor_x && jb->anchor_y)) && jb->var > 0.0 &&
-                  !(jb->ends & ~(SA_JOB_LEFT_END_NOT_RAGGED | SA_JOB_RIGHT_END_NOT_RAGGED));
+        bool ok = sa_job_header_ok(jb);
         long long lX = 0, lY = 0;
         if (ok) {
-            lX = jb->ref_len == 0 ? 0 : jb->ref_len - (k - 1);
-            if (lX < 0) lX = 0;
+            lX = sa_job_lX(jb->ref_len, k);
             lY = jb->n_events;
             ok = lX + lY > 0 && lX < (1 << 28) && lY < (1 << 28) && jb->n_anchors < (1 << 28);
         }
@@ -823,7 +747,7 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
         const long long N = lX + lY;
         d.row_off = n_rows; d.pk_off = n_pk; d.poff_off = n_poff; d.ev_off = n_ev;
         d.ref_off = n_ref; d.anc_off = n_anc; d.seg_slab = n_sslab; d.ck_slab = n_cslab;
-        n_rows += N + 2; n_pk += N + 1 + SA_PK_PAD + 160; n_poff += lX + 2; n_ev += lY;
+        n_rows += sa_region_rows(N); n_pk += sa_region_pk_words(N); n_poff += sa_region_poffs(lX); n_ev += lY;
         n_ref += (jb->ref_len + 15) & ~15ll; n_anc += 2ll * d.n_anchors;
         const long long sb = N / seg_step + 2;
         n_sslab += sb; n_cslab += N / SA_CKPT_EVERY + sb + 2;
@@ -1036,14 +960,11 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     A.regions = b->d_regions; A.rows = b->d_rows; A.pk = b->d_pk; A.poff = b->d_poff; A.pid = b->d_pid; A.prec = b->d_prec;
     A.seg_slab = d_sslab; A.ck_slab = d_cslab; A.counts = d_counts;
     A.expansion = p->diagonal_expansion; A.trace_back = p->trace_back_diagonals; A.min_diags = p->min_diags_between_trace_back;
-    A.pow_check = 1ll << (31 - SA_PK_SHIFT);
     A.k = k; A.n_alpha = m->n_alpha;
-    A.expect = (flags & SA_FLAG_EXPECT_INTERNAL) ? 1 : 0;   // the expectation pass: all three forward states of every diagonal, no ring kernels
-    A.ring_wide_on = !(getenv("SA_RING_WIDE") && atoi(getenv("SA_RING_WIDE")) == 0);
-    A.cand_per_diag = m->hdp ? SA_CAND_PER_DIAG_HDP : SA_CAND_PER_DIAG;
-    A.fast_hdp_ok = !(m->hdp != nullptr && (m->hdp->grid_length < 2 || m->hdp->n_slots * m->hdp->grid_length * 16 >= SA_HDP_FAST_MAX_BYTES));
-    // (HDP models on the ring / strip kernels: they read the emission plane, same table limit as the register kernels)
-    A.ring_on = !(getenv("SA_RING") && atoi(getenv("SA_RING")) == 0) && A.fast_hdp_ok && !(A.expect && m->hdp != nullptr);
+    // the batch's routing inputs, from the host planner's predicates.  ambig_distinct: a read that USES a letter with repeated options was refused
+    // above.  Known difference: the host's ambig_options_distinct() also sees an UNUSED such letter and then takes the reference-ordered kernels.
+    A.route.flags = flags; A.route.emission = m->emission; A.route.hdp = m->hdp != nullptr; A.route.hdp_plane_fits = sa_hdp_plane_fits(m);
+    A.route.ring_env = sa_ring_env_on(); A.route.ring_wide_env = sa_ring_wide_env_on(); A.route.ambig_distinct = 1;
     int lds_anchors = 0;
     for (int64_t j = 0; j < n_jobs; j++) lds_anchors = dj[(size_t) j].n_anchors > lds_anchors ? dj[(size_t) j].n_anchors : lds_anchors;
     if (lds_anchors > DPLAN_LDS_ANCHORS) lds_anchors = DPLAN_LDS_ANCHORS;

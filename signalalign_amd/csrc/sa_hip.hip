@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "sa_internal.h"
+#include "sa_plan_rules.h"
 #include "sa_chain.h"
 
 #define NEG_INF (-__builtin_inf())

@@ -212,6 +212,12 @@ int sa_plan_finalize(const sa_plan_t *pl, const sa_cand_t *cands, const int32_t 
 int64_t sa_model_kmer_id(const sa_model_t *m, const char *kmer);
 int sa_band_rows(const int64_t *ax, const int64_t *ay, int64_t n, int64_t lX, int64_t lY, int64_t expansion,
                  int64_t *xmyL, int64_t *xmyR);
+/* what both planners ask of a batch before planning it (host only; the per-region rules are in sa_plan_rules.h) */
+int sa_hdp_plane_fits(const sa_model_t *m);      /* no HDP, or its {y, slope} table fits 32-bit byte offsets */
+int sa_ring_env_on(void);                        /* SA_RING=0: never use the ring kernels (test / comparison hook) */
+int sa_ring_wide_env_on(void);                   /* SA_RING_WIDE=0: one-path regions stay on the register kernels whatever their band */
+int sa_job_header_ok(const sa_job_t *jb);        /* pointers, counts, var and ends of a job (not its anchors) */
+int sa_params_plannable(const sa_params_t *p);   /* the asserts of impl/pairwiseAligner.c:1460-1464, :1358-1359; threshold in [0, 1] */
 
 #ifdef __cplusplus
 }

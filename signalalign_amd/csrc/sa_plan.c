@@ -27,6 +27,7 @@
 #include <unistd.h>
 
 #include "sa_internal.h"
+#include "sa_plan_rules.h"
 
 /* ------------------------------------------------------------------------------------------------ */
 const char *sa_strerror(int code) {
@@ -292,33 +293,10 @@ int sa_load_ambig(const char *path, const char **map) {
     } while (0)
 
 /* ---- band ------------------------------------------------------------------------------------- */
-static inline int64_t clampz(int64_t z, int64_t hi) { return z < 0 ? 0 : (z > hi ? hi : z); }
-
-/* One anti-diagonal of the band: the stretch of x-y between the lower corner (xL,yL) and the upper
- * corner (xU,yU) of the current anchor-to-anchor box, snapped to the parity of xay. */
-static int clip_row(int64_t xay, int64_t xL, int64_t yL, int64_t xU, int64_t yU, int64_t *lo, int64_t *hi) {
-    int64_t a = xL - yL, b = xU - yU;
-    if ((xay + a) % 2 != 0) a++;
-    if ((xay + b) % 2 != 0) b++;
-    int64_t x = (xay + a) / 2;
-    if (x < xL) a += 2 * (xL - x);
-    int64_t y = (xay - a) / 2;
-    if (yL < y) a += 2 * (y - yL);
-    x = (xay + b) / 2;
-    if (xU < x) b -= 2 * (x - xU);
-    y = (xay - b) / 2;
-    if (y < yU) b -= 2 * (yU - y);
-    if ((xay + a) % 2 != 0 || (xay + b) % 2 != 0 || a > b) return SA_EBAND;
-    *lo = a;
-    *hi = b;
-    return SA_OK;
-}
-
 int sa_band_rows(const int64_t *ax, const int64_t *ay, int64_t n, int64_t lX, int64_t lY, int64_t e, int64_t *lo,
                  int64_t *hi) {
     int64_t N = lX + lY;
-    int rc = clip_row(0, 0, 0, 0, 0, &lo[0], &hi[0]);
-    if (rc) return rc;
+    lo[0] = hi[0] = 0; /* diagonal 0 is the cell (0, 0) */
     int64_t p_sum = 0, p_dif = 0; /* previous anchor in matrix coordinates, as x+y and x-y */
     int64_t d = 1;
     for (int64_t i = 0; d <= N; i++) {
@@ -329,13 +307,10 @@ int sa_band_rows(const int64_t *ax, const int64_t *ay, int64_t n, int64_t lX, in
             if (x <= (p_sum + p_dif) / 2 || y <= (p_sum - p_dif) / 2 || x > lX || y > lY) return SA_EBAND;
         }
         int64_t n_sum = x + y, n_dif = x - y;
-        int64_t xL = clampz((p_sum + p_dif - e) / 2, lX);
-        int64_t yL = clampz((n_sum - n_dif + e) / 2, lY);
-        int64_t xU = clampz((n_sum + n_dif + e) / 2, lX);
-        int64_t yU = clampz((p_sum - p_dif - e) / 2, lY);
-        int64_t last = n_sum < N ? n_sum : N;
+        int64_t last = n_sum < N ? n_sum : N, box[4];
+        sa_band_box_64(p_sum, p_dif, n_sum, n_dif, e, lX, lY, box);
         for (; d <= last; d++) {
-            rc = clip_row(d, xL, yL, xU, yU, &lo[d], &hi[d]);
+            int rc = sa_clip_row_64(d, box[0], box[1], box[2], box[3], &lo[d], &hi[d]);
             if (rc) return rc;
         }
         p_sum = n_sum;
@@ -499,13 +474,27 @@ void sa_plan_free(sa_plan_t *pl) {
     free(pl);
 }
 
-static int ring_env_on(void) { /* SA_RING=0: never use the ring kernels (test / comparison hook) */
+/* ---- what both planners ask of a batch before planning it (sa_internal.h) ---------------------- */
+int sa_ring_env_on(void) {
     const char *e = getenv("SA_RING");
     return !(e && atoi(e) == 0);
 }
-static int ring_wide_env_on(void) { /* SA_RING_WIDE=0: one-path regions stay on the register kernels whatever their band */
+int sa_ring_wide_env_on(void) {
     const char *e = getenv("SA_RING_WIDE");
     return !(e && atoi(e) == 0);
+}
+int sa_hdp_plane_fits(const sa_model_t *m) {
+    return m->hdp == NULL || !(m->hdp->grid_length < 2 || m->hdp->n_slots * m->hdp->grid_length * 16 >= SA_HDP_FAST_MAX_BYTES);
+}
+int sa_job_header_ok(const sa_job_t *jb) {
+    return jb->ref && jb->ref_len >= 0 && jb->n_events >= 0 && jb->n_anchors >= 0 && (!jb->n_events || jb->events) &&
+           (!jb->n_anchors || (jb->anchor_x && jb->anchor_y)) && jb->var > 0.0 &&
+           !(jb->ends & ~(SA_JOB_LEFT_END_NOT_RAGGED | SA_JOB_RIGHT_END_NOT_RAGGED));
+}
+int sa_params_plannable(const sa_params_t *p) {
+    return !(p->diagonal_expansion < 0 || p->diagonal_expansion % 2 != 0 || p->trace_back_diagonals < 1 ||
+             p->min_diags_between_trace_back < 2 || p->trace_back_diagonals + 1 >= p->min_diags_between_trace_back ||
+             !(p->threshold >= 0.0 && p->threshold <= 1.0));
 }
 /* The index form of path legality (fill_prec) needs the options of every ambiguity letter to be distinct characters */
 static int ambig_options_distinct(const char *const *ambig) {
@@ -520,17 +509,9 @@ static int ambig_options_distinct(const char *const *ambig) {
     return 1;
 }
 
-/* Per cell-path records of a SA_KIND_RING region with ambiguous positions.  Paths of column x enumerate the substitutions of
- * the window s[x-1 .. x+k-2] with the LAST position varying fastest (expand_kmer), so with n(c) options for letter c,
- *   shared(x) = product of n over the first k-1 letters of the window = P(x) / n(last letter),
- * path p of column x and path q of column x-1 are a legal step (k-1 shared letters, path_checkLegal) iff
- *   q mod shared(x) == p / n(last letter of x):
- * the legal predecessors of p are q = j * shared(x) + p / n_last(x), j < n(first letter of x-1) (strided), and the legal
- * successors of q in column x+1 are the n_last(x+1) consecutive paths from (q mod shared(x+1)) * n_last(x+1).  The NULL
- * k-mer of column 0 is a legal neighbour of everything (path_checkLegal with a NULL k-mer). */
+/* Per cell-path records of a SA_KIND_RING region with ambiguous positions (sa_plan_rules.h); s: the region's first letter */
 static int fill_prec(sa_plan_t *pl, const sa_region_t *R, const char *s, const char *const *ambig) {
-    const int k = pl->model->k;
-    const int64_t lX = R->lX;
+    const int64_t k = pl->model->k, lX = R->lX;
     if (!pl->prec) {
         if (pl->borrowed) return SA_EINVAL; /* sized by sa_plan_build whenever a thread counted several paths */
         pl->prec = calloc((size_t) (pl->cap_pid > 0 ? pl->cap_pid : 1), sizeof(sa_prec_t));
@@ -546,37 +527,16 @@ static int fill_prec(sa_plan_t *pl, const sa_region_t *R, const char *s, const c
     const int32_t *poff = pl->poff + R->poff_off;
     sa_prec_t *pr = pl->prec + R->pid_off;
 #define NOPT(c) ((ambig && ambig[(unsigned char) (c)]) ? (int64_t) strlen(ambig[(unsigned char) (c)]) : 1)
-    /* column 0: the NULL k-mer; every path of column 1 is a successor */
-    {
-        int64_t P1 = lX >= 1 ? poff[2] - poff[1] : 0;
-        if (P1 > 255) return SA_EUNSUPPORTED;
-        pr[0].x = 0; pr[0].pred0 = -1; pr[0].succ0 = lX >= 1 ? poff[1] : -1;
-        pr[0].meta = (uint32_t) P1;
-    }
-    for (int64_t x = 1; x <= lX; x++) {
+    int rc = sa_prec_col0(poff, lX, &pr[0]);
+    for (int64_t x = 1; x <= lX && rc == SA_OK; x++) {
         const char *w = s + (x - 1);
+        sa_prec_col_t col;
+        rc = sa_prec_column(&col, poff, x, lX, x >= 2 ? NOPT(w[-1]) : 1, NOPT(w[0]), NOPT(w[k - 1]), x < lX ? NOPT(w[k]) : 1);
         const int64_t P = poff[x + 1] - poff[x];
-        const int64_t n_last = NOPT(w[k - 1]);
-        const int64_t shared = P / n_last;
-        int64_t npred = 1, stride = 0;
-        if (x >= 2) { npred = NOPT(w[-1]); stride = shared; }
-        int64_t nsucc = 0, shared_n = 1, n_last_n = 1;
-        if (x < lX) {
-            n_last_n = NOPT(w[k]);
-            shared_n = P / NOPT(w[0]);
-            nsucc = n_last_n;
-        }
-        if (npred > 255 || nsucc > 255 || stride > 65535) return SA_EUNSUPPORTED;
-        for (int64_t p = 0; p < P; p++) {
-            sa_prec_t *o = &pr[poff[x] + p];
-            o->x = (int32_t) x;
-            o->pred0 = (int32_t) (x >= 2 ? poff[x - 1] + p / n_last : 0);
-            o->succ0 = x < lX ? (int32_t) (poff[x + 1] + (p % shared_n) * n_last_n) : -1;
-            o->meta = (uint32_t) (stride << 16) | (uint32_t) (npred << 8) | (uint32_t) nsucc;
-        }
+        for (int64_t p = 0; p < P && rc == SA_OK; p++) pr[poff[x] + p] = sa_prec_path(&col, poff, p);
     }
 #undef NOPT
-    return SA_OK;
+    return rc;
 }
 
 static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc, const int64_t *ax, const int64_t *ay,
@@ -597,11 +557,11 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
     R->ev_off = job_ev_off + rc.y1;
 
     /* paths per x: cell x = 0 is the NULL k-mer (one path, id -1) */
-    GROW(pl, poff, n_poff, cap_poff, lX + 2, int32_t);
+    GROW(pl, poff, n_poff, cap_poff, sa_region_poffs(lX), int32_t);
     R->poff_off = pl->n_poff;
     R->pid_off = pl->n_pid;
     int32_t *poff = pl->poff + pl->n_poff;
-    pl->n_poff += lX + 2;
+    pl->n_poff += sa_region_poffs(lX);
     GROW(pl, pid, n_pid, cap_pid, 1, int32_t);
     pl->pid[pl->n_pid++] = -1;
     poff[0] = 0;
@@ -629,45 +589,29 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
     /* band */
     int64_t *lo = malloc(sizeof(int64_t) * (N + 1)), *hi = malloc(sizeof(int64_t) * (N + 1));
     int32_t *span3 = malloc(sizeof(int32_t) * (N + 1));
-    if (!lo || !hi || !span3) {
-        free(lo); free(hi); free(span3);
-        return SA_ENOMEM;
-    }
-    int rcode = sa_band_rows(ax, ay, na, lX, lY, p->diagonal_expansion, lo, hi);
-    if (rcode) {
-        free(lo); free(hi); free(span3);
-        return rcode;
-    }
-    if (pl->n_rows + N + 2 > pl->cap_rows) {
-        if (pl->borrowed) {
-            free(lo); free(hi); free(span3);
-            return SA_EINVAL; /* the counting pass undercounted */
-        }
+    int rcode = lo && hi && span3 ? sa_band_rows(ax, ay, na, lX, lY, p->diagonal_expansion, lo, hi) : SA_ENOMEM;
+    if (rcode) { free(lo); free(hi); free(span3); return rcode; }
+    const int64_t n_rows = sa_region_rows(N), n_pk = sa_region_pk_words(N);
+    if (pl->n_rows + n_rows > pl->cap_rows) {
+        if (pl->borrowed) { free(lo); free(hi); free(span3); return SA_EINVAL; } /* the counting pass undercounted */
         int64_t nc = pl->cap_rows ? pl->cap_rows * 2 : 4096;
-        while (nc < pl->n_rows + N + 2) nc *= 2;
+        while (nc < pl->n_rows + n_rows) nc *= 2;
         void *np_ = realloc(pl->rows, sizeof(sa_row_t) * (size_t) nc);
-        if (!np_) {
-            free(lo); free(hi); free(span3);
-            return SA_ENOMEM;
-        }
+        if (!np_) { free(lo); free(hi); free(span3); return SA_ENOMEM; }
         pl->rows = np_;
         pl->cap_rows = nc;
     }
     R->row_off = pl->n_rows;
     sa_row_t *rows = pl->rows + pl->n_rows;
-    pl->n_rows += N + 2; /* one sentinel row behind diagonal N (SA_KIND_RING: its offset closes the last diagonal) */
+    pl->n_rows += n_rows;
     poff = pl->poff + R->poff_off;
-    int64_t K = lY + (lY & 1) + 2;
+    const int64_t K = sa_band_K(lY);
     R->K = (int32_t) K;
     int64_t foff = 0, max_rowpaths = 0, span = 0;
-    double cf = 0;
-    /* register-kernel regions start every diagonal on a 128-byte boundary of its plane: a cache line then belongs to
-     * one store instruction of one diagonal and never has to be merged with the next diagonal's bytes */
-    int fast_ok = maxP == 1 && !(pl->flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC));
-    /* HDP emissions on the register kernels: the {y, slope} table is addressed with 32-bit byte offsets */
-    if (m->hdp != NULL && (m->hdp->grid_length < 2 || m->hdp->n_slots * m->hdp->grid_length * 16 >= SA_HDP_FAST_MAX_BYTES))
-        fast_ok = 0;
-    const int64_t row_align = fast_ok ? SA_FAST_ROW_ALIGN : 1;
+    double cf = 0, wide_cells = 0;
+    /* a region that may go to the register kernels starts every diagonal on a multiple of SA_FAST_ROW_ALIGN cells of its plane */
+    const int maybe_fast = maxP == 1 && !(pl->flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC)) && sa_hdp_plane_fits(m);
+    const int64_t row_align = maybe_fast ? SA_FAST_ROW_ALIGN : 1;
     for (int64_t d = 0; d <= N; d++) {
         int64_t w = (hi[d] - lo[d]) / 2 + 1;
         int64_t x0 = (d + lo[d]) / 2, xe = x0 + w; /* cells cover x0 .. xe-1 */
@@ -678,70 +622,34 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
         foff += (paths + row_align - 1) / row_align * row_align;
         if (paths > max_rowpaths) max_rowpaths = paths;
         if (d >= 1) cf += (double) paths;
-        /* widest window of (x-y+K)>>1 over three consecutive diagonals plus one neighbour each side */
-        int64_t uL = (lo[d] + K) >> 1, uR = uL + w - 1;
-        int64_t wl = uL - 1, wr = uR + 1;
-        for (int64_t b = 1; b <= 2 && d - b >= 0; b++) {
-            int64_t l2 = (lo[d - b] + K) >> 1, r2 = l2 + (hi[d - b] - lo[d - b]) / 2;
-            if (l2 < wl) wl = l2;
-            if (r2 > wr) wr = r2;
-        }
-        span3[d] = (int32_t) (wr - wl + 1); /* lanes needed to hold this diagonal, the two before it and one neighbour each side */
-        if (wr - wl + 1 > span) span = wr - wl + 1;
+        span3[d] = sa_span3_64(rows, d, K);
+        if (span3[d] > span) span = span3[d];
+        if (d >= 1 && span3[d] > 64) wide_cells += (double) w;
     }
     /* packed band words for the register kernels */
-    GROW(pl, pk, n_pk, cap_pk, N + 1 + SA_PK_PAD + 160, int32_t);
+    GROW(pl, pk, n_pk, cap_pk, n_pk, int32_t);
     R->pk_off = pl->n_pk;
     {
         int32_t *pk = pl->pk + pl->n_pk;
-        memset(pk, 0, sizeof(int32_t) * (size_t) (N + 1 + SA_PK_PAD + 160));
+        memset(pk, 0, sizeof(int32_t) * (size_t) n_pk);
         rows = pl->rows + R->row_off;
-        for (int64_t d = 0; d <= N; d++) {
-            int64_t uL = ((int64_t) rows[d].xmyL + K) >> 1;
-            int64_t w = rows[d].width;
-            int32_t word = (int32_t) ((w > SA_PK_WIDTH_MASK ? SA_PK_WIDTH_MASK : w) | ((uint32_t) uL << SA_PK_SHIFT));
-            if (span3[d] <= 64) word |= SA_PK_FWD;
-            if (span3[d + 2 <= N ? d + 2 : N] <= 64) word |= SA_PK_BWD;
-            pk[SA_PK_PAD + d] = word;
-        }
-        pl->n_pk += N + 1 + SA_PK_PAD + 160;
+        for (int64_t d = 0; d <= N; d++)
+            pk[SA_PK_PAD + d] = sa_pk_word(rows[d].width, (uint32_t) (((int64_t) rows[d].xmyL + K) >> 1), span3[d],
+                                           span3[d + 2 <= N ? d + 2 : N]);
+        pl->n_pk += n_pk;
     }
     R->f_cellpaths = foff + 1; /* last cell of the match plane: a -inf sentinel the backward kernel reads for lanes without a cell */
     R->max_rowpaths = (int32_t) max_rowpaths;
     R->slots = (int32_t) ((span + 63) / 64);
     if (span > pl->max_span) pl->max_span = span;
-    if (foff + 1 > SA_FAST_MAX_CELLS || ((lX + lY + K) >> 1) >= (1ll << (31 - SA_PK_SHIFT))) fast_ok = 0;
     rows[N + 1].xmyL = 0; rows[N + 1].width = 0; rows[N + 1].foff = foff;
-    /* ring kernels (sa_ring.inc): several paths per cell, or one path and a band mostly wider than a wave */
-    /* (HDP models: both read the emission plane k_emit_hdp_ring fills, one value per cell-path; same table limit as above) */
-    const int hdp_plane_ok = m->hdp == NULL ||
-                             !(m->hdp->grid_length < 2 || m->hdp->n_slots * m->hdp->grid_length * 16 >= SA_HDP_FAST_MAX_BYTES);
-    /* (the expectation pass: ring kernels for regions with several paths per cell under a Gaussian model -- k_bwd_ring<EXPECT> --,
-     * never for one-path regions, which keep the register kernels' expectation variant) */
-    const int expect_ = (pl->flags & SA_FLAG_EXPECT_INTERNAL) != 0;
-    /* (the two-distribution emission exists in the register kernels and the reference-ordered ones: a one-path region with a wide
-     * band stays a register-kernel region -- their in-kernel memory-resident path --, one with several paths per cell is not
-     * SA_KIND_FAST and sends the batch to the reference-ordered kernels, sa_hip.hip batch_prepare_body -- unless the batch asks for
-     * the ring and strip kernels' two-distribution instances, SA_FLAG_TWO_DIST_ALL_KERNELS: the routing of a MeanOnly model then) */
-    /* (such a batch's regions with several paths per cell: rows of up to SA_RING_WIDE_MAX_ROWPATHS, sa_internal.h -- a MeanOnly
-     * model's routing is what it was) */
-    const int64_t ring_max_rowpaths = (m->emission != 0 && (pl->flags & SA_FLAG_TWO_DIST_ALL_KERNELS) && maxP > 1 && !expect_ &&
-                                       m->hdp == NULL) ? SA_RING_WIDE_MAX_ROWPATHS : SA_RING_MAX_ROWPATHS;
-    int ring_ok = !(pl->flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC)) && hdp_plane_ok &&
-                  (m->emission == 0 || (pl->flags & SA_FLAG_TWO_DIST_ALL_KERNELS)) &&
-                  (!expect_ || (maxP > 1 && m->hdp == NULL)) &&
-                  max_rowpaths <= ring_max_rowpaths && foff + 1 <= SA_FAST_MAX_CELLS && ring_env_on() &&
-                  (maxP == 1 || (maxP <= 255 && ambig_options_distinct(ambig)));
-    int use_ring = 0;
-    if (ring_ok && maxP > 1) use_ring = 1;
-    if (ring_ok && maxP == 1 && fast_ok) {
-        double wide_cells = 0;
-        for (int64_t d = 1; d <= N; d++)
-            if (span3[d] > 64) wide_cells += (double) rows[d].width;
-        use_ring = wide_cells > SA_RING_WIDE_FRACTION * cf && ring_wide_env_on();
-    }
+    const sa_route_in_t route = {
+        .flags = pl->flags, .emission = m->emission, .hdp = m->hdp != NULL, .hdp_plane_fits = sa_hdp_plane_fits(m),
+        .ring_env = sa_ring_env_on(), .ring_wide_env = sa_ring_wide_env_on(), .ambig_distinct = maxP == 1 || ambig_options_distinct(ambig),
+        .max_p = maxP, .max_rowpaths = max_rowpaths, .cellpaths = foff, .lX = lX, .lY = lY, .K = K, .cf = cf, .wide_cells = wide_cells};
+    R->kind = sa_route_kind(&route);
+    const int use_ring = R->kind == SA_KIND_RING, fast_ok = R->kind == SA_KIND_FAST;
     if (use_ring) {
-        fast_ok = 0;
         for (int64_t d = 0; d <= N + 1; d++) { /* (g0 << 32) | offset: see sa_internal.h */
             int64_t g0 = d <= N ? (int64_t) poff[(d + lo[d]) / 2] : 0;
             rows[d].foff |= g0 << 32;
@@ -752,7 +660,6 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
         }
         pl->n_ring_regions++;
     }
-    R->kind = use_ring ? SA_KIND_RING : (fast_ok ? SA_KIND_FAST : SA_KIND_GENERIC);
     R->max_p = maxP; /* 1: the ring kernels skip the per-path records */
     if (fast_ok) pl->n_fast_regions++;
 
@@ -773,19 +680,17 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
         /* the diagonal a traceback starts on keeps all three forward planes: its total there -- forward state x end state --
          * is the backward sweep's candidate bound (k_spec_match, sa_hip.hip) */
         pl->pk[R->pk_off + SA_PK_PAD + d] |= SA_PK_FULL;
-        S->from = d - (at_end ? 0 : p->trace_back_diagonals + 1);
+        S->from = sa_seg_from(d, at_end, p->trace_back_diagonals);
         S->to = traced_to;
-        if (S->from <= S->to) { /* would violate traceBackDiagonals+1 < minDiagsBetweenTraceBack */
-            free(lo); free(hi); free(span3);
-            return SA_EINVAL;
-        }
+        /* (from <= to would violate traceBackDiagonals+1 < minDiagsBetweenTraceBack) */
+        if (S->from <= S->to) { free(lo); free(hi); free(span3); return SA_EINVAL; }
         for (int64_t e = S->to + 2; e <= S->start; e++) {
             int64_t x0 = (e + rows[e].xmyL) / 2;
             cb += (double) (poff[x0 + rows[e].width] - poff[x0]);
         }
         /* checkpoints: diagonals from, from-10, ... > to */
         S->ck_base = pl->n_cks;
-        int64_t nck = (S->from - S->to + SA_CKPT_EVERY - 1) / SA_CKPT_EVERY;
+        int64_t nck = sa_seg_n_ck(S->from, S->to);
         S->n_ck = (int32_t) nck;
         GROW(pl, cks, n_cks, cap_cks, nck, sa_ck_t);
         for (int64_t c = 0; c < nck; c++) {
@@ -797,10 +702,7 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
             ck->nB = e < S->start ? rows[e + 1].width : 0;
             pl->n_vbuf += ck->nA + ck->nB;
         }
-        /* measured: 0.54 pairs per diagonal at threshold 0.01 with Gaussian emissions; HDP densities as broad as the bundled
-         * model's leave the posteriors flat across the band (3-6 candidates per diagonal at threshold 0.1); overflow re-runs
-         * the pass with 4x */
-        int64_t cap = (m->hdp ? SA_CAND_PER_DIAG_HDP : SA_CAND_PER_DIAG) * (S->from - S->to + 32);   /* (the 32: short tracebacks at a read's end) */
+        int64_t cap = sa_seg_cand_cap(m->hdp != NULL, S->from, S->to);
         if (p->threshold <= 0.0) { /* everything passes: every cell-path of the posterior diagonals */
             cap = 64;
             for (int64_t e = S->to + 1; e <= S->from; e++) {
@@ -813,26 +715,16 @@ static int add_region(sa_plan_t *pl, int64_t job, const sa_job_t *jb, rect_t rc,
         S->cand_off = pl->n_cand;
         pl->n_cand += cap;
         S->bscratch_off = pl->n_bscratch;
-        /* the ring kernels keep backward rows in LDS (a wide ring's checkpoint sums: 6 rows of its capacity, k_bwd_ring<WIDE>) */
-        if (R->kind != SA_KIND_RING) pl->n_bscratch += 12 * (int64_t) max_rowpaths;
-        else if (max_rowpaths > SA_RING_MAX_ROWPATHS) pl->n_bscratch += 6 * (int64_t) SA_RING_WIDE_MAX_ROWPATHS;
+        pl->n_bscratch += sa_seg_bscratch(R->kind, max_rowpaths);
         traced_to = S->from;
     }
     R->n_seg = (int32_t) (pl->n_segs - R->seg_off);
     {   /* derived flags (the words behind diagonal N are zero) */
         int32_t *pk = pl->pk + R->pk_off + SA_PK_PAD;
-        for (int64_t d = 0; d <= N; d++) {
-            /* (the expectation pass reads all three forward states of every diagonal: impl/pairwiseAligner.c:1423-1443) */
-            if ((pk[d] & SA_PK_CK) || !(pk[d + 1] & SA_PK_FWD) || !(pk[d + 2] & SA_PK_FWD) || d + 2 > N ||
-                (pl->flags & SA_FLAG_EXPECT_INTERNAL))
-                pk[d] |= SA_PK_FULL;
-            if (d < N && (pk[d + 1] & SA_PK_FWD)) pk[d] |= SA_PK_FWD_MORE;
-            if (d >= 1 && (pk[d - 1] & SA_PK_BWD)) pk[d] |= SA_PK_BWD_MORE;
-        }
+        for (int64_t d = 0; d <= N; d++)
+            pk[d] |= sa_pk_derived(pk[d], pk[d - 1], pk[d + 1], pk[d + 2], d, N, (pl->flags & SA_FLAG_EXPECT_INTERNAL) != 0);
     }
-    free(lo);
-    free(hi);
-    free(span3);
+    free(lo); free(hi); free(span3);
     pl->jobs[job].cells_fwd += cf;
     pl->jobs[job].cells_bwd += cb;
     pl->cells_fwd += cf;
@@ -892,24 +784,26 @@ static int fill_xc(sa_plan_t *pl) {
     return SA_OK;
 }
 
+/* anchors inside the matrix and strictly increasing */
+static int job_anchors_ok(const sa_job_t *jb, int64_t lX, int64_t lY) {
+    for (int64_t i = 0; i < jb->n_anchors; i++)
+        if (jb->anchor_x[i] < 0 || jb->anchor_y[i] < 0 || jb->anchor_x[i] >= lX || jb->anchor_y[i] >= lY ||
+            (i > 0 && (jb->anchor_x[i] <= jb->anchor_x[i - 1] || jb->anchor_y[i] <= jb->anchor_y[i - 1])))
+            return 0;
+    return 1;
+}
+
 /* plans job jb as job number j of pl (appends its regions, rows, segments ... to pl's arrays) */
 static int plan_job(sa_plan_t *pl, int64_t j, const sa_job_t *jb, const char *const *ambig) {
     const sa_model_t *m = pl->model;
     const sa_params_t *p = &pl->params;
-    if (!jb->ref || jb->ref_len < 0 || jb->n_events < 0 || jb->n_anchors < 0 || (jb->n_events && !jb->events) ||
-        (jb->n_anchors && (!jb->anchor_x || !jb->anchor_y)) || !(jb->var > 0.0) ||
-        (jb->ends & ~(SA_JOB_LEFT_END_NOT_RAGGED | SA_JOB_RIGHT_END_NOT_RAGGED)))
-        return SA_EINVAL;
+    if (!sa_job_header_ok(jb)) return SA_EINVAL;
     /* alignmentHasRaggedLeftEnd / alignmentHasRaggedRightEnd of getAlignedPairsUsingAnchors (impl/pairwiseAligner.c:2052-2080);
      * signalMachine passes 1, 1 (impl/signalMachine.c:436-437) = a zeroed `ends` */
     const int ragged_l = !(jb->ends & SA_JOB_LEFT_END_NOT_RAGGED), ragged_r = !(jb->ends & SA_JOB_RIGHT_END_NOT_RAGGED);
-    int64_t lX = jb->ref_len == 0 ? 0 : jb->ref_len - (m->k - 1); /* sequence_correctSeqLength */
-    if (lX < 0) lX = 0;
+    const int64_t lX = sa_job_lX(jb->ref_len, m->k);
     int64_t lY = jb->n_events;
-    for (int64_t i = 0; i < jb->n_anchors; i++)
-        if (jb->anchor_x[i] < 0 || jb->anchor_y[i] < 0 || jb->anchor_x[i] >= lX || jb->anchor_y[i] >= lY ||
-            (i > 0 && (jb->anchor_x[i] <= jb->anchor_x[i - 1] || jb->anchor_y[i] <= jb->anchor_y[i - 1])))
-            return SA_EBAND;
+    if (!job_anchors_ok(jb, lX, lY)) return SA_EBAND;
     /* events: keep only the mean column */
     if (pl->borrowed) {
         if (pl->n_ev + lY > pl->cap_ev) return SA_EINVAL; /* the counting pass undercounted */
@@ -992,8 +886,9 @@ static void *plan_worker(void *arg) {
 /* Counting pass of the threaded planner: how many entries of the big arrays (band rows, packed words, path offsets and
  * ids, emission constants, events) a range of jobs will occupy -- exactly, so that every thread can then write its
  * sub-plan straight into its slice of the final arrays (copying several hundred MB of sub-plans and handing them back
- * to the kernel cost more than planning them).  Follows plan_job / add_region; a job those would reject counts as
- * whatever it counts, the planning pass then fails with its error code. */
+ * to the kernel cost more than planning them).  Follows plan_job / add_region.  Counting stops at a job plan_job rejects
+ * on its header or anchors: plan_job makes the same two checks before it touches an array, plan_worker plans the jobs in
+ * the same order and stops there with plan_job's code, so the jobs behind it are never planned. */
 static void *count_worker(void *arg) {
     plan_worker_t *w = arg;
     const sa_model_t *m = w->pl->model;
@@ -1004,16 +899,10 @@ static void *count_worker(void *arg) {
     w->rc = SA_OK;
     for (int64_t j = 0; j < w->n; j++) {
         const sa_job_t *jb = &w->jobs[j];
-        if (!jb->ref || jb->ref_len < 0 || jb->n_events < 0 || jb->n_anchors < 0 || (jb->n_events && !jb->events) ||
-            (jb->n_anchors && (!jb->anchor_x || !jb->anchor_y)))
-            return NULL; /* plan_job rejects it */
-        int64_t lX = jb->ref_len == 0 ? 0 : jb->ref_len - (m->k - 1);
-        if (lX < 0) lX = 0;
+        if (!sa_job_header_ok(jb)) return NULL;
+        const int64_t lX = sa_job_lX(jb->ref_len, m->k);
         const int64_t lY = jb->n_events;
-        for (int64_t i = 0; i < jb->n_anchors; i++)
-            if (jb->anchor_x[i] < 0 || jb->anchor_y[i] < 0 || jb->anchor_x[i] >= lX || jb->anchor_y[i] >= lY ||
-                (i > 0 && (jb->anchor_x[i] <= jb->anchor_x[i - 1] || jb->anchor_y[i] <= jb->anchor_y[i - 1])))
-                return NULL;
+        if (!job_anchors_ok(jb, lX, lY)) return NULL;
         c->cap_ev += lY;
         rect_t *rects = malloc(sizeof(rect_t) * (size_t) (jb->n_anchors + 2));
         if (!rects) { w->rc = SA_ENOMEM; return NULL; }
@@ -1022,9 +911,9 @@ static void *count_worker(void *arg) {
         for (int64_t i = 0; i < nr; i++) {
             const int64_t rX = rects[i].x2 - rects[i].x1, rY = rects[i].y2 - rects[i].y1, N = rX + rY;
             if (N == 0) continue;
-            c->cap_rows += N + 2;
-            c->cap_pk += N + 1 + SA_PK_PAD + 160;
-            c->cap_poff += rX + 2;
+            c->cap_rows += sa_region_rows(N);
+            c->cap_pk += sa_region_pk_words(N);
+            c->cap_poff += sa_region_poffs(rX);
             int64_t paths = 1; /* the NULL k-mer of x = 0 */
             for (int64_t x = 1; x <= rX; x++) {
                 const unsigned char *s = (const unsigned char *) jb->ref + rects[i].x1 + (x - 1);
@@ -1107,10 +996,7 @@ static int plan_threads(int64_t n_jobs) {
 int sa_plan_build(sa_plan_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs, int64_t n_jobs,
                   const char *const *ambig, unsigned flags, int64_t chunk_budget) {
     if (!out || !m || !p || (!jobs && n_jobs > 0) || n_jobs < 0) return SA_EINVAL;
-    if (p->diagonal_expansion < 0 || p->diagonal_expansion % 2 != 0 || p->trace_back_diagonals < 1 ||
-        p->min_diags_between_trace_back < 2 || p->trace_back_diagonals + 1 >= p->min_diags_between_trace_back ||
-        !(p->threshold >= 0.0 && p->threshold <= 1.0))
-        return SA_EINVAL; /* the asserts of impl/pairwiseAligner.c:1460-1464, :1358-1359 */
+    if (!sa_params_plannable(p)) return SA_EINVAL;
     const int T = plan_threads(n_jobs);
     sa_plan_t *pl = NULL;
     int rc = SA_OK;
@@ -1187,9 +1073,8 @@ int sa_plan_build(sa_plan_t **out, const sa_model_t *m, const sa_params_t *p, co
             for (int t = 0; t < T; t++) want_prec |= W[t].pl->prec_cap != 0;
             want_prec = want_prec && !(flags & (SA_FLAG_EXACT | SA_FLAG_FORCE_GENERIC)) &&
                         (!(flags & SA_FLAG_EXPECT_INTERNAL) || m->hdp == NULL) &&
-                        (m->hdp == NULL ||   /* (HDP regions take the ring kernels too when the emission plane can be built) */
-                         !(m->hdp->grid_length < 2 || m->hdp->n_slots * m->hdp->grid_length * 16 >= SA_HDP_FAST_MAX_BYTES)) &&
-                        ring_env_on();
+                        sa_hdp_plane_fits(m) &&   /* (HDP regions take the ring kernels too when the emission plane can be built) */
+                        sa_ring_env_on();
             if (want_prec) {
                 pl->prec = get(sizeof(sa_prec_t) * (size_t) (ti > 0 ? ti : 1));
                 if (!pl->prec) rc = SA_ENOMEM;

@@ -35,6 +35,11 @@ def test_device_plan_equals_host_plan(monkeypatch):
     jobs = _mixed_jobs()
     for params in (sa.default_params(), sa.default_params(expansion=20, trace_back=40), sa.default_params(threshold=0.5, expansion=4)):
         assert sa.dplan_compare(pm, params, jobs) == 0
+    # N + 2 * expansion + 4 >= 2^30: the device evaluates the band with the 64-bit instance of the rules (sa_plan_rules.h), which
+    # no read the result records can name reaches otherwise -- the two smallest reads: make_read(900, 400) without anchors and the
+    # 4-event one
+    assert len(jobs[14]["ax"]) == 0 and len(jobs[15]["events"]) == 4
+    assert sa.dplan_compare(pm, sa.default_params(expansion=2**30, trace_back=100, min_diags=1000), jobs[14:16]) == 0
     for env in ({"SA_RING_WIDE": "0"}, {"SA_RING": "0"}, {"SA_F_BUDGET_CELLPATHS": "300000"}):
         for k_, v_ in env.items():
             monkeypatch.setenv(k_, v_)
