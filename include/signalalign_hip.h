@@ -735,6 +735,25 @@ int sa_mixture_assign(const sa_mixture_fit_t *fit, double canonical_mean, int32_
  * 1..16: SA_EINVAL.  Host only. */
 int sa_motif_kmer_pairs(int k, const char *canonical_motif, const char *modified_motif, const char *alphabet, char **pairs_out,
                         int64_t *n_out);
+/* ---- Gaussian kernel density estimate over a k-mer's rows (plot_kmer_distribution, src/signalalign/hiddenMarkovModel.py:654-773)
+ * KernelDensity(kernel="gaussian", bandwidth=h).score_samples (sklearn's default rtol = atol = 0) over x_i = descaled_units_i / 1e6,
+ * the n rows of one (strand, k-mer), at any set of query points (not necessarily a linspace, nor sorted):
+ *   log_density(q) = logsumexp_i(-((q - x_i) / h)^2 / 2) - log n - log h - log(2 pi) / 2
+ * evaluated in fp64 on the device as: r = 1 / h; z_i = (q - x_i) r; e_i = -0.5 (z_i z_i); E = max_i e_i (the nearest row);
+ * S = sum of exp(e_i - E) over the rows with e_i - E >= -64; (E + log S) - ((log n + log h) + log(2 pi) / 2).
+ *   order   S is one accumulator per query point starting at 0.0, the rows added in ascending order of descaled_units (equal
+ *           units give equal terms).  The value for one (k-mer, q, h) depends on the table's contents only -- not on the other
+ *           jobs or points of the call, on chunking, or on how the table was filled: equal tables give equal bits
+ *   cut     rows more than 64 below the largest exponent are not added: less than n exp(-64) < 7e-19 of a sum that is >= 1
+ *   finite  E is taken out before exp: finite for every q for which ((q - x_i) / h)^2 does not overflow
+ * kmer_ids NULL: every k-mer of the model (n_jobs is not read; out: n_kmers rows).  log_density_out: n_jobs x n_x doubles in ordinary
+ * host memory, moved in chunks through the library's device scratch.  A k-mer without rows: n_rows_out 0 and a row of -INFINITY.
+ * Checked before any device use -- SA_EINVAL: NULL t / x / log_density_out, strand outside 0..1, n_jobs < 0, n_x < 1, a bandwidth
+ * that is not finite or <= 0, a non-finite x, a k-mer id outside the model; n_jobs == 0 succeeds and writes nothing.  A k-mer
+ * with 2^32 rows or more: SA_EUNSUPPORTED.  kernel_ms_out (may be NULL): HIP-event time of the gather, sort and KDE kernels. */
+int sa_kmer_table_kde(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs, const double *x, int64_t n_x,
+                      double bandwidth, double *log_density_out /* n_jobs x n_x */, int64_t *n_rows_out /* n_jobs, may be NULL */,
+                      double *kernel_ms_out /* may be NULL */);
 /* Python's repr of a double (shortest round-trip digits); `out` needs 32 bytes; returns the length (test hook and writer) */
 int sa_format_py_repr(char *out, double v);
 /* the device's "%f" rounding of v[0 .. n) into units of 1e-6 and the negative-zero flag (test hook: must equal the host's,
@@ -962,6 +981,22 @@ int sa_hdp_state_distance_pairs(const sa_hdp_state_t *s, int metric, const int64
 /* compare_hdp_distrs (:2809-2842): s1's grid is the master, s2's densities are interpolated on it (no shortcut for equal ids) */
 int sa_hdp_state_compare(const sa_hdp_state_t *s1, const int64_t *dp1, const sa_hdp_state_t *s2, const int64_t *dp2,
                          int64_t n, int metric, int device, double *out);
+/* An HDP's distributions against a Gaussian table (get_kl_divergence / get_hellinger_distance / get_median_delta /
+ * compare_distributions, src/signalalign/hiddenMarkovModel.py:775-837).  Per entry p is the DP's stored posterior row on the state's
+ * own grid g and q = exp(-((g - mean) / sd)^2 / 2) / sqrt(2 pi) / sd (scipy's norm.pdf):
+ *   kl_bits     scipy.stats.entropy(pk=p, qk=q, base=2): p and q divided by their sums, sum of rel_entr, divided by log 2;
+ *               rel_entr(a, b) = a log1p((a - b) / b) for 0.5 < a / b < 2, a log(a / b) while the quotient is a normal number,
+ *               a (log a - log b) when it under- or overflows; 0 for a = 0, b >= 0; +inf otherwise (a > 0, b = 0)
+ *   hellinger   hellinger2 (:1119-1120): ||sqrt(p) - sqrt(q)||_2 / sqrt(2) on the values as they are (not normalised)
+ *   mode_delta  |g[first argmax p] - mean|
+ *   status      0: kl_bits is finite; 1: the DP is not observed (the Python reads an empty row and returns None; no ancestor stands
+ *               in; the fields are 0); 2: kl_bits is not finite (left in place; the other two fields are valid)
+ * One wave per entry on the device; every sum is one accumulator over the grid points in grid order.  Checked first -- SA_EINVAL:
+ * a NULL array, n < 0, an id outside [0, num_dps), a mean that is not finite, an sd that is not finite or <= 0; then SA_ESTATE
+ * unless the splines are finalised; n == 0 succeeds and writes nothing; then SA_ENODEVICE without a GPU. */
+typedef struct sa_hdp_gauss_cmp { double kl_bits, hellinger, mode_delta; int32_t status, pad; } sa_hdp_gauss_cmp_t;
+int sa_hdp_state_vs_gaussian(const sa_hdp_state_t *s, const int64_t *dp_ids, int64_t n, const double *mean, const double *sd,
+                             int device, sa_hdp_gauss_cmp_t *out, double *kernel_ms_out);
 /* get_nanopore_hdp_alphabet (impl/nanopore_hdp.c): the model's alphabet, NUL-terminated, into at least 64 bytes; k-mer ids count
  * in its order (sa_hdp_state_kmer_dp) */
 int sa_hdp_state_alphabet(const sa_hdp_state_t *s, char *alphabet_out);

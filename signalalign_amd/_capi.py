@@ -134,12 +134,12 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_plan_check_path_records", "sa_dplan_compare",
            "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
-           "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet",
+           "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet", "sa_hdp_state_vs_gaussian",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
            "sa_hmm_load_into_model", "sa_model_transitions10",
            "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
-           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
+           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_kmer_table_kde", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
            "sa_version", "sa_free"]
 
 
@@ -302,6 +302,7 @@ def lib():
     L.sa_kmer_table_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, dp]
     L.sa_kmer_table_mixture.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp, C.c_void_p, dp]
     L.sa_kmer_table_mixture_start.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp]
+    L.sa_kmer_table_kde.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, dp, C.c_int64, C.c_double, dp, ip, dp]
     L.sa_mixture_assign.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
     L.sa_motif_kmer_pairs.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), ip]
     L.sa_model_write_trained.argtypes = [C.c_char_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_char_p]
@@ -346,6 +347,7 @@ def lib():
     L.sa_hdp_state_distance_pairs.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_int64, C.c_int, dp]
     L.sa_hdp_state_compare.argtypes = [C.c_void_p, ip, C.c_void_p, ip, C.c_int64, C.c_int, C.c_int, dp]
     L.sa_hdp_state_alphabet.argtypes = [C.c_void_p, C.c_char_p]
+    L.sa_hdp_state_vs_gaussian.argtypes = [C.c_void_p, ip, C.c_int64, dp, dp, C.c_int, C.c_void_p, dp]
     _LIB = L
     return L
 
@@ -1357,6 +1359,21 @@ class HdpState:
         _chk(lib().sa_hdp_state_compare(self._h, _ip(a), other._h, _ip(b), len(a), int(metric), device, _dp(out)), "sa_hdp_state_compare")
         return out[:len(a)]
 
+    def vs_gaussian(self, dp_ids, mean, sd, device=0, stats=None):
+        """sa_hdp_state_vs_gaussian: structured array (HDP_GAUSS_CMP_DTYPE), entry i the stored distribution of DP dp_ids[i]
+        against the normal density (mean[i], sd[i]) on the state's grid (GPU).  stats (a dict): kernel_ms"""
+        ids = np.ascontiguousarray(dp_ids, dtype=np.int64).ravel()
+        m, s = np.ascontiguousarray(mean, dtype=np.float64).ravel(), np.ascontiguousarray(sd, dtype=np.float64).ravel()
+        if not len(ids) == len(m) == len(s):
+            raise SaError(-1, "vs_gaussian: one mean and one sd per DP id")
+        out = np.zeros(max(len(ids), 1), dtype=HDP_GAUSS_CMP_DTYPE)
+        ms = C.c_double(0.0)
+        _chk(lib().sa_hdp_state_vs_gaussian(self._h, _ip(ids), len(ids), _dp(m), _dp(s), device, out.ctypes.data, C.byref(ms)),
+             "sa_hdp_state_vs_gaussian")
+        if stats is not None:
+            stats["kernel_ms"] = ms.value
+        return out[:len(ids)]
+
     def distr_sample(self, device=0):
         """sa_hdp_state_distr_sample: what one sample of this state adds to every observed DP's collector (GPU)"""
         out = np.zeros((int(self.info.n_observed), int(self.info.grid_length)), dtype=np.float64)
@@ -1366,6 +1383,7 @@ class HdpState:
 
 HDP_LAYOUT_FLAT, HDP_LAYOUT_MULTISET, HDP_LAYOUT_MIDDLE_NTS, HDP_LAYOUT_COMPOSITION, HDP_LAYOUT_GROUP_MULTISET = 0, 1, 2, 3, 4
 HDP_METRIC_KL, HDP_METRIC_HELLINGER, HDP_METRIC_L2, HDP_METRIC_SHANNON_JENSEN = 0, 1, 2, 3
+HDP_GAUSS_CMP_DTYPE = np.dtype([("kl_bits", "<f8"), ("hellinger", "<f8"), ("mode_delta", "<f8"), ("status", "<i4"), ("pad", "<i4")])
 
 
 def hdp_distances(grid, rows, metric, device=0, stats=None):
@@ -1515,6 +1533,24 @@ class KmerTable:
         ids, nj, p, idp = self._mixture_args(kmer_ids, n_components, 1, 0.0, reg_covar)
         out = np.zeros((nj, 3, int(n_components)), dtype=np.float64)
         _chk(lib().sa_kmer_table_mixture_start(self._h, int(strand), idp, nj, C.byref(p), _dp(out)), "sa_kmer_table_mixture_start")
+        return out
+
+    def kde(self, x, kmer_ids=None, bandwidth=0.5, strand=0, info=None):
+        """sa_kmer_table_kde: the log density of a Gaussian kernel density estimate over each k-mer's rows at the query points x,
+        n_jobs x len(x), one row per k-mer id of `kmer_ids` (None: every k-mer of the model); -inf for a k-mer without rows.
+        info (a dict): kernel_ms, n_rows (per job)"""
+        alpha, k = self._model.alphabet()
+        ids = None if kmer_ids is None else np.ascontiguousarray(kmer_ids, dtype=np.int32).ravel()
+        nj = len(alpha) ** k if ids is None else len(ids)
+        q = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        out = np.empty((nj, len(q)), dtype=np.float64)
+        n_rows = np.zeros(max(nj, 1), dtype=np.int64)
+        kms = C.c_double()
+        _chk(lib().sa_kmer_table_kde(self._h, int(strand), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), nj,
+                                     _dp(q), len(q), float(bandwidth), _dp(out), _ip(n_rows), C.byref(kms)), "sa_kmer_table_kde")
+        if info is not None:
+            info["kernel_ms"] = kms.value
+            info["n_rows"] = n_rows[:nj]
         return out
 
     def close(self):

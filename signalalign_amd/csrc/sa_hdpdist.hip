@@ -4,6 +4,8 @@
 //                      (:2693-2710), l2_distance (:2720-2738), shannon_jensen_distance (:2748-2767)
 //   k_hdp_dist_pairs   the same point functions for a list of pairs (get_dir_proc_distance :2614-2636, compare_hdp_distrs :2809-2842)
 //   k_hdp_density      dir_proc_density (:2588-2612) = max(0, grid_spline_interp (impl/hdp_math_utils.c:471-495))
+//   k_hdp_vs_gauss     a DP's posterior row against a normal density: scipy's entropy in bits, hellinger2 and the distance of the
+//                      mode from the mean (src/signalalign/hiddenMarkovModel.py:775-837), one wave per entry
 // One thread owns a pair from the first grid point to the last: the trapezoid sum starts at 0.0 and adds 0.5 * (left + right) * dx
 // in grid order, as the reference does, and the point functions are the reference's expressions term for term.  Built with
 // -ffp-contract=off like everything else; no clamping and no special cases, so a zero density is a NaN for the two logarithmic
@@ -170,6 +172,80 @@ __global__ __launch_bounds__(256) void k_hdp_density(const double *__restrict__ 
     const size_t off = (size_t) row_of[d] * (size_t) grid_length;
     const double interp = spline_interp(qx[q], x, post + off, slope + off, grid_length);
     out[t] = interp > 0.0 ? interp : 0.0;
+}
+
+// ---- an HDP distribution against a normal density (hiddenMarkovModel.py:775-837) ---------------------------------------------------------
+// get_kl_divergence / get_hellinger_distance / get_median_delta for one DP: p is its stored posterior row on the state's own grid g,
+// q = exp(-((g - mean) / sd)^2 / 2) / sqrt(2 pi) / sd (scipy's norm.pdf, operation for operation).
+//   kl_bits     scipy.stats.entropy(pk=p, qk=q, base=2): both divided by their sums, the sum of rel_entr, divided by log(2)
+//   hellinger   hellinger2 (:1119-1120) on the values as they are: ||sqrt(p) - sqrt(q)|| / sqrt(2)
+//   mode_delta  |g[first argmax p] - mean|
+// One wave per entry: the lanes evaluate 64 grid points at a time (exp, log, sqrt), lane 0 adds them up in grid order, one
+// accumulator per sum started at 0.0 (scipy adds pairwise: the restatement's sequential sum is within 1.5e-15 of it, relative).
+// scipy.special.rel_entr (1.15: special/_convex_analysis.pxd)
+__device__ __forceinline__ double rel_entr(double a, double b) {
+    if (isnan(a) || isnan(b)) return NAN;
+    if (a <= 0.0 || b <= 0.0) return (a == 0.0 && b >= 0.0) ? 0.0 : INFINITY;
+    const double ratio = a / b;
+    if (0.5 < ratio && ratio < 2.0) return a * log1p((a - b) / b);               // (close together: more accurate)
+    if (2.2250738585072014e-308 < ratio && ratio < INFINITY) return a * log(ratio);
+    return a * (log(a) - log(b));                                                 // (the quotient under- or overflows, or is subnormal)
+}
+
+__device__ __forceinline__ double norm_pdf(double g, double mean, double sd) {
+    const double z = (g - mean) / sd;
+    return exp(-(z * z) / 2.0) / 2.5066282746310002 / sd;
+}
+
+__global__ __launch_bounds__(64) void k_hdp_vs_gauss(const double *__restrict__ grid, int grid_length, const double *__restrict__ post,
+                                                     const long long *__restrict__ row_of, const double *__restrict__ mean,
+                                                     const double *__restrict__ sd, sa_hdp_gauss_cmp_t *__restrict__ out) {
+    __shared__ double s_p[64], s_q[64], s_v[64], s_sum[2];
+    const long long e = blockIdx.x, row = row_of[e];
+    const int lane = threadIdx.x;
+    sa_hdp_gauss_cmp_t R;
+    R.kl_bits = 0.0; R.hellinger = 0.0; R.mode_delta = 0.0; R.status = 0; R.pad = 0;
+    if (row < 0) {   // not observed: the Python reads an empty row and returns None
+        R.status = 1;
+        if (lane == 0) out[e] = R;
+        return;
+    }
+    const double *p = post + (size_t) row * (size_t) grid_length;
+    const double mu = mean[e], sg = sd[e];
+    double sum_p = 0.0, sum_q = 0.0, sum_h = 0.0, sum_kl = 0.0, best = -INFINITY;
+    int arg = 0;
+    for (int g0 = 0; g0 < grid_length; g0 += 64) {
+        const int c = grid_length - g0 < 64 ? grid_length - g0 : 64;
+        if (lane < c) {
+            const double pv = p[g0 + lane], qv = norm_pdf(grid[g0 + lane], mu, sg), diff = sqrt(pv) - sqrt(qv);
+            s_p[lane] = pv; s_q[lane] = qv; s_v[lane] = diff * diff;
+        }
+        __syncthreads();
+        if (lane == 0)
+            for (int i = 0; i < c; i++) {
+                sum_p += s_p[i]; sum_q += s_q[i]; sum_h += s_v[i];
+                if (s_p[i] > best) { best = s_p[i]; arg = g0 + i; }
+            }
+        __syncthreads();
+    }
+    if (lane == 0) { s_sum[0] = sum_p; s_sum[1] = sum_q; }
+    __syncthreads();
+    sum_p = s_sum[0]; sum_q = s_sum[1];
+    for (int g0 = 0; g0 < grid_length; g0 += 64) {
+        const int c = grid_length - g0 < 64 ? grid_length - g0 : 64;
+        if (lane < c) s_v[lane] = rel_entr(p[g0 + lane] / sum_p, norm_pdf(grid[g0 + lane], mu, sg) / sum_q);
+        __syncthreads();
+        if (lane == 0)
+            for (int i = 0; i < c; i++) sum_kl += s_v[i];
+        __syncthreads();
+    }
+    if (lane == 0) {
+        R.kl_bits = sum_kl / 0.6931471805599453;
+        R.hellinger = sqrt(sum_h) / 1.4142135623730951;
+        R.mode_delta = fabs(grid[arg] - mu);
+        R.status = isfinite(R.kl_bits) ? 0 : 2;
+        out[e] = R;
+    }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
@@ -469,4 +545,42 @@ extern "C" int sa_hdp_state_compare(const sa_hdp_state_t *s1, const int64_t *dp1
     if ((rc = densities_on_device(s2, r2, (const double *) d_grid.p, G, d_second))) return rc;
     return pairs_from_device(metric, (const double *) d_grid.p, G, (const double *) d_post.p, (const long long *) d_r1.p,
                              (const double *) d_second.p, nullptr, n, out, nullptr);
+}
+
+extern "C" int sa_hdp_state_vs_gaussian(const sa_hdp_state_t *s, const int64_t *dp_ids, int64_t n, const double *mean, const double *sd,
+                                        int device, sa_hdp_gauss_cmp_t *out, double *kernel_ms_out) {
+    if (!s || !dp_ids || !mean || !sd || !out || n < 0 || n > 0x7fffffffll) return SA_EINVAL;
+    for (int64_t i = 0; i < n; i++)
+        if (dp_ids[i] < 0 || dp_ids[i] >= s->num_dps || !std::isfinite(mean[i]) || !std::isfinite(sd[i]) || !(sd[i] > 0.0)) return SA_EINVAL;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    int rc = check_state(s);
+    if (rc) return rc;
+    if (n == 0) return SA_OK;
+    if ((rc = use_device(device))) return rc;
+    std::vector<long long> rows((size_t) n);   // (no ancestor stands in for a DP that is not observed)
+    for (int64_t i = 0; i < n; i++) rows[(size_t) i] = s->observed[dp_ids[i]] ? (long long) s->row_of_dp[dp_ids[i]] : -1;
+    DevBuf d_grid, d_post, d_rows, d_mean, d_sd, d_out;
+    if ((rc = d_grid.put(s->grid, sizeof(double) * (size_t) s->grid_length)) ||
+        (rc = d_post.put(s->post, sizeof(double) * (size_t) s->n_observed * (size_t) s->grid_length)) ||
+        (rc = d_rows.put(rows.data(), sizeof(long long) * rows.size())) || (rc = d_mean.put(mean, sizeof(double) * (size_t) n)) ||
+        (rc = d_sd.put(sd, sizeof(double) * (size_t) n)) || (rc = d_out.alloc(sizeof(sa_hdp_gauss_cmp_t) * (size_t) n)))
+        return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) (void) hipEventDestroy(e0);
+        return SA_ENODEVICE;
+    }
+    (void) hipEventRecord(e0, 0);
+    hipLaunchKernelGGL(k_hdp_vs_gauss, dim3((unsigned) n), dim3(64), 0, 0, (const double *) d_grid.p, (int) s->grid_length,
+                       (const double *) d_post.p, (const long long *) d_rows.p, (const double *) d_mean.p, (const double *) d_sd.p,
+                       (sa_hdp_gauss_cmp_t *) d_out.p);
+    (void) hipEventRecord(e1, 0);
+    float ms = 0.f;
+    const bool ok = hipGetLastError() == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+                    hipMemcpy(out, d_out.p, sizeof(sa_hdp_gauss_cmp_t) * (size_t) n, hipMemcpyDeviceToHost) == hipSuccess;
+    (void) hipEventDestroy(e0);
+    (void) hipEventDestroy(e1);
+    if (!ok) { (void) hipGetLastError(); return SA_ENODEVICE; }
+    if (kernel_ms_out) *kernel_ms_out = (double) ms;
+    return SA_OK;
 }

@@ -26,6 +26,8 @@
 //                                        per pass) of the median and of the median absolute deviation
 //   k_kt_mixture<K> / k_kt_mix_gather    one block per (k-mer, K): a K-component Gaussian mixture by EM over the k-mer's rows
 //                                        (mixture_model.py:42-186; see the section further down)
+//   k_kt_kde<SKIP> / k_kt_kde_gather     one block per (k-mer, tile of 512 query points): the log density of a Gaussian kernel density
+//                                        estimate over the k-mer's rows (hiddenMarkovModel.py:654-773; see the section further down)
 // Within a k-mer's segment rows lie in arrival order; the keys are unique, so sa_kmer_table_rows sorts them on the host and
 // every statistic is independent of the order.  Scratch comes from the library's caching allocator.
 #include <hip/hip_runtime.h>
@@ -1317,6 +1319,245 @@ extern "C" int sa_motif_kmer_pairs(int k, const char *canonical_motif, const cha
     *pairs_out = o;
     *n_out = (int64_t) pairs.size();
     return SA_OK;
+}
+
+// ---- Gaussian kernel density estimate over a k-mer's descaled event means (hiddenMarkovModel.py:654-773) -------------------------
+// plot_kmer_distribution fits sklearn's KernelDensity(kernel="gaussian", bandwidth=h) to the rows of one k-mer and draws
+// exp(score_samples(x)); here score_samples (rtol = atol = 0) for any set of jobs and query points, in fp64.  x_i = units_i / 1e6.
+//   definition r = 1 / h (one correctly rounded division); for a query point q: d_i = q - x_i, z_i = d_i r, e_i = -0.5 (z_i z_i);
+//              E = the largest e_i (the nearest row's, found as min |d_i|: every operation is monotone in |d_i|);
+//              S = sum of exp(e_i - E) over the rows with e_i - E >= -KT_KDE_CUT;
+//              log density = (E + log S) - ((log n + log h) + log(2 pi) / 2)
+//   order      S is ONE accumulator per query point, started at 0.0, the rows added in ascending order of their units (equal units
+//              give equal terms, so ties need no rule).  A segment lies in arrival order, so every job's units are first copied and
+//              sorted (rocPRIM's segmented radix sort); the value of a (k-mer, q, h) is therefore a function of the table's contents
+//              only: not of the other jobs or points of the call, of the chunking, or of how the table was filled
+//   cut        a row further than KT_KDE_CUT = 64 below the largest exponent is not added; it is part of the definition and is
+//              tested per (row, point), so it does not depend on tiling.  What it leaves out is less than n exp(-64) of a sum that
+//              is at least 1: below 7e-19 for the n < 2^32 a job may have, less than a hundredth of an ulp.  The test is also what
+//              makes the kernel fast: the loop is bound by fp64 exp, and a wave whose 64 adjacent points all fail it for a row
+//              branches around the exp (SA_KDE_NO_SKIP=1, a measurement hook, evaluates every exp and multiplies by 0 or 1: same bits)
+//   finite     E is subtracted before exp, so the result is finite for every q for which ((q - x) r)^2 does not overflow
+//   shape      one work-group of 256 threads per (job, tile of 512 query points); a thread owns points t and t + 256 of the tile in
+//              registers, so each of its two slots is 64 adjacent points per wave.  The sorted rows go through LDS as doubles in
+//              chunks of KT_KDE_LDS_ROWS (16 KiB) and are read as broadcasts; two sweeps: min |d|, then the sum
+//   output     jobs are taken in chunks whose n_jobs x n_x block fits a device slab (8 M doubles; SA_KDE_SLAB: a test and
+//              measurement hook); each chunk is gathered, sorted, evaluated and copied to the caller's ordinary host memory
+#define KT_KDE_THREADS 256
+#define KT_KDE_PTS 2
+#define KT_KDE_TILE (KT_KDE_THREADS * KT_KDE_PTS)
+#define KT_KDE_LDS_ROWS 2048
+#define KT_KDE_CUT 64.0
+#define KT_KDE_HALF_LOG_2PI 0.9189385332046727
+#define KT_KDE_CHUNK_ROWS (1ll << 28)
+
+struct KtKdeJob {
+    long long a, n;             // the k-mer's segment of the table
+    long long so;               // where its units lie in the chunk's copy
+};
+
+__global__ __launch_bounds__(KT_KDE_THREADS) void k_kt_kde_gather(const KtRow *__restrict__ rows, const KtKdeJob *__restrict__ jobs,
+                                                                  long long *__restrict__ units) {
+    const KtKdeJob J = jobs[blockIdx.x];
+    for (long long i = threadIdx.x; i < J.n; i += KT_KDE_THREADS) units[J.so + i] = rows[J.a + i].desc;
+}
+
+// block b: job b / n_tiles, tile b % n_tiles.  out: n_jobs x n_x
+template <bool SKIP>
+__global__ __launch_bounds__(KT_KDE_THREADS) void k_kt_kde(const long long *__restrict__ sorted, const KtKdeJob *__restrict__ jobs,
+                                                           const double *__restrict__ x, long long n_x, long long n_tiles, double inv_h,
+                                                           double log_h, double *__restrict__ out) {
+    __shared__ double s_x[KT_KDE_LDS_ROWS];
+    const long long job = (long long) blockIdx.x / n_tiles, tile = (long long) blockIdx.x % n_tiles;
+    const int t = threadIdx.x;
+    const KtKdeJob J = jobs[job];
+    long long qi[KT_KDE_PTS];
+    bool ok[KT_KDE_PTS];
+    double q[KT_KDE_PTS], dmin[KT_KDE_PTS], emax[KT_KDE_PTS], s[KT_KDE_PTS];
+#pragma unroll
+    for (int p = 0; p < KT_KDE_PTS; p++) {
+        qi[p] = tile * KT_KDE_TILE + (long long) p * KT_KDE_THREADS + t;
+        ok[p] = qi[p] < n_x;
+        q[p] = ok[p] ? x[qi[p]] : 0.0;
+        dmin[p] = INFINITY;
+        emax[p] = 0.0;
+        s[p] = 0.0;
+    }
+    if (J.n == 0) {
+#pragma unroll
+        for (int p = 0; p < KT_KDE_PTS; p++)
+            if (ok[p]) out[(size_t) job * (size_t) n_x + (size_t) qi[p]] = -INFINITY;
+        return;
+    }
+    const long long *src = sorted + J.so;
+    for (int sweep = 0; sweep < 2; sweep++) {
+        if (sweep == 1) {
+#pragma unroll
+            for (int p = 0; p < KT_KDE_PTS; p++) {
+                const double z = dmin[p] * inv_h;
+                emax[p] = -0.5 * (z * z);
+            }
+        }
+        for (long long base = 0; base < J.n; base += KT_KDE_LDS_ROWS) {
+            const int c = (int) (J.n - base < KT_KDE_LDS_ROWS ? J.n - base : KT_KDE_LDS_ROWS);
+            __syncthreads();   // (the readers of the previous chunk are done)
+            for (int i = t; i < c; i += KT_KDE_THREADS) s_x[i] = (double) src[base + i] / 1e6;
+            __syncthreads();
+            if (sweep == 0) {
+                for (int i = 0; i < c; i++) {
+                    const double xi = s_x[i];
+#pragma unroll
+                    for (int p = 0; p < KT_KDE_PTS; p++) {
+                        const double d = fabs(q[p] - xi);
+                        dmin[p] = d < dmin[p] ? d : dmin[p];
+                    }
+                }
+            } else {
+                for (int i = 0; i < c; i++) {
+                    const double xi = s_x[i];
+#pragma unroll
+                    for (int p = 0; p < KT_KDE_PTS; p++) {
+                        const double z = (q[p] - xi) * inv_h;
+                        const double e = -0.5 * (z * z) - emax[p];
+                        const bool in = ok[p] && e >= -KT_KDE_CUT;
+                        if (SKIP) {
+                            if (in) s[p] += exp(e);
+                        } else {
+                            s[p] += exp(in ? e : -KT_KDE_CUT) * (in ? 1.0 : 0.0);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const double norm = (log((double) J.n) + log_h) + KT_KDE_HALF_LOG_2PI;
+#pragma unroll
+    for (int p = 0; p < KT_KDE_PTS; p++)
+        if (ok[p]) out[(size_t) job * (size_t) n_x + (size_t) qi[p]] = (emax[p] + log(s[p])) - norm;
+}
+
+// Slab size in doubles (see "output" above).  A chunk holds at least one job whatever the size.
+static size_t kt_kde_slab_doubles() {
+    if (const char *e = getenv("SA_KDE_SLAB")) {
+        const long long v = atoll(e);
+        if (v > 0) return (size_t) v;
+    }
+    return (size_t) 8 << 20;
+}
+
+extern "C" int sa_kmer_table_kde(const sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, int64_t n_jobs, const double *x, int64_t n_x,
+                                 double bandwidth, double *log_density_out, int64_t *n_rows_out, double *kernel_ms_out) {
+    if (!t || !x || !log_density_out || (strand != 0 && strand != 1) || n_jobs < 0 || n_x < 1 || !isfinite(bandwidth) || !(bandwidth > 0))
+        return SA_EINVAL;
+    for (int64_t i = 0; i < n_x; i++)
+        if (!isfinite(x[i])) return SA_EINVAL;
+    const long long nj = kmer_ids ? (long long) n_jobs : t->n_kmers;
+    for (long long j = 0; kmer_ids && j < nj; j++)
+        if (kmer_ids[j] < 0 || kmer_ids[j] >= t->n_kmers) return SA_EINVAL;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (nj == 0) return SA_OK;
+    const long long n_tiles = ((long long) n_x + KT_KDE_TILE - 1) / KT_KDE_TILE;
+    if (n_tiles > 0x7fffffffll) return SA_EUNSUPPORTED;
+    sa_kmer_table *T = const_cast<sa_kmer_table *>(t);
+    std::lock_guard<std::mutex> g(T->mu);
+    const KtSide &S = t->side[strand];
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    std::vector<long long> off((size_t) t->n_kmers + 1);
+    if (hipMemcpy(off.data(), S.d_off, 8 * off.size(), hipMemcpyDeviceToHost) != hipSuccess) return SA_ENODEVICE;
+    // chunks of jobs: the output block within the slab, the rows within what one sort takes, the grid within 2^31 blocks
+    const size_t slab = kt_kde_slab_doubles();
+    const long long jobs_per_launch = 0x7fffffffll / n_tiles;
+    std::vector<long long> chunk_first(1, 0);
+    size_t max_jobs = 0, max_rows = 0;
+    {
+        long long rows = 0, first = 0;
+        for (long long j = 0; j < nj; j++) {
+            const long long km = kmer_ids ? kmer_ids[j] : j, n = off[(size_t) km + 1] - off[(size_t) km];
+            if (n > 0xffffffffll) return SA_EUNSUPPORTED;   // (the segmented sort counts rows in 32 bits)
+            if (j > first && ((size_t) (j - first + 1) * (size_t) n_x > slab || rows + n > KT_KDE_CHUNK_ROWS || j - first >= jobs_per_launch)) {
+                chunk_first.push_back(j);
+                first = j;
+                rows = 0;
+            }
+            rows += n;
+            max_jobs = std::max(max_jobs, (size_t) (j - first + 1));
+            max_rows = std::max(max_rows, (size_t) rows);
+            if (n_rows_out) n_rows_out[j] = n;
+        }
+        chunk_first.push_back(nj);
+    }
+    const double inv_h = 1.0 / bandwidth, log_h = log(bandwidth);
+    const bool skip = !(getenv("SA_KDE_NO_SKIP") && atoi(getenv("SA_KDE_NO_SKIP")) != 0);
+    SaLayout L;
+    const size_t o_jobs = L.add(sizeof(KtKdeJob) * max_jobs), o_beg = L.add(4 * max_jobs), o_end = L.add(4 * max_jobs), o_up = L.end,
+                 o_x = L.add(8 * (size_t) n_x), o_u0 = L.add(8 * max_rows), o_u1 = L.add(8 * max_rows),
+                 o_out = L.add(8 * max_jobs * (size_t) n_x), bytes = L.end;
+    int rc = SA_OK;
+    char *h = nullptr, *d = nullptr;
+    void *d_tmp = nullptr;
+    size_t tmp_cap = 0;
+    double kms = 0;
+    if (g_sa_pool.get(SaPool::PINNED, (void **) &h, o_up, t->device) != hipSuccess) return SA_ENOMEM;
+    {
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, t->device));
+        SA_HIP_GOTO_DONE(hipMemcpy(d + o_x, x, 8 * (size_t) n_x, hipMemcpyHostToDevice));
+        KtKdeJob *hj = (KtKdeJob *) (h + o_jobs);
+        unsigned *hb = (unsigned *) (h + o_beg), *he = (unsigned *) (h + o_end);
+        const KtKdeJob *dj = (const KtKdeJob *) (d + o_jobs);
+        const unsigned *beg = (const unsigned *) (d + o_beg), *end = (const unsigned *) (d + o_end);
+        long long *u0 = (long long *) (d + o_u0), *u1 = (long long *) (d + o_u1);
+        double *d_out = (double *) (d + o_out);
+        for (size_t c = 0; c + 1 < chunk_first.size(); c++) {
+            const long long j0 = chunk_first[c], cj = chunk_first[c + 1] - j0;
+            long long rows = 0;
+            for (long long j = 0; j < cj; j++) {
+                const long long km = kmer_ids ? kmer_ids[j0 + j] : j0 + j;
+                hj[j].a = off[(size_t) km]; hj[j].n = off[(size_t) km + 1] - hj[j].a; hj[j].so = rows;
+                hb[j] = (unsigned) rows;
+                rows += hj[j].n;
+                he[j] = (unsigned) rows;
+            }
+            SA_HIP_GOTO_DONE(hipMemcpy(d, h, o_up, hipMemcpyHostToDevice));
+            if (rows) {
+                size_t need = 0;
+                SA_HIP_GOTO_DONE(rocprim::segmented_radix_sort_keys(nullptr, need, u0, u1, (unsigned) rows, (unsigned) cj, beg, end, 0, 64,
+                                                                    (hipStream_t) 0));
+                if (need > tmp_cap) {
+                    g_sa_pool.put(SaPool::DEVICE, d_tmp);
+                    d_tmp = nullptr;
+                    tmp_cap = 0;
+                    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, &d_tmp, need, t->device));
+                    tmp_cap = need;
+                }
+            }
+            SA_HIP_GOTO_DONE(hipEventRecord(T->e0, 0));
+            if (rows) {
+                size_t need = tmp_cap;
+                hipLaunchKernelGGL(k_kt_kde_gather, dim3((unsigned) cj), dim3(KT_KDE_THREADS), 0, 0, S.d_rows, dj, u0);
+                SA_HIP_GOTO_DONE(rocprim::segmented_radix_sort_keys(d_tmp, need, u0, u1, (unsigned) rows, (unsigned) cj, beg, end, 0, 64,
+                                                                    (hipStream_t) 0));
+            }
+            if (skip)
+                hipLaunchKernelGGL(k_kt_kde<true>, dim3((unsigned) (cj * n_tiles)), dim3(KT_KDE_THREADS), 0, 0, u1, dj, (const double *) (d + o_x),
+                                   (long long) n_x, n_tiles, inv_h, log_h, d_out);
+            else
+                hipLaunchKernelGGL(k_kt_kde<false>, dim3((unsigned) (cj * n_tiles)), dim3(KT_KDE_THREADS), 0, 0, u1, dj, (const double *) (d + o_x),
+                                   (long long) n_x, n_tiles, inv_h, log_h, d_out);
+            SA_HIP_GOTO_DONE(hipEventRecord(T->e1, 0));
+            SA_HIP_GOTO_DONE(hipGetLastError());
+            SA_HIP_GOTO_DONE(hipMemcpy(log_density_out + (size_t) j0 * (size_t) n_x, d_out, 8 * (size_t) cj * (size_t) n_x, hipMemcpyDeviceToHost));
+            float seg = 0;
+            SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, T->e0, T->e1));
+            kms += (double) seg;
+        }
+        if (kernel_ms_out) *kernel_ms_out = kms;
+    }
+done:
+    if (rc != SA_OK) (void) hipDeviceSynchronize();
+    g_sa_pool.put(SaPool::DEVICE, d_tmp);
+    g_sa_pool.put(SaPool::DEVICE, d);
+    g_sa_pool.put(SaPool::PINNED, h);
+    return rc;
 }
 
 // ---- host: Python's repr, the "%f" units, the model writer ----------------------------------------------------------------------
