@@ -781,6 +781,61 @@ int64_t sa_remap_anchors(const int64_t *ax, const int64_t *ay, int64_t n, const 
 int sa_estimate_params(const sa_model_t *m, double *table5_inout, const int64_t *strand_event_map, double *events4,
                        int64_t n_events, const char *strand_read, int64_t read_len, double *out7);
 
+/* ---- guide alignment: a basecalled read against its reference window (what the reference's driver asks bwa mem for,
+ * src/signalalign/signalAlignment.py:262-305) ------------------------------------------------------------------------------
+ * Local alignment with affine gaps inside a Suzuki-Kasahara adaptive band, integer scores, one wave per read on the GPU.  The
+ * rules (band geometry, steering, recurrence, tie-breaks, end cell, traceback) are written down in DESIGN.md and restated in
+ * tests/guide_ref.py; the device's answer equals that restatement bit for bit.  Operation types are sa_guide_to_anchors':
+ * 0 match, 1 reference-only, 2 read-only -- a result goes straight into sa_guide_to_anchors. */
+typedef struct sa_guide_job {
+    const char *read;  int64_t read_len;   /* nucleotides, any case */
+    const char *ref;   int64_t ref_len;    /* the window, already in the orientation the read is aligned in */
+    int64_t diag;                          /* reference index that read base 0 is expected at (sa_guide_seed); 0: window starts at the read */
+} sa_guide_job_t;
+typedef struct sa_guide_params {
+    int32_t match, mismatch;               /* scores of a pair of equal / different letters of ACGT (2, -4) */
+    int32_t gap_open, gap_extend;          /* a gap of length L costs gap_open + L * gap_extend (4, 2) */
+    int32_t ambiguous;                     /* score of any letter outside ACGT against anything (-1) */
+    int32_t band;                          /* cells per anti-diagonal: 64, 128, 192 or 256 (128) */
+    double min_read_fraction;              /* SA_GUIDE_SHORT unless the aligned read span reaches this share of the read (0.5) */
+} sa_guide_params_t;
+#define SA_GUIDE_NO_ALIGNMENT 1            /* no positive-scoring alignment: zero operations */
+#define SA_GUIDE_SHORT 2                   /* aligned read span < min_read_fraction * read_len */
+#define SA_GUIDE_BAND_EDGE 4               /* the path touched the first or last band offset: it may be clipped by the band (a warning) */
+#define SA_GUIDE_EMPTY 8                   /* read_len == 0 or ref_len == 0 */
+#define SA_GUIDE_TRACE 16                  /* the traceback left the band or the job's bands: the operations are not to be used */
+typedef struct sa_guide_result {
+    int32_t status;                        /* 0 or SA_GUIDE_* bits */
+    int64_t score, read_start, read_end, ref_start, ref_end;   /* half-open, in the job's coordinates */
+    int64_t op_first, n_ops;               /* run-length operations, read order, in the arrays below */
+} sa_guide_result_t;
+/* params NULL: the defaults above.  diag is clamped to [0, ref_len].  *op_type_out / *op_len_out (malloc'd, sa_free) hold every
+ * job's operations back to back.  SA_EINVAL (checked before any device use): a NULL array, n_jobs < 0, a length above 2^24, a band
+ * that is no multiple of 64 in 64..256, a score beyond +-1000, gap_extend < 1, gap_open < 0; then SA_ENODEVICE without a GPU (there
+ * is no CPU fallback).  The batch is cut into slices whose trace (band / 2 bytes per anti-diagonal) fits the device's free memory;
+ * SA_ENOMEM when one job's does not.  kernel_ms_out (may be NULL): HIP-event time of the kernels. */
+int sa_guide_align_batch(const sa_guide_job_t *jobs, int64_t n_jobs, const sa_guide_params_t *params, int device, unsigned flags,
+                         sa_guide_result_t *results_out, int32_t **op_type_out, int64_t **op_len_out, double *kernel_ms_out);
+/* sa_guide_align_batch keeps its device and pinned-host scratch between calls (grow only); this returns it */
+void sa_guide_release(void);
+/* Places a read inside a window that is longer than the band can absorb (host only).  Exact 15-mer matches between the read's
+ * first 2000 bases and the window (with try_both_strands also its reverse complement) vote on the diagonal (window index minus
+ * read index) in bins of 32; *diag_out is the median diagonal of the votes in the modal bin and its two neighbours, *reverse_out
+ * 1 when the reverse complement got more votes, *votes_out those votes, *hits_out all 15-mer hits of that strand.  Fewer than 8
+ * votes: no seed -- *diag_out = 0, *reverse_out = 0, and the return value is 1 (0 with a seed; SA_EINVAL for a NULL argument).
+ * The diagonal of a reversed seed counts in the reverse-complemented window.  The caller crops the window to band / 2 before
+ * the diagonal. */
+int sa_guide_seed(const char *read, int64_t read_len, const char *window, int64_t window_len, int try_both_strands,
+                  int64_t *diag_out, int *reverse_out, int64_t *votes_out, int64_t *hits_out);
+/* The exonerate line of a guide alignment as the reference's driver writes it (src/signalalign/__init__.py:25-64):
+ *   cigar: <label> <qstart> <qend> + <contig> <rstart> <rend> <+|-> <score> (M|D|I n)*
+ * ref_start / ref_end are contig coordinates of the aligned interval on the forward strand; on the minus strand the line carries
+ * them swapped (start > end) and the operations stay in read order.  Returns the length written (without the NUL), or the length
+ * needed when cap is too small (nothing is written then); SA_EINVAL for a NULL argument or an unknown operation. */
+int64_t sa_guide_format_cigar(const char *label, int64_t read_start, int64_t read_end, const char *contig, int64_t ref_start,
+                              int64_t ref_end, int forward, int64_t score, const int32_t *op_type, const int64_t *op_len,
+                              int64_t n_ops, char *out, int64_t cap);
+
 /* ---- HDP rebuild, the deterministic pieces --------------------------------------------------------
  * The state of a serialised NanoporeHDP as the reference's Gibbs sampler leaves it, and what is computed FROM a state without
  * random numbers.  The sampling sweep itself (sample_dp_factors / gibbs_factor_iteration, impl/hdp.c:2110-2260, rand()-driven)

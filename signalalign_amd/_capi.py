@@ -86,6 +86,28 @@ class EaJob(C.Structure):
                 ("n_events", C.c_int64), ("scale", C.c_double), ("shift", C.c_double), ("var", C.c_double)]
 
 
+class GuideJob(C.Structure):
+    _fields_ = [("read", C.c_char_p), ("read_len", C.c_int64), ("ref", C.c_char_p), ("ref_len", C.c_int64), ("diag", C.c_int64)]
+
+
+class GuideParams(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32),
+                ("ambiguous", C.c_int32), ("band", C.c_int32), ("min_read_fraction", C.c_double)]
+
+
+class GuideResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("score", C.c_int64), ("read_start", C.c_int64), ("read_end", C.c_int64),
+                ("ref_start", C.c_int64), ("ref_end", C.c_int64), ("op_first", C.c_int64), ("n_ops", C.c_int64)]
+
+
+class Cigar(C.Structure):
+    """sa_cigar_t (csrc/sa_io.h)"""
+    _fields_ = [("contig1", C.c_char_p), ("contig2", C.c_char_p), ("start1", C.c_int64), ("end1", C.c_int64),
+                ("start2", C.c_int64), ("end2", C.c_int64), ("strand1", C.c_int), ("strand2", C.c_int),
+                ("score", C.c_double), ("n_ops", C.c_int64), ("op_type", C.POINTER(C.c_int32)),
+                ("op_len", C.POINTER(C.c_int64))]
+
+
 class RawJob(C.Structure):
     _fields_ = [("raw", C.POINTER(C.c_int16)), ("n_samples", C.c_int64), ("digitisation", C.c_float), ("offset", C.c_float),
                 ("range", C.c_float), ("sample_rate", C.c_float), ("start_time", C.c_float)]
@@ -140,6 +162,7 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_hmm_load_into_model", "sa_model_transitions10",
            "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
            "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_kmer_table_kde", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
+           "sa_guide_align_batch", "sa_guide_release", "sa_guide_seed", "sa_guide_format_cigar",
            "sa_version", "sa_free"]
 
 
@@ -276,6 +299,16 @@ def lib():
     L.sa_event_align_batch.argtypes = [C.c_void_p, C.POINTER(EaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip,
                                        C.POINTER(C.c_int32), dp, dp]
     i32p = C.POINTER(C.c_int32)
+    L.sa_guide_align_batch.argtypes = [C.POINTER(GuideJob), C.c_int64, C.POINTER(GuideParams), C.c_int, C.c_uint,
+                                       C.POINTER(GuideResult), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), dp]
+    L.sa_guide_release.restype = None
+    L.sa_guide_seed.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int, ip, C.POINTER(C.c_int), ip, ip]
+    L.sa_guide_format_cigar.restype = C.c_int64
+    L.sa_guide_format_cigar.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int64,
+                                        i32p, ip, C.c_int64, C.c_char_p, C.c_int64]
+    L.sa_cigar_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(Cigar))]
+    L.sa_cigar_free.argtypes = [C.POINTER(Cigar)]
+    L.sa_cigar_free.restype = None
     L.sa_detect_events_batch.argtypes = [C.POINTER(RawJob), C.c_int64, C.POINTER(DetectorParams), C.c_int, C.c_uint,
                                          C.POINTER(C.c_void_p), ip, i32p, dp]
     L.sa_raw_event_align_batch.argtypes = [C.c_void_p, C.POINTER(RawJob), C.POINTER(C.c_char_p), C.c_int64,
@@ -860,6 +893,93 @@ def event_align_batch(model, jobs, device=0, flags=0, stats=None):
 
 def _i32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+GUIDE_NO_ALIGNMENT, GUIDE_SHORT, GUIDE_BAND_EDGE, GUIDE_EMPTY, GUIDE_TRACE = 1, 2, 4, 8, 16
+
+
+def guide_params(match=2, mismatch=-4, gap_open=4, gap_extend=2, ambiguous=-1, band=128, min_read_fraction=0.5):
+    return GuideParams(match, mismatch, gap_open, gap_extend, ambiguous, band, min_read_fraction)
+
+
+def guide_align_batch(jobs, params=None, device=0, stats=None):
+    """sa_guide_align_batch.  jobs: (read, window) or (read, window, diag) tuples, or dicts(read, ref, diag=0); params: a
+    GuideParams (guide_params()) or None for the defaults.  Returns per job a dict(status, score, read_start, read_end,
+    ref_start, ref_end, ops) with ops a list of (type, length) in read order -- what guide_to_anchors takes."""
+    n = len(jobs)
+    arr = (GuideJob * max(n, 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        if isinstance(j, dict):
+            j = (j["read"], j["ref"], j.get("diag", 0))
+        rb, wb = j[0].encode("latin-1"), j[1].encode("latin-1")
+        keep.append((rb, wb))
+        arr[i] = GuideJob(rb, len(rb), wb, len(wb), int(j[2]) if len(j) > 2 else 0)
+    res = (GuideResult * max(n, 1))()
+    pt, pl = C.c_void_p(), C.c_void_p()
+    kms = C.c_double()
+    t0 = time.perf_counter()
+    _chk(lib().sa_guide_align_batch(arr, n, C.byref(params) if params is not None else None, device, 0, res, C.byref(pt), C.byref(pl),
+                                    C.byref(kms)), "sa_guide_align_batch")
+    if stats is not None:
+        stats["kernel_ms"] = kms.value
+        stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+    tot = sum(int(res[i].n_ops) for i in range(n))
+    ot, ol = np.zeros(tot, dtype=np.int32), np.zeros(tot, dtype=np.int64)
+    if tot:
+        C.memmove(ot.ctypes.data, pt, 4 * tot)
+        C.memmove(ol.ctypes.data, pl, 8 * tot)
+    lib().sa_free(pt)
+    lib().sa_free(pl)
+    out = []
+    for i in range(n):
+        r = res[i]
+        a, z = int(r.op_first), int(r.op_first + r.n_ops)
+        out.append(dict(status=int(r.status), score=int(r.score), read_start=int(r.read_start), read_end=int(r.read_end),
+                        ref_start=int(r.ref_start), ref_end=int(r.ref_end),
+                        ops=[(int(t), int(ln)) for t, ln in zip(ot[a:z], ol[a:z])]))
+    del keep
+    return out
+
+
+def guide_release():
+    lib().sa_guide_release()
+
+
+def guide_seed(read, window, try_both_strands=True):
+    """sa_guide_seed -> dict(found, diag, reverse, votes, hits)"""
+    rb, wb = read.encode("latin-1"), window.encode("latin-1")
+    d, v, h, rev = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+    rc = lib().sa_guide_seed(rb, len(rb), wb, len(wb), 1 if try_both_strands else 0, C.byref(d), C.byref(rev), C.byref(v), C.byref(h))
+    if rc < 0:
+        raise SaError(int(rc), "sa_guide_seed")
+    return dict(found=rc == 0, diag=int(d.value), reverse=bool(rev.value), votes=int(v.value), hits=int(h.value))
+
+
+def guide_format_cigar(label, read_start, read_end, contig, ref_start, ref_end, forward, score, ops):
+    """sa_guide_format_cigar: the exonerate line (no newline) of an alignment; ref_start < ref_end are forward-strand contig
+    coordinates"""
+    t = np.array([o[0] for o in ops], dtype=np.int32)
+    ln = np.array([o[1] for o in ops], dtype=np.int64)
+    args = (label.encode(), read_start, read_end, contig.encode(), ref_start, ref_end, 1 if forward else 0, int(score), _i32p(t), _ip(ln), len(ops))
+    need = lib().sa_guide_format_cigar(*args, None, 0)
+    if need < 0:
+        raise SaError(int(need), "sa_guide_format_cigar")
+    buf = C.create_string_buffer(int(need) + 1)
+    lib().sa_guide_format_cigar(*args, buf, need + 1)
+    return buf.value.decode()
+
+
+def cigar_load(path):
+    """sa_cigar_load -> dict(contig1, contig2, start1, end1, start2, end2, strand1, strand2, score, ops)"""
+    pc = C.POINTER(Cigar)()
+    _chk(lib().sa_cigar_load(path.encode(), C.byref(pc)), "sa_cigar_load")
+    c = pc.contents
+    out = dict(contig1=c.contig1.decode(), contig2=c.contig2.decode(), start1=int(c.start1), end1=int(c.end1), start2=int(c.start2),
+               end2=int(c.end2), strand1=int(c.strand1), strand2=int(c.strand2), score=float(c.score),
+               ops=[(int(c.op_type[i]), int(c.op_len[i])) for i in range(c.n_ops)])
+    lib().sa_cigar_free(pc)
+    return out
 
 
 def _raw_jobs(jobs):

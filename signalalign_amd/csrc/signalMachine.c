@@ -14,6 +14,11 @@
  * Everything else (models, references, thresholds, output format) comes from the usual options; --device <n> picks the
  * GPU (one process per GPU, each with its share of the manifest: reads are independent).  Per read the same
  * files, stdout summary line and stderr SUCCESS line are produced as by one single-read invocation.
+ *
+ * Guide alignment on the GPU (not in the reference either): --guide-window <contig>:<start>-<end>[:+|:-] instead of -p, or a
+ * manifest's cigar column written as @<contig>:<start>-<end>[:+|:-], names the stretch of the -f reference the read lies in
+ * (0-based, half-open, as a cigar's own coordinates); the read is then aligned to it by sa_guide_align_batch, all such reads of
+ * a slice in one call, and the result stands in for the cigar file.
  */
 #define _GNU_SOURCE
 #include <ctype.h>
@@ -78,6 +83,12 @@ static void usage(void) {
                     "                  signalMachine installs; twoDist adds the inverse Gaussian on the event noise, every read with its own\n"
                     "                  noise scaling -- with --batch too; Gaussian models, not with -t / -c)\n");
     fprintf(stderr, "--device <n>: GPU to use\n");
+    fprintf(stderr, "--guide-window <contig>:<start>-<end>[:+|:-]: instead of -p: compute the guide alignment on the GPU, the read (2-D read\n"
+                    "                  with --twoD, else the template read) against that stretch of the -f reference (0-based, half-open);\n"
+                    "                  without a strand both are tried.  In a manifest: @<contig>:<start>-<end>[:+|:-] in the cigar column.\n"
+                    "                  Not with --rna\n");
+    fprintf(stderr, "--guide-band <n>: band width of that alignment: 64, 128 (default), 192 or 256\n");
+    fprintf(stderr, "--guide-cigars-out <dir>: write every computed guide alignment to <dir>/<label>.cigar (exonerate format, usable with -p)\n");
     fprintf(stderr, "--mea: also write <posteriors file>.mea, the rows of the full output on the maximum expected accuracy path\n");
     fprintf(stderr, "--site-calls: also write <posteriors file>.calls, per read and ambiguous site the normalised probability of\n"
                     "                  each of its letters (variantCaller.py MarginalizeFullVariants)\n");
@@ -372,6 +383,9 @@ typedef struct {
                    * a model of its own (read_t.model); the reads of a manifest share one batch on the strand's model_two and
                    * hand over their noise scalings (sa_batch_create_noise_scaled) */
     int batch_mode;
+    int device;                   /* --device, for the stage that runs ahead of a slice's GPU stage (the guide alignment) */
+    int guide_band;               /* --guide-band */
+    const char *guide_cigars_out; /* --guide-cigars-out */
     int64_t out_fmt, constraint_trim;
     int64_t snp_step;       /* --snp-step N: single-nucleotide probabilities, N substituted copies of every read's reference */
     const char *snp_dir;    /* --snp-dir: where <label>.tsv goes */
@@ -388,6 +402,7 @@ static const char *strand_name(int s) { return s == 0 ? "template" : "complement
 typedef struct {
     char *label, *npread_path, *cigar_path, *post_path, *post_path2, *seq_name;
     char *expect[2];      /* [strand]: where -t / -c write the strand's expectations */
+    char *guide_window;   /* <contig>:<start>-<end>[:+|:-] instead of a cigar file: the guide alignment is computed (guide_stage) */
     sa_cigar_t *pA;
     sa_npread_t *np;
     char *forward_seq, *backward_seq;
@@ -500,12 +515,15 @@ static int build_strand_job(const run_t *R, read_t *rd, int s, const int64_t *gx
 /* everything of impl/signalMachine.c:main between option parsing and performSignalAlignment, for one read */
 static int prepare_read(const run_t *R, read_t *rd, int fatal) {
     const double tp0 = now_s();
-    if (rd->cigar_path == NULL) return fail(rd, fatal, "[signalMachine]ERROR: Need to provide input guide alignments, exiting", NULL);
-    if (sa_cigar_load(rd->cigar_path, &rd->pA) != SA_OK)
-        return fail(rd, fatal, "[signalMachine]ERROR: Didn't find input alignment file, looked %s", rd->cigar_path);
-    fprintf(stderr, "[signalMachine]NOTICE: Using guide alignments from %s\n", rd->cigar_path);
+    if (rd->failed) return -1;   /* the guide stage gave up on it */
+    if (rd->pA == NULL) {        /* (a read with a guide window has its alignment, and its .npRead, from guide_stage) */
+        if (rd->cigar_path == NULL) return fail(rd, fatal, "[signalMachine]ERROR: Need to provide input guide alignments, exiting", NULL);
+        if (sa_cigar_load(rd->cigar_path, &rd->pA) != SA_OK)
+            return fail(rd, fatal, "[signalMachine]ERROR: Didn't find input alignment file, looked %s", rd->cigar_path);
+        fprintf(stderr, "[signalMachine]NOTICE: Using guide alignments from %s\n", rd->cigar_path);
+    }
     sa_cigar_t *pA = rd->pA;
-    if (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK)
+    if (rd->np == NULL && (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK))
         return fail(rd, fatal, "signalMachine: could not load the nanopore read %s", rd->npread_path);
     sa_npread_t *np = rd->np;
     if (pA->start2 < 0 || pA->end2 <= pA->start2 || pA->end2 > (R->two_d ? np->read_length : np->template_read_length))
@@ -642,6 +660,11 @@ static int64_t load_manifest(const char *path, read_t **out) {
         rd->label = strdup(f[0]);
         rd->npread_path = dup_field(f[1]);
         rd->cigar_path = dup_field(f[2]);
+        if (rd->cigar_path && rd->cigar_path[0] == '@') {   /* @<contig>:<start>-<end>[:+|:-]: computed, not read */
+            rd->guide_window = strdup(rd->cigar_path + 1);
+            free(rd->cigar_path);
+            rd->cigar_path = NULL;
+        }
         rd->post_path = dup_field(f[3]);
         rd->post_path2 = dup_field(f[4]);
         rd->seq_name = dup_field(f[5]);
@@ -706,6 +729,180 @@ static void parallel_for(int64_t n, void (*fn)(int64_t, void *), void *ctx) {
         if (started[k]) pthread_join(th[k], NULL);
 }
 
+
+/* ---- guide alignment on the GPU --------------------------------------------------------------------------------------------- */
+/* <contig>:<start>-<end>[:+|:-], read from the right (a contig name may hold colons); strand: 1 '+', 0 '-', -1 not given */
+static int parse_guide_window(const char *spec, char **contig, int64_t *start, int64_t *end, int *strand) {
+    size_t len = strlen(spec);
+    *strand = -1;
+    if (len >= 2 && spec[len - 2] == ':' && (spec[len - 1] == '+' || spec[len - 1] == '-')) {
+        *strand = spec[len - 1] == '+';
+        len -= 2;
+    }
+    size_t colon = len;
+    while (colon > 0 && spec[colon - 1] != ':') colon--;
+    if (colon < 2) return -1;   /* no colon, or an empty contig name */
+    char range[64];
+    if (len - colon == 0 || len - colon >= sizeof(range)) return -1;
+    memcpy(range, spec + colon, len - colon);
+    range[len - colon] = 0;
+    char *dash = NULL, *stop = NULL;
+    if (!isdigit((unsigned char) range[0])) return -1;
+    const long long a = strtoll(range, &dash, 10);
+    if (*dash != '-' || !isdigit((unsigned char) dash[1])) return -1;
+    const long long b = strtoll(dash + 1, &stop, 10);
+    if (*stop != 0 || b <= a) return -1;
+    *contig = strndup(spec, colon - 1);
+    *start = a;
+    *end = b;
+    return 0;
+}
+
+typedef struct {
+    read_t *rd;
+    char *contig, *oriented;   /* the window as the read is aligned to it: forward or reverse complement */
+    int64_t w_start, w_len, crop;
+    int reverse;
+    sa_guide_job_t job;
+} guide_item_t;
+
+typedef struct {
+    const run_t *R;
+    guide_item_t *items;
+} guide_ctx_t;
+
+/* host side of one read: the .npRead, the window, the seed */
+static void guide_prepare_one(int64_t i, void *ctx) {
+    const guide_ctx_t *g = ctx;
+    const run_t *R = g->R;
+    guide_item_t *it = &g->items[i];
+    read_t *rd = it->rd;
+    const int fatal = !R->batch_mode;
+    int64_t w_end = 0;
+    int strand = -1;
+    if (parse_guide_window(rd->guide_window, &it->contig, &it->w_start, &w_end, &strand) != 0) {
+        fail(rd, fatal, "signalMachine: cannot read the guide window %s (want <contig>:<start>-<end>[:+|:-])", rd->guide_window);
+        return;
+    }
+    if (R->fwd_ref == NULL) { fail(rd, fatal, "[signalMachine] ERROR: a guide window needs -f <fasta>", NULL); return; }
+    if (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK) {
+        fail(rd, fatal, "signalMachine: could not load the nanopore read %s", rd->npread_path);
+        return;
+    }
+    const char *read = R->two_d ? rd->np->two_d_read : rd->np->template_read;
+    const int64_t read_len = R->two_d ? rd->np->read_length : rd->np->template_read_length;
+    int ferr = 0;
+    char *window = sa_fasta_fetch(R->fwd_ref, it->contig, it->w_start, w_end - 1, &ferr);
+    if (window == NULL) {
+        fail(rd, fatal, ferr == -2 ? "sequence name %s is not in the reference fasta" : "[signalMachine] ERROR: Unable to fetch the guide window %s",
+             ferr == -2 ? it->contig : rd->guide_window);
+        return;
+    }
+    it->w_len = (int64_t) strlen(window);
+    int64_t diag = 0, votes = 0, hits = 0;
+    int reverse = 0, seeded;
+    if (strand == 0) {   /* told: minus */
+        it->oriented = sa_reverse_complement(window);
+        free(window);
+        seeded = sa_guide_seed(read, read_len, it->oriented, it->w_len, 0, &diag, &reverse, &votes, &hits) == 0;
+        reverse = 1;
+    } else {
+        seeded = sa_guide_seed(read, read_len, window, it->w_len, strand < 0, &diag, &reverse, &votes, &hits) == 0;
+        if (seeded && reverse) {
+            it->oriented = sa_reverse_complement(window);
+            free(window);
+        } else {
+            it->oriented = window;
+            reverse = 0;
+        }
+    }
+    if (!seeded) diag = 0;
+    it->reverse = reverse;
+    /* the band absorbs what lies within it of the seed's diagonal: the window starts band / 2 before */
+    it->crop = seeded && diag > R->guide_band / 2 ? diag - R->guide_band / 2 : 0;
+    it->job.read = read;
+    it->job.read_len = read_len;
+    it->job.ref = it->oriented + it->crop;
+    it->job.ref_len = it->w_len - it->crop;
+    it->job.diag = diag - it->crop;
+}
+
+/* The reads of a slice that name a window instead of a cigar file: ONE sa_guide_align_batch call, ahead of prepare_read's
+ * remaining work; the result becomes the read's sa_cigar_t.  A read whose alignment is unusable fails as a read with an unusable
+ * cigar file does. */
+static void guide_stage(const run_t *R, read_t *reads, int64_t n_reads) {
+    int64_t n = 0;
+    for (int64_t i = 0; i < n_reads; i++) n += reads[i].guide_window != NULL;
+    if (n == 0) return;
+    const int fatal = !R->batch_mode;
+    guide_item_t *items = xalloc(n, sizeof(guide_item_t), 1);
+    n = 0;
+    for (int64_t i = 0; i < n_reads; i++)
+        if (reads[i].guide_window != NULL) items[n++].rd = &reads[i];
+    guide_ctx_t ctx = {R, items};
+    parallel_for(n, guide_prepare_one, &ctx);
+    sa_guide_job_t *jobs = xalloc(n, sizeof(sa_guide_job_t), 1);
+    int64_t *who = xalloc(n, sizeof(int64_t), 0), n_jobs = 0;
+    for (int64_t i = 0; i < n; i++)
+        if (!items[i].rd->failed) { jobs[n_jobs] = items[i].job; who[n_jobs++] = i; }
+    sa_guide_result_t *res = xalloc(n_jobs, sizeof(sa_guide_result_t), 1);
+    int32_t *op_type = NULL;
+    int64_t *op_len = NULL;
+    sa_guide_params_t prm = {2, -4, 4, 2, -1, R->guide_band, 0.5};
+    int rc = n_jobs > 0 ? sa_guide_align_batch(jobs, n_jobs, &prm, R->device, 0, res, &op_type, &op_len, NULL) : SA_OK;
+    for (int64_t q = 0; q < n_jobs; q++) {
+        guide_item_t *it = &items[who[q]];
+        read_t *rd = it->rd;
+        if (rc != SA_OK) { fail(rd, fatal, "signalMachine: the guide alignment could not be computed: %s", sa_strerror(rc)); continue; }
+        const sa_guide_result_t *r = &res[q];
+        if (r->status & ~SA_GUIDE_BAND_EDGE) {
+            fail(rd, fatal, r->status & (SA_GUIDE_NO_ALIGNMENT | SA_GUIDE_EMPTY) ? "signalMachine: no guide alignment of the read inside %s"
+                 : r->status & SA_GUIDE_SHORT ? "signalMachine: the guide alignment inside %s covers less than half of the read"
+                 : "signalMachine: the guide alignment inside %s could not be traced", rd->guide_window);
+            continue;
+        }
+        if (r->status & SA_GUIDE_BAND_EDGE)
+            fprintf(stderr, "[signalMachine]WARNING: the guide alignment of %s touches the edge of its band (--guide-band %d): it may be clipped\n",
+                    rd->label, R->guide_band);
+        /* window coordinates of the aligned stretch in the orientation it was aligned in, then forward contig coordinates */
+        const int64_t a = it->crop + r->ref_start, b = it->crop + r->ref_end;
+        const int64_t fs = it->w_start + (it->reverse ? it->w_len - b : a), fe = it->w_start + (it->reverse ? it->w_len - a : b);
+        sa_cigar_t *c = xalloc(1, sizeof(sa_cigar_t), 1);
+        c->contig1 = strdup(it->contig);
+        c->contig2 = strdup(rd->label);
+        c->start2 = r->read_start; c->end2 = r->read_end; c->strand2 = 1;
+        c->start1 = it->reverse ? fe : fs; c->end1 = it->reverse ? fs : fe; c->strand1 = !it->reverse;
+        c->score = (double) r->score;
+        c->n_ops = r->n_ops;
+        c->op_type = xalloc(r->n_ops, sizeof(int32_t), 0);
+        c->op_len = xalloc(r->n_ops, sizeof(int64_t), 0);
+        memcpy(c->op_type, op_type + r->op_first, sizeof(int32_t) * (size_t) r->n_ops);
+        memcpy(c->op_len, op_len + r->op_first, sizeof(int64_t) * (size_t) r->n_ops);
+        rd->pA = c;
+        rd->seq_name = strdup(it->contig);   /* the window names the contig, whatever -n says */
+        fprintf(stderr, "[signalMachine]NOTICE: Guide alignment computed on the GPU inside %s: read %" PRId64 "-%" PRId64 " on %s %" PRId64 "-%" PRId64
+                        " %c, score %" PRId64 "\n", rd->guide_window, c->start2, c->end2, c->contig1, fs, fe, it->reverse ? '-' : '+', r->score);
+        if (R->guide_cigars_out) {
+            const int64_t need = sa_guide_format_cigar(rd->label, c->start2, c->end2, c->contig1, fs, fe, !it->reverse, r->score, c->op_type,
+                                                       c->op_len, c->n_ops, NULL, 0);
+            char *line = xalloc(need + 1, 1, 0);
+            sa_guide_format_cigar(rd->label, c->start2, c->end2, c->contig1, fs, fe, !it->reverse, r->score, c->op_type, c->op_len, c->n_ops,
+                                  line, need + 1);
+            char *path = xalloc((int64_t) (strlen(R->guide_cigars_out) + strlen(rd->label) + 16), 1, 0);
+            sprintf(path, "%s/%s.cigar", R->guide_cigars_out, rd->label);
+            FILE *fh = fopen(path, "w");
+            if (fh) { fprintf(fh, "%s\n", line); fclose(fh); }
+            else fprintf(stderr, "[signalMachine]WARNING: cannot write %s\n", path);
+            free(path);
+            free(line);
+        }
+    }
+    sa_free(op_type);
+    sa_free(op_len);
+    for (int64_t i = 0; i < n; i++) { free(items[i].contig); free(items[i].oriented); }
+    free(res); free(who); free(jobs); free(items);
+}
+
 /* One slice of the run's reads: host side of every read, one GPU batch per strand model, outputs.  (The whole manifest used to
  * be one batch: fine for thousands of reads, not for a flow cell.) */
 typedef struct {
@@ -728,6 +925,7 @@ static void prep_one(int64_t i, void *ctx) {
 static void *slice_prepare(void *arg) {
     slice_t *sl = arg;
     const double ts0 = now_s();
+    guide_stage(sl->R, sl->reads, sl->n_reads);
     parallel_for(sl->n_reads, prep_one, sl);
     t_add(&g_t_prep, now_s() - ts0);
     return NULL;
@@ -1778,7 +1976,8 @@ int main(int argc, char **argv) {
     R.constraint_trim = 14;
     char *t_model = NULL, *c_model = NULL, *label = NULL, *npread_path = NULL, *cigar_path = NULL, *post_path = NULL;
     char *t_expect = NULL, *c_expect = NULL, *t_hdp = NULL, *c_hdp = NULL, *fwd_ref = NULL, *bwd_ref = NULL,
-         *post_path2 = NULL, *seq_name = NULL, *ambig_model = NULL, *manifest = NULL;
+         *post_path2 = NULL, *seq_name = NULL, *ambig_model = NULL, *manifest = NULL, *guide_window = NULL;
+    R.guide_band = 128;
     static struct option long_options[] = {{"help", no_argument, 0, 'h'},
                                            {"sm3Hdp", no_argument, 0, 'd'},
                                            {"sparse_output", no_argument, 0, 's'},
@@ -1826,6 +2025,9 @@ int main(int argc, char **argv) {
                                            {"train-mixture-distances", required_argument, 0, 1043},
                                            {"snp-step", required_argument, 0, 1020},
                                            {"snp-dir", required_argument, 0, 1021},
+                                           {"guide-window", required_argument, 0, 1050},
+                                           {"guide-band", required_argument, 0, 1051},
+                                           {"guide-cigars-out", required_argument, 0, 1052},
                                            {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -1880,6 +2082,9 @@ int main(int argc, char **argv) {
                 if (sscanf(optarg, "%" SCNd64, &R.snp_step) != 1) R.snp_step = 0;
                 break;
             case 1021: R.snp_dir = strdup(optarg); break;
+            case 1050: guide_window = strdup(optarg); break;
+            case 1051: R.guide_band = atoi(optarg); break;
+            case 1052: R.guide_cigars_out = strdup(optarg); break;
             case 1003: batch_reads = atoll(optarg) > 0 ? atoll(optarg) : batch_reads; break;
             case 1004:
                 if (!strcmp(optarg, "twoDist")) R.two_dist = 1;
@@ -1891,7 +2096,11 @@ int main(int argc, char **argv) {
     if (!label) label = strdup("");
     if (t_model == NULL || (c_model == NULL && R.two_d)) die("Missing model files, exiting", NULL);
     if (R.out_fmt == 3 && post_path2 == NULL && manifest == NULL) die("Must pass in posteriorProbsFile2 if using 'both' outFmt", NULL);
-    if (cigar_path == NULL && manifest == NULL) die("[signalMachine]ERROR: Need to provide input guide alignments, exiting", NULL);
+    if (cigar_path != NULL && guide_window != NULL) die("signalMachine: -p and --guide-window exclude each other%s", "");
+    if (cigar_path == NULL && guide_window == NULL && manifest == NULL)
+        die("[signalMachine]ERROR: Need to provide input guide alignments, exiting", NULL);
+    if (R.guide_band < 64 || R.guide_band > 256 || R.guide_band % 64 != 0) die("signalMachine: --guide-band takes 64, 128, 192 or 256%s", "");
+    R.device = device;
     R.fwd_ref = fwd_ref;
     R.bwd_ref = bwd_ref;
 
@@ -1916,8 +2125,11 @@ int main(int argc, char **argv) {
         reads[0].label = label; reads[0].npread_path = npread_path; reads[0].cigar_path = cigar_path;
         reads[0].post_path = post_path; reads[0].post_path2 = post_path2; reads[0].seq_name = seq_name;
         reads[0].expect[0] = t_expect; reads[0].expect[1] = c_expect;
+        reads[0].guide_window = guide_window;
         R.expect_mode = t_expect != NULL || c_expect != NULL;
-        if (fwd_ref == NULL || seq_name == NULL) {
+        if (guide_window != NULL) {
+            if (fwd_ref == NULL) die("[signalMachine] ERROR: --guide-window needs -f <fasta>", NULL);
+        } else if (fwd_ref == NULL || seq_name == NULL) {
             /* the reference needs -n; kept after the cigar check so that the error order matches (impl/signalMachine.c:642-663) */
             sa_cigar_t *probe = NULL;
             if (sa_cigar_load(cigar_path, &probe) != SA_OK)
@@ -1926,6 +2138,17 @@ int main(int argc, char **argv) {
             die("[signalMachine] ERROR: need -f <fasta> and -n <sequence name>", NULL);
         }
     }
+    for (int64_t i = 0; i < n_reads; i++) {   /* guide windows: refused before anything runs */
+        if (reads[i].guide_window == NULL) continue;
+        if (R.rna) die("signalMachine: a guide window (%s) cannot be combined with --rna: RNA reads need a cigar file", reads[i].guide_window);
+        char *contig = NULL;
+        int64_t a, b;
+        int strand;
+        if (parse_guide_window(reads[i].guide_window, &contig, &a, &b, &strand) != 0)
+            die("signalMachine: cannot read the guide window %s (want <contig>:<start>-<end>[:+|:-])", reads[i].guide_window);
+        free(contig);
+    }
+    if (R.guide_cigars_out && mkdir(R.guide_cigars_out, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.guide_cigars_out);
     /* (the expectation pass keeps the reference-ordered kernels and the model's own noise; an HDP model has no such emission) */
     if (R.two_dist && (R.hdp || t_hdp != NULL || c_hdp != NULL || R.expect_mode || t_expect != NULL || c_expect != NULL))
         die("signalMachine: --emission twoDist aligns reads with a Gaussian model: not with an .nhdp, not with -t / -c%s", "");
