@@ -836,6 +836,71 @@ int64_t sa_guide_format_cigar(const char *label, int64_t read_start, int64_t rea
                               int64_t ref_end, int forward, int64_t score, const int32_t *op_type, const int64_t *op_len,
                               int64_t n_ops, char *out, int64_t cap);
 
+/* ---- locating a read in a whole reference (what `bwa mem` finds for the reference's driver before it aligns: the locus) --------
+ * A 15-mer index over every contig of a reference, resident on the GPU, and a batch kernel that votes each read's contig, strand
+ * and diagonal out of it; sa_locate_window turns an answer into the window that sa_guide_seed / sa_guide_align_batch take.  The
+ * index layout and the rules are written down in DESIGN.md ("Locating a read in a whole reference") and restated in
+ * tests/locate_ref.py; the library's index equals that restatement's bit for bit, the device's answer field for field.
+ *
+ * The index: contigs concatenated in the order given, positions global int32.  Every position whose 15 letters are all of ACGT
+ * (either case) and lie inside one contig gives an entry (code, pos), the code 2 bits per base, first base highest (sa_guide_seed's
+ * encoding); entries sorted by (code, pos); a prefix table of 2^q + 1 offsets over the top q bits of the 30-bit code, q even, the
+ * smallest with 2^q >= n_entries, clamped to [16, 26].  Built on the host (a stable LSD radix sort), uploaded once, resident until
+ * sa_ref_index_destroy.  device < 0: built and kept on the host only.  SA_EINVAL: a NULL pointer, n_contigs == 0, a negative
+ * length; SA_EUNSUPPORTED: 2^31 - 2^16 bases or more in all (checked on the lengths, before a sequence is read). */
+typedef struct sa_ref_index sa_ref_index_t;
+int sa_ref_index_build(sa_ref_index_t **out, const char *const *names, const char *const *seqs, const int64_t *lens,
+                       int64_t n_contigs, int device);
+/* every record of a FASTA in file order (a name ends at the first white space); SA_EIO when it cannot be read */
+int sa_ref_index_build_fasta(sa_ref_index_t **out, const char *fasta_path, int device);
+typedef struct sa_ref_index_info {
+    int64_t n_contigs, total_bases, n_entries;
+    int32_t q, device;                     /* table bits; the device the index lives on, -1 host only */
+    int64_t host_bytes, device_bytes;      /* of the four arrays below */
+    double build_seconds;                  /* host time of the build, the upload included */
+} sa_ref_index_info_t;
+int sa_ref_index_info(const sa_ref_index_t *idx, sa_ref_index_info_t *info);
+/* views of the host arrays, valid until the index is destroyed: n_entries codes and positions, 2^q + 1 offsets,
+ * n_contigs + 1 contig starts (the last one the total); any pointer may be NULL */
+int sa_ref_index_entries(const sa_ref_index_t *idx, const uint32_t **codes, const int32_t **pos, const int32_t **table,
+                         const int64_t **contig_start);
+int sa_ref_index_contig(const sa_ref_index_t *idx, int64_t i, const char **name, int64_t *start, int64_t *len);
+void sa_ref_index_destroy(sa_ref_index_t *idx);
+
+typedef struct sa_locate_params {
+    int32_t read_bases;                    /* seeds come from the read's first read_bases bases: 15..2048 (2000) */
+    int32_t max_occ;                       /* a seed with more occurrences on a strand gives no hit there: 1..65536 (32) */
+    int32_t span;                          /* width of the vote's window of keys: 1..8192 (128) */
+    int32_t min_votes;                     /* SA_LOCATE_NONE below: >= 1 (8) */
+    int32_t max_hits;                      /* hits kept per strand: a power of two in 1024..8192 (8192) */
+} sa_locate_params_t;
+#define SA_LOCATE_NONE 1                   /* votes < min_votes: contig -1, pos 0 */
+#define SA_LOCATE_AMBIGUOUS 2              /* located, but 4 * second_votes >= 3 * votes: another locus is nearly as good (a warning) */
+#define SA_LOCATE_OVERFLOW 4               /* a strand had more than max_hits hits: the later ones did not vote (a warning) */
+#define SA_LOCATE_EMPTY 8                  /* read_len < 15: every other field 0, contig -1 */
+typedef struct sa_locate_result {
+    int32_t status, contig, reverse;
+    int64_t pos;                           /* contig coordinate at which read base 0 is expected (may be < 0 or >= the contig's length);
+                                              on the reverse strand read base i is expected at pos - i */
+    int64_t key;                           /* the voted key, global: r - p forward, r + p reverse (r entry position, p seed position) */
+    int64_t votes, second_votes;           /* keys in [keys[best], + span); the best count clear of that window */
+    int64_t hits, seeds, repetitive;       /* kept hits of the chosen strand; the read's seeds; seeds above max_occ on that strand */
+} sa_locate_result_t;
+/* One workgroup per read.  params NULL: the defaults above.  SA_EINVAL (checked before any device use): a NULL array or read,
+ * n_reads < 0, a read length above 2^24 or below 0, a parameter outside its range; then SA_ENODEVICE without a GPU or for an index
+ * built with device < 0 (there is no CPU fallback).  The work happens on the index's device.  kernel_ms_out (may be NULL):
+ * HIP-event time of the kernel. */
+int sa_guide_locate_batch(const sa_ref_index_t *idx, const char *const *reads, const int64_t *read_lens, int64_t n_reads,
+                          const sa_locate_params_t *params, unsigned flags, sa_locate_result_t *out, double *kernel_ms_out);
+/* sa_guide_locate_batch keeps its device and pinned-host scratch between calls (grow only); this returns it */
+void sa_locate_release(void);
+/* The window to hand to the guide stage, [*start, *end) in the contig's coordinates, clipped to the contig: forward
+ * [pos - band, pos + read_len + read_len / 4 + band), reverse the mirror [pos + 1 - read_len - read_len / 4 - band, pos + 1 + band).
+ * SA_EINVAL: a NULL pointer, a result without a contig (SA_LOCATE_NONE, SA_LOCATE_EMPTY), read_len or band < 0, or a window that
+ * the clipping leaves empty. */
+int sa_locate_window(const sa_ref_index_t *idx, const sa_locate_result_t *r, int64_t read_len, int32_t band, int64_t *start,
+                     int64_t *end);
+
 /* ---- HDP rebuild, the deterministic pieces --------------------------------------------------------
  * The state of a serialised NanoporeHDP as the reference's Gibbs sampler leaves it, and what is computed FROM a state without
  * random numbers.  The sampling sweep itself (sample_dp_factors / gibbs_factor_iteration, impl/hdp.c:2110-2260, rand()-driven)

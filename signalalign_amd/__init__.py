@@ -12,7 +12,9 @@ from ._capi import (Batch, JobArray, Model, Params, SaError, build, default_ambi
                     HDP_LAYOUT_FLAT, HDP_LAYOUT_MULTISET, HDP_LAYOUT_MIDDLE_NTS, HDP_LAYOUT_COMPOSITION, HDP_LAYOUT_GROUP_MULTISET,
                     HDP_METRIC_KL, HDP_METRIC_HELLINGER, HDP_METRIC_L2, HDP_METRIC_SHANNON_JENSEN, HDP_GAUSS_CMP_DTYPE, hdp_distances, hdp_distances_paired, hdp_distances_release,
                     GuideParams, guide_params, guide_align_batch, guide_release, guide_seed, guide_format_cigar, cigar_load,
-                    GUIDE_NO_ALIGNMENT, GUIDE_SHORT, GUIDE_BAND_EDGE, GUIDE_EMPTY, GUIDE_TRACE)
+                    GUIDE_NO_ALIGNMENT, GUIDE_SHORT, GUIDE_BAND_EDGE, GUIDE_EMPTY, GUIDE_TRACE,
+                    RefIndex, LocateParams, locate_params, ref_index_build, ref_index_build_fasta, ref_index_info, ref_index_entries, guide_locate_batch,
+                    locate_release, locate_window, LOCATE_NONE, LOCATE_AMBIGUOUS, LOCATE_OVERFLOW, LOCATE_EMPTY, LOCATE_FIELDS)
 
 __all__ = ["Batch", "JobArray", "Model", "Params", "SaError", "build", "default_ambig", "default_params", "device_count", "device_memory", "pool_configure", "lib",
            "library_path", "plan_describe", "plan_digest", "plan_check_path_records", "dplan_compare", "expect_batch", "expect_last_stats", "scalings_mom", "event_align_batch", "detect_events_batch", "raw_event_align_batch", "detect_release", "DETECTOR_DNA", "DETECTOR_RNA", "RAW_NO_PEAK", "RAW_EVENT_DTYPE", "mea_batch", "mea_params", "MEA_INF", "guide_to_anchors", "remap_anchors", "estimate_params", "PAIR_DTYPE",
@@ -21,4 +23,6 @@ __all__ = ["Batch", "JobArray", "Model", "Params", "SaError", "build", "default_
            "HDP_LAYOUT_FLAT", "HDP_LAYOUT_MULTISET", "HDP_LAYOUT_MIDDLE_NTS", "HDP_LAYOUT_COMPOSITION", "HDP_LAYOUT_GROUP_MULTISET",
            "HDP_METRIC_KL", "HDP_METRIC_HELLINGER", "HDP_METRIC_L2", "HDP_METRIC_SHANNON_JENSEN", "HDP_GAUSS_CMP_DTYPE", "hdp_distances", "hdp_distances_paired", "hdp_distances_release",
            "GuideParams", "guide_params", "guide_align_batch", "guide_release", "guide_seed", "guide_format_cigar", "cigar_load",
-           "GUIDE_NO_ALIGNMENT", "GUIDE_SHORT", "GUIDE_BAND_EDGE", "GUIDE_EMPTY", "GUIDE_TRACE"]
+           "GUIDE_NO_ALIGNMENT", "GUIDE_SHORT", "GUIDE_BAND_EDGE", "GUIDE_EMPTY", "GUIDE_TRACE",
+           "RefIndex", "LocateParams", "locate_params", "ref_index_build", "ref_index_build_fasta", "ref_index_info", "ref_index_entries", "guide_locate_batch",
+           "locate_release", "locate_window", "LOCATE_NONE", "LOCATE_AMBIGUOUS", "LOCATE_OVERFLOW", "LOCATE_EMPTY", "LOCATE_FIELDS"]

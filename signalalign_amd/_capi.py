@@ -100,6 +100,21 @@ class GuideResult(C.Structure):
                 ("ref_start", C.c_int64), ("ref_end", C.c_int64), ("op_first", C.c_int64), ("n_ops", C.c_int64)]
 
 
+class RefIndexInfo(C.Structure):
+    """sa_ref_index_info_t (include/signalalign_hip.h)"""
+    _fields_ = [("n_contigs", C.c_int64), ("total_bases", C.c_int64), ("n_entries", C.c_int64), ("q", C.c_int32), ("device", C.c_int32),
+                ("host_bytes", C.c_int64), ("device_bytes", C.c_int64), ("build_seconds", C.c_double)]
+
+
+class LocateParams(C.Structure):
+    _fields_ = [("read_bases", C.c_int32), ("max_occ", C.c_int32), ("span", C.c_int32), ("min_votes", C.c_int32), ("max_hits", C.c_int32)]
+
+
+class LocateResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("contig", C.c_int32), ("reverse", C.c_int32), ("pos", C.c_int64), ("key", C.c_int64),
+                ("votes", C.c_int64), ("second_votes", C.c_int64), ("hits", C.c_int64), ("seeds", C.c_int64), ("repetitive", C.c_int64)]
+
+
 class Cigar(C.Structure):
     """sa_cigar_t (csrc/sa_io.h)"""
     _fields_ = [("contig1", C.c_char_p), ("contig2", C.c_char_p), ("start1", C.c_int64), ("end1", C.c_int64),
@@ -163,6 +178,8 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
            "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_kmer_table_kde", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
            "sa_guide_align_batch", "sa_guide_release", "sa_guide_seed", "sa_guide_format_cigar",
+           "sa_ref_index_build", "sa_ref_index_build_fasta", "sa_ref_index_info", "sa_ref_index_entries", "sa_ref_index_contig",
+           "sa_ref_index_destroy", "sa_guide_locate_batch", "sa_locate_release", "sa_locate_window",
            "sa_version", "sa_free"]
 
 
@@ -306,6 +323,17 @@ def lib():
     L.sa_guide_format_cigar.restype = C.c_int64
     L.sa_guide_format_cigar.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int64,
                                         i32p, ip, C.c_int64, C.c_char_p, C.c_int64]
+    L.sa_ref_index_build.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), ip, C.c_int64, C.c_int]
+    L.sa_ref_index_build_fasta.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
+    L.sa_ref_index_info.argtypes = [C.c_void_p, C.POINTER(RefIndexInfo)]
+    L.sa_ref_index_entries.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
+    L.sa_ref_index_contig.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), ip, ip]
+    L.sa_ref_index_destroy.argtypes = [C.c_void_p]
+    L.sa_ref_index_destroy.restype = None
+    L.sa_guide_locate_batch.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), ip, C.c_int64, C.POINTER(LocateParams), C.c_uint,
+                                        C.POINTER(LocateResult), dp]
+    L.sa_locate_release.restype = None
+    L.sa_locate_window.argtypes = [C.c_void_p, C.POINTER(LocateResult), C.c_int64, C.c_int32, ip, ip]
     L.sa_cigar_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(Cigar))]
     L.sa_cigar_free.argtypes = [C.POINTER(Cigar)]
     L.sa_cigar_free.restype = None
@@ -968,6 +996,104 @@ def guide_format_cigar(label, read_start, read_end, contig, ref_start, ref_end, 
     buf = C.create_string_buffer(int(need) + 1)
     lib().sa_guide_format_cigar(*args, buf, need + 1)
     return buf.value.decode()
+
+
+LOCATE_NONE, LOCATE_AMBIGUOUS, LOCATE_OVERFLOW, LOCATE_EMPTY = 1, 2, 4, 8
+LOCATE_FIELDS = ("status", "contig", "reverse", "pos", "key", "votes", "second_votes", "hits", "seeds", "repetitive")
+
+
+class RefIndex:
+    """sa_ref_index_t: the 15-mer index of a whole reference (device < 0: host only)"""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def close(self):
+        if self._h:
+            lib().sa_ref_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def contig(self, i):
+        """(name, start in the concatenation, length)"""
+        name, start, ln = C.c_char_p(), C.c_int64(), C.c_int64()
+        _chk(lib().sa_ref_index_contig(self._h, i, C.byref(name), C.byref(start), C.byref(ln)), "sa_ref_index_contig")
+        return name.value.decode(), int(start.value), int(ln.value)
+
+
+def ref_index_build(names, seqs, device=0, lens=None):
+    """sa_ref_index_build over (name, sequence) lists; lens overrides the sequences' own lengths (the argument checks)"""
+    n = len(names)
+    nb = [x.encode("latin-1") if x is not None else None for x in names]
+    sb = [x.encode("latin-1") if x is not None else None for x in seqs]
+    na, sq = (C.c_char_p * max(n, 1))(*nb), (C.c_char_p * max(n, 1))(*sb)
+    ln = (C.c_int64 * max(n, 1))(*(lens if lens is not None else [len(x) for x in sb]))
+    h = C.c_void_p()
+    _chk(lib().sa_ref_index_build(C.byref(h), na, sq, ln, n, device), "sa_ref_index_build")
+    return RefIndex(h)
+
+
+def ref_index_build_fasta(path, device=0):
+    h = C.c_void_p()
+    _chk(lib().sa_ref_index_build_fasta(C.byref(h), path.encode(), device), "sa_ref_index_build_fasta")
+    return RefIndex(h)
+
+
+def ref_index_info(index):
+    """sa_ref_index_info -> dict(n_contigs, total_bases, n_entries, q, device, host_bytes, device_bytes, build_seconds)"""
+    info = RefIndexInfo()
+    _chk(lib().sa_ref_index_info(index._h, C.byref(info)), "sa_ref_index_info")
+    return {f: getattr(info, f) for f, _ in RefIndexInfo._fields_}
+
+
+def ref_index_entries(index):
+    """sa_ref_index_entries -> dict(codes uint32, pos int32, table int32, starts int64): copies of the host arrays"""
+    info = ref_index_info(index)
+    p = [C.c_void_p() for _ in range(4)]
+    _chk(lib().sa_ref_index_entries(index._h, *[C.byref(x) for x in p]), "sa_ref_index_entries")
+    shapes = ((info["n_entries"], np.uint32), (info["n_entries"], np.int32), ((1 << info["q"]) + 1, np.int32), (info["n_contigs"] + 1, np.int64))
+    out = []
+    for ptr, (n, dt) in zip(p, shapes):
+        a = np.zeros(n, dtype=dt)
+        if n:
+            C.memmove(a.ctypes.data, ptr, a.nbytes)
+        out.append(a)
+    return dict(codes=out[0], pos=out[1], table=out[2], starts=out[3], q=int(info["q"]), total=int(info["total_bases"]))
+
+
+def locate_params(read_bases=2000, max_occ=32, span=128, min_votes=8, max_hits=8192):
+    return LocateParams(read_bases, max_occ, span, min_votes, max_hits)
+
+
+def guide_locate_batch(index, reads, params=None, stats=None):
+    """sa_guide_locate_batch: per read a dict of sa_locate_result_t's fields (LOCATE_FIELDS); params: a LocateParams or None"""
+    n = len(reads)
+    rb = [r.encode("latin-1") for r in reads]
+    arr = (C.c_char_p * max(n, 1))(*rb)
+    ln = (C.c_int64 * max(n, 1))(*[len(r) for r in rb])
+    res = (LocateResult * max(n, 1))()
+    kms = C.c_double()
+    t0 = time.perf_counter()
+    _chk(lib().sa_guide_locate_batch(index._h, arr, ln, n, C.byref(params) if params is not None else None, 0, res, C.byref(kms)),
+         "sa_guide_locate_batch")
+    if stats is not None:
+        stats["kernel_ms"] = kms.value
+        stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+    return [{f: int(getattr(res[i], f)) for f in LOCATE_FIELDS} for i in range(n)]
+
+
+def locate_release():
+    lib().sa_locate_release()
+
+
+def locate_window(index, result, read_len, band=128):
+    """sa_locate_window -> (start, end) in the contig's coordinates"""
+    r = LocateResult(**{f: result[f] for f in LOCATE_FIELDS})
+    a, b = C.c_int64(), C.c_int64()
+    _chk(lib().sa_locate_window(index._h, C.byref(r), read_len, band, C.byref(a), C.byref(b)), "sa_locate_window")
+    return int(a.value), int(b.value)
 
 
 def cigar_load(path):

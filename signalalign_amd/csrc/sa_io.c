@@ -8,6 +8,7 @@
 #define _GNU_SOURCE
 #include "sa_io.h"
 
+#include <ctype.h>
 #include <inttypes.h>
 #include <math.h>
 #include <stdint.h>
@@ -455,6 +456,62 @@ int sa_fasta_subsequence(const char *fasta_path, const char *name, int64_t start
     int err = 0;
     *out = strand ? sa_fasta_fetch(fasta_path, name, start, end - 1, &err) : sa_fasta_fetch(fasta_path, name, end, start - 1, &err);
     if (*out == NULL) return err == -2 ? SA_EINVAL : SA_EIO;
+    return SA_OK;
+}
+
+/* Every record of a FASTA, in file order (what sa_ref_index_build_fasta indexes): a name is the header up to the first white
+ * space, a sequence its lines joined with white space dropped, letters kept as they are.  Needs no .fai. */
+void sa_fasta_records_free(char **names, char **seqs, int64_t *lens, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        if (names) free(names[i]);
+        if (seqs) free(seqs[i]);
+    }
+    free(names); free(seqs); free(lens);
+}
+int sa_fasta_read_all(const char *fasta_path, char ***names_out, char ***seqs_out, int64_t **lens_out, int64_t *n_out) {
+    if (!fasta_path || !names_out || !seqs_out || !lens_out || !n_out) return SA_EINVAL;
+    FILE *fh = fopen(fasta_path, "r");
+    if (!fh) return SA_EIO;
+    char **names = NULL, **seqs = NULL, *line = NULL;
+    int64_t *lens = NULL, n = 0, cap = 0, seq_cap = 0;
+    size_t lcap = 0;
+    ssize_t got;
+    int rc = SA_OK;
+    while (rc == SA_OK && (got = getline(&line, &lcap, fh)) >= 0) {
+        if (line[0] == '>') {
+            if (n == cap) {
+                cap = cap ? cap * 2 : 16;
+                names = realloc(names, sizeof(char *) * (size_t) cap);
+                seqs = realloc(seqs, sizeof(char *) * (size_t) cap);
+                lens = realloc(lens, sizeof(int64_t) * (size_t) cap);
+                if (!names || !seqs || !lens) { rc = SA_ENOMEM; break; }
+            }
+            size_t e = 1;
+            while (line[e] && !isspace((unsigned char) line[e])) e++;
+            names[n] = strndup(line + 1, e - 1);
+            seq_cap = 1024;
+            seqs[n] = malloc((size_t) seq_cap);
+            lens[n] = 0;
+            if (!names[n] || !seqs[n]) rc = SA_ENOMEM;
+            n++;
+            continue;
+        }
+        if (n == 0) continue;   /* text ahead of the first header */
+        if (lens[n - 1] + got + 1 > seq_cap) {
+            while (lens[n - 1] + got + 1 > seq_cap) seq_cap *= 2;
+            char *bigger = realloc(seqs[n - 1], (size_t) seq_cap);
+            if (!bigger) { rc = SA_ENOMEM; break; }
+            seqs[n - 1] = bigger;
+        }
+        for (ssize_t i = 0; i < got; i++)
+            if (!isspace((unsigned char) line[i])) seqs[n - 1][lens[n - 1]++] = line[i];
+    }
+    free(line);
+    fclose(fh);
+    if (rc == SA_OK && n == 0) rc = SA_EIO;
+    if (rc != SA_OK) { sa_fasta_records_free(names, seqs, lens, n); return rc; }
+    for (int64_t i = 0; i < n; i++) seqs[i][lens[i]] = 0;
+    *names_out = names; *seqs_out = seqs; *lens_out = lens; *n_out = n;
     return SA_OK;
 }
 

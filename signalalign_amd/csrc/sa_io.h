@@ -47,6 +47,11 @@ void sa_cigar_free(sa_cigar_t *c);
  * Returns a heap string, NULL if the file/index is unreadable; *err = -2 if the name is not in the index. */
 char *sa_fasta_fetch(const char *fasta_path, const char *name, int64_t start, int64_t end_inclusive, int *err);
 
+/* every record of a FASTA in file order: names up to the first white space, sequences with their lines joined (NUL-terminated);
+ * SA_EIO for a file that cannot be read or holds no record.  sa_fasta_records_free returns all of it. */
+int sa_fasta_read_all(const char *fasta_path, char ***names_out, char ***seqs_out, int64_t **lens_out, int64_t *n_out);
+void sa_fasta_records_free(char **names, char **seqs, int64_t *lens, int64_t n);
+
 /* reverse complement of a nucleotide string (sonLib stString_reverseComplementString: A<->T, C<->G, rest kept) */
 char *sa_reverse_complement(const char *s);
 char *sa_complement(const char *s);

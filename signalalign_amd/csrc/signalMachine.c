@@ -19,6 +19,10 @@
  * manifest's cigar column written as @<contig>:<start>-<end>[:+|:-], names the stretch of the -f reference the read lies in
  * (0-based, half-open, as a cigar's own coordinates); the read is then aligned to it by sa_guide_align_batch, all such reads of
  * a slice in one call, and the result stands in for the cigar file.
+ *
+ * Without a window: --guide-locate instead of -p, or a manifest's cigar column of exactly @.  The -f reference is indexed once per
+ * process (sa_ref_index_build_fasta), all such reads of a slice are located by one sa_guide_locate_batch call, and each gets the
+ * window sa_locate_window names -- from there on it is a read with a guide window.
  */
 #define _GNU_SOURCE
 #include <ctype.h>
@@ -87,6 +91,9 @@ static void usage(void) {
                     "                  with --twoD, else the template read) against that stretch of the -f reference (0-based, half-open);\n"
                     "                  without a strand both are tried.  In a manifest: @<contig>:<start>-<end>[:+|:-] in the cigar column.\n"
                     "                  Not with --rna\n");
+    fprintf(stderr, "--guide-locate: instead of -p or --guide-window: find the read's contig, strand and place in the whole -f reference on\n"
+                    "                  the GPU, then go on as with the --guide-window that names them.  In a manifest: @ alone in the cigar\n"
+                    "                  column.  Needs no -n.  Not with --rna\n");
     fprintf(stderr, "--guide-band <n>: band width of that alignment: 64, 128 (default), 192 or 256\n");
     fprintf(stderr, "--guide-cigars-out <dir>: write every computed guide alignment to <dir>/<label>.cigar (exonerate format, usable with -p)\n");
     fprintf(stderr, "--mea: also write <posteriors file>.mea, the rows of the full output on the maximum expected accuracy path\n");
@@ -403,6 +410,7 @@ typedef struct {
     char *label, *npread_path, *cigar_path, *post_path, *post_path2, *seq_name;
     char *expect[2];      /* [strand]: where -t / -c write the strand's expectations */
     char *guide_window;   /* <contig>:<start>-<end>[:+|:-] instead of a cigar file: the guide alignment is computed (guide_stage) */
+    int guide_locate;     /* neither a cigar file nor a window: locate_stage writes guide_window */
     sa_cigar_t *pA;
     sa_npread_t *np;
     char *forward_seq, *backward_seq;
@@ -660,8 +668,9 @@ static int64_t load_manifest(const char *path, read_t **out) {
         rd->label = strdup(f[0]);
         rd->npread_path = dup_field(f[1]);
         rd->cigar_path = dup_field(f[2]);
-        if (rd->cigar_path && rd->cigar_path[0] == '@') {   /* @<contig>:<start>-<end>[:+|:-]: computed, not read */
-            rd->guide_window = strdup(rd->cigar_path + 1);
+        if (rd->cigar_path && rd->cigar_path[0] == '@') {   /* @<contig>:<start>-<end>[:+|:-]: computed, not read; @ alone: located first */
+            if (rd->cigar_path[1] == 0) rd->guide_locate = 1;
+            else rd->guide_window = strdup(rd->cigar_path + 1);
             free(rd->cigar_path);
             rd->cigar_path = NULL;
         }
@@ -785,7 +794,7 @@ static void guide_prepare_one(int64_t i, void *ctx) {
         return;
     }
     if (R->fwd_ref == NULL) { fail(rd, fatal, "[signalMachine] ERROR: a guide window needs -f <fasta>", NULL); return; }
-    if (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK) {
+    if (rd->np == NULL && (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK)) {   /* (locate_stage loads it too) */
         fail(rd, fatal, "signalMachine: could not load the nanopore read %s", rd->npread_path);
         return;
     }
@@ -825,6 +834,96 @@ static void guide_prepare_one(int64_t i, void *ctx) {
     it->job.ref = it->oriented + it->crop;
     it->job.ref_len = it->w_len - it->crop;
     it->job.diag = diag - it->crop;
+}
+
+/* The -f reference's index: built on first need, once per process, resident on the device until the process ends */
+static sa_ref_index_t *g_ref_index = NULL;
+static int g_ref_index_rc = SA_OK, g_ref_index_tried = 0;
+static pthread_mutex_t g_ref_index_mu = PTHREAD_MUTEX_INITIALIZER;
+
+static int ref_index_get(const run_t *R, sa_ref_index_t **out) {
+    pthread_mutex_lock(&g_ref_index_mu);
+    if (!g_ref_index_tried) {
+        g_ref_index_tried = 1;
+        g_ref_index_rc = sa_ref_index_build_fasta(&g_ref_index, R->fwd_ref, R->device);
+        sa_ref_index_info_t info;
+        if (g_ref_index_rc == SA_OK && sa_ref_index_info(g_ref_index, &info) == SA_OK)
+            fprintf(stderr, "[signalMachine]NOTICE: Indexed %s: %" PRId64 " contigs, %" PRId64 " bases, %" PRId64 " 15-mers, %.2f s\n", R->fwd_ref,
+                    info.n_contigs, info.total_bases, info.n_entries, info.build_seconds);
+    }
+    *out = g_ref_index;
+    const int rc = g_ref_index_rc;
+    pthread_mutex_unlock(&g_ref_index_mu);
+    return rc;
+}
+
+typedef struct {
+    const run_t *R;
+    read_t **rd;
+} locate_ctx_t;
+
+static void locate_load_one(int64_t i, void *ctx) {
+    const locate_ctx_t *c = ctx;
+    read_t *rd = c->rd[i];
+    if (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK)
+        fail(rd, !c->R->batch_mode, "signalMachine: could not load the nanopore read %s", rd->npread_path);
+}
+
+/* The reads of a slice that name neither a cigar file nor a window: ONE sa_guide_locate_batch call against the index of the whole
+ * -f reference; a located read gets the window spec that sa_locate_window gives and is a read with a guide window from there on.
+ * A read without a location fails as a read with an unreadable cigar file does. */
+static void locate_stage(const run_t *R, read_t *reads, int64_t n_reads) {
+    int64_t n = 0;
+    for (int64_t i = 0; i < n_reads; i++) n += reads[i].guide_locate && reads[i].guide_window == NULL && !reads[i].failed;
+    if (n == 0) return;
+    const int fatal = !R->batch_mode;
+    read_t **rd = xalloc(n, sizeof(read_t *), 0);
+    n = 0;
+    for (int64_t i = 0; i < n_reads; i++)
+        if (reads[i].guide_locate && reads[i].guide_window == NULL && !reads[i].failed) rd[n++] = &reads[i];
+    sa_ref_index_t *idx = NULL;
+    int rc = R->fwd_ref == NULL ? SA_EINVAL : ref_index_get(R, &idx);
+    if (rc != SA_OK) {
+        for (int64_t i = 0; i < n; i++)
+            fail(rd[i], fatal, R->fwd_ref == NULL ? "[signalMachine] ERROR: --guide-locate needs -f <fasta>%s"
+                 : "signalMachine: the reference could not be indexed: %s", R->fwd_ref == NULL ? "" : sa_strerror(rc));
+        free(rd);
+        return;
+    }
+    locate_ctx_t ctx = {R, rd};
+    parallel_for(n, locate_load_one, &ctx);
+    const char **seq = xalloc(n, sizeof(char *), 0);
+    int64_t *len = xalloc(n, sizeof(int64_t), 0), *who = xalloc(n, sizeof(int64_t), 0), n_live = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (rd[i]->failed) continue;
+        seq[n_live] = R->two_d ? rd[i]->np->two_d_read : rd[i]->np->template_read;
+        len[n_live] = R->two_d ? rd[i]->np->read_length : rd[i]->np->template_read_length;
+        who[n_live++] = i;
+    }
+    sa_locate_result_t *res = xalloc(n_live, sizeof(sa_locate_result_t), 1);
+    rc = n_live > 0 ? sa_guide_locate_batch(idx, seq, len, n_live, NULL, 0, res, NULL) : SA_OK;
+    for (int64_t q = 0; q < n_live; q++) {
+        read_t *r = rd[who[q]];
+        const sa_locate_result_t *l = &res[q];
+        if (rc != SA_OK) { fail(r, fatal, "signalMachine: the read could not be located: %s", sa_strerror(rc)); continue; }
+        int64_t start = 0, end = 0;
+        const char *contig = NULL;
+        if ((l->status & (SA_LOCATE_NONE | SA_LOCATE_EMPTY)) || sa_locate_window(idx, l, len[q], R->guide_band, &start, &end) != SA_OK ||
+            sa_ref_index_contig(idx, l->contig, &contig, NULL, NULL) != SA_OK) {
+            fail(r, fatal, "signalMachine: no location for the read in %s", R->fwd_ref);
+            continue;
+        }
+        r->guide_window = xalloc((int64_t) strlen(contig) + 64, 1, 0);
+        sprintf(r->guide_window, "%s:%" PRId64 "-%" PRId64 ":%c", contig, start, end, l->reverse ? '-' : '+');
+        fprintf(stderr, "[signalMachine]NOTICE: Read located at %s (%" PRId64 " votes, next %" PRId64 ")\n", r->guide_window, l->votes,
+                l->second_votes);
+        if (l->status & SA_LOCATE_AMBIGUOUS)
+            fprintf(stderr, "[signalMachine]WARNING: the location of %s is ambiguous: another locus has %" PRId64 " votes against %" PRId64 "\n",
+                    r->label, l->second_votes, l->votes);
+        if (l->status & SA_LOCATE_OVERFLOW)
+            fprintf(stderr, "[signalMachine]WARNING: %s has more 15-mer hits than the vote keeps (overflow): the later ones did not vote\n", r->label);
+    }
+    free(res); free(who); free(len); free(seq); free(rd);
 }
 
 /* The reads of a slice that name a window instead of a cigar file: ONE sa_guide_align_batch call, ahead of prepare_read's
@@ -925,6 +1024,7 @@ static void prep_one(int64_t i, void *ctx) {
 static void *slice_prepare(void *arg) {
     slice_t *sl = arg;
     const double ts0 = now_s();
+    locate_stage(sl->R, sl->reads, sl->n_reads);
     guide_stage(sl->R, sl->reads, sl->n_reads);
     parallel_for(sl->n_reads, prep_one, sl);
     t_add(&g_t_prep, now_s() - ts0);
@@ -1977,6 +2077,7 @@ int main(int argc, char **argv) {
     char *t_model = NULL, *c_model = NULL, *label = NULL, *npread_path = NULL, *cigar_path = NULL, *post_path = NULL;
     char *t_expect = NULL, *c_expect = NULL, *t_hdp = NULL, *c_hdp = NULL, *fwd_ref = NULL, *bwd_ref = NULL,
          *post_path2 = NULL, *seq_name = NULL, *ambig_model = NULL, *manifest = NULL, *guide_window = NULL;
+    int guide_locate = 0;
     R.guide_band = 128;
     static struct option long_options[] = {{"help", no_argument, 0, 'h'},
                                            {"sm3Hdp", no_argument, 0, 'd'},
@@ -2026,6 +2127,7 @@ int main(int argc, char **argv) {
                                            {"snp-step", required_argument, 0, 1020},
                                            {"snp-dir", required_argument, 0, 1021},
                                            {"guide-window", required_argument, 0, 1050},
+                                           {"guide-locate", no_argument, 0, 1053},
                                            {"guide-band", required_argument, 0, 1051},
                                            {"guide-cigars-out", required_argument, 0, 1052},
                                            {0, 0, 0, 0}};
@@ -2084,6 +2186,7 @@ int main(int argc, char **argv) {
             case 1021: R.snp_dir = strdup(optarg); break;
             case 1050: guide_window = strdup(optarg); break;
             case 1051: R.guide_band = atoi(optarg); break;
+            case 1053: guide_locate = 1; break;
             case 1052: R.guide_cigars_out = strdup(optarg); break;
             case 1003: batch_reads = atoll(optarg) > 0 ? atoll(optarg) : batch_reads; break;
             case 1004:
@@ -2097,7 +2200,9 @@ int main(int argc, char **argv) {
     if (t_model == NULL || (c_model == NULL && R.two_d)) die("Missing model files, exiting", NULL);
     if (R.out_fmt == 3 && post_path2 == NULL && manifest == NULL) die("Must pass in posteriorProbsFile2 if using 'both' outFmt", NULL);
     if (cigar_path != NULL && guide_window != NULL) die("signalMachine: -p and --guide-window exclude each other%s", "");
-    if (cigar_path == NULL && guide_window == NULL && manifest == NULL)
+    if (guide_locate && (cigar_path != NULL || guide_window != NULL)) die("signalMachine: --guide-locate excludes -p and --guide-window%s", "");
+    if (guide_locate && manifest != NULL) die("signalMachine: --guide-locate is for a single read; in a manifest write @ in the cigar column%s", "");
+    if (cigar_path == NULL && guide_window == NULL && !guide_locate && manifest == NULL)
         die("[signalMachine]ERROR: Need to provide input guide alignments, exiting", NULL);
     if (R.guide_band < 64 || R.guide_band > 256 || R.guide_band % 64 != 0) die("signalMachine: --guide-band takes 64, 128, 192 or 256%s", "");
     R.device = device;
@@ -2126,9 +2231,10 @@ int main(int argc, char **argv) {
         reads[0].post_path = post_path; reads[0].post_path2 = post_path2; reads[0].seq_name = seq_name;
         reads[0].expect[0] = t_expect; reads[0].expect[1] = c_expect;
         reads[0].guide_window = guide_window;
+        reads[0].guide_locate = guide_locate;
         R.expect_mode = t_expect != NULL || c_expect != NULL;
-        if (guide_window != NULL) {
-            if (fwd_ref == NULL) die("[signalMachine] ERROR: --guide-window needs -f <fasta>", NULL);
+        if (guide_window != NULL || guide_locate) {
+            if (fwd_ref == NULL) die(guide_locate ? "[signalMachine] ERROR: --guide-locate needs -f <fasta>" : "[signalMachine] ERROR: --guide-window needs -f <fasta>", NULL);
         } else if (fwd_ref == NULL || seq_name == NULL) {
             /* the reference needs -n; kept after the cigar check so that the error order matches (impl/signalMachine.c:642-663) */
             sa_cigar_t *probe = NULL;
@@ -2139,6 +2245,7 @@ int main(int argc, char **argv) {
         }
     }
     for (int64_t i = 0; i < n_reads; i++) {   /* guide windows: refused before anything runs */
+        if (reads[i].guide_locate && R.rna) die("signalMachine: --guide-locate (@ in a manifest) cannot be combined with --rna: RNA reads need a cigar file%s", "");
         if (reads[i].guide_window == NULL) continue;
         if (R.rna) die("signalMachine: a guide window (%s) cannot be combined with --rna: RNA reads need a cigar file", reads[i].guide_window);
         char *contig = NULL;
@@ -2261,5 +2368,6 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[signalMachine] timing: host stage %.3f s wall (thread-seconds: npRead+cigar parse %.3f, reference fetch "
                         "%.3f, parameter estimation+anchors %.3f), GPU stage %.3f s wall, render+write %.3f s wall\n",
                 g_t_prep, g_ts_parse, g_ts_fetch, g_ts_estimate, g_t_gpu, g_t_render);
+    sa_ref_index_destroy(g_ref_index);
     return n_failed == 0 ? 0 : 1;
 }
