@@ -623,12 +623,7 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
                              const char *const *ambig, int device, unsigned flags, bool deferred,
                              const sa_noise_scale_t *noise = nullptr, bool noise_scaled = false) {
     if (!out || !m || !p) return SA_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    if (device < 0 || device >= ndev) return SA_EINVAL;
+    if (const int rc = sa_device_check(device)) return rc;
     // Threshold 0 keeps every band cell, the ones of posterior 0 included: the default kernels' candidate filter (forward +
     // backward >= checkpoint maximum + log threshold) has no lower bound then and would pass lanes that hold no cell.  Such a
     // batch takes the reference-ordered kernels with host finalisation, which list a diagonal's cells explicitly.

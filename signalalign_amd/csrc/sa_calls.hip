@@ -286,14 +286,14 @@ extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t
                      o_count = L.add(4 * nj), o_off = L.add(8 * (nj + 1)), o_osite = L.add(4 * ns), o_ounits = L.add(8 * ns * stride),
                      o_oprob = L.add(8 * ns * stride), dev_bytes = L.end;
         guard.lock();
-        if ((rc = W.rebind(device)) != SA_OK || (rc = W.events()) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
+        if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
         if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
         const SiteTabs T = sites_tabs(S);
         float kms = 0;
         size_t n_kept = 0, o_hunits = 0, o_hprob = 0;
         if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
         SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_units, 0, 8 * ns * stride, 0));
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         if (nc) hipLaunchKernelGGL(k_site_accum, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
                                    (unsigned long long *) (d + o_units));
         hipLaunchKernelGGL(k_site_final, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
@@ -302,10 +302,9 @@ extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t
         hipLaunchKernelGGL(k_site_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
                            (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_osite),
                            (unsigned long long *) (d + o_ounits), (double *) (d + o_oprob));
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(W.time_end());
         SA_HIP_GOTO_DONE(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms));
         if (kernel_ms_out) *kernel_ms_out = (double) kms;
         // only the kept calls cross PCIe
         n_kept = (size_t) h_off[nj];
@@ -574,23 +573,22 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
     float kms0 = 0, kms1 = 0;
     size_t n_kept = 0;
     SiteTabs T;
-    if ((rc = W.rebind(device)) != SA_OK || (rc = W.events()) != SA_OK || (rc = sites_upload(P, device)) != SA_OK) return rc;
+    if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(P, device)) != SA_OK) return rc;
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
     T = sites_tabs(P);
     if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
     SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_cnt, 0, 2 * 4 * ns1, 0));   // (cnt and fill)
     SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_xmin, 0x7f, 4 * nj, 0));
     SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_xmax, 0xff, 4 * nj, 0));
-    SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+    SA_HIP_GOTO_DONE(W.time_begin());
     if (nc) hipLaunchKernelGGL(k_pos_count, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
                                (unsigned *) (d + o_cnt), (int *) (d + o_xmin), (int *) (d + o_xmax));
     hipLaunchKernelGGL(k_pos_job_scan, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned *) (d + o_cnt), (unsigned *) (d + o_loc),
                        (int *) (d + o_tot));
     hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const int *) (d + o_tot), (long long *) (d + o_base), (int) nj);
-    SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-    SA_HIP_GOTO_DONE(hipGetLastError());
+    SA_HIP_GOTO_DONE(W.time_end());
     SA_HIP_GOTO_DONE(hipMemcpy(h_base.data(), d + o_base, 8 * (nj + 1), hipMemcpyDeviceToHost));
-    SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms0, W.e0, W.e1));
+    SA_HIP_GOTO_DONE(W.time_ms(&kms0));
     {   // the buckets: 8 bytes per (record, covered ambiguous position)
         const size_t n_ent = (size_t) h_base[nj];
         if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_ent, 8 * (n_ent ? n_ent : 1), device) != hipSuccess) {
@@ -599,7 +597,7 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
             goto done;
         }
     }
-    SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+    SA_HIP_GOTO_DONE(W.time_begin());
     if (nc) hipLaunchKernelGGL(k_pos_scatter, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
                                (const unsigned *) (d + o_loc), (const long long *) (d + o_base), (unsigned *) (d + o_fill), d_ent);
     hipLaunchKernelGGL(k_pos_fold, dim3((unsigned) nj), dim3(256), 0, 0, T, (const unsigned *) (d + o_cnt), (const unsigned *) (d + o_loc),
@@ -608,10 +606,9 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
     hipLaunchKernelGGL(k_pos_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned *) (d + o_cnt), (const double *) (d + o_sum),
                        (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_oslot), (unsigned *) (d + o_on),
                        (double *) (d + o_osum), (double *) (d + o_oprob));
-    SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-    SA_HIP_GOTO_DONE(hipGetLastError());
+    SA_HIP_GOTO_DONE(W.time_end());
     SA_HIP_GOTO_DONE(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
-    SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms1, W.e0, W.e1));
+    SA_HIP_GOTO_DONE(W.time_ms(&kms1));
     if (kernel_ms_out) *kernel_ms_out = (double) kms0 + (double) kms1;
     n_kept = (size_t) h_off[nj];
     SA_HIP_GOTO_DONE(hipMemcpy(h_xmin.data(), d + o_xmin, 4 * nj, hipMemcpyDeviceToHost));

@@ -1,23 +1,12 @@
-// What the stages chained onto a finished batch share (sa_mea.hip, sa_calls.hip, sa_train.hip; sa_ea.hip and sa_detect.hip take
-// the error macro): the view of the batch's packed result records where sa_batch_run left them in HBM, the ambiguity table of
-// the site and position calls, the chunks the record kernels run over, the scans, and the layout of a call's device block.
+// What the stages chained onto a finished batch share (sa_mea.hip, sa_calls.hip, sa_train.hip): the view of the batch's packed
+// result records where sa_batch_run left them in HBM, the ambiguity table of the site and position calls, the printed units, the
+// chunks the record kernels run over, and the scans.  The error macro and the layout of a call's device block are sa_scratch.h's.
 #ifndef SA_CHAIN_H
 #define SA_CHAIN_H
 
 #include <algorithm>
 
 #include "sa_scratch.h"
-
-// a failed HIP call inside a function that cleans up at `done:` and returns `rc`
-#define SA_HIP_GOTO_DONE(call)                                                                              \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
-            goto done;                                                                                      \
-        }                                                                                                   \
-    } while (0)
 
 // A finished batch's records on its device: job j's are recs[first[j] .. first[j] + count[j]), in records of 16 bytes or (p8)
 // of 8.  They are read where the run left them, or -- after host finalisation (SA_FLAG_EXACT) or sa_batch_release_device --
@@ -83,17 +72,6 @@ static inline std::vector<SaRecChunk> sa_view_chunks(const SaBatchView &V, long 
     }
     return chunks;
 }
-
-// Running offsets of the arrays that share one block, each starting at a multiple of 256 bytes; `end` is the block's size.
-// Arrays that one copy or memset spans are added as ONE entry and told apart by the caller.
-struct SaLayout {
-    size_t end = 0;
-    size_t add(size_t bytes) {
-        const size_t o = sa_up256(end);
-        end = o + bytes;
-        return o;
-    }
-};
 
 // inclusive scan over the 64 lanes of a wave
 template <class T>

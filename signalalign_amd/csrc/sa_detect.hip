@@ -35,8 +35,7 @@
 #include <mutex>
 #include <vector>
 
-#include "sa_internal.h"
-#include "sa_chain.h"
+#include "sa_scratch.h"
 
 struct DetJob {
     long long raw_off;   // samples (int16) into the raw image, a multiple of 8; also the offset of t1 / t2 / peaks
@@ -237,11 +236,8 @@ __global__ __launch_bounds__(256) void k_det_events(const DetJob *__restrict__ j
 }
 
 // Device and pinned-host scratch of sa_detect_events_batch, kept between calls (sa_scratch.h).
-struct DetWorkspace : SaScratch {
-    void *d_ws = nullptr, *d_ev = nullptr, *h_raw = nullptr, *h_ev = nullptr;
-    size_t d_ws_cap = 0, d_ev_cap = 0, h_raw_cap = 0, h_ev_cap = 0;
-};
-static DetWorkspace g_det_ws;
+enum { DET_WS, DET_EV, DET_HRAW, DET_HEV };
+static SaScratch g_det_ws;
 
 extern "C" void sa_detect_release(void) {
     std::lock_guard<std::mutex> guard(g_det_ws.mu);
@@ -263,13 +259,8 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
     }
     for (int64_t j = 0; j < n_jobs; j++)
         if (!jobs[j].raw || jobs[j].n_samples < 1 || jobs[j].n_samples > 0x7fffffffLL - 8) return SA_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    if (device < 0 || device >= ndev) return SA_EINVAL;
-    if (n_jobs == 0) return SA_OK;
+    int rc = sa_device_check(device);
+    if (rc || n_jobs == 0) return rc;
     const size_t nj = (size_t) n_jobs;
     std::vector<DetJob> hj(nj);
     std::vector<int2> blk;
@@ -286,30 +277,28 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         ps_tot += (long long) J.n + 1;
         for (int b = 0; b < J.n; b += 256) blk.push_back(make_int2((int) j, b));
     }
-    DetWorkspace &W = g_det_ws;
+    SaScratch &W = g_det_ws;
     std::lock_guard<std::mutex> guard(W.mu);
-    int rc = SA_OK;
-    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
-    // device workspace: [jobs | blocks | raw | sum | sumsq | t1 | t2 | peaks | counts | offsets]; events in their own block
-    const size_t o_jobs = 0, o_blk = sa_up256(sizeof(DetJob) * nj), o_raw = sa_up256(o_blk + sizeof(int2) * blk.size()),
-                 o_s = sa_up256(o_raw + sizeof(int16_t) * (size_t) raw_tot), o_q = sa_up256(o_s + sizeof(double) * (size_t) ps_tot),
-                 o_t1 = sa_up256(o_q + sizeof(double) * (size_t) ps_tot), o_t2 = sa_up256(o_t1 + sizeof(float) * (size_t) raw_tot),
-                 o_pk = sa_up256(o_t2 + sizeof(float) * (size_t) raw_tot), o_cnt = sa_up256(o_pk + sizeof(int) * (size_t) raw_tot),
-                 o_off = sa_up256(o_cnt + sizeof(int) * nj), dev_bytes = o_off + sizeof(long long) * (nj + 1);
-    const size_t res_bytes = dev_bytes - o_cnt;   // counts | offsets, one copy back
-    const size_t raw_bytes = sizeof(int16_t) * (size_t) raw_tot;
+    if ((rc = W.rebind(device)) != SA_OK) return rc;
+    // device workspace: [jobs | blocks | raw | sum | sumsq | t1 | t2 | peaks | counts, offsets]; events in their own block.  Counts
+    // and offsets are ONE entry: one copy back
+    SaLayout L;
+    const size_t raw_bytes = sizeof(int16_t) * (size_t) raw_tot, res_bytes = sa_up256(sizeof(int) * nj) + sizeof(long long) * (nj + 1);
+    const size_t o_jobs = L.add(sizeof(DetJob) * nj), o_blk = L.add(sizeof(int2) * blk.size()), o_raw = L.add(raw_bytes),
+                 o_s = L.add(sizeof(double) * (size_t) ps_tot), o_q = L.add(sizeof(double) * (size_t) ps_tot),
+                 o_t1 = L.add(sizeof(float) * (size_t) raw_tot), o_t2 = L.add(sizeof(float) * (size_t) raw_tot),
+                 o_pk = L.add(sizeof(int) * (size_t) raw_tot), o_cnt = L.add(res_bytes), o_off = o_cnt + sa_up256(sizeof(int) * nj);
     float kms = 0;
     long long n_ev_tot = 0;
     const int *h_cnt;
     const long long *h_off;
     const DetEvent *h_ev;
-    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, dev_bytes, device)) != SA_OK) return rc;
+    if ((rc = W.dev(DET_WS, L.end)) != SA_OK) return rc;
     // events: at most one per peak plus one per read, and peaks are fewer than samples
-    if ((rc = W.dev(&W.d_ev, &W.d_ev_cap, sizeof(DetEvent) * (size_t) (raw_tot + (long long) nj), device)) != SA_OK) return rc;
-    if ((rc = W.pin(&W.h_raw, &W.h_raw_cap, raw_bytes > res_bytes ? raw_bytes : res_bytes, device)) != SA_OK) return rc;
-    if ((rc = W.events()) != SA_OK) return rc;
+    if ((rc = W.dev(DET_EV, sizeof(DetEvent) * (size_t) (raw_tot + (long long) nj))) != SA_OK) return rc;
+    if ((rc = W.pin(DET_HRAW, raw_bytes > res_bytes ? raw_bytes : res_bytes)) != SA_OK) return rc;
     {
-        int16_t *hr = (int16_t *) W.h_raw;
+        int16_t *hr = (int16_t *) W.at(DET_HRAW);
         sa_parallel_for(nj, [&](size_t j) {
             const DetJob &J = hj[j];
             memcpy(hr + J.raw_off, jobs[j].raw, sizeof(int16_t) * (size_t) J.n);
@@ -317,7 +306,7 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         });
     }
     {
-        char *d = (char *) W.d_ws;
+        char *d = (char *) W.at(DET_WS);
         const DetJob *d_jobs = (const DetJob *) (d + o_jobs);
         double *d_s = (double *) (d + o_s), *d_q = (double *) (d + o_q);
         float *d_t1 = (float *) (d + o_t1), *d_t2 = (float *) (d + o_t2);
@@ -325,8 +314,8 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         long long *d_off = (long long *) (d + o_off);
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(DetJob) * nj, hipMemcpyHostToDevice, 0));
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_blk, blk.data(), sizeof(int2) * blk.size(), hipMemcpyHostToDevice, 0));
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_raw, W.h_raw, raw_bytes, hipMemcpyHostToDevice, 0));
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_raw, W.at(DET_HRAW), raw_bytes, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         const unsigned lane_blocks = (unsigned) ((nj + DET_LANES - 1) / DET_LANES);
         hipLaunchKernelGGL(k_det_prefix, dim3(lane_blocks), dim3(DET_LANES), 0, 0, d_jobs, (int) nj, (const int16_t *) (d + o_raw), d_s, d_q);
         hipLaunchKernelGGL(k_det_tstat, dim3((unsigned) blk.size()), dim3(256), 0, 0, d_jobs, (const int2 *) (d + o_blk), d_s, d_q, d_t1,
@@ -335,21 +324,20 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
                            P.window_length1, P.window_length2, P.threshold1, P.threshold2, P.peak_height);
         hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, 0, d_cnt, (int) nj, d_off);
         hipLaunchKernelGGL(k_det_events, dim3((unsigned) nj), dim3(256), 0, 0, d_jobs, (const int *) d_pk, (const int *) d_cnt,
-                           (const long long *) d_off, (const double *) d_s, (const double *) d_q, (DetEvent *) W.d_ev);
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_raw, d + o_cnt, res_bytes, hipMemcpyDeviceToHost, 0));   // the raw image is uploaded by now
+                           (const long long *) d_off, (const double *) d_s, (const double *) d_q, (DetEvent *) W.at(DET_EV));
+        SA_HIP_GOTO_DONE(W.time_end());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(DET_HRAW), d + o_cnt, res_bytes, hipMemcpyDeviceToHost, 0));   // the raw image is uploaded by now
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
-        h_cnt = (const int *) W.h_raw;
-        h_off = (const long long *) ((const char *) W.h_raw + (o_off - o_cnt));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms));
+        h_cnt = (const int *) W.at(DET_HRAW);
+        h_off = (const long long *) ((const char *) W.at(DET_HRAW) + (o_off - o_cnt));
         n_ev_tot = h_off[nj];
-        if ((rc = W.pin(&W.h_ev, &W.h_ev_cap, sizeof(DetEvent) * (size_t) n_ev_tot, device)) != SA_OK) goto done;
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_ev, W.d_ev, sizeof(DetEvent) * (size_t) n_ev_tot, hipMemcpyDeviceToHost, 0));
+        if ((rc = W.pin(DET_HEV, sizeof(DetEvent) * (size_t) n_ev_tot)) != SA_OK) goto done;
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(DET_HEV), W.at(DET_EV), sizeof(DetEvent) * (size_t) n_ev_tot, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
-    h_ev = (const DetEvent *) W.h_ev;
+    h_ev = (const DetEvent *) W.at(DET_HEV);
     {
         std::atomic<bool> oom(false);
         sa_parallel_for(nj, [&](size_t j) {

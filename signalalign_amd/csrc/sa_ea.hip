@@ -26,8 +26,7 @@
 #include <mutex>
 #include <vector>
 
-#include "sa_internal.h"
-#include "sa_chain.h"
+#include "sa_scratch.h"
 
 #define EA_BW 100
 #define EA_HALF 50
@@ -427,12 +426,8 @@ __global__ void k_ea_expand(const double *__restrict__ kt, const int32_t *__rest
 }
 
 // Device and pinned-host scratch of sa_event_align_batch, kept between calls (sa_scratch.h).
-struct EaWorkspace : SaScratch {
-    void *d_ws = nullptr, *d_trace = nullptr, *h_in = nullptr, *h_res = nullptr;
-    size_t d_ws_cap = 0, d_trace_cap = 0, h_in_cap = 0, h_res_cap = 0;
-};
-static EaWorkspace g_ea_ws;
-static inline size_t ea_up(size_t x) { return sa_up256(x); }
+enum { EA_WS, EA_TRACE, EA_IN, EA_RES };
+static SaScratch g_ea_ws;
 
 extern "C" void sa_event_align_release(void) {
     std::lock_guard<std::mutex> guard(g_ea_ws.mu);
@@ -444,12 +439,8 @@ extern "C" int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs
                                     double *kernel_ms_out) {
     if (!m || (!jobs && n_jobs > 0) || n_jobs < 0 || !pairs_out || !n_pairs_out) return SA_EINVAL;
     if (m->hdp) return SA_EUNSUPPORTED;  // the reference builds this aligner's state machine without an HDP
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    if (device < 0 || device >= ndev) return SA_EINVAL;
+    int rc = sa_device_check(device);
+    if (rc) return rc;
     for (int64_t j = 0; j < n_jobs; j++) { pairs_out[j] = nullptr; n_pairs_out[j] = 0; if (status_out) status_out[j] = 0; }
     if (n_jobs == 0) return SA_OK;
     // host side: k-mer constants and offsets
@@ -464,15 +455,14 @@ extern "C" int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs
         ev_tot += (size_t) jb->n_events;
         kc_tot += 3 * (size_t) n_kmers;
     }
-    EaWorkspace &W = g_ea_ws;
+    SaScratch &W = g_ea_ws;
     std::lock_guard<std::mutex> guard(W.mu);
-    int rc = SA_OK;
-    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
+    if ((rc = W.rebind(device)) != SA_OK) return rc;
     // pinned upload image: event means | per-model k-mer constants {level mean, level sd, -log(sqrt(2 pi)) - log(sd)} |
     // k-mer id of every position (the device expands ids to per-position constants, k_ea_expand)
     const size_t kt_n = 3 * (size_t) m->n_kmers, in_bytes = sizeof(double) * (ev_tot + kt_n) + sizeof(int32_t) * (kc_tot / 3);
-    if ((rc = W.pin(&W.h_in, &W.h_in_cap, in_bytes, device)) != SA_OK) return rc;
-    double *ev = (double *) W.h_in, *kt = ev + ev_tot;
+    if ((rc = W.pin(EA_IN, in_bytes)) != SA_OK) return rc;
+    double *ev = (double *) W.at(EA_IN), *kt = ev + ev_tot;
     int32_t *ids = (int32_t *) (kt + kt_n);
     for (int64_t id = 0; id < m->n_kmers; id++) {
         const double mu = m->table5[5 * id], sd = m->table5[5 * id + 1];
@@ -524,25 +514,25 @@ extern "C" int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs
     memset(&P, 0, sizeof(P));
     float kms = 0;
     const size_t nj = (size_t) n_jobs;
-    // device workspace, kept between calls (grow only): [jobs | upload image | kc | ll | col | out | n,status,fills] and the trace plane
-    const size_t o_jobs = 0, o_in = ea_up(o_jobs + sizeof(EaJob) * nj), o_kc = ea_up(o_in + in_bytes),
-                 o_ll = ea_up(o_kc + sizeof(double) * kc_tot),
-                 o_col = ea_up(o_ll + sizeof(int) * 2 * (size_t) ll_tot), o_out = ea_up(o_col + sizeof(double) * (size_t) col_tot),
-                 o_res = ea_up(o_out + sizeof(int) * 2 * (size_t) out_tot), dev_bytes = o_res + sizeof(int) * 3 * nj;
-    const size_t res_bytes = dev_bytes - o_out;  // pair lists and the three per-read result words come back in one copy
+    // device workspace, kept between calls (grow only): [jobs | upload image | kc | ll | col | out, n,status,fills] and the trace
+    // plane; the pair lists and the three per-read result words are ONE entry: they come back in one copy
+    SaLayout L;
+    const size_t o_jobs = L.add(sizeof(EaJob) * nj), o_in = L.add(in_bytes), o_kc = L.add(sizeof(double) * kc_tot),
+                 o_ll = L.add(sizeof(int) * 2 * (size_t) ll_tot), o_col = L.add(sizeof(double) * (size_t) col_tot),
+                 res_bytes = sa_up256(sizeof(int) * 2 * (size_t) out_tot) + sizeof(int) * 3 * nj, o_out = L.add(res_bytes),
+                 o_res = o_out + res_bytes - sizeof(int) * 3 * nj;
     const int *h_out, *h_n, *h_st, *h_fills;
-    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, dev_bytes, device)) != SA_OK) goto done;
-    if ((rc = W.dev(&W.d_trace, &W.d_trace_cap, (size_t) trace_tot, device)) != SA_OK) goto done;
-    if ((rc = W.pin(&W.h_res, &W.h_res_cap, res_bytes, device)) != SA_OK) goto done;
-    if ((rc = W.events()) != SA_OK) goto done;
+    if ((rc = W.dev(EA_WS, L.end)) != SA_OK) goto done;
+    if ((rc = W.dev(EA_TRACE, (size_t) trace_tot)) != SA_OK) goto done;
+    if ((rc = W.pin(EA_RES, res_bytes)) != SA_OK) goto done;
     {
-        char *d = (char *) W.d_ws;
+        char *d = (char *) W.at(EA_WS);
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(EaJob) * nj, hipMemcpyHostToDevice, 0));
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.at(EA_IN), in_bytes, hipMemcpyHostToDevice, 0));
         P.jobs = (EaJob *) (d + o_jobs); P.ev = (double *) (d + o_in); P.kc = (double *) (d + o_kc);
-        P.trace = (unsigned char *) W.d_trace; P.ll = (int *) (d + o_ll); P.col = (double *) (d + o_col);
+        P.trace = (unsigned char *) W.at(EA_TRACE); P.ll = (int *) (d + o_ll); P.col = (double *) (d + o_col);
         P.out = (int *) (d + o_out); P.n_out = (int *) (d + o_res); P.status = P.n_out + nj; P.fills = P.status + nj;
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         {
             const long long n_pos = (long long) (kc_tot / 3);
             const double *d_kt = P.ev + ev_tot;
@@ -553,15 +543,14 @@ extern "C" int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs
             hipLaunchKernelGGL(k_event_align<true>, dim3((unsigned) n_jobs), dim3(EA_THREADS), 0, 0, P, (int) n_jobs);
         else
             hipLaunchKernelGGL(k_event_align<false>, dim3((unsigned) n_jobs), dim3(EA_THREADS), 0, 0, P, (int) n_jobs);
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(W.time_end());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(EA_RES), d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
-    h_out = (const int *) W.h_res;
-    h_n = (const int *) ((const char *) W.h_res + (o_res - o_out));
+    h_out = (const int *) W.at(EA_RES);
+    h_n = (const int *) ((const char *) W.at(EA_RES) + (o_res - o_out));
     h_st = h_n + nj; h_fills = h_st + nj;
     if (cells_out)
         for (int64_t j = 0; j < n_jobs; j++) cells_out[j] = (double) h_fills[(size_t) j];

@@ -24,15 +24,6 @@ static int cmp_i64(const void *a, const void *b) {
     const int64_t x = *(const int64_t *) a, y = *(const int64_t *) b;
     return x < y ? -1 : (x > y ? 1 : 0);
 }
-static int base_code(char c) {
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return -1;
-    }
-}
 
 /* the vote of one strand: returns the votes of the modal bin and its neighbours; *diag the median diagonal of those votes */
 static int64_t seed_vote(const seed_kmer_t *rk, int64_t n_rk, int64_t read_bases, const char *win, int64_t win_len, int64_t *diag,
@@ -49,8 +40,8 @@ static int64_t seed_vote(const seed_kmer_t *rk, int64_t n_rk, int64_t read_bases
     int64_t run = 0;   /* letters of ACGT in a row ending here */
     const uint32_t mask = (1u << (2 * SEED_K)) - 1u;
     for (int64_t i = 0; i < win_len; i++) {
-        const int c = base_code(win[i]);
-        if (c < 0) { run = 0; kmer = 0; continue; }
+        const int c = sa_base_code(win[i]);
+        if (c > 3) { run = 0; kmer = 0; continue; }
         kmer = ((kmer << 2) | (uint32_t) c) & mask;
         if (++run < SEED_K) continue;
         const int64_t wpos = i - (SEED_K - 1);
@@ -103,8 +94,8 @@ int sa_guide_seed(const char *read, int64_t read_len, const char *window, int64_
     uint32_t kmer = 0;
     const uint32_t mask = (1u << (2 * SEED_K)) - 1u;
     for (int64_t i = 0; i < bases; i++) {
-        const int c = base_code(read[i]);
-        if (c < 0) { run = 0; kmer = 0; continue; }
+        const int c = sa_base_code(read[i]);
+        if (c > 3) { run = 0; kmer = 0; continue; }
         kmer = ((kmer << 2) | (uint32_t) c) & mask;
         if (++run < SEED_K) continue;
         rk[n_rk].kmer = kmer;

@@ -34,8 +34,7 @@
 #include <mutex>
 #include <vector>
 
-#include "sa_internal.h"
-#include "sa_chain.h"
+#include "sa_io.h"
 #include "sa_scratch.h"
 
 #define GD_NEG (-(1 << 30))
@@ -292,11 +291,8 @@ __global__ __launch_bounds__(64) void k_guide_align(GdPlan P, int n_jobs) {
     if (lane == 0) P.res[job] = res;
 }
 
-struct GdWorkspace : SaScratch {
-    void *d_ws = nullptr, *d_trace = nullptr, *h_in = nullptr, *h_res = nullptr;
-    size_t d_ws_cap = 0, d_trace_cap = 0, h_in_cap = 0, h_res_cap = 0;
-};
-static GdWorkspace g_gd_ws;
+enum { GD_WS, GD_TRACE, GD_IN, GD_RES };
+static SaScratch g_gd_ws;
 
 extern "C" void sa_guide_release(void) {
     std::lock_guard<std::mutex> guard(g_gd_ws.mu);
@@ -305,13 +301,11 @@ extern "C" void sa_guide_release(void) {
 
 static size_t gd_row_bytes(int band) { return band <= 128 ? 64 : 128; }
 
-// one slice of the batch: jobs [j0, j1) share the trace plane
-static int gd_run_slice(GdWorkspace &W, const sa_guide_job_t *jobs, const std::vector<GdJob> &hj, int64_t j0, int64_t j1,
-                        const sa_guide_params_t &prm, int device, std::vector<GdRes> &res, std::vector<std::vector<unsigned int>> &ops,
-                        double *kernel_ms) {
+// one slice of the batch, as dense arrays: its jobs share the trace plane
+static int gd_run_slice(SaScratch &W, const sa_guide_job_t *jobs, std::vector<GdJob> &sj, const sa_guide_params_t &prm,
+                        std::vector<GdRes> &res, std::vector<std::vector<unsigned int>> &ops, double *kernel_ms) {
     int rc = SA_OK;
-    const size_t nj = (size_t) (j1 - j0);
-    std::vector<GdJob> sj(hj.begin() + j0, hj.begin() + j1);
+    const size_t nj = sj.size();
     size_t code_tot = 0, ll_tot = 0, op_tot = 0, trace_tot = 0;
     const size_t rb = gd_row_bytes(prm.band);
     for (GdJob &J : sj) {
@@ -321,51 +315,45 @@ static int gd_run_slice(GdWorkspace &W, const sa_guide_job_t *jobs, const std::v
         J.trace_off = (long long) trace_tot; trace_tot += sa_up256(((size_t) J.n_bands + 1) * rb);
     }
     const size_t in_bytes = sa_up256(sizeof(GdJob) * nj) + code_tot;
-    if ((rc = W.pin(&W.h_in, &W.h_in_cap, in_bytes, device)) != SA_OK) return rc;
-    memcpy(W.h_in, sj.data(), sizeof(GdJob) * nj);
-    unsigned char *codes = (unsigned char *) W.h_in + sa_up256(sizeof(GdJob) * nj);
-    static unsigned char code_of[256];
-    static std::once_flag once;
-    std::call_once(once, [] {
-        memset(code_of, 4, sizeof(code_of));
-        const char *up = "ACGT", *low = "acgt";
-        for (int i = 0; i < 4; i++) { code_of[(unsigned char) up[i]] = (unsigned char) i; code_of[(unsigned char) low[i]] = (unsigned char) i; }
-    });
+    if ((rc = W.pin(GD_IN, in_bytes)) != SA_OK) return rc;
+    memcpy(W.at(GD_IN), sj.data(), sizeof(GdJob) * nj);
+    unsigned char *codes = (unsigned char *) W.at(GD_IN) + sa_up256(sizeof(GdJob) * nj);
     sa_parallel_for(nj, [&](size_t k) {
-        const sa_guide_job_t &jb = jobs[j0 + (int64_t) k];
+        const sa_guide_job_t &jb = jobs[k];
         unsigned char *dst = codes + sj[k].code_off;
-        for (int64_t i = 0; i < jb.read_len; i++) dst[i] = code_of[(unsigned char) jb.read[i]];
+        for (int64_t i = 0; i < jb.read_len; i++) dst[i] = (unsigned char) sa_base_code(jb.read[i]);
         dst += jb.read_len;
-        for (int64_t i = 0; i < jb.ref_len; i++) dst[i] = code_of[(unsigned char) jb.ref[i]];
+        for (int64_t i = 0; i < jb.ref_len; i++) dst[i] = (unsigned char) sa_base_code(jb.ref[i]);
     });
-    // device workspace: [jobs | codes] (the upload image) | ll | operations | results; the trace plane is a slot of its own
-    const size_t o_in = 0, o_ll = sa_up256(o_in + in_bytes), o_ops = sa_up256(o_ll + sizeof(int) * ll_tot),
-                 o_res = sa_up256(o_ops + sizeof(unsigned int) * op_tot), dev_bytes = o_res + sizeof(GdRes) * nj;
-    const size_t back_bytes = dev_bytes - o_ops;
+    // device workspace: [jobs, codes] (the upload image) | ll | operations, results; the trace plane is a slot of its own.  The
+    // operations and the results are ONE entry: they come back in one copy
+    SaLayout L;
+    const size_t back_bytes = sa_up256(sizeof(unsigned int) * op_tot) + sizeof(GdRes) * nj;
+    const size_t o_in = L.add(in_bytes), o_ll = L.add(sizeof(int) * ll_tot), o_ops = L.add(back_bytes),
+                 o_res = o_ops + sa_up256(sizeof(unsigned int) * op_tot);
     float kms = 0;
     GdPlan P;
     memset(&P, 0, sizeof(P));
-    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, dev_bytes, device)) != SA_OK) return rc;
-    rc = W.dev(&W.d_trace, &W.d_trace_cap, trace_tot, device);
+    if ((rc = W.dev(GD_WS, L.end)) != SA_OK) return rc;
+    rc = W.dev(GD_TRACE, trace_tot);
     if (rc == SA_ENOMEM) {   // the caching allocator's parked blocks count as free memory: hand them back and try once more
         g_sa_pool.release(SaPool::DEVICE);
-        rc = W.dev(&W.d_trace, &W.d_trace_cap, trace_tot, device);
+        rc = W.dev(GD_TRACE, trace_tot);
     }
     if (rc != SA_OK) return rc;
-    if ((rc = W.pin(&W.h_res, &W.h_res_cap, back_bytes, device)) != SA_OK) return rc;
-    if ((rc = W.events()) != SA_OK) return rc;
+    if ((rc = W.pin(GD_RES, back_bytes)) != SA_OK) return rc;
     {
-        char *d = (char *) W.d_ws;
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
+        char *d = (char *) W.at(GD_WS);
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.at(GD_IN), in_bytes, hipMemcpyHostToDevice, 0));
         P.jobs = (const GdJob *) (d + o_in);
         P.codes = (const unsigned char *) (d + o_in + sa_up256(sizeof(GdJob) * nj));
-        P.trace = (unsigned char *) W.d_trace;
+        P.trace = (unsigned char *) W.at(GD_TRACE);
         P.ll = (int *) (d + o_ll);
         P.ops = (unsigned int *) (d + o_ops);
         P.res = (GdRes *) (d + o_res);
         P.match = prm.match; P.mismatch = prm.mismatch; P.amb = prm.ambiguous;
         P.gap_first = prm.gap_open + prm.gap_extend; P.gap_ext = prm.gap_extend;
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         const dim3 grid((unsigned) nj), block(64);
         switch (prm.band / 64) {
             case 1: hipLaunchKernelGGL(k_guide_align<1>, grid, block, 0, 0, P, (int) nj); break;
@@ -373,22 +361,21 @@ static int gd_run_slice(GdWorkspace &W, const sa_guide_job_t *jobs, const std::v
             case 3: hipLaunchKernelGGL(k_guide_align<3>, grid, block, 0, 0, P, (int) nj); break;
             default: hipLaunchKernelGGL(k_guide_align<4>, grid, block, 0, 0, P, (int) nj); break;
         }
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_ops, back_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(W.time_end());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(GD_RES), d + o_ops, back_bytes, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms));
     }
     *kernel_ms += (double) kms;
     {
-        const unsigned int *h_ops = (const unsigned int *) W.h_res;
-        const GdRes *h_res = (const GdRes *) ((const char *) W.h_res + (o_res - o_ops));
+        const unsigned int *h_ops = (const unsigned int *) W.at(GD_RES);
+        const GdRes *h_res = (const GdRes *) ((const char *) W.at(GD_RES) + (o_res - o_ops));
         for (size_t k = 0; k < nj; k++) {
             GdRes r = h_res[k];
             if (r.n_ops < 0 || r.n_ops > sj[k].op_cap) { r.n_ops = 0; r.status |= SA_GUIDE_TRACE; }
-            res[(size_t) j0 + k] = r;
+            res[k] = r;
             const unsigned int *src = h_ops + sj[k].op_off + (sj[k].op_cap - r.n_ops);
-            ops[(size_t) j0 + k].assign(src, src + r.n_ops);
+            ops[k].assign(src, src + r.n_ops);
         }
     }
 done:
@@ -416,12 +403,8 @@ extern "C" int sa_guide_align_batch(const sa_guide_job_t *jobs, int64_t n_jobs, 
     *op_type_out = nullptr;
     *op_len_out = nullptr;
     if (kernel_ms_out) *kernel_ms_out = 0.0;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    if (device < 0 || device >= ndev) return SA_EINVAL;
+    int rc = sa_device_check(device);
+    if (rc) return rc;
     std::vector<GdJob> hj((size_t) n_jobs);
     std::vector<GdRes> res((size_t) n_jobs);
     std::vector<std::vector<unsigned int>> ops((size_t) n_jobs);
@@ -439,17 +422,17 @@ extern "C" int sa_guide_align_batch(const sa_guide_job_t *jobs, int64_t n_jobs, 
         J.op_cap = J.n_bands + 2;
         live.push_back(j);
     }
-    GdWorkspace &W = g_gd_ws;
+    SaScratch &W = g_gd_ws;
     std::lock_guard<std::mutex> guard(W.mu);
-    int rc = SA_OK;
     double kms = 0.0;
     if (!live.empty()) {
         // slices: consecutive jobs whose trace fits three quarters of what is free (this workspace's own plane counts as free)
         int64_t free_b = 0, total_b = 0;
         if ((rc = sa_device_memory(device, &free_b, &total_b)) != SA_OK) return rc;
-        size_t budget = (size_t) ((double) ((size_t) free_b + W.d_trace_cap) * 0.75);
+        size_t budget = (size_t) ((double) ((size_t) free_b + W.cap(GD_TRACE)) * 0.75);
+        if ((rc = W.rebind(device)) != SA_OK) return rc;
         if (const char *e = getenv("SA_GUIDE_TRACE_MB")) budget = (size_t) (atof(e) * 1048576.0);   // (tests: several slices)
-        // the jobs of a slice are compacted: gd_run_slice works on a dense array
+        // the jobs of a slice are compacted: gd_run_slice works on dense arrays
         std::vector<sa_guide_job_t> cj;
         std::vector<GdJob> ch;
         std::vector<int64_t> who;
@@ -467,7 +450,7 @@ extern "C" int sa_guide_align_batch(const sa_guide_job_t *jobs, int64_t n_jobs, 
             for (size_t q = a; q < z; q++) { cj.push_back(jobs[live[q]]); ch.push_back(hj[(size_t) live[q]]); who.push_back(live[q]); }
             std::vector<GdRes> sres(z - a);
             std::vector<std::vector<unsigned int>> sops(z - a);
-            rc = gd_run_slice(W, cj.data(), ch, 0, (int64_t) (z - a), prm, device, sres, sops, &kms);
+            rc = gd_run_slice(W, cj.data(), ch, prm, sres, sops, &kms);
             for (size_t q = 0; q < z - a && rc == SA_OK; q++) { res[(size_t) who[q]] = sres[q]; ops[(size_t) who[q]].swap(sops[q]); }
             a = z;
         }

@@ -5,9 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
-#include "signalalign_hip.h"
+#include "sa_scratch.h"
 
 struct DevBuf {
     void *p = nullptr;
@@ -19,13 +17,11 @@ struct DevBuf {
     }
 };
 
+// (the HDP calls answer a device that is out of range as they answer a missing one, the line on stderr included)
 static inline int use_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        (void) hipGetLastError();
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
+    const int rc = sa_device_check(device);
+    if (rc == SA_EINVAL) fprintf(stderr, SA_NO_DEVICE_LINE);
+    if (rc) return SA_ENODEVICE;
     return hipSetDevice(device) == hipSuccess ? SA_OK : SA_ENODEVICE;
 }
 

@@ -278,11 +278,8 @@ void launch_pairs(int metric, hipStream_t st, const double *grid, int G, const d
 
 // Device and pinned-host scratch of sa_hdp_distances, kept between calls (sa_scratch.h): the rows, and two slabs of triangular
 // output with a pinned buffer each -- band k's kernel fills one slab while band k - 1's leaves the other.
-struct DistWorkspace : SaScratch {
-    void *d_rows = nullptr, *d_grid = nullptr, *d_slab[2] = {nullptr, nullptr}, *h_slab[2] = {nullptr, nullptr};
-    size_t d_rows_cap = 0, d_grid_cap = 0, d_slab_cap[2] = {0, 0}, h_slab_cap[2] = {0, 0};
-};
-DistWorkspace g_dist_ws;
+enum { DS_ROWS, DS_GRID, DS_SLAB, DS_HSLAB = DS_SLAB + 2 };   // (two slabs, two pinned buffers)
+SaScratch g_dist_ws;
 
 struct Band {
     long long tile_first, n_tiles, out_base, n_out;
@@ -299,8 +296,8 @@ size_t slab_doubles() {
 }
 
 // all-pairs distances of rows already on the device; tri_out is ordinary host memory
-int distances_from_device(DistWorkspace &W, const double *d_grid, int64_t G, const double *d_rows, int64_t n, int metric, int device,
-                          double *tri_out, double *kernel_ms_out) {
+int distances_from_device(SaScratch &W, const double *d_grid, int64_t G, const double *d_rows, int64_t n, int metric, double *tri_out,
+                          double *kernel_ms_out) {
     const long long n_tile_rows = (n + DT_TILE - 1) / DT_TILE;
     const size_t cap = slab_doubles();
     std::vector<Band> bands;
@@ -320,8 +317,8 @@ int distances_from_device(DistWorkspace &W, const double *d_grid, int64_t G, con
     int rc;
     const int n_slabs = bands.size() > 1 ? 2 : 1;
     for (int k = 0; k < n_slabs; k++) {
-        if ((rc = W.dev(&W.d_slab[k], &W.d_slab_cap[k], sizeof(double) * need, device))) return rc;
-        if ((rc = W.pin(&W.h_slab[k], &W.h_slab_cap[k], sizeof(double) * need, device))) return rc;
+        if ((rc = W.dev(DS_SLAB + k, sizeof(double) * need))) return rc;
+        if ((rc = W.pin(DS_HSLAB + k, sizeof(double) * need))) return rc;
     }
     hipStream_t s_kernel = nullptr, s_copy = nullptr;
     hipEvent_t k0[2] = {nullptr, nullptr}, k1[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
@@ -338,7 +335,7 @@ int distances_from_device(DistWorkspace &W, const double *d_grid, int64_t G, con
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, k0[k], k1[k]) != hipSuccess) return false;
         kernel_ms += (double) ms;
-        memcpy(tri_out + bands[b].out_base, W.h_slab[k], sizeof(double) * (size_t) bands[b].n_out);
+        memcpy(tri_out + bands[b].out_base, W.at(DS_HSLAB + k), sizeof(double) * (size_t) bands[b].n_out);
         return true;
     };
     for (size_t b = 0; b < bands.size() && ok; b++) {
@@ -346,11 +343,11 @@ int distances_from_device(DistWorkspace &W, const double *d_grid, int64_t G, con
         const Band &B = bands[b];
         if (b >= 2) ok = hipStreamWaitEvent(s_kernel, copied[k], 0) == hipSuccess;
         ok = ok && hipEventRecord(k0[k], s_kernel) == hipSuccess;
-        if (ok) launch_tiles(metric, s_kernel, (unsigned) B.n_tiles, d_grid, (int) G, d_rows, (long long) n, B.tile_first, B.out_base, (double *) W.d_slab[k]);
+        if (ok) launch_tiles(metric, s_kernel, (unsigned) B.n_tiles, d_grid, (int) G, d_rows, (long long) n, B.tile_first, B.out_base, (double *) W.at(DS_SLAB + k));
         ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(k1[k], s_kernel) == hipSuccess;
         if (b >= 1) ok = ok && collect(b - 1);   // (frees the pinned buffer band b + 1 copies into)
         ok = ok && hipStreamWaitEvent(s_copy, k1[k], 0) == hipSuccess &&
-             hipMemcpyAsync(W.h_slab[k], W.d_slab[k], sizeof(double) * (size_t) B.n_out, hipMemcpyDeviceToHost, s_copy) == hipSuccess &&
+             hipMemcpyAsync(W.at(DS_HSLAB + k), W.at(DS_SLAB + k), sizeof(double) * (size_t) B.n_out, hipMemcpyDeviceToHost, s_copy) == hipSuccess &&
              hipEventRecord(copied[k], s_copy) == hipSuccess;
     }
     if (ok && !bands.empty()) ok = collect(bands.size() - 1);
@@ -448,15 +445,14 @@ extern "C" int sa_hdp_distances(const double *grid, int64_t grid_length, const d
     if (n_rows == 1) return SA_OK;   // (no pair: nothing to write)
     int rc = use_device(device);
     if (rc) return rc;
-    DistWorkspace &W = g_dist_ws;
+    SaScratch &W = g_dist_ws;
     std::lock_guard<std::mutex> guard(W.mu);
     const size_t plane = sizeof(double) * (size_t) n_rows * (size_t) grid_length;
-    if ((rc = W.dev(&W.d_rows, &W.d_rows_cap, plane, device)) || (rc = W.dev(&W.d_grid, &W.d_grid_cap, sizeof(double) * (size_t) grid_length, device)))
-        return rc;
-    if (hipMemcpy(W.d_rows, rows, plane, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(W.d_grid, grid, sizeof(double) * (size_t) grid_length, hipMemcpyHostToDevice) != hipSuccess)
+    if ((rc = W.rebind(device)) || (rc = W.dev(DS_ROWS, plane)) || (rc = W.dev(DS_GRID, sizeof(double) * (size_t) grid_length))) return rc;
+    if (hipMemcpy(W.at(DS_ROWS), rows, plane, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(W.at(DS_GRID), grid, sizeof(double) * (size_t) grid_length, hipMemcpyHostToDevice) != hipSuccess)
         return SA_ENODEVICE;
-    return distances_from_device(W, (const double *) W.d_grid, grid_length, (const double *) W.d_rows, n_rows, metric, device, tri_out,
+    return distances_from_device(W, (const double *) W.at(DS_GRID), grid_length, (const double *) W.at(DS_ROWS), n_rows, metric, tri_out,
                                  kernel_ms_out);
 }
 

@@ -1251,10 +1251,18 @@ int sa_device_count(void) {
     return n;
 }
 
-int sa_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes) {
+int sa_device_check(int device, bool quiet) {
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return SA_ENODEVICE;
-    if (device < 0 || device >= n) return SA_EINVAL;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        (void) hipGetLastError();
+        if (!quiet) fprintf(stderr, SA_NO_DEVICE_LINE);
+        return SA_ENODEVICE;
+    }
+    return device < 0 || device >= n ? SA_EINVAL : SA_OK;
+}
+
+int sa_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes) {
+    if (const int rc = sa_device_check(device, /* quiet */ true)) return rc;
     HIPCHK(hipSetDevice(device));
     size_t f = 0, t = 0;
     HIPCHK(hipMemGetInfo(&f, &t));

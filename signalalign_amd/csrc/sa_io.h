@@ -52,6 +52,10 @@ char *sa_fasta_fetch(const char *fasta_path, const char *name, int64_t start, in
 int sa_fasta_read_all(const char *fasta_path, char ***names_out, char ***seqs_out, int64_t **lens_out, int64_t *n_out);
 void sa_fasta_records_free(char **names, char **seqs, int64_t *lens, int64_t n);
 
+/* letter code of the guide and locate stages: ACGTacgt -> 0..3, everything else 4 (the table is sa_io.c's) */
+extern const unsigned char sa_base_code_of[256] __attribute__((visibility("hidden")));
+static inline int sa_base_code(char c) { return sa_base_code_of[(unsigned char) c]; }
+
 /* reverse complement of a nucleotide string (sonLib stString_reverseComplementString: A<->T, C<->G, rest kept) */
 char *sa_reverse_complement(const char *s);
 char *sa_complement(const char *s);

@@ -14,16 +14,6 @@
 #define K SA_LOCATE_K
 #define MAX_TOTAL (((int64_t) 1 << 31) - ((int64_t) 1 << 16))
 
-static int base_code(char c) {
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return -1;
-    }
-}
-
 static double now_seconds(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -36,8 +26,8 @@ static int64_t contig_entries(const char *seq, int64_t len, int64_t start, uint3
     uint32_t kmer = 0;
     int64_t run = 0, n = 0;
     for (int64_t i = 0; i < len; i++) {
-        const int c = base_code(seq[i]);
-        if (c < 0) { run = 0; kmer = 0; continue; }
+        const int c = sa_base_code(seq[i]);
+        if (c > 3) { run = 0; kmer = 0; continue; }
         kmer = ((kmer << 2) | (uint32_t) c) & mask;
         if (++run < K) continue;
         if (codes) { codes[at + n] = kmer; pos[at + n] = (int32_t) (start + i - (K - 1)); }

@@ -36,8 +36,7 @@
 #include <mutex>
 #include <vector>
 
-#include "sa_internal.h"
-#include "sa_chain.h"
+#include "sa_io.h"
 #include "sa_scratch.h"
 #include "sa_locate.h"
 
@@ -330,16 +329,6 @@ __global__ __launch_bounds__(LC_THREADS) void k_guide_locate(LcPlan P, int n_job
 }
 
 // ---- the index's device copy ---------------------------------------------------------------------------------------------------
-static int lc_device_ok(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void) hipGetLastError();
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    return device >= ndev ? SA_EINVAL : SA_OK;
-}
-
 extern "C" void sa_locate_drop_device(struct sa_ref_index *idx) {
     if (!idx || idx->device < 0 || !idx->d_codes) return;
     (void) hipSetDevice(idx->device);
@@ -349,7 +338,7 @@ extern "C" void sa_locate_drop_device(struct sa_ref_index *idx) {
 }
 
 extern "C" int sa_locate_upload(struct sa_ref_index *idx) {
-    int rc = lc_device_ok(idx->device);
+    int rc = sa_device_check(idx->device);
     if (rc != SA_OK) return rc;
     const size_t n = (size_t) idx->n_entries, nt = ((size_t) 1 << idx->q) + 1, nc = (size_t) idx->n_contigs + 1;
     std::vector<int> starts(nc);
@@ -375,11 +364,8 @@ done:
 }
 
 // ---- the batch call --------------------------------------------------------------------------------------------------------------
-struct LcWorkspace : SaScratch {
-    void *d_ws = nullptr, *h_in = nullptr, *h_res = nullptr;
-    size_t d_ws_cap = 0, h_in_cap = 0, h_res_cap = 0;
-};
-static LcWorkspace g_lc_ws;
+enum { LC_WS, LC_IN, LC_RES };
+static SaScratch g_lc_ws;
 
 extern "C" void sa_locate_release(void) {
     std::lock_guard<std::mutex> guard(g_lc_ws.mu);
@@ -403,7 +389,7 @@ extern "C" int sa_guide_locate_batch(const sa_ref_index_t *idx, const char *cons
         fprintf(stderr, "[signalalign_hip] the reference index was built without a device; this library has no CPU fallback\n");
         return SA_ENODEVICE;
     }
-    int rc = lc_device_ok(idx->device);
+    int rc = sa_device_check(idx->device);
     if (rc != SA_OK) return rc;
     std::vector<LcJob> jobs;
     std::vector<int64_t> who;   // the reads that reach the device: a read shorter than a seed is answered here
@@ -422,36 +408,29 @@ extern "C" int sa_guide_locate_batch(const sa_ref_index_t *idx, const char *cons
     }
     const size_t nj = jobs.size();
     if (nj == 0) return SA_OK;
-    LcWorkspace &W = g_lc_ws;
+    SaScratch &W = g_lc_ws;
     std::lock_guard<std::mutex> guard(W.mu);
-    // the upload image: [jobs | letter codes]; the device workspace holds it and the results behind it
-    const size_t o_codes = sa_up256(sizeof(LcJob) * nj), in_bytes = o_codes + code_tot, o_res = sa_up256(in_bytes),
-                 res_bytes = sizeof(LcRes) * nj;
-    if ((rc = W.pin(&W.h_in, &W.h_in_cap, in_bytes, idx->device)) != SA_OK) return rc;
-    if ((rc = W.pin(&W.h_res, &W.h_res_cap, res_bytes, idx->device)) != SA_OK) return rc;
-    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, o_res + res_bytes, idx->device)) != SA_OK) return rc;
-    if ((rc = W.events()) != SA_OK) return rc;
-    memcpy(W.h_in, jobs.data(), sizeof(LcJob) * nj);
-    static unsigned char code_of[256];
-    static std::once_flag once;
-    std::call_once(once, [] {
-        memset(code_of, 4, sizeof(code_of));
-        const char *up = "ACGT", *low = "acgt";
-        for (int i = 0; i < 4; i++) { code_of[(unsigned char) up[i]] = (unsigned char) i; code_of[(unsigned char) low[i]] = (unsigned char) i; }
-    });
-    unsigned char *codes = (unsigned char *) W.h_in + o_codes;
+    // the upload image: [jobs, letter codes], ONE entry of the device workspace; the results behind it
+    SaLayout L;
+    const size_t o_codes = sa_up256(sizeof(LcJob) * nj), in_bytes = o_codes + code_tot, res_bytes = sizeof(LcRes) * nj;
+    const size_t o_in = L.add(in_bytes), o_res = L.add(res_bytes);
+    if ((rc = W.rebind(idx->device)) != SA_OK || (rc = W.pin(LC_IN, in_bytes)) != SA_OK) return rc;
+    if ((rc = W.pin(LC_RES, res_bytes)) != SA_OK) return rc;
+    if ((rc = W.dev(LC_WS, L.end)) != SA_OK) return rc;
+    memcpy(W.at(LC_IN), jobs.data(), sizeof(LcJob) * nj);
+    unsigned char *codes = (unsigned char *) W.at(LC_IN) + o_codes;
     sa_parallel_for(nj, [&](size_t k) {
         const char *src = reads[who[k]];
         unsigned char *dst = codes + jobs[k].code_off;
-        for (int i = 0; i < jobs[k].n; i++) dst[i] = code_of[(unsigned char) src[i]];
+        for (int i = 0; i < jobs[k].n; i++) dst[i] = (unsigned char) sa_base_code(src[i]);
     });
     float kms = 0;
     {
-        char *d = (char *) W.d_ws;
+        char *d = (char *) W.at(LC_WS);
         LcPlan P;
         memset(&P, 0, sizeof(P));
-        P.jobs = (const LcJob *) d;
-        P.codes = (const unsigned char *) (d + o_codes);
+        P.jobs = (const LcJob *) (d + o_in);
+        P.codes = (const unsigned char *) (d + o_in + o_codes);
         P.ix_codes = (const unsigned int *) idx->d_codes;
         P.ix_pos = (const int *) idx->d_pos;
         P.ix_table = (const int *) idx->d_table;
@@ -459,18 +438,17 @@ extern "C" int sa_guide_locate_batch(const sa_ref_index_t *idx, const char *cons
         P.res = (LcRes *) (d + o_res);
         P.n_entries = (int) idx->n_entries; P.q = idx->q; P.n_contigs = (int) idx->n_contigs; P.total = (int) idx->total;
         P.max_occ = prm.max_occ; P.span = prm.span; P.min_votes = prm.min_votes; P.max_hits = prm.max_hits;
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(d, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.at(LC_IN), in_bytes, hipMemcpyHostToDevice, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         hipLaunchKernelGGL(k_guide_locate, dim3((unsigned) nj), dim3(LC_THREADS), 0, 0, P, (int) nj);
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_res, res_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(W.time_end());
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(LC_RES), d + o_res, res_bytes, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
     for (size_t k = 0; k < nj; k++) {
-        const LcRes &r = ((const LcRes *) W.h_res)[k];
+        const LcRes &r = ((const LcRes *) W.at(LC_RES))[k];
         sa_locate_result_t &o = out[who[k]];
         o.status = r.status; o.contig = r.contig; o.reverse = r.reverse; o.pos = r.pos; o.key = r.key; o.votes = r.votes;
         o.second_votes = r.second_votes; o.hits = r.hits; o.seeds = r.seeds; o.repetitive = r.repetitive;

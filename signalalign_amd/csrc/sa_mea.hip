@@ -567,11 +567,8 @@ done:
 #undef FRONT
 }
 
-struct MeaWorkspace : SaScratch {
-    void *d_ws = nullptr, *d_gf = nullptr, *h_in = nullptr, *h_res = nullptr;
-    size_t d_ws_cap = 0, d_gf_cap = 0, h_in_cap = 0, h_res_cap = 0;
-};
-static MeaWorkspace g_mea_ws;
+enum { MEA_WS, MEA_GF, MEA_IN, MEA_RES, MEA_AUX };   // (MEA_AUX: the chained call's)
+static SaScratch g_mea_ws;
 
 static void mea_chain_release();
 extern "C" void sa_mea_release(void) {
@@ -585,8 +582,8 @@ extern "C" void sa_mea_release(void) {
 // Three tiers of the same algorithm: fronts in registers (64 edges), in LDS (256), in global memory (any length); a read
 // whose front outgrows a tier is handed to the next one.  SA_MEA_TIER=1|2 starts lower (tests).  h_status: pinned, one
 // word per read.
-static int mea_run_tiers(MeaWorkspace &W, MeaPlan &P, std::vector<MeaJob> &hj, char *d, size_t o_jobs, size_t o_ids,
-                         int *h_status, int device, float *kms_out) {
+static int mea_run_tiers(SaScratch &W, MeaPlan &P, std::vector<MeaJob> &hj, char *d, size_t o_jobs, size_t o_ids, int *h_status,
+                         float *kms_out) {
     const size_t nj = hj.size();
     int rc = SA_OK;
     float kms2 = 0;
@@ -605,12 +602,12 @@ static int mea_run_tiers(MeaWorkspace &W, MeaPlan &P, std::vector<MeaJob> &hj, c
                 hj[j].gf_off = (long long) gf_tot;
                 gf_tot += 2 * ((size_t) hj[j].n + 2);
             }
-            if ((rc = W.dev(&W.d_gf, &W.d_gf_cap, sizeof(MeaEdge) * gf_tot, device)) != SA_OK) goto done;
-            P.gf = (MeaEdge *) W.d_gf;
+            if ((rc = W.dev(MEA_GF, sizeof(MeaEdge) * gf_tot)) != SA_OK) goto done;
+            P.gf = (MeaEdge *) W.at(MEA_GF);
             SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
         }
         if (!all) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_ids, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, 0));
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         if (tier == 0) {
             if (!all) { rc = SA_EINVAL; goto done; }   // the register tier is only ever the first
             hipLaunchKernelGGL(k_mea_wave, dim3(grid), dim3(64), 0, 0, P, (int) nj);
@@ -619,11 +616,10 @@ static int mea_run_tiers(MeaWorkspace &W, MeaPlan &P, std::vector<MeaJob> &hj, c
         } else {
             hipLaunchKernelGGL(k_mea<true>, dim3(grid), dim3(64), 0, 0, P, d_ids, (int) grid);
         }
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(W.time_end());
         SA_HIP_GOTO_DONE(hipMemcpyAsync(h_status, P.status, 4 * nj, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms2, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms2));
         *kms_out += kms2;
         redo.clear();
         for (size_t j = 0; j < nj; j++)
@@ -640,12 +636,8 @@ extern "C" int sa_mea_batch(const sa_mea_job_t *jobs, int64_t n_jobs, int device
                             double *kernel_ms_out) {
     (void) flags;
     if ((!jobs && n_jobs > 0) || n_jobs < 0 || !path_out || !n_path_out) return SA_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "[signalalign_hip] no HIP device available; this library has no CPU fallback\n");
-        return SA_ENODEVICE;
-    }
-    if (device < 0 || device >= ndev) return SA_EINVAL;
+    int rc = sa_device_check(device);
+    if (rc) return rc;
     for (int64_t j = 0; j < n_jobs; j++) {
         path_out[j] = nullptr; n_path_out[j] = 0;
         if (status_out) status_out[j] = 0;
@@ -669,23 +661,23 @@ extern "C" int sa_mea_batch(const sa_mea_job_t *jobs, int64_t n_jobs, int device
         J.out_cap = (int) (jb->n < jb->n_events ? jb->n : jb->n_events);   // one pair per event at most
         n_tot += (size_t) jb->n; sh_tot += (size_t) jb->n_events; out_tot += (size_t) J.out_cap;
     }
-    MeaWorkspace &W = g_mea_ws;
+    SaScratch &W = g_mea_ws;
     std::lock_guard<std::mutex> guard(W.mu);
-    int rc = SA_OK;
     // pinned upload image: data (f64) | rows | cols | shortest (i32)
     const size_t o_h_rows = sizeof(double) * n_tot, o_h_cols = o_h_rows + 4 * n_tot, o_h_sh = o_h_cols + 4 * n_tot,
                  in_bytes = o_h_sh + 4 * sh_tot;
-    // device: [jobs | upload image | arena ref, ev, prev | out | sum | n_out, n_edges, status | ids]
-    const size_t o_jobs = 0, o_in = sa_up256(sizeof(MeaJob) * nj), o_arena = sa_up256(o_in + in_bytes),
-                 o_out = sa_up256(o_arena + 12 * n_tot), o_sum = sa_up256(o_out + 8 * out_tot), o_res = o_sum + 8 * nj,
-                 o_ids = sa_up256(o_res + 12 * nj), dev_bytes = o_ids + 4 * nj;
-    const size_t res_bytes = o_ids - o_out;
+    // device: [jobs | upload image | arena ref, ev, prev | out, sum, n_out, n_edges, status | ids]; the paths and the per-job words
+    // are ONE entry: a single copy brings [o_out, o_out + res_bytes) back
+    SaLayout L;
+    const size_t res_bytes = sa_up256(8 * out_tot) + (8 + 12) * nj;
+    const size_t o_jobs = L.add(sizeof(MeaJob) * nj), o_in = L.add(in_bytes), o_arena = L.add(12 * n_tot), o_out = L.add(res_bytes),
+                 o_sum = o_out + sa_up256(8 * out_tot), o_res = o_sum + 8 * nj, o_ids = L.add(4 * nj);
     MeaPlan P;
     memset(&P, 0, sizeof(P));
     float kms = 0;
-    if ((rc = W.pin(&W.h_in, &W.h_in_cap, in_bytes ? in_bytes : 8, device)) != SA_OK) return rc;
+    if ((rc = W.rebind(device)) != SA_OK || (rc = W.pin(MEA_IN, in_bytes ? in_bytes : 8)) != SA_OK) return rc;
     {
-        char *h = (char *) W.h_in;
+        char *h = (char *) W.at(MEA_IN);
         sa_parallel_for(nj, [&](size_t j) {
             const sa_mea_job_t *jb = &jobs[j];
             const size_t n = (size_t) jb->n, ns = (size_t) jb->n_events, a = (size_t) hj[j].off, s = (size_t) hj[j].sh_off;
@@ -697,13 +689,12 @@ extern "C" int sa_mea_batch(const sa_mea_job_t *jobs, int64_t n_jobs, int device
             if (ns) memcpy(h + o_h_sh + 4 * s, jb->shortest_ref_per_event, 4 * ns);
         });
     }
-    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, dev_bytes, device)) != SA_OK) goto done;
-    if ((rc = W.pin(&W.h_res, &W.h_res_cap, res_bytes, device)) != SA_OK) goto done;
-    if ((rc = W.events()) != SA_OK) goto done;
+    if ((rc = W.dev(MEA_WS, L.end)) != SA_OK) goto done;
+    if ((rc = W.pin(MEA_RES, res_bytes)) != SA_OK) goto done;
     {
-        char *d = (char *) W.d_ws;
+        char *d = (char *) W.at(MEA_WS);
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
-        if (in_bytes) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.h_in, in_bytes, hipMemcpyHostToDevice, 0));
+        if (in_bytes) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, W.at(MEA_IN), in_bytes, hipMemcpyHostToDevice, 0));
         P.jobs = (const MeaJob *) (d + o_jobs);
         P.data = (const double *) (d + o_in);
         P.rows = (const int *) (d + o_in + o_h_rows);
@@ -713,13 +704,13 @@ extern "C" int sa_mea_batch(const sa_mea_job_t *jobs, int64_t n_jobs, int device
         P.out = (int2 *) (d + o_out);
         P.sum = (double *) (d + o_sum);
         P.n_out = (int *) (d + o_res); P.n_edges = P.n_out + nj; P.status = P.n_edges + nj;
-        if ((rc = mea_run_tiers(W, P, hj, d, o_jobs, o_ids, (int *) ((char *) W.h_res + (o_res - o_out)) + 2 * nj, device, &kms)) != SA_OK) goto done;
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
+        if ((rc = mea_run_tiers(W, P, hj, d, o_jobs, o_ids, (int *) ((char *) W.at(MEA_RES) + (o_res - o_out)) + 2 * nj, &kms)) != SA_OK) goto done;
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(MEA_RES), d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms;
     {
-        const char *hr = (const char *) W.h_res;
+        const char *hr = (const char *) W.at(MEA_RES);
         const int2 *h_out = (const int2 *) hr;
         const double *h_sum = (const double *) (hr + (o_sum - o_out));
         const int *h_n = (const int *) (hr + (o_res - o_out)), *h_edges = h_n + nj, *h_status = h_edges + nj;
@@ -943,11 +934,7 @@ __global__ __launch_bounds__(64) void k_mea_from_pairs(const sa_pair16_t *__rest
     if (lane == 0) { n_dev[jb] = n_out; mins[2 * jb] = xmin; mins[2 * jb + 1] = ymin; }
 }
 
-struct MeaChainWorkspace : MeaWorkspace {
-    void *d_aux = nullptr;
-    size_t d_aux_cap = 0;
-};
-static MeaChainWorkspace g_mea_chain_ws;
+static SaScratch g_mea_chain_ws;
 static void mea_chain_release() {
     std::lock_guard<std::mutex> guard(g_mea_chain_ws.mu);
     g_mea_chain_ws.release();
@@ -991,7 +978,7 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
         n_tot += (size_t) count[j]; sh_tot += (size_t) n_events[j] + 1; out_tot += (size_t) J.out_cap;
     }
     if (trace) fprintf(stderr, "[trace] mea: view+layout %.3f ms\n", now_ms() - t0);
-    MeaChainWorkspace &W = g_mea_chain_ws;
+    SaScratch &W = g_mea_chain_ws;
     std::lock_guard<std::mutex> guard(W.mu);
     // device: [jobs | chain | data f64 | rows | cols | shortest | arena ref, ev, prev | out | sum | n_out, n_edges, status | mins | ids]
     // aux (dead after k_mea_from_pairs): [fill | sorted ref | sorted prob]
@@ -1007,12 +994,11 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
     MeaPlan P;
     memset(&P, 0, sizeof(P));
     float kms = 0, kms0 = 0;
-    if ((rc = W.dev(&W.d_ws, &W.d_ws_cap, dev_bytes, device)) != SA_OK) return rc;
-    if ((rc = W.dev(&W.d_aux, &W.d_aux_cap, aux_bytes ? aux_bytes : 256, device)) != SA_OK) return rc;
-    if ((rc = W.pin(&W.h_res, &W.h_res_cap, res_bytes, device)) != SA_OK) return rc;
-    if ((rc = W.events()) != SA_OK) return rc;
+    if ((rc = W.rebind(device)) != SA_OK || (rc = W.dev(MEA_WS, dev_bytes)) != SA_OK) return rc;
+    if ((rc = W.dev(MEA_AUX, aux_bytes ? aux_bytes : 256)) != SA_OK) return rc;
+    if ((rc = W.pin(MEA_RES, res_bytes)) != SA_OK) return rc;
     {
-        char *d = (char *) W.d_ws, *a = (char *) W.d_aux;
+        char *d = (char *) W.at(MEA_WS), *a = (char *) W.at(MEA_AUX);
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, hj.data(), sizeof(MeaJob) * nj, hipMemcpyHostToDevice, 0));
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chain, hc.data(), sizeof(MeaChain) * nj, hipMemcpyHostToDevice, 0));
         P.jobs = (const MeaJob *) (d + o_jobs);
@@ -1026,25 +1012,24 @@ extern "C" int sa_batch_mea(sa_batch_t *b, unsigned flags, sa_mea_pair_t **path_
         P.n_out = (int *) (d + o_res); P.n_edges = P.n_out + nj; P.status = P.n_edges + nj;
         P.n_dev = (const int *) (d + o_ndev);
         P.mins = (const int *) (d + o_mins);
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e0, 0));
+        SA_HIP_GOTO_DONE(W.time_begin());
         hipLaunchKernelGGL(k_mea_from_pairs, dim3((unsigned) nj), dim3(64), 0, 0, d_pairs, (const MeaChain *) (d + o_chain), P,
                            (int *) (a + a_fill), (int *) (a + a_sref), (int *) (a + a_sprob), (int *) (d + o_ndev),
                            (int *) (d + o_mins), (int) nj);
-        SA_HIP_GOTO_DONE(hipEventRecord(W.e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
+        SA_HIP_GOTO_DONE(W.time_end());
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms0, W.e0, W.e1));
+        SA_HIP_GOTO_DONE(W.time_ms(&kms0));
         if (trace) fprintf(stderr, "[trace] mea: matrices built at %.3f ms\n", now_ms() - t0);
-        if ((rc = mea_run_tiers(W, P, hj, d, o_jobs, o_ids, (int *) ((char *) W.h_res + (o_res - o_out)) + 2 * nj, device, &kms)) != SA_OK)
+        if ((rc = mea_run_tiers(W, P, hj, d, o_jobs, o_ids, (int *) ((char *) W.at(MEA_RES) + (o_res - o_out)) + 2 * nj, &kms)) != SA_OK)
             goto done;
         if (trace) fprintf(stderr, "[trace] mea: paths done at %.3f ms\n", now_ms() - t0);
-        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.h_res, d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
+        SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(MEA_RES), d + o_out, res_bytes, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
         if (trace) fprintf(stderr, "[trace] mea: %zu bytes on the host at %.3f ms\n", res_bytes, now_ms() - t0);
     }
     if (kernel_ms_out) *kernel_ms_out = (double) kms + (double) kms0;
     {
-        const char *hr = (const char *) W.h_res;
+        const char *hr = (const char *) W.at(MEA_RES);
         const int2 *h_out = (const int2 *) hr;
         const double *h_sum = (const double *) (hr + (o_sum - o_out));
         const int *h_n = (const int *) (hr + (o_res - o_out)), *h_status = h_n + 2 * nj;
@@ -1076,10 +1061,8 @@ __global__ void k_printed_posterior(long long first, long long n, double *out) {
 }
 extern "C" int sa_mea_printed_posterior_device(int64_t first, int64_t n, double *out, int device) {
     if (n < 0 || (n > 0 && !out) || n > (1ll << 31)) return SA_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SA_ENODEVICE;
-    if (device < 0 || device >= ndev) return SA_EINVAL;
-    if (n == 0) return SA_OK;
+    const int rc = sa_device_check(device, /* quiet */ true);
+    if (rc || n == 0) return rc;
     double *d = nullptr;
     if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
     if (hipMalloc((void **) &d, sizeof(double) * (size_t) n) != hipSuccess) return SA_ENOMEM;

@@ -1,7 +1,10 @@
-// Allocators and host fan-out shared by the library's HIP sources (what concerns a finished batch is in sa_chain.h):
+// What any HIP source of the library needs (what concerns a finished batch is in sa_chain.h):
+//   SA_HIP_GOTO_DONE, sa_up256, SaLayout   the error macro and the layout of a call's device block
+//   sa_device_check   the one "is there a device, is `device` one of them" check
 //   SaScratch   grow-only device and pinned-host scratch kept between calls of a one-shot entry point (sa_event_align_batch,
-//               sa_mea_batch), so that a caller feeding batches in a loop pays allocation once.  One instance per entry point
-//               and process; calls serialise on `mu`; the matching sa_*_release() returns the memory.
+//               sa_mea_batch, ...), so that a caller feeding batches in a loop pays allocation once, and the timed region around
+//               the call's launches.  One instance per entry point and process; calls serialise on `mu`; the matching
+//               sa_*_release() returns the memory.
 //   SaPool      caching allocators for a batch's working storage
 //   SaWorkers, sa_parallel_for   host-side fan-out over reads
 #ifndef SA_SCRATCH_H
@@ -22,56 +25,90 @@
 
 #include "sa_internal.h"
 
+// a failed HIP call inside a function that cleans up at `done:` and returns `rc`
+#define SA_HIP_GOTO_DONE(call)                                                                              \
+    do {                                                                                                    \
+        hipError_t e_ = (call);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            fprintf(stderr, "[signalalign_hip] %s failed: %s (%s:%d)\n", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            rc = e_ == hipErrorOutOfMemory ? SA_ENOMEM : SA_ENODEVICE;                                      \
+            goto done;                                                                                      \
+        }                                                                                                   \
+    } while (0)
+
+static inline size_t sa_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
+
+// Running offsets of the arrays that share one block, each starting at a multiple of 256 bytes; `end` is the block's size.
+// Arrays that one copy or memset spans are added as ONE entry and told apart by the caller.
+struct SaLayout {
+    size_t end = 0;
+    size_t add(size_t bytes) {
+        const size_t o = sa_up256(end);
+        end = o + bytes;
+        return o;
+    }
+};
+
+// sa_hip.hip: SA_ENODEVICE when the process has no HIP device -- with the library's one line about it on stderr, unless `quiet` --
+// and SA_EINVAL for a device outside [0, count).  Entry points that answer differently say so where they call it: the HDP calls
+// (sa_hdpdev.h) report an out-of-range device as SA_ENODEVICE too, line included, and sa_device_memory, sa_kmer_table_create and
+// the two *_device test hooks have always been quiet.
+#define SA_NO_DEVICE_LINE "[signalalign_hip] no HIP device available; this library has no CPU fallback\n"
+__attribute__((visibility("hidden"))) int sa_device_check(int device, bool quiet = false);
+
 struct SaScratch {
+    enum { MAX_SLOTS = 8 };   // a file's slot enum stays below this
     std::mutex mu;
     int device = -1;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct Slot {
-        void **p;
-        size_t *cap;
-        bool pinned;
-    };
-    std::vector<Slot> slots;
+    void *ptr[MAX_SLOTS] = {};
+    size_t caps[MAX_SLOTS] = {};
+    bool pinned[MAX_SLOTS] = {};
 
+    void *at(int slot) const { return ptr[slot]; }
+    size_t cap(int slot) const { return caps[slot]; }
+    void drop(int slot) {
+        if (ptr[slot]) (void) (pinned[slot] ? hipHostFree(ptr[slot]) : hipFree(ptr[slot]));
+        ptr[slot] = nullptr;
+        caps[slot] = 0;
+    }
     void release() {
         if (device >= 0) (void) hipSetDevice(device);
-        for (Slot &s : slots) {
-            if (*s.p) (void) (s.pinned ? hipHostFree(*s.p) : hipFree(*s.p));
-            *s.p = nullptr;
-            *s.cap = 0;
-        }
+        for (int s = 0; s < MAX_SLOTS; s++) drop(s);
         if (e0) (void) hipEventDestroy(e0);
         if (e1) (void) hipEventDestroy(e1);
         e0 = e1 = nullptr;
         device = -1;
     }
+    // once per call, under `mu`: what another device holds goes back, and `dev` becomes the thread's current device
     int rebind(int dev) {
         if (device != dev) { release(); device = dev; }
         return hipSetDevice(dev) == hipSuccess ? SA_OK : SA_ENODEVICE;
     }
-    int grow(void **p, size_t *cap, size_t bytes, int devno, bool pinned) {
-        int rc = rebind(devno);
-        if (rc) return rc;
-        bool known = false;
-        for (Slot &s : slots) known = known || s.p == p;
-        if (!known) slots.push_back({p, cap, pinned});
-        if (bytes <= *cap) return SA_OK;
-        if (*p) (void) (pinned ? hipHostFree(*p) : hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
+    // at least `bytes` in `slot` on the bound device, an eighth more when it has to grow; what the slot held is not kept
+    int grow(int slot, size_t bytes, bool pin_host) {
+        if (bytes <= caps[slot]) return SA_OK;
+        drop(slot);
+        pinned[slot] = pin_host;
         bytes += bytes / 8;
-        hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
-        if (e != hipSuccess) { *p = nullptr; (void) hipGetLastError(); return SA_ENOMEM; }
-        *cap = bytes;
+        hipError_t e = pin_host ? hipHostMalloc(&ptr[slot], bytes, hipHostMallocDefault) : hipMalloc(&ptr[slot], bytes);
+        if (e != hipSuccess) { ptr[slot] = nullptr; (void) hipGetLastError(); return SA_ENOMEM; }
+        caps[slot] = bytes;
         return SA_OK;
     }
-    int dev(void **p, size_t *cap, size_t bytes, int devno) { return grow(p, cap, bytes, devno, false); }
-    int pin(void **p, size_t *cap, size_t bytes, int devno) { return grow(p, cap, bytes, devno, true); }
-    int events() {
-        if (e0) return SA_OK;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return SA_ENODEVICE;
-        return SA_OK;
+    int dev(int slot, size_t bytes) { return grow(slot, bytes, false); }
+    int pin(int slot, size_t bytes) { return grow(slot, bytes, true); }
+    // The timed region around a call's launches on stream 0: time_begin(), the launches, time_end() (which also reports a launch
+    // that failed), the caller's synchronising copy, time_ms().
+    hipError_t time_begin() {
+        if ((!e0 && hipEventCreate(&e0) != hipSuccess) || (!e1 && hipEventCreate(&e1) != hipSuccess)) return hipErrorInvalidResourceHandle;
+        return hipEventRecord(e0, 0);
     }
+    hipError_t time_end() {
+        const hipError_t e = hipEventRecord(e1, 0);
+        return e != hipSuccess ? e : hipGetLastError();
+    }
+    hipError_t time_ms(float *ms) { return hipEventElapsedTime(ms, e0, e1); }
 };
 // Caching allocators for a batch's working storage.  A pipeline that sees every read once creates and destroys a batch
 // per 2000 reads: hipMalloc / hipFree of its 25 GB (0.1 - 1 s per batch, measured), hipHostMalloc of the 200 MB pinned
@@ -355,7 +392,5 @@ static inline void sa_parallel_for(size_t n, F fn) {
     work();
     for (std::thread &t : pool) t.join();
 }
-
-static inline size_t sa_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 #endif

@@ -378,9 +378,7 @@ struct sa_kmer_table {
 extern "C" int sa_kmer_table_create(sa_kmer_table_t **out, const sa_model_t *m, int64_t max_per_kmer, double min_prob, int device) {
     if (!out || !m || max_per_kmer < 1 || !(min_prob >= 0.0 && min_prob <= 1.0)) return SA_EINVAL;
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SA_ENODEVICE;
-    if (device < 0 || device >= ndev) return SA_EINVAL;
+    if (const int rc = sa_device_check(device, /* quiet */ true)) return rc;
     if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
     sa_kmer_table *t = new (std::nothrow) sa_kmer_table();
     if (!t) return SA_ENOMEM;
@@ -1645,15 +1643,12 @@ __global__ void k_kt_f6(const double *v, long long n, long long *u, int *nz, int
 }
 extern "C" int sa_f6_units_device(const double *v, int64_t n, int64_t *units_out, int32_t *neg_zero_out, int32_t *rc_out, int device) {
     if (n < 0 || (n > 0 && (!v || !units_out || !neg_zero_out || !rc_out)) || n > (1ll << 31)) return SA_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SA_ENODEVICE;
-    if (device < 0 || device >= ndev) return SA_EINVAL;
-    if (n == 0) return SA_OK;
+    int rc = sa_device_check(device, /* quiet */ true);
+    if (rc || n == 0) return rc;
     if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
     char *d = nullptr;
     const size_t o_u = sa_up256(8 * (size_t) n), o_z = sa_up256(o_u + 8 * (size_t) n), o_r = sa_up256(o_z + 4 * (size_t) n);
     if (hipMalloc((void **) &d, o_r + 4 * (size_t) n) != hipSuccess) return SA_ENOMEM;
-    int rc = SA_OK;
     SA_HIP_GOTO_DONE(hipMemcpy(d, v, 8 * (size_t) n, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_kt_f6, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, (const double *) d, (long long) n, (long long *) (d + o_u),
                        (int *) (d + o_z), (int *) (d + o_r));

@@ -117,3 +117,26 @@ def test_non_unit_variance_and_a_long_read(oracle):
     # all-unit batch again right after: the other kernel instance, same workspace
     again = sa.event_align_batch(pm, long_jobs)
     assert np.array_equal(again[0][0], got[3][0]) and np.array_equal(again[0][1], got[3][1])
+
+
+def test_a_batch_equals_its_jobs_one_at_a_time_and_scratch_is_reused(oracle):
+    """Release, a small call, the full call twice (the first grows every slot of the scratch, the second reuses it), every job
+    alone, release, the full call again: the same pair lists and status words each time."""
+    pm, jobs = None, []
+    for i, n_events in enumerate((40, 400, 75, 260, 130, 333, 57, 190)):
+        pm, _, one, _ = _jobs(oracle, cases.MODEL_6MER, 1, n_events, first=1300 + i)
+        jobs += one
+
+    def same(a, b):
+        return len(a) == len(b) and all(x[2] == y[2] and np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
+                                        for x, y in zip(a, b))
+    release = sa.lib().sa_event_align_release
+    release()
+    small = sa.event_align_batch(pm, jobs[:3])
+    first = sa.event_align_batch(pm, jobs)
+    second = sa.event_align_batch(pm, jobs)
+    assert all(st == 0 and len(k) > 0 for k, _, st in first)
+    assert same(first, second) and same(first[:3], small)
+    assert same([sa.event_align_batch(pm, [j])[0] for j in jobs], first)
+    release()
+    assert same(sa.event_align_batch(pm, jobs), first)

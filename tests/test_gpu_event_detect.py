@@ -178,3 +178,27 @@ def test_empty_read_is_einval():
     with pytest.raises(sa.SaError) as ei:
         sa.raw_event_align_batch(sa.Model.load(DNA_MODEL), [empty], [dna_sequence()])
     assert ei.value.code == -1
+
+
+def test_a_batch_equals_its_jobs_one_at_a_time_and_scratch_is_reused():
+    """Release, a call of three reads, the full call twice (the first grows every slot of the scratch, the second reuses it),
+    every read alone, release, the full call again: the same event tables and status words each time."""
+    jobs = [synth.make_raw(9500 + i, n // 8 + 1, n_samples=n) for i, n in enumerate((2000, 6000, 2345, 4097, 3001, 5555, 2600, 4800))]
+
+    def run(some):
+        st = {}
+        got = sa.detect_events_batch(some, stats=st)
+        return got, np.asarray(st["status"]).copy()
+
+    def same(a, b):
+        return len(a[0]) == len(b[0]) and all(np.array_equal(x, y) for x, y in zip(a[0], b[0])) and np.array_equal(a[1], b[1])
+    sa.detect_release()
+    small = run(jobs[:3])
+    first = run(jobs)
+    second = run(jobs)
+    assert all(len(g) > 1 for g in first[0])
+    assert same(first, second) and same((first[0][:3], first[1][:3]), small)
+    singles = [run([j]) for j in jobs]
+    assert same(([s[0][0] for s in singles], np.concatenate([s[1] for s in singles])), first)
+    sa.detect_release()
+    assert same(run(jobs), first)

@@ -309,3 +309,37 @@ def test_ties_everywhere(oracle, monkeypatch, tier):
     got = sa.mea_batch(jobs)
     _check_against_oracle(oracle, jobs, got)
     assert sum(1 for g in got if g[2] == 0) > 300
+
+
+def test_a_batch_equals_its_jobs_one_at_a_time_and_scratch_is_reused(oracle, monkeypatch):
+    """Release, a small call, the full call twice (the first grows every slot of the scratch, the second reuses it), every job
+    alone, release, the full call again: the same paths, sums, status words and edge counts each time.  The fronts start in LDS
+    (SA_MEA_TIER=1) and job 5's outgrow it, so the global tier's front lists are grown and reused as well."""
+    monkeypatch.setenv("SA_MEA_TIER", "1")
+    rng = np.random.default_rng(21)
+    jobs = []
+    for it in range(8):
+        n_ev, n_ref = (int(v) for v in rng.integers(15, 40, 2))
+        m, shortest = random_prob_matrix(rng, n_ev, n_ref, gaps=bool(it % 3))
+        jobs.append(_job(m, shortest))
+    n_ref, n_ev = 300, 10                     # a 300-edge front from the first event on, and a long last one
+    m = np.zeros((n_ev, n_ref))
+    m[0, :] = np.sort(rng.random(n_ref)) / n_ref
+    for ev in range(1, n_ev - 1):
+        m[ev, rng.choice(n_ref, 12, replace=False)] = rng.random(12) / 12
+    m[n_ev - 1, :] = np.sort(rng.random(n_ref)) / n_ref
+    jobs[5] = _job(m, np.zeros(n_ev))
+
+    def same(a, b):
+        return len(a) == len(b) and all(np.array_equal(x[0], y[0]) and x[1:] == y[1:] for x, y in zip(a, b))
+    release = sa.lib().sa_mea_release
+    release()
+    small = sa.mea_batch(jobs[:3])
+    first = sa.mea_batch(jobs)
+    second = sa.mea_batch(jobs)
+    assert first[5][2] == 0 and first[5][3] > 256
+    assert same(first, second) and same(first[:3], small)
+    assert same([sa.mea_batch([j])[0] for j in jobs], first)
+    release()
+    assert same(sa.mea_batch(jobs), first)
+    _check_against_oracle(oracle, jobs, first)
