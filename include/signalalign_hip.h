@@ -412,7 +412,10 @@ typedef struct sa_ea_pair {
 int sa_scalings_mom(const sa_model_t *m, const char *sequence, int64_t seq_len, const double *event_mean,
                     int64_t n_events, unsigned flags, double *shift_out, double *scale_out);
 /* cells_out[j] (may be NULL): band cells filled for job j (the reference's `fills`); kernel_ms_out (may be NULL):
- * HIP-event time of the kernel */
+ * HIP-event time of the kernel.
+ * SA_EINVAL, with one line on stderr and before any kernel is launched, when a job's scale, shift, var or one of its
+ * event means is not a finite number: with a NaN event the reference's own traceback leaves the band and reads memory it
+ * never wrote, so there is no result to reproduce (the pair-HMM batch refuses such an event the same way). */
 int sa_event_align_batch(const sa_model_t *m, const sa_ea_job_t *jobs, int64_t n_jobs, int device, unsigned flags,
                          sa_ea_pair_t **pairs_out, int64_t *n_pairs_out, int32_t *status_out, double *cells_out,
                          double *kernel_ms_out);

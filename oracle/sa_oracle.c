@@ -1560,12 +1560,28 @@ int sao_align_batch_mt2(const sao_model_t *m, const sao_job_t *jobs, int64_t n_j
  * Returns the number of pairs (ascending), 0 when the alignment is rejected, < 0 on error; *status: 0 ok,
  * bit 0 average emission too low, bit 1 not spanned, bit 2 gap too long, bit 3 more than 5 events per k-mer.
  * PARITY UNPINNED: the reference's tests of this function read fast5 files (tests/eventAlignerTests.c:223-320,
- * :404-430), which cannot be opened here; only the restatement itself stands behind these results.
+ * :404-430), which cannot be opened here.  What stands behind this restatement instead: a plain full-matrix Viterbi
+ * without any banding (tests/event_align_ref.py), compared on the shapes of tests/ea_cases.py by
+ * tests/test_oracle_event_align.py, and the literals reached through the raw-current chain (tests/test_host_event_detect.py).
  * ---------------------------------------------------------------------------------------------- */
 #define EA_BW 100
 int64_t sao_event_align(const sao_model_t *m, const double *event_mean, int64_t n_events, const int32_t *kmer_ids,
                         int64_t n_kmers, int32_t **kmer_idx_out, int32_t **event_idx_out, int *status) {
+    return sao_event_align_ex(m, event_mean, n_events, kmer_ids, n_kmers, kmer_idx_out, event_idx_out, status, NULL, NULL);
+}
+
+/* The same, and what the walk did.  *fills_out: cells filled, the reference's `fills` counter (the sum over bands of
+ * max(o_max - o_min, 0)).  *walk_flags_out: SAO_EA_WALK_NO_START no cell of the last column scored, so the walk started at
+ * (event 0, last k-mer) as the reference's does; SAO_EA_WALK_OUT_OF_BAND the traceback read the trace at an offset
+ * outside 0..99 (the reference indexes its flat array there: a neighbouring band's byte, or memory it does not own, which
+ * reads as FROM_D here); SAO_EA_WALK_UNSCORED the traceback stood on a cell inside the band whose score is LOG_ZERO.
+ * Results with a flag set follow the reference's undefined behaviour only as far as this restatement chose to. */
+int64_t sao_event_align_ex(const sao_model_t *m, const double *event_mean, int64_t n_events, const int32_t *kmer_ids,
+                           int64_t n_kmers, int32_t **kmer_idx_out, int32_t **event_idx_out, int *status,
+                           int64_t *fills_out, int *walk_flags_out) {
     if (status) *status = 0;
+    if (fills_out) *fills_out = 0;
+    if (walk_flags_out) *walk_flags_out = 0;
     *kmer_idx_out = NULL;
     *event_idx_out = NULL;
     if (n_events <= 0 || n_kmers <= 0) return -1;
@@ -1590,6 +1606,8 @@ int64_t sao_event_align(const sao_model_t *m, const double *event_mean, int64_t 
     SC(0, -1 - ll_km[0]) = 0.0f;                                          /* (event -1, k-mer -1) */
     SC(1, ll_ev[1] - 0) = lp_trim;                                        /* first event trimmed  */
     TR(1, ll_ev[1] - 0) = FROM_U;
+    int64_t fills = 0;
+    int walk = 0;
     for (int64_t b = 2; b < n_bands; b++) {
         double lo = SC(b - 1, 0), hi = SC(b - 1, EA_BW - 1);
         int right;
@@ -1613,6 +1631,7 @@ int64_t sao_event_align(const sao_model_t *m, const double *event_mean, int64_t 
         if (o_min < 0) o_min = 0;
         if (e_max < o_max) o_max = e_max;
         if (o_max > EA_BW) o_max = EA_BW;
+        if (o_max > o_min) fills += o_max - o_min;
         for (int64_t o = o_min; o < o_max; o++) {
             int64_t ev = (int64_t) ll_ev[b] - o, km = (int64_t) ll_km[b] + o;
             int64_t o_up = (int64_t) ll_ev[b - 1] - (ev - 1), o_left = (km - 1) - ll_km[b - 1], o_diag = (km - 1) - ll_km[b - 2];
@@ -1645,6 +1664,7 @@ int64_t sao_event_align(const sao_model_t *m, const double *event_mean, int64_t 
             if (s > best) { best = s; cur_ev = ev; }
         }
     }
+    if (!(best > -INFINITY)) walk |= SAO_EA_WALK_NO_START;
     int64_t cap = n_events + n_kmers + 2, n = 0;
     int32_t *ok = malloc(sizeof(int32_t) * (size_t) cap), *oe = malloc(sizeof(int32_t) * (size_t) cap);
     double sum_em = 0;
@@ -1655,12 +1675,17 @@ int64_t sao_event_align(const sao_model_t *m, const double *event_mean, int64_t 
         sum_em += emit(m, kmer_ids[cur_km], y, 1);
         int64_t b = (cur_ev + 1) + (cur_km + 1);
         int64_t o = (int64_t) ll_ev[b] - cur_ev;
-        uint8_t from = TR(b, o);
+        int64_t at = b * EA_BW + o;
+        if (!VALID(o)) walk |= SAO_EA_WALK_OUT_OF_BAND;
+        else if (score[at] == LOG_ZERO) walk |= SAO_EA_WALK_UNSCORED;
+        uint8_t from = (at >= 0 && at < n_bands * EA_BW) ? trace[at] : FROM_D;
         if (from == FROM_D) { cur_km--; cur_ev--; cur_gap = 0; }
         else if (from == FROM_U) { cur_ev--; cur_gap = 0; }
         else { cur_km--; cur_gap++; if (cur_gap > max_gap) max_gap = cur_gap; }
     }
     free(score); free(trace); free(ll_ev); free(ll_km);
+    if (fills_out) *fills_out = fills;
+    if (walk_flags_out) *walk_flags_out = walk;
 #undef SC
 #undef TR
 #undef VALID

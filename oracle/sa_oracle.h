@@ -168,6 +168,13 @@ int sao_estimate_params(sao_model_t *m, const int64_t *strand_event_map, double 
 /* event <-> k-mer pre-alignment, impl/eventAligner.c:899-1235 (PARITY UNPINNED, see sa_oracle.c) */
 int64_t sao_event_align(const sao_model_t *m, const double *event_mean, int64_t n_events, const int32_t *kmer_ids,
                         int64_t n_kmers, int32_t **kmer_idx_out, int32_t **event_idx_out, int *status);
+/* the same, with the reference's `fills` counter and what the traceback did (sa_oracle.c); the two last may be NULL */
+#define SAO_EA_WALK_NO_START 1    /* no cell of the last column scored: the walk starts at (event 0, last k-mer) */
+#define SAO_EA_WALK_OUT_OF_BAND 2 /* the traceback read a trace offset outside 0..99                             */
+#define SAO_EA_WALK_UNSCORED 4    /* the traceback stood on a cell whose score is LOG_ZERO                       */
+int64_t sao_event_align_ex(const sao_model_t *m, const double *event_mean, int64_t n_events, const int32_t *kmer_ids,
+                           int64_t n_kmers, int32_t **kmer_idx_out, int32_t **event_idx_out, int *status,
+                           int64_t *fills_out, int *walk_flags_out);
 void sao_scalings_mom(const sao_model_t *m, const double *event_mean, int64_t n_events, const int32_t *kmer_ids,
                       int64_t n_kmers, double *shift_out, double *scale_out); /* impl/eventAligner.c:784-843 */
 void sao_free(void *p);

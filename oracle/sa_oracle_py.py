@@ -174,12 +174,39 @@ def event_align(model, event_means, kmer_ids):
           C.byref(st))
     if n < 0:
         raise RuntimeError("sao_event_align failed: %d" % n)
-    k = np.array([ko[i] for i in range(n)], dtype=np.int32)
-    e = np.array([eo[i] for i in range(n)], dtype=np.int32)
+    return _ea_lists(ko, eo, n) + (st.value,)
+
+
+def _ea_lists(ko, eo, n):
+    k = np.ctypeslib.as_array(ko, shape=(n,)).astype(np.int32) if n else np.zeros(0, dtype=np.int32)
+    e = np.ctypeslib.as_array(eo, shape=(n,)).astype(np.int32) if n else np.zeros(0, dtype=np.int32)
     if n:
         lib().sao_free(ko)
         lib().sao_free(eo)
-    return k, e, st.value
+    return k, e
+
+
+EA_WALK_NO_START, EA_WALK_OUT_OF_BAND, EA_WALK_UNSCORED = 1, 2, 4
+
+
+def event_align_ex(model, event_means, kmer_ids):
+    """sao_event_align_ex: event_align and what the walk did.  Returns (kmer_idx, event_idx, status, fills, walk_flags):
+    fills is the reference's counter of filled band cells, walk_flags the EA_WALK_* bits (no last-column cell scored; the
+    traceback read a trace offset outside 0..99; it stood on a cell without a score)."""
+    ev = np.ascontiguousarray(event_means, dtype=np.float64)
+    ids = np.ascontiguousarray(kmer_ids, dtype=np.int32)
+    ko, eo, st = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.c_int()
+    fills, walk = C.c_int64(), C.c_int()
+    f = lib().sao_event_align_ex
+    f.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.c_int64,
+                  C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int),
+                  C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    f.restype = C.c_int64
+    n = f(model._h, _dp(ev), len(ev), ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(ko), C.byref(eo),
+          C.byref(st), C.byref(fills), C.byref(walk))
+    if n < 0:
+        raise RuntimeError("sao_event_align_ex failed: %d" % n)
+    return _ea_lists(ko, eo, n) + (st.value, fills.value, walk.value)
 
 
 MEA_INF = 2 ** 31 - 1   # shortest_ref_per_event entry of an event without rows (the reference's np.inf)

@@ -2,7 +2,9 @@
 against the CPU restatement.  PARITY UNPINNED against the reference itself -- its tests of this function read fast5
 files (tests/eventAlignerTests.c:223-320, :404-430) -- so what is checked here is: bit-identical pair lists and status
 words between the two restatements, and properties any correct alignment has (monotone, spanning, every event between
-the first and last aligned event used once, agreement with the generator's ground truth).
+the first and last aligned event used once, agreement with the generator's ground truth).  Behind the restatement
+stands a plain full-matrix Viterbi, compared on the CPU on the shapes of tests/ea_cases.py
+(tests/test_oracle_event_align.py); the same shapes are run here, with the cell count.
 """
 import numpy as np
 import pytest
@@ -11,6 +13,7 @@ import signalalign_amd as sa
 from signalalign_amd import synth
 
 import sa_cases as cases
+import ea_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -140,3 +143,104 @@ def test_a_batch_equals_its_jobs_one_at_a_time_and_scratch_is_reused(oracle):
     assert same([sa.event_align_batch(pm, [j])[0] for j in jobs], first)
     release()
     assert same(sa.event_align_batch(pm, jobs), first)
+
+
+# ---- the listed shapes (tests/ea_cases.py): the band, the two operand streams, the traceback blocks and the status
+# thresholds at their edges, against sao_event_align_ex; tests/test_oracle_event_align.py stands behind the oracle there
+
+_LISTS = {"6mer": (cases.MODEL_6MER, 0), "rna": (cases.MODEL_5MER, sa.FLAG_RNA)}
+
+
+def _listed(which):
+    """(model, flags, jobs, expected) of one list.  Nothing whose walk leaves the band on the oracle goes to the GPU:
+    the kernel would index past its staged trace rows there."""
+    model_path, flags = _LISTS[which]
+    cs = ea_cases.cases_rna() if which == "rna" else ea_cases.cases_6mer()
+    exp = ea_cases.expected(which)
+    assert all(e[4] == 0 for e in exp), [c[0] for c, e in zip(cs, exp) if e[4]]
+    jobs = [dict(sequence=seq, event_mean=ev, scale=sc, shift=sh, var=var) for _, seq, ev, sc, sh, var in cs]
+    return sa.Model.load(model_path), flags, jobs, exp
+
+
+def _assert_as_expected(got, cells, jobs, exp, what):
+    assert len(got) == len(exp) == len(cells)
+    for j, ((gk, ge, gst), (ek, ee, est, fills, _)) in enumerate(zip(got, exp)):
+        where = (what, j, len(jobs[j]["event_mean"]), len(jobs[j]["sequence"]))
+        assert gst == est, where
+        assert np.array_equal(gk, ek) and np.array_equal(ge, ee), where
+        assert cells[j] == fills, where + (cells[j], fills)
+
+
+@pytest.mark.parametrize("which", ["6mer", "rna"])
+def test_listed_shapes_in_one_call_pairs_status_and_cells(oracle, which):
+    """One call per model and flag: status words, pair lists and the cell count (the numerator of bench.py's
+    event_align_band_cell_updates_per_s) equal the oracle's, exactly.  The 6-mer list holds var != 1 beside var == 1."""
+    pm, flags, jobs, exp = _listed(which)
+    if which == "6mer":
+        assert {j["var"] for j in jobs} >= {1.0, 1.3, 0.8}
+        assert {e[2] for e in exp} >= {0, 1, 5, 8, 9}
+    stats = {}
+    got = sa.event_align_batch(pm, jobs, flags=flags, stats=stats)
+    _assert_as_expected(got, stats["cells"], jobs, exp, which)
+
+
+@pytest.mark.parametrize("which", ["6mer", "rna"])
+def test_listed_shapes_one_job_per_call(oracle, which):
+    """Every job alone: the per-read offsets into trace, ll, col and out (and the 4-byte alignment of the 100-byte trace
+    rows the traceback loads as words) are all zero here and arbitrary in the batch; a var == 1 job alone takes the
+    unit-variance instance of the kernel, in the 6-mer batch the other."""
+    pm, flags, jobs, exp = _listed(which)
+    got, cells = [], []
+    for job in jobs:
+        stats = {}
+        got.append(sa.event_align_batch(pm, [job], flags=flags, stats=stats)[0])
+        cells.append(stats["cells"][0])
+    _assert_as_expected(got, cells, jobs, exp, which + " alone")
+
+
+def test_listed_shapes_on_a_stale_and_on_a_fresh_trace_plane(oracle):
+    """The trace plane is kept between calls and never cleared: after a 12000-event read every byte the short reads'
+    tracebacks could reach holds another read's moves.  The list gives the same on that plane and on a fresh one."""
+    pm, flags, jobs, exp = _listed("6mer")
+    _, _, long_jobs, _ = _jobs(oracle, cases.MODEL_6MER, 1, 12000, first=5)
+    release = sa.lib().sa_event_align_release
+    release()
+    long_got = sa.event_align_batch(pm, long_jobs)
+    assert long_got[0][2] == 0 and len(long_got[0][0]) > 12000
+    for what in ("stale plane", "fresh plane"):
+        stats = {}
+        got = sa.event_align_batch(pm, jobs, flags=flags, stats=stats)
+        _assert_as_expected(got, stats["cells"], jobs, exp, what)
+        release()
+
+
+def test_a_value_that_is_not_finite_is_refused_before_the_kernel(oracle, capfd):
+    """NaN event means make the reference's own traceback leave the band: sa_event_align_batch refuses the
+    batch on the host -- SA_EINVAL and one line on stderr -- for an event mean, scale, shift or var that is not finite,
+    whichever job of the batch holds it; the good read beside it aligns as before when sent again."""
+    pm, flags, jobs, exp = _listed("6mer")
+    at = next(j for j, c in enumerate(ea_cases.cases_6mer()) if c[0] == "matched_114k")
+    good = jobs[at]
+
+    def broken(**kw):
+        bad = dict(good)
+        for key, (idx, val) in kw.items():
+            if idx is None:
+                bad[key] = val
+            else:
+                arr = np.array(bad[key], dtype=np.float64)
+                arr[idx] = val
+                bad[key] = arr
+        return bad
+    bad_jobs = [broken(event_mean=(57, np.nan)), broken(event_mean=(len(good["event_mean"]) - 1, np.inf)),
+                broken(event_mean=(0, -np.inf)), broken(scale=(None, np.nan)), broken(shift=(None, np.inf)),
+                broken(var=(None, np.inf))]
+    for i, bad in enumerate(bad_jobs):
+        capfd.readouterr()
+        with pytest.raises(sa.SaError) as ei:
+            sa.event_align_batch(pm, [good, bad] if i % 2 else [bad, good])
+        err = capfd.readouterr().err
+        assert ei.value.code == -1 and "not a finite number" in err and err.count("\n") == 1, (i, err)
+        stats = {}
+        again = sa.event_align_batch(pm, [good], stats=stats)
+        _assert_as_expected(again, stats["cells"], [good], [exp[at]], "after refusal %d" % i)
