@@ -464,7 +464,6 @@ static int batch_finish_body(sa_batch *b) {
         TRY(dalloc((void **) &b->d_cand_count, 4 * pl->n_segs));
         TRY(dalloc((void **) &b->d_seg_pass, 4 * pl->n_segs));
         TRY(dalloc((void **) &b->d_seg_off, 8 * (2 * pl->n_segs + 8)));  // n+1 offsets per group
-        TRY(dalloc((void **) &b->d_overflow, 4));
         TRY(dalloc((void **) &b->d_totals, 8 * pl->n_cks));
         TRY(dalloc((void **) &b->d_bscratch, 8 * pl->n_bscratch));
         if (b->expect) {
@@ -494,12 +493,10 @@ static int batch_finish_body(sa_batch *b) {
                 TRY(dalloc((void **) &b->d_sortkey, 8ll * at_least_1(pl->n_cand)));
                 TRY(dalloc((void **) &b->d_sortidx, 4ll * at_least_1(pl->n_cand)));
             }
-            b->gev.resize(4 * b->groups.size(), nullptr);
-            b->cev.resize(2 * b->chunks.size(), nullptr);
-            for (auto &e : b->gev)
-                if (g_handles.event(&e, device) != hipSuccess) return SA_ENODEVICE;
-            for (auto &e : b->cev)
-                if (g_handles.event(&e, device) != hipSuccess) return SA_ENODEVICE;
+            b->group_ev.resize(b->groups.size());
+            b->chunk_ev.resize(b->chunks.size());
+            for (sa_group_events &e : b->group_ev) TRY(events_make(e, device));
+            for (sa_chunk_events &e : b->chunk_ev) TRY(events_make(e, device));
             if (g_sa_pool.get(SaPool::PINNED, (void **) &b->h_seg_off, 8 * (size_t) (pl->n_segs + (long long) b->groups.size() + 1),
                               device) != hipSuccess ||
                 g_sa_pool.get(SaPool::PINNED, (void **) &b->h_overflow, 64, device) != hipSuccess) {
@@ -516,9 +513,9 @@ static int batch_finish_body(sa_batch *b) {
         b->put_blocks(0, sa_batch::BLK_PLAN);
         if (b->h_seg_off) { g_sa_pool.put(SaPool::PINNED, b->h_seg_off); b->h_seg_off = nullptr; }
         if (b->h_overflow) { g_sa_pool.put(SaPool::PINNED, b->h_overflow); b->h_overflow = nullptr; }
-        for (hipEvent_t e : b->gev) if (e) g_handles.park(e, device);
-        for (hipEvent_t e : b->cev) if (e) g_handles.park(e, device);
-        b->gev.clear(); b->cev.clear();
+        for (sa_group_events &e : b->group_ev) events_park(e, device);
+        for (sa_chunk_events &e : b->chunk_ev) events_park(e, device);
+        b->group_ev.clear(); b->chunk_ev.clear();
         b->seam_cap = 0; b->seam_cap_bwd = 0; b->seam_bwd_off = 0;
     };
     // A batch whose RESULTS take longer to cross PCIe than its kernels take to run (broad HDP densities at a low threshold: hundreds of
@@ -687,12 +684,8 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
         if (flags & SA_FLAG_POSITION_CALLS)
             TRY(m->k > SA_POS_MAX_K ? SA_EUNSUPPORTED : sa_ambig_build(m, jobs, n_jobs, ambig, 0, &b->ambig_tab[SA_TAB_POSITIONS]));
     }
-    if (g_handles.stream(&b->cstream[0], device, 0) != hipSuccess || g_handles.stream(&b->cstream[1], device, 0) != hipSuccess)
-        return SA_ENODEVICE;
-    b->stream = b->cstream[0];
-    if (g_handles.stream(&b->pair_stream, device, 1) != hipSuccess) return SA_ENODEVICE;   // the copy stream outranks the compute streams
-    for (int i = 0; i < 8; i++)
-        if (g_handles.event(&b->ev[i], device) != hipSuccess) return SA_ENODEVICE;
+    if (!b->lanes.lane(0, device) || !b->lanes.lane(1, device) || g_handles.stream(&b->lanes.pair, device, 1) != hipSuccess) return SA_ENODEVICE;
+    TRY(events_make(b->ev, device));
     // ---- the plan: on the device when the batch allows it (sa_dplan.inc: its first half here), else on the host ----
     {
         std::lock_guard<std::mutex> dp_lock(g_uploader.mu);

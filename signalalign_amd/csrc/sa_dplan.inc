@@ -611,7 +611,7 @@ struct DPlanPending {
 static void dplan_release(sa_batch *b, DPlanPending *P, bool arrays_too) {
     if (!P) return;
     if (P->done) { (void) hipEventSynchronize(P->done); g_handles.park(P->done, b->device); P->done = nullptr; }
-    if (arrays_too && b->d_blk && b->stream) (void) hipStreamSynchronize(b->stream);   // (the event gather writes d_ev from there)
+    if (arrays_too && b->d_blk && b->lanes.compute[0]) (void) hipStreamSynchronize(b->lanes.compute[0]);   // (the event gather writes d_ev from there)
     if (P->stage) g_sa_pool.put(SaPool::PINNED, P->stage);
     if (P->back) g_sa_pool.put(SaPool::PINNED, P->back);
     for (void *q : P->temps) g_sa_pool.put(SaPool::DEVICE, q);
@@ -718,7 +718,7 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     // its block chooses so) is sent in two pieces: the anchors on the upload stream, ahead of the planning kernels, and the
     // event records -- three quarters of the bytes -- on the batch's own stream, where every kernel that reads the event
     // means is queued later: sa_batch_create does not wait for them.
-    const bool blk_split = in_block && b->stream && rng_lo[0] && rng_lo[1] && (rng_hi[0] <= rng_lo[1] || rng_hi[1] <= rng_lo[0]) &&
+    const bool blk_split = in_block && b->lanes.compute[0] && rng_lo[0] && rng_lo[1] && (rng_hi[0] <= rng_lo[1] || rng_hi[1] <= rng_lo[0]) &&
                            !(getenv("SA_BLOCK_SPLIT") && atoi(getenv("SA_BLOCK_SPLIT")) == 0);   // (test hook)
 
     // ---- sizes and offsets from the reads' headers (no read data touched yet) ----
@@ -775,7 +775,7 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
     std::vector<void *> &temps = PP->temps;
     auto fail = [&](int rc) {
         (void) hipStreamSynchronize(g_uploader.stream);   // nothing of this plan may still be in flight when its blocks go back
-        if (b->d_blk && b->stream) (void) hipStreamSynchronize(b->stream);
+        if (b->d_blk && b->lanes.compute[0]) (void) hipStreamSynchronize(b->lanes.compute[0]);
         dplan_release(b, PP, true);
         if (b->d_blk) { g_sa_pool.put(SaPool::DEVICE, b->d_blk); b->d_blk = nullptr; }
         return rc;
@@ -943,10 +943,10 @@ static int dplan_front(sa_batch *b, const sa_model_t *m, const sa_params_t *p, c
         } else {
             // the event records: on the batch's own stream, behind the table they are gathered with, ahead of everything the
             // batch will ever queue there
-            DP_HIP(hipEventRecord(b->ev[7], st));
-            DP_HIP(hipStreamWaitEvent(b->stream, b->ev[7], 0));
-            DP_HIP(hipMemcpyAsync(d_blk + img_ev, rng_lo[0], (size_t) (rng_hi[0] - rng_lo[0]), hipMemcpyHostToDevice, b->stream));
-            hipLaunchKernelGGL(k_dplan_events, dim3((unsigned) n_jobs), dim3(DPLAN_NT), 0, b->stream, d_src, (const char *) d_blk, b->d_ev);
+            DP_HIP(hipEventRecord(b->ev.planner_gather, st));
+            DP_HIP(hipStreamWaitEvent(b->lanes.compute[0], b->ev.planner_gather, 0));
+            DP_HIP(hipMemcpyAsync(d_blk + img_ev, rng_lo[0], (size_t) (rng_hi[0] - rng_lo[0]), hipMemcpyHostToDevice, b->lanes.compute[0]));
+            hipLaunchKernelGGL(k_dplan_events, dim3((unsigned) n_jobs), dim3(DPLAN_NT), 0, b->lanes.compute[0], d_src, (const char *) d_blk, b->d_ev);
         }
         A.ingest_status = d_ingest;
     }

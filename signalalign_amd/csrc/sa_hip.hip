@@ -17,8 +17,9 @@
 //                        un-contracted arithmetic.  State lives in memory.  This is the exactness baseline.
 //   sa_result.inc        fold, finalize, scan, gather, k_fill_xc
 //   sa_runtime.inc       the process-wide host runtime: HIPCHK / TRY, handles, uploaders, allocators, memos
-//   here                 the launch classes, sa_batch, make_devplan; sa_dplan.inc (the device planner); sa_batch_destroy;
-//                        sa_batch_build.inc (a batch's creation); a pass, the run loop, the accessors and the rest of the public API
+//   here                 the launch classes, a batch's streams and events (sa_lanes, sa_*_events), sa_batch, make_devplan;
+//                        sa_dplan.inc (the device planner); sa_batch_destroy; sa_batch_build.inc (a batch's creation); a pass
+//                        (sa_ring_lanes, submit_group, enqueue_pass, after_pass), the two run paths, the accessors and the rest of the API
 //
 // The file is compiled with -ffp-contract=off; where fused multiply-add is wanted it is spelled fma().
 #include <hip/hip_runtime.h>
@@ -305,13 +306,61 @@ struct sa_launch_group {
     unsigned seam_first;       // their first wave slot in the seam storage
 };
 
+// A batch's queues.  Compute lane 0 carries a pass's forward sweeps and, in turn with lane 1, its groups; lanes 2 and 3 hold nothing but
+// forward launches of the ring-kernel classes (sa_ring_lanes).  Lane 0 is also the device planner's event gather's and sa_expect_batch's.
+struct sa_lanes {
+    enum { N = 4 };
+    hipStream_t compute[N] = {};   // 0 and 1 from the batch's creation, 2 and 3 on first need
+    hipStream_t pair = nullptr;    // the pairs themselves: high priority, the copy stream outranks the compute lanes
+    // compute lane q, made on first need; nullptr when no stream can be had
+    hipStream_t lane(int q, int device) {
+        if (!compute[q] && g_handles.stream(&compute[q], device, 0) != hipSuccess) compute[q] = nullptr;
+        return compute[q];
+    }
+    // waits for all of them -- asleep on a blocking event (sa_sync_stream) or, with `spin`, in hipStreamSynchronize; the first error
+    hipError_t drain(int device, bool spin) {
+        hipError_t first = hipSuccess;
+        for (hipStream_t s : {compute[0], compute[1], compute[2], compute[3], pair}) {
+            const hipError_t e = !s ? hipSuccess : spin ? hipStreamSynchronize(s) : sa_sync_stream(s, device);
+            if (first == hipSuccess) first = e;
+        }
+        return first;
+    }
+    void park(int device) {
+        for (hipStream_t s : compute) g_handles.park(s, device, 0);
+        g_handles.park(pair, device, 1);
+    }
+};
+// The events of a pass, of each of its chunks and of each of its groups: all() is what is made and parked
+struct sa_pass_events {
+    hipEvent_t pass_begin = nullptr, pass_end = nullptr;
+    hipEvent_t lane_fork = nullptr;           // sa_ring_lanes: lane 0 has queued what the other lanes' launches read
+    hipEvent_t lane_join[sa_lanes::N] = {};   // ... [q]: lane q has queued its launches, lane 0 waits for it ([0] is never made)
+    hipEvent_t planner_gather = nullptr;      // sa_dplan.inc: the upload stream has queued what the event gather on lane 0 reads
+    std::array<hipEvent_t *, 7> all() { return {&pass_begin, &lane_fork, &lane_join[1], &lane_join[2], &lane_join[3], &pass_end, &planner_gather}; }
+};
+struct sa_chunk_events {
+    hipEvent_t fwd_begin = nullptr, fwd_end = nullptr;
+    std::array<hipEvent_t *, 2> all() { return {&fwd_begin, &fwd_end}; }
+};
+struct sa_group_events {
+    hipEvent_t bwd_begin = nullptr, bwd_end = nullptr, ready = nullptr;   // ready: behind the group's last kernel
+    std::array<hipEvent_t *, 3> all() { return {&bwd_begin, &bwd_end, &ready}; }
+};
+template <typename E>   // (one of the three above)
+static int events_make(E &ev, int device) {
+    for (hipEvent_t *e : ev.all())
+        if (g_handles.event(e, device) != hipSuccess) return SA_ENODEVICE;
+    return SA_OK;
+}
+template <typename E>
+static void events_park(E &ev, int device) { for (hipEvent_t *e : ev.all()) g_handles.park(*e, device); }
+
 struct sa_batch {
     sa_plan_t *plan = nullptr;
     int device = -1;
     unsigned flags = 0;
-    hipStream_t stream = nullptr;             // == cstream[0]
-    hipStream_t cstream[2] = {};              // compute streams; groups alternate between them
-    hipStream_t xstream[2] = {};              // two more, for the forward launches of the ring-kernel classes
+    sa_lanes lanes;
     // device buffers (blocks() lists them)
     sa_region_t *d_regions = nullptr; sa_row_t *d_rows = nullptr; int *d_pk = nullptr; int *d_poff = nullptr; int *d_pid = nullptr;
     int *d_px = nullptr; double *d_xc = nullptr; double *d_ev = nullptr; sa_prec_t *d_prec = nullptr;
@@ -320,7 +369,7 @@ struct sa_batch {
                              // batch's own stream, possibly after sa_batch_create has returned: kept until the batch goes)
     sa_seg_t *d_segs = nullptr; sa_ck_t *d_cks = nullptr;
     double *d_F = nullptr; double *d_E = nullptr; double *d_vbuf = nullptr; sa_cand_t *d_cands = nullptr; int *d_cand_count = nullptr;
-    int *d_overflow = nullptr; double *d_totals = nullptr; double *d_bscratch = nullptr;
+    double *d_totals = nullptr; double *d_bscratch = nullptr;
     double *d_gsum = nullptr, *d_gmc = nullptr;   // expectation mode only
     bool expect = false;
     bool relax = false;        // memory-resident kernels in their RELAX flavour
@@ -358,9 +407,9 @@ struct sa_batch {
     std::vector<sa_launch_chunk> chunks;
     std::vector<sa_launch_group> groups;
     std::vector<int> ids_flat;
-    hipStream_t pair_stream = nullptr;   // the pairs themselves
-    std::vector<hipEvent_t> gev;   // per group: backward start, backward end, results ready, (unused)
-    std::vector<hipEvent_t> cev;   // per chunk: forward start, forward end
+    sa_pass_events ev;
+    std::vector<sa_chunk_events> chunk_ev;
+    std::vector<sa_group_events> group_ev;
     long long *h_seg_off = nullptr;      // pinned: per group n+1 exclusive offsets
     int *h_overflow = nullptr;           // pinned
     // results
@@ -380,7 +429,6 @@ struct sa_batch {
     std::thread *runner = nullptr;   // sa_batch_start .. sa_batch_wait
     int runner_rc = SA_OK;
     sa_batch_stats_t stats{};
-    hipEvent_t ev[8] = {};
     // Creation in two halves (sa_batch_create_deferred): what the second half needs.  `pending` is the device plan whose kernels
     // are queued; the caller's arrays (c_jobs, c_ambig) are only touched again if that plan turns a read down and the host
     // planner takes over -- which is why a deferred batch asks the caller to keep them until its first run has returned.
@@ -407,11 +455,11 @@ struct sa_batch {
     //   [BLK_PLAN, BLK_REST)  the planner's arrays: sa_dplan.inc's dplan_release gives them back when the device plan is dropped
     //   [BLK_REST, BLK_END)   everything else, kept until sa_batch_release_device or sa_batch_destroy
     // d_pairs_up is not listed: it survives sa_batch_release_device.
-    enum { BLK_PLAN = 18, BLK_REST = 27, BLK_END = 44 };
+    enum { BLK_PLAN = 17, BLK_REST = 26, BLK_END = 43 };
     std::array<void **, BLK_END> blocks() {
         const std::array all{
             (void **) &d_F, (void **) &d_E, (void **) &d_vbuf, (void **) &d_cands, (void **) &d_prob, (void **) &d_cand_count,
-            (void **) &d_seg_pass, (void **) &d_seg_off, (void **) &d_overflow, (void **) &d_totals, (void **) &d_bscratch,
+            (void **) &d_seg_pass, (void **) &d_seg_off, (void **) &d_totals, (void **) &d_bscratch,
             (void **) &d_gsum, (void **) &d_gmc, (void **) &d_seam, (void **) &d_spec, (void **) &d_sortkey, (void **) &d_sortidx,
             (void **) &d_out,
             (void **) &d_regions, (void **) &d_rows, (void **) &d_pk, (void **) &d_poff, (void **) &d_pid, (void **) &d_ev,
@@ -483,25 +531,15 @@ void sa_batch_destroy(sa_batch_t *b) {
     // batch may still be in flight (only possible after an error inside a run)
     const bool trace_d = getenv("SA_TRACE") != nullptr;
     const double td0 = now_ms();
-    if (!b->quiet) {   // (a failed or interrupted run, or a batch that never ran: 0.6-0.9 ms of API calls otherwise, per batch,
-                       // on the thread that is about to plan the next one)
-        for (int i = 0; i < 2; i++)
-            if (b->cstream[i]) (void) hipStreamSynchronize(b->cstream[i]);
-        for (int i = 0; i < 2; i++)
-            if (b->xstream[i]) (void) hipStreamSynchronize(b->xstream[i]);
-        if (b->pair_stream) (void) hipStreamSynchronize(b->pair_stream);
-    }
+    // (a failed or interrupted run, or a batch that never ran: 0.6-0.9 ms of API calls otherwise, per batch, on the thread that is
+    // about to plan the next one)
+    if (!b->quiet) (void) b->lanes.drain(b->device, true);
     const double td1 = now_ms();
     b->put_blocks(0, sa_batch::BLK_END);
-    for (int i = 0; i < 8; i++)
-        g_handles.park(b->ev[i], b->device);
-    for (hipEvent_t e : b->gev) g_handles.park(e, b->device);
-    for (hipEvent_t e : b->cev) g_handles.park(e, b->device);
-    for (int i = 0; i < 2; i++)
-        g_handles.park(b->cstream[i], b->device, 0);
-    for (int i = 0; i < 2; i++)
-        g_handles.park(b->xstream[i], b->device, 0);
-    g_handles.park(b->pair_stream, b->device, 1);
+    events_park(b->ev, b->device);
+    for (sa_group_events &e : b->group_ev) events_park(e, b->device);
+    for (sa_chunk_events &e : b->chunk_ev) events_park(e, b->device);
+    b->lanes.park(b->device);
     g_sa_pool.put(SaPool::PINNED, b->h_pairs);
     g_sa_pool.put(SaPool::PINNED, b->held_stage);
     g_sa_pool.put(SaPool::DEVICE, b->d_pairs_up);
@@ -516,18 +554,19 @@ void sa_batch_destroy(sa_batch_t *b) {
 
 #include "sa_batch_build.inc"
 
-// One pass = per chunk the forward sweeps (stream 0), then per group the backward/posterior kernels, the exact fold
-// of its checkpoints and -- with `finalize` -- the on-device finalisation (k_scan also writes the segment offsets
-// straight into pinned host memory).  Consecutive groups alternate between two compute streams: the next group's
-// waves move in while the previous group's last waves drain, so cutting the traceback work into groups costs no
-// idle tail.  Everything is queued up front; `after_group` waits for one group and requests its pairs.  No copy that
+// One pass = per chunk the forward sweeps (compute lane 0; the ring-kernel classes fork over up to four lanes and join
+// it again: sa_ring_lanes), then per group the backward/posterior kernels, the exact fold of its checkpoints and -- with
+// `finalize` -- the on-device finalisation (k_scan also writes the segment offsets straight into pinned host memory).
+// Consecutive groups alternate between compute lanes 0 and 1: the next group's waves move in while the previous group's
+// last waves drain, so cutting the traceback work into groups costs no idle tail.  Everything is queued up front;
+// `after_group` waits for one group's `ready` event and requests its pairs on the pair stream.  No copy that
 // depends on a kernel is ever queued: the copy engine works in order, and a transfer waiting for a kernel would hold
 // back the pair copies of groups that are already finished (measured: probes/copy_overlap.hip).
 static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, bool finalize) {
     sa_plan_t *pl = b->plan;
     const sa_launch_group &G = b->groups[g];
-    hipStream_t st = b->cstream[which_stream];
-    HIPCHK(hipEventRecord(b->gev[4 * g], st));
+    hipStream_t st = b->lanes.compute[which_stream];
+    HIPCHK(hipEventRecord(b->group_ev[(size_t) g].bwd_begin, st));
     const sa_ids &Lg = G.ids[LC_GENERIC], &Ls = G.ids[LC_STRIP], &Lf = G.ids[LC_FAST];
     if (Lg.n) launch_bwd_generic(P, b->d_ids + Lg.off, Lg.n, st, b->gen_threads, b->relax, b->ring_cap);
     if (Ls.n)
@@ -537,7 +576,7 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
         return launch_bwd_ring(P, b->d_ids + L.off, L.n, st, cap, multi);
     }));
     if (Lf.n) { const int rcl = launch_bwd_fast(P, b->d_ids + Lf.off, Lf.n, st); if (rcl) return rcl; }
-    HIPCHK(hipEventRecord(b->gev[4 * g + 1], st));
+    HIPCHK(hipEventRecord(b->group_ev[(size_t) g].bwd_end, st));
     if (G.ck1 > G.ck0)
         hipLaunchKernelGGL(k_fold, dim3((unsigned) ((G.ck1 - G.ck0 + 63) / 64)), dim3(64), 0, st, P, G.ck0, G.ck1);
     if (finalize) {
@@ -555,15 +594,45 @@ static int submit_group(sa_batch *b, const DevPlan &P, int g, int which_stream, 
             hipLaunchKernelGGL(k_gather_sorted, dim3((unsigned) n), dim3(64), 0, st, P, (int) G.seg0, n, b->d_prob, soff,
                                gout, spec, b->d_sortkey, b->d_sortidx, b->p8 ? 1 : 0);
     }
-    HIPCHK(hipEventRecord(b->gev[4 * g + 2], st));
+    HIPCHK(hipEventRecord(b->group_ev[(size_t) g].ready, st));
     return SA_OK;
 }
+
+// The lanes of a chunk's ring-kernel forward launches, one launch per class of row capacity (the strip kernels' list among them).
+// A forward launch holds one workgroup per read and lasts as long as its longest read's serial chain, so launches that follow each
+// other on one stream leave the chip mostly empty three times over: the lists go round the compute lanes and run side by side.
+// In this order: make it, queue on lane 0 what the launches read, fork(), one next() per list, join().
+struct sa_ring_lanes {
+    hipStream_t lane[sa_lanes::N] = {};
+    int n = 0, k = 0;
+    // as many lanes as lists, four at most, fewer when a stream cannot be had
+    sa_ring_lanes(sa_batch *b, const sa_ids *ids) {
+        const int n_lists = n_nonempty(ids, LC_RING, LC_N);
+        for (n = 0; n < n_lists && n < sa_lanes::N; n++)
+            if (!(lane[n] = b->lanes.lane(n, b->device))) break;
+        lane[0] = b->lanes.compute[0];
+        if (getenv("SA_TRACE")) fprintf(stderr, "[trace] pass: %d ring lists on %d lanes\n", n_lists, n);
+    }
+    int fork(sa_batch *b) {
+        if (n > 1) HIPCHK(hipEventRecord(b->ev.lane_fork, lane[0]));
+        for (int q = 1; q < n; q++) HIPCHK(hipStreamWaitEvent(lane[q], b->ev.lane_fork, 0));
+        return SA_OK;
+    }
+    hipStream_t next() { return lane[n > 1 ? k++ % n : 0]; }   // the strip list first: on lane 0
+    int join(sa_batch *b) {
+        for (int q = 1; q < n; q++) {
+            HIPCHK(hipEventRecord(b->ev.lane_join[q], lane[q]));
+            HIPCHK(hipStreamWaitEvent(lane[0], b->ev.lane_join[q], 0));
+        }
+        return SA_OK;
+    }
+};
 
 template <typename AfterGroup>
 static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
     sa_plan_t *pl = b->plan;
     DevPlan P = make_devplan(b);
-    hipStream_t s0 = b->cstream[0], s1 = b->cstream[1];
+    hipStream_t s0 = b->lanes.compute[0], s1 = b->lanes.compute[1];
     HIPCHK(hipMemsetAsync(b->d_cand_count, 0, 4 * (size_t) at_least_1(pl->n_segs), s0));
     if (b->d_spec)   // all bits set = NaN: "not a segment of the ring / strip kernels" until their forward sweep says otherwise
         HIPCHK(hipMemsetAsync(b->d_spec, 0xff, 8 * (size_t) at_least_1(pl->n_segs), s0));
@@ -573,51 +642,28 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
     if (pl->n_ev > 0)
         hipLaunchKernelGGL(k_check_events, dim3((unsigned) std::min<long long>((pl->n_ev + 255) / 256, 2048)), dim3(256), 0, s0,
                            (const double *) b->d_ev, (long long) pl->n_ev, b->h_overflow);
-    HIPCHK(hipEventRecord(b->ev[0], s0));
+    HIPCHK(hipEventRecord(b->ev.pass_begin, s0));
     for (size_t c = 0; c < b->chunks.size(); c++) {
         const sa_launch_chunk &C = b->chunks[c];
         const sa_ids &Lg = C.ids[LC_GENERIC], &Ls = C.ids[LC_STRIP], &Lf = C.ids[LC_FAST];
-        HIPCHK(hipEventRecord(b->cev[2 * c], s0));
+        HIPCHK(hipEventRecord(b->chunk_ev[c].fwd_begin, s0));
         if (Lg.n) launch_fwd_generic(P, b->d_ids + Lg.off, Lg.n, s0, b->gen_threads, b->relax, b->ring_cap);
-        {   // ring-kernel regions, one launch per class of row capacity.  A forward launch holds one workgroup per read and
-            // lasts as long as its longest read's serial chain, so launches that follow each other on one stream leave the chip
-            // mostly empty three times over: the classes alternate between the two compute streams and run side by side
-            const int n_cl = n_nonempty(C.ids, LC_RING, LC_N);   // (the strip kernels' list among them)
-            hipStream_t lanes[4] = {s0, s1, b->xstream[0], b->xstream[1]};
-            int n_lanes = n_cl < 4 ? n_cl : 4;
-            for (int q = 2; q < n_lanes; q++)   // the two extra streams are made on first need
-                if (!lanes[q]) {
-                    if (g_handles.stream(&b->xstream[q - 2], b->device, 0) != hipSuccess) { n_lanes = q; break; }
-                    lanes[q] = b->xstream[q - 2];
-                }
-            if (P.m.hdp) {   // the emission plane of this pass's ring / strip regions, ahead of the sweeps that read it (on s0: the
-                             // other lanes wait for the event recorded below)
-                if (Ls.n) launch_emit_hdp(P, b->d_ids + Ls.off, Ls.n, pl->regions[b->ids_flat[(size_t) Ls.off]].N, s0, true, false);
-                for (int cl = 0; cl < 16; cl++) {
-                    const sa_ids &L = C.ids[LC_RING + cl];
-                    if (L.n)
-                        launch_emit_hdp(P, b->d_ids + L.off, L.n, pl->regions[b->ids_flat[(size_t) L.off]].N, s0, true, ring_class(cl).multi);
-                }
-            }
-            if (n_lanes > 1) {
-                HIPCHK(hipEventRecord(b->ev[1], s0));
-                for (int q = 1; q < n_lanes; q++) HIPCHK(hipStreamWaitEvent(lanes[q], b->ev[1], 0));
-            }
-            int which = 0;
-            if (Ls.n) {
-                launch_fwd_strip(P, b->d_ids + Ls.off, Ls.n, lanes[0], b->d_seam, make_strip_t(P, pl->n_ev + 8, b->seam_cap, 0));
-                which = n_lanes > 1 ? 1 : 0;
-            }
-            TRY(for_each_ring_list(C.ids, [&](const sa_ids &L, int cap, bool multi) {
-                const int rcl = launch_fwd_ring(P, b->d_ids + L.off, L.n, lanes[n_lanes > 1 ? which : 0], cap, multi);
-                which = (which + 1) % (n_lanes > 1 ? n_lanes : 1);
-                return rcl;
-            }));
-            for (int q = 1; q < n_lanes; q++) {
-                HIPCHK(hipEventRecord(b->ev[1 + q], lanes[q]));
-                HIPCHK(hipStreamWaitEvent(s0, b->ev[1 + q], 0));
+        sa_ring_lanes R(b, C.ids);
+        if (P.m.hdp) {   // the emission plane of this pass's ring / strip regions, ahead of the sweeps that read it (on s0: the
+                         // other lanes wait for the fork)
+            if (Ls.n) launch_emit_hdp(P, b->d_ids + Ls.off, Ls.n, pl->regions[b->ids_flat[(size_t) Ls.off]].N, s0, true, false);
+            for (int cl = 0; cl < 16; cl++) {
+                const sa_ids &L = C.ids[LC_RING + cl];
+                if (L.n)
+                    launch_emit_hdp(P, b->d_ids + L.off, L.n, pl->regions[b->ids_flat[(size_t) L.off]].N, s0, true, ring_class(cl).multi);
             }
         }
+        TRY(R.fork(b));
+        if (Ls.n) launch_fwd_strip(P, b->d_ids + Ls.off, Ls.n, R.next(), b->d_seam, make_strip_t(P, pl->n_ev + 8, b->seam_cap, 0));
+        TRY(for_each_ring_list(C.ids, [&](const sa_ids &L, int cap, bool multi) {
+            return launch_fwd_ring(P, b->d_ids + L.off, L.n, R.next(), cap, multi);
+        }));
+        TRY(R.join(b));
         // (Round 5, measured and dropped: the pass's HDP regions in 2 / 4 / 8 slices on the two compute streams alternately, so that the
         // forward sweep of slice k runs beside the emission kernel of slice k + 1 -- neither keeps the chip busy alone --: forward
         // stage 15.8 -> 18.6 / 17.1 / 20.0 ms per 5000 reads.  A forward launch of fewer reads lasts as long as its longest chain and
@@ -629,24 +675,18 @@ static int enqueue_pass(sa_batch *b, bool finalize, AfterGroup after_group) {
             if (n_nonempty(C.ids, LC_FAST, LC_N) > 0 && sb_ > sa_)
                 hipLaunchKernelGGL(k_spec_match, dim3((unsigned) (sb_ - sa_)), dim3(64), 0, s0, P, (int) sa_, (int) (sb_ - sa_), b->d_spec);
         }
-        HIPCHK(hipEventRecord(b->cev[2 * c + 1], s0));
-        if (C.g1 - C.g0 > 1) HIPCHK(hipStreamWaitEvent(s1, b->cev[2 * c + 1], 0));
+        HIPCHK(hipEventRecord(b->chunk_ev[c].fwd_end, s0));
+        if (C.g1 - C.g0 > 1) HIPCHK(hipStreamWaitEvent(s1, b->chunk_ev[c].fwd_end, 0));
         int submitted = C.g0, completed = C.g0;
         while (completed < C.g1) {
-            while (submitted < C.g1) {
-                int rc = submit_group(b, P, submitted, (submitted - C.g0) & 1, finalize);
-                if (rc) return rc;
-                submitted++;
-            }
-            int rcg = after_group((size_t) completed);
-            if (rcg) return rcg;
-            completed++;
+            for (; submitted < C.g1; submitted++) TRY(submit_group(b, P, submitted, (submitted - C.g0) & 1, finalize));
+            TRY(after_group((size_t) completed++));
         }
         // the next chunk's forward sweep reuses the forward storage: both streams must be done with it
         for (int g = C.g0; g < C.g1; g++)
-            if ((g - C.g0) & 1) HIPCHK(hipStreamWaitEvent(s0, b->gev[4 * g + 2], 0));
+            if ((g - C.g0) & 1) HIPCHK(hipStreamWaitEvent(s0, b->group_ev[(size_t) g].ready, 0));
     }
-    HIPCHK(hipEventRecord(b->ev[5], s0));
+    HIPCHK(hipEventRecord(b->ev.pass_end, s0));
     HIPCHK(hipGetLastError());
     return SA_OK;
 }
@@ -656,18 +696,18 @@ static int collect_times(sa_batch *b) {
     float ms_f = 0, ms_b = 0, ms_tot = 0, t = 0;
     for (size_t c = 0; c < b->chunks.size(); c++) {
         const sa_launch_chunk &C = b->chunks[c];
-        HIPCHK(hipEventElapsedTime(&t, b->cev[2 * c], b->cev[2 * c + 1]));
+        HIPCHK(hipEventElapsedTime(&t, b->chunk_ev[c].fwd_begin, b->chunk_ev[c].fwd_end));
         ms_f += t;
         // backward stage of the chunk: from the end of its forward sweep to the last backward kernel's end (the
         // groups' kernels overlap on two streams; finalisation kernels of earlier groups run inside this window)
         float last = 0;
         for (int g = C.g0; g < C.g1; g++) {
-            HIPCHK(hipEventElapsedTime(&t, b->cev[2 * c + 1], b->gev[4 * g + 1]));
+            HIPCHK(hipEventElapsedTime(&t, b->chunk_ev[c].fwd_end, b->group_ev[(size_t) g].bwd_end));
             last = t > last ? t : last;
         }
         ms_b += last;
     }
-    HIPCHK(hipEventElapsedTime(&ms_tot, b->ev[0], b->ev[5]));
+    HIPCHK(hipEventElapsedTime(&ms_tot, b->ev.pass_begin, b->ev.pass_end));
     b->stats.ms_forward = ms_f;
     b->stats.ms_backward = ms_b;
     b->stats.ms_fold = ms_tot - ms_f - ms_b;  // what follows the last backward kernel: fold (+ finalisation) of the last group
@@ -697,233 +737,253 @@ static int grow_after_overflow(sa_batch *b) {
     return SA_OK;
 }
 
-// kernels only (host finalisation follows): SA_FLAG_EXACT and the expectation pass
-static int run_passes(sa_batch_t *b) {
-    for (int attempt = 0; attempt < 6; attempt++) {
-        int rc = enqueue_pass(b, false, [](size_t) { return (int) SA_OK; });
-        if (rc) return rc;
-        HIPCHK(sa_sync_stream(b->cstream[1], b->device));
-        HIPCHK(sa_sync_stream(b->cstream[0], b->device));
-        rc = collect_times(b);
-        if (rc) return rc;
-        if (b->h_overflow[2]) return SA_EINVAL;   // (k_spec_match: a forward value that is not a number)
-        if (!b->h_overflow[0]) return SA_OK;
-        rc = grow_after_overflow(b);
-        if (rc) return rc;
+// SA_SPEC_DEBUG: how far the exact totals of a traceback lie from its speculative total (expected: ~1e-3)
+static int spec_debug_dump(sa_batch *b) {
+    const sa_plan_t *pl = b->plan;
+    const long long n_segs = pl->n_segs;
+    std::vector<double> sp((size_t) n_segs), tt((size_t) at_least_1(pl->n_cks));
+    HIPCHK(hipMemcpy(sp.data(), b->d_spec, 8 * (size_t) n_segs, hipMemcpyDeviceToHost));
+    if (pl->n_cks) HIPCHK(hipMemcpy(tt.data(), b->d_totals, 8 * (size_t) pl->n_cks, hipMemcpyDeviceToHost));
+    double worst_lo = 0, worst_hi = 0;
+    long long n_spec = 0, shown = 0;
+    for (long long sg = 0; sg < n_segs; sg++) {
+        if (!(sp[(size_t) sg] == sp[(size_t) sg]) || !(sp[(size_t) sg] > -INFINITY)) continue;
+        n_spec++;
+        const sa_seg_t *S = &pl->segs[sg];
+        for (int c = 0; c < S->n_ck; c++) {
+            const double dlt = tt[(size_t) (S->ck_base + c)] - sp[(size_t) sg];
+            if (dlt < worst_lo) worst_lo = dlt;
+            if (dlt > worst_hi) worst_hi = dlt;
+            if (dlt < -b->spec_slack && shown < 6) {
+                shown++;
+                fprintf(stderr, "[spec] segment %lld (region %d, start %lld from %lld to %lld at_end %d) checkpoint %d of %d: total %.6f spec %.6f\n",
+                        sg, S->region, (long long) S->start, (long long) S->from, (long long) S->to, S->at_end, c, S->n_ck,
+                        tt[(size_t) (S->ck_base + c)], sp[(size_t) sg]);
+            }
+        }
     }
-    return SA_ENOMEM;
+    fprintf(stderr, "[spec] %lld segments with a speculative total; exact total - speculative total in [%.3e, %.3e]; slack %.3g\n",
+            n_spec, worst_lo, worst_hi, b->spec_slack);
+    return SA_OK;
 }
 
-static int batch_run_body(sa_batch_t *b) {
-    if (b->expect) return SA_ESTATE;
-    HIPCHK(hipSetDevice(b->device));
+// After a pass has been queued: waits for it, takes its times and looks at what its kernels raised.  *again: the pass has to be
+// repeated (more candidate slots, or a lower candidate bound).  `finalized`: k_finalize ran and the pairs travel on the pair stream
+// (trace_t0: SA_TRACE, the run's start), else host finalisation follows.  The groups' lanes only: the others were joined to lane 0.
+static int after_pass(sa_batch *b, bool finalized, const double *trace_t0, bool piped, bool *again) {
+    const sa_plan_t *pl = b->plan;
+    HIPCHK(sa_sync_stream(b->lanes.compute[1], b->device));
+    HIPCHK(sa_sync_stream(b->lanes.compute[0], b->device));
+    if (finalized) {
+        if (trace_t0) fprintf(stderr, "[trace] compute stream drained at %.3f ms\n", now_ms() - *trace_t0);
+        HIPCHK(sa_sync_stream(b->lanes.pair, b->device));
+        if (trace_t0) fprintf(stderr, "[trace] copies drained at %.3f ms (piped %d)\n", now_ms() - *trace_t0, (int) piped);
+    }
+    TRY(collect_times(b));
+    if (finalized && b->d_spec && getenv("SA_SPEC_DEBUG")) TRY(spec_debug_dump(b));
+    if (b->h_overflow[2]) {   // (k_check_events / k_spec_match)
+        if (finalized) fprintf(stderr, "[signalalign_hip] an event mean (or a model entry: a traceback's forward values) is not a finite number: no result\n");
+        return SA_EINVAL;
+    }
+    *again = true;
+    if (finalized && b->h_overflow[1] && b->d_spec) {
+        // a traceback's exact totals fell below its speculative total minus the slack (not seen with the default slack: the
+        // totals of one traceback agree to ~1e-2, the flat HDP fixture's to 0.15; tests/test_gpu_parity.py forces it with
+        // SA_TEST_SPEC_SLACK): its candidates may be incomplete -- the pass is repeated with a bound far lower (more candidates,
+        // same survivors): x4, then x256 more, and if that is not enough with no bound at all (slack +inf: every posterior
+        // cell-path is a candidate and k_finalize's check cannot fire again) -- never accepted as it is
+        if (std::isinf(b->spec_slack)) return SA_ESTATE;   // (cannot happen: with an infinite slack the flag is never raised)
+        b->spec_repeats++;
+        b->spec_slack = b->spec_repeats == 1 ? b->spec_slack * 4.0 : (b->spec_repeats == 2 ? b->spec_slack * 256.0 : (double) INFINITY);
+        if (!getenv("SA_TEST_SPEC_SLACK")) spec_memo_note(pl->model, b->device, b->spec_slack);
+        fprintf(stderr, "[signalalign_hip] a speculative candidate bound was too high; repeating the pass with slack %g\n", b->spec_slack);
+        return SA_OK;
+    }
+    if (b->h_overflow[0]) return grow_after_overflow(b);
+    *again = false;
+    return SA_OK;
+}
+
+// kernels only (host finalisation follows): SA_FLAG_EXACT and the expectation pass
+static int run_passes(sa_batch_t *b) {
+    bool again = true;
+    for (int attempt = 0; attempt < 6 && again; attempt++) {
+        TRY(enqueue_pass(b, false, [](size_t) { return (int) SA_OK; }));
+        TRY(after_pass(b, false, nullptr, false, &again));
+    }
+    return again ? SA_ENOMEM : SA_OK;
+}
+
+// the pinned result block: room for `total` records
+static int reserve_pairs(sa_batch *b, long long total) {
+    if (total > b->h_pairs_cap) {
+        g_sa_pool.put(SaPool::PINNED, b->h_pairs);
+        b->h_pairs = nullptr;
+        const long long cap = pairs_block_cap(total);
+        HIPCHK(g_sa_pool.get(SaPool::PINNED, (void **) &b->h_pairs, b->rec() * (size_t) cap, b->device));
+        b->h_pairs_cap = cap;
+    }
+    return SA_OK;
+}
+
+// SA_FLAG_EXACT: the kernels, then finalisation on the host with the C library's exp(): bit-identical to the reference's
+// posterior arithmetic
+static int run_exact(sa_batch *b) {
     sa_plan_t *pl = b->plan;
-    long long n_segs = pl->n_segs;
-    b->n_pairs_total = 0;
-    b->job_off.assign((size_t) pl->n_jobs + 1, 0);
-    auto reserve_pairs = [&](long long total) -> int {
-        if (total > b->h_pairs_cap) {
-            g_sa_pool.put(SaPool::PINNED, b->h_pairs);
-            b->h_pairs = nullptr;
-            const long long cap = pairs_block_cap(total);
-            HIPCHK(g_sa_pool.get(SaPool::PINNED, (void **) &b->h_pairs, b->rec() * (size_t) cap, b->device));
-            b->h_pairs_cap = cap;
-        }
-        return SA_OK;
-    };
-    // A first estimate of the result size (measured: 0.9 pairs per event at the default threshold) lets even the FIRST run
-    // of a batch overlap its copies with the kernels; with the caching allocator the buffer is a reused block.  If the
-    // estimate is short the run falls back to copying afterwards, as before.
-    if (!(b->flags & SA_FLAG_EXACT) && b->h_pairs_cap == 0 && pl->params.threshold >= 0.005) {
-        // (an estimate: when the pinned block cannot be had at that size the run copies after its kernels, exactly as with no estimate)
-        if (reserve_pairs(expected_pairs(b)) != SA_OK) {
-            (void) hipGetLastError();
-            b->h_pairs = nullptr;
-            b->h_pairs_cap = 0;
-        }
-    }
-    if (b->flags & SA_FLAG_EXACT) {
-        int rcp0 = run_passes(b);
-        if (rcp0) return rcp0;
-        // host finalisation with the C library's exp(): bit-identical to the reference's posterior arithmetic
-        std::vector<sa_cand_t> cands((size_t) at_least_1(pl->n_cand));
-        std::vector<int> counts((size_t) at_least_1(n_segs));
-        std::vector<double> totals((size_t) at_least_1(pl->n_cks));
-        if (pl->n_cand) HIPCHK(hipMemcpy(cands.data(), b->d_cands, sizeof(sa_cand_t) * (size_t) pl->n_cand, hipMemcpyDeviceToHost));
-        if (n_segs) HIPCHK(hipMemcpy(counts.data(), b->d_cand_count, 4 * (size_t) n_segs, hipMemcpyDeviceToHost));
-        if (pl->n_cks) HIPCHK(hipMemcpy(totals.data(), b->d_totals, 8 * (size_t) pl->n_cks, hipMemcpyDeviceToHost));
-        std::vector<sa_pair_t *> pp((size_t) at_least_1(pl->n_jobs), nullptr);
-        std::vector<int64_t> np((size_t) at_least_1(pl->n_jobs), 0);
-        int rc = sa_plan_finalize(pl, cands.data(), counts.data(), totals.data(), pp.data(), np.data());
-        if (rc) return rc;
-        if (!b->h_vc_bits.empty()) {   // SA_FLAG_VC_ROWS on host-finalised pairs: the same test as k_finalize's
-            b->job_all_n.assign((size_t) pl->n_jobs, 0);
-            b->job_all_sum.assign((size_t) pl->n_jobs, 0);
-            for (long long j = 0; j < pl->n_jobs; j++) {
-                const long long base = b->h_vc_off[(size_t) j];
-                int64_t kept = 0;
-                for (int64_t q = 0; q < np[j]; q++) {
-                    b->job_all_n[(size_t) j]++;
-                    b->job_all_sum[(size_t) j] += pp[j][q].prob_e7;
-                    const long long bit = base + pp[j][q].x;
-                    if ((b->h_vc_bits[(size_t) (bit >> 6)] >> (bit & 63)) & 1ull) pp[j][kept++] = pp[j][q];
-                }
-                np[j] = kept;
-            }
-        }
-        long long total = 0;
-        for (long long j = 0; j < pl->n_jobs; j++) total += np[j];
-        rc = reserve_pairs(total);
-        if (rc) return rc;
-        total = 0;
+    TRY(run_passes(b));
+    std::vector<sa_cand_t> cands((size_t) at_least_1(pl->n_cand));
+    std::vector<int> counts((size_t) at_least_1(pl->n_segs));
+    std::vector<double> totals((size_t) at_least_1(pl->n_cks));
+    if (pl->n_cand) HIPCHK(hipMemcpy(cands.data(), b->d_cands, sizeof(sa_cand_t) * (size_t) pl->n_cand, hipMemcpyDeviceToHost));
+    if (pl->n_segs) HIPCHK(hipMemcpy(counts.data(), b->d_cand_count, 4 * (size_t) pl->n_segs, hipMemcpyDeviceToHost));
+    if (pl->n_cks) HIPCHK(hipMemcpy(totals.data(), b->d_totals, 8 * (size_t) pl->n_cks, hipMemcpyDeviceToHost));
+    std::vector<sa_pair_t *> pp((size_t) at_least_1(pl->n_jobs), nullptr);
+    std::vector<int64_t> np((size_t) at_least_1(pl->n_jobs), 0);
+    TRY(sa_plan_finalize(pl, cands.data(), counts.data(), totals.data(), pp.data(), np.data()));
+    if (!b->h_vc_bits.empty()) {   // SA_FLAG_VC_ROWS on host-finalised pairs: the same test as k_finalize's
+        b->job_all_n.assign((size_t) pl->n_jobs, 0);
+        b->job_all_sum.assign((size_t) pl->n_jobs, 0);
         for (long long j = 0; j < pl->n_jobs; j++) {
-            b->job_off[j] = total;
+            const long long base = b->h_vc_off[(size_t) j];
+            int64_t kept = 0;
             for (int64_t q = 0; q < np[j]; q++) {
-                if (b->p8) reinterpret_cast<sa_pair8_t *>(b->h_pairs)[total + q] = sa_pair8_pack(pp[j][q].prob_e7, pp[j][q].x, pp[j][q].y);
-                else b->h_pairs[total + q] = sa_pair16_pack(pp[j][q].prob_e7, pp[j][q].x, pp[j][q].y, pp[j][q].path, pp[j][q].kmer_id);
+                b->job_all_n[(size_t) j]++;
+                b->job_all_sum[(size_t) j] += pp[j][q].prob_e7;
+                const long long bit = base + pp[j][q].x;
+                if ((b->h_vc_bits[(size_t) (bit >> 6)] >> (bit & 63)) & 1ull) pp[j][kept++] = pp[j][q];
             }
-            total += np[j];
-            free(pp[j]);
+            np[j] = kept;
         }
-        b->job_off[pl->n_jobs] = total;
-        b->n_pairs_total = total;
-        b->job_dev_off.clear();
-        b->ran = true;
-        return SA_OK;
     }
-    // default: finalisation on the device, group after group; the pairs of group g travel to the pinned host buffer
-    // on the copy stream while the kernels of group g+1 run
+    long long total = 0;
+    for (long long j = 0; j < pl->n_jobs; j++) total += np[j];
+    TRY(reserve_pairs(b, total));
+    total = 0;
+    for (long long j = 0; j < pl->n_jobs; j++) {
+        b->job_off[j] = total;
+        for (int64_t q = 0; q < np[j]; q++) {
+            if (b->p8) reinterpret_cast<sa_pair8_t *>(b->h_pairs)[total + q] = sa_pair8_pack(pp[j][q].prob_e7, pp[j][q].x, pp[j][q].y);
+            else b->h_pairs[total + q] = sa_pair16_pack(pp[j][q].prob_e7, pp[j][q].x, pp[j][q].y, pp[j][q].path, pp[j][q].kmer_id);
+        }
+        total += np[j];
+        free(pp[j]);
+    }
+    b->job_off[pl->n_jobs] = total;
+    b->n_pairs_total = total;
+    b->job_dev_off.clear();
+    return SA_OK;
+}
+
+// default: finalisation on the device, group after group; the pairs of group g travel to the pinned host buffer on the pair
+// stream while the kernels of group g+1 run.  gbase[g]: where group g's pairs start in it, gbase[n groups]: all pairs.
+static int run_device_finalized(sa_batch *b, std::vector<long long> &gbase) {
+    sa_plan_t *pl = b->plan;
     const size_t ng = b->groups.size();
-    std::vector<long long> gbase(ng + 1, 0);
-    bool done = false;
     const bool trace = getenv("SA_TRACE") != nullptr;
-    for (int attempt = 0; attempt < 6 && !done; attempt++) {
-        double t0 = now_ms();
+    bool again = true;
+    for (int attempt = 0; attempt < 6 && again; attempt++) {
+        const double t0 = now_ms();
         bool piped = true;
         long long running = 0;
         auto after_group = [&](size_t g) -> int {
             const sa_launch_group &G = b->groups[g];
-            HIPCHK(hipEventSynchronize(b->gev[4 * g + 2]));
+            HIPCHK(hipEventSynchronize(b->group_ev[g].ready));
             long long tg = b->h_seg_off[G.seg0 + g + (G.seg1 - G.seg0)];
             if (trace) fprintf(stderr, "[trace] group %zu ready at %.3f ms, %lld pairs\n", g, now_ms() - t0, tg);
             gbase[g] = running;
             if (piped && running + tg <= b->h_pairs_cap) {
                 if (tg > 0)
                     HIPCHK(hipMemcpyAsync(b->host_at(running), b->out_at(pl->segs[G.seg0].cand_off),
-                                          b->rec() * (size_t) tg, hipMemcpyDeviceToHost, b->pair_stream));
+                                          b->rec() * (size_t) tg, hipMemcpyDeviceToHost, b->lanes.pair));
             } else {
                 piped = false;  // first run (or a larger result than last time): size the pinned buffer afterwards
             }
             running += tg;
             return SA_OK;
         };
-        int rc = enqueue_pass(b, true, after_group);
-        if (rc) return rc;
+        TRY(enqueue_pass(b, true, after_group));
         gbase[ng] = running;
-        HIPCHK(sa_sync_stream(b->cstream[1], b->device));
-        HIPCHK(sa_sync_stream(b->cstream[0], b->device));
-        if (trace) fprintf(stderr, "[trace] compute stream drained at %.3f ms\n", now_ms() - t0);
-        HIPCHK(sa_sync_stream(b->pair_stream, b->device));
-        if (trace) fprintf(stderr, "[trace] copies drained at %.3f ms (piped %d)\n", now_ms() - t0, (int) piped);
-        rc = collect_times(b);
-        if (rc) return rc;
-        if (b->d_spec && getenv("SA_SPEC_DEBUG")) {
-            // diagnostic: how far the exact totals of a traceback lie from its speculative total (expected: ~1e-3)
-            std::vector<double> sp((size_t) n_segs), tt((size_t) at_least_1(pl->n_cks));
-            HIPCHK(hipMemcpy(sp.data(), b->d_spec, 8 * (size_t) n_segs, hipMemcpyDeviceToHost));
-            if (pl->n_cks) HIPCHK(hipMemcpy(tt.data(), b->d_totals, 8 * (size_t) pl->n_cks, hipMemcpyDeviceToHost));
-            double worst_lo = 0, worst_hi = 0;
-            long long n_spec = 0, shown = 0;
-            for (long long sg = 0; sg < n_segs; sg++) {
-                if (!(sp[(size_t) sg] == sp[(size_t) sg]) || !(sp[(size_t) sg] > -INFINITY)) continue;
-                n_spec++;
-                const sa_seg_t *S = &pl->segs[sg];
-                for (int c = 0; c < S->n_ck; c++) {
-                    const double dlt = tt[(size_t) (S->ck_base + c)] - sp[(size_t) sg];
-                    if (dlt < worst_lo) worst_lo = dlt;
-                    if (dlt > worst_hi) worst_hi = dlt;
-                    if (dlt < -b->spec_slack && shown < 6) {
-                        shown++;
-                        fprintf(stderr, "[spec] segment %lld (region %d, start %lld from %lld to %lld at_end %d) checkpoint %d of %d: total %.6f spec %.6f\n",
-                                sg, S->region, (long long) S->start, (long long) S->from, (long long) S->to, S->at_end, c, S->n_ck,
-                                tt[(size_t) (S->ck_base + c)], sp[(size_t) sg]);
-                    }
-                }
-            }
-            fprintf(stderr, "[spec] %lld segments with a speculative total; exact total - speculative total in [%.3e, %.3e]; slack %.3g\n",
-                    n_spec, worst_lo, worst_hi, b->spec_slack);
+        TRY(after_pass(b, true, trace ? &t0 : nullptr, piped, &again));
+        if (again || piped) continue;
+        TRY(reserve_pairs(b, running));
+        for (size_t g = 0; g < ng; g++) {
+            const sa_launch_group &G = b->groups[g];
+            long long tg = gbase[g + 1] - gbase[g];
+            if (tg > 0)
+                HIPCHK(hipMemcpyAsync(b->host_at(gbase[g]), b->out_at(pl->segs[G.seg0].cand_off),
+                                      b->rec() * (size_t) tg, hipMemcpyDeviceToHost, b->lanes.pair));
         }
-        if (b->h_overflow[2]) {
-            fprintf(stderr, "[signalalign_hip] an event mean (or a model entry: a traceback's forward values) is not a finite number: no result\n");
-            return SA_EINVAL;
-        }
-        if (b->h_overflow[1] && b->d_spec) {
-            // a traceback's exact totals fell below its speculative total minus the slack (not seen with the default slack: the
-            // totals of one traceback agree to ~1e-2, the flat HDP fixture's to 0.15; tests/test_gpu_parity.py forces it with
-            // SA_TEST_SPEC_SLACK): its candidates may be incomplete -- the pass is repeated with a bound far lower (more candidates,
-            // same survivors): x4, then x256 more, and if that is not enough with no bound at all (slack +inf: every posterior
-            // cell-path is a candidate and k_finalize's check cannot fire again) -- never accepted as it is
-            if (std::isinf(b->spec_slack)) return SA_ESTATE;   // (cannot happen: with an infinite slack the flag is never raised)
-            b->spec_repeats++;
-            b->spec_slack = b->spec_repeats == 1 ? b->spec_slack * 4.0 : (b->spec_repeats == 2 ? b->spec_slack * 256.0 : (double) INFINITY);
-            if (!getenv("SA_TEST_SPEC_SLACK")) spec_memo_note(pl->model, b->device, b->spec_slack);
-            fprintf(stderr, "[signalalign_hip] a speculative candidate bound was too high; repeating the pass with slack %g\n", b->spec_slack);
-            continue;
-        }
-        if (b->h_overflow[0]) {
-            rc = grow_after_overflow(b);
-            if (rc) return rc;
-            continue;
-        }
-        if (!piped) {
-            rc = reserve_pairs(running);
-            if (rc) return rc;
-            for (size_t g = 0; g < ng; g++) {
-                const sa_launch_group &G = b->groups[g];
-                long long tg = gbase[g + 1] - gbase[g];
-                if (tg > 0)
-                    HIPCHK(hipMemcpyAsync(b->host_at(gbase[g]), b->out_at(pl->segs[G.seg0].cand_off),
-                                          b->rec() * (size_t) tg, hipMemcpyDeviceToHost, b->pair_stream));
-            }
-            HIPCHK(sa_sync_stream(b->pair_stream, b->device));
-        }
-        done = true;
+        HIPCHK(sa_sync_stream(b->lanes.pair, b->device));
     }
-    if (!done) return SA_ENOMEM;
-    // job offsets: a job's pairs start where its first segment's do
-    {
-        std::vector<int> seg_group((size_t) at_least_1(n_segs), 0);
-        for (size_t g = 0; g < ng; g++)
-            for (long long sg = b->groups[g].seg0; sg < b->groups[g].seg1; sg++) seg_group[sg] = (int) g;
-        long long next = gbase[ng];
-        b->job_dev_off.assign((size_t) pl->n_jobs, 0);
-        for (long long j = pl->n_jobs - 1; j >= 0; j--) {
-            const sa_jobinfo_t *J = &pl->jobs[j];
-            long long first_seg = -1;
-            for (long long r = J->region_off; r < J->region_off + J->n_regions && first_seg < 0; r++)
-                if (pl->regions[r].n_seg > 0) first_seg = pl->regions[r].seg_off;
-            if (first_seg >= 0) {
-                int g = seg_group[first_seg];
-                next = gbase[g] + b->h_seg_off[first_seg + g];
-                // the group's pairs sit in d_out from its first segment's candidate slot on
-                b->job_dev_off[j] = pl->segs[b->groups[g].seg0].cand_off + b->h_seg_off[first_seg + g];
-            }
-            b->job_off[j] = next;  // jobs without segments are empty ranges in front of the next job
+    return again ? SA_ENOMEM : SA_OK;
+}
+
+// job offsets after device finalisation: a job's pairs start where its first segment's do
+static void index_jobs(sa_batch *b, const std::vector<long long> &gbase) {
+    const sa_plan_t *pl = b->plan;
+    const size_t ng = b->groups.size();
+    std::vector<int> seg_group((size_t) at_least_1(pl->n_segs), 0);
+    for (size_t g = 0; g < ng; g++)
+        for (long long sg = b->groups[g].seg0; sg < b->groups[g].seg1; sg++) seg_group[sg] = (int) g;
+    long long next = gbase[ng];
+    b->job_dev_off.assign((size_t) pl->n_jobs, 0);
+    for (long long j = pl->n_jobs - 1; j >= 0; j--) {
+        const sa_jobinfo_t *J = &pl->jobs[j];
+        long long first_seg = -1;
+        for (long long r = J->region_off; r < J->region_off + J->n_regions && first_seg < 0; r++)
+            if (pl->regions[r].n_seg > 0) first_seg = pl->regions[r].seg_off;
+        if (first_seg >= 0) {
+            int g = seg_group[first_seg];
+            next = gbase[g] + b->h_seg_off[first_seg + g];
+            // the group's pairs sit in d_out from its first segment's candidate slot on
+            b->job_dev_off[j] = pl->segs[b->groups[g].seg0].cand_off + b->h_seg_off[first_seg + g];
         }
-        b->job_off[pl->n_jobs] = gbase[ng];
-        b->n_pairs_total = gbase[ng];
+        b->job_off[j] = next;  // jobs without segments are empty ranges in front of the next job
     }
-    if (b->d_seg_all) {   // SA_FLAG_VC_ROWS: what the dropped rows would have added to a job's count and score
-        std::vector<long long> sa_((size_t) (2 * at_least_1(n_segs)), 0);
-        if (n_segs) HIPCHK(hipMemcpy(sa_.data(), b->d_seg_all, sizeof(long long) * 2 * (size_t) n_segs, hipMemcpyDeviceToHost));
-        b->job_all_n.assign((size_t) pl->n_jobs, 0);
-        b->job_all_sum.assign((size_t) pl->n_jobs, 0);
-        for (long long sg = 0; sg < n_segs; sg++) {
-            const long long j = pl->regions[pl->segs[sg].region].job;
-            b->job_all_n[(size_t) j] += sa_[(size_t) (2 * sg)];
-            b->job_all_sum[(size_t) j] += sa_[(size_t) (2 * sg + 1)];
-        }
+    b->job_off[pl->n_jobs] = gbase[ng];
+    b->n_pairs_total = gbase[ng];
+}
+
+// SA_FLAG_VC_ROWS after device finalisation: what the dropped rows would have added to a job's count and score
+static int vc_row_totals(sa_batch *b) {
+    const sa_plan_t *pl = b->plan;
+    const long long n_segs = pl->n_segs;
+    std::vector<long long> sa_((size_t) (2 * at_least_1(n_segs)), 0);
+    if (n_segs) HIPCHK(hipMemcpy(sa_.data(), b->d_seg_all, sizeof(long long) * 2 * (size_t) n_segs, hipMemcpyDeviceToHost));
+    b->job_all_n.assign((size_t) pl->n_jobs, 0);
+    b->job_all_sum.assign((size_t) pl->n_jobs, 0);
+    for (long long sg = 0; sg < n_segs; sg++) {
+        const long long j = pl->regions[pl->segs[sg].region].job;
+        b->job_all_n[(size_t) j] += sa_[(size_t) (2 * sg)];
+        b->job_all_sum[(size_t) j] += sa_[(size_t) (2 * sg + 1)];
     }
+    return SA_OK;
+}
+
+static int batch_run_body(sa_batch_t *b) {
+    if (b->expect) return SA_ESTATE;
+    HIPCHK(hipSetDevice(b->device));
+    sa_plan_t *pl = b->plan;
+    b->n_pairs_total = 0;
+    b->job_off.assign((size_t) pl->n_jobs + 1, 0);
+    if (b->flags & SA_FLAG_EXACT) {
+        TRY(run_exact(b));
+        b->ran = true;
+        return SA_OK;
+    }
+    // A first estimate of the result size (measured: 0.9 pairs per event at the default threshold) lets even the FIRST run
+    // of a batch overlap its copies with the kernels; with the caching allocator the buffer is a reused block.  If the
+    // estimate is short the run falls back to copying afterwards, as before.
+    // (an estimate: when the pinned block cannot be had at that size the run copies after its kernels, exactly as with no estimate)
+    if (b->h_pairs_cap == 0 && pl->params.threshold >= 0.005 && reserve_pairs(b, expected_pairs(b)) != SA_OK) {
+        (void) hipGetLastError();
+        b->h_pairs = nullptr;
+        b->h_pairs_cap = 0;
+    }
+    std::vector<long long> gbase(b->groups.size() + 1, 0);
+    TRY(run_device_finalized(b, gbase));
+    index_jobs(b, gbase);
+    if (b->d_seg_all) TRY(vc_row_totals(b));
     g_pairs_memo.note(pl->model->uid, b->device, pl->params.threshold, (double) b->n_pairs_total, (double) pl->n_ev);
     b->ran = true;
     return SA_OK;
@@ -1000,11 +1060,7 @@ int sa_batch_release_device(sa_batch_t *b) {
     if (!b->ran || b->runner) return SA_ESTATE;   // (between sa_batch_start and sa_batch_wait: the run is still using it)
     if (b->released) return SA_OK;
     if (hipSetDevice(b->device) != hipSuccess) return SA_ENODEVICE;
-    for (int i = 0; i < 2; i++) {   // (a finished run has drained them; a failed one may not have)
-        if (b->cstream[i]) HIPCHK(sa_sync_stream(b->cstream[i], b->device));
-        if (b->xstream[i]) HIPCHK(sa_sync_stream(b->xstream[i], b->device));
-    }
-    if (b->pair_stream) HIPCHK(sa_sync_stream(b->pair_stream, b->device));
+    HIPCHK(b->lanes.drain(b->device, false));   // (a finished run has drained them; a failed one may not have)
     b->put_blocks(0, sa_batch::BLK_END);
     if (b->held_stage) { g_sa_pool.put(SaPool::PINNED, b->held_stage); b->held_stage = nullptr; }
     for (SaAmbigTab *tab : b->ambig_tab) sa_ambig_release_device(tab);
@@ -1182,13 +1238,13 @@ int sa_expect_batch(const sa_model_t *m, const sa_params_t *p, const sa_job_t *j
         return SA_ENOMEM;
     }
     auto dl = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream));
+        if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->lanes.compute[0]));
         return SA_OK;
     };
     auto tail = [&]() -> int {
-        HIPCHK(hipMemsetAsync(d_red, 0, 64 * (size_t) at_least_1(n_jobs), b->stream));
+        HIPCHK(hipMemsetAsync(d_red, 0, 64 * (size_t) at_least_1(n_jobs), b->lanes.compute[0]));
         if (pl->n_regions > 0) {
-            hipLaunchKernelGGL(k_expect_reduce, dim3((unsigned) pl->n_regions), dim3(64), 0, b->stream, make_devplan(b), d_red,
+            hipLaunchKernelGGL(k_expect_reduce, dim3((unsigned) pl->n_regions), dim3(64), 0, b->lanes.compute[0], make_devplan(b), d_red,
                                (int) pl->n_regions);
             HIPCHK(hipGetLastError());
         }
@@ -1196,7 +1252,7 @@ int sa_expect_batch(const sa_model_t *m, const sa_params_t *p, const sa_job_t *j
         if (!rc_ && want_cands) rc_ = dl(hb + o_tot, b->d_totals, 8 * (size_t) pl->n_cks);
         if (!rc_ && want_cands) rc_ = dl(hb + o_cnt, b->d_cand_count, 4 * (size_t) pl->n_segs);
         if (!rc_ && want_cands) rc_ = dl(hb + o_cand, b->d_cands, sizeof(sa_cand_t) * (size_t) pl->n_cand);
-        if (!rc_ && sa_sync_stream(b->stream, b->device) != hipSuccess) rc_ = SA_ENODEVICE;
+        if (!rc_ && sa_sync_stream(b->lanes.compute[0], b->device) != hipSuccess) rc_ = SA_ENODEVICE;
         return rc_;
     };
     rc = tail();

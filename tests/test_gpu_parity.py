@@ -410,6 +410,35 @@ def test_strip_kernels_wide_bands_bit_identical_to_the_ring_kernels(oracle, monk
             assert np.array_equal(strip[j], ring[j]), (kw, j, len(strip[j]), len(ring[j]))
 
 
+def test_ring_classes_fork_over_four_lanes_and_a_batch_equals_its_jobs(monkeypatch, capfd):
+    """A pass forks the forward launches of its ring-kernel classes over up to four compute lanes and joins them again
+    (sa_ring_lanes).  Four reads without anchors -- the band is the whole matrix -- of 160, 260, 360 and 460 events: their widest
+    diagonals hold 92, 157, 217 and 276 cells (the planner, on the host), one read in each of the row classes (64, 128], (128, 192],
+    (192, 256] and (256, 320].  With SA_STRIP=0 those are four lists of the ring kernels, one per lane, beside two dense-anchor
+    reads on the register kernels; every job's pairs equal the pairs of the same job in a batch of its own (one list, one lane)."""
+    pm = sa.Model.load(cases.MODEL_6MER)
+    p = sa.default_params()
+    alpha, k, t10, tab = synth.parse_model_table(cases.MODEL_6MER)
+    jobs = []
+    for n_ev, idx in ((160, 52), (260, 53), (360, 54), (460, 55)):
+        r = synth.make_read(idx, n_ev, alpha, k, tab)
+        jobs.append(dict(r, ax=np.zeros(0, dtype=np.int64), ay=np.zeros(0, dtype=np.int64)))
+    jobs += cases.synthetic_jobs(cases.MODEL_6MER, 2, 900, 300)
+    monkeypatch.setenv("SA_STRIP", "0")
+    alone = [_run(pm, p, [job])[0][0] for job in jobs]
+    monkeypatch.setenv("SA_TRACE", "1")
+    capfd.readouterr()
+    got, st = _run(pm, p, jobs)
+    err = capfd.readouterr().err
+    monkeypatch.delenv("SA_TRACE")
+    assert st.n_ring_regions == 4 and st.n_strip_regions == 0 and st.n_fast_regions >= 2 and st.n_chunks == 1
+    assert st.n_ring_regions + st.n_fast_regions == st.n_regions
+    lines = [ln for ln in err.splitlines() if ln.startswith("[trace] pass:")]   # (one per pass: a repeated pass forks again)
+    assert lines and all(ln == "[trace] pass: 4 ring lists on 4 lanes" for ln in lines), lines
+    for j in range(len(jobs)):
+        assert len(got[j]) > 0 and np.array_equal(got[j], alone[j]), j
+
+
 def test_ring_kernels_ambiguous_positions_every_read_against_the_oracle(oracle, monkeypatch):
     """BASELINE configs[2] shape (ACEGT model, every CpG cytosine X -> C/E: 1, 2, 4 or 8 paths per cell) and the R7.3
     ACEGOT model with the default table's three-way code L -> C/E/O: the ring kernels with per-path neighbour records
