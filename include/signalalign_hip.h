@@ -644,6 +644,78 @@ typedef struct sa_snp_site {
 int sa_snp_write_read(const char *path, const char *fast5_input, const char *read_id, const char *contig, int backward,
                       const sa_snp_site_t *sites, int64_t n);
 
+/* ---- Single-nucleotide probabilities marginalised over reads ----------------------------------------------------------------
+ * Replaces call_sites_with_marginal_probs / scan_for_proposals (src/signalalign/scripts/variantCallingLib.py:114-164, :226-271)
+ * over the per-read files of --snp-step: an accumulator holds, per contig position, a forward sum and a backward sum of four
+ * doubles (A, C, G, T) and a row count, in HBM across batches, as sa_kmer_table_t holds its rows.
+ *   rows of a site   every (read, strand) line whose contig and position name it
+ *   order            calls in call order; inside one call ascending run ordinal, within a run strand t before c, then the order
+ *                    given.  A caller that adds reads in ascending run order gets "run order" over the whole table.
+ *   sums             (fwd if direction else bwd)[l] += p[l], doubles added serially in that order, starting from the sums the
+ *                    accumulator holds: add(A); add(B) is add(A + B), bit for bit
+ *   direction        (read mapped forward and strand t) or (read mapped backward and strand c)
+ *   marginal         m = [fwd[0] + bwd[3], fwd[1] + bwd[2], fwd[2] + bwd[1], fwd[3] + bwd[0]], total = ((m[0] + m[1]) + m[2]) + m[3],
+ *                    prob[l] = m[l] / total, called = the first letter of largest prob
+ * Two deliberate differences from the reference: its loader (load_variant_call_data) predates the contig column that
+ * CallMethylation.write now puts first and would mix contigs, so sites are grouped by (contig, position) here; and the row order
+ * is run order, not a directory listing's (the same difference as sa_kmer_table's).
+ * step >= 1: sa_snp_marginals_add_batch drops the positions outside call_methyls' window (sa_snp_site_window over the
+ * reference_index of every record of a group's jobs); step == 0: no window.  Storage is 76 bytes per contig position (sums,
+ * counts and the working arrays of an add) and as much again from the first checkpoint on: SA_ENOMEM when it does not fit,
+ * SA_ENODEVICE without a GPU.  One add call takes at most 2^30 rows (SA_EUNSUPPORTED).  An add that fails on the device after its
+ * first kernel leaves the accumulator unusable: every later call on it but destroy returns SA_ESTATE. */
+typedef struct sa_snp_marginals sa_snp_marginals_t;
+typedef struct sa_snp_job_map {   /* job j of a batch, for sa_snp_marginals_add_batch */
+    int32_t contig, pos_sign;     /* index p of the job's ref lies at contig position pos0 + pos_sign * p (pos_sign +1 or -1) */
+    int64_t pos0;
+    int64_t x0;                   /* a record's x has the TSV's reference_index x0 + x_sign * x (adjustReferenceCoordinate)  */
+    int32_t x_sign, strand;       /* strand 0 't', 1 'c'                                                                     */
+    int32_t direction, pad;       /* 1: forward sum, 0: backward sum                                                         */
+    int64_t run;                  /* run ordinal of the read                                                                 */
+    int64_t group;                /* jobs with the same id are the strands of one read's one step file: they share a window */
+} sa_snp_job_map_t;
+typedef struct sa_snp_marginal {
+    int64_t pos;
+    int32_t contig, depth;        /* depth: rows of the site                                                                 */
+    double fwd[4], bwd[4], prob[4];
+    double delta;                 /* max(prob) - prob[reference letter]; 0 without an A/C/G/T reference letter               */
+    char called, ref;             /* called: 'N' when total == 0; ref: upper-cased, 'N' without ref_by_contig                */
+    char is_proposal, pad[5];     /* reference letter in ACGT and != called (and total != 0)                                 */
+} sa_snp_marginal_t;
+int sa_snp_marginals_create(sa_snp_marginals_t **out, const int64_t *contig_lens, int64_t n_contigs, int64_t step, int device);
+void sa_snp_marginals_destroy(sa_snp_marginals_t *t);
+/* rows computed elsewhere for one read (`run` orders rows inside one call only; all rows here share it): sites[i].pos is a
+ * position of `contig`, sites[i].strand 0 or 1.  A position outside the contig, a strand that is neither: SA_EINVAL, nothing added. */
+int sa_snp_marginals_add_sites(sa_snp_marginals_t *t, int32_t contig, int64_t run, int direction, const sa_snp_site_t *sites, int64_t n);
+/* chained onto a finished batch created with SA_FLAG_POSITION_CALLS: the position calls are folded on the device by the code of
+ * sa_batch_position_calls, mapped by map[j] and added; no call crosses PCIe.  Rows are ordered by (run, strand, job).  Not run,
+ * or created without the flag: SA_ESTATE.  A kept position outside its contig, a bad contig, sign or strand: SA_EINVAL and
+ * nothing is added.  kernel_ms_out[0]: the shared position fold, kernel_ms_out[1]: what follows it (may be NULL). */
+int sa_snp_marginals_add_batch(sa_snp_marginals_t *t, sa_batch_t *b, const sa_snp_job_map_t *map, int64_t n_jobs, double *kernel_ms_out);
+/* the contract of sa_kmer_table_checkpoint / _rollback; rollback without a checkpoint: SA_ESTATE */
+int sa_snp_marginals_checkpoint(sa_snp_marginals_t *t);
+int sa_snp_marginals_rollback(sa_snp_marginals_t *t);
+/* marginal, normalisation, called base and comparison with the reference letter on the device; the sites with at least one row
+ * and at least min_depth of them come back in (contig, position) order (*sites_out malloc'd, sa_free).  ref_by_contig (may be
+ * NULL: no proposals): one sequence per contig, of at least the contig's length.  The accumulator is left as it is. */
+int sa_snp_marginals_finish(sa_snp_marginals_t *t, int64_t min_depth, const char *const *ref_by_contig, sa_snp_marginal_t **sites_out,
+                            int64_t *n_out, double *kernel_ms_out);
+/* ---- host helpers of the error-correction loop (scripts/jamison.py, variantCallingLib.py) ----
+ * sa_snp_group_sites: group_sites_in_window (jamison.py:66-83).  The n sites are sorted by (pos, delta); a group grows while the
+ * next site lies less than `window` after the previous one, and yields the position of its largest delta (the first of equals).
+ * The reference's loop stops with one site left over, so a trailing site that would start a group of its own is lost:
+ * keep_last == 0 restates that, keep_last != 0 keeps the site.  out needs n entries. */
+int sa_snp_group_sites(const int64_t *pos, const double *delta, int64_t n, int64_t window, int keep_last, int64_t *out, int64_t *n_out);
+/* sa_snp_substitute with an ascending list of contig positions instead of a period (make_degenerate_reference with positions) */
+int sa_snp_substitute_sites(const char *ref, int64_t len, int64_t contig_pos_of_ref0, int reversed, const int64_t *sites,
+                            int64_t n_sites, char letter, char *out);
+/* `ref` (contig `contig`, position 0 first) with the called base of every proposal of that contig written in: what
+ * call_sites_with_marginal_probs(get_sites=False) returns.  update_reference_with_marginal_probs passes get_sites=True and so
+ * gets a site list where it wants the sequence -- a reference bug; this is the intent.  out needs len + 1 bytes. */
+int sa_snp_apply_calls(const char *ref, int64_t len, const sa_snp_marginal_t *marginals, int64_t n, int32_t contig, char *out);
+/* one line per site, "contig\tsite\tdepth\tpA\tpC\tpG\tpT\tcalled\tref\tdelta\n", the doubles as Python's str(float) */
+int sa_snp_write_marginals(const char *path, const char *const *contig_names, const sa_snp_marginal_t *marginals, int64_t n);
+
 /* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
  * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
  * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output

@@ -67,6 +67,18 @@ class SnpSite(C.Structure):
     _fields_ = [("pos", C.c_int64), ("strand", C.c_int32), ("pad", C.c_int32), ("p", C.c_double * 4)]
 
 
+class SnpJobMap(C.Structure):
+    """sa_snp_job_map_t (include/signalalign_hip.h)"""
+    _fields_ = [("contig", C.c_int32), ("pos_sign", C.c_int32), ("pos0", C.c_int64), ("x0", C.c_int64), ("x_sign", C.c_int32),
+                ("strand", C.c_int32), ("direction", C.c_int32), ("pad", C.c_int32), ("run", C.c_int64), ("group", C.c_int64)]
+
+
+SNP_SITE_DTYPE = np.dtype([("pos", "<i8"), ("strand", "<i4"), ("pad", "<i4"), ("p", "<f8", (4,))])
+SNP_MARGINAL_DTYPE = np.dtype([("pos", "<i8"), ("contig", "<i4"), ("depth", "<i4"), ("fwd", "<f8", (4,)), ("bwd", "<f8", (4,)),
+                               ("prob", "<f8", (4,)), ("delta", "<f8"), ("called", "S1"), ("ref", "S1"), ("is_proposal", "i1"),
+                               ("pad", "S1", (5,))])
+
+
 class Pair(C.Structure):
     _fields_ = [("prob_e7", C.c_int64), ("x", C.c_int32), ("y", C.c_int32), ("path", C.c_int32),
                 ("kmer_id", C.c_int32)]
@@ -169,7 +181,10 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_batch_create", "sa_batch_create_noise_scaled", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
            "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
            "sa_plan_check_path_records", "sa_dplan_compare",
-           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
+           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read",
+           "sa_snp_marginals_create", "sa_snp_marginals_destroy", "sa_snp_marginals_add_sites", "sa_snp_marginals_add_batch",
+           "sa_snp_marginals_checkpoint", "sa_snp_marginals_rollback", "sa_snp_marginals_finish", "sa_snp_group_sites",
+           "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet", "sa_hdp_state_vs_gaussian",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
@@ -351,6 +366,18 @@ def lib():
     L.sa_snp_substitute.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_char, C.c_char_p]
     L.sa_snp_site_window.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip]
     L.sa_snp_write_read.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(SnpSite), C.c_int64]
+    L.sa_snp_marginals_create.argtypes = [C.POINTER(C.c_void_p), ip, C.c_int64, C.c_int64, C.c_int]
+    L.sa_snp_marginals_destroy.argtypes = [C.c_void_p]
+    L.sa_snp_marginals_destroy.restype = None
+    L.sa_snp_marginals_add_sites.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_int64]
+    L.sa_snp_marginals_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SnpJobMap), C.c_int64, dp]
+    L.sa_snp_marginals_checkpoint.argtypes = [C.c_void_p]
+    L.sa_snp_marginals_rollback.argtypes = [C.c_void_p]
+    L.sa_snp_marginals_finish.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), ip, dp]
+    L.sa_snp_group_sites.argtypes = [ip, dp, C.c_int64, C.c_int64, C.c_int, ip, ip]
+    L.sa_snp_substitute_sites.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, ip, C.c_int64, C.c_char, C.c_char_p]
+    L.sa_snp_apply_calls.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_char_p]
+    L.sa_snp_write_marginals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_int64]
     L.sa_kmer_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_double, C.c_int]
     L.sa_kmer_table_destroy.argtypes = [C.c_void_p]
     L.sa_kmer_table_destroy.restype = None
@@ -1864,6 +1891,117 @@ def snp_write_read(path, fast5_input, read_id, contig, backward, sites):
             arr[i].p[q] = float(p[q])
     _chk(lib().sa_snp_write_read(path.encode(), fast5_input.encode(), read_id.encode(), contig.encode(), 1 if backward else 0,
                                  arr, len(sites)), "sa_snp_write_read")
+
+
+class SnpMarginals:
+    """sa_snp_marginals_t: per contig position a forward and a backward sum of (pA, pC, pG, pT) over reads and a row count,
+    kept in HBM across add_sites / add_batch calls.  step >= 1: add_batch filters by call_methyls' window; 0: no window."""
+
+    def __init__(self, contig_lens, step=0, device=0):
+        self._h = C.c_void_p()
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        self.n_contigs = len(lens)
+        self.contig_lens = [int(v) for v in lens]
+        _chk(lib().sa_snp_marginals_create(C.byref(self._h), _ip(lens), len(lens), int(step), int(device)), "sa_snp_marginals_create")
+
+    def add_sites(self, contig, sites, direction, run=0):
+        """rows of one read: `sites` a SNP_SITE_DTYPE array, or an iterable of (pos, strand 0/1, (pA, pC, pG, pT))"""
+        if isinstance(sites, np.ndarray) and sites.dtype == SNP_SITE_DTYPE:
+            arr = np.ascontiguousarray(sites)
+        else:
+            sites = list(sites)
+            arr = np.zeros(len(sites), dtype=SNP_SITE_DTYPE)
+            for i, (pos, strand, p) in enumerate(sites):
+                arr[i]["pos"], arr[i]["strand"], arr[i]["p"] = int(pos), int(strand), p
+        _chk(lib().sa_snp_marginals_add_sites(self._h, int(contig), int(run), 1 if direction else 0, arr.ctypes.data, len(arr)),
+             "sa_snp_marginals_add_sites")
+
+    def add_batch(self, batch, job_map, stats=None):
+        """chained onto a finished Batch created with FLAG_POSITION_CALLS; job_map: per job a dict with the fields of
+        sa_snp_job_map_t (contig, pos0, pos_sign, x0, x_sign, strand, direction, run, group)"""
+        job_map = list(job_map)
+        arr = (SnpJobMap * max(len(job_map), 1))()
+        for i, m in enumerate(job_map):
+            for f in ("contig", "pos_sign", "pos0", "x0", "x_sign", "strand", "direction", "run", "group"):
+                setattr(arr[i], f, int(m[f]))
+        kms = (C.c_double * 2)()
+        _chk(lib().sa_snp_marginals_add_batch(self._h, batch._h, arr, len(job_map), kms), "sa_snp_marginals_add_batch")
+        if stats is not None:
+            stats["kernel_ms_position_fold"], stats["kernel_ms"] = kms[0], kms[1]
+
+    def checkpoint(self):
+        _chk(lib().sa_snp_marginals_checkpoint(self._h), "sa_snp_marginals_checkpoint")
+
+    def rollback(self):
+        _chk(lib().sa_snp_marginals_rollback(self._h), "sa_snp_marginals_rollback")
+
+    def finish(self, min_depth=1, ref_by_contig=None, stats=None):
+        """structured array (SNP_MARGINAL_DTYPE): the sites with rows, in (contig, position) order"""
+        refs = None
+        if ref_by_contig is not None:
+            keep = [r.encode() if isinstance(r, str) else bytes(r) for r in ref_by_contig]
+            if len(keep) != self.n_contigs or any(len(r) < n for r, n in zip(keep, self.contig_lens)):
+                raise ValueError("ref_by_contig: one sequence per contig, each at least as long as its contig")
+            refs = (C.c_char_p * len(keep))(*keep)
+        ptr = C.c_void_p()
+        n = np.zeros(1, dtype=np.int64)
+        kms = C.c_double()
+        _chk(lib().sa_snp_marginals_finish(self._h, int(min_depth), refs, C.byref(ptr), _ip(n), C.byref(kms)), "sa_snp_marginals_finish")
+        out = np.zeros(int(n[0]), dtype=SNP_MARGINAL_DTYPE)
+        if n[0]:
+            C.memmove(out.ctypes.data, ptr, out.nbytes)
+        lib().sa_free(ptr)
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+        return out
+
+    def close(self):
+        if self._h:
+            lib().sa_snp_marginals_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def snp_group_sites(pos, delta, window=6, keep_last=True):
+    """sa_snp_group_sites (group_sites_in_window): the position of the largest delta of every group"""
+    p = np.ascontiguousarray(pos, dtype=np.int64)
+    d = np.ascontiguousarray(delta, dtype=np.float64)
+    assert len(p) == len(d)
+    out = np.zeros(max(len(p), 1), dtype=np.int64)
+    n = np.zeros(1, dtype=np.int64)
+    _chk(lib().sa_snp_group_sites(_ip(p), _dp(d), len(p), int(window), 1 if keep_last else 0, _ip(out), _ip(n)), "sa_snp_group_sites")
+    return [int(v) for v in out[:int(n[0])]]
+
+
+def snp_substitute_sites(ref, contig_pos_of_ref0, sites, reversed=False, letter="X"):
+    """sa_snp_substitute_sites: `letter` at the listed contig positions (ascending) inside the window, the rest upper-cased"""
+    b = ref.encode() if isinstance(ref, str) else bytes(ref)
+    s = np.ascontiguousarray(sites, dtype=np.int64)
+    out = C.create_string_buffer(len(b) + 1)
+    _chk(lib().sa_snp_substitute_sites(b, len(b), int(contig_pos_of_ref0), 1 if reversed else 0, _ip(s), len(s),
+                                       letter.encode()[:1], out), "sa_snp_substitute_sites")
+    return out.raw[:len(b)].decode()
+
+
+def snp_apply_calls(ref, marginals, contig=0):
+    """sa_snp_apply_calls: `ref` with every proposal's called base written in"""
+    b = ref.encode() if isinstance(ref, str) else bytes(ref)
+    m = np.ascontiguousarray(marginals, dtype=SNP_MARGINAL_DTYPE)
+    out = C.create_string_buffer(len(b) + 1)
+    _chk(lib().sa_snp_apply_calls(b, len(b), m.ctypes.data, len(m), int(contig), out), "sa_snp_apply_calls")
+    return out.raw[:len(b)].decode()
+
+
+def snp_write_marginals(path, contig_names, marginals):
+    m = np.ascontiguousarray(marginals, dtype=SNP_MARGINAL_DTYPE)
+    keep = [c.encode() for c in contig_names]
+    names = (C.c_char_p * max(len(keep), 1))(*keep)
+    _chk(lib().sa_snp_write_marginals(os.fsencode(path), names, m.ctypes.data, len(m)), "sa_snp_write_marginals")
 
 
 def format_py_repr(v):

@@ -529,25 +529,26 @@ __global__ __launch_bounds__(64) void k_pos_compact(SiteTabs T, const unsigned *
 
 static SaScratch g_pos_ws;
 
-extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out,
-                                       int32_t *x_min_out, int32_t *x_max_out, double *kernel_ms_out) {
-    (void) flags;
-    if (!b || !calls_out || !n_out) return SA_EINVAL;
+// the position fold of a finished batch, left on the device (SaPosFold, sa_chain.h)
+int sa_pos_fold_run(sa_batch_t *b, SaPosFold *F) {
     SaAmbigTab *P = nullptr;
     int64_t nj64 = 0;
     int rc = sa_batch_ambig(b, SA_TAB_POSITIONS, &P, &nj64);
     if (rc) return rc;
-    const size_t nj = (size_t) nj64;
-    for (size_t j = 0; j < nj; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
-    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    const size_t nj = F->nj = (size_t) nj64;
+    F->tab = P;
+    F->n_kept = 0;
+    F->kernel_ms = 0.0;
+    F->h_off.assign(nj + 1, 0);
     if (nj == 0) return SA_OK;
-    const size_t stride = (size_t) (P->stride > 0 ? P->stride : 1), ns = (size_t) P->n_sites;
+    const size_t stride = F->stride = (size_t) (P->stride > 0 ? P->stride : 1), ns = (size_t) P->n_sites;
     SaBatchView V;
     if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
     if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
     const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
-    const int device = V.device;
-    const std::vector<long long> &count = V.count;
+    const int device = F->device = V.device;
+    F->count = V.count;
+    const std::vector<long long> &count = F->count;
     for (size_t j = 0; j < nj; j++)   // (a job's bucket entries, at most k per record, are counted in 32 bits)
         if ((long long) P->k * count[j] >= (long long) INT32_MAX) return SA_EUNSUPPORTED;
     const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, SA_ORDINAL_PER_JOB);
@@ -561,17 +562,13 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
                  o_base = L.add(8 * (nj + 1)), o_kept = L.add(4 * nj), o_off = L.add(8 * (nj + 1)), o_xmin = L.add(4 * nj),
                  o_xmax = L.add(4 * nj), o_oslot = L.add(4 * ns1), o_on = L.add(4 * ns1), o_osum = L.add(8 * ns1 * stride),
                  o_oprob = L.add(8 * ns1 * stride), dev_bytes = L.end;
-    std::vector<long long> h_base(nj + 1, 0), h_off(nj + 1, 0);
-    std::vector<int> h_xmin(nj), h_xmax(nj);
-    std::vector<int> h_slot;
-    std::vector<unsigned> h_cnt;
-    std::vector<double> h_sum, h_prob;
-    char *d = nullptr;
-    unsigned long long *d_ent = nullptr;
+    std::vector<long long> h_base(nj + 1, 0);
+    std::vector<long long> &h_off = F->h_off;
+    char *&d = F->d;
+    unsigned long long *&d_ent = F->d_ent;
     SaScratch &W = g_pos_ws;
-    std::unique_lock<std::mutex> guard(W.mu);
+    F->guard = std::unique_lock<std::mutex>(W.mu);
     float kms0 = 0, kms1 = 0;
-    size_t n_kept = 0;
     SiteTabs T;
     if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(P, device)) != SA_OK) return rc;
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
@@ -609,19 +606,71 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
     SA_HIP_GOTO_DONE(W.time_end());
     SA_HIP_GOTO_DONE(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
     SA_HIP_GOTO_DONE(W.time_ms(&kms1));
-    if (kernel_ms_out) *kernel_ms_out = (double) kms0 + (double) kms1;
-    n_kept = (size_t) h_off[nj];
-    SA_HIP_GOTO_DONE(hipMemcpy(h_xmin.data(), d + o_xmin, 4 * nj, hipMemcpyDeviceToHost));
-    SA_HIP_GOTO_DONE(hipMemcpy(h_xmax.data(), d + o_xmax, 4 * nj, hipMemcpyDeviceToHost));
+    F->kernel_ms = (double) kms0 + (double) kms1;
+    F->n_kept = (size_t) h_off[nj];
+    F->off = (const long long *) (d + o_off);
+    F->slot = (const int *) (d + o_oslot);
+    F->n_rows = (const unsigned *) (d + o_on);
+    F->sum = (const double *) (d + o_osum);
+    F->prob = (const double *) (d + o_oprob);
+    F->xmin = (const int *) (d + o_xmin);
+    F->xmax = (const int *) (d + o_xmax);
+    F->kind = T.kind;
+    F->h_x = P->x.data();
+    F->acgt.assign(P->letters.size() * 4, (signed char) -1);
+    for (size_t kd = 0; kd < P->letters.size(); kd++)
+        for (int l = 0; l < 4; l++) {
+            const size_t e = P->letters[kd].find("ACGT"[l]);
+            if (e != std::string::npos) F->acgt[kd * 4 + (size_t) l] = (signed char) e;
+        }
+done:
+    return rc;
+}
+
+void sa_pos_fold_release(SaPosFold *F, bool failed) {
+    if (failed && F->d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
+    if (F->d) g_sa_pool.put(SaPool::DEVICE, F->d);
+    if (F->d_ent) g_sa_pool.put(SaPool::DEVICE, F->d_ent);
+    F->d = nullptr;
+    F->d_ent = nullptr;
+    if (F->guard.owns_lock()) F->guard.unlock();
+}
+
+extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out,
+                                       int32_t *x_min_out, int32_t *x_max_out, double *kernel_ms_out) {
+    (void) flags;
+    if (!b || !calls_out || !n_out) return SA_EINVAL;
+    SaPosFold F;
+    {   // (the entries of the outputs are cleared before anything can fail, for a batch whose table exists)
+        SaAmbigTab *P0 = nullptr;
+        int64_t nj0 = 0;
+        const int rc0 = sa_batch_ambig(b, SA_TAB_POSITIONS, &P0, &nj0);
+        if (rc0) return rc0;
+        for (int64_t j = 0; j < nj0; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+        if (kernel_ms_out) *kernel_ms_out = 0.0;
+        if (nj0 == 0) return SA_OK;
+    }
+    int rc = sa_pos_fold_run(b, &F);
+    const size_t nj = F.nj, stride = F.stride, n_kept = F.n_kept;
+    const SaAmbigTab *P = F.tab;
+    const std::vector<long long> &count = F.count, &h_off = F.h_off;
+    std::vector<int> h_xmin(nj), h_xmax(nj);
+    std::vector<int> h_slot;
+    std::vector<unsigned> h_cnt;
+    std::vector<double> h_sum, h_prob;
+    if (rc != SA_OK) goto done;
+    if (kernel_ms_out) *kernel_ms_out = F.kernel_ms;
+    SA_HIP_GOTO_DONE(hipMemcpy(h_xmin.data(), F.xmin, 4 * nj, hipMemcpyDeviceToHost));
+    SA_HIP_GOTO_DONE(hipMemcpy(h_xmax.data(), F.xmax, 4 * nj, hipMemcpyDeviceToHost));
     if (n_kept) {   // only the kept positions cross PCIe
         h_slot.resize(n_kept);
         h_cnt.resize(n_kept);
         h_sum.resize(n_kept * stride);
         h_prob.resize(n_kept * stride);
-        SA_HIP_GOTO_DONE(hipMemcpy(h_slot.data(), d + o_oslot, 4 * n_kept, hipMemcpyDeviceToHost));
-        SA_HIP_GOTO_DONE(hipMemcpy(h_cnt.data(), d + o_on, 4 * n_kept, hipMemcpyDeviceToHost));
-        SA_HIP_GOTO_DONE(hipMemcpy(h_sum.data(), d + o_osum, 8 * n_kept * stride, hipMemcpyDeviceToHost));
-        SA_HIP_GOTO_DONE(hipMemcpy(h_prob.data(), d + o_oprob, 8 * n_kept * stride, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_slot.data(), F.slot, 4 * n_kept, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_cnt.data(), F.n_rows, 4 * n_kept, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_sum.data(), F.sum, 8 * n_kept * stride, hipMemcpyDeviceToHost));
+        SA_HIP_GOTO_DONE(hipMemcpy(h_prob.data(), F.prob, 8 * n_kept * stride, hipMemcpyDeviceToHost));
     }
     for (size_t j = 0; j < nj; j++) {
         const bool any = count[j] > 0;
@@ -652,9 +701,7 @@ extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_positio
         if (oom) rc = SA_ENOMEM;
     }
 done:
-    if (rc != SA_OK && d) (void) hipStreamSynchronize(0);
-    if (d) g_sa_pool.put(SaPool::DEVICE, d);
-    if (d_ent) g_sa_pool.put(SaPool::DEVICE, d_ent);
+    sa_pos_fold_release(&F, rc != SA_OK);
     if (rc != SA_OK)
         for (size_t j = 0; j < nj; j++) { free(calls_out[j]); calls_out[j] = nullptr; n_out[j] = 0; }
     return rc;

@@ -35,6 +35,32 @@ void sa_ambig_free(SaAmbigTab *s);               // NULL: nothing
 // sa_hip.hip: a finished batch's table `which` (SA_ESTATE: created without the table's flag, or not run)
 int sa_batch_ambig(sa_batch_t *b, int which, SaAmbigTab **tab, int64_t *n_jobs);
 
+// The position fold of a finished batch, left on its device (sa_calls.hip): what sa_batch_position_calls copies out and what
+// sa_snp_marginals_add_batch (sa_marginals.hip) reads in place.  Record r of job j, off[j] <= r < off[j + 1], in position order:
+// slot[r] (the batch-wide index of the position), n_rows[r], prob[r * stride + e] for letter e of the slot's kind.
+// sa_pos_fold_run takes the lock of the position calls' scratch and sa_pos_fold_release gives it back with the device blocks;
+// release after a failed run is allowed.
+struct SaPosFold {
+    size_t nj = 0, stride = 1, n_kept = 0;
+    int device = 0;
+    double kernel_ms = 0.0;
+    std::vector<long long> count;          // per job: its records
+    std::vector<long long> h_off;          // nj + 1
+    const long long *off = nullptr;        // device, nj + 1
+    const int *slot = nullptr, *xmin = nullptr, *xmax = nullptr;   // xmin / xmax: per job, of a job with records only
+    const unsigned *n_rows = nullptr;
+    const double *sum = nullptr, *prob = nullptr;
+    const unsigned char *kind = nullptr;   // device, per slot
+    const int *h_x = nullptr;              // host, per slot: its index in the job's ref
+    std::vector<signed char> acgt;         // host, kind * 4 + l: which letter of the kind is "ACGT"[l], -1 none
+    SaAmbigTab *tab = nullptr;
+    char *d = nullptr;                     // the call's device blocks (g_sa_pool)
+    unsigned long long *d_ent = nullptr;
+    std::unique_lock<std::mutex> guard;
+};
+int sa_pos_fold_run(sa_batch_t *b, SaPosFold *F);
+void sa_pos_fold_release(SaPosFold *F, bool failed);
+
 // The posterior the TSV prints, "%f" of prob_e7 / 1e7, in integers of 1e-6: a decimal rounding of a binary double.  Only a
 // last digit of 5 can tie; then the sign of q * 1e7 - prob_e7 (one fma, exact in sign) says on which side of the tie the
 // double q = prob_e7 / 1e7 lies, and an exact tie goes to even as glibc's printf does.  tests/test_host_mea.py checks every

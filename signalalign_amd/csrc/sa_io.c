@@ -786,3 +786,81 @@ int sa_snp_write_read(const char *path, const char *fast5_input, const char *rea
     free(v);
     return fclose(fh) == 0 ? SA_OK : SA_EIO;
 }
+
+/* ---- the error-correction loop over the marginals (include/signalalign_hip.h): group_sites_in_window (jamison.py:66-83),
+ * make_degenerate_reference with positions, the corrected reference and the marginals file ---- */
+typedef struct { int64_t pos; double delta; } snp_cand_t;
+static int cmp_snp_cand(const void *a, const void *b) {
+    const snp_cand_t *x = a, *y = b;
+    if (x->pos != y->pos) return x->pos < y->pos ? -1 : 1;
+    return x->delta < y->delta ? -1 : x->delta > y->delta;
+}
+int sa_snp_group_sites(const int64_t *pos, const double *delta, int64_t n, int64_t window, int keep_last, int64_t *out, int64_t *n_out) {
+    if (n < 0 || !n_out || (n > 0 && (!pos || !delta || !out))) return SA_EINVAL;
+    *n_out = 0;
+    if (n == 0) return SA_OK;
+    snp_cand_t *v = malloc(sizeof(*v) * (size_t) n);
+    if (!v) return SA_ENOMEM;
+    for (int64_t i = 0; i < n; i++) { v[i].pos = pos[i]; v[i].delta = delta[i]; }
+    qsort(v, (size_t) n, sizeof(*v), cmp_snp_cand);
+    int64_t i = 0, m = 0;
+    while (i + 1 < n || (keep_last && i < n)) {
+        int64_t best = i;
+        while (i + 1 < n && v[i + 1].pos - v[i].pos < window) {
+            i++;
+            if (v[i].delta > v[best].delta) best = i;
+        }
+        out[m++] = v[best].pos;
+        i++;
+    }
+    *n_out = m;
+    free(v);
+    return SA_OK;
+}
+
+int sa_snp_substitute_sites(const char *ref, int64_t len, int64_t contig_pos_of_ref0, int reversed, const int64_t *sites,
+                            int64_t n_sites, char letter, char *out) {
+    if (!ref || !out || len < 0 || n_sites < 0 || (n_sites > 0 && !sites)) return SA_EINVAL;
+    for (int64_t i = 1; i < n_sites; i++)
+        if (sites[i] < sites[i - 1]) return SA_EINVAL;
+    for (int64_t i = 0; i < len; i++) {
+        const char ch = ref[i];
+        out[i] = (ch >= 'a' && ch <= 'z') ? (char) (ch - 'a' + 'A') : ch;
+    }
+    out[len] = 0;
+    const int64_t lo = reversed ? contig_pos_of_ref0 - (len - 1) : contig_pos_of_ref0;
+    for (int64_t s = 0; s < n_sites; s++) {
+        if (sites[s] < lo || sites[s] >= lo + len) continue;
+        out[reversed ? contig_pos_of_ref0 - sites[s] : sites[s] - contig_pos_of_ref0] = letter;
+    }
+    return SA_OK;
+}
+
+int sa_snp_apply_calls(const char *ref, int64_t len, const sa_snp_marginal_t *marginals, int64_t n, int32_t contig, char *out) {
+    if (!ref || !out || len < 0 || n < 0 || (n > 0 && !marginals)) return SA_EINVAL;
+    memcpy(out, ref, (size_t) len);
+    out[len] = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const sa_snp_marginal_t *m = &marginals[i];
+        if (m->contig != contig || !m->is_proposal) continue;
+        if (m->pos < 0 || m->pos >= len) return SA_EINVAL;
+        out[m->pos] = m->called;
+    }
+    return SA_OK;
+}
+
+int sa_snp_write_marginals(const char *path, const char *const *contig_names, const sa_snp_marginal_t *marginals, int64_t n) {
+    if (!path || !contig_names || n < 0 || (n > 0 && !marginals)) return SA_EINVAL;
+    FILE *fh = fopen(path, "w");
+    if (!fh) return SA_EIO;
+    setvbuf(fh, NULL, _IOFBF, 1 << 16);
+    char num[5][40];
+    for (int64_t i = 0; i < n; i++) {
+        const sa_snp_marginal_t *m = &marginals[i];
+        for (int l = 0; l < 4; l++) sa_format_py_repr(num[l], m->prob[l]);
+        sa_format_py_repr(num[4], m->delta);
+        fprintf(fh, "%s\t%" PRId64 "\t%d\t%s\t%s\t%s\t%s\t%c\t%c\t%s\n", contig_names[m->contig], m->pos, (int) m->depth, num[0], num[1],
+                num[2], num[3], m->called, m->ref, num[4]);
+    }
+    return fclose(fh) == 0 ? SA_OK : SA_EIO;
+}

@@ -104,6 +104,17 @@ static void usage(void) {
     fprintf(stderr, "--snp-step <N> --snp-dir <dir>: single-nucleotide probabilities: every read is aligned N times, with X at the\n"
                     "                  reference positions = s (mod N) in run s; <dir>/<label>.tsv gets pA pC pG pT per covered position\n"
                     "                  (singleNucleotideProbabilities.py); no posteriors file: no -u, a manifest's posteriors column '-'\n");
+    fprintf(stderr, "--snp-marginals <file> (with --snp-step): the probabilities summed over all reads of the run on the GPU, one line per\n"
+                    "                  covered site: contig, site, depth, pA pC pG pT, called base, reference base, delta\n"
+                    "                  (variantCallingLib.py call_sites_with_marginal_probs); --snp-dir becomes optional: without it no\n"
+                    "                  per-read call leaves the GPU.  1-D runs only (not with --twoD)\n"
+                    "--snp-proposals <file> (with --snp-marginals): contig, site, delta of the sites whose called base differs from the\n"
+                    "                  reference, thinned per contig to the largest delta of each run of sites less than 6 apart\n"
+                    "                  (jamison.py group_sites_in_window; a trailing lone site is kept)\n"
+                    "--snp-sites <file> (lines contig<TAB>site; with --snp-marginals, not with --snp-step): the second pass: every read\n"
+                    "                  is aligned once, with X at the listed sites inside its window, and the same table comes out\n"
+                    "--snp-reference-out <fasta> (with --snp-sites): the -f reference with the called base written in at every site\n"
+                    "                  whose call differs from it, records and line width as in -f\n");
     fprintf(stderr, "--train-assignments <file>: write the top-N assignments table of the run (buildAlignment: kmer, strand, descaled\n"
                     "                  mean, posterior; what buildHdpUtil -l reads), selected on the GPU\n"
                     "--train-template-model <file> / --train-complement-model <file>: write the -T / -C model with its Gaussian event\n"
@@ -396,6 +407,16 @@ typedef struct {
     int64_t out_fmt, constraint_trim;
     int64_t snp_step;       /* --snp-step N: single-nucleotide probabilities, N substituted copies of every read's reference */
     const char *snp_dir;    /* --snp-dir: where <label>.tsv goes */
+    /* --snp-marginals / --snp-proposals: the over-reads table on the GPU, the -f reference's records it is laid over, and the
+     * run's first read (a read's run ordinal is its place in the manifest) */
+    const char *snp_marg, *snp_prop;
+    /* --snp-sites: the listed sites per record of the -f reference, ascending; --snp-reference-out */
+    const char *snp_sites_path, *snp_ref_out;
+    int64_t **snp_sites, *snp_n_sites;
+    sa_snp_marginals_t *snp_tab;
+    char **snp_names, **snp_seqs;
+    int64_t *snp_lens, snp_n_contigs;
+    const void *reads0;
     const char *fwd_ref, *bwd_ref;
     sa_params_t p;
     strand_model_t sm[2];   /* [strand]: 0 template, 1 complement (--twoD only) */
@@ -1865,7 +1886,9 @@ static int64_t run_slice_align(run_t *R, read_t *reads, int64_t n_reads, int dev
  * Every read strand becomes N jobs in one batch: job s aligns the read to its window with X at the contig positions = s (mod N)
  * (replace_periodic_reference_positions; the default ambiguity table makes X the four bases).  sa_batch_position_calls folds
  * the rows of every X position on the device (CallMethylation.call_methyls); the N step files of a read are merged into
- * DIR/<label>.tsv (discover_single_nucleotide_probabilities).  fast5_input names the .npRead: the one deliberate difference. */
+ * DIR/<label>.tsv (discover_single_nucleotide_probabilities).  fast5_input names the .npRead: the one deliberate difference.
+ * --snp-marginals: every batch is also added to one over-reads table on the device (sa_snp_marginals_add_batch), written at the
+ * end of the run; --snp-sites: the same with one copy per read, X at the listed sites only (1-D runs). */
 typedef struct {   /* what one strand's batch leaves, [read * N + step] each */
     sa_position_call_t **calls;
     int64_t *n_calls;
@@ -1892,6 +1915,15 @@ static int64_t snp_contig_pos(const read_t *rd, int s, int64_t t) {
     const int64_t off = rd->st[s].r_shift;
     const int same = (s == 0 && rd->forward) || (s == 1 && !rd->forward);
     return same ? off + t : off - 1 - t;
+}
+
+/* --snp-marginals: which record of the -f reference a read lies on */
+static int64_t snp_contig_index(const run_t *R, const read_t *rd) {
+    const char *name = rd->seq_name ? rd->seq_name : rd->pA->contig1;
+    int64_t ci = 0;
+    while (ci < R->snp_n_contigs && strcmp(R->snp_names[ci], name) != 0) ci++;
+    if (ci == R->snp_n_contigs) die("signalMachine: --snp-marginals: %s is no record of the -f reference", name);
+    return ci;
 }
 
 static void snp_output_one(int64_t j, void *ctx) {
@@ -1966,7 +1998,12 @@ static void snp_build_jobs(snp_slice_t *c) {
             const int64_t len = (int64_t) strlen(t);
             for (int64_t s = 0; s < N; s++) {
                 char *o = xalloc(len + 1, 1, 0);
-                sa_snp_substitute(t, len, from_fwd ? rd->win_lo : hi, !from_fwd, N, s, 'X', o);
+                if (sl->R->snp_sites) {   /* --snp-sites: X at the listed sites of the read's contig */
+                    const int64_t ci = snp_contig_index(sl->R, rd);
+                    sa_snp_substitute_sites(t, len, from_fwd ? rd->win_lo : hi, !from_fwd, sl->R->snp_sites[ci], sl->R->snp_n_sites[ci], 'X', o);
+                } else {
+                    sa_snp_substitute(t, len, from_fwd ? rd->win_lo : hi, !from_fwd, N, s, 'X', o);
+                }
                 c->tgt[q][j * N + s] = o;
                 c->jobs[q][j * N + s] = rd->jobs[q];
                 c->jobs[q][j * N + s].ref = o;
@@ -1997,6 +2034,35 @@ static void snp_close_up(snp_slice_t *c, int64_t n_before, const int64_t *kept_f
     }
 }
 
+/* --snp-marginals: the finished batch of strand q added to the run's table.  Job j * N + s is read j's copy s: where its target
+ * lies on the contig (snp_contig_pos), the reference_index of its records (adjust_ref), its direction, the read's place in the
+ * manifest as run ordinal, and one window per (read, step) */
+static int snp_add_to_marginals(snp_slice_t *c, int q, sa_batch_t *b) {
+    const run_t *R = c->sl.R;
+    const int64_t N = c->N, nj = c->sl.n_ok * N;
+    sa_snp_job_map_t *map = xalloc(nj, sizeof(*map), 1);
+    for (int64_t j = 0; j < c->sl.n_ok; j++) {
+        const read_t *rd = &c->sl.reads[c->sl.who[j]];
+        const int64_t ci = snp_contig_index(R, rd);
+        const int same = (q == 0 && rd->forward) || (q == 1 && !rd->forward);
+        const int64_t off = rd->st[q].r_shift, run = (int64_t) (rd - (const read_t *) R->reads0);
+        for (int64_t s = 0; s < N; s++) {
+            sa_snp_job_map_t *m = &map[j * N + s];
+            m->contig = (int32_t) ci;
+            m->pos_sign = m->x_sign = same ? 1 : -1;
+            m->pos0 = same ? off : off - 1;
+            m->x0 = same ? off : off - R->sm[q].k;   /* adjust_ref: len_kmers - (x + (len - off)) with len_kmers = len - k */
+            m->strand = q;
+            m->direction = same;
+            m->run = run;
+            m->group = run * N + s;
+        }
+    }
+    const int rc = sa_snp_marginals_add_batch(R->snp_tab, b, map, nj, NULL);
+    free(map);
+    return rc;
+}
+
 /* creates, runs and harvests the batch of strand q of a --snp-step slice into c->sr[q] */
 static int snp_run_strand_batch(snp_slice_t *c, int q) {
     snp_result_t *r = &c->sr[q];
@@ -2010,7 +2076,8 @@ static int snp_run_strand_batch(snp_slice_t *c, int q) {
     sa_batch_t *b = NULL;
     int rc = create_strand_batch(&b, &c->sl, q, c->jobs[q], nj, c->N, SA_FLAG_POSITION_CALLS);
     if (rc == SA_OK) rc = sa_batch_run(b);
-    if (rc == SA_OK) rc = sa_batch_position_calls(b, 0, r->calls, r->n_calls, r->x_min, r->x_max, NULL);
+    if (rc == SA_OK && c->sl.R->snp_dir) rc = sa_batch_position_calls(b, 0, r->calls, r->n_calls, r->x_min, r->x_max, NULL);
+    if (rc == SA_OK && c->sl.R->snp_tab) rc = snp_add_to_marginals(c, q, b);
     for (int64_t i = 0; i < nj && rc == SA_OK; i++) rc = sa_batch_all_pairs_summary(b, i, &r->n_pairs[i], &r->sum_e7[i]);
     sa_batch_destroy(b);
     return rc;
@@ -2021,16 +2088,19 @@ static int64_t run_slice_snp(run_t *R, read_t *reads, int64_t n_reads, int devic
     snp_slice_t c;
     memset(&c, 0, sizeof(c));
     slice_t *sl = &c.sl;
-    const int64_t N = c.N = R->snp_step;
+    const int64_t N = c.N = R->snp_step > 0 ? R->snp_step : 1;   /* (--snp-sites: one copy per read) */
     const double ts1 = now_s();
     slice_open(sl, R, reads, n_reads, device);
     snp_build_jobs(&c);
     int64_t *kept_from = xalloc(sl->n_ok, sizeof(int64_t), 0);
+    /* --snp-marginals: the table is checkpointed here, so that the retry below takes the slice's rows out again */
+    if (R->snp_tab && sa_snp_marginals_checkpoint(R->snp_tab) != SA_OK) die("signalMachine: --snp-marginals: checkpoint failed%s", "");
     for (int q = 0; q < n_strands(R) && sl->n_ok > 0; q++) {
         fprintf(stderr, "signalAlign - starting %s alignment\n", strand_name(q));
         const int64_t n_before = sl->n_ok;
         const int rc = snp_run_strand_batch(&c, q);
         if (drop_refused_reads(sl, rc, c.jobs, N, kept_from)) {
+            if (R->snp_tab && sa_snp_marginals_rollback(R->snp_tab) != SA_OK) die("signalMachine: --snp-marginals: rollback failed%s", "");
             snp_close_up(&c, n_before, kept_from);
             for (int q2 = 0; q2 <= q; q2++) snp_result_free(&c.sr[q2], n_before * N);
             q = -1;   /* both strands again, without the offenders */
@@ -2041,7 +2111,7 @@ static int64_t run_slice_snp(run_t *R, read_t *reads, int64_t n_reads, int devic
     free(kept_from);
     g_t_gpu += now_s() - ts1;
     const double ts2 = now_s();
-    parallel_for(sl->n_ok, snp_output_one, &c);
+    if (R->snp_dir) parallel_for(sl->n_ok, snp_output_one, &c);
     /* the summary lines of the N -s 0 runs of every read, step after step */
     for (int64_t j = 0; j < sl->n_ok; j++)
         for (int64_t s = 0; s < N; s++) {
@@ -2061,6 +2131,99 @@ static int64_t run_slice_snp(run_t *R, read_t *reads, int64_t n_reads, int devic
         free(c.tgt[q]); free(c.jobs[q]);
     }
     return slice_close(sl);
+}
+
+static int cmp_i64(const void *a, const void *b) {
+    const int64_t x = *(const int64_t *) a, y = *(const int64_t *) b;
+    return x < y ? -1 : x > y;
+}
+
+/* --snp-sites: lines "contig<TAB>site[<TAB>...]" (a --snp-proposals file among them) into ascending lists per record */
+static void load_snp_sites(run_t *R) {
+    FILE *fh = fopen(R->snp_sites_path, "r");
+    if (!fh) die("signalMachine: cannot read %s", R->snp_sites_path);
+    R->snp_sites = xalloc(R->snp_n_contigs, sizeof(int64_t *), 1);
+    R->snp_n_sites = xalloc(R->snp_n_contigs, sizeof(int64_t), 1);
+    char line[4096], name[2048];
+    while (fgets(line, sizeof line, fh)) {
+        int64_t site = 0;
+        if (line[0] == '\n' || line[0] == '#') continue;
+        if (sscanf(line, "%2047[^\t]\t%" SCNd64, name, &site) != 2) die("signalMachine: --snp-sites: cannot parse a line of %s", R->snp_sites_path);
+        int64_t ci = 0;
+        while (ci < R->snp_n_contigs && strcmp(R->snp_names[ci], name) != 0) ci++;
+        if (ci == R->snp_n_contigs || site < 0 || site >= R->snp_lens[ci]) die("signalMachine: --snp-sites: a site of %s is not in the -f reference", name);
+        R->snp_sites[ci] = realloc(R->snp_sites[ci], sizeof(int64_t) * (size_t) (R->snp_n_sites[ci] + 1));
+        if (!R->snp_sites[ci]) die("signalMachine: out of memory%s", "");
+        R->snp_sites[ci][R->snp_n_sites[ci]++] = site;
+    }
+    fclose(fh);
+    for (int64_t c = 0; c < R->snp_n_contigs; c++)
+        if (R->snp_n_sites[c]) qsort(R->snp_sites[c], (size_t) R->snp_n_sites[c], sizeof(int64_t), cmp_i64);
+}
+
+/* --snp-reference-out: every record of -f with the calls applied, lines as wide as the input's first sequence line */
+static void write_snp_reference(const run_t *R, const sa_snp_marginal_t *m, int64_t n) {
+    int64_t width = 60;
+    FILE *in = fopen(R->fwd_ref, "r");
+    if (in) {
+        char *buf = NULL;
+        size_t cap = 0;
+        ssize_t got;
+        while ((got = getline(&buf, &cap, in)) >= 0)
+            if (got > 0 && buf[0] != '>') {
+                while (got > 0 && (buf[got - 1] == '\n' || buf[got - 1] == '\r')) got--;
+                if (got > 0) width = (int64_t) got;
+                break;
+            }
+        free(buf);
+        fclose(in);
+    }
+    FILE *fh = fopen(R->snp_ref_out, "w");
+    if (!fh) die("signalMachine: cannot write %s", R->snp_ref_out);
+    for (int64_t c = 0; c < R->snp_n_contigs; c++) {
+        char *out = xalloc(R->snp_lens[c] + 1, 1, 0);
+        if (sa_snp_apply_calls(R->snp_seqs[c], R->snp_lens[c], m, n, (int32_t) c, out) != SA_OK) die("signalMachine: --snp-reference-out failed%s", "");
+        fprintf(fh, ">%s\n", R->snp_names[c]);
+        for (int64_t i = 0; i < R->snp_lens[c]; i += width)
+            fprintf(fh, "%.*s\n", (int) (R->snp_lens[c] - i < width ? R->snp_lens[c] - i : width), out + i);
+        free(out);
+    }
+    if (fclose(fh) != 0) die("signalMachine: cannot write %s", R->snp_ref_out);
+}
+
+/* --snp-marginals / --snp-proposals at the end of the run: finish on the device, the table, the thinned proposals per contig */
+static void write_snp_marginals(run_t *R) {
+    if (!R->snp_tab) return;
+    sa_snp_marginal_t *m = NULL;
+    int64_t n = 0;
+    if (sa_snp_marginals_finish(R->snp_tab, 1, (const char *const *) R->snp_seqs, &m, &n, NULL) != SA_OK)
+        die("signalMachine: --snp-marginals: the final step failed%s", "");
+    if (sa_snp_write_marginals(R->snp_marg, (const char *const *) R->snp_names, m, n) != SA_OK) die("signalMachine: cannot write %s", R->snp_marg);
+    if (R->snp_prop) {
+        FILE *fh = fopen(R->snp_prop, "w");
+        if (!fh) die("signalMachine: cannot write %s", R->snp_prop);
+        int64_t *pos = xalloc(n, sizeof(int64_t), 0), *keep = xalloc(n, sizeof(int64_t), 0);
+        double *delta = xalloc(n, sizeof(double), 0);
+        for (int64_t a = 0; a < n;) {   /* the sites come in (contig, position) order: one contig after the other */
+            int64_t e = a, np = 0, nk = 0;
+            for (; e < n && m[e].contig == m[a].contig; e++)
+                if (m[e].is_proposal) { pos[np] = m[e].pos; delta[np] = m[e].delta; np++; }
+            if (sa_snp_group_sites(pos, delta, np, 6, 1, keep, &nk) != SA_OK) die("signalMachine: --snp-proposals failed%s", "");
+            for (int64_t i = 0, j = 0; i < nk; i++) {   /* keep[] ascends, and so does pos[] */
+                while (pos[j] != keep[i]) j++;
+                char num[40];
+                sa_format_py_repr(num, delta[j]);
+                fprintf(fh, "%s\t%" PRId64 "\t%s\n", R->snp_names[m[a].contig], keep[i], num);
+            }
+            a = e;
+        }
+        free(pos); free(keep); free(delta);
+        if (fclose(fh) != 0) die("signalMachine: cannot write %s", R->snp_prop);
+    }
+    if (R->snp_ref_out) write_snp_reference(R, m, n);
+    sa_free(m);
+    sa_snp_marginals_destroy(R->snp_tab);
+    R->snp_tab = NULL;
 }
 
 int main(int argc, char **argv) {
@@ -2126,6 +2289,10 @@ int main(int argc, char **argv) {
                                            {"train-mixture-distances", required_argument, 0, 1043},
                                            {"snp-step", required_argument, 0, 1020},
                                            {"snp-dir", required_argument, 0, 1021},
+                                           {"snp-marginals", required_argument, 0, 1022},
+                                           {"snp-proposals", required_argument, 0, 1023},
+                                           {"snp-sites", required_argument, 0, 1024},
+                                           {"snp-reference-out", required_argument, 0, 1025},
                                            {"guide-window", required_argument, 0, 1050},
                                            {"guide-locate", no_argument, 0, 1053},
                                            {"guide-band", required_argument, 0, 1051},
@@ -2184,6 +2351,10 @@ int main(int argc, char **argv) {
                 if (sscanf(optarg, "%" SCNd64, &R.snp_step) != 1) R.snp_step = 0;
                 break;
             case 1021: R.snp_dir = strdup(optarg); break;
+            case 1022: R.snp_marg = strdup(optarg); break;
+            case 1023: R.snp_prop = strdup(optarg); break;
+            case 1024: R.snp_sites_path = strdup(optarg); break;
+            case 1025: R.snp_ref_out = strdup(optarg); break;
             case 1050: guide_window = strdup(optarg); break;
             case 1051: R.guide_band = atoi(optarg); break;
             case 1053: guide_locate = 1; break;
@@ -2272,16 +2443,25 @@ int main(int argc, char **argv) {
         if (R.train_n < 1 || !(R.train_min_prob >= 0 && R.train_min_prob <= 1)) die("signalMachine: bad --train-max-assignments / --train-min-prob%s", "");
     }
     if (R.expect_mode && (R.site_calls || R.agg_path)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate need the alignment mode, not -t/-c%s", ""); }
-    if (snp_set || R.snp_dir) {   /* --snp-step: its own outputs only */
-        if (!snp_set || R.snp_step < 1) { usage(); die("signalMachine: --snp-step takes a step N >= 1%s", ""); }
-        if (!R.snp_dir) { usage(); die("signalMachine: --snp-step needs --snp-dir <directory>%s", ""); }
-        if (R.expect_mode) { usage(); die("signalMachine: --snp-step cannot be combined with -t/-c%s", ""); }
-        if (R.mea) { usage(); die("signalMachine: --snp-step cannot be combined with --mea%s", ""); }
-        if (R.site_calls || R.agg_path) { usage(); die("signalMachine: --snp-step cannot be combined with --site-calls / --site-calls-aggregate%s", ""); }
-        if (R.want_train) { usage(); die("signalMachine: --snp-step cannot be combined with --train-*%s", ""); }
+    if (R.snp_prop && !R.snp_marg) { usage(); die("signalMachine: --snp-proposals needs --snp-marginals <file>%s", ""); }
+    if (R.snp_sites_path && snp_set) { usage(); die("signalMachine: --snp-sites cannot be combined with --snp-step%s", ""); }
+    if (R.snp_ref_out && !R.snp_sites_path) { usage(); die("signalMachine: --snp-reference-out needs --snp-sites <file>%s", ""); }
+    if (R.snp_sites_path && !R.snp_marg) { usage(); die("signalMachine: --snp-sites needs --snp-marginals <file>%s", ""); }
+    if (R.snp_sites_path && R.snp_dir) { usage(); die("signalMachine: --snp-sites writes no per-read files: --snp-dir not allowed%s", ""); }
+    if (R.snp_marg && !snp_set && !R.snp_sites_path) { usage(); die("signalMachine: --snp-marginals needs --snp-step <N> or --snp-sites <file>%s", ""); }
+    if (snp_set || R.snp_dir || R.snp_sites_path) {   /* --snp-step / --snp-sites: their own outputs only */
+        const char *opt = R.snp_sites_path ? "--snp-sites" : "--snp-step";
+        if (!R.snp_sites_path && (!snp_set || R.snp_step < 1)) { usage(); die("signalMachine: --snp-step takes a step N >= 1%s", ""); }
+        if (!R.snp_dir && !R.snp_marg) { usage(); die("signalMachine: --snp-step needs --snp-dir <directory>%s", ""); }
+        if (R.snp_marg && R.two_d) { usage(); die("signalMachine: --snp-marginals does not take --twoD runs%s", ""); }
+        if (R.expect_mode) { usage(); die("signalMachine: %s cannot be combined with -t/-c", opt); }
+        if (R.mea) { usage(); die("signalMachine: %s cannot be combined with --mea", opt); }
+        if (R.site_calls || R.agg_path) { usage(); die("signalMachine: %s cannot be combined with --site-calls / --site-calls-aggregate", opt); }
+        if (R.want_train) { usage(); die("signalMachine: %s cannot be combined with --train-*", opt); }
         for (int64_t i = 0; i < n_reads; i++)
             if (reads[i].post_path || reads[i].post_path2) {
                 usage();
+                if (R.snp_sites_path) die("signalMachine: --snp-sites writes no posteriors file: no -u / -i, a manifest's posteriors column '-'%s", "");
                 die(R.batch_mode ? "signalMachine: --snp-step writes no posteriors file: the manifest's posteriors column of %s must be '-'"
                                  : "signalMachine: --snp-step writes no posteriors file: -u / -i not allowed%s", R.batch_mode ? reads[i].label : "");
             }
@@ -2342,9 +2522,17 @@ int main(int argc, char **argv) {
     if (R.snp_step > 0) {   /* a slice holds at most --batch-reads jobs: N per read and strand */
         batch_reads /= R.snp_step;
         if (batch_reads < 1) batch_reads = 1;
-        if (mkdir(R.snp_dir, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.snp_dir);
+        if (R.snp_dir && mkdir(R.snp_dir, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.snp_dir);
     }
-    int64_t (*const run_slice)(run_t *, read_t *, int64_t, int) = R.expect_mode ? run_slice_expect : R.snp_step > 0 ? run_slice_snp : run_slice_align;
+    if (R.snp_marg) {   /* the table lies over every record of the -f reference */
+        if (sa_fasta_read_all(R.fwd_ref, &R.snp_names, &R.snp_seqs, &R.snp_lens, &R.snp_n_contigs) != SA_OK)
+            die("signalMachine: --snp-marginals: cannot read %s", R.fwd_ref);
+        const int rc = sa_snp_marginals_create(&R.snp_tab, R.snp_lens, R.snp_n_contigs, R.snp_step, device);
+        if (rc != SA_OK) die("signalMachine: --snp-marginals: %s", sa_strerror(rc));
+        R.reads0 = reads;
+        if (R.snp_sites_path) load_snp_sites(&R);
+    }
+    int64_t (*const run_slice)(run_t *, read_t *, int64_t, int) = R.expect_mode ? run_slice_expect : (R.snp_step > 0 || R.snp_sites_path) ? run_slice_snp : run_slice_align;
     slice_t cur = {.R = &R, .reads = reads, .n_reads = n_reads < batch_reads ? n_reads : batch_reads}, nxt;
     slice_prepare(&cur);
     for (int64_t off = 0; off < n_reads; off += batch_reads) {
@@ -2362,6 +2550,7 @@ int main(int argc, char **argv) {
     }
     if (R.agg_path) write_aggregate(R.agg_path);
     write_training(&R, t_model, c_model, device);
+    write_snp_marginals(&R);
     if (R.batch_mode)
         fprintf(stderr, "[signalMachine] batch: %" PRId64 " of %" PRId64 " reads aligned\n", n_reads - n_failed, n_reads);
     if (getenv("SA_CLI_TIMING"))
