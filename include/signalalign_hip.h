@@ -716,6 +716,75 @@ int sa_snp_apply_calls(const char *ref, int64_t len, const sa_snp_marginal_t *ma
 /* one line per site, "contig\tsite\tdepth\tpA\tpC\tpG\tpT\tcalled\tref\tdelta\n", the doubles as Python's str(float) */
 int sa_snp_write_marginals(const char *path, const char *const *contig_names, const sa_snp_marginal_t *marginals, int64_t n);
 
+/* ---- Per-position profile of all reads' posteriors -----------------------------------------------------------------------------
+ * Replaces src/signalalign/scripts/multipleAlignmentAnalysis.py (:52-69 is_forward_alignment, :118-242 main) over the full TSV of
+ * every read: an accumulator holds, per contig position, integer sums in HBM across batches, as sa_snp_marginals_t holds its sums.
+ *   a record         (x, kmer_id, prob_e7) of job j names k-mer index x of the job's ref.  For i in [0, k) it contributes to index
+ *                    p = x + i, which lies at contig position pos0 + pos_sign * p (:163-170); the letter is digit i of kmer_id,
+ *                    first letter most significant, complemented when pos_sign == -1 (A <-> T, C <-> G, every other letter itself)
+ *   a contribution   kmer_count += 1; units[letter] += the printed posterior in 1e-6 ("%f" of prob_e7 / 1e7);
+ *                    entropy_units += sa_profile_entropy_term(units): shannon_entropy's summand (:99-104)
+ *                    llrint((q log2 q + (1 - q) log2 (1 - q)) 2^40), q = units / 1e6, 0 at q = 0 and q = 1
+ *   spans            a job with records covers every contig position from the smallest to the largest its records touch;
+ *                    read_count is the number of such jobs (aligned_file_count, :194-201, one file being one 1-D job).  A covered
+ *                    position that no record touches is reported with kmer_count 0, ref 0 and zeros (:198-200)
+ *   finish           every position with read_count > 0 or kmer_count > 0 in (contig, position) order; prob[l] = units[l] / sum of
+ *                    units (0 when the sum is 0: the script divides by zero there); entropy = ((double) entropy_units 2^-40 /
+ *                    kmer_count) / -2.0, +0.0 when entropy_units == 0; ref the upper-cased reference letter where kmer_count > 0
+ *                    ('N' with ref_by_contig NULL); *letters_seen_out has bit l set when a contribution named letter l of the
+ *                    model's alphabet (all_characters).  The accumulator is left as it is.
+ * Every add is an integer atomic, so the table holds the same bits whatever the order, in one call or in many.
+ * Three deliberate differences from the script: the sums are integers, not floats in np.mean's pairwise order; orientation comes
+ * from the map (the script guesses it from the first rows, which breaks on 2-D files and on a leading palindrome); ref comes from
+ * the reference (the script takes it from the first row that names the position).  Contigs come in index order (the script sorts
+ * their names), and 1 - q of the entropy term is taken as (1e6 - units) / 1e6, which makes the term symmetric to the bit.
+ * Storage is 8 * (2 + letters of the alphabet) + 4 bytes per contig position (52 for ACGT), with one position more per contig, and
+ * as much again from the first checkpoint on: SA_ENOMEM when it does not fit, SA_ENODEVICE without a GPU.  An alphabet of more than
+ * SA_SITE_MAX_LETTERS letters, or with one of A, C, G, T but not its complement: SA_EUNSUPPORTED at create.
+ * All checks run before anything is added, and a refused call adds nothing: a bad contig index, a pos_sign that is not +-1, a mapped
+ * position outside its contig: SA_EINVAL.  A device failure after the first accumulating kernel leaves the table unusable: every
+ * later call on it but destroy returns SA_ESTATE. */
+typedef struct sa_position_profile sa_position_profile_t;
+typedef struct sa_profile_job_map {   /* job j of a batch or of sa_position_profile_add_records */
+    int32_t contig, pos_sign;         /* index p of the job's ref lies at contig position pos0 + pos_sign * p (pos_sign +1 or -1) */
+    int64_t pos0;
+} sa_profile_job_map_t;               /* 16 bytes */
+typedef struct sa_profile_site {
+    int64_t pos;
+    int32_t contig, read_count;            /* reads (jobs) whose span covers pos                                        */
+    int64_t kmer_count;                    /* (record, letter) contributions                                            */
+    int64_t entropy_units;                 /* sum of the rows' terms, units of 2^-40                                    */
+    int64_t units[SA_SITE_MAX_LETTERS];    /* printed posterior per letter of the model's alphabet, 1e-6                */
+    double entropy, prob[SA_SITE_MAX_LETTERS];
+    char ref, pad[7];                      /* 0: no row names this position                                             */
+} sa_profile_site_t;                       /* 176 bytes */
+#define SA_PROFILE_DIRECT 1u               /* every contribution is a global atomic: no LDS window (the fallback path, and the A/B) */
+int sa_position_profile_create(sa_position_profile_t **out, const sa_model_t *m, const int64_t *contig_lens, int64_t n_contigs, int device);
+void sa_position_profile_destroy(sa_position_profile_t *t);
+/* chained onto a finished batch: its records are read where the run left them in HBM (after sa_batch_release_device, and with
+ * SA_FLAG_EXACT, they go up again); map[j] places job j.  Not run: SA_ESTATE; a SA_FLAG_PAIRS8 batch (no k-mer in the record):
+ * SA_EUNSUPPORTED; a SA_FLAG_VC_ROWS batch (rows dropped), another device, n_jobs that is not the batch's, a model whose k or
+ * alphabet size differs from the table's: SA_EINVAL.  kernel_ms_out (may be NULL): HIP-event time of the call's kernels. */
+int sa_position_profile_add_batch(sa_position_profile_t *t, sa_batch_t *b, const sa_profile_job_map_t *map, int64_t n_jobs, unsigned flags,
+                                  double *kernel_ms_out);
+/* records from elsewhere: job j's are first[j] .. first[j + 1) (first[0] == 0).  A kmer_id outside the model, a prob_e7 outside
+ * [0, 1e7], an x outside [0, 2^28): SA_EINVAL, nothing added. */
+int sa_position_profile_add_records(sa_position_profile_t *t, const sa_profile_job_map_t *map, int64_t n_jobs, const int64_t *first /* n_jobs + 1 */,
+                                    const int32_t *x, const int32_t *kmer_id, const int64_t *prob_e7, unsigned flags, double *kernel_ms_out);
+/* the contract of sa_kmer_table_checkpoint / _rollback (the table is copied); rollback without a checkpoint: SA_ESTATE */
+int sa_position_profile_checkpoint(sa_position_profile_t *t);
+int sa_position_profile_rollback(sa_position_profile_t *t);
+/* the spans' difference array scanned, the sites made and compacted on the device (*sites_out malloc'd, sa_free).  ref_by_contig
+ * (may be NULL): one sequence per contig, of at least the contig's length. */
+int sa_position_profile_finish(sa_position_profile_t *t, const char *const *ref_by_contig, sa_profile_site_t **sites_out, int64_t *n_out,
+                               uint32_t *letters_seen_out, double *kernel_ms_out);
+/* the script's file (:203-242): the header "#contig\tposition\tref_char\tshannon_entropy\tkmer_aln_count\tread_aln_count" and
+ * "\tp<letter>" for every seen letter in sorted order, then one line per site, the doubles as Python's str(float), ref_char empty
+ * when 0.  Host only.  The script's histogram on stderr (qualify_entropies) is not reproduced. */
+int sa_position_profile_write(const char *path, const char *alphabet, uint32_t letters_seen, const char *const *contig_names,
+                              const sa_profile_site_t *sites, int64_t n);
+int64_t sa_profile_entropy_term(int64_t units);   /* test hook, host */
+
 /* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
  * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
  * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output

@@ -73,6 +73,15 @@ class SnpJobMap(C.Structure):
                 ("strand", C.c_int32), ("direction", C.c_int32), ("pad", C.c_int32), ("run", C.c_int64), ("group", C.c_int64)]
 
 
+class ProfileJobMap(C.Structure):
+    """sa_profile_job_map_t (include/signalalign_hip.h)"""
+    _fields_ = [("contig", C.c_int32), ("pos_sign", C.c_int32), ("pos0", C.c_int64)]
+
+
+PROFILE_DIRECT = 1
+PROFILE_SITE_DTYPE = np.dtype([("pos", "<i8"), ("contig", "<i4"), ("read_count", "<i4"), ("kmer_count", "<i8"), ("entropy_units", "<i8"),
+                               ("units", "<i8", (SITE_MAX_LETTERS,)), ("entropy", "<f8"), ("prob", "<f8", (SITE_MAX_LETTERS,)),
+                               ("ref", "S1"), ("pad", "S1", (7,))])
 SNP_SITE_DTYPE = np.dtype([("pos", "<i8"), ("strand", "<i4"), ("pad", "<i4"), ("p", "<f8", (4,))])
 SNP_MARGINAL_DTYPE = np.dtype([("pos", "<i8"), ("contig", "<i4"), ("depth", "<i4"), ("fwd", "<f8", (4,)), ("bwd", "<f8", (4,)),
                                ("prob", "<f8", (4,)), ("delta", "<f8"), ("called", "S1"), ("ref", "S1"), ("is_proposal", "i1"),
@@ -184,7 +193,10 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read",
            "sa_snp_marginals_create", "sa_snp_marginals_destroy", "sa_snp_marginals_add_sites", "sa_snp_marginals_add_batch",
            "sa_snp_marginals_checkpoint", "sa_snp_marginals_rollback", "sa_snp_marginals_finish", "sa_snp_group_sites",
-           "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
+           "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals",
+           "sa_position_profile_create", "sa_position_profile_destroy", "sa_position_profile_add_batch", "sa_position_profile_add_records",
+           "sa_position_profile_checkpoint", "sa_position_profile_rollback", "sa_position_profile_finish", "sa_position_profile_write",
+           "sa_profile_entropy_term", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet", "sa_hdp_state_vs_gaussian",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
@@ -374,6 +386,18 @@ def lib():
     L.sa_snp_marginals_checkpoint.argtypes = [C.c_void_p]
     L.sa_snp_marginals_rollback.argtypes = [C.c_void_p]
     L.sa_snp_marginals_finish.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), ip, dp]
+    L.sa_position_profile_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, ip, C.c_int64, C.c_int]
+    L.sa_position_profile_destroy.argtypes = [C.c_void_p]
+    L.sa_position_profile_destroy.restype = None
+    L.sa_position_profile_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProfileJobMap), C.c_int64, C.c_uint, dp]
+    L.sa_position_profile_add_records.argtypes = [C.c_void_p, C.POINTER(ProfileJobMap), C.c_int64, ip, C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_int32), ip, C.c_uint, dp]
+    L.sa_position_profile_checkpoint.argtypes = [C.c_void_p]
+    L.sa_position_profile_rollback.argtypes = [C.c_void_p]
+    L.sa_position_profile_finish.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), ip, C.POINTER(C.c_uint32), dp]
+    L.sa_position_profile_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int64]
+    L.sa_profile_entropy_term.argtypes = [C.c_int64]
+    L.sa_profile_entropy_term.restype = C.c_int64
     L.sa_snp_group_sites.argtypes = [ip, dp, C.c_int64, C.c_int64, C.c_int, ip, ip]
     L.sa_snp_substitute_sites.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, ip, C.c_int64, C.c_char, C.c_char_p]
     L.sa_snp_apply_calls.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_char_p]
@@ -1965,6 +1989,101 @@ class SnpMarginals:
             self.close()
         except Exception:
             pass
+
+
+class PositionProfile:
+    """sa_position_profile_t: per contig position the pile-up of all reads' posteriors (multipleAlignmentAnalysis.py) as integer
+    sums, kept in HBM across add_batch / add_records calls."""
+
+    def __init__(self, model, contig_lens, device=0):
+        self._h = C.c_void_p()
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        self.n_contigs = len(lens)
+        self.contig_lens = [int(v) for v in lens]
+        self.alphabet = model.alphabet()[0]
+        _chk(lib().sa_position_profile_create(C.byref(self._h), model._h, _ip(lens), len(lens), int(device)), "sa_position_profile_create")
+
+    @staticmethod
+    def _map(job_map):
+        job_map = list(job_map)
+        arr = (ProfileJobMap * max(len(job_map), 1))()
+        for i, m in enumerate(job_map):
+            arr[i].contig, arr[i].pos_sign, arr[i].pos0 = int(m["contig"]), int(m["pos_sign"]), int(m["pos0"])
+        return arr, len(job_map)
+
+    def add_batch(self, batch, job_map, flags=0, stats=None):
+        """chained onto a finished Batch; job_map: per job a dict with contig, pos0, pos_sign (sa_profile_job_map_t)"""
+        arr, n = self._map(job_map)
+        kms = C.c_double()
+        _chk(lib().sa_position_profile_add_batch(self._h, batch._h, arr, n, int(flags), C.byref(kms)), "sa_position_profile_add_batch")
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+
+    def add_records(self, job_map, first, x, kmer_id, prob_e7, flags=0, stats=None):
+        """records from elsewhere: job j's are first[j] .. first[j + 1) of x, kmer_id, prob_e7"""
+        arr, n = self._map(job_map)
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        kmer_id = np.ascontiguousarray(kmer_id, dtype=np.int32)
+        prob_e7 = np.ascontiguousarray(prob_e7, dtype=np.int64)
+        if len(first) != n + 1 or not (len(x) == len(kmer_id) == len(prob_e7)) or int(first[-1]) != len(x):
+            raise ValueError("first: n_jobs + 1 offsets into x, kmer_id and prob_e7, which have one entry per record")
+        kms = C.c_double()
+        _chk(lib().sa_position_profile_add_records(self._h, arr, n, _ip(first), _i32p(x), _i32p(kmer_id), _ip(prob_e7), int(flags),
+                                                   C.byref(kms)), "sa_position_profile_add_records")
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+
+    def checkpoint(self):
+        _chk(lib().sa_position_profile_checkpoint(self._h), "sa_position_profile_checkpoint")
+
+    def rollback(self):
+        _chk(lib().sa_position_profile_rollback(self._h), "sa_position_profile_rollback")
+
+    def finish(self, ref_by_contig=None, stats=None):
+        """(structured array of PROFILE_SITE_DTYPE in (contig, position) order, letters_seen bit mask)"""
+        refs = None
+        if ref_by_contig is not None:
+            keep = [r.encode() if isinstance(r, str) else bytes(r) for r in ref_by_contig]
+            if len(keep) != self.n_contigs or any(len(r) < n for r, n in zip(keep, self.contig_lens)):
+                raise ValueError("ref_by_contig: one sequence per contig, each at least as long as its contig")
+            refs = (C.c_char_p * len(keep))(*keep)
+        ptr = C.c_void_p()
+        n = np.zeros(1, dtype=np.int64)
+        seen = C.c_uint32()
+        kms = C.c_double()
+        _chk(lib().sa_position_profile_finish(self._h, refs, C.byref(ptr), _ip(n), C.byref(seen), C.byref(kms)), "sa_position_profile_finish")
+        out = np.zeros(int(n[0]), dtype=PROFILE_SITE_DTYPE)
+        if n[0]:
+            C.memmove(out.ctypes.data, ptr, out.nbytes)
+        lib().sa_free(ptr)
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+        return out, int(seen.value)
+
+    def close(self):
+        if self._h:
+            lib().sa_position_profile_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def position_profile_write(path, alphabet, letters_seen, contig_names, sites):
+    """sa_position_profile_write: the file of multipleAlignmentAnalysis.py"""
+    m = np.ascontiguousarray(sites, dtype=PROFILE_SITE_DTYPE)
+    keep = [c.encode() for c in contig_names]
+    names = (C.c_char_p * max(len(keep), 1))(*keep)
+    _chk(lib().sa_position_profile_write(os.fsencode(path), alphabet.encode(), int(letters_seen), names, m.ctypes.data, len(m)),
+         "sa_position_profile_write")
+
+
+def profile_entropy_term(units):
+    return int(lib().sa_profile_entropy_term(int(units)))
 
 
 def snp_group_sites(pos, delta, window=6, keep_last=True):

@@ -661,7 +661,7 @@ static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_par
 
     sa_batch *b = new sa_batch();
     std::unique_ptr<sa_batch, void (*)(sa_batch *)> owner(b, sa_batch_destroy);   // a failure below destroys the batch
-    b->c_m = m; b->c_p = *p; b->c_jobs = jobs; b->c_n = n_jobs; b->c_ambig = ambig; b->c_budget = budget; b->c_t0 = tc0;
+    b->c_m = m; b->c_k = m->k; b->c_n_alpha = m->n_alpha; b->c_p = *p; b->c_jobs = jobs; b->c_n = n_jobs; b->c_ambig = ambig; b->c_budget = budget; b->c_t0 = tc0;
     if (noise_scaled) b->c_noise.assign(noise, noise + n_jobs);
     b->device = device;
     b->flags = flags;

@@ -16,10 +16,11 @@ struct SaBatchView {
     bool p8 = false;
     unsigned batch_flags = 0;   // the batch's creation flags (SA_FLAG_EXPECT_INTERNAL among them)
     int device = 0;
+    int k = 0, n_alpha = 0;     // of the model the batch was created with: what a record's kmer_id is made of
     std::vector<long long> first, count, n_events;
 };
-// sa_hip.hip: SA_ESTATE for a batch that has not run (p8, batch_flags and device are filled even then).  Which batches a stage
-// accepts is the stage's own rule.
+// sa_hip.hip: SA_ESTATE for a batch that has not run (p8, batch_flags, device and the model's k and n_alpha are filled even
+// then).  Which batches a stage accepts is the stage's own rule.
 int sa_batch_view(sa_batch_t *b, SaBatchView *v);
 
 // The table of a batch's ambiguity letters (sa_calls.hip), built at sa_batch_create.  Index i of job j names the letter

@@ -434,6 +434,7 @@ struct sa_batch {
     // planner takes over -- which is why a deferred batch asks the caller to keep them until its first run has returned.
     struct DPlanPending *pending = nullptr;
     const sa_model_t *c_m = nullptr;
+    int c_k = 0, c_n_alpha = 0;   // c_m's k-mer length and alphabet size (kept: a chained stage asks after the model may be gone)
     sa_params_t c_p{};
     const sa_job_t *c_jobs = nullptr;
     int64_t c_n = 0;
@@ -1006,6 +1007,8 @@ int sa_batch_view(sa_batch_t *b, SaBatchView *v) {
     v->p8 = b->p8;
     v->batch_flags = b->flags;
     v->device = b->device;
+    v->k = b->c_k;
+    v->n_alpha = b->c_n_alpha;
     if (!b->ran) return SA_ESTATE;
     const sa_plan_t *pl = b->plan;
     const size_t nj = (size_t) pl->n_jobs;

@@ -219,6 +219,14 @@ int sa_ring_wide_env_on(void);                   /* SA_RING_WIDE=0: one-path reg
 int sa_job_header_ok(const sa_job_t *jb);        /* pointers, counts, var and ends of a job (not its anchors) */
 int sa_params_plannable(const sa_params_t *p);   /* the asserts of impl/pairwiseAligner.c:1460-1464, :1358-1359; threshold in [0, 1] */
 
+/* sa_profile.c: what sa_profile.hip checks on the host before it adds anything (SA_EINVAL, or SA_OK) */
+#define SA_PROFILE_UNITS_1 1000000   /* a printed posterior of 1.000000 */
+int sa_profile_check_map(const sa_profile_job_map_t *map, int64_t n_jobs, int64_t n_contigs);   /* contig index and sign of every job */
+int sa_profile_check_records(int64_t n_jobs, const int64_t *first, const int32_t *x, const int32_t *kmer_id, const int64_t *prob_e7,
+                             int64_t n_kmers);
+/* the contig positions lo <= hi that a job's records x_min .. x_max (k letters each) touch; an end outside the contig: SA_EINVAL */
+int sa_profile_span(const sa_profile_job_map_t *m, int64_t contig_len, int64_t x_min, int64_t x_max, int k, int64_t *lo, int64_t *hi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,11 @@ static void usage(void) {
                     "                  is aligned once, with X at the listed sites inside its window, and the same table comes out\n"
                     "--snp-reference-out <fasta> (with --snp-sites): the -f reference with the called base written in at every site\n"
                     "                  whose call differs from it, records and line width as in -f\n");
+    fprintf(stderr, "--position-profile <file> (with --batch): the pile-up of all reads' template alignments per position of the -f\n"
+                    "                  reference, summed on the GPU and written at the end of the run: contig, position, reference letter,\n"
+                    "                  entropy of the covering posteriors, k-mer rows and reads covering it, and the share of posterior\n"
+                    "                  mass on each letter seen (multipleAlignmentAnalysis.py); a manifest's posteriors column may be '-'.\n"
+                    "                  1-D DNA runs with -s 0 / 2 / 3 only: not with --twoD, --rna, -s 1, --snp-step or --snp-sites\n");
     fprintf(stderr, "--train-assignments <file>: write the top-N assignments table of the run (buildAlignment: kmer, strand, descaled\n"
                     "                  mean, posterior; what buildHdpUtil -l reads), selected on the GPU\n"
                     "--train-template-model <file> / --train-complement-model <file>: write the -T / -C model with its Gaussian event\n"
@@ -414,8 +419,10 @@ typedef struct {
     const char *snp_sites_path, *snp_ref_out;
     int64_t **snp_sites, *snp_n_sites;
     sa_snp_marginals_t *snp_tab;
-    char **snp_names, **snp_seqs;
+    char **snp_names, **snp_seqs;   /* (the records of -f: --position-profile lays its table over them too) */
     int64_t *snp_lens, snp_n_contigs;
+    const char *prof_path;          /* --position-profile: the per-position profile of the run's template batches, on the GPU */
+    sa_position_profile_t *prof_tab;
     const void *reads0;
     const char *fwd_ref, *bwd_ref;
     sa_params_t p;
@@ -1752,6 +1759,27 @@ static int64_t run_slice_expect(run_t *R, read_t *reads, int64_t n_reads, int de
     return slice_close(&sl);
 }
 
+static int snp_contig_pos_is_forward(const read_t *rd, int s);
+static int64_t snp_contig_index(const run_t *R, const read_t *rd);
+
+/* --position-profile: the slice's finished template batch added to the run's table.  Job j is read j's template strand, and where
+ * its target lies on the contig is snp_contig_pos written as an affine map, as snp_add_to_marginals does */
+static int profile_add_batch(const align_slice_t *c, sa_batch_t *b) {
+    const run_t *R = c->sl.R;
+    const int64_t nj = c->sl.n_ok;
+    sa_profile_job_map_t *map = xalloc(nj, sizeof(*map), 1);
+    for (int64_t j = 0; j < nj; j++) {
+        const read_t *rd = &c->sl.reads[c->sl.who[j]];
+        const int same = snp_contig_pos_is_forward(rd, 0);
+        map[j].contig = (int32_t) snp_contig_index(R, rd);
+        map[j].pos_sign = same ? 1 : -1;
+        map[j].pos0 = same ? rd->st[0].r_shift : rd->st[0].r_shift - 1;
+    }
+    const int rc = sa_position_profile_add_batch(R->prof_tab, b, map, nj, 0, NULL);
+    free(map);
+    return rc;
+}
+
 /* Creates, runs and harvests the batch of strand s of an alignment slice into c->sr[s]; whatever it returns, the result is one
  * strand_result_free can take.
  * -s 1 prints only the rows whose reference k-mer holds an X: the others stay on the device (SA_FLAG_VC_ROWS), the run's pair
@@ -1773,7 +1801,7 @@ static int run_strand_batch(align_slice_t *c, int s) {
     unsigned flags = want_calls ? SA_FLAG_SITE_CALLS : 0u, p8 = 0u;
     if (!R->mea && !want_calls) {
         if (R->out_fmt == 1 && !R->want_train && !getenv("SA_CLI_VC_ON_HOST")) flags |= SA_FLAG_VC_ROWS;
-        if ((R->out_fmt == 0 || R->out_fmt == 2) && !getenv("SA_CLI_PAIRS16")) p8 = SA_FLAG_PAIRS8;
+        if ((R->out_fmt == 0 || R->out_fmt == 2) && !getenv("SA_CLI_PAIRS16") && !R->prof_tab) p8 = SA_FLAG_PAIRS8;   /* (the profile reads path k-mers) */
     }
     for (int64_t j = 0; j < n; j++) c->bj[j] = sl->reads[sl->who[j]].jobs[s];
     sr->pairs = xalloc(n, sizeof(sa_pair_t *), 1);
@@ -1795,6 +1823,10 @@ static int run_strand_batch(align_slice_t *c, int s) {
     if (rc == SA_OK && R->want_train) {   /* (a batch that ran: nothing a retry without some reads would change) */
         rc = sa_kmer_table_add_batch(R->train_tab[s], b, c->bj, n, s, NULL);
         if (rc != SA_OK) die("signalMachine: --train-*: %s", sa_strerror(rc));
+    }
+    if (rc == SA_OK && R->prof_tab && s == 0) {
+        rc = profile_add_batch(c, b);
+        if (rc != SA_OK) die("signalMachine: --position-profile: %s", sa_strerror(rc));
     }
     if (R->mea) {
         for (int64_t j = 0; j < n && rc == SA_OK; j++) {
@@ -1863,6 +1895,8 @@ static int64_t run_slice_align(run_t *R, read_t *reads, int64_t n_reads, int dev
         if (rc == SA_OK) rc = sa_kmer_table_checkpoint(R->train_tab[s]);
         if (rc != SA_OK) die("signalMachine: --train-*: %s", sa_strerror(rc));
     }
+    /* --position-profile: the same for its table */
+    if (R->prof_tab && sa_position_profile_checkpoint(R->prof_tab) != SA_OK) die("signalMachine: --position-profile: checkpoint failed%s", "");
     for (int s = 0; s < n_strands(R) && sl->n_ok > 0; s++) {
         fprintf(stderr, "signalAlign - starting %s alignment\n", strand_name(s));
         const int64_t n_jobs = sl->n_ok;
@@ -1870,6 +1904,7 @@ static int64_t run_slice_align(run_t *R, read_t *reads, int64_t n_reads, int dev
         if (drop_refused_reads(sl, rc, NULL, 1, NULL)) {
             for (int q = 0; q < n_strands(R) && R->want_train; q++)
                 if (sa_kmer_table_rollback(R->train_tab[q]) != SA_OK) die("signalMachine: --train-*: rollback failed%s", "");
+            if (R->prof_tab && sa_position_profile_rollback(R->prof_tab) != SA_OK) die("signalMachine: --position-profile: rollback failed%s", "");
             for (int q = 0; q <= s; q++) strand_result_free(&c.sr[q], n_jobs);
             s = -1;   /* both strands again, without the offenders */
             continue;
@@ -1911,18 +1946,18 @@ typedef struct {
 } snp_slice_t;
 
 /* contig coordinate of index t of a strand's target (the TSV's reference_index of a k-mer at t covers t .. t + k - 1) */
+static int snp_contig_pos_is_forward(const read_t *rd, int s) { return (s == 0 && rd->forward) || (s == 1 && !rd->forward); }
 static int64_t snp_contig_pos(const read_t *rd, int s, int64_t t) {
     const int64_t off = rd->st[s].r_shift;
-    const int same = (s == 0 && rd->forward) || (s == 1 && !rd->forward);
-    return same ? off + t : off - 1 - t;
+    return snp_contig_pos_is_forward(rd, s) ? off + t : off - 1 - t;
 }
 
-/* --snp-marginals: which record of the -f reference a read lies on */
+/* --snp-marginals, --position-profile: which record of the -f reference a read lies on */
 static int64_t snp_contig_index(const run_t *R, const read_t *rd) {
     const char *name = rd->seq_name ? rd->seq_name : rd->pA->contig1;
     int64_t ci = 0;
     while (ci < R->snp_n_contigs && strcmp(R->snp_names[ci], name) != 0) ci++;
-    if (ci == R->snp_n_contigs) die("signalMachine: --snp-marginals: %s is no record of the -f reference", name);
+    if (ci == R->snp_n_contigs) die("signalMachine: %s is no record of the -f reference", name);
     return ci;
 }
 
@@ -2226,6 +2261,21 @@ static void write_snp_marginals(run_t *R) {
     R->snp_tab = NULL;
 }
 
+/* --position-profile at the end of the run: finish on the device, the script's file */
+static void write_position_profile(run_t *R) {
+    if (!R->prof_tab) return;
+    sa_profile_site_t *sites = NULL;
+    int64_t n = 0;
+    uint32_t seen = 0;
+    if (sa_position_profile_finish(R->prof_tab, (const char *const *) R->snp_seqs, &sites, &n, &seen, NULL) != SA_OK)
+        die("signalMachine: --position-profile: the final step failed%s", "");
+    if (sa_position_profile_write(R->prof_path, R->sm[0].alphabet, seen, (const char *const *) R->snp_names, sites, n) != SA_OK)
+        die("signalMachine: cannot write %s", R->prof_path);
+    sa_free(sites);
+    sa_position_profile_destroy(R->prof_tab);
+    R->prof_tab = NULL;
+}
+
 int main(int argc, char **argv) {
     run_t R;
     memset(&R, 0, sizeof(R));
@@ -2293,6 +2343,7 @@ int main(int argc, char **argv) {
                                            {"snp-proposals", required_argument, 0, 1023},
                                            {"snp-sites", required_argument, 0, 1024},
                                            {"snp-reference-out", required_argument, 0, 1025},
+                                           {"position-profile", required_argument, 0, 1026},
                                            {"guide-window", required_argument, 0, 1050},
                                            {"guide-locate", no_argument, 0, 1053},
                                            {"guide-band", required_argument, 0, 1051},
@@ -2355,6 +2406,7 @@ int main(int argc, char **argv) {
             case 1023: R.snp_prop = strdup(optarg); break;
             case 1024: R.snp_sites_path = strdup(optarg); break;
             case 1025: R.snp_ref_out = strdup(optarg); break;
+            case 1026: R.prof_path = strdup(optarg); break;
             case 1050: guide_window = strdup(optarg); break;
             case 1051: R.guide_band = atoi(optarg); break;
             case 1053: guide_locate = 1; break;
@@ -2368,6 +2420,7 @@ int main(int argc, char **argv) {
         }
     }
     if (!label) label = strdup("");
+    if (R.prof_path && manifest == NULL) { usage(); die("signalMachine: --position-profile needs --batch <manifest>%s", ""); }
     if (t_model == NULL || (c_model == NULL && R.two_d)) die("Missing model files, exiting", NULL);
     if (R.out_fmt == 3 && post_path2 == NULL && manifest == NULL) die("Must pass in posteriorProbsFile2 if using 'both' outFmt", NULL);
     if (cigar_path != NULL && guide_window != NULL) die("signalMachine: -p and --guide-window exclude each other%s", "");
@@ -2449,6 +2502,14 @@ int main(int argc, char **argv) {
     if (R.snp_sites_path && !R.snp_marg) { usage(); die("signalMachine: --snp-sites needs --snp-marginals <file>%s", ""); }
     if (R.snp_sites_path && R.snp_dir) { usage(); die("signalMachine: --snp-sites writes no per-read files: --snp-dir not allowed%s", ""); }
     if (R.snp_marg && !snp_set && !R.snp_sites_path) { usage(); die("signalMachine: --snp-marginals needs --snp-step <N> or --snp-sites <file>%s", ""); }
+    if (R.prof_path) {   /* --position-profile: 1-D DNA runs of a manifest that keep every row and every path k-mer */
+        if (R.two_d) { usage(); die("signalMachine: --position-profile does not take --twoD runs%s", ""); }
+        if (R.rna) { usage(); die("signalMachine: --position-profile does not take --rna runs%s", ""); }
+        if (R.out_fmt == 1) { usage(); die("signalMachine: --position-profile cannot be combined with -s 1 (it drops rows)%s", ""); }
+        if (snp_set || R.snp_sites_path) { usage(); die("signalMachine: --position-profile cannot be combined with --snp-step / --snp-sites%s", ""); }
+        if (R.expect_mode) { usage(); die("signalMachine: --position-profile needs the alignment mode, not -t/-c%s", ""); }
+        if (fwd_ref == NULL) { usage(); die("signalMachine: --position-profile needs -f <fasta>%s", ""); }
+    }
     if (snp_set || R.snp_dir || R.snp_sites_path) {   /* --snp-step / --snp-sites: their own outputs only */
         const char *opt = R.snp_sites_path ? "--snp-sites" : "--snp-step";
         if (!R.snp_sites_path && (!snp_set || R.snp_step < 1)) { usage(); die("signalMachine: --snp-step takes a step N >= 1%s", ""); }
@@ -2532,6 +2593,12 @@ int main(int argc, char **argv) {
         R.reads0 = reads;
         if (R.snp_sites_path) load_snp_sites(&R);
     }
+    if (R.prof_path) {   /* the table lies over every record of the -f reference */
+        if (sa_fasta_read_all(R.fwd_ref, &R.snp_names, &R.snp_seqs, &R.snp_lens, &R.snp_n_contigs) != SA_OK)
+            die("signalMachine: --position-profile: cannot read %s", R.fwd_ref);
+        const int rc = sa_position_profile_create(&R.prof_tab, R.sm[0].model, R.snp_lens, R.snp_n_contigs, device);
+        if (rc != SA_OK) die("signalMachine: --position-profile: %s", sa_strerror(rc));
+    }
     int64_t (*const run_slice)(run_t *, read_t *, int64_t, int) = R.expect_mode ? run_slice_expect : (R.snp_step > 0 || R.snp_sites_path) ? run_slice_snp : run_slice_align;
     slice_t cur = {.R = &R, .reads = reads, .n_reads = n_reads < batch_reads ? n_reads : batch_reads}, nxt;
     slice_prepare(&cur);
@@ -2551,6 +2618,7 @@ int main(int argc, char **argv) {
     if (R.agg_path) write_aggregate(R.agg_path);
     write_training(&R, t_model, c_model, device);
     write_snp_marginals(&R);
+    write_position_profile(&R);
     if (R.batch_mode)
         fprintf(stderr, "[signalMachine] batch: %" PRId64 " of %" PRId64 " reads aligned\n", n_reads - n_failed, n_reads);
     if (getenv("SA_CLI_TIMING"))
