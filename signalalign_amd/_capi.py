@@ -1917,16 +1917,71 @@ def snp_write_read(path, fast5_input, read_id, contig, backward, sites):
                                  arr, len(sites)), "sa_snp_write_read")
 
 
-class SnpMarginals:
-    """sa_snp_marginals_t: per contig position a forward and a backward sum of (pA, pC, pG, pT) over reads and a row count,
-    kept in HBM across add_sites / add_batch calls.  step >= 1: add_batch filters by call_methyls' window; 0: no window."""
+class _ContigAcc:
+    """What the tables kept in HBM over contig positions share: the lengths, checkpoint / rollback / close by the prefix of the
+    C functions' names (_PREFIX), and the two ends of finish."""
+    _PREFIX = None
 
-    def __init__(self, contig_lens, step=0, device=0):
+    def _create(self, contig_lens, create):
+        """create(handle by reference, lengths, their number) is the table's own sa_*_create call"""
         self._h = C.c_void_p()
         lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
         self.n_contigs = len(lens)
         self.contig_lens = [int(v) for v in lens]
-        _chk(lib().sa_snp_marginals_create(C.byref(self._h), _ip(lens), len(lens), int(step), int(device)), "sa_snp_marginals_create")
+        _chk(create(C.byref(self._h), _ip(lens), len(lens)), self._PREFIX + "create")
+
+    def _call(self, name):
+        _chk(getattr(lib(), self._PREFIX + name)(self._h), self._PREFIX + name)
+
+    def checkpoint(self):
+        self._call("checkpoint")
+
+    def rollback(self):
+        self._call("rollback")
+
+    def _refs(self, ref_by_contig):
+        """ref_by_contig as finish passes it on: NULL, or one C string per contig"""
+        if ref_by_contig is None:
+            return None
+        keep = [r.encode() if isinstance(r, str) else bytes(r) for r in ref_by_contig]
+        if len(keep) != self.n_contigs or any(len(r) < n for r, n in zip(keep, self.contig_lens)):
+            raise ValueError("ref_by_contig: one sequence per contig, each at least as long as its contig")
+        return (C.c_char_p * len(keep))(*keep)
+
+    def _finish(self, dtype, stats, call):
+        """call(sites by reference, their number, kernel_ms by reference) is the table's own sa_*_finish call; the sites are
+        copied out of the library's array, which is freed"""
+        ptr = C.c_void_p()
+        n = np.zeros(1, dtype=np.int64)
+        kms = C.c_double()
+        _chk(call(C.byref(ptr), _ip(n), C.byref(kms)), self._PREFIX + "finish")
+        out = np.zeros(int(n[0]), dtype=dtype)
+        if n[0]:
+            C.memmove(out.ctypes.data, ptr, out.nbytes)
+        lib().sa_free(ptr)
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+        return out
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._PREFIX + "destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SnpMarginals(_ContigAcc):
+    """sa_snp_marginals_t: per contig position a forward and a backward sum of (pA, pC, pG, pT) over reads and a row count,
+    kept in HBM across add_sites / add_batch calls.  step >= 1: add_batch filters by call_methyls' window; 0: no window."""
+    _PREFIX = "sa_snp_marginals_"
+
+    def __init__(self, contig_lens, step=0, device=0):
+        self._create(contig_lens, lambda h, lens, n: lib().sa_snp_marginals_create(h, lens, n, int(step), int(device)))
 
     def add_sites(self, contig, sites, direction, run=0):
         """rows of one read: `sites` a SNP_SITE_DTYPE array, or an iterable of (pos, strand 0/1, (pA, pC, pG, pT))"""
@@ -1953,55 +2008,21 @@ class SnpMarginals:
         if stats is not None:
             stats["kernel_ms_position_fold"], stats["kernel_ms"] = kms[0], kms[1]
 
-    def checkpoint(self):
-        _chk(lib().sa_snp_marginals_checkpoint(self._h), "sa_snp_marginals_checkpoint")
-
-    def rollback(self):
-        _chk(lib().sa_snp_marginals_rollback(self._h), "sa_snp_marginals_rollback")
-
     def finish(self, min_depth=1, ref_by_contig=None, stats=None):
         """structured array (SNP_MARGINAL_DTYPE): the sites with rows, in (contig, position) order"""
-        refs = None
-        if ref_by_contig is not None:
-            keep = [r.encode() if isinstance(r, str) else bytes(r) for r in ref_by_contig]
-            if len(keep) != self.n_contigs or any(len(r) < n for r, n in zip(keep, self.contig_lens)):
-                raise ValueError("ref_by_contig: one sequence per contig, each at least as long as its contig")
-            refs = (C.c_char_p * len(keep))(*keep)
-        ptr = C.c_void_p()
-        n = np.zeros(1, dtype=np.int64)
-        kms = C.c_double()
-        _chk(lib().sa_snp_marginals_finish(self._h, int(min_depth), refs, C.byref(ptr), _ip(n), C.byref(kms)), "sa_snp_marginals_finish")
-        out = np.zeros(int(n[0]), dtype=SNP_MARGINAL_DTYPE)
-        if n[0]:
-            C.memmove(out.ctypes.data, ptr, out.nbytes)
-        lib().sa_free(ptr)
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
-        return out
-
-    def close(self):
-        if self._h:
-            lib().sa_snp_marginals_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        refs = self._refs(ref_by_contig)
+        return self._finish(SNP_MARGINAL_DTYPE, stats,
+                            lambda ptr, n, kms: lib().sa_snp_marginals_finish(self._h, int(min_depth), refs, ptr, n, kms))
 
 
-class PositionProfile:
+class PositionProfile(_ContigAcc):
     """sa_position_profile_t: per contig position the pile-up of all reads' posteriors (multipleAlignmentAnalysis.py) as integer
     sums, kept in HBM across add_batch / add_records calls."""
+    _PREFIX = "sa_position_profile_"
 
     def __init__(self, model, contig_lens, device=0):
-        self._h = C.c_void_p()
-        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
-        self.n_contigs = len(lens)
-        self.contig_lens = [int(v) for v in lens]
         self.alphabet = model.alphabet()[0]
-        _chk(lib().sa_position_profile_create(C.byref(self._h), model._h, _ip(lens), len(lens), int(device)), "sa_position_profile_create")
+        self._create(contig_lens, lambda h, lens, n: lib().sa_position_profile_create(h, model._h, lens, n, int(device)))
 
     @staticmethod
     def _map(job_map):
@@ -2034,43 +2055,13 @@ class PositionProfile:
         if stats is not None:
             stats["kernel_ms"] = kms.value
 
-    def checkpoint(self):
-        _chk(lib().sa_position_profile_checkpoint(self._h), "sa_position_profile_checkpoint")
-
-    def rollback(self):
-        _chk(lib().sa_position_profile_rollback(self._h), "sa_position_profile_rollback")
-
     def finish(self, ref_by_contig=None, stats=None):
         """(structured array of PROFILE_SITE_DTYPE in (contig, position) order, letters_seen bit mask)"""
-        refs = None
-        if ref_by_contig is not None:
-            keep = [r.encode() if isinstance(r, str) else bytes(r) for r in ref_by_contig]
-            if len(keep) != self.n_contigs or any(len(r) < n for r, n in zip(keep, self.contig_lens)):
-                raise ValueError("ref_by_contig: one sequence per contig, each at least as long as its contig")
-            refs = (C.c_char_p * len(keep))(*keep)
-        ptr = C.c_void_p()
-        n = np.zeros(1, dtype=np.int64)
+        refs = self._refs(ref_by_contig)
         seen = C.c_uint32()
-        kms = C.c_double()
-        _chk(lib().sa_position_profile_finish(self._h, refs, C.byref(ptr), _ip(n), C.byref(seen), C.byref(kms)), "sa_position_profile_finish")
-        out = np.zeros(int(n[0]), dtype=PROFILE_SITE_DTYPE)
-        if n[0]:
-            C.memmove(out.ctypes.data, ptr, out.nbytes)
-        lib().sa_free(ptr)
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
+        out = self._finish(PROFILE_SITE_DTYPE, stats,
+                           lambda ptr, n, kms: lib().sa_position_profile_finish(self._h, refs, ptr, n, C.byref(seen), kms))
         return out, int(seen.value)
-
-    def close(self):
-        if self._h:
-            lib().sa_position_profile_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def position_profile_write(path, alphabet, letters_seen, contig_names, sites):

@@ -2,14 +2,15 @@
 // (src/signalalign/scripts/variantCallingLib.py:114-164, :226-271) over what --snp-step writes per read, kept in HBM across
 // batches (include/signalalign_hip.h has the semantics and the two deliberate differences from the reference).
 //
-// The accumulator holds, per contig position g (contigs one after the other): sum[g * 8 + 0..3] the forward sum of A, C, G, T,
-// sum[g * 8 + 4..7] the backward sum, depth[g] the rows added so far, and two working arrays of an add, tcnt[g] and tloc[g];
-// tcnt is zero between calls.
+// The accumulator is a table over contig positions (sa_contig_acc.h has the layout, the life cycle and the compaction of finish;
+// here are the sums and their kernels).  Its store is [sum | depth | tcnt | tloc], per position g: sum[g * 8 + 0..3] the forward
+// sum of A, C, G, T, sum[g * 8 + 4..7] the backward sum, depth[g] the rows added so far, and two working arrays of an add,
+// tcnt[g] and tloc[g].  A checkpoint covers [sum | depth]: tcnt is zero between calls and tloc is scratch.
 //
 // The reference adds doubles serially, row after row, so a site's rows of one add call are gathered into a bucket, the bucket
 // is put in order and ONE lane folds it, starting from the sums the accumulator holds.  Every row of a call has a unique
 // 32-bit ordinal (its rank in (run, strand, given order), made on the host), so a bucket's order does not depend on the
-// order in which the atomics handed out its places.  An add costs O(rows), not O(contig length): the touched sites are listed.
+// order in which the atomics handed out its places.  The touched sites are listed, so an add never walks the contigs.
 //
 // Kernels of an add over n rows {site, ordinal, direction, p[4]}:
 //   k_mg_count        one thread per row: ticket[i] = integer atomic increment of tcnt[site]
@@ -26,9 +27,8 @@
 //   k_mg_window       one thread per job: reference_index of the job's smallest and largest x into its group's range
 //   k_mg_batch_rows   one wave per job: every position call of the job becomes a row (contig position, window filter, the
 //                     letters' probabilities in A, C, G, T order); a kept position outside its contig raises a flag
-// Kernels of finish:
+// Kernels of finish, between which sa_acc_finish scans the blocks' counts:
 //   k_mg_mark         one block per 2048 positions: how many are reported
-//   k_mg_scan         exclusive scan of the blocks' counts (one block)
 //   k_mg_emit         marginal, probabilities, called letter, proposal and delta of every reported position, compacted in
 //                     (contig, position) order
 #include <hip/hip_runtime.h>
@@ -45,14 +45,11 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_chain.h"
+#include "sa_contig_acc.h"
 
 #define MG_SHORT 16u
 #define MG_MEDIUM 1024u
 #define MG_MAX_ROWS (1ll << 30)
-#define MG_MARK_THREADS 256
-#define MG_MARK_PER_THREAD 8
-#define MG_MARK_SPAN (MG_MARK_THREADS * MG_MARK_PER_THREAD)
 
 struct MgRow {
     long long site;   // global position, -1: dropped
@@ -68,19 +65,11 @@ struct MgJob {   // sa_snp_job_map_t as the device reads it
     int pad;
 };
 
-struct sa_snp_marginals {
-    int device = 0;
-    long long step = 0, n_contigs = 0, n_pos = 0;
-    std::vector<long long> coff;   // n_contigs + 1
-    long long *d_coff = nullptr;
-    double *d_sum = nullptr;
+// poisoned: an add failed after its first kernel, and tcnt[] may hold counts
+struct sa_snp_marginals : SaContigAcc {
+    long long step = 0;
+    double *d_sum = nullptr;   // the store's arrays
     unsigned *d_depth = nullptr, *d_tcnt = nullptr, *d_tloc = nullptr;
-    bool poisoned = false;   // an add failed after its first kernel: tcnt[] may hold counts, every later call is SA_ESTATE
-    bool ck = false;
-    double *ck_sum = nullptr;
-    unsigned *ck_depth = nullptr;
-    std::mutex mu;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
 __device__ __forceinline__ unsigned mg_pow2ceil(unsigned c) { return c <= 1u ? 1u : 1u << (32 - __clz((int) (c - 1u))); }
@@ -282,50 +271,29 @@ done:
 }
 
 extern "C" int sa_snp_marginals_create(sa_snp_marginals_t **out, const int64_t *contig_lens, int64_t n_contigs, int64_t step, int device) {
-    if (!out || n_contigs < 1 || n_contigs >= INT32_MAX || !contig_lens || step < 0) return SA_EINVAL;
+    if (!out || step < 0) return SA_EINVAL;
     *out = nullptr;
-    long long total = 0;
-    for (int64_t c = 0; c < n_contigs; c++) {
-        if (contig_lens[c] < 0 || contig_lens[c] > (int64_t) 1 << 40) return SA_EINVAL;
-        total += contig_lens[c];
-    }
-    if (const int rc = sa_device_check(device, /* quiet */ true)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
     sa_snp_marginals *t = new (std::nothrow) sa_snp_marginals();
     if (!t) return SA_ENOMEM;
-    t->device = device;
+    int rc = sa_acc_layout(t, contig_lens, n_contigs, /* pad */ 0);
+    if (rc != SA_OK) { delete t; return rc; }
     t->step = step;
-    t->n_contigs = n_contigs;
-    t->n_pos = total;
-    t->coff.assign((size_t) n_contigs + 1, 0);
-    for (int64_t c = 0; c < n_contigs; c++) t->coff[(size_t) c + 1] = t->coff[(size_t) c] + contig_lens[c];
-    const size_t np = (size_t) (total > 0 ? total : 1);
-    int rc = SA_OK;
-    SA_HIP_GOTO_DONE(hipEventCreate(&t->e0));
-    SA_HIP_GOTO_DONE(hipEventCreate(&t->e1));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_coff, 8 * t->coff.size(), device));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_sum, 8 * 8 * np, device));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_depth, 4 * np, device));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_tcnt, 4 * np, device));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_tloc, 4 * np, device));
-    SA_HIP_GOTO_DONE(hipMemcpy(t->d_coff, t->coff.data(), 8 * t->coff.size(), hipMemcpyHostToDevice));
-    SA_HIP_GOTO_DONE(hipMemset(t->d_sum, 0, 8 * 8 * np));   // (all bits zero is +0.0)
-    SA_HIP_GOTO_DONE(hipMemset(t->d_depth, 0, 4 * np));
-    SA_HIP_GOTO_DONE(hipMemset(t->d_tcnt, 0, 4 * np));
-    SA_HIP_GOTO_DONE(hipDeviceSynchronize());
-done:
+    const size_t np = (size_t) (t->n_slots > 0 ? t->n_slots : 1);
+    SaLayout L;
+    const size_t o_sum = L.add(8 * 8 * np), o_depth = L.add(4 * np), ck_bytes = L.end, o_tcnt = L.add(4 * np), o_tloc = L.add(4 * np);
+    rc = sa_acc_alloc(t, device, L.end, ck_bytes);
     if (rc != SA_OK) { sa_snp_marginals_destroy(t); return rc; }
+    t->d_sum = (double *) (t->d_store + o_sum);
+    t->d_depth = (unsigned *) (t->d_store + o_depth);
+    t->d_tcnt = (unsigned *) (t->d_store + o_tcnt);
+    t->d_tloc = (unsigned *) (t->d_store + o_tloc);
     *out = t;
     return SA_OK;
 }
 
 extern "C" void sa_snp_marginals_destroy(sa_snp_marginals_t *t) {
     if (!t) return;
-    (void) hipSetDevice(t->device);
-    void *blocks[] = {t->d_coff, t->d_sum, t->d_depth, t->d_tcnt, t->d_tloc, t->ck_sum, t->ck_depth};
-    for (void *p : blocks) g_sa_pool.put(SaPool::DEVICE, p);
-    if (t->e0) (void) hipEventDestroy(t->e0);
-    if (t->e1) (void) hipEventDestroy(t->e1);
+    sa_acc_free(t);
     delete t;
 }
 
@@ -350,9 +318,8 @@ extern "C" int sa_snp_marginals_add_sites(sa_snp_marginals_t *t, int32_t contig,
         r.dir = direction ? 1 : 0;
         for (int l = 0; l < 4; l++) r.p[l] = sites[i].p[l];
     }
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    SaAccEnter in(t);
+    if (in.rc) return in.rc;
     int rc = SA_OK;
     MgRow *d_rows = nullptr;
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_rows, sizeof(MgRow) * (size_t) n, t->device) != hipSuccess) return SA_ENOMEM;
@@ -419,8 +386,8 @@ extern "C" int sa_snp_marginals_add_batch(sa_snp_marginals_t *t, sa_batch_t *b, 
                                           double *kernel_ms_out) {
     if (!t || !b || n_jobs < 0 || (n_jobs > 0 && !map)) return SA_EINVAL;
     if (kernel_ms_out) kernel_ms_out[0] = kernel_ms_out[1] = 0.0;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
+    SaAccEnter in(t);
+    if (in.rc) return in.rc;
     SaPosFold F;
     int rc = sa_pos_fold_run(b, &F);
     char *d = nullptr;
@@ -467,7 +434,7 @@ extern "C" int sa_snp_marginals_add_batch(sa_snp_marginals_t *t, sa_batch_t *b, 
                      o_x = L.add(4 * (ns ? ns : 1)), o_acgt = L.add(F.acgt.size() + 1), o_err = L.add(4), o_rows = L.add(sizeof(MgRow) * n);
         float kms = 0;
         int h_err = 0;
-        if (hipSetDevice(t->device) != hipSuccess) { rc = SA_ENODEVICE; goto done; }
+        if (hipSetDevice(t->device) != hipSuccess) { rc = SA_ENODEVICE; goto done; }   // (the fold bound the batch's, the same one)
         if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, L.end, t->device) != hipSuccess) { d = nullptr; rc = SA_ENOMEM; goto done; }
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_jobs, jobs.data(), sizeof(MgJob) * nj, hipMemcpyHostToDevice, 0));
         SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_count, F.count.data(), 8 * nj, hipMemcpyHostToDevice, 0));
@@ -500,101 +467,39 @@ done:
     return rc;
 }
 
-extern "C" int sa_snp_marginals_checkpoint(sa_snp_marginals_t *t) {
-    if (!t) return SA_EINVAL;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    const size_t np = (size_t) (t->n_pos > 0 ? t->n_pos : 1);
-    int rc = SA_OK;
-    if (!t->ck_sum && g_sa_pool.get(SaPool::DEVICE, (void **) &t->ck_sum, 8 * 8 * np, t->device) != hipSuccess) { t->ck_sum = nullptr; return SA_ENOMEM; }
-    if (!t->ck_depth && g_sa_pool.get(SaPool::DEVICE, (void **) &t->ck_depth, 4 * np, t->device) != hipSuccess) { t->ck_depth = nullptr; return SA_ENOMEM; }
-    t->ck = false;
-    SA_HIP_GOTO_DONE(hipMemcpy(t->ck_sum, t->d_sum, 8 * 8 * np, hipMemcpyDeviceToDevice));
-    SA_HIP_GOTO_DONE(hipMemcpy(t->ck_depth, t->d_depth, 4 * np, hipMemcpyDeviceToDevice));
-    SA_HIP_GOTO_DONE(hipDeviceSynchronize());
-    t->ck = true;
-done:
-    return rc;
-}
-
-extern "C" int sa_snp_marginals_rollback(sa_snp_marginals_t *t) {
-    if (!t) return SA_EINVAL;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (!t->ck || t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    const size_t np = (size_t) (t->n_pos > 0 ? t->n_pos : 1);
-    int rc = SA_OK;
-    SA_HIP_GOTO_DONE(hipMemcpy(t->d_sum, t->ck_sum, 8 * 8 * np, hipMemcpyDeviceToDevice));
-    SA_HIP_GOTO_DONE(hipMemcpy(t->d_depth, t->ck_depth, 4 * np, hipMemcpyDeviceToDevice));
-    SA_HIP_GOTO_DONE(hipDeviceSynchronize());
-done:
-    return rc;
-}
+extern "C" int sa_snp_marginals_checkpoint(sa_snp_marginals_t *t) { return sa_acc_checkpoint(t); }
+extern "C" int sa_snp_marginals_rollback(sa_snp_marginals_t *t) { return sa_acc_rollback(t); }
 
 // ---- finish ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MG_MARK_THREADS) void k_mg_mark(const unsigned *__restrict__ depth, long long n_pos, unsigned min_depth,
-                                                            int *__restrict__ blk_cnt) {
-    __shared__ int total;
-    if (threadIdx.x == 0) total = 0;
-    __syncthreads();
-    const long long g0 = (long long) blockIdx.x * MG_MARK_SPAN + (long long) threadIdx.x * MG_MARK_PER_THREAD;
-    int mine = 0;
-    for (int q = 0; q < MG_MARK_PER_THREAD; q++)
-        if (g0 + q < n_pos && depth[g0 + q] >= min_depth) mine++;
-    if (mine) atomicAdd(&total, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
+__global__ __launch_bounds__(SA_ACC_THREADS) void k_mg_mark(const unsigned *__restrict__ depth, long long n_pos, unsigned min_depth,
+                                                           long long *__restrict__ blk_cnt) {
+    sa_acc_block_count(sa_acc_count(sa_acc_first_slot(), n_pos, [=](long long g, int) { return depth[g] >= min_depth; }), blk_cnt);
 }
 
-__global__ __launch_bounds__(SA_SCAN_THREADS) void k_mg_scan(const int *__restrict__ count, long long *__restrict__ off, long long n) {
-    sa_block_excl_scan([count](long long i) { return (long long) count[i]; }, off, n);
-}
+__device__ __forceinline__ int mg_letter_index(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 
-__device__ __forceinline__ int mg_letter_index(char c) {
-    if (c >= 'a' && c <= 'z') c = (char) (c - 'a' + 'A');
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-}
-
-__global__ __launch_bounds__(MG_MARK_THREADS) void k_mg_emit(const unsigned *__restrict__ depth, const double *__restrict__ sum,
-                                                            long long n_pos, unsigned min_depth, const long long *__restrict__ coff,
-                                                            int n_contigs, const char *__restrict__ ref,
-                                                            const long long *__restrict__ blk_off, sa_snp_marginal_t *__restrict__ out) {
-    __shared__ int wave_tot[MG_MARK_THREADS / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long g0 = (long long) blockIdx.x * MG_MARK_SPAN + (long long) threadIdx.x * MG_MARK_PER_THREAD;
-    int mine = 0;
-    for (int q = 0; q < MG_MARK_PER_THREAD; q++)
-        if (g0 + q < n_pos && depth[g0 + q] >= min_depth) mine++;
-    const int incl = sa_wave_incl_scan(mine, lane);
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    long long w = blk_off[blockIdx.x] + incl - mine;
-    for (int q = 0; q < wv; q++) w += wave_tot[q];
-    for (int q = 0; q < MG_MARK_PER_THREAD && mine; q++) {
+__global__ __launch_bounds__(SA_ACC_THREADS) void k_mg_emit(const unsigned *__restrict__ depth, const double *__restrict__ sum,
+                                                           long long n_pos, unsigned min_depth, const long long *__restrict__ coff,
+                                                           int n_contigs, const char *__restrict__ ref,
+                                                           const long long *__restrict__ blk_off, sa_snp_marginal_t *__restrict__ out) {
+    const long long g0 = sa_acc_first_slot();
+    const int mine = sa_acc_count(g0, n_pos, [=](long long g, int) { return depth[g] >= min_depth; });
+    long long w = sa_acc_place(mine, blk_off[blockIdx.x]);
+    for (int q = 0; q < SA_ACC_PER_THREAD && mine; q++) {
         const long long g = g0 + q;
         if (g >= n_pos || depth[g] < min_depth) continue;
-        int lo = 0, hi = n_contigs;   // the contig: the last c with coff[c] <= g (empty contigs share an offset with the next)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (coff[mid] <= g) lo = mid; else hi = mid;
-        }
+        const int c = sa_acc_contig_of(coff, n_contigs, g);
         sa_snp_marginal_t o;
-        o.pos = g - coff[lo];
-        o.contig = lo;
+        o.pos = g - coff[c];
+        o.contig = c;
         o.depth = (int32_t) depth[g];
         const double *s = sum + (size_t) g * 8;
         for (int l = 0; l < 4; l++) { o.fwd[l] = s[l]; o.bwd[l] = s[4 + l]; }
         double m[4];
         for (int l = 0; l < 4; l++) m[l] = o.fwd[l] + o.bwd[3 - l];   // (rc_probs on the backward sum)
         const double total = ((m[0] + m[1]) + m[2]) + m[3];
-        const int ri = ref ? mg_letter_index(ref[g]) : -1;
-        char rc_letter = 'N';
-        if (ref) {
-            rc_letter = ref[g];
-            if (rc_letter >= 'a' && rc_letter <= 'z') rc_letter = (char) (rc_letter - 'a' + 'A');
-        }
-        o.ref = rc_letter;
+        o.ref = sa_acc_ref_letter(ref, g);
+        const int ri = mg_letter_index(o.ref);   // ('N' without a reference: none)
         for (int q2 = 0; q2 < 5; q2++) o.pad[q2] = 0;
         if (total == 0.0) {
             for (int l = 0; l < 4; l++) o.prob[l] = 0.0;
@@ -616,69 +521,18 @@ __global__ __launch_bounds__(MG_MARK_THREADS) void k_mg_emit(const unsigned *__r
 
 extern "C" int sa_snp_marginals_finish(sa_snp_marginals_t *t, int64_t min_depth, const char *const *ref_by_contig,
                                        sa_snp_marginal_t **sites_out, int64_t *n_out, double *kernel_ms_out) {
-    if (!t || !sites_out || !n_out) return SA_EINVAL;
-    *sites_out = nullptr;
-    *n_out = 0;
-    if (kernel_ms_out) *kernel_ms_out = 0.0;
-    if (ref_by_contig)
-        for (long long c = 0; c < t->n_contigs; c++)
-            if (!ref_by_contig[c]) return SA_EINVAL;
+    if (const int rc = sa_acc_finish_args(t, ref_by_contig, sites_out, n_out, kernel_ms_out)) return rc;
     const unsigned md = (unsigned) std::min<int64_t>(std::max<int64_t>(min_depth, 1), (int64_t) UINT32_MAX);
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    const size_t np = (size_t) t->n_pos, nb = (np + MG_MARK_SPAN - 1) / MG_MARK_SPAN;
-    sa_snp_marginal_t *host = nullptr;
-    if (nb == 0) {
-        *sites_out = (sa_snp_marginal_t *) calloc(1, sizeof(sa_snp_marginal_t));
-        return *sites_out ? SA_OK : SA_ENOMEM;
-    }
-    int rc = SA_OK;
-    SaLayout L;   // [block counts | block offsets | reference letters]
-    const size_t o_cnt = L.add(4 * nb), o_off = L.add(8 * (nb + 1)), o_ref = L.add(ref_by_contig ? np : 1);
-    char *d = nullptr;
-    sa_snp_marginal_t *d_out = nullptr;
-    long long n_kept = 0;
-    float kms0 = 0, kms1 = 0;
-    if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, L.end, t->device) != hipSuccess) return SA_ENOMEM;
-    if (ref_by_contig)
-        for (long long c = 0; c < t->n_contigs; c++) {
-            const size_t len = (size_t) (t->coff[(size_t) c + 1] - t->coff[(size_t) c]);
-            if (len) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_ref + t->coff[(size_t) c], ref_by_contig[c], len, hipMemcpyHostToDevice, 0));
-        }
-    SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
-    hipLaunchKernelGGL(k_mg_mark, dim3((unsigned) nb), dim3(MG_MARK_THREADS), 0, 0, (const unsigned *) t->d_depth, (long long) np, md,
-                       (int *) (d + o_cnt));
-    hipLaunchKernelGGL(k_mg_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const int *) (d + o_cnt), (long long *) (d + o_off), (long long) nb);
-    SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
-    SA_HIP_GOTO_DONE(hipGetLastError());
-    SA_HIP_GOTO_DONE(hipMemcpy(&n_kept, d + o_off + 8 * nb, 8, hipMemcpyDeviceToHost));
-    SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms0, t->e0, t->e1));
-    host = (sa_snp_marginal_t *) calloc((size_t) (n_kept > 0 ? n_kept : 1), sizeof(sa_snp_marginal_t));
-    if (!host) { rc = SA_ENOMEM; goto done; }
-    if (n_kept > 0) {
-        if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_out, sizeof(sa_snp_marginal_t) * (size_t) n_kept, t->device) != hipSuccess) {
-            d_out = nullptr;
-            rc = SA_ENOMEM;
-            goto done;
-        }
-        SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
-        hipLaunchKernelGGL(k_mg_emit, dim3((unsigned) nb), dim3(MG_MARK_THREADS), 0, 0, (const unsigned *) t->d_depth, (const double *) t->d_sum,
-                           (long long) np, md, (const long long *) t->d_coff, (int) t->n_contigs,
-                           ref_by_contig ? (const char *) (d + o_ref) : (const char *) nullptr, (const long long *) (d + o_off), d_out);
-        SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
-        SA_HIP_GOTO_DONE(hipMemcpy(host, d_out, sizeof(sa_snp_marginal_t) * (size_t) n_kept, hipMemcpyDeviceToHost));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&kms1, t->e0, t->e1));
-    }
-    if (kernel_ms_out) *kernel_ms_out = (double) kms0 + (double) kms1;
-    *sites_out = host;
-    *n_out = n_kept;
-    host = nullptr;
-done:
-    if (rc != SA_OK) (void) hipStreamSynchronize(0);
-    g_sa_pool.put(SaPool::DEVICE, d);
-    if (d_out) g_sa_pool.put(SaPool::DEVICE, d_out);
-    free(host);
-    return rc;
+    SaAccEnter in(t);
+    if (in.rc) return in.rc;
+    return sa_acc_finish(
+        t, ref_by_contig, 0,
+        [&](unsigned nb, char *, long long *blk_cnt) {
+            hipLaunchKernelGGL(k_mg_mark, dim3(nb), dim3(SA_ACC_THREADS), 0, 0, (const unsigned *) t->d_depth, t->n_slots, md, blk_cnt);
+        },
+        [&](unsigned nb, char *, const long long *blk_off, const char *ref, sa_snp_marginal_t *d_out) {
+            hipLaunchKernelGGL(k_mg_emit, dim3(nb), dim3(SA_ACC_THREADS), 0, 0, (const unsigned *) t->d_depth, (const double *) t->d_sum,
+                               t->n_slots, md, (const long long *) t->d_coff, (int) t->n_contigs, ref, blk_off, d_out);
+        },
+        sites_out, n_out, kernel_ms_out);
 }

@@ -2,11 +2,12 @@
 // multipleAlignmentAnalysis.py:52-69, :118-242) over the records of finished batches, kept in HBM across batches
 // (include/signalalign_hip.h has the semantics and the three deliberate differences from the script; sa_profile.c the host half).
 //
-// The accumulator lies over slots: contig c's position q is slot coff[c] + c + q, and every contig has one slot more than positions
-// (where the difference array of its spans takes the -1 of a span that ends on the last position).  Per slot g, with S = 2 + letters
+// The accumulator is a table over contig positions (sa_contig_acc.h has the layout, the life cycle and the compaction of finish;
+// here are the sums and their kernels) in which every contig has one slot more than positions, where the difference array of its
+// spans takes the -1 of a span that ends on the last position.  Its store is [acc | diff | seen], per slot g, with S = 2 + letters
 // of the alphabet: acc[g * S + 0] the contributions, acc[g * S + 1] the entropy units, acc[g * S + 2 + l] the printed units of
-// letter l (64-bit integers), diff[g] the spans' difference array (int32); one word more holds the seen letters.  All of it is ONE
-// block, so that a checkpoint is one copy.
+// letter l (64-bit integers), diff[g] the spans' difference array (int32); one word more holds the seen letters.  A checkpoint
+// covers all of it.
 //
 // Kernels of an add:
 //   k_pf_range        one block per chunk of a job's records: the job's smallest and largest x (LDS, then one global atomic min /
@@ -21,9 +22,8 @@
 //                     result never depends on the window; SA_PROFILE_DIRECT sends every contribution that way.  The entropy term
 //                     is looked up once per record in the table of the 1 000 001 terms (the host function's values, built once
 //                     per process, one device copy per table).
-// Kernels of finish:
-//   k_pf_block_sums   one block per 2048 slots: the sum of its differences
-//   k_pf_scan         exclusive scan of the blocks' sums, and later of the blocks' counts (one block)
+// Kernels of finish, between which sa_acc_finish scans the blocks' counts:
+//   k_pf_block_sums   one block per 2048 slots: the sum of its differences, scanned over the blocks (k_acc_scan) before
 //   k_pf_mark         read_count of every slot from the scanned sums; how many slots of the block are reported
 //   k_pf_emit         the sites, compacted in (contig, position) order
 #include <hip/hip_runtime.h>
@@ -37,12 +37,10 @@
 #include <vector>
 
 #include "sa_internal.h"
-#include "sa_chain.h"
+#include "sa_contig_acc.h"
 
 #define PF_THREADS 256
 #define PF_LDS_WORDS 6144   // 48 KiB of window: three blocks per CU
-#define PF_SPAN_PER_THREAD 8
-#define PF_SPAN (PF_THREADS * PF_SPAN_PER_THREAD)
 #define PF_ERR_RECORD 1
 
 struct PfJob {
@@ -63,18 +61,14 @@ struct PfArgs {
     unsigned char comp[SA_SITE_MAX_LETTERS];
 };
 
-struct sa_position_profile {
-    int device = 0, k = 0, n_alpha = 0, S = 0;
-    long long n_kmers = 0, n_contigs = 0, n_slots = 0;
+// poisoned: an add failed after its spans went in, and part of the call may be in the table
+struct sa_position_profile : SaContigAcc {
+    int k = 0, n_alpha = 0, S = 0;
+    long long n_kmers = 0;
     char alphabet[SA_SITE_MAX_LETTERS + 1] = {0};
     unsigned char comp[SA_SITE_MAX_LETTERS] = {0};
-    std::vector<long long> coff, clen;   // slot of position 0 of every contig (n_contigs + 1), and the lengths
-    long long *d_coff = nullptr, *d_term = nullptr;
-    char *d_store = nullptr, *ck_store = nullptr;   // [acc | diff | seen]
-    size_t o_diff = 0, o_seen = 0, store_bytes = 0;
-    bool poisoned = false, ck = false;
-    std::mutex mu;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    long long *d_term = nullptr;
+    size_t o_diff = 0, o_seen = 0;   // of the store's [acc | diff | seen]
     unsigned long long *acc() const { return (unsigned long long *) d_store; }
     int *diff() const { return (int *) (d_store + o_diff); }
     unsigned *seen() const { return (unsigned *) (d_store + o_seen); }
@@ -202,54 +196,34 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_accumulate(const PfArgs A) {
 
 extern "C" int sa_position_profile_create(sa_position_profile_t **out, const sa_model_t *m, const int64_t *contig_lens, int64_t n_contigs,
                                           int device) {
-    if (!out || !m || n_contigs < 1 || n_contigs >= INT32_MAX || !contig_lens) return SA_EINVAL;
+    if (!out || !m) return SA_EINVAL;
     *out = nullptr;
-    long long total = 0;
-    for (int64_t c = 0; c < n_contigs; c++) {
-        if (contig_lens[c] < 0 || contig_lens[c] > (int64_t) 1 << 40) return SA_EINVAL;
-        total += contig_lens[c];
-    }
-    if (m->n_alpha > SA_SITE_MAX_LETTERS || m->n_alpha < 1 || m->k < 1 || m->n_kmers > (int64_t) INT32_MAX) return SA_EUNSUPPORTED;
-    unsigned char comp[SA_SITE_MAX_LETTERS] = {0};
-    for (int l = 0; l < m->n_alpha; l++) {
+    sa_position_profile *t = new (std::nothrow) sa_position_profile();
+    if (!t) return SA_ENOMEM;
+    int rc = sa_acc_layout(t, contig_lens, n_contigs, /* pad */ 1);
+    if (rc == SA_OK && (m->n_alpha > SA_SITE_MAX_LETTERS || m->n_alpha < 1 || m->k < 1 || m->n_kmers > (int64_t) INT32_MAX)) rc = SA_EUNSUPPORTED;
+    for (int l = 0; rc == SA_OK && l < m->n_alpha; l++) {
         const char c = m->alphabet[l];
         const char want = c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
         const char *hit = (const char *) memchr(m->alphabet, want, (size_t) m->n_alpha);
-        if (!hit) return SA_EUNSUPPORTED;
-        comp[l] = (unsigned char) (hit - m->alphabet);
+        if (!hit) rc = SA_EUNSUPPORTED;
+        else t->comp[l] = (unsigned char) (hit - m->alphabet);
     }
-    if (const int rc = sa_device_check(device, /* quiet */ true)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return SA_ENODEVICE;
-    sa_position_profile *t = new (std::nothrow) sa_position_profile();
-    if (!t) return SA_ENOMEM;
-    t->device = device;
+    if (rc != SA_OK) { delete t; return rc; }
     t->k = m->k;
     t->n_alpha = m->n_alpha;
     t->S = 2 + m->n_alpha;
     t->n_kmers = m->n_kmers;
-    t->n_contigs = n_contigs;
     memcpy(t->alphabet, m->alphabet, (size_t) m->n_alpha);
-    memcpy(t->comp, comp, sizeof comp);
-    t->coff.assign((size_t) n_contigs + 1, 0);
-    t->clen.assign(contig_lens, contig_lens + n_contigs);
-    for (int64_t c = 0; c < n_contigs; c++) t->coff[(size_t) c + 1] = t->coff[(size_t) c] + contig_lens[c] + 1;
-    t->n_slots = total + n_contigs;
     SaLayout L;
     (void) L.add(8 * (size_t) t->S * (size_t) t->n_slots);
     t->o_diff = L.add(4 * (size_t) t->n_slots);
     t->o_seen = L.add(4);
-    t->store_bytes = L.end;
     const std::vector<long long> &terms = pf_terms();
-    int rc = SA_OK;
-    SA_HIP_GOTO_DONE(hipEventCreate(&t->e0));
-    SA_HIP_GOTO_DONE(hipEventCreate(&t->e1));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_coff, 8 * t->coff.size(), device));
+    rc = sa_acc_alloc(t, device, L.end, L.end);
+    if (rc != SA_OK) goto done;
     SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_term, 8 * terms.size(), device));
-    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &t->d_store, t->store_bytes, device));
-    SA_HIP_GOTO_DONE(hipMemcpy(t->d_coff, t->coff.data(), 8 * t->coff.size(), hipMemcpyHostToDevice));
     SA_HIP_GOTO_DONE(hipMemcpy(t->d_term, terms.data(), 8 * terms.size(), hipMemcpyHostToDevice));
-    SA_HIP_GOTO_DONE(hipMemset(t->d_store, 0, t->store_bytes));
-    SA_HIP_GOTO_DONE(hipDeviceSynchronize());
 done:
     if (rc != SA_OK) { sa_position_profile_destroy(t); return rc; }
     *out = t;
@@ -258,11 +232,8 @@ done:
 
 extern "C" void sa_position_profile_destroy(sa_position_profile_t *t) {
     if (!t) return;
-    (void) hipSetDevice(t->device);
-    void *blocks[] = {t->d_coff, t->d_term, t->d_store, t->ck_store};
-    for (void *p : blocks) g_sa_pool.put(SaPool::DEVICE, p);
-    if (t->e0) (void) hipEventDestroy(t->e0);
-    if (t->e1) (void) hipEventDestroy(t->e1);
+    sa_acc_free(t);
+    g_sa_pool.put(SaPool::DEVICE, t->d_term);
     delete t;
 }
 
@@ -349,8 +320,8 @@ extern "C" int sa_position_profile_add_batch(sa_position_profile_t *t, sa_batch_
                                              unsigned flags, double *kernel_ms_out) {
     if (!t || !b || n_jobs < 0 || (n_jobs > 0 && !map) || (flags & ~SA_PROFILE_DIRECT)) return SA_EINVAL;
     if (kernel_ms_out) *kernel_ms_out = 0.0;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
+    SaAccEnter in(t);
+    if (in.rc) return in.rc;
     SaBatchView V;
     const int rc = sa_batch_view(b, &V);
     if (V.batch_flags & SA_FLAG_VC_ROWS) return SA_EINVAL;       // (it dropped rows; refused before the batch's state is looked at)
@@ -359,7 +330,7 @@ extern "C" int sa_position_profile_add_batch(sa_position_profile_t *t, sa_batch_
     if (V.batch_flags & SA_FLAG_EXPECT_INTERNAL) return SA_ESTATE;
     if ((int64_t) V.count.size() != n_jobs || V.device != t->device || V.k != t->k || V.n_alpha != t->n_alpha) return SA_EINVAL;
     if (sa_profile_check_map(map, n_jobs, t->n_contigs) != SA_OK) return SA_EINVAL;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;   // (the view may have bound the batch's, the same one)
     return pf_add(t, (const sa_pair16_t *) V.recs, V, map, flags, kernel_ms_out);
 }
 
@@ -377,10 +348,9 @@ extern "C" int sa_position_profile_add_records(sa_position_profile_t *t, const s
     for (int64_t j = 0; j < n_jobs; j++) V.count[(size_t) j] = first[j + 1] - first[j];
     std::vector<sa_pair16_t> recs(n);
     for (size_t i = 0; i < n; i++) recs[i] = sa_pair16_pack(prob_e7[i], x[i], 0, 0, kmer_id[i]);
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
+    SaAccEnter in(t);
+    if (in.rc) return in.rc;
     if (n == 0) return SA_OK;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
     int rc = SA_OK;
     sa_pair16_t *d_recs = nullptr;
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_recs, sizeof(sa_pair16_t) * n, t->device) != hipSuccess) return SA_ENOMEM;
@@ -391,123 +361,64 @@ done:
     return rc;
 }
 
-extern "C" int sa_position_profile_checkpoint(sa_position_profile_t *t) {
-    if (!t) return SA_EINVAL;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    int rc = SA_OK;
-    if (!t->ck_store && g_sa_pool.get(SaPool::DEVICE, (void **) &t->ck_store, t->store_bytes, t->device) != hipSuccess) {
-        t->ck_store = nullptr;
-        return SA_ENOMEM;
-    }
-    t->ck = false;
-    SA_HIP_GOTO_DONE(hipMemcpy(t->ck_store, t->d_store, t->store_bytes, hipMemcpyDeviceToDevice));
-    SA_HIP_GOTO_DONE(hipDeviceSynchronize());
-    t->ck = true;
-done:
-    return rc;
-}
-
-extern "C" int sa_position_profile_rollback(sa_position_profile_t *t) {
-    if (!t) return SA_EINVAL;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (!t->ck || t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    int rc = SA_OK;
-    SA_HIP_GOTO_DONE(hipMemcpy(t->d_store, t->ck_store, t->store_bytes, hipMemcpyDeviceToDevice));
-    SA_HIP_GOTO_DONE(hipDeviceSynchronize());
-done:
-    return rc;
-}
+extern "C" int sa_position_profile_checkpoint(sa_position_profile_t *t) { return sa_acc_checkpoint(t); }
+extern "C" int sa_position_profile_rollback(sa_position_profile_t *t) { return sa_acc_rollback(t); }
 
 // ---- finish ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PF_THREADS) void k_pf_block_sums(const int *__restrict__ diff, long long n_slots, long long *__restrict__ blk_sum) {
+__global__ __launch_bounds__(SA_ACC_THREADS) void k_pf_block_sums(const int *__restrict__ diff, long long n_slots, long long *__restrict__ blk_sum) {
     __shared__ long long total;
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
-    const long long g0 = (long long) blockIdx.x * PF_SPAN + (long long) threadIdx.x * PF_SPAN_PER_THREAD;
+    const long long g0 = sa_acc_first_slot();
     long long mine = 0;
-    for (int q = 0; q < PF_SPAN_PER_THREAD; q++)
+    for (int q = 0; q < SA_ACC_PER_THREAD; q++)
         if (g0 + q < n_slots) mine += diff[g0 + q];
     if (mine) atomicAdd((unsigned long long *) &total, (unsigned long long) mine);
     __syncthreads();
     if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(SA_SCAN_THREADS) void k_pf_scan(const long long *__restrict__ v, long long *__restrict__ off, long long n) {
-    sa_block_excl_scan([v](long long i) { return v[i]; }, off, n);
-}
-
-// read_count of the thread's PF_SPAN_PER_THREAD slots from g0 on: the differences before the block (before), then inside it
-__device__ __forceinline__ void pf_read_counts(const int *__restrict__ diff, long long n_slots, long long g0, long long before,
-                                               long long *wave_tot, long long *rc) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+// read_count of the thread's SA_ACC_PER_THREAD slots from g0 on: the differences before the block (before), then inside it
+__device__ __forceinline__ void pf_read_counts(const int *__restrict__ diff, long long n_slots, long long g0, long long before, long long *rc) {
     long long mine = 0;
-    for (int q = 0; q < PF_SPAN_PER_THREAD; q++)
+    for (int q = 0; q < SA_ACC_PER_THREAD; q++)
         if (g0 + q < n_slots) mine += diff[g0 + q];
-    const long long incl = sa_wave_incl_scan(mine, lane);
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    long long run = before + incl - mine;
-    for (int q = 0; q < wv; q++) run += wave_tot[q];
-    for (int q = 0; q < PF_SPAN_PER_THREAD; q++) {
+    long long run = sa_acc_place(mine, before);
+    for (int q = 0; q < SA_ACC_PER_THREAD; q++) {
         if (g0 + q < n_slots) run += diff[g0 + q];
         rc[q] = run;
     }
     __syncthreads();
 }
 
-__global__ __launch_bounds__(PF_THREADS) void k_pf_mark(const int *__restrict__ diff, const unsigned long long *__restrict__ acc, int S,
-                                                        long long n_slots, const long long *__restrict__ blk_before,
-                                                        long long *__restrict__ blk_cnt) {
-    __shared__ long long wave_tot[PF_THREADS / 64];
-    __shared__ int total;
-    if (threadIdx.x == 0) total = 0;
-    const long long g0 = (long long) blockIdx.x * PF_SPAN + (long long) threadIdx.x * PF_SPAN_PER_THREAD;
-    long long rc[PF_SPAN_PER_THREAD];
-    pf_read_counts(diff, n_slots, g0, blk_before[blockIdx.x], wave_tot, rc);
-    int mine = 0;
-    for (int q = 0; q < PF_SPAN_PER_THREAD; q++)
-        if (g0 + q < n_slots && (rc[q] > 0 || acc[(size_t) (g0 + q) * S] > 0)) mine++;
-    if (mine) atomicAdd(&total, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
+__global__ __launch_bounds__(SA_ACC_THREADS) void k_pf_mark(const int *__restrict__ diff, const unsigned long long *__restrict__ acc, int S,
+                                                           long long n_slots, const long long *__restrict__ blk_before,
+                                                           long long *__restrict__ blk_cnt) {
+    const long long g0 = sa_acc_first_slot();
+    long long rc[SA_ACC_PER_THREAD];
+    pf_read_counts(diff, n_slots, g0, blk_before[blockIdx.x], rc);
+    sa_acc_block_count(sa_acc_count(g0, n_slots, [&](long long g, int q) { return rc[q] > 0 || acc[(size_t) g * S] > 0; }), blk_cnt);
 }
 
-__global__ __launch_bounds__(PF_THREADS) void k_pf_emit(const int *__restrict__ diff, const unsigned long long *__restrict__ acc, int S,
-                                                        int n_alpha, long long n_slots, const long long *__restrict__ blk_before,
-                                                        const long long *__restrict__ blk_off, const long long *__restrict__ coff,
-                                                        int n_contigs, const char *__restrict__ ref, int have_ref,
-                                                        sa_profile_site_t *__restrict__ out) {
-    __shared__ long long wave_tot[PF_THREADS / 64];
-    __shared__ int cnt_tot[PF_THREADS / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long g0 = (long long) blockIdx.x * PF_SPAN + (long long) threadIdx.x * PF_SPAN_PER_THREAD;
-    long long rc[PF_SPAN_PER_THREAD];
-    pf_read_counts(diff, n_slots, g0, blk_before[blockIdx.x], wave_tot, rc);
-    int mine = 0;
-    for (int q = 0; q < PF_SPAN_PER_THREAD; q++)
-        if (g0 + q < n_slots && (rc[q] > 0 || acc[(size_t) (g0 + q) * S] > 0)) mine++;
-    const int incl = sa_wave_incl_scan(mine, lane);
-    if (lane == 63) cnt_tot[wv] = incl;
-    __syncthreads();
-    long long w = blk_off[blockIdx.x] + incl - mine;
-    for (int q = 0; q < wv; q++) w += cnt_tot[q];
-    for (int q = 0; q < PF_SPAN_PER_THREAD && mine; q++) {
+__global__ __launch_bounds__(SA_ACC_THREADS) void k_pf_emit(const int *__restrict__ diff, const unsigned long long *__restrict__ acc, int S,
+                                                           int n_alpha, long long n_slots, const long long *__restrict__ blk_before,
+                                                           const long long *__restrict__ blk_off, const long long *__restrict__ coff,
+                                                           int n_contigs, const char *__restrict__ ref, sa_profile_site_t *__restrict__ out) {
+    const long long g0 = sa_acc_first_slot();
+    long long rc[SA_ACC_PER_THREAD];
+    pf_read_counts(diff, n_slots, g0, blk_before[blockIdx.x], rc);
+    const int mine = sa_acc_count(g0, n_slots, [&](long long g, int q) { return rc[q] > 0 || acc[(size_t) g * S] > 0; });
+    long long w = sa_acc_place(mine, blk_off[blockIdx.x]);
+    for (int q = 0; q < SA_ACC_PER_THREAD && mine; q++) {
         const long long g = g0 + q;
         if (g >= n_slots) continue;
         const unsigned long long *a = acc + (size_t) g * S;
         const long long kc = (long long) a[0], eu = (long long) a[1];
         if (!(rc[q] > 0 || kc > 0)) continue;
-        int lo = 0, hi = n_contigs;   // the contig: the last c with coff[c] <= g (every contig has at least its extra slot)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (coff[mid] <= g) lo = mid; else hi = mid;
-        }
+        const int c = sa_acc_contig_of(coff, n_contigs, g);
         sa_profile_site_t o;
-        o.pos = g - coff[lo];
-        o.contig = lo;
+        o.pos = g - coff[c];
+        o.contig = c;
         o.read_count = (int32_t) rc[q];
         o.kmer_count = kc;
         o.entropy_units = eu;
@@ -518,12 +429,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_emit(const int *__restrict__ 
         }
         for (int l = 0; l < SA_SITE_MAX_LETTERS; l++) o.prob[l] = total > 0 ? (double) o.units[l] / (double) total : 0.0;
         o.entropy = eu == 0 ? 0.0 : ((double) eu * 9.094947017729282e-13 / (double) kc) / -2.0;   // (2^-40)
-        char r = 0;
-        if (kc > 0) {
-            r = have_ref ? ref[g] : 'N';
-            if (r >= 'a' && r <= 'z') r = (char) (r - 'a' + 'A');
-        }
-        o.ref = r;
+        o.ref = kc > 0 ? sa_acc_ref_letter(ref, g) : (char) 0;
         for (int q2 = 0; q2 < 7; q2++) o.pad[q2] = 0;
         out[w++] = o;
     }
@@ -531,70 +437,28 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_emit(const int *__restrict__ 
 
 extern "C" int sa_position_profile_finish(sa_position_profile_t *t, const char *const *ref_by_contig, sa_profile_site_t **sites_out,
                                           int64_t *n_out, uint32_t *letters_seen_out, double *kernel_ms_out) {
-    if (!t || !sites_out || !n_out) return SA_EINVAL;
-    *sites_out = nullptr;
-    *n_out = 0;
     if (letters_seen_out) *letters_seen_out = 0;
-    if (kernel_ms_out) *kernel_ms_out = 0.0;
-    if (ref_by_contig)
-        for (long long c = 0; c < t->n_contigs; c++)
-            if (!ref_by_contig[c]) return SA_EINVAL;
-    std::lock_guard<std::mutex> g(t->mu);
-    if (t->poisoned) return SA_ESTATE;
-    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
-    const size_t ns = (size_t) t->n_slots, nb = (ns + PF_SPAN - 1) / PF_SPAN;
-    int rc = SA_OK;
-    SaLayout L;   // [block sums | sums before each block | block counts | counts before each block | reference letters]
-    const size_t o_sum = L.add(8 * nb), o_before = L.add(8 * (nb + 1)), o_cnt = L.add(8 * nb), o_off = L.add(8 * (nb + 1)),
-                 o_ref = L.add(ref_by_contig ? ns : 1);
-    char *d = nullptr;
-    sa_profile_site_t *d_out = nullptr, *host = nullptr;
-    long long n_kept = 0;
+    if (const int rc = sa_acc_finish_args(t, ref_by_contig, sites_out, n_out, kernel_ms_out)) return rc;
+    SaAccEnter in(t);
+    if (in.rc) return in.rc;
     unsigned seen = 0;
-    float ms0 = 0, ms1 = 0;
-    if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, L.end, t->device) != hipSuccess) return SA_ENOMEM;
-    if (ref_by_contig)
-        for (long long c = 0; c < t->n_contigs; c++) {
-            const size_t len = (size_t) t->clen[(size_t) c];
-            if (len) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_ref + t->coff[(size_t) c], ref_by_contig[c], len, hipMemcpyHostToDevice, 0));
-        }
-    SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
-    hipLaunchKernelGGL(k_pf_block_sums, dim3((unsigned) nb), dim3(PF_THREADS), 0, 0, (const int *) t->diff(), (long long) ns, (long long *) (d + o_sum));
-    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const long long *) (d + o_sum), (long long *) (d + o_before), (long long) nb);
-    hipLaunchKernelGGL(k_pf_mark, dim3((unsigned) nb), dim3(PF_THREADS), 0, 0, (const int *) t->diff(), (const unsigned long long *) t->acc(), t->S,
-                       (long long) ns, (const long long *) (d + o_before), (long long *) (d + o_cnt));
-    hipLaunchKernelGGL(k_pf_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const long long *) (d + o_cnt), (long long *) (d + o_off), (long long) nb);
-    SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
-    SA_HIP_GOTO_DONE(hipGetLastError());
-    SA_HIP_GOTO_DONE(hipMemcpy(&n_kept, d + o_off + 8 * nb, 8, hipMemcpyDeviceToHost));
-    SA_HIP_GOTO_DONE(hipMemcpy(&seen, t->seen(), 4, hipMemcpyDeviceToHost));
-    SA_HIP_GOTO_DONE(hipEventElapsedTime(&ms0, t->e0, t->e1));
-    host = (sa_profile_site_t *) calloc((size_t) (n_kept > 0 ? n_kept : 1), sizeof(sa_profile_site_t));
-    if (!host) { rc = SA_ENOMEM; goto done; }
-    if (n_kept > 0) {
-        if (g_sa_pool.get(SaPool::DEVICE, (void **) &d_out, sizeof(sa_profile_site_t) * (size_t) n_kept, t->device) != hipSuccess) {
-            d_out = nullptr;
-            rc = SA_ENOMEM;
-            goto done;
-        }
-        SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
-        hipLaunchKernelGGL(k_pf_emit, dim3((unsigned) nb), dim3(PF_THREADS), 0, 0, (const int *) t->diff(), (const unsigned long long *) t->acc(), t->S,
-                           t->n_alpha, (long long) ns, (const long long *) (d + o_before), (const long long *) (d + o_off),
-                           (const long long *) t->d_coff, (int) t->n_contigs, (const char *) (d + o_ref), ref_by_contig ? 1 : 0, d_out);
-        SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
-        SA_HIP_GOTO_DONE(hipGetLastError());
-        SA_HIP_GOTO_DONE(hipMemcpy(host, d_out, sizeof(sa_profile_site_t) * (size_t) n_kept, hipMemcpyDeviceToHost));
-        SA_HIP_GOTO_DONE(hipEventElapsedTime(&ms1, t->e0, t->e1));
-    }
-    if (kernel_ms_out) *kernel_ms_out = (double) ms0 + (double) ms1;
-    if (letters_seen_out) *letters_seen_out = seen;
-    *sites_out = host;
-    *n_out = n_kept;
-    host = nullptr;
-done:
-    if (rc != SA_OK) (void) hipStreamSynchronize(0);
-    g_sa_pool.put(SaPool::DEVICE, d);
-    if (d_out) g_sa_pool.put(SaPool::DEVICE, d_out);
-    free(host);
+    if (hipMemcpy(&seen, t->seen(), 4, hipMemcpyDeviceToHost) != hipSuccess) return SA_ENODEVICE;
+    const size_t nb = sa_acc_blocks(t), o_before = sa_up256(8 * nb);   // the call's own scratch: [block sums | sums before each block]
+    const int *diff = t->diff();
+    const unsigned long long *acc = t->acc();
+    const int rc = sa_acc_finish(
+        t, ref_by_contig, o_before + 8 * (nb + 1),
+        [&](unsigned grid, char *own, long long *blk_cnt) {
+            long long *blk_sum = (long long *) own, *blk_before = (long long *) (own + o_before);
+            hipLaunchKernelGGL(k_pf_block_sums, dim3(grid), dim3(SA_ACC_THREADS), 0, 0, diff, t->n_slots, blk_sum);
+            hipLaunchKernelGGL(k_acc_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const long long *) blk_sum, blk_before, (long long) grid);
+            hipLaunchKernelGGL(k_pf_mark, dim3(grid), dim3(SA_ACC_THREADS), 0, 0, diff, acc, t->S, t->n_slots, (const long long *) blk_before, blk_cnt);
+        },
+        [&](unsigned grid, char *own, const long long *blk_off, const char *ref, sa_profile_site_t *d_out) {
+            hipLaunchKernelGGL(k_pf_emit, dim3(grid), dim3(SA_ACC_THREADS), 0, 0, diff, acc, t->S, t->n_alpha, t->n_slots,
+                               (const long long *) (own + o_before), blk_off, (const long long *) t->d_coff, (int) t->n_contigs, ref, d_out);
+        },
+        sites_out, n_out, kernel_ms_out);
+    if (rc == SA_OK && letters_seen_out) *letters_seen_out = seen;
     return rc;
 }

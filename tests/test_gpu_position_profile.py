@@ -70,14 +70,14 @@ def _shape_jobs(k, n_alpha, seed):
     return jobs
 
 
-def _expected(calls, alphabet, k, refs):
+def _expected(calls, alphabet, k, refs, names=NAMES):
     P = ref.Profile(term=_term)
     for jobs in calls:
         for j in jobs:
             if len(j["x"]):
-                P.add_file(ref.rows_of_records(NAMES[j["contig"]], j["pos0"], j["pos_sign"], k, alphabet, j["x"].tolist(),
+                P.add_file(ref.rows_of_records(names[j["contig"]], j["pos0"], j["pos_sign"], k, alphabet, j["x"].tolist(),
                                                j["kmer_id"].tolist(), j["prob_e7"].tolist()), j["pos_sign"] > 0)
-    return P.finish(alphabet, NAMES, refs), P.letters_seen(alphabet)
+    return P.finish(alphabet, names, refs), P.letters_seen(alphabet)
 
 
 def _add(t, jobs, flags=0):
@@ -233,6 +233,47 @@ def test_create_refuses_what_it_cannot_hold():
         with pytest.raises(sa.SaError) as e:
             sa.PositionProfile(m, lens)
         assert e.value.code == -1
+
+
+@pytest.mark.parametrize("last_len", [2038, 2039])
+def test_empty_contigs_and_a_span_that_ends_on_an_extra_slot(last_len):
+    """2048 slots (the positions and one more per contig): one block of finish; 2049: a second block of one slot.  A k-mer ends on
+    the last position of contig 3, so the -1 of its span lies on that contig's extra slot; no extra slot and no empty contig may
+    get a site."""
+    m, alphabet, k, _jobs, _r, _e = _shapes("acgt5")
+    lens = [0, 5, 0, last_len, 0]
+    assert sum(lens) + len(lens) == (2048 if last_len == 2038 else 2049)
+    rng = np.random.default_rng(43)
+    J = lambda *a: _job(*a, rng=rng, n_kmers=4 ** k)
+    jobs = [J(1, 0, 1, [0]),                                            # all of contig 1
+            J(3, last_len - (3 + k), 1, [0, 1, 3]),                     # forward, the last letter on the contig's last position
+            J(3, k + 1, -1, [0, 2])]                                    # backward, the last letter on position 0
+    names = ["c%d" % c for c in range(len(lens))]
+    refs = ["", "acGTn", "", "".join(rng.choice(list("ACGTacgtN"), size=last_len)), ""]
+    t = sa.PositionProfile(m, lens)
+    _add(t, jobs)
+    got, seen = t.finish(refs)
+    t.close()
+    _check(got, seen, *_expected([jobs], alphabet, k, refs, names), 4)
+    where = list(zip(got["contig"].tolist(), got["pos"].tolist()))
+    assert where[:5] == [(1, p) for p in range(5)] and where[5] == (3, 0) and where[-1] == (3, last_len - 1)
+    assert all(c in (1, 3) and p < lens[c] for c, p in where) and got["read_count"].min() == 1
+
+
+def test_a_table_whose_contigs_are_all_empty():
+    m, alphabet, k, _jobs, _r, _e = _shapes("acgt5")
+    t = sa.PositionProfile(m, [0, 0])
+    assert [len(t.finish()[0]), t.finish(["", ""])[1]] == [0, 0]
+    _add(t, [])                                                         # no record: nothing to refuse
+    t.checkpoint()
+    t.rollback()
+    for contig in (0, 1):
+        with pytest.raises(sa.SaError) as e:
+            _add(t, [_job(contig, 0, 1, [0], kmer_id=[0], prob_e7=[10 ** 7])])
+        assert e.value.code == -1                                       # SA_EINVAL: there is no position 0
+    got, seen = t.finish()
+    assert len(got) == 0 and seen == 0
+    t.close()
 
 
 # ---- chained onto a real batch ------------------------------------------------------------------------------------------------

@@ -197,6 +197,39 @@ def test_a_site_outside_its_contig_is_refused_and_nothing_is_added():
     t.close()
 
 
+@pytest.mark.parametrize("last_len", [2043, 2044])
+def test_empty_contigs_around_a_last_slot_that_is_reported(last_len):
+    """2048 positions: one block of finish, whose last slot is reported; 2049: a second block of one slot, reported.  The empty
+    contigs share their offset with the next one, and no site may be given to them."""
+    lens = [0, 5, 0, last_len, 0]
+    assert sum(lens) == (2048 if last_len == 2043 else 2049)
+    vals = _values(np.random.default_rng(41), 4)
+    calls = [[(1, 0, 0, 0, 1, tuple(vals[0].tolist())), (1, 4, 0, 1, 1, tuple(vals[1].tolist()))],
+             [(3, 0, 1, 0, 0, tuple(vals[2].tolist())), (3, last_len - 1, 1, 0, 0, tuple(vals[3].tolist()))]]
+    refs = ["", "acGTn", "", "C" * last_len, ""]
+    t = sa.SnpMarginals(lens)
+    for call in calls:
+        _add(t, call)
+    got = t.finish(1, refs)
+    t.close()
+    _check(got, ref.finish(ref.accumulate(calls), 1, refs))
+    assert list(zip(got["contig"].tolist(), got["pos"].tolist())) == [(1, 0), (1, 4), (3, 0), (3, last_len - 1)]
+
+
+def test_a_table_whose_contigs_are_all_empty():
+    t = sa.SnpMarginals([0, 0])
+    assert len(t.finish()) == 0 and len(t.finish(1, ["", ""])) == 0
+    t.add_sites(0, np.zeros(0, dtype=_capi.SNP_SITE_DTYPE), 1)     # no row: nothing to refuse
+    t.checkpoint()
+    t.rollback()
+    for contig in (0, 1):
+        with pytest.raises(sa.SaError) as e:
+            _add(t, [(contig, 0, 0, 0, 1, (0.25, 0.25, 0.25, 0.25))])
+        assert e.value.code == -1                                   # SA_EINVAL: there is no position 0
+    assert len(t.finish()) == 0
+    t.close()
+
+
 # ---- chained onto a real batch ------------------------------------------------------------------------------------------------
 STEP = 5
 K = 6
