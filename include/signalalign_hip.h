@@ -785,6 +785,65 @@ int sa_position_profile_write(const char *path, const char *alphabet, uint32_t l
                               const sa_profile_site_t *sites, int64_t n);
 int64_t sa_profile_entropy_term(int64_t units);   /* test hook, host */
 
+/* ---- Deviation of every read's alignment from its guide ------------------------------------------------------------------------
+ * Replaces validateSignalAlignment.py over the embedded full table of every read: analyze_event_skips
+ * (src/signalalign/visualization/plot_labelled_read.py:364-472), the histogram of absolute differences
+ * (validateSignalAlignment.py:178-192) and flag_large_gaps (:103-142), from the records a batch leaves in HBM.  All of it in the
+ * job's own coordinates (sa_pair_t): x the k-mer index in the job's ref, y the event index, the job's anchors the guide.
+ *   best_x[y]     of the records with event index y the x of the one with the largest prob_e7, among equal prob_e7 the largest x; an
+ *                 event with a record is ALIGNED
+ *   guide[y]      anchor_x of the anchor with anchor_y == y; else (a + b) / 2 in integer division of the last anchor before and the
+ *                 first anchor after y, or the one of the two that exists
+ *   diff, abs     best_x[y] - guide[y] and its absolute value, of aligned events
+ *   on the path   the MEA path handed in for the job holds a pair with that event_idx (its position is not looked at)
+ *   histogram     bucket min(abs / bucket_size, n_buckets - 1), once per aligned event
+ *   sets          the maximal runs of aligned events, in ascending y, with abs > threshold; events without records are skipped and
+ *                 end no run.  Per set the first and last event, the count, the largest abs (peak), the largest abs among its events
+ *                 on the path (mea_peak, 0 without one) and center_event = (sum of its y) / count in integer division
+ *   per job       status 0, SA_DEV_NO_GUIDE (no anchors: every count 0) or SA_DEV_NO_RECORDS (anchors and no record); max_event is
+ *                 the smallest y that attains max_abs (0 without aligned events)
+ * Three deliberate differences from the script: ties between equal posteriors go to the largest x (the script leaves them to row
+ * order; here the choice is an integer atomic maximum); a set still open when the read ends is reported, with open_end = 1 (the
+ * script's loop closes a set only on the next unflagged event and drops it: a caller who wants the script's list drops those
+ * sets); events are named by y (the script's EVENT_INDEX ranks raw starts of three tables of the fast5).
+ * Everything is an integer, so the outputs do not depend on launch shape or order, and SA_DEV_WINDOW gives the same bits.
+ * All argument checks run before any device work: threshold < 0, bucket_size < 1, n_buckets outside [1, 1024], an anchor_y that is
+ * not strictly increasing or outside [0, 2^31), an anchor_x outside [0, 2^28), n_events outside [0, 2^28], a record or an MEA event
+ * outside [0, n_events), a record's x outside [0, 2^28), a prob_e7 outside [0, 1e7]: SA_EINVAL.  More than 2^31 - 1 events in one
+ * call: SA_EUNSUPPORTED.  Without a GPU: SA_ENODEVICE. */
+#define SA_DEV_NO_GUIDE 1
+#define SA_DEV_NO_RECORDS 2
+#define SA_DEV_DIRECT 1u   /* every record is a global atomic maximum: no LDS window.  The default: on a batch of 2000 reads of 5000
+                            * events the window did not beat it (profiles/guide_deviation.json), so the flag only names it */
+#define SA_DEV_EVENTS 2u   /* *events_out: one sa_deviation_event_t per event of every job */
+#define SA_DEV_WINDOW 4u   /* the records' maxima go through a window in LDS first (the A/B of SA_DEV_DIRECT; not together with it) */
+#define SA_DEV_MAX_BUCKETS 1024
+typedef struct sa_deviation_params { int32_t threshold, bucket_size, n_buckets; } sa_deviation_params_t;   /* NULL: {10, 5, 64} */
+typedef struct sa_deviation_job { const int64_t *anchor_x, *anchor_y; int64_t n_anchors, n_events; } sa_deviation_job_t;
+typedef struct sa_deviation_read { int32_t status, n_sets; int64_t set_first; int64_t n_aligned, n_flagged, n_on_mea, sum_abs;
+                                   int32_t max_abs, max_abs_mea, max_event, pad; } sa_deviation_read_t;   /* 64 bytes */
+typedef struct sa_deviation_set { int32_t first_event, last_event, count, peak, mea_peak, center_event, open_end, pad; } sa_deviation_set_t;
+typedef struct sa_deviation_event { int32_t best_x, guide, diff; uint32_t flags; } sa_deviation_event_t;  /* bit 0 aligned, 1 on MEA, 2 flagged */
+/* Outputs of both calls: reads_out[n_jobs]; *sets_out (malloc'd, sa_free) all jobs' sets back to back, job j's n_sets from
+ * set_first on, *n_sets_out of them; hist_out[n_jobs * n_buckets] and total_hist_out[n_buckets] (the sum of the rows), either may
+ * be NULL; with SA_DEV_EVENTS *events_out (malloc'd, sa_free), the events of every job back to back in job order, an unaligned
+ * event all zeros (without the flag events_out may be NULL and is not touched); kernel_ms_out (may be NULL) the HIP-event time of
+ * the call's kernels.  mea_path / n_mea: per job its MEA path (sa_batch_mea's), or both NULL: no event is on a path.
+ * Chained onto a finished batch: the records are read where the run left them (16-byte and SA_FLAG_PAIRS8 records alike; after
+ * sa_batch_release_device, and with SA_FLAG_EXACT, they go up again).  jobs[j] carries the batch's own anchors and n_events.  Not
+ * run: SA_ESTATE; a SA_FLAG_VC_ROWS batch (rows dropped), n_jobs that is not the batch's, an n_events that differs: SA_EINVAL. */
+int sa_batch_guide_deviation(sa_batch_t *b, const sa_deviation_job_t *jobs, int64_t n_jobs, const sa_mea_pair_t *const *mea_path,
+                             const int64_t *n_mea, const sa_deviation_params_t *p, unsigned flags, sa_deviation_read_t *reads_out,
+                             sa_deviation_set_t **sets_out, int64_t *n_sets_out, int32_t *hist_out, int64_t *total_hist_out,
+                             sa_deviation_event_t **events_out, double *kernel_ms_out);
+/* records from elsewhere: job j's are first[j] .. first[j + 1) (first[0] == 0) of x, y, prob_e7 */
+int sa_guide_deviation_records(const sa_deviation_job_t *jobs, int64_t n_jobs, const int64_t *first /* n_jobs + 1 */, const int32_t *x,
+                               const int32_t *y, const int64_t *prob_e7, const sa_mea_pair_t *const *mea_path, const int64_t *n_mea,
+                               const sa_deviation_params_t *p, int device, unsigned flags, sa_deviation_read_t *reads_out,
+                               sa_deviation_set_t **sets_out, int64_t *n_sets_out, int32_t *hist_out, int64_t *total_hist_out,
+                               sa_deviation_event_t **events_out, double *kernel_ms_out);
+void sa_guide_deviation_release(void); /* returns the scratch the two calls keep between calls */
+
 /* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
  * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
  * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output

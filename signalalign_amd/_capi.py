@@ -79,6 +79,26 @@ class ProfileJobMap(C.Structure):
 
 
 PROFILE_DIRECT = 1
+
+
+class DeviationParams(C.Structure):
+    """sa_deviation_params_t (include/signalalign_hip.h)"""
+    _fields_ = [("threshold", C.c_int32), ("bucket_size", C.c_int32), ("n_buckets", C.c_int32)]
+
+
+class DeviationJob(C.Structure):
+    """sa_deviation_job_t (include/signalalign_hip.h)"""
+    _fields_ = [("anchor_x", C.POINTER(C.c_int64)), ("anchor_y", C.POINTER(C.c_int64)), ("n_anchors", C.c_int64), ("n_events", C.c_int64)]
+
+
+DEV_NO_GUIDE, DEV_NO_RECORDS = 1, 2
+DEV_DIRECT, DEV_EVENTS, DEV_WINDOW = 1, 2, 4
+DEVIATION_READ_DTYPE = np.dtype([("status", "<i4"), ("n_sets", "<i4"), ("set_first", "<i8"), ("n_aligned", "<i8"), ("n_flagged", "<i8"),
+                                 ("n_on_mea", "<i8"), ("sum_abs", "<i8"), ("max_abs", "<i4"), ("max_abs_mea", "<i4"), ("max_event", "<i4"),
+                                 ("pad", "<i4")])
+DEVIATION_SET_DTYPE = np.dtype([("first_event", "<i4"), ("last_event", "<i4"), ("count", "<i4"), ("peak", "<i4"), ("mea_peak", "<i4"),
+                                ("center_event", "<i4"), ("open_end", "<i4"), ("pad", "<i4")])
+DEVIATION_EVENT_DTYPE = np.dtype([("best_x", "<i4"), ("guide", "<i4"), ("diff", "<i4"), ("flags", "<u4")])
 PROFILE_SITE_DTYPE = np.dtype([("pos", "<i8"), ("contig", "<i4"), ("read_count", "<i4"), ("kmer_count", "<i8"), ("entropy_units", "<i8"),
                                ("units", "<i8", (SITE_MAX_LETTERS,)), ("entropy", "<f8"), ("prob", "<f8", (SITE_MAX_LETTERS,)),
                                ("ref", "S1"), ("pad", "S1", (7,))])
@@ -196,7 +216,8 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals",
            "sa_position_profile_create", "sa_position_profile_destroy", "sa_position_profile_add_batch", "sa_position_profile_add_records",
            "sa_position_profile_checkpoint", "sa_position_profile_rollback", "sa_position_profile_finish", "sa_position_profile_write",
-           "sa_profile_entropy_term", "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
+           "sa_profile_entropy_term", "sa_batch_guide_deviation", "sa_guide_deviation_records", "sa_guide_deviation_release",
+           "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet", "sa_hdp_state_vs_gaussian",
            "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
@@ -398,6 +419,12 @@ def lib():
     L.sa_position_profile_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int64]
     L.sa_profile_entropy_term.argtypes = [C.c_int64]
     L.sa_profile_entropy_term.restype = C.c_int64
+    dev_tail = [C.POINTER(DeviationParams), C.c_uint, C.c_void_p, C.POINTER(C.c_void_p), ip, C.POINTER(C.c_int32), ip, C.POINTER(C.c_void_p), dp]
+    L.sa_batch_guide_deviation.argtypes = [C.c_void_p, C.POINTER(DeviationJob), C.c_int64, C.POINTER(C.c_void_p), ip] + dev_tail
+    L.sa_guide_deviation_records.argtypes = ([C.POINTER(DeviationJob), C.c_int64, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ip,
+                                              C.POINTER(C.c_void_p), ip] + dev_tail[:1] + [C.c_int] + dev_tail[1:])
+    L.sa_guide_deviation_release.argtypes = []
+    L.sa_guide_deviation_release.restype = None
     L.sa_snp_group_sites.argtypes = [ip, dp, C.c_int64, C.c_int64, C.c_int, ip, ip]
     L.sa_snp_substitute_sites.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, ip, C.c_int64, C.c_char, C.c_char_p]
     L.sa_snp_apply_calls.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_char_p]
@@ -2075,6 +2102,88 @@ def position_profile_write(path, alphabet, letters_seen, contig_names, sites):
 
 def profile_entropy_term(units):
     return int(lib().sa_profile_entropy_term(int(units)))
+
+
+def _deviation_call(jobs, mea, params, flags, call):
+    """what batch_guide_deviation and guide_deviation_records share: the argument arrays, the call, the outputs as a dict"""
+    jobs = list(jobs)
+    n = len(jobs)
+    arr = (DeviationJob * max(n, 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        ax = np.ascontiguousarray(j["ax"], dtype=np.int64)
+        ay = np.ascontiguousarray(j["ay"], dtype=np.int64)
+        if len(ax) != len(ay):
+            raise ValueError("a job's ax and ay have one entry per anchor")
+        keep.append((ax, ay))
+        arr[i] = DeviationJob(_ip(ax), _ip(ay), len(ax), int(j["n_events"]))
+    paths, n_mea = None, None
+    if mea is not None:
+        if len(mea) != n:
+            raise ValueError("mea: one path per job")
+        paths = (C.c_void_p * max(n, 1))()
+        n_mea = np.zeros(max(n, 1), dtype=np.int64)
+        for i, m in enumerate(mea):
+            m = m[0] if isinstance(m, tuple) else m          # (Batch.mea() returns (path, sum, status) per job)
+            m = np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 2)
+            keep.append(m)
+            paths[i], n_mea[i] = m.ctypes.data, len(m)
+    p = None
+    if params is not None:
+        p = params if isinstance(params, DeviationParams) else DeviationParams(*[int(v) for v in params])
+    nb = p.n_buckets if p is not None else 64
+    reads = np.zeros(n, dtype=DEVIATION_READ_DTYPE)
+    hist = np.zeros((n, max(nb, 1)), dtype=np.int32)
+    total = np.zeros(max(nb, 1), dtype=np.int64)
+    sets_p, ev_p, n_sets, kms = C.c_void_p(), C.c_void_p(), np.zeros(1, dtype=np.int64), C.c_double()
+    tail = (C.byref(p) if p is not None else None, int(flags), reads.ctypes.data, C.byref(sets_p), _ip(n_sets),
+            hist.ctypes.data_as(C.POINTER(C.c_int32)), _ip(total), C.byref(ev_p) if flags & DEV_EVENTS else None, C.byref(kms))
+    call(arr, n, paths, _ip(n_mea) if n_mea is not None else None, tail)
+    sets = np.zeros(int(n_sets[0]), dtype=DEVIATION_SET_DTYPE)
+    if len(sets):
+        C.memmove(sets.ctypes.data, sets_p, sets.nbytes)
+    lib().sa_free(sets_p)
+    out = {"reads": reads, "sets": sets, "hist": hist, "total_hist": total, "kernel_ms": kms.value}
+    if flags & DEV_EVENTS:
+        ev = np.zeros(sum(int(j["n_events"]) for j in jobs), dtype=DEVIATION_EVENT_DTYPE)
+        if len(ev):
+            C.memmove(ev.ctypes.data, ev_p, ev.nbytes)
+        lib().sa_free(ev_p)
+        out["events"] = ev
+    return out
+
+
+def batch_guide_deviation(batch, jobs, mea=None, params=None, flags=0):
+    """sa_batch_guide_deviation, chained onto a finished Batch: how far every event's best-posterior position lies from the guide.
+    jobs: per job a dict with ax, ay (the job's anchors) and n_events -- the batch's own job dicts serve when they carry n_events,
+    else len(events) is taken; mea: per job its MEA path ([n, 2] of (x, y), or Batch.mea()'s tuples), or None;
+    params: (threshold, bucket_size, n_buckets), None for (10, 5, 64).  Returns a dict: reads (DEVIATION_READ_DTYPE), sets
+    (DEVIATION_SET_DTYPE, job j's at reads["set_first"][j]), hist [n_jobs, n_buckets], total_hist, kernel_ms and, with DEV_EVENTS,
+    events (DEVIATION_EVENT_DTYPE, job after job)."""
+    jobs = [j if "n_events" in j else dict(ax=j["ax"], ay=j["ay"], n_events=len(j["events"])) for j in jobs]
+
+    def call(arr, n, paths, n_mea, tail):
+        _chk(lib().sa_batch_guide_deviation(batch._h, arr, n, paths, n_mea, *tail), "sa_batch_guide_deviation")
+    return _deviation_call(jobs, mea, params, flags, call)
+
+
+def guide_deviation_records(jobs, first, x, y, prob_e7, mea=None, params=None, device=0, flags=0):
+    """sa_guide_deviation_records: the same from records the caller holds, job j's being first[j] .. first[j + 1) of x, y, prob_e7"""
+    first = np.ascontiguousarray(first, dtype=np.int64)
+    x = np.ascontiguousarray(x, dtype=np.int32)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    prob_e7 = np.ascontiguousarray(prob_e7, dtype=np.int64)
+    if len(first) != len(jobs) + 1 or not (len(x) == len(y) == len(prob_e7)) or int(first[-1]) != len(x):
+        raise ValueError("first: n_jobs + 1 offsets into x, y and prob_e7, which have one entry per record")
+
+    def call(arr, n, paths, n_mea, tail):
+        _chk(lib().sa_guide_deviation_records(arr, n, _ip(first), _i32p(x), _i32p(y), _ip(prob_e7), paths, n_mea, tail[0], int(device),
+                                              *tail[1:]), "sa_guide_deviation_records")
+    return _deviation_call(jobs, mea, params, flags, call)
+
+
+def guide_deviation_release():
+    lib().sa_guide_deviation_release()
 
 
 def snp_group_sites(pos, delta, window=6, keep_last=True):

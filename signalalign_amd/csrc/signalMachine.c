@@ -115,6 +115,16 @@ static void usage(void) {
                     "                  is aligned once, with X at the listed sites inside its window, and the same table comes out\n"
                     "--snp-reference-out <fasta> (with --snp-sites): the -f reference with the called base written in at every site\n"
                     "                  whose call differs from it, records and line width as in -f\n");
+    fprintf(stderr, "--guide-deviation <file>: how far every read's alignment lies from its guide, made on the GPU from the records of\n"
+                    "                  every batch (validateSignalAlignment.py): per read strand an R line (label, strand, status,\n"
+                    "                  n_aligned, n_flagged, n_on_mea, mean_abs, max_abs, max_abs_mea, max_event, n_sets), an H line (the\n"
+                    "                  histogram of |best position - guide position| in buckets of 5) and an S line per run of events\n"
+                    "                  that lie farther than the threshold from the guide; a T line with the summed histogram at the\n"
+                    "                  end.  Single reads and --batch; the posteriors file may be '-'.  The MEA paths are computed as\n"
+                    "                  with --mea.  Not with -t/-c, --train-*, --snp-step or --snp-sites\n");
+    fprintf(stderr, "--guide-deviation-threshold <n>: an event is flagged when it lies more than n positions from the guide (default 10)\n");
+    fprintf(stderr, "--guide-deviation-events <file> (with --guide-deviation): one row per aligned event: label, strand, event_index,\n"
+                    "                  reference_index, guide_reference_index, diff, on_mea, flagged\n");
     fprintf(stderr, "--position-profile <file> (with --batch): the pile-up of all reads' template alignments per position of the -f\n"
                     "                  reference, summed on the GPU and written at the end of the run: contig, position, reference letter,\n"
                     "                  entropy of the covering posteriors, k-mer rows and reads covering it, and the share of posterior\n"
@@ -423,6 +433,11 @@ typedef struct {
     int64_t *snp_lens, snp_n_contigs;
     const char *prof_path;          /* --position-profile: the per-position profile of the run's template batches, on the GPU */
     sa_position_profile_t *prof_tab;
+    /* --guide-deviation: every strand batch's deviation from its guide (sa_batch_guide_deviation), written read by read */
+    const char *dev_path, *dev_events_path;
+    FILE *dev_fh, *dev_events_fh;
+    sa_deviation_params_t dev_params;
+    int64_t dev_total[SA_DEV_MAX_BUCKETS];   /* the H lines written so far, summed: the T line */
     const void *reads0;
     const char *fwd_ref, *bwd_ref;
     sa_params_t p;
@@ -1143,6 +1158,13 @@ typedef struct {
     int p8;                     /* the batch holds 8-byte records (SA_FLAG_PAIRS8): path 0, the reference's k-mer at x */
     sa_site_call_t **calls;     /* --site-calls / --site-calls-aggregate only */
     int64_t *n_calls;
+    /* --guide-deviation only: [job] summaries and histogram rows, all jobs' sets, and (--guide-deviation-events) all jobs' events
+     * back to back, job j's from dev_ev_first[j] on */
+    sa_deviation_read_t *dev_reads;
+    sa_deviation_set_t *dev_sets;
+    int32_t *dev_hist;
+    sa_deviation_event_t *dev_events;
+    int64_t *dev_ev_first;
 } strand_result_t;
 
 /* a result of n_jobs jobs, filled as far as its batch got */
@@ -1155,6 +1177,8 @@ static void strand_result_free(strand_result_t *sr, int64_t n_jobs) {
     }
     free(sr->pairs); free(sr->n_pairs); free(sr->mea); free(sr->n_mea); free(sr->all_n); free(sr->all_sum);
     free(sr->calls); free(sr->n_calls);
+    free(sr->dev_reads); free(sr->dev_hist); free(sr->dev_ev_first);
+    sa_free(sr->dev_sets); sa_free(sr->dev_events);
     memset(sr, 0, sizeof(*sr));
 }
 
@@ -1780,6 +1804,62 @@ static int profile_add_batch(const align_slice_t *c, sa_batch_t *b) {
     return rc;
 }
 
+/* --guide-deviation: the finished batch of strand s against its own jobs' anchors, with the MEA paths just made of it */
+static int deviation_of_batch(align_slice_t *c, int s, sa_batch_t *b) {
+    const run_t *R = c->sl.R;
+    strand_result_t *sr = &c->sr[s];
+    const int64_t n = c->sl.n_ok;
+    sa_deviation_job_t *dj = xalloc(n, sizeof(*dj), 1);
+    sr->dev_ev_first = xalloc(n + 1, sizeof(int64_t), 1);
+    for (int64_t j = 0; j < n; j++) {
+        const sa_job_t *q = &c->bj[j];
+        dj[j] = (sa_deviation_job_t) {q->anchor_x, q->anchor_y, q->n_anchors, q->n_events};
+        sr->dev_ev_first[j + 1] = sr->dev_ev_first[j] + q->n_events;
+    }
+    sr->dev_reads = xalloc(n, sizeof(sa_deviation_read_t), 1);
+    sr->dev_hist = xalloc(n * R->dev_params.n_buckets, sizeof(int32_t), 1);
+    int64_t n_sets = 0;
+    const int rc = sa_batch_guide_deviation(b, dj, n, (const sa_mea_pair_t *const *) sr->mea, sr->n_mea, &R->dev_params,
+                                            R->dev_events_path ? SA_DEV_EVENTS : 0u, sr->dev_reads, &sr->dev_sets, &n_sets, sr->dev_hist, NULL,
+                                            R->dev_events_path ? &sr->dev_events : NULL, NULL);
+    free(dj);
+    return rc;
+}
+
+/* ... and the lines of job j's strand s, in read order (render_slice).  Events are printed as the TSV's event_index column prints
+ * them, positions as its reference_index maps x; diff stays in the job's coordinates. */
+static void write_deviation(run_t *R, const read_t *rd, int s, const strand_result_t *sr, int64_t j) {
+    const sa_deviation_read_t *r = &sr->dev_reads[j];
+    const int nb = R->dev_params.n_buckets;
+    const int64_t lo = rd->st[s].lo;
+    const char *strand = s == 0 ? "t" : "c";
+    char mean[400];
+    mean[sa_format_f6(mean, r->n_aligned ? (double) r->sum_abs / (double) r->n_aligned : 0.0)] = 0;
+    fprintf(R->dev_fh, "R\t%s\t%s\t%d\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%s\t%d\t%d\t%" PRId64 "\t%d\n", rd->label, strand, r->status,
+            r->n_aligned, r->n_flagged, r->n_on_mea, mean, r->max_abs, r->max_abs_mea, r->n_aligned ? lo + r->max_event : (int64_t) -1, r->n_sets);
+    fprintf(R->dev_fh, "H\t%s\t%s", rd->label, strand);
+    for (int q = 0; q < nb; q++) {
+        fprintf(R->dev_fh, "\t%d", sr->dev_hist[j * nb + q]);
+        R->dev_total[q] += sr->dev_hist[j * nb + q];
+    }
+    fputc('\n', R->dev_fh);
+    for (int64_t i = 0; i < r->n_sets; i++) {
+        const sa_deviation_set_t *t = &sr->dev_sets[r->set_first + i];
+        fprintf(R->dev_fh, "S\t%s\t%s\t%" PRId64 "\t%" PRId64 "\t%d\t%d\t%d\t%" PRId64 "\t%d\n", rd->label, strand, lo + t->first_event,
+                lo + t->last_event, t->count, t->peak, t->mea_peak, lo + t->center_event, t->open_end);
+    }
+    if (!R->dev_events_fh) return;
+    const int64_t ref_len = (int64_t) strlen(rd->st[s].target), ref_len_kmers = ref_len - R->sm[s].k, off = rd->st[s].r_shift;
+    const sa_deviation_event_t *ev = sr->dev_events + sr->dev_ev_first[j];
+    for (int64_t y = 0; y < sr->dev_ev_first[j + 1] - sr->dev_ev_first[j]; y++) {
+        if (!(ev[y].flags & 1u)) continue;
+        fprintf(R->dev_events_fh, "%s\t%s\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%d\t%d\t%d\n", rd->label, strand, lo + y,
+                adjust_ref(ev[y].best_x, off, ref_len_kmers, ref_len, s == 0, rd->forward),
+                adjust_ref(ev[y].guide, off, ref_len_kmers, ref_len, s == 0, rd->forward), ev[y].diff, (int) ((ev[y].flags >> 1) & 1u),
+                (int) ((ev[y].flags >> 2) & 1u));
+    }
+}
+
 /* Creates, runs and harvests the batch of strand s of an alignment slice into c->sr[s]; whatever it returns, the result is one
  * strand_result_free can take.
  * -s 1 prints only the rows whose reference k-mer holds an X: the others stay on the device (SA_FLAG_VC_ROWS), the run's pair
@@ -1791,6 +1871,7 @@ static int profile_add_batch(const align_slice_t *c, sa_batch_t *b) {
  * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker).
  * --train-*: the strand's rows go into the run's k-mer table right after its batch ran, while the records are still in HBM.
  * --mea: the pairs are copied out while the batch still has them on the device for the path step; the batch ends here.
+ * --guide-deviation: the batch is made and harvested as with --mea, and its deviation from the guide follows the paths.
  * Otherwise the batch stays alive for the rendering, which expands its packed records job by job. */
 static int run_strand_batch(align_slice_t *c, int s) {
     const slice_t *sl = &c->sl;
@@ -1798,8 +1879,9 @@ static int run_strand_batch(align_slice_t *c, int s) {
     strand_result_t *sr = &c->sr[s];
     const int64_t n = sl->n_ok;
     const int want_calls = R->site_calls || R->agg_path != NULL;
+    const int want_mea = R->mea || R->dev_path != NULL;
     unsigned flags = want_calls ? SA_FLAG_SITE_CALLS : 0u, p8 = 0u;
-    if (!R->mea && !want_calls) {
+    if (!want_mea && !want_calls) {
         if (R->out_fmt == 1 && !R->want_train && !getenv("SA_CLI_VC_ON_HOST")) flags |= SA_FLAG_VC_ROWS;
         if ((R->out_fmt == 0 || R->out_fmt == 2) && !getenv("SA_CLI_PAIRS16") && !R->prof_tab) p8 = SA_FLAG_PAIRS8;   /* (the profile reads path k-mers) */
     }
@@ -1810,7 +1892,7 @@ static int run_strand_batch(align_slice_t *c, int s) {
         sr->calls = xalloc(n, sizeof(sa_site_call_t *), 1);
         sr->n_calls = xalloc(n, sizeof(int64_t), 1);
     }
-    if (R->mea) {
+    if (want_mea) {
         sr->mea = xalloc(n, sizeof(sa_mea_pair_t *), 1);
         sr->n_mea = xalloc(n, sizeof(int64_t), 1);
     }
@@ -1828,13 +1910,17 @@ static int run_strand_batch(align_slice_t *c, int s) {
         rc = profile_add_batch(c, b);
         if (rc != SA_OK) die("signalMachine: --position-profile: %s", sa_strerror(rc));
     }
-    if (R->mea) {
+    if (want_mea) {
         for (int64_t j = 0; j < n && rc == SA_OK; j++) {
             sa_batch_n_pairs(b, j, &sr->n_pairs[j]);
             sr->pairs[j] = xalloc(sr->n_pairs[j], sizeof(sa_pair_t), 0);
             rc = sa_batch_pairs(b, j, sr->pairs[j], sr->n_pairs[j]);
         }
         if (rc == SA_OK) rc = sa_batch_mea(b, 0, sr->mea, sr->n_mea, NULL, NULL, NULL);
+        if (rc == SA_OK && R->dev_path) {
+            rc = deviation_of_batch(c, s, b);
+            if (rc != SA_OK) die("signalMachine: --guide-deviation: %s", sa_strerror(rc));
+        }
         sa_batch_destroy(b);
         return rc;
     }
@@ -1872,6 +1958,7 @@ static void render_slice(align_slice_t *c) {
             if (R->agg_path) agg_add_read(rd, s, c->tmpl_amb && c->tmpl_amb[j], sr->calls[j], sr->n_calls[j], R->sm[s].k);
         }
         report_read(R, rd, n_all, c->score[j]);
+        for (int s = 0; s < n_strands(R) && R->dev_path; s++) write_deviation(sl->R, rd, s, &c->sr[s], j);
     }
     free(c->tmpl_amb);
     free(c->score);
@@ -2279,6 +2366,7 @@ static void write_position_profile(run_t *R) {
 int main(int argc, char **argv) {
     run_t R;
     memset(&R, 0, sizeof(R));
+    R.dev_params = (sa_deviation_params_t) {10, 5, 64};
     R.train_min_prob = 0.8;   /* probability_threshold, number_of_kmer_assignments, og_model_weight (trainModels.py) */
     R.train_n = 10;
     R.train_weight = 100.0;
@@ -2344,6 +2432,9 @@ int main(int argc, char **argv) {
                                            {"snp-sites", required_argument, 0, 1024},
                                            {"snp-reference-out", required_argument, 0, 1025},
                                            {"position-profile", required_argument, 0, 1026},
+                                           {"guide-deviation", required_argument, 0, 1060},
+                                           {"guide-deviation-threshold", required_argument, 0, 1061},
+                                           {"guide-deviation-events", required_argument, 0, 1062},
                                            {"guide-window", required_argument, 0, 1050},
                                            {"guide-locate", no_argument, 0, 1053},
                                            {"guide-band", required_argument, 0, 1051},
@@ -2407,6 +2498,9 @@ int main(int argc, char **argv) {
             case 1024: R.snp_sites_path = strdup(optarg); break;
             case 1025: R.snp_ref_out = strdup(optarg); break;
             case 1026: R.prof_path = strdup(optarg); break;
+            case 1060: R.dev_path = strdup(optarg); break;
+            case 1061: R.dev_params.threshold = atoi(optarg); break;
+            case 1062: R.dev_events_path = strdup(optarg); break;
             case 1050: guide_window = strdup(optarg); break;
             case 1051: R.guide_band = atoi(optarg); break;
             case 1053: guide_locate = 1; break;
@@ -2510,6 +2604,13 @@ int main(int argc, char **argv) {
         if (R.expect_mode) { usage(); die("signalMachine: --position-profile needs the alignment mode, not -t/-c%s", ""); }
         if (fwd_ref == NULL) { usage(); die("signalMachine: --position-profile needs -f <fasta>%s", ""); }
     }
+    if (R.dev_events_path && !R.dev_path) { usage(); die("signalMachine: --guide-deviation-events needs --guide-deviation <file>%s", ""); }
+    if (R.dev_path) {   /* --guide-deviation: alignment runs that keep every row */
+        if (R.dev_params.threshold < 0) { usage(); die("signalMachine: --guide-deviation-threshold takes n >= 0%s", ""); }
+        if (R.expect_mode) { usage(); die("signalMachine: --guide-deviation needs the alignment mode, not -t/-c%s", ""); }
+        if (R.want_train) { usage(); die("signalMachine: --guide-deviation cannot be combined with --train-*%s", ""); }
+        if (snp_set || R.snp_dir || R.snp_sites_path) { usage(); die("signalMachine: --guide-deviation cannot be combined with --snp-step / --snp-sites%s", ""); }
+    }
     if (snp_set || R.snp_dir || R.snp_sites_path) {   /* --snp-step / --snp-sites: their own outputs only */
         const char *opt = R.snp_sites_path ? "--snp-sites" : "--snp-step";
         if (!R.snp_sites_path && (!snp_set || R.snp_step < 1)) { usage(); die("signalMachine: --snp-step takes a step N >= 1%s", ""); }
@@ -2599,6 +2700,16 @@ int main(int argc, char **argv) {
         const int rc = sa_position_profile_create(&R.prof_tab, R.sm[0].model, R.snp_lens, R.snp_n_contigs, device);
         if (rc != SA_OK) die("signalMachine: --position-profile: %s", sa_strerror(rc));
     }
+    if (R.dev_path) {
+        if (!(R.dev_fh = fopen(R.dev_path, "w"))) die("signalMachine: cannot open output %s", R.dev_path);
+        fprintf(R.dev_fh, "#guide-deviation threshold=%d bucket_size=%d n_buckets=%d; R label strand status n_aligned n_flagged n_on_mea mean_abs "
+                          "max_abs max_abs_mea max_event n_sets; H label strand counts; S label strand first_event last_event count peak "
+                          "mea_peak center_event open_end; T counts\n", R.dev_params.threshold, R.dev_params.bucket_size, R.dev_params.n_buckets);
+        if (R.dev_events_path) {
+            if (!(R.dev_events_fh = fopen(R.dev_events_path, "w"))) die("signalMachine: cannot open output %s", R.dev_events_path);
+            fprintf(R.dev_events_fh, "#label\tstrand\tevent_index\treference_index\tguide_reference_index\tdiff\ton_mea\tflagged\n");
+        }
+    }
     int64_t (*const run_slice)(run_t *, read_t *, int64_t, int) = R.expect_mode ? run_slice_expect : (R.snp_step > 0 || R.snp_sites_path) ? run_slice_snp : run_slice_align;
     slice_t cur = {.R = &R, .reads = reads, .n_reads = n_reads < batch_reads ? n_reads : batch_reads}, nxt;
     slice_prepare(&cur);
@@ -2619,6 +2730,12 @@ int main(int argc, char **argv) {
     write_training(&R, t_model, c_model, device);
     write_snp_marginals(&R);
     write_position_profile(&R);
+    if (R.dev_fh) {   /* --guide-deviation: the histogram summed over the reads written */
+        fprintf(R.dev_fh, "T");
+        for (int q = 0; q < R.dev_params.n_buckets; q++) fprintf(R.dev_fh, "\t%" PRId64, R.dev_total[q]);
+        fputc('\n', R.dev_fh);
+        if (fclose(R.dev_fh) != 0 || (R.dev_events_fh && fclose(R.dev_events_fh) != 0)) die("signalMachine: cannot write %s", R.dev_path);
+    }
     if (R.batch_mode)
         fprintf(stderr, "[signalMachine] batch: %" PRId64 " of %" PRId64 " reads aligned\n", n_reads - n_failed, n_reads);
     if (getenv("SA_CLI_TIMING"))
