@@ -258,6 +258,13 @@ int64_t sa_kmer_id(const sa_model_t *m, const char *kmer); /* impl/nanopore_hdp.
  *                          the emission of the reference's literal-data known answers (tests/stateMachineTests.c:441-698) and of its
  *                          scaled-model whole-read test (:842-852).  Same kernels and conditions as SA_EMISSION_TWO_DIST. */
 #define SA_EMISSION_TWO_DIST_SCALED_MODEL 2
+/* Event noise under an SA_EMISSION_TWO_DIST* model: every event's noise must be a finite number greater than zero; under
+ * SA_EMISSION_TWO_DIST zero is legal too and is replaced by 1e-9 as the reference does (impl/stateMachine.c:619-621).  NaN, +-inf, a
+ * negative value, and zero under SA_EMISSION_TWO_DIST_SCALED_MODEL give the reference a NaN total and no pairs; here sa_batch_create*
+ * (and sa_expect_batch / sa_align_batch through it) refuses the whole batch with SA_EINVAL and one line on stderr that names the
+ * job and the event, before anything is launched -- the rule of event means that are not finite (sa_batch_run).  A finite noise of
+ * any size is legal: 1e300 gives that read a total of -inf and no pairs, and leaves the other reads' results alone.  An
+ * SA_EMISSION_MEAN_ONLY model never reads the noise column. */
 int sa_model_set_emission(sa_model_t *m, int emission);
 /* A Gaussian model with the same alphabet, k-mer length, transitions and emission kind as `m` and the emission table `table5`
  * (5 * A^k doubles, copied): the per-read model the reference gets from emissions_signal_scaleNoise (impl/stateMachine.c:721-741)
@@ -349,7 +356,13 @@ int sa_align_batch(const sa_model_t *m, const sa_params_t *p, const sa_job_t *jo
 /* ---- batched getExpectationsUsingAnchors (impl/pairwiseAligner.c:2164-2184) --------------------
  * trans9_out[j*9 + from*3 + to] and likelihood_out[j] are ADDED to (the caller seeds pseudocounts, as
  * hmmContinuous_getExpectationsHmm does); HDP assignments (to==match && p>=threshold,
- * impl/pairwiseAligner.c:946-968) come back as (reference position, event index) pairs. */
+ * impl/pairwiseAligner.c:946-968) come back as (reference position, event index) pairs.
+ * A read whose total probability is -inf (an event beyond the HDP's grid where the density is zero, an event mean or noise so large
+ * that its squared deviation overflows: every path through the event has probability zero).  The reference adds -inf to the
+ * likelihood and exp(-inf - -inf) = NaN to every transition expectation.  Here every group of ten diagonals whose total is -inf adds
+ * -inf to likelihood_out[j] and NOTHING to trans9_out[j]: the read's likelihood is -inf -- the value to test for -- and its
+ * expectations are those of the tracebacks that ended before the event, all zero when there is none.  The same from the register,
+ * ring and memory-resident kernels; no other read of the batch is touched (tests/test_gpu_outlier_events.py). */
 typedef struct sa_assignment {
     int64_t ref_pos;   /* index into job.ref of the cell's k-mer pointer (cX) */
     int64_t event;     /* index into the job's event array (cY)               */

@@ -616,11 +616,36 @@ static int batch_finish(sa_batch *b) {
     return b->finish_rc;
 }
 
+// The event noise of a two-distribution model's jobs (a record's second value), read where the caller left it -- pageable memory or a
+// page-locked block alike.  upload_model_tables stores n, log n, 1 / n and 1.5 log n of it for every event, and the register kernels
+// evaluate the noise term in every lane, the ones without a k-mer / event pair included: a NaN there is not confined to the event's
+// own row.  The reference gives such a read a NaN total and no pairs (NaN, +-inf, negative; zero without the 1e-9 replacement of
+// impl/stateMachine.c:619-621, i.e. under SA_EMISSION_TWO_DIST_SCALED_MODEL: log 0 - log 0).  Such a batch is refused before anything
+// is launched, in the wording of sa_batch_run's line for event means.  Finite positive values of any size are legal.
+static int event_noise_check(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs) {
+    if (m->emission == SA_EMISSION_MEAN_ONLY || !jobs) return SA_OK;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        const sa_job_t *jb = &jobs[j];
+        if (jb->n_events <= 0 || jb->event_stride < 2 || !jb->events) continue;   // (stride 1: refused where the noise is read)
+        for (int64_t i = 0; i < jb->n_events; i++) {
+            const double n = jb->events[i * jb->event_stride + 1];
+            const bool legal = (n > 0.0 && n < INFINITY) || (n == 0.0 && m->emission == SA_EMISSION_TWO_DIST);
+            if (!legal) {
+                fprintf(stderr, "[signalalign_hip] an event noise (job %lld, event %lld) is not a finite number greater than zero: no result\n",
+                        (long long) j, (long long) i);
+                return SA_EINVAL;
+            }
+        }
+    }
+    return SA_OK;
+}
+
 static int batch_create_impl(sa_batch_t **out, const sa_model_t *m, const sa_params_t *p, const sa_job_t *jobs, int64_t n_jobs,
                              const char *const *ambig, int device, unsigned flags, bool deferred,
                              const sa_noise_scale_t *noise = nullptr, bool noise_scaled = false) {
     if (!out || !m || !p) return SA_EINVAL;
     if (const int rc = sa_device_check(device)) return rc;
+    if (const int rc = event_noise_check(m, jobs, n_jobs)) return rc;
     // Threshold 0 keeps every band cell, the ones of posterior 0 included: the default kernels' candidate filter (forward +
     // backward >= checkpoint maximum + log threshold) has no lower bound then and would pass lanes that hold no cell.  Such a
     // batch takes the reference-ordered kernels with host finalisation, which list a diagonal's cells explicitly.

@@ -507,7 +507,7 @@ __global__ __launch_bounds__(256) EMIT_ATTR void k_emit_hdp(const sa_region_t *_
         const double en = fma(e, inv_var, -cx);
         const double tc = fma(en, T.inv_dx, tc0);
         const int il = max(0, min(cvt_i32_sat(tc), nm2));
-        const unsigned off16 = (unsigned) cy + (unsigned) il * 16u;
+        const unsigned off16 = cvt_u32_sat(cy) + (unsigned) il * 16u;
         u32x4 a, b;
         hdp_load_coef(rs_coef, off16, a, b);
         buf_store_f64(rs_E, (unsigned) i * 8u, fo8, log_tab(value(en, tc, il, off16, true, a, b), LT));
@@ -680,7 +680,7 @@ __global__ __launch_bounds__(256) void k_emit_hdp_ring(const sa_region_t *__rest
                     en_[u] = fma(e_[u], inv_var, -cx);
                     tc_[u] = fma(en_[u], T.inv_dx, tc0);
                     il_[u] = max(0, min(cvt_i32_sat(tc_[u]), nm2));
-                    const unsigned cyu = (unsigned) cy;
+                    const unsigned cyu = cvt_u32_sat(cy);   // (a unit without a cell-path converts zeros or whatever slot 0 holds: as k_emit_hdp)
                     off_[u] = cyu + (unsigned) il_[u] * 16u;
                     a_[u] = u32x4{0u, 0u, 0u, 0u}; b_[u] = a_[u];   // (no cell-path: zeros, as a read beyond the table gives)
                     if (HOT) {
