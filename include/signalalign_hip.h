@@ -798,6 +798,94 @@ int sa_position_profile_write(const char *path, const char *alphabet, uint32_t l
                               const sa_profile_site_t *sites, int64_t n);
 int64_t sa_profile_entropy_term(int64_t units);   /* test hook, host */
 
+/* ---- Device-wide sort of 64-bit keys ---------------------------------------------------------------------------------------------
+ * sorted_out[0 .. n) = keys[0 .. n) ascending (host arrays; the test hook of the sort that sa_call_scores_finish runs on arrays in
+ * HBM): a least-significant-digit radix sort with 8-bit digits over tiles of SA_SORT_TILE keys; a digit in which all keys agree costs
+ * no pass.  n < 0 or a NULL array with n > 0: SA_EINVAL; then SA_ENODEVICE without a GPU; n above 2^31 - 1: SA_EUNSUPPORTED; n == 0
+ * succeeds and writes nothing.  kernel_ms_out (may be NULL): HIP-event time from the first kernel to the last. */
+#define SA_SORT_TILE 4096
+int sa_sort_u64(const uint64_t *keys, int64_t n, uint64_t *sorted_out, int device, double *kernel_ms_out);
+
+/* ---- Site calls scored against known truth: AUC, ROC, confusion ------------------------------------------------------------------
+ * Replaces the numbers of visualization/plot_variant_accuracy.py:44-175 over AggregateOverReadsFull.generate_labels / generate_labels2
+ * (src/signalalign/variantCaller.py:413-442): an accumulator holds, in HBM across batches, append-only arrays of scores, one per
+ * (level, read strand t / c, letter, class), and finish sorts them and counts.
+ *   level      0 per site per read, 1 per read (the mean of a read strand's site probabilities), 2 per genomic site
+ *   score      the probability of one letter, a double in [0, 1], kept as its bit pattern (non-negative doubles order as unsigned
+ *              integers; -0.0 is stored as +0.0).  A call of n letters gives n scores: the true letter's to that letter's positive
+ *              array, every other to its letter's negative array
+ *   truth      a positions table (CustomAmbiguityPositions.parseAmbiguityFile, utils/sequenceTools.py:587-600) looked up by (contig,
+ *              position, mapped strand) -- get_true_character's match of strand == forward_mapped; the first line of several that
+ *              name one key wins (.values[0]) -- or one letter per read (generate_labels2)
+ *   row        one per (level, strand group 0 t / 1 c / 2 both, letter) with at least one score, in that order:
+ *              auc2 = sum over positives p of [2 #(negatives < p) + #(negatives == p)], the trapezoid area under the ROC curve over
+ *              the distinct thresholds in units of 1 / (2 n_pos n_neg); auc = (double) auc2 / (2.0 n_pos n_neg), NaN when a count
+ *              is 0; tp, fp = positives, negatives >= threshold, fn, tn the rest; and on the grid t_k = (double) k / (double) n_bins,
+ *              k = 0 .. n_bins, tp_ge[k], fp_ge[k] = positives, negatives >= t_k.  The group of both strands is the union: its auc2
+ *              has the cross terms (template positives against complement negatives and the reverse)
+ * Every number is an integer count or one division of two integers: exact, independent of arrival order.  Two deliberate
+ * differences from the script: no average precision (a floating-point sum over all thresholds, with no exact form), and the curve
+ * is on a fixed grid, not at every distinct threshold.
+ * An array grows through the caching allocator by doubling; one add takes at most 2^30 scores and an array at most 2^31 - 1
+ * (SA_EUNSUPPORTED; for sa_call_scores_add_batch the bound is on the batch's sites, before they are labelled).  A device failure
+ * after the first appending kernel leaves the accumulator unusable: every later call on it but destroy returns SA_ESTATE. */
+typedef struct sa_call_scores sa_call_scores_t;
+typedef struct sa_truth_site {        /* one line of the positions file */
+    int32_t contig, mapped_strand;    /* mapped_strand 0 '+', 1 '-'; contig in [0, 2^21)                                           */
+    int64_t pos;                      /* in [0, 2^41)                                                                              */
+    char change_to, pad[7];           /* a letter of the accumulator's letters                                                     */
+} sa_truth_site_t;                    /* 24 bytes */
+typedef struct sa_score_job_map {     /* job j of a batch, for sa_call_scores_add_batch */
+    int32_t contig, x_sign;           /* a site's x has the TSV's reference_index x0 + x_sign * x (x_sign +1 or -1)                */
+    int64_t x0;
+    int32_t strand, mapped_strand;    /* read strand 0 't', 1 'c'; mapped strand 0 '+', 1 '-'                                      */
+    int32_t true_letter, pad;         /* index into letters: the read's label; -1: look every site up in the positions table       */
+} sa_score_job_map_t;                 /* 32 bytes */
+typedef struct sa_call_score_row {
+    int32_t level, group;             /* group 0 template, 1 complement, 2 both                                                    */
+    char letter, pad[7];
+    int64_t n_pos, n_neg;
+    uint64_t auc2;
+    double auc;
+    int64_t tp, fp, tn, fn;
+} sa_call_score_row_t;                /* 80 bytes */
+typedef struct sa_call_scores_counts {
+    int64_t unlabelled;               /* calls dropped because the positions table does not name them (generate_labels drops them) */
+    int64_t other_sites;              /* sites skipped because their letters are not the accumulator's                            */
+} sa_call_scores_counts_t;
+/* letters: 2 .. SA_SITE_MAX_LETTERS distinct characters in ascending order; n_bins >= 1; threshold not NaN; truth (may be NULL with
+ * n_truth == 0) is copied, sorted and kept on the device.  SA_EINVAL otherwise, and for a truth line with a letter outside
+ * `letters`, a strand that is neither, a contig or position outside the ranges above; then SA_ENODEVICE without a GPU. */
+int sa_call_scores_create(sa_call_scores_t **out, const char *letters, int32_t n_bins, double threshold, const sa_truth_site_t *truth,
+                          int64_t n_truth, int device);
+void sa_call_scores_destroy(sa_call_scores_t *s);
+/* chained onto a finished batch created with SA_FLAG_SITE_CALLS: the accumulate-and-normalise half of sa_batch_site_calls runs (the
+ * same launches), a kernel labels every site with a non-zero total, and no call crosses PCIe.  Level 0: every site of every job.
+ * Level 1: only jobs with true_letter >= 0 -- one lane per (job, letter) adds the site probabilities serially, in ascending
+ * reference_index when the mapped strand is '+' and descending when '-' (variantCaller.py:141-144, :172-178), and divides by the
+ * number of sites.  Not run, or created without the flag: SA_ESTATE.  n_jobs that is not the batch's, another device, a negative
+ * contig, an x_sign that is not +-1, a strand or mapped strand that is neither, a true_letter outside [-1, letters): SA_EINVAL,
+ * checked before anything is appended.  kernel_ms_out (may be NULL): HIP-event time of the call's kernels. */
+int sa_call_scores_add_batch(sa_call_scores_t *s, sa_batch_t *b, const sa_score_job_map_t *map, int64_t n_jobs, double *kernel_ms_out);
+/* scores made elsewhere: record i has prob[i * n_letters + l] for letter l and the true letter true_letter[i] (an index).  A level
+ * outside 0..2, a strand outside 0..1, a letter index outside the letters, a NaN or a value outside [0, 1]: SA_EINVAL, nothing added. */
+int sa_call_scores_add_records(sa_call_scores_t *s, int32_t level, int32_t strand, const double *prob, const int8_t *true_letter, int64_t n);
+/* checkpoint records the arrays' lengths and the counts, rollback truncates to them: nothing is copied.  Rollback without a
+ * checkpoint: SA_ESTATE */
+int sa_call_scores_checkpoint(sa_call_scores_t *s);
+int sa_call_scores_rollback(sa_call_scores_t *s);
+/* the arrays sorted into scratch (the accumulator is left as it is) and every count made on the device by binary search.
+ * *rows_out: the rows; *curves_out: per row tp_ge[n_bins + 1] then fp_ge[n_bins + 1] (both malloc'd, sa_free; curves_out and
+ * counts_out may be NULL).  kernel_ms_out (may be NULL): HIP-event time from the first sort to the last count. */
+int sa_call_scores_finish(sa_call_scores_t *s, sa_call_score_row_t **rows_out, int64_t *n_rows_out, int64_t **curves_out,
+                          sa_call_scores_counts_t *counts_out, double *kernel_ms_out);
+/* summary_path: "level\tstrand\tletter\tn_pos\tn_neg\tauc\ttp\tfp\ttn\tfn\taccuracy\tprecision\trecall" and one line per row (strand
+ * t, c or all), accuracy = (tp + tn) / (n_pos + n_neg), precision = tp / (tp + fp), recall = tp / n_pos, each one division of two
+ * integers, "nan" for 0 / 0, the doubles as Python's str(float).  curves_path (may be NULL; needs curves):
+ * "level\tstrand\tletter\tk\tthreshold\ttp_ge\tfp_ge\ttpr\tfpr\tprecision" and n_bins + 1 lines per row.  Host only. */
+int sa_call_scores_write(const char *summary_path, const char *curves_path, int32_t n_bins, const sa_call_score_row_t *rows,
+                         int64_t n_rows, const int64_t *curves);
+
 /* ---- Deviation of every read's alignment from its guide ------------------------------------------------------------------------
  * Replaces validateSignalAlignment.py over the embedded full table of every read: analyze_event_skips
  * (src/signalalign/visualization/plot_labelled_read.py:364-472), the histogram of absolute differences

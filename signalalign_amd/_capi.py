@@ -81,6 +81,28 @@ class ProfileJobMap(C.Structure):
 PROFILE_DIRECT = 1
 
 
+class TruthSite(C.Structure):
+    """sa_truth_site_t (include/signalalign_hip.h)"""
+    _fields_ = [("contig", C.c_int32), ("mapped_strand", C.c_int32), ("pos", C.c_int64), ("change_to", C.c_char), ("pad", C.c_char * 7)]
+
+
+class ScoreJobMap(C.Structure):
+    """sa_score_job_map_t (include/signalalign_hip.h)"""
+    _fields_ = [("contig", C.c_int32), ("x_sign", C.c_int32), ("x0", C.c_int64), ("strand", C.c_int32), ("mapped_strand", C.c_int32),
+                ("true_letter", C.c_int32), ("pad", C.c_int32)]
+
+
+class CallScoresCounts(C.Structure):
+    """sa_call_scores_counts_t (include/signalalign_hip.h)"""
+    _fields_ = [("unlabelled", C.c_int64), ("other_sites", C.c_int64)]
+
+
+SORT_TILE = 4096
+TRUTH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("mapped_strand", "<i4"), ("pos", "<i8"), ("change_to", "S1"), ("pad", "S1", (7,))])
+CALL_SCORE_ROW_DTYPE = np.dtype([("level", "<i4"), ("group", "<i4"), ("letter", "S1"), ("pad", "S1", (7,)), ("n_pos", "<i8"), ("n_neg", "<i8"),
+                                 ("auc2", "<u8"), ("auc", "<f8"), ("tp", "<i8"), ("fp", "<i8"), ("tn", "<i8"), ("fn", "<i8")])
+
+
 class DeviationParams(C.Structure):
     """sa_deviation_params_t (include/signalalign_hip.h)"""
     _fields_ = [("threshold", C.c_int32), ("bucket_size", C.c_int32), ("n_buckets", C.c_int32)]
@@ -216,7 +238,9 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals",
            "sa_position_profile_create", "sa_position_profile_destroy", "sa_position_profile_add_batch", "sa_position_profile_add_records",
            "sa_position_profile_checkpoint", "sa_position_profile_rollback", "sa_position_profile_finish", "sa_position_profile_write",
-           "sa_profile_entropy_term", "sa_batch_guide_deviation", "sa_guide_deviation_records", "sa_guide_deviation_release",
+           "sa_profile_entropy_term", "sa_sort_u64", "sa_call_scores_create", "sa_call_scores_destroy", "sa_call_scores_add_batch",
+           "sa_call_scores_add_records", "sa_call_scores_checkpoint", "sa_call_scores_rollback", "sa_call_scores_finish",
+           "sa_call_scores_write", "sa_batch_guide_deviation", "sa_guide_deviation_records", "sa_guide_deviation_release",
            "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
            "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
            "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet", "sa_hdp_state_vs_gaussian",
@@ -419,6 +443,16 @@ def lib():
     L.sa_position_profile_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int64]
     L.sa_profile_entropy_term.argtypes = [C.c_int64]
     L.sa_profile_entropy_term.restype = C.c_int64
+    L.sa_sort_u64.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, dp]
+    L.sa_call_scores_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_int]
+    L.sa_call_scores_destroy.argtypes = [C.c_void_p]
+    L.sa_call_scores_destroy.restype = None
+    L.sa_call_scores_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreJobMap), C.c_int64, dp]
+    L.sa_call_scores_add_records.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int8), C.c_int64]
+    L.sa_call_scores_checkpoint.argtypes = [C.c_void_p]
+    L.sa_call_scores_rollback.argtypes = [C.c_void_p]
+    L.sa_call_scores_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), ip, C.POINTER(C.c_void_p), C.POINTER(CallScoresCounts), dp]
+    L.sa_call_scores_write.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64, ip]
     dev_tail = [C.POINTER(DeviationParams), C.c_uint, C.c_void_p, C.POINTER(C.c_void_p), ip, C.POINTER(C.c_int32), ip, C.POINTER(C.c_void_p), dp]
     L.sa_batch_guide_deviation.argtypes = [C.c_void_p, C.POINTER(DeviationJob), C.c_int64, C.POINTER(C.c_void_p), ip] + dev_tail
     L.sa_guide_deviation_records.argtypes = ([C.POINTER(DeviationJob), C.c_int64, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ip,
@@ -2102,6 +2136,102 @@ def position_profile_write(path, alphabet, letters_seen, contig_names, sites):
 
 def profile_entropy_term(units):
     return int(lib().sa_profile_entropy_term(int(units)))
+
+
+def sort_u64(keys, device=0, stats=None):
+    """sa_sort_u64: the keys ascending, sorted on the device"""
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    out = np.empty_like(k)
+    kms = C.c_double()
+    _chk(lib().sa_sort_u64(k.ctypes.data, len(k), out.ctypes.data, int(device), C.byref(kms)), "sa_sort_u64")
+    if stats is not None:
+        stats["kernel_ms"] = kms.value
+    return out
+
+
+class CallScores:
+    """sa_call_scores_t: the scores of site calls against known truth, kept in HBM per (level, read strand, letter, class) across
+    add_batch / add_records calls; finish gives AUC, confusion and curve counts per (level, strand group, letter)."""
+
+    def __init__(self, letters, truth=(), n_bins=1000, threshold=0.500000001, device=0):
+        """truth: a TRUTH_SITE_DTYPE array, or an iterable of (contig index, position, mapped strand 0 '+' / 1 '-', change_to)"""
+        self._h = C.c_void_p()
+        self.letters, self.n_bins, self.threshold = letters, int(n_bins), float(threshold)
+        if isinstance(truth, np.ndarray) and truth.dtype == TRUTH_SITE_DTYPE:
+            t = np.ascontiguousarray(truth)
+        else:
+            truth = list(truth)
+            t = np.zeros(len(truth), dtype=TRUTH_SITE_DTYPE)
+            for i, (contig, pos, mapped, letter) in enumerate(truth):
+                t[i]["contig"], t[i]["pos"], t[i]["mapped_strand"], t[i]["change_to"] = int(contig), int(pos), int(mapped), letter.encode()
+        _chk(lib().sa_call_scores_create(C.byref(self._h), letters.encode(), self.n_bins, self.threshold, t.ctypes.data, len(t), int(device)),
+             "sa_call_scores_create")
+
+    def add_batch(self, batch, job_map, stats=None):
+        """chained onto a finished Batch created with FLAG_SITE_CALLS; job_map: per job a dict with the fields of sa_score_job_map_t
+        (contig, x0, x_sign, strand, mapped_strand, true_letter)"""
+        job_map = list(job_map)
+        arr = (ScoreJobMap * max(len(job_map), 1))()
+        for i, m in enumerate(job_map):
+            for f in ("contig", "x_sign", "x0", "strand", "mapped_strand", "true_letter"):
+                setattr(arr[i], f, int(m[f]))
+        kms = C.c_double()
+        _chk(lib().sa_call_scores_add_batch(self._h, batch._h, arr, len(job_map), C.byref(kms)), "sa_call_scores_add_batch")
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+
+    def add_records(self, level, strand, prob, true_letter):
+        """scores made elsewhere: prob n x len(letters), true_letter n indices into letters"""
+        prob = np.ascontiguousarray(prob, dtype=np.float64).reshape(-1, len(self.letters))
+        tl = np.ascontiguousarray(true_letter, dtype=np.int8)
+        if len(tl) != len(prob):
+            raise ValueError("one true letter per record")
+        _chk(lib().sa_call_scores_add_records(self._h, int(level), int(strand), _dp(prob), tl.ctypes.data_as(C.POINTER(C.c_int8)), len(tl)),
+             "sa_call_scores_add_records")
+
+    def checkpoint(self):
+        _chk(lib().sa_call_scores_checkpoint(self._h), "sa_call_scores_checkpoint")
+
+    def rollback(self):
+        _chk(lib().sa_call_scores_rollback(self._h), "sa_call_scores_rollback")
+
+    def finish(self, stats=None):
+        """(rows: CALL_SCORE_ROW_DTYPE array; curves: int64 array rows x 2 x (n_bins + 1), tp_ge then fp_ge; counts: dict)"""
+        rows_p, curves_p = C.c_void_p(), C.c_void_p()
+        n = np.zeros(1, dtype=np.int64)
+        counts = CallScoresCounts()
+        kms = C.c_double()
+        _chk(lib().sa_call_scores_finish(self._h, C.byref(rows_p), _ip(n), C.byref(curves_p), C.byref(counts), C.byref(kms)),
+             "sa_call_scores_finish")
+        rows = np.zeros(int(n[0]), dtype=CALL_SCORE_ROW_DTYPE)
+        curves = np.zeros((int(n[0]), 2, self.n_bins + 1), dtype=np.int64)
+        if n[0]:
+            C.memmove(rows.ctypes.data, rows_p, rows.nbytes)
+            C.memmove(curves.ctypes.data, curves_p, curves.nbytes)
+        lib().sa_free(rows_p)
+        lib().sa_free(curves_p)
+        if stats is not None:
+            stats["kernel_ms"] = kms.value
+        return rows, curves, dict(unlabelled=int(counts.unlabelled), other_sites=int(counts.other_sites))
+
+    def close(self):
+        if self._h:
+            lib().sa_call_scores_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def call_scores_write(summary_path, curves_path, n_bins, rows, curves=None):
+    """sa_call_scores_write: the summary and (curves_path not None) the curves of CallScores.finish"""
+    r = np.ascontiguousarray(rows, dtype=CALL_SCORE_ROW_DTYPE)
+    c = np.ascontiguousarray(curves if curves is not None else np.zeros(0), dtype=np.int64)
+    _chk(lib().sa_call_scores_write(os.fsencode(summary_path), os.fsencode(curves_path) if curves_path is not None else None, int(n_bins),
+                                    r.ctypes.data, len(r), _ip(c)), "sa_call_scores_write")
 
 
 def _deviation_call(jobs, mea, params, flags, call):

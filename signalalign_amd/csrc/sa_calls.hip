@@ -255,6 +255,60 @@ __global__ __launch_bounds__(64) void k_site_compact(SiteTabs T, const unsigned 
 // back to it at the end of the call (sa_pool_release / the pool's bounds reach it)
 static SaScratch g_site_ws;
 
+// the accumulate-and-normalise half of the site calls of a finished batch, left on the device (SaSiteFold, sa_chain.h)
+int sa_site_fold_run(sa_batch_t *b, SaSiteFold *F) {
+    SaAmbigTab *S = nullptr;
+    int64_t nj64 = 0;
+    int rc = sa_batch_ambig(b, SA_TAB_SITES, &S, &nj64);
+    if (rc) return rc;
+    const size_t nj = F->nj = (size_t) nj64;
+    const size_t stride = F->stride = (size_t) S->stride, ns = F->ns = (size_t) S->n_sites;
+    F->kernel_ms = 0.0;
+    F->h_x = S->x.data();
+    F->h_site_off = S->site_off.data();
+    F->letters = S->letters;
+    if (ns == 0) return SA_OK;   // (a batch without sites -- a SA_FLAG_PAIRS8 one among them -- has nothing to read on the device)
+    SaBatchView V;
+    if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
+    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+    const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
+    const int device = F->device = V.device;
+    const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, SA_ORDINAL_PER_JOB);   // (ordinals unused)
+    const size_t nc = chunks.size();
+    SaLayout L;   // device: [units | prob | chunks | count]
+    const size_t o_units = L.add(8 * ns * stride), o_prob = L.add(8 * ns * stride), o_chunks = L.add(sizeof(SaRecChunk) * nc),
+                 o_count = L.add(4 * nj);
+    SaScratch &W = g_site_ws;
+    F->ws = &W;
+    F->guard = std::unique_lock<std::mutex>(W.mu);
+    char *&d = F->d;
+    SiteTabs T;
+    if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
+    if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, L.end, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
+    T = sites_tabs(S);
+    if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
+    SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_units, 0, 8 * ns * stride, 0));
+    SA_HIP_GOTO_DONE(W.time_begin());
+    if (nc) hipLaunchKernelGGL(k_site_accum, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
+                               (unsigned long long *) (d + o_units));
+    hipLaunchKernelGGL(k_site_final, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
+                       (double *) (d + o_prob), (int *) (d + o_count));
+    F->units = (const unsigned long long *) (d + o_units);
+    F->prob = (const double *) (d + o_prob);
+    F->count = (const int *) (d + o_count);
+    F->site_off = T.site_off;
+    F->kind = T.kind;
+done:
+    return rc;
+}
+
+void sa_site_fold_release(SaSiteFold *F, bool failed) {
+    if (failed && F->d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
+    if (F->d) g_sa_pool.put(SaPool::DEVICE, F->d);
+    F->d = nullptr;
+    if (F->guard.owns_lock()) F->guard.unlock();
+}
+
 extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
     (void) flags;
     if (!b || !calls_out || !n_out) return SA_EINVAL;
@@ -270,38 +324,22 @@ extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t
     const int *h_site = nullptr;
     const unsigned long long *h_units = nullptr;
     const double *h_prob = nullptr;
-    char *d = nullptr, *h = nullptr;   // this call's device and pinned blocks (g_sa_pool)
-    SaScratch &W = g_site_ws;
-    std::unique_lock<std::mutex> guard(W.mu, std::defer_lock);
-    if (ns > 0) {   // (a batch without sites -- a SA_FLAG_PAIRS8 one among them -- has nothing to read on the device)
-        SaBatchView V;
-        if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
-        if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
-        const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
-        const int device = V.device;
-        const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, SA_ORDINAL_PER_JOB);   // (ordinals unused)
-        const size_t nc = chunks.size();
-        SaLayout L;   // device: [units | prob | chunks | count | off | out site | out units | out prob]
-        const size_t o_units = L.add(8 * ns * stride), o_prob = L.add(8 * ns * stride), o_chunks = L.add(sizeof(SaRecChunk) * nc),
-                     o_count = L.add(4 * nj), o_off = L.add(8 * (nj + 1)), o_osite = L.add(4 * ns), o_ounits = L.add(8 * ns * stride),
-                     o_oprob = L.add(8 * ns * stride), dev_bytes = L.end;
-        guard.lock();
-        if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
-        if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
+    char *d = nullptr, *h = nullptr;   // this call's device and pinned blocks (g_sa_pool), beside the fold's
+    SaSiteFold F;
+    if (ns > 0) {
+        if ((rc = sa_site_fold_run(b, &F)) != SA_OK) { sa_site_fold_release(&F, true); return rc; }
+        SaScratch &W = *F.ws;
+        const int device = F.device;
         const SiteTabs T = sites_tabs(S);
+        SaLayout L;   // device: [off | out site | out units | out prob]
+        const size_t o_off = L.add(8 * (nj + 1)), o_osite = L.add(4 * ns), o_ounits = L.add(8 * ns * stride),
+                     o_oprob = L.add(8 * ns * stride), dev_bytes = L.end;
         float kms = 0;
         size_t n_kept = 0, o_hunits = 0, o_hprob = 0;
-        if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
-        SA_HIP_GOTO_DONE(hipMemsetAsync(d + o_units, 0, 8 * ns * stride, 0));
-        SA_HIP_GOTO_DONE(W.time_begin());
-        if (nc) hipLaunchKernelGGL(k_site_accum, dim3((unsigned) nc), dim3(256), 0, 0, d_pairs, (const SaRecChunk *) (d + o_chunks), T,
-                                   (unsigned long long *) (d + o_units));
-        hipLaunchKernelGGL(k_site_final, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
-                           (double *) (d + o_prob), (int *) (d + o_count));
-        hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, (const int *) (d + o_count), (long long *) (d + o_off), (int) nj);
-        hipLaunchKernelGGL(k_site_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, (const unsigned long long *) (d + o_units),
-                           (const double *) (d + o_prob), (const long long *) (d + o_off), (int *) (d + o_osite),
-                           (unsigned long long *) (d + o_ounits), (double *) (d + o_oprob));
+        if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; rc = SA_ENOMEM; goto done; }
+        hipLaunchKernelGGL(k_site_scan, dim3(1), dim3(SA_SCAN_THREADS), 0, 0, F.count, (long long *) (d + o_off), (int) nj);
+        hipLaunchKernelGGL(k_site_compact, dim3((unsigned) nj), dim3(64), 0, 0, T, F.units, F.prob, (const long long *) (d + o_off),
+                           (int *) (d + o_osite), (unsigned long long *) (d + o_ounits), (double *) (d + o_oprob));
         SA_HIP_GOTO_DONE(W.time_end());
         SA_HIP_GOTO_DONE(hipMemcpy(h_off.data(), d + o_off, 8 * (nj + 1), hipMemcpyDeviceToHost));
         SA_HIP_GOTO_DONE(W.time_ms(&kms));
@@ -348,9 +386,10 @@ extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t
         if (oom) rc = SA_ENOMEM;
     }
 done:
-    if (rc != SA_OK && d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
+    if (rc != SA_OK && (d || F.d)) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
     if (d) g_sa_pool.put(SaPool::DEVICE, d);   // (every kernel and copy of the call has completed: synchronous copies above)
     if (h) g_sa_pool.put(SaPool::PINNED, h);
+    sa_site_fold_release(&F, false);
     if (rc != SA_OK)
         for (size_t j = 0; j < nj; j++) { free(calls_out[j]); calls_out[j] = nullptr; n_out[j] = 0; }
     return rc;

@@ -5,6 +5,7 @@
 #define SA_CHAIN_H
 
 #include <algorithm>
+#include <string>
 
 #include "sa_scratch.h"
 
@@ -35,6 +36,32 @@ void sa_ambig_release_device(SaAmbigTab *s);     // NULL: nothing
 void sa_ambig_free(SaAmbigTab *s);               // NULL: nothing
 // sa_hip.hip: a finished batch's table `which` (SA_ESTATE: created without the table's flag, or not run)
 int sa_batch_ambig(sa_batch_t *b, int which, SaAmbigTab **tab, int64_t *n_jobs);
+
+// The accumulate-and-normalise half of the site calls of a finished batch, left on its device (sa_calls.hip): what
+// sa_batch_site_calls compacts and copies out and what sa_call_scores_add_batch (sa_scores.hip) labels in place.  Site s of job j,
+// site_off[j] <= s < site_off[j + 1], in ascending x: units[s * stride + e] and prob[s * stride + e] for letter e of the site's kind
+// (prob 0 where the units sum to 0: such a site is not a call), count[j] the job's sites with a non-zero sum.  With ns == 0 nothing
+// is on the device.  sa_site_fold_run takes the lock of the site calls' scratch and starts its timed region (ws->time_begin), which
+// the caller ends after its own launches; sa_site_fold_release gives the lock back with the device block; release after a failed
+// run is allowed.
+struct SaSiteFold {
+    size_t nj = 0, stride = 1, ns = 0;
+    int device = 0;
+    double kernel_ms = 0.0;
+    const long long *site_off = nullptr;           // device, nj + 1
+    const unsigned char *kind = nullptr;           // device, per site
+    const unsigned long long *units = nullptr;     // device
+    const double *prob = nullptr;
+    const int *count = nullptr;
+    const int *h_x = nullptr;                      // host, per site: its k-mer index x
+    const long long *h_site_off = nullptr;         // host, nj + 1
+    std::vector<std::string> letters;              // host, per kind: the sorted letters
+    SaScratch *ws = nullptr;
+    char *d = nullptr;                             // the fold's device block (g_sa_pool)
+    std::unique_lock<std::mutex> guard;
+};
+int sa_site_fold_run(sa_batch_t *b, SaSiteFold *F);
+void sa_site_fold_release(SaSiteFold *F, bool failed);
 
 // The position fold of a finished batch, left on its device (sa_calls.hip): what sa_batch_position_calls copies out and what
 // sa_snp_marginals_add_batch (sa_marginals.hip) reads in place.  Record r of job j, off[j] <= r < off[j + 1], in position order:

@@ -101,6 +101,15 @@ static void usage(void) {
                     "                  each of its letters (variantCaller.py MarginalizeFullVariants)\n");
     fprintf(stderr, "--site-calls-aggregate <file>: write the per-site calls averaged over all reads of the run to <file>\n"
                     "                  (AggregateOverReadsFull); a manifest's posteriors file may then be '-' (no TSV for that read)\n");
+    fprintf(stderr, "--site-calls-accuracy <file>: score the run's site calls against known truth on the GPU: per level (0 per site per\n"
+                    "                  read, 1 per read, 2 per genomic site), strand (t, c, all) and letter n_pos, n_neg, auc, the confusion\n"
+                    "                  counts at the threshold, accuracy, precision and recall (plot_variant_accuracy.py).  Implies the site\n"
+                    "                  tables and the over-reads aggregation; needs one of the two truth options\n"
+                    "--site-calls-truth <positions.tsv>: contig, position, strand, change_from, change_to per line (the positions file)\n"
+                    "--site-calls-truth-reads <labels.tsv>: read label, true letter per line; such a read is labelled as a whole\n"
+                    "--site-calls-accuracy-curves <file>: per row and grid point threshold, tp_ge, fp_ge, tpr, fpr, precision\n"
+                    "--site-calls-accuracy-bins <n>: grid points k / n, k = 0 .. n (default 1000)\n"
+                    "--site-calls-accuracy-threshold <t>: the confusion counts' threshold (default 0.500000001)\n");
     fprintf(stderr, "--snp-step <N> --snp-dir <dir>: single-nucleotide probabilities: every read is aligned N times, with X at the\n"
                     "                  reference positions = s (mod N) in run s; <dir>/<label>.tsv gets pA pC pG pT per covered position\n"
                     "                  (singleNucleotideProbabilities.py); no posteriors file: no -u, a manifest's posteriors column '-'\n");
@@ -402,6 +411,11 @@ typedef struct {
     int mea; /* --mea: also write the maximum-expected-accuracy path of every read (not in the reference binary) */
     int site_calls;         /* --site-calls: also write <posteriors>.calls (not in the reference binary) */
     const char *agg_path;   /* --site-calls-aggregate: the over-reads table, written at the end of the run */
+    /* --site-calls-accuracy: the run's calls scored against known truth on the GPU (sa_call_scores_t), written at the end; it
+     * needs the over-reads table too (want_agg) */
+    const char *acc_path, *acc_curves_path, *acc_truth_path, *acc_reads_path;
+    int acc_bins, want_agg;
+    double acc_threshold;
     /* --train-*: the top-N assignments of the whole run in k-mer tables on the GPU (one per strand), written at the end */
     const char *train_assign, *train_model[2], *train_kmers;
     int want_train;         /* any of --train-assignments / --train-template-model / --train-complement-model / --train-mixture-* */
@@ -1425,6 +1439,186 @@ static void write_aggregate(const char *path) {
     free(rows);
 }
 
+/* ---- --site-calls-accuracy: the calls scored against known truth (plot_variant_accuracy.py:44-175) in one sa_call_scores_t.
+ * Levels 0 and 1 are added batch by batch while the batch's records lie in HBM (acc_add_batch), level 2 at the end of the run from
+ * the over-reads table, in the six decimals it prints (acc_add_aggregate).  The accumulator's letters are those of the run's first
+ * call, so it is made when that call is there.  A read named in --site-calls-truth-reads is labelled as a whole (generate_labels2),
+ * every other site by the positions file (generate_labels); level 2 takes the positions file only. ---- */
+typedef struct { int contig, strand; int64_t pos, line; char letter; } acc_truth_t;
+typedef struct { char *label; char letter; } acc_label_t;
+static struct {
+    sa_call_scores_t *acc;
+    int device, ck;                      /* ck: the accumulator was there, and checkpointed, when the slice began */
+    char letters[SA_SITE_MAX_LETTERS + 1];
+    char **contigs;                      /* a contig's index is its place here: the positions file's names first */
+    int n_contigs;
+    acc_truth_t *truth;                  /* sorted by (contig, pos, strand, line) */
+    int64_t n_truth;
+    acc_label_t *labels;                 /* sorted by label */
+    int64_t n_labels;
+} g_acc;
+static int acc_contig(const char *name) {
+    int ci = 0;
+    while (ci < g_acc.n_contigs && strcmp(g_acc.contigs[ci], name) != 0) ci++;
+    if (ci == g_acc.n_contigs) {
+        g_acc.contigs = realloc(g_acc.contigs, sizeof(char *) * (size_t) (g_acc.n_contigs + 1));
+        g_acc.contigs[g_acc.n_contigs++] = strdup(name);
+    }
+    return ci;
+}
+static int cmp_acc_truth(const void *a, const void *b) {
+    const acc_truth_t *x = a, *y = b;
+    if (x->contig != y->contig) return x->contig < y->contig ? -1 : 1;
+    if (x->pos != y->pos) return x->pos < y->pos ? -1 : 1;
+    if (x->strand != y->strand) return x->strand < y->strand ? -1 : 1;
+    return x->line < y->line ? -1 : x->line > y->line;
+}
+static int cmp_acc_label(const void *a, const void *b) { return strcmp(((const acc_label_t *) a)->label, ((const acc_label_t *) b)->label); }
+/* the two truth files, read before the run starts so that a bad one stops it */
+static void acc_load(const run_t *R) {
+    char line[4096], a[1024], st[64], from[64], to[64];
+    if (R->acc_truth_path) {
+        FILE *fh = fopen(R->acc_truth_path, "r");
+        if (!fh) die("signalMachine: --site-calls-truth: cannot read %s", R->acc_truth_path);
+        int64_t cap = 0, pos = 0;
+        while (fgets(line, sizeof line, fh)) {
+            if (line[0] == '\n' || line[0] == '#') continue;
+            if (sscanf(line, "%1023s %" SCNd64 " %63s %63s %63s", a, &pos, st, from, to) != 5 || (strcmp(st, "+") && strcmp(st, "-")) || strlen(to) != 1)
+                die("signalMachine: --site-calls-truth: not 'contig position +|- change_from change_to': %s", line);
+            if (g_acc.n_truth == cap) g_acc.truth = realloc(g_acc.truth, sizeof(acc_truth_t) * (size_t) (cap = cap ? 2 * cap : 1024));
+            g_acc.truth[g_acc.n_truth] = (acc_truth_t) {acc_contig(a), st[0] == '-', pos, g_acc.n_truth, to[0]};
+            g_acc.n_truth++;
+        }
+        fclose(fh);
+        qsort(g_acc.truth, (size_t) g_acc.n_truth, sizeof(acc_truth_t), cmp_acc_truth);
+    }
+    if (R->acc_reads_path) {
+        FILE *fh = fopen(R->acc_reads_path, "r");
+        if (!fh) die("signalMachine: --site-calls-truth-reads: cannot read %s", R->acc_reads_path);
+        int64_t cap = 0;
+        while (fgets(line, sizeof line, fh)) {
+            if (line[0] == '\n' || line[0] == '#') continue;
+            if (sscanf(line, "%1023s %63s", a, to) != 2 || strlen(to) != 1) die("signalMachine: --site-calls-truth-reads: not 'label letter': %s", line);
+            if (g_acc.n_labels == cap) g_acc.labels = realloc(g_acc.labels, sizeof(acc_label_t) * (size_t) (cap = cap ? 2 * cap : 1024));
+            g_acc.labels[g_acc.n_labels++] = (acc_label_t) {strdup(a), to[0]};
+        }
+        fclose(fh);
+        qsort(g_acc.labels, (size_t) g_acc.n_labels, sizeof(acc_label_t), cmp_acc_label);
+    }
+}
+/* index of the read's label letter in the accumulator's letters, -1 for a read without a label */
+static int acc_read_letter(const char *label) {
+    const acc_label_t key = {(char *) label, 0};
+    const acc_label_t *e = g_acc.n_labels ? bsearch(&key, g_acc.labels, (size_t) g_acc.n_labels, sizeof(acc_label_t), cmp_acc_label) : NULL;
+    if (!e) return -1;
+    const char *at = strchr(g_acc.letters, e->letter);
+    if (!at) die("signalMachine: --site-calls-truth-reads: the letter of read %s is not one of the sites' letters", label);
+    return (int) (at - g_acc.letters);
+}
+/* the first line of the positions file that names (contig, pos, mapped strand): its change_to, 0 when none does */
+static char acc_truth_letter(int contig, int64_t pos, int strand) {
+    int64_t lo = 0, hi = g_acc.n_truth;
+    const acc_truth_t key = {contig, strand, pos, -1, 0};
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (cmp_acc_truth(&g_acc.truth[mid], &key) < 0) lo = mid + 1; else hi = mid;
+    }
+    const acc_truth_t *e = lo < g_acc.n_truth ? &g_acc.truth[lo] : NULL;
+    return e && e->contig == contig && e->pos == pos && e->strand == strand ? e->letter : 0;
+}
+/* the accumulator, made when the run has its first call: its letters are that call's */
+static void acc_create(const run_t *R, const strand_result_t *sr, int64_t n) {
+    for (int64_t j = 0; j < n && !g_acc.acc; j++) {
+        if (sr->n_calls[j] <= 0) continue;
+        const sa_site_call_t *c = &sr->calls[j][0];
+        memcpy(g_acc.letters, c->letters, (size_t) c->n_letters);
+        g_acc.letters[c->n_letters] = 0;
+        sa_truth_site_t *t = xalloc(g_acc.n_truth, sizeof(*t), 1);
+        for (int64_t i = 0; i < g_acc.n_truth; i++) {
+            t[i].contig = g_acc.truth[i].contig; t[i].mapped_strand = g_acc.truth[i].strand; t[i].pos = g_acc.truth[i].pos;
+            t[i].change_to = g_acc.truth[i].letter;
+        }
+        const int rc = sa_call_scores_create(&g_acc.acc, g_acc.letters, R->acc_bins, R->acc_threshold, t, g_acc.n_truth, g_acc.device);
+        free(t);
+        if (rc == SA_EINVAL) die("signalMachine: --site-calls-truth: a change_to letter is not one of the sites' letters %s, or a position is negative", g_acc.letters);
+        if (rc != SA_OK) die("signalMachine: --site-calls-accuracy: %s", sa_strerror(rc));
+    }
+}
+/* levels 0 and 1 of the slice's finished batch of strand s.  The mapping strand of a job is the one order_calls gives its calls. */
+static int acc_add_batch(const align_slice_t *c, int s, sa_batch_t *b) {
+    const run_t *R = c->sl.R;
+    const int64_t nj = c->sl.n_ok;
+    acc_create(R, &c->sr[s], nj);
+    if (!g_acc.acc) return SA_OK;   /* (no call so far: nothing to score) */
+    sa_score_job_map_t *map = xalloc(nj, sizeof(*map), 1);
+    for (int64_t j = 0; j < nj; j++) {
+        const read_t *rd = &c->sl.reads[c->sl.who[j]];
+        const int idx = (s == 1 && c->tmpl_amb && c->tmpl_amb[j]) ? 1 : 0;
+        const int along = (s == 0 && rd->forward) || (s == 1 && !rd->forward);   /* adjust_ref as x0 + x_sign * x */
+        map[j].contig = acc_contig(rd->pA->contig1);
+        map[j].x_sign = along ? 1 : -1;
+        map[j].x0 = along ? rd->st[s].r_shift : rd->st[s].r_shift - R->sm[s].k;
+        map[j].strand = s;
+        map[j].mapped_strand = (idx == 0) == (rd->forward != 0) ? 0 : 1;
+        map[j].true_letter = acc_read_letter(rd->label);
+    }
+    const int rc = sa_call_scores_add_batch(g_acc.acc, b, map, nj, NULL);
+    free(map);
+    return rc;
+}
+/* level 2: every row of the over-reads table whose letters are the accumulator's and whose site the positions file names, with
+ * the values write_aggregate prints */
+static void acc_add_aggregate(void) {
+    const size_t nl = strlen(g_acc.letters);
+    for (int strand = 0; strand < 2 && g_acc.acc; strand++) {
+        double *prob = xalloc((int64_t) (g_agg.n * nl), sizeof(double), 0);
+        int8_t *tl = xalloc((int64_t) g_agg.n, 1, 0);
+        int64_t n = 0;
+        for (size_t i = 0; i < g_agg.cap; i++) {
+            const agg_entry_t *e = &g_agg.tab[i];
+            if (!e->used || (e->strand == 't') != (strand == 0) || (size_t) e->n != nl) continue;
+            double v[SA_SITE_MAX_LETTERS], total = 0.0;
+            int ok = 1;
+            for (size_t l = 0; l < nl && ok; l++) {   /* (the accumulator's letters are sorted: the table's column order) */
+                int t = 0;
+                while (t < e->n && e->letter[t] != g_acc.letters[l]) t++;
+                ok = t < e->n;
+                if (ok) { v[l] = e->sum[t]; total += v[l]; }
+            }
+            const char letter = ok ? acc_truth_letter(acc_contig(g_agg.contigs[e->contig]), e->pos, e->mapped == '-') : 0;
+            const char *at = letter ? strchr(g_acc.letters, letter) : NULL;
+            if (!at) continue;
+            char num[40];
+            for (size_t l = 0; l < nl; l++) {
+                sa_format_py_round6(num, v[l] / total);
+                prob[(size_t) n * nl + l] = strtod(num, NULL);
+            }
+            tl[n++] = (int8_t) (at - g_acc.letters);
+        }
+        const int rc = sa_call_scores_add_records(g_acc.acc, 2, strand, prob, tl, n);
+        if (rc != SA_OK) die("signalMachine: --site-calls-accuracy: %s", sa_strerror(rc));
+        free(prob); free(tl);
+    }
+}
+static void write_accuracy(const run_t *R) {
+    if (!R->acc_path) return;
+    sa_call_score_row_t *rows = NULL;
+    int64_t n_rows = 0, *curves = NULL;
+    sa_call_scores_counts_t counts = {0, 0};
+    if (g_acc.acc) {
+        acc_add_aggregate();
+        const int rc = sa_call_scores_finish(g_acc.acc, &rows, &n_rows, &curves, &counts, NULL);
+        if (rc != SA_OK) die("signalMachine: --site-calls-accuracy: %s", sa_strerror(rc));
+    }
+    if (sa_call_scores_write(R->acc_path, R->acc_curves_path, R->acc_bins, rows, n_rows, curves) != SA_OK)
+        die("signalMachine: cannot write %s", R->acc_path);
+    fprintf(stderr, "[signalMachine] accuracy: %" PRId64 " rows; %" PRId64 " calls without truth dropped, %" PRId64 " sites of other letters skipped\n",
+            n_rows, counts.unlabelled, counts.other_sites);
+    sa_free(rows); sa_free(curves);
+    sa_call_scores_destroy(g_acc.acc);
+    g_acc.acc = NULL;
+}
+
 static out_ctx_t out_ctx_for(const run_t *R, const read_t *rd, int s, const sa_pair_t *pairs, int64_t n_pairs, double score) {
     out_ctx_t o;
     o.label = rd->label; o.contig = rd->pA->contig1; o.sm = &R->sm[s]; o.npp = *np_params(rd->np, s);
@@ -1878,7 +2072,7 @@ static int run_strand_batch(align_slice_t *c, int s) {
     run_t *R = sl->R;
     strand_result_t *sr = &c->sr[s];
     const int64_t n = sl->n_ok;
-    const int want_calls = R->site_calls || R->agg_path != NULL;
+    const int want_calls = R->site_calls || R->want_agg;
     const int want_mea = R->mea || R->dev_path != NULL;
     unsigned flags = want_calls ? SA_FLAG_SITE_CALLS : 0u, p8 = 0u;
     if (!want_mea && !want_calls) {
@@ -1902,6 +2096,12 @@ static int run_strand_batch(align_slice_t *c, int s) {
     if (rc == SA_EUNSUPPORTED && p8) rc = create_strand_batch(&b, sl, s, c->bj, n, 1, flags);
     if (rc == SA_OK) rc = sa_batch_run(b);
     if (rc == SA_OK && want_calls) rc = sa_batch_site_calls(b, 0, sr->calls, sr->n_calls, NULL);
+    /* --site-calls-accuracy: scored while the records are in HBM.  (A 2-D run's complement waits for the rendering, which finds out
+     * the mapping strand of its calls: render_slice.) */
+    if (rc == SA_OK && R->acc_path && !(s == 1 && R->two_d)) {
+        rc = acc_add_batch(c, s, b);
+        if (rc != SA_OK) die("signalMachine: --site-calls-accuracy: %s", sa_strerror(rc));
+    }
     if (rc == SA_OK && R->want_train) {   /* (a batch that ran: nothing a retry without some reads would change) */
         rc = sa_kmer_table_add_batch(R->train_tab[s], b, c->bj, n, s, NULL);
         if (rc != SA_OK) die("signalMachine: --train-*: %s", sa_strerror(rc));
@@ -1955,10 +2155,14 @@ static void render_slice(align_slice_t *c) {
             const strand_result_t *sr = &c->sr[s];
             n_all[s] = sr->all_n ? sr->all_n[j] : sr->n_pairs[j];
             /* (the aggregate's sums over reads are taken here, in read order: they do not depend on the rendering threads) */
-            if (R->agg_path) agg_add_read(rd, s, c->tmpl_amb && c->tmpl_amb[j], sr->calls[j], sr->n_calls[j], R->sm[s].k);
+            if (R->want_agg) agg_add_read(rd, s, c->tmpl_amb && c->tmpl_amb[j], sr->calls[j], sr->n_calls[j], R->sm[s].k);
         }
         report_read(R, rd, n_all, c->score[j]);
         for (int s = 0; s < n_strands(R) && R->dev_path; s++) write_deviation(sl->R, rd, s, &c->sr[s], j);
+    }
+    if (R->acc_path && R->two_d && c->sr[1].batch && sl->n_ok > 0) {   /* (the records go up again from the batch's host copy) */
+        const int rc = acc_add_batch(c, 1, c->sr[1].batch);
+        if (rc != SA_OK) die("signalMachine: --site-calls-accuracy: %s", sa_strerror(rc));
     }
     free(c->tmpl_amb);
     free(c->score);
@@ -1984,6 +2188,9 @@ static int64_t run_slice_align(run_t *R, read_t *reads, int64_t n_reads, int dev
     }
     /* --position-profile: the same for its table */
     if (R->prof_tab && sa_position_profile_checkpoint(R->prof_tab) != SA_OK) die("signalMachine: --position-profile: checkpoint failed%s", "");
+    /* --site-calls-accuracy: the same; an accumulator that this slice makes is given up instead */
+    g_acc.ck = g_acc.acc != NULL;
+    if (g_acc.ck && sa_call_scores_checkpoint(g_acc.acc) != SA_OK) die("signalMachine: --site-calls-accuracy: checkpoint failed%s", "");
     for (int s = 0; s < n_strands(R) && sl->n_ok > 0; s++) {
         fprintf(stderr, "signalAlign - starting %s alignment\n", strand_name(s));
         const int64_t n_jobs = sl->n_ok;
@@ -1992,6 +2199,8 @@ static int64_t run_slice_align(run_t *R, read_t *reads, int64_t n_reads, int dev
             for (int q = 0; q < n_strands(R) && R->want_train; q++)
                 if (sa_kmer_table_rollback(R->train_tab[q]) != SA_OK) die("signalMachine: --train-*: rollback failed%s", "");
             if (R->prof_tab && sa_position_profile_rollback(R->prof_tab) != SA_OK) die("signalMachine: --position-profile: rollback failed%s", "");
+            if (g_acc.acc && g_acc.ck && sa_call_scores_rollback(g_acc.acc) != SA_OK) die("signalMachine: --site-calls-accuracy: rollback failed%s", "");
+            if (g_acc.acc && !g_acc.ck) { sa_call_scores_destroy(g_acc.acc); g_acc.acc = NULL; }
             for (int q = 0; q <= s; q++) strand_result_free(&c.sr[q], n_jobs);
             s = -1;   /* both strands again, without the offenders */
             continue;
@@ -2378,8 +2587,10 @@ int main(int argc, char **argv) {
     char *t_model = NULL, *c_model = NULL, *label = NULL, *npread_path = NULL, *cigar_path = NULL, *post_path = NULL;
     char *t_expect = NULL, *c_expect = NULL, *t_hdp = NULL, *c_hdp = NULL, *fwd_ref = NULL, *bwd_ref = NULL,
          *post_path2 = NULL, *seq_name = NULL, *ambig_model = NULL, *manifest = NULL, *guide_window = NULL;
-    int guide_locate = 0;
+    int guide_locate = 0, acc_opts = 0;
     R.guide_band = 128;
+    R.acc_bins = 1000;
+    R.acc_threshold = 0.500000001;
     static struct option long_options[] = {{"help", no_argument, 0, 'h'},
                                            {"sm3Hdp", no_argument, 0, 'd'},
                                            {"sparse_output", no_argument, 0, 's'},
@@ -2411,6 +2622,12 @@ int main(int argc, char **argv) {
                                            {"emission", required_argument, 0, 1004},
                                            {"site-calls", no_argument, 0, 1005},
                                            {"site-calls-aggregate", required_argument, 0, 1006},
+                                           {"site-calls-accuracy", required_argument, 0, 1070},
+                                           {"site-calls-accuracy-curves", required_argument, 0, 1071},
+                                           {"site-calls-accuracy-bins", required_argument, 0, 1072},
+                                           {"site-calls-accuracy-threshold", required_argument, 0, 1073},
+                                           {"site-calls-truth", required_argument, 0, 1074},
+                                           {"site-calls-truth-reads", required_argument, 0, 1075},
                                            {"train-assignments", required_argument, 0, 1010},
                                            {"train-template-model", required_argument, 0, 1011},
                                            {"train-complement-model", required_argument, 0, 1012},
@@ -2474,6 +2691,12 @@ int main(int argc, char **argv) {
             case 1002: R.mea = 1; break;
             case 1005: R.site_calls = 1; break;
             case 1006: R.agg_path = strdup(optarg); break;
+            case 1070: R.acc_path = strdup(optarg); break;
+            case 1071: R.acc_curves_path = strdup(optarg); break;
+            case 1072: R.acc_bins = atoi(optarg); acc_opts = 1; break;
+            case 1073: R.acc_threshold = atof(optarg); acc_opts = 1; break;
+            case 1074: R.acc_truth_path = strdup(optarg); break;
+            case 1075: R.acc_reads_path = strdup(optarg); break;
             case 1010: R.train_assign = strdup(optarg); break;
             case 1011: R.train_model[0] = strdup(optarg); break;
             case 1012: R.train_model[1] = strdup(optarg); break;
@@ -2589,7 +2812,15 @@ int main(int argc, char **argv) {
         if ((R.train_model[1] || R.mix_model[1]) && !R.two_d) die("signalMachine: --train-complement-model needs a 2-D run%s", "");
         if (R.train_n < 1 || !(R.train_min_prob >= 0 && R.train_min_prob <= 1)) die("signalMachine: bad --train-max-assignments / --train-min-prob%s", "");
     }
-    if (R.expect_mode && (R.site_calls || R.agg_path)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate need the alignment mode, not -t/-c%s", ""); }
+    if (!R.acc_path && (R.acc_curves_path || R.acc_truth_path || R.acc_reads_path || acc_opts)) {
+        usage();
+        die("signalMachine: --site-calls-truth* and --site-calls-accuracy-* need --site-calls-accuracy <file>%s", "");
+    }
+    if (R.acc_path && !R.acc_truth_path && !R.acc_reads_path) { usage(); die("signalMachine: --site-calls-accuracy needs --site-calls-truth <file> or --site-calls-truth-reads <file>%s", ""); }
+    if (R.acc_path && (R.acc_bins < 1 || R.acc_threshold != R.acc_threshold)) { usage(); die("signalMachine: --site-calls-accuracy-bins takes n >= 1, --site-calls-accuracy-threshold a number%s", ""); }
+    if (R.acc_path && R.two_d && (R.mea || R.dev_path)) { usage(); die("signalMachine: --site-calls-accuracy on a --twoD run cannot be combined with --mea / --guide-deviation%s", ""); }
+    R.want_agg = R.agg_path != NULL || R.acc_path != NULL;
+    if (R.expect_mode && (R.site_calls || R.want_agg)) { usage(); die("signalMachine: --site-calls / --site-calls-aggregate / --site-calls-accuracy need the alignment mode, not -t/-c%s", ""); }
     if (R.snp_prop && !R.snp_marg) { usage(); die("signalMachine: --snp-proposals needs --snp-marginals <file>%s", ""); }
     if (R.snp_sites_path && snp_set) { usage(); die("signalMachine: --snp-sites cannot be combined with --snp-step%s", ""); }
     if (R.snp_ref_out && !R.snp_sites_path) { usage(); die("signalMachine: --snp-reference-out needs --snp-sites <file>%s", ""); }
@@ -2618,7 +2849,7 @@ int main(int argc, char **argv) {
         if (R.snp_marg && R.two_d) { usage(); die("signalMachine: --snp-marginals does not take --twoD runs%s", ""); }
         if (R.expect_mode) { usage(); die("signalMachine: %s cannot be combined with -t/-c", opt); }
         if (R.mea) { usage(); die("signalMachine: %s cannot be combined with --mea", opt); }
-        if (R.site_calls || R.agg_path) { usage(); die("signalMachine: %s cannot be combined with --site-calls / --site-calls-aggregate", opt); }
+        if (R.site_calls || R.want_agg) { usage(); die("signalMachine: %s cannot be combined with --site-calls / --site-calls-aggregate / --site-calls-accuracy", opt); }
         if (R.want_train) { usage(); die("signalMachine: %s cannot be combined with --train-*", opt); }
         for (int64_t i = 0; i < n_reads; i++)
             if (reads[i].post_path || reads[i].post_path2) {
@@ -2700,6 +2931,10 @@ int main(int argc, char **argv) {
         const int rc = sa_position_profile_create(&R.prof_tab, R.sm[0].model, R.snp_lens, R.snp_n_contigs, device);
         if (rc != SA_OK) die("signalMachine: --position-profile: %s", sa_strerror(rc));
     }
+    if (R.acc_path) {
+        g_acc.device = device;
+        acc_load(&R);
+    }
     if (R.dev_path) {
         if (!(R.dev_fh = fopen(R.dev_path, "w"))) die("signalMachine: cannot open output %s", R.dev_path);
         fprintf(R.dev_fh, "#guide-deviation threshold=%d bucket_size=%d n_buckets=%d; R label strand status n_aligned n_flagged n_on_mea mean_abs "
@@ -2727,6 +2962,7 @@ int main(int argc, char **argv) {
         if (started) pthread_join(th, NULL);
     }
     if (R.agg_path) write_aggregate(R.agg_path);
+    write_accuracy(&R);
     write_training(&R, t_model, c_model, device);
     write_snp_marginals(&R);
     write_position_profile(&R);
