@@ -955,8 +955,8 @@ void sa_guide_deviation_release(void); /* returns the scratch the two calls keep
  *             sa_batch_pairs order (the reference's order comes from a directory listing: the one deliberate difference)
  * sa_kmer_table_add_batch reads a finished batch's records where the run left them in HBM (16- or 8-byte ones); after
  * sa_batch_release_device, and with SA_FLAG_EXACT (host-finalised pairs), the records are first copied up again, all of them; `jobs` / `n_jobs` are the batch's own (event means, scalings and, for
- * 8-byte records, the references).  SA_FLAG_VC_ROWS batch: SA_EINVAL; not run: SA_ESTATE; a descaled value outside
- * +-2^31 or not finite: SA_EUNSUPPORTED.  max_per_kmer < 1 or min_prob outside [0, 1]: SA_EINVAL. */
+ * 8-byte records, the references).  SA_FLAG_VC_ROWS batch: SA_EINVAL; not run: SA_ESTATE; a descaled value of magnitude
+ * 2147.483648 or more (beyond +-2^31 units) or not finite, from a batch or in sa_kmer_table_add_rows: SA_EUNSUPPORTED.  max_per_kmer < 1 or min_prob outside [0, 1]: SA_EINVAL. */
 typedef struct sa_kmer_table sa_kmer_table_t;
 typedef struct sa_kmer_row {
     int64_t descaled_units;   /* "%f" of the descaled mean in 1e-6                                        */

@@ -53,6 +53,7 @@
 #define KT_RUN_BITS 40
 #define KT_RUN_MASK ((1ull << KT_RUN_BITS) - 1ull)
 #define KT_UNITS_LIMIT 2147483648.0      // descaled values beyond +-2^31 are refused (their "%f" is not computed here)
+#define KT_DESC_LIMIT 2147.483648        // a table row's descaled value is below this in magnitude: |units| <= 2^31 (k_kt_stats squares them)
 #define KT_ERR_RANGE 1                   // err word bits
 #define KT_ERR_BOUNDS 2
 
@@ -70,6 +71,11 @@ __host__ __device__ static inline int kt_f6_units(double v, long long *units, in
     *units = (long long) r;
     *neg_zero = (signbit(v) && *units == 0) ? 1 : 0;
     return SA_OK;
+}
+// a row's descaled value: only what k_kt_stats can square in 64 bits is taken into a table
+__host__ __device__ static inline int kt_desc_units(double v, long long *units, int *neg_zero) {
+    if (!(fabs(v) < KT_DESC_LIMIT)) return SA_EUNSUPPORTED;
+    return kt_f6_units(v, units, neg_zero);
 }
 
 struct KtRow {                  // a kept row in HBM (24 bytes)
@@ -263,7 +269,7 @@ __global__ __launch_bounds__(256) void k_kt_compact_rec(KtRecs R, const KtState 
         if (y >= J.n_ev) { atomicOr(err, KT_ERR_BOUNDS); continue; }
         const double e = R.ev[J.ev_off + y], level = R.level[r.kmer];
         const double desc = (e + J.var * level - J.scale * level - J.shift) / J.var;   // signalMachine.c descale(); no contraction
-        if (kt_f6_units(desc, &r.desc, &r.neg_zero) != SA_OK) { atomicOr(err, KT_ERR_RANGE); continue; }
+        if (kt_desc_units(desc, &r.desc, &r.neg_zero) != SA_OK) { atomicOr(err, KT_ERR_RANGE); continue; }
         kt_put(st, off, fill, out, r, err);
     }
 }
@@ -319,7 +325,7 @@ __global__ __launch_bounds__(KT_STATS_THREADS) void k_kt_stats(const KtRow *__re
     for (long long i = t; i < n; i += KT_STATS_THREADS) {
         const long long v = rows[a + i].desc;
         S += v;
-        const unsigned long long u = (unsigned long long) (v < 0 ? -v : v), sq = u * u;   // |v| < 2^31: u^2 < 2^62
+        const unsigned long long u = (unsigned long long) (v < 0 ? -v : v), sq = u * u;   // |v| <= 2^31 (KT_DESC_LIMIT): u^2 <= 2^62
         lo += sq;
         hi += lo < sq ? 1ull : 0ull;
     }
@@ -691,7 +697,7 @@ extern "C" int sa_kmer_table_add_rows(sa_kmer_table_t *t, int strand, const int3
         KtRow r;
         r.kmer = kmer_ids[i];
         r.key = ((unsigned long long) pu << KT_RUN_BITS) | (KT_RUN_MASK - (t->run_next + (unsigned long long) i));
-        if (kt_f6_units(descaled[i], &r.desc, &r.neg_zero) != SA_OK) return SA_EUNSUPPORTED;
+        if (kt_desc_units(descaled[i], &r.desc, &r.neg_zero) != SA_OK) return SA_EUNSUPPORTED;
         rows.push_back(r);
     }
     int rc = SA_OK;

@@ -113,3 +113,57 @@ def write_trained(prior_path, st, out_path, weight=100.0, min_sd=0.0, mod_only=F
         for v in params:
             f.write("%s\t" % v)
         f.write("\n")
+
+
+RUN_BITS = 40
+RUN_MASK = (1 << RUN_BITS) - 1
+LEVELS = (50, 40, 30, 20, 10, 0)
+
+
+def min_units(min_prob):
+    """the smallest printed posterior, in units, with float(text) >= min_prob"""
+    u = 0
+    while u <= 1000000 and not (u / 1e6 >= min_prob):
+        u += 1
+    return u
+
+
+def key(prob_units, ordinal):
+    """a row's selection key as sa_train.hip defines it"""
+    return (int(prob_units) << RUN_BITS) | (RUN_MASK - int(ordinal))
+
+
+def top_n_arrays(kmer, prob_units, n, min_units, first_ordinal=0):
+    """top_n over integer arrays: row i has run ordinal first_ordinal + i -> {kmer_id: kept run ordinals (int64 array), posterior
+    descending, then ordinal ascending}"""
+    kmer = np.asarray(kmer, dtype=np.int64)
+    pu = np.asarray(prob_units, dtype=np.int64)
+    idx = np.nonzero(pu >= min_units)[0]
+    idx = idx[np.lexsort((idx, -pu[idx], kmer[idx]))]   # k-mer, then posterior descending, then run order
+    km = kmer[idx]
+    start = np.nonzero(np.r_[True, km[1:] != km[:-1]])[0] if len(km) else np.zeros(0, dtype=np.int64)
+    end = np.r_[start[1:], len(km)]
+    return {int(km[a]): idx[a:min(b, a + n)] + first_ordinal for a, b in zip(start.tolist(), end.tolist())}
+
+
+def settle_shift(keys, n):
+    """The radix selection of one k-mer written out: -> (shift, owner lane, digit) of the level that settles it, (None, None,
+    None) if it has at most n candidates (all are kept at the first level)."""
+    keys = [int(k) for k in keys]
+    if len(keys) <= n:
+        return None, None, None
+    need = n
+    for shift in LEVELS:
+        count = {}
+        for k in keys:
+            d = (k >> shift) & 1023
+            count[d] = count.get(d, 0) + 1
+        acc = 0
+        for digit in sorted(count, reverse=True):   # from the top bin down to the one holding the need-th largest key
+            if acc + count[digit] >= need:
+                break
+            acc += count[digit]
+        need -= acc
+        if count[digit] == need or shift == 0:
+            return shift, digit // 16, digit
+        keys = [k for k in keys if ((k >> shift) & 1023) == digit]

@@ -68,6 +68,12 @@ def expected_rows(rows, n, min_prob):
 
 def check_table(tab, rows, n, min_prob, strand=0):
     exp, kept = expected_rows(rows, n, min_prob)
+    check_rows_and_stats(tab, exp, strand)
+    return exp, kept
+
+
+def check_rows_and_stats(tab, exp, strand=0):
+    """exp: the KMER_ROW-shaped tuples the strand has to hold, in the table's order"""
     got = tab.rows(strand)
     g = list(zip(got["kmer_id"].tolist(), got["prob_units"].tolist(), got["descaled_units"].tolist(), got["neg_zero"].tolist(),
                  got["run"].tolist()))
@@ -84,7 +90,6 @@ def check_table(tab, rows, n, min_prob, strand=0):
             assert st["n"][km] == nn
             assert st["m"][km].tobytes() == np.float64(m).tobytes(), (km, med)
             assert st["s"][km].tobytes() == np.float64(s).tobytes(), (km, med)
-    return exp, kept
 
 
 def cpg_jobs():
@@ -315,15 +320,17 @@ def test_checkpoint_and_rollback(tmp_path):
     b2.close()
 
 
-def test_rows_tied_at_the_cutoff_take_run_order():
-    """N = 1 over reads whose best rows print 1.000000 many times: the run-order levels decide, on the tied rows only"""
+@pytest.mark.parametrize("flags", [0, sa.FLAG_PAIRS8])
+def test_rows_tied_at_the_cutoff_take_run_order(flags):
+    """N = 1 over reads whose best rows print 1.000000 many times: the run-order levels decide, on the tied rows only (copied
+    out of 16- and of 8-byte records)"""
     pm = sa.Model.load(cases.MODEL_6MER)
     _, k = pm.alphabet()
     p = sa.default_params()
     jobs = cases.synthetic_jobs(cases.MODEL_6MER, 6, 1500, 1300)
-    b = sa.Batch(pm, p, jobs)
+    b = sa.Batch(pm, p, jobs, flags=flags)
     b.run()
-    rows = batch_rows(b, jobs, pm.table5(), pm, k)
+    rows = batch_rows(b, jobs, pm.table5(), pm, k, p8=bool(flags))
     tied = {}
     for r in rows:
         if r[3] == "1.000000":
@@ -332,5 +339,28 @@ def test_rows_tied_at_the_cutoff_take_run_order():
     tab = sa.KmerTable(pm, 1, 0.8)
     tab.add_batch(b, 0)
     check_table(tab, rows, 1, 0.8)
+    tab.close()
+    b.close()
+
+
+def test_planted_rows_win_ties_against_a_batch():
+    """rows from add_rows and records of a batch tied at 1.000000, N = 1: the planted rows came first and are the ones kept"""
+    pm = sa.Model.load(cases.MODEL_6MER)
+    _, k = pm.alphabet()
+    p = sa.default_params()
+    jobs = cases.synthetic_jobs(cases.MODEL_6MER, 6, 1500, 1300)
+    b = sa.Batch(pm, p, jobs)
+    b.run()
+    rows = batch_rows(b, jobs, pm.table5(), pm, k)
+    ten = sorted({r[1] for r in rows if r[3] == "1.000000"})[:10]
+    assert len(ten) == 10
+    planted = [("t", km, "%f" % (50.0 + 1.5 * i), "1.000000") for i, km in enumerate(ten)]
+    tab = sa.KmerTable(pm, 1, 0.8)
+    tab.add_rows([r[1] for r in planted], [float(r[2]) for r in planted], [1.0] * 10)
+    tab.add_batch(b, 0)
+    exp, _ = check_table(tab, planted + rows, 1, 0.8)
+    by = {r[0]: r for r in exp}
+    for i, km in enumerate(ten):
+        assert by[km][1:] == (1000000, ref.units(planted[i][2])[0], 0, i)
     tab.close()
     b.close()
