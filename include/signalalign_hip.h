@@ -492,6 +492,44 @@ int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t *jobs, cons
 /* the detector's device and pinned-host scratch, kept between calls (grow only), returned */
 void sa_detect_release(void);
 
+/* ---- raw current -> the in-memory .npRead of a 1D read ---------------------------------------------------------------
+ * What NanoporeRead (src/signalalign/nanoporeRead.py) holds for a 1D read after load_from_raw2 has written the basecalled
+ * event table: the mapped rows (kmer_idx >= 0) of sa_raw_event_align_batch in time order, in the .npRead's own layout, and
+ * the strand event map over them.  Detection, MoM scalings and event alignment are the entry points above (one detector, one
+ * event aligner); the base-to-event map, the compaction to mapped rows and the table's seconds are one more kernel
+ * (k_raw_finish, one wave per read) on the rows the detector left on the device -- bit-identical to
+ * sa_raw_event_align_batch's rows; p_model_state and make_event_map (which compares those values) are computed on the host.
+ * DNA, template strand: SA_FLAG_RNA returns SA_EUNSUPPORTED, and so does an HDP model (as sa_raw_event_align_batch).
+ * SA_EINVAL, before any device use: a NULL array, n_jobs < 0, a read without samples, a sequence shorter than the model's k,
+ * a detector window < 1. */
+#define SA_RAW_MAP_LENGTH 32   /* status bit: the event map's length differs from the read's ("Read and event map lengths do not match") */
+typedef struct sa_raw_npread {
+    int32_t status;            /* sa_raw_event_align_batch's bits | SA_RAW_MAP_LENGTH; non-zero: nothing below is filled (the
+                                  arrays are NULL, n_events 0) but read_len and the MoM scalings                             */
+    int64_t n_events;          /* mapped rows only: the rows the reference writes to the basecalled table                    */
+    double *events4;           /* n_events x {mean, stdv, length, start - start of row 0}: the .npRead layout, sa_job_t's stride 4 */
+    int32_t *kmer_idx, *move;  /* per row */
+    double *p_model_state;     /* per row */
+    int64_t *raw_start, *raw_length;
+    int64_t read_len;
+    int64_t *strand_event_map; /* read_len entries: NanoporeRead.make_event_map (nanoporeRead.py:313-333) */
+    double mom_shift, mom_scale;
+} sa_raw_npread_t;
+/* params NULL: SA_DETECTOR_DNA.  out: n_jobs entries, released with sa_raw_npread_free (a read's arrays are one allocation: do
+ * not free them one by one).  A read the chain rejects fails alone: its status is set, its arrays are NULL, the others are
+ * what they are without it.  kernel_ms_out (may be NULL): detection + alignment + finishing kernels. */
+int  sa_npread_from_raw_batch(const sa_model_t *m, const sa_raw_job_t *jobs, const char *const *sequences, int64_t n_jobs,
+                              const sa_detector_params_t *params, int device, unsigned flags,
+                              sa_raw_npread_t *out, double *kernel_ms_out);
+void sa_raw_npread_free(sa_raw_npread_t *r, int64_t n);
+/* HIP-event time of k_raw_finish alone in the process's last sa_npread_from_raw_batch (probes/raw_front_door_rate.py) */
+double sa_npread_last_finish_ms(void);
+/* The fourteen lines of NanoporeRead.Write (nanoporeRead.py:438-540) for a 1D read: 2D length 0, the strand parameters
+ * 1 1 1 1 1 0 twice and has-2D 0 (signalMachine estimates them anew), no complement, model states spelled from `sequence` at
+ * kmer_idx, floats as Python prints a float64 (sa_format_py_repr), every list entry followed by a blank.  SA_EINVAL: NULL
+ * argument, a read with status != 0, a sequence whose length is not read_len; SA_EIO: the file cannot be written. */
+int  sa_raw_npread_write(const sa_raw_npread_t *r, const char *sequence, const sa_model_t *m, const char *path);
+
 /* fastaHandler_getSubSequence (impl/fasta_handler.c:15-44, htslib faidx underneath): bases [start, end) of the record
  * `name` (the header's first word) of a FASTA file; strand == 0 asks htslib for [end, start - 1] as the reference does.
  * Uses <path>.fai when it exists, otherwise scans the file (nothing is written).  *out is freed with sa_free.

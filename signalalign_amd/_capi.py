@@ -201,6 +201,20 @@ class DetectorParams(C.Structure):
 DETECTOR_DNA = (3, 6, 1.4, 9.0, 0.2)
 DETECTOR_RNA = (7, 14, 2.5, 9.0, 1.0)
 RAW_NO_PEAK = 16
+RAW_MAP_LENGTH = 32
+
+
+class RawNpRead(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_events", C.c_int64), ("events4", C.POINTER(C.c_double)),
+                ("kmer_idx", C.POINTER(C.c_int32)), ("move", C.POINTER(C.c_int32)), ("p_model_state", C.POINTER(C.c_double)),
+                ("raw_start", C.POINTER(C.c_int64)), ("raw_length", C.POINTER(C.c_int64)), ("read_len", C.c_int64),
+                ("strand_event_map", C.POINTER(C.c_int64)), ("mom_shift", C.c_double), ("mom_scale", C.c_double)]
+
+
+class RawRead(C.Structure):
+    _fields_ = [("digitisation", C.c_float), ("offset", C.c_float), ("range", C.c_float), ("sample_rate", C.c_float),
+                ("start_time", C.c_float), ("n_samples", C.c_int64), ("seq_len", C.c_int64), ("sequence", C.c_void_p),
+                ("samples", C.POINTER(C.c_int16))]
 RAW_EVENT_DTYPE = np.dtype([("raw_start", "<i8"), ("raw_length", "<i8"), ("mean", "<f8"), ("stdv", "<f8"), ("start", "<f8"),
                             ("length", "<f8"), ("kmer_idx", "<i4"), ("move", "<i4"), ("p_model_state", "<f8")])
 
@@ -232,7 +246,7 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_batch_create", "sa_batch_create_noise_scaled", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
            "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
            "sa_plan_check_path_records", "sa_dplan_compare",
-           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read",
+           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_npread_from_raw_batch", "sa_raw_npread_free", "sa_raw_npread_write", "sa_npread_last_finish_ms", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read",
            "sa_snp_marginals_create", "sa_snp_marginals_destroy", "sa_snp_marginals_add_sites", "sa_snp_marginals_add_batch",
            "sa_snp_marginals_checkpoint", "sa_snp_marginals_rollback", "sa_snp_marginals_finish", "sa_snp_group_sites",
            "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals",
@@ -415,6 +429,16 @@ def lib():
                                            C.POINTER(DetectorParams), C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip,
                                            C.POINTER(C.c_void_p), ip, i32p, dp, dp, dp]
     L.sa_detect_release.restype = None
+    L.sa_npread_from_raw_batch.argtypes = [C.c_void_p, C.POINTER(RawJob), C.POINTER(C.c_char_p), C.c_int64,
+                                           C.POINTER(DetectorParams), C.c_int, C.c_uint, C.POINTER(RawNpRead), dp]
+    L.sa_raw_npread_free.argtypes = [C.POINTER(RawNpRead), C.c_int64]
+    L.sa_raw_npread_free.restype = None
+    L.sa_raw_npread_write.argtypes = [C.POINTER(RawNpRead), C.c_char_p, C.c_void_p, C.c_char_p]
+    L.sa_npread_last_finish_ms.restype = C.c_double
+    L.sa_rawread_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(RawRead))]
+    L.sa_rawread_free.argtypes = [C.POINTER(RawRead)]
+    L.sa_rawread_free.restype = None
+    L.sa_rawread_is.argtypes = [C.c_char_p]
     L.sa_mea_batch.argtypes = [C.POINTER(MeaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, i32p, dp]
     L.sa_batch_mea.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, dp]
     L.sa_batch_site_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(SiteCall)), ip, dp]
@@ -1301,6 +1325,61 @@ def raw_event_align_batch(model, jobs, sequences, rna=False, params=None, device
 
 def detect_release():
     lib().sa_detect_release()
+
+
+def npread_from_raw_batch(model, jobs, sequences, params=None, device=0, flags=0, stats=None, write=None):
+    """sa_npread_from_raw_batch: per read a dict with status, read_len, shift, scale and -- when status is 0 -- events4
+    (n x 4: mean, stdv, length, start - start of row 0), kmer_idx, move, p_model_state, raw_start, raw_length and
+    strand_event_map; a failed read has None in their place.  write: optional list of paths (None to skip a read) that
+    sa_raw_npread_write writes before the results are released.  stats (a dict, optional): kernel_ms and finish_ms
+    (k_raw_finish alone)."""
+    n = len(jobs)
+    arr, keep = _raw_jobs(jobs)
+    seqs = [s.encode() for s in sequences]
+    sp = (C.c_char_p * max(n, 1))(*seqs)
+    res = (RawNpRead * max(n, 1))()
+    kms = C.c_double()
+    _chk(lib().sa_npread_from_raw_batch(model._h, arr, sp, n, _detector_params(params), device, flags, res, C.byref(kms)),
+         "sa_npread_from_raw_batch")
+    del keep
+    if stats is not None:
+        stats["kernel_ms"] = kms.value
+        stats["finish_ms"] = lib().sa_npread_last_finish_ms()
+    out = []
+    try:
+        for i in range(n):
+            r = res[i]
+            d = dict(status=int(r.status), read_len=int(r.read_len), shift=float(r.mom_shift), scale=float(r.mom_scale),
+                     n_events=int(r.n_events))
+            ne = int(r.n_events)
+            for name, width in (("events4", 4), ("kmer_idx", 1), ("move", 1), ("p_model_state", 1), ("raw_start", 1),
+                                ("raw_length", 1), ("strand_event_map", 0)):
+                ptr = getattr(r, name)
+                if not ptr:
+                    d[name] = None
+                    continue
+                cnt = int(r.read_len) if width == 0 else ne * width
+                a = np.ctypeslib.as_array(ptr, shape=(cnt,)).copy()
+                d[name] = a.reshape(ne, 4) if width == 4 else a
+            out.append(d)
+            if write is not None and write[i] is not None:
+                _chk(lib().sa_raw_npread_write(C.byref(r), seqs[i], model._h, os.fsencode(write[i])), "sa_raw_npread_write")
+    finally:
+        lib().sa_raw_npread_free(res, n)
+    return out
+
+
+def rawread_load(path):
+    """sa_rawread_load (the CLI's loader of a raw-read file): dict(raw, digitisation, offset, range, sample_rate, start_time,
+    sequence); raises SaError as the loader refuses."""
+    pr = C.POINTER(RawRead)()
+    _chk(lib().sa_rawread_load(os.fsencode(path), C.byref(pr)), "sa_rawread_load")
+    r = pr.contents
+    out = dict(raw=np.ctypeslib.as_array(r.samples, shape=(int(r.n_samples),)).copy(), digitisation=float(r.digitisation),
+               offset=float(r.offset), range=float(r.range), sample_rate=float(r.sample_rate), start_time=float(r.start_time),
+               sequence=C.string_at(r.sequence, int(r.seq_len)).decode())
+    lib().sa_rawread_free(pr)
+    return out
 
 
 def mea_batch(jobs, device=0, flags=0, stats=None):

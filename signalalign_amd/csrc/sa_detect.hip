@@ -23,6 +23,10 @@
 //
 // Mapping: k_det_prefix and k_det_peaks run one lane per read (64 reads per wave), each lane streaming its own read
 // with 16-byte loads; k_det_tstat is one thread per sample (both windows), k_det_events one block per read.
+//
+// sa_npread_from_raw_batch goes on from the detector's rows on the device to the in-memory .npRead of a 1D read: the same
+// MoM scalings and event aligner, then k_raw_finish (one wave per read: the base-to-event map, the compaction to mapped rows,
+// the table's seconds); p_model_state and make_event_map on the host ("Reads from raw current").
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -235,8 +239,107 @@ __global__ __launch_bounds__(256) void k_det_events(const DetJob *__restrict__ j
     }
 }
 
-// Device and pinned-host scratch of sa_detect_events_batch, kept between calls (sa_scratch.h).
-enum { DET_WS, DET_EV, DET_HRAW, DET_HEV };
+// ---- k_raw_finish: the detector's rows and the event aligner's pairs -> the rows of a 1D .npRead (sa_npread_from_raw_batch) ----
+struct FinJob {
+    long long ev_off;    // the read's rows in the detector's event block; also where its output rows start
+    long long pair_off;  // its pairs {k-mer, event}, ascending
+    int n_ev, n_pairs;   // n_pairs == 0: a read the chain rejected -- no rows
+    float sample_rate, start_time;
+};
+
+struct FinOut {          // each array has an entry per detected event; a read's rows start at its ev_off, mapped rows only, packed
+    double *ev4;         // {mean, stdv, length, start - start of row 0}
+    long long *raw_start, *raw_length;
+    int *kmer_idx, *move;
+    int *n_rows;         // per read
+};
+
+#define FIN_WAVE 64
+#define FIN_WAVES 4      // reads per block
+
+// One wave per read.
+//   1. all lanes clear the read's per-event k-mer index (-1) and move (0);
+//   2. alignment_to_base_event_map (impl/eventAligner.c:1310-1360): the pairs come in 64 at a time, one per lane, and are walked in
+//      order through wave-uniform state; lane 0 stores an event's k-mer index and move when the walk leaves the event;
+//   3. the mapped rows (kmer_idx >= 0) are compacted, 64 events a step: ballot of the mapped lanes, a lane's row is the running
+//      count plus the mapped lanes below it; event_table_to_basecalled_table's seconds in its own operation order (fp64 + - / and
+//      one float division, no contraction in this file).
+// Between the steps the wave's own stores have to be visible to its other lanes: the block synchronises (every wave of the block
+// reaches both barriers, also one without a read).
+__global__ __launch_bounds__(FIN_WAVE * FIN_WAVES) void k_raw_finish(const FinJob *__restrict__ jobs, int n_jobs, const DetEvent *__restrict__ ev,
+                                                                     const int2 *__restrict__ pairs, int *__restrict__ kidx,
+                                                                     int *__restrict__ mv, FinOut O) {
+    const int lane = threadIdx.x & (FIN_WAVE - 1);
+    const int r = blockIdx.x * FIN_WAVES + (int) (threadIdx.x / FIN_WAVE);
+    const bool live = r < n_jobs;
+    FinJob J = {0, 0, 0, 0, 1.0f, 0.0f};
+    if (live) J = jobs[r];
+    int *ki = kidx + J.ev_off, *mo = mv + J.ev_off;
+    for (int e = lane; e < J.n_ev; e += FIN_WAVE) { ki[e] = -1; mo[e] = 0; }
+    __syncthreads();
+    {
+        const int2 *p = pairs + J.pair_off;
+        int prev_k = 0, prev_e = -1, cur_k = -1, cur_mv = 0;
+        for (int base = 0; base < J.n_pairs; base += FIN_WAVE) {
+            const int2 mine = base + lane < J.n_pairs ? p[base + lane] : make_int2(0, 0);
+            const int n_here = min(FIN_WAVE, J.n_pairs - base);
+            for (int t = 0; t < n_here; t++) {
+                const int k = __shfl(mine.x, t), e = __shfl(mine.y, t);
+                if (e == prev_e) {
+                    if (k == prev_k || prev_k == 0) continue;   // the reference reports the first, skips the second
+                    cur_k = k;
+                    cur_mv += k - prev_k;
+                } else {
+                    if (lane == 0 && prev_e >= 0 && prev_e < J.n_ev) { ki[prev_e] = cur_k; mo[prev_e] = cur_mv; }
+                    cur_k = k;
+                    cur_mv = k - prev_k;
+                }
+                prev_k = k;
+                prev_e = e;
+            }
+        }
+        if (lane == 0 && prev_e >= 0 && prev_e < J.n_ev) { ki[prev_e] = cur_k; mo[prev_e] = cur_mv; }
+    }
+    __syncthreads();
+    if (!live) return;
+    const DetEvent *src = ev + J.ev_off;
+    const float sr = J.sample_rate;
+    const double st_sr = (double) (J.start_time / sr);
+    // row 0: the first mapped event
+    int first = -1;
+    for (int base = 0; base < J.n_ev && first < 0; base += FIN_WAVE) {
+        const int e = base + lane;
+        const unsigned long long m = __ballot(e < J.n_ev && ki[e] >= 0);
+        if (m) first = base + __ffsll((long long) m) - 1;
+    }
+    int n_rows = 0;
+    if (first >= 0) {
+        const double start0 = ((double) (unsigned long long) src[first].start) / sr + st_sr;
+        for (int base = 0; base < J.n_ev; base += FIN_WAVE) {
+            const int e = base + lane;
+            const int k = e < J.n_ev ? ki[e] : -1;
+            const unsigned long long m = __ballot(k >= 0);
+            if (k >= 0) {
+                const long long row = J.ev_off + n_rows + __popcll(m & ((1ull << lane) - 1ull));
+                const DetEvent v = src[e];
+                O.ev4[4 * row] = (double) v.mean;
+                O.ev4[4 * row + 1] = (double) v.stdv;
+                O.ev4[4 * row + 2] = (double) (v.length / sr);
+                O.ev4[4 * row + 3] = (((double) (unsigned long long) v.start) / sr + st_sr) - start0;
+                O.raw_start[row] = v.start;
+                O.raw_length[row] = (long long) (unsigned long long) v.length;
+                O.kmer_idx[row] = k;
+                O.move[row] = mo[e];
+            }
+            n_rows += __popcll(m);
+        }
+    }
+    if (lane == 0) O.n_rows[r] = n_rows;
+}
+
+// Device and pinned-host scratch of sa_detect_events_batch, kept between calls (sa_scratch.h); the last two are the finishing
+// stage's (sa_npread_from_raw_batch).
+enum { DET_WS, DET_EV, DET_HRAW, DET_HEV, DET_FIN, DET_HFIN };
 static SaScratch g_det_ws;
 
 extern "C" void sa_detect_release(void) {
@@ -246,22 +349,18 @@ extern "C" void sa_detect_release(void) {
 
 static const sa_detector_params_t k_det_dna = SA_DETECTOR_DNA, k_det_rna = SA_DETECTOR_RNA;
 
-extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, const sa_detector_params_t *params, int device,
-                                      unsigned flags, sa_raw_event_t **events_out, int64_t *n_events_out, int32_t *status_out,
-                                      double *kernel_ms_out) {
-    if ((!jobs && n_jobs > 0) || n_jobs < 0 || n_jobs > (1 << 30) || !events_out || !n_events_out) return SA_EINVAL;
-    const sa_detector_params_t P = params ? *params : ((flags & SA_FLAG_RNA) ? k_det_rna : k_det_dna);
-    if (P.window_length1 < 1 || P.window_length2 < 1) return SA_EINVAL;
-    for (int64_t j = 0; j < n_jobs; j++) {
-        events_out[j] = nullptr;
-        n_events_out[j] = 0;
-        if (status_out) status_out[j] = 0;
-    }
-    for (int64_t j = 0; j < n_jobs; j++)
-        if (!jobs[j].raw || jobs[j].n_samples < 1 || jobs[j].n_samples > 0x7fffffffLL - 8) return SA_EINVAL;
-    int rc = sa_device_check(device);
-    if (rc || n_jobs == 0) return rc;
-    const size_t nj = (size_t) n_jobs;
+// What one detection run leaves behind for the caller, who holds g_det_ws.mu for as long as it reads any of it: the event rows and
+// their offsets on the device (k_raw_finish reads them there), the counts, offsets and rows in pinned memory.
+struct DetRun {
+    const DetEvent *d_ev, *h_ev;
+    const long long *d_off, *h_off;
+    const int *h_cnt;
+    float kms;
+};
+
+// the five detection kernels for a batch whose arguments have been checked; the caller holds g_det_ws.mu
+static int det_run(const sa_raw_job_t *jobs, size_t nj, const sa_detector_params_t &P, int device, DetRun *R) {
+    int rc;
     std::vector<DetJob> hj(nj);
     std::vector<int2> blk;
     long long raw_tot = 0, ps_tot = 0;
@@ -278,7 +377,6 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         for (int b = 0; b < J.n; b += 256) blk.push_back(make_int2((int) j, b));
     }
     SaScratch &W = g_det_ws;
-    std::lock_guard<std::mutex> guard(W.mu);
     if ((rc = W.rebind(device)) != SA_OK) return rc;
     // device workspace: [jobs | blocks | raw | sum | sumsq | t1 | t2 | peaks | counts, offsets]; events in their own block.  Counts
     // and offsets are ONE entry: one copy back
@@ -288,11 +386,7 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
                  o_s = L.add(sizeof(double) * (size_t) ps_tot), o_q = L.add(sizeof(double) * (size_t) ps_tot),
                  o_t1 = L.add(sizeof(float) * (size_t) raw_tot), o_t2 = L.add(sizeof(float) * (size_t) raw_tot),
                  o_pk = L.add(sizeof(int) * (size_t) raw_tot), o_cnt = L.add(res_bytes), o_off = o_cnt + sa_up256(sizeof(int) * nj);
-    float kms = 0;
     long long n_ev_tot = 0;
-    const int *h_cnt;
-    const long long *h_off;
-    const DetEvent *h_ev;
     if ((rc = W.dev(DET_WS, L.end)) != SA_OK) return rc;
     // events: at most one per peak plus one per read, and peaks are fewer than samples
     if ((rc = W.dev(DET_EV, sizeof(DetEvent) * (size_t) (raw_tot + (long long) nj))) != SA_OK) return rc;
@@ -328,16 +422,44 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         SA_HIP_GOTO_DONE(W.time_end());
         SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(DET_HRAW), d + o_cnt, res_bytes, hipMemcpyDeviceToHost, 0));   // the raw image is uploaded by now
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
-        SA_HIP_GOTO_DONE(W.time_ms(&kms));
-        h_cnt = (const int *) W.at(DET_HRAW);
-        h_off = (const long long *) ((const char *) W.at(DET_HRAW) + (o_off - o_cnt));
-        n_ev_tot = h_off[nj];
+        SA_HIP_GOTO_DONE(W.time_ms(&R->kms));
+        R->h_cnt = (const int *) W.at(DET_HRAW);
+        R->h_off = (const long long *) ((const char *) W.at(DET_HRAW) + (o_off - o_cnt));
+        R->d_off = d_off;
+        n_ev_tot = R->h_off[nj];
         if ((rc = W.pin(DET_HEV, sizeof(DetEvent) * (size_t) n_ev_tot)) != SA_OK) goto done;
         SA_HIP_GOTO_DONE(hipMemcpyAsync(W.at(DET_HEV), W.at(DET_EV), sizeof(DetEvent) * (size_t) n_ev_tot, hipMemcpyDeviceToHost, 0));
         SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
+        R->d_ev = (const DetEvent *) W.at(DET_EV);
+        R->h_ev = (const DetEvent *) W.at(DET_HEV);
     }
-    if (kernel_ms_out) *kernel_ms_out = (double) kms;
-    h_ev = (const DetEvent *) W.at(DET_HEV);
+done:
+    return rc;
+}
+
+extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, const sa_detector_params_t *params, int device,
+                                      unsigned flags, sa_raw_event_t **events_out, int64_t *n_events_out, int32_t *status_out,
+                                      double *kernel_ms_out) {
+    if ((!jobs && n_jobs > 0) || n_jobs < 0 || n_jobs > (1 << 30) || !events_out || !n_events_out) return SA_EINVAL;
+    const sa_detector_params_t P = params ? *params : ((flags & SA_FLAG_RNA) ? k_det_rna : k_det_dna);
+    if (P.window_length1 < 1 || P.window_length2 < 1) return SA_EINVAL;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        events_out[j] = nullptr;
+        n_events_out[j] = 0;
+        if (status_out) status_out[j] = 0;
+    }
+    for (int64_t j = 0; j < n_jobs; j++)
+        if (!jobs[j].raw || jobs[j].n_samples < 1 || jobs[j].n_samples > 0x7fffffffLL - 8) return SA_EINVAL;
+    int rc = sa_device_check(device);
+    if (rc || n_jobs == 0) return rc;
+    const size_t nj = (size_t) n_jobs;
+    std::lock_guard<std::mutex> guard(g_det_ws.mu);
+    DetRun run;
+    if ((rc = det_run(jobs, nj, P, device, &run)) != SA_OK) return rc;
+    const int *h_cnt = run.h_cnt;
+    const long long *h_off = run.h_off;
+    const DetEvent *h_ev = run.h_ev;
+    if (kernel_ms_out) *kernel_ms_out = (double) run.kms;
     {
         std::atomic<bool> oom(false);
         sa_parallel_for(nj, [&](size_t j) {
@@ -365,10 +487,34 @@ extern "C" int sa_detect_events_batch(const sa_raw_job_t *jobs, int64_t n_jobs, 
         });
         if (oom) rc = SA_ENOMEM;
     }
-done:
     if (rc != SA_OK)
         for (size_t j = 0; j < nj; j++) { free(events_out[j]); events_out[j] = nullptr; n_events_out[j] = 0; }
     return rc;
+}
+
+// MoM scalings of every read's event means (the aligned order) and ONE sa_event_align_batch call with var = 1: the middle of
+// load_from_raw2, shared by sa_raw_event_align_batch and sa_npread_from_raw_batch
+static int raw_scale_and_align(const sa_model_t *m, const char *const *sequences, const std::vector<std::vector<double>> &means,
+                               int device, unsigned flags, std::vector<sa_ea_job_t> &ej, std::vector<double> &shift,
+                               std::vector<double> &scale, sa_ea_pair_t **pairs, int64_t *n_pairs, int32_t *ea_st, double *ea_ms) {
+    const size_t nj = means.size();
+    int rc = SA_OK;
+    for (size_t j = 0; j < nj && rc == SA_OK; j++) {
+        const int64_t n = (int64_t) means[j].size(), len = (int64_t) strlen(sequences[j]);
+        rc = sa_scalings_mom(m, sequences[j], len, means[j].data(), n, flags, &shift[j], &scale[j]);
+        ej[j] = sa_ea_job_t{sequences[j], len, means[j].data(), n, scale[j], shift[j], 1.0};
+    }
+    if (rc == SA_OK) rc = sa_event_align_batch(m, ej.data(), (int64_t) nj, device, flags & SA_FLAG_RNA, pairs, n_pairs, ea_st, nullptr, ea_ms);
+    return rc;
+}
+
+// p_model_state of an event mapped to a k-mer with level (mu, sd) under the MoM scalings:
+// emissions_signal_strawManGetKmerEventMatchProbWithDescaling_MeanOnly with var = 1 (sa_ea.hip: ea_emit), then exp
+static inline double raw_p_model_state(double mean, double mu, double sd, double sc, double sh) {
+    const double c = sd == 0.0 ? -INFINITY : (-0.91893853320467267 - log(sd));
+    const double en = (mean + 1.0 * mu - sc * mu - sh) / 1.0;
+    const double a = (en - mu) / (sd == 0.0 ? 1.0 : sd);
+    return exp(log(1 / 1.0) + (c + (-0.5 * a * a)));
 }
 
 extern "C" int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t *jobs, const char *const *sequences, int64_t n_jobs,
@@ -394,17 +540,12 @@ extern "C" int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t 
     std::vector<sa_ea_pair_t *> pairs(nj, nullptr);
     std::vector<int64_t> n_pairs(nj, 0);
     std::vector<int32_t> ea_st(nj, 0);
-    for (size_t j = 0; j < nj && rc == SA_OK; j++) {
+    for (size_t j = 0; j < nj; j++) {
         const int64_t n = n_events_out[j];
         means[j].resize((size_t) n);
         for (int64_t e = 0; e < n; e++) means[j][(size_t) e] = events_out[j][rna ? n - 1 - e : e].mean;
-        const int64_t len = (int64_t) strlen(sequences[j]);
-        rc = sa_scalings_mom(m, sequences[j], len, means[j].data(), n, flags, &shift[j], &scale[j]);
-        ej[j] = sa_ea_job_t{sequences[j], len, means[j].data(), n, scale[j], shift[j], 1.0};
     }
-    if (rc == SA_OK)
-        rc = sa_event_align_batch(m, ej.data(), n_jobs, device, flags & SA_FLAG_RNA, pairs.data(), n_pairs.data(), ea_st.data(),
-                                  nullptr, &ea_ms);
+    rc = raw_scale_and_align(m, sequences, means, device, flags, ej, shift, scale, pairs.data(), n_pairs.data(), ea_st.data(), &ea_ms);
     if (rc == SA_OK) {
         std::atomic<int> bad(SA_OK);
         sa_parallel_for(nj, [&](size_t j) {
@@ -424,11 +565,7 @@ extern "C" int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t 
                 sa_raw_event_t &r = row(e);
                 const int64_t id = ids[(size_t) k];
                 const double mu = m->table5[5 * id], sd = m->table5[5 * id + 1];
-                // emissions_signal_strawManGetKmerEventMatchProbWithDescaling_MeanOnly with var = 1 (sa_ea.hip: ea_emit)
-                const double c = sd == 0.0 ? -INFINITY : (-0.91893853320467267 - log(sd));
-                const double en = (r.mean + 1.0 * mu - sc * mu - sh) / 1.0;
-                const double a = (en - mu) / (sd == 0.0 ? 1.0 : sd);
-                r.p_model_state = exp(log(1 / 1.0) + (c + (-0.5 * a * a)));
+                r.p_model_state = raw_p_model_state(r.mean, mu, sd, sc, sh);
                 r.kmer_idx = (int32_t) k;
             };
             const sa_ea_pair_t *p = pairs[j];
@@ -474,5 +611,189 @@ extern "C" int sa_raw_event_align_batch(const sa_model_t *m, const sa_raw_job_t 
     }
     if (rc != SA_OK)
         for (size_t j = 0; j < nj; j++) { free(events_out[j]); events_out[j] = nullptr; n_events_out[j] = 0; }
+    return rc;
+}
+
+// ---- raw current -> the in-memory .npRead of a 1D read --------------------------------------------------------------------
+static std::atomic<double> g_fin_ms(0.0);
+
+extern "C" double sa_npread_last_finish_ms(void) { return g_fin_ms.load(); }
+
+extern "C" void sa_raw_npread_free(sa_raw_npread_t *r, int64_t n) {
+    if (!r) return;
+    for (int64_t j = 0; j < n; j++) {
+        free(r[j].events4);   // a read's arrays are one allocation that events4 heads
+        memset(&r[j], 0, sizeof(r[j]));
+    }
+}
+
+// NanoporeRead.make_event_map (nanoporeRead.py:313-333) over the rows; returns the map's length, of which at most `cap`
+// entries are written
+static int64_t raw_make_event_map(const int32_t *move, const double *p, int64_t n, int k, int64_t *map, int64_t cap) {
+    int64_t len = 0;
+    auto put = [&](int64_t v) { if (len < cap) map[len] = v; len++; };
+    auto last = [&]() -> int64_t { return len - 1 < cap ? map[len - 1] : map[cap - 1]; };
+    put(0);
+    double previous = 0;
+    for (int64_t i = 1; i < n; i++) {
+        const int32_t mv = move[i];
+        if (mv == 1) put(i);
+        if (mv > 1) {
+            for (int32_t s = 0; s < mv - 1; s++) put(i - 1);
+            put(i);
+        }
+        if (mv == 0 && p[i] > previous && len - 1 < cap) map[len - 1] = i;
+        previous = p[i];
+    }
+    const int64_t fin = last();
+    for (int s = 0; s < k - 1; s++) put(fin);
+    return len;
+}
+
+extern "C" int sa_npread_from_raw_batch(const sa_model_t *m, const sa_raw_job_t *jobs, const char *const *sequences, int64_t n_jobs,
+                                        const sa_detector_params_t *params, int device, unsigned flags, sa_raw_npread_t *out,
+                                        double *kernel_ms_out) {
+    if (!m || n_jobs < 0 || n_jobs > (1 << 30) || ((!jobs || !sequences || !out) && n_jobs > 0)) return SA_EINVAL;
+    if (flags & SA_FLAG_RNA) return SA_EUNSUPPORTED;   // the reference's RNA path reverses reads and events: not built here
+    if (m->hdp) return SA_EUNSUPPORTED;                // as sa_raw_event_align_batch
+    const sa_detector_params_t P = params ? *params : k_det_dna;
+    if (P.window_length1 < 1 || P.window_length2 < 1) return SA_EINVAL;
+    for (int64_t j = 0; j < n_jobs; j++) memset(&out[j], 0, sizeof(out[j]));
+    for (int64_t j = 0; j < n_jobs; j++)
+        if (!jobs[j].raw || jobs[j].n_samples < 1 || jobs[j].n_samples > 0x7fffffffLL - 8 || !sequences[j] ||
+            (int64_t) strlen(sequences[j]) < m->k)
+            return SA_EINVAL;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    int rc = sa_device_check(device);
+    if (rc || n_jobs == 0) return rc;
+    const size_t nj = (size_t) n_jobs;
+    SaScratch &W = g_det_ws;
+    std::lock_guard<std::mutex> guard(W.mu);   // held to the end: the detector's rows are read where it left them
+    DetRun run;
+    if ((rc = det_run(jobs, nj, P, device, &run)) != SA_OK) return rc;
+    std::vector<std::vector<double>> means(nj);
+    std::vector<sa_ea_job_t> ej(nj);
+    std::vector<double> shift(nj), scale(nj);
+    std::vector<sa_ea_pair_t *> pairs(nj, nullptr);
+    std::vector<int64_t> n_pairs(nj, 0);
+    std::vector<int32_t> ea_st(nj, 0);
+    std::vector<FinJob> fj(nj);
+    double ea_ms = 0;
+    float fin_ms = 0;
+    sa_parallel_for(nj, [&](size_t j) {
+        const long long a = run.h_off[j], n = run.h_off[j + 1] - a;
+        means[j].resize((size_t) n);
+        for (long long e = 0; e < n; e++) means[j][(size_t) e] = run.h_ev[a + e].mean;
+    });
+    rc = raw_scale_and_align(m, sequences, means, device, 0, ej, shift, scale, pairs.data(), n_pairs.data(), ea_st.data(), &ea_ms);
+    if (rc == SA_OK && (rc = W.rebind(device)) == SA_OK) {
+        long long pair_tot = 0;
+        const long long ev_tot = run.h_off[nj];
+        for (size_t j = 0; j < nj; j++) {
+            out[j].status = ea_st[j] | (run.h_cnt[j] == 0 ? SA_RAW_NO_PEAK : 0);
+            FinJob &F = fj[j];
+            F.ev_off = run.h_off[j];
+            F.n_ev = (int) (run.h_off[j + 1] - run.h_off[j]);
+            F.pair_off = pair_tot;
+            F.n_pairs = out[j].status == 0 ? (int) n_pairs[j] : 0;
+            F.sample_rate = jobs[j].sample_rate;
+            F.start_time = jobs[j].start_time;
+            pair_tot += F.n_pairs;
+        }
+        // device block: [jobs, pairs (ONE entry: one copy up) | k-mer index and move per event | the rows: events4, raw_start,
+        // raw_length, kmer_idx, move, rows per read (ONE entry: one copy back into the pinned block)]
+        SaLayout L;
+        const size_t ne = (size_t) ev_tot, in_pairs = sa_up256(sizeof(FinJob) * nj), in_bytes = in_pairs + sizeof(int2) * (size_t) pair_tot;
+        const size_t r_rs = sa_up256(sizeof(double) * 4 * ne), r_rl = r_rs + sa_up256(sizeof(long long) * ne),
+                     r_ki = r_rl + sa_up256(sizeof(long long) * ne), r_mv = r_ki + sa_up256(sizeof(int) * ne),
+                     r_n = r_mv + sa_up256(sizeof(int) * ne), res_bytes = r_n + sizeof(int) * nj;
+        const size_t o_in = L.add(in_bytes), o_ki = L.add(sizeof(int) * ne), o_mv = L.add(sizeof(int) * ne), o_res = L.add(res_bytes);
+        if ((rc = W.dev(DET_FIN, L.end)) != SA_OK) goto done;
+        if ((rc = W.pin(DET_HFIN, in_bytes > res_bytes ? in_bytes : res_bytes)) != SA_OK) goto done;
+        {
+            char *h = (char *) W.at(DET_HFIN), *d = (char *) W.at(DET_FIN);
+            memcpy(h, fj.data(), sizeof(FinJob) * nj);
+            int2 *hp = (int2 *) (h + in_pairs);
+            sa_parallel_for(nj, [&](size_t j) {
+                if (fj[j].n_pairs > 0) memcpy(hp + fj[j].pair_off, pairs[j], sizeof(int2) * (size_t) fj[j].n_pairs);
+            });
+            FinOut O;
+            O.ev4 = (double *) (d + o_res);
+            O.raw_start = (long long *) (d + o_res + r_rs);
+            O.raw_length = (long long *) (d + o_res + r_rl);
+            O.kmer_idx = (int *) (d + o_res + r_ki);
+            O.move = (int *) (d + o_res + r_mv);
+            O.n_rows = (int *) (d + o_res + r_n);
+            SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_in, h, in_bytes, hipMemcpyHostToDevice, 0));
+            SA_HIP_GOTO_DONE(W.time_begin());
+            hipLaunchKernelGGL(k_raw_finish, dim3((unsigned) ((nj + FIN_WAVES - 1) / FIN_WAVES)), dim3(FIN_WAVE * FIN_WAVES), 0, 0,
+                               (const FinJob *) (d + o_in), (int) nj, run.d_ev, (const int2 *) (d + o_in + in_pairs), (int *) (d + o_ki),
+                               (int *) (d + o_mv), O);
+            SA_HIP_GOTO_DONE(W.time_end());
+            // (the upload image has been consumed by the time the rows come back over it: one stream)
+            SA_HIP_GOTO_DONE(hipMemcpyAsync(h, d + o_res, res_bytes, hipMemcpyDeviceToHost, 0));
+            SA_HIP_GOTO_DONE(hipStreamSynchronize(0));
+            SA_HIP_GOTO_DONE(W.time_ms(&fin_ms));
+            g_fin_ms = (double) fin_ms;
+            // the host's share: p_model_state (an exp and a log) and make_event_map, which compares those values
+            const double *h_ev4 = (const double *) h;
+            const long long *h_rs = (const long long *) (h + r_rs), *h_rl = (const long long *) (h + r_rl);
+            const int *h_ki = (const int *) (h + r_ki), *h_mv = (const int *) (h + r_mv), *h_n = (const int *) (h + r_n);
+            std::atomic<int> bad(SA_OK);
+            sa_parallel_for(nj, [&](size_t j) {
+                sa_raw_npread_t &o = out[j];
+                o.read_len = ej[j].seq_len;
+                o.mom_shift = shift[j];
+                o.mom_scale = scale[j];
+                if (o.status != 0) return;
+                const size_t n = (size_t) h_n[j], a = (size_t) fj[j].ev_off, rl = (size_t) o.read_len;
+                if (n == 0) { o.status = SA_RAW_MAP_LENGTH; return; }
+                const int64_t n_kmers = o.read_len - (m->k - 1);
+                std::vector<int32_t> ids((size_t) n_kmers);
+                const int rck = sa_ea_kmer_ids(m, sequences[j], n_kmers, false, ids.data());
+                if (rck) { bad = rck; return; }
+                // one allocation per read: doubles, then 64-bit integers, then 32-bit ones
+                char *blk = (char *) malloc(sizeof(double) * 5 * n + sizeof(int64_t) * (2 * n + rl) + sizeof(int32_t) * 2 * n);
+                if (!blk) { bad = SA_ENOMEM; return; }
+                o.n_events = (int64_t) n;
+                o.events4 = (double *) blk;
+                o.p_model_state = o.events4 + 4 * n;
+                o.raw_start = (int64_t *) (o.p_model_state + n);
+                o.raw_length = o.raw_start + n;
+                o.strand_event_map = o.raw_length + n;
+                o.kmer_idx = (int32_t *) (o.strand_event_map + rl);
+                o.move = o.kmer_idx + n;
+                memcpy(o.events4, h_ev4 + 4 * a, sizeof(double) * 4 * n);
+                memcpy(o.raw_start, h_rs + a, sizeof(int64_t) * n);
+                memcpy(o.raw_length, h_rl + a, sizeof(int64_t) * n);
+                memcpy(o.kmer_idx, h_ki + a, sizeof(int32_t) * n);
+                memcpy(o.move, h_mv + a, sizeof(int32_t) * n);
+                bool in_range = true;
+                for (size_t i = 0; i < n; i++) {
+                    const int32_t kx = o.kmer_idx[i];
+                    if (kx < 0 || kx >= n_kmers) { in_range = false; break; }
+                    const int64_t id = ids[(size_t) kx];
+                    o.p_model_state[i] = raw_p_model_state(o.events4[4 * i], m->table5[5 * id], m->table5[5 * id + 1], scale[j], shift[j]);
+                }
+                if (!in_range || raw_make_event_map(o.move, o.p_model_state, (int64_t) n, m->k, o.strand_event_map, o.read_len) != o.read_len) {
+                    // the reference's "Read and event map lengths do not match"
+                    free(blk);
+                    const int64_t len = o.read_len;
+                    memset(&o, 0, sizeof(o));
+                    o.status = SA_RAW_MAP_LENGTH;
+                    o.read_len = len;
+                    o.mom_shift = shift[j];
+                    o.mom_scale = scale[j];
+                }
+            });
+            rc = bad;
+        }
+    }
+done:
+    if (kernel_ms_out) *kernel_ms_out = (double) run.kms + ea_ms + (double) fin_ms;
+    for (size_t j = 0; j < nj; j++) free(pairs[j]);
+    if (rc != SA_OK) {
+        for (size_t j = 0; j < nj; j++) { free(out[j].events4); memset(&out[j], 0, sizeof(out[j])); }
+    }
     return rc;
 }

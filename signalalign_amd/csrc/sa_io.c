@@ -402,6 +402,103 @@ done:
     return SA_OK;
 }
 
+/* NanoporeRead.Write (nanoporeRead.py:438-540) for a 1D read built from raw current */
+int sa_raw_npread_write(const sa_raw_npread_t *r, const char *sequence, const sa_model_t *m, const char *path) {
+    if (!r || !sequence || !m || !path || r->status != 0 || r->n_events < 1 || !r->events4 || !r->kmer_idx || !r->p_model_state ||
+        !r->strand_event_map || (int64_t) strlen(sequence) != r->read_len)
+        return SA_EINVAL;
+    const int k = m->k;
+    for (int64_t i = 0; i < r->n_events; i++)
+        if (r->kmer_idx[i] < 0 || r->kmer_idx[i] + k > r->read_len) return SA_EINVAL;
+    FILE *f = fopen(path, "w");
+    if (!f) return SA_EIO;
+    char num[40];
+    /* line 1: 2D length, template events, complement events, template read length, complement read length, the two
+     * strands' scale shift var scale_sd var_sd drift, has 2D */
+    fprintf(f, "0 %" PRId64 " 0 %" PRId64 " 0 1 1 1 1 1 0 1 1 1 1 1 0 0\n", r->n_events, r->read_len);
+    fputs("\n", f);                                   /* 2: the 2D read */
+    fprintf(f, "%s\n", sequence);                     /* 3: the template read */
+    for (int64_t i = 0; i < r->read_len; i++) fprintf(f, "%" PRId64 " ", r->strand_event_map[i]);
+    fputs("\n\n\n\n", f);                             /* 4 ends; 5 complement read, 6 its strand map, 7 the template 2D map: empty */
+    for (int64_t i = 0; i < 4 * r->n_events; i++) {   /* 8: the template events */
+        num[sa_format_py_repr(num, r->events4[i])] = 0;
+        fputs(num, f);
+        fputc(' ', f);
+    }
+    fputs("\n\n\n", f);                               /* 8 ends; 9 the complement 2D map, 10 its events: empty */
+    for (int64_t i = 0; i < r->n_events; i++) {       /* 11: model states */
+        fwrite(sequence + r->kmer_idx[i], 1, (size_t) k, f);
+        fputc(' ', f);
+    }
+    fputs("\n", f);
+    for (int64_t i = 0; i < r->n_events; i++) {       /* 12: their probabilities */
+        num[sa_format_py_repr(num, r->p_model_state[i])] = 0;
+        fputs(num, f);
+        fputc(' ', f);
+    }
+    fputs("\n\n\n", f);                               /* 12 ends; 13, 14: the complement's, empty */
+    const int bad = ferror(f);
+    return (fclose(f) != 0 || bad) ? SA_EIO : SA_OK;
+}
+
+/* ---- a read as raw current ---------------------------------------------------------------------- */
+void sa_rawread_free(sa_rawread_t *r) {
+    if (!r) return;
+    free(r->sequence);
+    free(r->samples);
+    free(r);
+}
+
+int sa_rawread_is(const char *path) {
+    char magic[8];
+    FILE *f = path ? fopen(path, "rb") : NULL;
+    if (!f) return 0;
+    const int yes = fread(magic, 1, 8, f) == 8 && memcmp(magic, SA_RAWREAD_MAGIC, 8) == 0;
+    fclose(f);
+    return yes;
+}
+
+int sa_rawread_load(const char *path, sa_rawread_t **out) {
+    if (!path || !out) return SA_EINVAL;
+    *out = NULL;
+    FILE *f = fopen(path, "rb");
+    if (!f) return SA_EIO;
+    unsigned char head[8 + 5 * 4 + 2 * 8];
+    sa_rawread_t *r = NULL;
+    int rc = SA_EIO;
+    const size_t got = fread(head, 1, sizeof(head), f);
+    if (got >= 8 && memcmp(head, SA_RAWREAD_MAGIC, 8) != 0) { rc = SA_EINVAL; goto done; }
+    if (got != sizeof(head)) goto done;
+    if (!(r = calloc(1, sizeof(*r)))) { rc = SA_ENOMEM; goto done; }
+    {
+        float a[5];
+        memcpy(a, head + 8, sizeof(a));   /* little-endian file, little-endian host */
+        r->digitisation = a[0]; r->offset = a[1]; r->range = a[2]; r->sample_rate = a[3]; r->start_time = a[4];
+        memcpy(&r->n_samples, head + 28, 8);
+        memcpy(&r->seq_len, head + 36, 8);
+    }
+    if (r->n_samples < 1 || r->n_samples > 0x7fffffffLL || r->seq_len < 0) { rc = SA_EINVAL; goto done; }
+    {   /* the size the header promises against the file's, before anything is allocated for it */
+        if (fseeko(f, 0, SEEK_END) != 0) goto done;
+        const off_t size = ftello(f);
+        if (size < 0 || r->seq_len > (int64_t) size || (int64_t) size != (int64_t) sizeof(head) + r->seq_len + 2 * r->n_samples) goto done;
+        if (fseeko(f, (off_t) sizeof(head), SEEK_SET) != 0) goto done;
+    }
+    r->sequence = malloc((size_t) r->seq_len + 1);
+    r->samples = malloc(sizeof(int16_t) * (size_t) r->n_samples);
+    if (!r->sequence || !r->samples) { rc = SA_ENOMEM; goto done; }
+    if (fread(r->sequence, 1, (size_t) r->seq_len, f) != (size_t) r->seq_len) goto done;
+    r->sequence[r->seq_len] = 0;
+    if (memchr(r->sequence, 0, (size_t) r->seq_len) != NULL) { rc = SA_EINVAL; goto done; }
+    if (fread(r->samples, sizeof(int16_t), (size_t) r->n_samples, f) != (size_t) r->n_samples) goto done;
+    rc = SA_OK;
+done:
+    fclose(f);
+    if (rc != SA_OK) { sa_rawread_free(r); return rc; }
+    *out = r;
+    return SA_OK;
+}
+
 /* ---- cigar -------------------------------------------------------------------------------------- */
 void sa_cigar_free(sa_cigar_t *c) {
     if (!c) return;

@@ -30,6 +30,22 @@ typedef struct sa_npread {
 int sa_npread_load(const char *path, sa_npread_t **out);
 void sa_npread_free(sa_npread_t *r);
 
+/* ---- a read as raw current (this repository reads no HDF5; signalalign_amd/rawio.py writes the file).  Little-endian:
+ * the 8 bytes "SARAW1\0\0" | five float32: digitisation, offset, range, sampling_rate, start_time | int64 n_samples |
+ * int64 seq_len | seq_len sequence bytes | n_samples int16 samples.
+ * SA_EIO: unreadable, or shorter than its header says (also: bytes left over); SA_EINVAL: another magic, n_samples outside
+ * 1 .. 2^31 - 1, seq_len < 0.  (A sequence shorter than the model's k is the caller's to refuse.) */
+#define SA_RAWREAD_MAGIC "SARAW1\0"
+typedef struct sa_rawread {
+    float digitisation, offset, range, sample_rate, start_time;
+    int64_t n_samples, seq_len;
+    char *sequence;      /* NUL-terminated */
+    int16_t *samples;
+} sa_rawread_t;
+int sa_rawread_is(const char *path);   /* 1: the file begins with the magic; 0: it does not, or cannot be read */
+int sa_rawread_load(const char *path, sa_rawread_t **out);
+void sa_rawread_free(sa_rawread_t *r);
+
 /* ---- guide alignment in exonerate cigar format (sonLib cigarRead; written by utils/bwaWrapper.py:213) ---- */
 typedef struct sa_cigar {
     char *contig1, *contig2;     /* reference name, query name                  */

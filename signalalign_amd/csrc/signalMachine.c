@@ -23,6 +23,10 @@
  * Without a window: --guide-locate instead of -p, or a manifest's cigar column of exactly @.  The -f reference is indexed once per
  * process (sa_ref_index_build_fasta), all such reads of a slice are located by one sa_guide_locate_batch call, and each gets the
  * window sa_locate_window names -- from there on it is a read with a guide window.
+ *
+ * Reads from raw current (not in the reference binary, which starts from the .npRead its Python writes): -q, or a manifest's read
+ * column, may name a raw-read file (sa_io.h; recognised by its magic).  All such reads of a slice go through one
+ * sa_npread_from_raw_batch call ahead of the guide stages (raw_stage) and come out as 1D reads; --npread-out keeps the .npRead.
  */
 #define _GNU_SOURCE
 #include <ctype.h>
@@ -94,6 +98,13 @@ static void usage(void) {
     fprintf(stderr, "--guide-locate: instead of -p or --guide-window: find the read's contig, strand and place in the whole -f reference on\n"
                     "                  the GPU, then go on as with the --guide-window that names them.  In a manifest: @ alone in the cigar\n"
                     "                  column.  Needs no -n.  Not with --rna\n");
+    fprintf(stderr, "-q <raw-read file> (also a manifest's read column): a read given as raw current and basecalled sequence (recognised by its\n"
+                    "                  magic; signalalign_amd/rawio.py writes one): events are detected, aligned to the sequence and mapped to\n"
+                    "                  its bases on the GPU, which stands in for the .npRead of a 1D read.  DNA with a Gaussian -T model: not with\n"
+                    "                  --twoD, -C, --rna or an .nhdp\n"
+                    "--npread-out <dir>: write <dir>/<label>.npRead for every raw read (usable with -q)\n"
+                    "--raw-detector <w1,w2,t1,t2,peak>: the event detector's two window lengths, two thresholds and peak height\n"
+                    "                  (default 3,6,1.4,9.0,0.2)\n");
     fprintf(stderr, "--guide-band <n>: band width of that alignment: 64, 128 (default), 192 or 256\n");
     fprintf(stderr, "--guide-cigars-out <dir>: write every computed guide alignment to <dir>/<label>.cigar (exonerate format, usable with -p)\n");
     fprintf(stderr, "--mea: also write <posteriors file>.mea, the rows of the full output on the maximum expected accuracy path\n");
@@ -433,6 +444,9 @@ typedef struct {
     int device;                   /* --device, for the stage that runs ahead of a slice's GPU stage (the guide alignment) */
     int guide_band;               /* --guide-band */
     const char *guide_cigars_out; /* --guide-cigars-out */
+    const char *npread_out;       /* --npread-out: where raw_stage writes <label>.npRead of every raw read */
+    int raw_detector_set;         /* --raw-detector */
+    sa_detector_params_t raw_detector;
     int64_t out_fmt, constraint_trim;
     int64_t snp_step;       /* --snp-step N: single-nucleotide probabilities, N substituted copies of every read's reference */
     const char *snp_dir;    /* --snp-dir: where <label>.tsv goes */
@@ -468,6 +482,7 @@ typedef struct {
     char *expect[2];      /* [strand]: where -t / -c write the strand's expectations */
     char *guide_window;   /* <contig>:<start>-<end>[:+|:-] instead of a cigar file: the guide alignment is computed (guide_stage) */
     int guide_locate;     /* neither a cigar file nor a window: locate_stage writes guide_window */
+    int raw;              /* npread_path names a raw-read file (sa_rawread_is): raw_stage fills np */
     sa_cigar_t *pA;
     sa_npread_t *np;
     char *forward_seq, *backward_seq;
@@ -796,6 +811,79 @@ static void parallel_for(int64_t n, void (*fn)(int64_t, void *), void *ctx) {
 }
 
 
+/* ---- reads given as raw current --------------------------------------------------------------------------------------------- */
+/* The reads of a slice whose -q / manifest file is a raw-read file (sa_io.h): ONE sa_npread_from_raw_batch call -- event detection,
+ * MoM scalings, event alignment and the base-to-event map on the GPU -- gives each the sa_npread_t that sa_npread_load would have
+ * read from the .npRead the reference's Python writes for a 1D read: template read, strand event map, events, the default
+ * parameters (estimate_strand replaces them).  From there on it is a read like any other.  A read the chain rejects fails as a
+ * read with an unreadable .npRead does. */
+static void raw_stage(const run_t *R, read_t *reads, int64_t n_reads) {
+    int64_t n = 0;
+    for (int64_t i = 0; i < n_reads; i++) n += reads[i].raw && !reads[i].failed;
+    if (n == 0) return;
+    const int fatal = !R->batch_mode;
+    read_t **rd = xalloc(n, sizeof(read_t *), 0);
+    sa_rawread_t **rr = xalloc(n, sizeof(sa_rawread_t *), 1);
+    sa_raw_job_t *jobs = xalloc(n, sizeof(sa_raw_job_t), 1);
+    const char **seq = xalloc(n, sizeof(char *), 0);
+    n = 0;
+    for (int64_t i = 0; i < n_reads; i++) {
+        read_t *r = &reads[i];
+        if (!r->raw || r->failed) continue;
+        sa_rawread_t *w = NULL;
+        const int rc = sa_rawread_load(r->npread_path, &w);
+        if (rc != SA_OK) { fail(r, fatal, "signalMachine: could not load the raw read %s", r->npread_path); continue; }
+        if (w->seq_len < R->sm[0].k) {
+            sa_rawread_free(w);
+            fail(r, fatal, "signalMachine: the sequence of the raw read %s is shorter than the model's k-mers", r->npread_path);
+            continue;
+        }
+        rd[n] = r;
+        rr[n] = w;
+        jobs[n] = (sa_raw_job_t) {w->samples, w->n_samples, w->digitisation, w->offset, w->range, w->sample_rate, w->start_time};
+        seq[n++] = w->sequence;
+    }
+    sa_raw_npread_t *out = xalloc(n, sizeof(sa_raw_npread_t), 1);
+    const int rc = n > 0 ? sa_npread_from_raw_batch(R->sm[0].model, jobs, seq, n, R->raw_detector_set ? &R->raw_detector : NULL, R->device, 0,
+                                                    out, NULL) : SA_OK;
+    for (int64_t q = 0; q < n; q++) {
+        read_t *r = rd[q];
+        const sa_raw_npread_t *o = &out[q];
+        if (rc != SA_OK) { fail(r, fatal, "signalMachine: the raw reads could not be turned into events: %s", sa_strerror(rc)); continue; }
+        if (o->status != 0) {
+            char what[160];
+            snprintf(what, sizeof(what), "%s (status %d)", (o->status & SA_RAW_MAP_LENGTH) ? "Read and event map lengths do not match"
+                     : (o->status & SA_RAW_NO_PEAK) ? "the event detector found no event boundary"
+                     : "its events do not align to its sequence", (int) o->status);
+            fail(r, fatal, "signalMachine: no event table for the raw read: %s", what);
+            continue;
+        }
+        if (R->npread_out) {
+            char *path = xalloc((int64_t) (strlen(R->npread_out) + strlen(r->label) + 16), 1, 0);
+            sprintf(path, "%s/%s.npRead", R->npread_out, r->label);
+            if (sa_raw_npread_write(o, seq[q], R->sm[0].model, path) != SA_OK) fprintf(stderr, "[signalMachine]WARNING: cannot write %s\n", path);
+            free(path);
+        }
+        sa_npread_t *np = xalloc(1, sizeof(sa_npread_t), 1);
+        np->template_params = np->complement_params = (sa_strand_params_t) {1, 1, 1, 1, 1, 0, 0};   /* the .npRead's 1 1 1 1 1 0 */
+        np->n_template_events = o->n_events;
+        np->template_read_length = o->read_len;
+        np->two_d_read = strdup("");
+        np->complement_read = strdup("");
+        np->template_read = strdup(seq[q]);
+        np->template_strand_event_map = xalloc(o->read_len, sizeof(int64_t), 0);
+        memcpy(np->template_strand_event_map, o->strand_event_map, sizeof(int64_t) * (size_t) o->read_len);
+        np->template_events = xalloc(4 * o->n_events, sizeof(double), 0);
+        memcpy(np->template_events, o->events4, sizeof(double) * 4 * (size_t) o->n_events);
+        r->np = np;
+        fprintf(stderr, "[signalMachine]NOTICE: %s from raw current: %" PRId64 " samples, %" PRId64 " events on %" PRId64 " bases (shift %f, scale %f)\n",
+                r->label, rr[q]->n_samples, o->n_events, o->read_len, o->mom_shift, o->mom_scale);
+    }
+    sa_raw_npread_free(out, n);
+    for (int64_t q = 0; q < n; q++) sa_rawread_free(rr[q]);
+    free(out); free(seq); free(jobs); free(rr); free(rd);
+}
+
 /* ---- guide alignment on the GPU --------------------------------------------------------------------------------------------- */
 /* <contig>:<start>-<end>[:+|:-], read from the right (a contig name may hold colons); strand: 1 '+', 0 '-', -1 not given */
 static int parse_guide_window(const char *spec, char **contig, int64_t *start, int64_t *end, int *strand) {
@@ -845,6 +933,7 @@ static void guide_prepare_one(int64_t i, void *ctx) {
     read_t *rd = it->rd;
     const int fatal = !R->batch_mode;
     int64_t w_end = 0;
+    if (rd->failed) return;   /* the raw stage gave up on it */
     int strand = -1;
     if (parse_guide_window(rd->guide_window, &it->contig, &it->w_start, &w_end, &strand) != 0) {
         fail(rd, fatal, "signalMachine: cannot read the guide window %s (want <contig>:<start>-<end>[:+|:-])", rd->guide_window);
@@ -922,7 +1011,7 @@ typedef struct {
 static void locate_load_one(int64_t i, void *ctx) {
     const locate_ctx_t *c = ctx;
     read_t *rd = c->rd[i];
-    if (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK)
+    if (rd->np == NULL && (rd->npread_path == NULL || sa_npread_load(rd->npread_path, &rd->np) != SA_OK))   /* (raw_stage fills it too) */
         fail(rd, !c->R->batch_mode, "signalMachine: could not load the nanopore read %s", rd->npread_path);
 }
 
@@ -1081,6 +1170,7 @@ static void prep_one(int64_t i, void *ctx) {
 static void *slice_prepare(void *arg) {
     slice_t *sl = arg;
     const double ts0 = now_s();
+    raw_stage(sl->R, sl->reads, sl->n_reads);
     locate_stage(sl->R, sl->reads, sl->n_reads);
     guide_stage(sl->R, sl->reads, sl->n_reads);
     parallel_for(sl->n_reads, prep_one, sl);
@@ -2656,6 +2746,8 @@ int main(int argc, char **argv) {
                                            {"guide-locate", no_argument, 0, 1053},
                                            {"guide-band", required_argument, 0, 1051},
                                            {"guide-cigars-out", required_argument, 0, 1052},
+                                           {"npread-out", required_argument, 0, 1080},
+                                           {"raw-detector", required_argument, 0, 1081},
                                            {0, 0, 0, 0}};
     for (;;) {
         int idx = 0;
@@ -2728,6 +2820,16 @@ int main(int argc, char **argv) {
             case 1051: R.guide_band = atoi(optarg); break;
             case 1053: guide_locate = 1; break;
             case 1052: R.guide_cigars_out = strdup(optarg); break;
+            case 1080: R.npread_out = strdup(optarg); break;
+            case 1081: {
+                sa_detector_params_t *d = &R.raw_detector;
+                char tail = 0;
+                if (sscanf(optarg, "%d,%d,%f,%f,%f%c", &d->window_length1, &d->window_length2, &d->threshold1, &d->threshold2, &d->peak_height,
+                           &tail) != 5 || d->window_length1 < 1 || d->window_length2 < 1)
+                    die("signalMachine: --raw-detector takes w1,w2,t1,t2,peak with window lengths >= 1, not %s", optarg);
+                R.raw_detector_set = 1;
+                break;
+            }
             case 1003: batch_reads = atoll(optarg) > 0 ? atoll(optarg) : batch_reads; break;
             case 1004:
                 if (!strcmp(optarg, "twoDist")) R.two_dist = 1;
@@ -2796,6 +2898,14 @@ int main(int argc, char **argv) {
             die("signalMachine: cannot read the guide window %s (want <contig>:<start>-<end>[:+|:-])", reads[i].guide_window);
         free(contig);
     }
+    for (int64_t i = 0; i < n_reads; i++) {   /* reads given as raw current: DNA, template strand, Gaussian event alignment */
+        reads[i].raw = reads[i].npread_path != NULL && sa_rawread_is(reads[i].npread_path);
+        if (!reads[i].raw) continue;
+        if (R.two_d || c_model != NULL) die("signalMachine: a raw read (%s) is a 1D read: not with --twoD or a complement model", reads[i].npread_path);
+        if (R.rna) die("signalMachine: a raw read (%s) cannot be combined with --rna: RNA reads need a .npRead", reads[i].npread_path);
+        if (R.hdp || t_hdp != NULL) die("signalMachine: a raw read (%s) needs a Gaussian template model for its event alignment: not with an .nhdp", reads[i].npread_path);
+    }
+    if (R.npread_out && mkdir(R.npread_out, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.npread_out);
     if (R.guide_cigars_out && mkdir(R.guide_cigars_out, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.guide_cigars_out);
     /* (the expectation pass keeps the reference-ordered kernels and the model's own noise; an HDP model has no such emission) */
     if (R.two_dist && (R.hdp || t_hdp != NULL || c_hdp != NULL || R.expect_mode || t_expect != NULL || c_expect != NULL))
