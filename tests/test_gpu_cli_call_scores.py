@@ -244,3 +244,75 @@ def test_two_d_read_both_strands(tmp_path):
     pr = subprocess.run(base + ["--site-calls-truth", truth, "-u", str(tmp_path / "x.tsv"), "--site-calls-accuracy", summ, "--mea"],
                         capture_output=True, text=True, timeout=120)
     assert pr.returncode != 0 and "--mea" in pr.stderr
+
+
+def test_refused_reads_leave_the_scores_of_the_others(oracle, tmp_path):
+    """The six reads of the batch run with two reads the planner refuses (an N in their reference window) among them: one at the
+    head of the first slice, ahead of any call, so that the slice that would make the accumulator is the one started over, and one
+    in the second slice, which is checkpointed and rolled back.  6 of 8 reads align, and every file of the good reads and of the
+    run equals the six-read run's."""
+    npread_path = os.path.join(cases.GOLDEN, "npReads", "r9p4_oneD.npRead")
+    read = oracle.parse_npread(npread_path)["template_read"]
+    L, m0, L2 = 1500, 100, 1380
+    ref_a = list(read[:L + 400])
+    for i in range(60, len(ref_a) - 60):
+        if read[i:i + 2] == "CG":
+            ref_a[i] = "X"
+    ref_a = "".join(ref_a) + "ACGTACGTAC"
+    pre, post = "GATTACA" * 9, "CCGGTTAA" * 6
+    contig = list(pre + _revcomp(read[m0:m0 + L2]) + post)
+    for p in range(len(pre) + 20, len(pre) + L2 - 20):
+        if contig[p] == "C" and contig[p + 1] == "G":
+            contig[p + 1] = "X"
+    ref_m = "".join(contig)
+    ref_n = ref_a[:700] + "N" + ref_a[701:]
+    comp = str.maketrans("ACGT", "TGCA")
+    fasta, bfasta = str(tmp_path / "three.fa"), str(tmp_path / "three_bwd.fa")
+    _write_fasta_records(fasta, [("chrA", ref_a), ("chrM", ref_m), ("chrN", ref_n)])
+    _write_fasta_records(bfasta, [("chrA", ref_a.translate(comp)), ("chrM", ref_m.translate(comp)), ("chrN", ref_n.translate(comp))])
+    amb = str(tmp_path / "ce.ambig")
+    with open(amb, "w") as f:
+        f.write("X\tCE\n")
+
+    def line(run, label, chrom, cigar_text):
+        cigar = str(tmp_path / (label + ".cigar"))
+        with open(cigar, "w") as f:
+            f.write(cigar_text)
+        return "%s\t%s\t%s\t%s\t-\t%s\n" % (label, npread_path, cigar, str(tmp_path / run / (label + ".tsv")), chrom)
+
+    def manifest(run):
+        os.mkdir(str(tmp_path / run))
+        good = [line(run, "r%d" % i, "chrA", "cigar: r%d %d %d + chrA %d %d + 1 M %d\n" % (i, s, s + L, s, s + L, L))
+                for i, s in enumerate((0, 120, 250, 330))]
+        for i, (s, n) in enumerate(((m0, L2), (m0 + 90, L2 - 200))):
+            t_hi = len(pre) + L2 - (s - m0)
+            good.append(line(run, "rm%d" % i, "chrM", "cigar: rm%d %d %d + chrM %d %d - 1 M %d\n" % (i, s, s + n, t_hi, t_hi - n, n)))
+        return good
+
+    truth, truth_reads = str(tmp_path / "positions.tsv"), str(tmp_path / "labels.tsv")
+    with open(truth, "w") as f:
+        for name, seq in (("chrA", ref_a), ("chrM", ref_m)):
+            f.writelines("%s\t%d\t%s\tC\t%s\n" % (name, pos, strand, "CE"[pos % 2]) for pos in range(len(seq)) for strand in "+-" if pos % 5)
+    open(truth_reads, "w").write("r1\tE\nrm0\tC\n")
+    base = [BIN, "-T", cases.MODEL_CPG, "-f", fasta, "-b", bfasta, "-s", "0", "-g", "100", "-a", amb, "--batch-reads", "3", "--site-calls",
+            "--site-calls-truth", truth, "--site-calls-truth-reads", truth_reads, "--site-calls-accuracy-bins", str(N_BINS)]
+
+    def run(name, lines, status, word):
+        man = str(tmp_path / (name + ".manifest"))
+        open(man, "w").writelines(lines)
+        outs = [str(tmp_path / name / f) for f in ("agg.tsv", "acc.tsv", "curves.tsv")]
+        pr = subprocess.run(base + ["--batch", man, "--site-calls-aggregate", outs[0], "--site-calls-accuracy", outs[1],
+                                    "--site-calls-accuracy-curves", outs[2]], capture_output=True, text=True, timeout=300)
+        assert pr.returncode == status, pr.stderr[-2000:]
+        assert word in pr.stderr, pr.stderr[-2000:]
+        return pr, {f: open(os.path.join(str(tmp_path / name), f), "rb").read() for f in sorted(os.listdir(str(tmp_path / name)))}
+
+    _, want = run("six", manifest("six"), 0, "6 of 6 reads aligned")
+    assert len(want) == 3 + 2 * 6 and all(want.values())
+    lines = manifest("eight")    # slices of three: [bad0, r0, r1], [r2, bad1, r3], [rm0, rm1]
+    for at, label in ((0, "bad0"), (4, "bad1")):
+        lines.insert(at, line("eight", label, "chrN", "cigar: %s %d %d + chrN %d %d + 1 M %d\n" % (label, 60, 60 + L, 60, 60 + L, L)))
+    pr, got = run("eight", lines, 1, "6 of 8 reads aligned")
+    assert "read bad0 skipped: alignment job rejected" in pr.stderr and "read bad1 skipped: alignment job rejected" in pr.stderr
+    assert sorted(got) == sorted(want)        # (no file of a refused read)
+    assert got == want
