@@ -1023,6 +1023,45 @@ int sa_kmer_table_write(const sa_kmer_table_t *t, int strand, const char *path, 
  * checkpoint: SA_ESTATE. */
 int sa_kmer_table_checkpoint(sa_kmer_table_t *t);
 int sa_kmer_table_rollback(sa_kmer_table_t *t);
+/* The table from the rows that cover labelled positions only -- trainModels.py:161-286 (generate_build_alignments_positions,
+ * build_alignments_positions, get_kmers_covering_positions, filter_top_n_kmers, write_and_generate_build_alignments_positions)
+ * without the full TSVs: a row with the TSV's reference_index ri on contig c covers the positions line (c, p, S) when
+ * p - (k - 1) <= ri <= p (k the model's k-mer length; the same window for both site strands, as the reference has it) and S is the
+ * site strand the reference pairs with the row: '+' for the t rows of a forward-mapped read and the c rows of a backward-mapped
+ * one, '-' for the other two.  A row is OFFERED when its printed posterior is >= min_prob and it covers at least one line; the
+ * offered rows go through the table's selection as every row does without positions (per strand and path k-mer, ties by run
+ * order; a row's run ordinal counts every record of the run, offered or not).  Two deliberate differences from the script: it
+ * pools t and c rows in filter_top_n_kmers, the table keeps them apart; its tie order comes from a directory listing and an
+ * unstable sort, here it is run order.
+ * Coverage counts: per distinct line (contig, position, strand) the number of offered rows that cover it over the whole run; a
+ * row within k - 1 of two lines counts once for each.  Integers, independent of arrival order.
+ * sa_kmer_table_set_positions: the lines are copied, sorted, deduplicated and kept on the table's device as packed 64-bit keys.
+ * Only on an empty table (SA_ESTATE otherwise); n == 0 keeps nothing (and then nothing is ever offered); a strand that is neither,
+ * a contig outside [0, 2^21), a position outside [0, 2^41): SA_EINVAL.  From then on sa_kmer_table_add_batch and
+ * sa_kmer_table_add_rows return SA_ESTATE (they carry no coordinates) and sa_kmer_table_add_batch_at is the way in; on a table
+ * without positions sa_kmer_table_add_batch_at returns SA_ESTATE.
+ * sa_kmer_table_add_batch_at: sa_kmer_table_add_batch with map[j] placing job j.  One kernel sets a bit per reference position of
+ * every job (one search of the keys each), the selection's passes test that bit, and one pass over the records adds the offered
+ * ones to the counts.  n_jobs that is not the batch's, a contig outside the range, an x_sign that is not +-1, a site strand that is
+ * neither, |x0| >= 2^42: SA_EINVAL, checked before anything is added.
+ * sa_kmer_table_position_counts: the distinct lines in (contig, strand, position) order and their counts, both malloc'd
+ * (sa_free); *n_out of them.  sa_kmer_table_checkpoint / _rollback cover the counts. */
+typedef struct sa_train_site {        /* one line of the positions file (its first three columns) */
+    int32_t contig, mapped_strand;    /* the ranges of sa_truth_site_t: mapped_strand 0 '+', 1 '-'; contig in [0, 2^21)            */
+    int64_t pos;                      /* in [0, 2^41)                                                                              */
+} sa_train_site_t;                    /* 16 bytes */
+typedef struct sa_train_job_map {     /* job j of a batch, for sa_kmer_table_add_batch_at */
+    int32_t contig, x_sign;           /* a record at x has the TSV's reference_index x0 + x_sign * x (x_sign +1 or -1)             */
+    int64_t x0;
+    int32_t site_strand, pad;         /* the site strand S its rows pair with, 0 '+', 1 '-'                                        */
+} sa_train_job_map_t;                 /* 24 bytes */
+int sa_kmer_table_set_positions(sa_kmer_table_t *t, const sa_train_site_t *sites, int64_t n);
+int sa_kmer_table_add_batch_at(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand,
+                               const sa_train_job_map_t *map, double *kernel_ms_out);
+int sa_kmer_table_position_counts(const sa_kmer_table_t *t, sa_train_site_t **sites_out, int64_t **counts_out, int64_t *n_out);
+/* HIP-event times of the last sa_kmer_table_add_batch_at: ms_out[0] the cover mask's kernel, ms_out[1] the counts pass (both are
+ * part of that call's kernel_ms_out) */
+int sa_kmer_table_add_at_times(const sa_kmer_table_t *t, double ms_out[2]);
 /* per k-mer (out: one entry per kmer_id) statistics over the table's rows, computed exactly on the device: mean = the double
  * nearest S / (n 1e6), sd = sqrt of the double nearest (n Q - S^2) / (n^2 1e12); median and MAD exact in half / quarter units,
  * MAD converted and divided by 0.6744897501960817 (scipy's scale='normal') */

@@ -92,6 +92,16 @@ class ScoreJobMap(C.Structure):
                 ("true_letter", C.c_int32), ("pad", C.c_int32)]
 
 
+class TrainSite(C.Structure):
+    """sa_train_site_t (include/signalalign_hip.h)"""
+    _fields_ = [("contig", C.c_int32), ("mapped_strand", C.c_int32), ("pos", C.c_int64)]
+
+
+class TrainJobMap(C.Structure):
+    """sa_train_job_map_t (include/signalalign_hip.h)"""
+    _fields_ = [("contig", C.c_int32), ("x_sign", C.c_int32), ("x0", C.c_int64), ("site_strand", C.c_int32), ("pad", C.c_int32)]
+
+
 class CallScoresCounts(C.Structure):
     """sa_call_scores_counts_t (include/signalalign_hip.h)"""
     _fields_ = [("unlabelled", C.c_int64), ("other_sites", C.c_int64)]
@@ -99,6 +109,8 @@ class CallScoresCounts(C.Structure):
 
 SORT_TILE = 4096
 TRUTH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("mapped_strand", "<i4"), ("pos", "<i8"), ("change_to", "S1"), ("pad", "S1", (7,))])
+TRAIN_SITE_DTYPE = np.dtype([("contig", "<i4"), ("mapped_strand", "<i4"), ("pos", "<i8")])
+TRAIN_JOB_MAP_DTYPE = np.dtype([("contig", "<i4"), ("x_sign", "<i4"), ("x0", "<i8"), ("site_strand", "<i4"), ("pad", "<i4")])
 CALL_SCORE_ROW_DTYPE = np.dtype([("level", "<i4"), ("group", "<i4"), ("letter", "S1"), ("pad", "S1", (7,)), ("n_pos", "<i8"), ("n_neg", "<i8"),
                                  ("auc2", "<u8"), ("auc", "<f8"), ("tp", "<i8"), ("fp", "<i8"), ("tn", "<i8"), ("fn", "<i8")])
 
@@ -262,7 +274,8 @@ EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alp
            "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
            "sa_hmm_load_into_model", "sa_model_transitions10",
            "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
-           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_kmer_table_kde", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
+           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_set_positions", "sa_kmer_table_add_batch_at",
+           "sa_kmer_table_position_counts", "sa_kmer_table_add_at_times", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_kmer_table_kde", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
            "sa_guide_align_batch", "sa_guide_release", "sa_guide_seed", "sa_guide_format_cigar",
            "sa_ref_index_build", "sa_ref_index_build_fasta", "sa_ref_index_info", "sa_ref_index_entries", "sa_ref_index_contig",
            "sa_ref_index_destroy", "sa_guide_locate_batch", "sa_locate_release", "sa_locate_window",
@@ -496,6 +509,10 @@ def lib():
     L.sa_kmer_table_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
     L.sa_kmer_table_checkpoint.argtypes = [C.c_void_p]
     L.sa_kmer_table_rollback.argtypes = [C.c_void_p]
+    L.sa_kmer_table_set_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.sa_kmer_table_add_batch_at.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int64, C.c_int, C.c_void_p, dp]
+    L.sa_kmer_table_position_counts.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), ip]
+    L.sa_kmer_table_add_at_times.argtypes = [C.c_void_p, dp]
     L.sa_kmer_table_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, dp]
     L.sa_kmer_table_mixture.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp, C.c_void_p, dp]
     L.sa_kmer_table_mixture_start.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp]
@@ -1901,6 +1918,50 @@ class KmerTable:
              "sa_kmer_table_add_batch")
         if stats is not None:
             stats["kernel_ms"] = kms.value
+
+    def set_positions(self, sites):
+        """sa_kmer_table_set_positions: from now on only rows that cover one of `sites` are offered.  sites: a TRAIN_SITE_DTYPE
+        array, or an iterable of (contig index, position, site strand 0 '+' / 1 '-')"""
+        if isinstance(sites, np.ndarray) and sites.dtype == TRAIN_SITE_DTYPE:
+            t = np.ascontiguousarray(sites)
+        else:
+            sites = list(sites)
+            t = np.zeros(len(sites), dtype=TRAIN_SITE_DTYPE)
+            for i, (contig, pos, strand) in enumerate(sites):
+                t[i]["contig"], t[i]["pos"], t[i]["mapped_strand"] = int(contig), int(pos), int(strand)
+        _chk(lib().sa_kmer_table_set_positions(self._h, t.ctypes.data if len(t) else None, len(t)), "sa_kmer_table_set_positions")
+
+    def add_batch_at(self, batch, job_map, strand=0, stats=None):
+        """sa_kmer_table_add_batch_at: add_batch on a table with positions; job_map: a TRAIN_JOB_MAP_DTYPE array, or per job a dict
+        with the fields of sa_train_job_map_t (contig, x_sign, x0, site_strand)"""
+        if isinstance(job_map, np.ndarray) and job_map.dtype == TRAIN_JOB_MAP_DTYPE:
+            m = np.ascontiguousarray(job_map)
+        else:
+            job_map = list(job_map)
+            m = np.zeros(len(job_map), dtype=TRAIN_JOB_MAP_DTYPE)
+            for i, j in enumerate(job_map):
+                for f in ("contig", "x_sign", "x0", "site_strand"):
+                    m[i][f] = int(j[f])
+        kms = C.c_double()
+        _chk(lib().sa_kmer_table_add_batch_at(self._h, batch._h, batch._arr, len(m), int(strand), m.ctypes.data if len(m) else None,
+                                              C.byref(kms)), "sa_kmer_table_add_batch_at")
+        if stats is not None:
+            parts = np.zeros(2)
+            _chk(lib().sa_kmer_table_add_at_times(self._h, _dp(parts)), "sa_kmer_table_add_at_times")
+            stats["kernel_ms"], stats["mask_ms"], stats["counts_ms"] = kms.value, float(parts[0]), float(parts[1])
+
+    def position_counts(self):
+        """sa_kmer_table_position_counts: (sites: TRAIN_SITE_DTYPE array in (contig, strand, position) order, counts: int64 array)"""
+        sp, cp = C.c_void_p(), C.c_void_p()
+        n = np.zeros(1, dtype=np.int64)
+        _chk(lib().sa_kmer_table_position_counts(self._h, C.byref(sp), C.byref(cp), _ip(n)), "sa_kmer_table_position_counts")
+        sites, counts = np.zeros(int(n[0]), dtype=TRAIN_SITE_DTYPE), np.zeros(int(n[0]), dtype=np.int64)
+        if n[0]:
+            C.memmove(sites.ctypes.data, sp, sites.nbytes)
+            C.memmove(counts.ctypes.data, cp, counts.nbytes)
+        lib().sa_free(sp)
+        lib().sa_free(cp)
+        return sites, counts
 
     def add_rows(self, kmer_ids, descaled, prob, strand=0):
         k = np.ascontiguousarray(kmer_ids, dtype=np.int32)

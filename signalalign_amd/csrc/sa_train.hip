@@ -22,6 +22,9 @@
 //   k_kt_scan                            one block of 1024 threads: exclusive scan of the kept counts into the new table's offsets
 //   k_kt_compact_rows / _rec<P8>         the rows at or above the k-mer's threshold into the k-mer's segment of the new table;
 //                                        for records the descaled mean is computed and rounded as "%f" prints it
+//   k_kt_cover / k_kt_cover_count<P8>    a table with positions (trainModels.py:161-286, the rows that cover labelled positions):
+//                                        one bit per (job, reference position) from one search of the sorted position keys, which
+//                                        the record kernels above test; and per add one pass that counts the offered rows per key
 //   k_kt_stats                           one block per k-mer: exact integer sums (S, and Q in two words), radix selection (8 bits
 //                                        per pass) of the median and of the median absolute deviation
 //   k_kt_mixture<K> / k_kt_mix_gather    one block per (k-mer, K): a K-component Gaussian mixture by EM over the k-mer's rows
@@ -91,6 +94,10 @@ struct KtState {                // per k-mer selection state
 struct KtJob {                  // per job of a batch
     long long ev_off, n_ev, x_off, n_x;
     double scale, shift, var;
+    // a table with positions (sa_kmer_table_add_batch_at): the job's words of the cover mask, its reference positions, and where
+    // they lie: reference_index = x0 + x_sign * x on `contig`, paired with site strand `site_strand`
+    long long m_off, m_nx, x0;
+    int contig, x_sign, site_strand, pad;
 };
 struct KtRecs {
     const void *recs;
@@ -100,10 +107,11 @@ struct KtRecs {
     const int *xk;              // 8-byte records: k-mer id of every reference position of every job
     const double *level;        // level mean per k-mer
     long long min_units, n_kmers;
+    const unsigned long long *mask;   // the cover mask (k_kt_cover), bit x of job j at word jobs[j].m_off; NULL: every row is offered
 };
 
 __device__ static inline bool kt_rec(const KtRecs &R, bool p8, const SaRecChunk &C, int i, int *kmer, unsigned long long *key, long long *y,
-                                     unsigned *err) {
+                                     int *xo, unsigned *err) {
     long long pe7;
     int x;
     if (p8) {
@@ -116,13 +124,20 @@ __device__ static inline bool kt_rec(const KtRecs &R, bool p8, const SaRecChunk 
         *kmer = R.xk[J.x_off + x];
     } else {
         const sa_pair16_t r = ((const sa_pair16_t *) R.recs)[C.first + i];
+        x = (int) (r.a & 0xfffffffull);
         *y = (long long) ((r.a >> 28) & 0xfffffffull);
         *kmer = (int) (unsigned) (r.b & 0xffffffffull);
         pe7 = (long long) ((r.b >> 32) & 0xffffffull);
     }
+    *xo = x;
     if (*kmer < 0 || *kmer >= R.n_kmers) { atomicOr(err, KT_ERR_BOUNDS); return false; }
     const long long u = sa_printed_units(pe7);
     if (u < R.min_units) return false;
+    if (R.mask) {   // a table with positions: only a row that covers one is offered
+        const long long m_nx = R.jobs[C.job].m_nx, m_off = R.jobs[C.job].m_off;
+        if (x >= m_nx) { atomicOr(err, KT_ERR_BOUNDS); return false; }
+        if (!((R.mask[m_off + (x >> 6)] >> (x & 63)) & 1ull)) return false;
+    }
     *key = ((unsigned long long) u << KT_RUN_BITS) | (KT_RUN_MASK - (unsigned long long) (C.local + i));
     return true;
 }
@@ -147,10 +162,10 @@ __global__ __launch_bounds__(256) void k_kt_hist_rec(KtRecs R, const KtState *__
                                                      unsigned *__restrict__ err) {
     const SaRecChunk C = R.chunks[blockIdx.x];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
-        int kmer;
+        int kmer, x;
         unsigned long long key;
         long long y;
-        if (kt_rec(R, P8, C, i, &kmer, &key, &y, err)) kt_count(st, hist, kmer, key, shift);
+        if (kt_rec(R, P8, C, i, &kmer, &key, &y, &x, err)) kt_count(st, hist, kmer, key, shift);
     }
 }
 
@@ -227,10 +242,10 @@ __global__ __launch_bounds__(256) void k_kt_tie_rec(KtRecs R, const KtState *__r
                                                     unsigned long long *__restrict__ n_tie, unsigned long long cap, unsigned *__restrict__ err) {
     const SaRecChunk C = R.chunks[blockIdx.x];
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
-        int kmer;
+        int kmer, x;
         unsigned long long key;
         long long y;
-        if (kt_rec(R, P8, C, i, &kmer, &key, &y, err)) kt_tie(st, kmer, key, tie, n_tie, cap, err);
+        if (kt_rec(R, P8, C, i, &kmer, &key, &y, &x, err)) kt_tie(st, kmer, key, tie, n_tie, cap, err);
     }
 }
 
@@ -264,13 +279,83 @@ __global__ __launch_bounds__(256) void k_kt_compact_rec(KtRecs R, const KtState 
     for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
         KtRow r;
         long long y;
-        if (!kt_rec(R, P8, C, i, &r.kmer, &r.key, &y, err)) continue;
+        int x;
+        if (!kt_rec(R, P8, C, i, &r.kmer, &r.key, &y, &x, err)) continue;
         if (r.key < st[r.kmer].thr) continue;
         if (y >= J.n_ev) { atomicOr(err, KT_ERR_BOUNDS); continue; }
         const double e = R.ev[J.ev_off + y], level = R.level[r.kmer];
         const double desc = (e + J.var * level - J.scale * level - J.shift) / J.var;   // signalMachine.c descale(); no contraction
         if (kt_desc_units(desc, &r.desc, &r.neg_zero) != SA_OK) { atomicOr(err, KT_ERR_RANGE); continue; }
         kt_put(st, off, fill, out, r, err);
+    }
+}
+
+// ---- a table with positions: the cover mask and the coverage counts ------------------------------------------------------------
+// A positions line as a key: (contig, site strand, position), so the lines a row can cover are one run of the sorted keys.
+#define KT_POS_MAX_CONTIG (1ll << 21)
+#define KT_POS_MAX_POS (1ll << 41)
+#define KT_POS_MAX_X0 (1ll << 42)
+__host__ __device__ static inline unsigned long long kt_pos_key(long long contig, int strand, long long pos) {
+    return ((unsigned long long) contig << 42) | ((unsigned long long) strand << 41) | (unsigned long long) pos;
+}
+// the first index of a[0 .. n) whose entry is >= key
+__device__ __forceinline__ long long kt_lower_bound(const unsigned long long *__restrict__ a, long long n, unsigned long long key) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// The keys a row at reference_index ri of job J covers are those in [*lo, *hi]: positions ri .. ri + k - 1 (p - (k - 1) <= ri <= p).
+// false: the window lies outside the positions a key can have.
+__device__ static inline bool kt_window(const KtJob &J, long long ri, int k, unsigned long long *lo, unsigned long long *hi) {
+    const long long a = ri < 0 ? 0 : ri, b = ri + k - 1 < KT_POS_MAX_POS ? ri + k - 1 : KT_POS_MAX_POS - 1;
+    if (b < a) return false;
+    *lo = kt_pos_key(J.contig, J.site_strand, a);
+    *hi = kt_pos_key(J.contig, J.site_strand, b);
+    return true;
+}
+
+// The cover mask: one thread per (job, x), a wave per 64-bit word (a job's bits start at a word of their own, woff[j]); one
+// lower-bound search of the sorted keys answers "is there a key of this contig and site strand in [ri, ri + k - 1]", and the
+// wave's ballot is the word.  The selection's passes (kt_rec) then test one bit per record.
+__global__ __launch_bounds__(256) void k_kt_cover(const KtJob *__restrict__ jobs, const long long *__restrict__ woff, long long n_jobs,
+                                                  long long n_words, const unsigned long long *__restrict__ keys, long long n_keys, int k,
+                                                  unsigned long long *__restrict__ mask) {
+    const long long gid = (long long) blockIdx.x * blockDim.x + threadIdx.x, w = gid >> 6;
+    if (w >= n_words) return;   // (a whole wave: the ballot below sees full waves only)
+    long long lo = 0, hi = n_jobs;   // the job whose words hold w: the last j with woff[j] <= w
+    while (hi - lo > 1) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (woff[mid] <= w) lo = mid; else hi = mid;
+    }
+    const KtJob J = jobs[lo];
+    const long long x = ((w - J.m_off) << 6) + (threadIdx.x & 63);
+    bool covered = false;
+    unsigned long long k_lo, k_hi;
+    if (x < J.m_nx && kt_window(J, J.x0 + (long long) J.x_sign * x, k, &k_lo, &k_hi)) {
+        const long long at = kt_lower_bound(keys, n_keys, k_lo);
+        covered = at < n_keys && keys[at] <= k_hi;
+    }
+    const unsigned long long word = __ballot(covered);
+    if ((threadIdx.x & 63) == 0) mask[w] = word;
+}
+
+// The coverage counts, once per add: an offered record (kt_rec: posterior and mask bit) walks the at most k keys of its window
+// and adds one to each, a 64-bit integer atomic per key straight into HBM (no LDS stage: DESIGN.md, "Training from labelled positions").
+template <bool P8>
+__global__ __launch_bounds__(256) void k_kt_cover_count(KtRecs R, const unsigned long long *__restrict__ keys, long long n_keys, int k,
+                                                        unsigned long long *__restrict__ cnt, unsigned *__restrict__ err) {
+    const SaRecChunk C = R.chunks[blockIdx.x];
+    const KtJob J = R.jobs[C.job];
+    for (int i = threadIdx.x; i < C.n; i += blockDim.x) {
+        int kmer, x;
+        unsigned long long key, k_lo, k_hi;
+        long long y;
+        if (!kt_rec(R, P8, C, i, &kmer, &key, &y, &x, err)) continue;
+        if (!kt_window(J, J.x0 + (long long) J.x_sign * x, k, &k_lo, &k_hi)) continue;
+        for (long long at = kt_lower_bound(keys, n_keys, k_lo); at < n_keys && keys[at] <= k_hi; at++) atomicAdd(&cnt[at], 1ull);
     }
 }
 
@@ -377,6 +462,12 @@ struct sa_kmer_table {
     unsigned long long ck_run = 0;
     KtSide ck_side[2];
     bool ck_taken[2] = {false, false};
+    // sa_kmer_table_set_positions: the distinct lines as sorted keys (kt_pos_key), and per key the offered rows that cover it:
+    // d_pcnt holds n_pkey live counts and then n_pkey more, their values at the checkpoint
+    bool has_pos = false;
+    std::vector<unsigned long long> h_pkey;
+    unsigned long long *d_pkey = nullptr, *d_pcnt = nullptr;
+    double at_ms[2] = {0.0, 0.0};     // the last add's cover mask and counts pass
     std::mutex mu;
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
@@ -426,6 +517,8 @@ extern "C" void sa_kmer_table_destroy(sa_kmer_table_t *t) {
         }
     }
     g_sa_pool.put(SaPool::DEVICE, t->d_level);
+    g_sa_pool.put(SaPool::DEVICE, t->d_pkey);
+    g_sa_pool.put(SaPool::DEVICE, t->d_pcnt);
     if (t->e0) (void) hipEventDestroy(t->e0);
     if (t->e1) (void) hipEventDestroy(t->e1);
     delete t;
@@ -569,6 +662,9 @@ extern "C" int sa_kmer_table_checkpoint(sa_kmer_table_t *t) {
             t->ck_side[s] = KtSide();
             t->ck_taken[s] = false;
         }
+    if (!t->h_pkey.empty() &&
+        hipMemcpy(t->d_pcnt + t->h_pkey.size(), t->d_pcnt, 8 * t->h_pkey.size(), hipMemcpyDeviceToDevice) != hipSuccess)
+        return SA_ENODEVICE;
     t->ck = true;
     t->ck_run = t->run_next;
     return SA_OK;
@@ -588,6 +684,9 @@ extern "C" int sa_kmer_table_rollback(sa_kmer_table_t *t) {
             t->ck_taken[s] = false;
         }
     t->run_next = t->ck_run;
+    if (!t->h_pkey.empty() &&
+        hipMemcpy(t->d_pcnt, t->d_pcnt + t->h_pkey.size(), 8 * t->h_pkey.size(), hipMemcpyDeviceToDevice) != hipSuccess)
+        return SA_ENODEVICE;
     return SA_OK;
 }
 
@@ -607,10 +706,12 @@ static int kt_kmer_ids(const sa_kmer_table *t, const char *ref, long long n_x, i
     return SA_OK;
 }
 
-extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand,
-                                       double *kernel_ms_out) {
-    if (!t || !b || (n_jobs > 0 && !jobs) || n_jobs < 0 || (strand != 0 && strand != 1)) return SA_EINVAL;
+// sa_kmer_table_add_batch (map NULL) and sa_kmer_table_add_batch_at (map[j] places job j on a table with positions)
+static int kt_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand, const sa_train_job_map_t *map,
+                        bool at, double *kernel_ms_out) {
+    if (!t || !b || (n_jobs > 0 && !jobs) || n_jobs < 0 || (strand != 0 && strand != 1) || (at && n_jobs > 0 && !map)) return SA_EINVAL;
     std::lock_guard<std::mutex> g(t->mu);
+    if (at != t->has_pos) return SA_ESTATE;   // (rows without coordinates on a table with positions, or the reverse)
     SaBatchView V;
     int rc = sa_batch_view(b, &V);
     if (V.batch_flags & SA_FLAG_VC_ROWS) return SA_EINVAL;   // (it dropped rows; refused before the batch's state is looked at)
@@ -624,32 +725,49 @@ extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const 
     long long n_total = 0;
     for (size_t j = 0; j < nj; j++) n_total += count[j];
     if (t->run_next + (unsigned long long) n_total > KT_RUN_MASK) return SA_EUNSUPPORTED;
-    // per job: events (dense means) and, for 8-byte records, the k-mer id of every reference position
+    // per job: events (dense means), for 8-byte records the k-mer id of every reference position, and with positions the job's
+    // words of the cover mask
     std::vector<KtJob> kj(nj);
-    long long n_ev = 0, n_x = 0;
+    std::vector<long long> woff(nj + 1, 0);
+    long long n_ev = 0, n_x = 0, n_words = 0;
     for (size_t j = 0; j < nj; j++) {
         const sa_job_t &J = jobs[j];
         if (J.n_events < 0 || (J.n_events > 0 && (!J.events || J.event_stride < 1)) || !(J.var != 0)) return SA_EINVAL;
         kj[j].ev_off = n_ev; kj[j].n_ev = J.n_events;
         kj[j].scale = J.scale; kj[j].shift = J.shift; kj[j].var = J.var;
         n_ev += J.n_events;
-        const long long lx = p8 ? std::max<long long>(0, J.ref_len - t->k + 1) : 0;
+        const long long positions = std::max<long long>(0, J.ref_len - t->k + 1), lx = p8 ? positions : 0;
         if (p8 && lx > 0 && !J.ref) return SA_EINVAL;
         kj[j].x_off = n_x; kj[j].n_x = lx;
         n_x += lx;
+        kj[j].m_off = n_words; kj[j].m_nx = 0; kj[j].x0 = 0;
+        kj[j].contig = 0; kj[j].x_sign = 1; kj[j].site_strand = 0; kj[j].pad = 0;
+        if (at) {
+            const sa_train_job_map_t &m = map[j];
+            if (m.contig < 0 || m.contig >= KT_POS_MAX_CONTIG || (m.x_sign != 1 && m.x_sign != -1) ||
+                (m.site_strand != 0 && m.site_strand != 1) || m.x0 <= -KT_POS_MAX_X0 || m.x0 >= KT_POS_MAX_X0)
+                return SA_EINVAL;
+            kj[j].m_nx = positions; kj[j].x0 = m.x0;
+            kj[j].contig = m.contig; kj[j].x_sign = m.x_sign; kj[j].site_strand = m.site_strand;
+            n_words += (positions + 63) / 64;
+        }
+        woff[j + 1] = n_words;
     }
     const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, (long long) t->run_next);   // (run ordinals)
     const long long nc = (long long) chunks.size();
-    // one pinned staging block and one device block: [jobs | chunks | events | k-mer ids]
+    // one pinned staging block and one device block: [jobs | chunks | events | k-mer ids | mask word offsets]; the device block
+    // has the cover mask behind that
     SaLayout L;
     const size_t o_jobs = L.add(sizeof(KtJob) * nj), o_ch = L.add(sizeof(SaRecChunk) * (size_t) nc), o_ev = L.add(8 * (size_t) n_ev),
-                 o_xk = L.add(4 * (size_t) n_x + 4), bytes = L.end;
+                 o_xk = L.add(4 * (size_t) n_x + 4), o_woff = L.add(8 * (nj + 1)), bytes = L.end, o_mask = L.add(8 * (size_t) n_words + 8),
+                 o_cerr = L.add(8), d_bytes = L.end;
     char *h = nullptr, *d = nullptr;
     if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
     if (g_sa_pool.get(SaPool::PINNED, (void **) &h, bytes, t->device) != hipSuccess) return SA_ENOMEM;
     {
         memcpy(h + o_jobs, kj.data(), sizeof(KtJob) * nj);
         if (nc) memcpy(h + o_ch, chunks.data(), sizeof(SaRecChunk) * (size_t) nc);
+        memcpy(h + o_woff, woff.data(), 8 * (nj + 1));
         double *ev = (double *) (h + o_ev);
         int *xk = (int *) (h + o_xk);
         std::vector<int> bad(nj, SA_OK);
@@ -661,7 +779,7 @@ extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const 
         });
         for (size_t j = 0; j < nj; j++)
             if (bad[j] != SA_OK) { rc = bad[j]; goto done; }
-        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, bytes, t->device));
+        SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d, d_bytes, t->device));
         SA_HIP_GOTO_DONE(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
         KtRecs R;
         R.recs = V.recs;
@@ -672,8 +790,43 @@ extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const 
         R.level = t->d_level;
         R.min_units = t->min_units;
         R.n_kmers = t->n_kmers;
-        rc = kt_merge(t, strand, &R, p8, nc, nullptr, 0, kernel_ms_out);
-        if (rc == SA_OK) t->run_next += (unsigned long long) n_total;
+        R.mask = nullptr;
+        const long long n_keys = (long long) t->h_pkey.size();
+        double merge_ms = 0.0;
+        float seg = 0;
+        if (at) {   // the cover mask, once for the three passes of the selection and the counts pass
+            R.mask = (const unsigned long long *) (d + o_mask);
+            t->at_ms[0] = t->at_ms[1] = 0.0;
+            if (n_words) {
+                SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
+                hipLaunchKernelGGL(k_kt_cover, dim3((unsigned) ((n_words * 64 + 255) / 256)), dim3(256), 0, 0, R.jobs,
+                                   (const long long *) (d + o_woff), (long long) nj, n_words, t->d_pkey, n_keys, t->k,
+                                   (unsigned long long *) (d + o_mask));
+                SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
+                SA_HIP_GOTO_DONE(hipGetLastError());
+                SA_HIP_GOTO_DONE(hipEventSynchronize(t->e1));
+                SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, t->e0, t->e1));
+                t->at_ms[0] = seg;
+            }
+        }
+        rc = kt_merge(t, strand, &R, p8, nc, nullptr, 0, &merge_ms);
+        if (rc != SA_OK) goto done;
+        t->run_next += (unsigned long long) n_total;
+        if (at && nc && n_keys) {   // the coverage counts of the offered records
+            unsigned h_err = 0;
+            unsigned *cerr = (unsigned *) (d + o_cerr);
+            SA_HIP_GOTO_DONE(hipMemsetAsync(cerr, 0, 8, 0));
+            SA_HIP_GOTO_DONE(hipEventRecord(t->e0, 0));
+            if (p8) hipLaunchKernelGGL(k_kt_cover_count<true>, dim3((unsigned) nc), dim3(256), 0, 0, R, t->d_pkey, n_keys, t->k, t->d_pcnt, cerr);
+            else hipLaunchKernelGGL(k_kt_cover_count<false>, dim3((unsigned) nc), dim3(256), 0, 0, R, t->d_pkey, n_keys, t->k, t->d_pcnt, cerr);
+            SA_HIP_GOTO_DONE(hipEventRecord(t->e1, 0));
+            SA_HIP_GOTO_DONE(hipGetLastError());
+            SA_HIP_GOTO_DONE(hipMemcpy(&h_err, cerr, 4, hipMemcpyDeviceToHost));
+            SA_HIP_GOTO_DONE(hipEventElapsedTime(&seg, t->e0, t->e1));
+            t->at_ms[1] = seg;
+            if (h_err) { rc = SA_EINVAL; goto done; }   // (cannot happen: the selection read the same records)
+        }
+        if (kernel_ms_out) *kernel_ms_out = merge_ms + (at ? t->at_ms[0] + t->at_ms[1] : 0.0);
     }
 done:
     g_sa_pool.put(SaPool::DEVICE, d);
@@ -681,10 +834,90 @@ done:
     return rc;
 }
 
+extern "C" int sa_kmer_table_add_batch(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand,
+                                       double *kernel_ms_out) {
+    return kt_add_batch(t, b, jobs, n_jobs, strand, nullptr, false, kernel_ms_out);
+}
+
+extern "C" int sa_kmer_table_add_batch_at(sa_kmer_table_t *t, sa_batch_t *b, const sa_job_t *jobs, int64_t n_jobs, int strand,
+                                          const sa_train_job_map_t *map, double *kernel_ms_out) {
+    return kt_add_batch(t, b, jobs, n_jobs, strand, map, true, kernel_ms_out);
+}
+
+extern "C" int sa_kmer_table_set_positions(sa_kmer_table_t *t, const sa_train_site_t *sites, int64_t n) {
+    if (!t || n < 0 || (n > 0 && !sites)) return SA_EINVAL;
+    std::vector<unsigned long long> keys((size_t) n);
+    for (int64_t i = 0; i < n; i++) {
+        const sa_train_site_t &s = sites[i];
+        if (s.contig < 0 || s.contig >= KT_POS_MAX_CONTIG || s.pos < 0 || s.pos >= KT_POS_MAX_POS || (s.mapped_strand != 0 && s.mapped_strand != 1))
+            return SA_EINVAL;
+        keys[(size_t) i] = kt_pos_key(s.contig, s.mapped_strand, s.pos);
+    }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->run_next != 0 || t->side[0].n_rows != 0 || t->side[1].n_rows != 0) return SA_ESTATE;
+    int rc = SA_OK;
+    unsigned long long *d_key = nullptr, *d_cnt = nullptr;
+    const size_t nk = keys.size();
+    if (hipSetDevice(t->device) != hipSuccess) return SA_ENODEVICE;
+    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d_key, 8 * (nk ? nk : 1), t->device));
+    SA_HIP_GOTO_DONE(g_sa_pool.get(SaPool::DEVICE, (void **) &d_cnt, 16 * (nk ? nk : 1), t->device));
+    if (nk) SA_HIP_GOTO_DONE(hipMemcpy(d_key, keys.data(), 8 * nk, hipMemcpyHostToDevice));
+    SA_HIP_GOTO_DONE(hipMemset(d_cnt, 0, 16 * (nk ? nk : 1)));   // (an empty table's counts, live and at a checkpoint)
+    g_sa_pool.put(SaPool::DEVICE, t->d_pkey);
+    g_sa_pool.put(SaPool::DEVICE, t->d_pcnt);
+    t->d_pkey = d_key;
+    t->d_pcnt = d_cnt;
+    d_key = d_cnt = nullptr;
+    t->h_pkey.swap(keys);
+    t->has_pos = true;
+done:
+    g_sa_pool.put(SaPool::DEVICE, d_key);
+    g_sa_pool.put(SaPool::DEVICE, d_cnt);
+    return rc;
+}
+
+extern "C" int sa_kmer_table_position_counts(const sa_kmer_table_t *t, sa_train_site_t **sites_out, int64_t **counts_out, int64_t *n_out) {
+    if (!t || !sites_out || !counts_out || !n_out) return SA_EINVAL;
+    *sites_out = nullptr;
+    *counts_out = nullptr;
+    *n_out = 0;
+    std::lock_guard<std::mutex> g(const_cast<sa_kmer_table *>(t)->mu);
+    if (!t->has_pos) return SA_ESTATE;
+    const size_t nk = t->h_pkey.size();
+    sa_train_site_t *s = (sa_train_site_t *) calloc(nk ? nk : 1, sizeof(sa_train_site_t));
+    int64_t *c = (int64_t *) calloc(nk ? nk : 1, sizeof(int64_t));
+    if (!s || !c) { free(s); free(c); return SA_ENOMEM; }
+    if (nk && (hipSetDevice(t->device) != hipSuccess || hipMemcpy(c, t->d_pcnt, 8 * nk, hipMemcpyDeviceToHost) != hipSuccess)) {
+        free(s); free(c);
+        return SA_ENODEVICE;
+    }
+    for (size_t i = 0; i < nk; i++) {
+        const unsigned long long key = t->h_pkey[i];
+        s[i].contig = (int32_t) (key >> 42);
+        s[i].mapped_strand = (int32_t) ((key >> 41) & 1ull);
+        s[i].pos = (int64_t) (key & ((1ull << 41) - 1ull));
+    }
+    *sites_out = s;
+    *counts_out = c;
+    *n_out = (int64_t) nk;
+    return SA_OK;
+}
+
+extern "C" int sa_kmer_table_add_at_times(const sa_kmer_table_t *t, double ms_out[2]) {
+    if (!t || !ms_out) return SA_EINVAL;
+    std::lock_guard<std::mutex> g(const_cast<sa_kmer_table *>(t)->mu);
+    ms_out[0] = t->at_ms[0];
+    ms_out[1] = t->at_ms[1];
+    return SA_OK;
+}
+
 extern "C" int sa_kmer_table_add_rows(sa_kmer_table_t *t, int strand, const int32_t *kmer_ids, const double *descaled, const double *prob,
                                       int64_t n) {
     if (!t || n < 0 || (n > 0 && (!kmer_ids || !descaled || !prob)) || (strand != 0 && strand != 1)) return SA_EINVAL;
     std::lock_guard<std::mutex> g(t->mu);
+    if (t->has_pos) return SA_ESTATE;   // (rows without coordinates)
     if (t->run_next + (unsigned long long) n > KT_RUN_MASK) return SA_EUNSUPPORTED;
     std::vector<KtRow> rows;
     rows.reserve((size_t) n);

@@ -155,7 +155,7 @@ static void usage(void) {
                     "--train-template-model <file> / --train-complement-model <file>: write the -T / -C model with its Gaussian event\n"
                     "                  means and SDs retrained on that table (trainModels.py train_normal_emmissions)\n"
                     "--train-min-prob <p> (0.8), --train-max-assignments <n> (10), --train-weight <w> (100), --train-min-sd <s> (0),\n"
-                    "--train-median, --train-mod-only, --train-kmers <file> (one k-mer per line: only those are trained)\n"
+                    "--train-median, --train-mod-only, --train-kmers <file> (one k-mer per line: only those are trained), --train-positions <positions.tsv> (only rows whose k-mer covers a labelled position; not with --rna), --train-positions-coverage <file> (offered rows per position)\n"
                     "                  with any --train-* output, a manifest's posteriors file may be '-' as well\n"
                     "--train-mixture-motifs <canonical:modified,...> (e.g. CCAGG:CEAGG,CCTGG:CETGG) with --train-mixture-template-model\n"
                     "                  <file> / --train-mixture-complement-model <file> / --train-mixture-distances <file>: every\n"
@@ -270,6 +270,7 @@ typedef struct {
     double acc_threshold;
     /* --train-*: the top-N assignments of the whole run in k-mer tables on the GPU (one per strand), written at the end */
     char *train_assign, *train_model[2], *train_kmers;
+    char *train_pos, *train_pos_cov;   /* --train-positions: only the rows that cover a line of the positions file; --train-positions-coverage */
     int want_train;         /* any of --train-assignments / --train-template-model / --train-complement-model / --train-mixture-* */
     double train_min_prob, train_weight, train_min_sd;
     int64_t train_n;
@@ -477,6 +478,7 @@ static void parse_options(run_t *R, int argc, char **argv) {
         {"train-max-assignments", Y, 0, 1014}, {"train-weight", Y, 0, 1015}, {"train-min-sd", Y, 0, 1016}, {"train-median", N, 0, 1017},
         {"train-mod-only", N, 0, 1018}, {"train-kmers", Y, 0, 1019}, {"train-mixture-motifs", Y, 0, 1040}, {"train-mixture-template-model", Y, 0, 1041},
         {"train-mixture-complement-model", Y, 0, 1042}, {"train-mixture-distances", Y, 0, 1043},
+        {"train-positions", Y, 0, 1044}, {"train-positions-coverage", Y, 0, 1045},
         {"snp-step", Y, 0, 1020}, {"snp-dir", Y, 0, 1021}, {"snp-marginals", Y, 0, 1022}, {"snp-proposals", Y, 0, 1023}, {"snp-sites", Y, 0, 1024},
         {"snp-reference-out", Y, 0, 1025}, {"position-profile", Y, 0, 1026},
         {"guide-deviation", Y, 0, 1060}, {"guide-deviation-threshold", Y, 0, 1061}, {"guide-deviation-events", Y, 0, 1062},
@@ -489,7 +491,7 @@ static void parse_options(run_t *R, int argc, char **argv) {
         {'b', &R->bwd_ref}, {'n', &one->seq_name}, {'i', &one->post_path2}, {1000, &R->manifest}, {1006, &R->agg_path}, {1070, &R->acc_path},
         {1071, &R->acc_curves_path}, {1074, &R->acc_truth_path}, {1075, &R->acc_reads_path}, {1010, &R->train_assign}, {1011, &R->train_model[0]},
         {1012, &R->train_model[1]}, {1019, &R->train_kmers}, {1040, &R->mix_motifs}, {1041, &R->mix_model[0]}, {1042, &R->mix_model[1]},
-        {1043, &R->mix_dist}, {1021, &R->snp_dir}, {1022, &R->snp_marg}, {1023, &R->snp_prop}, {1024, &R->snp_sites_path}, {1025, &R->snp_ref_out},
+        {1043, &R->mix_dist}, {1044, &R->train_pos}, {1045, &R->train_pos_cov}, {1021, &R->snp_dir}, {1022, &R->snp_marg}, {1023, &R->snp_prop}, {1024, &R->snp_sites_path}, {1025, &R->snp_ref_out},
         {1026, &R->prof_path}, {1060, &R->dev_path}, {1062, &R->dev_events_path}, {1050, &one->guide_window}, {1052, &R->guide_cigars_out},
         {1080, &R->npread_out}};
     const struct { int key; int *flag; } flags[] = {{'e', &R->two_d}, {'r', &R->rna}, {'d', &R->hdp}, {1002, &R->mea}, {1005, &R->site_calls},
@@ -644,6 +646,9 @@ static void check_modes(const run_t *R, const read_t *reads, int64_t n_reads) {
         {R->want_train && (expect || R->mea), 0, "signalMachine: --train-* needs the alignment mode without --mea%s", ""},
         {R->want_train && (R->train_model[1] || R->mix_model[1]) && !R->two_d, 0, "signalMachine: --train-complement-model needs a 2-D run%s", ""},
         {R->want_train && (R->train_n < 1 || !(R->train_min_prob >= 0 && R->train_min_prob <= 1)), 0, "signalMachine: bad --train-max-assignments / --train-min-prob%s", ""},
+        {R->train_pos && !R->want_train, U, "signalMachine: --train-positions needs a --train-* output%s", ""},
+        {R->train_pos_cov && !R->train_pos, U, "signalMachine: --train-positions-coverage needs --train-positions <file>%s", ""},
+        {R->train_pos && R->rna, U, "signalMachine: --train-positions does not take --rna runs%s", ""},
         {!R->acc_path && (R->acc_curves_path || R->acc_truth_path || R->acc_reads_path || R->acc_opts), U,
          "signalMachine: --site-calls-truth* and --site-calls-accuracy-* need --site-calls-accuracy <file>%s", ""},
         {R->acc_path && !R->acc_truth_path && !R->acc_reads_path, U, "signalMachine: --site-calls-accuracy needs --site-calls-truth <file> or --site-calls-truth-reads <file>%s", ""},

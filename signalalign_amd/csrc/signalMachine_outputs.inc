@@ -387,7 +387,64 @@ static void acc_finish(output_t *o) {
 typedef struct {
     output_t o;
     sa_kmer_table_t *tab[2];
+    /* --train-positions: the lines of the positions file; a contig's index is its place in `contigs`, the file's names first */
+    sa_train_site_t *pos;
+    int64_t n_pos;
+    char **contigs;
+    int n_contigs;
 } train_t;
+static int train_contig(train_t *tr, const char *name) {
+    int ci = 0;
+    while (ci < tr->n_contigs && strcmp(tr->contigs[ci], name) != 0) ci++;
+    if (ci == tr->n_contigs) {
+        tr->contigs = realloc(tr->contigs, sizeof(char *) * (size_t) (tr->n_contigs + 1));
+        tr->contigs[tr->n_contigs++] = strdup(name);
+    }
+    return ci;
+}
+/* --train-positions: the file is read before the run starts, so that a bad line stops it (its first three columns take part) */
+static void train_open(output_t *o) {
+    train_t *tr = (train_t *) o;
+    const run_t *R = o->R;
+    if (!R->train_pos) return;
+    char line[4096], a[1024], st[64];
+    FILE *fh = fopen(R->train_pos, "r");
+    if (!fh) die("signalMachine: --train-positions: cannot read %s", R->train_pos);
+    int64_t cap = 0, pos = 0;
+    while (fgets(line, sizeof line, fh)) {
+        if (line[0] == '\n' || line[0] == '#') continue;
+        if (sscanf(line, "%1023s %" SCNd64 " %63s", a, &pos, st) != 3 || (strcmp(st, "+") && strcmp(st, "-")) || pos < 0)
+            die("signalMachine: --train-positions: not 'contig position +|- ...': %s", line);
+        if (tr->n_pos == cap) tr->pos = realloc(tr->pos, sizeof(sa_train_site_t) * (size_t) (cap = cap ? 2 * cap : 1024));
+        tr->pos[tr->n_pos++] = (sa_train_site_t) {train_contig(tr, a), st[0] == '-', pos};
+    }
+    fclose(fh);
+}
+/* strand s's table, made when it is first needed; with --train-positions it takes only the rows that cover a line */
+static int train_table(train_t *tr, int s) {
+    const run_t *R = tr->o.R;
+    if (tr->tab[s]) return SA_OK;
+    int rc = sa_kmer_table_create(&tr->tab[s], R->sm[s].model, R->train_n, R->train_min_prob, R->device);
+    if (rc == SA_OK && R->train_pos) rc = sa_kmer_table_set_positions(tr->tab[s], tr->pos, tr->n_pos);
+    return rc;
+}
+/* --train-positions-coverage: per distinct line the offered rows of both strands' tables that cover it; contigs in the order the
+ * positions file first names them, '+' before '-', then by position (the tables' own order of keys) */
+static void write_train_coverage(const train_t *tr) {
+    const run_t *R = tr->o.R;
+    FILE *f = fopen(R->train_pos_cov, "w");
+    if (!f) die("signalMachine: cannot write %s", R->train_pos_cov);
+    sa_train_site_t *site[2] = {NULL, NULL};
+    int64_t *cnt[2] = {NULL, NULL}, n[2] = {0, 0};
+    for (int s = 0; s < n_strands(R); s++)
+        if (sa_kmer_table_position_counts(tr->tab[s], &site[s], &cnt[s], &n[s]) != SA_OK || n[s] != n[0])
+            die("signalMachine: --train-positions-coverage: no counts%s", "");
+    for (int64_t i = 0; i < n[0]; i++)
+        fprintf(f, "%s\t%" PRId64 "\t%c\t%" PRId64 "\n", tr->contigs[site[0][i].contig], site[0][i].pos, site[0][i].mapped_strand ? '-' : '+',
+                cnt[0][i] + (n_strands(R) > 1 ? cnt[1][i] : 0));
+    if (fclose(f) != 0) die("signalMachine: cannot write %s", R->train_pos_cov);
+    for (int s = 0; s < 2; s++) { sa_free(site[s]); sa_free(cnt[s]); }
+}
 
 /* --train-mixture-motifs: the (canonical, modified) k-mer ids of every motif pair of the list, for the model of strand s:
  * get_motif_kmer_pairs with the reference's flanks (A, T, G, C), the pairs of all motifs as one sorted set (mixture_model.py
@@ -538,8 +595,8 @@ static void train_finish(output_t *o) {
     train_t *tr = (train_t *) o;
     const run_t *R = o->R;
     for (int s = 0; s < n_strands(R); s++)   /* (a run without a read that aligned: empty tables) */
-        if (!tr->tab[s] && sa_kmer_table_create(&tr->tab[s], R->sm[s].model, R->train_n, R->train_min_prob, R->device) != SA_OK)
-            die("signalMachine: --train-*: no k-mer table%s", "");
+        if (train_table(tr, s) != SA_OK) die("signalMachine: --train-*: no k-mer table%s", "");
+    if (R->train_pos_cov) write_train_coverage(tr);
     if (R->train_assign) {   /* the template table's 't' rows, then the complement table's 'c' rows */
         for (int s = 0; s < n_strands(R); s++)
             if (sa_kmer_table_write(tr->tab[s], s, R->train_assign, s > 0) != SA_OK) die("signalMachine: cannot write %s", R->train_assign);
@@ -580,7 +637,7 @@ static int train_checkpoint(output_t *o) {
     train_t *tr = (train_t *) o;
     const run_t *R = o->R;
     for (int s = 0; s < n_strands(R); s++) {
-        int rc = tr->tab[s] ? SA_OK : sa_kmer_table_create(&tr->tab[s], R->sm[s].model, R->train_n, R->train_min_prob, R->device);
+        int rc = train_table(tr, s);
         if (rc == SA_OK) rc = sa_kmer_table_checkpoint(tr->tab[s]);
         if (rc != SA_OK) die_opt(o->opt, sa_strerror(rc));
     }
@@ -592,7 +649,24 @@ static int train_rollback(output_t *o) {
     return rc;
 }
 static int train_add_batch(output_t *o, slice_t *sl, int s, sa_batch_t *b) {   /* (a batch that ran: nothing a retry without some reads would change) */
-    const int rc = sa_kmer_table_add_batch(((train_t *) o)->tab[s], b, sl->jobs[s], sl->n_ok, s, NULL);
+    train_t *tr = (train_t *) o;
+    const run_t *R = o->R;
+    int rc;
+    if (R->train_pos) {   /* where each read's rows lie: write_full's reference_index (adjust_ref) as x0 + x_sign * x */
+        sa_train_job_map_t *map = xalloc(sl->n_ok, sizeof(*map), 1);
+        for (int64_t j = 0; j < sl->n_ok; j++) {
+            const read_t *rd = &sl->reads[sl->who[j]];
+            const int along = (s == 0 && rd->forward) || (s == 1 && !rd->forward);
+            map[j].contig = train_contig(tr, rd->pA->contig1);
+            map[j].x_sign = along ? 1 : -1;
+            map[j].x0 = along ? rd->st[s].r_shift : rd->st[s].r_shift - R->sm[s].k;   /* len_kmers - (x + (len - off)), len_kmers = len - k */
+            map[j].site_strand = along ? 0 : 1;   /* strand_pairs: forward t '+', c '-'; backward t '-', c '+' */
+        }
+        rc = sa_kmer_table_add_batch_at(tr->tab[s], b, sl->jobs[s], sl->n_ok, s, map, NULL);
+        free(map);
+    } else {
+        rc = sa_kmer_table_add_batch(tr->tab[s], b, sl->jobs[s], sl->n_ok, s, NULL);
+    }
     if (rc != SA_OK) die_opt(o->opt, sa_strerror(rc));
     return SA_OK;
 }
@@ -880,7 +954,7 @@ static void outputs_open(run_t *R) {
     output_t *agg = output_new(R, R->want_agg, sizeof(agg_t), (output_t) {.opt = "--site-calls-aggregate", .add_read = agg_add_read, .finish = agg_finish});
     output_t *acc = output_new(R, R->acc_path != NULL, sizeof(acc_t), (output_t) {.opt = "--site-calls-accuracy", .open = acc_open, .checkpoint = acc_checkpoint, .rollback = acc_rollback, .add_batch = acc_add_batch, .rendered = acc_rendered, .finish = acc_finish});
     if (acc) ((acc_t *) acc)->agg = (agg_t *) agg;
-    output_new(R, R->want_train, sizeof(train_t), (output_t) {.opt = "--train-*", .checkpoint = train_checkpoint, .rollback = train_rollback, .add_batch = train_add_batch, .finish = train_finish});
+    output_new(R, R->want_train, sizeof(train_t), (output_t) {.opt = "--train-*", .open = train_open, .checkpoint = train_checkpoint, .rollback = train_rollback, .add_batch = train_add_batch, .finish = train_finish});
     output_new(R, R->dev_path != NULL, sizeof(deviation_t), (output_t) {.opt = "--guide-deviation", .open = dev_open, .add_batch = dev_add_batch, .add_read = dev_add_read, .finish = dev_finish});
     for (int i = 0; i < R->n_out; i++)
         if (R->out[i]->open) R->out[i]->open(R->out[i]);
