@@ -28,18 +28,39 @@ class SaError(RuntimeError):
         super().__init__("%s: %s (%d)" % (what, msg, code))
 
 
-class Params(C.Structure):
+ABI = {}    # C type name -> its one mirror here: a _Struct class, or the np.dtype of a struct that is only read as numpy records
+
+
+class _Struct(C.Structure):
+    """A C.Structure that mirrors the C type _c_name_ of the header _c_header_; stating the name registers it in ABI."""
+    _c_header_ = "include/signalalign_hip.h"
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        ABI[cls._c_name_] = cls
+
+
+def _record_dtype(c_name, fields):
+    """the np.dtype that mirrors the C struct c_name, registered in ABI"""
+    ABI[c_name] = np.dtype(fields)
+    return ABI[c_name]
+
+
+class Params(_Struct):
+    _c_name_ = "sa_params_t"
     _fields_ = [("threshold", C.c_double), ("diagonal_expansion", C.c_int64), ("trace_back_diagonals", C.c_int64),
                 ("min_diags_between_trace_back", C.c_int64), ("split_matrix_bigger_than_this", C.c_int64)]
 
 
-class HdpDesc(C.Structure):
+class HdpDesc(_Struct):
+    _c_name_ = "sa_hdp_desc_t"
     _fields_ = [("num_dps", C.c_int64), ("grid_length", C.c_int64), ("grid_start", C.c_double),
                 ("grid_stop", C.c_double), ("parent", C.POINTER(C.c_int64)), ("observed", C.POINTER(C.c_uint8)),
                 ("post_pred", C.POINTER(C.POINTER(C.c_double))), ("slopes", C.POINTER(C.POINTER(C.c_double)))]
 
 
-class Job(C.Structure):
+class Job(_Struct):
+    _c_name_ = "sa_job_t"
     _fields_ = [("ref", C.c_char_p), ("ref_len", C.c_int64), ("events", C.POINTER(C.c_double)),
                 ("event_stride", C.c_int64), ("n_events", C.c_int64), ("anchor_x", C.POINTER(C.c_int64)),
                 ("anchor_y", C.POINTER(C.c_int64)), ("n_anchors", C.c_int64), ("scale", C.c_double),
@@ -49,105 +70,107 @@ class Job(C.Structure):
 JOB_LEFT_END_NOT_RAGGED, JOB_RIGHT_END_NOT_RAGGED = 1, 2   # sa_job_t.ends (alignmentHasRaggedLeftEnd / RightEnd, inverted)
 
 
-class SiteCall(C.Structure):
-    """sa_site_call_t (include/signalalign_hip.h)"""
+class SiteCall(_Struct):
+    _c_name_ = "sa_site_call_t"
     _fields_ = [("x", C.c_int32), ("n_letters", C.c_int32), ("letters", C.c_char * SITE_MAX_LETTERS),
                 ("units", C.c_int64 * SITE_MAX_LETTERS), ("prob", C.c_double * SITE_MAX_LETTERS)]
 
 
-class PositionCall(C.Structure):
-    """sa_position_call_t (include/signalalign_hip.h)"""
+class PositionCall(_Struct):
+    _c_name_ = "sa_position_call_t"
     _fields_ = [("p", C.c_int32), ("n_rows", C.c_int32), ("n_letters", C.c_int32), ("pad", C.c_int32),
                 ("letters", C.c_char * SITE_MAX_LETTERS), ("sum", C.c_double * SITE_MAX_LETTERS),
                 ("prob", C.c_double * SITE_MAX_LETTERS)]
 
 
-class SnpSite(C.Structure):
-    """sa_snp_site_t (include/signalalign_hip.h)"""
+class SnpSite(_Struct):
+    _c_name_ = "sa_snp_site_t"
     _fields_ = [("pos", C.c_int64), ("strand", C.c_int32), ("pad", C.c_int32), ("p", C.c_double * 4)]
 
 
-class SnpJobMap(C.Structure):
-    """sa_snp_job_map_t (include/signalalign_hip.h)"""
+class SnpJobMap(_Struct):
+    _c_name_ = "sa_snp_job_map_t"
     _fields_ = [("contig", C.c_int32), ("pos_sign", C.c_int32), ("pos0", C.c_int64), ("x0", C.c_int64), ("x_sign", C.c_int32),
                 ("strand", C.c_int32), ("direction", C.c_int32), ("pad", C.c_int32), ("run", C.c_int64), ("group", C.c_int64)]
 
 
-class ProfileJobMap(C.Structure):
-    """sa_profile_job_map_t (include/signalalign_hip.h)"""
+class ProfileJobMap(_Struct):
+    _c_name_ = "sa_profile_job_map_t"
     _fields_ = [("contig", C.c_int32), ("pos_sign", C.c_int32), ("pos0", C.c_int64)]
 
 
 PROFILE_DIRECT = 1
 
 
-class TruthSite(C.Structure):
-    """sa_truth_site_t (include/signalalign_hip.h)"""
+class TruthSite(_Struct):
+    _c_name_ = "sa_truth_site_t"
     _fields_ = [("contig", C.c_int32), ("mapped_strand", C.c_int32), ("pos", C.c_int64), ("change_to", C.c_char), ("pad", C.c_char * 7)]
 
 
-class ScoreJobMap(C.Structure):
-    """sa_score_job_map_t (include/signalalign_hip.h)"""
+class ScoreJobMap(_Struct):
+    _c_name_ = "sa_score_job_map_t"
     _fields_ = [("contig", C.c_int32), ("x_sign", C.c_int32), ("x0", C.c_int64), ("strand", C.c_int32), ("mapped_strand", C.c_int32),
                 ("true_letter", C.c_int32), ("pad", C.c_int32)]
 
 
-class TrainSite(C.Structure):
-    """sa_train_site_t (include/signalalign_hip.h)"""
+class TrainSite(_Struct):
+    _c_name_ = "sa_train_site_t"
     _fields_ = [("contig", C.c_int32), ("mapped_strand", C.c_int32), ("pos", C.c_int64)]
 
 
-class TrainJobMap(C.Structure):
-    """sa_train_job_map_t (include/signalalign_hip.h)"""
+class TrainJobMap(_Struct):
+    _c_name_ = "sa_train_job_map_t"
     _fields_ = [("contig", C.c_int32), ("x_sign", C.c_int32), ("x0", C.c_int64), ("site_strand", C.c_int32), ("pad", C.c_int32)]
 
 
-class CallScoresCounts(C.Structure):
-    """sa_call_scores_counts_t (include/signalalign_hip.h)"""
+class CallScoresCounts(_Struct):
+    _c_name_ = "sa_call_scores_counts_t"
     _fields_ = [("unlabelled", C.c_int64), ("other_sites", C.c_int64)]
 
 
 SORT_TILE = 4096
-TRUTH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("mapped_strand", "<i4"), ("pos", "<i8"), ("change_to", "S1"), ("pad", "S1", (7,))])
-TRAIN_SITE_DTYPE = np.dtype([("contig", "<i4"), ("mapped_strand", "<i4"), ("pos", "<i8")])
-TRAIN_JOB_MAP_DTYPE = np.dtype([("contig", "<i4"), ("x_sign", "<i4"), ("x0", "<i8"), ("site_strand", "<i4"), ("pad", "<i4")])
-CALL_SCORE_ROW_DTYPE = np.dtype([("level", "<i4"), ("group", "<i4"), ("letter", "S1"), ("pad", "S1", (7,)), ("n_pos", "<i8"), ("n_neg", "<i8"),
-                                 ("auc2", "<u8"), ("auc", "<f8"), ("tp", "<i8"), ("fp", "<i8"), ("tn", "<i8"), ("fn", "<i8")])
+TRUTH_SITE_DTYPE, TRAIN_SITE_DTYPE, TRAIN_JOB_MAP_DTYPE = np.dtype(TruthSite), np.dtype(TrainSite), np.dtype(TrainJobMap)
+CALL_SCORE_ROW_DTYPE = _record_dtype("sa_call_score_row_t", [
+    ("level", "<i4"), ("group", "<i4"), ("letter", "S1"), ("pad", "S1", (7,)), ("n_pos", "<i8"), ("n_neg", "<i8"), ("auc2", "<u8"),
+    ("auc", "<f8"), ("tp", "<i8"), ("fp", "<i8"), ("tn", "<i8"), ("fn", "<i8")])
 
 
-class DeviationParams(C.Structure):
-    """sa_deviation_params_t (include/signalalign_hip.h)"""
+class DeviationParams(_Struct):
+    _c_name_ = "sa_deviation_params_t"
     _fields_ = [("threshold", C.c_int32), ("bucket_size", C.c_int32), ("n_buckets", C.c_int32)]
 
 
-class DeviationJob(C.Structure):
-    """sa_deviation_job_t (include/signalalign_hip.h)"""
+class DeviationJob(_Struct):
+    _c_name_ = "sa_deviation_job_t"
     _fields_ = [("anchor_x", C.POINTER(C.c_int64)), ("anchor_y", C.POINTER(C.c_int64)), ("n_anchors", C.c_int64), ("n_events", C.c_int64)]
 
 
 DEV_NO_GUIDE, DEV_NO_RECORDS = 1, 2
 DEV_DIRECT, DEV_EVENTS, DEV_WINDOW = 1, 2, 4
-DEVIATION_READ_DTYPE = np.dtype([("status", "<i4"), ("n_sets", "<i4"), ("set_first", "<i8"), ("n_aligned", "<i8"), ("n_flagged", "<i8"),
-                                 ("n_on_mea", "<i8"), ("sum_abs", "<i8"), ("max_abs", "<i4"), ("max_abs_mea", "<i4"), ("max_event", "<i4"),
-                                 ("pad", "<i4")])
-DEVIATION_SET_DTYPE = np.dtype([("first_event", "<i4"), ("last_event", "<i4"), ("count", "<i4"), ("peak", "<i4"), ("mea_peak", "<i4"),
-                                ("center_event", "<i4"), ("open_end", "<i4"), ("pad", "<i4")])
-DEVIATION_EVENT_DTYPE = np.dtype([("best_x", "<i4"), ("guide", "<i4"), ("diff", "<i4"), ("flags", "<u4")])
-PROFILE_SITE_DTYPE = np.dtype([("pos", "<i8"), ("contig", "<i4"), ("read_count", "<i4"), ("kmer_count", "<i8"), ("entropy_units", "<i8"),
-                               ("units", "<i8", (SITE_MAX_LETTERS,)), ("entropy", "<f8"), ("prob", "<f8", (SITE_MAX_LETTERS,)),
-                               ("ref", "S1"), ("pad", "S1", (7,))])
-SNP_SITE_DTYPE = np.dtype([("pos", "<i8"), ("strand", "<i4"), ("pad", "<i4"), ("p", "<f8", (4,))])
-SNP_MARGINAL_DTYPE = np.dtype([("pos", "<i8"), ("contig", "<i4"), ("depth", "<i4"), ("fwd", "<f8", (4,)), ("bwd", "<f8", (4,)),
-                               ("prob", "<f8", (4,)), ("delta", "<f8"), ("called", "S1"), ("ref", "S1"), ("is_proposal", "i1"),
-                               ("pad", "S1", (5,))])
+DEVIATION_READ_DTYPE = _record_dtype("sa_deviation_read_t", [
+    ("status", "<i4"), ("n_sets", "<i4"), ("set_first", "<i8"), ("n_aligned", "<i8"), ("n_flagged", "<i8"), ("n_on_mea", "<i8"),
+    ("sum_abs", "<i8"), ("max_abs", "<i4"), ("max_abs_mea", "<i4"), ("max_event", "<i4"), ("pad", "<i4")])
+DEVIATION_SET_DTYPE = _record_dtype("sa_deviation_set_t", [
+    ("first_event", "<i4"), ("last_event", "<i4"), ("count", "<i4"), ("peak", "<i4"), ("mea_peak", "<i4"), ("center_event", "<i4"),
+    ("open_end", "<i4"), ("pad", "<i4")])
+DEVIATION_EVENT_DTYPE = _record_dtype("sa_deviation_event_t", [("best_x", "<i4"), ("guide", "<i4"), ("diff", "<i4"), ("flags", "<u4")])
+PROFILE_SITE_DTYPE = _record_dtype("sa_profile_site_t", [
+    ("pos", "<i8"), ("contig", "<i4"), ("read_count", "<i4"), ("kmer_count", "<i8"), ("entropy_units", "<i8"),
+    ("units", "<i8", (SITE_MAX_LETTERS,)), ("entropy", "<f8"), ("prob", "<f8", (SITE_MAX_LETTERS,)), ("ref", "S1"), ("pad", "S1", (7,))])
+SNP_SITE_DTYPE = np.dtype(SnpSite)
+SNP_MARGINAL_DTYPE = _record_dtype("sa_snp_marginal_t", [
+    ("pos", "<i8"), ("contig", "<i4"), ("depth", "<i4"), ("fwd", "<f8", (4,)), ("bwd", "<f8", (4,)), ("prob", "<f8", (4,)),
+    ("delta", "<f8"), ("called", "S1"), ("ref", "S1"), ("is_proposal", "i1"), ("pad", "S1", (5,))])
 
 
-class Pair(C.Structure):
+class Pair(_Struct):
+    _c_name_ = "sa_pair_t"
     _fields_ = [("prob_e7", C.c_int64), ("x", C.c_int32), ("y", C.c_int32), ("path", C.c_int32),
                 ("kmer_id", C.c_int32)]
 
 
-class BatchStats(C.Structure):
+class BatchStats(_Struct):
+    _c_name_ = "sa_batch_stats_t"
     _fields_ = [("cells_forward", C.c_double), ("cells_backward", C.c_double), ("ms_forward", C.c_double),
                 ("ms_backward", C.c_double), ("ms_fold", C.c_double), ("ms_total_device", C.c_double),
                 ("f_bytes", C.c_double), ("n_regions", C.c_int64), ("n_segments", C.c_int64),
@@ -156,54 +179,63 @@ class BatchStats(C.Structure):
                 ("device_bytes", C.c_double)]
 
 
-class EaJob(C.Structure):
+class EaJob(_Struct):
+    _c_name_ = "sa_ea_job_t"
     _fields_ = [("sequence", C.c_char_p), ("seq_len", C.c_int64), ("event_mean", C.POINTER(C.c_double)),
                 ("n_events", C.c_int64), ("scale", C.c_double), ("shift", C.c_double), ("var", C.c_double)]
 
 
-class GuideJob(C.Structure):
+class GuideJob(_Struct):
+    _c_name_ = "sa_guide_job_t"
     _fields_ = [("read", C.c_char_p), ("read_len", C.c_int64), ("ref", C.c_char_p), ("ref_len", C.c_int64), ("diag", C.c_int64)]
 
 
-class GuideParams(C.Structure):
+class GuideParams(_Struct):
+    _c_name_ = "sa_guide_params_t"
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32),
                 ("ambiguous", C.c_int32), ("band", C.c_int32), ("min_read_fraction", C.c_double)]
 
 
-class GuideResult(C.Structure):
+class GuideResult(_Struct):
+    _c_name_ = "sa_guide_result_t"
     _fields_ = [("status", C.c_int32), ("score", C.c_int64), ("read_start", C.c_int64), ("read_end", C.c_int64),
                 ("ref_start", C.c_int64), ("ref_end", C.c_int64), ("op_first", C.c_int64), ("n_ops", C.c_int64)]
 
 
-class RefIndexInfo(C.Structure):
-    """sa_ref_index_info_t (include/signalalign_hip.h)"""
+class RefIndexInfo(_Struct):
+    _c_name_ = "sa_ref_index_info_t"
     _fields_ = [("n_contigs", C.c_int64), ("total_bases", C.c_int64), ("n_entries", C.c_int64), ("q", C.c_int32), ("device", C.c_int32),
                 ("host_bytes", C.c_int64), ("device_bytes", C.c_int64), ("build_seconds", C.c_double)]
 
 
-class LocateParams(C.Structure):
+class LocateParams(_Struct):
+    _c_name_ = "sa_locate_params_t"
     _fields_ = [("read_bases", C.c_int32), ("max_occ", C.c_int32), ("span", C.c_int32), ("min_votes", C.c_int32), ("max_hits", C.c_int32)]
 
 
-class LocateResult(C.Structure):
+class LocateResult(_Struct):
+    _c_name_ = "sa_locate_result_t"
     _fields_ = [("status", C.c_int32), ("contig", C.c_int32), ("reverse", C.c_int32), ("pos", C.c_int64), ("key", C.c_int64),
                 ("votes", C.c_int64), ("second_votes", C.c_int64), ("hits", C.c_int64), ("seeds", C.c_int64), ("repetitive", C.c_int64)]
 
 
-class Cigar(C.Structure):
-    """sa_cigar_t (csrc/sa_io.h)"""
+class Cigar(_Struct):
+    _c_name_ = "sa_cigar_t"
+    _c_header_ = "signalalign_amd/csrc/sa_io.h"
     _fields_ = [("contig1", C.c_char_p), ("contig2", C.c_char_p), ("start1", C.c_int64), ("end1", C.c_int64),
                 ("start2", C.c_int64), ("end2", C.c_int64), ("strand1", C.c_int), ("strand2", C.c_int),
                 ("score", C.c_double), ("n_ops", C.c_int64), ("op_type", C.POINTER(C.c_int32)),
                 ("op_len", C.POINTER(C.c_int64))]
 
 
-class RawJob(C.Structure):
+class RawJob(_Struct):
+    _c_name_ = "sa_raw_job_t"
     _fields_ = [("raw", C.POINTER(C.c_int16)), ("n_samples", C.c_int64), ("digitisation", C.c_float), ("offset", C.c_float),
                 ("range", C.c_float), ("sample_rate", C.c_float), ("start_time", C.c_float)]
 
 
-class DetectorParams(C.Structure):
+class DetectorParams(_Struct):
+    _c_name_ = "sa_detector_params_t"
     _fields_ = [("window_length1", C.c_int32), ("window_length2", C.c_int32), ("threshold1", C.c_float),
                 ("threshold2", C.c_float), ("peak_height", C.c_float)]
 
@@ -216,22 +248,29 @@ RAW_NO_PEAK = 16
 RAW_MAP_LENGTH = 32
 
 
-class RawNpRead(C.Structure):
+class RawNpRead(_Struct):
+    _c_name_ = "sa_raw_npread_t"
     _fields_ = [("status", C.c_int32), ("n_events", C.c_int64), ("events4", C.POINTER(C.c_double)),
                 ("kmer_idx", C.POINTER(C.c_int32)), ("move", C.POINTER(C.c_int32)), ("p_model_state", C.POINTER(C.c_double)),
                 ("raw_start", C.POINTER(C.c_int64)), ("raw_length", C.POINTER(C.c_int64)), ("read_len", C.c_int64),
                 ("strand_event_map", C.POINTER(C.c_int64)), ("mom_shift", C.c_double), ("mom_scale", C.c_double)]
 
 
-class RawRead(C.Structure):
+class RawRead(_Struct):
+    _c_name_ = "sa_rawread_t"
+    _c_header_ = "signalalign_amd/csrc/sa_io.h"
     _fields_ = [("digitisation", C.c_float), ("offset", C.c_float), ("range", C.c_float), ("sample_rate", C.c_float),
                 ("start_time", C.c_float), ("n_samples", C.c_int64), ("seq_len", C.c_int64), ("sequence", C.c_void_p),
                 ("samples", C.POINTER(C.c_int16))]
-RAW_EVENT_DTYPE = np.dtype([("raw_start", "<i8"), ("raw_length", "<i8"), ("mean", "<f8"), ("stdv", "<f8"), ("start", "<f8"),
-                            ("length", "<f8"), ("kmer_idx", "<i4"), ("move", "<i4"), ("p_model_state", "<f8")])
 
 
-class MeaJob(C.Structure):
+RAW_EVENT_DTYPE = _record_dtype("sa_raw_event_t", [
+    ("raw_start", "<i8"), ("raw_length", "<i8"), ("mean", "<f8"), ("stdv", "<f8"), ("start", "<f8"), ("length", "<f8"),
+    ("kmer_idx", "<i4"), ("move", "<i4"), ("p_model_state", "<f8")])
+
+
+class MeaJob(_Struct):
+    _c_name_ = "sa_mea_job_t"
     _fields_ = [("event_idx", C.POINTER(C.c_int32)), ("ref_idx", C.POINTER(C.c_int32)), ("posterior", C.POINTER(C.c_double)),
                 ("n", C.c_int64), ("shortest_ref_per_event", C.POINTER(C.c_int32)), ("n_events", C.c_int64)]
 
@@ -240,55 +279,23 @@ MEA_INF = 2 ** 31 - 1
 MEA_STATUS = {0: "ok", 1: "empty", 2: "single event", 3: "no forward edge", 4: "no path", 5: "bad event index"}
 
 
-class PlanInfo(C.Structure):
+class PlanInfo(_Struct):
+    _c_name_ = "sa_plan_info_t"
     _fields_ = [("n_regions", C.c_int64), ("n_segments", C.c_int64), ("n_checkpoints", C.c_int64),
                 ("cells_forward", C.c_double), ("cells_backward", C.c_double), ("f_cellpaths", C.c_int64),
                 ("max_span", C.c_int64), ("n_fast_regions", C.c_int64), ("n_ring_regions", C.c_int64)]
 
 
-PAIR_DTYPE = np.dtype([("prob_e7", "<i8"), ("x", "<i4"), ("y", "<i4"), ("path", "<i4"), ("kmer_id", "<i4")])
-POSITION_CALL_DTYPE = np.dtype([("p", "<i4"), ("n_rows", "<i4"), ("n_letters", "<i4"), ("pad", "<i4"),
-                                ("letters", "S1", (SITE_MAX_LETTERS,)), ("sum", "<f8", (SITE_MAX_LETTERS,)),
-                                ("prob", "<f8", (SITE_MAX_LETTERS,))])
-SITE_CALL_DTYPE = np.dtype([("x", "<i4"), ("n_letters", "<i4"), ("letters", "S1", (SITE_MAX_LETTERS,)),
-                            ("units", "<i8", (SITE_MAX_LETTERS,)), ("prob", "<f8", (SITE_MAX_LETTERS,))])
-
-EXPORTS = ["sa_model_create", "sa_model_load", "sa_model_destroy", "sa_model_alphabet", "sa_model_table5",
-           "sa_model_set_to_hdp_expected_values", "sa_model_set_emission", "sa_model_clone_with_table", "sa_kmer_id", "sa_default_ambig", "sa_load_ambig",
-           "sa_batch_create", "sa_batch_create_noise_scaled", "sa_batch_create_deferred", "sa_batch_prepare", "sa_batch_run", "sa_batch_n_pairs", "sa_batch_all_pairs_summary", "sa_batch_pairs", "sa_batch_pairs16", "sa_batch_pairs16_all", "sa_batch_pairs8", "sa_batch_pairs8_all", "sa_batch_pairs_all", "sa_batch_stats",
-           "sa_batch_job_cells", "sa_batch_release_device", "sa_batch_destroy", "sa_align_batch", "sa_expect_batch", "sa_expect_last_stats", "sa_plan_describe", "sa_plan_digest",
-           "sa_plan_check_path_records", "sa_dplan_compare",
-           "sa_guide_to_anchors", "sa_remap_anchors", "sa_estimate_params", "sa_scalings_mom", "sa_event_align_batch", "sa_event_align_release", "sa_detect_events_batch", "sa_raw_event_align_batch", "sa_detect_release", "sa_npread_from_raw_batch", "sa_raw_npread_free", "sa_raw_npread_write", "sa_npread_last_finish_ms", "sa_pool_release", "sa_pool_release_device", "sa_pool_configure", "sa_host_alloc", "sa_host_free", "sa_pair_roundtrip", "sa_fasta_subsequence", "sa_format_f6", "sa_batch_start", "sa_batch_wait", "sa_mea_batch", "sa_mea_release", "sa_mea_params", "sa_batch_mea", "sa_batch_site_calls", "sa_batch_position_calls", "sa_snp_substitute", "sa_snp_site_window", "sa_snp_write_read",
-           "sa_snp_marginals_create", "sa_snp_marginals_destroy", "sa_snp_marginals_add_sites", "sa_snp_marginals_add_batch",
-           "sa_snp_marginals_checkpoint", "sa_snp_marginals_rollback", "sa_snp_marginals_finish", "sa_snp_group_sites",
-           "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals",
-           "sa_position_profile_create", "sa_position_profile_destroy", "sa_position_profile_add_batch", "sa_position_profile_add_records",
-           "sa_position_profile_checkpoint", "sa_position_profile_rollback", "sa_position_profile_finish", "sa_position_profile_write",
-           "sa_profile_entropy_term", "sa_sort_u64", "sa_call_scores_create", "sa_call_scores_destroy", "sa_call_scores_add_batch",
-           "sa_call_scores_add_records", "sa_call_scores_checkpoint", "sa_call_scores_rollback", "sa_call_scores_finish",
-           "sa_call_scores_write", "sa_batch_guide_deviation", "sa_guide_deviation_records", "sa_guide_deviation_release",
-           "sa_format_py_round6", "sa_mea_printed_posterior", "sa_mea_printed_posterior_device", "sa_device_count", "sa_device_memory", "sa_strerror", "sa_hdp_state_load", "sa_hdp_state_write", "sa_hdp_state_info", "sa_hdp_state_free", "sa_hdp_state_distr_sample", "sa_hdp_state_sample_weights", "sa_hdp_finalize_distributions",
-           "sa_hdp_state_new", "sa_hdp_state_new_tree", "sa_hdp_nig_params_from_table", "sa_hdp_state_pass_data", "sa_hdp_state_pass_assignments", "sa_hdp_state_pass_assignment_file", "sa_hdp_state_kmer_dp", "sa_hdp_state_gibbs", "sa_hdp_state_finalize", "sa_hdp_state_samples_taken", "sa_hdp_digamma", "sa_hdp_trigamma",
-           "sa_hdp_distances", "sa_hdp_distances_release", "sa_hdp_distances_paired", "sa_hdp_state_densities", "sa_hdp_state_distances", "sa_hdp_state_distance_pairs", "sa_hdp_state_compare", "sa_hdp_state_alphabet", "sa_hdp_state_vs_gaussian",
-           "sa_hmm_create", "sa_hmm_destroy", "sa_hmm_view", "sa_hmm_set_event_model", "sa_hmm_add_expectations",
-           "sa_hmm_add_emission_expectation", "sa_hmm_add_assignment", "sa_hmm_add_expectations_file", "sa_hmm_write", "sa_hmm_load", "sa_hmm_normalize",
-           "sa_hmm_load_into_model", "sa_model_transitions10",
-           "sa_kmer_table_create", "sa_kmer_table_destroy", "sa_kmer_table_add_batch", "sa_kmer_table_add_rows", "sa_kmer_table_rows",
-           "sa_kmer_table_write", "sa_kmer_table_checkpoint", "sa_kmer_table_rollback", "sa_kmer_table_set_positions", "sa_kmer_table_add_batch_at",
-           "sa_kmer_table_position_counts", "sa_kmer_table_add_at_times", "sa_kmer_table_stats", "sa_kmer_table_mixture", "sa_kmer_table_mixture_start", "sa_kmer_table_kde", "sa_mixture_assign", "sa_motif_kmer_pairs", "sa_model_write_trained", "sa_format_py_repr", "sa_f6_units_device", "sa_f6_units",
-           "sa_guide_align_batch", "sa_guide_release", "sa_guide_seed", "sa_guide_format_cigar",
-           "sa_ref_index_build", "sa_ref_index_build_fasta", "sa_ref_index_info", "sa_ref_index_entries", "sa_ref_index_contig",
-           "sa_ref_index_destroy", "sa_guide_locate_batch", "sa_locate_release", "sa_locate_window",
-           "sa_version", "sa_free"]
+PAIR_DTYPE, POSITION_CALL_DTYPE, SITE_CALL_DTYPE = np.dtype(Pair), np.dtype(PositionCall), np.dtype(SiteCall)
 
 
-class MixtureParams(C.Structure):
-    """sa_mixture_params_t (include/signalalign_hip.h)"""
+class MixtureParams(_Struct):
+    _c_name_ = "sa_mixture_params_t"
     _fields_ = [("n_components", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("reg_covar", C.c_double)]
 
 
-class HmmView(C.Structure):
-    """sa_hmm_view_t (include/signalalign_hip.h)"""
+class HmmView(_Struct):
+    _c_name_ = "sa_hmm_view_t"
     _fields_ = [("type", C.c_int), ("n_states", C.c_int), ("n_alpha", C.c_int), ("k", C.c_int), ("alphabet", C.c_char * 64),
                 ("n_kmers", C.c_int64), ("transitions", C.POINTER(C.c_double)), ("likelihood", C.POINTER(C.c_double)),
                 ("event_model", C.POINTER(C.c_double)), ("event_expectations", C.POINTER(C.c_double)),
@@ -297,8 +304,8 @@ class HmmView(C.Structure):
                 ("assignment_kmers", C.POINTER(C.c_char)), ("has_model", C.c_int)]
 
 
-class HdpStateInfo(C.Structure):
-    """sa_hdp_state_info_t (include/signalalign_hip.h)"""
+class HdpStateInfo(_Struct):
+    _c_name_ = "sa_hdp_state_info_t"
     _fields_ = ([(n, C.c_int64) for n in ("num_dps", "depth", "grid_length", "n_data", "n_factors", "n_base_factors", "n_observed",
                                           "base_dp", "alphabet_size", "kmer_length")] +
                 [(n, C.c_double) for n in ("mu", "nu", "alpha", "beta", "grid_start", "grid_stop")] +
@@ -309,6 +316,215 @@ class HdpStateInfo(C.Structure):
                  ("observed", C.POINTER(C.c_uint8)), ("row_of_dp", C.POINTER(C.c_int64)), ("post", C.POINTER(C.c_double)),
                  ("slope", C.POINTER(C.c_double)), ("f_type", C.POINTER(C.c_int64)), ("f_parent", C.POINTER(C.c_int64)),
                  ("f_ref", C.POINTER(C.c_int64)), ("f_params", C.POINTER(C.c_double)), ("f_n_children", C.POINTER(C.c_int64))])
+
+
+# Every function bound from the library: name -> (restype, argtypes), in the order of include/signalalign_hip.h.  lib() applies
+# it; nothing is called through ctypes' guessed widths.  Opaque handles and caller-typed buffers are void pointers.
+_P, _vp, _str = C.POINTER, C.c_void_p, C.c_char_p
+_pf64, _pi64, _pi32, _pvp, _pstr = _P(C.c_double), _P(C.c_int64), _P(C.c_int32), _P(C.c_void_p), _P(C.c_char_p)
+SIGNATURES = {
+    "sa_pair_roundtrip": (C.c_int, [_vp, _vp, C.c_int64]),
+    "sa_model_create": (C.c_int, [_pvp, C.c_int, _str, C.c_int, _pf64, _pf64, _P(HdpDesc)]),
+    "sa_model_load": (C.c_int, [_pvp, _str, _str]),
+    "sa_model_destroy": (None, [_vp]),
+    "sa_model_alphabet": (C.c_int, [_vp, _str, _pi32, _pi32]),
+    "sa_model_table5": (_pf64, [_vp]),
+    "sa_model_set_to_hdp_expected_values": (C.c_int, [_vp]),
+    "sa_kmer_id": (C.c_int64, [_vp, _str]),
+    "sa_model_set_emission": (C.c_int, [_vp, C.c_int]),
+    "sa_model_clone_with_table": (C.c_int, [_pvp, _vp, _pf64]),
+    "sa_default_ambig": (None, [_pstr]),
+    "sa_load_ambig": (C.c_int, [_str, _pstr]),
+    "sa_batch_create": (C.c_int, [_pvp, _vp, _P(Params), _P(Job), C.c_int64, _pstr, C.c_int, C.c_uint]),
+    "sa_batch_create_noise_scaled": (C.c_int, [_pvp, _vp, _P(Params), _P(Job), _pf64, C.c_int64, _pstr, C.c_int, C.c_uint]),
+    "sa_batch_run": (C.c_int, [_vp]),
+    "sa_batch_create_deferred": (C.c_int, [_pvp, _vp, _P(Params), _P(Job), C.c_int64, _pstr, C.c_int, C.c_uint]),
+    "sa_batch_prepare": (C.c_int, [_vp]),
+    "sa_batch_start": (C.c_int, [_vp]),
+    "sa_batch_wait": (C.c_int, [_vp]),
+    "sa_batch_n_pairs": (C.c_int, [_vp, C.c_int64, _pi64]),
+    "sa_batch_pairs": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64]),
+    "sa_batch_all_pairs_summary": (C.c_int, [_vp, C.c_int64, _pi64, _pi64]),
+    "sa_batch_pairs16": (C.c_int, [_vp, C.c_int64, _pvp, _pi64]),
+    "sa_batch_pairs16_all": (C.c_int, [_vp, _pvp, _pi64]),
+    "sa_batch_pairs8": (C.c_int, [_vp, C.c_int64, _pvp, _pi64]),
+    "sa_batch_pairs8_all": (C.c_int, [_vp, _pvp, _pi64]),
+    "sa_batch_pairs_all": (C.c_int, [_vp, _vp, C.c_int64, _pi64]),
+    "sa_batch_release_device": (C.c_int, [_vp]),
+    "sa_batch_stats": (C.c_int, [_vp, _P(BatchStats)]),
+    "sa_batch_job_cells": (C.c_int, [_vp, C.c_int64, _pf64, _pf64]),
+    "sa_batch_destroy": (None, [_vp]),
+    "sa_align_batch": (C.c_int, [_vp, _P(Params), _P(Job), C.c_int64, _pstr, C.c_int, C.c_uint, _P(_P(Pair)), _pi64]),
+    "sa_expect_batch": (C.c_int, [_vp, _P(Params), _P(Job), C.c_int64, _pstr, C.c_int, C.c_uint, _pf64, _pf64, _pvp, _pi64]),
+    "sa_expect_last_stats": (C.c_int, [_P(BatchStats)]),
+    "sa_plan_describe": (C.c_int, [_vp, _P(Params), _P(Job), _pstr, C.c_uint, _P(PlanInfo), _pi64, C.c_int64, _pi64, C.c_int64,
+                                   _pi64, C.c_int64]),
+    "sa_plan_check_path_records": (C.c_int64, [_vp, _P(Params), _P(Job), _pstr, _pi64]),
+    "sa_dplan_compare": (C.c_int, [_vp, _P(Params), _P(Job), C.c_int64, _pstr, C.c_int, C.c_uint]),
+    "sa_scalings_mom": (C.c_int, [_vp, _str, C.c_int64, _pf64, C.c_int64, C.c_uint, _pf64, _pf64]),
+    "sa_event_align_batch": (C.c_int, [_vp, _P(EaJob), C.c_int64, C.c_int, C.c_uint, _pvp, _pi64, _pi32, _pf64, _pf64]),
+    "sa_event_align_release": (None, []),
+    "sa_detect_events_batch": (C.c_int, [_P(RawJob), C.c_int64, _P(DetectorParams), C.c_int, C.c_uint, _pvp, _pi64, _pi32, _pf64]),
+    "sa_raw_event_align_batch": (C.c_int, [_vp, _P(RawJob), _pstr, C.c_int64, _P(DetectorParams), C.c_int, C.c_uint, _pvp, _pi64,
+                                           _pvp, _pi64, _pi32, _pf64, _pf64, _pf64]),
+    "sa_detect_release": (None, []),
+    "sa_npread_from_raw_batch": (C.c_int, [_vp, _P(RawJob), _pstr, C.c_int64, _P(DetectorParams), C.c_int, C.c_uint,
+                                           _P(RawNpRead), _pf64]),
+    "sa_raw_npread_free": (None, [_P(RawNpRead), C.c_int64]),
+    "sa_npread_last_finish_ms": (C.c_double, []),
+    "sa_raw_npread_write": (C.c_int, [_P(RawNpRead), _str, _vp, _str]),
+    "sa_fasta_subsequence": (C.c_int, [_str, _str, C.c_int64, C.c_int64, C.c_int, _pvp]),
+    "sa_format_f6": (C.c_int, [_str, C.c_double]),
+    "sa_format_py_round6": (C.c_int, [_str, C.c_double]),
+    "sa_pool_configure": (C.c_int, [C.c_int64, C.c_int64]),
+    "sa_host_alloc": (_vp, [C.c_size_t]),
+    "sa_host_free": (None, [_vp]),
+    "sa_pool_release": (None, []),
+    "sa_pool_release_device": (None, []),
+    "sa_mea_batch": (C.c_int, [_P(MeaJob), C.c_int64, C.c_int, C.c_uint, _pvp, _pi64, _pf64, _pi32, _pi32, _pf64]),
+    "sa_mea_release": (None, []),
+    "sa_batch_mea": (C.c_int, [_vp, C.c_uint, _pvp, _pi64, _pf64, _pi32, _pf64]),
+    "sa_mea_printed_posterior": (C.c_double, [C.c_int64]),
+    "sa_mea_printed_posterior_device": (C.c_int, [C.c_int64, C.c_int64, _pf64, C.c_int]),
+    "sa_mea_params": (C.c_int64, [_pi64, _pi64, _pf64, C.c_int64, _pi32, _pi32, _pf64, _pi32, _pi64]),
+    "sa_batch_site_calls": (C.c_int, [_vp, C.c_uint, _P(_P(SiteCall)), _pi64, _pf64]),
+    "sa_batch_position_calls": (C.c_int, [_vp, C.c_uint, _P(_P(PositionCall)), _pi64, _pi32, _pi32, _pf64]),
+    "sa_snp_substitute": (C.c_int, [_str, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_char, _str]),
+    "sa_snp_site_window": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _pi64, _pi64]),
+    "sa_snp_write_read": (C.c_int, [_str, _str, _str, _str, C.c_int, _P(SnpSite), C.c_int64]),
+    "sa_snp_marginals_create": (C.c_int, [_pvp, _pi64, C.c_int64, C.c_int64, C.c_int]),
+    "sa_snp_marginals_destroy": (None, [_vp]),
+    "sa_snp_marginals_add_sites": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int, _vp, C.c_int64]),
+    "sa_snp_marginals_add_batch": (C.c_int, [_vp, _vp, _P(SnpJobMap), C.c_int64, _pf64]),
+    "sa_snp_marginals_checkpoint": (C.c_int, [_vp]),
+    "sa_snp_marginals_rollback": (C.c_int, [_vp]),
+    "sa_snp_marginals_finish": (C.c_int, [_vp, C.c_int64, _pstr, _pvp, _pi64, _pf64]),
+    "sa_snp_group_sites": (C.c_int, [_pi64, _pf64, C.c_int64, C.c_int64, C.c_int, _pi64, _pi64]),
+    "sa_snp_substitute_sites": (C.c_int, [_str, C.c_int64, C.c_int64, C.c_int, _pi64, C.c_int64, C.c_char, _str]),
+    "sa_snp_apply_calls": (C.c_int, [_str, C.c_int64, _vp, C.c_int64, C.c_int32, _str]),
+    "sa_snp_write_marginals": (C.c_int, [_str, _pstr, _vp, C.c_int64]),
+    "sa_position_profile_create": (C.c_int, [_pvp, _vp, _pi64, C.c_int64, C.c_int]),
+    "sa_position_profile_destroy": (None, [_vp]),
+    "sa_position_profile_add_batch": (C.c_int, [_vp, _vp, _P(ProfileJobMap), C.c_int64, C.c_uint, _pf64]),
+    "sa_position_profile_add_records": (C.c_int, [_vp, _P(ProfileJobMap), C.c_int64, _pi64, _pi32, _pi32, _pi64, C.c_uint, _pf64]),
+    "sa_position_profile_checkpoint": (C.c_int, [_vp]),
+    "sa_position_profile_rollback": (C.c_int, [_vp]),
+    "sa_position_profile_finish": (C.c_int, [_vp, _pstr, _pvp, _pi64, _P(C.c_uint32), _pf64]),
+    "sa_position_profile_write": (C.c_int, [_str, _str, C.c_uint32, _pstr, _vp, C.c_int64]),
+    "sa_profile_entropy_term": (C.c_int64, [C.c_int64]),
+    "sa_sort_u64": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, _pf64]),
+    "sa_call_scores_create": (C.c_int, [_pvp, _str, C.c_int32, C.c_double, _vp, C.c_int64, C.c_int]),
+    "sa_call_scores_destroy": (None, [_vp]),
+    "sa_call_scores_add_batch": (C.c_int, [_vp, _vp, _P(ScoreJobMap), C.c_int64, _pf64]),
+    "sa_call_scores_add_records": (C.c_int, [_vp, C.c_int32, C.c_int32, _pf64, _P(C.c_int8), C.c_int64]),
+    "sa_call_scores_checkpoint": (C.c_int, [_vp]),
+    "sa_call_scores_rollback": (C.c_int, [_vp]),
+    "sa_call_scores_finish": (C.c_int, [_vp, _pvp, _pi64, _pvp, _P(CallScoresCounts), _pf64]),
+    "sa_call_scores_write": (C.c_int, [_str, _str, C.c_int32, _vp, C.c_int64, _pi64]),
+    "sa_batch_guide_deviation": (C.c_int, [_vp, _P(DeviationJob), C.c_int64, _pvp, _pi64, _P(DeviationParams), C.c_uint, _vp, _pvp,
+                                           _pi64, _pi32, _pi64, _pvp, _pf64]),
+    "sa_guide_deviation_records": (C.c_int, [_P(DeviationJob), C.c_int64, _pi64, _pi32, _pi32, _pi64, _pvp, _pi64,
+                                             _P(DeviationParams), C.c_int, C.c_uint, _vp, _pvp, _pi64, _pi32, _pi64, _pvp, _pf64]),
+    "sa_guide_deviation_release": (None, []),
+    "sa_kmer_table_create": (C.c_int, [_pvp, _vp, C.c_int64, C.c_double, C.c_int]),
+    "sa_kmer_table_destroy": (None, [_vp]),
+    "sa_kmer_table_add_batch": (C.c_int, [_vp, _vp, _P(Job), C.c_int64, C.c_int, _pf64]),
+    "sa_kmer_table_add_rows": (C.c_int, [_vp, C.c_int, _pi32, _pf64, _pf64, C.c_int64]),
+    "sa_kmer_table_rows": (C.c_int, [_vp, C.c_int, _pvp, _pi64]),
+    "sa_kmer_table_write": (C.c_int, [_vp, C.c_int, _str, C.c_int]),
+    "sa_kmer_table_checkpoint": (C.c_int, [_vp]),
+    "sa_kmer_table_rollback": (C.c_int, [_vp]),
+    "sa_kmer_table_set_positions": (C.c_int, [_vp, _vp, C.c_int64]),
+    "sa_kmer_table_add_batch_at": (C.c_int, [_vp, _vp, _P(Job), C.c_int64, C.c_int, _vp, _pf64]),
+    "sa_kmer_table_position_counts": (C.c_int, [_vp, _pvp, _pvp, _pi64]),
+    "sa_kmer_table_add_at_times": (C.c_int, [_vp, _pf64]),
+    "sa_kmer_table_stats": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _pf64]),
+    "sa_model_write_trained": (C.c_int, [_str, _vp, C.c_double, C.c_double, C.c_int, _vp, _str]),
+    "sa_kmer_table_mixture": (C.c_int, [_vp, C.c_int, _pi32, C.c_int64, _P(MixtureParams), _pf64, _vp, _pf64]),
+    "sa_kmer_table_mixture_start": (C.c_int, [_vp, C.c_int, _pi32, C.c_int64, _P(MixtureParams), _pf64]),
+    "sa_mixture_assign": (C.c_int, [_vp, C.c_double, _pi32, _pi32, _pf64]),
+    "sa_motif_kmer_pairs": (C.c_int, [C.c_int, _str, _str, _str, _pvp, _pi64]),
+    "sa_kmer_table_kde": (C.c_int, [_vp, C.c_int, _pi32, C.c_int64, _pf64, C.c_int64, C.c_double, _pf64, _pi64, _pf64]),
+    "sa_format_py_repr": (C.c_int, [_str, C.c_double]),
+    "sa_f6_units_device": (C.c_int, [_pf64, C.c_int64, _pi64, _pi32, _pi32, C.c_int]),
+    "sa_f6_units": (C.c_int, [C.c_double, _pi64, _pi32]),
+    "sa_plan_digest": (C.c_int, [_vp, _P(Params), _P(Job), C.c_int64, _pstr, C.c_uint, C.c_int, _P(PlanInfo), _P(C.c_uint64)]),
+    "sa_guide_to_anchors": (C.c_int64, [C.c_int64, C.c_int64, C.c_int, C.c_int64, _pi32, _pi64, C.c_int64, C.c_int64, _pi64, _pi64,
+                                        C.c_int64]),
+    "sa_remap_anchors": (C.c_int64, [_pi64, _pi64, C.c_int64, _pi64, C.c_int64, _pi64, _pi64]),
+    "sa_estimate_params": (C.c_int, [_vp, _pf64, _pi64, _pf64, C.c_int64, _str, C.c_int64, _pf64]),
+    "sa_guide_align_batch": (C.c_int, [_P(GuideJob), C.c_int64, _P(GuideParams), C.c_int, C.c_uint, _P(GuideResult), _pvp, _pvp,
+                                       _pf64]),
+    "sa_guide_release": (None, []),
+    "sa_guide_seed": (C.c_int, [_str, C.c_int64, _str, C.c_int64, C.c_int, _pi64, _pi32, _pi64, _pi64]),
+    "sa_guide_format_cigar": (C.c_int64, [_str, C.c_int64, C.c_int64, _str, C.c_int64, C.c_int64, C.c_int, C.c_int64, _pi32, _pi64,
+                                          C.c_int64, _str, C.c_int64]),
+    "sa_ref_index_build": (C.c_int, [_pvp, _pstr, _pstr, _pi64, C.c_int64, C.c_int]),
+    "sa_ref_index_build_fasta": (C.c_int, [_pvp, _str, C.c_int]),
+    "sa_ref_index_info": (C.c_int, [_vp, _P(RefIndexInfo)]),
+    "sa_ref_index_entries": (C.c_int, [_vp, _pvp, _pvp, _pvp, _pvp]),
+    "sa_ref_index_contig": (C.c_int, [_vp, C.c_int64, _pstr, _pi64, _pi64]),
+    "sa_ref_index_destroy": (None, [_vp]),
+    "sa_guide_locate_batch": (C.c_int, [_vp, _pstr, _pi64, C.c_int64, _P(LocateParams), C.c_uint, _P(LocateResult), _pf64]),
+    "sa_locate_release": (None, []),
+    "sa_locate_window": (C.c_int, [_vp, _P(LocateResult), C.c_int64, C.c_int32, _pi64, _pi64]),
+    "sa_hdp_state_load": (C.c_int, [_pvp, _str]),
+    "sa_hdp_state_write": (C.c_int, [_vp, _str]),
+    "sa_hdp_state_info": (C.c_int, [_vp, _P(HdpStateInfo)]),
+    "sa_hdp_state_free": (None, [_vp]),
+    "sa_hdp_state_distr_sample": (C.c_int, [_vp, C.c_int, _pf64]),
+    "sa_hdp_state_sample_weights": (C.c_int, [_vp, _P(_pi64), _P(_pi64), _P(_pf64), _pi64]),
+    "sa_hdp_finalize_distributions": (C.c_int, [_pf64, C.c_int64, _pf64, C.c_int64, C.c_int64, C.c_int, _pf64, _pf64]),
+    "sa_hmm_create": (C.c_int, [_pvp, _vp, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "sa_hmm_destroy": (None, [_vp]),
+    "sa_hmm_view": (C.c_int, [_vp, _P(HmmView)]),
+    "sa_hmm_set_event_model": (C.c_int, [_vp, _pf64]),
+    "sa_hmm_add_expectations": (C.c_int, [_vp, _pf64, C.c_double]),
+    "sa_hmm_add_emission_expectation": (C.c_int, [_vp, C.c_int64, C.c_double, C.c_double]),
+    "sa_hmm_add_assignment": (C.c_int, [_vp, _str, C.c_double]),
+    "sa_hmm_write": (C.c_int, [_vp, _str]),
+    "sa_hmm_load": (C.c_int, [_pvp, _str, C.c_int, C.c_double, C.c_double]),
+    "sa_hmm_add_expectations_file": (C.c_int, [_vp, _str]),
+    "sa_hmm_normalize": (C.c_int, [_vp]),
+    "sa_hmm_load_into_model": (C.c_int, [_vp, _vp]),
+    "sa_model_transitions10": (C.c_int, [_vp, _pf64]),
+    "sa_hdp_state_new": (C.c_int, [_pvp, C.c_int, _str, C.c_int64, _pi64, _pf64, _pf64, _pf64, C.c_double, C.c_double, C.c_int64,
+                                   C.c_double, C.c_double, C.c_double, C.c_double]),
+    "sa_hdp_state_new_tree": (C.c_int, [_pvp, C.c_int64, C.c_int64, _pi64, _pf64, _pf64, _pf64, C.c_double, C.c_double, C.c_int64,
+                                        C.c_double, C.c_double, C.c_double, C.c_double]),
+    "sa_hdp_nig_params_from_table": (C.c_int, [_pf64, C.c_int64, _pf64, _pf64, _pf64, _pf64]),
+    "sa_hdp_state_pass_data": (C.c_int, [_vp, _pf64, _pi64, C.c_int64]),
+    "sa_hdp_state_pass_assignments": (C.c_int, [_vp, _str, _pf64, C.c_int64]),
+    "sa_hdp_state_pass_assignment_file": (C.c_int, [_vp, _str, _str, _pi64]),
+    "sa_hdp_state_kmer_dp": (C.c_int, [_vp, _str]),
+    "sa_hdp_state_gibbs": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.c_int]),
+    "sa_hdp_state_finalize": (C.c_int, [_vp, C.c_int]),
+    "sa_hdp_state_samples_taken": (C.c_int64, [_vp]),
+    "sa_hdp_digamma": (C.c_double, [C.c_double]),
+    "sa_hdp_trigamma": (C.c_double, [C.c_double]),
+    "sa_hdp_distances": (C.c_int, [_pf64, C.c_int64, _pf64, C.c_int64, C.c_int, C.c_int, _pf64, _pf64]),
+    "sa_hdp_distances_release": (None, []),
+    "sa_hdp_distances_paired": (C.c_int, [_pf64, C.c_int64, _pf64, _pf64, C.c_int64, C.c_int, C.c_int, _pf64, _pf64]),
+    "sa_hdp_state_densities": (C.c_int, [_vp, _pi64, C.c_int64, _pf64, C.c_int64, C.c_int, _pf64]),
+    "sa_hdp_state_distances": (C.c_int, [_vp, C.c_int, C.c_int, _pf64, _pf64]),
+    "sa_hdp_state_distance_pairs": (C.c_int, [_vp, C.c_int, _pi64, _pi64, C.c_int64, C.c_int, _pf64]),
+    "sa_hdp_state_compare": (C.c_int, [_vp, _pi64, _vp, _pi64, C.c_int64, C.c_int, C.c_int, _pf64]),
+    "sa_hdp_state_vs_gaussian": (C.c_int, [_vp, _pi64, C.c_int64, _pf64, _pf64, C.c_int, _vp, _pf64]),
+    "sa_hdp_state_alphabet": (C.c_int, [_vp, _str]),
+    "sa_device_count": (C.c_int, []),
+    "sa_device_memory": (C.c_int, [C.c_int, _pi64, _pi64]),
+    "sa_strerror": (_str, [C.c_int]),
+    "sa_version": (_str, []),
+    "sa_free": (None, [_vp]),
+}
+IO_SIGNATURES = {      # the loaders of signalalign_amd/csrc/sa_io.h that the package binds: exported, not in the public header
+    "sa_rawread_is": (C.c_int, [_str]),
+    "sa_rawread_load": (C.c_int, [_str, _P(_P(RawRead))]),
+    "sa_rawread_free": (None, [_P(RawRead)]),
+    "sa_cigar_load": (C.c_int, [_str, _P(_P(Cigar))]),
+    "sa_cigar_free": (None, [_P(Cigar)]),
+}
+EXPORTS = list(SIGNATURES)     # the public header's functions
 
 
 def library_path():
@@ -335,233 +551,10 @@ def lib():
     if not os.path.exists(so):
         raise ImportError("libsignalalign_hip.so is not built (run __graft_entry__.build()); there is no fallback")
     L = C.CDLL(so)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-    L.sa_strerror.restype = C.c_char_p
-    L.sa_strerror.argtypes = [C.c_int]
-    L.sa_version.restype = C.c_char_p
-    L.sa_device_count.restype = C.c_int
-    L.sa_model_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_int, dp, dp, C.POINTER(HdpDesc)]
-    L.sa_model_load.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_char_p]
-    L.sa_model_destroy.argtypes = [C.c_void_p]
-    L.sa_model_alphabet.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sa_model_table5.restype = dp
-    L.sa_model_table5.argtypes = [C.c_void_p]
-    L.sa_model_set_to_hdp_expected_values.argtypes = [C.c_void_p]
-    L.sa_model_set_emission.argtypes = [C.c_void_p, C.c_int]
-    L.sa_model_transitions10.argtypes = [C.c_void_p, dp]
-    L.sa_hmm_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]
-    L.sa_hmm_destroy.argtypes = [C.c_void_p]
-    L.sa_hmm_destroy.restype = None
-    L.sa_hmm_view.argtypes = [C.c_void_p, C.POINTER(HmmView)]
-    L.sa_hmm_set_event_model.argtypes = [C.c_void_p, dp]
-    L.sa_hmm_add_expectations.argtypes = [C.c_void_p, dp, C.c_double]
-    L.sa_hmm_add_emission_expectation.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_double]
-    L.sa_hmm_add_assignment.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
-    L.sa_hmm_write.argtypes = [C.c_void_p, C.c_char_p]
-    L.sa_hmm_load.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_double, C.c_double]
-    L.sa_hmm_normalize.argtypes = [C.c_void_p]
-    L.sa_hmm_add_expectations_file.argtypes = [C.c_void_p, C.c_char_p]
-    L.sa_hmm_load_into_model.argtypes = [C.c_void_p, C.c_void_p]
-    L.sa_kmer_id.restype = C.c_int64
-    L.sa_kmer_id.argtypes = [C.c_void_p, C.c_char_p]
-    L.sa_default_ambig.argtypes = [C.POINTER(C.c_char_p)]
-    L.sa_load_ambig.argtypes = [C.c_char_p, C.POINTER(C.c_char_p)]
-    L.sa_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64,
-                                  C.POINTER(C.c_char_p), C.c_int, C.c_uint]
-    L.sa_batch_create_noise_scaled.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(Params), C.POINTER(Job), dp, C.c_int64,
-                                               C.POINTER(C.c_char_p), C.c_int, C.c_uint]
-    L.sa_model_clone_with_table.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, dp]
-    L.sa_batch_create_deferred.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64,
-                                  C.POINTER(C.c_char_p), C.c_int, C.c_uint]
-    L.sa_batch_run.argtypes = [C.c_void_p]
-    L.sa_plan_check_path_records.restype = C.c_int64
-    L.sa_plan_check_path_records.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.POINTER(C.c_char_p), ip]
-    L.sa_dplan_compare.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64, C.POINTER(C.c_char_p), C.c_int,
-                                   C.c_uint]
-    L.sa_pool_configure.argtypes = [C.c_int64, C.c_int64]
-    L.sa_host_alloc.argtypes = [C.c_size_t]
-    L.sa_host_alloc.restype = C.c_void_p
-    L.sa_host_free.argtypes = [C.c_void_p]
-    L.sa_host_free.restype = None
-    L.sa_batch_n_pairs.argtypes = [C.c_void_p, C.c_int64, ip]
-    L.sa_batch_all_pairs_summary.argtypes = [C.c_void_p, C.c_int64, ip, ip]
-    L.sa_batch_pairs.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    L.sa_batch_pairs16.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), ip]
-    L.sa_batch_pairs_all.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, ip]
-    L.sa_batch_pairs16_all.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), ip]
-    L.sa_batch_pairs8.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), ip]
-    L.sa_batch_pairs8_all.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), ip]
-    L.sa_batch_stats.argtypes = [C.c_void_p, C.POINTER(BatchStats)]
-    L.sa_batch_job_cells.argtypes = [C.c_void_p, C.c_int64, dp, dp]
-    L.sa_batch_destroy.argtypes = [C.c_void_p]
-    L.sa_fasta_subsequence.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
-    L.sa_batch_start.argtypes = [C.c_void_p]
-    L.sa_batch_prepare.argtypes = [C.c_void_p]
-    L.sa_batch_wait.argtypes = [C.c_void_p]
-    L.sa_plan_describe.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.POINTER(C.c_char_p), C.c_uint,
-                                   C.POINTER(PlanInfo), ip, C.c_int64, ip, C.c_int64, ip, C.c_int64]
-    L.sa_plan_digest.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64, C.POINTER(C.c_char_p), C.c_uint,
-                                 C.c_int, C.POINTER(PlanInfo), C.POINTER(C.c_uint64)]
-    L.sa_guide_to_anchors.restype = C.c_int64
-    L.sa_guide_to_anchors.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_int32), ip, C.c_int64,
-                                      C.c_int64, ip, ip, C.c_int64]
-    L.sa_remap_anchors.restype = C.c_int64
-    L.sa_remap_anchors.argtypes = [ip, ip, C.c_int64, ip, C.c_int64, ip, ip]
-    L.sa_estimate_params.argtypes = [C.c_void_p, dp, ip, dp, C.c_int64, C.c_char_p, C.c_int64, dp]
-    L.sa_expect_batch.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Job), C.c_int64, C.POINTER(C.c_char_p),
-                                  C.c_int, C.c_uint, dp, dp, C.POINTER(C.c_void_p), ip]
-    L.sa_expect_last_stats.argtypes = [C.POINTER(BatchStats)]
-    L.sa_scalings_mom.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, dp, C.c_int64, C.c_uint, dp, dp]
-    L.sa_event_align_batch.argtypes = [C.c_void_p, C.POINTER(EaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip,
-                                       C.POINTER(C.c_int32), dp, dp]
-    i32p = C.POINTER(C.c_int32)
-    L.sa_guide_align_batch.argtypes = [C.POINTER(GuideJob), C.c_int64, C.POINTER(GuideParams), C.c_int, C.c_uint,
-                                       C.POINTER(GuideResult), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), dp]
-    L.sa_guide_release.restype = None
-    L.sa_guide_seed.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int, ip, C.POINTER(C.c_int), ip, ip]
-    L.sa_guide_format_cigar.restype = C.c_int64
-    L.sa_guide_format_cigar.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int64,
-                                        i32p, ip, C.c_int64, C.c_char_p, C.c_int64]
-    L.sa_ref_index_build.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), ip, C.c_int64, C.c_int]
-    L.sa_ref_index_build_fasta.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
-    L.sa_ref_index_info.argtypes = [C.c_void_p, C.POINTER(RefIndexInfo)]
-    L.sa_ref_index_entries.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
-    L.sa_ref_index_contig.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), ip, ip]
-    L.sa_ref_index_destroy.argtypes = [C.c_void_p]
-    L.sa_ref_index_destroy.restype = None
-    L.sa_guide_locate_batch.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), ip, C.c_int64, C.POINTER(LocateParams), C.c_uint,
-                                        C.POINTER(LocateResult), dp]
-    L.sa_locate_release.restype = None
-    L.sa_locate_window.argtypes = [C.c_void_p, C.POINTER(LocateResult), C.c_int64, C.c_int32, ip, ip]
-    L.sa_cigar_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(Cigar))]
-    L.sa_cigar_free.argtypes = [C.POINTER(Cigar)]
-    L.sa_cigar_free.restype = None
-    L.sa_detect_events_batch.argtypes = [C.POINTER(RawJob), C.c_int64, C.POINTER(DetectorParams), C.c_int, C.c_uint,
-                                         C.POINTER(C.c_void_p), ip, i32p, dp]
-    L.sa_raw_event_align_batch.argtypes = [C.c_void_p, C.POINTER(RawJob), C.POINTER(C.c_char_p), C.c_int64,
-                                           C.POINTER(DetectorParams), C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip,
-                                           C.POINTER(C.c_void_p), ip, i32p, dp, dp, dp]
-    L.sa_detect_release.restype = None
-    L.sa_npread_from_raw_batch.argtypes = [C.c_void_p, C.POINTER(RawJob), C.POINTER(C.c_char_p), C.c_int64,
-                                           C.POINTER(DetectorParams), C.c_int, C.c_uint, C.POINTER(RawNpRead), dp]
-    L.sa_raw_npread_free.argtypes = [C.POINTER(RawNpRead), C.c_int64]
-    L.sa_raw_npread_free.restype = None
-    L.sa_raw_npread_write.argtypes = [C.POINTER(RawNpRead), C.c_char_p, C.c_void_p, C.c_char_p]
-    L.sa_npread_last_finish_ms.restype = C.c_double
-    L.sa_rawread_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(RawRead))]
-    L.sa_rawread_free.argtypes = [C.POINTER(RawRead)]
-    L.sa_rawread_free.restype = None
-    L.sa_rawread_is.argtypes = [C.c_char_p]
-    L.sa_mea_batch.argtypes = [C.POINTER(MeaJob), C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, i32p, dp]
-    L.sa_batch_mea.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_void_p), ip, dp, i32p, dp]
-    L.sa_batch_site_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(SiteCall)), ip, dp]
-    L.sa_format_py_round6.argtypes = [C.c_char_p, C.c_double]
-    L.sa_batch_position_calls.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.POINTER(PositionCall)), ip, i32p, i32p, dp]
-    L.sa_snp_substitute.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_char, C.c_char_p]
-    L.sa_snp_site_window.argtypes = [C.c_int64, C.c_int64, C.c_int64, ip, ip]
-    L.sa_snp_write_read.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(SnpSite), C.c_int64]
-    L.sa_snp_marginals_create.argtypes = [C.POINTER(C.c_void_p), ip, C.c_int64, C.c_int64, C.c_int]
-    L.sa_snp_marginals_destroy.argtypes = [C.c_void_p]
-    L.sa_snp_marginals_destroy.restype = None
-    L.sa_snp_marginals_add_sites.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_void_p, C.c_int64]
-    L.sa_snp_marginals_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SnpJobMap), C.c_int64, dp]
-    L.sa_snp_marginals_checkpoint.argtypes = [C.c_void_p]
-    L.sa_snp_marginals_rollback.argtypes = [C.c_void_p]
-    L.sa_snp_marginals_finish.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), ip, dp]
-    L.sa_position_profile_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, ip, C.c_int64, C.c_int]
-    L.sa_position_profile_destroy.argtypes = [C.c_void_p]
-    L.sa_position_profile_destroy.restype = None
-    L.sa_position_profile_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ProfileJobMap), C.c_int64, C.c_uint, dp]
-    L.sa_position_profile_add_records.argtypes = [C.c_void_p, C.POINTER(ProfileJobMap), C.c_int64, ip, C.POINTER(C.c_int32),
-                                                  C.POINTER(C.c_int32), ip, C.c_uint, dp]
-    L.sa_position_profile_checkpoint.argtypes = [C.c_void_p]
-    L.sa_position_profile_rollback.argtypes = [C.c_void_p]
-    L.sa_position_profile_finish.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), ip, C.POINTER(C.c_uint32), dp]
-    L.sa_position_profile_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int64]
-    L.sa_profile_entropy_term.argtypes = [C.c_int64]
-    L.sa_profile_entropy_term.restype = C.c_int64
-    L.sa_sort_u64.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, dp]
-    L.sa_call_scores_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_int]
-    L.sa_call_scores_destroy.argtypes = [C.c_void_p]
-    L.sa_call_scores_destroy.restype = None
-    L.sa_call_scores_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreJobMap), C.c_int64, dp]
-    L.sa_call_scores_add_records.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int8), C.c_int64]
-    L.sa_call_scores_checkpoint.argtypes = [C.c_void_p]
-    L.sa_call_scores_rollback.argtypes = [C.c_void_p]
-    L.sa_call_scores_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), ip, C.POINTER(C.c_void_p), C.POINTER(CallScoresCounts), dp]
-    L.sa_call_scores_write.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64, ip]
-    dev_tail = [C.POINTER(DeviationParams), C.c_uint, C.c_void_p, C.POINTER(C.c_void_p), ip, C.POINTER(C.c_int32), ip, C.POINTER(C.c_void_p), dp]
-    L.sa_batch_guide_deviation.argtypes = [C.c_void_p, C.POINTER(DeviationJob), C.c_int64, C.POINTER(C.c_void_p), ip] + dev_tail
-    L.sa_guide_deviation_records.argtypes = ([C.POINTER(DeviationJob), C.c_int64, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ip,
-                                              C.POINTER(C.c_void_p), ip] + dev_tail[:1] + [C.c_int] + dev_tail[1:])
-    L.sa_guide_deviation_release.argtypes = []
-    L.sa_guide_deviation_release.restype = None
-    L.sa_snp_group_sites.argtypes = [ip, dp, C.c_int64, C.c_int64, C.c_int, ip, ip]
-    L.sa_snp_substitute_sites.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int, ip, C.c_int64, C.c_char, C.c_char_p]
-    L.sa_snp_apply_calls.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_char_p]
-    L.sa_snp_write_marginals.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_int64]
-    L.sa_kmer_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_double, C.c_int]
-    L.sa_kmer_table_destroy.argtypes = [C.c_void_p]
-    L.sa_kmer_table_destroy.restype = None
-    L.sa_kmer_table_add_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int64, C.c_int, dp]
-    L.sa_kmer_table_add_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), dp, dp, C.c_int64]
-    L.sa_kmer_table_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), ip]
-    L.sa_kmer_table_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
-    L.sa_kmer_table_checkpoint.argtypes = [C.c_void_p]
-    L.sa_kmer_table_rollback.argtypes = [C.c_void_p]
-    L.sa_kmer_table_set_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.sa_kmer_table_add_batch_at.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int64, C.c_int, C.c_void_p, dp]
-    L.sa_kmer_table_position_counts.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), ip]
-    L.sa_kmer_table_add_at_times.argtypes = [C.c_void_p, dp]
-    L.sa_kmer_table_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, dp]
-    L.sa_kmer_table_mixture.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp, C.c_void_p, dp]
-    L.sa_kmer_table_mixture_start.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, C.POINTER(MixtureParams), dp]
-    L.sa_kmer_table_kde.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int64, dp, C.c_int64, C.c_double, dp, ip, dp]
-    L.sa_mixture_assign.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
-    L.sa_motif_kmer_pairs.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), ip]
-    L.sa_model_write_trained.argtypes = [C.c_char_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_char_p]
-    L.sa_format_py_repr.argtypes = [C.c_char_p, C.c_double]
-    L.sa_f6_units_device.argtypes = [dp, C.c_int64, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
-    L.sa_f6_units.argtypes = [C.c_double, ip, C.POINTER(C.c_int32)]
-    L.sa_mea_printed_posterior_device.argtypes = [C.c_int64, C.c_int64, dp, C.c_int]
-    L.sa_mea_printed_posterior.restype = C.c_double
-    L.sa_mea_printed_posterior.argtypes = [C.c_int64]
-    L.sa_mea_params.restype = C.c_int64
-    L.sa_mea_params.argtypes = [ip, ip, dp, C.c_int64, i32p, i32p, dp, i32p, ip]
-    L.sa_free.argtypes = [C.c_void_p]
-    L.sa_hdp_state_load.argtypes = [C.POINTER(C.c_void_p), C.c_char_p]
-    L.sa_hdp_state_write.argtypes = [C.c_void_p, C.c_char_p]
-    L.sa_hdp_state_info.argtypes = [C.c_void_p, C.POINTER(HdpStateInfo)]
-    L.sa_hdp_state_free.argtypes = [C.c_void_p]
-    L.sa_hdp_state_distr_sample.argtypes = [C.c_void_p, C.c_int, dp]
-    L.sa_hdp_state_sample_weights.argtypes = [C.c_void_p, C.POINTER(ip), C.POINTER(ip), C.POINTER(dp), ip]
-    L.sa_hdp_finalize_distributions.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int64, C.c_int, dp, dp]
-    L.sa_hdp_state_new.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_int64, ip, dp, dp, dp, C.c_double, C.c_double, C.c_int64,
-                                   C.c_double, C.c_double, C.c_double, C.c_double]
-    L.sa_hdp_state_new_tree.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_int64, ip, dp, dp, dp, C.c_double, C.c_double, C.c_int64,
-                                        C.c_double, C.c_double, C.c_double, C.c_double]
-    L.sa_hdp_nig_params_from_table.argtypes = [dp, C.c_int64, dp, dp, dp, dp]
-    L.sa_hdp_state_pass_data.argtypes = [C.c_void_p, dp, ip, C.c_int64]
-    L.sa_hdp_state_pass_assignments.argtypes = [C.c_void_p, C.c_char_p, dp, C.c_int64]
-    L.sa_hdp_state_pass_assignment_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, ip]
-    L.sa_hdp_state_kmer_dp.argtypes = [C.c_void_p, C.c_char_p]
-    L.sa_hdp_state_gibbs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.c_int]
-    L.sa_hdp_state_finalize.argtypes = [C.c_void_p, C.c_int]
-    L.sa_hdp_state_samples_taken.argtypes = [C.c_void_p]
-    L.sa_hdp_state_samples_taken.restype = C.c_int64
-    L.sa_hdp_digamma.argtypes = [C.c_double]
-    L.sa_hdp_digamma.restype = C.c_double
-    L.sa_hdp_trigamma.argtypes = [C.c_double]
-    L.sa_hdp_trigamma.restype = C.c_double
-    L.sa_hdp_distances.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_int, dp, dp]
-    L.sa_hdp_distances_release.restype = None
-    L.sa_hdp_distances_paired.argtypes = [dp, C.c_int64, dp, dp, C.c_int64, C.c_int, C.c_int, dp, dp]
-    L.sa_hdp_state_densities.argtypes = [C.c_void_p, ip, C.c_int64, dp, C.c_int64, C.c_int, dp]
-    L.sa_hdp_state_distances.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp]
-    L.sa_hdp_state_distance_pairs.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_int64, C.c_int, dp]
-    L.sa_hdp_state_compare.argtypes = [C.c_void_p, ip, C.c_void_p, ip, C.c_int64, C.c_int, C.c_int, dp]
-    L.sa_hdp_state_alphabet.argtypes = [C.c_void_p, C.c_char_p]
-    L.sa_hdp_state_vs_gaussian.argtypes = [C.c_void_p, ip, C.c_int64, dp, dp, C.c_int, C.c_void_p, dp]
+    for table in (SIGNATURES, IO_SIGNATURES):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)       # (a symbol the library lacks is an error here, not at its first call)
+            fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 
@@ -577,6 +570,70 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _copy_out(ptr, shape, dtype, free=True):
+    """`shape` records of `dtype` copied out of the library's array at `ptr`, which is then released with sa_free (free=False: it
+    stays the library's)"""
+    out = np.zeros(shape, dtype=dtype)
+    if out.nbytes:
+        C.memmove(out.ctypes.data, ptr, out.nbytes)
+    if free:
+        lib().sa_free(ptr)
+    return out
+
+
+def _timing(stats, kernel_ms, t0=None):
+    """kernel_ms -- and call_ms, the C call alone without the wrapper's marshalling, when it was timed from t0 -- into the optional
+    stats dict"""
+    if stats is not None:
+        stats["kernel_ms"] = kernel_ms.value
+        if t0 is not None:
+            stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+
+
+def _records(struct, dicts):
+    """(a C array of `struct` with one element per dict, filled by the struct's own field list but its padding; their number)"""
+    dicts = list(dicts)
+    arr = (struct * max(len(dicts), 1))()
+    names = [f for f, _ in struct._fields_ if f != "pad"]
+    for i, d in enumerate(dicts):
+        for f in names:
+            setattr(arr[i], f, int(d[f]))
+    return arr, len(dicts)
+
+
+class _Handle:
+    """Owner of one library handle (self._h): close() hands it to the class's destroy function (_DESTROY) once, as does collection."""
+    _DESTROY = None
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def device_count():
@@ -599,8 +656,9 @@ def default_ambig(table=None):
     return arr
 
 
-class Model:
+class Model(_Handle):
     """StateMachine3 / StateMachine3_HDP as the C library holds it."""
+    _DESTROY = "sa_model_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -608,8 +666,7 @@ class Model:
     @classmethod
     def create(cls, alphabet, k, transitions10, table5, hdp=None):
         h = C.c_void_p()
-        t10 = np.ascontiguousarray(transitions10, dtype=np.float64)
-        tb = np.ascontiguousarray(table5, dtype=np.float64)
+        t10, tb = _f64(transitions10), _f64(table5)
         _chk(lib().sa_model_create(C.byref(h), 3, alphabet.encode(), k, _dp(t10), _dp(tb), hdp), "sa_model_create")
         return cls(h)
 
@@ -647,23 +704,12 @@ class Model:
     def clone_with_table(self, table5):
         """sa_model_clone_with_table: the same model with another emission table (a read's own noise scaling)."""
         h = C.c_void_p()
-        tb = np.ascontiguousarray(table5, dtype=np.float64)
+        tb = _f64(table5)
         _chk(lib().sa_model_clone_with_table(C.byref(h), self._h, _dp(tb)), "sa_model_clone_with_table")
         return Model(h)
 
     def set_to_hdp_expected_values(self):
         _chk(lib().sa_model_set_to_hdp_expected_values(self._h), "sa_model_set_to_hdp_expected_values")
-
-    def close(self):
-        if self._h:
-            lib().sa_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _make_jobs(jobs):
@@ -686,17 +732,17 @@ def _make_jobs(jobs):
     return arr, keep
 
 
-class HostBlock:
+class HostBlock(_Handle):
     """sa_host_alloc: one page-locked block; empty(shape, dtype) carves 8-byte aligned numpy arrays out of it (for the event
     records and anchor arrays of jobs passed with FLAG_INPUTS_IN_HOST_BLOCK)."""
+    _DESTROY = "sa_host_free"
 
     def __init__(self, nbytes):
-        L = lib()
         self.nbytes = int(nbytes)
-        self._p = L.sa_host_alloc(self.nbytes)
-        if not self._p:
+        self._h = lib().sa_host_alloc(self.nbytes)
+        if not self._h:
             raise SaError(-2, "sa_host_alloc")
-        self._buf = (C.c_char * self.nbytes).from_address(self._p)
+        self._buf = (C.c_char * self.nbytes).from_address(self._h)
         self._used = 0
 
     def empty(self, shape, dtype):
@@ -709,16 +755,8 @@ class HostBlock:
         return np.frombuffer(self._buf, dtype=dt, count=n, offset=off).reshape(shape)
 
     def close(self):
-        if self._p:
-            self._buf = None
-            lib().sa_host_free(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._buf = None
+        super().close()
 
 
 def jobs_bytes_in_block(jobs):
@@ -755,8 +793,9 @@ class JobArray:
         self.arr, self._keep = _make_jobs(jobs)
 
 
-class Batch:
+class Batch(_Handle):
     """sa_batch_t: plan + HBM-resident inputs; run() launches the kernels."""
+    _DESTROY = "sa_batch_destroy"
 
     def __init__(self, model, params, jobs, ambig=None, device=0, flags=0, deferred=False, noise=None):
         """deferred=True: sa_batch_create_deferred (the plan is collected on the batch's first use; the job arrays and the
@@ -888,19 +927,9 @@ class Batch:
         st = np.zeros(max(n, 1), dtype=np.int32)
         kms = C.c_double()
         t0 = time.perf_counter()
-        _chk(lib().sa_batch_mea(self._h, 0, ptrs, _ip(cnt), _dp(sums), st.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(kms)),
-             "sa_batch_mea")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
-            stats["call_ms"] = (time.perf_counter() - t0) * 1e3
-        out = []
-        for i in range(n):
-            a = np.zeros((int(cnt[i]), 2), dtype=np.int32)
-            if cnt[i]:
-                C.memmove(a.ctypes.data, ptrs[i], 8 * int(cnt[i]))
-            lib().sa_free(ptrs[i])
-            out.append((a, float(sums[i]), int(st[i])))
-        return out
+        _chk(lib().sa_batch_mea(self._h, 0, ptrs, _ip(cnt), _dp(sums), _i32p(st), C.byref(kms)), "sa_batch_mea")
+        _timing(stats, kms, t0)
+        return [(_copy_out(ptrs[i], (int(cnt[i]), 2), np.int32), float(sums[i]), int(st[i])) for i in range(n)]
 
     def site_calls(self, stats=None):
         """sa_batch_site_calls (a batch created with FLAG_SITE_CALLS, after run()): per job a dict of numpy arrays -- x [n] (k-mer
@@ -912,16 +941,10 @@ class Batch:
         kms = C.c_double()
         t0 = time.perf_counter()
         _chk(lib().sa_batch_site_calls(self._h, 0, ptrs, _ip(cnt), C.byref(kms)), "sa_batch_site_calls")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
-            stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+        _timing(stats, kms, t0)
         out = []
         for i in range(n):
-            m = int(cnt[i])
-            rec = np.zeros(m, dtype=SITE_CALL_DTYPE)
-            if m:
-                C.memmove(rec.ctypes.data, ptrs[i], C.sizeof(SiteCall) * m)
-            lib().sa_free(ptrs[i])
+            rec = _copy_out(ptrs[i], int(cnt[i]), SITE_CALL_DTYPE)
             letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
             out.append({"x": rec["x"].copy(), "letters": letters, "units": rec["units"].copy(), "prob": rec["prob"].copy()})
         return out
@@ -937,20 +960,13 @@ class Batch:
         xmin = np.zeros(max(n, 1), dtype=np.int32)
         xmax = np.zeros(max(n, 1), dtype=np.int32)
         kms = C.c_double()
-        i32 = C.POINTER(C.c_int32)
         t0 = time.perf_counter()
-        _chk(lib().sa_batch_position_calls(self._h, 0, ptrs, _ip(cnt), xmin.ctypes.data_as(i32), xmax.ctypes.data_as(i32),
-                                           C.byref(kms)), "sa_batch_position_calls")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
-            stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+        _chk(lib().sa_batch_position_calls(self._h, 0, ptrs, _ip(cnt), _i32p(xmin), _i32p(xmax), C.byref(kms)),
+             "sa_batch_position_calls")
+        _timing(stats, kms, t0)
         out = []
         for i in range(n):
-            m = int(cnt[i])
-            rec = np.zeros(m, dtype=POSITION_CALL_DTYPE)
-            if m:
-                C.memmove(rec.ctypes.data, ptrs[i], C.sizeof(PositionCall) * m)
-            lib().sa_free(ptrs[i])
+            rec = _copy_out(ptrs[i], int(cnt[i]), POSITION_CALL_DTYPE)
             letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
             out.append({"p": rec["p"].copy(), "n_rows": rec["n_rows"].copy(), "letters": letters, "sum": rec["sum"].copy(),
                         "prob": rec["prob"].copy(), "x_min": int(xmin[i]), "x_max": int(xmax[i])})
@@ -960,17 +976,6 @@ class Batch:
         s = BatchStats()
         _chk(lib().sa_batch_stats(self._h, C.byref(s)), "sa_batch_stats")
         return s
-
-    def close(self):
-        if self._h:
-            lib().sa_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def expect_batch(model, params, jobs, ambig=None, device=0, flags=0, pseudocount=0.0):
@@ -988,13 +993,7 @@ def expect_batch(model, params, jobs, ambig=None, device=0, flags=0, pseudocount
     cnt = np.zeros(max(n, 1), dtype=np.int64)
     _chk(lib().sa_expect_batch(model._h, C.byref(params), arr, n, amb, device, flags, _dp(trans), _dp(lik), ptrs,
                                _ip(cnt)), "sa_expect_batch")
-    assigns = []
-    for j in range(n):
-        a = np.zeros((int(cnt[j]), 2), dtype=np.int64)
-        if cnt[j]:
-            C.memmove(a.ctypes.data, ptrs[j], 16 * int(cnt[j]))
-        lib().sa_free(ptrs[j])
-        assigns.append(a)
+    assigns = [_copy_out(ptrs[j], (int(cnt[j]), 2), np.int64) for j in range(n)]
     del keep
     return trans[:n], lik[:n], assigns
 
@@ -1031,7 +1030,7 @@ FLAG_RNA = 4
 
 def scalings_mom(model, sequence, event_means, flags=0):
     """sa_scalings_mom: (shift, scale) by the method of moments (impl/eventAligner.c:784-843)."""
-    ev = np.ascontiguousarray(event_means, dtype=np.float64)
+    ev = _f64(event_means)
     sb = sequence.encode()
     sh, sc = C.c_double(), C.c_double()
     _chk(lib().sa_scalings_mom(model._h, sb, len(sb), _dp(ev), len(ev), flags, C.byref(sh), C.byref(sc)), "sa_scalings_mom")
@@ -1045,7 +1044,7 @@ def event_align_batch(model, jobs, device=0, flags=0, stats=None):
     arr = (EaJob * max(n, 1))()
     keep = []
     for i, j in enumerate(jobs):
-        ev = np.ascontiguousarray(j["event_mean"], dtype=np.float64)
+        ev = _f64(j["event_mean"])
         sb = j["sequence"].encode()
         keep.append((ev, sb))
         arr[i] = EaJob(sb, len(sb), _dp(ev), len(ev), j["scale"], j["shift"], j.get("var", 1.0))
@@ -1055,25 +1054,17 @@ def event_align_batch(model, jobs, device=0, flags=0, stats=None):
     cells = np.zeros(max(n, 1), dtype=np.float64)
     kms = C.c_double()
     t0 = time.perf_counter()
-    _chk(lib().sa_event_align_batch(model._h, arr, n, device, flags, ptrs, _ip(cnt), st.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    _dp(cells), C.byref(kms)), "sa_event_align_batch")
+    _chk(lib().sa_event_align_batch(model._h, arr, n, device, flags, ptrs, _ip(cnt), _i32p(st), _dp(cells), C.byref(kms)),
+         "sa_event_align_batch")
+    _timing(stats, kms, t0)
     if stats is not None:
         stats["cells"] = cells[:n].copy()
-        stats["kernel_ms"] = kms.value
-        stats["call_ms"] = (time.perf_counter() - t0) * 1e3  # the C call alone, without this wrapper's marshalling
     out = []
     for i in range(n):
-        a = np.zeros((int(cnt[i]), 2), dtype=np.int32)
-        if cnt[i]:
-            C.memmove(a.ctypes.data, ptrs[i], 8 * int(cnt[i]))
-        lib().sa_free(ptrs[i])
+        a = _copy_out(ptrs[i], (int(cnt[i]), 2), np.int32)
         out.append((a[:, 0].copy(), a[:, 1].copy(), int(st[i])))
     del keep
     return out
-
-
-def _i32p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 GUIDE_NO_ALIGNMENT, GUIDE_SHORT, GUIDE_BAND_EDGE, GUIDE_EMPTY, GUIDE_TRACE = 1, 2, 4, 8, 16
@@ -1102,16 +1093,9 @@ def guide_align_batch(jobs, params=None, device=0, stats=None):
     t0 = time.perf_counter()
     _chk(lib().sa_guide_align_batch(arr, n, C.byref(params) if params is not None else None, device, 0, res, C.byref(pt), C.byref(pl),
                                     C.byref(kms)), "sa_guide_align_batch")
-    if stats is not None:
-        stats["kernel_ms"] = kms.value
-        stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+    _timing(stats, kms, t0)
     tot = sum(int(res[i].n_ops) for i in range(n))
-    ot, ol = np.zeros(tot, dtype=np.int32), np.zeros(tot, dtype=np.int64)
-    if tot:
-        C.memmove(ot.ctypes.data, pt, 4 * tot)
-        C.memmove(ol.ctypes.data, pl, 8 * tot)
-    lib().sa_free(pt)
-    lib().sa_free(pl)
+    ot, ol = _copy_out(pt, tot, np.int32), _copy_out(pl, tot, np.int64)
     out = []
     for i in range(n):
         r = res[i]
@@ -1155,19 +1139,12 @@ LOCATE_NONE, LOCATE_AMBIGUOUS, LOCATE_OVERFLOW, LOCATE_EMPTY = 1, 2, 4, 8
 LOCATE_FIELDS = ("status", "contig", "reverse", "pos", "key", "votes", "second_votes", "hits", "seeds", "repetitive")
 
 
-class RefIndex:
+class RefIndex(_Handle):
     """sa_ref_index_t: the 15-mer index of a whole reference (device < 0: host only)"""
+    _DESTROY = "sa_ref_index_destroy"
 
     def __init__(self, handle):
         self._h = handle
-
-    def close(self):
-        if self._h:
-            lib().sa_ref_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
     def contig(self, i):
         """(name, start in the concatenation, length)"""
@@ -1207,12 +1184,7 @@ def ref_index_entries(index):
     p = [C.c_void_p() for _ in range(4)]
     _chk(lib().sa_ref_index_entries(index._h, *[C.byref(x) for x in p]), "sa_ref_index_entries")
     shapes = ((info["n_entries"], np.uint32), (info["n_entries"], np.int32), ((1 << info["q"]) + 1, np.int32), (info["n_contigs"] + 1, np.int64))
-    out = []
-    for ptr, (n, dt) in zip(p, shapes):
-        a = np.zeros(n, dtype=dt)
-        if n:
-            C.memmove(a.ctypes.data, ptr, a.nbytes)
-        out.append(a)
+    out = [_copy_out(ptr, n, dt, free=False) for ptr, (n, dt) in zip(p, shapes)]      # (the arrays stay the index's)
     return dict(codes=out[0], pos=out[1], table=out[2], starts=out[3], q=int(info["q"]), total=int(info["total_bases"]))
 
 
@@ -1231,9 +1203,7 @@ def guide_locate_batch(index, reads, params=None, stats=None):
     t0 = time.perf_counter()
     _chk(lib().sa_guide_locate_batch(index._h, arr, ln, n, C.byref(params) if params is not None else None, 0, res, C.byref(kms)),
          "sa_guide_locate_batch")
-    if stats is not None:
-        stats["kernel_ms"] = kms.value
-        stats["call_ms"] = (time.perf_counter() - t0) * 1e3
+    _timing(stats, kms, t0)
     return [{f: int(getattr(res[i], f)) for f in LOCATE_FIELDS} for i in range(n)]
 
 
@@ -1269,21 +1239,13 @@ def _raw_jobs(jobs):
     for i, j in enumerate(jobs):
         raw = np.ascontiguousarray(j["raw"], dtype=np.int16)
         keep.append(raw)
-        arr[i] = RawJob(raw.ctypes.data_as(C.POINTER(C.c_int16)), len(raw), j["digitisation"], j["offset"], j["range"],
+        arr[i] = RawJob(raw.ctypes.data_as(_P(C.c_int16)), len(raw), j["digitisation"], j["offset"], j["range"],
                         j["sample_rate"], j["start_time"])
     return arr, keep
 
 
 def _detector_params(params):
     return None if params is None else C.byref(DetectorParams(*params))
-
-
-def _raw_events(ptrs, cnt, i):
-    a = np.zeros(int(cnt[i]), dtype=RAW_EVENT_DTYPE)
-    if cnt[i]:
-        C.memmove(a.ctypes.data, ptrs[i], RAW_EVENT_DTYPE.itemsize * int(cnt[i]))
-    lib().sa_free(ptrs[i])
-    return a
 
 
 def detect_events_batch(jobs, params=None, rna=False, device=0, stats=None):
@@ -1299,10 +1261,10 @@ def detect_events_batch(jobs, params=None, rna=False, device=0, stats=None):
     _chk(lib().sa_detect_events_batch(arr, n, _detector_params(params), device, FLAG_RNA if rna else 0, ptrs, _ip(cnt), _i32p(st),
                                       C.byref(kms)), "sa_detect_events_batch")
     del keep
+    _timing(stats, kms)
     if stats is not None:
         stats["status"] = st[:n].copy()
-        stats["kernel_ms"] = kms.value
-    return [_raw_events(ptrs, cnt, i) for i in range(n)]
+    return [_copy_out(ptrs[i], int(cnt[i]), RAW_EVENT_DTYPE) for i in range(n)]
 
 
 def raw_event_align_batch(model, jobs, sequences, rna=False, params=None, device=0, stats=None):
@@ -1322,16 +1284,12 @@ def raw_event_align_batch(model, jobs, sequences, rna=False, params=None, device
                                         _ip(ev_n), pr_p, _ip(pr_n), _i32p(st), _dp(sh), _dp(sc), C.byref(kms)),
          "sa_raw_event_align_batch")
     del keep
-    if stats is not None:
-        stats["kernel_ms"] = kms.value
+    _timing(stats, kms)
     k = model.alphabet()[1]
     out = []
     for i in range(n):
-        ev = _raw_events(ev_p, ev_n, i)
-        a = np.zeros((int(pr_n[i]), 2), dtype=np.int32)
-        if pr_n[i]:
-            C.memmove(a.ctypes.data, pr_p[i], 8 * int(pr_n[i]))
-        lib().sa_free(pr_p[i])
+        ev = _copy_out(ev_p[i], int(ev_n[i]), RAW_EVENT_DTYPE)
+        a = _copy_out(pr_p[i], (int(pr_n[i]), 2), np.int32)
         seq = sequences[i].replace("U", "T") if rna else sequences[i]
         kmers = [seq[p:p + k][::-1] if rna else seq[p:p + k] for p in range(len(seq) - k + 1)]
         ms = [kmers[x] if x >= 0 else "" for x in ev["kmer_idx"].tolist()]
@@ -1359,8 +1317,8 @@ def npread_from_raw_batch(model, jobs, sequences, params=None, device=0, flags=0
     _chk(lib().sa_npread_from_raw_batch(model._h, arr, sp, n, _detector_params(params), device, flags, res, C.byref(kms)),
          "sa_npread_from_raw_batch")
     del keep
+    _timing(stats, kms)
     if stats is not None:
-        stats["kernel_ms"] = kms.value
         stats["finish_ms"] = lib().sa_npread_last_finish_ms()
     out = []
     try:
@@ -1407,9 +1365,7 @@ def mea_batch(jobs, device=0, flags=0, stats=None):
     arr = (MeaJob * max(n, 1))()
     keep = []
     for i, j in enumerate(jobs):
-        ev = np.ascontiguousarray(j["event_idx"], dtype=np.int32)
-        rf = np.ascontiguousarray(j["ref_idx"], dtype=np.int32)
-        po = np.ascontiguousarray(j["posterior"], dtype=np.float64)
+        ev, rf, po = _i32(j["event_idx"]), _i32(j["ref_idx"]), _f64(j["posterior"])
         sh = np.asarray(j["shortest"], dtype=np.float64)
         sh = np.ascontiguousarray(np.where(np.isfinite(sh), sh, MEA_INF).astype(np.int32))
         keep.append((ev, rf, po, sh))
@@ -1422,25 +1378,15 @@ def mea_batch(jobs, device=0, flags=0, stats=None):
     kms = C.c_double()
     t0 = time.perf_counter()
     _chk(lib().sa_mea_batch(arr, n, device, flags, ptrs, _ip(cnt), _dp(sums), _i32p(st), _i32p(ne), C.byref(kms)), "sa_mea_batch")
-    if stats is not None:
-        stats["kernel_ms"] = kms.value
-        stats["call_ms"] = (time.perf_counter() - t0) * 1e3
-    out = []
-    for i in range(n):
-        a = np.zeros((int(cnt[i]), 2), dtype=np.int32)
-        if cnt[i]:
-            C.memmove(a.ctypes.data, ptrs[i], 8 * int(cnt[i]))
-        lib().sa_free(ptrs[i])
-        out.append((a, float(sums[i]), int(st[i]), int(ne[i])))
+    _timing(stats, kms, t0)
+    out = [(_copy_out(ptrs[i], (int(cnt[i]), 2), np.int32), float(sums[i]), int(st[i]), int(ne[i])) for i in range(n)]
     del keep
     return out
 
 
 def mea_params(reference_index, event_index, posterior):
     """sa_mea_params: event-table columns -> (event_idx, ref_idx, posterior, shortest_ref_per_event)."""
-    ri = np.ascontiguousarray(reference_index, dtype=np.int64)
-    ei = np.ascontiguousarray(event_index, dtype=np.int64)
-    po = np.ascontiguousarray(posterior, dtype=np.float64)
+    ri, ei, po = _i64(reference_index), _i64(event_index), _f64(posterior)
     n = len(ri)
     rows = np.zeros(max(n, 1), dtype=np.int32)
     cols = np.zeros(max(n, 1), dtype=np.int32)
@@ -1469,17 +1415,14 @@ def guide_to_anchors(start1, end1, strand1, start2, ops, trim):
     ln = np.array([o[1] for o in ops], dtype=np.int64)
     cap = int(ln.sum()) + 1
     ax, ay = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
-    n = lib().sa_guide_to_anchors(start1, end1, int(strand1), start2, t.ctypes.data_as(C.POINTER(C.c_int32)), _ip(ln),
-                                  len(t), trim, _ip(ax), _ip(ay), cap)
+    n = lib().sa_guide_to_anchors(start1, end1, int(strand1), start2, _i32p(t), _ip(ln), len(t), trim, _ip(ax), _ip(ay), cap)
     if n < 0:
         raise SaError(int(n), "sa_guide_to_anchors")
     return ax[:n].copy(), ay[:n].copy()
 
 
 def remap_anchors(ax, ay, event_map, map_offset):
-    axa = np.ascontiguousarray(ax, dtype=np.int64)
-    aya = np.ascontiguousarray(ay, dtype=np.int64)
-    em = np.ascontiguousarray(event_map, dtype=np.int64)
+    axa, aya, em = _i64(ax), _i64(ay), _i64(event_map)
     ox, oy = np.zeros(len(axa) + 1, dtype=np.int64), np.zeros(len(axa) + 1, dtype=np.int64)
     n = lib().sa_remap_anchors(_ip(axa), _ip(aya), len(axa), _ip(em), map_offset, _ip(ox), _ip(oy))
     if n < 0:
@@ -1488,7 +1431,7 @@ def remap_anchors(ax, ay, event_map, map_offset):
 
 
 def estimate_params(model, table5, strand_event_map, events4, strand_read):
-    em = np.ascontiguousarray(strand_event_map, dtype=np.int64)
+    em = _i64(strand_event_map)
     out = np.zeros(7, dtype=np.float64)
     _chk(lib().sa_estimate_params(model._h, _dp(table5), _ip(em), _dp(events4), events4.shape[0],
                                   strand_read.encode(), len(strand_read), _dp(out)), "sa_estimate_params")
@@ -1536,9 +1479,10 @@ def device_memory(device=0):
 HMM_GAUSSIAN, HMM_HDP = 0, 1
 
 
-class Hmm:
+class Hmm(_Handle):
     """sa_hmm_t: the expectations object of the EM loop (Hmm / ContinuousPairHmm / HdpHmm, impl/continuousHmm.c).  The numpy arrays
     `transitions`, `event_model`, `event_expectations`, `posteriors`, `observed` are VIEWS of the object's own storage."""
+    _DESTROY = "sa_hmm_destroy"
 
     def __init__(self, handle):
         self._h = handle
@@ -1604,11 +1548,11 @@ class Hmm:
         return [raw[i * k:(i + 1) * k] for i in range(n)], np.ctypeslib.as_array(v.assignment_events, shape=(n,)).copy()
 
     def set_event_model(self, table5):
-        t = np.ascontiguousarray(table5, dtype=np.float64)
+        t = _f64(table5)
         _chk(lib().sa_hmm_set_event_model(self._h, _dp(t)), "sa_hmm_set_event_model")
 
     def add_expectations(self, trans9, likelihood):
-        t = np.ascontiguousarray(trans9, dtype=np.float64).reshape(-1)
+        t = _f64(trans9).reshape(-1)
         _chk(lib().sa_hmm_add_expectations(self._h, _dp(t), float(likelihood)), "sa_hmm_add_expectations")
 
     def add_emission_expectation(self, kmer_index, mean, p):
@@ -1630,21 +1574,11 @@ class Hmm:
     def load_into_model(self, model):
         _chk(lib().sa_hmm_load_into_model(model._h, self._h), "sa_hmm_load_into_model")
 
-    def close(self):
-        if self._h:
-            lib().sa_hmm_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class HdpState:
+class HdpState(_Handle):
     """The whole state of a serialised NanoporeHDP (sa_hdp_state_*: the deterministic pieces of the HDP rebuild).  Arrays are
     copies (numpy) of the views sa_hdp_state_info hands out."""
+    _DESTROY = "sa_hdp_state_free"
 
     def __init__(self, path=None, _handle=None):
         self._h = _handle if _handle is not None else C.c_void_p()
@@ -1662,10 +1596,8 @@ class HdpState:
         """sa_hdp_state_new: a NanoporeHDP without data.  layout: HDP_LAYOUT_*; grid = (start, stop, length); nig = (mu, nu, alpha,
         beta); gamma: fixed concentration parameters by depth, or gamma_alpha / gamma_beta: a Gamma prior on them."""
         h = C.c_void_p()
-        g = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.float64)
-        ga = None if gamma_alpha is None else np.ascontiguousarray(gamma_alpha, dtype=np.float64)
-        gb = None if gamma_beta is None else np.ascontiguousarray(gamma_beta, dtype=np.float64)
-        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int64)
+        g, ga, gb = (None if v is None else _f64(v) for v in (gamma, gamma_alpha, gamma_beta))
+        gr = None if groups is None else _i64(groups)
         depth = 2 if int(layout) == HDP_LAYOUT_FLAT else 3   # (the C entry point reads `depth` values of each vector it is given)
         for v in (g, ga, gb):
             if v is not None and len(v) != depth:
@@ -1682,10 +1614,8 @@ class HdpState:
     def new_tree(cls, parents, depth, grid, nig, gamma=None, gamma_alpha=None, gamma_beta=None):
         """sa_hdp_state_new_tree: a plain HierarchicalDirichletProcess over the tree `parents` (-1 for the base DP)"""
         h = C.c_void_p()
-        pa = np.ascontiguousarray(parents, dtype=np.int64)
-        g = None if gamma is None else np.ascontiguousarray(gamma, dtype=np.float64)
-        ga = None if gamma_alpha is None else np.ascontiguousarray(gamma_alpha, dtype=np.float64)
-        gb = None if gamma_beta is None else np.ascontiguousarray(gamma_beta, dtype=np.float64)
+        pa = _i64(parents)
+        g, ga, gb = (None if v is None else _f64(v) for v in (gamma, gamma_alpha, gamma_beta))
         for v in (g, ga, gb):
             if v is not None and len(v) != int(depth):
                 raise SaError(-1, "sa_hdp_state_new_tree: %d concentration parameters for depth %d" % (len(v), int(depth)))
@@ -1695,15 +1625,14 @@ class HdpState:
         return cls(_handle=h)
 
     def pass_data(self, data, dp_ids):
-        d = np.ascontiguousarray(data, dtype=np.float64)
-        i = np.ascontiguousarray(dp_ids, dtype=np.int64)
+        d, i = _f64(data), _i64(dp_ids)
         _chk(lib().sa_hdp_state_pass_data(self._h, _dp(d), _ip(i), len(d)), "sa_hdp_state_pass_data")
         self.refresh()
 
     def pass_assignments(self, kmers, events):
         """(k-mers as a list of str or one concatenated str, event means): hdpHmm_loadFromFile's hand-over"""
         km = kmers if isinstance(kmers, str) else "".join(kmers)
-        e = np.ascontiguousarray(events, dtype=np.float64)
+        e = _f64(events)
         _chk(lib().sa_hdp_state_pass_assignments(self._h, km.encode(), _dp(e), len(e)), "sa_hdp_state_pass_assignments")
         self.refresh()
 
@@ -1728,17 +1657,6 @@ class HdpState:
 
     def samples_taken(self):
         return int(lib().sa_hdp_state_samples_taken(self._h))
-
-    def close(self):
-        if self._h:
-            lib().sa_hdp_state_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def write(self, path):
         _chk(lib().sa_hdp_state_write(self._h, os.fsencode(path)), "sa_hdp_state_write")
@@ -1765,11 +1683,7 @@ class HdpState:
         _chk(lib().sa_hdp_state_sample_weights(self._h, C.byref(rs), C.byref(col), C.byref(w), C.byref(nnz)),
              "sa_hdp_state_sample_weights")
         n = int(nnz.value)
-        out = (np.ctypeslib.as_array(rs, shape=(int(self.info.n_observed) + 1,)).copy(),
-               np.ctypeslib.as_array(col, shape=(max(n, 1),))[:n].copy(), np.ctypeslib.as_array(w, shape=(max(n, 1),))[:n].copy())
-        for q in (rs, col, w):
-            lib().sa_free(C.cast(q, C.c_void_p))
-        return out
+        return _copy_out(rs, int(self.info.n_observed) + 1, np.int64), _copy_out(col, n, np.int64), _copy_out(w, n, np.float64)
 
     def alphabet(self):
         buf = C.create_string_buffer(64)
@@ -1778,8 +1692,7 @@ class HdpState:
 
     def densities(self, dp_ids, x, device=0):
         """sa_hdp_state_densities: dir_proc_density of every DP id at every query point, len(dp_ids) x len(x) (GPU)"""
-        ids = np.ascontiguousarray(dp_ids, dtype=np.int64).ravel()
-        q = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        ids, q = _i64(dp_ids).ravel(), _f64(x).ravel()
         out = np.empty((len(ids), len(q)), dtype=np.float64)
         _chk(lib().sa_hdp_state_densities(self._h, _ip(ids), len(ids), _dp(q), len(q), device, _dp(out)), "sa_hdp_state_densities")
         return out
@@ -1790,13 +1703,12 @@ class HdpState:
         out = np.empty(max(n * (n - 1) // 2, 1), dtype=np.float64)
         ms = C.c_double(0.0)
         _chk(lib().sa_hdp_state_distances(self._h, int(metric), device, _dp(out), C.byref(ms)), "sa_hdp_state_distances")
-        if stats is not None:
-            stats["kernel_ms"] = ms.value
+        _timing(stats, ms)
         return out[:n * (n - 1) // 2]
 
     def distance_pairs(self, metric, dp1, dp2, device=0):
         """sa_hdp_state_distance_pairs: get_dir_proc_distance for pairs of DP ids (GPU)"""
-        a, b = np.ascontiguousarray(dp1, dtype=np.int64).ravel(), np.ascontiguousarray(dp2, dtype=np.int64).ravel()
+        a, b = _i64(dp1).ravel(), _i64(dp2).ravel()
         if len(a) != len(b):
             raise SaError(-1, "distance_pairs: as many first ids as second ids")
         out = np.empty(max(len(a), 1), dtype=np.float64)
@@ -1806,7 +1718,7 @@ class HdpState:
 
     def compare(self, other, dp1, dp2, metric, device=0):
         """sa_hdp_state_compare: compare_hdp_distrs, this state's grid is the master (GPU)"""
-        a, b = np.ascontiguousarray(dp1, dtype=np.int64).ravel(), np.ascontiguousarray(dp2, dtype=np.int64).ravel()
+        a, b = _i64(dp1).ravel(), _i64(dp2).ravel()
         if len(a) != len(b):
             raise SaError(-1, "compare: as many first ids as second ids")
         out = np.empty(max(len(a), 1), dtype=np.float64)
@@ -1816,16 +1728,14 @@ class HdpState:
     def vs_gaussian(self, dp_ids, mean, sd, device=0, stats=None):
         """sa_hdp_state_vs_gaussian: structured array (HDP_GAUSS_CMP_DTYPE), entry i the stored distribution of DP dp_ids[i]
         against the normal density (mean[i], sd[i]) on the state's grid (GPU).  stats (a dict): kernel_ms"""
-        ids = np.ascontiguousarray(dp_ids, dtype=np.int64).ravel()
-        m, s = np.ascontiguousarray(mean, dtype=np.float64).ravel(), np.ascontiguousarray(sd, dtype=np.float64).ravel()
+        ids, m, s = _i64(dp_ids).ravel(), _f64(mean).ravel(), _f64(sd).ravel()
         if not len(ids) == len(m) == len(s):
             raise SaError(-1, "vs_gaussian: one mean and one sd per DP id")
         out = np.zeros(max(len(ids), 1), dtype=HDP_GAUSS_CMP_DTYPE)
         ms = C.c_double(0.0)
         _chk(lib().sa_hdp_state_vs_gaussian(self._h, _ip(ids), len(ids), _dp(m), _dp(s), device, out.ctypes.data, C.byref(ms)),
              "sa_hdp_state_vs_gaussian")
-        if stats is not None:
-            stats["kernel_ms"] = ms.value
+        _timing(stats, ms)
         return out[:len(ids)]
 
     def distr_sample(self, device=0):
@@ -1837,37 +1747,33 @@ class HdpState:
 
 HDP_LAYOUT_FLAT, HDP_LAYOUT_MULTISET, HDP_LAYOUT_MIDDLE_NTS, HDP_LAYOUT_COMPOSITION, HDP_LAYOUT_GROUP_MULTISET = 0, 1, 2, 3, 4
 HDP_METRIC_KL, HDP_METRIC_HELLINGER, HDP_METRIC_L2, HDP_METRIC_SHANNON_JENSEN = 0, 1, 2, 3
-HDP_GAUSS_CMP_DTYPE = np.dtype([("kl_bits", "<f8"), ("hellinger", "<f8"), ("mode_delta", "<f8"), ("status", "<i4"), ("pad", "<i4")])
+HDP_GAUSS_CMP_DTYPE = _record_dtype("sa_hdp_gauss_cmp_t", [("kl_bits", "<f8"), ("hellinger", "<f8"), ("mode_delta", "<f8"), ("status", "<i4"), ("pad", "<i4")])
 
 
 def hdp_distances(grid, rows, metric, device=0, stats=None):
     """sa_hdp_distances: all pairs among the rows (n_rows x grid_length, one grid) -- the triangular vector, [(i - 1) * i / 2 + j]
     for i > j (GPU).  stats (a dict): kernel_ms"""
-    g = np.ascontiguousarray(grid, dtype=np.float64)
-    r = np.ascontiguousarray(rows, dtype=np.float64)
+    g, r = _f64(grid), _f64(rows)
     if r.ndim != 2 or g.ndim != 1 or r.shape[1] != len(g):
         raise SaError(-1, "hdp_distances: rows must be n_rows x len(grid)")
     n = r.shape[0]
     out = np.empty(max(n * (n - 1) // 2, 1), dtype=np.float64)
     ms = C.c_double(0.0)
     _chk(lib().sa_hdp_distances(_dp(g), len(g), _dp(r), n, int(metric), device, _dp(out), C.byref(ms)), "sa_hdp_distances")
-    if stats is not None:
-        stats["kernel_ms"] = ms.value
+    _timing(stats, ms)
     return out[:n * (n - 1) // 2]
 
 
 def hdp_distances_paired(grid, a, b, metric, device=0, stats=None):
     """sa_hdp_distances_paired: row i of a against row i of b (GPU)"""
-    g = np.ascontiguousarray(grid, dtype=np.float64)
-    pa, pb = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    g, pa, pb = _f64(grid), _f64(a), _f64(b)
     if pa.ndim != 2 or pa.shape != pb.shape or g.ndim != 1 or pa.shape[1] != len(g):
         raise SaError(-1, "hdp_distances_paired: a and b must both be n x len(grid)")
     out = np.empty(max(pa.shape[0], 1), dtype=np.float64)
     ms = C.c_double(0.0)
     _chk(lib().sa_hdp_distances_paired(_dp(g), len(g), _dp(pa), _dp(pb), pa.shape[0], int(metric), device, _dp(out), C.byref(ms)),
          "sa_hdp_distances_paired")
-    if stats is not None:
-        stats["kernel_ms"] = ms.value
+    _timing(stats, ms)
     return out[:pa.shape[0]]
 
 
@@ -1877,7 +1783,7 @@ def hdp_distances_release():
 
 def hdp_nig_params_from_table(table5):
     """sa_hdp_nig_params_from_table: (mu, nu, alpha, beta) by maximum likelihood from a lookup table (5 doubles per k-mer)"""
-    t = np.ascontiguousarray(table5, dtype=np.float64).reshape(-1)
+    t = _f64(table5).reshape(-1)
     out = [C.c_double() for _ in range(4)]
     _chk(lib().sa_hdp_nig_params_from_table(_dp(t), len(t) // 5, *[C.byref(o) for o in out]), "sa_hdp_nig_params_from_table")
     return tuple(o.value for o in out)
@@ -1885,8 +1791,8 @@ def hdp_nig_params_from_table(table5):
 
 def hdp_finalize_distributions(grid, collectors, samples, device=0):
     """sa_hdp_finalize_distributions: (collectors / samples, spline slopes), both n_rows x grid_length (GPU)"""
-    grid = np.ascontiguousarray(grid, dtype=np.float64)
-    s = np.ascontiguousarray(collectors, dtype=np.float64).reshape(-1, len(grid))
+    grid = _f64(grid)
+    s = _f64(collectors).reshape(-1, len(grid))
     y, k = np.zeros_like(s), np.zeros_like(s)
     _chk(lib().sa_hdp_finalize_distributions(_dp(grid), len(grid), _dp(s), s.shape[0], int(samples), device, _dp(y), _dp(k)),
          "sa_hdp_finalize_distributions")
@@ -1894,16 +1800,17 @@ def hdp_finalize_distributions(grid, collectors, samples, device=0):
 
 
 # ---- Gaussian k-mer emission training (sa_kmer_table_*, sa_model_write_trained) ----------------------------------------
-KMER_ROW_DTYPE = np.dtype([("descaled_units", "<i8"), ("run", "<i8"), ("kmer_id", "<i4"), ("prob_units", "<i4"),
+KMER_ROW_DTYPE = _record_dtype("sa_kmer_row_t", [("descaled_units", "<i8"), ("run", "<i8"), ("kmer_id", "<i4"), ("prob_units", "<i4"),
                            ("neg_zero", "<i4"), ("pad", "<i4")])
-KMER_STAT_DTYPE = np.dtype([("n", "<i8"), ("m", "<f8"), ("s", "<f8")])
-MIXTURE_FIT_DTYPE = np.dtype([("n", "<i8"), ("kmer_id", "<i4"), ("n_iter", "<i4"), ("converged", "<i4"), ("status", "<i4"),
+KMER_STAT_DTYPE = _record_dtype("sa_kmer_stat_t", [("n", "<i8"), ("m", "<f8"), ("s", "<f8")])
+MIXTURE_FIT_DTYPE = _record_dtype("sa_mixture_fit_t", [("n", "<i8"), ("kmer_id", "<i4"), ("n_iter", "<i4"), ("converged", "<i4"), ("status", "<i4"),
                               ("lower_bound", "<f8"), ("weight", "<f8", (4,)), ("mean", "<f8", (4,)), ("sd", "<f8", (4,))])
 
 
-class KmerTable:
+class KmerTable(_Handle):
     """sa_kmer_table_t: per strand (0 't', 1 'c') and path k-mer the max_per_kmer rows of largest printed posterior
     (>= min_prob), kept in HBM across add_batch / add_rows calls."""
+    _DESTROY = "sa_kmer_table_destroy"
 
     def __init__(self, model, max_per_kmer=10, min_prob=0.8, device=0):
         self._h = C.c_void_p()
@@ -1916,8 +1823,7 @@ class KmerTable:
         kms = C.c_double()
         _chk(lib().sa_kmer_table_add_batch(self._h, batch._h, batch._arr, batch.n_jobs, int(strand), C.byref(kms)),
              "sa_kmer_table_add_batch")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
+        _timing(stats, kms)
 
     def set_positions(self, sites):
         """sa_kmer_table_set_positions: from now on only rows that cover one of `sites` are offered.  sites: a TRAIN_SITE_DTYPE
@@ -1936,15 +1842,12 @@ class KmerTable:
         with the fields of sa_train_job_map_t (contig, x_sign, x0, site_strand)"""
         if isinstance(job_map, np.ndarray) and job_map.dtype == TRAIN_JOB_MAP_DTYPE:
             m = np.ascontiguousarray(job_map)
+            mp, n = m.ctypes.data, len(m)
         else:
-            job_map = list(job_map)
-            m = np.zeros(len(job_map), dtype=TRAIN_JOB_MAP_DTYPE)
-            for i, j in enumerate(job_map):
-                for f in ("contig", "x_sign", "x0", "site_strand"):
-                    m[i][f] = int(j[f])
+            mp, n = _records(TrainJobMap, job_map)
         kms = C.c_double()
-        _chk(lib().sa_kmer_table_add_batch_at(self._h, batch._h, batch._arr, len(m), int(strand), m.ctypes.data if len(m) else None,
-                                              C.byref(kms)), "sa_kmer_table_add_batch_at")
+        _chk(lib().sa_kmer_table_add_batch_at(self._h, batch._h, batch._arr, n, int(strand), mp if n else None, C.byref(kms)),
+             "sa_kmer_table_add_batch_at")
         if stats is not None:
             parts = np.zeros(2)
             _chk(lib().sa_kmer_table_add_at_times(self._h, _dp(parts)), "sa_kmer_table_add_at_times")
@@ -1955,32 +1858,19 @@ class KmerTable:
         sp, cp = C.c_void_p(), C.c_void_p()
         n = np.zeros(1, dtype=np.int64)
         _chk(lib().sa_kmer_table_position_counts(self._h, C.byref(sp), C.byref(cp), _ip(n)), "sa_kmer_table_position_counts")
-        sites, counts = np.zeros(int(n[0]), dtype=TRAIN_SITE_DTYPE), np.zeros(int(n[0]), dtype=np.int64)
-        if n[0]:
-            C.memmove(sites.ctypes.data, sp, sites.nbytes)
-            C.memmove(counts.ctypes.data, cp, counts.nbytes)
-        lib().sa_free(sp)
-        lib().sa_free(cp)
-        return sites, counts
+        return _copy_out(sp, int(n[0]), TRAIN_SITE_DTYPE), _copy_out(cp, int(n[0]), np.int64)
 
     def add_rows(self, kmer_ids, descaled, prob, strand=0):
-        k = np.ascontiguousarray(kmer_ids, dtype=np.int32)
-        d = np.ascontiguousarray(descaled, dtype=np.float64)
-        p = np.ascontiguousarray(prob, dtype=np.float64)
+        k, d, p = _i32(kmer_ids), _f64(descaled), _f64(prob)
         assert len(k) == len(d) == len(p)
-        _chk(lib().sa_kmer_table_add_rows(self._h, int(strand), k.ctypes.data_as(C.POINTER(C.c_int32)), _dp(d), _dp(p), len(k)),
-             "sa_kmer_table_add_rows")
+        _chk(lib().sa_kmer_table_add_rows(self._h, int(strand), _i32p(k), _dp(d), _dp(p), len(k)), "sa_kmer_table_add_rows")
 
     def rows(self, strand=0):
         """structured array (KMER_ROW_DTYPE): k-mer ascending, posterior descending, then run order"""
         ptr = C.c_void_p()
         n = np.zeros(1, dtype=np.int64)
         _chk(lib().sa_kmer_table_rows(self._h, int(strand), C.byref(ptr), _ip(n)), "sa_kmer_table_rows")
-        out = np.zeros(int(n[0]), dtype=KMER_ROW_DTYPE)
-        if n[0]:
-            C.memmove(out.ctypes.data, ptr, out.nbytes)
-        lib().sa_free(ptr)
-        return out
+        return _copy_out(ptr, int(n[0]), KMER_ROW_DTYPE)
 
     def write(self, path, strand=-1, append=False):
         _chk(lib().sa_kmer_table_write(self._h, int(strand), os.fsencode(path), int(bool(append))), "sa_kmer_table_write")
@@ -1999,16 +1889,15 @@ class KmerTable:
         kms = C.c_double()
         _chk(lib().sa_kmer_table_stats(self._h, int(strand), int(bool(use_median)), out.ctypes.data, C.byref(kms)),
              "sa_kmer_table_stats")
-        if info is not None:
-            info["kernel_ms"] = kms.value
+        _timing(info, kms)
         return out
 
     def _mixture_args(self, kmer_ids, n_components, max_iter, tol, reg_covar):
         alpha, k = self._model.alphabet()
-        ids = None if kmer_ids is None else np.ascontiguousarray(kmer_ids, dtype=np.int32)
+        ids = None if kmer_ids is None else _i32(kmer_ids)
         nj = len(alpha) ** k if ids is None else len(ids)
         p = MixtureParams(int(n_components), int(max_iter), float(tol), float(reg_covar))
-        return ids, nj, p, (None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)))
+        return ids, nj, p, (None if ids is None else _i32p(ids))
 
     def mixture(self, kmer_ids=None, n_components=2, strand=0, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, info=None):
         """sa_kmer_table_mixture: structured array (MIXTURE_FIT_DTYPE), one entry per k-mer id of `kmer_ids` (None: every
@@ -2017,13 +1906,12 @@ class KmerTable:
         out = np.zeros(nj, dtype=MIXTURE_FIT_DTYPE)
         ini = None
         if init is not None:
-            ini = np.ascontiguousarray(init, dtype=np.float64).reshape(-1)
+            ini = _f64(init).reshape(-1)
             assert len(ini) == nj * 3 * int(n_components)
         kms = C.c_double()
         _chk(lib().sa_kmer_table_mixture(self._h, int(strand), idp, nj, C.byref(p), None if ini is None else _dp(ini),
                                          out.ctypes.data, C.byref(kms)), "sa_kmer_table_mixture")
-        if info is not None:
-            info["kernel_ms"] = kms.value
+        _timing(info, kms)
         return out
 
     def mixture_start(self, kmer_ids=None, n_components=2, strand=0, reg_covar=1e-6):
@@ -2038,29 +1926,18 @@ class KmerTable:
         n_jobs x len(x), one row per k-mer id of `kmer_ids` (None: every k-mer of the model); -inf for a k-mer without rows.
         info (a dict): kernel_ms, n_rows (per job)"""
         alpha, k = self._model.alphabet()
-        ids = None if kmer_ids is None else np.ascontiguousarray(kmer_ids, dtype=np.int32).ravel()
+        ids = None if kmer_ids is None else _i32(kmer_ids).ravel()
         nj = len(alpha) ** k if ids is None else len(ids)
-        q = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        q = _f64(x).ravel()
         out = np.empty((nj, len(q)), dtype=np.float64)
         n_rows = np.zeros(max(nj, 1), dtype=np.int64)
         kms = C.c_double()
-        _chk(lib().sa_kmer_table_kde(self._h, int(strand), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), nj,
-                                     _dp(q), len(q), float(bandwidth), _dp(out), _ip(n_rows), C.byref(kms)), "sa_kmer_table_kde")
+        _chk(lib().sa_kmer_table_kde(self._h, int(strand), None if ids is None else _i32p(ids), nj, _dp(q), len(q), float(bandwidth),
+                                     _dp(out), _ip(n_rows), C.byref(kms)), "sa_kmer_table_kde")
+        _timing(info, kms)
         if info is not None:
-            info["kernel_ms"] = kms.value
             info["n_rows"] = n_rows[:nj]
         return out
-
-    def close(self):
-        if self._h:
-            lib().sa_kmer_table_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def model_write_trained(prior_path, stats, out_path, weight=100.0, min_sd=0.0, mod_only=False, kmer_mask=None):
@@ -2118,15 +1995,17 @@ def snp_write_read(path, fast5_input, read_id, contig, backward, sites):
                                  arr, len(sites)), "sa_snp_write_read")
 
 
-class _ContigAcc:
+class _ContigAcc(_Handle):
     """What the tables kept in HBM over contig positions share: the lengths, checkpoint / rollback / close by the prefix of the
     C functions' names (_PREFIX), and the two ends of finish."""
     _PREFIX = None
 
+    _DESTROY = property(lambda self: self._PREFIX + "destroy")
+
     def _create(self, contig_lens, create):
         """create(handle by reference, lengths, their number) is the table's own sa_*_create call"""
         self._h = C.c_void_p()
-        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        lens = _i64(contig_lens)
         self.n_contigs = len(lens)
         self.contig_lens = [int(v) for v in lens]
         _chk(create(C.byref(self._h), _ip(lens), len(lens)), self._PREFIX + "create")
@@ -2156,24 +2035,8 @@ class _ContigAcc:
         n = np.zeros(1, dtype=np.int64)
         kms = C.c_double()
         _chk(call(C.byref(ptr), _ip(n), C.byref(kms)), self._PREFIX + "finish")
-        out = np.zeros(int(n[0]), dtype=dtype)
-        if n[0]:
-            C.memmove(out.ctypes.data, ptr, out.nbytes)
-        lib().sa_free(ptr)
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
-        return out
-
-    def close(self):
-        if self._h:
-            getattr(lib(), self._PREFIX + "destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _timing(stats, kms)
+        return _copy_out(ptr, int(n[0]), dtype)
 
 
 class SnpMarginals(_ContigAcc):
@@ -2199,13 +2062,9 @@ class SnpMarginals(_ContigAcc):
     def add_batch(self, batch, job_map, stats=None):
         """chained onto a finished Batch created with FLAG_POSITION_CALLS; job_map: per job a dict with the fields of
         sa_snp_job_map_t (contig, pos0, pos_sign, x0, x_sign, strand, direction, run, group)"""
-        job_map = list(job_map)
-        arr = (SnpJobMap * max(len(job_map), 1))()
-        for i, m in enumerate(job_map):
-            for f in ("contig", "pos_sign", "pos0", "x0", "x_sign", "strand", "direction", "run", "group"):
-                setattr(arr[i], f, int(m[f]))
+        arr, n = _records(SnpJobMap, job_map)
         kms = (C.c_double * 2)()
-        _chk(lib().sa_snp_marginals_add_batch(self._h, batch._h, arr, len(job_map), kms), "sa_snp_marginals_add_batch")
+        _chk(lib().sa_snp_marginals_add_batch(self._h, batch._h, arr, n, kms), "sa_snp_marginals_add_batch")
         if stats is not None:
             stats["kernel_ms_position_fold"], stats["kernel_ms"] = kms[0], kms[1]
 
@@ -2225,36 +2084,23 @@ class PositionProfile(_ContigAcc):
         self.alphabet = model.alphabet()[0]
         self._create(contig_lens, lambda h, lens, n: lib().sa_position_profile_create(h, model._h, lens, n, int(device)))
 
-    @staticmethod
-    def _map(job_map):
-        job_map = list(job_map)
-        arr = (ProfileJobMap * max(len(job_map), 1))()
-        for i, m in enumerate(job_map):
-            arr[i].contig, arr[i].pos_sign, arr[i].pos0 = int(m["contig"]), int(m["pos_sign"]), int(m["pos0"])
-        return arr, len(job_map)
-
     def add_batch(self, batch, job_map, flags=0, stats=None):
         """chained onto a finished Batch; job_map: per job a dict with contig, pos0, pos_sign (sa_profile_job_map_t)"""
-        arr, n = self._map(job_map)
+        arr, n = _records(ProfileJobMap, job_map)
         kms = C.c_double()
         _chk(lib().sa_position_profile_add_batch(self._h, batch._h, arr, n, int(flags), C.byref(kms)), "sa_position_profile_add_batch")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
+        _timing(stats, kms)
 
     def add_records(self, job_map, first, x, kmer_id, prob_e7, flags=0, stats=None):
         """records from elsewhere: job j's are first[j] .. first[j + 1) of x, kmer_id, prob_e7"""
-        arr, n = self._map(job_map)
-        first = np.ascontiguousarray(first, dtype=np.int64)
-        x = np.ascontiguousarray(x, dtype=np.int32)
-        kmer_id = np.ascontiguousarray(kmer_id, dtype=np.int32)
-        prob_e7 = np.ascontiguousarray(prob_e7, dtype=np.int64)
+        arr, n = _records(ProfileJobMap, job_map)
+        first, x, kmer_id, prob_e7 = _i64(first), _i32(x), _i32(kmer_id), _i64(prob_e7)
         if len(first) != n + 1 or not (len(x) == len(kmer_id) == len(prob_e7)) or int(first[-1]) != len(x):
             raise ValueError("first: n_jobs + 1 offsets into x, kmer_id and prob_e7, which have one entry per record")
         kms = C.c_double()
         _chk(lib().sa_position_profile_add_records(self._h, arr, n, _ip(first), _i32p(x), _i32p(kmer_id), _ip(prob_e7), int(flags),
                                                    C.byref(kms)), "sa_position_profile_add_records")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
+        _timing(stats, kms)
 
     def finish(self, ref_by_contig=None, stats=None):
         """(structured array of PROFILE_SITE_DTYPE in (contig, position) order, letters_seen bit mask)"""
@@ -2284,14 +2130,14 @@ def sort_u64(keys, device=0, stats=None):
     out = np.empty_like(k)
     kms = C.c_double()
     _chk(lib().sa_sort_u64(k.ctypes.data, len(k), out.ctypes.data, int(device), C.byref(kms)), "sa_sort_u64")
-    if stats is not None:
-        stats["kernel_ms"] = kms.value
+    _timing(stats, kms)
     return out
 
 
-class CallScores:
+class CallScores(_Handle):
     """sa_call_scores_t: the scores of site calls against known truth, kept in HBM per (level, read strand, letter, class) across
     add_batch / add_records calls; finish gives AUC, confusion and curve counts per (level, strand group, letter)."""
+    _DESTROY = "sa_call_scores_destroy"
 
     def __init__(self, letters, truth=(), n_bins=1000, threshold=0.500000001, device=0):
         """truth: a TRUTH_SITE_DTYPE array, or an iterable of (contig index, position, mapped strand 0 '+' / 1 '-', change_to)"""
@@ -2310,23 +2156,18 @@ class CallScores:
     def add_batch(self, batch, job_map, stats=None):
         """chained onto a finished Batch created with FLAG_SITE_CALLS; job_map: per job a dict with the fields of sa_score_job_map_t
         (contig, x0, x_sign, strand, mapped_strand, true_letter)"""
-        job_map = list(job_map)
-        arr = (ScoreJobMap * max(len(job_map), 1))()
-        for i, m in enumerate(job_map):
-            for f in ("contig", "x_sign", "x0", "strand", "mapped_strand", "true_letter"):
-                setattr(arr[i], f, int(m[f]))
+        arr, n = _records(ScoreJobMap, job_map)
         kms = C.c_double()
-        _chk(lib().sa_call_scores_add_batch(self._h, batch._h, arr, len(job_map), C.byref(kms)), "sa_call_scores_add_batch")
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
+        _chk(lib().sa_call_scores_add_batch(self._h, batch._h, arr, n, C.byref(kms)), "sa_call_scores_add_batch")
+        _timing(stats, kms)
 
     def add_records(self, level, strand, prob, true_letter):
         """scores made elsewhere: prob n x len(letters), true_letter n indices into letters"""
-        prob = np.ascontiguousarray(prob, dtype=np.float64).reshape(-1, len(self.letters))
+        prob = _f64(prob).reshape(-1, len(self.letters))
         tl = np.ascontiguousarray(true_letter, dtype=np.int8)
         if len(tl) != len(prob):
             raise ValueError("one true letter per record")
-        _chk(lib().sa_call_scores_add_records(self._h, int(level), int(strand), _dp(prob), tl.ctypes.data_as(C.POINTER(C.c_int8)), len(tl)),
+        _chk(lib().sa_call_scores_add_records(self._h, int(level), int(strand), _dp(prob), tl.ctypes.data_as(_P(C.c_int8)), len(tl)),
              "sa_call_scores_add_records")
 
     def checkpoint(self):
@@ -2343,33 +2184,16 @@ class CallScores:
         kms = C.c_double()
         _chk(lib().sa_call_scores_finish(self._h, C.byref(rows_p), _ip(n), C.byref(curves_p), C.byref(counts), C.byref(kms)),
              "sa_call_scores_finish")
-        rows = np.zeros(int(n[0]), dtype=CALL_SCORE_ROW_DTYPE)
-        curves = np.zeros((int(n[0]), 2, self.n_bins + 1), dtype=np.int64)
-        if n[0]:
-            C.memmove(rows.ctypes.data, rows_p, rows.nbytes)
-            C.memmove(curves.ctypes.data, curves_p, curves.nbytes)
-        lib().sa_free(rows_p)
-        lib().sa_free(curves_p)
-        if stats is not None:
-            stats["kernel_ms"] = kms.value
+        rows = _copy_out(rows_p, int(n[0]), CALL_SCORE_ROW_DTYPE)
+        curves = _copy_out(curves_p, (int(n[0]), 2, self.n_bins + 1), np.int64)
+        _timing(stats, kms)
         return rows, curves, dict(unlabelled=int(counts.unlabelled), other_sites=int(counts.other_sites))
-
-    def close(self):
-        if self._h:
-            lib().sa_call_scores_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def call_scores_write(summary_path, curves_path, n_bins, rows, curves=None):
     """sa_call_scores_write: the summary and (curves_path not None) the curves of CallScores.finish"""
     r = np.ascontiguousarray(rows, dtype=CALL_SCORE_ROW_DTYPE)
-    c = np.ascontiguousarray(curves if curves is not None else np.zeros(0), dtype=np.int64)
+    c = _i64(curves if curves is not None else np.zeros(0))
     _chk(lib().sa_call_scores_write(os.fsencode(summary_path), os.fsencode(curves_path) if curves_path is not None else None, int(n_bins),
                                     r.ctypes.data, len(r), _ip(c)), "sa_call_scores_write")
 
@@ -2381,8 +2205,7 @@ def _deviation_call(jobs, mea, params, flags, call):
     arr = (DeviationJob * max(n, 1))()
     keep = []
     for i, j in enumerate(jobs):
-        ax = np.ascontiguousarray(j["ax"], dtype=np.int64)
-        ay = np.ascontiguousarray(j["ay"], dtype=np.int64)
+        ax, ay = _i64(j["ax"]), _i64(j["ay"])
         if len(ax) != len(ay):
             raise ValueError("a job's ax and ay have one entry per anchor")
         keep.append((ax, ay))
@@ -2395,7 +2218,7 @@ def _deviation_call(jobs, mea, params, flags, call):
         n_mea = np.zeros(max(n, 1), dtype=np.int64)
         for i, m in enumerate(mea):
             m = m[0] if isinstance(m, tuple) else m          # (Batch.mea() returns (path, sum, status) per job)
-            m = np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 2)
+            m = _i32(m).reshape(-1, 2)
             keep.append(m)
             paths[i], n_mea[i] = m.ctypes.data, len(m)
     p = None
@@ -2407,19 +2230,12 @@ def _deviation_call(jobs, mea, params, flags, call):
     total = np.zeros(max(nb, 1), dtype=np.int64)
     sets_p, ev_p, n_sets, kms = C.c_void_p(), C.c_void_p(), np.zeros(1, dtype=np.int64), C.c_double()
     tail = (C.byref(p) if p is not None else None, int(flags), reads.ctypes.data, C.byref(sets_p), _ip(n_sets),
-            hist.ctypes.data_as(C.POINTER(C.c_int32)), _ip(total), C.byref(ev_p) if flags & DEV_EVENTS else None, C.byref(kms))
+            _i32p(hist), _ip(total), C.byref(ev_p) if flags & DEV_EVENTS else None, C.byref(kms))
     call(arr, n, paths, _ip(n_mea) if n_mea is not None else None, tail)
-    sets = np.zeros(int(n_sets[0]), dtype=DEVIATION_SET_DTYPE)
-    if len(sets):
-        C.memmove(sets.ctypes.data, sets_p, sets.nbytes)
-    lib().sa_free(sets_p)
+    sets = _copy_out(sets_p, int(n_sets[0]), DEVIATION_SET_DTYPE)
     out = {"reads": reads, "sets": sets, "hist": hist, "total_hist": total, "kernel_ms": kms.value}
     if flags & DEV_EVENTS:
-        ev = np.zeros(sum(int(j["n_events"]) for j in jobs), dtype=DEVIATION_EVENT_DTYPE)
-        if len(ev):
-            C.memmove(ev.ctypes.data, ev_p, ev.nbytes)
-        lib().sa_free(ev_p)
-        out["events"] = ev
+        out["events"] = _copy_out(ev_p, sum(int(j["n_events"]) for j in jobs), DEVIATION_EVENT_DTYPE)
     return out
 
 
@@ -2439,10 +2255,7 @@ def batch_guide_deviation(batch, jobs, mea=None, params=None, flags=0):
 
 def guide_deviation_records(jobs, first, x, y, prob_e7, mea=None, params=None, device=0, flags=0):
     """sa_guide_deviation_records: the same from records the caller holds, job j's being first[j] .. first[j + 1) of x, y, prob_e7"""
-    first = np.ascontiguousarray(first, dtype=np.int64)
-    x = np.ascontiguousarray(x, dtype=np.int32)
-    y = np.ascontiguousarray(y, dtype=np.int32)
-    prob_e7 = np.ascontiguousarray(prob_e7, dtype=np.int64)
+    first, x, y, prob_e7 = _i64(first), _i32(x), _i32(y), _i64(prob_e7)
     if len(first) != len(jobs) + 1 or not (len(x) == len(y) == len(prob_e7)) or int(first[-1]) != len(x):
         raise ValueError("first: n_jobs + 1 offsets into x, y and prob_e7, which have one entry per record")
 
@@ -2458,8 +2271,7 @@ def guide_deviation_release():
 
 def snp_group_sites(pos, delta, window=6, keep_last=True):
     """sa_snp_group_sites (group_sites_in_window): the position of the largest delta of every group"""
-    p = np.ascontiguousarray(pos, dtype=np.int64)
-    d = np.ascontiguousarray(delta, dtype=np.float64)
+    p, d = _i64(pos), _f64(delta)
     assert len(p) == len(d)
     out = np.zeros(max(len(p), 1), dtype=np.int64)
     n = np.zeros(1, dtype=np.int64)
@@ -2470,7 +2282,7 @@ def snp_group_sites(pos, delta, window=6, keep_last=True):
 def snp_substitute_sites(ref, contig_pos_of_ref0, sites, reversed=False, letter="X"):
     """sa_snp_substitute_sites: `letter` at the listed contig positions (ascending) inside the window, the rest upper-cased"""
     b = ref.encode() if isinstance(ref, str) else bytes(ref)
-    s = np.ascontiguousarray(sites, dtype=np.int64)
+    s = _i64(sites)
     out = C.create_string_buffer(len(b) + 1)
     _chk(lib().sa_snp_substitute_sites(b, len(b), int(contig_pos_of_ref0), 1 if reversed else 0, _ip(s), len(s),
                                        letter.encode()[:1], out), "sa_snp_substitute_sites")
@@ -2508,10 +2320,9 @@ def f6_units(v):
 
 
 def f6_units_device(values, device=0):
-    v = np.ascontiguousarray(values, dtype=np.float64)
+    v = _f64(values)
     u = np.zeros(len(v), dtype=np.int64)
     z = np.zeros(len(v), dtype=np.int32)
     r = np.zeros(len(v), dtype=np.int32)
-    _chk(lib().sa_f6_units_device(_dp(v), len(v), _ip(u), z.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  r.ctypes.data_as(C.POINTER(C.c_int32)), int(device)), "sa_f6_units_device")
+    _chk(lib().sa_f6_units_device(_dp(v), len(v), _ip(u), _i32p(z), _i32p(r), int(device)), "sa_f6_units_device")
     return u, z, r

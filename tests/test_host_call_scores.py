@@ -1,7 +1,6 @@
 """Call scores, the host side (no GPU): the header, EXPORTS and the ctypes mirror agree; the restatement (call_scores_ref.py) gives
 hand-computed answers; sa_call_scores_write prints the restatement's text byte for byte; the device entry points refuse loudly."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -10,16 +9,16 @@ import pytest
 import signalalign_amd as sa
 from signalalign_amd import _capi
 
+from abi_header import header_text
+
 import call_scores_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sa_sort_u64", "sa_call_scores_create", "sa_call_scores_destroy", "sa_call_scores_add_batch", "sa_call_scores_add_records",
        "sa_call_scores_checkpoint", "sa_call_scores_rollback", "sa_call_scores_finish", "sa_call_scores_write"]
 
 
 def test_header_exports_and_ctypes_agree():
-    hdr = open(os.path.join(ROOT, "include", "signalalign_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header_text()
     declared = set(re.findall(r"\b(sa_(?:sort|call_scores)_[a-z0-9_]+)\s*\(", hdr))
     assert set(NEW) == declared
     assert declared <= set(_capi.EXPORTS)

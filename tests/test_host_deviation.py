@@ -2,21 +2,20 @@
 agree on the new names, every refused argument is refused before the device is looked for, and the restatement in deviation_ref.py
 gives a hand-worked answer."""
 import ctypes as C
-import os
 import re
 
 import signalalign_amd as sa
 from signalalign_amd import _capi
 
+from abi_header import header_text
+
 import deviation_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sa_batch_guide_deviation", "sa_guide_deviation_records", "sa_guide_deviation_release"]
 
 
 def test_header_exports_and_ctypes_agree():
-    hdr = open(os.path.join(ROOT, "include", "signalalign_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header_text()
     declared = set(re.findall(r"\b(sa_(?:batch_)?guide_deviation[a-z0-9_]*)\s*\(", hdr))
     assert set(NEW) == declared
     assert declared <= set(_capi.EXPORTS)

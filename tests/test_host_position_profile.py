@@ -2,7 +2,6 @@
 ctypes agree on the new names, the entropy term equals the formula, the writer equals the restatement in profile_ref.py byte for
 byte, the restatement gives a hand-computed answer, and without a GPU the accumulator refuses."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -11,17 +10,17 @@ import pytest
 import signalalign_amd as sa
 from signalalign_amd import _capi
 
+from abi_header import header_text
+
 import profile_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sa_position_profile_create", "sa_position_profile_destroy", "sa_position_profile_add_batch", "sa_position_profile_add_records",
        "sa_position_profile_checkpoint", "sa_position_profile_rollback", "sa_position_profile_finish", "sa_position_profile_write",
        "sa_profile_entropy_term"]
 
 
 def test_header_exports_and_ctypes_agree():
-    hdr = open(os.path.join(ROOT, "include", "signalalign_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header_text()
     declared = set(re.findall(r"\b(sa_(?:position_)?profile_[a-z0-9_]+)\s*\(", hdr))
     assert set(NEW) == declared
     assert declared <= set(_capi.EXPORTS)

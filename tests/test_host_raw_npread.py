@@ -12,6 +12,8 @@ import pytest
 import signalalign_amd as sa
 from signalalign_amd import _capi, rawio
 
+from abi_header import header_text
+
 import raw_npread_ref as N
 import sa_cases as cases
 from test_host_event_detect import DNA_MODEL, dna_sequence, fixture
@@ -21,7 +23,7 @@ NEW = ("sa_npread_from_raw_batch", "sa_raw_npread_free", "sa_raw_npread_write", 
 
 
 def test_header_exports_and_mirror_agree_on_the_new_symbols():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "signalalign_hip.h")).read(), flags=re.S)
+    hdr = header_text()
     L = sa.lib()
     for name in NEW:
         assert re.search(r"\b%s\(" % name, hdr) and name in _capi.EXPORTS and hasattr(L, name), name

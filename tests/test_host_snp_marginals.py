@@ -1,7 +1,6 @@
 """CPU checks of the host side of the marginals over reads (sa_snp_marginals_*, sa_snp_group_sites, sa_snp_substitute_sites,
 sa_snp_apply_calls, sa_snp_write_marginals): header, export list and ctypes agree on the new names, the helpers equal the
 restatement in snp_marginals_ref.py, and without a GPU the accumulator refuses."""
-import os
 import random
 import re
 
@@ -11,17 +10,17 @@ import pytest
 import signalalign_amd as sa
 from signalalign_amd import _capi
 
+from abi_header import header_text
+
 import snp_marginals_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sa_snp_marginals_create", "sa_snp_marginals_destroy", "sa_snp_marginals_add_sites", "sa_snp_marginals_add_batch",
        "sa_snp_marginals_checkpoint", "sa_snp_marginals_rollback", "sa_snp_marginals_finish", "sa_snp_group_sites",
        "sa_snp_substitute_sites", "sa_snp_apply_calls", "sa_snp_write_marginals"]
 
 
 def test_header_exports_and_ctypes_agree():
-    hdr = open(os.path.join(ROOT, "include", "signalalign_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header_text()
     declared = set(re.findall(r"\b(sa_snp_[a-z0-9_]+)\s*\(", hdr))
     assert set(NEW) <= declared
     assert declared <= set(_capi.EXPORTS)

@@ -11,6 +11,8 @@ import numpy as np
 import signalalign_amd as sa
 from signalalign_amd import _capi
 
+from abi_header import header_text
+
 import kmer_training_ref as kref
 import sa_cases as cases
 import train_positions_ref as ref
@@ -70,9 +72,7 @@ WIDTH = {"int32_t": 4, "int64_t": 8}
 
 
 def _header_struct(name):
-    hdr = open(os.path.join(ROOT, "include", "signalalign_hip.h")).read()
-    body = re.search(r"typedef struct \w+ \{([^}]*)\} %s;" % name, hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    body = re.search(r"typedef struct \w+ \{([^}]*)\} %s;" % name, header_text()).group(1)
     fields = []
     for typ, names in re.findall(r"(int32_t|int64_t)\s+([^;]+);", body):
         fields += [(n.strip(), WIDTH[typ]) for n in names.split(",")]
@@ -80,7 +80,7 @@ def _header_struct(name):
 
 
 def test_header_exports_and_ctypes_agree():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "signalalign_hip.h")).read(), flags=re.S)
+    hdr = header_text()
     L = sa.lib()
     for name in NEW:
         assert re.search(r"\bint %s\s*\(" % name, hdr), name
