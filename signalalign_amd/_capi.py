@@ -1015,7 +1015,7 @@ def plan_describe(model, params, job, ambig=None, flags=0):
     cap_rows = int(lx + nev + 8 * (arr[0].n_anchors + 4))
     regions = np.zeros(4 * (arr[0].n_anchors + 2), dtype=np.int64)
     rows = np.zeros(3 * cap_rows, dtype=np.int64)
-    segs = np.zeros(4 * (cap_rows // 100 + 16), dtype=np.int64)
+    segs = np.zeros(4 * (cap_rows + 16), dtype=np.int64)   # (one segment per diagonal at most)
     _chk(lib().sa_plan_describe(model._h, C.byref(params), arr, amb, flags, C.byref(info), _ip(regions),
                                 len(regions) // 4, _ip(rows), cap_rows, _ip(segs), len(segs) // 4), "sa_plan_describe")
     nrow = 0

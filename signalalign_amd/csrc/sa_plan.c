@@ -491,8 +491,11 @@ int sa_job_header_ok(const sa_job_t *jb) {
            (!jb->n_anchors || (jb->anchor_x && jb->anchor_y)) && jb->var > 0.0 &&
            !(jb->ends & ~(SA_JOB_LEFT_END_NOT_RAGGED | SA_JOB_RIGHT_END_NOT_RAGGED));
 }
+/* trace_back_diagonals = 0 is planned: the reference's `assert(traceBackDiagonals >= 1)` (:1460) guards nothing (a traceback from
+ * diagonal d then emits (to, d - 1], and min_diags >= 2 keeps that stretch non-empty), vanishes from its release build (NDEBUG) and
+ * the oracle computes the case; the other asserts keep `from > to`, without which the schedule does not advance. */
 int sa_params_plannable(const sa_params_t *p) {
-    return !(p->diagonal_expansion < 0 || p->diagonal_expansion % 2 != 0 || p->trace_back_diagonals < 1 ||
+    return !(p->diagonal_expansion < 0 || p->diagonal_expansion % 2 != 0 || p->trace_back_diagonals < 0 ||
              p->min_diags_between_trace_back < 2 || p->trace_back_diagonals + 1 >= p->min_diags_between_trace_back ||
              !(p->threshold >= 0.0 && p->threshold <= 1.0));
 }

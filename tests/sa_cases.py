@@ -60,6 +60,25 @@ def oracle_params(oracle, p):
                          p.split_matrix_bigger_than_this, 14)
 
 
+def check_plan_geometry(oracle, sa, model, k, p, job, tag=None, ambig=None, flags=0):
+    """The host planner's view of one job (sa.plan_describe) against the oracle: its regions are getSplitPoints' and every band row of
+    every region is band_construct's for the anchors of that region.  Returns what plan_describe returned."""
+    ax, ay = np.asarray(job["ax"], dtype=np.int64), np.asarray(job["ay"], dtype=np.int64)
+    lX, lY = len(job["ref"]) - (k - 1), len(job["events"])
+    rl, rr = job.get("ragged", (1, 1))
+    info, regions, rows, segs = sa.plan_describe(model, p, job, ambig=ambig, flags=flags)
+    exp_regions = oracle.split_points(ax, ay, lX, lY, p.split_matrix_bigger_than_this, rl, rr)
+    assert np.array_equal(regions, exp_regions), tag
+    off = 0
+    for r, (x1, y1, x2, y2) in enumerate(regions):
+        sel = (ax + ay >= x1 + y1) & (ax + ay < x2 + y2)
+        L, R = oracle.band(ax[sel] - x1, ay[sel] - y1, x2 - x1, y2 - y1, p.diagonal_expansion)
+        n = len(L)
+        assert np.array_equal(rows[off:off + n, 1], L) and np.array_equal(rows[off:off + n, 2], R), (tag, r)
+        off += n
+    return info, regions, rows, segs
+
+
 def npread_job(oracle, npread_name, model_path, reference=None):
     """A bundled .npRead aligned to `reference` (default: its own template read) with a single-M guide
     alignment: the substitution for BASELINE config 1 described in SURVEY.md section 8(c)."""

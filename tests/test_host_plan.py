@@ -313,16 +313,7 @@ def test_plan_geometry_random_anchor_sets(oracle):
         if p.trace_back_diagonals + 1 >= p.min_diags_between_trace_back:
             continue
         op = cases.oracle_params(oracle, p)
-        info, regions, rows, segs = sa.plan_describe(m, p, job)
-        exp_regions = oracle.split_points(ax, ay, lX, lY, p.split_matrix_bigger_than_this, 1, 1)
-        assert np.array_equal(regions, exp_regions), it
-        off = 0
-        for r, (x1, y1, x2, y2) in enumerate(regions):
-            sel = (ax + ay >= x1 + y1) & (ax + ay < x2 + y2)
-            L, R = oracle.band(ax[sel] - x1, ay[sel] - y1, x2 - x1, y2 - y1, p.diagonal_expansion)
-            n = len(L)
-            assert np.array_equal(rows[off:off + n, 1], L) and np.array_equal(rows[off:off + n, 2], R), (it, r)
-            off += n
+        info, regions, rows, segs = cases.check_plan_geometry(oracle, sa, m, k, p, job, tag=it)
         om.set_read_params(job["scale"], job["shift"], job["var"])
         _, st = oracle.align(om, job["ref"], job["events"], ax, ay, op, want_stats=True)
         assert info.cells_forward == st.cells_forward and info.cells_backward == st.cells_backward, it
