@@ -983,6 +983,101 @@ int sa_guide_deviation_records(const sa_deviation_job_t *jobs, int64_t n_jobs, c
                                sa_deviation_event_t **events_out, double *kernel_ms_out);
 void sa_guide_deviation_release(void); /* returns the scratch the two calls keep between calls */
 
+/* ---- Labelled signal: reference position, k-mer and posterior of every stretch of raw current ------------------------------------
+ * Replaces, over the records a batch leaves in HBM and the raw starts of a raw read (sa_raw_npread_t), what alignedsignal.py and
+ * mea_algorithm.py build per read from the tables embedded in a fast5: CreateLabels.add_mea_labels through
+ * match_events_with_signalalign, add_signal_align_predictions through create_label_from_events, fix_sa_reference_indexes,
+ * match_ref_position_with_raw_start_band and AlignedSignal.generate_label_mapping.  All coordinates are the job's own (sa_pair_t):
+ * x the k-mer index in the job's ref, y the event index.
+ *   reference_index  ref_first + ref_step * x + base_shift: the reference_index the TSV prints for x (affine, step +1 or -1), moved
+ *                    to the labelled base of the k-mer as fix_sa_reference_indexes does (base_shift)
+ *   prob_units       sa_printed_units(prob_e7): the posterior the TSV prints, in units of 1e-6
+ *   MEA set          SA_LABEL_MEA: one segment per pair of the job's MEA path, in path order (ascending y).  The record is the one at
+ *                    cell (x, y); of several records of the cell the one with the lowest prob_e7, among equals the earliest in
+ *                    sa_batch_pairs order (the row signalMachine's MEA output prints).  raw_start / raw_length are the job's at y.
+ *                    A pair whose cell holds no record yields no segment and is counted in mea_without_record.
+ *   full set         SA_LABEL_FULL: one segment per record, ordered by raw_start as np.sort(kind='mergesort') orders them:
+ *                    raw_start strictly increases with y, so by y, equal y in sa_batch_pairs order
+ *   bands            SA_LABEL_BANDS: one entry per x with a record, in ascending x: raw_start that of the smallest y among the
+ *                    records of x, raw_length = raw_start[y_max] - raw_start[y_min] + raw_length[y_max], n_records their number
+ *   per-sample map   SA_LABEL_SAMPLES (needs SA_LABEL_MEA): per sample t of the job the index i, within the job's MEA segments, of
+ *                    the segment with start_i <= t < start_(i+1) -- for the last segment start <= t < start + length -- and -1 for
+ *                    every other sample: a gap left by unmapped events belongs to the segment before it
+ *   per job          status 0, SA_LABEL_NO_RECORDS, or (with SA_LABEL_MEA) SA_LABEL_NO_PATH: the path is NULL or empty, the full
+ *                    set and the bands are still made, the MEA set is empty and every sample is -1.  Of each set the first entry
+ *                    in the call's back-to-back array and the count (sample_first / n_samples: the job's part of the map, also
+ *                    when it is not made).  Over the MEA segments: minus_strand = the first one's reference_index >= the last's
+ *                    (check_strand_mapping; 0 without segments); n_positions = 1 + the consecutive segments whose x differ (the
+ *                    distinct x of a monotone path); skipped_positions = the sum over consecutive segments of max(|dx| - 1, 0);
+ *                    stay_events = the consecutive segments with dx == 0; first_sample = the first segment's raw_start,
+ *                    end_sample = the last one's raw_start + raw_length, labelled_samples = their difference (the samples of the
+ *                    map that are not -1); all 0 without segments.
+ * Deliberate differences from the scripts: the bands are made for every position with a record (the script makes them for the
+ * positions of a variant table only); a tie of posteriors within a cell goes to the earliest record (the script keeps what its sort
+ * leaves); the k-mer is a kmer_id, spelled in full by the caller (the script's S5 field cuts a 6-mer to five letters).
+ * Everything is an integer, so the outputs do not depend on launch shape or order and compare exactly.
+ * All argument checks run before any device work, SA_EINVAL: a NULL array; n_events that differs from the batch's or lies outside
+ * [0, 2^28]; a raw_start that is negative or not strictly increasing; raw_length < 1; raw_start + raw_length > n_samples; ref_step
+ * other than +1 / -1; an MEA event or a record's y outside [0, n_events); an MEA path whose events do not strictly increase; an x
+ * outside [0, 2^28); a prob_e7 outside [0, 1e7]; SA_LABEL_SAMPLES without SA_LABEL_MEA; an unknown flag.  More than 2^31 - 1 samples,
+ * records, events or x slots (the sum over the jobs of x_max - x_min + 1, for the bands) in one call: SA_EUNSUPPORTED.  Without a GPU:
+ * SA_ENODEVICE. */
+#define SA_LABEL_NO_RECORDS 1
+#define SA_LABEL_NO_PATH 2
+#define SA_LABEL_MEA 1u
+#define SA_LABEL_FULL 2u
+#define SA_LABEL_BANDS 4u
+#define SA_LABEL_SAMPLES 8u
+#define SA_LABEL_TIMES 16u            /* a HIP event pair around every kernel: sa_signal_labels_last_kernel_ms (probes/signal_labels_rate.py) */
+#define SA_LABEL_SAMPLE_TILE 4096     /* samples of one read that a block of the per-sample fill writes */
+/* the kernels in launch order, as sa_signal_labels_last_kernel_ms numbers them */
+#define SA_LABEL_K_COUNT 0
+#define SA_LABEL_K_SCAN_EVENTS 1
+#define SA_LABEL_K_SCATTER 2
+#define SA_LABEL_K_ORDER 3
+#define SA_LABEL_K_FULL 4
+#define SA_LABEL_K_FIND 5
+#define SA_LABEL_K_SCAN_PATH 6
+#define SA_LABEL_K_BAND_ACC 7
+#define SA_LABEL_K_SCAN_BANDS 8
+#define SA_LABEL_K_JOB_SCAN 9
+#define SA_LABEL_K_MEA_EMIT 10
+#define SA_LABEL_K_BAND_EMIT 11
+#define SA_LABEL_K_READS 12
+#define SA_LABEL_K_FILL 13
+#define SA_LABEL_N_KERNELS 14
+typedef struct sa_label_job {
+    const int64_t *raw_start, *raw_length;  /* per event y of the job: the rows of sa_raw_npread_t */
+    int64_t n_events, n_samples;
+    int64_t ref_first; int32_t ref_step;    /* the reference_index the TSV prints for x: ref_first + ref_step * x */
+    int32_t base_shift;                     /* fix_sa_reference_indexes: added to every reference_index */
+} sa_label_job_t;
+typedef struct sa_label_segment { int64_t raw_start, raw_length, reference_index; int32_t x, y, kmer_id, prob_units; } sa_label_segment_t; /* 40 bytes */
+typedef struct sa_label_band { int64_t raw_start, raw_length, reference_index; int32_t x, n_records; } sa_label_band_t;                 /* 32 bytes */
+typedef struct sa_label_read { int32_t status, minus_strand; int64_t mea_first, n_mea, full_first, n_full, band_first, n_bands,
+                               sample_first, n_samples, mea_without_record, n_positions, skipped_positions, stay_events,
+                               labelled_samples, first_sample, end_sample; } sa_label_read_t;   /* 128 bytes */
+/* Outputs of both calls: reads_out[n_jobs]; with its flag *mea_out, *full_out, *bands_out (malloc'd, sa_free): all jobs' entries
+ * back to back, job j's n_mea / n_full / n_bands from mea_first / full_first / band_first on; with SA_LABEL_SAMPLES *samples_out
+ * (malloc'd, sa_free): all jobs' samples back to back, job j's n_samples from sample_first on.  Without its flag a pointer may be
+ * NULL and is not touched, and the set's counts are 0 (the full set's excepted: they are the job's records).  kernel_ms_out (may be
+ * NULL): the HIP-event time of the call's kernels.  mea_path / n_mea: per job its MEA path (sa_batch_mea's), or both NULL.
+ * Chained onto a finished batch: the records are read where the run left them (after sa_batch_release_device, and with
+ * SA_FLAG_EXACT, they go up again).  Not run, a SA_FLAG_PAIRS8 batch (no k-mer in the record) or a SA_FLAG_VC_ROWS batch (rows
+ * dropped): SA_ESTATE, as sa_batch_mea answers; n_jobs that is not the batch's: SA_EINVAL. */
+int sa_batch_signal_labels(sa_batch_t *b, const sa_label_job_t *jobs, int64_t n_jobs, const sa_mea_pair_t *const *mea_path,
+                           const int64_t *n_mea, unsigned flags, sa_label_read_t *reads_out, sa_label_segment_t **mea_out,
+                           sa_label_segment_t **full_out, sa_label_band_t **bands_out, int32_t **samples_out, double *kernel_ms_out);
+/* records from elsewhere: job j's are first[j] .. first[j + 1) (first[0] == 0) of x, y, kmer_id, prob_e7, in sa_batch_pairs order */
+int sa_signal_labels_records(const sa_label_job_t *jobs, int64_t n_jobs, const int64_t *first /* n_jobs + 1 */, const int32_t *x,
+                             const int32_t *y, const int32_t *kmer_id, const int64_t *prob_e7, const sa_mea_pair_t *const *mea_path,
+                             const int64_t *n_mea, int device, unsigned flags, sa_label_read_t *reads_out, sa_label_segment_t **mea_out,
+                             sa_label_segment_t **full_out, sa_label_band_t **bands_out, int32_t **samples_out, double *kernel_ms_out);
+void sa_signal_labels_release(void); /* returns the scratch the two calls keep between calls */
+/* The HIP-event time of each kernel of the process's last call with SA_LABEL_TIMES, out[SA_LABEL_K_*] (0 for a kernel that call did
+ * not launch); at most n entries are written; returns SA_LABEL_N_KERNELS. */
+int sa_signal_labels_last_kernel_ms(double *out, int32_t n);
+
 /* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
  * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
  * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output

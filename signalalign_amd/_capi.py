@@ -154,6 +154,27 @@ DEVIATION_SET_DTYPE = _record_dtype("sa_deviation_set_t", [
     ("first_event", "<i4"), ("last_event", "<i4"), ("count", "<i4"), ("peak", "<i4"), ("mea_peak", "<i4"), ("center_event", "<i4"),
     ("open_end", "<i4"), ("pad", "<i4")])
 DEVIATION_EVENT_DTYPE = _record_dtype("sa_deviation_event_t", [("best_x", "<i4"), ("guide", "<i4"), ("diff", "<i4"), ("flags", "<u4")])
+
+
+class LabelJob(_Struct):
+    _c_name_ = "sa_label_job_t"
+    _fields_ = [("raw_start", C.POINTER(C.c_int64)), ("raw_length", C.POINTER(C.c_int64)), ("n_events", C.c_int64), ("n_samples", C.c_int64),
+                ("ref_first", C.c_int64), ("ref_step", C.c_int32), ("base_shift", C.c_int32)]
+
+
+LABEL_NO_RECORDS, LABEL_NO_PATH = 1, 2
+LABEL_MEA, LABEL_FULL, LABEL_BANDS, LABEL_SAMPLES, LABEL_TIMES = 1, 2, 4, 8, 16
+LABEL_SAMPLE_TILE = 4096
+LABEL_KERNELS = ("count", "scan_events", "scatter", "order", "full", "find", "scan_path", "band_acc", "scan_bands", "job_scan", "mea_emit",
+                 "band_emit", "reads", "fill")     # SA_LABEL_K_*: the order of sa_signal_labels_last_kernel_ms
+LABEL_SEGMENT_DTYPE = _record_dtype("sa_label_segment_t", [
+    ("raw_start", "<i8"), ("raw_length", "<i8"), ("reference_index", "<i8"), ("x", "<i4"), ("y", "<i4"), ("kmer_id", "<i4"),
+    ("prob_units", "<i4")])
+LABEL_BAND_DTYPE = _record_dtype("sa_label_band_t", [
+    ("raw_start", "<i8"), ("raw_length", "<i8"), ("reference_index", "<i8"), ("x", "<i4"), ("n_records", "<i4")])
+LABEL_READ_DTYPE = _record_dtype("sa_label_read_t", [("status", "<i4"), ("minus_strand", "<i4")] + [(n, "<i8") for n in (
+    "mea_first", "n_mea", "full_first", "n_full", "band_first", "n_bands", "sample_first", "n_samples", "mea_without_record",
+    "n_positions", "skipped_positions", "stay_events", "labelled_samples", "first_sample", "end_sample")])
 PROFILE_SITE_DTYPE = _record_dtype("sa_profile_site_t", [
     ("pos", "<i8"), ("contig", "<i4"), ("read_count", "<i4"), ("kmer_count", "<i8"), ("entropy_units", "<i8"),
     ("units", "<i8", (SITE_MAX_LETTERS,)), ("entropy", "<f8"), ("prob", "<f8", (SITE_MAX_LETTERS,)), ("ref", "S1"), ("pad", "S1", (7,))])
@@ -426,6 +447,11 @@ SIGNATURES = {
     "sa_guide_deviation_records": (C.c_int, [_P(DeviationJob), C.c_int64, _pi64, _pi32, _pi32, _pi64, _pvp, _pi64,
                                              _P(DeviationParams), C.c_int, C.c_uint, _vp, _pvp, _pi64, _pi32, _pi64, _pvp, _pf64]),
     "sa_guide_deviation_release": (None, []),
+    "sa_batch_signal_labels": (C.c_int, [_vp, _P(LabelJob), C.c_int64, _pvp, _pi64, C.c_uint, _vp, _pvp, _pvp, _pvp, _pvp, _pf64]),
+    "sa_signal_labels_records": (C.c_int, [_P(LabelJob), C.c_int64, _pi64, _pi32, _pi32, _pi32, _pi64, _pvp, _pi64, C.c_int, C.c_uint,
+                                           _vp, _pvp, _pvp, _pvp, _pvp, _pf64]),
+    "sa_signal_labels_release": (None, []),
+    "sa_signal_labels_last_kernel_ms": (C.c_int, [_pf64, C.c_int32]),
     "sa_kmer_table_create": (C.c_int, [_pvp, _vp, C.c_int64, C.c_double, C.c_int]),
     "sa_kmer_table_destroy": (None, [_vp]),
     "sa_kmer_table_add_batch": (C.c_int, [_vp, _vp, _P(Job), C.c_int64, C.c_int, _pf64]),
@@ -2267,6 +2293,87 @@ def guide_deviation_records(jobs, first, x, y, prob_e7, mea=None, params=None, d
 
 def guide_deviation_release():
     lib().sa_guide_deviation_release()
+
+
+def _label_call(jobs, mea, flags, call):
+    """what batch_signal_labels and signal_labels_records share: the argument arrays, the call, the outputs per read"""
+    jobs = list(jobs)
+    n = len(jobs)
+    arr = (LabelJob * max(n, 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        rs, rl = _i64(j["raw_start"]), _i64(j["raw_length"])
+        if len(rs) != len(rl):
+            raise ValueError("a job's raw_start and raw_length have one entry per event")
+        keep.append((rs, rl))
+        arr[i] = LabelJob(_ip(rs), _ip(rl), int(j.get("n_events", len(rs))), int(j["n_samples"]), int(j.get("ref_first", 0)),
+                          int(j.get("ref_step", 1)), int(j.get("base_shift", 0)))
+    paths, n_mea = None, None
+    if mea is not None:
+        if len(mea) != n:
+            raise ValueError("mea: one path per job")
+        paths = (C.c_void_p * max(n, 1))()
+        n_mea = np.zeros(max(n, 1), dtype=np.int64)
+        for i, m in enumerate(mea):
+            m = m[0] if isinstance(m, tuple) else m          # (Batch.mea() returns (path, sum, status) per job)
+            if m is None:
+                continue                                     # a NULL path
+            m = _i32(m).reshape(-1, 2)
+            keep.append(m)
+            paths[i], n_mea[i] = m.ctypes.data, len(m)
+    flags = int(flags)
+    reads = np.zeros(n, dtype=LABEL_READ_DTYPE)
+    ptrs = [C.c_void_p() for _ in range(4)]
+    kms = C.c_double()
+    wanted = [bool(flags & f) for f in (LABEL_MEA, LABEL_FULL, LABEL_BANDS, LABEL_SAMPLES)]
+    tail = (flags, reads.ctypes.data) + tuple(C.byref(p) if w else None for p, w in zip(ptrs, wanted)) + (C.byref(kms),)
+    call(arr, n, paths, _ip(n_mea) if n_mea is not None else None, tail)
+
+    def total(first, count):
+        return int(reads[first][-1] + reads[count][-1]) if n else 0
+    out = {"reads": reads, "kernel_ms": kms.value}
+    sets = (("mea", "mea_first", "n_mea", LABEL_SEGMENT_DTYPE), ("full", "full_first", "n_full", LABEL_SEGMENT_DTYPE),
+            ("bands", "band_first", "n_bands", LABEL_BAND_DTYPE), ("samples", "sample_first", "n_samples", np.dtype(np.int32)))
+    for (name, first, count, dtype), p, w in zip(sets, ptrs, wanted):
+        if w:
+            flat = _copy_out(p, total(first, count), dtype)
+            out[name] = [flat[int(r[first]):int(r[first] + r[count])] for r in reads]
+    return out
+
+
+def batch_signal_labels(batch, jobs, mea=None, flags=LABEL_MEA):
+    """sa_batch_signal_labels, chained onto a finished Batch: the labelled signal of every read.  jobs: per job a dict with raw_start,
+    raw_length (per event), n_samples and, optionally, ref_first (0), ref_step (1), base_shift (0); mea: per job its MEA path ([n, 2]
+    of (x, y), Batch.mea()'s tuples, or None), or None.  Returns a dict: reads (LABEL_READ_DTYPE), kernel_ms and, per flag, mea and
+    full (per read LABEL_SEGMENT_DTYPE records), bands (LABEL_BAND_DTYPE) and samples (int32), each a list with one array per read."""
+    def call(arr, n, paths, n_mea, tail):
+        _chk(lib().sa_batch_signal_labels(batch._h, arr, n, paths, n_mea, *tail), "sa_batch_signal_labels")
+    return _label_call(jobs, mea, flags, call)
+
+
+def signal_labels_records(jobs, first, x, y, kmer_id, prob_e7, mea=None, device=0, flags=LABEL_MEA):
+    """sa_signal_labels_records: the same from records the caller holds, job j's being first[j] .. first[j + 1) of x, y, kmer_id and
+    prob_e7, in sa_batch_pairs order"""
+    first, x, y, kmer_id, prob_e7 = _i64(first), _i32(x), _i32(y), _i32(kmer_id), _i64(prob_e7)
+    if len(first) != len(jobs) + 1 or not (len(x) == len(y) == len(kmer_id) == len(prob_e7)) or int(first[-1]) != len(x):
+        raise ValueError("first: n_jobs + 1 offsets into x, y, kmer_id and prob_e7, which have one entry per record")
+
+    def call(arr, n, paths, n_mea, tail):
+        _chk(lib().sa_signal_labels_records(arr, n, _ip(first), _i32p(x), _i32p(y), _i32p(kmer_id), _ip(prob_e7), paths, n_mea,
+                                            int(device), *tail), "sa_signal_labels_records")
+    return _label_call(jobs, mea, flags, call)
+
+
+def signal_labels_release():
+    lib().sa_signal_labels_release()
+
+
+def signal_labels_last_kernel_ms():
+    """{kernel: HIP-event ms} of the process's last call with LABEL_TIMES"""
+    out = np.zeros(len(LABEL_KERNELS), dtype=np.float64)
+    n = lib().sa_signal_labels_last_kernel_ms(_dp(out), len(out))
+    assert n == len(LABEL_KERNELS)
+    return dict(zip(LABEL_KERNELS, out.tolist()))
 
 
 def snp_group_sites(pos, delta, window=6, keep_last=True):

@@ -102,7 +102,7 @@ static void usage(void) {
                     "                  magic; signalalign_amd/rawio.py writes one): events are detected, aligned to the sequence and mapped to\n"
                     "                  its bases on the GPU, which stands in for the .npRead of a 1D read.  DNA with a Gaussian -T model: not with\n"
                     "                  --twoD, -C, --rna or an .nhdp\n"
-                    "--npread-out <dir>: write <dir>/<label>.npRead for every raw read (usable with -q)\n"
+                    "--npread-out <dir>: write <dir>/<label>.npRead for every raw read (usable with -q); --signal-labels <dir>: write <dir>/<label>.labels.tsv for every raw read, made on the GPU: raw_start, raw_length, reference_index, posterior_probability, kmer per event on the MEA path (alignedsignal.py add_mea_labels); --signal-labels-kmer-index <n> (2): the labelled base of the k-mer; --signal-labels-full, -bands, -samples: also <label>.full.tsv (every row), .bands.tsv (reference_index, raw_start, raw_length, n_records per position), .samples.i64 (per raw sample the reference_index of its MEA segment or -1, little-endian int64).  Not with --twoD, -t/-c, --snp-step or --snp-sites\n"
                     "--raw-detector <w1,w2,t1,t2,peak>: the event detector's two window lengths, two thresholds and peak height\n"
                     "                  (default 3,6,1.4,9.0,0.2)\n");
     fprintf(stderr, "--guide-band <n>: band width of that alignment: 64, 128 (default), 192 or 256\n");
@@ -223,6 +223,7 @@ typedef struct {
     char *guide_window;   /* <contig>:<start>-<end>[:+|:-] instead of a cigar file: the guide alignment is computed (guide_stage) */
     int guide_locate;     /* neither a cigar file nor a window: locate_stage writes guide_window */
     int raw;              /* npread_path names a raw-read file (sa_rawread_is): raw_stage fills np */
+    int64_t *raw_start, *raw_length, n_raw_samples;   /* a raw read's events in samples, per template event (--signal-labels) */
     sa_cigar_t *pA;
     sa_npread_t *np;
     char *forward_seq, *backward_seq;
@@ -300,6 +301,9 @@ typedef struct {
     char *prof_path;                       /* --position-profile: the per-position profile of the run's template batches, on the GPU */
     char *dev_path, *dev_events_path;   /* --guide-deviation: every strand batch's deviation from its guide, written read by read */
     sa_deviation_params_t dev_params;
+    /* --signal-labels: every template batch's labelled signal (sa_batch_signal_labels), <dir>/<label>.labels.tsv and the files of the sub-options */
+    char *lab_dir;
+    int lab_full, lab_bands, lab_samples, lab_kmer_index, lab_kmer_index_set;
     char *model_path[2], *hdp_path[2], *ambig_path;   /* -T -C, -v -w, -a */
     char *fwd_ref, *bwd_ref;
     sa_params_t p;
@@ -421,6 +425,11 @@ typedef struct {
     int32_t *dev_hist;
     sa_deviation_event_t *dev_events;
     int64_t *dev_ev_first;
+    /* --signal-labels only: [job] records, and all jobs' MEA segments, full set, bands and per-sample maps back to back */
+    sa_label_read_t *lab_reads;
+    sa_label_segment_t *lab_mea, *lab_full;
+    sa_label_band_t *lab_bands;
+    int32_t *lab_samples;
 } strand_result_t;
 
 typedef struct {   /* what one strand's batch of a --snp-step / --snp-sites slice leaves, [read * N + step] each */
@@ -458,7 +467,7 @@ static void parse_options(run_t *R, int argc, char **argv) {
     read_t *one = &R->one;
     R->dev_params = (sa_deviation_params_t) {10, 5, 64};
     R->train_min_prob = 0.8; R->train_n = 10; R->train_weight = 100.0;   /* probability_threshold, number_of_kmer_assignments, og_model_weight (trainModels.py) */
-    R->batch_reads = 2048; R->constraint_trim = 14; R->guide_band = 128;
+    R->batch_reads = 2048; R->constraint_trim = 14; R->guide_band = 128; R->lab_kmer_index = 2;
     R->acc_bins = 1000; R->acc_threshold = 0.500000001;
     R->p = (sa_params_t) {.threshold = 0.01, .diagonal_expansion = 50, .trace_back_diagonals = 50, .min_diags_between_trace_back = 1000,
                           .split_matrix_bigger_than_this = (int64_t) 3000 * 3000};
@@ -483,7 +492,9 @@ static void parse_options(run_t *R, int argc, char **argv) {
         {"snp-reference-out", Y, 0, 1025}, {"position-profile", Y, 0, 1026},
         {"guide-deviation", Y, 0, 1060}, {"guide-deviation-threshold", Y, 0, 1061}, {"guide-deviation-events", Y, 0, 1062},
         {"guide-window", Y, 0, 1050}, {"guide-locate", N, 0, 1053}, {"guide-band", Y, 0, 1051}, {"guide-cigars-out", Y, 0, 1052},
-        {"npread-out", Y, 0, 1080}, {"raw-detector", Y, 0, 1081}, {0, 0, 0, 0}};
+        {"npread-out", Y, 0, 1080}, {"raw-detector", Y, 0, 1081},
+        {"signal-labels", Y, 0, 1090}, {"signal-labels-kmer-index", Y, 0, 1091}, {"signal-labels-full", N, 0, 1092},
+        {"signal-labels-bands", N, 0, 1093}, {"signal-labels-samples", N, 0, 1094}, {0, 0, 0, 0}};
     /* the options that name a file or another string, and the flags */
     const struct { int key; char **to; } strings[] = {
         {'a', &R->ambig_path}, {'T', &R->model_path[0]}, {'C', &R->model_path[1]}, {'L', &one->label}, {'q', &one->npread_path}, {'p', &one->cigar_path},
@@ -493,9 +504,10 @@ static void parse_options(run_t *R, int argc, char **argv) {
         {1012, &R->train_model[1]}, {1019, &R->train_kmers}, {1040, &R->mix_motifs}, {1041, &R->mix_model[0]}, {1042, &R->mix_model[1]},
         {1043, &R->mix_dist}, {1044, &R->train_pos}, {1045, &R->train_pos_cov}, {1021, &R->snp_dir}, {1022, &R->snp_marg}, {1023, &R->snp_prop}, {1024, &R->snp_sites_path}, {1025, &R->snp_ref_out},
         {1026, &R->prof_path}, {1060, &R->dev_path}, {1062, &R->dev_events_path}, {1050, &one->guide_window}, {1052, &R->guide_cigars_out},
-        {1080, &R->npread_out}};
+        {1080, &R->npread_out}, {1090, &R->lab_dir}};
     const struct { int key; int *flag; } flags[] = {{'e', &R->two_d}, {'r', &R->rna}, {'d', &R->hdp}, {1002, &R->mea}, {1005, &R->site_calls},
-                                                    {1017, &R->train_median}, {1018, &R->train_mod_only}, {1053, &one->guide_locate}};
+                                                    {1017, &R->train_median}, {1018, &R->train_mod_only}, {1053, &one->guide_locate},
+                                                    {1092, &R->lab_full}, {1093, &R->lab_bands}, {1094, &R->lab_samples}};
     for (;;) {
         int idx = 0, known = 0;
         int key = getopt_long(argc, argv, "h:d:e:s:r:o:a:T:C:a:L:q:f:b:g:i:p:u:v:w:t:c:x:D:m:n:", long_options, &idx);
@@ -524,6 +536,7 @@ static void parse_options(run_t *R, int argc, char **argv) {
                 break;
             case 1061: R->dev_params.threshold = atoi(optarg); break;
             case 1051: R->guide_band = atoi(optarg); break;
+            case 1091: R->lab_kmer_index = atoi(optarg); R->lab_kmer_index_set = 1; break;
             case 1081: {
                 sa_detector_params_t *d = &R->raw_detector;
                 char tail = 0;
@@ -635,7 +648,7 @@ static void check_reads(const run_t *R, read_t *reads, int64_t n_reads) {
 /* the modes against each other: what the options decide once the reads have said whether this is an expectations run */
 static void check_modes(const run_t *R, const read_t *reads, int64_t n_reads) {
     const int U = 1, expect = R->expect_mode, snp = R->snp_set || R->snp_sites_path != NULL, snp_any = snp || R->snp_dir != NULL;
-    const int calls = R->site_calls || R->want_agg, prof = R->prof_path != NULL, dev = R->dev_path != NULL;
+    const int calls = R->site_calls || R->want_agg, prof = R->prof_path != NULL, dev = R->dev_path != NULL, lab = R->lab_dir != NULL;
     const char *opt = R->snp_sites_path ? "--snp-sites" : "--snp-step";
     const refusal_t rows[] = {
         /* (the expectation pass keeps the reference-ordered kernels and the model's own noise; an HDP model has no such emission) */
@@ -674,6 +687,12 @@ static void check_modes(const run_t *R, const read_t *reads, int64_t n_reads) {
         {dev && expect, U, "signalMachine: --guide-deviation needs the alignment mode, not -t/-c%s", ""},
         {dev && R->want_train, U, "signalMachine: --guide-deviation cannot be combined with --train-*%s", ""},
         {dev && snp_any, U, "signalMachine: --guide-deviation cannot be combined with --snp-step / --snp-sites%s", ""},
+        /* --signal-labels: 1-D alignment runs of raw reads */
+        {!lab && (R->lab_full || R->lab_bands || R->lab_samples || R->lab_kmer_index_set), U, "signalMachine: --signal-labels-* need --signal-labels <dir>%s", ""},
+        {lab && R->two_d, U, "signalMachine: --signal-labels does not take --twoD runs%s", ""},
+        {lab && expect, U, "signalMachine: --signal-labels needs the alignment mode, not -t/-c%s", ""},
+        {lab && snp_any, U, "signalMachine: --signal-labels cannot be combined with --snp-step / --snp-sites%s", ""},
+        {lab && !R->batch_mode && !reads[0].raw, U, "signalMachine: --signal-labels needs a read given as raw current: an .npRead has no raw starts%s", ""},
         /* --snp-step / --snp-sites: their own outputs only */
         {snp_any && !R->snp_sites_path && (!R->snp_set || R->snp_step < 1), U, "signalMachine: --snp-step takes a step N >= 1%s", ""},
         {snp_any && !R->snp_dir && !R->snp_marg, U, "signalMachine: --snp-step needs --snp-dir <directory>%s", ""},
@@ -717,6 +736,11 @@ static void load_models(run_t *R) {
         mix_pair_t *probe = NULL;
         mixture_pairs(R, s, &probe);
         free(probe);
+    }
+    if (R->lab_dir && (R->lab_kmer_index < 0 || R->lab_kmer_index >= R->sm[0].k)) {
+        char k[16];
+        snprintf(k, sizeof(k), "%d", R->sm[0].k);
+        die("signalMachine: --signal-labels-kmer-index takes an index inside the model's k-mer: 0 <= n < %s", k);
     }
     if (!R->ambig_path) {
         sa_default_ambig(R->ambig);
@@ -764,6 +788,7 @@ int main(int argc, char **argv) {
     check_reads(&R, reads, n_reads);
     check_modes(&R, reads, n_reads);
     load_models(&R);
+    if (R.lab_dir && mkdir(R.lab_dir, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.lab_dir);
     if (R.snp_step > 0) {   /* a slice holds at most --batch-reads jobs: N per read and strand */
         R.batch_reads = R.batch_reads / R.snp_step < 1 ? 1 : R.batch_reads / R.snp_step;
         if (R.snp_dir && mkdir(R.snp_dir, 0777) != 0 && errno != EEXIST) die("signalMachine: cannot create %s", R.snp_dir);

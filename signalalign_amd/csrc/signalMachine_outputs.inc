@@ -804,6 +804,99 @@ static void dev_finish(output_t *o) {   /* the histogram summed over the reads w
     if (fclose(d->fh) != 0 || (d->events_fh && fclose(d->events_fh) != 0)) die("signalMachine: cannot write %s", o->R->dev_path);
 }
 
+/* ---- --signal-labels: the labelled signal of every raw read of a template batch (sa_batch_signal_labels), written read by read as
+ * the reads are rendered -- so a read the planner refused, whose slice started over, never has a file.  A read given as .npRead has
+ * no raw starts: its job goes into the call with one-sample events (the call wants every job of the batch) and nothing is written. ---- */
+static int lab_add_batch(output_t *o, slice_t *sl, int s, sa_batch_t *b) {
+    const run_t *R = o->R;
+    strand_result_t *sr = &sl->sr[s];
+    const int64_t n = sl->n_ok;
+    const int k = R->sm[s].k;
+    sa_label_job_t *lj = xalloc(n, sizeof(*lj), 1);
+    int64_t *plain = NULL, n_plain = 0;   /* 0, 1, 2, ...: the raw starts of the reads that have none */
+    for (int64_t j = 0; j < n; j++)
+        if (!sl->reads[sl->who[j]].raw_start && sl->jobs[s][j].n_events > n_plain) n_plain = sl->jobs[s][j].n_events;
+    if (n_plain > 0) {
+        plain = xalloc(2 * n_plain, sizeof(int64_t), 0);
+        for (int64_t y = 0; y < n_plain; y++) { plain[y] = y; plain[n_plain + y] = 1; }
+    }
+    for (int64_t j = 0; j < n; j++) {
+        const read_t *rd = &sl->reads[sl->who[j]];
+        const sa_job_t *q = &sl->jobs[s][j];
+        const int same = (s == 0 && rd->forward) || (s == 1 && !rd->forward);   /* adjust_ref: x + off, or off - k - x */
+        sa_label_job_t *l = &lj[j];
+        l->n_events = q->n_events;
+        l->ref_first = same ? rd->st[s].r_shift : rd->st[s].r_shift - k;
+        l->ref_step = same ? 1 : -1;
+        l->base_shift = same ? R->lab_kmer_index : (k - 1) - R->lab_kmer_index;
+        if (rd->raw_start) {
+            l->raw_start = rd->raw_start + rd->st[s].lo; l->raw_length = rd->raw_length + rd->st[s].lo; l->n_samples = rd->n_raw_samples;
+        } else {
+            l->raw_start = plain; l->raw_length = plain + n_plain; l->n_samples = q->n_events;
+        }
+    }
+    sr->lab_reads = xalloc(n, sizeof(sa_label_read_t), 1);
+    const unsigned flags = SA_LABEL_MEA | (R->lab_full ? SA_LABEL_FULL : 0u) | (R->lab_bands ? SA_LABEL_BANDS : 0u) | (R->lab_samples ? SA_LABEL_SAMPLES : 0u);
+    const int rc = sa_batch_signal_labels(b, lj, n, (const sa_mea_pair_t *const *) sr->mea, sr->n_mea, flags, sr->lab_reads, &sr->lab_mea,
+                                          R->lab_full ? &sr->lab_full : NULL, R->lab_bands ? &sr->lab_bands : NULL,
+                                          R->lab_samples ? &sr->lab_samples : NULL, NULL);
+    free(lj); free(plain);
+    if (rc != SA_OK) die_opt(o->opt, sa_strerror(rc));
+    return SA_OK;
+}
+static FILE *lab_file(const run_t *R, const read_t *rd, const char *suffix) {
+    char *path = xalloc((int64_t) (strlen(R->lab_dir) + strlen(rd->label) + strlen(suffix) + 4), 1, 0);
+    sprintf(path, "%s/%s.%s", R->lab_dir, rd->label, suffix);
+    FILE *fh = fopen(path, "w");
+    if (!fh) die("signalMachine: cannot open output %s", path);
+    free(path);
+    return fh;
+}
+/* raw_start raw_length reference_index posterior_probability kmer: the label dtype's fields in create_label_from_events' order, the
+ * posterior as "%f" prints it, the k-mer spelled in full */
+static void lab_write_segments(const run_t *R, const read_t *rd, const char *suffix, const sa_label_segment_t *seg, int64_t n) {
+    FILE *fh = lab_file(R, rd, suffix);
+    char kmer[16];
+    for (int64_t i = 0; i < n; i++) {
+        kmer_string(&R->sm[0], seg[i].kmer_id, kmer);
+        fprintf(fh, "%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%d.%06d\t%s\n", seg[i].raw_start, seg[i].raw_length, seg[i].reference_index,
+                seg[i].prob_units / 1000000, seg[i].prob_units % 1000000, kmer);
+    }
+    if (fclose(fh) != 0) die("signalMachine: cannot write the label files of %s", rd->label);
+}
+static void lab_add_read(output_t *o, slice_t *sl, int64_t j) {
+    const run_t *R = o->R;
+    const read_t *rd = &sl->reads[sl->who[j]];
+    const strand_result_t *sr = &sl->sr[0];
+    const sa_label_read_t *r = &sr->lab_reads[j];
+    if (!rd->raw_start) {
+        fprintf(stderr, "[signalMachine]NOTICE: %s is not given as raw current: no label files\n", rd->label);
+        return;
+    }
+    lab_write_segments(R, rd, "labels.tsv", sr->lab_mea + r->mea_first, r->n_mea);
+    if (R->lab_full) lab_write_segments(R, rd, "full.tsv", sr->lab_full + r->full_first, r->n_full);
+    if (R->lab_bands) {
+        FILE *fh = lab_file(R, rd, "bands.tsv");
+        for (int64_t i = 0; i < r->n_bands; i++) {
+            const sa_label_band_t *b = &sr->lab_bands[r->band_first + i];
+            fprintf(fh, "%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%d\n", b->reference_index, b->raw_start, b->raw_length, b->n_records);
+        }
+        if (fclose(fh) != 0) die("signalMachine: cannot write the label files of %s", rd->label);
+    }
+    if (R->lab_samples) {   /* the covering MEA segment's reference_index per raw sample, little-endian int64 */
+        FILE *fh = lab_file(R, rd, "samples.i64");
+        const int32_t *at = sr->lab_samples + r->sample_first;
+        const sa_label_segment_t *seg = sr->lab_mea + r->mea_first;
+        unsigned char *buf = xalloc(r->n_samples > 0 ? r->n_samples : 1, 8, 0);
+        for (int64_t t = 0; t < r->n_samples; t++) {
+            const uint64_t v = (uint64_t) (at[t] < 0 ? (int64_t) -1 : seg[at[t]].reference_index);
+            for (int q = 0; q < 8; q++) buf[8 * t + q] = (unsigned char) (v >> (8 * q));
+        }
+        if (fwrite(buf, 8, (size_t) r->n_samples, fh) != (size_t) r->n_samples || fclose(fh) != 0) die("signalMachine: cannot write the label files of %s", rd->label);
+        free(buf);
+    }
+}
+
 /* ---- --snp-marginals / --snp-proposals: the probabilities summed over all reads in one table on the GPU, laid over every record of -f ---- */
 typedef struct {
     output_t o;
@@ -956,6 +1049,7 @@ static void outputs_open(run_t *R) {
     if (acc) ((acc_t *) acc)->agg = (agg_t *) agg;
     output_new(R, R->want_train, sizeof(train_t), (output_t) {.opt = "--train-*", .open = train_open, .checkpoint = train_checkpoint, .rollback = train_rollback, .add_batch = train_add_batch, .finish = train_finish});
     output_new(R, R->dev_path != NULL, sizeof(deviation_t), (output_t) {.opt = "--guide-deviation", .open = dev_open, .add_batch = dev_add_batch, .add_read = dev_add_read, .finish = dev_finish});
+    output_new(R, R->lab_dir != NULL, sizeof(output_t), (output_t) {.opt = "--signal-labels", .add_batch = lab_add_batch, .add_read = lab_add_read});
     for (int i = 0; i < R->n_out; i++)
         if (R->out[i]->open) R->out[i]->open(R->out[i]);
 }

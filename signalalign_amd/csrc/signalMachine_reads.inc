@@ -276,6 +276,13 @@ static void raw_stage(const run_t *R, read_t *reads, int64_t n_reads) {
         np->template_events = xalloc(4 * o->n_events, sizeof(double), 0);
         memcpy(np->template_events, o->events4, sizeof(double) * 4 * (size_t) o->n_events);
         r->np = np;
+        if (R->lab_dir) {   /* --signal-labels: where every event lies in the raw current */
+            r->raw_start = xalloc(o->n_events, sizeof(int64_t), 0);
+            r->raw_length = xalloc(o->n_events, sizeof(int64_t), 0);
+            memcpy(r->raw_start, o->raw_start, sizeof(int64_t) * (size_t) o->n_events);
+            memcpy(r->raw_length, o->raw_length, sizeof(int64_t) * (size_t) o->n_events);
+            r->n_raw_samples = rr[q]->n_samples;
+        }
         fprintf(stderr, "[signalMachine]NOTICE: %s from raw current: %" PRId64 " samples, %" PRId64 " events on %" PRId64 " bases (shift %f, scale %f)\n",
                 r->label, rr[q]->n_samples, o->n_events, o->read_len, o->mom_shift, o->mom_scale);
     }
@@ -553,6 +560,8 @@ static void release_read(read_t *rd) {
     if (rd->pA) sa_cigar_free(rd->pA);
     if (rd->np) sa_npread_free(rd->np);
     free(rd->forward_seq); free(rd->backward_seq);
+    free(rd->raw_start); free(rd->raw_length);
+    rd->raw_start = rd->raw_length = NULL;
     for (int s = 0; s < 2; s++) { free(rd->ax[s]); free(rd->ay[s]); rd->ax[s] = rd->ay[s] = NULL; }
     for (int s = 0; s < 2; s++) { if (rd->model[s]) sa_model_destroy(rd->model[s]); rd->model[s] = NULL; }
     rd->pA = NULL; rd->np = NULL; rd->forward_seq = rd->backward_seq = NULL;
