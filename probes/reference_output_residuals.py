@@ -1,8 +1,9 @@
 """Where do the CPU restatement's posteriors differ from the ones the REFERENCE printed?  
 
 For the two reference output files pinned by tests/test_oracle_reference_outputs.py: every reference row (x, y, p) is located in
-THIS run's band (built from this run's anchors -- lastz's for the Zymo read, an alignment rebuilt from the rows for the E. coli
-read -- where the reference's came from bwa), its distance to the band's edge on its anti-diagonal and to the nearest anchor is
+THIS run's band (built from this run's anchors -- lastz's for the Zymo read, where the reference's came from bwa; bwa's own for the
+E. coli read, though at trace_back 100 where the file was written at 40: profiles/r04_reference_output_residuals.json was recorded
+with an alignment rebuilt from the rows, before tests/sa_cases.py took bwa's), its distance to the band's edge on its anti-diagonal and to the nearest anchor is
 taken, and |dp| is tabulated against that distance.  CPU only.  usage: python probes/reference_output_residuals.py"""
 import json
 import os
@@ -112,7 +113,7 @@ def ecoli():
     target = window[s1:e1]
     pairs = oracle.align(om, target, ev[lo:hi], ax, ay, oracle.Params(0.01, EXPANSION, 100, 1000, 3000 * 3000, 14))
     mine = {(int(q["x"]) + s1, int(q["y"]) + lo): int(q["prob_e7"]) / 1e7 for q in pairs}
-    return analyse("r9p4_oneD (1-D read; guide alignment rebuilt from the reference's own rows)", gold, mine, ax, ay,
+    return analyse("r9p4_oneD (1-D read; bwa's guide alignment, trace_back 100)", gold, mine, ax, ay,
                    len(target) - (k - 1), hi - lo, s1, lo)
 
 

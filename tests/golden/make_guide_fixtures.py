@@ -2,7 +2,9 @@
 tests/golden/npReads/r9p4_oneD.npRead, as the reference ships it (run in the build container, where /root/reference exists).  The
 fixture is data: the first record's FLAG, POS and CIGAR of tests/minion_test_reads/oneD_alignments.sam.  Its SEQ is the template
 read of the bundled .npRead (asserted here), and POS - 1 is the first position of the window that
-tests/golden/expected/reference_output_ecoli1d.npz holds."""
+tests/golden/expected/reference_output_ecoli1d.npz holds.  It is the alignment that file was written with (together with
+traceBackDiagonals = 40 and an A at the window's one unknown base): tests/sa_cases.py parses it -- leading S = read start 42, M/D/I =
+operations 0/1/2 -- and with it all of the file's rows are reproduced."""
 import json
 import os
 

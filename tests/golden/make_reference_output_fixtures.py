@@ -5,7 +5,11 @@ where /root/reference exists; the fixtures are data: positions, event indices, p
            = signalMachine's output for tests/test_npReads/ZymoC_ch_1_file1.npRead (2-D, R7.3, ZYMO contig)
   ecoli1d  tests/test_alignments/ecoli1D_test_alignments_sm3/6deaf971-...sm.forward.tsv
            = signalMachine's output for tests/test_npReads/r9p4_oneD.npRead (1-D, R9.4 5-mer ACEGT model, E. coli window).
-           The E. coli reference is a missing blob; the window the read aligns to is rebuilt from the rows' own k-mers.
+           The E. coli reference is a missing blob; the window the read aligns to is rebuilt from the rows' own k-mers.  One
+           base of it (index 6138) is covered by no row and stored as '?': it is an A (only A reproduces the rows).  The file was
+           written with bwa's guide alignment (tests/golden/cigars/r9p4_oneD_bwa.json) and traceBackDiagonals = 40
+           (impl/pairwiseAligner.c:2026); with both the restatement reproduces all 11,892 rows
+           (tests/test_oracle_reference_outputs.py).  Nothing here needs regenerating for that.
 """
 import os
 

@@ -1,5 +1,7 @@
 """Shared test inputs: the same seeded jobs are handed to the CPU oracle and to the HIP library."""
+import json
 import os
+import re
 
 import numpy as np
 
@@ -183,42 +185,83 @@ def write_npread_1d(path, read, event_map, events4):
         f.write("\n\n\n\n\n\n\n")
 
 
-def reference_output_ecoli1d_inputs(oracle):
+# What the reference ran with when it wrote the posteriors of its bundled reads (tests/golden/expected/reference_output_*.npz):
+# threshold, diagonal expansion, traceBackDiagonals, minDiagsBetweenTraceBack, splitMatrixBiggerThanThis, constraint trim.  The
+# traceback length is pairwiseAlignmentBandingParameters_construct's 40 (impl/pairwiseAligner.c:2026), not the 50 signalMachine's
+# -g defaults to nor the 100 the Python driver passes: only 40 reproduces the rows of the E. coli 1-D read (39 and 41 do not).
+REFERENCE_RUN = dict(threshold=0.01, expansion=50, trace_back=40, min_diags=1000, split=3000 * 3000, trim=14)
+ECOLI1D_MODEL = os.path.join(GOLDEN, "models", "testModelR9p4_5mer_acegt_template.model")
+
+
+def reference_run_params(oracle, trace_back=None):
+    """REFERENCE_RUN as the oracle's Params (trace_back: another traceback length, for the controls)"""
+    q = REFERENCE_RUN
+    return oracle.Params(q["threshold"], q["expansion"], q["trace_back"] if trace_back is None else trace_back, q["min_diags"],
+                         q["split"], q["trim"])
+
+
+def sam_cigar_operations(cigar):
+    """A SAM CIGAR as (read start, [(operation, length)]): leading S = the read's first aligned base, M/D/I = operations 0/1/2 of
+    sa_guide_to_anchors (D consumes reference, I consumes read), a trailing S is dropped."""
+    toks = re.findall(r"([0-9]+)([A-Z=])", cigar)
+    assert "".join(n + c for n, c in toks) == cigar and all(c in "SMDI" for _, c in toks), cigar
+    start = int(toks[0][0]) if toks[0][1] == "S" else 0
+    body = toks[1 if toks[0][1] == "S" else 0: len(toks) - (toks[-1][1] == "S")]
+    assert all(c != "S" for _, c in body)
+    return start, [({"M": 0, "D": 1, "I": 2}[c], int(n)) for n, c in body]
+
+
+def reference_output_ecoli1d_inputs(oracle, unknown="A"):
     """The reference's output for the bundled R9.4 1-D read (tests/golden/expected/reference_output_ecoli1d.npz) as an alignment
     job: (posteriors by (window position, event), reference window rebuilt from the rows' k-mers, parsed .npRead, (start1, end1,
-    start2, end2), guide-alignment operations).  The E. coli genome is a missing blob and the guide alignment bwa made is not
-    shipped: the operations are rebuilt from the rows themselves -- per reference position its most probable event (p >= 0.5)
-    mapped to a read base -- which is cruder than the original."""
+    start2, end2), guide-alignment operations).  The E. coli genome is a missing blob, so the window comes from the rows; the guide
+    alignment is the one the file was made with, bwa's (tests/golden/cigars/r9p4_oneD_bwa.json: 42S30M1D11M...2S at POS 3560629,
+    i.e. read 42-6540 on window 0-6817).  With it, REFERENCE_RUN and the two-distribution emission the CPU restatement gives the
+    file's 11,892 cells and no other, every posterior within the print precision (tests/test_oracle_reference_outputs.py).
+    unknown: the letter for the one window base no row covers (index 6138); only A reproduces the file."""
     z = np.load(os.path.join(GOLDEN, "expected", "reference_output_ecoli1d.npz"))
     gold = {(int(x), int(y)): float(p) for x, y, p in zip(z["x"], z["y"], z["p"])}
-    window = str(z["window"]).replace("?", "A")      # (one base no row covers)
+    assert str(z["window"]).count("?") == 1
+    window = str(z["window"]).replace("?", unknown)
     r = oracle.parse_npread(os.path.join(GOLDEN, "npReads", "r9p4_oneD.npRead"))
-    em = r["template_strand_event_map"]
-    best = {}
-    for (x, y), p in gold.items():
-        if p >= 0.5 and (x not in best or p > best[x][1]):
-            best[x] = (y, p)
-    m, last = [], -1
-    for x in sorted(best):
-        b = int(np.searchsorted(em, best[x][0], side="right") - 1)
-        if b > last:
-            m.append((x, b))
-            last = b
-    ops = []
+    bwa = json.load(open(os.path.join(GOLDEN, "cigars", "r9p4_oneD_bwa.json")))
+    assert bwa["flag"] == 0
+    s2, ops = sam_cigar_operations(bwa["cigar"])
+    s1 = bwa["pos"] - 1 - int(z["first_position"])
+    e1 = s1 + sum(n for t, n in ops if t != 2)
+    e2 = s2 + sum(n for t, n in ops if t != 1)
+    assert (s1, e1, s2, e2) == (0, len(window), 42, 6540) and e1 == 6817
+    return gold, window, r, (s1, e1, s2, e2), ops
 
-    def push(t, n):
-        if n > 0:
-            if ops and ops[-1][0] == t:
-                ops[-1] = (t, ops[-1][1] + n)
-            else:
-                ops.append((t, n))
-    for (x, b), (x2, b2) in zip(m[:-1], m[1:]):
-        mm = min(x2 - x, b2 - b)
-        push(0, mm)
-        push(1, x2 - x - mm)
-        push(2, b2 - b - mm)
-    push(0, 1)
-    return gold, window, r, (m[0][0], m[-1][0] + 1, m[0][1], m[-1][1] + 1), ops
+
+def against_reference_rows(mine, gold):
+    """A run's {(x, y): p} against the reference's: (rows of the reference that are missing, rows the reference has not, worst
+    |dp| over the common rows)."""
+    missing = sorted(set(gold) - set(mine))
+    extra = sorted(set(mine) - set(gold))
+    worst = max([abs(mine[k] - gold[k]) for k in set(mine) & set(gold)] + [0.0])
+    return missing, extra, worst
+
+
+# the reference prints six decimals (half a unit: 5e-7); prob_e7 carries the posterior in units of 1e-7
+PRINT_PRECISION = 5e-7 + 1e-7
+
+
+def check_reference_rows(mine, gold, kernel_error, tag):
+    """The bars of a run against the rows the reference printed.  kernel_error 0 (the restatement, the reference-ordered kernels):
+    the reference's set exactly, every posterior within the print precision.  kernel_error 1e-5 (the register kernels' contract):
+    every row of the reference present -- none of its posteriors is within 1e-5 of the threshold -- at most two rows it has not,
+    each below threshold + 1e-5 (the reference has three cells within 2.4e-5 under the threshold, two of them within 1e-5), and
+    every posterior within 1e-5 plus the print precision.  Prints and returns (missing, extra, worst |dp|)."""
+    missing, extra, worst = against_reference_rows(mine, gold)
+    print("%s against the reference's rows: %d rows, %d missing, %d extra, max |dp| %.3g" % (tag, len(mine), len(missing), len(extra), worst))
+    assert not missing, (tag, len(missing), missing[:5])
+    if kernel_error == 0:
+        assert not extra, (tag, len(extra), extra[:5])
+    else:
+        assert len(extra) <= 2 and all(mine[k] < REFERENCE_RUN["threshold"] + kernel_error for k in extra), (tag, [(k, mine[k]) for k in extra[:5]])
+    assert worst <= kernel_error + PRINT_PRECISION, (tag, worst)
+    return missing, extra, worst
 
 
 def reference_residual(mine, gold):
@@ -228,7 +271,7 @@ def reference_residual(mine, gold):
     that total on every tenth diagonal of a traceback, and its approximate logAdd makes the total depend on the diagonal it is
     evaluated on (un-banded restatement on the Zymo read: totals ten diagonals apart differ by 6e-5 in the median, 5e-4 at the
     95th percentile, 1.7e-3 at most); which diagonals those are depends on where the tracebacks fire, i.e. on the guide
-    alignment, which cannot be the reference's (bwa's is not shipped).  So the bar that the explanation supports is RELATIVE:
+    alignment, which for the Zymo read is lastz's and not the one the file was made with.  So the bar that the explanation supports is RELATIVE:
     |dp| <= 1.5e-3 p + 2e-6 (the print precision).  Returns (share of the reference's rows found, median |dp|, share of the found
     rows within that bar, share within 1e-4 absolute, the rows beyond the bar as (x + y, x, y, reference p, this run's p))."""
     common = sorted(set(mine) & set(gold))
