@@ -1078,6 +1078,97 @@ void sa_signal_labels_release(void); /* returns the scratch the two calls keep b
  * not launch); at most n entries are written; returns SA_LABEL_N_KERNELS. */
 int sa_signal_labels_last_kernel_ms(double *out, int32_t n);
 
+/* ---- Call quality: call accuracy against the alignment's distance from its guide, and the breaks of the MEA path -------------------
+ * Replaces visualization/plot_accuracy_vs_alignment_deviation.py (get_distance_from_guide_alignment, alignedsignal.py:388-425, over
+ * match_ref_position_with_raw_start_band, :428-443, then true_false = data[label] > threshold) and
+ * visualization/plot_breaks_in_alignments.py (find_gaps_in_alignment_data, :139-148, len(mea_data), percent_correct), from what a
+ * finished SA_FLAG_SITE_CALLS batch leaves in HBM.  All of it in the job's own coordinates (sa_pair_t): x the k-mer index in the
+ * job's ref, y the event index, the job's anchors the guide.  Everything is an integer but the one comparison of a probability.
+ *   calls         the sites of the batch's site fold, labelled exactly as sa_call_scores_add_batch labels them, with the letters,
+ *                 the threshold and the positions table of the sa_call_scores_t handed in and one sa_score_job_map_t per job
+ *                 (true_letter >= 0 labels the whole read, -1 looks (contig, x0 + x_sign * x, mapped_strand) up).  A site with a
+ *                 non-zero total whose kind has other letters counts in n_other_sites, one the table does not name in n_unlabelled;
+ *                 neither goes further.  correct = prob[true_letter] > threshold (strict)
+ *   band          SA_LABEL_BANDS' rule: over the records with the call's x, y_min and y_max; raw_start = raw_start[y_min],
+ *                 raw_length = raw_start[y_max] - raw_start[y_min] + raw_length[y_max]; mid2 = 2 * raw_start + raw_length, twice the
+ *                 script's v_position_middle
+ *   guide row     the anchor with anchor_x == x (of several the first for x_sign +1, the last for -1: the one the script's walk in
+ *                 ascending reference_index meets first); else for x_sign +1 the last anchor with anchor_x < x, for x_sign -1 the
+ *                 first anchor with anchor_x > x.  A call is OUTSIDE the guide when that row does not exist (the script's iloc[-1]
+ *                 wraps to the last row) or when no anchor has a reference_index at or beyond the call's (the script leaves NaN): it
+ *                 counts in n_outside, has guide_event -1 and delta2 0, enters no histogram and no sum, and is still a call with its
+ *                 correct flag.  Every call of a job without anchors is outside
+ *   delta2        mid2 - 2 * guide_mid, twice the script's guide_delta; guide_mid = np.round(raw_start[ay] + raw_length[ay] / 2) in
+ *                 integers: raw_start + raw_length / 2 for an even raw_length, else the even one of the two neighbours
+ *   histogram     bin = floor((delta2 - 2 * bin_lo) / (2 * bin_width)) (a floor, not C's truncation); slot 0 is underflow
+ *                 (delta2 < 2 * bin_lo), slot n_bins + 1 overflow, slot bin + 1 otherwise; hist[slot * 2 + correct], once per inside
+ *                 call: (n_bins + 2) * 2 counts per job and summed over the call
+ *   gaps          over consecutive pairs i - 1, i of the job's MEA path (ascending event order):
+ *                 gap = raw_start[y_i] - (raw_start[y_(i-1)] + raw_length[y_(i-1)]), reported when gap > min_gap (strict)
+ *   per job       status, bits: SA_CQ_NO_GUIDE (no anchors), SA_CQ_NO_SITES (no site with a non-zero total), SA_CQ_NO_PATH (the path
+ *                 is NULL or empty).  n_calls counts the labelled calls, inside or outside.  sum_abs_delta2 and max_abs_delta2 are
+ *                 over the inside calls; max_x is the smallest x that attains the maximum, -1 without an inside call.  The script's
+ *                 accuracy and gap ratio are one division each, left to the caller: n_correct / n_calls, n_gaps / n_path
+ * Deliberate differences from the scripts: every call finds its guide row on its own (the script advances one guide row per call, so
+ * of two calls that share a gap between guide rows the second is measured against a later row); outside calls are named, not wrapped
+ * or NaN; the accuracy-against-delta curve of 20 linspace bins is not made, the fixed-grid histogram of correct and wrong calls
+ * carries it; sites are looked up in a positions table (the script labels a whole sample); the band is over the records of x (the
+ * script makes it over the variant-caller rows of the position).
+ * All argument checks run before any device work, SA_EINVAL: a NULL array; n_jobs that is not the batch's; n_events that differs
+ * from the batch's or lies outside [0, 2^28]; a raw_start that is negative or not strictly increasing; raw_length < 1; anchors whose
+ * anchor_y do not strictly increase or whose anchor_x decrease, an anchor_x outside [0, 2^28), an anchor_y outside [0, n_events); an
+ * MEA event outside [0, n_events) or a path whose events do not strictly increase; bin_width < 1, bin_lo or bin_width beyond 2^40 in
+ * magnitude, n_bins outside [1, SA_CQ_MAX_BINS], min_gap < 0; a map entry sa_call_scores_add_batch refuses; another device than the
+ * accumulator's; an unknown flag.  sa_call_quality_records only: site_x not strictly ascending within a job or outside [0, 2^28); a
+ * site_prob that is NaN or outside [0, 1]; a record's x outside [0, 2^28) or y outside [0, n_events); a site with no record of its
+ * x.  A batch not run or created without SA_FLAG_SITE_CALLS: SA_ESTATE.  More than 2^31 - 1 sites, records, events or path pairs in
+ * one call, or a raw_start + raw_length beyond 2^31 - 1: SA_EUNSUPPORTED.  Without a GPU: SA_ENODEVICE. */
+#define SA_CQ_NO_GUIDE 1
+#define SA_CQ_NO_SITES 2
+#define SA_CQ_NO_PATH 4
+#define SA_CQ_CALLS 1u          /* *calls_out: one sa_callq_call_t per labelled call */
+#define SA_CQ_BAND_DIRECT 2u    /* every record is a global atomic pair into its site's y_min / y_max: no window in LDS.  The A/B of the
+                                 * default, which first combines the records of a tile per site in LDS and won beyond the spread of
+                                 * three calls on a site batch of 28 records per site (profiles/call_quality.json); same bytes */
+#define SA_CQ_MAX_BINS 1024
+typedef struct sa_callq_params { int64_t bin_lo, bin_width; int32_t n_bins, min_gap; } sa_callq_params_t;  /* NULL: {-10000, 100, 200, 30} */
+typedef struct sa_callq_job { const int64_t *anchor_x, *anchor_y; int64_t n_anchors;
+                              const int64_t *raw_start, *raw_length; int64_t n_events; } sa_callq_job_t;
+typedef struct sa_callq_read { int32_t status, max_x; int64_t n_calls, n_correct, n_unlabelled, n_other_sites, n_outside, sum_abs_delta2,
+                               max_abs_delta2, n_path, n_gaps, sum_gap, max_gap, call_first, gap_first; } sa_callq_read_t;   /* 112 bytes */
+typedef struct sa_callq_call { int64_t raw_start, raw_length, delta2; double prob_true;   /* the band; prob_true the double the site fold holds */
+                               int32_t x, guide_event, true_letter, correct, outside, pad; } sa_callq_call_t;               /* 56 bytes */
+typedef struct sa_callq_gap  { int32_t y_before, y_after; int64_t gap; } sa_callq_gap_t;
+/* Outputs of both calls: reads_out[n_jobs]; with SA_CQ_CALLS *calls_out (malloc'd, sa_free) all jobs' calls back to back, job j's
+ * n_calls from call_first on in ascending x, *n_calls_out of them (without the flag both may be NULL and are not touched, and
+ * call_first is 0); *gaps_out (malloc'd, sa_free) all jobs' gaps back to back in path order, job j's n_gaps from gap_first on,
+ * *n_gaps_out of them; hist_out[n_jobs * (n_bins + 2) * 2] (may be NULL) and total_hist_out[(n_bins + 2) * 2] (the sum of the rows,
+ * may be NULL); kernel_ms_out (may be NULL) the HIP-event time of the call's kernels, the site fold's among them.  mea_path / n_mea:
+ * per job its MEA path (sa_batch_mea's; a job's may be NULL with n_mea 0), or both NULL.
+ * `s` is only read -- its letters, threshold, positions table and device: nothing is appended to it, and sa_call_scores_finish
+ * afterwards gives the rows it would have given.  Chained onto a finished batch the call runs the site fold itself, as
+ * sa_call_scores_add_batch does, and reads the records where the run left them (after sa_batch_release_device, and with
+ * SA_FLAG_EXACT, they go up again); jobs[j] carries the batch's own anchors and n_events and the raw read's starts and lengths. */
+int sa_batch_call_quality(sa_call_scores_t *s, sa_batch_t *b, const sa_score_job_map_t *map, const sa_callq_job_t *jobs, int64_t n_jobs,
+                          const sa_mea_pair_t *const *mea_path, const int64_t *n_mea, const sa_callq_params_t *p, unsigned flags,
+                          sa_callq_read_t *reads_out, sa_callq_call_t **calls_out, int64_t *n_calls_out, sa_callq_gap_t **gaps_out,
+                          int64_t *n_gaps_out, int64_t *hist_out, int64_t *total_hist_out, double *kernel_ms_out);
+/* sites and records from elsewhere: job j's sites are site_first[j] .. site_first[j + 1) (site_first[0] == 0) of site_x, ascending,
+ * with site_prob[i * n_letters + l] for letter l of the accumulator's letters; site_other (may be NULL) marks with a non-zero byte
+ * the sites of other letters; job j's records are rec_first[j] .. rec_first[j + 1) of rec_x, rec_y.  Every site counts as one with a
+ * non-zero total. */
+int sa_call_quality_records(sa_call_scores_t *s, const sa_score_job_map_t *map, const sa_callq_job_t *jobs, int64_t n_jobs,
+                            const int64_t *site_first /* n_jobs + 1 */, const int32_t *site_x, const double *site_prob,
+                            const uint8_t *site_other, const int64_t *rec_first /* n_jobs + 1 */, const int32_t *rec_x,
+                            const int32_t *rec_y, const sa_mea_pair_t *const *mea_path, const int64_t *n_mea, const sa_callq_params_t *p,
+                            unsigned flags, sa_callq_read_t *reads_out, sa_callq_call_t **calls_out, int64_t *n_calls_out,
+                            sa_callq_gap_t **gaps_out, int64_t *n_gaps_out, int64_t *hist_out, int64_t *total_hist_out,
+                            double *kernel_ms_out);
+void sa_call_quality_release(void); /* returns the scratch the two calls keep between calls */
+/* The HIP-event time of the process's last call's kernels: out[0] k_cq_band, [1] k_cq_calls (both passes), [2] k_cq_gaps (both
+ * passes) and the scans; at most n entries are written; returns 3. */
+int sa_call_quality_last_kernel_ms(double *out, int32_t n);
+
 /* ---- Gaussian k-mer emission training (trainModels.train_normal_emmissions, src/signalalign/train/trainModels.py:735-828)
  * A k-mer table keeps, per strand (0 = template 't', 1 = complement 'c') and path k-mer (kmer_id), the `max_per_kmer` rows of
  * largest printed posterior among the rows whose printed posterior is >= min_prob -- generate_top_n_kmers_from_sa_output

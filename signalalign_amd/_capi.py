@@ -175,6 +175,30 @@ LABEL_BAND_DTYPE = _record_dtype("sa_label_band_t", [
 LABEL_READ_DTYPE = _record_dtype("sa_label_read_t", [("status", "<i4"), ("minus_strand", "<i4")] + [(n, "<i8") for n in (
     "mea_first", "n_mea", "full_first", "n_full", "band_first", "n_bands", "sample_first", "n_samples", "mea_without_record",
     "n_positions", "skipped_positions", "stay_events", "labelled_samples", "first_sample", "end_sample")])
+
+
+class CallqParams(_Struct):
+    _c_name_ = "sa_callq_params_t"
+    _fields_ = [("bin_lo", C.c_int64), ("bin_width", C.c_int64), ("n_bins", C.c_int32), ("min_gap", C.c_int32)]
+
+
+class CallqJob(_Struct):
+    _c_name_ = "sa_callq_job_t"
+    _fields_ = [("anchor_x", C.POINTER(C.c_int64)), ("anchor_y", C.POINTER(C.c_int64)), ("n_anchors", C.c_int64),
+                ("raw_start", C.POINTER(C.c_int64)), ("raw_length", C.POINTER(C.c_int64)), ("n_events", C.c_int64)]
+
+
+CQ_NO_GUIDE, CQ_NO_SITES, CQ_NO_PATH = 1, 2, 4
+CQ_CALLS, CQ_BAND_DIRECT = 1, 2
+CQ_MAX_BINS = 1024
+CQ_KERNELS = ("band", "calls", "gaps")     # the order of sa_call_quality_last_kernel_ms
+CALLQ_READ_DTYPE = _record_dtype("sa_callq_read_t", [("status", "<i4"), ("max_x", "<i4")] + [(n, "<i8") for n in (
+    "n_calls", "n_correct", "n_unlabelled", "n_other_sites", "n_outside", "sum_abs_delta2", "max_abs_delta2", "n_path", "n_gaps",
+    "sum_gap", "max_gap", "call_first", "gap_first")])
+CALLQ_CALL_DTYPE = _record_dtype("sa_callq_call_t", [
+    ("raw_start", "<i8"), ("raw_length", "<i8"), ("delta2", "<i8"), ("prob_true", "<f8"), ("x", "<i4"), ("guide_event", "<i4"),
+    ("true_letter", "<i4"), ("correct", "<i4"), ("outside", "<i4"), ("pad", "<i4")])
+CALLQ_GAP_DTYPE = _record_dtype("sa_callq_gap_t", [("y_before", "<i4"), ("y_after", "<i4"), ("gap", "<i8")])
 PROFILE_SITE_DTYPE = _record_dtype("sa_profile_site_t", [
     ("pos", "<i8"), ("contig", "<i4"), ("read_count", "<i4"), ("kmer_count", "<i8"), ("entropy_units", "<i8"),
     ("units", "<i8", (SITE_MAX_LETTERS,)), ("entropy", "<f8"), ("prob", "<f8", (SITE_MAX_LETTERS,)), ("ref", "S1"), ("pad", "S1", (7,))])
@@ -452,6 +476,13 @@ SIGNATURES = {
                                            _vp, _pvp, _pvp, _pvp, _pvp, _pf64]),
     "sa_signal_labels_release": (None, []),
     "sa_signal_labels_last_kernel_ms": (C.c_int, [_pf64, C.c_int32]),
+    "sa_batch_call_quality": (C.c_int, [_vp, _vp, _P(ScoreJobMap), _P(CallqJob), C.c_int64, _pvp, _pi64, _P(CallqParams), C.c_uint, _vp,
+                                        _pvp, _pi64, _pvp, _pi64, _pi64, _pi64, _pf64]),
+    "sa_call_quality_records": (C.c_int, [_vp, _P(ScoreJobMap), _P(CallqJob), C.c_int64, _pi64, _pi32, _pf64, _P(C.c_uint8), _pi64, _pi32,
+                                          _pi32, _pvp, _pi64, _P(CallqParams), C.c_uint, _vp, _pvp, _pi64, _pvp, _pi64, _pi64, _pi64,
+                                          _pf64]),
+    "sa_call_quality_release": (None, []),
+    "sa_call_quality_last_kernel_ms": (C.c_int, [_pf64, C.c_int32]),
     "sa_kmer_table_create": (C.c_int, [_pvp, _vp, C.c_int64, C.c_double, C.c_int]),
     "sa_kmer_table_destroy": (None, [_vp]),
     "sa_kmer_table_add_batch": (C.c_int, [_vp, _vp, _P(Job), C.c_int64, C.c_int, _pf64]),
@@ -2374,6 +2405,103 @@ def signal_labels_last_kernel_ms():
     n = lib().sa_signal_labels_last_kernel_ms(_dp(out), len(out))
     assert n == len(LABEL_KERNELS)
     return dict(zip(LABEL_KERNELS, out.tolist()))
+
+
+def _callq_call(scores, job_map, jobs, mea, params, flags, hist, call):
+    """what batch_call_quality and call_quality_records share: the argument arrays, the call, the outputs as a dict"""
+    jobs = list(jobs)
+    n = len(jobs)
+    marr, nm = _records(ScoreJobMap, job_map)
+    if nm != n:
+        raise ValueError("job_map: one entry per job")
+    arr = (CallqJob * max(n, 1))()
+    keep = []
+    for i, j in enumerate(jobs):
+        ax, ay, rs, rl = _i64(j["ax"]), _i64(j["ay"]), _i64(j["raw_start"]), _i64(j["raw_length"])
+        if len(ax) != len(ay) or len(rs) != len(rl):
+            raise ValueError("a job's ax and ay have one entry per anchor, its raw_start and raw_length one per event")
+        keep.append((ax, ay, rs, rl))
+        arr[i] = CallqJob(_ip(ax), _ip(ay), len(ax), _ip(rs), _ip(rl), int(j.get("n_events", len(rs))))
+    paths, n_mea = None, None
+    if mea is not None:
+        if len(mea) != n:
+            raise ValueError("mea: one path per job")
+        paths = (C.c_void_p * max(n, 1))()
+        n_mea = np.zeros(max(n, 1), dtype=np.int64)
+        for i, m in enumerate(mea):
+            m = m[0] if isinstance(m, tuple) else m          # (Batch.mea() returns (path, sum, status) per job)
+            if m is None:
+                continue                                     # a NULL path
+            m = _i32(m).reshape(-1, 2)
+            keep.append(m)
+            paths[i], n_mea[i] = m.ctypes.data, len(m)
+    p = None
+    if params is not None:
+        p = params if isinstance(params, CallqParams) else CallqParams(*[int(v) for v in params])
+    nb = p.n_bins if p is not None else 200
+    slots = max(nb, 1) + 2
+    flags = int(flags)
+    reads = np.zeros(n, dtype=CALLQ_READ_DTYPE)
+    per_job = np.zeros((n, slots, 2), dtype=np.int64) if hist else None
+    total = np.zeros((slots, 2), dtype=np.int64)
+    calls_p, gaps_p, n_calls, n_gaps, kms = C.c_void_p(), C.c_void_p(), np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64), C.c_double()
+    want = bool(flags & CQ_CALLS)
+    tail = (paths, _ip(n_mea) if n_mea is not None else None, C.byref(p) if p is not None else None, flags, reads.ctypes.data,
+            C.byref(calls_p) if want else None, _ip(n_calls) if want else None, C.byref(gaps_p), _ip(n_gaps),
+            _ip(per_job) if hist else None, _ip(total), C.byref(kms))
+    call(scores._h, marr, arr, n, tail)
+    out = {"reads": reads, "gaps": _copy_out(gaps_p, int(n_gaps[0]), CALLQ_GAP_DTYPE), "total_hist": total, "kernel_ms": kms.value}
+    if hist:
+        out["hist"] = per_job
+    if want:
+        out["calls"] = _copy_out(calls_p, int(n_calls[0]), CALLQ_CALL_DTYPE)
+    return out
+
+
+def batch_call_quality(scores, batch, job_map, jobs, mea=None, params=None, flags=0, hist=True):
+    """sa_batch_call_quality, chained onto a finished Batch created with FLAG_SITE_CALLS: every labelled site call against the
+    distance of its band from the guide, and the breaks of the MEA paths.  scores: a CallScores (only read: its letters, threshold
+    and positions table); job_map: per job the fields of sa_score_job_map_t, as CallScores.add_batch takes them; jobs: per job a
+    dict with ax, ay (the job's anchors) and raw_start, raw_length (per event); mea: per job its MEA path ([n, 2] of (x, y),
+    Batch.mea()'s tuples, or None), or None; params: (bin_lo, bin_width, n_bins, min_gap), None for (-10000, 100, 200, 30).
+    Returns a dict: reads (CALLQ_READ_DTYPE), gaps (CALLQ_GAP_DTYPE, job j's at reads["gap_first"][j]), total_hist
+    [n_bins + 2, 2] (wrong, correct), kernel_ms, with hist the per-job hist [n_jobs, n_bins + 2, 2] and, with CQ_CALLS, calls
+    (CALLQ_CALL_DTYPE, job j's at reads["call_first"][j])."""
+    def call(s, marr, arr, n, tail):
+        _chk(lib().sa_batch_call_quality(s, batch._h, marr, arr, n, *tail), "sa_batch_call_quality")
+    return _callq_call(scores, job_map, jobs, mea, params, flags, hist, call)
+
+
+def call_quality_records(scores, job_map, jobs, site_first, site_x, site_prob, rec_first, rec_x, rec_y, site_other=None, mea=None,
+                         params=None, flags=0, hist=True):
+    """sa_call_quality_records: the same from sites and records the caller holds -- job j's sites site_first[j] .. site_first[j + 1)
+    of site_x (ascending) with site_prob [n_sites, len(letters)] and, optionally, site_other (non-zero: a site of other letters),
+    its records rec_first[j] .. rec_first[j + 1) of rec_x, rec_y"""
+    site_first, site_x, rec_first, rec_x, rec_y = _i64(site_first), _i32(site_x), _i64(rec_first), _i32(rec_x), _i32(rec_y)
+    site_prob = _f64(site_prob).reshape(-1, len(scores.letters))
+    other = None if site_other is None else np.ascontiguousarray(site_other, dtype=np.uint8)
+    if (len(site_first) != len(jobs) + 1 or len(rec_first) != len(jobs) + 1 or int(site_first[-1]) != len(site_x) or
+            len(site_prob) != len(site_x) or (other is not None and len(other) != len(site_x)) or len(rec_x) != len(rec_y) or
+            int(rec_first[-1]) != len(rec_x)):
+        raise ValueError("site_first and rec_first: n_jobs + 1 offsets into the per-site and the per-record arrays")
+
+    def call(s, marr, arr, n, tail):
+        _chk(lib().sa_call_quality_records(s, marr, arr, n, _ip(site_first), _i32p(site_x), _dp(site_prob),
+                                           other.ctypes.data_as(_P(C.c_uint8)) if other is not None else None, _ip(rec_first),
+                                           _i32p(rec_x), _i32p(rec_y), *tail), "sa_call_quality_records")
+    return _callq_call(scores, job_map, jobs, mea, params, flags, hist, call)
+
+
+def call_quality_release():
+    lib().sa_call_quality_release()
+
+
+def call_quality_last_kernel_ms():
+    """{kernel: HIP-event ms} of the process's last call-quality call"""
+    out = np.zeros(len(CQ_KERNELS), dtype=np.float64)
+    n = lib().sa_call_quality_last_kernel_ms(_dp(out), len(out))
+    assert n == len(CQ_KERNELS)
+    return dict(zip(CQ_KERNELS, out.tolist()))
 
 
 def snp_group_sites(pos, delta, window=6, keep_last=True):

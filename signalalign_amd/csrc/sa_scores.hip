@@ -7,8 +7,8 @@
 //
 // Kernels of an add chained onto a batch, after the fold that sa_batch_site_calls shares (SaSiteFold):
 //   k_score_sites   one wave per job, 64 sites at a time: a site with a non-zero total and the accumulator's letters gets its true
-//                   letter (the job's label, or a binary search of the sorted positions table); per (letter, class) the lanes
-//                   that append are counted by ballot, ONE integer atomic moves the array's cursor for all of them, and each
+//                   letter (the job's label, or a binary search of the sorted positions table: sc_site_label, sa_site_label.h,
+//                   which sa_callq.hip shares); per (letter, class) the lanes that append are counted by ballot, ONE integer atomic moves the array's cursor for all of them, and each
 //                   writes its key at the cursor plus its rank.  The order inside an array is whatever the atomics hand out:
 //                   finish sorts, so nothing reported depends on it
 //   k_score_reads   one lane per (job with a label, letter): the site probabilities added serially in the reference's order, the
@@ -37,42 +37,13 @@
 #include "sa_internal.h"
 #include "sa_chain.h"
 #include "sa_sort.h"
+#include "sa_site_label.h"
 
 #define SC_LEVELS 3
 #define SC_MAX_ADD (1ll << 30)
 #define SC_MAX_ARRAY ((long long) INT32_MAX)
-#define SC_MAX_CONTIG (1ll << 21)
-#define SC_MAX_POS (1ll << 41)
-
-struct ScArray {
-    unsigned long long *d = nullptr;
-    size_t n = 0, cap = 0;
-};
-
-struct ScJob {   // sa_score_job_map_t as the device reads it
-    long long x0;
-    int contig, x_sign, strand, mapped, true_letter, ascending;   // ascending: the read-level sum walks the job's sites in ascending x
-};
-
-struct sa_call_scores {
-    std::mutex mu;
-    int device = -1, nl = 0, n_bins = 0;
-    double threshold = 0.0;
-    char letters[SA_SITE_MAX_LETTERS + 1] = {0};
-    std::vector<ScArray> arr;                 // index sc_array(level, strand, letter, cls)
-    std::vector<size_t> ck_n;
-    sa_call_scores_counts_t counts = {0, 0}, ck_counts = {0, 0};
-    bool has_ck = false, poisoned = false;
-    char *d_truth = nullptr;                  // [keys | letters], sorted by key
-    size_t n_truth = 0, o_tlet = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-
 __host__ __device__ static inline int sc_array(int nl, int level, int strand, int letter, int cls) {
     return ((level * 2 + strand) * nl + letter) * 2 + cls;   // cls 1: positive
-}
-__host__ __device__ static inline unsigned long long sc_truth_key(long long contig, long long pos, int mapped) {
-    return ((unsigned long long) contig << 42) | ((unsigned long long) pos << 1) | (unsigned long long) mapped;
 }
 // a score's key: its bit pattern, -0.0 as +0.0
 __device__ static inline unsigned long long sc_key_dev(double v) { return v == 0.0 ? 0ull : (unsigned long long) __double_as_longlong(v); }
@@ -82,34 +53,14 @@ static inline unsigned long long sc_key_host(double v) {
     return u;
 }
 
-// the first index of a[0 .. n) whose entry is >= key (upper: > key)
-template <bool UPPER>
-__device__ __forceinline__ unsigned long long sc_bound(const unsigned long long *__restrict__ a, unsigned long long n, unsigned long long key) {
-    unsigned long long lo = 0, hi = n;
-    while (lo < hi) {
-        const unsigned long long mid = lo + ((hi - lo) >> 1);
-        const unsigned long long v = a[mid];
-        if (UPPER ? v <= key : v < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 struct ScDev {   // what the appending kernels share
     unsigned long long *const *ptr;    // per array
     const unsigned *cap;               // per array: entries it has room for
     unsigned *cur;                     // per array: entries it holds
     unsigned long long *misc;          // [0] unlabelled calls, [1] sites of other letters
-    const unsigned long long *tkey;    // the positions table
-    const signed char *tlet;
-    unsigned long long n_truth;
+    ScTruth T;                         // the positions table
     int nl;
 };
-
-__device__ __forceinline__ bool sc_site_live(const unsigned long long *__restrict__ units, long long s, int stride) {
-    unsigned long long tot = 0;
-    for (int l = 0; l < stride; l++) tot += units[(size_t) s * (size_t) stride + (size_t) l];   // (the entries past a kind's letters are 0)
-    return tot != 0;
-}
 
 __global__ __launch_bounds__(64) void k_score_sites(const ScJob *__restrict__ jobs, const long long *__restrict__ site_off,
                                                     const unsigned char *__restrict__ kind, const unsigned char *__restrict__ kind_ok,
@@ -121,23 +72,11 @@ __global__ __launch_bounds__(64) void k_score_sites(const ScJob *__restrict__ jo
     unsigned long long n_unl = 0, n_oth = 0;
     for (long long base = s0; base < s1; base += 64) {
         const long long s = base + lane;
-        const bool live = s < s1 && sc_site_live(units, s, stride);
-        const bool ok = live && kind_ok[kind[s]];
-        int tl = -1;
-        if (ok) {
-            tl = J.true_letter;
-            if (tl < 0) {
-                const long long r = J.x0 + (long long) J.x_sign * x_of_site[s];
-                if (r >= 0 && r < SC_MAX_POS) {
-                    const unsigned long long key = sc_truth_key(J.contig, r, J.mapped);
-                    const unsigned long long at = sc_bound<false>(D.tkey, D.n_truth, key);
-                    if (at < D.n_truth && D.tkey[at] == key) tl = D.tlet[at];
-                }
-            }
-        }
-        n_oth += (unsigned long long) __popcll(__ballot(live && !ok));
-        n_unl += (unsigned long long) __popcll(__ballot(ok && tl < 0));
-        const bool lab = ok && tl >= 0;
+        int tl;
+        const int what = sc_site_label(J, s < s1, s, kind, kind_ok, x_of_site, units, stride, D.T, &tl);
+        n_oth += (unsigned long long) __popcll(__ballot(what == SC_SITE_OTHER));
+        n_unl += (unsigned long long) __popcll(__ballot(what == SC_SITE_UNLABELLED));
+        const bool lab = what == SC_SITE_LABELLED;
         if (!__any(lab)) continue;
         for (int l = 0; l < D.nl; l++)
             for (int cls = 0; cls < 2; cls++) {
@@ -232,15 +171,6 @@ __global__ __launch_bounds__(256) void k_score_counts(ScFour F, int n_bins, unsi
 }
 
 // ---- the host side --------------------------------------------------------------------------------------------------------------
-struct ScEnter {   // the lock, the poison check and the device of every call on an accumulator
-    std::unique_lock<std::mutex> g;
-    int rc;
-    explicit ScEnter(sa_call_scores *s) : g(s->mu), rc(SA_OK) {
-        if (s->poisoned) rc = SA_ESTATE;
-        else if (hipSetDevice(s->device) != hipSuccess) rc = SA_ENODEVICE;
-    }
-};
-
 // room for `need` entries in array a; what it holds is kept
 static int sc_grow(sa_call_scores *s, ScArray &A, size_t need) {
     if (need <= A.cap) return SA_OK;
@@ -389,15 +319,7 @@ extern "C" int sa_call_scores_add_batch(sa_call_scores_t *s, sa_batch_t *b, cons
     if ((size_t) n_jobs != nj || (ns > 0 && F.device != s->device)) { rc = SA_EINVAL; goto done; }
     for (size_t j = 0; j < nj; j++) {
         const sa_score_job_map_t &m = map[j];
-        if (m.contig < 0 || m.contig >= SC_MAX_CONTIG || (m.x_sign != 1 && m.x_sign != -1) || (m.strand != 0 && m.strand != 1) ||
-            (m.mapped_strand != 0 && m.mapped_strand != 1) || m.true_letter < -1 || m.true_letter >= nl) {
-            rc = SA_EINVAL;
-            goto done;
-        }
-        ScJob &J = jobs[j];
-        J.x0 = m.x0; J.contig = m.contig; J.x_sign = m.x_sign; J.strand = m.strand; J.mapped = m.mapped_strand;
-        J.true_letter = m.true_letter;
-        J.ascending = (m.x_sign == 1) == (m.mapped_strand == 0);   // ascending reference_index on '+', descending on '-'
+        if (!sc_job_from_map(m, nl, &jobs[j])) { rc = SA_EINVAL; goto done; }
         const long long sites = F.h_site_off[j + 1] - F.h_site_off[j];
         ub0[m.strand] += sites;
         ub1[m.strand] += m.true_letter >= 0 && sites > 0;
@@ -441,9 +363,9 @@ extern "C" int sa_call_scores_add_batch(sa_call_scores_t *s, sa_batch_t *b, cons
         D.cap = (const unsigned *) (d + o_cap);
         D.cur = (unsigned *) (d + o_cur);
         D.misc = (unsigned long long *) (d + o_misc);
-        D.tkey = (const unsigned long long *) s->d_truth;
-        D.tlet = (const signed char *) (s->d_truth + s->o_tlet);
-        D.n_truth = s->n_truth;
+        D.T.tkey = (const unsigned long long *) s->d_truth;
+        D.T.tlet = (const signed char *) (s->d_truth + s->o_tlet);
+        D.T.n_truth = s->n_truth;
         D.nl = nl;
         appending = true;
         hipLaunchKernelGGL(k_score_sites, dim3((unsigned) nj), dim3(64), 0, 0, (const ScJob *) (d + o_jobs), F.site_off, F.kind,

@@ -120,7 +120,7 @@ static void usage(void) {
                     "--site-calls-truth-reads <labels.tsv>: read label, true letter per line; such a read is labelled as a whole\n"
                     "--site-calls-accuracy-curves <file>: per row and grid point threshold, tp_ge, fp_ge, tpr, fpr, precision\n"
                     "--site-calls-accuracy-bins <n>: grid points k / n, k = 0 .. n (default 1000)\n"
-                    "--site-calls-accuracy-threshold <t>: the confusion counts' threshold (default 0.500000001)\n");
+                    "--site-calls-accuracy-threshold <t>: the confusion counts' threshold (default 0.500000001); --site-calls-accuracy-quality <file> (raw reads, 1-D): per read an R line (label strand status n_calls n_correct n_unlabelled n_other_sites n_outside sum_abs_delta2 max_abs_delta2 max_reference_index n_path n_gaps sum_gap max_gap: calls against the distance of their band from the guide, plot_accuracy_vs_alignment_deviation.py; breaks of the MEA path, plot_breaks_in_alignments.py), a G line per gap (label strand event_before event_after gap), at the end an H line per histogram slot (bin_lo or under / over, wrong, correct); -quality-calls <file>: one line per call (label strand reference_index raw_start raw_length guide_event delta true_letter prob correct outside); -quality-bins lo,width,n (-10000,100,200); -quality-min-gap n (30)\n");
     fprintf(stderr, "--snp-step <N> --snp-dir <dir>: single-nucleotide probabilities: every read is aligned N times, with X at the\n"
                     "                  reference positions = s (mod N) in run s; <dir>/<label>.tsv gets pA pC pG pT per covered position\n"
                     "                  (singleNucleotideProbabilities.py); no posteriors file: no -u, a manifest's posteriors column '-'\n");
@@ -267,8 +267,13 @@ typedef struct {
     /* --site-calls-accuracy: the run's calls scored against known truth on the GPU (sa_call_scores_t), written at the end; it
      * needs the over-reads table too (want_agg) */
     char *acc_path, *acc_curves_path, *acc_truth_path, *acc_reads_path;
-    int acc_bins, acc_opts, want_agg;   /* acc_opts: --site-calls-accuracy-bins or -threshold was given */
+    int acc_bins, acc_opts, want_agg;   /* acc_opts: --site-calls-accuracy-bins, -threshold or a -quality option was given */
     double acc_threshold;
+    /* --site-calls-accuracy-quality: every template batch's calls against their distance from the guide, and the breaks of the MEA
+     * paths (sa_batch_call_quality), written read by read; cq_calls_path: one line per call */
+    char *cq_path, *cq_calls_path;
+    sa_callq_params_t cq_params;
+    int cq_opts;                        /* a -quality sub-option was given */
     /* --train-*: the top-N assignments of the whole run in k-mer tables on the GPU (one per strand), written at the end */
     char *train_assign, *train_model[2], *train_kmers;
     char *train_pos, *train_pos_cov;   /* --train-positions: only the rows that cover a line of the positions file; --train-positions-coverage */
@@ -426,6 +431,11 @@ typedef struct {
     sa_deviation_event_t *dev_events;
     int64_t *dev_ev_first;
     /* --signal-labels only: [job] records, and all jobs' MEA segments, full set, bands and per-sample maps back to back */
+    /* --site-calls-accuracy-quality only: [job] summaries and histogram rows, all jobs' calls and gaps back to back */
+    sa_callq_read_t *cq_reads;
+    sa_callq_call_t *cq_calls;
+    sa_callq_gap_t *cq_gaps;
+    int64_t *cq_hist;
     sa_label_read_t *lab_reads;
     sa_label_segment_t *lab_mea, *lab_full;
     sa_label_band_t *lab_bands;
@@ -469,6 +479,7 @@ static void parse_options(run_t *R, int argc, char **argv) {
     R->train_min_prob = 0.8; R->train_n = 10; R->train_weight = 100.0;   /* probability_threshold, number_of_kmer_assignments, og_model_weight (trainModels.py) */
     R->batch_reads = 2048; R->constraint_trim = 14; R->guide_band = 128; R->lab_kmer_index = 2;
     R->acc_bins = 1000; R->acc_threshold = 0.500000001;
+    R->cq_params = (sa_callq_params_t) {-10000, 100, 200, 30};
     R->p = (sa_params_t) {.threshold = 0.01, .diagonal_expansion = 50, .trace_back_diagonals = 50, .min_diags_between_trace_back = 1000,
                           .split_matrix_bigger_than_this = (int64_t) 3000 * 3000};
     const int N = no_argument, Y = required_argument, O = optional_argument;
@@ -482,7 +493,8 @@ static void parse_options(run_t *R, int argc, char **argv) {
         {"batch", Y, 0, 1000}, {"device", Y, 0, 1001}, {"mea", N, 0, 1002}, {"batch-reads", Y, 0, 1003}, {"emission", Y, 0, 1004},
         {"site-calls", N, 0, 1005}, {"site-calls-aggregate", Y, 0, 1006}, {"site-calls-accuracy", Y, 0, 1070}, {"site-calls-accuracy-curves", Y, 0, 1071},
         {"site-calls-accuracy-bins", Y, 0, 1072}, {"site-calls-accuracy-threshold", Y, 0, 1073}, {"site-calls-truth", Y, 0, 1074},
-        {"site-calls-truth-reads", Y, 0, 1075},
+        {"site-calls-truth-reads", Y, 0, 1075}, {"site-calls-accuracy-quality", Y, 0, 1076}, {"site-calls-accuracy-quality-calls", Y, 0, 1077},
+        {"site-calls-accuracy-quality-bins", Y, 0, 1078}, {"site-calls-accuracy-quality-min-gap", Y, 0, 1079},
         {"train-assignments", Y, 0, 1010}, {"train-template-model", Y, 0, 1011}, {"train-complement-model", Y, 0, 1012}, {"train-min-prob", Y, 0, 1013},
         {"train-max-assignments", Y, 0, 1014}, {"train-weight", Y, 0, 1015}, {"train-min-sd", Y, 0, 1016}, {"train-median", N, 0, 1017},
         {"train-mod-only", N, 0, 1018}, {"train-kmers", Y, 0, 1019}, {"train-mixture-motifs", Y, 0, 1040}, {"train-mixture-template-model", Y, 0, 1041},
@@ -500,7 +512,7 @@ static void parse_options(run_t *R, int argc, char **argv) {
         {'a', &R->ambig_path}, {'T', &R->model_path[0]}, {'C', &R->model_path[1]}, {'L', &one->label}, {'q', &one->npread_path}, {'p', &one->cigar_path},
         {'u', &one->post_path}, {'t', &one->expect[0]}, {'c', &one->expect[1]}, {'v', &R->hdp_path[0]}, {'w', &R->hdp_path[1]}, {'f', &R->fwd_ref},
         {'b', &R->bwd_ref}, {'n', &one->seq_name}, {'i', &one->post_path2}, {1000, &R->manifest}, {1006, &R->agg_path}, {1070, &R->acc_path},
-        {1071, &R->acc_curves_path}, {1074, &R->acc_truth_path}, {1075, &R->acc_reads_path}, {1010, &R->train_assign}, {1011, &R->train_model[0]},
+        {1071, &R->acc_curves_path}, {1074, &R->acc_truth_path}, {1075, &R->acc_reads_path}, {1076, &R->cq_path}, {1077, &R->cq_calls_path}, {1010, &R->train_assign}, {1011, &R->train_model[0]},
         {1012, &R->train_model[1]}, {1019, &R->train_kmers}, {1040, &R->mix_motifs}, {1041, &R->mix_model[0]}, {1042, &R->mix_model[1]},
         {1043, &R->mix_dist}, {1044, &R->train_pos}, {1045, &R->train_pos_cov}, {1021, &R->snp_dir}, {1022, &R->snp_marg}, {1023, &R->snp_prop}, {1024, &R->snp_sites_path}, {1025, &R->snp_ref_out},
         {1026, &R->prof_path}, {1060, &R->dev_path}, {1062, &R->dev_events_path}, {1050, &one->guide_window}, {1052, &R->guide_cigars_out},
@@ -526,6 +538,16 @@ static void parse_options(run_t *R, int argc, char **argv) {
             case 1001: R->device = atoi(optarg); break;
             case 1072: R->acc_bins = atoi(optarg); R->acc_opts = 1; break;
             case 1073: R->acc_threshold = atof(optarg); R->acc_opts = 1; break;
+            case 1078: {
+                long long lo = 0, width = 0;
+                int n = 0;
+                char tail = 0;
+                if (sscanf(optarg, "%lld,%lld,%d%c", &lo, &width, &n, &tail) != 3) width = 0;   /* (refused with the other bad grids) */
+                R->cq_params.bin_lo = lo; R->cq_params.bin_width = width; R->cq_params.n_bins = n;
+                R->cq_opts = 1;
+                break;
+            }
+            case 1079: R->cq_params.min_gap = atoi(optarg); R->cq_opts = 1; break;
             case 1013: R->train_min_prob = atof(optarg); break;
             case 1014: R->train_n = atoll(optarg); break;
             case 1015: R->train_weight = atof(optarg); break;
@@ -559,6 +581,8 @@ static void parse_options(run_t *R, int argc, char **argv) {
     R->batch_mode = R->manifest != NULL;
     R->want_train = R->train_assign || R->train_model[0] || R->train_model[1] || R->mix_motifs;
     R->want_agg = R->agg_path != NULL || R->acc_path != NULL;
+    if (R->cq_calls_path) R->cq_opts = 1;
+    if (R->cq_path || R->cq_opts) R->acc_opts = 1;
 }
 
 /* A table of refusals: the first row that is refused ends the run with its message, after the usage text where the row says so.
@@ -649,6 +673,8 @@ static void check_reads(const run_t *R, read_t *reads, int64_t n_reads) {
 static void check_modes(const run_t *R, const read_t *reads, int64_t n_reads) {
     const int U = 1, expect = R->expect_mode, snp = R->snp_set || R->snp_sites_path != NULL, snp_any = snp || R->snp_dir != NULL;
     const int calls = R->site_calls || R->want_agg, prof = R->prof_path != NULL, dev = R->dev_path != NULL, lab = R->lab_dir != NULL;
+    const int cq = R->cq_path != NULL;
+    const sa_callq_params_t *cp = &R->cq_params;
     const char *opt = R->snp_sites_path ? "--snp-sites" : "--snp-step";
     const refusal_t rows[] = {
         /* (the expectation pass keeps the reference-ordered kernels and the model's own noise; an HDP model has no such emission) */
@@ -668,6 +694,13 @@ static void check_modes(const run_t *R, const read_t *reads, int64_t n_reads) {
         {R->acc_path && (R->acc_bins < 1 || R->acc_threshold != R->acc_threshold), U, "signalMachine: --site-calls-accuracy-bins takes n >= 1, --site-calls-accuracy-threshold a number%s", ""},
         {R->acc_path && R->two_d && (R->mea || dev), U, "signalMachine: --site-calls-accuracy on a --twoD run cannot be combined with --mea / --guide-deviation%s", ""},
         {expect && calls, U, "signalMachine: --site-calls / --site-calls-aggregate / --site-calls-accuracy need the alignment mode, not -t/-c%s", ""},
+        /* --site-calls-accuracy-quality: 1-D accuracy runs of raw reads */
+        {!cq && R->cq_opts, U, "signalMachine: --site-calls-accuracy-quality-* need --site-calls-accuracy-quality <file>%s", ""},
+        {cq && (cp->bin_width < 1 || cp->bin_width > (1ll << 40) || cp->bin_lo < -(1ll << 40) || cp->bin_lo > (1ll << 40) || cp->n_bins < 1 ||
+                cp->n_bins > SA_CQ_MAX_BINS || cp->min_gap < 0), U,
+         "signalMachine: --site-calls-accuracy-quality-bins takes lo,width,n with width >= 1 and 1 <= n <= 1024, -min-gap n >= 0%s", ""},
+        {cq && R->two_d, U, "signalMachine: --site-calls-accuracy-quality does not take --twoD runs%s", ""},
+        {cq && !R->batch_mode && !reads[0].raw, U, "signalMachine: --site-calls-accuracy-quality needs a read given as raw current: an .npRead has no raw starts%s", ""},
         {R->snp_prop && !R->snp_marg, U, "signalMachine: --snp-proposals needs --snp-marginals <file>%s", ""},
         {R->snp_sites_path && R->snp_set, U, "signalMachine: --snp-sites cannot be combined with --snp-step%s", ""},
         {R->snp_ref_out && !R->snp_sites_path, U, "signalMachine: --snp-reference-out needs --snp-sites <file>%s", ""},

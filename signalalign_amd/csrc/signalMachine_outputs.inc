@@ -285,17 +285,16 @@ static void acc_create(acc_t *ac, const strand_result_t *sr, int64_t n) {
         if (rc != SA_OK) die("signalMachine: --site-calls-accuracy: %s", sa_strerror(rc));
     }
 }
-/* levels 0 and 1 of the slice's finished batch of strand s.  The mapping strand of a job is the one order_calls gives its calls. */
-static void acc_add(acc_t *ac, const slice_t *sl, int s, sa_batch_t *b) {
+/* Where every job of the slice's strand s lies: adjust_ref as x0 + x_sign * x, the mapping strand the one order_calls gives the job's
+ * calls, the read's label where --site-calls-truth-reads names it. */
+static sa_score_job_map_t *acc_job_map(acc_t *ac, const slice_t *sl, int s) {
     const run_t *R = ac->o.R;
     const int64_t nj = sl->n_ok;
-    acc_create(ac, &sl->sr[s], nj);
-    if (!ac->acc) return;   /* (no call so far: nothing to score) */
     sa_score_job_map_t *map = xalloc(nj, sizeof(*map), 1);
     for (int64_t j = 0; j < nj; j++) {
         const read_t *rd = &sl->reads[sl->who[j]];
         const int idx = (s == 1 && sl->tmpl_amb && sl->tmpl_amb[j]) ? 1 : 0;
-        const int along = (s == 0 && rd->forward) || (s == 1 && !rd->forward);   /* adjust_ref as x0 + x_sign * x */
+        const int along = (s == 0 && rd->forward) || (s == 1 && !rd->forward);
         map[j].contig = acc_contig(ac, rd->pA->contig1);
         map[j].x_sign = along ? 1 : -1;
         map[j].x0 = along ? rd->st[s].r_shift : rd->st[s].r_shift - R->sm[s].k;
@@ -303,6 +302,14 @@ static void acc_add(acc_t *ac, const slice_t *sl, int s, sa_batch_t *b) {
         map[j].mapped_strand = (idx == 0) == (rd->forward != 0) ? 0 : 1;
         map[j].true_letter = acc_read_letter(ac, rd->label);
     }
+    return map;
+}
+/* levels 0 and 1 of the slice's finished batch of strand s */
+static void acc_add(acc_t *ac, const slice_t *sl, int s, sa_batch_t *b) {
+    const int64_t nj = sl->n_ok;
+    acc_create(ac, &sl->sr[s], nj);
+    if (!ac->acc) return;   /* (no call so far: nothing to score) */
+    sa_score_job_map_t *map = acc_job_map(ac, sl, s);
     const int rc = sa_call_scores_add_batch(ac->acc, b, map, nj, NULL);
     free(map);
     if (rc != SA_OK) die_opt(ac->o.opt, sa_strerror(rc));
@@ -381,6 +388,110 @@ static void acc_finish(output_t *o) {
     sa_free(rows); sa_free(curves);
     sa_call_scores_destroy(ac->acc);
     ac->acc = NULL;
+}
+
+/* ---- --site-calls-accuracy-quality: every template batch's labelled calls against the distance of their band from the guide, and
+ * the breaks of the MEA paths (sa_batch_call_quality), with the letters, threshold and positions table of the run's accumulator;
+ * written read by read as the reads are rendered.  A read given as .npRead has no raw starts: its job goes into the call with
+ * one-sample events (the call wants every job of the batch) and nothing is written for it. ---- */
+typedef struct {
+    output_t o;
+    acc_t *acc;
+    FILE *fh, *calls_fh;
+    int64_t total[(SA_CQ_MAX_BINS + 2) * 2];   /* the histogram rows of the reads written so far, summed: the H lines */
+} callq_t;
+static void cq_open(output_t *o) {
+    callq_t *cq = (callq_t *) o;
+    const run_t *R = o->R;
+    if (!(cq->fh = fopen(R->cq_path, "w"))) die("signalMachine: cannot open output %s", R->cq_path);
+    fprintf(cq->fh, "#call-quality bin_lo=%" PRId64 " bin_width=%" PRId64 " n_bins=%d min_gap=%d; R label strand status n_calls n_correct n_unlabelled "
+                    "n_other_sites n_outside sum_abs_delta2 max_abs_delta2 max_reference_index n_path n_gaps sum_gap max_gap; G label strand "
+                    "event_before event_after gap; H bin_lo wrong correct\n", R->cq_params.bin_lo, R->cq_params.bin_width, R->cq_params.n_bins,
+            R->cq_params.min_gap);
+    if (R->cq_calls_path) {
+        if (!(cq->calls_fh = fopen(R->cq_calls_path, "w"))) die("signalMachine: cannot open output %s", R->cq_calls_path);
+        fprintf(cq->calls_fh, "#label\tstrand\treference_index\traw_start\traw_length\tguide_event\tdelta\ttrue_letter\tprob\tcorrect\toutside\n");
+    }
+}
+/* the finished template batch against its own jobs' anchors, with the MEA paths just made of it (after acc_add_batch, which makes
+ * the accumulator at the run's first call; before that there is nothing to label) */
+static int cq_add_batch(output_t *o, slice_t *sl, int s, sa_batch_t *b) {
+    callq_t *cq = (callq_t *) o;
+    const run_t *R = o->R;
+    strand_result_t *sr = &sl->sr[s];
+    const int64_t n = sl->n_ok, n_slots = ((int64_t) R->cq_params.n_bins + 2) * 2;
+    if (s != 0 || !cq->acc->acc) return SA_OK;
+    sa_callq_job_t *cj = xalloc(n, sizeof(*cj), 1);
+    int64_t *plain = NULL, n_plain = 0;   /* 0, 1, 2, ...: the raw starts of the reads that have none */
+    for (int64_t j = 0; j < n; j++)
+        if (!sl->reads[sl->who[j]].raw_start && sl->jobs[s][j].n_events > n_plain) n_plain = sl->jobs[s][j].n_events;
+    if (n_plain > 0) {
+        plain = xalloc(2 * n_plain, sizeof(int64_t), 0);
+        for (int64_t y = 0; y < n_plain; y++) { plain[y] = y; plain[n_plain + y] = 1; }
+    }
+    for (int64_t j = 0; j < n; j++) {
+        const read_t *rd = &sl->reads[sl->who[j]];
+        const sa_job_t *q = &sl->jobs[s][j];
+        cj[j] = (sa_callq_job_t) {q->anchor_x, q->anchor_y, q->n_anchors, rd->raw_start ? rd->raw_start + rd->st[s].lo : plain,
+                                  rd->raw_start ? rd->raw_length + rd->st[s].lo : plain + n_plain, q->n_events};
+    }
+    sa_score_job_map_t *map = acc_job_map(cq->acc, sl, s);
+    sr->cq_reads = xalloc(n, sizeof(sa_callq_read_t), 1);
+    sr->cq_hist = xalloc(n * n_slots, sizeof(int64_t), 1);
+    int64_t n_calls = 0, n_gaps = 0;
+    const int rc = sa_batch_call_quality(cq->acc->acc, b, map, cj, n, (const sa_mea_pair_t *const *) sr->mea, sr->n_mea, &R->cq_params,
+                                         cq->calls_fh ? SA_CQ_CALLS : 0u, sr->cq_reads, cq->calls_fh ? &sr->cq_calls : NULL,
+                                         cq->calls_fh ? &n_calls : NULL, &sr->cq_gaps, &n_gaps, sr->cq_hist, NULL, NULL);
+    free(map); free(cj); free(plain);
+    if (rc != SA_OK) die_opt(o->opt, sa_strerror(rc));
+    return SA_OK;
+}
+/* ... and the lines of job j.  Events are printed as the TSV's event_index column prints them, positions as the .calls file prints
+ * them; delta is delta2 / 2, an integer or <n>.5 */
+static void cq_add_read(output_t *o, slice_t *sl, int64_t j) {
+    callq_t *cq = (callq_t *) o;
+    const run_t *R = o->R;
+    const read_t *rd = &sl->reads[sl->who[j]];
+    const strand_result_t *sr = &sl->sr[0];
+    if (!rd->raw_start) {
+        fprintf(stderr, "[signalMachine]NOTICE: %s is not given as raw current: no call quality\n", rd->label);
+        return;
+    }
+    if (!sr->cq_reads) return;   /* (the run had no site call yet when the read's batch finished) */
+    const sa_callq_read_t *r = &sr->cq_reads[j];
+    const int64_t n_slots = ((int64_t) R->cq_params.n_bins + 2) * 2, lo = rd->st[0].lo;
+    const int64_t ref_len = (int64_t) strlen(rd->st[0].target), ref_len_kmers = ref_len - R->sm[0].k, off = rd->st[0].r_shift;
+    fprintf(cq->fh, "R\t%s\tt\t%d\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64
+                    "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\n", rd->label, r->status, r->n_calls, r->n_correct, r->n_unlabelled, r->n_other_sites,
+            r->n_outside, r->sum_abs_delta2, r->max_abs_delta2,
+            r->max_x >= 0 ? adjust_ref(r->max_x, off, ref_len_kmers, ref_len, 1, rd->forward) : (int64_t) -1, r->n_path, r->n_gaps, r->sum_gap,
+            r->max_gap);
+    for (int64_t i = 0; i < r->n_gaps; i++) {
+        const sa_callq_gap_t *g = &sr->cq_gaps[r->gap_first + i];
+        fprintf(cq->fh, "G\t%s\tt\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\n", rd->label, lo + g->y_before, lo + g->y_after, g->gap);
+    }
+    for (int64_t q = 0; q < n_slots; q++) cq->total[q] += sr->cq_hist[j * n_slots + q];
+    for (int64_t i = 0; cq->calls_fh && i < r->n_calls; i++) {
+        const sa_callq_call_t *c = &sr->cq_calls[r->call_first + i];
+        const int64_t half = c->delta2 < 0 ? -c->delta2 : c->delta2;
+        char prob[40];
+        sa_format_py_repr(prob, c->prob_true);
+        fprintf(cq->calls_fh, "%s\tt\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%" PRId64 "\t%s%" PRId64 "%s\t%c\t%s\t%d\t%d\n", rd->label,
+                adjust_ref(c->x, off, ref_len_kmers, ref_len, 1, rd->forward), c->raw_start, c->raw_length,
+                c->guide_event >= 0 ? lo + c->guide_event : (int64_t) -1, c->delta2 < 0 ? "-" : "", half / 2, half % 2 ? ".5" : "",
+                cq->acc->letters[c->true_letter], prob, c->correct, c->outside);
+    }
+}
+static void cq_finish(output_t *o) {   /* the histogram summed over the reads written */
+    callq_t *cq = (callq_t *) o;
+    const sa_callq_params_t *p = &o->R->cq_params;
+    for (int q = 0; q < p->n_bins + 2; q++) {
+        if (q == 0) fprintf(cq->fh, "H\tunder");
+        else if (q == p->n_bins + 1) fprintf(cq->fh, "H\tover");
+        else fprintf(cq->fh, "H\t%" PRId64, p->bin_lo + (int64_t) (q - 1) * p->bin_width);
+        fprintf(cq->fh, "\t%" PRId64 "\t%" PRId64 "\n", cq->total[2 * q], cq->total[2 * q + 1]);
+    }
+    if (fclose(cq->fh) != 0 || (cq->calls_fh && fclose(cq->calls_fh) != 0)) die("signalMachine: cannot write %s", o->R->cq_path);
 }
 
 /* ---- --train-*: the top-N assignments of the whole run in k-mer tables on the GPU, one per strand ---- */
@@ -1047,6 +1158,8 @@ static void outputs_open(run_t *R) {
     output_t *agg = output_new(R, R->want_agg, sizeof(agg_t), (output_t) {.opt = "--site-calls-aggregate", .add_read = agg_add_read, .finish = agg_finish});
     output_t *acc = output_new(R, R->acc_path != NULL, sizeof(acc_t), (output_t) {.opt = "--site-calls-accuracy", .open = acc_open, .checkpoint = acc_checkpoint, .rollback = acc_rollback, .add_batch = acc_add_batch, .rendered = acc_rendered, .finish = acc_finish});
     if (acc) ((acc_t *) acc)->agg = (agg_t *) agg;
+    output_t *cq = output_new(R, R->cq_path != NULL, sizeof(callq_t), (output_t) {.opt = "--site-calls-accuracy-quality", .open = cq_open, .add_batch = cq_add_batch, .add_read = cq_add_read, .finish = cq_finish});
+    if (cq) ((callq_t *) cq)->acc = (acc_t *) acc;
     output_new(R, R->want_train, sizeof(train_t), (output_t) {.opt = "--train-*", .open = train_open, .checkpoint = train_checkpoint, .rollback = train_rollback, .add_batch = train_add_batch, .finish = train_finish});
     output_new(R, R->dev_path != NULL, sizeof(deviation_t), (output_t) {.opt = "--guide-deviation", .open = dev_open, .add_batch = dev_add_batch, .add_read = dev_add_read, .finish = dev_finish});
     output_new(R, R->lab_dir != NULL, sizeof(output_t), (output_t) {.opt = "--signal-labels", .add_batch = lab_add_batch, .add_read = lab_add_read});

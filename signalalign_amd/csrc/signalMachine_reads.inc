@@ -276,7 +276,7 @@ static void raw_stage(const run_t *R, read_t *reads, int64_t n_reads) {
         np->template_events = xalloc(4 * o->n_events, sizeof(double), 0);
         memcpy(np->template_events, o->events4, sizeof(double) * 4 * (size_t) o->n_events);
         r->np = np;
-        if (R->lab_dir) {   /* --signal-labels: where every event lies in the raw current */
+        if (R->lab_dir || R->cq_path) {   /* --signal-labels, --site-calls-accuracy-quality: where every event lies in the raw current */
             r->raw_start = xalloc(o->n_events, sizeof(int64_t), 0);
             r->raw_length = xalloc(o->n_events, sizeof(int64_t), 0);
             memcpy(r->raw_start, o->raw_start, sizeof(int64_t) * (size_t) o->n_events);

@@ -138,7 +138,8 @@ static void align_free_strand(slice_t *sl, int s, int64_t n_jobs) {
     free(sr->calls); free(sr->n_calls);
     free(sr->dev_reads); free(sr->dev_hist); free(sr->dev_ev_first);
     sa_free(sr->dev_sets); sa_free(sr->dev_events);
-    free(sr->lab_reads);
+    free(sr->lab_reads); free(sr->cq_reads); free(sr->cq_hist);
+    sa_free(sr->cq_calls); sa_free(sr->cq_gaps);
     sa_free(sr->lab_mea); sa_free(sr->lab_full); sa_free(sr->lab_bands); sa_free(sr->lab_samples);
     memset(sr, 0, sizeof(*sr));
 }
@@ -318,7 +319,8 @@ static int64_t run_slice_expect(run_t *R, read_t *reads, int64_t n_reads) {
  * -s 0 / -s 2 without --mea: 8-byte result records where the batch allows them (one path per cell: no ambiguity letter in any
  * read's reference; fewer than 2^20 positions and events per read) -- the planner says SA_EUNSUPPORTED otherwise and the strand's
  * batch is made again with 16-byte records.  SA_CLI_PAIRS16=1: always 16-byte records (the test's checker).
- * --mea, --guide-deviation, --signal-labels: the pairs are copied out while the batch still has them on the device for the path step.
+ * --mea, --guide-deviation, --signal-labels, --site-calls-accuracy-quality: the pairs are copied out while the batch still has them
+ * on the device for the path step.
  * The run-wide outputs take the batch while its records are in HBM (outputs_add_batch); with --mea the batch ends there.
  * Otherwise the batch stays alive for the rendering, which expands its packed records job by job. */
 static int align_run_strand(slice_t *sl, int s) {
@@ -326,7 +328,7 @@ static int align_run_strand(slice_t *sl, int s) {
     strand_result_t *sr = &sl->sr[s];
     const int64_t n = sl->n_ok;
     const int want_calls = R->site_calls || R->want_agg;
-    const int want_mea = R->mea || R->dev_path != NULL || R->lab_dir != NULL;
+    const int want_mea = R->mea || R->dev_path != NULL || R->lab_dir != NULL || R->cq_path != NULL;
     unsigned flags = want_calls ? SA_FLAG_SITE_CALLS : 0u, p8 = 0u;
     if (!want_mea && !want_calls) {
         if (R->out_fmt == 1 && !R->want_train && !getenv("SA_CLI_VC_ON_HOST")) flags |= SA_FLAG_VC_ROWS;
