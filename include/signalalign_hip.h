@@ -647,6 +647,14 @@ typedef struct sa_site_call {
  * kernel_ms_out (may be NULL): HIP-event time of the kernels.  SA_ESTATE: created without SA_FLAG_SITE_CALLS, or not run.
  * Deterministic: the sums are integer atomics. */
 int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out);
+/* The same calls from records the caller holds, through the same kernels: job j's records are first[j] .. first[j + 1) of x,
+ * kmer_id and prob_e7, in sa_batch_pairs order.  Of a job only ref and ref_len are read; `ambig` is the map sa_batch_create takes
+ * (NULL: no site anywhere).  Checked before the device is touched, SA_EINVAL: first[0] != 0 or first not monotone; x outside
+ * [0, ref_len - k]; kmer_id outside [0, n_alpha^k); prob_e7 outside [0, 10^7]; a NULL array with records.  More than
+ * SA_SITE_MAX_LETTERS options at a site: SA_EUNSUPPORTED, as at creation.  calls_out / n_out: n_jobs entries, as above. */
+int sa_site_calls_records(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig,
+                          const int64_t *first /* n_jobs + 1 */, const int32_t *x, const int32_t *kmer_id, const int64_t *prob_e7,
+                          int device, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out);
 
 /* ---- Per-position marginals: single-nucleotide probabilities ------------------------------------------------------------
  * Replaces CallMethylation.call_methyls (src/signalalign/scripts/alignmentAnalysisLib.py:159-247) over one full TSV per job, in
@@ -657,8 +665,12 @@ int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_ou
  *   sum       per letter, the printed posterior of those rows ("%f" of prob_e7 / 1e7 read back as a double, i.e. units / 1e6)
  *             added serially in row order (sa_batch_pairs order, the TSV's), starting from 0
  *   prob      sum[l] / total, total = ((0 + sum[0]) + sum[1]) + ... over the sorted letters -- the reference's bits
- * One record per (job, position with at least one row), in ascending p.  x_min_out / x_max_out (n_jobs entries each, may be
- * NULL): the smallest and largest x of the job's records, -1 for a job without records.
+ * One record per (job, position with at least one row), in ascending p.  A position whose rows all print 0.000000 (possible
+ * only with a threshold below 5e-7) has total 0: the reference divides by zero there (alignmentAnalysisLib.py:230-233,
+ * ZeroDivisionError); here the record is reported with its n_rows, sum all 0.0 and prob all 0.0, the site calls' rule for a
+ * zero sum.
+ * x_min_out / x_max_out (n_jobs entries each, may be NULL): the smallest and largest x of the job's records, -1 for a job
+ * without records.
  * SA_FLAG_POSITION_CALLS at sa_batch_create / _deferred: the batch records its ambiguous positions (one host pass over each
  * reference).  With SA_FLAG_VC_ROWS: SA_EINVAL; with SA_FLAG_PAIRS8, or an ambiguity letter with more than SA_SITE_MAX_LETTERS
  * distinct options: SA_EUNSUPPORTED (both at creation).  The call: SA_ESTATE when created without the flag or not run.  Works
@@ -673,6 +685,13 @@ typedef struct sa_position_call {
 } sa_position_call_t;
 int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out, int32_t *x_min_out,
                             int32_t *x_max_out, double *kernel_ms_out);
+/* The same calls from records the caller holds, through the same kernels; the arguments and their checks are those of
+ * sa_site_calls_records (x is a k-mer index: 0 <= x <= ref_len - k), the row order is the records' order within their job.
+ * A model with k > 32: SA_EUNSUPPORTED, as at creation. */
+int sa_position_calls_records(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig,
+                              const int64_t *first /* n_jobs + 1 */, const int32_t *x, const int32_t *kmer_id, const int64_t *prob_e7,
+                              int device, sa_position_call_t **calls_out, int64_t *n_out, int32_t *x_min_out, int32_t *x_max_out,
+                              double *kernel_ms_out);
 
 /* ---- host helpers of signalMachine --snp-step (singleNucleotideProbabilities.py:551-723) -------------------------------
  * sa_snp_substitute: the window of replace_periodic_sequence_positions (utils/sequenceTools.py:207-254).  ref[i] lies at contig

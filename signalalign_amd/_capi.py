@@ -434,6 +434,9 @@ SIGNATURES = {
     "sa_mea_params": (C.c_int64, [_pi64, _pi64, _pf64, C.c_int64, _pi32, _pi32, _pf64, _pi32, _pi64]),
     "sa_batch_site_calls": (C.c_int, [_vp, C.c_uint, _P(_P(SiteCall)), _pi64, _pf64]),
     "sa_batch_position_calls": (C.c_int, [_vp, C.c_uint, _P(_P(PositionCall)), _pi64, _pi32, _pi32, _pf64]),
+    "sa_site_calls_records": (C.c_int, [_vp, _P(Job), C.c_int64, _pstr, _pi64, _pi32, _pi32, _pi64, C.c_int, _P(_P(SiteCall)), _pi64, _pf64]),
+    "sa_position_calls_records": (C.c_int, [_vp, _P(Job), C.c_int64, _pstr, _pi64, _pi32, _pi32, _pi64, C.c_int, _P(_P(PositionCall)),
+                                            _pi64, _pi32, _pi32, _pf64]),
     "sa_snp_substitute": (C.c_int, [_str, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_char, _str]),
     "sa_snp_site_window": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _pi64, _pi64]),
     "sa_snp_write_read": (C.c_int, [_str, _str, _str, _str, C.c_int, _P(SnpSite), C.c_int64]),
@@ -999,12 +1002,7 @@ class Batch(_Handle):
         t0 = time.perf_counter()
         _chk(lib().sa_batch_site_calls(self._h, 0, ptrs, _ip(cnt), C.byref(kms)), "sa_batch_site_calls")
         _timing(stats, kms, t0)
-        out = []
-        for i in range(n):
-            rec = _copy_out(ptrs[i], int(cnt[i]), SITE_CALL_DTYPE)
-            letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
-            out.append({"x": rec["x"].copy(), "letters": letters, "units": rec["units"].copy(), "prob": rec["prob"].copy()})
-        return out
+        return _site_calls_out(ptrs, cnt, n)
 
     def position_calls(self, stats=None):
         """sa_batch_position_calls (a batch created with FLAG_POSITION_CALLS, after run()): per job a dict -- p [n] (ambiguous
@@ -1021,18 +1019,78 @@ class Batch(_Handle):
         _chk(lib().sa_batch_position_calls(self._h, 0, ptrs, _ip(cnt), _i32p(xmin), _i32p(xmax), C.byref(kms)),
              "sa_batch_position_calls")
         _timing(stats, kms, t0)
-        out = []
-        for i in range(n):
-            rec = _copy_out(ptrs[i], int(cnt[i]), POSITION_CALL_DTYPE)
-            letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
-            out.append({"p": rec["p"].copy(), "n_rows": rec["n_rows"].copy(), "letters": letters, "sum": rec["sum"].copy(),
-                        "prob": rec["prob"].copy(), "x_min": int(xmin[i]), "x_max": int(xmax[i])})
-        return out
+        return _position_calls_out(ptrs, cnt, xmin, xmax, n)
 
     def stats(self):
         s = BatchStats()
         _chk(lib().sa_batch_stats(self._h, C.byref(s)), "sa_batch_stats")
         return s
+
+
+def _site_calls_out(ptrs, cnt, n):
+    """the per-job dicts of Batch.site_calls / site_calls_records from the library's arrays, which are released"""
+    out = []
+    for i in range(n):
+        rec = _copy_out(ptrs[i], int(cnt[i]), SITE_CALL_DTYPE)
+        letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
+        out.append({"x": rec["x"].copy(), "letters": letters, "units": rec["units"].copy(), "prob": rec["prob"].copy()})
+    return out
+
+
+def _position_calls_out(ptrs, cnt, xmin, xmax, n):
+    """the per-job dicts of Batch.position_calls / position_calls_records from the library's arrays, which are released"""
+    out = []
+    for i in range(n):
+        rec = _copy_out(ptrs[i], int(cnt[i]), POSITION_CALL_DTYPE)
+        letters = np.array([b"".join(r["letters"][:r["n_letters"]]).decode() for r in rec], dtype=object)
+        out.append({"p": rec["p"].copy(), "n_rows": rec["n_rows"].copy(), "letters": letters, "sum": rec["sum"].copy(),
+                    "prob": rec["prob"].copy(), "x_min": int(xmin[i]), "x_max": int(xmax[i])})
+    return out
+
+
+def _calls_records_args(refs, first, x, kmer_id, prob_e7):
+    """what site_calls_records and position_calls_records share: jobs of which only ref / ref_len are set, and the record arrays"""
+    refs = [r.encode() if isinstance(r, str) else r for r in refs]
+    n = len(refs)
+    arr = (Job * max(n, 1))()
+    for i, r in enumerate(refs):
+        arr[i].ref, arr[i].ref_len = r, len(r)
+    first, x, kmer_id, prob_e7 = _i64(first), _i32(x), _i32(kmer_id), _i64(prob_e7)
+    if len(first) != n + 1 or not (len(x) == len(kmer_id) == len(prob_e7)) or int(first[-1]) != len(x):
+        raise ValueError("first: n_jobs + 1 offsets into x, kmer_id and prob_e7, which have one entry per record")
+    return n, arr, (refs, first, x, kmer_id, prob_e7)
+
+
+def site_calls_records(model, refs, first, x, kmer_id, prob_e7, ambig=None, device=0, stats=None):
+    """sa_site_calls_records: Batch.site_calls' result from records the caller holds -- refs: one reference per job; job j's records
+    are first[j] .. first[j + 1) of x, kmer_id, prob_e7; ambig as Batch takes it"""
+    n, arr, keep = _calls_records_args(refs, first, x, kmer_id, prob_e7)
+    amb = ambig if ambig is not None else default_ambig()
+    ptrs = (C.POINTER(SiteCall) * max(n, 1))()
+    cnt = np.zeros(max(n, 1), dtype=np.int64)
+    kms = C.c_double()
+    t0 = time.perf_counter()
+    _chk(lib().sa_site_calls_records(model._h, arr, n, amb, _ip(keep[1]), _i32p(keep[2]), _i32p(keep[3]), _ip(keep[4]), int(device), ptrs,
+                                     _ip(cnt), C.byref(kms)), "sa_site_calls_records")
+    _timing(stats, kms, t0)
+    return _site_calls_out(ptrs, cnt, n)
+
+
+def position_calls_records(model, refs, first, x, kmer_id, prob_e7, ambig=None, device=0, stats=None):
+    """sa_position_calls_records: Batch.position_calls' result from records the caller holds, the arguments as site_calls_records';
+    the row order is the records' order within their job"""
+    n, arr, keep = _calls_records_args(refs, first, x, kmer_id, prob_e7)
+    amb = ambig if ambig is not None else default_ambig()
+    ptrs = (C.POINTER(PositionCall) * max(n, 1))()
+    cnt = np.zeros(max(n, 1), dtype=np.int64)
+    xmin = np.zeros(max(n, 1), dtype=np.int32)
+    xmax = np.zeros(max(n, 1), dtype=np.int32)
+    kms = C.c_double()
+    t0 = time.perf_counter()
+    _chk(lib().sa_position_calls_records(model._h, arr, n, amb, _ip(keep[1]), _i32p(keep[2]), _i32p(keep[3]), _ip(keep[4]), int(device), ptrs,
+                                         _ip(cnt), _i32p(xmin), _i32p(xmax), C.byref(kms)), "sa_position_calls_records")
+    _timing(stats, kms, t0)
+    return _position_calls_out(ptrs, cnt, xmin, xmax, n)
 
 
 def expect_batch(model, params, jobs, ambig=None, device=0, flags=0, pseudocount=0.0):

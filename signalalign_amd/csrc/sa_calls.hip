@@ -255,22 +255,31 @@ __global__ __launch_bounds__(64) void k_site_compact(SiteTabs T, const unsigned 
 // back to it at the end of the call (sa_pool_release / the pool's bounds reach it)
 static SaScratch g_site_ws;
 
-// the accumulate-and-normalise half of the site calls of a finished batch, left on the device (SaSiteFold, sa_chain.h)
-int sa_site_fold_run(sa_batch_t *b, SaSiteFold *F) {
-    SaAmbigTab *S = nullptr;
-    int64_t nj64 = 0;
-    int rc = sa_batch_ambig(b, SA_TAB_SITES, &S, &nj64);
-    if (rc) return rc;
-    const size_t nj = F->nj = (size_t) nj64;
-    const size_t stride = F->stride = (size_t) S->stride, ns = F->ns = (size_t) S->n_sites;
+// the records of a call that brings its own (sa_*_calls_records), up into a block of the caching allocator; the caller holds
+// the scratch's lock and has bound it to `device`
+static int fold_records_upload(const std::vector<sa_pair16_t> &recs, int device, char **d_recs) {
+    const size_t bytes = sizeof(sa_pair16_t) * recs.size();
+    if (g_sa_pool.get(SaPool::DEVICE, (void **) d_recs, bytes, device) != hipSuccess) { *d_recs = nullptr; return SA_ENOMEM; }
+    if (bytes && hipMemcpy(*d_recs, recs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return SA_ENODEVICE;
+    return SA_OK;
+}
+
+// what the table alone says of a site fold: the host half of SaSiteFold
+static void site_fold_init(const SaAmbigTab *S, size_t nj, SaSiteFold *F) {
+    F->nj = nj;
+    F->stride = (size_t) S->stride;
+    F->ns = (size_t) S->n_sites;
     F->kernel_ms = 0.0;
     F->h_x = S->x.data();
     F->h_site_off = S->site_off.data();
     F->letters = S->letters;
-    if (ns == 0) return SA_OK;   // (a batch without sites -- a SA_FLAG_PAIRS8 one among them -- has nothing to read on the device)
-    SaBatchView V;
-    if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
-    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+}
+
+// The site fold of table S (n_sites > 0) over the 16-byte records of view V: V.recs on V.device, or -- h_recs -- the host
+// records that go up first.  What sa_site_fold_run promises of the lock and the timed region holds here.
+static int site_fold_records(SaAmbigTab *S, const SaBatchView &V, const std::vector<sa_pair16_t> *h_recs, SaSiteFold *F) {
+    int rc = SA_OK;
+    const size_t nj = F->nj, stride = F->stride, ns = F->ns;
     const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
     const int device = F->device = V.device;
     const std::vector<SaRecChunk> chunks = sa_view_chunks(V, SA_CHAIN_CHUNK, SA_ORDINAL_PER_JOB);   // (ordinals unused)
@@ -284,6 +293,10 @@ int sa_site_fold_run(sa_batch_t *b, SaSiteFold *F) {
     char *&d = F->d;
     SiteTabs T;
     if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(S, device)) != SA_OK) return rc;
+    if (h_recs) {
+        if ((rc = fold_records_upload(*h_recs, device, &F->d_recs)) != SA_OK) return rc;
+        d_pairs = (const sa_pair16_t *) F->d_recs;
+    }
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, L.end, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
     T = sites_tabs(S);
     if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
@@ -302,32 +315,39 @@ done:
     return rc;
 }
 
-void sa_site_fold_release(SaSiteFold *F, bool failed) {
-    if (failed && F->d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
-    if (F->d) g_sa_pool.put(SaPool::DEVICE, F->d);
-    F->d = nullptr;
-    if (F->guard.owns_lock()) F->guard.unlock();
-}
-
-extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
-    (void) flags;
-    if (!b || !calls_out || !n_out) return SA_EINVAL;
+// the accumulate-and-normalise half of the site calls of a finished batch, left on the device (SaSiteFold, sa_chain.h)
+int sa_site_fold_run(sa_batch_t *b, SaSiteFold *F) {
     SaAmbigTab *S = nullptr;
     int64_t nj64 = 0;
     int rc = sa_batch_ambig(b, SA_TAB_SITES, &S, &nj64);
     if (rc) return rc;
-    const size_t nj = (size_t) nj64;
-    for (size_t j = 0; j < nj; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
-    if (kernel_ms_out) *kernel_ms_out = 0.0;
-    const size_t stride = (size_t) S->stride, ns = (size_t) S->n_sites;
+    site_fold_init(S, (size_t) nj64, F);
+    if (F->ns == 0) return SA_OK;   // (a batch without sites -- a SA_FLAG_PAIRS8 one among them -- has nothing to read on the device)
+    SaBatchView V;
+    if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
+    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+    return site_fold_records(S, V, nullptr, F);
+}
+
+void sa_site_fold_release(SaSiteFold *F, bool failed) {
+    if (failed && (F->d || F->d_recs)) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
+    if (F->d) g_sa_pool.put(SaPool::DEVICE, F->d);
+    if (F->d_recs) g_sa_pool.put(SaPool::DEVICE, F->d_recs);
+    F->d = F->d_recs = nullptr;
+    if (F->guard.owns_lock()) F->guard.unlock();
+}
+
+// The second half of the site calls: fold F of table S (run, when the table has sites) compacted and copied out into the
+// cleared calls_out / n_out, one entry per job; the fold is released.
+static int site_calls_out(const SaAmbigTab *S, SaSiteFold &F, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
+    int rc = SA_OK;
+    const size_t nj = F.nj, stride = (size_t) S->stride, ns = (size_t) S->n_sites;
     std::vector<long long> h_off(nj + 1, 0);
     const int *h_site = nullptr;
     const unsigned long long *h_units = nullptr;
     const double *h_prob = nullptr;
     char *d = nullptr, *h = nullptr;   // this call's device and pinned blocks (g_sa_pool), beside the fold's
-    SaSiteFold F;
     if (ns > 0) {
-        if ((rc = sa_site_fold_run(b, &F)) != SA_OK) { sa_site_fold_release(&F, true); return rc; }
         SaScratch &W = *F.ws;
         const int device = F.device;
         const SiteTabs T = sites_tabs(S);
@@ -395,11 +415,80 @@ done:
     return rc;
 }
 
+extern "C" int sa_batch_site_calls(sa_batch_t *b, unsigned flags, sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
+    (void) flags;
+    if (!b || !calls_out || !n_out) return SA_EINVAL;
+    SaAmbigTab *S = nullptr;
+    int64_t nj64 = 0;
+    int rc = sa_batch_ambig(b, SA_TAB_SITES, &S, &nj64);
+    if (rc) return rc;
+    for (int64_t j = 0; j < nj64; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    SaSiteFold F;
+    if ((rc = sa_site_fold_run(b, &F)) != SA_OK) { sa_site_fold_release(&F, true); return rc; }
+    return site_calls_out(S, F, calls_out, n_out, kernel_ms_out);
+}
+
+// What sa_site_calls_records and sa_position_calls_records check before the device, and the records packed as a batch leaves
+// them: job j's are first[j] .. first[j + 1), each with x a k-mer index of the job's reference.  The view gets the jobs' ranges.
+static int calls_records_pack(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const int64_t *first, const int32_t *x,
+                              const int32_t *kmer_id, const int64_t *prob_e7, std::vector<sa_pair16_t> *recs, SaBatchView *V) {
+    if (!m || n_jobs < 0 || (n_jobs > 0 && !jobs) || !first || first[0] != 0) return SA_EINVAL;
+    for (int64_t j = 0; j < n_jobs; j++)
+        if (first[j + 1] < first[j] || jobs[j].ref_len < 0 || (jobs[j].ref_len > 0 && !jobs[j].ref)) return SA_EINVAL;
+    const int64_t n = first[n_jobs];
+    if (n > 0 && (!x || !kmer_id || !prob_e7)) return SA_EINVAL;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        const int64_t lx = jobs[j].ref_len - (m->k - 1);   // the job's k-mers
+        if (lx > SA_PAIR16_MAX_COORD) return SA_EUNSUPPORTED;   // (as the planners refuse such a matrix)
+        for (int64_t i = first[j]; i < first[j + 1]; i++)
+            if (x[i] < 0 || x[i] >= lx || kmer_id[i] < 0 || kmer_id[i] >= m->n_kmers || prob_e7[i] < 0 || prob_e7[i] > (int64_t) SA_PROB_1)
+                return SA_EINVAL;
+    }
+    try {   // (every record is valid: only now is there anything to hold them)
+        recs->resize((size_t) n);
+        V->first.assign(first, first + n_jobs);
+        V->count.resize((size_t) n_jobs);
+    } catch (const std::bad_alloc &) {
+        return SA_ENOMEM;
+    }
+    for (int64_t i = 0; i < n; i++) (*recs)[(size_t) i] = sa_pair16_pack(prob_e7[i], x[i], 0, 0, kmer_id[i]);
+    for (int64_t j = 0; j < n_jobs; j++) V->count[(size_t) j] = first[j + 1] - first[j];
+    V->k = m->k;
+    V->n_alpha = m->n_alpha;
+    return SA_OK;
+}
+
+extern "C" int sa_site_calls_records(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig, const int64_t *first,
+                                     const int32_t *x, const int32_t *kmer_id, const int64_t *prob_e7, int device,
+                                     sa_site_call_t **calls_out, int64_t *n_out, double *kernel_ms_out) {
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (!calls_out || !n_out) return SA_EINVAL;
+    std::vector<sa_pair16_t> recs;
+    SaBatchView V;
+    int rc = calls_records_pack(m, jobs, n_jobs, first, x, kmer_id, prob_e7, &recs, &V);
+    if (rc) return rc;
+    SaAmbigTab *S = nullptr;
+    if ((rc = sa_ambig_build(m, jobs, n_jobs, ambig, m->k - 1, &S)) != SA_OK) return rc;
+    for (int64_t j = 0; j < n_jobs; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+    SaSiteFold F;
+    site_fold_init(S, (size_t) n_jobs, &F);
+    if (F.ns > 0) {   // (as for a batch, a call without sites has nothing to do on the device)
+        V.device = device;
+        if ((rc = sa_device_check(device)) == SA_OK) rc = site_fold_records(S, V, &recs, &F);
+    }
+    if (rc != SA_OK) sa_site_fold_release(&F, true);
+    else rc = site_calls_out(S, F, calls_out, n_out, kernel_ms_out);
+    sa_ambig_free(S);   // (its device copy goes back with it)
+    return rc;
+}
+
 // ---- Per-position marginals (sa_batch_position_calls): CallMethylation.call_methyls (alignmentAnalysisLib.py:159-247) ----
 // A position is an index p of a job's reference that holds an ambiguity letter; every record with x <= p <= x + k - 1 adds its
 // printed posterior to the letter that its path k-mer has at p.  The reference adds floating-point values serially in TSV row
 // order, so the sums are made in that order: the rows of each position are gathered into a bucket, the bucket is put in row
-// order and folded by one lane.
+// order and folded by one lane.  A position whose rows all print 0.000000 has total 0, where the reference divides by zero
+// (alignmentAnalysisLib.py:230-233): it is reported with its rows, every sum and every probability 0.0.
 //
 // Tables (built at sa_batch_create with SA_FLAG_POSITION_CALLS): the sites' tables (ambig_tab_build) with tail 0, i.e. one bit
 // per reference position of every job, set at an ambiguous one; a "site" of that table is a position, its slot below.
@@ -531,7 +620,7 @@ __global__ __launch_bounds__(256) void k_pos_fold(SiteTabs T, const unsigned *__
         double *ps = sum + (size_t) s * (size_t) T.stride, *pp = prob + (size_t) s * (size_t) T.stride;
         for (int l = 0; l < nl; l++) {
             ps[l] = acc[l];
-            pp[l] = acc[l] / total;
+            pp[l] = total != 0.0 ? acc[l] / total : 0.0;   // (every row printed 0.000000: the site fold's rule for a zero sum)
         }
         atomicAdd(&n_kept, 1);
     }
@@ -568,22 +657,21 @@ __global__ __launch_bounds__(64) void k_pos_compact(SiteTabs T, const unsigned *
 
 static SaScratch g_pos_ws;
 
-// the position fold of a finished batch, left on the device (SaPosFold, sa_chain.h)
-int sa_pos_fold_run(sa_batch_t *b, SaPosFold *F) {
-    SaAmbigTab *P = nullptr;
-    int64_t nj64 = 0;
-    int rc = sa_batch_ambig(b, SA_TAB_POSITIONS, &P, &nj64);
-    if (rc) return rc;
-    const size_t nj = F->nj = (size_t) nj64;
+// what the table alone says of a position fold
+static void pos_fold_init(SaAmbigTab *P, size_t nj, SaPosFold *F) {
+    F->nj = nj;
     F->tab = P;
     F->n_kept = 0;
     F->kernel_ms = 0.0;
     F->h_off.assign(nj + 1, 0);
-    if (nj == 0) return SA_OK;
-    const size_t stride = F->stride = (size_t) (P->stride > 0 ? P->stride : 1), ns = (size_t) P->n_sites;
-    SaBatchView V;
-    if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
-    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+    F->stride = (size_t) (P->stride > 0 ? P->stride : 1);
+}
+
+// The position fold of table P (nj > 0 jobs) over the 16-byte records of view V: V.recs on V.device, or -- h_recs -- the host
+// records that go up first.  What sa_pos_fold_run promises of the lock holds here.
+static int pos_fold_records(SaAmbigTab *P, const SaBatchView &V, const std::vector<sa_pair16_t> *h_recs, SaPosFold *F) {
+    int rc = SA_OK;
+    const size_t nj = F->nj, stride = F->stride, ns = (size_t) P->n_sites;
     const sa_pair16_t *d_pairs = (const sa_pair16_t *) V.recs;
     const int device = F->device = V.device;
     F->count = V.count;
@@ -610,6 +698,10 @@ int sa_pos_fold_run(sa_batch_t *b, SaPosFold *F) {
     float kms0 = 0, kms1 = 0;
     SiteTabs T;
     if ((rc = W.rebind(device)) != SA_OK || (rc = sites_upload(P, device)) != SA_OK) return rc;
+    if (h_recs) {
+        if ((rc = fold_records_upload(*h_recs, device, &F->d_recs)) != SA_OK) return rc;
+        d_pairs = (const sa_pair16_t *) F->d_recs;
+    }
     if (g_sa_pool.get(SaPool::DEVICE, (void **) &d, dev_bytes, device) != hipSuccess) { d = nullptr; return SA_ENOMEM; }
     T = sites_tabs(P);
     if (nc) SA_HIP_GOTO_DONE(hipMemcpyAsync(d + o_chunks, chunks.data(), sizeof(SaRecChunk) * nc, hipMemcpyHostToDevice, 0));
@@ -666,30 +758,35 @@ done:
     return rc;
 }
 
+// the position fold of a finished batch, left on the device (SaPosFold, sa_chain.h)
+int sa_pos_fold_run(sa_batch_t *b, SaPosFold *F) {
+    SaAmbigTab *P = nullptr;
+    int64_t nj64 = 0;
+    int rc = sa_batch_ambig(b, SA_TAB_POSITIONS, &P, &nj64);
+    if (rc) return rc;
+    pos_fold_init(P, (size_t) nj64, F);
+    if (nj64 == 0) return SA_OK;
+    SaBatchView V;
+    if ((rc = sa_batch_view(b, &V)) != SA_OK) return rc;
+    if (V.p8 || (V.batch_flags & SA_FLAG_VC_ROWS)) return SA_ESTATE;   // (such records name no k-mer / are not all the rows)
+    return pos_fold_records(P, V, nullptr, F);
+}
+
 void sa_pos_fold_release(SaPosFold *F, bool failed) {
-    if (failed && F->d) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
+    if (failed && (F->d || F->d_recs)) (void) hipStreamSynchronize(0);   // (a failed call may have left work queued on its blocks)
     if (F->d) g_sa_pool.put(SaPool::DEVICE, F->d);
     if (F->d_ent) g_sa_pool.put(SaPool::DEVICE, F->d_ent);
-    F->d = nullptr;
+    if (F->d_recs) g_sa_pool.put(SaPool::DEVICE, F->d_recs);
+    F->d = F->d_recs = nullptr;
     F->d_ent = nullptr;
     if (F->guard.owns_lock()) F->guard.unlock();
 }
 
-extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out,
-                                       int32_t *x_min_out, int32_t *x_max_out, double *kernel_ms_out) {
-    (void) flags;
-    if (!b || !calls_out || !n_out) return SA_EINVAL;
-    SaPosFold F;
-    {   // (the entries of the outputs are cleared before anything can fail, for a batch whose table exists)
-        SaAmbigTab *P0 = nullptr;
-        int64_t nj0 = 0;
-        const int rc0 = sa_batch_ambig(b, SA_TAB_POSITIONS, &P0, &nj0);
-        if (rc0) return rc0;
-        for (int64_t j = 0; j < nj0; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
-        if (kernel_ms_out) *kernel_ms_out = 0.0;
-        if (nj0 == 0) return SA_OK;
-    }
-    int rc = sa_pos_fold_run(b, &F);
+// The second half of the position calls: fold F (of at least one job; fold_rc is what its run returned) copied out into the
+// cleared calls_out / n_out, one entry per job; the fold is released.
+static int pos_calls_out(SaPosFold &F, int fold_rc, sa_position_call_t **calls_out, int64_t *n_out, int32_t *x_min_out, int32_t *x_max_out,
+                         double *kernel_ms_out) {
+    int rc = fold_rc;
     const size_t nj = F.nj, stride = F.stride, n_kept = F.n_kept;
     const SaAmbigTab *P = F.tab;
     const std::vector<long long> &count = F.count, &h_off = F.h_off;
@@ -743,5 +840,45 @@ done:
     sa_pos_fold_release(&F, rc != SA_OK);
     if (rc != SA_OK)
         for (size_t j = 0; j < nj; j++) { free(calls_out[j]); calls_out[j] = nullptr; n_out[j] = 0; }
+    return rc;
+}
+
+extern "C" int sa_batch_position_calls(sa_batch_t *b, unsigned flags, sa_position_call_t **calls_out, int64_t *n_out,
+                                       int32_t *x_min_out, int32_t *x_max_out, double *kernel_ms_out) {
+    (void) flags;
+    if (!b || !calls_out || !n_out) return SA_EINVAL;
+    SaPosFold F;
+    {   // (the entries of the outputs are cleared before anything can fail, for a batch whose table exists)
+        SaAmbigTab *P0 = nullptr;
+        int64_t nj0 = 0;
+        const int rc0 = sa_batch_ambig(b, SA_TAB_POSITIONS, &P0, &nj0);
+        if (rc0) return rc0;
+        for (int64_t j = 0; j < nj0; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+        if (kernel_ms_out) *kernel_ms_out = 0.0;
+        if (nj0 == 0) return SA_OK;
+    }
+    return pos_calls_out(F, sa_pos_fold_run(b, &F), calls_out, n_out, x_min_out, x_max_out, kernel_ms_out);
+}
+
+extern "C" int sa_position_calls_records(const sa_model_t *m, const sa_job_t *jobs, int64_t n_jobs, const char *const *ambig,
+                                         const int64_t *first, const int32_t *x, const int32_t *kmer_id, const int64_t *prob_e7, int device,
+                                         sa_position_call_t **calls_out, int64_t *n_out, int32_t *x_min_out, int32_t *x_max_out,
+                                         double *kernel_ms_out) {
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (!calls_out || !n_out) return SA_EINVAL;
+    std::vector<sa_pair16_t> recs;
+    SaBatchView V;
+    int rc = calls_records_pack(m, jobs, n_jobs, first, x, kmer_id, prob_e7, &recs, &V);
+    if (rc) return rc;
+    SaAmbigTab *P = nullptr;
+    if ((rc = m->k > SA_POS_MAX_K ? SA_EUNSUPPORTED : sa_ambig_build(m, jobs, n_jobs, ambig, 0, &P)) != SA_OK) return rc;
+    for (int64_t j = 0; j < n_jobs; j++) { calls_out[j] = nullptr; n_out[j] = 0; }
+    if (n_jobs > 0 && (rc = sa_device_check(device)) == SA_OK) {
+        SaPosFold F;
+        pos_fold_init(P, (size_t) n_jobs, &F);
+        V.device = device;
+        rc = pos_calls_out(F, pos_fold_records(P, V, &recs, &F), calls_out, n_out, x_min_out, x_max_out, kernel_ms_out);
+    }
+    sa_ambig_free(P);   // (its device copy goes back with it)
     return rc;
 }

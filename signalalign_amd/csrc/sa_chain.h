@@ -58,6 +58,7 @@ struct SaSiteFold {
     std::vector<std::string> letters;              // host, per kind: the sorted letters
     SaScratch *ws = nullptr;
     char *d = nullptr;                             // the fold's device block (g_sa_pool)
+    char *d_recs = nullptr;                        // the records of sa_site_calls_records (g_sa_pool); a batch's stay the batch's
     std::unique_lock<std::mutex> guard;
 };
 int sa_site_fold_run(sa_batch_t *b, SaSiteFold *F);
@@ -84,6 +85,7 @@ struct SaPosFold {
     SaAmbigTab *tab = nullptr;
     char *d = nullptr;                     // the call's device blocks (g_sa_pool)
     unsigned long long *d_ent = nullptr;
+    char *d_recs = nullptr;                // the records of sa_position_calls_records (g_sa_pool); a batch's stay the batch's
     std::unique_lock<std::mutex> guard;
 };
 int sa_pos_fold_run(sa_batch_t *b, SaPosFold *F);

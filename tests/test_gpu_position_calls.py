@@ -12,6 +12,7 @@ import signalalign_amd as sa
 from signalalign_amd import _capi, synth
 
 import sa_cases as cases
+from calls_ref import check_position_calls as check, restate_positions as restate
 
 pytestmark = pytest.mark.gpu
 
@@ -27,58 +28,6 @@ def with_x(jobs, step, phase=0):
             ref[i] = "X"
         out.append(dict(job, ref="".join(ref)))
     return out
-
-
-def restate(pairs, ref, k, alphabet, amb):
-    """call_methyls over one job's rows: every row whose k-mer covers an ambiguous position adds the posterior the TSV prints,
-    read back with float(), to the letter its path k-mer has there -- serially, in row order, from 0; the total runs over the
-    position's sorted letters; each sum is divided by it.  Returns {p: (letters, n_rows, sums, probs)}."""
-    n_alpha = len(alphabet)
-    acc = {}
-    for x, kmer_id, prob_e7 in zip(pairs["x"].tolist(), pairs["kmer_id"].tolist(), pairs["prob_e7"].tolist()):
-        value = None
-        digits = []
-        v = kmer_id
-        for _ in range(k):
-            digits.append(alphabet[v % n_alpha])
-            v //= n_alpha
-        digits.reverse()
-        for d in range(k):
-            c = ref[x + d]
-            if c not in amb:
-                continue
-            if value is None:
-                value = float("%f" % (prob_e7 / 1e7))
-            letters = "".join(sorted(set(amb[c])))
-            entry = acc.setdefault(x + d, [letters, 0, [0] * len(letters)])
-            if digits[d] in letters:
-                entry[1] += 1
-                entry[2][letters.index(digits[d])] += value
-    out = {}
-    for p, (letters, n, sums) in acc.items():
-        if n == 0:
-            continue
-        total = 0
-        for s in sums:
-            total += s
-        out[p] = (letters, n, [float(s) for s in sums], [s / total for s in sums])
-    return out
-
-
-def check(got, exp, pairs):
-    assert got["p"].tolist() == sorted(exp)
-    for i, p in enumerate(got["p"].tolist()):
-        letters, n, sums, probs = exp[p]
-        m = len(letters)
-        assert got["letters"][i] == letters
-        assert int(got["n_rows"][i]) == n, p
-        assert got["sum"][i][:m].tobytes() == np.asarray(sums, dtype=np.float64).tobytes(), (p, got["sum"][i][:m], sums)
-        assert got["prob"][i][:m].tobytes() == np.asarray(probs, dtype=np.float64).tobytes(), (p, got["prob"][i][:m], probs)
-        assert not got["sum"][i][m:].any() and not got["prob"][i][m:].any()
-    if len(pairs):
-        assert got["x_min"] == int(pairs["x"].min()) and got["x_max"] == int(pairs["x"].max())
-    else:
-        assert got["x_min"] == -1 and got["x_max"] == -1
 
 
 def _model(path, nhdp=None):

@@ -11,56 +11,11 @@ import signalalign_amd as sa
 from signalalign_amd import _capi, synth
 
 import sa_cases as cases
+from calls_ref import check_site_calls as check_calls, restate_sites as restate
 
 pytestmark = pytest.mark.gpu
 
 CE = {"X": "CE"}
-
-
-def printed_units(prob_e7):
-    """"%f" of prob_e7 / 1e7 in integers of 1e-6 (the posterior column of the full TSV)"""
-    p = np.asarray(prob_e7, dtype=np.int64)
-    k, rem = p // 10, p % 10
-    out = k + (rem > 5)
-    for i in np.nonzero(rem == 5)[0]:
-        out[i] = int(("%f" % (int(p[i]) / 1e7)).replace(".", ""))
-    return out
-
-
-def restate(pairs, ref, k, alphabet, amb):
-    """get_data (:141-172) over one job's pairs: a site is a k-mer index whose last letter is an ambiguity letter; per letter
-    the printed posteriors of the pairs whose path k-mer ends in it, summed; normalised over the site's letters; sites with a
-    zero total are not reported.  Returns {x: (letters, units, prob)}."""
-    units = printed_units(pairs["prob_e7"])
-    last = np.array([alphabet[i] for i in (pairs["kmer_id"] % len(alphabet))])
-    acc = {}
-    for x, l, u in zip(pairs["x"].tolist(), last.tolist(), units.tolist()):
-        c = ref[x + k - 1]
-        if c not in amb:
-            continue
-        letters = "".join(sorted(set(amb[c])))
-        if x not in acc:
-            acc[x] = (letters, [0] * len(letters))
-        if l in letters:
-            acc[x][1][letters.index(l)] += u
-    out = {}
-    for x, (letters, u) in acc.items():
-        tot = sum(u)
-        if tot > 0:
-            out[x] = (letters, u, [np.float64(v) / np.float64(tot) for v in u])
-    return out
-
-
-def check_calls(got, exp):
-    assert sorted(exp) == got["x"].tolist()
-    assert np.all(np.diff(got["x"]) > 0)
-    for i, x in enumerate(got["x"].tolist()):
-        letters, u, p = exp[x]
-        n = len(letters)
-        assert got["letters"][i] == letters
-        assert got["units"][i][:n].tolist() == u, x
-        assert got["prob"][i][:n].tobytes() == np.asarray(p, dtype=np.float64).tobytes(), x
-        assert not got["units"][i][n:].any() and not got["prob"][i][n:].any()
 
 
 def _model(path, nhdp=None):

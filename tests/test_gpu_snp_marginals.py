@@ -324,6 +324,52 @@ def test_chained_equals_unchained(flags):
     b.close()
 
 
+# read 516 with 40 foreign bases: position 227 of the job of phase 2 is covered by seven rows, each of 1e-7 .. 4e-7 (found by
+# running reads 500 .. 529 once; about one in six has such a position)
+ZERO_READ, ZERO_TAIL = 516, 40
+
+
+def _zero_total_case(read=ZERO_READ, tail=ZERO_TAIL):
+    """one forward read of 300 events whose reference runs on for `tail` foreign bases past its last event, as STEP jobs with X at
+    the contig positions = s (mod STEP), at threshold 1e-7: out in the tail the posteriors fall off, and somewhere every row that
+    covers an X prints 0.000000"""
+    job = cases.synthetic_jobs(cases.MODEL_6MER, 1, 300, read)[0]
+    other = cases.synthetic_jobs(cases.MODEL_6MER, 1, 300, read + 1000)[0]
+    ref_, lo = job["ref"] + other["ref"][:tail], 100
+    jobs = [dict(job, ref=sa.snp_substitute(ref_, lo, False, STEP, s)) for s in range(STEP)]
+    job_map = [dict(contig=0, pos0=lo, pos_sign=1, x0=lo, x_sign=1, strand=0, direction=1, run=0, group=s) for s in range(STEP)]
+    pm = sa.Model.load(cases.MODEL_6MER)
+    b = sa.Batch(pm, sa.default_params(threshold=1e-7), jobs, ambig=sa.default_ambig({"X": "ACGT"}), flags=sa.FLAG_POSITION_CALLS)
+    b.run()
+    return b, job_map, lo
+
+
+def _zero_total_positions(b):
+    """[(job, position, rows)] of the batch's position calls whose sums are all zero"""
+    return [(j, int(p), int(n)) for j, c in enumerate(b.position_calls())
+            for p, n, s in zip(c["p"], c["n_rows"], c["sum"]) if n > 0 and not s.any()]
+
+
+def test_add_batch_adds_a_row_of_zeros_for_a_position_whose_rows_all_print_zero():
+    """k_pos_fold reports such a position with probabilities of 0.0 (the reference divides by zero there); k_mg_batch_rows copies
+    them into a row: the site gains depth and nothing else, as add_sites fed the same zeros"""
+    b, job_map, lo = _zero_total_case()
+    zero = _zero_total_positions(b)
+    assert (2, 227, 7) in zero, "the batch no longer holds the position whose rows all print zero"
+    calls = b.position_calls()
+    assert not any(np.isnan(c["prob"]).any() for c in calls)
+    exp, n_rows, _ = _unchained(b, job_map)
+    got, _ = _chained(b, job_map)
+    assert n_rows > 50 and got.tobytes() == exp.tobytes()
+    for j, p, n in zero:
+        site = got[(got["contig"] == 0) & (got["pos"] == lo + p)]
+        # (one job per phase: no other job has an X at this contig position)
+        assert len(site) == 1 and site["depth"][0] == 1
+        assert not site["fwd"].any() and not site["bwd"].any() and not site["prob"].any() and site["called"][0] == b"N"
+        assert calls[j]["prob"][calls[j]["p"].tolist().index(p)].tobytes() == np.zeros(8).tobytes()
+    b.close()
+
+
 def test_chained_over_several_forward_passes(monkeypatch):
     jobs, job_map = _batch_case()
     monkeypatch.setenv("SA_F_BUDGET_CELLPATHS", "400000")
